@@ -8,10 +8,15 @@ are already in HBM: frame formation (LLRs from bits + QBER) -> 50 iterations -> 
 decisions (+ for N > 1 the RCCL gather of decoded blocks to rank 0).
 
 value = K bits of every successfully reconciled frame / wall time (whole job, all ranks), Mbit/s.
-The headline run executes all 50 iterations for every frame (enable_syndrome = 0: no work skipped);
-the AFF3CT-default early-exit mode is reported beside it under "early_exit".
+The headline run executes all 50 iterations for every frame (enable_syndrome = 0: no work skipped).
+
+A plain run sets up, warms up, times the --steps steps of the headline and prints the result line; the
+other legs (AFF3CT-default early exit, layered schedule, fp16 / int8 / SPA variants, BASELINE configs 3
+and 5, the deep FER points, the CPU baseline, the copy-rate probe) run only with --full.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
   python bench.py --gpus 1 --steps 5 --warmup 1
+  python bench.py --gpus 1 --steps 5 --warmup 1 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 """
@@ -112,6 +117,33 @@ def cpu_baseline(code, frames_llr_fn, rule, param, n_ite, K):
                 sample="%d frames of the same workload (flooding %s %.2f, %d iterations fixed), %.1f s wall" % (n, rule, param, n_ite, dt)), r, llr
 
 
+def dump_outputs(q, directory, N, words, cw, it, ok, seed=12345, max_sample_bytes=48 << 20):
+    """The headline's last timed step as a caller of the hot path receives it, as .npy files in float32 (about 32 MB at the default
+    workload): the hard decisions of a fixed, seeded sample of frames bit by bit (decoded_bits [S, N], their frame numbers in
+    decoded_frame_index, float64), and per frame of the whole batch the count of ones in the decoded word, the iterations executed,
+    the syndrome verdict and whether the word is Alice's codeword with a zero syndrome (what `value` counts)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    F = words.shape[0]
+    w = words.cpu().numpy().view(np.uint32).copy()
+    if N % 32:
+        w[:, -1] &= np.uint32((0xFFFFFFFF << (32 - N % 32)) & 0xFFFFFFFF)      # MSB-first: bits past N are not part of the word
+    S = max(1, min(128, F, max_sample_bytes // (4 * N)))
+    idx = np.sort(np.random.default_rng(seed).choice(F, S, replace=False))
+    good = ((words == cw).all(dim=1)) & (ok == 1)
+    arrays = {
+        "decoded_bits": q.unpack_bits(w[idx], N).astype(np.float32),
+        "decoded_frame_index": idx.astype(np.float64),
+        "decoded_ones": np.bitwise_count(w).sum(axis=1, dtype=np.int64).astype(np.float32),
+        "frame_iterations": it.cpu().numpy().astype(np.float32),
+        "frame_syndrome_ok": ok.cpu().numpy().astype(np.float32),
+        "frame_reconciled": good.cpu().numpy().astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log("outputs of the last timed step written to %s (%s)" % (directory, ", ".join("%s %s" % (k, list(v.shape)) for k, v in arrays.items())))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -139,7 +171,15 @@ def main():
     ap.add_argument("--fer-frames", type=int, default=1 << 20, help="frames of the deep FER point at the headline QBER")
     ap.add_argument("--peg", type=int, default=2, help="PEG depth of the second code the FER / config-3 legs report beside the seeded shuffle (0 = skip)")
     ap.add_argument("--msg-dtype", default="f32", choices=["f32", "f16", "i8"], help="experiment: message storage of the main legs (the contract run uses f32)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (early exit, variants, configs 3 and 5, deep FER, CPU baseline, "
+                    "copy probe); the --no-* options skip legs of a full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the headline's last timed step (decoded words, per-frame status) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:      # a plain run measures the headline and nothing else
+        args.no_early = args.no_layered = args.no_fp16 = args.no_int8 = args.no_spa = args.no_cpu = True
+        args.no_config3 = args.no_config5 = args.no_fer_deep = True
 
     import numpy as np
     import torch
@@ -244,6 +284,16 @@ def main():
     kstats = {s["name"]: s for s in dec.profile_read()}
     dec.profile(False)
     good, it_sum, n_all = verdicts(dec)
+    if args.dump_outputs:
+        it_h, ok_h = dec.fetch_status()
+        if world > 1:      # rank 0 writes the whole job's frames: decoded blocks and per-frame status gathered like the timed step's blocks
+            words_h, cw_h = shard.gather_blocks(out, total_frames, dst=0), shard.gather_blocks(cw, total_frames, dst=0)
+            it_h, ok_h = shard.gather_blocks(it_h, total_frames, dst=0), shard.gather_blocks(ok_h, total_frames, dst=0)
+        else:
+            words_h, cw_h = out, cw
+        if rank == 0:
+            dump_outputs(q, args.dump_outputs, N, words_h, cw_h, it_h, ok_h)
+        barrier()
     out_headline = out.clone()            # the later legs reuse `out`; the CPU cross-check below is about THIS leg
     value = good * K * args.steps / dt / 1e6
     fer = 1.0 - good / n_all
@@ -617,7 +667,7 @@ def main():
 
     # what this device copies at (read once + written once, non-temporal) in the decoder's access shape: the measured ceiling beside the data sheet's
     probe = None
-    if rank == 0:
+    if rank == 0 and args.full:
         probe = {"rows_256B_GBs": q.copy_probe(4 << 30, 6, False, local_rank), "wide_16B_per_lane_GBs": q.copy_probe(4 << 30, 6, True, local_rank),
                  "what": "hand-written copy kernels of libqldpc (qldpc_copy_probe), 4 GiB read + 4 GiB written per launch, bytes read + bytes written per second"}
         probe["frac_of_copy"] = achieved / max(probe["rows_256B_GBs"], probe["wide_16B_per_lane_GBs"])

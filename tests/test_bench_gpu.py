@@ -1,4 +1,4 @@
-"""bench.py keeps its contract: one JSON line with the driver's keys plus `roofline` and `cpu_baseline` (small workload here)."""
+"""bench.py keeps its contract: one JSON line with the driver's keys plus `roofline` and, with --full, `cpu_baseline` and the other legs."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "256", "--n", "8192", "--k", "6554",
-                        "--n-ite", "12", "--fer-frames", "8192"], capture_output=True, text=True, timeout=600)
+                        "--n-ite", "12", "--fer-frames", "8192", "--full"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -37,7 +37,7 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
 def test_default_bench_line_covers_configs_2_3_5_and_every_moved_frac_is_at_most_one():
     """one default run puts BASELINE configs 2 (the line itself), 3 and 5 in front of the driver, each with its own roofline,
     moved bytes beside algorithmic bytes, and no fraction above 1 (round 1's layered mode summed one pass three times)."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu"], capture_output=True, text=True, timeout=1500)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu", "--full"], capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
     assert "configs[1]" in d["config"]["workload"] and d["config"]["frames_per_gpu"] == 4096
@@ -76,3 +76,36 @@ def test_default_bench_line_covers_configs_2_3_5_and_every_moved_frac_is_at_most
     assert sp["fixed"]["fer"] == 0.0 and sp["early_exit"]["fer"] == 0.0 and sp["early_exit"]["avg_iterations"] < e["avg_iterations"] and sp["fixed"]["value"] > 0.6 * d["value"]
     fracs += [sp["fixed"]["cn_update_frac"]]
     assert all(0.0 < f <= 1.0 for f in fracs), fracs
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_the_headline_only_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain run times exactly --steps steps of the headline and nothing else; --dump-outputs writes the last timed step (float32 /
+    float64 .npy, at most 64 MB), and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / ("run%d" % run)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "256", "--n", "8192", "--k", "6554",
+                            "--n-ite", "12", "--dump-outputs", str(d_out)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["metric"] == "reconciled_key_Mbit_s" and d["unit"] == "Mbit/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["fer"] < 0.5
+        assert d["roofline"]["launches"] % 3 == 0 and d["iterations_executed"] == 12 and d["roofline"]["copy_probe"] is None      # no probe run
+        for leg in ("cpu_baseline", "early_exit", "layered_schedule", "fp16_messages", "int8_messages", "spa_rule", "fer_deep",
+                    "config3_multirate_stream", "config5_layered_1e6"):
+            assert d[leg] is None, leg
+        files = sorted(f.name for f in d_out.iterdir())
+        assert files == sorted(n + ".npy" for n in ("decoded_bits", "decoded_frame_index", "decoded_ones", "frame_iterations", "frame_syndrome_ok", "frame_reconciled"))
+        assert sum(f.stat().st_size for f in d_out.iterdir()) <= 64 << 20
+        a = {f[:-4]: np.load(d_out / f) for f in files}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+        assert a["decoded_bits"].shape == (128, 8192) and set(np.unique(a["decoded_bits"])) <= {0.0, 1.0}
+        assert a["decoded_ones"].shape == a["frame_reconciled"].shape == (256,)
+        assert (a["frame_iterations"] <= 12).all() and abs(a["frame_reconciled"].mean() - (1.0 - d["fer"])) < 1e-9
+        dumps.append(a)
+    for k in dumps[0]:
+        assert (dumps[0][k] == dumps[1][k]).all(), k

@@ -448,12 +448,19 @@ def test_device_choice_function_round_robin(tmp_path):
     assert subprocess.run([str(exe)], capture_output=True, text=True).stdout.strip() == "ok"
 
 
-def test_test_hooks_are_not_in_the_maintainer_build():
-    """VERDICT r2 weak #8: the fault-injection letters of -L exist only under -DLDPC_TEST_HOOKS."""
+def test_test_hooks_are_not_in_the_maintainer_build(tmp_path):
+    """the fault-injection letters of -L exist only under -DLDPC_TEST_HOOKS.  Preprocessed against the reference's
+    headers where they lie, else against empty stand-ins of the same names: only the LDPC_TEST_HOOKS sections of the plugin matter here."""
     ref = "/root/reference/errorcorrection"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present on this machine")
     src = os.path.join(ROOT, "qcrypto-ldpc_amd", "host", "ldpc_reconcile.c")
+    if not os.path.isdir(ref):
+        ref = str(tmp_path)
+        ours = (os.path.dirname(src), os.path.join(ROOT, "include"))
+        for f in (src, os.path.join(ours[0], "ldpc_reconcile.h")):
+            for inc in re.findall(r'^#include "([^"]+)"', open(f).read(), re.M):
+                if not any(os.path.exists(os.path.join(d, inc)) for d in ours):
+                    (tmp_path / inc).parent.mkdir(parents=True, exist_ok=True)
+                    (tmp_path / inc).touch()
     out = {}
     for name, flags in (("plain", []), ("hooks", ["-DLDPC_TEST_HOOKS"])):
         r = subprocess.run(["gcc", "-std=gnu11", "-E", "-P", "-I" + ref, "-I" + os.path.join(ROOT, "include")] + flags + [src], capture_output=True, text=True)

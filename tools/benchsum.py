@@ -15,7 +15,7 @@ for spec in sys.argv[1:]:
             env[k] = v
         else:
             args.append(e)
-    p = subprocess.run([sys.executable, ROOT + "/bench.py", "--no-cpu"] + args, capture_output=True, text=True, env=env)
+    p = subprocess.run([sys.executable, ROOT + "/bench.py", "--full", "--no-cpu"] + args, capture_output=True, text=True, env=env)
     try:
         d = json.loads(p.stdout.strip().splitlines()[-1])
         r = d["roofline"]
