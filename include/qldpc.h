@@ -71,11 +71,17 @@ typedef enum qldpc_rule {
     QLDPC_RULE_AMS_MINSTAR = 7    /* Update_rule_AMS<min_star>                       */
 } qldpc_rule;
 
-/* Decoder_LDPC_BP_{flooding,horizontal_layered}; VAR/main.cpp (alist-v1.0.1):203-237 */
+/* Decoder_LDPC_BP_{flooding,horizontal_layered,vertical_layered}; VAR/main.cpp (alist-v1.0.1):203-237, 240-256 */
 typedef enum qldpc_schedule {
     QLDPC_SCHED_FLOODING = 0,
-    QLDPC_SCHED_HLAYERED = 1      /* horizontal layered, checks visited in the code's layer order */
+    QLDPC_SCHED_HLAYERED = 1,     /* horizontal layered, checks visited in the code's layer order */
 #define QLDPC_RECON_SCHED_AUTO 2  /* qldpc_recon_cfg.schedule only: chosen by the batch size of the session's decoders */
+    QLDPC_SCHED_VLAYERED = 3      /* vertical layered (VAR/main.cpp (alist-v1.0.1):240-256), VNs visited in the code's vlayer order: per (VN, check) pair the
+                                     horizontal recursion with only the VN's own message and posterior written.  FRAMES engine (auto resolves to it), fp32
+                                     messages, all rules, freeze_messages 0 / 1, frames_per_lane 0 / 1 / 2 / 4, syndrome form, erasures; engine = EDGES,
+                                     msg_dtype 1 / 2, layer_chain = 1 and compact = 1 are refused with QLDPC_EUNSUPPORTED, and sessions (qldpc_recon_cfg)
+                                     refuse it with QLDPC_EINVAL.  AFF3CT's source is not in the reference tree: parity is unpinned against AFF3CT,
+                                     bit-exact means against the project's CPU reference of the recursion (tests/vlayered_ref.py) */
 } qldpc_schedule;
 
 /*
@@ -155,6 +161,10 @@ int qldpc_code_export_edges(const qldpc_code *code, int *var, int *chk);
 /* Number of conflict-free layers of the horizontal-layered order, and that order (M entries). */
 int qldpc_code_layer_count(const qldpc_code *code);
 int qldpc_code_layer_order(const qldpc_code *code, int *check_order, int *layer_ptr /* layers+1 */);
+/* The same for the vertical-layered order: classes of VNs that share no check (N entries; built on first use).  Both return 1 when the
+ * classes in order are the sequential sweep in index order, 0 when the sweep runs in the exported (coloured) order. */
+int qldpc_code_vlayer_count(const qldpc_code *code);
+int qldpc_code_vlayer_order(const qldpc_code *code, int *vn_order, int *vlayer_ptr /* classes+1 */);
 /* H x over GF(2) for one host word of 0/1 ints; returns the syndrome weight (>= 0) or a status. */
 int qldpc_code_syndrome_host(const qldpc_code *code, const int *x, int *s);
 

@@ -49,7 +49,7 @@ _preload_torch_hip_runtime()
 _L = C.CDLL(LIB_PATH)
 
 RULES = {"MS": 0, "OMS": 1, "NMS": 2, "SPA": 3, "LSPA": 4, "AMS_MIN": 5, "AMS_MINSTAR_L2": 6, "AMS_MINSTAR": 7}
-SCHEDULES = {"flooding": 0, "hlayered": 1}
+SCHEDULES = {"flooding": 0, "hlayered": 1, "vlayered": 3}      # 2 is QLDPC_RECON_SCHED_AUTO (sessions only)
 VN_CHANNEL, VN_PINNED, VN_PUNCTURED = 0, 1, 2
 CONFIRMED_BIT_LLR = 23.025850929840455
 
@@ -91,11 +91,12 @@ _sig("qldpc_code_from_edges", C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.P
 _sig("qldpc_code_ira", C.c_int, [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_uint64, C.POINTER(_vp)])
 _sig("qldpc_code_ira_peg", C.c_int, [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_vp)])
 _sig("qldpc_code_free", None, [_vp])
-for _n in ("n", "m", "e", "max_cn_degree", "max_vn_degree", "is_ira", "layer_count"):
+for _n in ("n", "m", "e", "max_cn_degree", "max_vn_degree", "is_ira", "layer_count", "vlayer_count"):
     _sig("qldpc_code_" + _n, C.c_int, [_vp])
 _sig("qldpc_code_qc_peg", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_char_p, C.POINTER(_vp), _ip])
 _sig("qldpc_code_export_edges", C.c_int, [_vp, _ip, _ip])
 _sig("qldpc_code_layer_order", C.c_int, [_vp, _ip, _ip])
+_sig("qldpc_code_vlayer_order", C.c_int, [_vp, _ip, _ip])
 _sig("qldpc_code_syndrome_host", C.c_int, [_vp, _ip, _ip])
 _sig("qldpc_decoder_cfg_default", None, [C.POINTER(DecoderCfg)])
 _sig("qldpc_decoder_create", C.c_int, [_vp, C.c_int, _ip, C.POINTER(DecoderCfg), C.POINTER(_vp)])
@@ -261,6 +262,19 @@ class Code:
         nat = _chk(_L.qldpc_code_layer_order(self._h, order.ctypes.data_as(_ip), ptr.ctypes.data_as(_ip)), "Code.layer_order")
         return order, ptr, bool(nat)
 
+    @property
+    def n_vlayers(self):
+        """classes of the vertical-layered sweep (the order is built on first use)"""
+        return _chk(_L.qldpc_code_vlayer_count(self._h), "Code.n_vlayers")
+
+    def vlayer_order(self):
+        """(vn_order[N], vlayer_ptr[n_vlayers+1], natural) of the vertical-layered sweep: VNs of one class share no check;
+        natural = the classes in order are the sequential v = 0..N-1 sweep, else the sweep runs in vn_order."""
+        order = np.empty(self.N, np.int32)
+        ptr = np.empty(self.n_vlayers + 1, np.int32)
+        nat = _chk(_L.qldpc_code_vlayer_order(self._h, order.ctypes.data_as(_ip), ptr.ctypes.data_as(_ip)), "Code.vlayer_order")
+        return order, ptr, bool(nat)
+
     def syndrome(self, x):
         x = _np_i32(x)
         s = np.empty(self.M, np.int32)
@@ -280,7 +294,7 @@ def _torch():
 
 
 class Decoder:
-    """module::Decoder_LDPC_BP_{flooding,horizontal_layered}<B,Q,Rule> as a batched HIP decoder.
+    """module::Decoder_LDPC_BP_{flooding,horizontal_layered,vertical_layered}<B,Q,Rule> as a batched HIP decoder.
 
     Decoder(code, K, n_ite, info_bits_pos, rule=("NMS", 0.75), enable_syndrome, syndrome_depth, n_frames)
     mirrors the AFF3CT ctor (VAR/main.cpp (alist-v1.0.1):203-237).

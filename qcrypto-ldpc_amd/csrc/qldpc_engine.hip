@@ -1,7 +1,7 @@
 /*
  * qldpc_engine.hip -- decoder object, launch sequencing and the C ABI of the batched BP decoder.
  *
- * Mirrors module::Decoder_LDPC_BP_flooding / _horizontal_layered as the reference harness drives
+ * Mirrors module::Decoder_LDPC_BP_flooding / _horizontal_layered / _vertical_layered as the reference harness drives
  * them (BS/src/main.cpp:193,365,389; VAR/main.cpp (alist-v1.0.1):179-256,438): create(K, N, n_ite,
  * H, info_bits_pos, rule, enable_syndrome, syndrome_depth, n_frames), decode_siho(Y_N, V_K), reset().
  * Everything heavy is a HIP kernel from qldpc_kernels.h; there is no CPU fallback.
@@ -175,6 +175,8 @@ extern "C" void qldpc_decoder_free(qldpc_decoder *d)
     for (auto &b : d->cn_buckets) (void)hipFree(b.d_list);
     for (auto &b : d->vn_buckets) (void)hipFree(b.d_list);
     for (auto &l : d->layer_buckets) for (auto &b : l) { (void)hipFree(b.d_list); (void)hipFree(b.d_rec); }
+    for (auto &b : d->vlayer_classes) (void)hipFree(b.d_list);
+    (void)hipFree(d->d_vn_chk);
     (void)hipFree(d->d_cn_ptr); (void)hipFree(d->d_cn_tr); (void)hipFree(d->d_cn_var); (void)hipFree(d->d_vn_ptr); (void)hipFree(d->d_info_pos); (void)hipFree(d->d_cn_var_t); (void)hipFree(d->d_vn_tr);
     (void)hipFree(d->d_chain_order); (void)hipFree(d->d_chain_dep); (void)hipFree(d->d_chain_ver); (void)hipFree(d->d_chain_ctl);
     (void)hipFree(d->d_llr); (void)hipFree(d->d_llr8); (void)hipFree(d->d_ybits); (void)hipFree(d->d_ebits); (void)hipFree(d->d_fmag); (void)hipFree(d->d_fnch); (void)hipFree(d->d_vcls); (void)hipFree(d->d_a); (void)hipFree(d->d_b); (void)hipFree(d->d_post);
@@ -320,6 +322,17 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
     if (cfg->schedule == QLDPC_SCHED_FLOODING) {
         if ((rc = make_buckets(d, code->cn_ptr, nullptr, d->M, CN_CAPS, 4, d->cn_buckets))) return rc;
         if ((rc = make_buckets(d, code->vn_ptr, nullptr, d->N, VN_CAPS, 2, d->vn_buckets))) return rc;
+    } else if (cfg->schedule == QLDPC_SCHED_VLAYERED) {
+        /* one VN list per class of the code's vlayer order (built on first use); the kernel walks list -> vn_ptr -> {vn_chk, vn_tr} -> cn_ptr -> cn_var */
+        const int n_cls = qldpc_code_vlayer_count(code);
+        if (n_cls < 0) return n_cls;
+        for (int l = 0; l < n_cls; l++)
+            if ((rc = make_buckets(d, code->vn_ptr, code->vlayer_order + code->vlayer_ptr[l], code->vlayer_ptr[l + 1] - code->vlayer_ptr[l], nullptr, 0, d->vlayer_classes))) return rc;
+        if ((rc = dev_alloc(d, &d->d_vn_chk, (size_t)d->E))) return rc;
+        HIPCHK(hipMemcpy(d->d_vn_chk, code->vn_chk, sizeof(int) * (size_t)d->E, hipMemcpyHostToDevice));
+        double dc2 = 0.0;
+        for (int c = 0; c < d->M; c++) { const double dc = code->cn_ptr[c + 1] - code->cn_ptr[c]; dc2 += dc * dc; }
+        d->vl_rows = 2.0 * dc2 + 2.0 * d->N;
     } else {
         d->n_layers = code->n_layers;
         d->layer_buckets.resize((size_t)code->n_layers);
@@ -462,12 +475,17 @@ extern "C" int qldpc_decoder_create(const qldpc_code *code, int K, const int *in
     if (cfg->n_ite <= 0) { qldpc_set_error("decoder_create: n_ite=%d", cfg->n_ite); return QLDPC_EINVAL; }
     if (cfg->max_frames <= 0) { qldpc_set_error("decoder_create: max_frames=%d", cfg->max_frames); return QLDPC_EINVAL; }
     if (cfg->rule < QLDPC_RULE_MS || cfg->rule > QLDPC_RULE_AMS_MINSTAR) { qldpc_set_error("decoder_create: rule=%d", cfg->rule); return QLDPC_EINVAL; }
-    if (cfg->schedule != QLDPC_SCHED_FLOODING && cfg->schedule != QLDPC_SCHED_HLAYERED) { qldpc_set_error("decoder_create: schedule=%d", cfg->schedule); return QLDPC_EINVAL; }
+    if (cfg->schedule != QLDPC_SCHED_FLOODING && cfg->schedule != QLDPC_SCHED_HLAYERED && cfg->schedule != QLDPC_SCHED_VLAYERED) { qldpc_set_error("decoder_create: schedule=%d", cfg->schedule); return QLDPC_EINVAL; }
     if (cfg->enable_syndrome && cfg->syndrome_depth < 1) { qldpc_set_error("decoder_create: syndrome_depth=%d", cfg->syndrome_depth); return QLDPC_EINVAL; }
     if (cfg->frames_per_lane != 0 && cfg->frames_per_lane != 1 && cfg->frames_per_lane != 2 && cfg->frames_per_lane != 4) { qldpc_set_error("decoder_create: frames_per_lane=%d", cfg->frames_per_lane); return QLDPC_EINVAL; }
     if (cfg->msg_dtype < 0 || cfg->msg_dtype > 2) { qldpc_set_error("decoder_create: msg_dtype=%d", cfg->msg_dtype); return QLDPC_EINVAL; }
     if (cfg->compact < 0 || cfg->compact > 2 || cfg->layer_chain < 0 || cfg->layer_chain > 2 || cfg->reserved[0]) { qldpc_set_error("decoder_create: compact=%d, layer_chain=%d (0 auto, 1 on, 2 off), reserved words must be zero", cfg->compact, cfg->layer_chain); return QLDPC_EINVAL; }
     if (!(cfg->quant_scale >= 0.0f) || cfg->quant_scale > 64.0f) { qldpc_set_error("decoder_create: quant_scale=%g", (double)cfg->quant_scale); return QLDPC_EINVAL; }
+    if (cfg->schedule == QLDPC_SCHED_VLAYERED && (cfg->engine == QLDPC_ENGINE_EDGES || cfg->msg_dtype != 0 || cfg->layer_chain == 1 || cfg->compact == 1)) {
+        qldpc_set_error("the vertical-layered schedule runs on the FRAMES engine with fp32 messages, one launch per class and no compaction "
+                        "(have engine=%d, msg_dtype=%d, layer_chain=%d, compact=%d)", cfg->engine, cfg->msg_dtype, cfg->layer_chain, cfg->compact);
+        return QLDPC_EUNSUPPORTED;
+    }
     qldpc_decoder *d = new (std::nothrow) qldpc_decoder();
     if (!d) return QLDPC_ENOMEM;
     int rc = create_impl(code, K, info_bits_pos, cfg, d);
@@ -811,6 +829,13 @@ static int run_flooding(qldpc_decoder *d)
 
 static int bx_of(const qldpc_decoder *d) { return std::max(1, std::min((d->N + QK_WAVES - 1) / QK_WAVES, 8192 / std::max(1, d->G))); }
 
+/* for the length of a layered run, d->G = the groups that hold frames (run_layered says why) */
+struct live_groups {
+    qldpc_decoder *d; int saved;
+    explicit live_groups(qldpc_decoder *d_) : d(d_), saved(d_->G) { const int gl = std::max(1, (d->n_frames + d->FG - 1) / d->FG); if (gl < d->G) d->G = gl; }
+    ~live_groups() { d->G = saved; }
+};
+
 template <int V>
 static int run_layered(qldpc_decoder *d)
 {
@@ -820,11 +845,7 @@ static int run_layered(qldpc_decoder *d)
      * groups that hold frames only.  The layered schedule has no generations: d->G only sizes grids, copies and the status pass, the arrays are
      * strided per group.  Empty groups were skipped inside the kernels before, but their workgroups were still dispatched -- 23 small launches per
      * sweep each carrying up to 8 x the workgroups: the config-3 stream on session decoders sized for 512 blocks 15.7 -> 13.65 ms (sized for 256: 13.9 -> 13.5). */
-    struct live_groups {
-        qldpc_decoder *d; int saved;
-        explicit live_groups(qldpc_decoder *d_) : d(d_), saved(d_->G) { const int gl = std::max(1, (d->n_frames + d->FG - 1) / d->FG); if (gl < d->G) d->G = gl; }
-        ~live_groups() { d->G = saved; }
-    } live_guard(d);
+    live_groups live_guard(d);
     const size_t G = (size_t)d->G, FG = (size_t)d->FG;
     const size_t cell = d->msg_i8 ? 1 : sizeof(float);
     HIPCHK(hipMemcpyAsync(d->d_a, d->msg_i8 ? (const void *)d->d_llr8 : (const void *)d->d_llr, G * d->N * FG * cell, hipMemcpyDeviceToDevice, d->stream));   /* var_nodes = Y_N */
@@ -895,6 +916,50 @@ static int run_layered(qldpc_decoder *d)
     return QLDPC_OK;
 }
 
+/*
+ * Vertical-layered run (qldpc_kernels_vl.h): state and per-sweep chain as in run_layered -- var_nodes = Y_N from whatever load formed the frames,
+ * one launch per class, then ballots -> syndrome -> status after EVERY sweep, the last included.  The messages are cleared at run start: sweep 0
+ * already reads messages written earlier in the same sweep, so the horizontal sweep's "take them as zero" shortcut does not hold.
+ */
+template <int V>
+static int run_vlayered(qldpc_decoder *d)
+{
+    int rc;
+    const int n_ite = d->cfg.n_ite;
+    live_groups live_guard(d);      /* sweeps run over the groups that hold frames only (see run_layered) */
+    const size_t G = (size_t)d->G, FG = (size_t)d->FG;
+    HIPCHK(hipMemcpyAsync(d->d_a, d->d_llr, G * d->N * FG * sizeof(float), hipMemcpyDeviceToDevice, d->stream));   /* var_nodes = Y_N */
+    HIPCHK(hipMemsetAsync(d->d_b, 0, G * d->E * FG * sizeof(float), d->stream));                                   /* messages = 0 */
+    auto ballots = [&]() {
+        hipLaunchKernelGGL((qk_post_ballots<V>), dim3((unsigned)std::max(1, std::min((d->N + 32 * QK_WAVES - 1) / (32 * QK_WAVES), 8192 / std::max(1, d->G))), (unsigned)d->G), dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_sgn, d->d_hard, d->N, d->d_done);
+    };
+    int ite = 0;
+    for (; ite < n_ite; ite++) {
+        {
+            prof_scope ps(d, KS_VLAYER, bytes_layer(d), d->vl_rows * 4.0 * live_frames(d));
+            for (auto &b : d->vlayer_classes) { qldpc_launch_vlayer<V>(d, b); LAUNCHCHK(); }
+        }
+        if (d->cfg.enable_syndrome) {
+            {
+                prof_scope ps(d, KS_SYND, 0.0, (double)d->N * 4.0 * d->n_frames);
+                ballots();
+                LAUNCHCHK();
+            }
+            if ((rc = synd_pass<V>(d, d->d_sgn, 1))) return rc;
+            if ((rc = status_pass<V>(d, ite + 1))) return rc;
+            if (d->poll_every > 0 && ((ite + 1) % d->poll_every) == 0) {
+                int active = 1;
+                if ((rc = poll_active(d, &active))) return rc;
+                if (active == 0) { ite++; break; }
+            }
+        }
+    }
+    d->last_iters = std::min(ite, n_ite);
+    ballots();
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
 template <int V>
 static int run_v(qldpc_decoder *d)
 {
@@ -907,7 +972,7 @@ static int run_v(qldpc_decoder *d)
         hipLaunchKernelGGL((qk_status_init<V>), dim3((unsigned)d->G), dim3(64), 0, d->stream, d->d_unsat, d->d_done, d->d_depth, d->d_iters, d->n_frames, d->cfg.n_ite, d->d_work, d->d_active);
         LAUNCHCHK();
     }
-    int rc = d->cfg.schedule == QLDPC_SCHED_FLOODING ? run_flooding<V>(d) : run_layered<V>(d);
+    int rc = d->cfg.schedule == QLDPC_SCHED_FLOODING ? run_flooding<V>(d) : (d->cfg.schedule == QLDPC_SCHED_VLAYERED ? run_vlayered<V>(d) : run_layered<V>(d));
     if (rc) return rc;
     /* success flag: syndrome of the hard decision, in every generation (a frame's result lives where it converged) */
     const int last = d->cur_gen;

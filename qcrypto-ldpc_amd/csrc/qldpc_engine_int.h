@@ -26,8 +26,8 @@
         }                                                                                               \
     } while (0)
 
-enum { KS_CN = 0, KS_VN, KS_LAYER, KS_SYND, KS_STATUS, KS_LOAD, KS_FETCH, KS_COUNT };
-static const char *const ks_names[KS_COUNT] = {"cn_update", "vn_update", "layer_update", "syndrome", "status", "load", "fetch"};
+enum { KS_CN = 0, KS_VN, KS_LAYER, KS_SYND, KS_STATUS, KS_LOAD, KS_FETCH, KS_VLAYER, KS_COUNT };
+static const char *const ks_names[KS_COUNT] = {"cn_update", "vn_update", "layer_update", "syndrome", "status", "load", "fetch", "vn_vlayer"};
 
 struct prof_rec { int kind; double bytes, moved; hipEvent_t a, b; };
 
@@ -64,6 +64,11 @@ struct qldpc_decoder {
     std::vector<bucket> cn_buckets, vn_buckets;
     std::vector<std::vector<bucket>> layer_buckets;   /* per layer */
     int n_layers;
+    /* vertical-layered schedule (qldpc_kernels_vl.h): one list per class of check-disjoint VNs, the check of every VN-major slot, and the rows a
+     * sweep moves per frame (it recomputes a check's fold for each of its VNs: 2 sum dc^2 - E + N read, E + N written) */
+    std::vector<bucket> vlayer_classes;
+    int *d_vn_chk;
+    double vl_rows;
     /* one launch per sweep for small batches (qldpc_kernels_chain.h): execution order, per-edge {dv, rank}, per-VN version counters, ticket / fault words */
     int layer_cst;      /* layered min-sum keeps {cst1, cst2} per check and two ballot words per edge instead of dc messages (qldpc_kernels_cst.h) */
     int chain, chain_blocks, chain_lds; int *d_chain_order, *d_chain_dep, *d_chain_ver, *d_chain_ctl; int chain_sweeps;
@@ -165,12 +170,14 @@ static inline int want_ballots(const qldpc_decoder *d, int mode)
 /* kernel-launch dispatchers (qldpc_launch.hip); `first`: the check pass of iteration 0 in coded-LLR mode */
 template <int V> void qldpc_launch_cn(qldpc_decoder *d, const bucket &b, bool first);
 template <int V> void qldpc_launch_layer(qldpc_decoder *d, const bucket &b);
+template <int V> void qldpc_launch_vlayer(qldpc_decoder *d, const bucket &b);
 void qldpc_launch_layer_chain(qldpc_decoder *d, int sweep);      /* V = 1 only */
 int qldpc_chain_resident_blocks(qldpc_decoder *d);
 template <int V, int MODE> void qldpc_launch_vn(qldpc_decoder *d, const bucket &b, float *post_out);
 #define QLDPC_DECLARE_LAUNCH(V)                                                                   \
     extern template void qldpc_launch_cn<V>(qldpc_decoder *, const bucket &, bool);                \
     extern template void qldpc_launch_layer<V>(qldpc_decoder *, const bucket &);                   \
+    extern template void qldpc_launch_vlayer<V>(qldpc_decoder *, const bucket &);                  \
     extern template void qldpc_launch_vn<V, QK_VN_FIRST>(qldpc_decoder *, const bucket &, float *); \
     extern template void qldpc_launch_vn<V, QK_VN_NORMAL>(qldpc_decoder *, const bucket &, float *); \
     extern template void qldpc_launch_vn<V, QK_VN_POST>(qldpc_decoder *, const bucket &, float *);

@@ -90,6 +90,7 @@ void qldpc_code_free(qldpc_code *c)
     if (!c) return;
     free(c->cn_ptr); free(c->cn_var); free(c->vn_ptr); free(c->vn_chk); free(c->transpose);
     free(c->layer_ptr); free(c->layer_order);
+    free(c->vlayer_ptr); free(c->vlayer_order);
     free(c);
 }
 
@@ -233,7 +234,8 @@ static int dissolve_last_class(const qldpc_code *g, int *lvl, int k)
     return k - 1;
 }
 
-static int build_layers(qldpc_code *g)
+/* level schedule or colouring of the M "checks" of g over its N "VNs" (build_vlayers hands in the graph turned round) */
+static int order_classes(const qldpc_code *g, int *n_out, int **ptr_out, int **order_out, int *natural_out)
 {
     const int N = g->N, M = g->M;
     int *lvl = (int *)malloc(sizeof(int) * (size_t)M);
@@ -248,12 +250,12 @@ static int build_layers(qldpc_code *g)
         for (int j = g->cn_ptr[c]; j < g->cn_ptr[c + 1]; j++) last[g->cn_var[j]] = l;
         if (l > nlev) nlev = l;
     }
-    g->layer_natural = 1;
+    int natural = 1;
     int dsat = 0;
     if (nlev > 256 && nlev > M / 16 && !getenv("QLDPC_FIRST_FIT_LAYERS") && (dsat = colour_dsatur(g, lvl)) > 0) {
         for (int again = 1; again; ) { const int k2 = dissolve_last_class(g, lvl, dsat); again = k2 < dsat; dsat = k2; }
         nlev = dsat;
-        g->layer_natural = 0;
+        natural = 0;
     }
     if (!dsat && nlev > 256 && nlev > M / 16) {
         /* greedy colouring, first-fit, with a per-VN bitset of used colours */
@@ -286,20 +288,51 @@ static int build_layers(qldpc_code *g)
             if (col + 1 > nlev) nlev = col + 1;
         }
         free(used); free(acc);
-        g->layer_natural = 0;
+        natural = 0;
     }
     free(last);
-    g->n_layers = nlev;
-    g->layer_ptr = (int *)calloc((size_t)nlev + 1, sizeof(int));
-    g->layer_order = (int *)malloc(sizeof(int) * (size_t)M);
-    if (!g->layer_ptr || !g->layer_order) { free(lvl); return QLDPC_ENOMEM; }
-    for (int c = 0; c < M; c++) g->layer_ptr[lvl[c]]++;
-    for (int l = 0; l < nlev; l++) g->layer_ptr[l + 1] += g->layer_ptr[l];
+    int *ptr = (int *)calloc((size_t)nlev + 1, sizeof(int));
+    int *order = (int *)malloc(sizeof(int) * (size_t)M);
     int *fill = (int *)calloc((size_t)nlev, sizeof(int));
-    if (!fill) { free(lvl); return QLDPC_ENOMEM; }
-    for (int c = 0; c < M; c++) { int l = lvl[c] - 1; g->layer_order[g->layer_ptr[l] + fill[l]++] = c; }
+    if (!ptr || !order || !fill) { free(ptr); free(order); free(fill); free(lvl); return QLDPC_ENOMEM; }
+    for (int c = 0; c < M; c++) ptr[lvl[c]]++;
+    for (int l = 0; l < nlev; l++) ptr[l + 1] += ptr[l];
+    for (int c = 0; c < M; c++) { int l = lvl[c] - 1; order[ptr[l] + fill[l]++] = c; }
     free(fill); free(lvl);
+    *n_out = nlev; *ptr_out = ptr; *order_out = order; *natural_out = natural;
     return QLDPC_OK;
+}
+
+static int build_layers(qldpc_code *g)
+{
+    return order_classes(g, &g->n_layers, &g->layer_ptr, &g->layer_order, &g->layer_natural);
+}
+
+/*
+ * The mirror image for the vertical-layered decoder: level(v) = 1 + max level of any earlier VN sharing a check.  VNs of one level
+ * share no check, and running levels in order is operation-for-operation the sequential v = 0..N-1 sweep of
+ * Decoder_LDPC_BP_vertical_layered.  A dual-diagonal parity chain makes level(v) = v; then the VN-conflict graph is coloured (DSATUR on
+ * the per-check used-colour words, first-fit with growing bitsets when 64 colours do not do: the VNs of a check are a clique, so a
+ * rate-0.9 mother with dc ~ 40 may need more), which is the sequential sweep in the VN order qldpc_code_vlayer_order exports.
+ * Built on first use (no cost for codes that never run this schedule); codes are shared between threads, hence the lock.
+ */
+static int g_vlayer_lock;
+static int build_vlayers(const qldpc_code *cg)
+{
+    qldpc_code *g = (qldpc_code *)cg;
+    int rc = QLDPC_OK;
+    while (__atomic_exchange_n(&g_vlayer_lock, 1, __ATOMIC_ACQUIRE)) usleep(50);
+    if (!g->vlayer_order) {
+        qldpc_code t;      /* the graph turned round: VNs in the place of checks */
+        memset(&t, 0, sizeof(t));
+        t.N = g->M; t.M = g->N; t.E = g->E;
+        t.cn_ptr = g->vn_ptr; t.cn_var = g->vn_chk; t.vn_ptr = g->cn_ptr; t.vn_chk = g->cn_var;
+        int n = 0, natural = 0, *ptr = NULL, *order = NULL;
+        rc = order_classes(&t, &n, &ptr, &order, &natural);
+        if (rc == QLDPC_OK) { g->n_vlayers = n; g->vlayer_ptr = ptr; g->vlayer_natural = natural; g->vlayer_order = order; }
+    }
+    __atomic_store_n(&g_vlayer_lock, 0, __ATOMIC_RELEASE);
+    return rc;
 }
 
 static int detect_ira(const qldpc_code *g)
@@ -578,6 +611,23 @@ int qldpc_code_layer_order(const qldpc_code *c, int *check_order, int *layer_ptr
     if (check_order) memcpy(check_order, c->layer_order, sizeof(int) * (size_t)c->M);
     if (layer_ptr) memcpy(layer_ptr, c->layer_ptr, sizeof(int) * ((size_t)c->n_layers + 1));
     return c->layer_natural;
+}
+
+int qldpc_code_vlayer_count(const qldpc_code *c)
+{
+    if (!c) return QLDPC_EINVAL;
+    const int rc = build_vlayers(c);
+    return rc != QLDPC_OK ? rc : c->n_vlayers;
+}
+
+int qldpc_code_vlayer_order(const qldpc_code *c, int *vn_order, int *vlayer_ptr)
+{
+    if (!c) return QLDPC_EINVAL;
+    const int rc = build_vlayers(c);
+    if (rc != QLDPC_OK) return rc;
+    if (vn_order) memcpy(vn_order, c->vlayer_order, sizeof(int) * (size_t)c->N);
+    if (vlayer_ptr) memcpy(vlayer_ptr, c->vlayer_ptr, sizeof(int) * ((size_t)c->n_vlayers + 1));
+    return c->vlayer_natural;
 }
 
 int qldpc_code_syndrome_host(const qldpc_code *c, const int *x, int *s)

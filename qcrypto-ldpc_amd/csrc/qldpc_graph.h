@@ -28,6 +28,11 @@ struct qldpc_code {
     int *layer_ptr;   /* [n_layers+1] into layer_order                                */
     int *layer_order; /* [M] checks in execution order                                */
     int layer_natural;/* 1: order is equivalent to c = 0..M-1 (level schedule)        */
+    /* vertical-layered execution order: classes of mutually check-disjoint VNs, built on first use (qldpc_code_vlayer_*) */
+    int n_vlayers;
+    int *vlayer_ptr;   /* [n_vlayers+1] into vlayer_order                             */
+    int *vlayer_order; /* [N] VNs in execution order (NULL until built)               */
+    int vlayer_natural;/* 1: order is equivalent to v = 0..N-1 (level schedule)       */
 };
 
 void qldpc_set_error(const char *fmt, ...);

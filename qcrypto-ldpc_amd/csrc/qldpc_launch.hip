@@ -6,6 +6,7 @@
 #include "qldpc_engine_int.h"
 #include "qldpc_kernels_h16.h"
 #include "qldpc_kernels_cst.h"
+#include "qldpc_kernels_vl.h"
 
 #ifndef QL_V
 #error "compile with -DQL_V=1, 2 or 4"
@@ -129,6 +130,26 @@ void qldpc_launch_layer(qldpc_decoder *d, const bucket &b)
     }
 }
 
+/* one class of the vertical-layered sweep (qldpc_kernels_vl.h): fp32 messages only, the host refuses the other forms */
+template <int V, int FAM>
+static void launch_vlayer_fam(qldpc_decoder *d, const bucket &b)
+{
+    dim3 grid((unsigned)grid_x(b.n, 1), (unsigned)d->G);
+    qk_rule r{d->cfg.rule, d->cfg.rule_param};
+    hipLaunchKernelGGL((qk_vn_vlayer<V, FAM>), grid, dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_b, b.d_list, b.n, d->d_vn_ptr, d->d_vn_chk, d->d_vn_tr,
+                       d->d_cn_ptr, d->d_cn_var, d->N, (size_t)d->E * d->FG, d->d_done, r, d->freeze, d->has_synd ? d->d_synd : nullptr, d->M);
+}
+template <int V>
+void qldpc_launch_vlayer(qldpc_decoder *d, const bucket &b)
+{
+    switch (family_of(d->cfg.rule)) {
+    case QK_FAM_MS: launch_vlayer_fam<V, QK_FAM_MS>(d, b); break;
+    case QK_FAM_SPA: launch_vlayer_fam<V, QK_FAM_SPA>(d, b); break;
+    case QK_FAM_LSPA: launch_vlayer_fam<V, QK_FAM_LSPA>(d, b); break;
+    default: launch_vlayer_fam<V, QK_FAM_AMS>(d, b); break;
+    }
+}
+
 template <int V, int CAP, int UNX, int MODE, typename MT>
 static void launch_vn_k(qldpc_decoder *d, const bucket &b, float *post_out)
 {
@@ -175,6 +196,7 @@ void qldpc_launch_vn(qldpc_decoder *d, const bucket &b, float *post_out)
 
 template void qldpc_launch_cn<QL_V>(qldpc_decoder *, const bucket &, bool);
 template void qldpc_launch_layer<QL_V>(qldpc_decoder *, const bucket &);
+template void qldpc_launch_vlayer<QL_V>(qldpc_decoder *, const bucket &);
 template void qldpc_launch_vn<QL_V, QK_VN_FIRST>(qldpc_decoder *, const bucket &, float *);
 template void qldpc_launch_vn<QL_V, QK_VN_NORMAL>(qldpc_decoder *, const bucket &, float *);
 template void qldpc_launch_vn<QL_V, QK_VN_POST>(qldpc_decoder *, const bucket &, float *);

@@ -9,7 +9,7 @@
  *   one AFF3CT-style row per BER: FRA | BE | FE | BER | FER | SIM_THR (Mb/s)          (Reporter_BFER/_throughput)
  *
  * usage: qldpc_sim [-N n] [-K k | -a alist | -q qc] [-r MS|OMS|NMS|SPA|LSPA|AMS_MIN|AMS_MINSTAR_L2|AMS_MINSTAR] [-p param]
- *                  [-i n_ite] [-f frames_per_ber] [-b batch] [-s ber_min:ber_max:ber_step] [-S seed] [-l (layered)] [-n (no syndrome)]
+ *                  [-i n_ite] [-f frames_per_ber] [-b batch] [-s ber_min:ber_max:ber_step] [-S seed] [-l (horizontal layered)] [-v (vertical layered)] [-n (no syndrome)]
  *                  [-P depth (progressive-edge-growth information part instead of the seeded socket shuffle)]
  *                  [-d parity_ber (dirty disclosed parity bits, BS/data_dvb/data5)]
  *                  [-G IDENTITY|LU_DEC|QC (encoder construction: p.G_method / Encoder_LDPC_from_QC)]
@@ -61,7 +61,7 @@ int main(int argc, char **argv)
     double ber_min = 0.01, ber_max = 0.03, ber_step = 0.005;
     uint64_t seed = 0;
     const char *g_method = NULL;
-    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:Rln")) != -1) {
+    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:Rlvn")) != -1) {
         switch (opt) {
         case 'N': N = atoi(optarg); break;
         case 'K': K = atoi(optarg); break;
@@ -82,6 +82,7 @@ int main(int argc, char **argv)
         case 'o': pattern_out = optarg; break;
         case 'G': g_method = optarg; break;      /* p.G_method (VAR/main.cpp (alist-v1.0.1):135): IDENTITY | LU_DEC; QC = Encoder_LDPC_from_QC ((qc):145) */
         case 'l': layered = 1; break;
+        case 'v': layered = 2; break;      /* Decoder_LDPC_BP_vertical_layered, VAR/main.cpp (alist-v1.0.1):240-256 */
         case 'n': synd = 0; break;
         default: fprintf(stderr, "see the header of qldpc_sim.c for usage\n"); return 2;
         }
@@ -105,7 +106,7 @@ int main(int argc, char **argv)
 
     qldpc_decoder_cfg cfg;
     qldpc_decoder_cfg_default(&cfg);
-    cfg.schedule = layered ? QLDPC_SCHED_HLAYERED : QLDPC_SCHED_FLOODING;
+    cfg.schedule = layered == 2 ? QLDPC_SCHED_VLAYERED : (layered ? QLDPC_SCHED_HLAYERED : QLDPC_SCHED_FLOODING);
     cfg.rule = rule; cfg.rule_param = param; cfg.n_ite = n_ite; cfg.enable_syndrome = synd; cfg.syndrome_depth = 1; cfg.max_frames = batch;
     if (msg_bits != 32 && msg_bits != 16 && msg_bits != 8) { fprintf(stderr, "-Q 32 | 16 | 8\n"); return 2; }
     cfg.msg_dtype = msg_bits == 16 ? 1 : (msg_bits == 8 ? 2 : 0);      /* 16: binary16 message storage; 8: fixed-point min-sum */
@@ -113,7 +114,7 @@ int main(int argc, char **argv)
     if ((rc = qldpc_decoder_create(H, K, pos, &cfg, &dec))) return die("decoder", rc);
 
     printf("# * libqldpc %d on HIP device 0; Decoder_LDPC_BP_%s_Update_rule_%s (param %g), n_ite %d, syndrome %d, %d-bit messages\n", qldpc_version(),
-           layered ? "horizontal_layered" : "flooding", rule_name, (double)param, n_ite, synd, msg_bits);
+           layered == 2 ? "vertical_layered" : (layered ? "horizontal_layered" : "flooding"), rule_name, (double)param, n_ite, synd, msg_bits);
     printf("#    ** Info. bits (K) = %d\n#    ** Frame size (N) = %d\n#    ** Code rate  (R) = %f\n#    ** max CN degree   = %d\n", K, N, (double)K / N, qldpc_code_max_cn_degree(H));
     printf("#    ** Est. QKD Key Rate After Priv Amp = %f\n", (double)(K - (N - K)) / (double)K);
     printf("# %8s | %8s | %8s | %8s | %9s | %9s | %10s\n", "EP", "FRA", "BE", "FE", "BER", "FER", "SIM_THR");
