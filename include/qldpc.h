@@ -74,7 +74,7 @@ typedef enum qldpc_rule {
 /* Decoder_LDPC_BP_{flooding,horizontal_layered,vertical_layered}; VAR/main.cpp (alist-v1.0.1):203-237, 240-256 */
 typedef enum qldpc_schedule {
     QLDPC_SCHED_FLOODING = 0,
-    QLDPC_SCHED_HLAYERED = 1,     /* horizontal layered, checks visited in the code's layer order */
+    QLDPC_SCHED_HLAYERED = 1,     /* horizontal layered, checks visited in the code's layer order; compact = 1 is honoured with fp32 messages and a launch per layer */
 #define QLDPC_RECON_SCHED_AUTO 2  /* qldpc_recon_cfg.schedule only: chosen by the batch size of the session's decoders */
     QLDPC_SCHED_VLAYERED = 3      /* vertical layered (VAR/main.cpp (alist-v1.0.1):240-256), VNs visited in the code's vlayer order: per (VN, check) pair the
                                      horizontal recursion with only the VN's own message and posterior written.  FRAMES engine (auto resolves to it), fp32
@@ -193,12 +193,17 @@ typedef struct qldpc_decoder_cfg {
                             oracle's integer decoder; qldpc_fetch_post_dev then returns the integer posteriors           */
     float quant_scale;   /* msg_dtype 2: quantiser steps per LLR unit (0 = 8.0); OMS offset = rint(rule_param * quant_scale)
                             steps, NMS factor = rint(rule_param * 128) / 128                                          */
-    int compact;         /* FRAMES engine, flooding, enable_syndrome, freeze_messages = 0: active-frame compaction.
+    int compact;         /* FRAMES engine, enable_syndrome, freeze_messages = 0: active-frame compaction.
                             Once the frames that have not converged fit into <= 0.6 of the groups in flight they are dealt into fewer,
                             full groups (the message arrays are not copied: the next check pass reads them through a slot map), so a
                             group no longer runs until its slowest frame.  Decisions, iteration counts and success flags are unchanged;
-                            qldpc_fetch_post_dev is refused after a run that compacted.  0 = auto (batches of >= 4 groups), 1 = whenever
-                            a group can be saved, 2 = never                                                          */
+                            qldpc_fetch_post_dev is refused after a run that compacted.  0 = auto (flooding: batches of >= 4 groups;
+                            layered schedules: never), 1 = whenever a group can be saved, 2 = never.
+                            Horizontal layered: only 1 compacts -- fp32 messages (explicit or the compressed check state), frames_per_lane
+                            1 / 2 / 4, a launch per layer; the posteriors are gathered into a side buffer and the first sweep afterwards reads
+                            the old generation's messages through the slot map into a second one (two pairs, allocated at the first compaction
+                            and counted by qldpc_decoder_device_bytes).  layer_chain = 1, msg_dtype = 2, freeze_messages = 1 and
+                            enable_syndrome = 0 run as without it.  The vertical-layered schedule refuses 1.                */
     int layer_chain;     /* horizontal layered, fp32 messages, 64-frame groups, freeze_messages = 0, check degree <= 40: run a sweep as ONE launch in
                             which a check waits for the earlier checks on its own variable nodes (per-VN version counters, agent-coherent posterior
                             rows) instead of one launch per layer of mutually VN-disjoint checks.  Same results bit for bit.  0 = auto (fixed-iteration

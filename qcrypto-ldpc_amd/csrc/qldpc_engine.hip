@@ -190,6 +190,7 @@ extern "C" void qldpc_decoder_free(qldpc_decoder *d)
     if (d->e_ev[1]) (void)hipEventDestroy(d->e_ev[1]);
     if (d->h_active) (void)hipHostFree(d->h_active);
     (void)hipFree(d->d_work); (void)hipFree(d->d_gcount); (void)hipFree(d->d_goff); (void)hipFree(d->d_llr_alt[0]); (void)hipFree(d->d_llr_alt[1]); (void)hipFree(d->d_llr8_alt[0]); (void)hipFree(d->d_llr8_alt[1]);
+    (void)hipFree(d->d_post_alt[0]); (void)hipFree(d->d_post_alt[1]); (void)hipFree(d->d_msg_alt[0]); (void)hipFree(d->d_msg_alt[1]);
     for (size_t k = 1; k < d->gens.size(); k++) {
         gen_state &n = d->gens[k];
         (void)hipFree(n.sgn); if (n.hard != n.sgn) (void)hipFree(n.hard); (void)hipFree(n.unsat); (void)hipFree(n.done); (void)hipFree(n.ybits); (void)hipFree(n.synd); (void)hipFree(n.ebits);
@@ -319,6 +320,7 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
         if ((rc = dev_alloc(d, &d->e_ctl, QE_CTL_WORDS))) return rc;      /* claim / rank / barrier / fault words of qe_xcd */
         return QLDPC_OK;
     }
+    bool chain_asked = false;      /* horizontal layered: the one-launch sweep was asked for */
     if (cfg->schedule == QLDPC_SCHED_FLOODING) {
         if ((rc = make_buckets(d, code->cn_ptr, nullptr, d->M, CN_CAPS, 4, d->cn_buckets))) return rc;
         if ((rc = make_buckets(d, code->vn_ptr, nullptr, d->N, VN_CAPS, 2, d->vn_buckets))) return rc;
@@ -354,7 +356,7 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
          * 64-frame groups, messages never frozen, check degree <= 32, and the state must fit the message array.  QLDPC_LAYER_CST = 0 keeps the dc messages. */
         d->layer_cst = 0;
         const char *chain_env = getenv("QLDPC_LAYER_CHAIN");
-        const bool chain_asked = chain_env ? atoi(chain_env) != 0 : cfg->layer_chain == 1;      /* an explicit request for the one-launch sweep keeps the explicit messages it works on */
+        chain_asked = chain_env ? atoi(chain_env) != 0 : cfg->layer_chain == 1;      /* an explicit request for the one-launch sweep keeps the explicit messages it works on */
         if (!chain_asked && !d->msg_i8 && !d->msg_half && d->V == 1 && !d->freeze && (family_of(cfg->rule) == QK_FAM_MS || family_of(cfg->rule) == QK_FAM_AMS) && d->max_dc <= 32 &&
             (size_t)d->M * 1024 <= (size_t)d->E * 256)
             d->layer_cst = 1;
@@ -450,13 +452,15 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
     HIPCHK(hipHostMalloc((void **)&d->h_active, 4 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
     memset(d->h_active, 0, 4 * sizeof(int));
     HIPCHK(hipHostGetDevicePointer((void **)&d->h_active_dev, d->h_active, 0));
-    /* active-frame compaction (early exit, flooding, messages not frozen): reserved[0] = 0 auto (batches of >= 4 groups), 1 always, 2 never */
+    /* active-frame compaction (early exit, messages not frozen): 0 auto (flooding: batches of >= 4 groups; layered: never), 1 always, 2 never.
+     * The horizontal-layered schedule compacts only when told to (1), with fp32 messages and a launch per layer; the vertical-layered one never does. */
     d->G0 = d->G;
     d->compact_mode = cfg->compact;
     if (const char *e = getenv("QLDPC_COMPACT")) d->compact_mode = atoi(e);
     d->compact_ratio = 0.6f;
     if (const char *e = getenv("QLDPC_COMPACT_RATIO")) { const float x = (float)atof(e); if (x > 0.0f && x <= 1.0f) d->compact_ratio = x; }
-    if (!cfg->enable_syndrome || cfg->schedule != QLDPC_SCHED_FLOODING || d->freeze || (d->compact_mode == 0 && d->G < 4)) d->compact_mode = 2;
+    const bool layered_compact = cfg->schedule == QLDPC_SCHED_HLAYERED && d->compact_mode == 1 && !d->msg_i8 && !chain_asked && !d->chain;
+    if (!cfg->enable_syndrome || (cfg->schedule != QLDPC_SCHED_FLOODING && !layered_compact) || d->freeze || (d->compact_mode == 0 && d->G < 4)) d->compact_mode = 2;
     if (d->compact_mode != 2) {
         if ((rc = dev_alloc(d, &d->d_gcount, (size_t)d->G))) return rc;
         if ((rc = dev_alloc(d, &d->d_goff, (size_t)d->G + 1))) return rc;
@@ -502,12 +506,13 @@ static void use_gen(qldpc_decoder *d, int k)
     d->G = n.G;
     d->d_sgn = n.sgn; d->d_hard = n.hard; d->d_unsat = n.unsat; d->d_done = n.done; d->d_ybits = n.ybits; d->d_synd = n.synd; d->d_ebits = n.ebits;
     d->d_depth = n.depth; d->d_iters = n.iters; d->d_fmag = n.fmag; d->d_fnch = n.fnch; d->d_llr = n.llr; d->d_llr8 = n.llr8;
+    if (n.post) { d->d_a = n.post; d->d_b = n.msg; }      /* layered: each generation has its own posteriors and messages */
 }
 /* back to the batch as loaded (generation 0 = the decoder's base arrays) */
 static void view_reset(qldpc_decoder *d)
 {
     if (d->cur_gen != 0) { use_gen(d, 0); d->cur_gen = 0; }
-    d->remap_src = nullptr;
+    d->remap_src = nullptr; d->remap_msg = nullptr;
 }
 static void gen0_capture(qldpc_decoder *d)
 {
@@ -516,6 +521,7 @@ static void gen0_capture(qldpc_decoder *d)
     n.G = n.cap = d->G0;
     n.sgn = d->d_sgn; n.hard = d->d_hard; n.unsat = d->d_unsat; n.done = d->d_done; n.ybits = d->d_ybits; n.synd = d->d_synd; n.ebits = d->d_ebits;
     n.depth = d->d_depth; n.iters = d->d_iters; n.origin = nullptr; n.src = nullptr; n.fmag = d->d_fmag; n.fnch = d->d_fnch; n.llr = d->d_llr; n.llr8 = d->d_llr8;
+    n.post = d->d_a; n.msg = d->d_b;
 }
 
 static int ensure_llr(qldpc_decoder *d)
@@ -720,6 +726,8 @@ static int poll_active(qldpc_decoder *d, int *active, int *active_frames = nullp
 /*
  * Open the next generation: the `active_frames` frames that have not converged move into ceil(active_frames / FG) full groups
  * (qldpc_kernels_compact.h).  The message arrays are not touched: the next check pass reads through d->remap_src.
+ * Layered schedule: the posteriors are gathered into a side buffer, the next sweep reads the messages of the old generation through d->remap_src and
+ * writes them into a side buffer too (the layer kernels update in place: a generation cannot take the place of the one it is read from).
  */
 template <typename T> static int gen_alloc(qldpc_decoder *d, T **p, size_t n) { return *p ? QLDPC_OK : dev_alloc(d, p, n); }
 
@@ -750,8 +758,25 @@ static int compact(qldpc_decoder *d, int active_frames)
     if (d->has_synd && (rc = gen_alloc(d, &n.synd, C * d->M * V))) return rc;
     if (d->llr_coded && d->has_erase && (rc = gen_alloc(d, &n.ebits, C * d->N * V))) return rc;
     n.G = Gn;
-    n.llr = nullptr; n.llr8 = nullptr;
-    const bool rows8 = !d->llr_coded && d->msg_i8, rows32 = !d->llr_coded && !d->msg_i8;
+    n.llr = nullptr; n.llr8 = nullptr; n.post = nullptr; n.msg = nullptr;
+    const bool layered = d->cfg.schedule == QLDPC_SCHED_HLAYERED;      /* reads no channel LLRs after var_nodes = Y_N: they stay where they are */
+    const bool rows8 = !layered && !d->llr_coded && d->msg_i8, rows32 = !layered && !d->llr_coded && !d->msg_i8;
+    if (layered) {
+        const int side = k & 1;
+        if (d->lay_alt_cap[side] < n.cap) {      /* sized by the first generation that uses it; grows if a later batch needs more */
+            (void)hipStreamSynchronize(d->stream);
+            if (d->d_post_alt[side]) d->bytes -= (size_t)d->lay_alt_cap[side] * ((size_t)d->N + d->E) * FG * sizeof(float);
+            (void)hipFree(d->d_post_alt[side]); (void)hipFree(d->d_msg_alt[side]);
+            d->d_post_alt[side] = nullptr; d->d_msg_alt[side] = nullptr;
+            d->lay_alt_cap[side] = 0;
+            if ((rc = dev_alloc(d, &d->d_post_alt[side], C * d->N * FG)) || (rc = dev_alloc(d, &d->d_msg_alt[side], C * d->E * FG))) {
+                if (d->d_post_alt[side]) { d->bytes -= C * d->N * FG * sizeof(float); (void)hipFree(d->d_post_alt[side]); d->d_post_alt[side] = nullptr; }
+                return rc;
+            }
+            d->lay_alt_cap[side] = n.cap;
+        }
+        n.post = d->d_post_alt[side]; n.msg = d->d_msg_alt[side];
+    }
     if (rows8 || rows32) {      /* the decoder reads an LLR array: its rows move too, ping-pong between two side buffers (the loaded batch stays intact) */
         const int side = k & 1;
         if (d->llr_alt_cap[side] < n.cap) {      /* sized by the first generation that uses it (later ones are smaller); grows if a later batch needs more */
@@ -779,6 +804,12 @@ static int compact(qldpc_decoder *d, int active_frames)
     if (rows32) hipLaunchKernelGGL((qk_compact_rows<V, float>), dim3(bx, (unsigned)Gn), dim3(QK_THREADS), 0, d->stream, o.llr, n.llr, n.src, d->N, 1.0f);
     if (rows8) hipLaunchKernelGGL((qk_compact_rows<V, uint8_t>), dim3(bx, (unsigned)Gn), dim3(QK_THREADS), 0, d->stream, (const uint8_t *)o.llr8, (uint8_t *)n.llr8, n.src, d->N, (uint8_t)0);
     LAUNCHCHK();
+    if (layered) {
+        prof_scope pr(d, KS_COMPACT_ROWS, 2.0 * d->N * 4.0 * active_frames);
+        hipLaunchKernelGGL((qk_compact_rows<V, float>), dim3(bx, (unsigned)Gn), dim3(QK_THREADS), 0, d->stream, (const float *)o.post, n.post, n.src, d->N, 1.0f);
+        LAUNCHCHK();
+        d->remap_msg = o.msg;
+    }
     d->cur_gen = k;
     use_gen(d, k);
     d->remap_src = n.src;
@@ -833,7 +864,7 @@ static int bx_of(const qldpc_decoder *d) { return std::max(1, std::min((d->N + Q
 struct live_groups {
     qldpc_decoder *d; int saved;
     explicit live_groups(qldpc_decoder *d_) : d(d_), saved(d_->G) { const int gl = std::max(1, (d->n_frames + d->FG - 1) / d->FG); if (gl < d->G) d->G = gl; }
-    ~live_groups() { d->G = saved; }
+    ~live_groups() { if (d->cur_gen == 0) d->G = saved; }      /* a run that compacted leaves the last generation's view, as a flooding run does */
 };
 
 template <int V>
@@ -872,7 +903,7 @@ static int run_layered(qldpc_decoder *d)
     int ite = 0;
     for (; ite < n_ite; ite++) {
         {
-            prof_scope ps(d, KS_LAYER, bytes_layer(d), moved_layer(d));
+            prof_scope ps(d, d->remap_src ? KS_LAYER_REMAP : KS_LAYER, bytes_layer(d), moved_layer(d));
             d->layer_first = (skip_clear && ite == 0) ? 1 : 0;
             if (chain) {
                 HIPCHK(hipMemsetAsync(d->d_chain_ctl + QC_CTL_SHARD0, 0, sizeof(int) * 32 * QC_SHARDS, d->stream));      /* the ticket counters; the fault word stays */
@@ -882,6 +913,7 @@ static int run_layered(qldpc_decoder *d)
             else
                 for (int l = 0; l < d->n_layers; l++)
                     for (auto &b : d->layer_buckets[(size_t)l]) { qldpc_launch_layer<V>(d, b); LAUNCHCHK(); }
+            d->remap_src = nullptr; d->remap_msg = nullptr;      /* every message row is in the current generation's layout now */
         }
         if (d->cfg.enable_syndrome) {
             {
@@ -892,9 +924,17 @@ static int run_layered(qldpc_decoder *d)
             if ((rc = synd_pass<V>(d, d->d_sgn, 1))) return rc;
             if ((rc = status_pass<V>(d, ite + 1))) return rc;
             if (d->poll_every > 0 && ((ite + 1) % d->poll_every) == 0) {
-                int active = 1;
-                if ((rc = poll_active(d, &active))) return rc;
+                int active = 1, left = 0;
+                if ((rc = poll_active(d, &active, &left))) return rc;
                 if (active == 0) { ite++; break; }
+                if (d->compact_mode != 2) d->live_lanes = active * d->FG;      /* byte accounting of the profile follows the groups still running */
+                /* compact = 1: deal the frames still running into fewer, full groups whenever that saves one (the rule of run_flooding; d->G is the
+                 * number of groups that hold frames).  Never before sweep 0 is done, so the "messages are zero" shortcut and the remap read never meet. */
+                const int Gn = (left + d->FG - 1) / d->FG;
+                if (d->compact_mode != 2 && d->cur_gen + 1 < QLDPC_MAX_GENS && ite + 2 < n_ite && Gn < d->G &&
+                    (d->compact_mode == 1 || (float)Gn <= d->compact_ratio * (float)d->G)) {
+                    if ((rc = compact<V>(d, left))) return rc;
+                }
             }
         }
     }

@@ -26,8 +26,8 @@
         }                                                                                               \
     } while (0)
 
-enum { KS_CN = 0, KS_VN, KS_LAYER, KS_SYND, KS_STATUS, KS_LOAD, KS_FETCH, KS_VLAYER, KS_COUNT };
-static const char *const ks_names[KS_COUNT] = {"cn_update", "vn_update", "layer_update", "syndrome", "status", "load", "fetch", "vn_vlayer"};
+enum { KS_CN = 0, KS_VN, KS_LAYER, KS_SYND, KS_STATUS, KS_LOAD, KS_FETCH, KS_VLAYER, KS_LAYER_REMAP, KS_COMPACT_ROWS, KS_COUNT };
+static const char *const ks_names[KS_COUNT] = {"cn_update", "vn_update", "layer_update", "syndrome", "status", "load", "fetch", "vn_vlayer", "layer_update_remap", "compact_rows"};
 
 struct prof_rec { int kind; double bytes, moved; hipEvent_t a, b; };
 
@@ -47,7 +47,8 @@ struct gen_state {
     u64 *sgn, *hard, *unsat, *done, *ybits, *synd, *ebits;
     int *depth, *iters, *origin, *src;   /* origin[slot] = frame index in the caller's batch (-1: padding); src[slot] = slot in the previous generation */
     float *fmag; int *fnch;
-    float *llr; uint32_t *llr8;          /* channel LLR rows in this generation's layout (NULL with coded LLRs) */
+    float *llr; uint32_t *llr8;          /* channel LLR rows in this generation's layout (NULL with coded LLRs, and in a layered run: not read after var_nodes = Y_N) */
+    float *post, *msg;                   /* layered schedule: posteriors and messages / check state of this generation (flooding: NULL past generation 0, its arrays are re-used in place) */
 };
 #define QLDPC_MAX_GENS 6
 
@@ -87,9 +88,12 @@ struct qldpc_decoder {
     int cur_gen, compact_mode, compactions;
     int live_lanes;                  /* lanes of the groups still active at the last poll (byte accounting of the profile; 0 = not polled yet) */
     float compact_ratio;             /* compact when the active frames fit into <= ratio * G groups */
-    const int *remap_src;            /* != NULL: the next check pass reads var_to_chk through this map (set by a compaction) */
+    const int *remap_src;            /* != NULL: the next check pass reads var_to_chk (layered: the next sweep reads the messages) through this map (set by a compaction) */
+    const float *remap_msg;          /* layered: the previous generation's message / check-state array that sweep reads */
     int *d_gcount, *d_goff;          /* [G0], [G0 + 1] */
     int llr_alt_cap[2]; float *d_llr_alt[2]; uint32_t *d_llr8_alt[2];   /* side buffers for compacted LLR rows (generations ping-pong between them; capacity in groups) */
+    int lay_alt_cap[2]; float *d_post_alt[2], *d_msg_alt[2];            /* layered: side buffers of the posteriors and messages of generations >= 1 (ping-pong by generation parity: the
+                                                                         * layer kernels update in place, so a generation cannot be written over the one it is read from) */
     size_t bytes;
     int n_frames;                    /* loaded */
     int loaded, ran;

@@ -701,13 +701,22 @@ __global__ __launch_bounds__(QK_THREADS) void qk_vn_flood(const MT *__restrict__
  *   var_nodes[v_i] = contributions[i] + messages[k]
  * msg is CN-major [G][E][FG]; post is [G][N][FG].  One wavefront per check.
  */
-template <int V, int DCMAX, int FAM>
+/* REMAP: the first sweep after a compaction (qldpc_kernels_compact.h).  The posteriors were gathered into the new generation's array; the check's
+ * own messages are still laid out for the old generation in ANOTHER array: frame (lane, j) of this group reads slot remap.src[g * FG + lane * V + j]
+ * of remap.msg_old (a per-lane base pointer; padding lanes read slot 0, their results are never looked at) and every row is written to msg in the new
+ * layout.  Never sweep 0 (`first` is not looked at) and never with frozen messages.  A template flag: the instances every other sweep runs carry an
+ * empty argument and are the kernels they were. */
+template <bool REMAP> struct qk_layer_remap {};
+template <> struct qk_layer_remap<true> { const float *msg_old; const int *src; };
+
+template <int V, int DCMAX, int FAM, bool REMAP = false>
 __global__ __launch_bounds__(QK_THREADS) void qk_cn_layer(float *__restrict__ post, float *__restrict__ msg,
                                                           const int *__restrict__ list, int n_list,
                                                           const int *__restrict__ cn_ptr, const int *__restrict__ cn_var,
                                                           int N, size_t group_stride, const u64 *__restrict__ done, qk_rule rule, int freeze, const u64 *__restrict__ synd, int M,
                                                           int first /* sweep 0: messages are all zero -- they are not read (and the host has not cleared the array) */,
-                                                          const int *__restrict__ rec = nullptr, int rec_stride = 0 /* bucket::d_rec (DCMAX > 0 only) */)
+                                                          const int *__restrict__ rec = nullptr, int rec_stride = 0 /* bucket::d_rec (DCMAX > 0 only) */,
+                                                          qk_layer_remap<REMAP> remap = qk_layer_remap<REMAP>{})
 {
     constexpr int FG = 64 * V;
     const int g = blockIdx.y;
@@ -747,6 +756,15 @@ __global__ __launch_bounds__(QK_THREADS) void qk_cn_layer(float *__restrict__ po
     const bool any_frozen = qk_frozen<V>(done, g, lane, frozen) && freeze;
     float *pg = post + (size_t)g * N * FG + lane * V;
     float *mg = msg + (size_t)g * group_stride + lane * V;
+    [[maybe_unused]] const float *mo[V];      /* REMAP only */
+    if constexpr (REMAP) {
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+            int s = remap.src[(size_t)g * FG + lane * V + j];
+            s = s < 0 ? 0 : s;
+            mo[j] = remap.msg_old + (size_t)(s / FG) * group_stride + (s % FG);
+        }
+    }
 
     qk_acc<FAM> acc[V];
 #pragma unroll
@@ -764,7 +782,10 @@ __global__ __launch_bounds__(QK_THREADS) void qk_cn_layer(float *__restrict__ po
         for (int k = 0; k < DCMAX; k++)
             if (k < deg) {
                 qk_load<V>(x[k], pg + (size_t)vn[k] * FG);
-                if (!first) qk_ldm<V>(m[k], mg + (size_t)(b + k) * FG);        /* the check's own messages: read once, written once per sweep */
+                if constexpr (REMAP) {
+#pragma unroll
+                    for (int j = 0; j < V; j++) m[k][j] = qk_ldm1(mo[j] + (size_t)(b + k) * FG);
+                } else if (!first) qk_ldm<V>(m[k], mg + (size_t)(b + k) * FG);        /* the check's own messages: read once, written once per sweep */
                 else {
 #pragma unroll
                     for (int j = 0; j < V; j++) m[k][j] = 0.0f;
@@ -792,7 +813,10 @@ __global__ __launch_bounds__(QK_THREADS) void qk_cn_layer(float *__restrict__ po
         for (int k = 0; k < deg; k++) {
             float p[V], m[V];
             qk_load<V>(p, pg + (size_t)cn_var[b + k] * FG);
-            if (!first) qk_load<V>(m, mg + (size_t)(b + k) * FG);
+            if constexpr (REMAP) {
+#pragma unroll
+                for (int j = 0; j < V; j++) m[j] = qk_ldm1(mo[j] + (size_t)(b + k) * FG);
+            } else if (!first) qk_load<V>(m, mg + (size_t)(b + k) * FG);
             else {
 #pragma unroll
                 for (int j = 0; j < V; j++) m[j] = 0.0f;
@@ -805,7 +829,10 @@ __global__ __launch_bounds__(QK_THREADS) void qk_cn_layer(float *__restrict__ po
         for (int k = 0; k < deg; k++) {
             float p[V], m[V], o[V];
             qk_load<V>(p, pg + (size_t)cn_var[b + k] * FG);
-            if (!first) qk_load<V>(m, mg + (size_t)(b + k) * FG);
+            if constexpr (REMAP) {
+#pragma unroll
+                for (int j = 0; j < V; j++) m[j] = qk_ldm1(mo[j] + (size_t)(b + k) * FG);
+            } else if (!first) qk_load<V>(m, mg + (size_t)(b + k) * FG);
             else {
 #pragma unroll
                 for (int j = 0; j < V; j++) m[j] = 0.0f;

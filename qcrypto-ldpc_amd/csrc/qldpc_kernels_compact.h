@@ -16,9 +16,21 @@
  *              after it writes var_to_chk in the new layout over the old one.  So a compaction costs one check pass that
  *              fetches the rows of all old groups, and nothing else on the message arrays.
  *
+ * Horizontal-layered schedule (compact = 1 only; fp32 messages, a launch per layer): its kernels update posteriors and messages IN PLACE, so a wave
+ * writing slot (g', l') of a check's rows could overwrite a slot another wave has yet to read through the map.  The new generation therefore lives in
+ * side buffers, two pairs that ping-pong by generation parity (allocated at the first compaction, sized by the generation's capacity):
+ *   posteriors  : [G][N][FG] gathered into the new layout by qk_compact_rows<V, float>
+ *   messages    : NOT copied.  The first sweep after the compaction runs the REMAP instances of qk_cn_layer / qk_cn_layer_cst: the check's own message
+ *                 rows [G][E][FG] -- or, on the compressed check state, its {cst1, cst2} rows and per-frame masks -- are read from the OLD generation's
+ *                 array through src[] (a per-lane base pointer) and written to the new one.  Sweep 0's "messages are zero" shortcut never meets it: a
+ *                 compaction needs a status pass, i.e. a finished sweep
+ *   channel LLRs: not moved -- a layered run does not read them after var_nodes = Y_N (per-frame erasures and shortening live in those rows)
+ *   ballots     : the target syndromes are re-dealt (qk_compact_ballots); the hard-decision ballots of a frame are final in the generation it converged in
+ * A compaction costs the posterior gather plus one sweep with gathered reads (tests/test_layered_compaction_gpu.py, profiles/layered_compact.json).
+ *
  * The old generation keeps its ballots / done bits / iteration counts: frames that converged there are read from there
  * by the fetch calls (origin[] says where they belong in the caller's order).  Decisions, iteration counts and success
- * flags are those of the uncompacted run bit for bit (tests/test_compaction_gpu.py, tests/fuzz_parity.py).
+ * flags are those of the uncompacted run bit for bit (tests/test_compaction_gpu.py, tests/test_layered_compaction_gpu.py, tests/fuzz_parity.py).
  */
 #ifndef QLDPC_KERNELS_COMPACT_H
 #define QLDPC_KERNELS_COMPACT_H

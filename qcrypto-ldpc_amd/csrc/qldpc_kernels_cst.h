@@ -50,12 +50,14 @@ template <> struct qk_cst_of<QK_FAM_AMS> {
     static __device__ __forceinline__ bool took1(const qk_acc<QK_FAM_AMS> &a, float x) { return fabsf(x) == a.mn; }
 };
 
-template <int DCMAX, int FAM>
+/* REMAP: the first sweep after a compaction (qldpc_kernels_compact.h), as in qk_cn_layer: the lane's frame reads its four state words from the old
+ * generation's array remap.msg_old through the slot map (a per-lane base pointer) and the rows are written to st in the new layout; never sweep 0. */
+template <int DCMAX, int FAM, bool REMAP = false>
 __global__ __launch_bounds__(QK_THREADS) void qk_cn_layer_cst(float *__restrict__ post, float *__restrict__ st,
                                                               const int *__restrict__ list, int n_list,
                                                               const int *__restrict__ cn_ptr, const int *__restrict__ cn_var,
                                                               int N, size_t group_stride, const u64 *__restrict__ done, qk_rule rule, const u64 *__restrict__ synd, int M,
-                                                              int first, const int *__restrict__ rec, int rec_stride)
+                                                              int first, const int *__restrict__ rec, int rec_stride, qk_layer_remap<REMAP> remap = qk_layer_remap<REMAP>{})
 {
     static_assert(DCMAX > 0 && DCMAX <= 32, "one mask bit per edge");
     static_assert(FAM == QK_FAM_MS || FAM == QK_FAM_AMS, "rules whose messages take two magnitudes per check");
@@ -93,7 +95,13 @@ __global__ __launch_bounds__(QK_THREADS) void qk_cn_layer_cst(float *__restrict_
         if (k < deg) x[k] = pg[(size_t)vn[k] * 64];
     float c1 = 0.0f, c2 = 0.0f;
     uint32_t neg = 0u, took1 = 0u;
-    if (!first) {
+    if constexpr (REMAP) {
+        int s = remap.src[(size_t)g * 64 + lane];
+        s = s < 0 ? 0 : s;
+        const float *orow = remap.msg_old + (size_t)(s / 64) * group_stride + (size_t)c * (64 * QK_CST_ROWS) + (s % 64);
+        c1 = qk_ldm1(orow); c2 = qk_ldm1(orow + 64);
+        neg = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(orow + 128)); took1 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(orow + 192));
+    } else if (!first) {
         c1 = qk_ldm1(crow); c2 = qk_ldm1(crow + 64);
         neg = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(crow + 128)); took1 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(crow + 192));
     }

@@ -99,6 +99,17 @@ static void launch_layer_one(qldpc_decoder *d, const bucket &b)
                                d->N, (size_t)d->E * 64, d->d_done, qi_rule_of(d), d->has_synd ? d->d_synd : nullptr, d->M);
         return;
     }
+    if (d->remap_src) {      /* the first sweep after a compaction: the messages / the check state are read from the old generation's array through the slot map (never sweep 0) */
+        if (d->layer_cst) {
+            if constexpr (V == 1 && (FAM == QK_FAM_MS || FAM == QK_FAM_AMS) && CAP > 0)
+                hipLaunchKernelGGL((qk_cn_layer_cst<(CAP > 32 ? 32 : CAP), FAM, true>), grid, dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_b, b.d_list, b.n, d->d_cn_ptr, d->d_cn_var,
+                                   d->N, (size_t)d->E * d->FG, d->d_done, r, d->has_synd ? d->d_synd : nullptr, d->M, 0, b.d_rec, QK_REC_HDR + b.cap, qk_layer_remap<true>{d->remap_msg, d->remap_src});
+            return;
+        }
+        hipLaunchKernelGGL((qk_cn_layer<V, CAP, FAM, true>), grid, dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_b, b.d_list, b.n, d->d_cn_ptr, d->d_cn_var,
+                           d->N, (size_t)d->E * d->FG, d->d_done, r, 0, d->has_synd ? d->d_synd : nullptr, d->M, 0, CAP > 0 ? b.d_rec : nullptr, QK_REC_HDR + b.cap, qk_layer_remap<true>{d->remap_msg, d->remap_src});
+        return;
+    }
     if (d->layer_cst) {      /* min-sum / AMS on the compressed check state (qldpc_kernels_cst.h): the host set this only for V = 1, degrees <= 32 */
         if constexpr (V == 1 && (FAM == QK_FAM_MS || FAM == QK_FAM_AMS) && CAP > 0)
             hipLaunchKernelGGL((qk_cn_layer_cst<(CAP > 32 ? 32 : CAP), FAM>), grid, dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_b, b.d_list, b.n, d->d_cn_ptr, d->d_cn_var,
