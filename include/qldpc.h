@@ -433,6 +433,37 @@ int qldpc_privamp(int device, const uint32_t *key_words, int workbits, uint32_t 
 /* device pointers; the key's tail bits past workbits must already be zero */
 int qldpc_privamp_dev(const uint32_t *d_key_words, int workbits, uint32_t seed, int final_bits, uint32_t *d_final_words, void *hip_stream);
 
+/*
+ * The same hash for a batch of blocks in one launch (csrc/qldpc_privamp_batch.hip).  With A one word step of the LFSR and R = A^numwords,
+ * final key bit i = parity(v_key & R^i seed) where v_key = XOR_j (A^T)^(j+1) key[j] is a 32-bit functional of the key: O(numwords +
+ * final_bits) work per block, no bound from the LDS and none at 2^17 final bits.  Bit-identical to qldpc_privamp and to the reference.
+ *
+ * qldpc_privamp_create allocates everything (pinned staging, device buffers for max_blocks blocks of max_key_bits -> max_final_bits bits,
+ * descriptor rows, the jump tables, which are built on the device per call, one per distinct key length); no call afterwards allocates.
+ * max_key_bits and max_final_bits may each be up to 2^24 and max_blocks up to 65 535 (QLDPC_ESIZE above, and when max_blocks x the two row
+ * lengths pass 2^31 words).  The packed key and output areas of the host form (max_blocks rows of max_key_bits / max_final_bits, pinned and
+ * on the device) are allocated whichever form is used afterwards: a caller of qldpc_privamp_blocks_dev alone pays for them too.
+ * final_bits[i] may exceed workbits[i]; final_bits[i] == 0 leaves block i alone; n == 0 is QLDPC_OK.  A bad argument in any block
+ * (NULL row: QLDPC_EINVAL; workbits <= 0, final_bits < 0, a value over the context's sizes, n > max_blocks: QLDPC_ESIZE) refuses the
+ * whole call before any work is queued, and qldpc_last_error() names the block.  A context is not re-entrant; a call first waits for the
+ * previous call on the same context to have run (its descriptor rows are reused).
+ */
+typedef struct qldpc_privamp_ctx qldpc_privamp_ctx;
+int  qldpc_privamp_create(int device, int max_blocks, int max_key_bits, int max_final_bits, qldpc_privamp_ctx **out);
+void qldpc_privamp_free(qldpc_privamp_ctx *pa);
+size_t qldpc_privamp_device_bytes(const qldpc_privamp_ctx *pa);
+/* host buffers, n <= max_blocks blocks of any mix of lengths; key tail bits past workbits[i] are ignored (priv_amp.c:196-198) */
+int qldpc_privamp_blocks(qldpc_privamp_ctx *pa, int n, const uint32_t *const *key_words, const int *workbits,
+                         const uint32_t *seeds, const int *final_bits, uint32_t *const *final_words);
+/* device-resident keys and outputs, rows key_stride / out_stride words apart; workbits / seeds / final_bits are host arrays;
+   asynchronous on hip_stream; writes exactly ceil(final_bits[i]/32) words of row i */
+int qldpc_privamp_blocks_dev(qldpc_privamp_ctx *pa, int n, const uint32_t *d_keys, size_t key_stride, const int *workbits,
+                             const uint32_t *seeds, const int *final_bits, uint32_t *d_out, size_t out_stride, void *hip_stream);
+/* host mirrors of the two halves, for tests: the key fold in `lanes` equal chunks (any lanes >= 1 gives the same value; 0 on a bad
+   argument), and the expansion of a functional into the final key words */
+uint32_t qldpc_privamp_key_functional(const uint32_t *key_words, int workbits, int lanes);
+int qldpc_privamp_expand_host(uint32_t functional, int workbits, uint32_t seed, int final_bits, uint32_t *final_words);
+
 #ifdef __cplusplus
 }
 #endif

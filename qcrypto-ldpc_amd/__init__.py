@@ -576,6 +576,104 @@ def privamp(key_words, workbits, seed, final_bits, device=0):
     return out
 
 
+_sig("qldpc_privamp_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)])
+_sig("qldpc_privamp_free", None, [_vp])
+_sig("qldpc_privamp_device_bytes", C.c_size_t, [_vp])
+_sig("qldpc_privamp_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _up, _ip, C.POINTER(_up)])
+_sig("qldpc_privamp_blocks_dev", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _ip, _up, _ip, _vp, C.c_size_t, _vp])
+_sig("qldpc_privamp_key_functional", C.c_uint32, [_up, C.c_int, C.c_int])
+_sig("qldpc_privamp_expand_host", C.c_int, [C.c_uint32, C.c_int, C.c_uint32, C.c_int, _up])
+
+
+def privamp_key_functional(words, workbits, lanes=1):
+    """v_key = XOR_j (A^T)^(j+1) key[j]: the 32 bits of the key the hash depends on, folded in `lanes` equal chunks (host mirror)"""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    if int(workbits) <= 0 or w.size < (int(workbits) + 31) // 32 or int(lanes) < 1:
+        raise QldpcError(-6, "privamp_key_functional: %d words, workbits = %d, lanes = %d" % (w.size, workbits, lanes))
+    return int(_L.qldpc_privamp_key_functional(w.ctypes.data_as(_up), int(workbits), int(lanes)))
+
+
+def privamp_expand_host(v, workbits, seed, final_bits):
+    """final key bit i = parity(v & R^i seed), R = A^numwords (host mirror) -> ceil(final_bits/32) words, MSB-first"""
+    out = np.zeros((max(int(final_bits), 0) + 31) // 32, np.uint32)
+    _chk(_L.qldpc_privamp_expand_host(int(v) & 0xFFFFFFFF, int(workbits), int(seed) & 0xFFFFFFFF, int(final_bits), out.ctypes.data_as(_up)),
+         "privamp_expand_host")
+    return out
+
+
+class PrivAmp:
+    """privAmp_doPrivAmp's hash for batches of blocks of any mix of lengths, one launch per call (qldpc_privamp_blocks*).
+    Everything is allocated here; blocks() / blocks_dev() allocate nothing on the device."""
+
+    def __init__(self, device=0, max_blocks=64, max_key_bits=1 << 16, max_final_bits=1 << 16):
+        h = _vp()
+        _chk(_L.qldpc_privamp_create(int(device), int(max_blocks), int(max_key_bits), int(max_final_bits), C.byref(h)), "PrivAmp")
+        self._h = h
+        self.device, self.max_blocks, self.max_key_bits, self.max_final_bits = int(device), int(max_blocks), int(max_key_bits), int(max_final_bits)
+
+    @property
+    def device_bytes(self):
+        return int(_L.qldpc_privamp_device_bytes(self._h))
+
+    @staticmethod
+    def _args(n, workbits, seeds, final_bits):
+        wb = np.ascontiguousarray(workbits, dtype=np.int32).ravel()
+        sd = (np.asarray(seeds, dtype=np.int64).ravel() & 0xFFFFFFFF).astype(np.uint32)
+        fb = np.ascontiguousarray(final_bits, dtype=np.int32).ravel()
+        if not (wb.size == sd.size == fb.size == n):
+            raise QldpcError(-6, "PrivAmp: %d blocks, %d workbits, %d seeds, %d final_bits" % (n, wb.size, sd.size, fb.size))
+        return wb, sd, fb
+
+    def blocks(self, keys, workbits, seeds, final_bits, out=None):
+        """keys: list of uint32 word arrays (bits past workbits[i] are ignored) -> list of ceil(final_bits[i]/32)-word arrays.
+        out: arrays to write into instead (a refused call leaves them untouched)"""
+        n = len(keys)
+        wb, sd, fb = self._args(n, workbits, seeds, final_bits)
+        kws = [np.ascontiguousarray(k, dtype=np.uint32) for k in keys]
+        for i, k in enumerate(kws):
+            if wb[i] > 0 and k.size < (int(wb[i]) + 31) // 32:
+                raise QldpcError(-6, "PrivAmp.blocks: block %d has %d words, workbits = %d" % (i, k.size, wb[i]))
+        if out is None:
+            out = [np.zeros((max(int(f), 0) + 31) // 32, np.uint32) for f in fb]
+        for i, o in enumerate(out):
+            if o.dtype != np.uint32 or not o.flags.c_contiguous or o.size < (max(int(fb[i]), 0) + 31) // 32:
+                raise QldpcError(-6, "PrivAmp.blocks: out[%d] must be a contiguous uint32 array of ceil(final_bits/32) words" % i)
+        kp = (_up * max(n, 1))(*[k.ctypes.data_as(_up) for k in kws])
+        op = (_up * max(n, 1))(*[o.ctypes.data_as(_up) for o in out])
+        _chk(_L.qldpc_privamp_blocks(self._h, n, kp, wb.ctypes.data_as(_ip), sd.ctypes.data_as(_up), fb.ctypes.data_as(_ip), op), "PrivAmp.blocks")
+        return out
+
+    def blocks_dev(self, keys_t, workbits, seeds, final_bits, out_t=None, stream=None):
+        """keys_t: torch int32 [n, key_stride] on the device -> out_t int32 [n, out_stride] (row i: ceil(final_bits[i]/32) words written,
+        the rest left as it is); asynchronous on `stream` (default: torch's current stream)"""
+        torch = _torch()
+        n = int(keys_t.shape[0])
+        wb, sd, fb = self._args(n, workbits, seeds, final_bits)
+        if keys_t.dtype != torch.int32 or keys_t.dim() != 2 or keys_t.stride(1) != 1 or not keys_t.is_cuda:
+            raise QldpcError(-6, "PrivAmp.blocks_dev: keys_t must be a device int32 [n, stride] tensor with unit column stride")
+        if out_t is None:
+            out_t = torch.zeros((n, max(1, (int(fb.max(initial=0)) + 31) // 32)), dtype=torch.int32, device=keys_t.device)
+        if out_t.dtype != torch.int32 or out_t.dim() != 2 or out_t.stride(1) != 1 or not out_t.is_cuda or out_t.shape[0] != n:
+            raise QldpcError(-6, "PrivAmp.blocks_dev: out_t must be a device int32 [n, stride] tensor with unit column stride")
+        if keys_t.device.index != self.device or out_t.device.index != self.device:
+            raise QldpcError(-1, "PrivAmp.blocks_dev: keys_t / out_t are on %s / %s, the context is on device %d" % (keys_t.device, out_t.device, self.device))
+        # a row holds shape[1] words even where the rows lie further apart, so the library's row checks use the shape
+        for i in range(n):
+            if (int(wb[i]) + 31) // 32 > keys_t.shape[1] or (int(fb[i]) + 31) // 32 > out_t.shape[1]:
+                raise QldpcError(-6, "PrivAmp.blocks_dev: block %d does not fit its rows" % i)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _chk(_L.qldpc_privamp_blocks_dev(self._h, n, keys_t.data_ptr(), int(keys_t.stride(0)) if n > 1 else int(keys_t.shape[1]), wb.ctypes.data_as(_ip),
+                                         sd.ctypes.data_as(_up), fb.ctypes.data_as(_ip), out_t.data_ptr(),
+                                         int(out_t.stride(0)) if n > 1 else int(out_t.shape[1]), s.cuda_stream), "PrivAmp.blocks_dev")
+        return out_t
+
+    def __del__(self):
+        try:
+            _L.qldpc_privamp_free(self._h)
+        except Exception:
+            pass
+
+
 def crc32_words(words, n_bits, lanes=0):
     """CRC-32 of the key bits; lanes > 0: the chunked fold the device verification uses (same value)"""
     w = np.ascontiguousarray(words, dtype=np.uint32)

@@ -9,6 +9,8 @@
  *
  * usage: qldpc_stream [-e epochs] [-k key_bits] [-b max_blocks] [-S seed] [-r reps] [-q qmin:qmax] [-l (layered) | -f (flooding); default: the sessions' choice = layered for batches] [-P depth (PEG mothers)]
  *                     [-g rate_gap] [-G gap_profile] [-p (per-kernel profile of Bob's decoders in a second pass)]
+ *                     [-H (privacy amplification of the reconciled blocks after every timed decode: ONE qldpc_privamp_blocks call, final_bits =
+ *                          key_bits - leaked bits, seed from the block index; adds pa_ms_mean, pa_ms_best, distill_Mbit_s_mean)]
  *                     (defaults: 512 epochs x 52 429 bits, max_blocks 512, PEG depth 2 = the library's default)
  * prints one JSON object on stdout.
  */
@@ -56,10 +58,10 @@ static void *part_main(void *arg)
 
 int main(int argc, char **argv)
 {
-    int epochs = 512, key_bits = 52429, batch = 512, reps = 3, layered = -1, profile = 0, peg = 2, opt, a_lanes = 0, b_lanes = 0, verbose = 0, split = 1, gap_profile = 0;
+    int epochs = 512, key_bits = 52429, batch = 512, reps = 3, layered = -1, profile = 0, peg = 2, opt, a_lanes = 0, b_lanes = 0, verbose = 0, split = 1, gap_profile = 0, hash = 0;
     uint64_t seed = 42;
     double qmin = 0.005, qmax = 0.06, gap = 0.0;
-    while ((opt = getopt(argc, argv, "e:k:b:S:r:q:lfpP:g:A:B:vT:G:")) != -1) {
+    while ((opt = getopt(argc, argv, "e:k:b:S:r:q:lfpP:g:A:B:vT:G:H")) != -1) {
         switch (opt) {
         case 'e': epochs = atoi(optarg); break;
         case 'k': key_bits = atoi(optarg); break;
@@ -76,6 +78,7 @@ int main(int argc, char **argv)
         case 'B': b_lanes = atoi(optarg); break;
         case 'v': verbose = 1; break;
         case 'G': gap_profile = atoi(optarg); break;      /* qldpc_recon_cfg.gap_profile */
+        case 'H': hash = 1; break;
         case 'T': split = atoi(optarg); break;      /* experiment: T sessions on T host threads, each decoding every T-th epoch */
         default: fprintf(stderr, "usage: see the head of qldpc_stream.c\n"); return 2;
         }
@@ -189,6 +192,18 @@ int main(int argc, char **argv)
     int good = 0;
     long leaked = 0;
     double it_sum = 0.0;
+    /* -H: the hash stage on the blocks Bob has just reconciled; the context and its argument arrays exist before the timed region */
+    qldpc_privamp_ctx *pa = NULL;
+    const uint32_t **pa_keys = NULL;
+    uint32_t **pa_out = NULL, *pa_seed = NULL, *pa_buf = NULL;
+    int *pa_wb = NULL, *pa_fb = NULL;
+    double pa_best = 1e30, pa_sum = 0.0, final_sum = 0.0;
+    if (hash) {
+        if ((rc = qldpc_privamp_create(cfg.device, epochs, key_bits, key_bits, &pa))) return die("privamp_create", rc);
+        pa_keys = calloc((size_t)epochs, sizeof(*pa_keys)); pa_out = calloc((size_t)epochs, sizeof(*pa_out)); pa_seed = calloc((size_t)epochs, 4);
+        pa_wb = calloc((size_t)epochs, sizeof(int)); pa_fb = calloc((size_t)epochs, sizeof(int)); pa_buf = calloc((size_t)epochs * W, 4);
+        if (!pa_keys || !pa_out || !pa_seed || !pa_wb || !pa_fb || !pa_buf) return 1;
+    }
     for (int rep = -1; rep < reps; rep++) {
         memcpy(work, bob, (size_t)epochs * W * 4);
         t0 = now_s();
@@ -204,6 +219,23 @@ int main(int argc, char **argv)
                 pos[ri]++;
             }
             fprintf(stderr, " -> %d failed\n", bad);
+        }
+        if (hash) {
+            int m = 0;
+            long bits = 0;
+            for (int e = 0; e < epochs; e++) {
+                if (status[e] != QLDPC_OK) continue;
+                const int fb = key_bits - qldpc_recon_leaked_bits(&msgs[e]);
+                pa_keys[m] = work + (size_t)e * W; pa_out[m] = pa_buf + (size_t)e * W; pa_wb[m] = key_bits; pa_fb[m] = fb > 0 ? fb : 0;
+                pa_seed[m] = 0x9e3779b9u * (uint32_t)(e + 1) | 1u;
+                bits += pa_fb[m];
+                m++;
+            }
+            t0 = now_s();
+            rc = qldpc_privamp_blocks(pa, m, pa_keys, pa_wb, pa_seed, pa_fb, pa_out);
+            const double dp = now_s() - t0;
+            if (rc) return die("privamp_blocks", rc);
+            if (rep >= 0) { pa_sum += dp; final_sum += (double)bits; if (dp < pa_best) pa_best = dp; }
         }
         if (rep < 0) continue;
         sum += dt;
@@ -232,6 +264,8 @@ int main(int argc, char **argv)
            (double)good * key_bits / mean / 1e6, (double)good * key_bits / best / 1e6, (double)leaked / fmax(1.0, (double)good * key_bits), it_sum / epochs,
            t_enc * 1e3, per_rate[0], per_rate[1], per_rate[2], per_rate[3], fail_rate[0], fail_rate[1], fail_rate[2], fail_rate[3], maxed[0], maxed[1], maxed[2], maxed[3],
            it_mean[0] / fmax(1, per_rate[0]), it_mean[1] / fmax(1, per_rate[1]), it_mean[2] / fmax(1, per_rate[2]), it_mean[3] / fmax(1, per_rate[3]), it_max[0], it_max[1], it_max[2], it_max[3]);
+    if (hash)
+        printf(", \"pa_ms_mean\": %.3f, \"pa_ms_best\": %.3f, \"distill_Mbit_s_mean\": %.1f", pa_sum / reps * 1e3, pa_best * 1e3, final_sum / (sum + pa_sum) / 1e6);
     if (profile) {
         qldpc_kernel_stat st[16];
         qldpc_recon_profile_enable(rb, 1);
@@ -244,6 +278,7 @@ int main(int argc, char **argv)
         printf("}");
     }
     printf("}\n");
+    qldpc_privamp_free(pa);
     qldpc_recon_free(ra);
     qldpc_recon_free(rb);
     return good == epochs ? 0 : 3;
