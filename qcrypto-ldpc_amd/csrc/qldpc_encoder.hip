@@ -22,15 +22,7 @@
 
 #include "../../include/qldpc.h"
 #include "qldpc_graph.h"
-
-#define HIPCHK(expr)                                                                                    \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess) {                                                                        \
-            qldpc_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));     \
-            return QLDPC_EHIP;                                                                          \
-        }                                                                                               \
-    } while (0)
+#include "qldpc_hip.h"
 
 struct qldpc_encoder {
     int N, M, K, R;          /* R = number of parity positions (rank of H) */

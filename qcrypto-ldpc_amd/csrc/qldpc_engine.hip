@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "qldpc_engine_int.h"
@@ -165,6 +166,14 @@ extern "C" void qldpc_decoder_cfg_default(qldpc_decoder_cfg *cfg)
 
 static void view_reset(qldpc_decoder *d);
 
+/* everything a generation past 0 owns (hard aliases sgn with 8-bit messages; llr / llr8 / post / msg are views into the decoder's side buffers) */
+static void gen_release(gen_state &n)
+{
+    (void)hipFree(n.sgn); if (n.hard != n.sgn) (void)hipFree(n.hard); (void)hipFree(n.unsat); (void)hipFree(n.done); (void)hipFree(n.ybits); (void)hipFree(n.synd); (void)hipFree(n.ebits);
+    (void)hipFree(n.depth); (void)hipFree(n.iters); (void)hipFree(n.origin); (void)hipFree(n.src); (void)hipFree(n.fmag); (void)hipFree(n.fnch);
+    n = gen_state{};
+}
+
 extern "C" void qldpc_decoder_free(qldpc_decoder *d)
 {
     if (!d) return;
@@ -191,11 +200,7 @@ extern "C" void qldpc_decoder_free(qldpc_decoder *d)
     if (d->h_active) (void)hipHostFree(d->h_active);
     (void)hipFree(d->d_work); (void)hipFree(d->d_gcount); (void)hipFree(d->d_goff); (void)hipFree(d->d_llr_alt[0]); (void)hipFree(d->d_llr_alt[1]); (void)hipFree(d->d_llr8_alt[0]); (void)hipFree(d->d_llr8_alt[1]);
     (void)hipFree(d->d_post_alt[0]); (void)hipFree(d->d_post_alt[1]); (void)hipFree(d->d_msg_alt[0]); (void)hipFree(d->d_msg_alt[1]);
-    for (size_t k = 1; k < d->gens.size(); k++) {
-        gen_state &n = d->gens[k];
-        (void)hipFree(n.sgn); if (n.hard != n.sgn) (void)hipFree(n.hard); (void)hipFree(n.unsat); (void)hipFree(n.done); (void)hipFree(n.ybits); (void)hipFree(n.synd); (void)hipFree(n.ebits);
-        (void)hipFree(n.depth); (void)hipFree(n.iters); (void)hipFree(n.origin); (void)hipFree(n.src); (void)hipFree(n.fmag); (void)hipFree(n.fnch);
-    }
+    for (size_t k = 1; k < d->gens.size(); k++) gen_release(d->gens[k]);
     delete d;
 }
 
@@ -532,12 +537,7 @@ static int ensure_llr(qldpc_decoder *d)
 
 extern "C" int qldpc_decoder_set_stream(qldpc_decoder *d, void *s) { if (!d) return QLDPC_EINVAL; d->stream = (hipStream_t)s; return QLDPC_OK; }
 extern "C" size_t qldpc_decoder_device_bytes(const qldpc_decoder *d) { return d ? d->bytes : 0; }
-extern "C" int qldpc_last_run_iterations(const qldpc_decoder *dc)
-{
-    qldpc_decoder *d = const_cast<qldpc_decoder *>(dc);
-    if (!d) return QLDPC_EINVAL;
-    return d->last_iters;
-}
+extern "C" int qldpc_last_run_iterations(const qldpc_decoder *d) { return d ? d->last_iters : (int)QLDPC_EINVAL; }
 
 /* early-exit bookkeeping of the last run (FRAMES engine): out[0] = lane-iterations executed (groups that ran an iteration x frames
  * per group, counted by the status pass), out[1] = compactions, out[2] = groups in the last generation, out[3] = frames per group.
@@ -637,8 +637,7 @@ static double live_frames(const qldpc_decoder *d) { return (double)(d->live_lane
 static double bytes_cn(const qldpc_decoder *d) { return 2.0 * d->E * msg_b(d) * live_frames(d); }
 static double bytes_vn(const qldpc_decoder *d, int mode)
 {
-    if (mode == QK_VN_FIRST) return ((double)d->E * msg_b(d) + d->N * llr_b(d)) * live_frames(d);
-    if (mode == QK_VN_POST) return ((double)d->E * msg_b(d) + d->N * llr_b(d)) * live_frames(d);
+    if (mode != QK_VN_NORMAL) return ((double)d->E * msg_b(d) + d->N * llr_b(d)) * live_frames(d);      /* FIRST writes the messages only, POST reads them only */
     return (2.0 * d->E * msg_b(d) + d->N * llr_b(d)) * live_frames(d);
 }
 /* what a variable-node pass has to fetch in the data form in use: with coded LLRs the channel values are N/8 bytes of received-bit
@@ -656,6 +655,22 @@ static double moved_layer(const qldpc_decoder *d)
     if (!d->layer_cst) return bytes_layer(d);
     return (2.0 * d->E * 4.0 + 8.0 * d->M * 4.0) * live_frames(d);
 }
+
+/* fn(std::integral_constant<int, V>{}) for the decoder's frames-per-lane value: the one place that turns d->V into a template argument */
+template <typename F>
+static auto with_v(const qldpc_decoder *d, F fn)
+{
+    switch (d->V) {
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    default: return fn(std::integral_constant<int, 4>{});
+    }
+}
+
+/* grids {x, groups}: x = the workgroups that cover n_items at per_block each, capped so that the whole launch stays at 4 096 (load and fetch: a wave
+ * per packed word) or 8 192 (the row kernels of a run: per_block rows a workgroup) workgroups */
+static inline dim3 grid_4k(const qldpc_decoder *d, int n_words) { return dim3((unsigned)std::max(1, std::min((n_words + QK_WAVES - 1) / QK_WAVES, 4096 / std::max(1, d->G))), (unsigned)d->G); }
+static inline dim3 grid_8k(int n_items, int per_block, int G) { return dim3((unsigned)std::max(1, std::min((n_items + per_block - 1) / per_block, 8192 / std::max(1, G))), (unsigned)G); }
 
 template <int V, int MODE>
 static int vn_pass(qldpc_decoder *d, float *post_out)
@@ -686,7 +701,7 @@ static int synd_pass(qldpc_decoder *d, const u64 *mask, int skip_done)
         const int lo = part ? Mp : 0, hi = part ? d->M : Mp;
         const int bx = std::max(1, std::min((hi - lo + 255) / 256, 4096 / std::max(1, d->G)));
         hipLaunchKernelGGL((qk_syndrome<V>), dim3((unsigned)((d->G < 8 ? d->G : g8) * bx)), dim3(256), 0, d->stream, mask, d->d_cn_var_t, d->max_dc, d->M, d->N,
-                           d->d_unsat, d->d_done, skip_done, d->has_synd ? d->d_synd : nullptr, d->G, bx, lo, hi, part);
+                           d->d_unsat, d->d_done, skip_done, target_synd(d), d->G, bx, lo, hi, part);
     }
     LAUNCHCHK();
     return QLDPC_OK;
@@ -702,7 +717,7 @@ static int status_pass(qldpc_decoder *d, int ite_done)
 }
 /* blocking: how many groups still have unconverged frames after the status pass launched last, and how many frames those are.
  * The kernel writes the counts and then its sequence number into mapped pinned memory; the host spins on the sequence word. */
-static int poll_active(qldpc_decoder *d, int *active, int *active_frames = nullptr)
+static int poll_active(qldpc_decoder *d, int *active, int *active_frames)
 {
     int *h = d->h_active;
     const auto t0 = std::chrono::steady_clock::now();
@@ -719,7 +734,7 @@ static int poll_active(qldpc_decoder *d, int *active, int *active_frames = nullp
         }
     }
     *active = h[0];
-    if (active_frames) *active_frames = h[1];
+    *active_frames = h[1];
     return QLDPC_OK;
 }
 
@@ -742,9 +757,7 @@ static int compact(qldpc_decoder *d, int active_frames)
     gen_state &n = d->gens[(size_t)k];
     if (n.cap < Gn) {      /* first use (or a larger need than any run before): sized for the largest batch this generation can get */
         (void)hipStreamSynchronize(d->stream);
-        (void)hipFree(n.sgn); if (n.hard != n.sgn) (void)hipFree(n.hard); (void)hipFree(n.unsat); (void)hipFree(n.done); (void)hipFree(n.ybits); (void)hipFree(n.synd); (void)hipFree(n.ebits);
-        (void)hipFree(n.depth); (void)hipFree(n.iters); (void)hipFree(n.origin); (void)hipFree(n.src); (void)hipFree(n.fmag); (void)hipFree(n.fnch);
-        n = gen_state{};
+        gen_release(n);
         n.cap = std::max(Gn, std::min(o.cap, (int)(d->compact_ratio * (float)o.cap) + 1));
     }
     const size_t C = (size_t)n.cap;
@@ -800,13 +813,13 @@ static int compact(qldpc_decoder *d, int active_frames)
     if (d->llr_coded) hipLaunchKernelGGL((qk_compact_ballots<V>), dim3((unsigned)((d->N + 64 * QK_WAVES - 1) / (64 * QK_WAVES)), (unsigned)Gn), dim3(QK_THREADS), 0, d->stream, o.ybits, n.ybits, n.src, d->N);
     if (d->has_synd) hipLaunchKernelGGL((qk_compact_ballots<V>), dim3((unsigned)((d->M + 64 * QK_WAVES - 1) / (64 * QK_WAVES)), (unsigned)Gn), dim3(QK_THREADS), 0, d->stream, o.synd, n.synd, n.src, d->M);
     if (d->llr_coded && d->has_erase) hipLaunchKernelGGL((qk_compact_ballots<V>), dim3((unsigned)((d->N + 64 * QK_WAVES - 1) / (64 * QK_WAVES)), (unsigned)Gn), dim3(QK_THREADS), 0, d->stream, o.ebits, n.ebits, n.src, d->N);
-    const unsigned bx = (unsigned)std::max(1, std::min((d->N + QK_WAVES - 1) / QK_WAVES, 8192 / std::max(1, Gn)));
-    if (rows32) hipLaunchKernelGGL((qk_compact_rows<V, float>), dim3(bx, (unsigned)Gn), dim3(QK_THREADS), 0, d->stream, o.llr, n.llr, n.src, d->N, 1.0f);
-    if (rows8) hipLaunchKernelGGL((qk_compact_rows<V, uint8_t>), dim3(bx, (unsigned)Gn), dim3(QK_THREADS), 0, d->stream, (const uint8_t *)o.llr8, (uint8_t *)n.llr8, n.src, d->N, (uint8_t)0);
+    const dim3 rows = grid_8k(d->N, QK_WAVES, Gn);
+    if (rows32) hipLaunchKernelGGL((qk_compact_rows<V, float>), rows, dim3(QK_THREADS), 0, d->stream, o.llr, n.llr, n.src, d->N, 1.0f);
+    if (rows8) hipLaunchKernelGGL((qk_compact_rows<V, uint8_t>), rows, dim3(QK_THREADS), 0, d->stream, (const uint8_t *)o.llr8, (uint8_t *)n.llr8, n.src, d->N, (uint8_t)0);
     LAUNCHCHK();
     if (layered) {
         prof_scope pr(d, KS_COMPACT_ROWS, 2.0 * d->N * 4.0 * active_frames);
-        hipLaunchKernelGGL((qk_compact_rows<V, float>), dim3(bx, (unsigned)Gn), dim3(QK_THREADS), 0, d->stream, (const float *)o.post, n.post, n.src, d->N, 1.0f);
+        hipLaunchKernelGGL((qk_compact_rows<V, float>), rows, dim3(QK_THREADS), 0, d->stream, (const float *)o.post, n.post, n.src, d->N, 1.0f);
         LAUNCHCHK();
         d->remap_msg = o.msg;
     }
@@ -818,6 +831,40 @@ static int compact(qldpc_decoder *d, int active_frames)
 }
 
 /* ------------------------------------------------------------------ run ---------------------- */
+
+/* the sign ballots of the posteriors of a layered run (what the variable-node pass of a flooding run leaves behind) */
+template <int V>
+static int post_ballots(qldpc_decoder *d)
+{
+    if (d->msg_i8) hipLaunchKernelGGL(qi_post_ballots, grid_8k(d->N, QK_WAVES, d->G), dim3(QK_THREADS), 0, d->stream, (const uint32_t *)d->d_a, d->d_sgn, (u64 *)nullptr, d->N, d->d_done);
+    else hipLaunchKernelGGL((qk_post_ballots<V>), grid_8k(d->N, 32 * QK_WAVES, d->G), dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_sgn, d->d_hard, d->N, d->d_done);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+/*
+ * What follows an iteration / a sweep when the syndrome test is on, `ite_done` of them done: syndrome pass, status pass and -- every poll_every
+ * iterations -- the host's look at what the status pass counted.  *stop: no group has a frame left to decode.  Otherwise, few enough frames left:
+ * deal them into fewer, full groups (the next check pass / sweep reads through the slot map; d->G is the number of groups that hold frames).
+ * track_live: the byte accounting of the profile follows the groups still running.
+ */
+template <int V>
+static int early_exit_step(qldpc_decoder *d, int ite_done, bool track_live, bool *stop)
+{
+    int rc;
+    *stop = false;
+    if ((rc = synd_pass<V>(d, d->d_sgn, 1)) || (rc = status_pass<V>(d, ite_done))) return rc;
+    if (d->poll_every <= 0 || (ite_done % d->poll_every) != 0) return QLDPC_OK;
+    int active = 1, left = 0;
+    if ((rc = poll_active(d, &active, &left))) return rc;
+    if (track_live) d->live_lanes = active * d->FG;
+    *stop = active == 0;
+    const int Gn = (left + d->FG - 1) / d->FG;
+    if (!*stop && d->compact_mode != 2 && d->cur_gen + 1 < QLDPC_MAX_GENS && ite_done + 1 < d->cfg.n_ite && Gn < d->G &&
+        (d->compact_mode == 1 || (float)Gn <= d->compact_ratio * (float)d->G))
+        return compact<V>(d, left);
+    return QLDPC_OK;
+}
 
 template <int V>
 static int run_flooding(qldpc_decoder *d)
@@ -831,23 +878,12 @@ static int run_flooding(qldpc_decoder *d)
     int ite = 0;
     for (; ite < n_ite; ite++) {
         if ((rc = cn_pass<V>(d, skip_first && ite == 0))) return rc;
-        if (ite == n_ite - 1) { ite++; break; }
+        if (ite == n_ite - 1) { ite++; break; }      /* no test after the last iteration: the closing _compute_post and run_v's success flag follow */
         if ((rc = vn_pass<V, QK_VN_NORMAL>(d, nullptr))) return rc;
         if (d->cfg.enable_syndrome) {
-            if ((rc = synd_pass<V>(d, d->d_sgn, 1))) return rc;
-            if ((rc = status_pass<V>(d, ite + 1))) return rc;
-            if (d->poll_every > 0 && ((ite + 1) % d->poll_every) == 0) {
-                int active = 1, left = 0;
-                if ((rc = poll_active(d, &active, &left))) return rc;
-                d->live_lanes = active * d->FG;
-                if (active == 0) { ite++; break; }
-                /* few enough frames left: deal them into fewer, full groups (the next check pass reads through the slot map) */
-                const int Gn = (left + d->FG - 1) / d->FG;
-                if (d->compact_mode != 2 && d->cur_gen + 1 < QLDPC_MAX_GENS && ite + 2 < n_ite && Gn < d->G &&
-                    (d->compact_mode == 1 || (float)Gn <= d->compact_ratio * (float)d->G)) {
-                    if ((rc = compact<V>(d, left))) return rc;
-                }
-            }
+            bool stop;
+            if ((rc = early_exit_step<V>(d, ite + 1, true, &stop))) return rc;
+            if (stop) { ite++; break; }
         }
     }
     d->last_iters = ite;
@@ -857,8 +893,6 @@ static int run_flooding(qldpc_decoder *d)
     d->post_closes_run = 0;
     return rc;
 }
-
-static int bx_of(const qldpc_decoder *d) { return std::max(1, std::min((d->N + QK_WAVES - 1) / QK_WAVES, 8192 / std::max(1, d->G))); }
 
 /* for the length of a layered run, d->G = the groups that hold frames (run_layered says why) */
 struct live_groups {
@@ -896,10 +930,6 @@ static int run_layered(qldpc_decoder *d)
             }
         }
     }
-    auto ballots = [&]() {
-        if (d->msg_i8) hipLaunchKernelGGL(qi_post_ballots, dim3((unsigned)bx_of(d), (unsigned)d->G), dim3(QK_THREADS), 0, d->stream, (const uint32_t *)d->d_a, d->d_sgn, (u64 *)nullptr, d->N, d->d_done);
-        else hipLaunchKernelGGL((qk_post_ballots<V>), dim3((unsigned)std::max(1, std::min((d->N + 32 * QK_WAVES - 1) / (32 * QK_WAVES), 8192 / std::max(1, d->G))), (unsigned)d->G), dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_sgn, d->d_hard, d->N, d->d_done);
-    };
     int ite = 0;
     for (; ite < n_ite; ite++) {
         {
@@ -918,29 +948,17 @@ static int run_layered(qldpc_decoder *d)
         if (d->cfg.enable_syndrome) {
             {
                 prof_scope ps(d, KS_SYND, 0.0, (double)d->N * 4.0 * d->n_frames);      /* the sign ballots of the posteriors: N rows read */
-                ballots();
-                LAUNCHCHK();
+                if ((rc = post_ballots<V>(d))) return rc;
             }
-            if ((rc = synd_pass<V>(d, d->d_sgn, 1))) return rc;
-            if ((rc = status_pass<V>(d, ite + 1))) return rc;
-            if (d->poll_every > 0 && ((ite + 1) % d->poll_every) == 0) {
-                int active = 1, left = 0;
-                if ((rc = poll_active(d, &active, &left))) return rc;
-                if (active == 0) { ite++; break; }
-                if (d->compact_mode != 2) d->live_lanes = active * d->FG;      /* byte accounting of the profile follows the groups still running */
-                /* compact = 1: deal the frames still running into fewer, full groups whenever that saves one (the rule of run_flooding; d->G is the
-                 * number of groups that hold frames).  Never before sweep 0 is done, so the "messages are zero" shortcut and the remap read never meet. */
-                const int Gn = (left + d->FG - 1) / d->FG;
-                if (d->compact_mode != 2 && d->cur_gen + 1 < QLDPC_MAX_GENS && ite + 2 < n_ite && Gn < d->G &&
-                    (d->compact_mode == 1 || (float)Gn <= d->compact_ratio * (float)d->G)) {
-                    if ((rc = compact<V>(d, left))) return rc;
-                }
-            }
+            /* the live lanes are followed only where the run can compact (compact = 1).  A compaction never comes before sweep 0 is done, so the
+             * "messages are zero" shortcut of that sweep and the remap read never meet. */
+            bool stop;
+            if ((rc = early_exit_step<V>(d, ite + 1, d->compact_mode != 2, &stop))) return rc;
+            if (stop) { ite++; break; }
         }
     }
     d->last_iters = std::min(ite, n_ite);
-    ballots();
-    LAUNCHCHK();
+    if ((rc = post_ballots<V>(d))) return rc;
     if (chain) {
         /* a wait that ran into its bound left the fault word set: the decode cannot be trusted; say so and go back to a launch per layer */
         int ctl[4] = {0, 0, 0, 0};
@@ -970,9 +988,6 @@ static int run_vlayered(qldpc_decoder *d)
     const size_t G = (size_t)d->G, FG = (size_t)d->FG;
     HIPCHK(hipMemcpyAsync(d->d_a, d->d_llr, G * d->N * FG * sizeof(float), hipMemcpyDeviceToDevice, d->stream));   /* var_nodes = Y_N */
     HIPCHK(hipMemsetAsync(d->d_b, 0, G * d->E * FG * sizeof(float), d->stream));                                   /* messages = 0 */
-    auto ballots = [&]() {
-        hipLaunchKernelGGL((qk_post_ballots<V>), dim3((unsigned)std::max(1, std::min((d->N + 32 * QK_WAVES - 1) / (32 * QK_WAVES), 8192 / std::max(1, d->G))), (unsigned)d->G), dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_sgn, d->d_hard, d->N, d->d_done);
-    };
     int ite = 0;
     for (; ite < n_ite; ite++) {
         {
@@ -982,22 +997,15 @@ static int run_vlayered(qldpc_decoder *d)
         if (d->cfg.enable_syndrome) {
             {
                 prof_scope ps(d, KS_SYND, 0.0, (double)d->N * 4.0 * d->n_frames);
-                ballots();
-                LAUNCHCHK();
+                if ((rc = post_ballots<V>(d))) return rc;
             }
-            if ((rc = synd_pass<V>(d, d->d_sgn, 1))) return rc;
-            if ((rc = status_pass<V>(d, ite + 1))) return rc;
-            if (d->poll_every > 0 && ((ite + 1) % d->poll_every) == 0) {
-                int active = 1;
-                if ((rc = poll_active(d, &active))) return rc;
-                if (active == 0) { ite++; break; }
-            }
+            bool stop;
+            if ((rc = early_exit_step<V>(d, ite + 1, d->compact_mode != 2, &stop))) return rc;      /* create forces compact_mode = 2 for this schedule: no live lanes, no compaction */
+            if (stop) { ite++; break; }
         }
     }
     d->last_iters = std::min(ite, n_ite);
-    ballots();
-    LAUNCHCHK();
-    return QLDPC_OK;
+    return post_ballots<V>(d);
 }
 
 template <int V>
@@ -1047,14 +1055,10 @@ template <int S>
 static void launch_qe_cn(qldpc_decoder *d, const uint32_t *bits, int slot, int syndrome_only)
 {
     dim3 grid((unsigned)((d->M + QE_CPB - 1) / QE_CPB), (unsigned)d->n_frames);
-    qk_rule r{d->cfg.rule, d->cfg.rule_param};
     float *c2v_out = (slot & 1) ? d->e_c2v1 : d->d_b;        /* ping-pong by iteration parity */
-    if (d->cfg.rule == QLDPC_RULE_SPA)
-        hipLaunchKernelGGL((qe_cn<S, QK_FAM_SPA>), grid, dim3(QE_THREADS), 0, d->stream, d->d_a, c2v_out, d->d_cn_ptr, d->d_cn_tr, d->d_cn_var, bits,
-                           d->M, d->E, d->eW, d->e_unsat, d->e_stride, slot, d->e_done_at, r, syndrome_only, d->has_synd ? d->e_synd : nullptr, (d->M + 31) / 32);
-    else
-        hipLaunchKernelGGL((qe_cn<S, QK_FAM_MS>), grid, dim3(QE_THREADS), 0, d->stream, d->d_a, c2v_out, d->d_cn_ptr, d->d_cn_tr, d->d_cn_var, bits,
-                           d->M, d->E, d->eW, d->e_unsat, d->e_stride, slot, d->e_done_at, r, syndrome_only, d->has_synd ? d->e_synd : nullptr, (d->M + 31) / 32);
+    const auto kernel = d->cfg.rule == QLDPC_RULE_SPA ? qe_cn<S, QK_FAM_SPA> : qe_cn<S, QK_FAM_MS>;
+    hipLaunchKernelGGL(kernel, grid, dim3(QE_THREADS), 0, d->stream, d->d_a, c2v_out, d->d_cn_ptr, d->d_cn_tr, d->d_cn_var, bits,
+                       d->M, d->E, d->eW, d->e_unsat, d->e_stride, slot, d->e_done_at, rule_of(d), syndrome_only, d->has_synd ? d->e_synd : nullptr, (d->M + 31) / 32);
 }
 static int edge_cn(qldpc_decoder *d, const uint32_t *bits, int slot, int syndrome_only)
 {
@@ -1158,7 +1162,7 @@ static int launch_persist(qldpc_decoder *d)
     }
     const int nCN = (d->M + QE_CPB - 1) / QE_CPB, nVN = (d->N + QE_THREADS - 1) / QE_THREADS;
     int nb = std::max(1, std::min(d->persist_blocks, std::max(nCN, nVN)));
-    qk_rule r{d->cfg.rule, d->cfg.rule_param};
+    qk_rule r = rule_of(d);
     float *v2c = d->d_a, *c2v0 = d->d_b, *c2v1 = d->e_c2v1;
     const float *llr = d->d_llr;
     const int *cn_ptr = d->d_cn_ptr, *cn_tr = d->d_cn_tr, *cn_var = d->d_cn_var, *vn_ptr = d->d_vn_ptr;
@@ -1204,7 +1208,6 @@ static int run_edges_persist(qldpc_decoder *d)
 static int run_edges(qldpc_decoder *d)
 {
     int rc;
-    d->iters_pending = 0;
     if (d->persist && !d->prof_on && d->n_frames <= QE_PERSIST_MAX_FRAMES) {
         rc = run_edges_persist(d);
         if (rc != QLDPC_EUNSUPPORTED) return rc;      /* not co-resident on this device: the launch-per-pass path below */
@@ -1213,7 +1216,6 @@ static int run_edges(qldpc_decoder *d)
     const int P = (synd && d->poll_every > 0) ? d->poll_every : n_ite;
     const bool graphs = d->use_graphs && !d->prof_on;
     int ite = 0, pending = -1, flip = 0, chunk = 0;
-    bool stopped = false;
     while (ite < n_ite) {
         const int ite1 = std::min(n_ite, ite + P);
         if (graphs) {
@@ -1228,14 +1230,13 @@ static int run_edges(qldpc_decoder *d)
                 HIPCHK(hipEventSynchronize(d->e_ev[pending]));
                 bool all = true;
                 for (int f = 0; f < F; f++) all = all && d->h_done[(size_t)pending * F + f] >= 0;
-                if (all) { stopped = true; break; }
+                if (all) break;
             }
             HIPCHK(hipMemcpyAsync(d->h_done + (size_t)flip * F, d->e_done_at, sizeof(int) * (size_t)F, hipMemcpyDeviceToHost, d->stream));
             HIPCHK(hipEventRecord(d->e_ev[flip], d->stream));
             pending = flip; flip ^= 1;
         }
     }
-    (void)stopped;
     d->last_iters = ite;
     /* success flag: syndrome of the final hard decisions into the last slot */
     return edge_cn(d, d->e_hard, n_ite + 1, 1);
@@ -1252,11 +1253,7 @@ extern "C" int qldpc_run(qldpc_decoder *d)
         if (rc == QLDPC_OK) d->ran = 1;
         return rc;
     }
-    switch (d->V) {
-    case 1: rc = run_v<1>(d); break;
-    case 2: rc = run_v<2>(d); break;
-    default: rc = run_v<4>(d); break;
-    }
+    rc = with_v(d, [&](auto v) { return run_v<v()>(d); });
     if (rc == QLDPC_OK) d->ran = 1;
     return rc;
 }
@@ -1293,11 +1290,7 @@ extern "C" int qldpc_load_llr_dev(qldpc_decoder *d, const float *d_llr, int n_fr
     {
         prof_scope ps(d, KS_LOAD, 2.0 * d->N * 4.0 * n_frames);
         dim3 grid((unsigned)((d->N + 63) / 64), (unsigned)d->G);
-        switch (d->V) {
-        case 1: hipLaunchKernelGGL((qk_load_llr<1>), grid, dim3(256), 0, d->stream, d_llr, d->d_llr, d->N, n_frames); break;
-        case 2: hipLaunchKernelGGL((qk_load_llr<2>), grid, dim3(256), 0, d->stream, d_llr, d->d_llr, d->N, n_frames); break;
-        default: hipLaunchKernelGGL((qk_load_llr<4>), grid, dim3(256), 0, d->stream, d_llr, d->d_llr, d->N, n_frames); break;
-        }
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_llr<v()>), grid, dim3(256), 0, d->stream, d_llr, d->d_llr, d->N, n_frames); });
         LAUNCHCHK();
         if (d->msg_i8) {
             const size_t n_dwords = (size_t)d->G * d->N * 64;
@@ -1339,12 +1332,8 @@ extern "C" int qldpc_load_bits_short_dev(qldpc_decoder *d, const uint32_t *d_bit
     if (d->d_ybits) {
         /* flooding, fp32 / binary16 messages: keep the received bits as ballots and rebuild Y in the VN passes (qk_coded_llr) */
         prof_scope ps(d, KS_LOAD, ((double)W * 4.0 + d->N / 8.0) * n_frames);
-        dim3 grid((unsigned)std::max(1, std::min((W + QK_WAVES - 1) / QK_WAVES, 4096 / std::max(1, d->G))), (unsigned)d->G);
-        switch (d->V) {
-        case 1: hipLaunchKernelGGL((qk_load_syndrome<1>), grid, dim3(QK_THREADS), 0, d->stream, d_bits, d->d_ybits, d->N, W, n_frames); break;
-        case 2: hipLaunchKernelGGL((qk_load_syndrome<2>), grid, dim3(QK_THREADS), 0, d->stream, d_bits, d->d_ybits, d->N, W, n_frames); break;
-        default: hipLaunchKernelGGL((qk_load_syndrome<4>), grid, dim3(QK_THREADS), 0, d->stream, d_bits, d->d_ybits, d->N, W, n_frames); break;
-        }
+        const dim3 grid = grid_4k(d, W);
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_syndrome<v()>), grid, dim3(QK_THREADS), 0, d->stream, d_bits, d->d_ybits, d->N, W, n_frames); });
         LAUNCHCHK();
         const int total = d->G * d->FG;
         hipLaunchKernelGGL(qk_load_frame_consts, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, d->stream, d_llr_mag, d_n_channel, d->d_fmag, d->d_fnch, n_frames, total, d->N);
@@ -1358,7 +1347,7 @@ extern "C" int qldpc_load_bits_short_dev(qldpc_decoder *d, const uint32_t *d_bit
     if (d->msg_i8) {
         /* 8-bit variant: straight into the quantised array, no fp32 LLRs in between */
         prof_scope ps(d, KS_LOAD, ((double)W * 4.0 + d->N) * n_frames);
-        dim3 grid((unsigned)std::max(1, std::min((W + QK_WAVES - 1) / QK_WAVES, 4096 / std::max(1, d->G))), (unsigned)d->G);
+        const dim3 grid = grid_4k(d, W);
         hipLaunchKernelGGL(qi_load_bits, grid, dim3(QK_THREADS), 0, d->stream, d_bits, d_llr_mag, d_vn_class, d->d_llr8, d->N, W, n_frames, d_n_channel, d->quant_scale);
         LAUNCHCHK();
         d->loaded = 1; d->ran = 0;
@@ -1367,18 +1356,9 @@ extern "C" int qldpc_load_bits_short_dev(qldpc_decoder *d, const uint32_t *d_bit
     if ((rc = ensure_llr(d))) return rc;
     {
         prof_scope ps(d, KS_LOAD, ((double)W * 4.0 + d->N * 4.0) * n_frames);
-        dim3 grid((unsigned)std::max(1, std::min((W + QK_WAVES - 1) / QK_WAVES, 4096 / std::max(1, d->G))), (unsigned)d->G);
-        switch (d->V) {
-        case 1: hipLaunchKernelGGL((qk_load_bits<1>), grid, dim3(QK_THREADS), 0, d->stream, d_bits, d_llr_mag, d_vn_class, d->d_llr, d->N, W, n_frames, d_n_channel); break;
-        case 2: hipLaunchKernelGGL((qk_load_bits<2>), grid, dim3(QK_THREADS), 0, d->stream, d_bits, d_llr_mag, d_vn_class, d->d_llr, d->N, W, n_frames, d_n_channel); break;
-        default: hipLaunchKernelGGL((qk_load_bits<4>), grid, dim3(QK_THREADS), 0, d->stream, d_bits, d_llr_mag, d_vn_class, d->d_llr, d->N, W, n_frames, d_n_channel); break;
-        }
+        const dim3 grid = grid_4k(d, W);
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_bits<v()>), grid, dim3(QK_THREADS), 0, d->stream, d_bits, d_llr_mag, d_vn_class, d->d_llr, d->N, W, n_frames, d_n_channel); });
         LAUNCHCHK();
-        if (d->msg_i8) {
-            const size_t n_dwords = (size_t)d->G * d->N * 64;
-            hipLaunchKernelGGL(qi_quant_llr, dim3((unsigned)std::min<size_t>((n_dwords + 255) / 256, 16384)), dim3(256), 0, d->stream, d->d_llr, d->d_llr8, n_dwords, d->quant_scale);
-            LAUNCHCHK();
-        }
     }
     d->loaded = 1; d->ran = 0;
     return QLDPC_OK;
@@ -1398,12 +1378,8 @@ extern "C" int qldpc_load_syndrome_dev(qldpc_decoder *d, const uint32_t *d_synd_
         HIPCHK(hipMemcpyAsync(d->e_synd, d_synd_bits, sizeof(uint32_t) * (size_t)n_frames * Wm, hipMemcpyDeviceToDevice, d->stream));
     } else {
         if (!d->d_synd && (rc = dev_alloc(d, &d->d_synd, (size_t)d->G * d->M * d->V))) return rc;
-        dim3 grid((unsigned)std::max(1, std::min((Wm + QK_WAVES - 1) / QK_WAVES, 4096 / std::max(1, d->G))), (unsigned)d->G);
-        switch (d->V) {
-        case 1: hipLaunchKernelGGL((qk_load_syndrome<1>), grid, dim3(QK_THREADS), 0, d->stream, d_synd_bits, d->d_synd, d->M, Wm, n_frames); break;
-        case 2: hipLaunchKernelGGL((qk_load_syndrome<2>), grid, dim3(QK_THREADS), 0, d->stream, d_synd_bits, d->d_synd, d->M, Wm, n_frames); break;
-        default: hipLaunchKernelGGL((qk_load_syndrome<4>), grid, dim3(QK_THREADS), 0, d->stream, d_synd_bits, d->d_synd, d->M, Wm, n_frames); break;
-        }
+        const dim3 grid = grid_4k(d, Wm);
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_syndrome<v()>), grid, dim3(QK_THREADS), 0, d->stream, d_synd_bits, d->d_synd, d->M, Wm, n_frames); });
         LAUNCHCHK();
     }
     d->has_synd = 1; d->ran = 0;
@@ -1428,25 +1404,17 @@ extern "C" int qldpc_load_erasures_dev(qldpc_decoder *d, const uint32_t *d_erase
         d->ran = 0;
         return QLDPC_OK;
     }
-    dim3 grid((unsigned)std::max(1, std::min((W + QK_WAVES - 1) / QK_WAVES, 4096 / std::max(1, d->G))), (unsigned)d->G);
+    const dim3 grid = grid_4k(d, W);
     if (d->llr_coded) {
         if (!d->d_ebits && (rc = dev_alloc(d, &d->d_ebits, (size_t)d->G * d->N * d->V))) return rc;
-        switch (d->V) {
-        case 1: hipLaunchKernelGGL((qk_load_syndrome<1>), grid, dim3(QK_THREADS), 0, d->stream, d_erase_bits, d->d_ebits, d->N, W, n_frames); break;
-        case 2: hipLaunchKernelGGL((qk_load_syndrome<2>), grid, dim3(QK_THREADS), 0, d->stream, d_erase_bits, d->d_ebits, d->N, W, n_frames); break;
-        default: hipLaunchKernelGGL((qk_load_syndrome<4>), grid, dim3(QK_THREADS), 0, d->stream, d_erase_bits, d->d_ebits, d->N, W, n_frames); break;
-        }
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_syndrome<v()>), grid, dim3(QK_THREADS), 0, d->stream, d_erase_bits, d->d_ebits, d->N, W, n_frames); });
         LAUNCHCHK();
         d->has_erase = 1; d->ran = 0;
         return QLDPC_OK;
     }
     if (d->msg_i8) hipLaunchKernelGGL((qk_erase_rows<4, uint8_t>), grid, dim3(QK_THREADS), 0, d->stream, d_erase_bits, (uint8_t *)d->d_llr8, d->N, W, n_frames);
     else {
-        switch (d->V) {
-        case 1: hipLaunchKernelGGL((qk_erase_rows<1, float>), grid, dim3(QK_THREADS), 0, d->stream, d_erase_bits, d->d_llr, d->N, W, n_frames); break;
-        case 2: hipLaunchKernelGGL((qk_erase_rows<2, float>), grid, dim3(QK_THREADS), 0, d->stream, d_erase_bits, d->d_llr, d->N, W, n_frames); break;
-        default: hipLaunchKernelGGL((qk_erase_rows<4, float>), grid, dim3(QK_THREADS), 0, d->stream, d_erase_bits, d->d_llr, d->N, W, n_frames); break;
-        }
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_erase_rows<v(), float>), grid, dim3(QK_THREADS), 0, d->stream, d_erase_bits, d->d_llr, d->N, W, n_frames); });
     }
     LAUNCHCHK();
     d->ran = 0;
@@ -1498,12 +1466,8 @@ extern "C" int qldpc_fetch_packed_dev(qldpc_decoder *d, uint32_t *d_out)
         return QLDPC_OK;
     }
     return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) -> int {
-        dim3 grid((unsigned)std::max(1, std::min((W + QK_WAVES - 1) / QK_WAVES, 4096 / std::max(1, d->G))), (unsigned)d->G);
-        switch (d->V) {
-        case 1: hipLaunchKernelGGL((qk_fetch_packed<1>), grid, dim3(QK_THREADS), 0, d->stream, d->d_hard, d_out, d->N, W, n_slots, origin, fin); break;
-        case 2: hipLaunchKernelGGL((qk_fetch_packed<2>), grid, dim3(QK_THREADS), 0, d->stream, d->d_hard, d_out, d->N, W, n_slots, origin, fin); break;
-        default: hipLaunchKernelGGL((qk_fetch_packed<4>), grid, dim3(QK_THREADS), 0, d->stream, d->d_hard, d_out, d->N, W, n_slots, origin, fin); break;
-        }
+        const dim3 grid = grid_4k(d, W);
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_fetch_packed<v()>), grid, dim3(QK_THREADS), 0, d->stream, d->d_hard, d_out, d->N, W, n_slots, origin, fin); });
         LAUNCHCHK();
         return (int)QLDPC_OK;
     });
@@ -1524,11 +1488,7 @@ extern "C" int qldpc_fetch_info_dev(qldpc_decoder *d, int *d_V_K)
     }
     return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) -> int {
         dim3 gk((unsigned)std::max(1, std::min((d->K + 255) / 256, 64)), (unsigned)n_slots);
-        switch (d->V) {
-        case 1: hipLaunchKernelGGL((qk_fetch_info<1>), gk, dim3(256), 0, d->stream, d->d_hard, d->d_info_pos, d_V_K, d->N, d->K, n_slots, origin, fin); break;
-        case 2: hipLaunchKernelGGL((qk_fetch_info<2>), gk, dim3(256), 0, d->stream, d->d_hard, d->d_info_pos, d_V_K, d->N, d->K, n_slots, origin, fin); break;
-        default: hipLaunchKernelGGL((qk_fetch_info<4>), gk, dim3(256), 0, d->stream, d->d_hard, d->d_info_pos, d_V_K, d->N, d->K, n_slots, origin, fin); break;
-        }
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_fetch_info<v()>), gk, dim3(256), 0, d->stream, d->d_hard, d->d_info_pos, d_V_K, d->N, d->K, n_slots, origin, fin); });
         LAUNCHCHK();
         return (int)QLDPC_OK;
     });
@@ -1548,11 +1508,7 @@ extern "C" int qldpc_fetch_status_dev(qldpc_decoder *d, int *d_iters, int *d_ok)
     }
     return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) -> int {
         dim3 gs((unsigned)((n_slots + 255) / 256));
-        switch (d->V) {
-        case 1: hipLaunchKernelGGL((qk_status_out<1>), gs, dim3(256), 0, d->stream, d->d_unsat, d->d_iters, d_iters, d_ok, n_slots, origin, fin); break;
-        case 2: hipLaunchKernelGGL((qk_status_out<2>), gs, dim3(256), 0, d->stream, d->d_unsat, d->d_iters, d_iters, d_ok, n_slots, origin, fin); break;
-        default: hipLaunchKernelGGL((qk_status_out<4>), gs, dim3(256), 0, d->stream, d->d_unsat, d->d_iters, d_iters, d_ok, n_slots, origin, fin); break;
-        }
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_status_out<v()>), gs, dim3(256), 0, d->stream, d->d_unsat, d->d_iters, d_iters, d_ok, n_slots, origin, fin); });
         LAUNCHCHK();
         return (int)QLDPC_OK;
     });
@@ -1576,12 +1532,7 @@ extern "C" int qldpc_fetch_post_dev(qldpc_decoder *d, float *d_post_out)
     const float *src;
     if (d->cfg.schedule == QLDPC_SCHED_FLOODING) {
         if (!d->d_post) { if ((rc = dev_alloc(d, &d->d_post, (size_t)d->G * d->N * d->FG))) return rc; }
-        switch (d->V) {
-        case 1: rc = vn_pass<1, QK_VN_POST>(d, d->d_post); break;
-        case 2: rc = vn_pass<2, QK_VN_POST>(d, d->d_post); break;
-        default: rc = vn_pass<4, QK_VN_POST>(d, d->d_post); break;
-        }
-        if (rc) return rc;
+        if ((rc = with_v(d, [&](auto v) { return vn_pass<v(), QK_VN_POST>(d, d->d_post); }))) return rc;
         src = d->d_post;
     } else if (d->msg_i8) {
         if (!d->d_post) { if ((rc = dev_alloc(d, &d->d_post, (size_t)d->G * d->N * d->FG))) return rc; }
@@ -1593,11 +1544,7 @@ extern "C" int qldpc_fetch_post_dev(qldpc_decoder *d, float *d_post_out)
         src = d->d_a;
     }
     dim3 grid((unsigned)((d->N + 63) / 64), (unsigned)d->G);
-    switch (d->V) {
-    case 1: hipLaunchKernelGGL((qk_unload_f32<1>), grid, dim3(256), 0, d->stream, src, d_post_out, d->N, d->n_frames); break;
-    case 2: hipLaunchKernelGGL((qk_unload_f32<2>), grid, dim3(256), 0, d->stream, src, d_post_out, d->N, d->n_frames); break;
-    default: hipLaunchKernelGGL((qk_unload_f32<4>), grid, dim3(256), 0, d->stream, src, d_post_out, d->N, d->n_frames); break;
-    }
+    with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_unload_f32<v()>), grid, dim3(256), 0, d->stream, src, d_post_out, d->N, d->n_frames); });
     LAUNCHCHK();
     return QLDPC_OK;
 }

@@ -12,19 +12,9 @@
 #include <algorithm>
 #include <vector>
 
-#include "../../include/qldpc.h"
-#include "qldpc_graph.h"
+#include "qldpc_hip.h"
 #include "qldpc_kernels.h"
 #include "qldpc_kernels_i8.h"
-
-#define HIPCHK(expr)                                                                                    \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess) {                                                                        \
-            qldpc_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));     \
-            return QLDPC_EHIP;                                                                          \
-        }                                                                                               \
-    } while (0)
 
 enum { KS_CN = 0, KS_VN, KS_LAYER, KS_SYND, KS_STATUS, KS_LOAD, KS_FETCH, KS_VLAYER, KS_LAYER_REMAP, KS_COMPACT_ROWS, KS_COUNT };
 static const char *const ks_names[KS_COUNT] = {"cn_update", "vn_update", "layer_update", "syndrome", "status", "load", "fetch", "vn_vlayer", "layer_update_remap", "compact_rows"};
@@ -72,7 +62,7 @@ struct qldpc_decoder {
     double vl_rows;
     /* one launch per sweep for small batches (qldpc_kernels_chain.h): execution order, per-edge {dv, rank}, per-VN version counters, ticket / fault words */
     int layer_cst;      /* layered min-sum keeps {cst1, cst2} per check and two ballot words per edge instead of dc messages (qldpc_kernels_cst.h) */
-    int chain, chain_blocks, chain_lds; int *d_chain_order, *d_chain_dep, *d_chain_ver, *d_chain_ctl; int chain_sweeps;
+    int chain, chain_blocks, chain_lds; int *d_chain_order, *d_chain_dep, *d_chain_ver, *d_chain_ctl;
     int layer_first;                 /* layered fp32 run, sweep 0, messages not frozen: the layer kernels treat the messages as zero instead of reading a cleared array */
     /* state */
     float *d_llr, *d_a, *d_b;        /* flooding: a = v2c, b = c2v ; layered: a = post, b = msg */
@@ -123,7 +113,7 @@ struct qldpc_decoder {
     hipEvent_t e_ev[2];
     int use_graphs, graph_frames;
     int persist, persist_blocks;     /* one cooperative launch per decode (qe_persist): enabled / co-resident workgroups (0 = not probed yet) */
-    int *e_ctl; int iters_pending;   /* control words of the one-launch decode (qe_xcd); its iteration count / fault flag are read back on demand */
+    int *e_ctl;                      /* control words of the one-launch decode (qe_xcd): claim / rank / barrier / fault words and its iteration count */
     hipStream_t cap_stream;
     std::vector<hipGraphExec_t> e_graphs;   /* one per chunk of poll_every iterations */
     /* profiling */
@@ -131,12 +121,6 @@ struct qldpc_decoder {
     std::vector<prof_rec> prof_pending;
     qldpc_kernel_stat stats[KS_COUNT];
 };
-
-#define LAUNCHCHK()                                                                                     \
-    do {                                                                                                \
-        hipError_t e__ = hipGetLastError();                                                             \
-        if (e__ != hipSuccess) { qldpc_set_error("%s:%d: kernel launch -> %s", __FILE__, __LINE__, hipGetErrorString(e__)); return QLDPC_EHIP; } \
-    } while (0)
 
 static inline int grid_x(int n_items, int per_wave)
 {
@@ -163,6 +147,11 @@ static inline qi_rule qi_rule_of(const qldpc_decoder *d)
     qr.param = std::min(128, std::max(0, qr.param));
     return qr;
 }
+
+/* what the launchers hand to the kernels again and again: the target syndromes of the syndrome form (NULL: H x = 0), the rule, the coded channel LLRs */
+static inline const u64 *target_synd(const qldpc_decoder *d) { return d->has_synd ? d->d_synd : nullptr; }
+static inline qk_rule rule_of(const qldpc_decoder *d) { return qk_rule{d->cfg.rule, d->cfg.rule_param}; }
+static inline qk_coded_llr coded_llr_of(const qldpc_decoder *d) { return qk_coded_llr{d->d_ybits, d->d_fmag, d->d_fnch, d->d_vcls, d->has_erase ? d->d_ebits : nullptr}; }
 
 /* the in-between variable-node passes only need to leave ballots when the syndrome test reads them; _compute_post always does */
 static inline int want_ballots(const qldpc_decoder *d, int mode)

@@ -16,55 +16,55 @@ template <int V, int CAP, int FAM>
 static void launch_cn_one(qldpc_decoder *d, const bucket &b, bool first)
 {
     dim3 grid((unsigned)grid_x(b.n, 1), (unsigned)d->G);
-    qk_rule r{d->cfg.rule, d->cfg.rule_param};
+    const qk_rule r = rule_of(d);
     if (first && !d->msg_i8) {      /* iteration 0 with coded LLRs: inputs rebuilt from the received bits, var_to_chk is not read (see qk_cn_flood FIRST) */
-        qk_coded_llr c{d->d_ybits, d->d_fmag, d->d_fnch, d->d_vcls, d->has_erase ? d->d_ebits : nullptr};
+        const qk_coded_llr c = coded_llr_of(d);
         if (d->msg_half)
             hipLaunchKernelGGL((qk_cn_flood<V, CAP, FAM, __half, true>), grid, dim3(QK_THREADS), 0, d->stream, (const __half *)d->d_a, (__half *)d->d_b, b.d_list, b.n,
-                               d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, d->freeze, d->has_synd ? d->d_synd : nullptr, d->M, d->d_cn_var, d->N, c);
+                               d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, d->freeze, target_synd(d), d->M, d->d_cn_var, d->N, c);
         else
             hipLaunchKernelGGL((qk_cn_flood<V, CAP, FAM, float, true>), grid, dim3(QK_THREADS), 0, d->stream, (const float *)d->d_a, d->d_b, b.d_list, b.n,
-                               d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, d->freeze, d->has_synd ? d->d_synd : nullptr, d->M, d->d_cn_var, d->N, c);
+                               d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, d->freeze, target_synd(d), d->M, d->d_cn_var, d->N, c);
         return;
     }
     if (d->remap_src) {      /* the check pass right after a compaction: var_to_chk is read through the slot map (never the first pass) */
         if (d->msg_i8) {
             if constexpr (V == QI_V && FAM == QK_FAM_MS)
                 hipLaunchKernelGGL((qi_cn_flood<CAP, false, true>), grid, dim3(QK_THREADS), 0, d->stream, (const uint32_t *)d->d_a, (uint32_t *)d->d_b, b.d_list, b.n,
-                                   d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * 64, d->d_done, qi_rule_of(d), d->has_synd ? d->d_synd : nullptr, d->M, (const uint32_t *)nullptr, (const int *)nullptr, 0,
+                                   d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * 64, d->d_done, qi_rule_of(d), target_synd(d), d->M, (const uint32_t *)nullptr, (const int *)nullptr, 0,
                                    d->remap_src);
         } else if (d->msg_half)
             hipLaunchKernelGGL((qk_cn_flood<V, CAP, FAM, __half, false, true>), grid, dim3(QK_THREADS), 0, d->stream, (const __half *)d->d_a, (__half *)d->d_b, b.d_list, b.n,
-                               d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, 0, d->has_synd ? d->d_synd : nullptr, d->M, (const int *)nullptr, 0, qk_coded_llr{}, d->remap_src);
+                               d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, 0, target_synd(d), d->M, (const int *)nullptr, 0, qk_coded_llr{}, d->remap_src);
         else
             hipLaunchKernelGGL((qk_cn_flood<V, CAP, FAM, float, false, true>), grid, dim3(QK_THREADS), 0, d->stream, (const float *)d->d_a, d->d_b, b.d_list, b.n,
-                               d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, 0, d->has_synd ? d->d_synd : nullptr, d->M, (const int *)nullptr, 0, qk_coded_llr{}, d->remap_src);
+                               d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, 0, target_synd(d), d->M, (const int *)nullptr, 0, qk_coded_llr{}, d->remap_src);
         return;
     }
     if (d->msg_i8) {
         if constexpr (V == QI_V && FAM == QK_FAM_MS) {
             if (first)
                 hipLaunchKernelGGL((qi_cn_flood<CAP, true>), grid, dim3(QK_THREADS), 0, d->stream, (const uint32_t *)d->d_a, (uint32_t *)d->d_b, b.d_list, b.n,
-                                   d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * 64, d->d_done, qi_rule_of(d), d->has_synd ? d->d_synd : nullptr, d->M, d->d_llr8, d->d_cn_var, d->N);
+                                   d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * 64, d->d_done, qi_rule_of(d), target_synd(d), d->M, d->d_llr8, d->d_cn_var, d->N);
             else
                 hipLaunchKernelGGL((qi_cn_flood<CAP, false>), grid, dim3(QK_THREADS), 0, d->stream, (const uint32_t *)d->d_a, (uint32_t *)d->d_b, b.d_list, b.n,
-                                   d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * 64, d->d_done, qi_rule_of(d), d->has_synd ? d->d_synd : nullptr, d->M, (const uint32_t *)nullptr, (const int *)nullptr, 0);
+                                   d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * 64, d->d_done, qi_rule_of(d), target_synd(d), d->M, (const uint32_t *)nullptr, (const int *)nullptr, 0);
         }
         return;
     }
     if (d->msg_half && !d->freeze && d->packed_h16) {
         if constexpr (V == 2 && FAM == QK_FAM_MS && CAP > 0) {      /* packed binary16 fold (qldpc_kernels_h16.h), bit-identical */
             hipLaunchKernelGGL((qh_cn_flood<CAP>), grid, dim3(QK_THREADS), 0, d->stream, (const uint32_t *)d->d_a, (uint32_t *)d->d_b, b.d_list, b.n,
-                               d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * 64, d->d_done, r, d->has_synd ? d->d_synd : nullptr, d->M);
+                               d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * 64, d->d_done, r, target_synd(d), d->M);
             return;
         }
     }
     if (d->msg_half)
         hipLaunchKernelGGL((qk_cn_flood<V, CAP, FAM, __half>), grid, dim3(QK_THREADS), 0, d->stream, (const __half *)d->d_a, (__half *)d->d_b, b.d_list, b.n,
-                           d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, d->freeze, d->has_synd ? d->d_synd : nullptr, d->M);
+                           d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, d->freeze, target_synd(d), d->M);
     else
         hipLaunchKernelGGL((qk_cn_flood<V, CAP, FAM, float>), grid, dim3(QK_THREADS), 0, d->stream, (const float *)d->d_a, d->d_b, b.d_list, b.n,
-                           d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, d->freeze, d->has_synd ? d->d_synd : nullptr, d->M);
+                           d->d_cn_ptr, d->d_cn_tr, (size_t)d->E * d->FG, d->d_done, r, d->freeze, target_synd(d), d->M);
 }
 template <int V, int FAM>
 static void launch_cn_fam(qldpc_decoder *d, const bucket &b, bool first)
@@ -92,32 +92,32 @@ template <int V, int CAP, int FAM>
 static void launch_layer_one(qldpc_decoder *d, const bucket &b)
 {
     dim3 grid((unsigned)grid_x(b.n, 1), (unsigned)d->G);
-    qk_rule r{d->cfg.rule, d->cfg.rule_param};
+    const qk_rule r = rule_of(d);
     if (d->msg_i8) {
         if constexpr (V == QI_V && FAM == QK_FAM_MS)
             hipLaunchKernelGGL((qi_cn_layer<CAP>), grid, dim3(QK_THREADS), 0, d->stream, (uint32_t *)d->d_a, (uint32_t *)d->d_b, b.d_list, b.n, d->d_cn_ptr, d->d_cn_var,
-                               d->N, (size_t)d->E * 64, d->d_done, qi_rule_of(d), d->has_synd ? d->d_synd : nullptr, d->M);
+                               d->N, (size_t)d->E * 64, d->d_done, qi_rule_of(d), target_synd(d), d->M);
         return;
     }
     if (d->remap_src) {      /* the first sweep after a compaction: the messages / the check state are read from the old generation's array through the slot map (never sweep 0) */
         if (d->layer_cst) {
             if constexpr (V == 1 && (FAM == QK_FAM_MS || FAM == QK_FAM_AMS) && CAP > 0)
                 hipLaunchKernelGGL((qk_cn_layer_cst<(CAP > 32 ? 32 : CAP), FAM, true>), grid, dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_b, b.d_list, b.n, d->d_cn_ptr, d->d_cn_var,
-                                   d->N, (size_t)d->E * d->FG, d->d_done, r, d->has_synd ? d->d_synd : nullptr, d->M, 0, b.d_rec, QK_REC_HDR + b.cap, qk_layer_remap<true>{d->remap_msg, d->remap_src});
+                                   d->N, (size_t)d->E * d->FG, d->d_done, r, target_synd(d), d->M, 0, b.d_rec, QK_REC_HDR + b.cap, qk_layer_remap<true>{d->remap_msg, d->remap_src});
             return;
         }
         hipLaunchKernelGGL((qk_cn_layer<V, CAP, FAM, true>), grid, dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_b, b.d_list, b.n, d->d_cn_ptr, d->d_cn_var,
-                           d->N, (size_t)d->E * d->FG, d->d_done, r, 0, d->has_synd ? d->d_synd : nullptr, d->M, 0, CAP > 0 ? b.d_rec : nullptr, QK_REC_HDR + b.cap, qk_layer_remap<true>{d->remap_msg, d->remap_src});
+                           d->N, (size_t)d->E * d->FG, d->d_done, r, 0, target_synd(d), d->M, 0, CAP > 0 ? b.d_rec : nullptr, QK_REC_HDR + b.cap, qk_layer_remap<true>{d->remap_msg, d->remap_src});
         return;
     }
     if (d->layer_cst) {      /* min-sum / AMS on the compressed check state (qldpc_kernels_cst.h): the host set this only for V = 1, degrees <= 32 */
         if constexpr (V == 1 && (FAM == QK_FAM_MS || FAM == QK_FAM_AMS) && CAP > 0)
             hipLaunchKernelGGL((qk_cn_layer_cst<(CAP > 32 ? 32 : CAP), FAM>), grid, dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_b, b.d_list, b.n, d->d_cn_ptr, d->d_cn_var,
-                               d->N, (size_t)d->E * d->FG, d->d_done, r, d->has_synd ? d->d_synd : nullptr, d->M, d->layer_first, b.d_rec, QK_REC_HDR + b.cap);
+                               d->N, (size_t)d->E * d->FG, d->d_done, r, target_synd(d), d->M, d->layer_first, b.d_rec, QK_REC_HDR + b.cap);
         return;
     }
     hipLaunchKernelGGL((qk_cn_layer<V, CAP, FAM>), grid, dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_b, b.d_list, b.n, d->d_cn_ptr, d->d_cn_var,
-                       d->N, (size_t)d->E * d->FG, d->d_done, r, d->freeze, d->has_synd ? d->d_synd : nullptr, d->M, d->layer_first, CAP > 0 ? b.d_rec : nullptr, QK_REC_HDR + b.cap);
+                       d->N, (size_t)d->E * d->FG, d->d_done, r, d->freeze, target_synd(d), d->M, d->layer_first, CAP > 0 ? b.d_rec : nullptr, QK_REC_HDR + b.cap);
 }
 template <int V, int FAM>
 static void launch_layer_fam(qldpc_decoder *d, const bucket &b)
@@ -146,9 +146,9 @@ template <int V, int FAM>
 static void launch_vlayer_fam(qldpc_decoder *d, const bucket &b)
 {
     dim3 grid((unsigned)grid_x(b.n, 1), (unsigned)d->G);
-    qk_rule r{d->cfg.rule, d->cfg.rule_param};
+    const qk_rule r = rule_of(d);
     hipLaunchKernelGGL((qk_vn_vlayer<V, FAM>), grid, dim3(QK_THREADS), 0, d->stream, d->d_a, d->d_b, b.d_list, b.n, d->d_vn_ptr, d->d_vn_chk, d->d_vn_tr,
-                       d->d_cn_ptr, d->d_cn_var, d->N, (size_t)d->E * d->FG, d->d_done, r, d->freeze, d->has_synd ? d->d_synd : nullptr, d->M);
+                       d->d_cn_ptr, d->d_cn_var, d->N, (size_t)d->E * d->FG, d->d_done, r, d->freeze, target_synd(d), d->M);
 }
 template <int V>
 void qldpc_launch_vlayer(qldpc_decoder *d, const bucket &b)
@@ -166,7 +166,7 @@ static void launch_vn_k(qldpc_decoder *d, const bucket &b, float *post_out)
 {
     dim3 grid((unsigned)grid_x(b.n, UNX), (unsigned)d->G);
     if (d->llr_coded) {
-        qk_coded_llr c{d->d_ybits, d->d_fmag, d->d_fnch, d->d_vcls, d->has_erase ? d->d_ebits : nullptr};
+        const qk_coded_llr c = coded_llr_of(d);
         hipLaunchKernelGGL((qk_vn_flood<V, CAP, UNX, MODE, MT, true>), grid, dim3(QK_THREADS), 0, d->stream, (const MT *)d->d_b, (const float *)nullptr, (MT *)d->d_a, d->d_sgn, d->d_hard,
                            post_out, b.d_list, b.n, d->d_vn_ptr, d->N, (size_t)d->E * d->FG, d->d_done, c, want_ballots(d, MODE), d->d_vn_tr);
         return;
@@ -182,7 +182,7 @@ static void launch_vn_one(qldpc_decoder *d, const bucket &b, float *post_out)
         if constexpr (V == QI_V) {
             dim3 grid((unsigned)grid_x(b.n, UN), (unsigned)d->G);
             if (d->llr_coded) {
-                qk_coded_llr c{d->d_ybits, d->d_fmag, d->d_fnch, d->d_vcls, d->has_erase ? d->d_ebits : nullptr};
+                const qk_coded_llr c = coded_llr_of(d);
                 hipLaunchKernelGGL((qi_vn_flood<CAP, UN, MODE, true>), grid, dim3(QK_THREADS), 0, d->stream, (const uint32_t *)d->d_b, (const uint32_t *)nullptr, (uint32_t *)d->d_a, d->d_sgn, (u64 *)nullptr,
                                    post_out, b.d_list, b.n, d->d_vn_ptr, d->N, (size_t)d->E * 64, d->d_done, c, d->quant_scale, want_ballots(d, MODE), d->d_vn_tr);
             } else
@@ -219,12 +219,12 @@ template void qldpc_launch_vn<QL_V, QK_VN_POST>(qldpc_decoder *, const bucket &,
 template <int DCMAX, int FAM>
 static void launch_chain_one(qldpc_decoder *d, int sweep)
 {
-    qk_rule r{d->cfg.rule, d->cfg.rule_param};
+    const qk_rule r = rule_of(d);
     const int total = d->M * d->G;
     const unsigned grid = (unsigned)std::max(1, std::min((total + QK_WAVES - 1) / QK_WAVES, d->chain_blocks));
     hipLaunchKernelGGL((qk_cn_layer_chain<DCMAX, FAM>), dim3(grid), dim3(QK_THREADS), (size_t)d->chain_lds, d->stream, d->d_a, d->d_b, d->d_chain_order, d->M, d->G, d->d_cn_ptr, d->d_cn_var,
                        d->d_chain_dep, d->d_chain_ver, d->d_chain_ctl, sweep, d->N, (size_t)d->E * d->FG, d->d_done, r,
-                       d->has_synd ? d->d_synd : nullptr, d->layer_first, getenv("QLDPC_DEBUG") ? 1 : 0);
+                       target_synd(d), d->layer_first, getenv("QLDPC_DEBUG") ? 1 : 0);
 }
 template <int FAM>
 static void launch_chain_fam(qldpc_decoder *d, int sweep)

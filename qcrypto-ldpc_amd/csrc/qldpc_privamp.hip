@@ -19,15 +19,7 @@
 
 #include "../../include/qldpc.h"
 #include "qldpc_graph.h"
-
-#define HIPCHK(expr)                                                                                    \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess) {                                                                        \
-            qldpc_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));     \
-            return QLDPC_EHIP;                                                                          \
-        }                                                                                               \
-    } while (0)
+#include "qldpc_hip.h"
 
 #define PA_FEEDBACK 0xe0000200u
 #define PA_JUMPS 17                /* output bit index < 2^17 */

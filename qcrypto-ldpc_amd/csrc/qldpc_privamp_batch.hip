@@ -27,15 +27,7 @@
 
 #include "../../include/qldpc.h"
 #include "qldpc_graph.h"
-
-#define HIPCHK(expr)                                                                                    \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess) {                                                                        \
-            qldpc_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));     \
-            return QLDPC_EHIP;                                                                          \
-        }                                                                                               \
-    } while (0)
+#include "qldpc_hip.h"
 
 #define PAB_FEEDBACK 0xe0000200u
 #define PAB_MAX_BITS (1 << 24)     /* max_key_bits and max_final_bits of a context (qldpc.h states it) */

@@ -25,15 +25,7 @@
 
 #include "../../include/qldpc.h"
 #include "qldpc_graph.h"
-
-#define HIPCHK(expr)                                                                                    \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess) {                                                                        \
-            qldpc_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));     \
-            return QLDPC_EHIP;                                                                          \
-        }                                                                                               \
-    } while (0)
+#include "qldpc_hip.h"
 
 /*
  * One of the two staging sets of an entry: while batch i decodes, batch i + 1 is copied into the other set's pinned block, sent to
