@@ -299,6 +299,51 @@ int qldpc_last_run_iterations(const qldpc_decoder *dec);
  * Synchronises the decoder's stream. */
 int qldpc_last_run_stats(qldpc_decoder *dec, long long out[4]);
 
+/* ------------------------------------------------------------------ decoder gangs ------------ */
+/*
+ * A gang steps several horizontal-layered decoders ("members") in lockstep: colour step s of a sweep covers every member that has a layer s,
+ * and is ONE launch per kernel class present (degree cap 8 / 12 / 20 / 40 / any, rule family, explicit messages or compressed check state;
+ * csrc/qldpc_kernels_gang.h) instead of one launch per member and bucket -- the launch granularity of a mixed-rate batch is then that of the
+ * whole batch, not of its smallest group.  The kernels run the members' own per-check code, so every result (hard decisions, iteration counts,
+ * success flags, posteriors) is bit-identical to qldpc_run on each member.  Ballot, syndrome and status passes stay per member.
+ *
+ * Members are loaded and read with their own qldpc_load_* / qldpc_fetch_* calls (syndrome form, erasures and shortened loads included) and stay
+ * usable on their own: qldpc_run on a member is legal before and after gang runs, and a decoder may belong to several gangs.  Members are not
+ * owned and must outlive the gang.  The gang has ONE stream (member 0's at creation, or qldpc_gang_set_stream); a taken member found on another
+ * stream when a run starts is waited for there and moved to the gang's.  Steps are ordered by the stream alone.  The host polls the members'
+ * early-exit counters every p sweeps, p = the smallest non-zero polling period of a member (none: every sweep is issued, converged groups
+ * return early inside the kernels); a member with no frame left takes no part in later launches.
+ *
+ * qldpc_gang_create refuses with QLDPC_EUNSUPPORTED a member that is not: FRAMES engine, QLDPC_SCHED_HLAYERED, fp32 messages, 64-frame groups
+ * (frames_per_lane 1), compaction not enabled, one-launch sweep (layer_chain) not in use; with QLDPC_EINVAL members on different devices or with
+ * different n_ite / enable_syndrome, a NULL or repeated member and n outside 1 .. QLDPC_GANG_MAX_MEMBERS; qldpc_last_error() names the member.
+ * Rules, rule parameters, syndrome_depth, freeze_messages, codes and frame counts may differ.  qldpc_gang_run returns QLDPC_ESTATE before anything
+ * is queued when a taken member has nothing loaded.  Flooding, vertical-layered, binary16 and 8-bit members are not built.
+ *
+ * Unmeasured: what a gang gains over decoders side by side on their own streams.  tools/gang_cost.py measures it; until it has run on the
+ * device nothing in the library turns a gang on by itself (sessions: QLDPC_RECON_GANG=1).
+ */
+typedef struct qldpc_gang qldpc_gang;
+#define QLDPC_GANG_MAX_MEMBERS 32      /* per gang; launches cover up to 8 members each */
+int  qldpc_gang_create(qldpc_decoder *const *members, int n, qldpc_gang **out);
+void qldpc_gang_free(qldpc_gang *g);                       /* members are not owned and must outlive the gang */
+int  qldpc_gang_set_stream(qldpc_gang *g, void *hip_stream); /* sets every member's stream: loads, the run and fetches are ordered on it */
+/* take[n]: which members take part (NULL = every member); the others are left as they are.  Afterwards each taken member is as after qldpc_run. */
+int  qldpc_gang_run(qldpc_gang *g, const unsigned char *take /* n flags, NULL = every member */);
+/* of the last qldpc_gang_run: out[0] = sweeps issued, out[1] = layer launches issued, out[2] = layer launches the members would have issued alone
+ * for the sweeps each took part in, out[3] = members the host dropped before the last sweep */
+int  qldpc_gang_last_run_stats(qldpc_gang *g, long long out[4]);
+/* host only, no device needed */
+/* The planning a gang uses, as a function of the codes: rule[i] = qldpc_rule of member i, compressed[i] != 0 (NULL = none) = it keeps the compressed
+ * check state (min-sum / AMS rules, check degree <= 32: QLDPC_EINVAL otherwise).  *steps = the largest layer count, *launches_per_sweep = the sum
+ * over steps of the distinct kernel classes present, *solo_launches_per_sweep = the sum of the members' own launches (outputs may be NULL).
+ * A check's cap is the smallest of 8, 12, 20, 40 that holds its degree, else 0. */
+int  qldpc_gang_plan(const qldpc_code *const *codes, const int *rule, const int *compressed, int n,
+                     int *steps, int *launches_per_sweep, int *solo_launches_per_sweep);
+/* Host mirror of the kernels' block -> (member, block within the member's range) mapping of one launch (the same inline function): n in 1 .. 8
+ * members, member m owns blocks [prefix[m], prefix[m + 1]); members of zero blocks own none.  A block at or past prefix[n]: QLDPC_EINVAL. */
+int  qldpc_gang_locate_host(const int *prefix /* n + 1, non-decreasing, prefix[0] = 0 */, int n, int block, int *member, int *local);
+
 /* ------------------------------------------------------------------ encoder (Alice) ---------- */
 /* method: "IRA" (dual-diagonal accumulate), "IDENTITY" / "LU_DEC" (Encoder_LDPC_from_H's two G_methods, VAR/main.cpp (alist-v1.0.1):135-145:
  * GF(2) elimination of any H, parity positions searched from the first / from the last column) or "QC" (Encoder_LDPC_from_QC,

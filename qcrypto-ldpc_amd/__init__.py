@@ -123,6 +123,13 @@ _sig("qldpc_profile_read", C.c_int, [_vp, C.POINTER(KernelStat), C.c_int])
 _sig("qldpc_profile_clear", C.c_int, [_vp])
 _sig("qldpc_last_run_iterations", C.c_int, [_vp])
 _sig("qldpc_last_run_stats", C.c_int, [_vp, C.POINTER(C.c_longlong)])
+_sig("qldpc_gang_create", C.c_int, [C.POINTER(_vp), C.c_int, C.POINTER(_vp)])
+_sig("qldpc_gang_free", None, [_vp])
+_sig("qldpc_gang_set_stream", C.c_int, [_vp, _vp])
+_sig("qldpc_gang_run", C.c_int, [_vp, C.POINTER(C.c_ubyte)])
+_sig("qldpc_gang_last_run_stats", C.c_int, [_vp, C.POINTER(C.c_longlong)])
+_sig("qldpc_gang_plan", C.c_int, [C.POINTER(_vp), _ip, _ip, C.c_int, _ip, _ip, _ip])
+_sig("qldpc_gang_locate_host", C.c_int, [_ip, C.c_int, C.c_int, _ip, _ip])
 _sig("qldpc_encoder_create", C.c_int, [_vp, C.c_char_p, C.c_int, C.POINTER(_vp)])
 _sig("qldpc_encoder_free", None, [_vp])
 _sig("qldpc_encoder_reserve", C.c_int, [_vp, C.c_int])
@@ -466,6 +473,67 @@ class Decoder:
             _L.qldpc_decoder_free(self._h)
         except Exception:
             pass
+
+
+class DecoderGang:
+    """Several horizontal-layered Decoders stepped in lockstep: every colour step of a sweep is one launch per kernel class for all
+    members (qldpc.h "decoder gangs").  Members are loaded and read through their own calls and give what Decoder.run() gives, bit for bit."""
+
+    def __init__(self, decoders):
+        self.members = list(decoders)      # kept alive: the gang does not own them
+        arr = (_vp * max(1, len(self.members)))(*[d._h for d in self.members])
+        h = _vp()
+        _chk(_L.qldpc_gang_create(arr, len(self.members), C.byref(h)), "DecoderGang")
+        self._h = h
+
+    def set_stream(self, stream=None):
+        torch = _torch()
+        s = stream if stream is not None else torch.cuda.current_stream(self.members[0].device)
+        _chk(_L.qldpc_gang_set_stream(self._h, _vp(s.cuda_stream)), "DecoderGang.set_stream")
+
+    def run(self, take=None):
+        """take: one flag per member (None = every member); the others are left as they are"""
+        flags = None
+        if take is not None:
+            if len(take) != len(self.members):
+                raise QldpcError(-1, "DecoderGang.run: len(take) != number of members")
+            flags = (C.c_ubyte * len(self.members))(*[1 if t else 0 for t in take])
+        _chk(_L.qldpc_gang_run(self._h, flags), "DecoderGang.run")
+
+    def last_run_stats(self):
+        """sweeps issued, layer launches issued, layer launches the members would have issued alone, members dropped before the last sweep"""
+        out = (C.c_longlong * 4)()
+        _chk(_L.qldpc_gang_last_run_stats(self._h, out), "DecoderGang.last_run_stats")
+        return dict(sweeps=int(out[0]), launches=int(out[1]), solo_launches=int(out[2]), dropped=int(out[3]))
+
+    def __del__(self):
+        try:
+            _L.qldpc_gang_free(self._h)
+        except Exception:
+            pass
+
+
+def gang_plan(codes, rules, compressed=None):
+    """The launch plan of a gang on these codes (host only): dict(steps, launches_per_sweep, solo_launches_per_sweep).
+    rules[i]: rule name of member i; compressed[i]: it keeps the compressed check state (min-sum / AMS rules, check degree <= 32)."""
+    n = len(codes)
+    if len(rules) != n or (compressed is not None and len(compressed) != n):
+        raise QldpcError(-1, "gang_plan: one rule (and one compressed flag) per code")
+    arr = (_vp * max(1, n))(*[c._h for c in codes])
+    r = _np_i32([RULES[x] for x in rules])
+    cs = _np_i32([1 if x else 0 for x in compressed]) if compressed is not None else None
+    st, la, so = C.c_int(), C.c_int(), C.c_int()
+    _chk(_L.qldpc_gang_plan(arr, r.ctypes.data_as(_ip), cs.ctypes.data_as(_ip) if cs is not None else None, n, C.byref(st), C.byref(la), C.byref(so)), "gang_plan")
+    return dict(steps=st.value, launches_per_sweep=la.value, solo_launches_per_sweep=so.value)
+
+
+def gang_locate(prefix, block):
+    """(member, block within the member's range) of a block of a gang launch whose member m owns [prefix[m], prefix[m + 1]): the host mirror
+    of the kernels' mapping"""
+    p = _np_i32(prefix)
+    m, loc = C.c_int(), C.c_int()
+    _chk(_L.qldpc_gang_locate_host(p.ctypes.data_as(_ip), p.size - 1, int(block), C.byref(m), C.byref(loc)), "gang_locate")
+    return m.value, loc.value
 
 
 class Encoder:

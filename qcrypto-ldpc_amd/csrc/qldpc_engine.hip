@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <optional>
 #include <type_traits>
 #include <vector>
 
@@ -185,7 +186,7 @@ extern "C" void qldpc_decoder_free(qldpc_decoder *d)
     for (auto &b : d->vn_buckets) (void)hipFree(b.d_list);
     for (auto &l : d->layer_buckets) for (auto &b : l) { (void)hipFree(b.d_list); (void)hipFree(b.d_rec); }
     for (auto &b : d->vlayer_classes) (void)hipFree(b.d_list);
-    (void)hipFree(d->d_vn_chk);
+    (void)hipFree(d->d_vn_chk); (void)hipFree(d->d_gang);
     (void)hipFree(d->d_cn_ptr); (void)hipFree(d->d_cn_tr); (void)hipFree(d->d_cn_var); (void)hipFree(d->d_vn_ptr); (void)hipFree(d->d_info_pos); (void)hipFree(d->d_cn_var_t); (void)hipFree(d->d_vn_tr);
     (void)hipFree(d->d_chain_order); (void)hipFree(d->d_chain_dep); (void)hipFree(d->d_chain_ver); (void)hipFree(d->d_chain_ctl);
     (void)hipFree(d->d_llr); (void)hipFree(d->d_llr8); (void)hipFree(d->d_ybits); (void)hipFree(d->d_ebits); (void)hipFree(d->d_fmag); (void)hipFree(d->d_fnch); (void)hipFree(d->d_vcls); (void)hipFree(d->d_a); (void)hipFree(d->d_b); (void)hipFree(d->d_post);
@@ -848,13 +849,20 @@ static int post_ballots(qldpc_decoder *d)
  * deal them into fewer, full groups (the next check pass / sweep reads through the slot map; d->G is the number of groups that hold frames).
  * track_live: the byte accounting of the profile follows the groups still running.
  */
+/* its two halves, which a gang run (gang_run) issues for all members before it waits for any of them: the launches ... */
 template <int V>
-static int early_exit_step(qldpc_decoder *d, int ite_done, bool track_live, bool *stop)
+static int early_exit_launch(qldpc_decoder *d, int ite_done)
+{
+    int rc;
+    if ((rc = synd_pass<V>(d, d->d_sgn, 1)) || (rc = status_pass<V>(d, ite_done))) return rc;
+    return QLDPC_OK;
+}
+/* ... and the host's look at the count of the status pass launched last */
+template <int V>
+static int early_exit_poll(qldpc_decoder *d, int ite_done, bool track_live, bool *stop)
 {
     int rc;
     *stop = false;
-    if ((rc = synd_pass<V>(d, d->d_sgn, 1)) || (rc = status_pass<V>(d, ite_done))) return rc;
-    if (d->poll_every <= 0 || (ite_done % d->poll_every) != 0) return QLDPC_OK;
     int active = 1, left = 0;
     if ((rc = poll_active(d, &active, &left))) return rc;
     if (track_live) d->live_lanes = active * d->FG;
@@ -864,6 +872,15 @@ static int early_exit_step(qldpc_decoder *d, int ite_done, bool track_live, bool
         (d->compact_mode == 1 || (float)Gn <= d->compact_ratio * (float)d->G))
         return compact<V>(d, left);
     return QLDPC_OK;
+}
+template <int V>
+static int early_exit_step(qldpc_decoder *d, int ite_done, bool track_live, bool *stop)
+{
+    int rc;
+    *stop = false;
+    if ((rc = early_exit_launch<V>(d, ite_done))) return rc;
+    if (d->poll_every <= 0 || (ite_done % d->poll_every) != 0) return QLDPC_OK;
+    return early_exit_poll<V>(d, ite_done, track_live, stop);
 }
 
 template <int V>
@@ -901,23 +918,20 @@ struct live_groups {
     ~live_groups() { if (d->cur_gen == 0) d->G = saved; }      /* a run that compacted leaves the last generation's view, as a flooding run does */
 };
 
+/* The parts of a layered run: run_layered strings them together for one decoder, gang_run for several decoders in lockstep.
+ * All of them run with live_groups in place. */
+static inline bool layered_skip_clear(const qldpc_decoder *d) { return !d->msg_i8 && !d->freeze; }
+
+/* prologue: var_nodes = Y_N, messages = 0 where a sweep reads them before it writes them, the one-launch sweep's counters */
 template <int V>
-static int run_layered(qldpc_decoder *d)
+static int layered_begin(qldpc_decoder *d, bool *chain_out)
 {
-    int rc;
-    const int n_ite = d->cfg.n_ite;
-    /* A decoder sized for more frames than the call brought (the sessions' decoders take every batch up to max_blocks) runs its sweeps over the
-     * groups that hold frames only.  The layered schedule has no generations: d->G only sizes grids, copies and the status pass, the arrays are
-     * strided per group.  Empty groups were skipped inside the kernels before, but their workgroups were still dispatched -- 23 small launches per
-     * sweep each carrying up to 8 x the workgroups: the config-3 stream on session decoders sized for 512 blocks 15.7 -> 13.65 ms (sized for 256: 13.9 -> 13.5). */
-    live_groups live_guard(d);
     const size_t G = (size_t)d->G, FG = (size_t)d->FG;
     const size_t cell = d->msg_i8 ? 1 : sizeof(float);
     HIPCHK(hipMemcpyAsync(d->d_a, d->msg_i8 ? (const void *)d->d_llr8 : (const void *)d->d_llr, G * d->N * FG * cell, hipMemcpyDeviceToDevice, d->stream));   /* var_nodes = Y_N */
     /* messages = 0: fp32 sweeps that never mask a store (freeze = 0) do not clear and re-read E rows per frame group for that -- sweep 0's
      * layer kernels take the messages as zero and write every row (config 5: 0.92 GB not written and not read per decode) */
-    const bool skip_clear = !d->msg_i8 && !d->freeze;
-    if (!skip_clear) HIPCHK(hipMemsetAsync(d->d_b, 0, G * d->E * FG * cell, d->stream));
+    if (!layered_skip_clear(d)) HIPCHK(hipMemsetAsync(d->d_b, 0, G * d->E * FG * cell, d->stream));
     bool chain = false;
     if constexpr (V == 1) {
         chain = d->chain != 0;
@@ -930,34 +944,42 @@ static int run_layered(qldpc_decoder *d)
             }
         }
     }
-    int ite = 0;
-    for (; ite < n_ite; ite++) {
-        {
-            prof_scope ps(d, d->remap_src ? KS_LAYER_REMAP : KS_LAYER, bytes_layer(d), moved_layer(d));
-            d->layer_first = (skip_clear && ite == 0) ? 1 : 0;
-            if (chain) {
-                HIPCHK(hipMemsetAsync(d->d_chain_ctl + QC_CTL_SHARD0, 0, sizeof(int) * 32 * QC_SHARDS, d->stream));      /* the ticket counters; the fault word stays */
-                qldpc_launch_layer_chain(d, ite);
-                LAUNCHCHK();
-            }
-            else
-                for (int l = 0; l < d->n_layers; l++)
-                    for (auto &b : d->layer_buckets[(size_t)l]) { qldpc_launch_layer<V>(d, b); LAUNCHCHK(); }
-            d->remap_src = nullptr; d->remap_msg = nullptr;      /* every message row is in the current generation's layout now */
-        }
-        if (d->cfg.enable_syndrome) {
-            {
-                prof_scope ps(d, KS_SYND, 0.0, (double)d->N * 4.0 * d->n_frames);      /* the sign ballots of the posteriors: N rows read */
-                if ((rc = post_ballots<V>(d))) return rc;
-            }
-            /* the live lanes are followed only where the run can compact (compact = 1).  A compaction never comes before sweep 0 is done, so the
-             * "messages are zero" shortcut of that sweep and the remap read never meet. */
-            bool stop;
-            if ((rc = early_exit_step<V>(d, ite + 1, d->compact_mode != 2, &stop))) return rc;
-            if (stop) { ite++; break; }
-        }
+    *chain_out = chain;
+    return QLDPC_OK;
+}
+
+/* sweep `ite`: a launch per layer and bucket, or the one launch of the chain */
+template <int V>
+static int layered_sweep(qldpc_decoder *d, int ite, bool chain)
+{
+    prof_scope ps(d, d->remap_src ? KS_LAYER_REMAP : KS_LAYER, bytes_layer(d), moved_layer(d));
+    d->layer_first = (layered_skip_clear(d) && ite == 0) ? 1 : 0;
+    if (chain) {
+        HIPCHK(hipMemsetAsync(d->d_chain_ctl + QC_CTL_SHARD0, 0, sizeof(int) * 32 * QC_SHARDS, d->stream));      /* the ticket counters; the fault word stays */
+        qldpc_launch_layer_chain(d, ite);
+        LAUNCHCHK();
     }
-    d->last_iters = std::min(ite, n_ite);
+    else
+        for (int l = 0; l < d->n_layers; l++)
+            for (auto &b : d->layer_buckets[(size_t)l]) { qldpc_launch_layer<V>(d, b); LAUNCHCHK(); }
+    d->remap_src = nullptr; d->remap_msg = nullptr;      /* every message row is in the current generation's layout now */
+    return QLDPC_OK;
+}
+
+/* after a sweep with the syndrome test on: the sign ballots of the posteriors the test reads (N rows read) */
+template <int V>
+static int layered_test_ballots(qldpc_decoder *d)
+{
+    prof_scope ps(d, KS_SYND, 0.0, (double)d->N * 4.0 * d->n_frames);
+    return post_ballots<V>(d);
+}
+
+/* epilogue: `ite` sweeps were issued; the closing ballots, and the one-launch sweep's fault word */
+template <int V>
+static int layered_end(qldpc_decoder *d, int ite, bool chain)
+{
+    int rc;
+    d->last_iters = std::min(ite, d->cfg.n_ite);
     if ((rc = post_ballots<V>(d))) return rc;
     if (chain) {
         /* a wait that ran into its bound left the fault word set: the decode cannot be trusted; say so and go back to a launch per layer */
@@ -972,6 +994,33 @@ static int run_layered(qldpc_decoder *d)
         }
     }
     return QLDPC_OK;
+}
+
+template <int V>
+static int run_layered(qldpc_decoder *d)
+{
+    int rc;
+    const int n_ite = d->cfg.n_ite;
+    /* A decoder sized for more frames than the call brought (the sessions' decoders take every batch up to max_blocks) runs its sweeps over the
+     * groups that hold frames only.  The layered schedule has no generations: d->G only sizes grids, copies and the status pass, the arrays are
+     * strided per group.  Empty groups were skipped inside the kernels before, but their workgroups were still dispatched -- 23 small launches per
+     * sweep each carrying up to 8 x the workgroups: the config-3 stream on session decoders sized for 512 blocks 15.7 -> 13.65 ms (sized for 256: 13.9 -> 13.5). */
+    live_groups live_guard(d);
+    bool chain = false;
+    if ((rc = layered_begin<V>(d, &chain))) return rc;
+    int ite = 0;
+    for (; ite < n_ite; ite++) {
+        if ((rc = layered_sweep<V>(d, ite, chain))) return rc;
+        if (d->cfg.enable_syndrome) {
+            if ((rc = layered_test_ballots<V>(d))) return rc;
+            /* the live lanes are followed only where the run can compact (compact = 1).  A compaction never comes before sweep 0 is done, so the
+             * "messages are zero" shortcut of that sweep and the remap read never meet. */
+            bool stop;
+            if ((rc = early_exit_step<V>(d, ite + 1, d->compact_mode != 2, &stop))) return rc;
+            if (stop) { ite++; break; }
+        }
+    }
+    return layered_end<V>(d, ite, chain);
 }
 
 /*
@@ -1008,8 +1057,9 @@ static int run_vlayered(qldpc_decoder *d)
     return post_ballots<V>(d);
 }
 
+/* what every FRAMES run starts and ends with (run_v; gang_run per member) */
 template <int V>
-static int run_v(qldpc_decoder *d)
+static int run_begin(qldpc_decoder *d)
 {
     view_reset(d);
     gen0_capture(d);
@@ -1020,9 +1070,13 @@ static int run_v(qldpc_decoder *d)
         hipLaunchKernelGGL((qk_status_init<V>), dim3((unsigned)d->G), dim3(64), 0, d->stream, d->d_unsat, d->d_done, d->d_depth, d->d_iters, d->n_frames, d->cfg.n_ite, d->d_work, d->d_active);
         LAUNCHCHK();
     }
-    int rc = d->cfg.schedule == QLDPC_SCHED_FLOODING ? run_flooding<V>(d) : (d->cfg.schedule == QLDPC_SCHED_VLAYERED ? run_vlayered<V>(d) : run_layered<V>(d));
-    if (rc) return rc;
+    return QLDPC_OK;
+}
+template <int V>
+static int run_end(qldpc_decoder *d)
+{
     /* success flag: syndrome of the hard decision, in every generation (a frame's result lives where it converged) */
+    int rc = QLDPC_OK;
     const int last = d->cur_gen;
     for (int k = 0; k <= last && !rc; k++) {
         use_gen(d, k);
@@ -1031,6 +1085,16 @@ static int run_v(qldpc_decoder *d)
     }
     use_gen(d, last);
     return rc;
+}
+
+template <int V>
+static int run_v(qldpc_decoder *d)
+{
+    int rc;
+    if ((rc = run_begin<V>(d))) return rc;
+    rc = d->cfg.schedule == QLDPC_SCHED_FLOODING ? run_flooding<V>(d) : (d->cfg.schedule == QLDPC_SCHED_VLAYERED ? run_vlayered<V>(d) : run_layered<V>(d));
+    if (rc) return rc;
+    return run_end<V>(d);
 }
 
 /* fn(origin, final_mask, n_slots) once per generation, with that generation's view in place: which slots hold a frame's result
@@ -1256,6 +1320,235 @@ extern "C" int qldpc_run(qldpc_decoder *d)
     rc = with_v(d, [&](auto v) { return run_v<v()>(d); });
     if (rc == QLDPC_OK) d->ran = 1;
     return rc;
+}
+
+/* ------------------------------------------------------------------ decoder gangs ------------ */
+
+/* the member's qk_gang_entry array: what its solo layer launches pass as arguments, written once */
+static int gang_entries(qldpc_decoder *d)
+{
+    if (d->d_gang) return QLDPC_OK;
+    std::vector<qk_gang_entry> h;
+    d->gang_off.clear();
+    for (int l = 0; l < d->n_layers; l++) {
+        d->gang_off.push_back((int)h.size());
+        for (auto &b : d->layer_buckets[(size_t)l]) {
+            qk_gang_entry e{};
+            qk_gang_set(e.post, d->d_a); qk_gang_set(e.msg, d->d_b); qk_gang_set(e.done, d->d_done);
+            qk_gang_set(e.list, b.d_list); qk_gang_set(e.rec, b.cap > 0 ? b.d_rec : (int *)nullptr);
+            qk_gang_set(e.cn_ptr, d->d_cn_ptr); qk_gang_set(e.cn_var, d->d_cn_var);
+            e.group_stride = (size_t)d->E * d->FG;
+            e.n = b.n; e.rec_stride = QK_REC_HDR + b.cap; e.N = d->N; e.M = d->M;
+            e.rule = rule_of(d); e.freeze = d->freeze;
+            h.push_back(e);
+        }
+    }
+    HIPCHK(hipSetDevice(d->device));
+    int rc = dev_alloc(d, &d->d_gang, h.size());
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(d->d_gang, h.data(), h.size() * sizeof(qk_gang_entry), hipMemcpyHostToDevice));
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_gang_create(qldpc_decoder *const *members, int n, qldpc_gang **out)
+{
+    if (!out) return QLDPC_EINVAL;
+    *out = nullptr;
+    if (!members || n < 1 || n > QLDPC_GANG_MAX_MEMBERS) { qldpc_set_error("qldpc_gang_create: %d members (1 .. %d)", n, QLDPC_GANG_MAX_MEMBERS); return QLDPC_EINVAL; }
+    for (int i = 0; i < n; i++) {
+        const qldpc_decoder *d = members[i];
+        if (!d) { qldpc_set_error("qldpc_gang_create: member %d is NULL", i); return QLDPC_EINVAL; }
+        for (int j = 0; j < i; j++) if (members[j] == d) { qldpc_set_error("qldpc_gang_create: member %d is member %d again", i, j); return QLDPC_EINVAL; }
+        const char *why = nullptr;
+        if (d->engine != QLDPC_ENGINE_FRAMES) why = "not on the FRAMES engine";
+        else if (d->cfg.schedule != QLDPC_SCHED_HLAYERED) why = "schedule is not QLDPC_SCHED_HLAYERED";
+        else if (d->msg_i8 || d->msg_half) why = "messages are not fp32";
+        else if (d->V != 1) why = "frame groups are not 64 wide (frames_per_lane != 1)";
+        else if (d->compact_mode != 2) why = "active-frame compaction is enabled";
+        else if (d->chain || d->cfg.layer_chain == 1) why = "the one-launch sweep (layer_chain) is in use";
+        if (why) { qldpc_set_error("qldpc_gang_create: member %d: %s", i, why); return QLDPC_EUNSUPPORTED; }
+        if (d->device != members[0]->device) { qldpc_set_error("qldpc_gang_create: member %d is on device %d, member 0 on device %d", i, d->device, members[0]->device); return QLDPC_EINVAL; }
+        if (d->cfg.n_ite != members[0]->cfg.n_ite || !d->cfg.enable_syndrome != !members[0]->cfg.enable_syndrome) {
+            qldpc_set_error("qldpc_gang_create: member %d has n_ite=%d, enable_syndrome=%d, member 0 has %d, %d (a gang sweeps in lockstep)", i, d->cfg.n_ite, d->cfg.enable_syndrome,
+                            members[0]->cfg.n_ite, members[0]->cfg.enable_syndrome);
+            return QLDPC_EINVAL;
+        }
+    }
+    qldpc_gang *g = new (std::nothrow) qldpc_gang();
+    if (!g) return QLDPC_ENOMEM;
+    g->device = members[0]->device;
+    g->stream = members[0]->stream;
+    for (int i = 0; i < n; i++) {
+        qldpc_decoder *d = members[i];
+        int rc = gang_entries(d);
+        if (rc) { delete g; return rc; }
+        g->m.push_back(d);
+        int nb = 0;
+        for (int l = 0; l < d->n_layers; l++) {
+            const auto &bs = d->layer_buckets[(size_t)l];
+            for (size_t k = 0; k < bs.size(); k++) gang_plan_add(g->steps, l, bs[k].cap, family_of(d->cfg.rule), d->layer_cst, gang_slot{i, d->gang_off[(size_t)l] + (int)k, bs[k].n});
+            nb += (int)bs.size();
+        }
+        g->buckets.push_back(nb);
+    }
+    *out = g;
+    return QLDPC_OK;
+}
+
+extern "C" void qldpc_gang_free(qldpc_gang *g) { delete g; }
+
+extern "C" int qldpc_gang_set_stream(qldpc_gang *g, void *hip_stream)
+{
+    if (!g) return QLDPC_EINVAL;
+    g->stream = (hipStream_t)hip_stream;
+    for (auto *d : g->m) d->stream = g->stream;
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_gang_last_run_stats(qldpc_gang *g, long long out[4])
+{
+    if (!g || !out) return QLDPC_EINVAL;
+    for (int k = 0; k < 4; k++) out[k] = g->stats[k];
+    return QLDPC_OK;
+}
+
+/* the planning of qldpc_gang_create as a function of the codes alone: a check's bucket is the smallest of CN_CAPS that holds its degree, else 0 */
+extern "C" int qldpc_gang_plan(const qldpc_code *const *codes, const int *rule, const int *compressed, int n, int *steps, int *launches_per_sweep, int *solo_launches_per_sweep)
+{
+    if (!codes || !rule || n < 1 || n > QLDPC_GANG_MAX_MEMBERS) { qldpc_set_error("qldpc_gang_plan: %d codes (1 .. %d), codes and rules must be given", n, QLDPC_GANG_MAX_MEMBERS); return QLDPC_EINVAL; }
+    gang_steps plan;
+    int solo = 0;
+    for (int i = 0; i < n; i++) {
+        const qldpc_code *c = codes[i];
+        if (!c || rule[i] < QLDPC_RULE_MS || rule[i] > QLDPC_RULE_AMS_MINSTAR) { qldpc_set_error("qldpc_gang_plan: code %d: NULL or rule out of range", i); return QLDPC_EINVAL; }
+        const int fam = family_of(rule[i]), cst = compressed && compressed[i] ? 1 : 0;
+        if (cst && ((fam != QK_FAM_MS && fam != QK_FAM_AMS) || c->max_dc > 32)) {
+            qldpc_set_error("qldpc_gang_plan: code %d: the compressed check state takes the min-sum and AMS rules and check degrees <= 32", i);
+            return QLDPC_EINVAL;
+        }
+        for (int l = 0; l < c->n_layers; l++) {
+            int cnt[5] = {0, 0, 0, 0, 0};
+            for (int k = c->layer_ptr[l]; k < c->layer_ptr[l + 1]; k++) {
+                const int id = c->layer_order[k], deg = c->cn_ptr[id + 1] - c->cn_ptr[id];
+                int b = 4;
+                for (int q = 0; q < 4; q++) if (deg <= CN_CAPS[q]) { b = q; break; }
+                cnt[b]++;
+            }
+            for (int q = 0; q < 5; q++)
+                if (cnt[q]) { gang_plan_add(plan, l, q < 4 ? CN_CAPS[q] : 0, fam, cst, gang_slot{i, 0, cnt[q]}); solo++; }
+        }
+    }
+    int launches = 0;
+    for (auto &st : plan) launches += (int)st.size();
+    if (steps) *steps = (int)plan.size();
+    if (launches_per_sweep) *launches_per_sweep = launches;
+    if (solo_launches_per_sweep) *solo_launches_per_sweep = solo;
+    return QLDPC_OK;
+}
+
+/* one class of one step for the members still taking part, QK_GANG_SLOTS to a launch */
+static int gang_launch_class(qldpc_gang *g, const gang_class &c, const bool *live, bool first_sweep)
+{
+    qk_gang_args a;
+    int k = 0;
+    auto flush = [&]() -> int {
+        for (int j = k; j < QK_GANG_SLOTS; j++) { a.entry[j] = a.entry[0]; a.synd[j] = a.synd[0]; a.prefix[j + 1] = a.prefix[k]; }
+        int rc = qldpc_launch_layer_gang(g->stream, c.cap, c.fam, c.cst, a, (unsigned)a.prefix[k]);
+        if (rc) return rc;
+        LAUNCHCHK();
+        g->stats[1]++;
+        k = 0;
+        return QLDPC_OK;
+    };
+    for (const auto &s : c.slots) {
+        if (!live[s.member]) continue;
+        const qldpc_decoder *d = g->m[(size_t)s.member];
+        const long long blocks = (long long)grid_x(s.n, 1) * d->G;      /* d->G: the groups that hold frames (live_groups) */
+        if (blocks > 0x7fffffffLL) { qldpc_set_error("qldpc_gang_run: member %d: %lld workgroups in one step", s.member, blocks); return QLDPC_ESIZE; }
+        if (k > 0 && (k == QK_GANG_SLOTS || (long long)a.prefix[k] + blocks > 0x7fffffffLL)) { int rc = flush(); if (rc) return rc; }
+        if (k == 0) { a.prefix[0] = 0; a.first = 0u; }
+        qk_gang_set(a.entry[k], d->d_gang + s.entry);
+        qk_gang_set(a.synd[k], target_synd(d));
+        a.prefix[k + 1] = a.prefix[k] + (int)blocks;
+        if (first_sweep && layered_skip_clear(d)) a.first |= 1u << k;      /* sweep 0: the member's messages are taken as zero (layered_sweep) */
+        k++;
+    }
+    return k > 0 ? flush() : QLDPC_OK;
+}
+
+extern "C" int qldpc_gang_run(qldpc_gang *g, const unsigned char *take)
+{
+    if (!g) return QLDPC_EINVAL;
+    const int n = (int)g->m.size();
+    bool live[QLDPC_GANG_MAX_MEMBERS], in[QLDPC_GANG_MAX_MEMBERS];
+    int left = 0, first_in = -1;
+    for (int i = 0; i < n; i++) {
+        in[i] = live[i] = !take || take[i];
+        if (!in[i]) continue;
+        if (!g->m[(size_t)i]->loaded) { qldpc_set_error("qldpc_gang_run: member %d has nothing loaded", i); return QLDPC_ESTATE; }
+        if (first_in < 0) first_in = i;
+        left++;
+    }
+    for (int k = 0; k < 4; k++) g->stats[k] = 0;
+    if (!left) return QLDPC_OK;
+    HIPCHK(hipSetDevice(g->device));
+    int rc;
+    /* one stream for the whole gang: a member that was moved to another stream since is waited for there and brought back */
+    for (int i = 0; i < n; i++) {
+        qldpc_decoder *d = g->m[(size_t)i];
+        if (in[i] && d->stream != g->stream) { HIPCHK(hipStreamSynchronize(d->stream)); d->stream = g->stream; }
+    }
+    const int n_ite = g->m[(size_t)first_in]->cfg.n_ite;
+    const bool synd = g->m[(size_t)first_in]->cfg.enable_syndrome != 0;
+    /* the host looks at the mailboxes every p sweeps, p = the smallest poll_every a member asks for; none asks: every sweep is issued and the
+     * kernels return early for converged groups, as in a small solo run */
+    int p = 0;
+    std::optional<live_groups> lg[QLDPC_GANG_MAX_MEMBERS];
+    int swept[QLDPC_GANG_MAX_MEMBERS];
+    for (int i = 0; i < n; i++) {
+        if (!in[i]) continue;
+        qldpc_decoder *d = g->m[(size_t)i];
+        if (d->poll_every > 0 && (p == 0 || d->poll_every < p)) p = d->poll_every;
+        bool chain;
+        if ((rc = run_begin<1>(d))) return rc;
+        lg[i].emplace(d);
+        if ((rc = layered_begin<1>(d, &chain))) return rc;
+        swept[i] = 0;
+    }
+    int ite = 0;
+    for (; ite < n_ite && left > 0; ite++) {
+        {
+            qldpc_decoder *lead = nullptr;
+            double bytes = 0.0, moved = 0.0;
+            for (int i = 0; i < n; i++)
+                if (live[i]) { qldpc_decoder *d = g->m[(size_t)i]; if (!lead) lead = d; bytes += bytes_layer(d); moved += moved_layer(d); g->stats[2] += g->buckets[(size_t)i]; swept[i] = ite + 1; }
+            prof_scope ps(lead, KS_LAYER_GANG, bytes, moved);      /* one record per sweep, as KS_LAYER, on the first member taking part */
+            for (const auto &step : g->steps)
+                for (const auto &c : step)
+                    if ((rc = gang_launch_class(g, c, live, ite == 0))) return rc;
+            g->stats[0]++;
+        }
+        if (!synd) continue;
+        for (int i = 0; i < n; i++)
+            if (live[i] && ((rc = layered_test_ballots<1>(g->m[(size_t)i])) || (rc = early_exit_launch<1>(g->m[(size_t)i], ite + 1)))) return rc;
+        if (p <= 0 || ((ite + 1) % p) != 0) continue;
+        for (int i = 0; i < n; i++) {
+            if (!live[i]) continue;
+            bool stop;
+            if ((rc = early_exit_poll<1>(g->m[(size_t)i], ite + 1, false, &stop))) return rc;
+            if (stop) { live[i] = false; left--; }
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        if (!in[i]) continue;
+        qldpc_decoder *d = g->m[(size_t)i];
+        if (swept[i] < (int)g->stats[0]) g->stats[3]++;      /* left before the last sweep */
+        if ((rc = layered_end<1>(d, swept[i], false))) return rc;
+        lg[i].reset();
+        if ((rc = run_end<1>(d))) return rc;
+        d->ran = 1;
+    }
+    return QLDPC_OK;
 }
 
 /* ------------------------------------------------------------------ load --------------------- */

@@ -15,9 +15,10 @@
 #include "qldpc_hip.h"
 #include "qldpc_kernels.h"
 #include "qldpc_kernels_i8.h"
+#include "qldpc_kernels_gang.h"
 
-enum { KS_CN = 0, KS_VN, KS_LAYER, KS_SYND, KS_STATUS, KS_LOAD, KS_FETCH, KS_VLAYER, KS_LAYER_REMAP, KS_COMPACT_ROWS, KS_COUNT };
-static const char *const ks_names[KS_COUNT] = {"cn_update", "vn_update", "layer_update", "syndrome", "status", "load", "fetch", "vn_vlayer", "layer_update_remap", "compact_rows"};
+enum { KS_CN = 0, KS_VN, KS_LAYER, KS_SYND, KS_STATUS, KS_LOAD, KS_FETCH, KS_VLAYER, KS_LAYER_REMAP, KS_COMPACT_ROWS, KS_LAYER_GANG, KS_COUNT };
+static const char *const ks_names[KS_COUNT] = {"cn_update", "vn_update", "layer_update", "syndrome", "status", "load", "fetch", "vn_vlayer", "layer_update_remap", "compact_rows", "layer_update_gang"};
 
 struct prof_rec { int kind; double bytes, moved; hipEvent_t a, b; };
 
@@ -63,6 +64,9 @@ struct qldpc_decoder {
     /* one launch per sweep for small batches (qldpc_kernels_chain.h): execution order, per-edge {dv, rank}, per-VN version counters, ticket / fault words */
     int layer_cst;      /* layered min-sum keeps {cst1, cst2} per check and two ballot words per edge instead of dc messages (qldpc_kernels_cst.h) */
     int chain, chain_blocks, chain_lds; int *d_chain_order, *d_chain_dep, *d_chain_ver, *d_chain_ctl;
+    /* decoder gangs (qldpc_kernels_gang.h): what a solo layer launch passes as arguments, once per (layer, bucket), written when the decoder first
+     * joins a gang; the entry of layer_buckets[l][k] is d_gang[gang_off[l] + k] */
+    qk_gang_entry *d_gang; std::vector<int> gang_off;
     int layer_first;                 /* layered fp32 run, sweep 0, messages not frozen: the layer kernels treat the messages as zero instead of reading a cleared array */
     /* state */
     float *d_llr, *d_a, *d_b;        /* flooding: a = v2c, b = c2v ; layered: a = post, b = msg */
@@ -159,6 +163,32 @@ static inline int want_ballots(const qldpc_decoder *d, int mode)
     if (mode == QK_VN_POST) return 1 | (d->post_closes_run ? 2 : 0);      /* bit 1: skip groups that converged as a whole (their ballots are final) */
     return d->cfg.enable_syndrome ? 1 : 0;
 }
+
+/*
+ * A gang of horizontal-layered decoders (qldpc.h "decoder gangs").  steps[s] = the kernel classes of colour step s, each with the members'
+ * buckets that fall into it (in member order): one launch per class and QK_GANG_SLOTS live members.  Built once by qldpc_gang_create with the
+ * planner qldpc_gang_plan uses (gang_plan_add); a run only filters by the members still taking part.
+ */
+struct gang_slot { int member, entry, n; };      /* entry: index into the member's d_gang */
+struct gang_class { int cap, fam, cst; std::vector<gang_slot> slots; };
+typedef std::vector<std::vector<gang_class>> gang_steps;
+static inline void gang_plan_add(gang_steps &steps, int step, int cap, int fam, int cst, gang_slot s)
+{
+    if ((int)steps.size() <= step) steps.resize((size_t)step + 1);
+    for (auto &c : steps[(size_t)step])
+        if (c.cap == cap && c.fam == fam && c.cst == cst) { c.slots.push_back(s); return; }
+    steps[(size_t)step].push_back(gang_class{cap, fam, cst, {s}});
+}
+struct qldpc_gang {
+    std::vector<qldpc_decoder *> m;
+    gang_steps steps;
+    std::vector<int> buckets;        /* per member: layer launches of a sweep on its own */
+    int device;
+    hipStream_t stream;
+    long long stats[4];
+};
+/* one class of one colour step for up to QK_GANG_SLOTS members (qldpc_launch_gang.hip) */
+int qldpc_launch_layer_gang(hipStream_t stream, int cap, int fam, int cst, const qk_gang_args &a, unsigned grid);
 
 /* kernel-launch dispatchers (qldpc_launch.hip); `first`: the check pass of iteration 0 in coded-LLR mode */
 template <int V> void qldpc_launch_cn(qldpc_decoder *d, const bucket &b, bool first);

@@ -709,21 +709,17 @@ __global__ __launch_bounds__(QK_THREADS) void qk_vn_flood(const MT *__restrict__
 template <bool REMAP> struct qk_layer_remap {};
 template <> struct qk_layer_remap<true> { const float *msg_old; const int *src; };
 
-template <int V, int DCMAX, int FAM, bool REMAP = false>
-__global__ __launch_bounds__(QK_THREADS) void qk_cn_layer(float *__restrict__ post, float *__restrict__ msg,
-                                                          const int *__restrict__ list, int n_list,
-                                                          const int *__restrict__ cn_ptr, const int *__restrict__ cn_var,
-                                                          int N, size_t group_stride, const u64 *__restrict__ done, qk_rule rule, int freeze, const u64 *__restrict__ synd, int M,
-                                                          int first /* sweep 0: messages are all zero -- they are not read (and the host has not cleared the array) */,
-                                                          const int *__restrict__ rec = nullptr, int rec_stride = 0 /* bucket::d_rec (DCMAX > 0 only) */,
-                                                          qk_layer_remap<REMAP> remap = qk_layer_remap<REMAP>{})
+/* The update of list entry i (< n_list, wave-uniform) for group g: the whole kernel behind its grid mapping, shared by qk_cn_layer (a launch per
+ * decoder: g = blockIdx.y, i from blockIdx.x) and qk_cn_layer_gang (qldpc_kernels_gang.h: several decoders in one 1-D grid), so that both run the
+ * same instructions on a check. */
+template <int V, int DCMAX, int FAM, bool REMAP>
+__device__ __forceinline__ void qk_cn_layer_body(const int g, const int lane, const int i, float *__restrict__ post, float *__restrict__ msg,
+                                                 const int *__restrict__ list,
+                                                 const int *__restrict__ cn_ptr, const int *__restrict__ cn_var,
+                                                 int N, size_t group_stride, const u64 *__restrict__ done, qk_rule rule, int freeze, const u64 *__restrict__ synd, int M,
+                                                 int first, const int *__restrict__ rec, int rec_stride, qk_layer_remap<REMAP> remap)
 {
     constexpr int FG = 64 * V;
-    const int g = blockIdx.y;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i = blockIdx.x * QK_WAVES + wave;
-    if (i >= n_list) return;
     /* with records the wave's check, first edge, degree and VNs arrive in one scalar round trip, asked for together with the done words */
     int c, b, deg;
     [[maybe_unused]] int rvn[DCMAX > 0 ? DCMAX : 1];
@@ -843,6 +839,23 @@ __global__ __launch_bounds__(QK_THREADS) void qk_cn_layer(float *__restrict__ po
             qk_store_masked<V>(pg + (size_t)cn_var[b + k] * FG, p, frozen, any_frozen);
         }
     }
+}
+
+template <int V, int DCMAX, int FAM, bool REMAP = false>
+__global__ __launch_bounds__(QK_THREADS) void qk_cn_layer(float *__restrict__ post, float *__restrict__ msg,
+                                                          const int *__restrict__ list, int n_list,
+                                                          const int *__restrict__ cn_ptr, const int *__restrict__ cn_var,
+                                                          int N, size_t group_stride, const u64 *__restrict__ done, qk_rule rule, int freeze, const u64 *__restrict__ synd, int M,
+                                                          int first /* sweep 0: messages are all zero -- they are not read (and the host has not cleared the array) */,
+                                                          const int *__restrict__ rec = nullptr, int rec_stride = 0 /* bucket::d_rec (DCMAX > 0 only) */,
+                                                          qk_layer_remap<REMAP> remap = qk_layer_remap<REMAP>{})
+{
+    const int g = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int i = blockIdx.x * QK_WAVES + wave;
+    if (i >= n_list) return;
+    qk_cn_layer_body<V, DCMAX, FAM, REMAP>(g, lane, i, post, msg, list, cn_ptr, cn_var, N, group_stride, done, rule, freeze, synd, M, first, rec, rec_stride, remap);
 }
 
 /* ballots of an explicit posterior array (layered schedule): sgn = signbit, hard = !(p >= 0) */

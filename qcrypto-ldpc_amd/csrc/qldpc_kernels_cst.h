@@ -52,20 +52,17 @@ template <> struct qk_cst_of<QK_FAM_AMS> {
 
 /* REMAP: the first sweep after a compaction (qldpc_kernels_compact.h), as in qk_cn_layer: the lane's frame reads its four state words from the old
  * generation's array remap.msg_old through the slot map (a per-lane base pointer) and the rows are written to st in the new layout; never sweep 0. */
-template <int DCMAX, int FAM, bool REMAP = false>
-__global__ __launch_bounds__(QK_THREADS) void qk_cn_layer_cst(float *__restrict__ post, float *__restrict__ st,
-                                                              const int *__restrict__ list, int n_list,
-                                                              const int *__restrict__ cn_ptr, const int *__restrict__ cn_var,
-                                                              int N, size_t group_stride, const u64 *__restrict__ done, qk_rule rule, const u64 *__restrict__ synd, int M,
-                                                              int first, const int *__restrict__ rec, int rec_stride, qk_layer_remap<REMAP> remap = qk_layer_remap<REMAP>{})
+/* the update of list entry i (< n_list, wave-uniform) for group g: shared by qk_cn_layer_cst and qk_cn_layer_cst_gang (qldpc_kernels_gang.h), as
+ * qk_cn_layer_body is */
+template <int DCMAX, int FAM, bool REMAP>
+__device__ __forceinline__ void qk_cn_layer_cst_body(const int g, const int lane, const int i, float *__restrict__ post, float *__restrict__ st,
+                                                     const int *__restrict__ list,
+                                                     const int *__restrict__ cn_ptr, const int *__restrict__ cn_var,
+                                                     int N, size_t group_stride, const u64 *__restrict__ done, qk_rule rule, const u64 *__restrict__ synd, int M,
+                                                     int first, const int *__restrict__ rec, int rec_stride, qk_layer_remap<REMAP> remap)
 {
     static_assert(DCMAX > 0 && DCMAX <= 32, "one mask bit per edge");
     static_assert(FAM == QK_FAM_MS || FAM == QK_FAM_AMS, "rules whose messages take two magnitudes per check");
-    const int g = blockIdx.y;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i = blockIdx.x * QK_WAVES + wave;
-    if (i >= n_list) return;
     float *pg = post + (size_t)g * N * 64 + lane;
 
     /* what this wave works on: one aligned record per list entry (bucket::d_rec) asked for together with the group's done word -- one
@@ -125,6 +122,21 @@ __global__ __launch_bounds__(QK_THREADS) void qk_cn_layer_cst(float *__restrict_
     __builtin_nontemporal_store(qk_cst_of<FAM>::c2(acc), crow + 64);
     __builtin_nontemporal_store(neg, reinterpret_cast<uint32_t *>(crow + 128));
     __builtin_nontemporal_store(took1, reinterpret_cast<uint32_t *>(crow + 192));
+}
+
+template <int DCMAX, int FAM, bool REMAP = false>
+__global__ __launch_bounds__(QK_THREADS) void qk_cn_layer_cst(float *__restrict__ post, float *__restrict__ st,
+                                                              const int *__restrict__ list, int n_list,
+                                                              const int *__restrict__ cn_ptr, const int *__restrict__ cn_var,
+                                                              int N, size_t group_stride, const u64 *__restrict__ done, qk_rule rule, const u64 *__restrict__ synd, int M,
+                                                              int first, const int *__restrict__ rec, int rec_stride, qk_layer_remap<REMAP> remap = qk_layer_remap<REMAP>{})
+{
+    const int g = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int i = blockIdx.x * QK_WAVES + wave;
+    if (i >= n_list) return;
+    qk_cn_layer_cst_body<DCMAX, FAM, REMAP>(g, lane, i, post, st, list, cn_ptr, cn_var, N, group_stride, done, rule, synd, M, first, rec, rec_stride, remap);
 }
 
 #endif /* QLDPC_KERNELS_CST_H */

@@ -65,6 +65,7 @@ struct qldpc_recon {
     long created;                   /* entries built so far (tests: nothing is built after a preload) */
     recon_lane lane[RECON_LANES];
     int profiling;
+    int gang;                       /* QLDPC_RECON_GANG=1 when the session was made: Bob-side calls with several layered rate groups decode in rounds, one gang run each (run_call_gang) */
 };
 
 #define CRC_POLY 0xEDB88320u      /* CRC-32 (IEEE 802.3), reflected */
@@ -403,6 +404,8 @@ extern "C" int qldpc_recon_create(const qldpc_recon_cfg *cfg, qldpc_recon **out)
     r->keep = mothers + 6;
     r->created = 0;
     r->profiling = 0;
+    r->gang = 0;
+    if (const char *env = getenv("QLDPC_RECON_GANG")) r->gang = atoi(env) == 1;
     memset(r->lane, 0, sizeof(r->lane));
     if (hipSetDevice(cfg->device) != hipSuccess) { delete r; return QLDPC_EHIP; }
     /* the session's own streams: nothing of it runs on the null stream, so a second session or other work on the device does not
@@ -755,7 +758,35 @@ static int job_stage(lane_run *L, recon_job &j, hipStream_t cs)
     return QLDPC_OK;
 }
 
-static int job_launch(lane_run *L, recon_job &j, hipStream_t cs)
+/* the three parts of a job on the compute stream: load (after its staging has arrived), run, fetch + verify + results on their way back.  job_launch is
+ * the three in order; a gang round (run_call_gang) loads every member, makes one gang run in place of the members' job_run, and fetches every member. */
+static int job_load(lane_run *L, recon_job &j, hipStream_t cs)
+{
+    recon_entry *e = j.e;
+    stage_set *st = j.st;
+    hipStream_t s = L->lane->stream;
+    const int n = (int)j.idx.size(), K = e->K, M = e->M;
+    const int Wk = K / 32, Wm = (M + 31) / 32;
+    int rc;
+    uint32_t *d_keys = st->d_in, *d_disc = d_keys + (size_t)n * Wk;
+    float *d_mag = reinterpret_cast<float *>(d_disc + (size_t)n * Wm);
+    int *d_nch = reinterpret_cast<int *>(d_mag + n);
+    if (cs != s) HIPCHK(hipStreamWaitEvent(s, st->ev_in, 0));
+    if (L->call->bob) {
+        if ((rc = qldpc_decoder_set_stream(e->dec, (void *)s))) return rc;
+        if ((rc = qldpc_load_bits_short_dev(e->dec, st->d_bits, d_mag, e->d_cls, d_nch, n))) return rc;
+        if (j.any_punct && (rc = qldpc_load_erasures_dev(e->dec, st->d_erase, n))) return rc;
+    }
+    return QLDPC_OK;
+}
+
+static int job_run(lane_run *L, recon_job &j)
+{
+    if (L->call->bob) return qldpc_run(j.e->dec);      /* the host polls the decoder's early-exit mailbox in here */
+    return QLDPC_OK;                                   /* Alice: the encoder runs in job_fetch, with what reads its codewords */
+}
+
+static int job_fetch(lane_run *L, recon_job &j, hipStream_t cs)
 {
     recon_entry *e = j.e;
     stage_set *st = j.st;
@@ -767,13 +798,8 @@ static int job_launch(lane_run *L, recon_job &j, hipStream_t cs)
     float *d_mag = reinterpret_cast<float *>(d_disc + (size_t)n * Wm);
     int *d_nch = reinterpret_cast<int *>(d_mag + n), *d_np = d_nch + n;
     uint32_t *d_crc = reinterpret_cast<uint32_t *>(d_np + n);
-    if (cs != s) HIPCHK(hipStreamWaitEvent(s, st->ev_in, 0));
     size_t res_words;
     if (L->call->bob) {
-        if ((rc = qldpc_decoder_set_stream(e->dec, (void *)s))) return rc;
-        if ((rc = qldpc_load_bits_short_dev(e->dec, st->d_bits, d_mag, e->d_cls, d_nch, n))) return rc;
-        if (j.any_punct && (rc = qldpc_load_erasures_dev(e->dec, st->d_erase, n))) return rc;
-        if ((rc = qldpc_run(e->dec))) return rc;      /* the host polls the decoder's early-exit mailbox in here */
         if ((rc = qldpc_fetch_packed_dev(e->dec, e->d_out))) return rc;
         if ((rc = qldpc_fetch_status_dev(e->dec, e->d_iters, e->d_ok))) return rc;
         uint32_t *res_keys = st->d_res;
@@ -795,6 +821,13 @@ static int job_launch(lane_run *L, recon_job &j, hipStream_t cs)
     }
     HIPCHK(hipMemcpyAsync(st->h_res, st->d_res, sizeof(uint32_t) * res_words, hipMemcpyDeviceToHost, cs));
     HIPCHK(hipEventRecord(st->ev_done, cs));
+    return QLDPC_OK;
+}
+
+static int job_launch(lane_run *L, recon_job &j, hipStream_t cs)
+{
+    int rc;
+    if ((rc = job_load(L, j, cs)) || (rc = job_run(L, j)) || (rc = job_fetch(L, j, cs))) return rc;
     return QLDPC_OK;
 }
 
@@ -858,13 +891,92 @@ static void lane_main(lane_run *L)
     L->rc = rc;
 }
 
+struct recon_group { recon_entry *e; std::vector<int> idx; double cost; };
+
+/*
+ * QLDPC_RECON_GANG=1, Bob's side, two or more rate groups with layered decoders: the call runs on ONE host thread and one lane, in rounds.  Round k
+ * takes the k-th job of every group: all are staged (while round k - 1 decodes), every member is loaded, ONE gang run steps them in lockstep (a launch
+ * per colour step and kernel class for all of them instead of a launch per group on its own stream), every member is fetched and verified.  A round
+ * that only one group still takes part in runs as a job of today's path.  What a block reports is what job_launch gives: the gang run is bit-identical
+ * to the members' own runs.
+ * The two staging sets of an entry alternate between its jobs, and the host writes a set's pinned block while the job two back may still be on its way:
+ * with three jobs per code the set's previous user is waited for (its ev_done) before job_stage writes h_in.
+ */
+static int run_call_gang(qldpc_recon *r, const recon_call &call, std::vector<recon_group> &groups)
+{
+    int rc = QLDPC_OK;
+    lane_run L;
+    L.r = r; L.lane = &r->lane[0]; L.call = &call; L.rc = QLDPC_OK;
+    hipStream_t s = L.lane->stream, cs = L.lane->copy;
+    const size_t B = (size_t)r->cfg.max_blocks, ng = groups.size();
+    std::vector<std::vector<recon_job>> jobs(ng);
+    size_t rounds = 0;
+    for (size_t g = 0; g < ng; g++) {
+        for (size_t at = 0; at < groups[g].idx.size(); at += B) {
+            recon_job j;
+            j.e = groups[g].e; j.st = nullptr; j.any_punct = false;
+            j.idx.assign(groups[g].idx.begin() + (long)at, groups[g].idx.begin() + (long)std::min(groups[g].idx.size(), at + B));
+            jobs[g].push_back(std::move(j));
+        }
+        rounds = std::max(rounds, jobs[g].size());
+    }
+    auto stage_round = [&](size_t k) -> int {
+        for (size_t g = 0; g < ng; g++) {
+            if (k >= jobs[g].size()) continue;
+            recon_entry *e = jobs[g][k].e;
+            HIPCHK(hipEventSynchronize(e->set[e->next_set].ev_done));      /* the set's previous user has left its pinned block */
+            int rc2 = job_stage(&L, jobs[g][k], cs);
+            if (rc2) return rc2;
+        }
+        return QLDPC_OK;
+    };
+    auto finish_round = [&](size_t k) -> int {
+        for (size_t g = 0; g < ng; g++) {
+            if (k >= jobs[g].size()) continue;
+            int rc2 = job_finish(&L, jobs[g][k]);
+            if (rc2) return rc2;
+        }
+        return QLDPC_OK;
+    };
+    qldpc_gang *gang = nullptr;
+    std::vector<qldpc_decoder *> members, have;
+    size_t launched = 0, finished = 0;
+    rc = stage_round(0);
+    for (size_t k = 0; k < rounds && !rc; k++) {
+        if (k + 1 < rounds) rc = stage_round(k + 1);
+        std::vector<size_t> in;
+        for (size_t g = 0; g < ng; g++) if (k < jobs[g].size()) in.push_back(g);
+        if (!rc && in.size() == 1) rc = job_launch(&L, jobs[in[0]][k], cs);
+        else if (!rc) {
+            members.clear();
+            for (size_t g : in) members.push_back(groups[g].e->dec);
+            if (members != have) {      /* groups drop out as their jobs run out: a gang per set of members, at most one per group and call */
+                qldpc_gang_free(gang); gang = nullptr; have.clear();
+                rc = qldpc_gang_create(members.data(), (int)members.size(), &gang);
+                if (!rc) { have = members; rc = qldpc_gang_set_stream(gang, (void *)s); }
+            }
+            for (size_t t = 0; t < in.size() && !rc; t++) rc = job_load(&L, jobs[in[t]][k], cs);
+            if (!rc) rc = qldpc_gang_run(gang, nullptr);
+            for (size_t t = 0; t < in.size() && !rc; t++) rc = job_fetch(&L, jobs[in[t]][k], cs);
+        }
+        if (!rc) launched = k + 1;
+        if (!rc && k > 0) { rc = finish_round(k - 1); if (!rc) finished = k; }
+    }
+    for (size_t k = finished; k < launched && !rc; k++) rc = finish_round(k);
+    std::string err = rc ? qldpc_last_error() : "";
+    if (rc) { (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(cs); }
+    qldpc_gang_free(gang);
+    if (rc) qldpc_set_error("%s", err.c_str());
+    return rc;
+}
+
 /* groups: blocks by code.  Entries are looked up / built here, in the calling thread; jobs of one entry stay on one lane, the
  * entries are dealt onto the lanes largest first. */
 static int run_call(qldpc_recon *r, const recon_call &call, const std::vector<char> &skip)
 {
     int rc;
     HIPCHK(hipSetDevice(r->cfg.device));
-    struct group { recon_entry *e; std::vector<int> idx; double cost; };
+    typedef recon_group group;
     std::vector<group> groups;
     const int n = call.n;
     std::vector<char> taken(skip);
@@ -885,6 +997,18 @@ static int run_call(qldpc_recon *r, const recon_call &call, const std::vector<ch
     if (const char *env = getenv("QLDPC_RECON_LANES")) n_lanes = std::max(1, std::min(RECON_LANES, atoi(env)));
     n_lanes = std::min(n_lanes, (int)groups.size());
     std::sort(groups.begin(), groups.end(), [](const group &a, const group &b) { return a.cost > b.cost; });
+    if (r->gang && call.bob && groups.size() >= 2 && groups.size() <= (size_t)QLDPC_GANG_MAX_MEMBERS) {
+        /* only when every group's decoder can be a member (layered sessions); otherwise today's path */
+        std::vector<qldpc_decoder *> decs;
+        for (auto &g : groups) decs.push_back(g.e->dec);
+        qldpc_gang *probe = nullptr;
+        if (qldpc_gang_create(decs.data(), (int)decs.size(), &probe) == QLDPC_OK) {
+            qldpc_gang_free(probe);
+            rc = run_call_gang(r, call, groups);
+            cache_trim(r);
+            return rc;
+        }
+    }
     std::vector<lane_run> runs((size_t)n_lanes);
     std::vector<double> load((size_t)n_lanes, 0.0);
     for (int l = 0; l < n_lanes; l++) { runs[(size_t)l].r = r; runs[(size_t)l].lane = &r->lane[l]; runs[(size_t)l].call = &call; runs[(size_t)l].rc = QLDPC_OK; }
