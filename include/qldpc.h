@@ -33,6 +33,7 @@
  *                                         rate choice (BS/src/main.cpp:29,235-266), frame formation, verification; bound by
  *                                         qcrypto-ldpc_amd/host/ldpc_reconcile.c (packet handlers, cascade fallback, batched ingest)
  *   qldpc_privamp*                        the hash loop of privAmp_doPrivAmp         subcomponents/priv_amp.c:190-218
+ *   qldpc_toeplitz*                       (not in the reference) Toeplitz hashing, the sound replacement of that loop
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -508,6 +509,50 @@ int qldpc_privamp_blocks_dev(qldpc_privamp_ctx *pa, int n, const uint32_t *d_key
    argument), and the expansion of a functional into the final key words */
 uint32_t qldpc_privamp_key_functional(const uint32_t *key_words, int workbits, int lanes);
 int qldpc_privamp_expand_host(uint32_t functional, int workbits, uint32_t seed, int final_bits, uint32_t *final_words);
+
+/* ------------------------------------------------------------------ Toeplitz-hash privacy amplification ---- */
+/*
+ * The hash of qldpc_privamp* keeps the reference's wire behaviour and with it 32 bits of the key.  This is the hash a
+ * deployment needs: Toeplitz hashing, whose every output bit reads the whole key and which carries the leftover-hash guarantee.  For a
+ * block of key_bits = n >= 1, out_bits = m >= 0 and seed bits t_0 .. t_(n+m-2)
+ *
+ *     y_i = XOR_{j < n} x_j t_(i+j)        i = 0 .. m-1
+ *
+ * x_j = bit j of key_words and t_k = bit k of seed_words, both MSB-first (word[j/32] & (1u << (31 - j%32)), helpers.h:65-70); key bits
+ * at index >= n and seed bits at index >= n + m - 1 are ignored; y is written MSB-first into ceil(m/32) words, the unused low bits of
+ * the last word zero.  This is T reverse(x) with the Toeplitz matrix T[i][j] = t[i - j + n - 1]: the same 2-universal family, indexed so
+ * that output bit i reads one contiguous window of t.  m may exceed n; m == 0 leaves the block alone; n and m are at most 2^24.
+ *
+ * THE SEED IS THE CALLER'S.  The library makes none: the caller supplies n + m - 1 uniformly random bits per block
+ * (qldpc_toeplitz_seed_words words).  They may be public and the blocks of a call may share them.  The guarantee of the hash is the
+ * quality of that seed and nothing the library can check.
+ *
+ * An n x m GF(2) matrix-vector product per block, on the device, all blocks of a call in one launch (csrc/qldpc_toeplitz.hip).
+ * Conventions as qldpc_privamp_create / _blocks / _blocks_dev: qldpc_toeplitz_create allocates everything (pinned staging and device rows
+ * for max_blocks keys, seeds and outputs, descriptor rows), whichever form is used afterwards, and no call afterwards allocates;
+ * max_blocks up to 65 535, max_key_bits and max_out_bits up to 2^24 (QLDPC_ESIZE above, for max_blocks <= 0, and when max_blocks x the
+ * row lengths pass 2^31 words).  A bad argument in any block (NULL row: QLDPC_EINVAL; key_bits <= 0, out_bits < 0, a value over the
+ * context's sizes, n > max_blocks: QLDPC_ESIZE) refuses the whole call before any work is queued, and qldpc_last_error() names the block.
+ * n == 0 is QLDPC_OK.  A context is not re-entrant; a call first waits for the previous call on the same context to have run.
+ */
+typedef struct qldpc_toeplitz_ctx qldpc_toeplitz_ctx;
+/* ceil((key_bits + out_bits - 1) / 32); 0 for out_bits <= 0 or key_bits <= 0 */
+size_t qldpc_toeplitz_seed_words(int key_bits, int out_bits);
+int    qldpc_toeplitz_create(int device, int max_blocks, int max_key_bits, int max_out_bits, qldpc_toeplitz_ctx **out);
+void   qldpc_toeplitz_free(qldpc_toeplitz_ctx *tz);
+size_t qldpc_toeplitz_device_bytes(const qldpc_toeplitz_ctx *tz);
+/* host buffers, n <= max_blocks blocks of any mix of lengths.  When all n seed_words pointers are equal the seed is uploaded once and
+   shared (the row then covers the longest key_bits + out_bits - 1 of the call); otherwise once per block */
+int    qldpc_toeplitz_blocks(qldpc_toeplitz_ctx *tz, int n, const uint32_t *const *key_words, const int *key_bits,
+                             const uint32_t *const *seed_words, const int *out_bits, uint32_t *const *out_words);
+/* device-resident rows key_stride / seed_stride / out_stride words apart (seed_stride 0: every block reads row 0); key_bits / out_bits are
+   host arrays; asynchronous on hip_stream; writes exactly ceil(out_bits[i]/32) words of row i */
+int    qldpc_toeplitz_blocks_dev(qldpc_toeplitz_ctx *tz, int n, const uint32_t *d_keys, size_t key_stride, const int *key_bits,
+                                 const uint32_t *d_seeds, size_t seed_stride, const int *out_bits,
+                                 uint32_t *d_out, size_t out_stride, void *hip_stream);
+/* host mirror, for tests: the kernel's own window / fold functions (csrc/qldpc_toeplitz_core.h), the key consumed in tiles of tile_words
+   (0 = the kernel's tile; every tile size gives the same words) */
+int    qldpc_toeplitz_host(const uint32_t *key_words, int key_bits, const uint32_t *seed_words, int out_bits, int tile_words, uint32_t *out_words);
 
 #ifdef __cplusplus
 }

@@ -742,6 +742,137 @@ class PrivAmp:
             pass
 
 
+# ---- Toeplitz-hash privacy amplification (qldpc_toeplitz_*): y_i = XOR_j x_j t_(i+j), the caller's seed of n + m - 1 bits ----------
+
+_sig("qldpc_toeplitz_seed_words", C.c_size_t, [C.c_int, C.c_int])
+_sig("qldpc_toeplitz_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)])
+_sig("qldpc_toeplitz_free", None, [_vp])
+_sig("qldpc_toeplitz_device_bytes", C.c_size_t, [_vp])
+_sig("qldpc_toeplitz_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, C.POINTER(_up), _ip, C.POINTER(_up)])
+_sig("qldpc_toeplitz_blocks_dev", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _ip, _vp, C.c_size_t, _ip, _vp, C.c_size_t, _vp])
+_sig("qldpc_toeplitz_host", C.c_int, [_up, C.c_int, _up, C.c_int, C.c_int, _up])
+
+
+def toeplitz_seed_words(key_bits, out_bits):
+    """words of a seed of key_bits + out_bits - 1 bits; 0 for key_bits <= 0 or out_bits <= 0"""
+    return int(_L.qldpc_toeplitz_seed_words(int(key_bits), int(out_bits)))
+
+
+def toeplitz_host(key_words, key_bits, seed_words, out_bits, tile_words=0):
+    """y_i = XOR_{j < key_bits} x_j t_(i+j) on the host with the kernel's own window / fold functions, the key consumed in tiles of
+    tile_words (0: the kernel's tile) -> ceil(out_bits/32) words, MSB-first"""
+    kw = np.ascontiguousarray(key_words, dtype=np.uint32)
+    sw = np.ascontiguousarray(seed_words, dtype=np.uint32)
+    key_bits, out_bits = int(key_bits), int(out_bits)
+    if key_bits <= 0 or out_bits < 0 or kw.size < (key_bits + 31) // 32 or sw.size < toeplitz_seed_words(key_bits, out_bits):
+        raise QldpcError(-6, "toeplitz_host: %d key words, key_bits = %d, %d seed words, out_bits = %d" % (kw.size, key_bits, sw.size, out_bits))
+    out = np.zeros((out_bits + 31) // 32, np.uint32)
+    _chk(_L.qldpc_toeplitz_host(kw.ctypes.data_as(_up), key_bits, sw.ctypes.data_as(_up), out_bits, int(tile_words), out.ctypes.data_as(_up)),
+         "toeplitz_host")
+    return out
+
+
+class Toeplitz:
+    """Toeplitz hashing for batches of blocks of any mix of lengths, one launch per call (qldpc_toeplitz_blocks*).  The seeds are the
+    caller's: key_bits + out_bits - 1 uniformly random bits per block, which may be public and shared by the blocks of a call.
+    Everything is allocated here; blocks() / blocks_dev() allocate nothing on the device."""
+
+    def __init__(self, max_blocks=64, max_key_bits=1 << 16, max_out_bits=1 << 16, device=0):
+        h = _vp()
+        _chk(_L.qldpc_toeplitz_create(int(device), int(max_blocks), int(max_key_bits), int(max_out_bits), C.byref(h)), "Toeplitz")
+        self._h = h
+        self.device, self.max_blocks, self.max_key_bits, self.max_out_bits = int(device), int(max_blocks), int(max_key_bits), int(max_out_bits)
+
+    @property
+    def device_bytes(self):
+        return int(_L.qldpc_toeplitz_device_bytes(self._h))
+
+    @staticmethod
+    def _args(n, key_bits, out_bits):
+        kb = np.ascontiguousarray(key_bits, dtype=np.int32).ravel()
+        ob = np.ascontiguousarray(out_bits, dtype=np.int32).ravel()
+        if not (kb.size == ob.size == n):
+            raise QldpcError(-6, "Toeplitz: %d blocks, %d key_bits, %d out_bits" % (n, kb.size, ob.size))
+        return kb, ob
+
+    def blocks(self, keys, key_bits, seeds, out_bits, out=None):
+        """keys, seeds: lists of uint32 word arrays (key bits past key_bits[i] and seed bits past key_bits[i] + out_bits[i] - 1 are
+        ignored) -> list of ceil(out_bits[i]/32)-word arrays.  seeds may also be ONE array: it is uploaded once and shared by the blocks.
+        out: arrays to write into instead (a refused call leaves them untouched)"""
+        n = len(keys)
+        kb, ob = self._args(n, key_bits, out_bits)
+        kws = [np.ascontiguousarray(k, dtype=np.uint32) for k in keys]
+        if isinstance(seeds, np.ndarray) and seeds.ndim == 1:
+            one = np.ascontiguousarray(seeds, dtype=np.uint32)
+            sws = [one] * n
+        else:
+            if len(seeds) != n:
+                raise QldpcError(-6, "Toeplitz.blocks: %d blocks, %d seeds" % (n, len(seeds)))
+            same = n > 0 and all(s is seeds[0] for s in seeds)
+            first = np.ascontiguousarray(seeds[0], dtype=np.uint32) if same else None
+            sws = [first if same else np.ascontiguousarray(s, dtype=np.uint32) for s in seeds]
+        for i in range(n):
+            if kb[i] > 0 and kws[i].size < (int(kb[i]) + 31) // 32:
+                raise QldpcError(-6, "Toeplitz.blocks: block %d has %d key words, key_bits = %d" % (i, kws[i].size, kb[i]))
+            if sws[i].size < toeplitz_seed_words(kb[i], ob[i]):
+                raise QldpcError(-6, "Toeplitz.blocks: block %d has %d seed words, %d -> %d bits need %d" %
+                                 (i, sws[i].size, kb[i], ob[i], toeplitz_seed_words(kb[i], ob[i])))
+        if out is None:
+            out = [np.zeros((max(int(f), 0) + 31) // 32, np.uint32) for f in ob]
+        for i, o in enumerate(out):
+            if o.dtype != np.uint32 or not o.flags.c_contiguous or o.size < (max(int(ob[i]), 0) + 31) // 32:
+                raise QldpcError(-6, "Toeplitz.blocks: out[%d] must be a contiguous uint32 array of ceil(out_bits/32) words" % i)
+        kp = (_up * max(n, 1))(*[k.ctypes.data_as(_up) for k in kws])
+        sp = (_up * max(n, 1))(*[s.ctypes.data_as(_up) for s in sws])
+        op = (_up * max(n, 1))(*[o.ctypes.data_as(_up) for o in out])
+        _chk(_L.qldpc_toeplitz_blocks(self._h, n, kp, kb.ctypes.data_as(_ip), sp, ob.ctypes.data_as(_ip), op), "Toeplitz.blocks")
+        return out
+
+    def blocks_dev(self, keys_t, key_bits, seeds_t, out_bits, seed_shared=False, out_t=None, stream=None):
+        """keys_t: torch int32 [n, key_stride] on the device; seeds_t: int32 [n, seed_stride], or with seed_shared a 1-D tensor or
+        one row that every block reads -> out_t int32 [n, out_stride] (row i: ceil(out_bits[i]/32) words written, the rest left as it
+        is); asynchronous on `stream` (default: torch's current stream)"""
+        torch = _torch()
+        n = int(keys_t.shape[0])
+        kb, ob = self._args(n, key_bits, out_bits)
+
+        def rows(t, count):
+            return t.dtype == torch.int32 and t.dim() == 2 and t.stride(1) == 1 and t.is_cuda and t.shape[0] == count
+
+        if not rows(keys_t, n):
+            raise QldpcError(-6, "Toeplitz.blocks_dev: keys_t must be a device int32 [n, stride] tensor with unit column stride")
+        if seed_shared and seeds_t.dim() == 1:
+            seeds_t = seeds_t.unsqueeze(0)
+        if not rows(seeds_t, 1 if seed_shared else n):
+            raise QldpcError(-6, "Toeplitz.blocks_dev: seeds_t must be a device int32 [n, stride] tensor with unit column stride (one row with seed_shared)")
+        if out_t is None:
+            out_t = torch.zeros((n, max(1, (int(ob.max(initial=0)) + 31) // 32)), dtype=torch.int32, device=keys_t.device)
+        if not rows(out_t, n):
+            raise QldpcError(-6, "Toeplitz.blocks_dev: out_t must be a device int32 [n, stride] tensor with unit column stride")
+        if keys_t.device.index != self.device or seeds_t.device.index != self.device or out_t.device.index != self.device:
+            raise QldpcError(-1, "Toeplitz.blocks_dev: keys_t / seeds_t / out_t are on %s / %s / %s, the context is on device %d" %
+                             (keys_t.device, seeds_t.device, out_t.device, self.device))
+        # a row holds shape[1] words even where the rows lie further apart, so the library's row checks use the shape
+        for i in range(n):
+            if (int(kb[i]) + 31) // 32 > keys_t.shape[1] or (int(ob[i]) + 31) // 32 > out_t.shape[1] or toeplitz_seed_words(kb[i], ob[i]) > seeds_t.shape[1]:
+                raise QldpcError(-6, "Toeplitz.blocks_dev: block %d does not fit its rows" % i)
+
+        def stride(t):
+            return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _chk(_L.qldpc_toeplitz_blocks_dev(self._h, n, keys_t.data_ptr(), stride(keys_t), kb.ctypes.data_as(_ip),
+                                          seeds_t.data_ptr(), 0 if seed_shared else stride(seeds_t), ob.ctypes.data_as(_ip),
+                                          out_t.data_ptr(), stride(out_t), s.cuda_stream), "Toeplitz.blocks_dev")
+        return out_t
+
+    def __del__(self):
+        try:
+            _L.qldpc_toeplitz_free(self._h)
+        except Exception:
+            pass
+
+
 def crc32_words(words, n_bits, lanes=0):
     """CRC-32 of the key bits; lanes > 0: the chunked fold the device verification uses (same value)"""
     w = np.ascontiguousarray(words, dtype=np.uint32)

@@ -1,0 +1,309 @@
+/*
+ * qldpc_toeplitz.hip -- Toeplitz-hash privacy amplification for a batch of blocks in one launch (qldpc_toeplitz_*).
+ *
+ *     y_i = XOR_{j < n} x_j t_{i+j},    i < m,    seed t of n + m - 1 bits
+ *
+ * an n x m GF(2) matrix-vector product per block, with no shortcut: every output bit reads the whole key (that is what makes the
+ * family 2-universal, and what the LFSR hash of qldpc_privamp* lacks).  In words, with W(p) the 32 seed bits from bit p on,
+ * y_i = parity(XOR_j key[j] & W(i + 32 j)).  The arithmetic is qldpc_toeplitz_core.h (bit-reversed words: one funnel shift per window).
+ *
+ * tz_hash: grid = (4 x groups of 32 output words, blocks), 256 lanes = 8 halves of 32 lanes.  Half h of workgroup (C, r) owns output word
+ *     32 C + 4 h + r, lane s of it output bit s of that word.  All halves of a workgroup meet key word j in the same step, so key[j] is
+ *     wave-uniform (scalar loads, bit-reversed on the scalar unit), and half h is then at seed word 32 C + r + 4 h + j: the halves lie
+ *     4 words = 16 bytes apart in the staged seed, so each lane takes the next 4 seed words with one aligned 16-byte LDS read (a
+ *     broadcast inside a half) and rolls its window through them, one funnel shift per key word.  That alignment is why a workgroup owns
+ *     every 4th word (r) and not 8 adjacent ones.
+ *     The seed words a workgroup needs for TZ_TILE key words (TZ_TILE + 32) are staged bit-reversed in LDS, tile after tile: neither the
+ *     key nor the seed is bounded by the LDS.  The output word of a half is its 32 parities by ballot.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+#include "../../include/qldpc.h"
+#include "qldpc_graph.h"
+#include "qldpc_hip.h"
+#include "qldpc_toeplitz_core.h"
+
+#define TZ_MAX_BLOCKS 65535        /* blocks are the y dimension of the grid */
+#define TZ_LANES 256
+#define TZ_TILE 2048               /* key words per staged seed tile; a multiple of 8 */
+#define TZ_SPAN 32                 /* seed words past the tile that the 8 halves of a workgroup reach (28 + 1, and 3 of padding in front) */
+
+struct tz_desc {                   /* one row per block, written by the host */
+    uint32_t key_words, tail_mask, out_bits, seed_words;
+    uint64_t key_off, seed_off, out_off;      /* in words from the key / seed / output base of the call */
+};
+
+__global__ __launch_bounds__(TZ_LANES) void tz_hash(const tz_desc *__restrict__ descs, const uint32_t *__restrict__ keys,
+                                                    const uint32_t *__restrict__ seeds, uint32_t *__restrict__ outs)
+{
+    /* s_w[x] = bit-reversed seed word (w0 + j0 + x - 3): the 4 words after a half's current one start at a multiple of 4 */
+    __shared__ uint4 s_seed[(TZ_TILE + TZ_SPAN) / 4];
+    uint32_t *s_w = (uint32_t *)s_seed;
+    const tz_desc d = descs[blockIdx.y];
+    const uint32_t outwords = (d.out_bits + 31u) / 32u;
+    const uint32_t w0 = (blockIdx.x >> 2) * 32u + (blockIdx.x & 3u);
+    if (w0 >= outwords) return;                                 /* the whole workgroup: the grid is as wide as the call's longest output */
+    const uint32_t t = threadIdx.x, h = t >> 5, s = t & 31u;
+    const uint32_t word = w0 + 4u * h;
+    const bool wave_on = (uint32_t)__builtin_amdgcn_readfirstlane((int)word) < outwords;      /* the wave's first half */
+    const uint32_t *__restrict__ key = keys + d.key_off;
+    const uint32_t *__restrict__ seed = seeds + d.seed_off;
+    const uint32_t last = d.key_words - 1u;
+    uint32_t acc = 0;
+    for (uint32_t j0 = 0; j0 < d.key_words; j0 += TZ_TILE) {
+        const uint32_t tw = min((uint32_t)TZ_TILE, d.key_words - j0);
+        if (j0) __syncthreads();
+        for (uint32_t x = t; x < tw + TZ_SPAN; x += TZ_LANES) {
+            const uint64_t g = (uint64_t)w0 + j0 + x - 3u;
+            s_w[x] = (x >= 3u && g < d.seed_words) ? tz_brev(seed[g]) : 0u;      /* past the block's seed: met by masked key bits or by lanes past out_bits only */
+        }
+        __syncthreads();
+        if (!wave_on) continue;
+        /* groups of 8 key words; the key's last word goes through the masked loop */
+        const uint32_t full = j0 + tw == d.key_words ? (tw - 1u) & ~7u : tw;
+        uint32_t lo = s_w[4u * h + 3u];
+        const uint4 *quad = s_seed + h + 1u;
+        for (uint32_t jj = 0; jj < full; jj += 8u) {
+            const uint4 a = quad[jj >> 2], b = quad[(jj >> 2) + 1u];
+            const uint32_t *k = key + j0 + jj;
+            acc = tz_fold(acc, tz_brev(k[0]), tz_window(lo, a.x, s));
+            acc = tz_fold(acc, tz_brev(k[1]), tz_window(a.x, a.y, s));
+            acc = tz_fold(acc, tz_brev(k[2]), tz_window(a.y, a.z, s));
+            acc = tz_fold(acc, tz_brev(k[3]), tz_window(a.z, a.w, s));
+            acc = tz_fold(acc, tz_brev(k[4]), tz_window(a.w, b.x, s));
+            acc = tz_fold(acc, tz_brev(k[5]), tz_window(b.x, b.y, s));
+            acc = tz_fold(acc, tz_brev(k[6]), tz_window(b.y, b.z, s));
+            acc = tz_fold(acc, tz_brev(k[7]), tz_window(b.z, b.w, s));
+            lo = b.w;
+        }
+        acc = tz_lane_words(acc, key, j0 + full, tw - full, last, d.tail_mask, s_w + 4u * h + 3u + full, s);
+    }
+    if (!wave_on) return;
+    const unsigned long long votes = __ballot(32u * word + s < d.out_bits && tz_parity(acc));
+    if (s == 0 && word < outwords) outs[d.out_off + word] = tz_brev((uint32_t)(votes >> (t & 32u)));
+}
+
+/* ------------------------------------------------------------------ host ---- */
+
+/* host mirror: every output bit through tz_lane_words, the key in tiles of tile_words, the seed window rebuilt per tile as the kernel stages it */
+extern "C" int qldpc_toeplitz_host(const uint32_t *key_words, int key_bits, const uint32_t *seed_words, int out_bits, int tile_words, uint32_t *out_words)
+{
+    if (key_bits <= 0 || out_bits < 0 || key_bits > TZ_MAX_BITS || out_bits > TZ_MAX_BITS || tile_words < 0) {
+        qldpc_set_error("toeplitz_host: key_bits=%d out_bits=%d tile_words=%d", key_bits, out_bits, tile_words);
+        return QLDPC_ESIZE;
+    }
+    if (out_bits == 0) return QLDPC_OK;
+    if (!key_words || !seed_words || !out_words) return QLDPC_EINVAL;
+    const uint32_t nw = ((uint32_t)key_bits + 31u) / 32u, ow = ((uint32_t)out_bits + 31u) / 32u, sw = tz_seed_words(key_bits, out_bits);
+    const uint32_t tile = tile_words ? (uint32_t)tile_words : (uint32_t)TZ_TILE, mask = tz_tail_mask(key_bits);
+    uint32_t *win = (uint32_t *)malloc(4 * ((size_t)(tile < nw ? tile : nw) + 1));
+    if (!win) return QLDPC_ENOMEM;
+    for (uint32_t w = 0; w < ow; w++) {
+        uint32_t acc[32];
+        memset(acc, 0, sizeof(acc));
+        for (uint32_t j0 = 0; j0 < nw; j0 += tile) {
+            const uint32_t tw = nw - j0 < tile ? nw - j0 : tile;
+            for (uint32_t k = 0; k <= tw; k++) win[k] = w + j0 + k < sw ? tz_brev(seed_words[w + j0 + k]) : 0u;
+            for (uint32_t s = 0; s < 32; s++) acc[s] = tz_lane_words(acc[s], key_words, j0, tw, nw - 1u, mask, win, s);
+        }
+        uint32_t word = 0;
+        for (uint32_t s = 0; s < 32; s++)
+            if (32u * w + s < (uint32_t)out_bits) word |= tz_parity(acc[s]) << (31 - s);
+        out_words[w] = word;
+    }
+    free(win);
+    return QLDPC_OK;
+}
+
+extern "C" size_t qldpc_toeplitz_seed_words(int key_bits, int out_bits) { return tz_seed_words(key_bits, out_bits); }
+
+struct qldpc_toeplitz_ctx {
+    int device, max_blocks, max_key_bits, max_out_bits;
+    size_t key_cap, seed_cap, out_cap;    /* words of the packed key / seed / output areas of the host form */
+    size_t in_words;                      /* descriptor rows, packed keys and packed seeds of a full call: one upload per host call */
+    uint32_t *h_in, *d_in, *h_out, *d_out;
+    hipEvent_t done;                      /* after the last call's launch: the staging is reused only once that call has run */
+    hipStream_t stream;                   /* of the host form */
+    size_t dev_bytes;
+};
+
+static size_t tz_desc_words(int n) { return (size_t)n * (sizeof(tz_desc) / 4); }
+
+extern "C" void qldpc_toeplitz_free(qldpc_toeplitz_ctx *tz)
+{
+    if (!tz) return;
+    (void)hipSetDevice(tz->device);
+    if (tz->done) { (void)hipEventSynchronize(tz->done); (void)hipEventDestroy(tz->done); }
+    if (tz->stream) (void)hipStreamDestroy(tz->stream);
+    if (tz->h_in) (void)hipHostFree(tz->h_in);
+    if (tz->h_out) (void)hipHostFree(tz->h_out);
+    if (tz->d_in) (void)hipFree(tz->d_in);
+    if (tz->d_out) (void)hipFree(tz->d_out);
+    delete tz;
+}
+
+static int tz_create(qldpc_toeplitz_ctx *tz)
+{
+    HIPCHK(hipSetDevice(tz->device));
+    const size_t kw = ((size_t)tz->max_key_bits + 31) / 32, ow = ((size_t)tz->max_out_bits + 31) / 32;
+    tz->key_cap = (size_t)tz->max_blocks * kw;
+    tz->seed_cap = (size_t)tz->max_blocks * tz_seed_words(tz->max_key_bits, tz->max_out_bits);
+    tz->out_cap = (size_t)tz->max_blocks * ow;
+    tz->in_words = tz_desc_words(tz->max_blocks) + tz->key_cap + tz->seed_cap;
+    const size_t out_words = tz->out_cap ? tz->out_cap : 1;
+    if (hipHostMalloc((void **)&tz->h_in, 4 * tz->in_words, hipHostMallocDefault) != hipSuccess) return QLDPC_ENOMEM;
+    if (hipHostMalloc((void **)&tz->h_out, 4 * out_words, hipHostMallocDefault) != hipSuccess) return QLDPC_ENOMEM;
+    if (hipMalloc((void **)&tz->d_in, 4 * tz->in_words) != hipSuccess) return QLDPC_ENOMEM;
+    if (hipMalloc((void **)&tz->d_out, 4 * out_words) != hipSuccess) return QLDPC_ENOMEM;
+    tz->dev_bytes = 4 * (tz->in_words + out_words);
+    HIPCHK(hipStreamCreateWithFlags(&tz->stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&tz->done, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(tz->done, tz->stream));
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_toeplitz_create(int device, int max_blocks, int max_key_bits, int max_out_bits, qldpc_toeplitz_ctx **out)
+{
+    if (!out) return QLDPC_EINVAL;
+    *out = nullptr;
+    if (max_blocks > TZ_MAX_BLOCKS) { qldpc_set_error("toeplitz_create: max_blocks=%d (up to %d)", max_blocks, TZ_MAX_BLOCKS); return QLDPC_ESIZE; }
+    if (max_blocks < 1 || max_key_bits < 1 || max_out_bits < 0 || max_key_bits > TZ_MAX_BITS || max_out_bits > TZ_MAX_BITS) {
+        qldpc_set_error("toeplitz_create: max_blocks=%d max_key_bits=%d max_out_bits=%d (bits up to %d)", max_blocks, max_key_bits, max_out_bits, TZ_MAX_BITS);
+        return QLDPC_ESIZE;
+    }
+    const uint64_t row = ((uint64_t)max_key_bits + 31) / 32 + tz_seed_words(max_key_bits, max_out_bits) + ((uint64_t)max_out_bits + 31) / 32 + 16;
+    if ((uint64_t)max_blocks * row >= (1ull << 31)) {
+        qldpc_set_error("toeplitz_create: %d blocks of %d -> %d bits pass 2^31 staged words", max_blocks, max_key_bits, max_out_bits);
+        return QLDPC_ESIZE;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { qldpc_set_error("no HIP device visible: libqldpc has no CPU fallback"); return QLDPC_ENODEV; }
+    if (device < 0 || device >= ndev) return QLDPC_ENODEV;
+    qldpc_toeplitz_ctx *tz = new (std::nothrow) qldpc_toeplitz_ctx();
+    if (!tz) return QLDPC_ENOMEM;
+    tz->device = device; tz->max_blocks = max_blocks; tz->max_key_bits = max_key_bits; tz->max_out_bits = max_out_bits;
+    const int rc = tz_create(tz);
+    if (rc) { qldpc_toeplitz_free(tz); return rc; }
+    *out = tz;
+    return QLDPC_OK;
+}
+
+extern "C" size_t qldpc_toeplitz_device_bytes(const qldpc_toeplitz_ctx *tz) { return tz ? tz->dev_bytes : 0; }
+
+/* argument checks of both forms; nothing is written before every block has passed */
+static int tz_check(const qldpc_toeplitz_ctx *tz, int n, const int *key_bits, const int *out_bits, const char *who)
+{
+    if (!tz) return QLDPC_EINVAL;
+    if (n < 0) return QLDPC_EINVAL;
+    if (n > tz->max_blocks) { qldpc_set_error("%s: %d blocks, the context holds %d", who, n, tz->max_blocks); return QLDPC_ESIZE; }
+    if (n == 0) return QLDPC_OK;
+    if (!key_bits || !out_bits) { qldpc_set_error("%s: NULL argument array", who); return QLDPC_EINVAL; }
+    for (int i = 0; i < n; i++) {
+        if (key_bits[i] <= 0 || out_bits[i] < 0) { qldpc_set_error("%s: block %d: key_bits=%d out_bits=%d", who, i, key_bits[i], out_bits[i]); return QLDPC_ESIZE; }
+        if (key_bits[i] > tz->max_key_bits) { qldpc_set_error("%s: block %d: key_bits=%d, the context holds %d", who, i, key_bits[i], tz->max_key_bits); return QLDPC_ESIZE; }
+        if (out_bits[i] > tz->max_out_bits) { qldpc_set_error("%s: block %d: out_bits=%d, the context holds %d", who, i, out_bits[i], tz->max_out_bits); return QLDPC_ESIZE; }
+    }
+    return QLDPC_OK;
+}
+
+/* descriptor rows into the pinned staging.  packed: rows one after the other (host form; one_seed: every block reads the seed at 0);
+ * else rows key_stride / seed_stride / out_stride words apart.  *grid_x and the words of the three areas out */
+static void tz_fill(qldpc_toeplitz_ctx *tz, int n, const int *key_bits, const int *out_bits, size_t key_stride, size_t seed_stride, size_t out_stride,
+                    int packed, int one_seed, unsigned *grid_x, size_t *key_words, size_t *seed_words, size_t *out_words)
+{
+    tz_desc *descs = (tz_desc *)tz->h_in;
+    size_t koff = 0, soff = 0, ooff = 0, smax = 0;
+    unsigned gx = 0;
+    for (int i = 0; i < n; i++) {
+        tz_desc &d = descs[i];
+        d.key_words = ((uint32_t)key_bits[i] + 31u) / 32u;
+        d.tail_mask = tz_tail_mask(key_bits[i]);
+        d.out_bits = (uint32_t)out_bits[i];
+        d.seed_words = tz_seed_words(key_bits[i], out_bits[i]);
+        const uint32_t ow = (d.out_bits + 31u) / 32u;
+        d.key_off = packed ? koff : (uint64_t)i * key_stride;
+        d.seed_off = packed ? (one_seed ? 0 : soff) : (uint64_t)i * seed_stride;
+        d.out_off = packed ? ooff : (uint64_t)i * out_stride;
+        koff += d.key_words; soff += d.seed_words; ooff += ow;
+        if (d.seed_words > smax) smax = d.seed_words;
+        const unsigned g = 4u * ((ow + 31u) / 32u);
+        if (g > gx) gx = g;
+    }
+    *grid_x = gx; *key_words = koff; *seed_words = one_seed ? smax : soff; *out_words = ooff;
+}
+
+static int tz_launch(qldpc_toeplitz_ctx *tz, int n, unsigned grid_x, const uint32_t *d_keys, const uint32_t *d_seeds, uint32_t *d_out, hipStream_t s)
+{
+    hipLaunchKernelGGL(tz_hash, dim3(grid_x, (unsigned)n), dim3(TZ_LANES), 0, s, (const tz_desc *)tz->d_in, d_keys, d_seeds, d_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { qldpc_set_error("toeplitz_blocks launch: %s", hipGetErrorString(e)); return QLDPC_EHIP; }
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_toeplitz_blocks(qldpc_toeplitz_ctx *tz, int n, const uint32_t *const *key_words, const int *key_bits,
+                                     const uint32_t *const *seed_words, const int *out_bits, uint32_t *const *out_words)
+{
+    int rc = tz_check(tz, n, key_bits, out_bits, "toeplitz_blocks");
+    if (rc || n == 0) return rc;
+    if (!key_words || !seed_words || !out_words) { qldpc_set_error("toeplitz_blocks: NULL argument array"); return QLDPC_EINVAL; }
+    int one_seed = 1;
+    for (int i = 0; i < n; i++) {
+        if (!key_words[i] || !seed_words[i] || (!out_words[i] && out_bits[i] > 0)) {
+            qldpc_set_error("toeplitz_blocks: block %d: NULL %s row", i, !key_words[i] ? "key" : !seed_words[i] ? "seed" : "output");
+            return QLDPC_EINVAL;
+        }
+        if (seed_words[i] != seed_words[0]) one_seed = 0;
+    }
+    HIPCHK(hipSetDevice(tz->device));
+    HIPCHK(hipEventSynchronize(tz->done));
+    unsigned grid_x = 0;
+    size_t kw = 0, sw = 0, ow = 0;
+    tz_fill(tz, n, key_bits, out_bits, 0, 0, 0, 1, one_seed, &grid_x, &kw, &sw, &ow);
+    if (grid_x == 0) return QLDPC_OK;                            /* every block asks for 0 bits */
+    const size_t head = tz_desc_words(n);
+    const tz_desc *descs = (const tz_desc *)tz->h_in;
+    uint32_t *h_keys = tz->h_in + head, *h_seeds = h_keys + kw;
+    for (int i = 0; i < n; i++) memcpy(h_keys + descs[i].key_off, key_words[i], 4 * (size_t)descs[i].key_words);
+    if (one_seed) memcpy(h_seeds, seed_words[0], 4 * sw);        /* the caller's one row covers the longest key_bits + out_bits - 1 of the call */
+    else for (int i = 0; i < n; i++) memcpy(h_seeds + descs[i].seed_off, seed_words[i], 4 * (size_t)descs[i].seed_words);
+    HIPCHK(hipMemcpyAsync(tz->d_in, tz->h_in, 4 * (head + kw + sw), hipMemcpyHostToDevice, tz->stream));
+    rc = tz_launch(tz, n, grid_x, tz->d_in + head, tz->d_in + head + kw, tz->d_out, tz->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(tz->h_out, tz->d_out, 4 * ow, hipMemcpyDeviceToHost, tz->stream));
+    HIPCHK(hipEventRecord(tz->done, tz->stream));
+    HIPCHK(hipStreamSynchronize(tz->stream));
+    for (int i = 0; i < n; i++)
+        if (out_bits[i] > 0) memcpy(out_words[i], tz->h_out + descs[i].out_off, 4 * (size_t)((descs[i].out_bits + 31u) / 32u));
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_toeplitz_blocks_dev(qldpc_toeplitz_ctx *tz, int n, const uint32_t *d_keys, size_t key_stride, const int *key_bits,
+                                         const uint32_t *d_seeds, size_t seed_stride, const int *out_bits,
+                                         uint32_t *d_out, size_t out_stride, void *hip_stream)
+{
+    int rc = tz_check(tz, n, key_bits, out_bits, "toeplitz_blocks_dev");
+    if (rc || n == 0) return rc;
+    if (!d_keys || !d_seeds || !d_out) { qldpc_set_error("toeplitz_blocks_dev: NULL device pointer"); return QLDPC_EINVAL; }
+    for (int i = 0; i < n; i++) {
+        if (((size_t)key_bits[i] + 31) / 32 > key_stride) { qldpc_set_error("toeplitz_blocks_dev: block %d: key_bits=%d pass a key row of %zu words", i, key_bits[i], key_stride); return QLDPC_ESIZE; }
+        if (seed_stride && tz_seed_words(key_bits[i], out_bits[i]) > seed_stride) { qldpc_set_error("toeplitz_blocks_dev: block %d: %d -> %d bits pass a seed row of %zu words", i, key_bits[i], out_bits[i], seed_stride); return QLDPC_ESIZE; }
+        if (((size_t)out_bits[i] + 31) / 32 > out_stride) { qldpc_set_error("toeplitz_blocks_dev: block %d: out_bits=%d pass an output row of %zu words", i, out_bits[i], out_stride); return QLDPC_ESIZE; }
+    }
+    HIPCHK(hipSetDevice(tz->device));
+    HIPCHK(hipEventSynchronize(tz->done));                       /* the previous call's descriptors are free again */
+    unsigned grid_x = 0;
+    size_t kw = 0, sw = 0, ow = 0;
+    tz_fill(tz, n, key_bits, out_bits, key_stride, seed_stride, out_stride, 0, 0, &grid_x, &kw, &sw, &ow);
+    if (grid_x == 0) return QLDPC_OK;
+    const hipStream_t s = (hipStream_t)hip_stream;
+    HIPCHK(hipMemcpyAsync(tz->d_in, tz->h_in, 4 * tz_desc_words(n), hipMemcpyHostToDevice, s));
+    rc = tz_launch(tz, n, grid_x, d_keys, d_seeds, d_out, s);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(tz->done, s));
+    return QLDPC_OK;
+}

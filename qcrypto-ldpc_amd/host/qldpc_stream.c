@@ -11,6 +11,10 @@
  *                     [-g rate_gap] [-G gap_profile] [-p (per-kernel profile of Bob's decoders in a second pass)]
  *                     [-H (privacy amplification of the reconciled blocks after every timed decode: ONE qldpc_privamp_blocks call, final_bits =
  *                          key_bits - leaked bits, seed from the block index; adds pa_ms_mean, pa_ms_best, distill_Mbit_s_mean)]
+ *                     [-U (Toeplitz hashing of the reconciled blocks after every timed decode: ONE qldpc_toeplitz_blocks call, out_bits =
+ *                          key_bits - leaked bits, one seed of 2 key_bits - 1 bits shared by the call.  The seed comes from this tool's own
+ *                          deterministic generator: a MEASUREMENT seed, not a random one, and nothing to deploy.  Adds tpa_ms_mean,
+ *                          tpa_ms_best, tdistill_Mbit_s_mean; may be given together with -H)]
  *                     (defaults: 512 epochs x 52 429 bits, max_blocks 512, PEG depth 2 = the library's default)
  * prints one JSON object on stdout.
  */
@@ -58,10 +62,10 @@ static void *part_main(void *arg)
 
 int main(int argc, char **argv)
 {
-    int epochs = 512, key_bits = 52429, batch = 512, reps = 3, layered = -1, profile = 0, peg = 2, opt, a_lanes = 0, b_lanes = 0, verbose = 0, split = 1, gap_profile = 0, hash = 0;
+    int epochs = 512, key_bits = 52429, batch = 512, reps = 3, layered = -1, profile = 0, peg = 2, opt, a_lanes = 0, b_lanes = 0, verbose = 0, split = 1, gap_profile = 0, hash = 0, toeplitz = 0;
     uint64_t seed = 42;
     double qmin = 0.005, qmax = 0.06, gap = 0.0;
-    while ((opt = getopt(argc, argv, "e:k:b:S:r:q:lfpP:g:A:B:vT:G:H")) != -1) {
+    while ((opt = getopt(argc, argv, "e:k:b:S:r:q:lfpP:g:A:B:vT:G:HU")) != -1) {
         switch (opt) {
         case 'e': epochs = atoi(optarg); break;
         case 'k': key_bits = atoi(optarg); break;
@@ -79,6 +83,7 @@ int main(int argc, char **argv)
         case 'v': verbose = 1; break;
         case 'G': gap_profile = atoi(optarg); break;      /* qldpc_recon_cfg.gap_profile */
         case 'H': hash = 1; break;
+        case 'U': toeplitz = 1; break;
         case 'T': split = atoi(optarg); break;      /* experiment: T sessions on T host threads, each decoding every T-th epoch */
         default: fprintf(stderr, "usage: see the head of qldpc_stream.c\n"); return 2;
         }
@@ -204,6 +209,20 @@ int main(int argc, char **argv)
         pa_wb = calloc((size_t)epochs, sizeof(int)); pa_fb = calloc((size_t)epochs, sizeof(int)); pa_buf = calloc((size_t)epochs * W, 4);
         if (!pa_keys || !pa_out || !pa_seed || !pa_wb || !pa_fb || !pa_buf) return 1;
     }
+    /* -U: the same stage with the Toeplitz hash, one measurement seed shared by the blocks of the call */
+    qldpc_toeplitz_ctx *tz = NULL;
+    const uint32_t **tz_keys = NULL, **tz_seeds = NULL;
+    uint32_t **tz_out = NULL, *tz_seed = NULL, *tz_buf = NULL;
+    int *tz_kb = NULL, *tz_ob = NULL;
+    double tz_best = 1e30, tz_sum = 0.0, tz_final_sum = 0.0;
+    if (toeplitz) {
+        if ((rc = qldpc_toeplitz_create(cfg.device, epochs, key_bits, key_bits, &tz))) return die("toeplitz_create", rc);
+        const size_t sw = qldpc_toeplitz_seed_words(key_bits, key_bits);
+        tz_keys = calloc((size_t)epochs, sizeof(*tz_keys)); tz_seeds = calloc((size_t)epochs, sizeof(*tz_seeds)); tz_out = calloc((size_t)epochs, sizeof(*tz_out));
+        tz_kb = calloc((size_t)epochs, sizeof(int)); tz_ob = calloc((size_t)epochs, sizeof(int)); tz_buf = calloc((size_t)epochs * W, 4); tz_seed = calloc(sw, 4);
+        if (!tz_keys || !tz_seeds || !tz_out || !tz_kb || !tz_ob || !tz_buf || !tz_seed) return 1;
+        for (size_t w = 0; w < sw; w++) tz_seed[w] = (uint32_t)rng_next();
+    }
     for (int rep = -1; rep < reps; rep++) {
         memcpy(work, bob, (size_t)epochs * W * 4);
         t0 = now_s();
@@ -237,6 +256,22 @@ int main(int argc, char **argv)
             if (rc) return die("privamp_blocks", rc);
             if (rep >= 0) { pa_sum += dp; final_sum += (double)bits; if (dp < pa_best) pa_best = dp; }
         }
+        if (toeplitz) {
+            int m = 0;
+            long bits = 0;
+            for (int e = 0; e < epochs; e++) {
+                if (status[e] != QLDPC_OK) continue;
+                const int ob = key_bits - qldpc_recon_leaked_bits(&msgs[e]);
+                tz_keys[m] = work + (size_t)e * W; tz_seeds[m] = tz_seed; tz_out[m] = tz_buf + (size_t)e * W; tz_kb[m] = key_bits; tz_ob[m] = ob > 0 ? ob : 0;
+                bits += tz_ob[m];
+                m++;
+            }
+            t0 = now_s();
+            rc = qldpc_toeplitz_blocks(tz, m, tz_keys, tz_kb, tz_seeds, tz_ob, tz_out);
+            const double dp = now_s() - t0;
+            if (rc) return die("toeplitz_blocks", rc);
+            if (rep >= 0) { tz_sum += dp; tz_final_sum += (double)bits; if (dp < tz_best) tz_best = dp; }
+        }
         if (rep < 0) continue;
         sum += dt;
         if (dt < best) best = dt;
@@ -266,6 +301,8 @@ int main(int argc, char **argv)
            it_mean[0] / fmax(1, per_rate[0]), it_mean[1] / fmax(1, per_rate[1]), it_mean[2] / fmax(1, per_rate[2]), it_mean[3] / fmax(1, per_rate[3]), it_max[0], it_max[1], it_max[2], it_max[3]);
     if (hash)
         printf(", \"pa_ms_mean\": %.3f, \"pa_ms_best\": %.3f, \"distill_Mbit_s_mean\": %.1f", pa_sum / reps * 1e3, pa_best * 1e3, final_sum / (sum + pa_sum) / 1e6);
+    if (toeplitz)
+        printf(", \"tpa_ms_mean\": %.3f, \"tpa_ms_best\": %.3f, \"tdistill_Mbit_s_mean\": %.1f", tz_sum / reps * 1e3, tz_best * 1e3, tz_final_sum / (sum + tz_sum) / 1e6);
     if (profile) {
         qldpc_kernel_stat st[16];
         qldpc_recon_profile_enable(rb, 1);
@@ -279,6 +316,7 @@ int main(int argc, char **argv)
     }
     printf("}\n");
     qldpc_privamp_free(pa);
+    qldpc_toeplitz_free(tz);
     qldpc_recon_free(ra);
     qldpc_recon_free(rb);
     return good == epochs ? 0 : 3;
