@@ -34,6 +34,7 @@
  *                                         qcrypto-ldpc_amd/host/ldpc_reconcile.c (packet handlers, cascade fallback, batched ingest)
  *   qldpc_privamp*                        the hash loop of privAmp_doPrivAmp         subcomponents/priv_amp.c:190-218
  *   qldpc_toeplitz*                       (not in the reference) Toeplitz hashing, the sound replacement of that loop
+ *   qldpc_mc_*                            the simulation loop itself: source, encoder, BSC, decoder, Monitor_BFER   BS/src/main.cpp:335-393
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -553,6 +554,72 @@ int    qldpc_toeplitz_blocks_dev(qldpc_toeplitz_ctx *tz, int n, const uint32_t *
 /* host mirror, for tests: the kernel's own window / fold functions (csrc/qldpc_toeplitz_core.h), the key consumed in tiles of tile_words
    (0 = the kernel's tile; every tile size gives the same words) */
 int    qldpc_toeplitz_host(const uint32_t *key_words, int key_bits, const uint32_t *seed_words, int out_bits, int tile_words, uint32_t *out_words);
+
+/* ------------------------------------------------------------------ Monte-Carlo FER loop ---- */
+/*
+ * The loop of the reference harness -- source -> encoder -> BSC -> decoder -> monitor (BS/src/main.cpp:335-393, Monitor_BFER's max_fe stop
+ * rule) -- with nothing per bit crossing the host (csrc/qldpc_mc.hip).  Frame number i is a 64-bit GLOBAL index and its content a pure
+ * function of (seed, i) (csrc/qldpc_mc_core.h): it does not depend on the batch size, the launch shape or the device, so ranks and batches
+ * take disjoint index ranges and a failed frame can be generated again alone.
+ *
+ *   generator  Philox4x32-10, key = (seed low word, seed high word)
+ *   source     info word j of frame i = output word j % 4 at counter (j / 4, 0, i_lo, i_hi), MSB-first, the bits past K cleared
+ *   channel    VN v of frame i flips iff u < T[class(v)], u = output word v % 4 at counter (v / 4, 1, i_lo, i_hi), T = floor(p 2^32) in
+ *              double on the host with p = qber (QLDPC_VN_CHANNEL), parity_ber (QLDPC_VN_PINNED: dirty disclosed parity, 0 = exact) or
+ *              0 (QLDPC_VN_PUNCTURED); rx = cw ^ flips.  A flip probability is exactly T / 2^32.
+ *
+ * vn_class (a HOST array of N classes) may be NULL: the harness's classes, QLDPC_VN_CHANNEL at info_bits_pos and QLDPC_VN_PINNED elsewhere.
+ * Status codes as everywhere: QLDPC_ESIZE for qber outside (0, 0.5) in qldpc_mc_run and outside [0, 1) in the frame calls, for a batch above
+ * the decoder's max_frames and for fail_cap < 1; QLDPC_ENODEV without a device.  qldpc_mc_run has no CPU fallback.  Everything is queued on
+ * the decoder's stream; one object is not re-entrant.  Not built: a random puncture pattern per frame, sessions / gangs as the decoder under
+ * test, a multi-GPU driver (first_frame makes sharding the caller's loop).
+ */
+typedef struct qldpc_mc qldpc_mc;
+typedef struct qldpc_mc_cfg {
+    uint64_t seed;
+    int batch;             /* frames per decoder launch, <= the decoder's max_frames; 0 = the decoder's max_frames                  */
+    int fail_cap;          /* the global indices of the first fail_cap failed frames of a run are kept (>= 1; default 1024)         */
+    double parity_ber;     /* flip probability of a pinned VN, in [0, 1)                                                             */
+    int reserved[2];       /* must be zero                                                                                           */
+} qldpc_mc_cfg;
+typedef struct qldpc_mc_result {
+    uint64_t frames;        /* frames decoded: a multiple of the batch unless max_frames cut the last batch short                    */
+    uint64_t bit_errors;    /* sum of be = popcount((decoded ^ codeword) & mask of info_bits_pos)                                    */
+    uint64_t frame_errors;  /* frames with be > 0                                                                                    */
+    uint64_t undetected;    /* ... whose hard decision nevertheless has a zero syndrome                                              */
+    uint64_t not_converged; /* frames whose hard decision has a non-zero syndrome                                                    */
+    uint64_t iter_sum, iter_max;
+    uint64_t channel_flips, channel_bits;   /* flips drawn at QLDPC_VN_CHANNEL VNs / such VNs seen: the empirical QBER               */
+    uint64_t batches;
+    uint64_t next_frame;    /* first_frame + frames: where a following run continues                                                 */
+    double decode_ms;       /* qldpc_run alone, by hipEvents: what SIM_THR of the harness means                                      */
+    double source_ms, encode_ms, channel_ms, load_ms, monitor_ms;   /* the other stages of the batches, by hipEvents: info words, encoder,
+                               BSC, qldpc_load_bits_dev, fetch + monitor                                                             */
+    double total_ms;        /* the whole call on the host's clock                                                                    */
+} qldpc_mc_result;
+
+void   qldpc_mc_cfg_default(qldpc_mc_cfg *cfg);
+/* host mirrors, no device needed: one generator call, and info words [n][ceil(K/32)] / flip words [n][ceil(N/32)] (either may be NULL)
+   of frames [first_frame, first_frame + n_frames); info_bits_pos NULL = 0 .. K-1 */
+int    qldpc_mc_philox_host(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
+int    qldpc_mc_frames_host(int K, int N, const int *info_bits_pos, const uint8_t *vn_class, uint64_t seed, double qber, double parity_ber,
+                            uint64_t first_frame, int n_frames, uint32_t *info_words, uint32_t *flip_words);
+/* dec and enc (same code, same K; info_bits_pos are the encoder's) are not owned and must outlive the object */
+int    qldpc_mc_create(qldpc_decoder *dec, qldpc_encoder *enc, const uint8_t *vn_class, const qldpc_mc_cfg *cfg, qldpc_mc **out);
+void   qldpc_mc_free(qldpc_mc *mc);
+size_t qldpc_mc_device_bytes(const qldpc_mc *mc);
+/* the source alone, for callers with a loop of their own: device rows d_info[n][ceil(K/32)], d_cw[n][ceil(N/32)] (Alice's codeword) and
+   d_rx[n][ceil(N/32)] (what Bob holds); d_rx, or d_cw and d_rx, may be NULL.  Asynchronous on the decoder's stream. */
+int    qldpc_mc_frames_dev(qldpc_mc *mc, uint64_t first_frame, int n_frames, double qber, uint32_t *d_info, uint32_t *d_cw, uint32_t *d_rx);
+/* Per batch: generate, encode, load, run, fetch, monitor, one read-back of the counters.  Stops at the first batch boundary at which
+   frame_errors >= max_frame_errors (0 = never) or max_frames is reached; the last batch may be ragged.  Counters, histogram and failed-frame
+   list start from zero in every call. */
+int    qldpc_mc_run(qldpc_mc *mc, double qber, uint64_t first_frame, uint64_t max_frames, uint64_t max_frame_errors, qldpc_mc_result *result);
+/* of the last run: frames per iteration count, n_ite + 1 bins; writes min(cap, n_ite + 1) and returns n_ite + 1 (or a status) */
+int    qldpc_mc_iter_hist(qldpc_mc *mc, uint64_t *hist, int cap);
+/* of the last run: the global indices of the failed frames kept (the first fail_cap in batch order, ascending); writes min(cap, kept) and
+   returns kept (or a status) */
+int    qldpc_mc_failed_frames(qldpc_mc *mc, uint64_t *frames, int cap);
 
 #ifdef __cplusplus
 }

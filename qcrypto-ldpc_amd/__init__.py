@@ -873,6 +873,136 @@ class Toeplitz:
             pass
 
 
+# ---- Monte-Carlo FER loop (qldpc_mc_*): frame i is a pure function of (seed, i); source, channel and monitor run on the device -------
+
+class McCfg(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("batch", C.c_int), ("fail_cap", C.c_int), ("parity_ber", C.c_double), ("reserved", C.c_int * 2)]
+
+
+class McResult(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("frames", "bit_errors", "frame_errors", "undetected", "not_converged", "iter_sum", "iter_max",
+                                          "channel_flips", "channel_bits", "batches", "next_frame")] + [(n, C.c_double) for n in ("decode_ms", "source_ms", "encode_ms", "channel_ms", "load_ms", "monitor_ms", "total_ms")]
+
+
+_u8p = C.POINTER(C.c_uint8)
+_u64p = C.POINTER(C.c_uint64)
+_sig("qldpc_mc_cfg_default", None, [C.POINTER(McCfg)])
+_sig("qldpc_mc_philox_host", C.c_int, [_up, _up, _up])
+_sig("qldpc_mc_frames_host", C.c_int, [C.c_int, C.c_int, _ip, _u8p, C.c_uint64, C.c_double, C.c_double, C.c_uint64, C.c_int, _up, _up])
+_sig("qldpc_mc_create", C.c_int, [_vp, _vp, _u8p, C.POINTER(McCfg), C.POINTER(_vp)])
+_sig("qldpc_mc_free", None, [_vp])
+_sig("qldpc_mc_device_bytes", C.c_size_t, [_vp])
+_sig("qldpc_mc_frames_dev", C.c_int, [_vp, C.c_uint64, C.c_int, C.c_double, _vp, _vp, _vp])
+_sig("qldpc_mc_run", C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(McResult)])
+_sig("qldpc_mc_iter_hist", C.c_int, [_vp, _u64p, C.c_int])
+_sig("qldpc_mc_failed_frames", C.c_int, [_vp, _u64p, C.c_int])
+
+
+def mc_philox_host(counter, key):
+    """Philox4x32-10 of a (counter[4], key[2]) -> 4 uint32 words (host mirror of the kernels' generator)"""
+    c = np.ascontiguousarray(counter, dtype=np.uint32).ravel()
+    k = np.ascontiguousarray(key, dtype=np.uint32).ravel()
+    if c.size != 4 or k.size != 2:
+        raise QldpcError(-6, "mc_philox_host: %d counter words, %d key words" % (c.size, k.size))
+    out = np.empty(4, np.uint32)
+    _chk(_L.qldpc_mc_philox_host(c.ctypes.data_as(_up), k.ctypes.data_as(_up), out.ctypes.data_as(_up)), "mc_philox_host")
+    return out
+
+
+def _mc_class_arg(vn_class, N, where):
+    if vn_class is None:
+        return None
+    cls = np.ascontiguousarray(vn_class, dtype=np.uint8).ravel()
+    if cls.size != N:
+        raise QldpcError(-6, "%s: %d VN classes, N = %d" % (where, cls.size, N))
+    return cls
+
+
+def mc_frames_host(K, N, seed, qber, first_frame, n_frames, info_bits_pos=None, vn_class=None, parity_ber=0.0):
+    """Frames [first_frame, first_frame + n_frames) of the Monte-Carlo frame definition on the host, no device needed ->
+    (info words [n, ceil(K/32)], flip words [n, ceil(N/32)]), uint32, MSB-first.  vn_class None: QLDPC_VN_CHANNEL at info_bits_pos
+    (None = 0 .. K-1), QLDPC_VN_PINNED elsewhere."""
+    K, N, n = int(K), int(N), int(n_frames)
+    pos = None
+    if info_bits_pos is not None:
+        pos = _np_i32(info_bits_pos).ravel()
+        if pos.size != K:
+            raise QldpcError(-6, "mc_frames_host: len(info_bits_pos) != K")
+    cls = _mc_class_arg(vn_class, N, "mc_frames_host")
+    info = np.zeros((max(n, 0), (max(K, 0) + 31) // 32), np.uint32)
+    flips = np.zeros((max(n, 0), (max(N, 0) + 31) // 32), np.uint32)
+    _chk(_L.qldpc_mc_frames_host(K, N, pos.ctypes.data_as(_ip) if pos is not None else None, cls.ctypes.data_as(_u8p) if cls is not None else None,
+                                 int(seed) & 0xFFFFFFFFFFFFFFFF, float(qber), float(parity_ber), int(first_frame) & 0xFFFFFFFFFFFFFFFF, n,
+                                 info.ctypes.data_as(_up), flips.ctypes.data_as(_up)), "mc_frames_host")
+    return info, flips
+
+
+class MonteCarlo:
+    """The harness's loop source -> encoder -> BSC -> decoder -> monitor on the device (qldpc_mc_*), around a Decoder and an Encoder of
+    the same code, which it keeps alive but does not own.  Frame i is a pure function of (seed, i): run() over [first_frame, first_frame +
+    max_frames) gives the same counters whatever the batch, and ranges add up."""
+
+    def __init__(self, decoder, encoder, vn_class=None, seed=0, batch=0, parity_ber=0.0, fail_cap=1024):
+        cfg = McCfg()
+        _L.qldpc_mc_cfg_default(C.byref(cfg))
+        cfg.seed, cfg.batch, cfg.fail_cap, cfg.parity_ber = int(seed) & 0xFFFFFFFFFFFFFFFF, int(batch), int(fail_cap), float(parity_ber)
+        cls = _mc_class_arg(vn_class, decoder.N, "MonteCarlo")
+        h = _vp()
+        _chk(_L.qldpc_mc_create(decoder._h, encoder._h, cls.ctypes.data_as(_u8p) if cls is not None else None, C.byref(cfg), C.byref(h)), "MonteCarlo")
+        self._h = h
+        self.decoder, self.encoder = decoder, encoder
+        self.N, self.K, self.device = decoder.N, decoder.K, decoder.device
+        self.seed, self.batch, self.fail_cap, self.parity_ber = int(seed), int(batch) or decoder.max_frames, int(fail_cap), float(parity_ber)
+
+    @property
+    def device_bytes(self):
+        return int(_L.qldpc_mc_device_bytes(self._h))
+
+    def run(self, qber, first_frame=0, max_frames=None, max_frame_errors=0):
+        """-> dict of the counters (frames, bit_errors, frame_errors, undetected, not_converged, iter_sum, iter_max, channel_flips,
+        channel_bits, batches, next_frame, decode_ms and the other stages' source_ms .. monitor_ms by hipEvents, total_ms).  Stops at the first batch boundary with frame_errors >= max_frame_errors
+        (0 = never) or after max_frames (None = one batch)."""
+        res = McResult()
+        n = self.batch if max_frames is None else int(max_frames)
+        _chk(_L.qldpc_mc_run(self._h, float(qber), int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, int(max_frame_errors), C.byref(res)), "MonteCarlo.run")
+        return {name: getattr(res, name) for name, _ in McResult._fields_}
+
+    def frames(self, first_frame, n_frames, qber):
+        """the source alone -> device int32 tensors (info [n, ceil(K/32)], cw [n, ceil(N/32)], rx [n, ceil(N/32)]): what
+        mc_frames_host gives, the codeword by the encoder, rx = cw ^ flips"""
+        torch = _torch()
+        n = int(n_frames)
+        dev = "cuda:%d" % self.device
+        info = torch.empty((n, (self.K + 31) // 32), dtype=torch.int32, device=dev)
+        cw = torch.empty((n, (self.N + 31) // 32), dtype=torch.int32, device=dev)
+        rx = torch.empty_like(cw)
+        _chk(_L.qldpc_mc_frames_dev(self._h, int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, float(qber), _vp(info.data_ptr()), _vp(cw.data_ptr()),
+                                    _vp(rx.data_ptr())), "MonteCarlo.frames")
+        self.decoder.sync()
+        return info, cw, rx
+
+    def iter_hist(self):
+        """frames per iteration count of the last run, n_ite + 1 bins (uint64)"""
+        out = np.zeros(1, np.uint64)
+        bins = _chk(_L.qldpc_mc_iter_hist(self._h, out.ctypes.data_as(_u64p), 1), "MonteCarlo.iter_hist")      # the call returns n_ite + 1
+        if bins > 1:
+            out = np.zeros(bins, np.uint64)
+            _chk(_L.qldpc_mc_iter_hist(self._h, out.ctypes.data_as(_u64p), bins), "MonteCarlo.iter_hist")
+        return out
+
+    def failed_frames(self):
+        """global indices of the failed frames of the last run that were kept (the first fail_cap), ascending (uint64)"""
+        out = np.zeros(self.fail_cap, np.uint64)
+        n = _chk(_L.qldpc_mc_failed_frames(self._h, out.ctypes.data_as(_u64p), out.size), "MonteCarlo.failed_frames")
+        return out[:n].copy()
+
+    def __del__(self):
+        try:
+            _L.qldpc_mc_free(self._h)
+        except Exception:
+            pass
+
+
 def crc32_words(words, n_bits, lanes=0):
     """CRC-32 of the key bits; lanes > 0: the chunked fold the device verification uses (same value)"""
     w = np.ascontiguousarray(words, dtype=np.uint32)

@@ -16,6 +16,10 @@
  *                  [-R (with -e: report every random pattern -- one per batch -- and keep the best; -o file writes its VN indices)]
  *                  [-Q 32|16|8 (message storage: fp32 = the AFF3CT float build, binary16, 8-bit fixed-point min-sum)]
  *                  [-e f (puncture parity bits to reach the rate min_cr(ber, f); random pattern re-drawn per batch, main.cpp:321-333,359-362)]
+ *                  [-D (the loop on the device: qldpc_mc_run generates, encodes, decodes and counts, nothing per bit crosses the host; frames
+ *                      [0, frames_per_ber) of seed -S at every BER, so the rows of a table share their random numbers; SIM_THR is the decode
+ *                      time by hipEvents; -e and -R are host-only and refused)]
+ *                  [-E n (with -D: stop a BER point at the first batch boundary with n frame errors, Monitor_BFER's max_fe)]
  */
 #include <math.h>
 #include <stdint.h>
@@ -52,7 +56,8 @@ static int die(const char *what, int rc)
 
 int main(int argc, char **argv)
 {
-    int N = 8192, K = 6554, n_ite = 50, frames = 256, batch = 256, layered = 0, synd = 1, peg = 0, msg_bits = 32, search = 0, opt;
+    int N = 8192, K = 6554, n_ite = 50, frames = 256, batch = 256, layered = 0, synd = 1, peg = 0, msg_bits = 32, search = 0, on_device = 0, opt;
+    uint64_t max_fe = 0;
     const char *pattern_out = NULL;
     double parity_ber = 0.0;      /* > 0: the disclosed parity bits are themselves wrong with this probability (main.cpp (test effect of dirty parities)) */
     double target_eff = 0.0;      /* > 0: puncture parity bits up to min_cr(ber, f), as BS/src/main.cpp:235-333 does */
@@ -61,7 +66,7 @@ int main(int argc, char **argv)
     double ber_min = 0.01, ber_max = 0.03, ber_step = 0.005;
     uint64_t seed = 0;
     const char *g_method = NULL;
-    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:Rlvn")) != -1) {
+    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:DRlvn")) != -1) {
         switch (opt) {
         case 'N': N = atoi(optarg); break;
         case 'K': K = atoi(optarg); break;
@@ -79,6 +84,8 @@ int main(int argc, char **argv)
         case 'd': parity_ber = atof(optarg); break;
         case 'Q': msg_bits = atoi(optarg); break;
         case 'R': search = 1; break;
+        case 'D': on_device = 1; break;
+        case 'E': max_fe = strtoull(optarg, NULL, 0); break;
         case 'o': pattern_out = optarg; break;
         case 'G': g_method = optarg; break;      /* p.G_method (VAR/main.cpp (alist-v1.0.1):135): IDENTITY | LU_DEC; QC = Encoder_LDPC_from_QC ((qc):145) */
         case 'l': layered = 1; break;
@@ -91,6 +98,8 @@ int main(int argc, char **argv)
     int rule = -1;
     for (int i = 0; i < 8; i++) if (!strcmp(rule_name, names[i])) rule = i;
     if (rule < 0) { fprintf(stderr, "unknown rule %s\n", rule_name); return 2; }
+    if (on_device && (target_eff > 0.0 || search)) { fprintf(stderr, "qldpc_sim: -e and -R draw a puncture pattern per batch on the host and do not run with -D\n"); return 2; }
+    if (max_fe && !on_device) { fprintf(stderr, "qldpc_sim: -E needs -D\n"); return 2; }
 
     qldpc_code *H = NULL;
     int rc = alist ? qldpc_code_from_alist(alist, &H) : qc ? qldpc_code_from_qc(qc, &H) : peg ? qldpc_code_ira_peg(N, K, 0.125f, 11, 3, peg, 7, &H) : qldpc_code_ira(N, K, 0.125f, 11, 3, 7, &H);
@@ -119,6 +128,26 @@ int main(int argc, char **argv)
     printf("#    ** Est. QKD Key Rate After Priv Amp = %f\n", (double)(K - (N - K)) / (double)K);
     printf("# %8s | %8s | %8s | %8s | %9s | %9s | %10s\n", "EP", "FRA", "BE", "FE", "BER", "FER", "SIM_THR");
     printf("# %8s | %8s | %8s | %8s | %9s | %9s | %10s\n", "", "", "", "", "", "", "(Mb/s)");
+
+    if (on_device) {      /* the same table, every row one qldpc_mc_run */
+        qldpc_mc_cfg mcfg;
+        qldpc_mc_cfg_default(&mcfg);
+        mcfg.seed = seed; mcfg.batch = batch; mcfg.parity_ber = parity_ber;
+        qldpc_mc *mc = NULL;
+        if ((rc = qldpc_mc_create(dec, enc, NULL, &mcfg, &mc))) return die("mc_create", rc);      /* NULL: info VNs through the BSC, the others pinned, as below */
+        for (double ber = ber_min; ber <= ber_max + 1e-12; ber += ber_step) {
+            qldpc_mc_result r;
+            if ((rc = qldpc_mc_run(mc, ber, 0, (uint64_t)(frames > 0 ? frames : 0), max_fe, &r))) return die("mc_run", rc);
+            printf("  %8.4f | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", ber, (unsigned long long)r.frames, (unsigned long long)r.bit_errors,
+                   (unsigned long long)r.frame_errors, (double)r.bit_errors / ((double)r.frames * K), (double)r.frame_errors / (double)r.frames,
+                   (double)r.frames * K / (r.decode_ms * 1e-3) / 1e6);
+            fflush(stdout);
+        }
+        qldpc_mc_free(mc);
+        qldpc_decoder_free(dec); qldpc_encoder_free(enc); qldpc_code_free(H);
+        free(pos); free(is_info);
+        return 0;
+    }
 
     int *ref_bits = (int *)malloc(sizeof(int) * (size_t)batch * K), *enc_bits = (int *)malloc(sizeof(int) * (size_t)batch * N);
     int *dec_bits = (int *)malloc(sizeof(int) * (size_t)batch * K);

@@ -1,0 +1,263 @@
+"""Monte-Carlo FER loop on the device (qldpc_mc_*): the frames against the host mirror word for word, and every counter of
+MonteCarlo.run against numpy over mc_frames_host -> CPU oracle -> compare.  Exact equality everywhere."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import mc_ref
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIM = os.path.join(ROOT, "qcrypto-ldpc_amd", "host", "qldpc_sim")
+SEED = 0x0123456789ABCDEF
+FAR = 2 ** 32 - 100
+N_ITE = 20
+# chosen by the scan recorded in the docstring of test_run_equals_the_oracle_counter_for_counter
+QBER = {"peg": 0.26, "ira": 0.03}          # every class fails between 10 % and 90 % of 192 frames
+QBER_DEAD = {"peg": 0.40, "ira": 0.06}     # every frame fails
+KINDS = {"flood": dict(schedule="flooding"), "hlay": dict(schedule="hlayered"), "i8": dict(schedule="flooding", msg_dtype="i8")}
+COUNTERS = ("frames", "bit_errors", "frame_errors", "undetected", "not_converged", "iter_sum", "iter_max", "channel_flips", "channel_bits")
+
+
+class _Setup:
+    def __init__(self, q, O, name):
+        self.name = name
+        self.code = q.Code.from_alist(os.path.join(ROOT, "tests", "golden", "PEGReg504x1008.alist")) if name == "peg" else q.Code.ira(2000, 1590)
+        self.enc = q.Encoder(self.code, "IDENTITY" if name == "peg" else "IRA")
+        self.K, self.N, self.pos = self.enc.K, self.code.N, self.enc.info_bits_pos
+        assert (self.K, self.N) == ((504, 1008) if name == "peg" else (1590, 2000))
+        self.cls = mc_ref.classes(self.K, self.N, self.pos)
+        var, chk = self.code.edges()
+        self.og = O.Graph.from_edges(self.N, self.code.M, var, chk)
+        order, _, _ = self.code.layer_order()                        # the layered oracle visits the checks in the code's layer order
+        inv = np.empty(self.code.M, np.int32)
+        inv[order] = np.arange(self.code.M, dtype=np.int32)
+        newc = inv[chk]
+        idx = np.argsort(newc, kind="stable")
+        self.ogl = O.Graph.from_edges(self.N, self.code.M, var[idx], newc[idx])
+        self._ref, self._dec, self.q, self.O = {}, {}, q, O
+
+    def decoder(self, kind, n_frames=192):
+        key = (kind, n_frames)
+        if key not in self._dec:
+            self._dec[key] = self.q.Decoder(self.code, self.K, N_ITE, info_bits_pos=self.pos, rule="NMS", rule_param=0.75, n_frames=n_frames, **KINDS[kind])
+        return self._dec[key]
+
+    def codewords(self, info_words):
+        info = mc_ref.unpack(info_words, self.K)
+        cw = self.enc.encode(info)
+        assert (cw[:, self.pos] == info).all()
+        for x in cw[:3]:
+            assert self.og.syndrome(x)[0] == 0
+        return cw
+
+    def reference(self, kind, qber, first, n):
+        """counters, histogram and failed frames of frames [first, first + n) by numpy: mc_frames_host -> oracle -> compare; computed once"""
+        key = (kind, qber, first, n)
+        if key in self._ref:
+            return self._ref[key]
+        q, O = self.q, self.O
+        info_w, flip_w = q.mc_frames_host(self.K, self.N, SEED, qber, first, n, info_bits_pos=self.pos)
+        cw = self.codewords(info_w)
+        flips = mc_ref.unpack(flip_w, self.N)
+        y = cw ^ flips
+        mag, pin = np.float32(q.bsc_llr(qber)), np.float32(q.CONFIRMED_BIT_LLR)
+        llr = np.where(y == 1, -mag, mag).astype(np.float32)
+        llr[:, self.cls == 1] = np.where(y[:, self.cls == 1] == 1, -pin, pin)
+        if kind == "flood":
+            r = O.decode(self.og, llr, "NMS", 0.75, N_ITE, n_threads=8)
+        elif kind == "hlay":
+            r = O.decode(self.ogl, llr, "NMS", 0.75, N_ITE, "hlayered", n_threads=8)
+        else:
+            r = O.decode(self.og, llr, "NMS", 0.75, N_ITE, n_threads=8, msg_i8=True, quant_scale=8.0)
+        be = (r["hard"][:, self.pos] != cw[:, self.pos]).sum(1)
+        ok, it = r["synd_ok"] != 0, r["iters"]
+        ctr = dict(frames=n, bit_errors=int(be.sum()), frame_errors=int((be > 0).sum()), undetected=int(((be > 0) & ok).sum()),
+                   not_converged=int((~ok).sum()), iter_sum=int(it.sum()), iter_max=int(it.max()),
+                   channel_flips=int(flips[:, self.cls == 0].sum()), channel_bits=n * int((self.cls == 0).sum()))
+        assert ctr["channel_flips"] == mc_ref.popcount(flip_w)             # parity_ber = 0: every flip is a channel flip
+        out = (ctr, np.bincount(it, minlength=N_ITE + 1).astype(np.uint64), (first + np.nonzero(be > 0)[0]).astype(np.uint64))
+        self._ref[key] = out
+        return out
+
+
+@pytest.fixture(scope="module")
+def setups(q, O):
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            cache[name] = _Setup(q, O, name)
+        return cache[name]
+    return get
+
+
+def u32(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+def counters(res):
+    return {k: int(res[k]) for k in COUNTERS}
+
+
+@pytest.mark.parametrize("name", ["peg", "ira"])
+@pytest.mark.parametrize("first,n", [(0, 192), (FAR, 192), (3, 70)])
+def test_device_frames_equal_the_host_mirror(q, setups, name, first, n):
+    s = setups(name)
+    mc = q.MonteCarlo(s.decoder("flood"), s.enc, seed=SEED)
+    info, cw, rx = (u32(t) for t in mc.frames(first, n, 0.07))
+    ref_info, ref_flips = q.mc_frames_host(s.K, s.N, SEED, 0.07, first, n, info_bits_pos=s.pos)
+    ref_cw = mc_ref.pack(s.codewords(ref_info))
+    assert info.shape == ref_info.shape and (info == ref_info).all()
+    assert cw.shape == ref_cw.shape and (cw == ref_cw).all()
+    assert (rx == ref_cw ^ ref_flips).all() and ref_flips.any()
+
+
+@pytest.mark.parametrize("name", ["peg", "ira"])
+def test_device_frames_with_punctured_vns_and_dirty_parity(q, setups, name):
+    s = setups(name)
+    cls = s.cls.copy()
+    cls[np.nonzero(cls == 1)[0][::5]] = q.VN_PUNCTURED
+    mc = q.MonteCarlo(s.decoder("flood"), s.enc, vn_class=cls, seed=SEED + 1, parity_ber=0.25)
+    info, cw, rx = (u32(t) for t in mc.frames(FAR + 90, 33, 0.11))
+    ref_info, ref_flips = q.mc_frames_host(s.K, s.N, SEED + 1, 0.11, FAR + 90, 33, vn_class=cls, parity_ber=0.25)
+    assert (info == ref_info).all() and (rx ^ cw == ref_flips).all()
+    f = mc_ref.unpack(ref_flips, s.N)
+    assert f[:, cls == 1].any() and not f[:, cls == 2].any()
+
+
+@pytest.mark.parametrize("kind", sorted(KINDS))
+@pytest.mark.parametrize("name", ["peg", "ira"])
+def test_run_equals_the_oracle_counter_for_counter(q, setups, name, kind):
+    """Every counter, the histogram and the failed-frame list against numpy over mc_frames_host -> oracle -> compare; the oracle must fail
+    between 10 % and 90 % of the 192 frames (asserted first).  QBER per code:
+    Chosen by a scan with the oracle on the CPU (frames [0, 192) of SEED, NMS 0.75, 20 iterations, all-zero codeword; failed frames of 192):
+      PEGReg504x1008, IDENTITY encoder (the 504 parity VNs pinned, so the waterfall lies far above the code's BSC threshold):
+          qber   0.22  0.24  0.26  0.28  0.30  0.36
+          flood     9    52   115   166   187   192
+          hlay      0    14    62   135   172   192
+          i8       14    56   126   171   188   192
+      IRA(2000, 1590), the 410 parity VNs pinned:
+          qber   0.020 0.025 0.030 0.035 0.040 0.045
+          flood     2    33   120   175   191   192
+          hlay      0    13    66   146   185   192
+          i8        2    34   117   173   191   192
+    -> 0.26 (PEG) and 0.03 (IRA); the frames of the test carry the source's codewords instead of the all-zero one."""
+    s = setups(name)
+    ctr, hist, failed = s.reference(kind, QBER[name], 0, 192)
+    print(name, kind, ctr)
+    assert 0.1 * 192 <= ctr["frame_errors"] <= 0.9 * 192
+    mc = q.MonteCarlo(s.decoder(kind), s.enc, seed=SEED)
+    res = mc.run(QBER[name], 0, 192)
+    assert counters(res) == ctr
+    assert res["batches"] == 1 and res["next_frame"] == 192 and res["decode_ms"] > 0
+    assert (mc.iter_hist() == hist).all() and int(hist.sum()) == 192
+    assert (mc.failed_frames() == failed).all()
+
+
+def test_spa_is_a_tolerance_class_frames_and_flips_only(q, setups):
+    s = setups("peg")
+    dec = q.Decoder(s.code, s.K, N_ITE, info_bits_pos=s.pos, rule="SPA", n_frames=192)
+    res = q.MonteCarlo(dec, s.enc, seed=SEED).run(QBER["peg"], 0, 192)
+    flips = q.mc_frames_host(s.K, s.N, SEED, QBER["peg"], 0, 192, info_bits_pos=s.pos)[1]
+    assert res["frames"] == 192 and res["channel_flips"] == mc_ref.popcount(flips) and res["channel_bits"] == 192 * s.K
+
+
+@pytest.mark.parametrize("name,kind", [("ira", "flood"), ("peg", "i8"), ("ira", "hlay")])
+def test_batch_and_range_invariance(q, setups, name, kind):
+    s = setups(name)
+    qber = QBER[name]
+    dec = s.decoder(kind, 512)
+    one = q.MonteCarlo(dec, s.enc, seed=SEED, batch=512)
+    r1 = one.run(qber, 0, 512)
+    h1, f1 = one.iter_hist(), one.failed_frames()
+    assert r1["batches"] == 1 and r1["frames"] == 512 and 0 < r1["frame_errors"] < 512
+    assert r1["channel_flips"] == mc_ref.popcount(q.mc_frames_host(s.K, s.N, SEED, qber, 0, 512, info_bits_pos=s.pos)[1])
+    three = q.MonteCarlo(dec, s.enc, seed=SEED, batch=192)
+    r3 = three.run(qber, 0, 512)                                          # 192 + 192 + 128
+    assert r3["batches"] == 3 and counters(r3) == counters(r1)
+    assert (three.iter_hist() == h1).all() and (three.failed_frames() == f1).all()
+    ra = three.run(qber, 0, 200)                                          # 192 + 8
+    ha, fa = three.iter_hist(), three.failed_frames()
+    rb = one.run(qber, ra["next_frame"], 312)
+    assert ra["next_frame"] == 200 and ra["batches"] == 2 and rb["next_frame"] == 512
+    for k in COUNTERS:
+        assert (max(ra[k], rb[k]) if k == "iter_max" else ra[k] + rb[k]) == r1[k], k
+    assert (ha + one.iter_hist() == h1).all() and (np.concatenate([fa, one.failed_frames()]) == f1).all()
+    # the small decoder of the oracle test sees the same first 192 frames
+    ctr, _, failed = s.reference(kind, qber, 0, 192)
+    assert (f1[f1 < 192] == failed).all()
+
+
+def test_stop_rule(q, setups):
+    s = setups("peg")
+    qber = QBER_DEAD["peg"]
+    ctr, _, _ = s.reference("flood", qber, 0, 192)
+    assert ctr["frame_errors"] == 192                                     # the oracle fails every frame here
+    mc = q.MonteCarlo(s.decoder("flood"), s.enc, seed=SEED, batch=192, fail_cap=200)
+    r = mc.run(qber, 0, 1920, max_frame_errors=1)
+    assert r["batches"] == 1 and r["frames"] == 192 and r["next_frame"] == 192 and counters(r) == ctr
+    r = mc.run(qber, 0, 1920, max_frame_errors=193)                       # reached inside the second batch: stops at its end
+    assert r["batches"] == 2 and r["frames"] == 384
+    r = mc.run(qber, 0, 1920, max_frame_errors=0)
+    assert r["batches"] == 10 and r["frames"] == 1920 and r["frame_errors"] == 1920
+    kept = mc.failed_frames()                                             # the first fail_cap failures, in batch order
+    assert kept.size == 200 and (kept[:192] == np.arange(192)).all() and (kept[192:] >= 192).all() and (kept[192:] < 384).all()
+
+
+def test_qldpc_sim_device_loop_prints_the_same_row(q, setups):
+    s = setups("peg")
+    if not os.path.exists(SIM):
+        subprocess.check_call(["make", "-C", os.path.dirname(SIM)])
+    alist = os.path.join(ROOT, "tests", "golden", "PEGReg504x1008.alist")
+    args = [SIM, "-a", alist, "-r", "NMS", "-p", "0.75", "-i", str(N_ITE), "-b", "192", "-s", "0.26:0.26:0.01", "-S", str(SEED), "-D"]
+
+    def row(extra):
+        p = subprocess.run(args + extra, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stdout + p.stderr
+        rows = [l for l in p.stdout.splitlines() if not l.startswith("#") and "|" in l]
+        assert len(rows) == 1
+        f = [x.strip() for x in rows[0].split("|")]
+        return dict(fra=int(f[1]), be=int(f[2]), fe=int(f[3]), thr=float(f[6]))
+
+    mc = q.MonteCarlo(s.decoder("flood"), s.enc, seed=SEED)
+    res = mc.run(0.26, 0, 500)                                            # 192 + 192 + 116
+    got = row(["-f", "500"])
+    assert (got["fra"], got["be"], got["fe"]) == (res["frames"], res["bit_errors"], res["frame_errors"]) and got["fra"] == 500 and got["thr"] > 0
+    res = mc.run(0.26, 0, 1920, max_frame_errors=1)
+    got = row(["-f", "1920", "-E", "1"])
+    assert (got["fra"], got["be"], got["fe"]) == (res["frames"], res["bit_errors"], res["frame_errors"]) and got["fra"] == 192
+    for refused in (["-e", "1.6"], ["-e", "1.6", "-R"]):                   # a random puncture pattern per batch stays host-only
+        p = subprocess.run(args + ["-f", "192"] + refused, capture_output=True, text=True, timeout=60)
+        assert p.returncode != 0 and "-D" in p.stderr
+
+
+def test_errors_leave_everything_usable(q, setups):
+    s = setups("peg")
+    dec = s.decoder("flood")
+    ctr, _, _ = s.reference("flood", QBER["peg"], 0, 192)
+    mc = q.MonteCarlo(dec, s.enc, seed=SEED)
+    for bad in (0.0, 0.5, -0.1, 0.7, float("nan")):
+        with pytest.raises(q.QldpcError) as e:
+            mc.run(bad, 0, 192)
+        assert e.value.status == -6, bad
+    assert counters(mc.run(QBER["peg"], 0, 192)) == ctr
+    for bad in (-0.01, 1.0):
+        with pytest.raises(q.QldpcError) as e:
+            mc.frames(0, 4, bad)
+        assert e.value.status == -6
+    assert mc.frames(0, 4, 0.0)[2].shape == (4, 32)                       # [0, 1) in the frame calls: 0 is no flips
+    for kw in (dict(batch=193), dict(batch=-1), dict(fail_cap=0), dict(parity_ber=1.0)):
+        with pytest.raises(q.QldpcError) as e:
+            q.MonteCarlo(dec, s.enc, seed=SEED, **kw)
+        assert e.value.status == -6, kw
+    with pytest.raises(q.QldpcError):
+        q.MonteCarlo(dec, setups("ira").enc, seed=SEED)                   # an encoder of another code
+    small = q.MonteCarlo(dec, s.enc, seed=SEED, batch=100, fail_cap=5)    # the same decoder serves a following good object
+    r = small.run(QBER["peg"], 0, 192)
+    assert counters(r) == ctr and r["batches"] == 2 and small.device_bytes > 0
+    kept = small.failed_frames()
+    assert kept.size == 5 and r["frame_errors"] > 5 and (np.diff(kept.astype(np.int64)) > 0).all() and (kept < 100).all()
+    assert counters(mc.run(QBER["peg"], 0, 192)) == ctr
