@@ -35,6 +35,7 @@
  *   qldpc_privamp*                        the hash loop of privAmp_doPrivAmp         subcomponents/priv_amp.c:190-218
  *   qldpc_toeplitz*                       (not in the reference) Toeplitz hashing, the sound replacement of that loop
  *   qldpc_mc_*                            the simulation loop itself: source, encoder, BSC, decoder, Monitor_BFER   BS/src/main.cpp:335-393
+ *   qldpc_mc_search / _patterns_dev       the puncture-pattern search around it: shuffle, erase, first FER = 0 / n  BS/src/main.cpp:235-411
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -573,6 +574,33 @@ int    qldpc_toeplitz_host(const uint32_t *key_words, int key_bits, const uint32
  * the decoder's max_frames and for fail_cap < 1; QLDPC_ENODEV without a device.  qldpc_mc_run has no CPU fallback.  Everything is queued on
  * the decoder's stream; one object is not re-entrant.  Not built: a random puncture pattern per frame, sessions / gangs as the decoder under
  * test, a multi-GPU driver (first_frame makes sharding the caller's loop).
+ *
+ * Puncture patterns and the search over them (BS/src/main.cpp:235-411: shuffle the parity positions, erase the first bits_to_puncture of the
+ * shuffle -- LLRs[pattern[i]] = 0 --, simulate, keep the first shuffle that goes through with FER = 0 / n).  Pattern p (a 64-bit GLOBAL
+ * index) is a pure function of (seed, p, n_cand, n_punct, key_bits), like the frames independent of batch, launch shape and device:
+ *
+ *   candidates an ascending list of distinct VNs cand[0 .. n_cand-1]; default: every QLDPC_VN_PINNED VN of the class map, ascending (with the
+ *              harness's classes the parity VNs, its `for a = K .. N-1`)
+ *   key        u_c = output word c % 4 of the generator at counter (c / 4, 2, p_lo, p_hi), key = (seed low word, seed high word);
+ *              u'_c = u_c >> (32 - key_bits)
+ *   selection  the n_punct candidates smallest in the lexicographic order (u'_c, c), 0 <= n_punct <= n_cand: equal keys go to the lower
+ *              candidate index.  A uniformly random subset, up to 32-bit key collisions broken by index.
+ *
+ * key_bits is 32 in production and 0 stands for 32; smaller values exist so that TESTS can force equal keys and reach the tie rule (as
+ * tile_words of qldpc_toeplitz_host and lanes of qldpc_crc32_words_chunked).  A pattern is an erase row of ceil(N / 32) words, MSB-first; an
+ * erasure overrides whatever the frame holds at that VN (qldpc_load_erasures_dev).
+ *
+ * qldpc_mc_search: frame k of pattern p is Monte-Carlo frame first_frame + p F + k (F = frames_per_pattern), so the counter row of a pattern is
+ * a pure function of (seed, p, F, first_frame, n_punct, key_bits, qber, candidates, decoder configuration) and depends neither on the batch
+ * nor on first_pattern nor on how a search is split into calls.  A round is floor(batch / F) patterns in one generate / load / erase / run /
+ * fetch / monitor sequence with one read-back of its counter rows; the last round may be ragged.  With stop_at_goal the search stops after the
+ * first round that holds a pattern without frame errors; `patterns` is therefore round-granular (as `frames` of qldpc_mc_run), goal, best and
+ * the rows are not.  Status codes: QLDPC_ESIZE for n_punct outside [0, n_cand], frames_per_pattern outside [1, batch], key_bits outside
+ * 0 .. 32, qber outside (0, 0.5); QLDPC_EINVAL for a candidate or puncture list that is not ascending, distinct and inside [0, N) and for
+ * non-zero reserved fields.  A refused call queues nothing.  What the pattern calls need on the device is allocated by the first
+ * qldpc_mc_search / qldpc_mc_patterns_dev / qldpc_mc_set_puncture (and counted by qldpc_mc_device_bytes); later calls allocate nothing.
+ * Not built: patterns per frame rather than per pattern slot, common frames across patterns, shortening patterns, feeding a found pattern
+ * into qldpc_recon_*.
  */
 typedef struct qldpc_mc qldpc_mc;
 typedef struct qldpc_mc_cfg {
@@ -620,6 +648,46 @@ int    qldpc_mc_iter_hist(qldpc_mc *mc, uint64_t *hist, int cap);
 /* of the last run: the global indices of the failed frames kept (the first fail_cap in batch order, ascending); writes min(cap, kept) and
    returns kept (or a status) */
 int    qldpc_mc_failed_frames(qldpc_mc *mc, uint64_t *frames, int cap);
+
+/* host mirror, no device needed: the candidate indices (into the candidate list) of pattern `pattern`, ascending */
+int    qldpc_mc_pattern_host(uint64_t seed, uint64_t pattern, int n_cand, int n_punct, int key_bits, int *idx /* n_punct */);
+/* the candidate VNs of the object (a HOST array): ascending, distinct, inside [0, N); NULL = every QLDPC_VN_PINNED VN of the class map */
+int    qldpc_mc_set_candidates(qldpc_mc *mc, const int *vn, int n);
+/* erase rows of patterns [first_pattern, first_pattern + n_patterns): d_erase[n_patterns][ceil(N/32)], MSB-first; asynchronous on the
+   decoder's stream */
+int    qldpc_mc_patterns_dev(qldpc_mc *mc, uint64_t first_pattern, int n_patterns, int n_punct, int key_bits, uint32_t *d_erase);
+/* the VNs of a pattern over the object's candidates, ascending (host side) */
+int    qldpc_mc_pattern_vns(qldpc_mc *mc, uint64_t pattern, int n_punct, int key_bits, int *vn /* n_punct */);
+/* a fixed puncture set for qldpc_mc_run (a HOST array, ascending, distinct): these VNs are erased in every frame, everything else of the run is
+   unchanged, so its counters equal the search's row of that pattern over the same frames.  n = 0 clears it: the run then issues exactly the
+   launches it issues without this call. */
+int    qldpc_mc_set_puncture(qldpc_mc *mc, const int *vn, int n);
+
+typedef struct qldpc_mc_search_cfg {
+    int n_punct;              /* VNs erased per pattern, 0 .. n_cand                                                                  */
+    int frames_per_pattern;   /* F, 1 .. batch                                                                                        */
+    int key_bits;             /* 0 = 32; below 32 for tests only                                                                      */
+    int stop_at_goal;         /* stop after the first round that holds a pattern without frame errors                                 */
+    uint64_t first_frame;
+    int reserved[2];          /* must be zero                                                                                         */
+} qldpc_mc_search_cfg;
+typedef struct qldpc_mc_pattern_stat { uint64_t pattern, frames, frame_errors, bit_errors, undetected, not_converged, iter_sum; } qldpc_mc_pattern_stat;
+typedef struct qldpc_mc_search_result {
+    uint64_t patterns, frames, batches;   /* evaluated: whole rounds                                                                  */
+    uint64_t goal;            /* lowest pattern index with 0 frame errors in its F frames; UINT64_MAX = none                          */
+    uint64_t best, best_frame_errors, best_bit_errors;   /* fewest frame errors, then fewest bit errors, then lowest index            */
+    uint64_t next_pattern;    /* first_pattern + patterns                                                                             */
+    double decode_ms;         /* qldpc_run alone, by hipEvents                                                                        */
+    double pattern_ms, expand_ms, generate_ms, load_ms, erase_ms, monitor_ms;   /* the other stages of the rounds, by hipEvents: pattern
+                                 kernel, rows -> frame rows, source + encoder + BSC, qldpc_load_bits_dev, qldpc_load_erasures_dev,
+                                 fetch + per-pattern monitor                                                                          */
+    double total_ms;          /* the whole call on the host's clock                                                                   */
+} qldpc_mc_search_result;
+/* patterns [first_pattern, first_pattern + max_patterns) in rounds, see above */
+int    qldpc_mc_search(qldpc_mc *mc, double qber, const qldpc_mc_search_cfg *cfg, uint64_t first_pattern, uint64_t max_patterns,
+                       qldpc_mc_search_result *res);
+/* of the last search: one row per evaluated pattern, in pattern order; writes min(cap, count) and returns the count (or a status) */
+int    qldpc_mc_search_stats(qldpc_mc *mc, qldpc_mc_pattern_stat *rows, int cap);
 
 #ifdef __cplusplus
 }

@@ -898,6 +898,28 @@ _sig("qldpc_mc_iter_hist", C.c_int, [_vp, _u64p, C.c_int])
 _sig("qldpc_mc_failed_frames", C.c_int, [_vp, _u64p, C.c_int])
 
 
+class McSearchCfg(C.Structure):
+    _fields_ = [("n_punct", C.c_int), ("frames_per_pattern", C.c_int), ("key_bits", C.c_int), ("stop_at_goal", C.c_int), ("first_frame", C.c_uint64),
+                ("reserved", C.c_int * 2)]
+
+
+class McSearchResult(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("patterns", "frames", "batches", "goal", "best", "best_frame_errors", "best_bit_errors", "next_pattern")] + [
+        (n, C.c_double) for n in ("decode_ms", "pattern_ms", "expand_ms", "generate_ms", "load_ms", "erase_ms", "monitor_ms", "total_ms")]
+
+
+MC_PATTERN_STAT = np.dtype([(n, np.uint64) for n in ("pattern", "frames", "frame_errors", "bit_errors", "undetected", "not_converged", "iter_sum")])
+MC_NO_PATTERN = 0xFFFFFFFFFFFFFFFF          # goal / best of a search that found none
+
+_sig("qldpc_mc_pattern_host", C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _ip])
+_sig("qldpc_mc_set_candidates", C.c_int, [_vp, _ip, C.c_int])
+_sig("qldpc_mc_patterns_dev", C.c_int, [_vp, C.c_uint64, C.c_int, C.c_int, C.c_int, _vp])
+_sig("qldpc_mc_pattern_vns", C.c_int, [_vp, C.c_uint64, C.c_int, C.c_int, _ip])
+_sig("qldpc_mc_set_puncture", C.c_int, [_vp, _ip, C.c_int])
+_sig("qldpc_mc_search", C.c_int, [_vp, C.c_double, C.POINTER(McSearchCfg), C.c_uint64, C.c_uint64, C.POINTER(McSearchResult)])
+_sig("qldpc_mc_search_stats", C.c_int, [_vp, _vp, C.c_int])
+
+
 def mc_philox_host(counter, key):
     """Philox4x32-10 of a (counter[4], key[2]) -> 4 uint32 words (host mirror of the kernels' generator)"""
     c = np.ascontiguousarray(counter, dtype=np.uint32).ravel()
@@ -935,6 +957,15 @@ def mc_frames_host(K, N, seed, qber, first_frame, n_frames, info_bits_pos=None, 
                                  int(seed) & 0xFFFFFFFFFFFFFFFF, float(qber), float(parity_ber), int(first_frame) & 0xFFFFFFFFFFFFFFFF, n,
                                  info.ctypes.data_as(_up), flips.ctypes.data_as(_up)), "mc_frames_host")
     return info, flips
+
+
+def mc_pattern_host(seed, pattern, n_cand, n_punct, key_bits=32):
+    """Puncture pattern `pattern` of the Monte-Carlo pattern definition on the host, no device needed -> the n_punct chosen candidate
+    indices (into an ascending candidate list of n_cand entries), ascending, int32.  key_bits below 32 coarsens the keys (tests only)."""
+    idx = np.full(max(int(n_punct), 0), -1, np.int32)
+    _chk(_L.qldpc_mc_pattern_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(pattern) & 0xFFFFFFFFFFFFFFFF, int(n_cand), int(n_punct), int(key_bits),
+                                  idx.ctypes.data_as(_ip)), "mc_pattern_host")
+    return idx
 
 
 class MonteCarlo:
@@ -995,6 +1026,55 @@ class MonteCarlo:
         out = np.zeros(self.fail_cap, np.uint64)
         n = _chk(_L.qldpc_mc_failed_frames(self._h, out.ctypes.data_as(_u64p), out.size), "MonteCarlo.failed_frames")
         return out[:n].copy()
+
+    def set_candidates(self, vn=None):
+        """the VNs a pattern may puncture: ascending, distinct, inside [0, N); None = every VN_PINNED VN of the class map"""
+        if vn is None:
+            _chk(_L.qldpc_mc_set_candidates(self._h, None, 0), "MonteCarlo.set_candidates")
+            return
+        v = _np_i32(vn).ravel()
+        _chk(_L.qldpc_mc_set_candidates(self._h, v.ctypes.data_as(_ip), v.size), "MonteCarlo.set_candidates")
+
+    def patterns(self, first_pattern, n_patterns, n_punct, key_bits=32):
+        """erase rows of patterns [first_pattern, first_pattern + n_patterns) -> device int32 tensor [n, ceil(N/32)], MSB-first"""
+        torch = _torch()
+        n = int(n_patterns)
+        rows = torch.empty((max(n, 0), (self.N + 31) // 32), dtype=torch.int32, device="cuda:%d" % self.device)
+        _chk(_L.qldpc_mc_patterns_dev(self._h, int(first_pattern) & 0xFFFFFFFFFFFFFFFF, n, int(n_punct), int(key_bits), _vp(rows.data_ptr())),
+             "MonteCarlo.patterns")
+        self.decoder.sync()
+        return rows
+
+    def pattern_vns(self, pattern, n_punct, key_bits=32):
+        """the VNs pattern `pattern` punctures, ascending (int32)"""
+        vn = np.full(max(int(n_punct), 0), -1, np.int32)
+        _chk(_L.qldpc_mc_pattern_vns(self._h, int(pattern) & 0xFFFFFFFFFFFFFFFF, int(n_punct), int(key_bits), vn.ctypes.data_as(_ip)), "MonteCarlo.pattern_vns")
+        return vn
+
+    def set_puncture(self, vn):
+        """a fixed puncture set for run(): these VNs (ascending, distinct) are erased in every frame; an empty list clears it"""
+        v = _np_i32(vn).ravel() if vn is not None else np.zeros(0, np.int32)
+        _chk(_L.qldpc_mc_set_puncture(self._h, v.ctypes.data_as(_ip), v.size), "MonteCarlo.set_puncture")
+
+    def search(self, qber, n_punct, frames_per_pattern, first_pattern=0, max_patterns=None, stop_at_goal=True, first_frame=0, key_bits=32):
+        """Patterns [first_pattern, first_pattern + max_patterns) (None = one round), each over its own frames_per_pattern frames
+        first_frame + p F + k, floor(batch / F) patterns per decoder launch -> dict of the result (patterns, frames, batches, goal, best,
+        best_frame_errors, best_bit_errors, next_pattern, the stage times) plus `stats`, one MC_PATTERN_STAT row per evaluated pattern.
+        goal / best are MC_NO_PATTERN where there is none.  With stop_at_goal the search ends after the first round that holds a
+        pattern without frame errors."""
+        cfg = McSearchCfg()
+        cfg.n_punct, cfg.frames_per_pattern, cfg.key_bits, cfg.stop_at_goal = int(n_punct), int(frames_per_pattern), int(key_bits), int(bool(stop_at_goal))
+        cfg.first_frame = int(first_frame) & 0xFFFFFFFFFFFFFFFF
+        if max_patterns is None:
+            max_patterns = self.batch // max(int(frames_per_pattern), 1) if 1 <= int(frames_per_pattern) <= self.batch else 1
+        res = McSearchResult()
+        _chk(_L.qldpc_mc_search(self._h, float(qber), C.byref(cfg), int(first_pattern) & 0xFFFFFFFFFFFFFFFF, int(max_patterns), C.byref(res)), "MonteCarlo.search")
+        out = {name: getattr(res, name) for name, _ in McSearchResult._fields_}
+        stats = np.zeros(int(res.patterns), MC_PATTERN_STAT)
+        n = _chk(_L.qldpc_mc_search_stats(self._h, _vp(stats.ctypes.data), stats.size), "MonteCarlo.search")
+        assert n == stats.size
+        out["stats"] = stats
+        return out
 
     def __del__(self):
         try:

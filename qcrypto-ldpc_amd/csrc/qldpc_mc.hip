@@ -12,6 +12,14 @@
  *     wave and counter from lane 0 -- plus, per frame, one on the iteration histogram and, for a failed frame, one returning add on the
  *     slot counter of the failed-frame list.
  *
+ * mc_patterns: one workgroup per puncture pattern (the definition and the radix select are qldpc_mc_core.h): per key digit a histogram in LDS
+ *     over keys recomputed on the fly (n_cand / 4 Philox calls per pass, nothing stored), lane 0 picks the bucket; the final pass walks the
+ *     candidates in index order in chunks of 4 x 256, the rank among equal keys = a running count + a shuffle prefix over the chunk, and sets
+ *     the erase bits of the row it zeroed at its start.
+ * mc_expand_rows: a pattern row -> the F frame rows of its slots, the layout qldpc_load_erasures_dev reads; 16-byte stores.
+ * mc_monitor_patterns: the arithmetic of mc_monitor, the waves dealt out per pattern (every frame of a wave belongs to one pattern), so ONE
+ *     atomicAdd per wave and counter onto the counter row of that pattern.
+ *
  * No kernel waits on another wave.  The decoder and the encoder are driven through their public calls only; qldpc_engine_int.h is read for
  * the decoder's sizes, device and stream.
  */
@@ -105,6 +113,106 @@ __global__ __launch_bounds__(MC_LANES) void mc_monitor(const uint32_t *__restric
     if (s_nc) atomicAdd(ctr + MC_NOT_CONVERGED, s_nc);
 }
 
+/* ---- puncture patterns ---- */
+#define MC_PAT_LANES 256
+static_assert(MC_PAT_LANES == MC_SEL_BINS, "mc_patterns clears one histogram bin per lane");
+enum { MCP_FRAMES = 0, MCP_FRAME_ERRORS, MCP_BIT_ERRORS, MCP_UNDETECTED, MCP_NOT_CONVERGED, MCP_ITER_SUM, MCP_COUNTERS };
+
+/* rows[blockIdx.x][Wn] = the erase row of pattern first + blockIdx.x; cand[n_cand] ascending VNs below 32 Wn; n_punct <= n_cand; key_bits 1 .. 32 */
+__global__ __launch_bounds__(MC_PAT_LANES) void mc_patterns(uint32_t *__restrict__ rows, const int *__restrict__ cand, unsigned n_cand, unsigned n_punct,
+                                                            int key_bits, unsigned Wn, uint64_t seed, uint64_t first)
+{
+    __shared__ uint32_t hist[MC_SEL_BINS];
+    __shared__ uint32_t sel[2];
+    __shared__ unsigned wave_eq[MC_PAT_LANES / 64];
+    const unsigned t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const uint64_t p = first + blockIdx.x;
+    uint32_t *row = rows + (size_t)blockIdx.x * Wn;
+    for (unsigned w = t; w < Wn; w += MC_PAT_LANES) row[w] = 0u;
+    if (n_punct == 0) return;
+    const unsigned blocks = (n_cand + 3u) / 4u;
+    uint32_t prefix = 0, mask = 0, k = n_punct, u[4];
+    for (int shift = mc_select_top_shift(key_bits); shift >= 0; shift -= MC_SEL_BITS) {
+        hist[t] = 0u;
+        __syncthreads();
+        for (unsigned q = t; q < blocks; q += MC_PAT_LANES) {
+            mc_pattern_keys(seed, p, q, key_bits, u);
+            for (unsigned b = 0; b < 4; b++)
+                if (4u * q + b < n_cand && (u[b] & mask) == prefix) atomicAdd(&hist[(u[b] >> shift) & (MC_SEL_BINS - 1)], 1u);
+        }
+        __syncthreads();
+        if (t == 0) { uint32_t kk = k; sel[0] = mc_select_digit(hist, &kk); sel[1] = kk; }
+        __syncthreads();
+        prefix |= sel[0] << shift; k = sel[1];
+        mask |= (uint32_t)(MC_SEL_BINS - 1) << shift;
+    }
+    /* T = prefix, r = k.  The barriers above also order the zeroing of the row before the bits set below. */
+    unsigned equal_base = 0;
+    for (unsigned q0 = 0; q0 < blocks; q0 += MC_PAT_LANES) {
+        const unsigned q = q0 + t;
+        unsigned mine = 0;
+        if (q < blocks) {
+            mc_pattern_keys(seed, p, q, key_bits, u);
+            for (unsigned b = 0; b < 4; b++) mine += 4u * q + b < n_cand && u[b] == prefix;
+        }
+        unsigned incl = mine;
+        for (unsigned s = 1; s < 64u; s <<= 1) { const unsigned v = __shfl_up(incl, s, 64); if (lane >= s) incl += v; }
+        if (lane == 63u) wave_eq[wave] = incl;
+        __syncthreads();
+        unsigned before = equal_base + incl - mine;
+        for (unsigned w = 0; w < MC_PAT_LANES / 64; w++) { if (w < wave) before += wave_eq[w]; equal_base += wave_eq[w]; }
+        if (q < blocks)
+            for (unsigned b = 0; b < 4; b++) {
+                if (4u * q + b >= n_cand) break;
+                if (mc_pattern_takes(u[b], prefix, k, before)) { const unsigned v = (unsigned)cand[4u * q + b]; atomicOr(&row[v >> 5], 0x80000000u >> (v & 31u)); }
+                before += u[b] == prefix;
+            }
+        __syncthreads();
+    }
+}
+
+/* frames[slot][Wn] = pat[slot / F][Wn] for the `total` words of the slots, four words per lane */
+__global__ __launch_bounds__(MC_LANES) void mc_expand_rows(const uint32_t *__restrict__ pat, uint32_t *__restrict__ frames, unsigned total, unsigned Wn, unsigned F)
+{
+    const unsigned i = (blockIdx.x * MC_LANES + threadIdx.x) * 4u;
+    if (i >= total) return;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    for (unsigned j = 0; j < 4; j++)
+        if (i + j < total) { const unsigned slot = (i + j) / Wn, word = (i + j) - slot * Wn; w[j] = pat[(size_t)(slot / F) * Wn + word]; }
+    if (i + 4u <= total) *(uint4 *)(frames + i) = make_uint4(w[0], w[1], w[2], w[3]);
+    else for (unsigned j = 0; i + j < total; j++) frames[i + j] = w[j];
+}
+
+/* wpp waves per pattern (<= F): wave (pat, sub) takes frames sub, sub + wpp, ... of the F frames of pattern slot pat */
+__global__ __launch_bounds__(MC_LANES) void mc_monitor_patterns(const uint32_t *__restrict__ out, const uint32_t *__restrict__ cw, const uint32_t *__restrict__ info_mask,
+                                                                const int *__restrict__ iters, const int *__restrict__ ok, unsigned n_pat, unsigned F, unsigned wpp,
+                                                                unsigned Wn, int n_ite, mc_u64 *__restrict__ rows)
+{
+    const unsigned lane = threadIdx.x & 63u, wid = blockIdx.x * (MC_LANES / 64) + (threadIdx.x >> 6);
+    if (wid >= n_pat * wpp) return;
+    const unsigned pat = wid / wpp, sub = wid - pat * wpp;
+    mc_u64 s_frames = 0, s_be = 0, s_fe = 0, s_ud = 0, s_nc = 0, s_it = 0;
+    for (unsigned k = sub; k < F; k += wpp) {
+        const unsigned f = pat * F + k;
+        const size_t row = (size_t)f * Wn;
+        unsigned be = 0;
+        for (unsigned w = lane; w < Wn; w += 64u) be += (unsigned)__popc((out[row + w] ^ cw[row + w]) & info_mask[w]);
+        be = mc_wave_sum(be);
+        const int it = min(max(iters[f], 0), n_ite);
+        const bool good = ok[f] != 0;
+        s_frames++; s_be += be; s_it += (mc_u64)it;
+        s_fe += be > 0; s_ud += good && be > 0; s_nc += !good;
+    }
+    if (lane != 0 || s_frames == 0) return;
+    mc_u64 *r = rows + (size_t)pat * MCP_COUNTERS;
+    atomicAdd(r + MCP_FRAMES, s_frames);
+    atomicAdd(r + MCP_ITER_SUM, s_it);
+    if (s_be) atomicAdd(r + MCP_BIT_ERRORS, s_be);
+    if (s_fe) atomicAdd(r + MCP_FRAME_ERRORS, s_fe);
+    if (s_ud) atomicAdd(r + MCP_UNDETECTED, s_ud);
+    if (s_nc) atomicAdd(r + MCP_NOT_CONVERGED, s_nc);
+}
+
 /* ------------------------------------------------------------------ host ---- */
 
 struct qldpc_mc {
@@ -119,6 +227,16 @@ struct qldpc_mc {
     mc_u64 *h_ctr;                     /* pinned, MC_COUNTERS */
     hipEvent_t ev[7];                  /* the stage boundaries of a batch: source | encode | channel | load | run | fetch + monitor */
     size_t dev_bytes;
+    /* puncture patterns and the search over them; the device side is allocated at first use (mc_search_reserve) */
+    std::vector<uint8_t> h_cls;        /* [N] the class map, for the default candidates */
+    std::vector<int> cand;             /* the candidate VNs, ascending */
+    bool cand_dirty, search_ready;
+    int n_fixed;                       /* VNs of the fixed puncture set of qldpc_mc_run (0 = none) */
+    int *d_cand;                       /* [N] */
+    uint32_t *d_pat, *d_erase, *d_fixed;   /* [batch][Wn] pattern rows, [batch][Wn] frame rows, [Wn] the fixed set */
+    mc_u64 *d_rows, *h_rows;           /* [batch][MCP_COUNTERS] counter rows of a round; pinned copy */
+    hipEvent_t sev[8];                 /* of a search round: patterns | expand | generate | load | erase | run | fetch + monitor */
+    std::vector<qldpc_mc_pattern_stat> stats;   /* of the last search */
 };
 
 extern "C" void qldpc_mc_cfg_default(qldpc_mc_cfg *cfg)
@@ -132,10 +250,13 @@ extern "C" void qldpc_mc_free(qldpc_mc *mc)
 {
     if (!mc) return;
     (void)hipSetDevice(mc->device);
-    void *dev[] = {mc->d_cls, mc->d_info_mask, mc->d_chan_mask, mc->d_info, mc->d_cw, mc->d_rx, mc->d_out, mc->d_mag, mc->d_iters, mc->d_ok, mc->d_ctr};
+    void *dev[] = {mc->d_cls, mc->d_info_mask, mc->d_chan_mask, mc->d_info, mc->d_cw, mc->d_rx, mc->d_out, mc->d_mag, mc->d_iters, mc->d_ok, mc->d_ctr,
+                   mc->d_cand, mc->d_pat, mc->d_erase, mc->d_fixed, mc->d_rows};
     for (void *p : dev) if (p) (void)hipFree(p);
     if (mc->h_ctr) (void)hipHostFree(mc->h_ctr);
+    if (mc->h_rows) (void)hipHostFree(mc->h_rows);
     for (hipEvent_t e : mc->ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : mc->sev) if (e) (void)hipEventDestroy(e);
     delete mc;
 }
 
@@ -144,6 +265,14 @@ template <typename T> static int mc_alloc(qldpc_mc *mc, T **p, size_t count)
     if (hipMalloc((void **)p, sizeof(T) * count) != hipSuccess) { *p = nullptr; qldpc_set_error("mc_create: device allocation of %zu bytes failed", sizeof(T) * count); return QLDPC_ENOMEM; }
     mc->dev_bytes += sizeof(T) * count;
     return QLDPC_OK;
+}
+
+/* the candidates a NULL list stands for: every QLDPC_VN_PINNED VN, ascending (the harness's `for a = K .. N-1`) */
+static void mc_default_candidates(qldpc_mc *mc)
+{
+    mc->cand.clear();
+    for (int v = 0; v < mc->N; v++) if (mc->h_cls[(size_t)v] == QLDPC_VN_PINNED) mc->cand.push_back(v);
+    mc->cand_dirty = true;
 }
 
 static int mc_build(qldpc_mc *mc, const uint8_t *vn_class)
@@ -160,6 +289,8 @@ static int mc_build(qldpc_mc *mc, const uint8_t *vn_class)
     }
     for (int v = 0; v < mc->N; v++)
         if (cls[(size_t)v] == QLDPC_VN_CHANNEL) { chan_mask[(size_t)v >> 5] |= 0x80000000u >> (v & 31); mc->channel_vns++; }
+    mc->h_cls.assign(cls.begin(), cls.begin() + mc->N);
+    mc_default_candidates(mc);
     HIPCHK(hipSetDevice(mc->device));
     if ((rc = mc_alloc(mc, &mc->d_cls, 32 * Wn)) || (rc = mc_alloc(mc, &mc->d_info_mask, Wn)) || (rc = mc_alloc(mc, &mc->d_chan_mask, Wn)) ||
         (rc = mc_alloc(mc, &mc->d_info, B * (size_t)mc->Wk)) || (rc = mc_alloc(mc, &mc->d_cw, B * Wn)) || (rc = mc_alloc(mc, &mc->d_rx, B * Wn)) ||
@@ -242,6 +373,15 @@ static void mc_result(const qldpc_mc *mc, uint64_t first, qldpc_mc_result *r)
     r->next_frame = first + r->frames;
 }
 
+/* the erase rows of n frames from pattern rows that cover F slots each, into the decoder: after qldpc_load_bits_dev */
+static int mc_erase(qldpc_mc *mc, const uint32_t *d_rows, int n, int F, hipStream_t s)
+{
+    const unsigned total = (unsigned)n * (unsigned)mc->Wn;
+    hipLaunchKernelGGL(mc_expand_rows, dim3(mc_blocks(((size_t)total + 3) / 4)), dim3(MC_LANES), 0, s, d_rows, mc->d_erase, total, (unsigned)mc->Wn, (unsigned)F);
+    LAUNCHCHK();
+    return qldpc_load_erasures_dev(mc->dec, mc->d_erase, n);
+}
+
 extern "C" int qldpc_mc_run(qldpc_mc *mc, double qber, uint64_t first_frame, uint64_t max_frames, uint64_t max_frame_errors, qldpc_mc_result *result)
 {
     if (!mc || !result) return QLDPC_EINVAL;
@@ -263,6 +403,7 @@ extern "C" int qldpc_mc_run(qldpc_mc *mc, double qber, uint64_t first_frame, uin
         if (rc) return rc;
         HIPCHK(hipEventRecord(mc->ev[3], s));
         if ((rc = qldpc_load_bits_dev(mc->dec, mc->d_rx, mc->d_mag, mc->d_cls, nb))) return rc;
+        if (mc->n_fixed && (rc = mc_erase(mc, mc->d_fixed, nb, nb, s))) return rc;      /* the fixed puncture set: one row for all nb frames */
         HIPCHK(hipEventRecord(mc->ev[4], s));
         if ((rc = qldpc_run(mc->dec))) return rc;
         HIPCHK(hipEventRecord(mc->ev[5], s));
@@ -316,4 +457,174 @@ extern "C" int qldpc_mc_failed_frames(qldpc_mc *mc, uint64_t *frames, int cap)
     const int n = std::min(listed, cap);
     if (n) memcpy(frames, all.data(), sizeof(uint64_t) * (size_t)n);
     return listed;
+}
+
+/* ------------------------------------------------------------------ puncture patterns, search ---- */
+
+/* everything the pattern calls need on the device, once; then the candidate list if it changed */
+static int mc_search_reserve(qldpc_mc *mc)
+{
+    HIPCHK(hipSetDevice(mc->device));
+    if (!mc->search_ready) {
+        const size_t Wn = (size_t)mc->Wn, B = (size_t)mc->batch;
+        int rc = QLDPC_OK;
+        if ((!mc->d_cand && (rc = mc_alloc(mc, &mc->d_cand, (size_t)mc->N))) || (!mc->d_pat && (rc = mc_alloc(mc, &mc->d_pat, B * Wn))) ||
+            (!mc->d_erase && (rc = mc_alloc(mc, &mc->d_erase, B * Wn))) || (!mc->d_fixed && (rc = mc_alloc(mc, &mc->d_fixed, Wn))) ||
+            (!mc->d_rows && (rc = mc_alloc(mc, &mc->d_rows, B * MCP_COUNTERS))))
+            return rc;
+        if (!mc->h_rows && hipHostMalloc((void **)&mc->h_rows, sizeof(mc_u64) * B * MCP_COUNTERS, hipHostMallocDefault) != hipSuccess) { mc->h_rows = nullptr; return QLDPC_ENOMEM; }
+        for (hipEvent_t &e : mc->sev) if (!e) HIPCHK(hipEventCreate(&e));
+        if ((rc = qldpc_decoder_reserve(mc->dec))) return rc;      /* the decoder's erasure ballots */
+        mc->search_ready = true;
+    }
+    if (mc->cand_dirty) {
+        HIPCHK(hipStreamSynchronize(mc->dec->stream));      /* a queued pattern kernel may still read the old list */
+        if (!mc->cand.empty()) HIPCHK(hipMemcpy(mc->d_cand, mc->cand.data(), sizeof(int) * mc->cand.size(), hipMemcpyHostToDevice));
+        mc->cand_dirty = false;
+    }
+    return QLDPC_OK;
+}
+
+static int mc_pattern_args(const qldpc_mc *mc, const char *who, int n_punct, int key_bits)
+{
+    if (n_punct < 0 || n_punct > (int)mc->cand.size()) { qldpc_set_error("%s: n_punct=%d outside [0, %d candidates]", who, n_punct, (int)mc->cand.size()); return QLDPC_ESIZE; }
+    if (key_bits < 0 || key_bits > 32) { qldpc_set_error("%s: key_bits=%d outside 0 .. 32", who, key_bits); return QLDPC_ESIZE; }
+    return QLDPC_OK;
+}
+
+static int mc_vn_list_args(const qldpc_mc *mc, const char *who, const int *vn, int n)
+{
+    if (n < 0 || (n > 0 && !vn)) { qldpc_set_error("%s: n=%d", who, n); return QLDPC_EINVAL; }
+    const int bad = mc_vn_list_check(vn, n, mc->N);
+    if (bad >= 0) { qldpc_set_error("%s: entry %d = %d is not ascending, distinct and inside [0, %d)", who, bad, vn[bad], mc->N); return QLDPC_EINVAL; }
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_set_candidates(qldpc_mc *mc, const int *vn, int n)
+{
+    if (!mc) return QLDPC_EINVAL;
+    if (!vn) { mc_default_candidates(mc); return QLDPC_OK; }
+    const int rc = mc_vn_list_args(mc, "mc_set_candidates", vn, n);
+    if (rc) return rc;
+    mc->cand.assign(vn, vn + n);
+    mc->cand_dirty = true;
+    return QLDPC_OK;
+}
+
+static void mc_launch_patterns(qldpc_mc *mc, uint64_t first, int n, int n_punct, int key_bits, uint32_t *d_rows, hipStream_t s)
+{
+    hipLaunchKernelGGL(mc_patterns, dim3((unsigned)n), dim3(MC_PAT_LANES), 0, s, d_rows, (const int *)mc->d_cand, (unsigned)mc->cand.size(), (unsigned)n_punct,
+                       mc_key_bits(key_bits), (unsigned)mc->Wn, mc->seed, first);
+}
+
+extern "C" int qldpc_mc_patterns_dev(qldpc_mc *mc, uint64_t first_pattern, int n_patterns, int n_punct, int key_bits, uint32_t *d_erase)
+{
+    if (!mc || n_patterns < 0 || (n_patterns && !d_erase)) return QLDPC_EINVAL;
+    int rc = mc_pattern_args(mc, "mc_patterns_dev", n_punct, key_bits);
+    if (rc || (rc = mc_search_reserve(mc)) || n_patterns == 0) return rc;
+    mc_launch_patterns(mc, first_pattern, n_patterns, n_punct, key_bits, d_erase, mc->dec->stream);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_pattern_vns(qldpc_mc *mc, uint64_t pattern, int n_punct, int key_bits, int *vn)
+{
+    if (!mc || (n_punct > 0 && !vn)) return QLDPC_EINVAL;
+    int rc = mc_pattern_args(mc, "mc_pattern_vns", n_punct, key_bits);
+    if (rc || (rc = qldpc_mc_pattern_host(mc->seed, pattern, (int)mc->cand.size(), n_punct, key_bits, vn))) return rc;
+    for (int i = 0; i < n_punct; i++) vn[i] = mc->cand[(size_t)vn[i]];
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_set_puncture(qldpc_mc *mc, const int *vn, int n)
+{
+    if (!mc) return QLDPC_EINVAL;
+    int rc = mc_vn_list_args(mc, "mc_set_puncture", vn, n);
+    if (rc) return rc;
+    if (n == 0) { mc->n_fixed = 0; return QLDPC_OK; }
+    if ((rc = mc_search_reserve(mc))) return rc;
+    std::vector<uint32_t> row((size_t)mc->Wn);
+    mc_vn_list_row(vn, n, mc->N, row.data());
+    HIPCHK(hipStreamSynchronize(mc->dec->stream));
+    HIPCHK(hipMemcpy(mc->d_fixed, row.data(), sizeof(uint32_t) * row.size(), hipMemcpyHostToDevice));
+    mc->n_fixed = n;
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_search(qldpc_mc *mc, double qber, const qldpc_mc_search_cfg *cfg, uint64_t first_pattern, uint64_t max_patterns, qldpc_mc_search_result *res)
+{
+    if (!mc || !cfg || !res) return QLDPC_EINVAL;
+    memset(res, 0, sizeof(*res));
+    res->goal = res->best = UINT64_MAX;
+    res->next_pattern = first_pattern;
+    if (cfg->reserved[0] || cfg->reserved[1]) { qldpc_set_error("mc_search: reserved fields %d, %d must be zero", cfg->reserved[0], cfg->reserved[1]); return QLDPC_EINVAL; }
+    if (!(qber > 0.0 && qber < 0.5)) { qldpc_set_error("mc_search: qber=%g outside (0, 0.5)", qber); return QLDPC_ESIZE; }
+    if (cfg->frames_per_pattern < 1 || cfg->frames_per_pattern > mc->batch) { qldpc_set_error("mc_search: frames_per_pattern=%d outside [1, batch=%d]", cfg->frames_per_pattern, mc->batch); return QLDPC_ESIZE; }
+    int rc = mc_pattern_args(mc, "mc_search", cfg->n_punct, cfg->key_bits);
+    if (rc || (rc = mc_search_reserve(mc))) return rc;
+    const hipStream_t s = mc->dec->stream;
+    const unsigned F = (unsigned)cfg->frames_per_pattern, Wn = (unsigned)mc->Wn;
+    const uint64_t per_round = (uint64_t)mc->batch / F;
+    mc->stats.clear();
+    const auto t_start = std::chrono::steady_clock::now();
+    for (uint64_t done = 0; done < max_patterns;) {
+        const int np = (int)std::min<uint64_t>(per_round, max_patterns - done), nb = np * (int)F;
+        const uint64_t p0 = first_pattern + done, frame0 = cfg->first_frame + p0 * F;      /* frame k of pattern p = first_frame + p F + k */
+        HIPCHK(hipEventRecord(mc->sev[0], s));
+        mc_launch_patterns(mc, p0, np, cfg->n_punct, cfg->key_bits, mc->d_pat, s);
+        LAUNCHCHK();
+        HIPCHK(hipEventRecord(mc->sev[1], s));
+        const unsigned total = (unsigned)nb * Wn;
+        hipLaunchKernelGGL(mc_expand_rows, dim3(mc_blocks(((size_t)total + 3) / 4)), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_pat, mc->d_erase, total, Wn, F);
+        LAUNCHCHK();
+        HIPCHK(hipEventRecord(mc->sev[2], s));
+        if ((rc = mc_generate(mc, frame0, nb, qber, mc->d_info, mc->d_cw, mc->d_rx, mc->d_mag, s))) return rc;
+        HIPCHK(hipEventRecord(mc->sev[3], s));
+        if ((rc = qldpc_load_bits_dev(mc->dec, mc->d_rx, mc->d_mag, mc->d_cls, nb))) return rc;
+        HIPCHK(hipEventRecord(mc->sev[4], s));
+        if ((rc = qldpc_load_erasures_dev(mc->dec, mc->d_erase, nb))) return rc;
+        HIPCHK(hipEventRecord(mc->sev[5], s));
+        if ((rc = qldpc_run(mc->dec))) return rc;
+        HIPCHK(hipEventRecord(mc->sev[6], s));
+        if ((rc = qldpc_fetch_packed_dev(mc->dec, mc->d_out))) return rc;
+        if ((rc = qldpc_fetch_status_dev(mc->dec, mc->d_iters, mc->d_ok))) return rc;
+        HIPCHK(hipMemsetAsync(mc->d_rows, 0, sizeof(mc_u64) * (size_t)np * MCP_COUNTERS, s));
+        const unsigned wpp = std::min(F, std::max(1u, (unsigned)MC_MAX_WAVES / (unsigned)np)), waves = (unsigned)np * wpp;
+        hipLaunchKernelGGL(mc_monitor_patterns, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_out, (const uint32_t *)mc->d_cw,
+                           (const uint32_t *)mc->d_info_mask, (const int *)mc->d_iters, (const int *)mc->d_ok, (unsigned)np, F, wpp, Wn, mc->n_ite, mc->d_rows);
+        LAUNCHCHK();
+        HIPCHK(hipEventRecord(mc->sev[7], s));
+        HIPCHK(hipMemcpyAsync(mc->h_rows, mc->d_rows, sizeof(mc_u64) * (size_t)np * MCP_COUNTERS, hipMemcpyDeviceToHost, s));      /* the one read-back of a round */
+        HIPCHK(hipStreamSynchronize(s));
+        double *const stage[7] = {&res->pattern_ms, &res->expand_ms, &res->generate_ms, &res->load_ms, &res->erase_ms, &res->decode_ms, &res->monitor_ms};
+        for (int k = 0; k < 7; k++) {
+            float ms = 0.0f;
+            HIPCHK(hipEventElapsedTime(&ms, mc->sev[k], mc->sev[k + 1]));
+            *stage[k] += (double)ms;
+        }
+        for (int i = 0; i < np; i++) {
+            const mc_u64 *c = mc->h_rows + (size_t)i * MCP_COUNTERS;
+            qldpc_mc_pattern_stat st = {p0 + (uint64_t)i, c[MCP_FRAMES], c[MCP_FRAME_ERRORS], c[MCP_BIT_ERRORS], c[MCP_UNDETECTED], c[MCP_NOT_CONVERGED], c[MCP_ITER_SUM]};
+            mc->stats.push_back(st);
+            if (st.frame_errors == 0 && res->goal == UINT64_MAX) res->goal = st.pattern;
+            if (res->best == UINT64_MAX || st.frame_errors < res->best_frame_errors || (st.frame_errors == res->best_frame_errors && st.bit_errors < res->best_bit_errors)) {
+                res->best = st.pattern; res->best_frame_errors = st.frame_errors; res->best_bit_errors = st.bit_errors;
+            }
+        }
+        res->batches++;
+        res->patterns += (uint64_t)np; res->frames += (uint64_t)nb;
+        done += (uint64_t)np;
+        if (cfg->stop_at_goal && res->goal != UINT64_MAX) break;
+    }
+    res->next_pattern = first_pattern + res->patterns;
+    res->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_search_stats(qldpc_mc *mc, qldpc_mc_pattern_stat *rows, int cap)
+{
+    if (!mc || cap < 0 || (cap && !rows)) return QLDPC_EINVAL;
+    const size_t n = std::min((size_t)cap, mc->stats.size());
+    if (n) memcpy(rows, mc->stats.data(), sizeof(qldpc_mc_pattern_stat) * n);
+    return (int)mc->stats.size();
 }

@@ -1,6 +1,6 @@
 /*
- * qldpc_mc_core.h -- the frame definition of the Monte-Carlo loop (qldpc_mc_*), plain C, shared by the kernels (qldpc_mc.hip) and by
- * their host mirror (qldpc_mc_host.c), so that the CPU suite runs what the lanes run.
+ * qldpc_mc_core.h -- the frame definition and the puncture-pattern definition of the Monte-Carlo loop (qldpc_mc_*), plain C, shared by the
+ * kernels (qldpc_mc.hip) and by their host mirror (qldpc_mc_host.c), so that the CPU suite runs what the lanes run.
  *
  * Frame i (a 64-bit global index) is a pure function of (seed, i): nothing depends on the batch size, the launch shape or the device.
  *
@@ -77,6 +77,63 @@ MC_FN uint32_t mc_flip_word(uint64_t seed, uint64_t frame, uint32_t w, const uin
             if (o[b] < t[b]) flips |= 0x80000000u >> (4u * g + b);
     }
     return flips;
+}
+
+/*
+ * Puncture patterns (qldpc_mc_patterns_dev, qldpc_mc_search).  Pattern p (a 64-bit global index) over an ascending candidate list
+ * cand[0 .. n_cand-1] is a pure function of (seed, p, n_cand, n_punct, key_bits):
+ *
+ *   key        u_c = output word c % 4 at counter (c / 4, 2, p_lo, p_hi), key = (seed low word, seed high word); u'_c = u_c >> (32 - key_bits)
+ *   selection  the n_punct candidates smallest in the lexicographic order (u'_c, c): equal keys go to the lower candidate index
+ *
+ * key_bits is 32 in production (0 stands for 32): a uniformly random subset up to 32-bit key collisions broken by index.  Smaller values
+ * exist for TESTS only, which force equal keys with them and so reach the tie rule.
+ *
+ * The selection is a radix select, not a sort: the digits of u' from the top, MC_SEL_BITS at a time; per digit a histogram of the candidates
+ * whose higher digits equal the prefix found so far, and mc_select_digit picks the bucket that holds rank k.  What remains is the threshold
+ * key T and the number r of candidates with u' == T to take, the first r in index order.  Kernel and host mirror share every function here.
+ */
+#define MC_STREAM_PATTERN 2u
+#define MC_SEL_BITS 8
+#define MC_SEL_BINS (1 << MC_SEL_BITS)
+
+MC_FN int mc_key_bits(int key_bits) { return key_bits == 0 ? 32 : key_bits; }
+
+/* the coarsened keys of candidates 4 q .. 4 q + 3 of pattern p; key_bits in 1 .. 32 */
+MC_FN void mc_pattern_keys(uint64_t seed, uint64_t p, uint32_t q, int key_bits, uint32_t u[4])
+{
+    mc_philox(q, MC_STREAM_PATTERN, (uint32_t)p, (uint32_t)(p >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), u);
+    for (int b = 0; b < 4; b++) u[b] >>= 32 - key_bits;
+}
+
+/* the shift of the top digit that can be non-zero */
+MC_FN int mc_select_top_shift(int key_bits) { return MC_SEL_BITS * ((key_bits + MC_SEL_BITS - 1) / MC_SEL_BITS - 1); }
+
+/* hist = the digit histogram of the candidates still in play, *k (1-based, at most their number) the rank looked for among them: returns the
+ * digit whose bucket holds it and leaves in *k the rank inside that bucket */
+MC_FN uint32_t mc_select_digit(const uint32_t *hist, uint32_t *k)
+{
+    uint32_t d = 0;
+    while (d < MC_SEL_BINS - 1 && hist[d] < *k) { *k -= hist[d]; d++; }
+    return d;
+}
+
+/* does the final pass take candidate c with key u?  below counts the candidates before c with u' == T */
+MC_FN int mc_pattern_takes(uint32_t u, uint32_t T, uint32_t r, uint32_t equal_before) { return u < T || (u == T && equal_before < r); }
+
+/* a list of VNs (candidates, a puncture set): ascending, distinct, inside [0, N).  Returns -1, or the index of the first offending entry */
+static inline int mc_vn_list_check(const int *vn, int n, int N)
+{
+    for (int i = 0; i < n; i++)
+        if (vn[i] < 0 || vn[i] >= N || (i > 0 && vn[i] <= vn[i - 1])) return i;
+    return -1;
+}
+
+/* the packed MSB-first row (ceil(N / 32) words) of a checked list */
+static inline void mc_vn_list_row(const int *vn, int n, int N, uint32_t *row)
+{
+    for (int w = 0; w < (N + 31) / 32; w++) row[w] = 0;
+    for (int i = 0; i < n; i++) row[vn[i] >> 5] |= 0x80000000u >> (vn[i] & 31);
 }
 
 /*

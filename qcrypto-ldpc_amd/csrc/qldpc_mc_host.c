@@ -1,6 +1,7 @@
 /*
- * qldpc_mc_host.c -- host mirror of the Monte-Carlo frame definition (qldpc_mc_philox_host, qldpc_mc_frames_host): the functions of
- * qldpc_mc_core.h that the kernels of qldpc_mc.hip run per lane, here in a loop over frames and words.  Plain C, no device.
+ * qldpc_mc_host.c -- host mirror of the Monte-Carlo frame and pattern definitions (qldpc_mc_philox_host, qldpc_mc_frames_host,
+ * qldpc_mc_pattern_host): the functions of qldpc_mc_core.h that the kernels of qldpc_mc.hip run per lane, here in a loop over frames and
+ * words, or over candidates.  Plain C, no device.
  */
 #include <stdlib.h>
 
@@ -46,4 +47,37 @@ int qldpc_mc_frames_host(int K, int N, const int *info_bits_pos, const uint8_t *
     }
     free(cls); free(cls4);
     return rc;
+}
+
+/* the radix select of qldpc_mc_core.h in a loop over the candidates: per digit one pass that recomputes the keys, then the final pass in index
+ * order.  idx = the chosen candidate indices (into the candidate list), ascending. */
+int qldpc_mc_pattern_host(uint64_t seed, uint64_t pattern, int n_cand, int n_punct, int key_bits, int *idx)
+{
+    if (n_cand < 0 || n_punct < 0 || n_punct > n_cand) { qldpc_set_error("mc_pattern_host: n_punct=%d outside [0, n_cand=%d]", n_punct, n_cand); return QLDPC_ESIZE; }
+    if (key_bits < 0 || key_bits > 32) { qldpc_set_error("mc_pattern_host: key_bits=%d outside 0 .. 32", key_bits); return QLDPC_ESIZE; }
+    if (n_punct == 0) return QLDPC_OK;
+    if (!idx) return QLDPC_EINVAL;
+    const int kb = mc_key_bits(key_bits);
+    const uint32_t blocks = ((uint32_t)n_cand + 3u) / 4u;
+    uint32_t prefix = 0, mask = 0, k = (uint32_t)n_punct, u[4];
+    for (int shift = mc_select_top_shift(kb); shift >= 0; shift -= MC_SEL_BITS) {
+        uint32_t hist[MC_SEL_BINS] = {0};
+        for (uint32_t q = 0; q < blocks; q++) {
+            mc_pattern_keys(seed, pattern, q, kb, u);
+            for (uint32_t b = 0; b < 4 && 4 * q + b < (uint32_t)n_cand; b++)
+                if ((u[b] & mask) == prefix) hist[(u[b] >> shift) & (MC_SEL_BINS - 1)]++;
+        }
+        prefix |= mc_select_digit(hist, &k) << shift;
+        mask |= (uint32_t)(MC_SEL_BINS - 1) << shift;
+    }
+    uint32_t equal = 0;
+    int out = 0;      /* reaches n_punct exactly: the candidates below T plus the first k at T */
+    for (uint32_t q = 0; q < blocks; q++) {
+        mc_pattern_keys(seed, pattern, q, kb, u);
+        for (uint32_t b = 0; b < 4 && 4 * q + b < (uint32_t)n_cand; b++) {
+            if (out < n_punct && mc_pattern_takes(u[b], prefix, k, equal)) idx[out++] = (int)(4 * q + b);
+            equal += u[b] == prefix;
+        }
+    }
+    return QLDPC_OK;
 }

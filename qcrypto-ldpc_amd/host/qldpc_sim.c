@@ -20,6 +20,12 @@
  *                      [0, frames_per_ber) of seed -S at every BER, so the rows of a table share their random numbers; SIM_THR is the decode
  *                      time by hipEvents; -e and -R are host-only and refused)]
  *                  [-E n (with -D: stop a BER point at the first batch boundary with n frame errors, Monitor_BFER's max_fe)]
+ *                  [-X f (with -D: the puncture-pattern search of BS/src/main.cpp:235-411 on the device, qldpc_mc_search: per BER point up to
+ *                      frames_per_ber (-f) random patterns of the n_punct parity bits that -e f would puncture, each over -F frames of its own,
+ *                      batch / F patterns per decoder launch; stops after the first round that holds a pattern with FER = 0 / F; prints one
+ *                      `#   pattern` line per evaluated pattern and the `best of` line of -R; -o file writes the best pattern's VN indices;
+ *                      -E does not apply)]
+ *                  [-F n (with -X: frames per pattern, default 64)]
  */
 #include <math.h>
 #include <stdint.h>
@@ -58,6 +64,8 @@ int main(int argc, char **argv)
 {
     int N = 8192, K = 6554, n_ite = 50, frames = 256, batch = 256, layered = 0, synd = 1, peg = 0, msg_bits = 32, search = 0, on_device = 0, opt;
     uint64_t max_fe = 0;
+    double search_eff = 0.0;      /* -X: > 0 = the pattern search on the device towards this efficiency */
+    int frames_per_pattern = 64;
     const char *pattern_out = NULL;
     double parity_ber = 0.0;      /* > 0: the disclosed parity bits are themselves wrong with this probability (main.cpp (test effect of dirty parities)) */
     double target_eff = 0.0;      /* > 0: puncture parity bits up to min_cr(ber, f), as BS/src/main.cpp:235-333 does */
@@ -66,7 +74,7 @@ int main(int argc, char **argv)
     double ber_min = 0.01, ber_max = 0.03, ber_step = 0.005;
     uint64_t seed = 0;
     const char *g_method = NULL;
-    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:DRlvn")) != -1) {
+    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:DRlvn")) != -1) {
         switch (opt) {
         case 'N': N = atoi(optarg); break;
         case 'K': K = atoi(optarg); break;
@@ -86,6 +94,8 @@ int main(int argc, char **argv)
         case 'R': search = 1; break;
         case 'D': on_device = 1; break;
         case 'E': max_fe = strtoull(optarg, NULL, 0); break;
+        case 'X': search_eff = atof(optarg); break;
+        case 'F': frames_per_pattern = atoi(optarg); break;
         case 'o': pattern_out = optarg; break;
         case 'G': g_method = optarg; break;      /* p.G_method (VAR/main.cpp (alist-v1.0.1):135): IDENTITY | LU_DEC; QC = Encoder_LDPC_from_QC ((qc):145) */
         case 'l': layered = 1; break;
@@ -100,6 +110,9 @@ int main(int argc, char **argv)
     if (rule < 0) { fprintf(stderr, "unknown rule %s\n", rule_name); return 2; }
     if (on_device && (target_eff > 0.0 || search)) { fprintf(stderr, "qldpc_sim: -e and -R draw a puncture pattern per batch on the host and do not run with -D\n"); return 2; }
     if (max_fe && !on_device) { fprintf(stderr, "qldpc_sim: -E needs -D\n"); return 2; }
+    if (search_eff != 0.0 && !on_device) { fprintf(stderr, "qldpc_sim: -X is the pattern search on the device and needs -D\n"); return 2; }
+    if (search_eff != 0.0 && max_fe) { fprintf(stderr, "qldpc_sim: -E does not apply to the pattern search (-X), which stops at the first pattern without frame errors\n"); return 2; }
+    if (search_eff < 0.0) { fprintf(stderr, "qldpc_sim: -X f with f > 0\n"); return 2; }
 
     qldpc_code *H = NULL;
     int rc = alist ? qldpc_code_from_alist(alist, &H) : qc ? qldpc_code_from_qc(qc, &H) : peg ? qldpc_code_ira_peg(N, K, 0.125f, 11, 3, peg, 7, &H) : qldpc_code_ira(N, K, 0.125f, 11, 3, 7, &H);
@@ -135,7 +148,47 @@ int main(int argc, char **argv)
         mcfg.seed = seed; mcfg.batch = batch; mcfg.parity_ber = parity_ber;
         qldpc_mc *mc = NULL;
         if ((rc = qldpc_mc_create(dec, enc, NULL, &mcfg, &mc))) return die("mc_create", rc);      /* NULL: info VNs through the BSC, the others pinned, as below */
-        for (double ber = ber_min; ber <= ber_max + 1e-12; ber += ber_step) {
+        for (double ber = ber_min; search_eff > 0.0 && ber <= ber_max + 1e-12; ber += ber_step) {      /* every row one qldpc_mc_search */
+            const int n_par = N - K;
+            int n_punct = qldpc_parity_bits_to_punct(N, K, qldpc_min_code_rate((float)ber, (float)search_eff));      /* as -e computes it */
+            if (n_punct < 0) { printf("# ber %.4f: mother code rate already above the goal, nothing to puncture\n", ber); n_punct = 0; }
+            if (n_punct > n_par) n_punct = n_par;
+            printf("# ber %.4f: puncturing %d of %d parity bits -> rate %.4f, efficiency f = %.3f\n", ber, n_punct, n_par, (double)K / (N - n_punct),
+                   ((double)(n_par - n_punct) / K) / (double)qldpc_binary_entropy((float)ber));
+            qldpc_mc_search_cfg scfg;
+            memset(&scfg, 0, sizeof(scfg));
+            scfg.n_punct = n_punct; scfg.frames_per_pattern = frames_per_pattern; scfg.stop_at_goal = 1;
+            qldpc_mc_search_result r;
+            if ((rc = qldpc_mc_search(mc, ber, &scfg, 0, (uint64_t)(frames > 0 ? frames : 0), &r))) return die("mc_search", rc);
+            qldpc_mc_pattern_stat *rows = (qldpc_mc_pattern_stat *)malloc(sizeof(*rows) * (size_t)(r.patterns ? r.patterns : 1));
+            if (!rows || (rc = qldpc_mc_search_stats(mc, rows, (int)r.patterns)) < 0) return die("mc_search_stats", rows ? rc : QLDPC_ENOMEM);
+            uint64_t be = 0, fe = 0;
+            for (uint64_t i = 0; i < r.patterns; i++) {
+                printf("#   pattern %3llu: FE %llu / %d, BE %llu\n", (unsigned long long)rows[i].pattern, (unsigned long long)rows[i].frame_errors, frames_per_pattern,
+                       (unsigned long long)rows[i].bit_errors);
+                be += rows[i].bit_errors; fe += rows[i].frame_errors;
+            }
+            free(rows);
+            if (r.goal != UINT64_MAX) printf("# ber %.4f: goal puncture pattern %llu (FER = 0 / %d)\n", ber, (unsigned long long)r.goal, frames_per_pattern);
+            if (r.patterns) {
+                printf("# ber %.4f: best of %llu patterns: FE %llu, BE %llu per %d frames\n", ber, (unsigned long long)r.patterns, (unsigned long long)r.best_frame_errors,
+                       (unsigned long long)r.best_bit_errors, frames_per_pattern);
+                if (pattern_out) {
+                    int *vn = (int *)malloc(sizeof(int) * (size_t)(n_punct ? n_punct : 1));
+                    if (!vn || (rc = qldpc_mc_pattern_vns(mc, r.best, n_punct, 0, vn))) return die("mc_pattern_vns", vn ? rc : QLDPC_ENOMEM);
+                    FILE *fo = fopen(pattern_out, "w");
+                    if (!fo) { perror(pattern_out); return 1; }
+                    fprintf(fo, "# qldpc_sim puncture pattern: N %d K %d ber %.4f punctured %d FE %llu\n", N, K, ber, n_punct, (unsigned long long)r.best_frame_errors);
+                    for (int i = 0; i < n_punct; i++) fprintf(fo, "%d\n", vn[i]);
+                    fclose(fo);
+                    free(vn);
+                }
+                printf("  %8.4f | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", ber, (unsigned long long)r.frames, (unsigned long long)be, (unsigned long long)fe,
+                       (double)be / ((double)r.frames * K), (double)fe / (double)r.frames, (double)r.frames * K / (r.decode_ms * 1e-3) / 1e6);
+            }
+            fflush(stdout);
+        }
+        for (double ber = ber_min; search_eff == 0.0 && ber <= ber_max + 1e-12; ber += ber_step) {
             qldpc_mc_result r;
             if ((rc = qldpc_mc_run(mc, ber, 0, (uint64_t)(frames > 0 ? frames : 0), max_fe, &r))) return die("mc_run", rc);
             printf("  %8.4f | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", ber, (unsigned long long)r.frames, (unsigned long long)r.bit_errors,
