@@ -36,6 +36,7 @@
  *   qldpc_toeplitz*                       (not in the reference) Toeplitz hashing, the sound replacement of that loop
  *   qldpc_mc_*                            the simulation loop itself: source, encoder, BSC, decoder, Monitor_BFER   BS/src/main.cpp:335-393
  *   qldpc_mc_search / _patterns_dev       the puncture-pattern search around it: shuffle, erase, first FER = 0 / n  BS/src/main.cpp:235-411
+ *   qldpc_mc_set_channel / _awgn_table    the channel of the fixed-point sims: BPSK over AWGN, 6-bit received values  ML/BPSK_nrldpc_sim_RM_FP.m
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -561,7 +562,8 @@ int    qldpc_toeplitz_host(const uint32_t *key_words, int key_bits, const uint32
  * The loop of the reference harness -- source -> encoder -> BSC -> decoder -> monitor (BS/src/main.cpp:335-393, Monitor_BFER's max_fe stop
  * rule) -- with nothing per bit crossing the host (csrc/qldpc_mc.hip).  Frame number i is a 64-bit GLOBAL index and its content a pure
  * function of (seed, i) (csrc/qldpc_mc_core.h): it does not depend on the batch size, the launch shape or the device, so ranks and batches
- * take disjoint index ranges and a failed frame can be generated again alone.
+ * take disjoint index ranges and a failed frame can be generated again alone.  The channel is the BSC below unless qldpc_mc_set_channel set a
+ * table of a quantised soft-output channel (further down).
  *
  *   generator  Philox4x32-10, key = (seed low word, seed high word)
  *   source     info word j of frame i = output word j % 4 at counter (j / 4, 0, i_lo, i_hi), MSB-first, the bits past K cleared
@@ -617,12 +619,13 @@ typedef struct qldpc_mc_result {
     uint64_t undetected;    /* ... whose hard decision nevertheless has a zero syndrome                                              */
     uint64_t not_converged; /* frames whose hard decision has a non-zero syndrome                                                    */
     uint64_t iter_sum, iter_max;
-    uint64_t channel_flips, channel_bits;   /* flips drawn at QLDPC_VN_CHANNEL VNs / such VNs seen: the empirical QBER               */
+    uint64_t channel_flips, channel_bits;   /* flips drawn at QLDPC_VN_CHANNEL VNs / such VNs seen: the empirical QBER (with a table: the
+                                               hard-decision error rate of those VNs)                                                */
     uint64_t batches;
     uint64_t next_frame;    /* first_frame + frames: where a following run continues                                                 */
     double decode_ms;       /* qldpc_run alone, by hipEvents: what SIM_THR of the harness means                                      */
     double source_ms, encode_ms, channel_ms, load_ms, monitor_ms;   /* the other stages of the batches, by hipEvents: info words, encoder,
-                               BSC, qldpc_load_bits_dev, fetch + monitor                                                             */
+                               channel, qldpc_load_bits_dev (with a table: qldpc_load_llr_dev), fetch + monitor                      */
     double total_ms;        /* the whole call on the host's clock                                                                    */
 } qldpc_mc_result;
 
@@ -648,6 +651,53 @@ int    qldpc_mc_iter_hist(qldpc_mc *mc, uint64_t *hist, int cap);
 /* of the last run: the global indices of the failed frames kept (the first fail_cap in batch order, ascending); writes min(cap, kept) and
    returns kept (or a status) */
 int    qldpc_mc_failed_frames(qldpc_mc *mc, uint64_t *frames, int cap);
+
+/*
+ * Quantised soft-output channels.  Besides the BSC the loop runs any binary-input channel with 2 <= Q <= 256 output levels given by a
+ * threshold table (csrc/qldpc_mc_core.h): VN v of frame i draws u = output word v % 4 of the generator at counter (v / 4, 3, i_lo, i_hi) --
+ * stream 3, so the BSC's frames do not move -- and, b being its codeword bit,
+ *
+ *   level = #{k : u >= cum[b][k]}        P(level | b) = (cum[b][level] - cum[b][level - 1]) / 2^32 exactly, cum[b][-1] = 0, cum[b][Q-1] = 2^32
+ *
+ * cum[b] (Q - 1 entries, uint64_t) is non-decreasing with entries in [0, 2^32]; repeated entries are levels of probability zero, entries equal
+ * to 2^32 levels that nothing reaches.  Per class: QLDPC_VN_CHANNEL LLR = value[level]; QLDPC_VN_PINNED LLR = +-QLDPC_CONFIRMED_BIT_LLR by the
+ * codeword bit, the sign inverted iff the same u < floor(parity_ber 2^32); QLDPC_VN_PUNCTURED LLR = 0.  The rx bit of a VN is its codeword bit,
+ * inverted iff the sign of the LLR contradicts it (b = 0 and LLR < 0, or b = 1 and LLR > 0; 0 contradicts nothing), so channel_flips /
+ * channel_bits becomes the hard-decision error rate of the channel VNs.  Frames stay a pure function of (seed, i) and the table; no floating
+ * point is computed on the device.
+ *
+ * With a table set, qldpc_mc_run and qldpc_mc_search generate through the soft kernel and load the decoder with qldpc_load_llr_dev; their
+ * qber argument is validated as before and otherwise IGNORED.  The fixed puncture set and the search's erase rows go on top as with the BSC.
+ * qldpc_mc_frames_dev stays the BSC's frame call whatever is set.  qldpc_mc_set_channel returns QLDPC_ESIZE for levels outside 2 .. 256 (or a
+ * batch whose quads pass 2^31 lanes) and QLDPC_EINVAL for a missing array, a decreasing row, an entry above 2^32 or non-zero reserved words; a
+ * refused call leaves the previous table in force.  NULL, or levels = 0, returns the object to the BSC.  The first accepted table allocates
+ * the LLR rows [batch][N] (counted by qldpc_mc_device_bytes).  Not built: unquantised float noise, a table per VN class, non-binary input.
+ */
+typedef struct qldpc_mc_channel {
+    int levels;                /* Q, 2 .. 256; 0 = no table (the BSC)                                                                    */
+    const uint64_t *cum[2];    /* cum[b][Q - 1], b = the codeword bit                                                                     */
+    const float *value;        /* value[Q]: the LLR of a level                                                                            */
+    int reserved[2];           /* must be zero                                                                                            */
+} qldpc_mc_channel;
+enum { QLDPC_MC_SOURCE_RANDOM = 0, QLDPC_MC_SOURCE_ZERO = 1 };
+int    qldpc_mc_set_channel(qldpc_mc *mc, const qldpc_mc_channel *table);
+/* QLDPC_MC_SOURCE_ZERO: all-zero info words, hence the all-zero codeword, in every call that generates frames (the published fixed-point
+   AWGN table of the reference needs it, tests/matlab_fp.py); QLDPC_MC_SOURCE_RANDOM is the default */
+int    qldpc_mc_set_source(qldpc_mc *mc, int mode);
+/* host only: the table of BPSK over AWGN, r = (1 - 2 b) + sigma n quantised to floor(r / rmax * maxq) clamped to [-maxq - 1, maxq]: Q = 2 maxq
+   + 2 levels (1 <= maxq <= 127), boundary k at (k - maxq) rmax / maxq, cum[b][k] = floor(2^32 Phi((boundary_k - (1 - 2 b)) / sigma)) with
+   Phi(x) = erfc(-x / sqrt 2) / 2 in double, value[l] = l - maxq - 1.  cum0, cum1: Q - 1 entries; value: Q.  QLDPC_ESIZE for sigma or rmax not
+   positive and finite or maxq outside 1 .. 127 */
+int    qldpc_mc_awgn_table(double sigma, double rmax, int maxq, uint64_t *cum0, uint64_t *cum1, float *value);
+/* host mirror, no device needed: LLR rows llr[n][N] and flip words [n][ceil(N/32)] (either may be NULL) of frames [first_frame, first_frame +
+   n_frames) whose codewords are cw_words[n][ceil(N/32)] (NULL = the all-zero codeword); info_bits_pos and vn_class as qldpc_mc_frames_host */
+int    qldpc_mc_llr_host(int K, int N, const int *info_bits_pos, const uint8_t *vn_class, uint64_t seed, double parity_ber,
+                         const qldpc_mc_channel *table, const uint32_t *cw_words, uint64_t first_frame, int n_frames, float *llr,
+                         uint32_t *flip_words);
+/* the soft counterpart of qldpc_mc_frames_dev through the table that is set (QLDPC_ESTATE without one): d_info[n][ceil(K/32)],
+   d_cw[n][ceil(N/32)], d_rx[n][ceil(N/32)] (may be NULL) and d_llr[n][N] float, frame-major as qldpc_load_llr_dev takes them.  QLDPC_ESIZE
+   where n_frames * 8 ceil(N/32) passes 2^31.  Asynchronous on the decoder's stream. */
+int    qldpc_mc_llr_dev(qldpc_mc *mc, uint64_t first_frame, int n_frames, uint32_t *d_info, uint32_t *d_cw, uint32_t *d_rx, float *d_llr);
 
 /* host mirror, no device needed: the candidate indices (into the candidate list) of pattern `pattern`, ascending */
 int    qldpc_mc_pattern_host(uint64_t seed, uint64_t pattern, int n_cand, int n_punct, int key_bits, int *idx /* n_punct */);

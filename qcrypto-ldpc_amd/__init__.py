@@ -920,6 +920,19 @@ _sig("qldpc_mc_search", C.c_int, [_vp, C.c_double, C.POINTER(McSearchCfg), C.c_u
 _sig("qldpc_mc_search_stats", C.c_int, [_vp, _vp, C.c_int])
 
 
+class McChannel(C.Structure):
+    _fields_ = [("levels", C.c_int), ("cum", _u64p * 2), ("value", C.POINTER(C.c_float)), ("reserved", C.c_int * 2)]
+
+
+MC_SOURCE = {"random": 0, "zero": 1}
+_fp = C.POINTER(C.c_float)
+_sig("qldpc_mc_set_channel", C.c_int, [_vp, C.POINTER(McChannel)])
+_sig("qldpc_mc_set_source", C.c_int, [_vp, C.c_int])
+_sig("qldpc_mc_awgn_table", C.c_int, [C.c_double, C.c_double, C.c_int, _u64p, _u64p, _fp])
+_sig("qldpc_mc_llr_host", C.c_int, [C.c_int, C.c_int, _ip, _u8p, C.c_uint64, C.c_double, C.POINTER(McChannel), _up, C.c_uint64, C.c_int, _fp, _up])
+_sig("qldpc_mc_llr_dev", C.c_int, [_vp, C.c_uint64, C.c_int, _vp, _vp, _vp, _vp])
+
+
 def mc_philox_host(counter, key):
     """Philox4x32-10 of a (counter[4], key[2]) -> 4 uint32 words (host mirror of the kernels' generator)"""
     c = np.ascontiguousarray(counter, dtype=np.uint32).ravel()
@@ -968,6 +981,59 @@ def mc_pattern_host(seed, pattern, n_cand, n_punct, key_bits=32):
     return idx
 
 
+def _mc_channel_arg(cum0, cum1, value, where):
+    """-> (McChannel, the arrays it points into): levels = len(value), the rows uint64 of levels - 1 entries"""
+    c0, c1 = (np.ascontiguousarray(c, dtype=np.uint64).ravel() for c in (cum0, cum1))
+    val = np.ascontiguousarray(value, dtype=np.float32).ravel()
+    if c0.size != c1.size or c0.size + 1 != val.size:
+        raise QldpcError(-6, "%s: %d and %d thresholds for %d levels" % (where, c0.size, c1.size, val.size))
+    t = McChannel()
+    t.levels = val.size
+    t.cum[0], t.cum[1], t.value = c0.ctypes.data_as(_u64p), c1.ctypes.data_as(_u64p), val.ctypes.data_as(_fp)
+    return t, (c0, c1, val)
+
+
+def mc_awgn_sigma(ebno_db, rate):
+    """the noise deviation of BPSK at Eb/N0 (dB) and code rate `rate`: sqrt(1 / (2 rate 10^(ebno_db / 10)))"""
+    return float(np.sqrt(1.0 / (2.0 * float(rate) * 10.0 ** (float(ebno_db) / 10.0))))
+
+
+def mc_awgn_table(sigma, rmax=3.0, maxq=31):
+    """The threshold table of BPSK over AWGN quantised to floor(r / rmax * maxq), clamped to [-maxq - 1, maxq] (host only) ->
+    (cum0, cum1 [2 maxq + 1] uint64, value [2 maxq + 2] float32 = -maxq - 1 .. maxq): what MonteCarlo.set_channel takes"""
+    q = 2 * int(maxq) + 2
+    c0, c1, val = np.zeros(max(q - 1, 1), np.uint64), np.zeros(max(q - 1, 1), np.uint64), np.zeros(max(q, 1), np.float32)
+    _chk(_L.qldpc_mc_awgn_table(float(sigma), float(rmax), int(maxq), c0.ctypes.data_as(_u64p), c1.ctypes.data_as(_u64p), val.ctypes.data_as(_fp)), "mc_awgn_table")
+    return c0, c1, val
+
+
+def mc_llr_host(K, N, seed, table, first_frame, n_frames, cw_words=None, info_bits_pos=None, vn_class=None, parity_ber=0.0):
+    """Frames [first_frame, first_frame + n_frames) of the quantised-channel definition on the host, no device needed: table =
+    (cum0, cum1, value), cw_words [n, ceil(N/32)] the packed codewords (None = all-zero) -> (LLRs [n, N] float32, flip words
+    [n, ceil(N/32)] uint32: the VNs whose LLR sign contradicts the codeword bit)"""
+    K, N, n = int(K), int(N), int(n_frames)
+    pos = None
+    if info_bits_pos is not None:
+        pos = _np_i32(info_bits_pos).ravel()
+        if pos.size != K:
+            raise QldpcError(-6, "mc_llr_host: len(info_bits_pos) != K")
+    cls = _mc_class_arg(vn_class, N, "mc_llr_host")
+    t, keep = _mc_channel_arg(*table, "mc_llr_host")
+    Wn = (max(N, 0) + 31) // 32
+    cw = None
+    if cw_words is not None:
+        cw = np.ascontiguousarray(cw_words, dtype=np.uint32)
+        if cw.shape != (max(n, 0), Wn):
+            raise QldpcError(-6, "mc_llr_host: codeword words %s, expected (%d, %d)" % (cw.shape, n, Wn))
+    llr = np.zeros((max(n, 0), max(N, 0)), np.float32)
+    flips = np.zeros((max(n, 0), Wn), np.uint32)
+    _chk(_L.qldpc_mc_llr_host(K, N, pos.ctypes.data_as(_ip) if pos is not None else None, cls.ctypes.data_as(_u8p) if cls is not None else None,
+                              int(seed) & 0xFFFFFFFFFFFFFFFF, float(parity_ber), C.byref(t), cw.ctypes.data_as(_up) if cw is not None else None,
+                              int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, llr.ctypes.data_as(_fp), flips.ctypes.data_as(_up)), "mc_llr_host")
+    del keep
+    return llr, flips
+
+
 class MonteCarlo:
     """The harness's loop source -> encoder -> BSC -> decoder -> monitor on the device (qldpc_mc_*), around a Decoder and an Encoder of
     the same code, which it keeps alive but does not own.  Frame i is a pure function of (seed, i): run() over [first_frame, first_frame +
@@ -1011,6 +1077,46 @@ class MonteCarlo:
                                     _vp(rx.data_ptr())), "MonteCarlo.frames")
         self.decoder.sync()
         return info, cw, rx
+
+    def set_channel(self, cum0=None, cum1=None, value=None):
+        """A quantised soft-output channel in place of the BSC: level = #{k : u >= cum[b][k]} of the VN's stream-3 word u and codeword bit
+        b, LLR = value[level] (include/qldpc.h).  run() and search() then ignore their qber (it is still validated).  None returns to the BSC."""
+        if cum0 is None and cum1 is None and value is None:
+            _chk(_L.qldpc_mc_set_channel(self._h, None), "MonteCarlo.set_channel")
+            return
+        t, keep = _mc_channel_arg(cum0, cum1, value, "MonteCarlo.set_channel")
+        _chk(_L.qldpc_mc_set_channel(self._h, C.byref(t)), "MonteCarlo.set_channel")
+        del keep
+
+    def set_awgn(self, sigma=None, rmax=3.0, maxq=31, ebno_db=None, rate=None):
+        """BPSK over AWGN quantised to 2 maxq + 2 levels (mc_awgn_table): sigma, or ebno_db together with rate -> sigma"""
+        if (sigma is None) == (ebno_db is None) or (ebno_db is not None and rate is None):
+            raise QldpcError(-1, "MonteCarlo.set_awgn: sigma, or ebno_db together with rate")
+        if sigma is None:
+            sigma = mc_awgn_sigma(ebno_db, rate)
+        self.set_channel(*mc_awgn_table(sigma, rmax, maxq))
+        return float(sigma)
+
+    def set_source(self, mode):
+        """"random" (the default) or "zero": all-zero info words, hence the all-zero codeword"""
+        if mode not in MC_SOURCE:
+            raise QldpcError(-1, "MonteCarlo.set_source: %r is neither 'random' nor 'zero'" % (mode,))
+        _chk(_L.qldpc_mc_set_source(self._h, MC_SOURCE[mode]), "MonteCarlo.set_source")
+
+    def llr_frames(self, first_frame, n_frames):
+        """the frames of the table that is set -> device tensors (info [n, ceil(K/32)], cw [n, ceil(N/32)], rx [n, ceil(N/32)] int32 and
+        llr [n, N] float32): the LLR rows and rx ^ cw are what mc_llr_host gives for the encoder's codewords"""
+        torch = _torch()
+        n = int(n_frames)
+        dev = "cuda:%d" % self.device
+        info = torch.empty((n, (self.K + 31) // 32), dtype=torch.int32, device=dev)
+        cw = torch.empty((n, (self.N + 31) // 32), dtype=torch.int32, device=dev)
+        rx = torch.empty_like(cw)
+        llr = torch.empty((n, self.N), dtype=torch.float32, device=dev)
+        _chk(_L.qldpc_mc_llr_dev(self._h, int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, _vp(info.data_ptr()), _vp(cw.data_ptr()), _vp(rx.data_ptr()),
+                                 _vp(llr.data_ptr())), "MonteCarlo.llr_frames")
+        self.decoder.sync()
+        return info, cw, rx, llr
 
     def iter_hist(self):
         """frames per iteration count of the last run, n_ite + 1 bins (uint64)"""

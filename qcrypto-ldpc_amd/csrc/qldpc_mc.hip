@@ -7,6 +7,10 @@
  * mc_channel: one lane per codeword word: 8 Philox calls, the 32 classes of the word by two 16-byte loads from the padded class map (32 N
  *     bytes shared by all frames: L2-resident), the two thresholds wave-uniform kernel arguments; rx = cw ^ flips.  The lanes of word 0 also
  *     write the frame's |LLR| for qldpc_load_bits_dev.
+ * mc_soft_channel: the quantised soft-output channel of a threshold table (qldpc_mc_core.h), one lane per four VNs: one Philox call, one class
+ *     word, both threshold rows and the value row in LDS (3 KB, loaded once per workgroup), a halving search per VN, one 16-byte store of the
+ *     four LLRs where the address allows it (scalars where N % 4 != 0 shifts a row or cuts its last quad); the rx word = the OR of the flip
+ *     nibbles of the 8 lanes of a codeword word by xor-shuffles, stored by the first of them.  No atomics, no floating-point arithmetic.
  * mc_monitor: one wave per frame (a wave strides over the frames): be = popcount((out ^ cw) & info_mask) and the flips at channel VNs summed
  *     over the lanes by shuffles, the per-frame verdicts summed in (wave-uniform) registers over the wave's frames, then ONE atomicAdd per
  *     wave and counter from lane 0 -- plus, per frame, one on the iteration histogram and, for a failed frame, one returning add on the
@@ -62,6 +66,38 @@ __global__ __launch_bounds__(MC_LANES) void mc_channel(const uint32_t *__restric
     const uint32_t cls4[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     rx[i] = cw[i] ^ mc_flip_word(seed, first + f, w, cls4, t_channel, t_pinned);
     if (w == 0 && llr_mag) llr_mag[f] = mag;
+}
+
+/* rows of 8 Wn quads (the padding past N is QLDPC_VN_PUNCTURED: LLR 0, no flip, nothing stored), total = n 8 Wn lanes: a multiple of 8, as the
+ * block size is, so the 8 lanes of a codeword word leave or stay together and the shuffles below see all of them.  rx may be NULL. */
+__global__ __launch_bounds__(MC_LANES) void mc_soft_channel(const uint32_t *__restrict__ cw, uint32_t *__restrict__ rx, float *__restrict__ llr,
+                                                            const uint32_t *__restrict__ cls4, const mc_soft_table *__restrict__ tab, unsigned total,
+                                                            unsigned Qn, unsigned N, uint64_t seed, uint64_t first, uint32_t t_pinned)
+{
+    static_assert(MC_LANES == MC_SOFT_MAX_LEVELS, "mc_soft_channel loads one table entry per lane");
+    __shared__ uint32_t thr[2][MC_SOFT_MAX_LEVELS];
+    __shared__ float value[MC_SOFT_MAX_LEVELS];
+    const unsigned t = threadIdx.x;
+    thr[0][t] = t < MC_SOFT_MAX_LEVELS - 1 ? tab->thr[0][t] : 0xFFFFFFFFu;
+    thr[1][t] = t < MC_SOFT_MAX_LEVELS - 1 ? tab->thr[1][t] : 0xFFFFFFFFu;
+    value[t] = tab->value[t];
+    const uint32_t live0 = tab->live[0], live1 = tab->live[1];
+    __syncthreads();
+    const unsigned i = blockIdx.x * MC_LANES + t;
+    if (i >= total) return;
+    const unsigned f = i / Qn, q = i - f * Qn, sh = 28u - 4u * (q & 7u);
+    const uint32_t c = cw[i >> 3];
+    float l[4];
+    uint32_t flips = mc_soft_quad(seed, first + f, q, cls4[q], (c >> sh) & 0xfu, thr[0], live0, thr[1], live1, value, t_pinned, l) << sh;
+    const unsigned v = 4u * q;
+    if (v < N) {
+        float *p = llr + (size_t)f * N + v;
+        if (v + 4u <= N && ((uintptr_t)p & 15u) == 0) *(float4 *)p = make_float4(l[0], l[1], l[2], l[3]);
+        else for (unsigned b = 0; b < 4u && v + b < N; b++) p[b] = l[b];
+    }
+    if (!rx) return;
+    for (int s = 1; s < 8; s <<= 1) flips |= (uint32_t)__shfl_xor((int)flips, s, 64);
+    if ((q & 7u) == 0) rx[i >> 3] = c ^ flips;
 }
 
 __device__ static inline unsigned mc_wave_sum(unsigned x)
@@ -237,6 +273,11 @@ struct qldpc_mc {
     mc_u64 *d_rows, *h_rows;           /* [batch][MCP_COUNTERS] counter rows of a round; pinned copy */
     hipEvent_t sev[8];                 /* of a search round: patterns | expand | generate | load | erase | run | fetch + monitor */
     std::vector<qldpc_mc_pattern_stat> stats;   /* of the last search */
+    /* a quantised soft-output channel in place of the BSC; the device side is allocated by the first accepted qldpc_mc_set_channel */
+    bool soft;                         /* a table is in force */
+    int source;                        /* QLDPC_MC_SOURCE_* */
+    mc_soft_table *d_tab;
+    float *d_llr;                      /* [batch][N], what qldpc_load_llr_dev takes */
 };
 
 extern "C" void qldpc_mc_cfg_default(qldpc_mc_cfg *cfg)
@@ -251,7 +292,7 @@ extern "C" void qldpc_mc_free(qldpc_mc *mc)
     if (!mc) return;
     (void)hipSetDevice(mc->device);
     void *dev[] = {mc->d_cls, mc->d_info_mask, mc->d_chan_mask, mc->d_info, mc->d_cw, mc->d_rx, mc->d_out, mc->d_mag, mc->d_iters, mc->d_ok, mc->d_ctr,
-                   mc->d_cand, mc->d_pat, mc->d_erase, mc->d_fixed, mc->d_rows};
+                   mc->d_cand, mc->d_pat, mc->d_erase, mc->d_fixed, mc->d_rows, mc->d_tab, mc->d_llr};
     for (void *p : dev) if (p) (void)hipFree(p);
     if (mc->h_ctr) (void)hipHostFree(mc->h_ctr);
     if (mc->h_rows) (void)hipHostFree(mc->h_rows);
@@ -336,18 +377,28 @@ extern "C" size_t qldpc_mc_device_bytes(const qldpc_mc *mc) { return mc ? mc->de
 static unsigned mc_blocks(size_t lanes) { return (unsigned)((lanes + MC_LANES - 1) / MC_LANES); }
 
 /* source -> encoder -> channel for frames [first, first + n) on stream s; d_cw / d_rx / d_mag may be NULL from the right; ev != NULL: ev[1] after the
- * source, ev[2] after the encoder */
+ * source, ev[2] after the encoder.  d_llr != NULL: the channel of the table instead of the BSC, LLR rows into d_llr (d_rx may then be NULL alone,
+ * qber and d_mag are not used); the caller has checked n 8 Wn < 2^31 */
 static int mc_generate(qldpc_mc *mc, uint64_t first, int n, double qber, uint32_t *d_info, uint32_t *d_cw, uint32_t *d_rx, float *d_mag, hipStream_t s,
-                       hipEvent_t *ev = nullptr)
+                       hipEvent_t *ev = nullptr, float *d_llr = nullptr)
 {
     const unsigned ti = (unsigned)n * (unsigned)mc->Wk, tn = (unsigned)n * (unsigned)mc->Wn;
-    hipLaunchKernelGGL(mc_source, dim3(mc_blocks(ti)), dim3(MC_LANES), 0, s, d_info, ti, (unsigned)mc->Wk, mc->K, mc->seed, first);
-    LAUNCHCHK();
+    if (mc->source == QLDPC_MC_SOURCE_ZERO) HIPCHK(hipMemsetAsync(d_info, 0, sizeof(uint32_t) * ti, s));
+    else {
+        hipLaunchKernelGGL(mc_source, dim3(mc_blocks(ti)), dim3(MC_LANES), 0, s, d_info, ti, (unsigned)mc->Wk, mc->K, mc->seed, first);
+        LAUNCHCHK();
+    }
     if (ev) HIPCHK(hipEventRecord(ev[1], s));
     if (!d_cw) return QLDPC_OK;
     const int rc = qldpc_encode_packed_dev(mc->enc, d_info, d_cw, n, (void *)s);
-    if (rc || !d_rx) return rc;
+    if (rc || (!d_rx && !d_llr)) return rc;
     if (ev) HIPCHK(hipEventRecord(ev[2], s));
+    if (d_llr) {
+        hipLaunchKernelGGL(mc_soft_channel, dim3(mc_blocks(8 * (size_t)tn)), dim3(MC_LANES), 0, s, (const uint32_t *)d_cw, d_rx, d_llr, (const uint32_t *)mc->d_cls,
+                           (const mc_soft_table *)mc->d_tab, 8u * tn, 8u * (unsigned)mc->Wn, (unsigned)mc->N, mc->seed, first, mc_threshold(mc->parity_ber));
+        LAUNCHCHK();
+        return QLDPC_OK;
+    }
     hipLaunchKernelGGL(mc_channel, dim3(mc_blocks(tn)), dim3(MC_LANES), 0, s, (const uint32_t *)d_cw, d_rx, (const uint4 *)mc->d_cls, tn, (unsigned)mc->Wn,
                        mc->seed, first, mc_threshold(qber), mc_threshold(mc->parity_ber), d_mag, qldpc_bsc_llr((float)qber));
     LAUNCHCHK();
@@ -362,6 +413,60 @@ extern "C" int qldpc_mc_frames_dev(qldpc_mc *mc, uint64_t first_frame, int n_fra
     if (n_frames == 0) return QLDPC_OK;
     HIPCHK(hipSetDevice(mc->device));
     return mc_generate(mc, first_frame, n_frames, qber, d_info, d_cw, d_rx, nullptr, mc->dec->stream);
+}
+
+/* the frames of a batch into the decoder, by the channel in force: generate (ev as mc_generate takes it), ev_channel, load */
+static int mc_generate_load(qldpc_mc *mc, uint64_t first, int n, double qber, hipStream_t s, hipEvent_t *ev, hipEvent_t ev_channel)
+{
+    const int rc = mc_generate(mc, first, n, qber, mc->d_info, mc->d_cw, mc->d_rx, mc->d_mag, s, ev, mc->soft ? mc->d_llr : nullptr);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(ev_channel, s));
+    return mc->soft ? qldpc_load_llr_dev(mc->dec, mc->d_llr, n) : qldpc_load_bits_dev(mc->dec, mc->d_rx, mc->d_mag, mc->d_cls, n);
+}
+
+/* mc_soft_channel runs n 8 Wn lanes */
+static int mc_soft_lanes_check(const qldpc_mc *mc, const char *who, int n_frames)
+{
+    if ((uint64_t)n_frames * 8u * (uint64_t)mc->Wn < (1ull << 31)) return QLDPC_OK;
+    qldpc_set_error("%s: %d frames of N = %d pass 2^31 lanes of four VNs", who, n_frames, mc->N);
+    return QLDPC_ESIZE;
+}
+
+extern "C" int qldpc_mc_set_source(qldpc_mc *mc, int mode)
+{
+    if (!mc) return QLDPC_EINVAL;
+    if (mode != QLDPC_MC_SOURCE_RANDOM && mode != QLDPC_MC_SOURCE_ZERO) { qldpc_set_error("mc_set_source: mode=%d", mode); return QLDPC_EINVAL; }
+    mc->source = mode;
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_set_channel(qldpc_mc *mc, const qldpc_mc_channel *table)
+{
+    if (!mc) return QLDPC_EINVAL;
+    if (!table || table->levels == 0) { mc->soft = false; return QLDPC_OK; }
+    if (table->reserved[0] || table->reserved[1]) { qldpc_set_error("mc_set_channel: reserved words %d, %d must be zero", table->reserved[0], table->reserved[1]); return QLDPC_EINVAL; }
+    mc_soft_table tab;
+    int rc = mc_soft_table_build(table->levels, table->cum[0], table->cum[1], table->value, &tab);
+    if (rc == -1) { qldpc_set_error("mc_set_channel: levels=%d outside 2 .. %d", table->levels, MC_SOFT_MAX_LEVELS); return QLDPC_ESIZE; }
+    if (rc) { qldpc_set_error("mc_set_channel: a missing array, a row that decreases or an entry above 2^32"); return QLDPC_EINVAL; }
+    if ((rc = mc_soft_lanes_check(mc, "mc_set_channel", mc->batch))) return rc;
+    HIPCHK(hipSetDevice(mc->device));
+    if ((!mc->d_tab && (rc = mc_alloc(mc, &mc->d_tab, 1))) || (!mc->d_llr && (rc = mc_alloc(mc, &mc->d_llr, (size_t)mc->batch * (size_t)mc->N)))) return rc;
+    HIPCHK(hipStreamSynchronize(mc->dec->stream));      /* a queued channel kernel may still read the old table */
+    HIPCHK(hipMemcpy(mc->d_tab, &tab, sizeof(tab), hipMemcpyHostToDevice));
+    mc->soft = true;
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_llr_dev(qldpc_mc *mc, uint64_t first_frame, int n_frames, uint32_t *d_info, uint32_t *d_cw, uint32_t *d_rx, float *d_llr)
+{
+    if (!mc || !d_info || !d_cw || !d_llr || n_frames < 0) return QLDPC_EINVAL;
+    if (!mc->soft) { qldpc_set_error("mc_llr_dev: no channel table is set (qldpc_mc_set_channel)"); return QLDPC_ESTATE; }
+    const int rc = mc_soft_lanes_check(mc, "mc_llr_dev", n_frames);
+    if (rc) return rc;
+    if (n_frames == 0) return QLDPC_OK;
+    HIPCHK(hipSetDevice(mc->device));
+    return mc_generate(mc, first_frame, n_frames, 0.0, d_info, d_cw, d_rx, nullptr, mc->dec->stream, nullptr, d_llr);
 }
 
 static void mc_result(const qldpc_mc *mc, uint64_t first, qldpc_mc_result *r)
@@ -399,10 +504,8 @@ extern "C" int qldpc_mc_run(qldpc_mc *mc, double qber, uint64_t first_frame, uin
         const int nb = (int)std::min<uint64_t>((uint64_t)mc->batch, max_frames - done);
         const uint64_t first = first_frame + done;
         HIPCHK(hipEventRecord(mc->ev[0], s));
-        int rc = mc_generate(mc, first, nb, qber, mc->d_info, mc->d_cw, mc->d_rx, mc->d_mag, s, mc->ev);
+        int rc = mc_generate_load(mc, first, nb, qber, s, mc->ev, mc->ev[3]);
         if (rc) return rc;
-        HIPCHK(hipEventRecord(mc->ev[3], s));
-        if ((rc = qldpc_load_bits_dev(mc->dec, mc->d_rx, mc->d_mag, mc->d_cls, nb))) return rc;
         if (mc->n_fixed && (rc = mc_erase(mc, mc->d_fixed, nb, nb, s))) return rc;      /* the fixed puncture set: one row for all nb frames */
         HIPCHK(hipEventRecord(mc->ev[4], s));
         if ((rc = qldpc_run(mc->dec))) return rc;
@@ -578,9 +681,7 @@ extern "C" int qldpc_mc_search(qldpc_mc *mc, double qber, const qldpc_mc_search_
         hipLaunchKernelGGL(mc_expand_rows, dim3(mc_blocks(((size_t)total + 3) / 4)), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_pat, mc->d_erase, total, Wn, F);
         LAUNCHCHK();
         HIPCHK(hipEventRecord(mc->sev[2], s));
-        if ((rc = mc_generate(mc, frame0, nb, qber, mc->d_info, mc->d_cw, mc->d_rx, mc->d_mag, s))) return rc;
-        HIPCHK(hipEventRecord(mc->sev[3], s));
-        if ((rc = qldpc_load_bits_dev(mc->dec, mc->d_rx, mc->d_mag, mc->d_cls, nb))) return rc;
+        if ((rc = mc_generate_load(mc, frame0, nb, qber, s, nullptr, mc->sev[3]))) return rc;
         HIPCHK(hipEventRecord(mc->sev[4], s));
         if ((rc = qldpc_load_erasures_dev(mc->dec, mc->d_erase, nb))) return rc;
         HIPCHK(hipEventRecord(mc->sev[5], s));

@@ -1,6 +1,7 @@
 /*
- * qldpc_mc_core.h -- the frame definition and the puncture-pattern definition of the Monte-Carlo loop (qldpc_mc_*), plain C, shared by the
- * kernels (qldpc_mc.hip) and by their host mirror (qldpc_mc_host.c), so that the CPU suite runs what the lanes run.
+ * qldpc_mc_core.h -- the frame definition, the quantised-channel definition and the puncture-pattern definition of the Monte-Carlo loop
+ * (qldpc_mc_*), plain C, shared by the kernels (qldpc_mc.hip) and by their host mirror (qldpc_mc_host.c), so that the CPU suite runs what
+ * the lanes run.
  *
  * Frame i (a 64-bit global index) is a pure function of (seed, i): nothing depends on the batch size, the launch shape or the device.
  *
@@ -77,6 +78,88 @@ MC_FN uint32_t mc_flip_word(uint64_t seed, uint64_t frame, uint32_t w, const uin
             if (o[b] < t[b]) flips |= 0x80000000u >> (4u * g + b);
     }
     return flips;
+}
+
+/*
+ * Quantised soft-output channels (qldpc_mc_set_channel, mc_soft_channel).  A binary-input channel with Q <= 256 output levels is given by
+ * thresholds: VN v of frame i draws u = output word v % 4 at counter (v / 4, 3, i_lo, i_hi) and its level is the number of thresholds of the
+ * sent bit's row that u has passed,
+ *
+ *   level = #{k : u >= cum[b][k]},   so that   P(level | b) = (cum[b][level] - cum[b][level - 1]) / 2^32   exactly
+ *
+ * (cum[b][-1] = 0, cum[b][Q-1] = 2^32); the decoder is handed value[level].  The rows are non-decreasing with entries in [0, 2^32]; the
+ * entries equal to 2^32 -- levels that nothing reaches -- sit at the end of a row, so a row is kept as its 32-bit thresholds below 2^32
+ * and their number (live).  Repeated thresholds give levels of probability zero.  Per class:
+ *
+ *   QLDPC_VN_CHANNEL    LLR = value[level]
+ *   QLDPC_VN_PINNED     LLR = +-QLDPC_CONFIRMED_BIT_LLR by the sent bit, the sign inverted iff the same u < floor(parity_ber 2^32)
+ *   QLDPC_VN_PUNCTURED  LLR = 0
+ *
+ * and the VN's flip bit (the rx row, hence channel_flips) is set iff the sign of the LLR contradicts the sent bit: b = 0 and LLR < 0, or
+ * b = 1 and LLR > 0.  An LLR of 0 is no flip.  Stream 3 is this channel's own: the frames of the BSC (stream 1) do not move.
+ */
+#define MC_STREAM_SOFT 3u
+#define MC_SOFT_MAX_LEVELS 256
+#define MC_CONFIRMED_LLR 23.025850929840455f       /* QLDPC_CONFIRMED_BIT_LLR of include/qldpc.h */
+
+typedef struct mc_soft_table {
+    uint32_t levels, live[2];                      /* Q; the thresholds below 2^32 per row, at most Q - 1 */
+    uint32_t thr[2][MC_SOFT_MAX_LEVELS - 1];
+    float value[MC_SOFT_MAX_LEVELS];
+} mc_soft_table;
+
+/* #{k < live : u >= thr[k]} of an ascending row, live <= 255: eight halving steps, no data-dependent branch */
+MC_FN uint32_t mc_soft_level(const uint32_t *thr, uint32_t live, uint32_t u)
+{
+    uint32_t lo = 0;      /* thr[0 .. lo-1] <= u */
+    for (uint32_t step = MC_SOFT_MAX_LEVELS / 2; step; step >>= 1) {
+        const uint32_t m = lo + step;
+        if (m <= live && thr[m - 1] <= u) lo = m;
+    }
+    return lo;
+}
+
+/* VNs 4 g .. 4 g + 3 of frame `frame`: cls4 = their classes, one per byte, lowest byte first; bits = their sent bits, VN 4 g + b at bit 3 - b
+ * (the MSB-first nibble of the codeword word); thr0 / thr1 / value = the table (LDS in the kernel).  Writes the four LLRs and returns the
+ * four flip bits in the layout of `bits`.  One Philox call, none where all four are punctured (the padding past N is). */
+MC_FN uint32_t mc_soft_quad(uint64_t seed, uint64_t frame, uint32_t g, uint32_t cls4, uint32_t bits, const uint32_t *thr0, uint32_t live0,
+                            const uint32_t *thr1, uint32_t live1, const float *value, uint32_t t_pinned, float llr[4])
+{
+    uint32_t o[4] = {0u, 0u, 0u, 0u}, flips = 0;
+    if (cls4 != 0x02020202u)
+        mc_philox(g, MC_STREAM_SOFT, (uint32_t)frame, (uint32_t)(frame >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), o);
+    for (uint32_t b = 0; b < 4; b++) {
+        const uint32_t c = (cls4 >> (8u * b)) & 0xffu, sent = (bits >> (3u - b)) & 1u;
+        float l = 0.0f;
+        if (c == 0u) l = value[sent ? mc_soft_level(thr1, live1, o[b]) : mc_soft_level(thr0, live0, o[b])];
+        else if (c == 1u) l = (sent != 0u) != (o[b] < t_pinned) ? -MC_CONFIRMED_LLR : MC_CONFIRMED_LLR;
+        llr[b] = l;
+        if (sent ? l > 0.0f : l < 0.0f) flips |= 8u >> b;
+    }
+    return flips;
+}
+
+/* (levels, cum0[levels - 1], cum1[levels - 1], value[levels]) -> the table.  Returns 0, -1 for levels outside 2 .. 256, -2 for a missing
+ * array, a decreasing row or an entry above 2^32; the table is written only on 0 */
+static inline int mc_soft_table_build(int levels, const uint64_t *cum0, const uint64_t *cum1, const float *value, mc_soft_table *t)
+{
+    if (levels < 2 || levels > MC_SOFT_MAX_LEVELS) return -1;
+    if (!cum0 || !cum1 || !value) return -2;
+    const uint64_t *cum[2] = {cum0, cum1};
+    for (int b = 0; b < 2; b++)
+        for (int k = 0; k < levels - 1; k++)
+            if (cum[b][k] > 4294967296ull || (k > 0 && cum[b][k] < cum[b][k - 1])) return -2;
+    t->levels = (uint32_t)levels;
+    for (int b = 0; b < 2; b++) {
+        t->live[b] = 0;
+        for (int k = 0; k < MC_SOFT_MAX_LEVELS - 1; k++) {
+            const int live = k < levels - 1 && cum[b][k] < 4294967296ull;
+            t->thr[b][k] = live ? (uint32_t)cum[b][k] : 0xFFFFFFFFu;
+            t->live[b] += (uint32_t)live;
+        }
+    }
+    for (int l = 0; l < MC_SOFT_MAX_LEVELS; l++) t->value[l] = l < levels ? value[l] : 0.0f;
+    return 0;
 }
 
 /*

@@ -1,8 +1,9 @@
 /*
- * qldpc_mc_host.c -- host mirror of the Monte-Carlo frame and pattern definitions (qldpc_mc_philox_host, qldpc_mc_frames_host,
- * qldpc_mc_pattern_host): the functions of qldpc_mc_core.h that the kernels of qldpc_mc.hip run per lane, here in a loop over frames and
- * words, or over candidates.  Plain C, no device.
+ * qldpc_mc_host.c -- host mirror of the Monte-Carlo frame, channel and pattern definitions (qldpc_mc_philox_host, qldpc_mc_frames_host,
+ * qldpc_mc_llr_host, qldpc_mc_pattern_host): the functions of qldpc_mc_core.h that the kernels of qldpc_mc.hip run per lane, here in a loop
+ * over frames and words, or over candidates; and the table builder of the quantised AWGN channel (qldpc_mc_awgn_table).  Plain C, no device.
  */
+#include <math.h>
 #include <stdlib.h>
 
 #include "../../include/qldpc.h"
@@ -46,6 +47,66 @@ int qldpc_mc_frames_host(int K, int N, const int *info_bits_pos, const uint8_t *
                 flip_words[(size_t)f * Wn + w] = mc_flip_word(seed, first_frame + (uint64_t)f, (uint32_t)w, cls4 + 8 * (size_t)w, tc, tp);
     }
     free(cls); free(cls4);
+    return rc;
+}
+
+int qldpc_mc_awgn_table(double sigma, double rmax, int maxq, uint64_t *cum0, uint64_t *cum1, float *value)
+{
+    if (!(sigma > 0.0 && sigma < INFINITY) || !(rmax > 0.0 && rmax < INFINITY) || maxq < 1 || 2 * maxq + 2 > MC_SOFT_MAX_LEVELS) {
+        qldpc_set_error("mc_awgn_table: sigma=%g rmax=%g (positive, finite), maxq=%d (1 .. %d)", sigma, rmax, maxq, MC_SOFT_MAX_LEVELS / 2 - 1);
+        return QLDPC_ESIZE;
+    }
+    if (!cum0 || !cum1 || !value) return QLDPC_EINVAL;
+    const int Q = 2 * maxq + 2;
+    uint64_t *cum[2] = {cum0, cum1};
+    for (int b = 0; b < 2; b++)
+        for (int k = 0; k < Q - 1; k++) {
+            const double boundary = (double)(k - maxq) * rmax / (double)maxq, x = (boundary - (double)(1 - 2 * b)) / sigma;
+            cum[b][k] = (uint64_t)floor(4294967296.0 * (0.5 * erfc(-x / sqrt(2.0))));
+        }
+    for (int l = 0; l < Q; l++) value[l] = (float)(l - maxq - 1);
+    return QLDPC_OK;
+}
+
+int qldpc_mc_llr_host(int K, int N, const int *info_bits_pos, const uint8_t *vn_class, uint64_t seed, double parity_ber, const qldpc_mc_channel *table,
+                      const uint32_t *cw_words, uint64_t first_frame, int n_frames, float *llr, uint32_t *flip_words)
+{
+    if (K < 1 || N < 1 || K > N) { qldpc_set_error("mc_llr_host: K=%d N=%d", K, N); return QLDPC_ESIZE; }
+    if (!(parity_ber >= 0.0 && parity_ber < 1.0)) { qldpc_set_error("mc_llr_host: parity_ber=%g outside [0, 1)", parity_ber); return QLDPC_ESIZE; }
+    if (!table || n_frames < 0 || (!llr && !flip_words)) return QLDPC_EINVAL;
+    if (table->reserved[0] || table->reserved[1]) { qldpc_set_error("mc_llr_host: reserved words of the table must be zero"); return QLDPC_EINVAL; }
+    const int Wn = (N + 31) / 32;
+    mc_soft_table *t = (mc_soft_table *)malloc(sizeof(*t));
+    uint8_t *cls = (uint8_t *)malloc(32 * (size_t)Wn);
+    uint32_t *cls4 = (uint32_t *)malloc(4 * 8 * (size_t)Wn);
+    int rc = QLDPC_OK;
+    if (!t || !cls || !cls4) rc = QLDPC_ENOMEM;
+    else if ((rc = mc_soft_table_build(table->levels, table->cum[0], table->cum[1], table->value, t))) {
+        qldpc_set_error("mc_llr_host: levels=%d outside 2 .. %d, or a row that decreases or passes 2^32", table->levels, MC_SOFT_MAX_LEVELS);
+        rc = rc == -1 ? QLDPC_ESIZE : QLDPC_EINVAL;
+    } else if (mc_classes(K, N, info_bits_pos, vn_class, cls, NULL)) {
+        qldpc_set_error("mc_llr_host: info_bits_pos outside [0, %d) or repeated, or a VN class above 2", N);
+        rc = QLDPC_EINVAL;
+    } else {
+        mc_pack_classes(cls, Wn, cls4);
+        const uint32_t tp = mc_threshold(parity_ber);
+        for (int f = 0; f < n_frames; f++)
+            for (int w = 0; w < Wn; w++) {
+                const uint32_t c = cw_words ? cw_words[(size_t)f * Wn + w] : 0u;
+                uint32_t flips = 0;
+                for (uint32_t g = 0; g < 8; g++) {
+                    float l[4];
+                    flips |= mc_soft_quad(seed, first_frame + (uint64_t)f, 8u * (uint32_t)w + g, cls4[8 * (size_t)w + g], (c >> (28u - 4u * g)) & 0xfu, t->thr[0],
+                                          t->live[0], t->thr[1], t->live[1], t->value, tp, l) << (28u - 4u * g);
+                    for (int b = 0; b < 4 && llr; b++) {
+                        const int v = 32 * w + 4 * (int)g + b;
+                        if (v < N) llr[(size_t)f * N + v] = l[b];
+                    }
+                }
+                if (flip_words) flip_words[(size_t)f * Wn + w] = flips;
+            }
+    }
+    free(t); free(cls); free(cls4);
     return rc;
 }
 

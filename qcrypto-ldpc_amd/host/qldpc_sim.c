@@ -26,6 +26,13 @@
  *                      `#   pattern` line per evaluated pattern and the `best of` line of -R; -o file writes the best pattern's VN indices;
  *                      -E does not apply)]
  *                  [-F n (with -X: frames per pattern, default 64)]
+ *                  [-A ebno_db[:rmax:maxq] (with -D: BPSK over AWGN quantised to 2 maxq + 2 levels, floor(r / rmax * maxq) clamped to [-maxq - 1, maxq],
+ *                      defaults 3 and 31, in place of the BSC -- the experiment of the reference's fixed-point MATLAB sims -- through
+ *                      qldpc_mc_set_channel; every VN goes through the channel but the -u first ones; sigma from the rate K / (N - u); one row, with
+ *                      Eb/N0 in place of the QBER; -s and -X do not apply)]
+ *                  [-u n (with -A: the first n VNs are punctured, LLR 0: the 2 z of the 5G NR matrices)]
+ *                  [-z (with -D: the all-zero codeword instead of random info words, qldpc_mc_set_source)]
+ *                  [-c scale (with -Q 8: quantiser steps per LLR unit, default 8; 1 for LLRs that are integers already, as -A gives them)]
  */
 #include <math.h>
 #include <stdint.h>
@@ -66,6 +73,8 @@ int main(int argc, char **argv)
     uint64_t max_fe = 0;
     double search_eff = 0.0;      /* -X: > 0 = the pattern search on the device towards this efficiency */
     int frames_per_pattern = 64;
+    int awgn = 0, awgn_maxq = 31, awgn_punct = 0, zero_source = 0;      /* -A, -u, -z */
+    double ebno_db = 0.0, awgn_rmax = 3.0, quant_scale = 0.0;
     const char *pattern_out = NULL;
     double parity_ber = 0.0;      /* > 0: the disclosed parity bits are themselves wrong with this probability (main.cpp (test effect of dirty parities)) */
     double target_eff = 0.0;      /* > 0: puncture parity bits up to min_cr(ber, f), as BS/src/main.cpp:235-333 does */
@@ -74,7 +83,7 @@ int main(int argc, char **argv)
     double ber_min = 0.01, ber_max = 0.03, ber_step = 0.005;
     uint64_t seed = 0;
     const char *g_method = NULL;
-    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:DRlvn")) != -1) {
+    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:u:c:DRlvnz")) != -1) {
         switch (opt) {
         case 'N': N = atoi(optarg); break;
         case 'K': K = atoi(optarg); break;
@@ -96,6 +105,10 @@ int main(int argc, char **argv)
         case 'E': max_fe = strtoull(optarg, NULL, 0); break;
         case 'X': search_eff = atof(optarg); break;
         case 'F': frames_per_pattern = atoi(optarg); break;
+        case 'A': { const int got = sscanf(optarg, "%lf:%lf:%d", &ebno_db, &awgn_rmax, &awgn_maxq); if (got != 1 && got != 3) { fprintf(stderr, "-A ebno_db[:rmax:maxq]\n"); return 2; } awgn = 1; break; }
+        case 'u': awgn_punct = atoi(optarg); break;
+        case 'z': zero_source = 1; break;
+        case 'c': quant_scale = atof(optarg); break;
         case 'o': pattern_out = optarg; break;
         case 'G': g_method = optarg; break;      /* p.G_method (VAR/main.cpp (alist-v1.0.1):135): IDENTITY | LU_DEC; QC = Encoder_LDPC_from_QC ((qc):145) */
         case 'l': layered = 1; break;
@@ -113,6 +126,9 @@ int main(int argc, char **argv)
     if (search_eff != 0.0 && !on_device) { fprintf(stderr, "qldpc_sim: -X is the pattern search on the device and needs -D\n"); return 2; }
     if (search_eff != 0.0 && max_fe) { fprintf(stderr, "qldpc_sim: -E does not apply to the pattern search (-X), which stops at the first pattern without frame errors\n"); return 2; }
     if (search_eff < 0.0) { fprintf(stderr, "qldpc_sim: -X f with f > 0\n"); return 2; }
+    if ((awgn || zero_source) && !on_device) { fprintf(stderr, "qldpc_sim: -A and -z belong to the loop on the device and need -D\n"); return 2; }
+    if (awgn && search_eff != 0.0) { fprintf(stderr, "qldpc_sim: -A does not run with the pattern search (-X)\n"); return 2; }
+    if (awgn_punct && !awgn) { fprintf(stderr, "qldpc_sim: -u needs -A\n"); return 2; }
 
     qldpc_code *H = NULL;
     int rc = alist ? qldpc_code_from_alist(alist, &H) : qc ? qldpc_code_from_qc(qc, &H) : peg ? qldpc_code_ira_peg(N, K, 0.125f, 11, 3, peg, 7, &H) : qldpc_code_ira(N, K, 0.125f, 11, 3, 7, &H);
@@ -132,6 +148,7 @@ int main(int argc, char **argv)
     cfg.rule = rule; cfg.rule_param = param; cfg.n_ite = n_ite; cfg.enable_syndrome = synd; cfg.syndrome_depth = 1; cfg.max_frames = batch;
     if (msg_bits != 32 && msg_bits != 16 && msg_bits != 8) { fprintf(stderr, "-Q 32 | 16 | 8\n"); return 2; }
     cfg.msg_dtype = msg_bits == 16 ? 1 : (msg_bits == 8 ? 2 : 0);      /* 16: binary16 message storage; 8: fixed-point min-sum */
+    cfg.quant_scale = (float)quant_scale;
     qldpc_decoder *dec = NULL;
     if ((rc = qldpc_decoder_create(H, K, pos, &cfg, &dec))) return die("decoder", rc);
 
@@ -147,7 +164,30 @@ int main(int argc, char **argv)
         qldpc_mc_cfg_default(&mcfg);
         mcfg.seed = seed; mcfg.batch = batch; mcfg.parity_ber = parity_ber;
         qldpc_mc *mc = NULL;
-        if ((rc = qldpc_mc_create(dec, enc, NULL, &mcfg, &mc))) return die("mc_create", rc);      /* NULL: info VNs through the BSC, the others pinned, as below */
+        if (awgn && (awgn_punct < 0 || awgn_punct >= N)) { fprintf(stderr, "qldpc_sim: -u %d outside [0, N = %d)\n", awgn_punct, N); return 2; }
+        uint8_t *cls = awgn ? (uint8_t *)calloc((size_t)N, 1) : NULL;      /* -A: every VN through the channel (class 0) but the punctured ones */
+        for (int v = 0; cls && v < awgn_punct; v++) cls[v] = QLDPC_VN_PUNCTURED;
+        if ((rc = qldpc_mc_create(dec, enc, cls, &mcfg, &mc))) return die("mc_create", rc);      /* NULL: info VNs through the BSC, the others pinned, as below */
+        free(cls);
+        if (zero_source && (rc = qldpc_mc_set_source(mc, QLDPC_MC_SOURCE_ZERO))) return die("mc_set_source", rc);
+        if (awgn) {      /* one row: the loop at this Eb/N0 */
+            const double rate = (double)K / (double)(N - awgn_punct), sigma = sqrt(1.0 / (2.0 * rate * pow(10.0, ebno_db / 10.0)));
+            const int Q = 2 * awgn_maxq + 2;
+            uint64_t *cum = (uint64_t *)malloc(sizeof(uint64_t) * 2 * 256);
+            float *value = (float *)malloc(sizeof(float) * 256);
+            if (!cum || !value) return die("mc_awgn_table", QLDPC_ENOMEM);
+            if ((rc = qldpc_mc_awgn_table(sigma, awgn_rmax, awgn_maxq, cum, cum + 256, value))) return die("mc_awgn_table", rc);
+            const qldpc_mc_channel table = {Q, {cum, cum + 256}, value, {0, 0}};
+            if ((rc = qldpc_mc_set_channel(mc, &table))) return die("mc_set_channel", rc);
+            free(cum); free(value);
+            printf("# Eb/N0 %.4f dB at rate %d / %d: sigma %.6f, %d levels, rmax %g\n", ebno_db, K, N - awgn_punct, sigma, Q, awgn_rmax);
+            qldpc_mc_result r;
+            if ((rc = qldpc_mc_run(mc, 0.25 /* not used with a table */, 0, (uint64_t)(frames > 0 ? frames : 0), max_fe, &r))) return die("mc_run", rc);
+            printf("  %8.4f | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", ebno_db, (unsigned long long)r.frames, (unsigned long long)r.bit_errors,
+                   (unsigned long long)r.frame_errors, (double)r.bit_errors / ((double)r.frames * K), (double)r.frame_errors / (double)r.frames,
+                   (double)r.frames * K / (r.decode_ms * 1e-3) / 1e6);
+            ber_min = 1.0; ber_max = 0.0;      /* no BSC rows */
+        }
         for (double ber = ber_min; search_eff > 0.0 && ber <= ber_max + 1e-12; ber += ber_step) {      /* every row one qldpc_mc_search */
             const int n_par = N - K;
             int n_punct = qldpc_parity_bits_to_punct(N, K, qldpc_min_code_rate((float)ber, (float)search_eff));      /* as -e computes it */

@@ -8,6 +8,9 @@ output file:
 
 split:  the per-batch hipEvent time of every stage of qldpc_mc_run (source, encode, channel, load, decode, fetch + monitor), averaged over
         --steps batches after one warm-up batch, the share (source + channel + monitor) / decode, and frames per second of the whole call.
+        With --awgn the same batches are run again through the 6-bit AWGN table (qldpc_mc_set_channel; sigma 0.4869, whose hard-decision
+        error rate is the BSC's 2 %) and `channel_ms` and `load_ms` of the soft path (mc_soft_channel, qldpc_load_llr_dev) are printed beside
+        the BSC's (mc_channel, qldpc_load_bits_dev).  The levels are not scaled to LLRs, so the soft leg's decode counters mean nothing.
 sim:    frames per second of `qldpc_sim` with and without -D at the same point.  A process is timed as a whole at two frame counts and the
         difference taken, so that building the code and the decoder does not count.
 """
@@ -21,10 +24,11 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 N, K, QBER, BATCH, N_ITE = 65536, 52429, 0.02, 4096, 50
+AWGN_SIGMA = 0.4869                                                    # Phi(-1 / sigma) = 0.02
 STAGES = ("source_ms", "encode_ms", "channel_ms", "load_ms", "decode_ms", "monitor_ms")
 
 
-def leg_split(q, steps):
+def leg_split(q, steps, awgn=False):
     code = q.Code.ira(N, K)
     enc = q.Encoder(code, "IRA")
     dec = q.Decoder(code, enc.K, N_ITE, info_bits_pos=enc.info_bits_pos, rule="NMS", rule_param=0.75, n_frames=BATCH)
@@ -34,7 +38,19 @@ def leg_split(q, steps):
     assert r["frames"] == steps * BATCH and r["batches"] == steps
     per_batch = {k: r[k] / steps for k in STAGES}
     around = per_batch["source_ms"] + per_batch["channel_ms"] + per_batch["monitor_ms"]
-    return dict(workload="N %d K %d flooding NMS 0.75, <= %d iterations, early exit, QBER %.3f, %d batches of %d frames" % (N, K, N_ITE, QBER, steps, BATCH),
+    soft = {}
+    if awgn:
+        mc.set_awgn(sigma=AWGN_SIGMA)
+        mc.run(QBER, 0, BATCH)                                         # warm-up of the soft path: its first launches
+        s = mc.run(QBER, BATCH, steps * BATCH)
+        assert s["frames"] == steps * BATCH and s["batches"] == steps
+        soft = dict(awgn=dict(sigma=AWGN_SIGMA, levels=64, per_batch_ms={k: s[k] / steps for k in STAGES},
+                              channel_ms_soft_vs_bsc=(s["channel_ms"] / steps, per_batch["channel_ms"]),
+                              load_ms_soft_vs_bsc=(s["load_ms"] / steps, per_batch["load_ms"]),
+                              hard_error_rate=s["channel_flips"] / s["channel_bits"], device_bytes=mc.device_bytes))
+        print("per batch of %d frames: channel_ms soft %.4f / BSC %.4f, load_ms soft %.4f / BSC %.4f" % (
+            BATCH, s["channel_ms"] / steps, per_batch["channel_ms"], s["load_ms"] / steps, per_batch["load_ms"]))
+    return dict(soft, workload="N %d K %d flooding NMS 0.75, <= %d iterations, early exit, QBER %.3f, %d batches of %d frames" % (N, K, N_ITE, QBER, steps, BATCH),
                 per_batch_ms=per_batch, source_channel_monitor_over_decode=around / per_batch["decode_ms"],
                 frames_per_s=r["frames"] / (r["total_ms"] * 1e-3), decode_only_frames_per_s=r["frames"] / (r["decode_ms"] * 1e-3),
                 frame_errors=r["frame_errors"], avg_iterations=r["iter_sum"] / r["frames"], empirical_qber=r["channel_flips"] / r["channel_bits"],
@@ -66,12 +82,13 @@ def main():
     ap.add_argument("--leg", choices=("split", "sim"), required=True)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mc_cost.json"))
     ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--awgn", action="store_true", help="leg split: also time the soft path (6-bit AWGN table) beside the BSC's")
     args = ap.parse_args()
     if args.leg == "sim":
         leg = leg_sim()
     else:
         import _qldpc_loader
-        leg = leg_split(_qldpc_loader.load(), args.steps)
+        leg = leg_split(_qldpc_loader.load(), args.steps, args.awgn)
     out = {}
     if os.path.exists(args.out):
         out = json.load(open(args.out))
