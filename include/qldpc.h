@@ -36,7 +36,8 @@
  *   qldpc_toeplitz*                       (not in the reference) Toeplitz hashing, the sound replacement of that loop
  *   qldpc_mc_*                            the simulation loop itself: source, encoder, BSC, decoder, Monitor_BFER   BS/src/main.cpp:335-393
  *   qldpc_mc_search / _patterns_dev       the puncture-pattern search around it: shuffle, erase, first FER = 0 / n  BS/src/main.cpp:235-411
- *   qldpc_mc_set_channel / _awgn_table    the channel of the fixed-point sims: BPSK over AWGN, 6-bit received values  ML/BPSK_nrldpc_sim_RM_FP.m
+ *   qldpc_mc_sweep                        the BER loop around both, with its puncture count per BER                BS/src/main.cpp:233-272
+ *   qldpc_mc_set_channel / _awgn_table   the channel of the fixed-point sims: BPSK over AWGN, 6-bit received values  ML/BPSK_nrldpc_sim_RM_FP.m
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -738,6 +739,81 @@ int    qldpc_mc_search(qldpc_mc *mc, double qber, const qldpc_mc_search_cfg *cfg
                        qldpc_mc_search_result *res);
 /* of the last search: one row per evaluated pattern, in pattern order; writes min(cap, count) and returns the count (or a status) */
 int    qldpc_mc_search_stats(qldpc_mc *mc, qldpc_mc_pattern_stat *rows, int cap);
+
+/*
+ * The QBER sweep (the harness's outermost loop, `for (float ber = ber_min; ber <= ber_max; ber += ber_step)`, BS/src/main.cpp:233, with
+ * parity_bits_to_punct(K, N, min_cr(ber, target_efficiency)) punctured parity bits per BER, :235,272): operating points side by side in one
+ * batch, each with its own monitor row and stop rule, and lanes that pass from closed points to open ones.
+ *
+ *   point      a sweep has P operating points, 1 <= P <= QLDPC_MC_SWEEP_MAX_POINTS; point q = (qber_q in (0, 0.5), n_punct_q >= 0)
+ *   puncture   the sets are nested: the caller gives ONE order punct_order[n_order], a HOST array of distinct VNs inside [0, N) that need
+ *              not be ascending (the order is the point of it); point q erases the first n_punct_q VNs of it on top of the fixed set of
+ *              qldpc_mc_set_puncture.  n_order = 0: no puncturing, every n_punct_q must be 0
+ *   frames     frame k of EVERY point is Monte-Carlo frame first_frame + k: the same info word and the same Philox words, so the flip
+ *              sets of two points are nested as their thresholds are.  The row of a point is exactly what the point would get alone: its
+ *              counters equal those of qldpc_mc_run(qber_q, first_frame, max_frames = frames_q, max_frame_errors = 0) after
+ *              qldpc_mc_set_puncture(fixed set + prefix_q), for any batch, any chunk and any set of neighbouring points
+ *   rounds     a chunk is C frames, 1 <= C <= batch (cfg.chunk = 0: min(64, batch)); a round has S = floor(batch / C) chunk slots.
+ *              Point q is OPEN iff done_q < max_frames and (max_frame_errors == 0 or fe_q < max_frame_errors);
+ *              need_q = ceil((max_frames - done_q) / C) for an open point
+ *   deal       cycles over the open points in ascending q and on each visit gives one chunk to a point with give_q < need_q; it stops when
+ *              the S slots are used or a whole cycle has given nothing.  The chunks of a point are consecutive in the batch, points in
+ *              ascending order, frame slots without holes; the j-th chunk of point q covers k in [done_q + j C, min(done_q + (j + 1) C,
+ *              max_frames)), so only the last chunk of a point can be ragged.  The deal is a pure function of (done[], fe[], C, S,
+ *              max_frames, max_frame_errors): nothing depends on timing (qldpc_mc_sweep_deal_host is that function)
+ *
+ * One round is one sequence generate / encode / channel / load / erase / qldpc_run / fetch / monitor that ends with ONE read-back of the P
+ * counter rows; the host updates done and fe from those rows and deals the next round.  The sweep ends when no point is open.  frames_q is
+ * therefore round-granular (as `frames` of qldpc_mc_run is batch-granular); the rows, given frames_q, are not.  A point that reaches
+ * max_frames is closed by QLDPC_MC_CLOSED_MAX_FRAMES, whatever its frame errors; otherwise by QLDPC_MC_CLOSED_MAX_FE.  Rounds count from 0.
+ *
+ * Status codes: QLDPC_ESIZE for P outside its range, a qber outside (0, 0.5), chunk outside [0, batch], max_frames == 0, an n_punct outside
+ * [0, n_order]; QLDPC_EINVAL for a missing array, an order with a repeated or out-of-range VN, non-zero reserved fields; QLDPC_ESTATE while a
+ * table of qldpc_mc_set_channel is in force.  A refused call queues nothing and leaves the last sweep's rows readable.  The kernels run at
+ * most batch ceil(N / 32) lanes, which qldpc_mc_create has checked against 2^31.  The first sweep allocates what sweeps need on the device
+ * (the slot tables, the point rows {threshold, |LLR|}, the erase rows of QLDPC_MC_SWEEP_MAX_POINTS points, the frame erase rows if the search
+ * has not made them, the counter and histogram rows and the pinned copies of slot tables and counter rows), counted by
+ * qldpc_mc_device_bytes; later sweeps allocate nothing.  A sweep touches neither the counters, histogram and failed-frame list of the last
+ * qldpc_mc_run nor the rows of the last search.  Its gain over one qldpc_mc_run per point is not measured yet (tools/mc_sweep_cost.py).
+ * Not built: points of a table channel (a table per point); failed-frame lists per point (a failed frame of a point is regenerated with
+ * qldpc_mc_run over its index); a puncture pattern drawn per point (qldpc_mc_search does that at one QBER); one encode shared by the points
+ * that sit on the same frame; a multi-GPU driver; the deal on the device.
+ */
+#define QLDPC_MC_SWEEP_MAX_POINTS 4096
+enum { QLDPC_MC_CLOSED_MAX_FE = 1, QLDPC_MC_CLOSED_MAX_FRAMES = 2 };
+typedef struct qldpc_mc_point { double qber; int n_punct; int reserved; /* must be zero */ } qldpc_mc_point;
+typedef struct qldpc_mc_sweep_cfg {
+    const qldpc_mc_point *points; int n_points;
+    const int *punct_order; int n_order;
+    int chunk;                 /* C; 0 = min(64, batch)                                                                                */
+    uint64_t first_frame, max_frames, max_frame_errors;   /* per point; max_frame_errors = 0: no stop rule                            */
+    int reserved[2];           /* must be zero                                                                                         */
+} qldpc_mc_sweep_cfg;
+typedef struct qldpc_mc_point_stat {
+    double qber; int n_punct;
+    int closed_by;             /* QLDPC_MC_CLOSED_*                                                                                    */
+    uint64_t frames, frame_errors, bit_errors, undetected, not_converged, iter_sum, iter_max, channel_flips, channel_bits;   /* as qldpc_mc_result */
+    uint64_t last_round;       /* the last round in which the point received frames                                                    */
+} qldpc_mc_point_stat;
+typedef struct qldpc_mc_sweep_result {
+    uint64_t rounds, frames, batches;   /* frames = the sum over the points; one decoder launch per round                              */
+    double decode_ms;          /* qldpc_run alone, by hipEvents                                                                        */
+    double source_ms, encode_ms, channel_ms, load_ms, erase_ms, monitor_ms;   /* the other stages of the rounds, by hipEvents: slot tables +
+                                  info words, encoder, BSC per point, qldpc_load_bits_dev, expansion + qldpc_load_erasures_dev, fetch +
+                                  per-point monitor                                                                                    */
+    double total_ms;           /* the whole call on the host's clock                                                                   */
+} qldpc_mc_sweep_result;
+int    qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc_mc_sweep_result *res);
+/* of the last sweep: one row per point, in point order; writes min(cap, P) and returns P (or a status) */
+int    qldpc_mc_sweep_stats(qldpc_mc *mc, qldpc_mc_point_stat *rows, int cap);
+/* of the last sweep: frames per iteration count of one point, n_ite + 1 bins; writes min(cap, n_ite + 1) and returns n_ite + 1 (or a
+   status: QLDPC_ESIZE for a point the last sweep did not have) */
+int    qldpc_mc_sweep_hist(qldpc_mc *mc, int point, uint64_t *hist, int cap);
+/* host mirror, no device needed: the deal of one round over n_points points with `slots` chunk slots of `chunk` frames; give[n_points] = the
+   chunks of each point; returns the chunks dealt (or a status: QLDPC_ESIZE for n_points outside 1 .. QLDPC_MC_SWEEP_MAX_POINTS, chunk < 1,
+   slots < 1 or max_frames == 0, QLDPC_EINVAL for a missing array) */
+int    qldpc_mc_sweep_deal_host(int n_points, int chunk, int slots, uint64_t max_frames, uint64_t max_frame_errors, const uint64_t *done,
+                                const uint64_t *frame_errors, int *give);
 
 #ifdef __cplusplus
 }

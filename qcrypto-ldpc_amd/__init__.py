@@ -920,6 +920,31 @@ _sig("qldpc_mc_search", C.c_int, [_vp, C.c_double, C.POINTER(McSearchCfg), C.c_u
 _sig("qldpc_mc_search_stats", C.c_int, [_vp, _vp, C.c_int])
 
 
+class McPoint(C.Structure):
+    _fields_ = [("qber", C.c_double), ("n_punct", C.c_int), ("reserved", C.c_int)]
+
+
+class McSweepCfg(C.Structure):
+    _fields_ = [("points", C.POINTER(McPoint)), ("n_points", C.c_int), ("punct_order", _ip), ("n_order", C.c_int), ("chunk", C.c_int),
+                ("first_frame", C.c_uint64), ("max_frames", C.c_uint64), ("max_frame_errors", C.c_uint64), ("reserved", C.c_int * 2)]
+
+
+class McSweepResult(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("rounds", "frames", "batches")] + [
+        (n, C.c_double) for n in ("decode_ms", "source_ms", "encode_ms", "channel_ms", "load_ms", "erase_ms", "monitor_ms", "total_ms")]
+
+
+MC_POINT_STAT = np.dtype([("qber", np.float64), ("n_punct", np.int32), ("closed_by", np.int32)] + [(n, np.uint64) for n in (
+    "frames", "frame_errors", "bit_errors", "undetected", "not_converged", "iter_sum", "iter_max", "channel_flips", "channel_bits", "last_round")])
+MC_SWEEP_MAX_POINTS = 4096
+MC_CLOSED_MAX_FE, MC_CLOSED_MAX_FRAMES = 1, 2          # closed_by of a point row
+
+_sig("qldpc_mc_sweep", C.c_int, [_vp, C.POINTER(McSweepCfg), C.POINTER(McSweepResult)])
+_sig("qldpc_mc_sweep_stats", C.c_int, [_vp, _vp, C.c_int])
+_sig("qldpc_mc_sweep_hist", C.c_int, [_vp, C.c_int, _u64p, C.c_int])
+_sig("qldpc_mc_sweep_deal_host", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _u64p, _u64p, _ip])
+
+
 class McChannel(C.Structure):
     _fields_ = [("levels", C.c_int), ("cum", _u64p * 2), ("value", C.POINTER(C.c_float)), ("reserved", C.c_int * 2)]
 
@@ -979,6 +1004,20 @@ def mc_pattern_host(seed, pattern, n_cand, n_punct, key_bits=32):
     _chk(_L.qldpc_mc_pattern_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(pattern) & 0xFFFFFFFFFFFFFFFF, int(n_cand), int(n_punct), int(key_bits),
                                   idx.ctypes.data_as(_ip)), "mc_pattern_host")
     return idx
+
+
+def mc_sweep_deal(done, frame_errors, chunk, slots, max_frames, max_frame_errors=0):
+    """the deal of one round of MonteCarlo.sweep (qldpc_mc_sweep_deal_host, no device needed): done[P] and frame_errors[P] of the points ->
+    give[P] (int32), the chunks of `chunk` frames each point receives out of `slots`"""
+    d = np.ascontiguousarray(done, dtype=np.uint64).ravel()
+    fe = np.ascontiguousarray(frame_errors, dtype=np.uint64).ravel()
+    if d.size != fe.size:
+        raise QldpcError(-6, "mc_sweep_deal: %d done counts, %d frame-error counts" % (d.size, fe.size))
+    give = np.zeros(d.size, np.int32)
+    used = _chk(_L.qldpc_mc_sweep_deal_host(d.size, int(chunk), int(slots), int(max_frames), int(max_frame_errors), d.ctypes.data_as(_u64p),
+                                            fe.ctypes.data_as(_u64p), give.ctypes.data_as(_ip)), "mc_sweep_deal")
+    assert used == int(give.sum())
+    return give
 
 
 def _mc_channel_arg(cum0, cum1, value, where):
@@ -1180,6 +1219,52 @@ class MonteCarlo:
         n = _chk(_L.qldpc_mc_search_stats(self._h, _vp(stats.ctypes.data), stats.size), "MonteCarlo.search")
         assert n == stats.size
         out["stats"] = stats
+        return out
+
+    def sweep(self, qbers, n_punct=None, punct_order=None, first_frame=0, max_frames=None, max_frame_errors=0, chunk=0):
+        """P operating points side by side in one batch (qldpc_mc_sweep): point q = (qbers[q], n_punct[q]) erases the first n_punct[q] VNs
+        of punct_order on top of set_puncture's set; frame k of every point is frame first_frame + k; a point closes at max_frames (None = one
+        batch) or at max_frame_errors (0 = never), and its lanes pass to the open points, `chunk` frames at a time (0 = min(64, batch)).
+        -> dict of the result (rounds, frames, batches, the stage times) plus `points`, one MC_POINT_STAT row per point: exactly the
+        counters of run(qbers[q], first_frame, frames_q) with that point's puncture set."""
+        qb = np.ascontiguousarray(qbers, dtype=np.float64).ravel()
+        npn = np.zeros(qb.size, np.int32) if n_punct is None else _np_i32(n_punct).ravel()
+        if npn.size != qb.size:
+            raise QldpcError(-6, "MonteCarlo.sweep: %d qbers, %d n_punct" % (qb.size, npn.size))
+        pts = (McPoint * max(qb.size, 1))()
+        for i in range(qb.size):
+            pts[i].qber, pts[i].n_punct = float(qb[i]), int(npn[i])
+        order = _np_i32(punct_order).ravel() if punct_order is not None else np.zeros(0, np.int32)
+        cfg = McSweepCfg()
+        cfg.points, cfg.n_points = pts, qb.size
+        cfg.punct_order, cfg.n_order = (order.ctypes.data_as(_ip) if order.size else None), order.size
+        cfg.chunk, cfg.first_frame = int(chunk), int(first_frame) & 0xFFFFFFFFFFFFFFFF
+        cfg.max_frames, cfg.max_frame_errors = (self.batch if max_frames is None else int(max_frames)), int(max_frame_errors)
+        res = McSweepResult()
+        _chk(_L.qldpc_mc_sweep(self._h, C.byref(cfg), C.byref(res)), "MonteCarlo.sweep")
+        out = {name: getattr(res, name) for name, _ in McSweepResult._fields_}
+        out["points"] = self.sweep_stats()
+        assert out["points"].size == qb.size
+        return out
+
+    def sweep_stats(self):
+        """the point rows of the last sweep (MC_POINT_STAT), in point order"""
+        n = _chk(_L.qldpc_mc_sweep_stats(self._h, None, 0), "MonteCarlo.sweep_stats")
+        rows = np.zeros(n, MC_POINT_STAT)
+        if n:
+            _chk(_L.qldpc_mc_sweep_stats(self._h, _vp(rows.ctypes.data), n), "MonteCarlo.sweep_stats")
+        return rows
+
+    def sweep_hist(self):
+        """frames per iteration count of every point of the last sweep -> uint64 [P, n_ite + 1]"""
+        P = _chk(_L.qldpc_mc_sweep_stats(self._h, None, 0), "MonteCarlo.sweep_hist")
+        if P == 0:
+            return np.zeros((0, 0), np.uint64)
+        one = np.zeros(1, np.uint64)
+        bins = _chk(_L.qldpc_mc_sweep_hist(self._h, 0, one.ctypes.data_as(_u64p), 1), "MonteCarlo.sweep_hist")      # the call returns n_ite + 1
+        out = np.zeros((P, bins), np.uint64)
+        for q in range(P):
+            _chk(_L.qldpc_mc_sweep_hist(self._h, q, out[q].ctypes.data_as(_u64p), bins), "MonteCarlo.sweep_hist")
         return out
 
     def __del__(self):

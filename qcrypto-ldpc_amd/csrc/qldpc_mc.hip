@@ -24,6 +24,15 @@
  * mc_monitor_patterns: the arithmetic of mc_monitor, the waves dealt out per pattern (every frame of a wave belongs to one pattern), so ONE
  *     atomicAdd per wave and counter onto the counter row of that pattern.
  *
+ * mc_source_points / mc_channel_points: the lane layouts of mc_source / mc_channel for the QBER sweep (qldpc_mc_sweep): the frame index of a slot
+ *     comes from the slot table of the round instead of first + f, the channel threshold and the |LLR| of the slot from the row {threshold,
+ *     |LLR|} of the slot's point (P rows of 8 bytes: L2-resident); mc_info_word and mc_flip_word unchanged, so a frame is the frame of
+ *     qldpc_mc_frames_host.
+ * mc_expand_points: mc_expand_rows with the erase row of a slot looked up through the slot's point.
+ * mc_monitor_points: the arithmetic of mc_monitor, flips included, the waves dealt out per chunk (every frame of a wave belongs to one point):
+ *     ONE atomicAdd per wave and counter onto the counter row of that point and one atomicMax for iter_max, per frame one add on the point's
+ *     histogram row; no failed-frame list.
+ *
  * No kernel waits on another wave.  The decoder and the encoder are driven through their public calls only; qldpc_engine_int.h is read for
  * the decoder's sizes, device and stream.
  */
@@ -249,6 +258,92 @@ __global__ __launch_bounds__(MC_LANES) void mc_monitor_patterns(const uint32_t *
     if (s_nc) atomicAdd(r + MCP_NOT_CONVERGED, s_nc);
 }
 
+/* ---- QBER sweep: operating points side by side in one batch ---- */
+struct mc_point_row { uint32_t t_channel; float mag; };      /* of a point: floor(qber 2^32), qldpc_bsc_llr(qber) */
+#define MCW_COUNTERS MC_FAIL_SLOTS                            /* a point's counter row: MC_FRAMES .. MC_CHANNEL_BITS */
+
+__global__ __launch_bounds__(MC_LANES) void mc_source_points(uint32_t *__restrict__ info, unsigned total, unsigned Wk, int K, uint64_t seed,
+                                                             const uint64_t *__restrict__ slot_frame)
+{
+    const unsigned i = blockIdx.x * MC_LANES + threadIdx.x;
+    if (i >= total) return;
+    const unsigned f = i / Wk, j = i - f * Wk;
+    info[i] = mc_info_word(seed, slot_frame[f], j, K);
+}
+
+__global__ __launch_bounds__(MC_LANES) void mc_channel_points(const uint32_t *__restrict__ cw, uint32_t *__restrict__ rx, const uint4 *__restrict__ cls,
+                                                              unsigned total, unsigned Wn, uint64_t seed, const uint64_t *__restrict__ slot_frame,
+                                                              const uint32_t *__restrict__ slot_point, const mc_point_row *__restrict__ points,
+                                                              uint32_t t_pinned, float *__restrict__ llr_mag)
+{
+    const unsigned i = blockIdx.x * MC_LANES + threadIdx.x;
+    if (i >= total) return;
+    const unsigned f = i / Wn, w = i - f * Wn;
+    const mc_point_row pt = points[slot_point[f]];
+    const uint4 a = cls[2u * w], b = cls[2u * w + 1u];
+    const uint32_t cls4[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    rx[i] = cw[i] ^ mc_flip_word(seed, slot_frame[f], w, cls4, pt.t_channel, t_pinned);
+    if (w == 0) llr_mag[f] = pt.mag;
+}
+
+/* frames[slot][Wn] = rows[slot_point[slot]][Wn] for the `total` words of the slots, four words per lane */
+__global__ __launch_bounds__(MC_LANES) void mc_expand_points(const uint32_t *__restrict__ rows, uint32_t *__restrict__ frames, unsigned total, unsigned Wn,
+                                                             const uint32_t *__restrict__ slot_point)
+{
+    const unsigned i = (blockIdx.x * MC_LANES + threadIdx.x) * 4u;
+    if (i >= total) return;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    for (unsigned j = 0; j < 4; j++)
+        if (i + j < total) { const unsigned slot = (i + j) / Wn, word = (i + j) - slot * Wn; w[j] = rows[(size_t)slot_point[slot] * Wn + word]; }
+    if (i + 4u <= total) *(uint4 *)(frames + i) = make_uint4(w[0], w[1], w[2], w[3]);
+    else for (unsigned j = 0; i + j < total; j++) frames[i + j] = w[j];
+}
+
+/* wpc waves per chunk: wave (chunk, sub) takes frames sub, sub + wpc, ... of the chunk_len frames that start at slot chunk_start; a chunk
+ * belongs to one point, whose counter row [MCW_COUNTERS] and histogram row [n_ite + 1] the wave adds to */
+__global__ __launch_bounds__(MC_LANES) void mc_monitor_points(const uint32_t *__restrict__ out, const uint32_t *__restrict__ cw, const uint32_t *__restrict__ rx,
+                                                              const uint32_t *__restrict__ info_mask, const uint32_t *__restrict__ chan_mask,
+                                                              const int *__restrict__ iters, const int *__restrict__ ok, unsigned n_chunks, unsigned wpc,
+                                                              const uint32_t *__restrict__ chunk_point, const uint32_t *__restrict__ chunk_start,
+                                                              const uint32_t *__restrict__ chunk_len, unsigned Wn, int n_ite, unsigned channel_vns,
+                                                              mc_u64 *__restrict__ rows, mc_u64 *__restrict__ hists)
+{
+    const unsigned lane = threadIdx.x & 63u, wid = blockIdx.x * (MC_LANES / 64) + (threadIdx.x >> 6);
+    if (wid >= n_chunks * wpc) return;
+    const unsigned c = wid / wpc, sub = wid - c * wpc, point = chunk_point[c], start = chunk_start[c], len = chunk_len[c];
+    mc_u64 *hist = hists + (size_t)point * (size_t)(n_ite + 1);
+    mc_u64 s_frames = 0, s_be = 0, s_fe = 0, s_ud = 0, s_nc = 0, s_it = 0, s_mx = 0, s_fl = 0;
+    for (unsigned k = sub; k < len; k += wpc) {
+        const unsigned f = start + k;
+        const size_t row = (size_t)f * Wn;
+        unsigned be = 0, fl = 0;
+        for (unsigned w = lane; w < Wn; w += 64u) {
+            const uint32_t x = cw[row + w];
+            be += (unsigned)__popc((out[row + w] ^ x) & info_mask[w]);
+            fl += (unsigned)__popc((rx[row + w] ^ x) & chan_mask[w]);
+        }
+        be = mc_wave_sum(be);
+        fl = mc_wave_sum(fl);
+        const int it = min(max(iters[f], 0), n_ite);
+        const bool good = ok[f] != 0;
+        s_frames++; s_be += be; s_fl += fl; s_it += (mc_u64)it;
+        s_mx = max(s_mx, (mc_u64)it);
+        s_fe += be > 0; s_ud += good && be > 0; s_nc += !good;
+        if (lane == 0) atomicAdd(hist + it, 1ull);
+    }
+    if (lane != 0 || s_frames == 0) return;
+    mc_u64 *r = rows + (size_t)point * MCW_COUNTERS;
+    atomicAdd(r + MC_FRAMES, s_frames);
+    atomicAdd(r + MC_ITER_SUM, s_it);
+    atomicMax(r + MC_ITER_MAX, s_mx);
+    atomicAdd(r + MC_CHANNEL_BITS, s_frames * channel_vns);
+    if (s_fl) atomicAdd(r + MC_FLIPS, s_fl);
+    if (s_be) atomicAdd(r + MC_BIT_ERRORS, s_be);
+    if (s_fe) atomicAdd(r + MC_FRAME_ERRORS, s_fe);
+    if (s_ud) atomicAdd(r + MC_UNDETECTED, s_ud);
+    if (s_nc) atomicAdd(r + MC_NOT_CONVERGED, s_nc);
+}
+
 /* ------------------------------------------------------------------ host ---- */
 
 struct qldpc_mc {
@@ -278,6 +373,16 @@ struct qldpc_mc {
     int source;                        /* QLDPC_MC_SOURCE_* */
     mc_soft_table *d_tab;
     float *d_llr;                      /* [batch][N], what qldpc_load_llr_dev takes */
+    /* the QBER sweep; the device side is allocated by the first qldpc_mc_sweep (mc_sweep_reserve) */
+    bool sweep_ready;
+    std::vector<uint32_t> h_fixed;     /* [Wn] the fixed set of qldpc_mc_set_puncture (empty = none): a point's erase row = this OR its prefix */
+    mc_u64 *d_slots, *h_slots;         /* the tables of a round and their pinned copy: [batch] 64-bit frame indices, then [batch] 32-bit words each
+                                          of slot -> point, chunk -> point, chunk -> first slot, chunk -> frames */
+    mc_point_row *d_points;            /* [QLDPC_MC_SWEEP_MAX_POINTS] */
+    uint32_t *d_prows;                 /* [QLDPC_MC_SWEEP_MAX_POINTS][Wn] the erase rows of the points */
+    mc_u64 *d_wctr, *h_wctr, *d_whist; /* [QLDPC_MC_SWEEP_MAX_POINTS][MCW_COUNTERS] counter rows, pinned copy; [..][n_ite + 1] histogram rows */
+    hipEvent_t wev[8];                 /* of a sweep round: source | encode | channel | load | erase | run | fetch + monitor */
+    std::vector<qldpc_mc_point_stat> wstats;    /* of the last sweep */
 };
 
 extern "C" void qldpc_mc_cfg_default(qldpc_mc_cfg *cfg)
@@ -292,12 +397,16 @@ extern "C" void qldpc_mc_free(qldpc_mc *mc)
     if (!mc) return;
     (void)hipSetDevice(mc->device);
     void *dev[] = {mc->d_cls, mc->d_info_mask, mc->d_chan_mask, mc->d_info, mc->d_cw, mc->d_rx, mc->d_out, mc->d_mag, mc->d_iters, mc->d_ok, mc->d_ctr,
-                   mc->d_cand, mc->d_pat, mc->d_erase, mc->d_fixed, mc->d_rows, mc->d_tab, mc->d_llr};
+                   mc->d_cand, mc->d_pat, mc->d_erase, mc->d_fixed, mc->d_rows, mc->d_tab, mc->d_llr,
+                   mc->d_slots, mc->d_points, mc->d_prows, mc->d_wctr, mc->d_whist};
     for (void *p : dev) if (p) (void)hipFree(p);
     if (mc->h_ctr) (void)hipHostFree(mc->h_ctr);
     if (mc->h_rows) (void)hipHostFree(mc->h_rows);
+    if (mc->h_slots) (void)hipHostFree(mc->h_slots);
+    if (mc->h_wctr) (void)hipHostFree(mc->h_wctr);
     for (hipEvent_t e : mc->ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : mc->sev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : mc->wev) if (e) (void)hipEventDestroy(e);
     delete mc;
 }
 
@@ -644,13 +753,14 @@ extern "C" int qldpc_mc_set_puncture(qldpc_mc *mc, const int *vn, int n)
     if (!mc) return QLDPC_EINVAL;
     int rc = mc_vn_list_args(mc, "mc_set_puncture", vn, n);
     if (rc) return rc;
-    if (n == 0) { mc->n_fixed = 0; return QLDPC_OK; }
+    if (n == 0) { mc->n_fixed = 0; mc->h_fixed.clear(); return QLDPC_OK; }
     if ((rc = mc_search_reserve(mc))) return rc;
     std::vector<uint32_t> row((size_t)mc->Wn);
     mc_vn_list_row(vn, n, mc->N, row.data());
     HIPCHK(hipStreamSynchronize(mc->dec->stream));
     HIPCHK(hipMemcpy(mc->d_fixed, row.data(), sizeof(uint32_t) * row.size(), hipMemcpyHostToDevice));
     mc->n_fixed = n;
+    mc->h_fixed.swap(row);      /* the sweep builds its points' erase rows on the host */
     return QLDPC_OK;
 }
 
@@ -728,4 +838,177 @@ extern "C" int qldpc_mc_search_stats(qldpc_mc *mc, qldpc_mc_pattern_stat *rows, 
     const size_t n = std::min((size_t)cap, mc->stats.size());
     if (n) memcpy(rows, mc->stats.data(), sizeof(qldpc_mc_pattern_stat) * n);
     return (int)mc->stats.size();
+}
+
+/* ------------------------------------------------------------------ QBER sweep ---- */
+
+/* everything the sweep needs on the device, once */
+static int mc_sweep_reserve(qldpc_mc *mc)
+{
+    HIPCHK(hipSetDevice(mc->device));
+    if (mc->sweep_ready) return QLDPC_OK;
+    const size_t Wn = (size_t)mc->Wn, B = (size_t)mc->batch, P = QLDPC_MC_SWEEP_MAX_POINTS, bins = (size_t)mc->n_ite + 1;
+    int rc = QLDPC_OK;
+    if ((!mc->d_slots && (rc = mc_alloc(mc, &mc->d_slots, 3 * B))) || (!mc->d_points && (rc = mc_alloc(mc, &mc->d_points, P))) ||
+        (!mc->d_prows && (rc = mc_alloc(mc, &mc->d_prows, P * Wn))) || (!mc->d_erase && (rc = mc_alloc(mc, &mc->d_erase, B * Wn))) ||
+        (!mc->d_wctr && (rc = mc_alloc(mc, &mc->d_wctr, P * MCW_COUNTERS))) || (!mc->d_whist && (rc = mc_alloc(mc, &mc->d_whist, P * bins))))
+        return rc;
+    if (!mc->h_slots && hipHostMalloc((void **)&mc->h_slots, sizeof(mc_u64) * 3 * B, hipHostMallocDefault) != hipSuccess) { mc->h_slots = nullptr; return QLDPC_ENOMEM; }
+    if (!mc->h_wctr && hipHostMalloc((void **)&mc->h_wctr, sizeof(mc_u64) * P * MCW_COUNTERS, hipHostMallocDefault) != hipSuccess) { mc->h_wctr = nullptr; return QLDPC_ENOMEM; }
+    for (hipEvent_t &e : mc->wev) if (!e) HIPCHK(hipEventCreate(&e));
+    if ((rc = qldpc_decoder_reserve(mc->dec))) return rc;      /* the decoder's erasure ballots */
+    mc->sweep_ready = true;
+    return QLDPC_OK;
+}
+
+/* every argument check of qldpc_mc_sweep: nothing is touched before all of them pass */
+static int mc_sweep_args(const qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg)
+{
+    if (cfg->reserved[0] || cfg->reserved[1]) { qldpc_set_error("mc_sweep: reserved fields %d, %d must be zero", cfg->reserved[0], cfg->reserved[1]); return QLDPC_EINVAL; }
+    if (mc->soft) { qldpc_set_error("mc_sweep: a channel table is in force (qldpc_mc_set_channel); the sweep's points are points of the BSC"); return QLDPC_ESTATE; }
+    if (cfg->n_points < 1 || cfg->n_points > QLDPC_MC_SWEEP_MAX_POINTS) { qldpc_set_error("mc_sweep: n_points=%d outside 1 .. %d", cfg->n_points, QLDPC_MC_SWEEP_MAX_POINTS); return QLDPC_ESIZE; }
+    if (cfg->chunk < 0 || cfg->chunk > mc->batch) { qldpc_set_error("mc_sweep: chunk=%d outside [0, batch=%d]", cfg->chunk, mc->batch); return QLDPC_ESIZE; }
+    if (cfg->max_frames == 0) { qldpc_set_error("mc_sweep: max_frames=0"); return QLDPC_ESIZE; }
+    if (!cfg->points || cfg->n_order < 0 || (cfg->n_order > 0 && !cfg->punct_order)) { qldpc_set_error("mc_sweep: a missing array (points, or punct_order with n_order=%d)", cfg->n_order); return QLDPC_EINVAL; }
+    std::vector<bool> seen((size_t)mc->N, false);
+    for (int i = 0; i < cfg->n_order; i++) {
+        const int v = cfg->punct_order[i];
+        if (v < 0 || v >= mc->N || seen[(size_t)v]) { qldpc_set_error("mc_sweep: punct_order[%d] = %d is repeated or outside [0, %d)", i, v, mc->N); return QLDPC_EINVAL; }
+        seen[(size_t)v] = true;
+    }
+    for (int q = 0; q < cfg->n_points; q++) {
+        const qldpc_mc_point &pt = cfg->points[q];
+        if (pt.reserved) { qldpc_set_error("mc_sweep: reserved field %d of point %d must be zero", pt.reserved, q); return QLDPC_EINVAL; }
+        if (!(pt.qber > 0.0 && pt.qber < 0.5)) { qldpc_set_error("mc_sweep: qber=%g of point %d outside (0, 0.5)", pt.qber, q); return QLDPC_ESIZE; }
+        if (pt.n_punct < 0 || pt.n_punct > cfg->n_order) { qldpc_set_error("mc_sweep: n_punct=%d of point %d outside [0, n_order=%d]", pt.n_punct, q, cfg->n_order); return QLDPC_ESIZE; }
+    }
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc_mc_sweep_result *res)
+{
+    if (!mc || !cfg || !res) return QLDPC_EINVAL;
+    memset(res, 0, sizeof(*res));
+    int rc = mc_sweep_args(mc, cfg);
+    if (rc || (rc = mc_sweep_reserve(mc))) return rc;
+    const hipStream_t s = mc->dec->stream;
+    const int P = cfg->n_points, C = cfg->chunk ? cfg->chunk : std::min(64, mc->batch), S = mc->batch / C;
+    const unsigned Wn = (unsigned)mc->Wn, Wk = (unsigned)mc->Wk;
+    const size_t B = (size_t)mc->batch, bins = (size_t)mc->n_ite + 1;
+    const uint64_t max_frames = cfg->max_frames, max_fe = cfg->max_frame_errors;
+    /* the tables of a round inside the one buffer */
+    uint64_t *const h_frame = (uint64_t *)mc->h_slots;
+    uint32_t *const h_point = (uint32_t *)(mc->h_slots + B), *const h_cpoint = h_point + B, *const h_cstart = h_cpoint + B, *const h_clen = h_cstart + B;
+    const uint64_t *const d_frame = (const uint64_t *)mc->d_slots;
+    const uint32_t *const d_point = (const uint32_t *)(mc->d_slots + B), *const d_cpoint = d_point + B, *const d_cstart = d_cpoint + B, *const d_clen = d_cstart + B;
+
+    /* per sweep: the point rows and the erase rows (fixed set OR prefix), built here once */
+    std::vector<mc_point_row> prow((size_t)P);
+    std::vector<uint32_t> erows((size_t)P * Wn, 0u);
+    bool any_erase = false;
+    for (int q = 0; q < P; q++) {
+        prow[(size_t)q].t_channel = mc_threshold(cfg->points[q].qber);
+        prow[(size_t)q].mag = qldpc_bsc_llr((float)cfg->points[q].qber);
+        uint32_t *row = erows.data() + (size_t)q * Wn;
+        if (mc->n_fixed) memcpy(row, mc->h_fixed.data(), sizeof(uint32_t) * Wn);
+        for (int i = 0; i < cfg->points[q].n_punct; i++) { const int v = cfg->punct_order[i]; row[v >> 5] |= 0x80000000u >> (v & 31); }
+        any_erase = any_erase || mc->n_fixed || cfg->points[q].n_punct > 0;
+    }
+    HIPCHK(hipStreamSynchronize(s));      /* a queued kernel may still read the rows of an earlier sweep */
+    HIPCHK(hipMemcpy(mc->d_points, prow.data(), sizeof(mc_point_row) * (size_t)P, hipMemcpyHostToDevice));
+    if (any_erase) HIPCHK(hipMemcpy(mc->d_prows, erows.data(), sizeof(uint32_t) * erows.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(mc->d_wctr, 0, sizeof(mc_u64) * (size_t)P * MCW_COUNTERS, s));
+    HIPCHK(hipMemsetAsync(mc->d_whist, 0, sizeof(mc_u64) * (size_t)P * bins, s));
+    mc->wstats.assign((size_t)P, qldpc_mc_point_stat());
+    for (int q = 0; q < P; q++) { mc->wstats[(size_t)q].qber = cfg->points[q].qber; mc->wstats[(size_t)q].n_punct = cfg->points[q].n_punct; }
+
+    std::vector<uint64_t> done((size_t)P, 0), fe((size_t)P, 0);
+    std::vector<int> give((size_t)P);
+    const auto t_start = std::chrono::steady_clock::now();
+    for (uint64_t round = 0;; round++) {
+        const int n_chunks = mc_sweep_deal(P, C, S, max_frames, max_fe, done.data(), fe.data(), give.data());
+        if (n_chunks == 0) break;      /* no point is open */
+        unsigned nb = 0, nc = 0;
+        for (int q = 0; q < P; q++)
+            for (int j = 0; j < give[(size_t)q]; j++, nc++) {
+                const uint64_t k0 = done[(size_t)q] + (uint64_t)j * (uint64_t)C;
+                const unsigned len = (unsigned)std::min<uint64_t>((uint64_t)C, max_frames - k0);
+                h_cpoint[nc] = (uint32_t)q; h_cstart[nc] = nb; h_clen[nc] = len;
+                for (unsigned i = 0; i < len; i++, nb++) { h_frame[nb] = cfg->first_frame + k0 + i; h_point[nb] = (uint32_t)q; }
+                mc->wstats[(size_t)q].last_round = round;
+            }
+        const unsigned ti = nb * Wk, tn = nb * Wn;
+        HIPCHK(hipEventRecord(mc->wev[0], s));
+        HIPCHK(hipMemcpyAsync(mc->d_slots, mc->h_slots, sizeof(mc_u64) * 3 * B, hipMemcpyHostToDevice, s));      /* pinned: the host rewrites it after the sync below */
+        if (mc->source == QLDPC_MC_SOURCE_ZERO) HIPCHK(hipMemsetAsync(mc->d_info, 0, sizeof(uint32_t) * ti, s));
+        else {
+            hipLaunchKernelGGL(mc_source_points, dim3(mc_blocks(ti)), dim3(MC_LANES), 0, s, mc->d_info, ti, Wk, mc->K, mc->seed, d_frame);
+            LAUNCHCHK();
+        }
+        HIPCHK(hipEventRecord(mc->wev[1], s));
+        if ((rc = qldpc_encode_packed_dev(mc->enc, mc->d_info, mc->d_cw, (int)nb, (void *)s))) return rc;
+        HIPCHK(hipEventRecord(mc->wev[2], s));
+        hipLaunchKernelGGL(mc_channel_points, dim3(mc_blocks(tn)), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_cw, mc->d_rx, (const uint4 *)mc->d_cls, tn, Wn, mc->seed,
+                           d_frame, d_point, (const mc_point_row *)mc->d_points, mc_threshold(mc->parity_ber), mc->d_mag);
+        LAUNCHCHK();
+        HIPCHK(hipEventRecord(mc->wev[3], s));
+        if ((rc = qldpc_load_bits_dev(mc->dec, mc->d_rx, mc->d_mag, mc->d_cls, (int)nb))) return rc;
+        HIPCHK(hipEventRecord(mc->wev[4], s));
+        if (any_erase) {
+            hipLaunchKernelGGL(mc_expand_points, dim3(mc_blocks(((size_t)tn + 3) / 4)), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_prows, mc->d_erase, tn, Wn, d_point);
+            LAUNCHCHK();
+            if ((rc = qldpc_load_erasures_dev(mc->dec, mc->d_erase, (int)nb))) return rc;
+        }
+        HIPCHK(hipEventRecord(mc->wev[5], s));
+        if ((rc = qldpc_run(mc->dec))) return rc;
+        HIPCHK(hipEventRecord(mc->wev[6], s));
+        if ((rc = qldpc_fetch_packed_dev(mc->dec, mc->d_out))) return rc;
+        if ((rc = qldpc_fetch_status_dev(mc->dec, mc->d_iters, mc->d_ok))) return rc;
+        const unsigned wpc = std::min((unsigned)C, std::max(1u, (unsigned)MC_MAX_WAVES / nc)), waves = nc * wpc;
+        hipLaunchKernelGGL(mc_monitor_points, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_out, (const uint32_t *)mc->d_cw, (const uint32_t *)mc->d_rx,
+                           (const uint32_t *)mc->d_info_mask, (const uint32_t *)mc->d_chan_mask, (const int *)mc->d_iters, (const int *)mc->d_ok, nc, wpc, d_cpoint, d_cstart,
+                           d_clen, Wn, mc->n_ite, mc->channel_vns, mc->d_wctr, mc->d_whist);
+        LAUNCHCHK();
+        HIPCHK(hipEventRecord(mc->wev[7], s));
+        HIPCHK(hipMemcpyAsync(mc->h_wctr, mc->d_wctr, sizeof(mc_u64) * (size_t)P * MCW_COUNTERS, hipMemcpyDeviceToHost, s));      /* the one read-back of a round */
+        HIPCHK(hipStreamSynchronize(s));
+        double *const stage[7] = {&res->source_ms, &res->encode_ms, &res->channel_ms, &res->load_ms, &res->erase_ms, &res->decode_ms, &res->monitor_ms};
+        for (int k = 0; k < 7; k++) {
+            float ms = 0.0f;
+            HIPCHK(hipEventElapsedTime(&ms, mc->wev[k], mc->wev[k + 1]));
+            *stage[k] += (double)ms;
+        }
+        for (int q = 0; q < P; q++) { done[(size_t)q] = mc->h_wctr[(size_t)q * MCW_COUNTERS + MC_FRAMES]; fe[(size_t)q] = mc->h_wctr[(size_t)q * MCW_COUNTERS + MC_FRAME_ERRORS]; }
+        res->rounds++; res->batches++;
+    }
+    for (int q = 0; q < P; q++) {
+        const mc_u64 *c = mc->h_wctr + (size_t)q * MCW_COUNTERS;
+        qldpc_mc_point_stat &st = mc->wstats[(size_t)q];
+        st.frames = c[MC_FRAMES]; st.frame_errors = c[MC_FRAME_ERRORS]; st.bit_errors = c[MC_BIT_ERRORS]; st.undetected = c[MC_UNDETECTED];
+        st.not_converged = c[MC_NOT_CONVERGED]; st.iter_sum = c[MC_ITER_SUM]; st.iter_max = c[MC_ITER_MAX];
+        st.channel_flips = c[MC_FLIPS]; st.channel_bits = c[MC_CHANNEL_BITS];
+        st.closed_by = st.frames >= max_frames ? QLDPC_MC_CLOSED_MAX_FRAMES : QLDPC_MC_CLOSED_MAX_FE;
+        res->frames += st.frames;
+    }
+    res->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_sweep_stats(qldpc_mc *mc, qldpc_mc_point_stat *rows, int cap)
+{
+    if (!mc || cap < 0 || (cap && !rows)) return QLDPC_EINVAL;
+    const size_t n = std::min((size_t)cap, mc->wstats.size());
+    if (n) memcpy(rows, mc->wstats.data(), sizeof(qldpc_mc_point_stat) * n);
+    return (int)mc->wstats.size();
+}
+
+extern "C" int qldpc_mc_sweep_hist(qldpc_mc *mc, int point, uint64_t *hist, int cap)
+{
+    if (!mc || cap < 0 || (cap && !hist)) return QLDPC_EINVAL;
+    if (point < 0 || (size_t)point >= mc->wstats.size()) { qldpc_set_error("mc_sweep_hist: point=%d, the last sweep had %d", point, (int)mc->wstats.size()); return QLDPC_ESIZE; }
+    const int bins = std::min(cap, mc->n_ite + 1);
+    HIPCHK(hipSetDevice(mc->device));
+    HIPCHK(hipStreamSynchronize(mc->dec->stream));
+    if (bins) HIPCHK(hipMemcpy(hist, mc->d_whist + (size_t)point * (size_t)(mc->n_ite + 1), sizeof(mc_u64) * (size_t)bins, hipMemcpyDeviceToHost));
+    return mc->n_ite + 1;
 }

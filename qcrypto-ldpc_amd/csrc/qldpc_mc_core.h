@@ -220,6 +220,31 @@ static inline void mc_vn_list_row(const int *vn, int n, int N, uint32_t *row)
 }
 
 /*
+ * The QBER sweep (qldpc_mc_sweep): the deal of one round, a pure function of its arguments.  Point q is open iff done[q] < max_frames and
+ * (max_fe == 0 or fe[q] < max_fe) and then needs ceil((max_frames - done[q]) / C) chunks.  The deal cycles over the open points in ascending
+ * q and on each visit gives one chunk to a point that has fewer than it needs; it stops when the S slots are used or a whole cycle has given
+ * nothing.  Returns the chunks dealt; give[P] is written in full.  C >= 1.
+ */
+#define MC_SWEEP_MAX_POINTS 4096                   /* QLDPC_MC_SWEEP_MAX_POINTS of include/qldpc.h */
+
+static inline int mc_sweep_open(uint64_t done, uint64_t fe, uint64_t max_frames, uint64_t max_fe) { return done < max_frames && (max_fe == 0 || fe < max_fe); }
+
+static inline int mc_sweep_deal(int P, int C, int S, uint64_t max_frames, uint64_t max_fe, const uint64_t *done, const uint64_t *fe, int *give)
+{
+    int used = 0, gave = 1;
+    for (int q = 0; q < P; q++) give[q] = 0;
+    while (used < S && gave) {
+        gave = 0;
+        for (int q = 0; q < P && used < S; q++) {
+            if (!mc_sweep_open(done[q], fe[q], max_frames, max_fe)) continue;
+            const uint64_t left = max_frames - done[q], need = left / (uint64_t)C + (left % (uint64_t)C != 0);      /* no left + C - 1: it may wrap */
+            if ((uint64_t)give[q] < need) { give[q]++; used++; gave = 1; }
+        }
+    }
+    return used;
+}
+
+/*
  * Host side.  The padded class map cls[32 ceil(N / 32)] of a (K, N, info_bits_pos, vn_class): vn_class != NULL is copied (every entry 0 .. 2), else the
  * harness's classes (BS/src/main.cpp:348-354): QLDPC_VN_CHANNEL at info_bits_pos (NULL = 0 .. K-1), QLDPC_VN_PINNED elsewhere.  mask
  * (optional, ceil(N / 32) words) = the packed mask of info_bits_pos.  Returns 0, or -1 for a position outside [0, N), a repeated position or

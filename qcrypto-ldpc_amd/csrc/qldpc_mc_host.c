@@ -1,7 +1,8 @@
 /*
  * qldpc_mc_host.c -- host mirror of the Monte-Carlo frame, channel and pattern definitions (qldpc_mc_philox_host, qldpc_mc_frames_host,
  * qldpc_mc_llr_host, qldpc_mc_pattern_host): the functions of qldpc_mc_core.h that the kernels of qldpc_mc.hip run per lane, here in a loop
- * over frames and words, or over candidates; and the table builder of the quantised AWGN channel (qldpc_mc_awgn_table).  Plain C, no device.
+ * over frames and words, or over candidates; the table builder of the quantised AWGN channel (qldpc_mc_awgn_table); and the deal of one
+ * round of the QBER sweep (qldpc_mc_sweep_deal_host), the function qldpc_mc_sweep itself calls per round.  Plain C, no device.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -141,4 +142,16 @@ int qldpc_mc_pattern_host(uint64_t seed, uint64_t pattern, int n_cand, int n_pun
         }
     }
     return QLDPC_OK;
+}
+
+int qldpc_mc_sweep_deal_host(int n_points, int chunk, int slots, uint64_t max_frames, uint64_t max_frame_errors, const uint64_t *done,
+                             const uint64_t *frame_errors, int *give)
+{
+    if (n_points < 1 || n_points > MC_SWEEP_MAX_POINTS || chunk < 1 || slots < 1 || max_frames == 0) {
+        qldpc_set_error("mc_sweep_deal_host: n_points=%d (1 .. %d), chunk=%d, slots=%d (at least 1), max_frames=%llu (at least 1)", n_points, MC_SWEEP_MAX_POINTS,
+                        chunk, slots, (unsigned long long)max_frames);
+        return QLDPC_ESIZE;
+    }
+    if (!done || !frame_errors || !give) return QLDPC_EINVAL;
+    return mc_sweep_deal(n_points, chunk, slots, max_frames, max_frame_errors, done, frame_errors, give);
 }

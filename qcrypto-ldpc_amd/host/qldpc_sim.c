@@ -32,6 +32,11 @@
  *                      Eb/N0 in place of the QBER; -s and -X do not apply)]
  *                  [-u n (with -A: the first n VNs are punctured, LLR 0: the 2 z of the 5G NR matrices)]
  *                  [-z (with -D: the all-zero codeword instead of random info words, qldpc_mc_set_source)]
+ *                  [-W (with -D: the -s table from ONE qldpc_mc_sweep instead of one qldpc_mc_run per row: the rows side by side in every batch,
+ *                      -E as the stop rule of each row, the lanes of a finished row passing to the others; with -W, -e f is legal under -D: the
+ *                      row at `ber` punctures parity_bits_to_punct(N, K, min_cr(ber, f)) parity VNs, a prefix of ONE order of the parity VNs
+ *                      (bit-reversed positions along the accumulator, so that every prefix is evenly spaced, the spacing the sessions use); a row
+ *                      whose count is negative is skipped with the harness's message; -X and -A do not apply)]
  *                  [-c scale (with -Q 8: quantiser steps per LLR unit, default 8; 1 for LLRs that are integers already, as -A gives them)]
  */
 #include <math.h>
@@ -73,7 +78,7 @@ int main(int argc, char **argv)
     uint64_t max_fe = 0;
     double search_eff = 0.0;      /* -X: > 0 = the pattern search on the device towards this efficiency */
     int frames_per_pattern = 64;
-    int awgn = 0, awgn_maxq = 31, awgn_punct = 0, zero_source = 0;      /* -A, -u, -z */
+    int awgn = 0, awgn_maxq = 31, awgn_punct = 0, zero_source = 0, sweep = 0;      /* -A, -u, -z, -W */
     double ebno_db = 0.0, awgn_rmax = 3.0, quant_scale = 0.0;
     const char *pattern_out = NULL;
     double parity_ber = 0.0;      /* > 0: the disclosed parity bits are themselves wrong with this probability (main.cpp (test effect of dirty parities)) */
@@ -83,7 +88,7 @@ int main(int argc, char **argv)
     double ber_min = 0.01, ber_max = 0.03, ber_step = 0.005;
     uint64_t seed = 0;
     const char *g_method = NULL;
-    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:u:c:DRlvnz")) != -1) {
+    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:u:c:DRWlvnz")) != -1) {
         switch (opt) {
         case 'N': N = atoi(optarg); break;
         case 'K': K = atoi(optarg); break;
@@ -108,6 +113,7 @@ int main(int argc, char **argv)
         case 'A': { const int got = sscanf(optarg, "%lf:%lf:%d", &ebno_db, &awgn_rmax, &awgn_maxq); if (got != 1 && got != 3) { fprintf(stderr, "-A ebno_db[:rmax:maxq]\n"); return 2; } awgn = 1; break; }
         case 'u': awgn_punct = atoi(optarg); break;
         case 'z': zero_source = 1; break;
+        case 'W': sweep = 1; break;
         case 'c': quant_scale = atof(optarg); break;
         case 'o': pattern_out = optarg; break;
         case 'G': g_method = optarg; break;      /* p.G_method (VAR/main.cpp (alist-v1.0.1):135): IDENTITY | LU_DEC; QC = Encoder_LDPC_from_QC ((qc):145) */
@@ -121,7 +127,9 @@ int main(int argc, char **argv)
     int rule = -1;
     for (int i = 0; i < 8; i++) if (!strcmp(rule_name, names[i])) rule = i;
     if (rule < 0) { fprintf(stderr, "unknown rule %s\n", rule_name); return 2; }
-    if (on_device && (target_eff > 0.0 || search)) { fprintf(stderr, "qldpc_sim: -e and -R draw a puncture pattern per batch on the host and do not run with -D\n"); return 2; }
+    if (sweep && !on_device) { fprintf(stderr, "qldpc_sim: -W is the sweep on the device and needs -D\n"); return 2; }
+    if (sweep && (search_eff != 0.0 || awgn)) { fprintf(stderr, "qldpc_sim: -W sweeps the BSC rows of -s and runs neither with the pattern search (-X) nor with -A\n"); return 2; }
+    if (on_device && ((target_eff > 0.0 && !sweep) || search)) { fprintf(stderr, "qldpc_sim: -e and -R draw a puncture pattern per batch on the host and do not run with -D\n"); return 2; }
     if (max_fe && !on_device) { fprintf(stderr, "qldpc_sim: -E needs -D\n"); return 2; }
     if (search_eff != 0.0 && !on_device) { fprintf(stderr, "qldpc_sim: -X is the pattern search on the device and needs -D\n"); return 2; }
     if (search_eff != 0.0 && max_fe) { fprintf(stderr, "qldpc_sim: -E does not apply to the pattern search (-X), which stops at the first pattern without frame errors\n"); return 2; }
@@ -187,6 +195,54 @@ int main(int argc, char **argv)
                    (unsigned long long)r.frame_errors, (double)r.bit_errors / ((double)r.frames * K), (double)r.frame_errors / (double)r.frames,
                    (double)r.frames * K / (r.decode_ms * 1e-3) / 1e6);
             ber_min = 1.0; ber_max = 0.0;      /* no BSC rows */
+        }
+        if (sweep) {      /* the same table from ONE qldpc_mc_sweep: a point per row */
+            const int n_par = N - K;
+            int n_rows = 0, bits = 0, n_order = 0;
+            for (double ber = ber_min; ber <= ber_max + 1e-12; ber += ber_step) n_rows++;
+            qldpc_mc_point *pts = (qldpc_mc_point *)calloc((size_t)(n_rows ? n_rows : 1), sizeof(*pts));
+            int *order = (int *)malloc(sizeof(int) * (size_t)(n_par ? n_par : 1)), *par = (int *)malloc(sizeof(int) * (size_t)(n_par ? n_par : 1));
+            if (!pts || !order || !par) return die("mc_sweep", QLDPC_ENOMEM);
+            if (target_eff > 0.0) {      /* parity VN j along the accumulator, visited in bit-reversed j: every prefix is evenly spaced */
+                int m = 0;
+                for (int v = 0; v < N; v++) if (!is_info[v]) par[m++] = v;
+                while ((1 << bits) < n_par) bits++;
+                for (int i = 0; i < (1 << bits); i++) {
+                    int j = 0;
+                    for (int b = 0; b < bits; b++) j |= ((i >> b) & 1) << (bits - 1 - b);
+                    if (j < n_par) order[n_order++] = par[j];
+                }
+            }
+            int P = 0;
+            for (double ber = ber_min; ber <= ber_max + 1e-12; ber += ber_step) {
+                int n_punct = 0;
+                if (target_eff > 0.0) {
+                    n_punct = qldpc_parity_bits_to_punct(N, K, qldpc_min_code_rate((float)ber, (float)target_eff));
+                    if (n_punct < 0) { printf("# ber %.4f: mother code rate already above the goal, nothing to puncture\n", ber); continue; }
+                    if (n_punct > n_par) n_punct = n_par;
+                    printf("# ber %.4f: puncturing %d of %d parity bits -> rate %.4f, efficiency f = %.3f\n", ber, n_punct, n_par, (double)K / (N - n_punct),
+                           ((double)(n_par - n_punct) / K) / (double)qldpc_binary_entropy((float)ber));
+                }
+                pts[P].qber = ber; pts[P].n_punct = n_punct; P++;
+            }
+            if (P > 0) {
+                qldpc_mc_sweep_cfg wcfg;
+                memset(&wcfg, 0, sizeof(wcfg));
+                wcfg.points = pts; wcfg.n_points = P; wcfg.punct_order = n_order ? order : NULL; wcfg.n_order = n_order;
+                wcfg.max_frames = (uint64_t)(frames > 0 ? frames : 0); wcfg.max_frame_errors = max_fe;
+                qldpc_mc_sweep_result w;
+                if ((rc = qldpc_mc_sweep(mc, &wcfg, &w))) return die("mc_sweep", rc);
+                qldpc_mc_point_stat *rows = (qldpc_mc_point_stat *)malloc(sizeof(*rows) * (size_t)P);
+                if (!rows || (rc = qldpc_mc_sweep_stats(mc, rows, P)) < 0) return die("mc_sweep_stats", rows ? rc : QLDPC_ENOMEM);
+                printf("# sweep: %d points in %llu rounds, %llu frames\n", P, (unsigned long long)w.rounds, (unsigned long long)w.frames);
+                for (int q = 0; q < P; q++)      /* SIM_THR: the sweep's decode time is shared by the rows, so it is the sweep's throughput in every row */
+                    printf("  %8.4f | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", rows[q].qber, (unsigned long long)rows[q].frames, (unsigned long long)rows[q].bit_errors,
+                           (unsigned long long)rows[q].frame_errors, (double)rows[q].bit_errors / ((double)rows[q].frames * K),
+                           (double)rows[q].frame_errors / (double)rows[q].frames, (double)w.frames * K / (w.decode_ms * 1e-3) / 1e6);
+                free(rows);
+            }
+            free(pts); free(order); free(par);
+            ber_min = 1.0; ber_max = 0.0;      /* the rows are printed */
         }
         for (double ber = ber_min; search_eff > 0.0 && ber <= ber_max + 1e-12; ber += ber_step) {      /* every row one qldpc_mc_search */
             const int n_par = N - K;
