@@ -37,6 +37,7 @@
  *   qldpc_mc_*                            the simulation loop itself: source, encoder, BSC, decoder, Monitor_BFER   BS/src/main.cpp:335-393
  *   qldpc_mc_search / _patterns_dev       the puncture-pattern search around it: shuffle, erase, first FER = 0 / n  BS/src/main.cpp:235-411
  *   qldpc_mc_sweep                        the BER loop around both, with its puncture count per BER                BS/src/main.cpp:233-272
+ *   qldpc_mc_strata / _weight_frames_*    the same loop over fixed error weights instead of BERs: FER(q) for every q   (no counterpart)
  *   qldpc_mc_set_channel / _awgn_table   the channel of the fixed-point sims: BPSK over AWGN, 6-bit received values  ML/BPSK_nrldpc_sim_RM_FP.m
  */
 #ifndef QLDPC_H
@@ -807,13 +808,96 @@ int    qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc_mc_swee
 /* of the last sweep: one row per point, in point order; writes min(cap, P) and returns P (or a status) */
 int    qldpc_mc_sweep_stats(qldpc_mc *mc, qldpc_mc_point_stat *rows, int cap);
 /* of the last sweep: frames per iteration count of one point, n_ite + 1 bins; writes min(cap, n_ite + 1) and returns n_ite + 1 (or a
-   status: QLDPC_ESIZE for a point the last sweep did not have) */
+   status: QLDPC_ESIZE for a point the last sweep did not have, QLDPC_ESTATE after a later qldpc_mc_strata, whose rows then hold the device) */
 int    qldpc_mc_sweep_hist(qldpc_mc *mc, int point, uint64_t *hist, int cap);
 /* host mirror, no device needed: the deal of one round over n_points points with `slots` chunk slots of `chunk` frames; give[n_points] = the
    chunks of each point; returns the chunks dealt (or a status: QLDPC_ESIZE for n_points outside 1 .. QLDPC_MC_SWEEP_MAX_POINTS, chunk < 1,
    slots < 1 or max_frames == 0, QLDPC_EINVAL for a missing array) */
 int    qldpc_mc_sweep_deal_host(int n_points, int chunk, int slots, uint64_t max_frames, uint64_t max_frame_errors, const uint64_t *done,
                                 const uint64_t *frame_errors, int *give);
+
+/*
+ * Fixed-weight error strata: the step that makes a deep FER affordable on the BSC, and there it is exact.  Conditioned on the number W of
+ * flipped channel bits the flip set is uniform over the C(n, W) subsets, and with the decoder's |LLR| held fixed the failure probability
+ * P_f(w) of weight w does not depend on the QBER, so FER(q) = sum_w Binom(n, q)(w) P_f(w) for every q from ONE set of fixed-weight runs: the
+ * binomial tail is known in closed form and only the narrow transition of P_f(w) is simulated.  It also answers how many errors a block may
+ * hold and still decode.
+ *
+ *   frame      the fixed-weight frame (i, w) (csrc/qldpc_mc_core.h): the key of VN v is u_v, output word v % 4 of the generator at counter
+ *              (v / 4, 1, i_lo, i_hi) -- exactly the word the BSC frame compares with its threshold -- coarsened to u'_v = u_v >>
+ *              (32 - key_bits), key_bits 1 .. 32 (0 stands for 32; smaller values exist so that tests can force ties).  The flip set is the
+ *              w VNs of class QLDPC_VN_CHANNEL smallest in the order (u'_v, v): equal keys go to the lower VN; 0 <= w <= channel VNs.
+ *              QLDPC_VN_PINNED VNs keep their rule (flip iff u_v < floor(parity_ber 2^32)), QLDPC_VN_PUNCTURED VNs never flip.  The weight
+ *              counts channel VNs before any erasure of qldpc_mc_set_puncture: an erased VN may be in the set and then has no effect
+ *   identity   at key_bits = 32 the BSC set {v channel : u_v < T} is, for every T, the fixed-weight set of its own size: the frame of
+ *              qldpc_mc_frames_host with c channel flips IS the fixed-weight frame of weight c, bit for bit, and the flip sets of two
+ *              weights of one frame are nested
+ *   strata     qldpc_mc_strata runs 1 <= n_strata <= QLDPC_MC_SWEEP_MAX_POINTS weights (any order, repeats allowed) side by side in one
+ *              batch; every slot is decoded with |LLR| = qldpc_bsc_llr((float)design_qber), design_qber in (0, 0.5); frame k of every
+ *              stratum is Monte-Carlo frame first_frame + k.  Open / closed, need, chunks, the deal (qldpc_mc_sweep_deal_host), the rounds
+ *              and the one read-back per round are those of qldpc_mc_sweep, and the two calls run the same round loop; the fixed set of
+ *              qldpc_mc_set_puncture is honoured.  The row of a stratum is what the stratum would get alone, for any batch, chunk and
+ *              neighbours; channel_flips is counted by the monitor kernel from rx ^ cw and so comes out as frames x weight
+ *   estimate   qldpc_mc_strata_fer_host, from strictly ascending weights w_0 < .. < w_last: p_s = frame_errors_s / frames_s; P^(w) is
+ *              piecewise linear in w between neighbouring strata; b(w) = exp(lgamma(n + 1) - lgamma(w + 1) - lgamma(n - w + 1) + w ln q +
+ *              (n - w) log1p(-q)) in double.  out[0] = sum_{w_0 <= w <= w_last} b(w) P^(w); out[1] = sum_{w < w_0} b(w); out[2] =
+ *              sum_{w > w_last} b(w); out[3] = sqrt(sum_s c_s^2 p_s (1 - p_s) / frames_s), c_s = sum_w b(w) hat_s(w) the binomial mass that
+ *              stratum s carries through the interpolation, so that out[0] = sum_s c_s p_s
+ *
+ * The caller turns out[1] and out[2] into bounds: as far as the interpolation holds, FER(q) lies between out[0] and out[0] + out[1] +
+ * out[2]; where the top stratum fails every frame, out[2] counts in full.  Limits: P_f below the lowest stratum that saw a failure is
+ * bounded only by the frames spent there (0 of F frames bounds p_s by about 3 / F at 95 %): stratification removes the binomial tail, NOT an
+ * error floor.  The linear interpolation is an assumption between strata (contiguous weights need none), out[3] is the sampling error of the
+ * p_s alone, and P_f(w) is that of the decoder at the design |LLR|: a decoder fed the |LLR| of each q differs where its rule is not
+ * scale-invariant.
+ *
+ * Status codes: QLDPC_ESIZE for a weight outside [0, channel VNs], n_strata outside its range, design_qber outside (0, 0.5), chunk outside
+ * [0, batch], max_frames == 0, key_bits outside 0 .. 32, and in the estimate frames_s == 0 (or frame_errors_s > frames_s) or qber outside
+ * (0, 1); QLDPC_EINVAL for a missing array, non-zero reserved fields, or weights not strictly ascending in the estimate; QLDPC_ESTATE while a
+ * table of qldpc_mc_set_channel is in force; QLDPC_ENODEV without a device.  A refused call queues nothing and leaves earlier rows readable.
+ * The first strata call allocates what it needs (what the first sweep allocates: the two calls share the slot tables and the device rows),
+ * counted by qldpc_mc_device_bytes; later calls allocate nothing.  The device rows belong to whichever of qldpc_mc_sweep / qldpc_mc_strata ran
+ * last: qldpc_mc_sweep_hist after a strata run and qldpc_mc_strata_hist after a sweep return QLDPC_ESTATE; the stat rows of both are kept on
+ * the host, separately, and stay readable.  The fixed-weight channel costs about five times the generator work of the BSC kernel (four digit
+ * passes and the final one); measured once at the headline shape it took 0.8 ms per 4 096-frame round beside 81 ms of decode
+ * (tools/mc_strata_cost.py, profiles/mc_strata_cost.json).
+ * Not built: a matched |LLR| per stratum; strata of a table channel; failed-frame lists per stratum; an adaptive choice of weights; a
+ * multi-GPU driver; the deal on the device.
+ */
+typedef struct qldpc_mc_strata_cfg {
+    const int *weights; int n_strata;   /* HOST array                                                                                 */
+    double design_qber;        /* every slot is decoded with |LLR| = qldpc_bsc_llr((float)design_qber)                                 */
+    int key_bits;              /* 0 = 32                                                                                               */
+    int chunk;                 /* C; 0 = min(64, batch)                                                                                */
+    uint64_t first_frame, max_frames, max_frame_errors;   /* per stratum; max_frame_errors = 0: no stop rule                          */
+    int reserved[2];           /* must be zero                                                                                         */
+} qldpc_mc_strata_cfg;
+typedef qldpc_mc_sweep_result qldpc_mc_strata_result;     /* rounds, frames, batches, stage times; channel_ms = the fixed-weight channel */
+typedef struct qldpc_mc_stratum_stat {
+    int weight;
+    int closed_by;             /* QLDPC_MC_CLOSED_*                                                                                    */
+    uint64_t frames, frame_errors, bit_errors, undetected, not_converged, iter_sum, iter_max, channel_flips, channel_bits;   /* as qldpc_mc_result */
+    uint64_t last_round;       /* the last round in which the stratum received frames                                                  */
+} qldpc_mc_stratum_stat;
+/* host mirror, no device needed: frames [first_frame, first_frame + n_frames), frame f at weight weights[f]: info_words[n][ceil(K/32)] and
+   flip_words[n][ceil(N/32)] as qldpc_mc_frames_host gives them (either may be NULL; weights is read for flip_words only); info_bits_pos and
+   vn_class as there */
+int    qldpc_mc_weight_frames_host(int K, int N, const int *info_bits_pos, const uint8_t *vn_class, uint64_t seed, double parity_ber,
+                                   uint64_t first_frame, int n_frames, const int *weights /* n_frames */, int key_bits, uint32_t *info_words,
+                                   uint32_t *flip_words);
+/* the source alone, one weight for the call: DEVICE buffers d_info[n][ceil(K/32)], d_cw[n][ceil(N/32)], d_rx[n][ceil(N/32)] = cw ^ flips
+   (d_cw / d_rx may be NULL from the right); asynchronous on the decoder's stream, like qldpc_mc_frames_dev */
+int    qldpc_mc_weight_frames_dev(qldpc_mc *mc, uint64_t first_frame, int n_frames, int weight, int key_bits, uint32_t *d_info, uint32_t *d_cw,
+                                  uint32_t *d_rx);
+int    qldpc_mc_strata(qldpc_mc *mc, const qldpc_mc_strata_cfg *cfg, qldpc_mc_strata_result *res);
+/* of the last strata run: one row per stratum, in the caller's order; writes min(cap, n_strata) and returns n_strata (or a status) */
+int    qldpc_mc_strata_stats(qldpc_mc *mc, qldpc_mc_stratum_stat *rows, int cap);
+/* of the last strata run: frames per iteration count of one stratum, n_ite + 1 bins; writes min(cap, n_ite + 1) and returns n_ite + 1 (or a
+   status: QLDPC_ESIZE for a stratum the last run did not have, QLDPC_ESTATE after a later qldpc_mc_sweep) */
+int    qldpc_mc_strata_hist(qldpc_mc *mc, int stratum, uint64_t *hist, int cap);
+/* host only: the estimate above over n_channel channel VNs at `qber`; weights strictly ascending */
+int    qldpc_mc_strata_fer_host(int n_channel, int n_strata, const int *weights, const uint64_t *frames, const uint64_t *frame_errors, double qber,
+                                double out[4]);
 
 #ifdef __cplusplus
 }

@@ -945,6 +945,24 @@ _sig("qldpc_mc_sweep_hist", C.c_int, [_vp, C.c_int, _u64p, C.c_int])
 _sig("qldpc_mc_sweep_deal_host", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _u64p, _u64p, _ip])
 
 
+class McStrataCfg(C.Structure):
+    _fields_ = [("weights", _ip), ("n_strata", C.c_int), ("design_qber", C.c_double), ("key_bits", C.c_int), ("chunk", C.c_int),
+                ("first_frame", C.c_uint64), ("max_frames", C.c_uint64), ("max_frame_errors", C.c_uint64), ("reserved", C.c_int * 2)]
+
+
+McStrataResult = McSweepResult          # rounds, frames, batches, the stage times; channel_ms is the fixed-weight channel
+MC_STRATUM_STAT = np.dtype([("weight", np.int32), ("closed_by", np.int32)] + [(n, np.uint64) for n in (
+    "frames", "frame_errors", "bit_errors", "undetected", "not_converged", "iter_sum", "iter_max", "channel_flips", "channel_bits", "last_round")])
+
+_dp = C.POINTER(C.c_double)
+_sig("qldpc_mc_weight_frames_host", C.c_int, [C.c_int, C.c_int, _ip, _u8p, C.c_uint64, C.c_double, C.c_uint64, C.c_int, _ip, C.c_int, _up, _up])
+_sig("qldpc_mc_weight_frames_dev", C.c_int, [_vp, C.c_uint64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp])
+_sig("qldpc_mc_strata", C.c_int, [_vp, C.POINTER(McStrataCfg), C.POINTER(McStrataResult)])
+_sig("qldpc_mc_strata_stats", C.c_int, [_vp, _vp, C.c_int])
+_sig("qldpc_mc_strata_hist", C.c_int, [_vp, C.c_int, _u64p, C.c_int])
+_sig("qldpc_mc_strata_fer_host", C.c_int, [C.c_int, C.c_int, _ip, _u64p, _u64p, C.c_double, _dp])
+
+
 class McChannel(C.Structure):
     _fields_ = [("levels", C.c_int), ("cum", _u64p * 2), ("value", C.POINTER(C.c_float)), ("reserved", C.c_int * 2)]
 
@@ -1018,6 +1036,43 @@ def mc_sweep_deal(done, frame_errors, chunk, slots, max_frames, max_frame_errors
                                             fe.ctypes.data_as(_u64p), give.ctypes.data_as(_ip)), "mc_sweep_deal")
     assert used == int(give.sum())
     return give
+
+
+def mc_weight_frames_host(K, N, seed, weights, first_frame, n_frames, key_bits=0, info_bits_pos=None, vn_class=None, parity_ber=0.0):
+    """Frames [first_frame, first_frame + n_frames) of the fixed-weight frame definition on the host, no device needed: frame f flips the
+    weights[f] channel VNs with the smallest stream-1 words (a scalar `weights` stands for every frame) -> (info words [n, ceil(K/32)],
+    flip words [n, ceil(N/32)]), uint32, MSB-first.  key_bits below 32 coarsens the keys (tests only); the classes as mc_frames_host."""
+    K, N, n = int(K), int(N), int(n_frames)
+    pos = None
+    if info_bits_pos is not None:
+        pos = _np_i32(info_bits_pos).ravel()
+        if pos.size != K:
+            raise QldpcError(-6, "mc_weight_frames_host: len(info_bits_pos) != K")
+    cls = _mc_class_arg(vn_class, N, "mc_weight_frames_host")
+    w = np.full(max(n, 0), int(weights), np.int32) if np.ndim(weights) == 0 else _np_i32(weights).ravel()
+    if w.size != max(n, 0):
+        raise QldpcError(-6, "mc_weight_frames_host: %d weights for %d frames" % (w.size, n))
+    info = np.zeros((max(n, 0), (max(K, 0) + 31) // 32), np.uint32)
+    flips = np.zeros((max(n, 0), (max(N, 0) + 31) // 32), np.uint32)
+    _chk(_L.qldpc_mc_weight_frames_host(K, N, pos.ctypes.data_as(_ip) if pos is not None else None, cls.ctypes.data_as(_u8p) if cls is not None else None,
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, float(parity_ber), int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, w.ctypes.data_as(_ip),
+                                        int(key_bits), info.ctypes.data_as(_up), flips.ctypes.data_as(_up)), "mc_weight_frames_host")
+    return info, flips
+
+
+def mc_strata_fer(n_channel, weights, frames, frame_errors, qber):
+    """FER(qber) of a BSC over n_channel channel VNs from fixed-weight strata (qldpc_mc_strata_fer_host, no device needed): weights strictly
+    ascending, frames and frame_errors per stratum -> float64 [4]: the binomial-weighted failure rate over [w_0, w_last] with P_f linear
+    between strata, the binomial mass below w_0, the mass above w_last, the standard error of the first from the sampling of the strata"""
+    w = _np_i32(weights).ravel()
+    fr = np.ascontiguousarray(frames, dtype=np.uint64).ravel()
+    fe = np.ascontiguousarray(frame_errors, dtype=np.uint64).ravel()
+    if fr.size != w.size or fe.size != w.size:
+        raise QldpcError(-6, "mc_strata_fer: %d weights, %d frame counts, %d frame-error counts" % (w.size, fr.size, fe.size))
+    out = np.zeros(4, np.float64)
+    _chk(_L.qldpc_mc_strata_fer_host(int(n_channel), w.size, w.ctypes.data_as(_ip), fr.ctypes.data_as(_u64p), fe.ctypes.data_as(_u64p), float(qber),
+                                     out.ctypes.data_as(_dp)), "mc_strata_fer")
+    return out
 
 
 def _mc_channel_arg(cum0, cum1, value, where):
@@ -1265,6 +1320,59 @@ class MonteCarlo:
         out = np.zeros((P, bins), np.uint64)
         for q in range(P):
             _chk(_L.qldpc_mc_sweep_hist(self._h, q, out[q].ctypes.data_as(_u64p), bins), "MonteCarlo.sweep_hist")
+        return out
+
+    def weight_frames(self, first_frame, n_frames, weight, key_bits=0):
+        """the source alone at one fixed error weight -> device int32 tensors (info [n, ceil(K/32)], cw [n, ceil(N/32)], rx [n, ceil(N/32)]):
+        what mc_weight_frames_host gives, the codeword by the encoder, rx = cw ^ flips"""
+        torch = _torch()
+        n = int(n_frames)
+        dev = "cuda:%d" % self.device
+        info = torch.empty((max(n, 0), (self.K + 31) // 32), dtype=torch.int32, device=dev)
+        cw = torch.empty((max(n, 0), (self.N + 31) // 32), dtype=torch.int32, device=dev)
+        rx = torch.empty_like(cw)
+        _chk(_L.qldpc_mc_weight_frames_dev(self._h, int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, int(weight), int(key_bits), _vp(info.data_ptr()), _vp(cw.data_ptr()),
+                                           _vp(rx.data_ptr())), "MonteCarlo.weight_frames")
+        self.decoder.sync()
+        return info, cw, rx
+
+    def strata(self, weights, design_qber, first_frame=0, max_frames=None, max_frame_errors=0, chunk=0, key_bits=0):
+        """Fixed error weights side by side in one batch (qldpc_mc_strata): stratum s flips exactly weights[s] channel VNs of every frame, the
+        ones with the smallest channel words, and is decoded with |LLR| = bsc_llr(design_qber); frame k of every stratum is frame
+        first_frame + k; a stratum closes at max_frames (None = one batch) or at max_frame_errors (0 = never), and its lanes pass to the open
+        ones, `chunk` frames at a time (0 = min(64, batch)) -> dict of the result (rounds, frames, batches, the stage times) plus `strata`,
+        one MC_STRATUM_STAT row per weight in the caller's order.  mc_strata_fer turns the rows into FER(q) for any q."""
+        w = _np_i32(weights).ravel()
+        cfg = McStrataCfg()
+        cfg.weights, cfg.n_strata = (w.ctypes.data_as(_ip) if w.size else None), w.size
+        cfg.design_qber, cfg.key_bits, cfg.chunk = float(design_qber), int(key_bits), int(chunk)
+        cfg.first_frame = int(first_frame) & 0xFFFFFFFFFFFFFFFF
+        cfg.max_frames, cfg.max_frame_errors = (self.batch if max_frames is None else int(max_frames)), int(max_frame_errors)
+        res = McStrataResult()
+        _chk(_L.qldpc_mc_strata(self._h, C.byref(cfg), C.byref(res)), "MonteCarlo.strata")
+        out = {name: getattr(res, name) for name, _ in McStrataResult._fields_}
+        out["strata"] = self.strata_stats()
+        assert out["strata"].size == w.size
+        return out
+
+    def strata_stats(self):
+        """the stratum rows of the last strata run (MC_STRATUM_STAT), in the caller's order"""
+        n = _chk(_L.qldpc_mc_strata_stats(self._h, None, 0), "MonteCarlo.strata_stats")
+        rows = np.zeros(n, MC_STRATUM_STAT)
+        if n:
+            _chk(_L.qldpc_mc_strata_stats(self._h, _vp(rows.ctypes.data), n), "MonteCarlo.strata_stats")
+        return rows
+
+    def strata_hist(self):
+        """frames per iteration count of every stratum of the last strata run -> uint64 [n_strata, n_ite + 1]"""
+        P = _chk(_L.qldpc_mc_strata_stats(self._h, None, 0), "MonteCarlo.strata_hist")
+        if P == 0:
+            return np.zeros((0, 0), np.uint64)
+        one = np.zeros(1, np.uint64)
+        bins = _chk(_L.qldpc_mc_strata_hist(self._h, 0, one.ctypes.data_as(_u64p), 1), "MonteCarlo.strata_hist")      # the call returns n_ite + 1
+        out = np.zeros((P, bins), np.uint64)
+        for q in range(P):
+            _chk(_L.qldpc_mc_strata_hist(self._h, q, out[q].ctypes.data_as(_u64p), bins), "MonteCarlo.strata_hist")
         return out
 
     def __del__(self):

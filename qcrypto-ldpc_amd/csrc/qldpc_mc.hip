@@ -33,6 +33,15 @@
  *     ONE atomicAdd per wave and counter onto the counter row of that point and one atomicMax for iter_max, per frame one add on the point's
  *     histogram row; no failed-frame list.
  *
+ * mc_channel_weight: the fixed-weight channel of the error strata (qldpc_mc_strata, the definition is qldpc_mc_core.h), one workgroup per frame
+ *     slot: per key digit a histogram in LDS over the keys of the channel-class VNs, recomputed on the fly from the padded class map (N / 4
+ *     Philox calls per pass, nothing stored: at N = 65 536 the keys of a frame do not fit in LDS), lane 0 picks the bucket.  The final pass
+ *     gives a lane a whole codeword word, 256 words per trip: 8 Philox calls, the 32 classes as mc_channel reads them, three masks (keys below
+ *     the threshold key, keys equal to it, pinned flips); the rank of the word among equal keys = a running count + a shuffle prefix over the
+ *     trip; rx = cw ^ (selected | pinned) is one plain store per word, no global atomics.  The weight, the |LLR| and the frame index of a slot
+ *     come from the tables of the round ({weight, |LLR|} rows in the layout of mc_channel_points' {threshold, |LLR|}), or from the arguments
+ *     for qldpc_mc_weight_frames_dev.
+ *
  * No kernel waits on another wave.  The decoder and the encoder are driven through their public calls only; qldpc_engine_int.h is read for
  * the decoder's sizes, device and stream.
  */
@@ -344,6 +353,67 @@ __global__ __launch_bounds__(MC_LANES) void mc_monitor_points(const uint32_t *__
     if (s_nc) atomicAdd(r + MC_NOT_CONVERGED, s_nc);
 }
 
+/* ---- fixed-weight error strata ---- */
+struct mc_stratum_row { uint32_t weight; float mag; };       /* of a stratum: its weight, qldpc_bsc_llr(design_qber) */
+static_assert(sizeof(mc_stratum_row) == sizeof(mc_point_row), "a stratum row travels in the point rows of the sweep");
+
+/* rx[slot][Wn] = cw[slot][Wn] ^ the flips of the fixed-weight frame of the slot; gridDim.x = the slots.  slot_frame == NULL: frame first + slot;
+ * slot_stratum == NULL: every slot is `one`.  cls = the padded class map (past N: QLDPC_VN_PUNCTURED, never selected); key_bits 1 .. 32;
+ * weight <= the channel VNs of cls */
+__global__ __launch_bounds__(MC_PAT_LANES) void mc_channel_weight(const uint32_t *__restrict__ cw, uint32_t *__restrict__ rx, const uint4 *__restrict__ cls, unsigned Wn,
+                                                                  uint64_t seed, uint64_t first, const uint64_t *__restrict__ slot_frame,
+                                                                  const uint32_t *__restrict__ slot_stratum, const mc_stratum_row *__restrict__ strata,
+                                                                  mc_stratum_row one, int key_bits, uint32_t t_pinned, float *__restrict__ llr_mag)
+{
+    __shared__ uint32_t hist[MC_SEL_BINS];
+    __shared__ uint32_t sel[2];
+    __shared__ unsigned wave_eq[MC_PAT_LANES / 64];
+    const unsigned t = threadIdx.x, lane = t & 63u, wave = t >> 6, slot = blockIdx.x;
+    const uint64_t frame = slot_frame ? slot_frame[slot] : first + slot;
+    const mc_stratum_row st = slot_stratum ? strata[slot_stratum[slot]] : one;
+    const uint32_t *cls4 = (const uint32_t *)cls;
+    const unsigned quads = 8u * Wn;
+    uint32_t prefix = 0, mask = 0, k = st.weight, u[4];
+    for (int shift = mc_select_top_shift(key_bits); shift >= 0 && st.weight; shift -= MC_SEL_BITS) {      /* uniform over the workgroup; weight 0: T = 0, r = 0 */
+        hist[t] = 0u;
+        __syncthreads();
+        for (unsigned g = t; g < quads; g += MC_PAT_LANES) {
+            const uint32_t m = mc_weight_quad(seed, frame, g, cls4[g], 0u, u);
+            for (unsigned b = 0; b < 4; b++) {
+                const uint32_t key = u[b] >> (32 - key_bits);
+                if (((m >> b) & 1u) && (key & mask) == prefix) atomicAdd(&hist[(key >> shift) & (MC_SEL_BINS - 1)], 1u);
+            }
+        }
+        __syncthreads();
+        if (t == 0) { uint32_t kk = k; sel[0] = mc_select_digit(hist, &kk); sel[1] = kk; }
+        __syncthreads();
+        prefix |= sel[0] << shift; k = sel[1];
+        mask |= (uint32_t)(MC_SEL_BINS - 1) << shift;
+    }
+    /* T = prefix, r = k */
+    const size_t row = (size_t)slot * Wn;
+    unsigned equal_base = 0;
+    for (unsigned w0 = 0; w0 < Wn; w0 += MC_PAT_LANES) {
+        const unsigned w = w0 + t;
+        uint32_t less = 0, eq = 0, pin = 0;
+        if (w < Wn) {
+            const uint4 a = cls[2u * w], b = cls[2u * w + 1u];
+            const uint32_t c4[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+            mc_weight_masks(seed, frame, w, c4, key_bits, prefix, t_pinned, &less, &eq, &pin);
+        }
+        const unsigned mine = (unsigned)__popc(eq);
+        unsigned incl = mine;
+        for (unsigned s = 1; s < 64u; s <<= 1) { const unsigned v = __shfl_up(incl, s, 64); if (lane >= s) incl += v; }
+        if (lane == 63u) wave_eq[wave] = incl;
+        __syncthreads();
+        unsigned before = equal_base + incl - mine;
+        for (unsigned x = 0; x < MC_PAT_LANES / 64; x++) { if (x < wave) before += wave_eq[x]; equal_base += wave_eq[x]; }
+        if (w < Wn) rx[row + w] = cw[row + w] ^ (mc_weight_take(less, eq, prefix, k, before) | pin);
+        __syncthreads();
+    }
+    if (t == 0 && llr_mag) llr_mag[slot] = st.mag;
+}
+
 /* ------------------------------------------------------------------ host ---- */
 
 struct qldpc_mc {
@@ -383,7 +453,11 @@ struct qldpc_mc {
     mc_u64 *d_wctr, *h_wctr, *d_whist; /* [QLDPC_MC_SWEEP_MAX_POINTS][MCW_COUNTERS] counter rows, pinned copy; [..][n_ite + 1] histogram rows */
     hipEvent_t wev[8];                 /* of a sweep round: source | encode | channel | load | erase | run | fetch + monitor */
     std::vector<qldpc_mc_point_stat> wstats;    /* of the last sweep */
+    /* the error strata run the sweep's rounds on the sweep's tables and device rows; rows_owner says whose counters and histograms those hold */
+    int rows_owner;                    /* MC_ROWS_* */
+    std::vector<qldpc_mc_stratum_stat> tstats;  /* of the last strata run */
 };
+enum { MC_ROWS_NONE = 0, MC_ROWS_SWEEP, MC_ROWS_STRATA };
 
 extern "C" void qldpc_mc_cfg_default(qldpc_mc_cfg *cfg)
 {
@@ -885,45 +959,43 @@ static int mc_sweep_args(const qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg)
     return QLDPC_OK;
 }
 
-extern "C" int qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc_mc_sweep_result *res)
+/* the rounds of qldpc_mc_sweep and of qldpc_mc_strata: P rows side by side in one batch, each over frames first_frame + k with its own counter
+ * row, histogram row and stop rule; per round the deal, the slot tables, generate / encode / channel / load / erase / run / fetch / monitor and
+ * ONE read-back of the P counter rows, which stay in h_wctr.  The caller has checked every argument and reserved the device side. */
+struct mc_rounds_job {
+    int P, C;
+    uint64_t first_frame, max_frames, max_fe;
+    const mc_point_row *rows;          /* [P] {threshold, |LLR|} of the sweep's points, or the strata's {weight, |LLR|} in the same layout */
+    const uint32_t *erows;             /* [P][Wn] the erase rows, NULL = nothing is erased */
+    int weight_key_bits;               /* 0: the BSC of the rows' thresholds (mc_channel_points); 1 .. 32: the rows' fixed weights (mc_channel_weight) */
+    int owner;                         /* MC_ROWS_*: whose rows the device holds from here on */
+};
+
+static int mc_rounds(qldpc_mc *mc, const mc_rounds_job &job, uint64_t *last_round /* [P] */, qldpc_mc_sweep_result *res)
 {
-    if (!mc || !cfg || !res) return QLDPC_EINVAL;
-    memset(res, 0, sizeof(*res));
-    int rc = mc_sweep_args(mc, cfg);
-    if (rc || (rc = mc_sweep_reserve(mc))) return rc;
     const hipStream_t s = mc->dec->stream;
-    const int P = cfg->n_points, C = cfg->chunk ? cfg->chunk : std::min(64, mc->batch), S = mc->batch / C;
+    const int P = job.P, C = job.C, S = mc->batch / C;
     const unsigned Wn = (unsigned)mc->Wn, Wk = (unsigned)mc->Wk;
     const size_t B = (size_t)mc->batch, bins = (size_t)mc->n_ite + 1;
-    const uint64_t max_frames = cfg->max_frames, max_fe = cfg->max_frame_errors;
+    const uint64_t max_frames = job.max_frames, max_fe = job.max_fe;
+    const bool any_erase = job.erows != nullptr;
+    const mc_stratum_row no_row = {0u, 0.0f};      /* mc_channel_weight reads the rows of the round */
     /* the tables of a round inside the one buffer */
     uint64_t *const h_frame = (uint64_t *)mc->h_slots;
     uint32_t *const h_point = (uint32_t *)(mc->h_slots + B), *const h_cpoint = h_point + B, *const h_cstart = h_cpoint + B, *const h_clen = h_cstart + B;
     const uint64_t *const d_frame = (const uint64_t *)mc->d_slots;
     const uint32_t *const d_point = (const uint32_t *)(mc->d_slots + B), *const d_cpoint = d_point + B, *const d_cstart = d_cpoint + B, *const d_clen = d_cstart + B;
 
-    /* per sweep: the point rows and the erase rows (fixed set OR prefix), built here once */
-    std::vector<mc_point_row> prow((size_t)P);
-    std::vector<uint32_t> erows((size_t)P * Wn, 0u);
-    bool any_erase = false;
-    for (int q = 0; q < P; q++) {
-        prow[(size_t)q].t_channel = mc_threshold(cfg->points[q].qber);
-        prow[(size_t)q].mag = qldpc_bsc_llr((float)cfg->points[q].qber);
-        uint32_t *row = erows.data() + (size_t)q * Wn;
-        if (mc->n_fixed) memcpy(row, mc->h_fixed.data(), sizeof(uint32_t) * Wn);
-        for (int i = 0; i < cfg->points[q].n_punct; i++) { const int v = cfg->punct_order[i]; row[v >> 5] |= 0x80000000u >> (v & 31); }
-        any_erase = any_erase || mc->n_fixed || cfg->points[q].n_punct > 0;
-    }
-    HIPCHK(hipStreamSynchronize(s));      /* a queued kernel may still read the rows of an earlier sweep */
-    HIPCHK(hipMemcpy(mc->d_points, prow.data(), sizeof(mc_point_row) * (size_t)P, hipMemcpyHostToDevice));
-    if (any_erase) HIPCHK(hipMemcpy(mc->d_prows, erows.data(), sizeof(uint32_t) * erows.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipStreamSynchronize(s));      /* a queued kernel may still read the rows of an earlier call */
+    HIPCHK(hipMemcpy(mc->d_points, job.rows, sizeof(mc_point_row) * (size_t)P, hipMemcpyHostToDevice));
+    if (any_erase) HIPCHK(hipMemcpy(mc->d_prows, job.erows, sizeof(uint32_t) * (size_t)P * Wn, hipMemcpyHostToDevice));
+    mc->rows_owner = job.owner;
     HIPCHK(hipMemsetAsync(mc->d_wctr, 0, sizeof(mc_u64) * (size_t)P * MCW_COUNTERS, s));
     HIPCHK(hipMemsetAsync(mc->d_whist, 0, sizeof(mc_u64) * (size_t)P * bins, s));
-    mc->wstats.assign((size_t)P, qldpc_mc_point_stat());
-    for (int q = 0; q < P; q++) { mc->wstats[(size_t)q].qber = cfg->points[q].qber; mc->wstats[(size_t)q].n_punct = cfg->points[q].n_punct; }
 
     std::vector<uint64_t> done((size_t)P, 0), fe((size_t)P, 0);
     std::vector<int> give((size_t)P);
+    int rc = QLDPC_OK;
     const auto t_start = std::chrono::steady_clock::now();
     for (uint64_t round = 0;; round++) {
         const int n_chunks = mc_sweep_deal(P, C, S, max_frames, max_fe, done.data(), fe.data(), give.data());
@@ -934,8 +1006,8 @@ extern "C" int qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc
                 const uint64_t k0 = done[(size_t)q] + (uint64_t)j * (uint64_t)C;
                 const unsigned len = (unsigned)std::min<uint64_t>((uint64_t)C, max_frames - k0);
                 h_cpoint[nc] = (uint32_t)q; h_cstart[nc] = nb; h_clen[nc] = len;
-                for (unsigned i = 0; i < len; i++, nb++) { h_frame[nb] = cfg->first_frame + k0 + i; h_point[nb] = (uint32_t)q; }
-                mc->wstats[(size_t)q].last_round = round;
+                for (unsigned i = 0; i < len; i++, nb++) { h_frame[nb] = job.first_frame + k0 + i; h_point[nb] = (uint32_t)q; }
+                last_round[q] = round;
             }
         const unsigned ti = nb * Wk, tn = nb * Wn;
         HIPCHK(hipEventRecord(mc->wev[0], s));
@@ -948,8 +1020,12 @@ extern "C" int qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc
         HIPCHK(hipEventRecord(mc->wev[1], s));
         if ((rc = qldpc_encode_packed_dev(mc->enc, mc->d_info, mc->d_cw, (int)nb, (void *)s))) return rc;
         HIPCHK(hipEventRecord(mc->wev[2], s));
-        hipLaunchKernelGGL(mc_channel_points, dim3(mc_blocks(tn)), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_cw, mc->d_rx, (const uint4 *)mc->d_cls, tn, Wn, mc->seed,
-                           d_frame, d_point, (const mc_point_row *)mc->d_points, mc_threshold(mc->parity_ber), mc->d_mag);
+        if (job.weight_key_bits)
+            hipLaunchKernelGGL(mc_channel_weight, dim3(nb), dim3(MC_PAT_LANES), 0, s, (const uint32_t *)mc->d_cw, mc->d_rx, (const uint4 *)mc->d_cls, Wn, mc->seed, (uint64_t)0,
+                               d_frame, d_point, (const mc_stratum_row *)mc->d_points, no_row, job.weight_key_bits, mc_threshold(mc->parity_ber), mc->d_mag);
+        else
+            hipLaunchKernelGGL(mc_channel_points, dim3(mc_blocks(tn)), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_cw, mc->d_rx, (const uint4 *)mc->d_cls, tn, Wn, mc->seed,
+                               d_frame, d_point, (const mc_point_row *)mc->d_points, mc_threshold(mc->parity_ber), mc->d_mag);
         LAUNCHCHK();
         HIPCHK(hipEventRecord(mc->wev[3], s));
         if ((rc = qldpc_load_bits_dev(mc->dec, mc->d_rx, mc->d_mag, mc->d_cls, (int)nb))) return rc;
@@ -981,16 +1057,46 @@ extern "C" int qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc
         for (int q = 0; q < P; q++) { done[(size_t)q] = mc->h_wctr[(size_t)q * MCW_COUNTERS + MC_FRAMES]; fe[(size_t)q] = mc->h_wctr[(size_t)q * MCW_COUNTERS + MC_FRAME_ERRORS]; }
         res->rounds++; res->batches++;
     }
+    for (int q = 0; q < P; q++) res->frames += mc->h_wctr[(size_t)q * MCW_COUNTERS + MC_FRAMES];
+    res->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc_mc_sweep_result *res)
+{
+    if (!mc || !cfg || !res) return QLDPC_EINVAL;
+    memset(res, 0, sizeof(*res));
+    int rc = mc_sweep_args(mc, cfg);
+    if (rc || (rc = mc_sweep_reserve(mc))) return rc;
+    const int P = cfg->n_points;
+    const size_t Wn = (size_t)mc->Wn;
+    /* per sweep: the point rows and the erase rows (fixed set OR prefix), built here once */
+    std::vector<mc_point_row> prow((size_t)P);
+    std::vector<uint32_t> erows((size_t)P * Wn, 0u);
+    bool any_erase = false;
+    for (int q = 0; q < P; q++) {
+        prow[(size_t)q].t_channel = mc_threshold(cfg->points[q].qber);
+        prow[(size_t)q].mag = qldpc_bsc_llr((float)cfg->points[q].qber);
+        uint32_t *row = erows.data() + (size_t)q * Wn;
+        if (mc->n_fixed) memcpy(row, mc->h_fixed.data(), sizeof(uint32_t) * Wn);
+        for (int i = 0; i < cfg->points[q].n_punct; i++) { const int v = cfg->punct_order[i]; row[v >> 5] |= 0x80000000u >> (v & 31); }
+        any_erase = any_erase || mc->n_fixed || cfg->points[q].n_punct > 0;
+    }
+    mc->wstats.assign((size_t)P, qldpc_mc_point_stat());
+    for (int q = 0; q < P; q++) { mc->wstats[(size_t)q].qber = cfg->points[q].qber; mc->wstats[(size_t)q].n_punct = cfg->points[q].n_punct; }
+    const mc_rounds_job job = {P, cfg->chunk ? cfg->chunk : std::min(64, mc->batch), cfg->first_frame, cfg->max_frames, cfg->max_frame_errors, prow.data(),
+                               any_erase ? erows.data() : nullptr, 0, MC_ROWS_SWEEP};
+    std::vector<uint64_t> last((size_t)P, 0);
+    if ((rc = mc_rounds(mc, job, last.data(), res))) return rc;
     for (int q = 0; q < P; q++) {
         const mc_u64 *c = mc->h_wctr + (size_t)q * MCW_COUNTERS;
         qldpc_mc_point_stat &st = mc->wstats[(size_t)q];
         st.frames = c[MC_FRAMES]; st.frame_errors = c[MC_FRAME_ERRORS]; st.bit_errors = c[MC_BIT_ERRORS]; st.undetected = c[MC_UNDETECTED];
         st.not_converged = c[MC_NOT_CONVERGED]; st.iter_sum = c[MC_ITER_SUM]; st.iter_max = c[MC_ITER_MAX];
         st.channel_flips = c[MC_FLIPS]; st.channel_bits = c[MC_CHANNEL_BITS];
-        st.closed_by = st.frames >= max_frames ? QLDPC_MC_CLOSED_MAX_FRAMES : QLDPC_MC_CLOSED_MAX_FE;
-        res->frames += st.frames;
+        st.closed_by = st.frames >= cfg->max_frames ? QLDPC_MC_CLOSED_MAX_FRAMES : QLDPC_MC_CLOSED_MAX_FE;
+        st.last_round = last[(size_t)q];
     }
-    res->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     return QLDPC_OK;
 }
 
@@ -1006,9 +1112,106 @@ extern "C" int qldpc_mc_sweep_hist(qldpc_mc *mc, int point, uint64_t *hist, int 
 {
     if (!mc || cap < 0 || (cap && !hist)) return QLDPC_EINVAL;
     if (point < 0 || (size_t)point >= mc->wstats.size()) { qldpc_set_error("mc_sweep_hist: point=%d, the last sweep had %d", point, (int)mc->wstats.size()); return QLDPC_ESIZE; }
+    if (mc->rows_owner != MC_ROWS_SWEEP) { qldpc_set_error("mc_sweep_hist: the device rows hold a later qldpc_mc_strata run"); return QLDPC_ESTATE; }
     const int bins = std::min(cap, mc->n_ite + 1);
     HIPCHK(hipSetDevice(mc->device));
     HIPCHK(hipStreamSynchronize(mc->dec->stream));
     if (bins) HIPCHK(hipMemcpy(hist, mc->d_whist + (size_t)point * (size_t)(mc->n_ite + 1), sizeof(mc_u64) * (size_t)bins, hipMemcpyDeviceToHost));
+    return mc->n_ite + 1;
+}
+
+/* ------------------------------------------------------------------ fixed-weight error strata ---- */
+
+static int mc_weight_args(const qldpc_mc *mc, const char *who, int weight, int key_bits)
+{
+    if (weight < 0 || (unsigned)weight > mc->channel_vns) { qldpc_set_error("%s: weight=%d outside [0, %u channel VNs]", who, weight, mc->channel_vns); return QLDPC_ESIZE; }
+    if (key_bits < 0 || key_bits > 32) { qldpc_set_error("%s: key_bits=%d outside 0 .. 32", who, key_bits); return QLDPC_ESIZE; }
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_weight_frames_dev(qldpc_mc *mc, uint64_t first_frame, int n_frames, int weight, int key_bits, uint32_t *d_info, uint32_t *d_cw, uint32_t *d_rx)
+{
+    if (!mc || !d_info || (d_rx && !d_cw) || n_frames < 0) return QLDPC_EINVAL;
+    int rc = mc_weight_args(mc, "mc_weight_frames_dev", weight, key_bits);
+    if (rc) return rc;
+    if ((uint64_t)n_frames * (uint64_t)mc->Wn >= (1ull << 31)) { qldpc_set_error("mc_weight_frames_dev: %d frames of N = %d pass 2^31 words", n_frames, mc->N); return QLDPC_ESIZE; }
+    if (n_frames == 0) return QLDPC_OK;
+    HIPCHK(hipSetDevice(mc->device));
+    const hipStream_t s = mc->dec->stream;
+    if ((rc = mc_generate(mc, first_frame, n_frames, 0.0, d_info, d_cw, nullptr, nullptr, s)) || !d_rx) return rc;      /* source and encoder */
+    const mc_stratum_row one = {(uint32_t)weight, 0.0f};
+    hipLaunchKernelGGL(mc_channel_weight, dim3((unsigned)n_frames), dim3(MC_PAT_LANES), 0, s, (const uint32_t *)d_cw, d_rx, (const uint4 *)mc->d_cls, (unsigned)mc->Wn, mc->seed,
+                       first_frame, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (const mc_stratum_row *)nullptr, one,
+                       mc_key_bits(key_bits), mc_threshold(mc->parity_ber), (float *)nullptr);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+/* every argument check of qldpc_mc_strata: nothing is touched before all of them pass */
+static int mc_strata_args(const qldpc_mc *mc, const qldpc_mc_strata_cfg *cfg)
+{
+    if (cfg->reserved[0] || cfg->reserved[1]) { qldpc_set_error("mc_strata: reserved fields %d, %d must be zero", cfg->reserved[0], cfg->reserved[1]); return QLDPC_EINVAL; }
+    if (mc->soft) { qldpc_set_error("mc_strata: a channel table is in force (qldpc_mc_set_channel); error weights are weights of the BSC"); return QLDPC_ESTATE; }
+    if (cfg->n_strata < 1 || cfg->n_strata > QLDPC_MC_SWEEP_MAX_POINTS) { qldpc_set_error("mc_strata: n_strata=%d outside 1 .. %d", cfg->n_strata, QLDPC_MC_SWEEP_MAX_POINTS); return QLDPC_ESIZE; }
+    if (!(cfg->design_qber > 0.0 && cfg->design_qber < 0.5)) { qldpc_set_error("mc_strata: design_qber=%g outside (0, 0.5)", cfg->design_qber); return QLDPC_ESIZE; }
+    if (cfg->chunk < 0 || cfg->chunk > mc->batch) { qldpc_set_error("mc_strata: chunk=%d outside [0, batch=%d]", cfg->chunk, mc->batch); return QLDPC_ESIZE; }
+    if (cfg->max_frames == 0) { qldpc_set_error("mc_strata: max_frames=0"); return QLDPC_ESIZE; }
+    if (!cfg->weights) { qldpc_set_error("mc_strata: a missing array (weights)"); return QLDPC_EINVAL; }
+    for (int q = 0; q < cfg->n_strata; q++) {
+        const int rc = mc_weight_args(mc, "mc_strata", cfg->weights[q], cfg->key_bits);
+        if (rc) return rc;
+    }
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_strata(qldpc_mc *mc, const qldpc_mc_strata_cfg *cfg, qldpc_mc_strata_result *res)
+{
+    if (!mc || !cfg || !res) return QLDPC_EINVAL;
+    memset(res, 0, sizeof(*res));
+    int rc = mc_strata_args(mc, cfg);
+    if (rc || (rc = mc_sweep_reserve(mc))) return rc;
+    const int P = cfg->n_strata;
+    const size_t Wn = (size_t)mc->Wn;
+    /* per call: the stratum rows in the layout of the point rows, and the fixed set as every stratum's erase row */
+    std::vector<mc_point_row> prow((size_t)P);
+    std::vector<uint32_t> erows;
+    const float mag = qldpc_bsc_llr((float)cfg->design_qber);
+    for (int q = 0; q < P; q++) { prow[(size_t)q].t_channel = (uint32_t)cfg->weights[q]; prow[(size_t)q].mag = mag; }
+    if (mc->n_fixed) for (int q = 0; q < P; q++) erows.insert(erows.end(), mc->h_fixed.begin(), mc->h_fixed.begin() + (ptrdiff_t)Wn);
+    mc->tstats.assign((size_t)P, qldpc_mc_stratum_stat());
+    for (int q = 0; q < P; q++) mc->tstats[(size_t)q].weight = cfg->weights[q];
+    const mc_rounds_job job = {P, cfg->chunk ? cfg->chunk : std::min(64, mc->batch), cfg->first_frame, cfg->max_frames, cfg->max_frame_errors, prow.data(),
+                               mc->n_fixed ? erows.data() : nullptr, mc_key_bits(cfg->key_bits), MC_ROWS_STRATA};
+    std::vector<uint64_t> last((size_t)P, 0);
+    if ((rc = mc_rounds(mc, job, last.data(), res))) return rc;
+    for (int q = 0; q < P; q++) {
+        const mc_u64 *c = mc->h_wctr + (size_t)q * MCW_COUNTERS;
+        qldpc_mc_stratum_stat &st = mc->tstats[(size_t)q];
+        st.frames = c[MC_FRAMES]; st.frame_errors = c[MC_FRAME_ERRORS]; st.bit_errors = c[MC_BIT_ERRORS]; st.undetected = c[MC_UNDETECTED];
+        st.not_converged = c[MC_NOT_CONVERGED]; st.iter_sum = c[MC_ITER_SUM]; st.iter_max = c[MC_ITER_MAX];
+        st.channel_flips = c[MC_FLIPS]; st.channel_bits = c[MC_CHANNEL_BITS];
+        st.closed_by = st.frames >= cfg->max_frames ? QLDPC_MC_CLOSED_MAX_FRAMES : QLDPC_MC_CLOSED_MAX_FE;
+        st.last_round = last[(size_t)q];
+    }
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_strata_stats(qldpc_mc *mc, qldpc_mc_stratum_stat *rows, int cap)
+{
+    if (!mc || cap < 0 || (cap && !rows)) return QLDPC_EINVAL;
+    const size_t n = std::min((size_t)cap, mc->tstats.size());
+    if (n) memcpy(rows, mc->tstats.data(), sizeof(qldpc_mc_stratum_stat) * n);
+    return (int)mc->tstats.size();
+}
+
+extern "C" int qldpc_mc_strata_hist(qldpc_mc *mc, int stratum, uint64_t *hist, int cap)
+{
+    if (!mc || cap < 0 || (cap && !hist)) return QLDPC_EINVAL;
+    if (stratum < 0 || (size_t)stratum >= mc->tstats.size()) { qldpc_set_error("mc_strata_hist: stratum=%d, the last run had %d", stratum, (int)mc->tstats.size()); return QLDPC_ESIZE; }
+    if (mc->rows_owner != MC_ROWS_STRATA) { qldpc_set_error("mc_strata_hist: the device rows hold a later qldpc_mc_sweep"); return QLDPC_ESTATE; }
+    const int bins = std::min(cap, mc->n_ite + 1);
+    HIPCHK(hipSetDevice(mc->device));
+    HIPCHK(hipStreamSynchronize(mc->dec->stream));
+    if (bins) HIPCHK(hipMemcpy(hist, mc->d_whist + (size_t)stratum * (size_t)(mc->n_ite + 1), sizeof(mc_u64) * (size_t)bins, hipMemcpyDeviceToHost));
     return mc->n_ite + 1;
 }

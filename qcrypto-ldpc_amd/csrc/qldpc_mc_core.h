@@ -1,7 +1,7 @@
 /*
- * qldpc_mc_core.h -- the frame definition, the quantised-channel definition and the puncture-pattern definition of the Monte-Carlo loop
- * (qldpc_mc_*), plain C, shared by the kernels (qldpc_mc.hip) and by their host mirror (qldpc_mc_host.c), so that the CPU suite runs what
- * the lanes run.
+ * qldpc_mc_core.h -- the frame definition, the quantised-channel definition, the puncture-pattern definition and the fixed-weight frame
+ * definition of the Monte-Carlo loop (qldpc_mc_*), plain C, shared by the kernels (qldpc_mc.hip) and by their host mirror (qldpc_mc_host.c), so
+ * that the CPU suite runs what the lanes run.
  *
  * Frame i (a 64-bit global index) is a pure function of (seed, i): nothing depends on the batch size, the launch shape or the device.
  *
@@ -217,6 +217,67 @@ static inline void mc_vn_list_row(const int *vn, int n, int N, uint32_t *row)
 {
     for (int w = 0; w < (N + 31) / 32; w++) row[w] = 0;
     for (int i = 0; i < n; i++) row[vn[i] >> 5] |= 0x80000000u >> (vn[i] & 31);
+}
+
+/*
+ * Fixed-weight error strata (qldpc_mc_weight_frames_*, qldpc_mc_strata).  Conditioned on the number of flipped channel bits a BSC's flip set
+ * is uniform over the subsets of that size, so the fixed-weight frame (i, w) is defined on the words the BSC already draws:
+ *
+ *   key        u_v = output word v % 4 at counter (v / 4, 1, i_lo, i_hi) -- the word mc_flip_word compares with its threshold;
+ *              u'_v = u_v >> (32 - key_bits), key_bits 1 .. 32 (0 stands for 32; below 32 for TESTS only, which force ties with it)
+ *   flip set   the w VNs of class QLDPC_VN_CHANNEL smallest in the order (u'_v, v): equal keys go to the lower VN; 0 <= w <= channel VNs
+ *   others     QLDPC_VN_PINNED flips iff u_v < floor(parity_ber 2^32), as in the BSC frame; QLDPC_VN_PUNCTURED never
+ *
+ * At key_bits = 32 the BSC set {v channel : u_v < T} is, for every T, the fixed-weight set of its own size, and the sets of two weights of one
+ * frame are nested.  The select is the radix select of the puncture patterns (mc_select_top_shift, mc_select_digit, mc_pattern_takes) over
+ * keys recomputed per pass; it ends with the threshold key T and the number r of channel VNs with u' == T to take, the first r in VN order
+ * (weight 0: T = 0, r = 0, no pass).  The final pass works on whole codeword words: three masks per word, then the first bits of `eq`.
+ */
+
+/* VNs 4 g .. 4 g + 3 of frame `frame`: cls4 = their classes, one per byte, lowest byte first.  Returns bit b = VN 4 g + b is QLDPC_VN_CHANNEL,
+ * bit 4 + b = it is QLDPC_VN_PINNED, and in u their stream-1 words; no Philox call (u = 0) where no VN is a channel VN and none a pinned VN
+ * that can flip (t_pinned = 0: the digit passes need the channel VNs only) */
+MC_FN uint32_t mc_weight_quad(uint64_t seed, uint64_t frame, uint32_t g, uint32_t cls4, uint32_t t_pinned, uint32_t u[4])
+{
+    uint32_t chan = 0, pinned = 0;
+    for (uint32_t b = 0; b < 4; b++) {
+        const uint32_t c = (cls4 >> (8u * b)) & 0xffu;
+        chan |= (uint32_t)(c == 0u) << b;
+        pinned |= (uint32_t)(c == 1u) << b;
+    }
+    if (chan | (t_pinned ? pinned : 0u))
+        mc_philox(g, MC_STREAM_CHANNEL, (uint32_t)frame, (uint32_t)(frame >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), u);
+    else u[0] = u[1] = u[2] = u[3] = 0u;
+    return chan | pinned << 4;
+}
+
+/* codeword word w (VNs 32 w .. 32 w + 31, MSB-first) of frame `frame` against the threshold key T: less = the channel VNs with u' < T, eq = those
+ * with u' == T, pin = the pinned VNs that flip.  cls4 as mc_flip_word takes it; key_bits in 1 .. 32.  8 Philox calls at the most. */
+MC_FN void mc_weight_masks(uint64_t seed, uint64_t frame, uint32_t w, const uint32_t cls4[8], int key_bits, uint32_t T, uint32_t t_pinned,
+                           uint32_t *less, uint32_t *eq, uint32_t *pin)
+{
+    uint32_t l = 0, e = 0, p = 0, u[4];
+    for (uint32_t g = 0; g < 8; g++) {
+        const uint32_t m = mc_weight_quad(seed, frame, 8u * w + g, cls4[g], t_pinned, u);
+        for (uint32_t b = 0; b < 4; b++) {
+            const uint32_t bit = 0x80000000u >> (4u * g + b), k = u[b] >> (32 - key_bits);
+            if ((m >> b) & 1u) { if (k < T) l |= bit; else if (k == T) e |= bit; }
+            else if (((m >> (4u + b)) & 1u) && u[b] < t_pinned) p |= bit;
+        }
+    }
+    *less = l; *eq = e; *pin = p;
+}
+
+/* the selected VNs of a word: all of `less`, and of `eq` in VN order (from the MSB) those that mc_pattern_takes takes, given that equal_before
+ * channel VNs with u' == T precede the word and r of them are taken in all */
+MC_FN uint32_t mc_weight_take(uint32_t less, uint32_t eq, uint32_t T, uint32_t r, uint32_t equal_before)
+{
+    uint32_t sel = less;
+    for (; eq && mc_pattern_takes(T, T, r, equal_before); equal_before++) {
+        const uint32_t top = 0x80000000u >> __builtin_clz(eq);
+        sel |= top; eq ^= top;
+    }
+    return sel;
 }
 
 /*

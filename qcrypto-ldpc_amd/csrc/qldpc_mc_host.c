@@ -1,8 +1,9 @@
 /*
  * qldpc_mc_host.c -- host mirror of the Monte-Carlo frame, channel and pattern definitions (qldpc_mc_philox_host, qldpc_mc_frames_host,
- * qldpc_mc_llr_host, qldpc_mc_pattern_host): the functions of qldpc_mc_core.h that the kernels of qldpc_mc.hip run per lane, here in a loop
- * over frames and words, or over candidates; the table builder of the quantised AWGN channel (qldpc_mc_awgn_table); and the deal of one
- * round of the QBER sweep (qldpc_mc_sweep_deal_host), the function qldpc_mc_sweep itself calls per round.  Plain C, no device.
+ * qldpc_mc_llr_host, qldpc_mc_pattern_host, qldpc_mc_weight_frames_host): the functions of qldpc_mc_core.h that the kernels of qldpc_mc.hip
+ * run per lane, here in a loop over frames and words, or over candidates; the table builder of the quantised AWGN channel
+ * (qldpc_mc_awgn_table); the deal of one round of the QBER sweep (qldpc_mc_sweep_deal_host), the function qldpc_mc_sweep itself calls per
+ * round; and the FER estimate over fixed-weight strata (qldpc_mc_strata_fer_host).  Plain C, no device.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -154,4 +155,105 @@ int qldpc_mc_sweep_deal_host(int n_points, int chunk, int slots, uint64_t max_fr
     }
     if (!done || !frame_errors || !give) return QLDPC_EINVAL;
     return mc_sweep_deal(n_points, chunk, slots, max_frames, max_frame_errors, done, frame_errors, give);
+}
+
+/* the radix select of a fixed-weight frame (qldpc_mc_core.h) in a loop over the quads: per digit one pass that recomputes the keys of the
+ * channel VNs, then the final pass word by word with the running count of equal keys that the kernel forms by a prefix over its lanes */
+int qldpc_mc_weight_frames_host(int K, int N, const int *info_bits_pos, const uint8_t *vn_class, uint64_t seed, double parity_ber, uint64_t first_frame,
+                                int n_frames, const int *weights, int key_bits, uint32_t *info_words, uint32_t *flip_words)
+{
+    if (K < 1 || N < 1 || K > N) { qldpc_set_error("mc_weight_frames_host: K=%d N=%d", K, N); return QLDPC_ESIZE; }
+    if (!(parity_ber >= 0.0 && parity_ber < 1.0)) { qldpc_set_error("mc_weight_frames_host: parity_ber=%g outside [0, 1)", parity_ber); return QLDPC_ESIZE; }
+    if (key_bits < 0 || key_bits > 32) { qldpc_set_error("mc_weight_frames_host: key_bits=%d outside 0 .. 32", key_bits); return QLDPC_ESIZE; }
+    if (n_frames < 0 || (!info_words && !flip_words) || (n_frames > 0 && flip_words && !weights)) return QLDPC_EINVAL;
+    if (n_frames == 0) return QLDPC_OK;
+    const int Wk = (K + 31) / 32, Wn = (N + 31) / 32, kb = mc_key_bits(key_bits);
+    uint8_t *cls = (uint8_t *)malloc(32 * (size_t)Wn);
+    uint32_t *cls4 = (uint32_t *)malloc(4 * 8 * (size_t)Wn);
+    int rc = QLDPC_OK, channel_vns = 0;
+    if (!cls || !cls4) rc = QLDPC_ENOMEM;
+    else if (mc_classes(K, N, info_bits_pos, vn_class, cls, NULL)) {
+        qldpc_set_error("mc_weight_frames_host: info_bits_pos outside [0, %d) or repeated, or a VN class above 2", N);
+        rc = QLDPC_EINVAL;
+    } else {
+        for (int v = 0; v < N; v++) channel_vns += cls[v] == 0;
+        for (int f = 0; f < n_frames && flip_words; f++)
+            if (weights[f] < 0 || weights[f] > channel_vns) {
+                qldpc_set_error("mc_weight_frames_host: weights[%d]=%d outside [0, %d channel VNs]", f, weights[f], channel_vns);
+                rc = QLDPC_ESIZE;
+                break;
+            }
+    }
+    if (rc) { free(cls); free(cls4); return rc; }      /* nothing is written by a refused call */
+    mc_pack_classes(cls, Wn, cls4);
+    if (info_words)
+        for (int f = 0; f < n_frames; f++)
+            for (int j = 0; j < Wk; j++) info_words[(size_t)f * Wk + j] = mc_info_word(seed, first_frame + (uint64_t)f, (uint32_t)j, K);
+    const uint32_t tp = mc_threshold(parity_ber);
+    for (int f = 0; f < n_frames && flip_words; f++) {
+        const uint64_t frame = first_frame + (uint64_t)f;
+        uint32_t prefix = 0, mask = 0, k = (uint32_t)weights[f], u[4];
+        for (int shift = mc_select_top_shift(kb); shift >= 0 && weights[f] > 0; shift -= MC_SEL_BITS) {
+            uint32_t hist[MC_SEL_BINS] = {0};
+            for (uint32_t g = 0; g < 8u * (uint32_t)Wn; g++) {
+                const uint32_t m = mc_weight_quad(seed, frame, g, cls4[g], 0u, u);
+                for (uint32_t b = 0; b < 4; b++) {
+                    const uint32_t key = u[b] >> (32 - kb);
+                    if (((m >> b) & 1u) && (key & mask) == prefix) hist[(key >> shift) & (MC_SEL_BINS - 1)]++;
+                }
+            }
+            prefix |= mc_select_digit(hist, &k) << shift;
+            mask |= (uint32_t)(MC_SEL_BINS - 1) << shift;
+        }
+        uint32_t equal = 0;      /* T = prefix, r = k (weight 0: both 0) */
+        for (int w = 0; w < Wn; w++) {
+            uint32_t less, eq, pin;
+            mc_weight_masks(seed, frame, (uint32_t)w, cls4 + 8 * (size_t)w, kb, prefix, tp, &less, &eq, &pin);
+            flip_words[(size_t)f * Wn + w] = mc_weight_take(less, eq, prefix, k, equal) | pin;
+            equal += (uint32_t)__builtin_popcount(eq);
+        }
+    }
+    free(cls); free(cls4);
+    return QLDPC_OK;
+}
+
+/* Binom(n, q)(w) in double by lgamma */
+static double mc_binom_pmf(int n, int w, double lq, double l1q)
+{
+    return exp(lgamma((double)n + 1.0) - lgamma((double)w + 1.0) - lgamma((double)(n - w) + 1.0) + (double)w * lq + (double)(n - w) * l1q);
+}
+
+int qldpc_mc_strata_fer_host(int n_channel, int n_strata, const int *weights, const uint64_t *frames, const uint64_t *frame_errors, double qber, double out[4])
+{
+    if (n_channel < 1 || n_strata < 1 || n_strata > MC_SWEEP_MAX_POINTS || !(qber > 0.0 && qber < 1.0)) {
+        qldpc_set_error("mc_strata_fer_host: n_channel=%d (at least 1), n_strata=%d (1 .. %d), qber=%g (inside (0, 1))", n_channel, n_strata, MC_SWEEP_MAX_POINTS, qber);
+        return QLDPC_ESIZE;
+    }
+    if (!weights || !frames || !frame_errors || !out) return QLDPC_EINVAL;
+    for (int s = 0; s < n_strata; s++) {
+        if (weights[s] < 0 || weights[s] > n_channel) { qldpc_set_error("mc_strata_fer_host: weights[%d]=%d outside [0, %d]", s, weights[s], n_channel); return QLDPC_ESIZE; }
+        if (s > 0 && weights[s] <= weights[s - 1]) { qldpc_set_error("mc_strata_fer_host: weights[%d]=%d is not above weights[%d]=%d", s, weights[s], s - 1, weights[s - 1]); return QLDPC_EINVAL; }
+        if (frames[s] == 0 || frame_errors[s] > frames[s]) {
+            qldpc_set_error("mc_strata_fer_host: stratum %d has %llu frames and %llu frame errors", s, (unsigned long long)frames[s], (unsigned long long)frame_errors[s]);
+            return QLDPC_ESIZE;
+        }
+    }
+    const double lq = log(qber), l1q = log1p(-qber);
+    double fer = 0.0, var = 0.0, below = 0.0, above = 0.0;
+    for (int w = 0; w < weights[0]; w++) below += mc_binom_pmf(n_channel, w, lq, l1q);
+    for (int w = weights[n_strata - 1] + 1; w <= n_channel; w++) above += mc_binom_pmf(n_channel, w, lq, l1q);
+    for (int s = 0; s < n_strata; s++) {      /* c_s: the stratum's own weight, and its share of the weights between it and both neighbours */
+        double c = mc_binom_pmf(n_channel, weights[s], lq, l1q);
+        if (s > 0)
+            for (int w = weights[s - 1] + 1; w < weights[s]; w++)
+                c += mc_binom_pmf(n_channel, w, lq, l1q) * ((double)(w - weights[s - 1]) / (double)(weights[s] - weights[s - 1]));
+        if (s + 1 < n_strata)
+            for (int w = weights[s] + 1; w < weights[s + 1]; w++)
+                c += mc_binom_pmf(n_channel, w, lq, l1q) * ((double)(weights[s + 1] - w) / (double)(weights[s + 1] - weights[s]));
+        const double p = (double)frame_errors[s] / (double)frames[s];
+        fer += c * p;
+        var += c * c * p * (1.0 - p) / (double)frames[s];
+    }
+    out[0] = fer; out[1] = below; out[2] = above; out[3] = sqrt(var);
+    return QLDPC_OK;
 }

@@ -37,6 +37,12 @@
  *                      row at `ber` punctures parity_bits_to_punct(N, K, min_cr(ber, f)) parity VNs, a prefix of ONE order of the parity VNs
  *                      (bit-reversed positions along the accumulator, so that every prefix is evenly spaced, the spacing the sessions use); a row
  *                      whose count is negative is skipped with the harness's message; -X and -A do not apply)]
+ *                  [-w lo:hi:step[:design_qber] (with -D: fixed-weight error strata, ONE qldpc_mc_strata over the weights lo, lo + step, .. <= hi: every frame of
+ *                      a row flips exactly that many key VNs, the ones with the smallest channel words, and is decoded with |LLR| = ln((1-p)/p) of
+ *                      design_qber (default: the first QBER of -s; the letter -q is the QC file); one row per weight with the weight in the EP
+ *                      column, -E as the stop rule of each row; then one `# strata ber` line per QBER of the -s table with the four numbers of
+ *                      qldpc_mc_strata_fer_host: FER over the simulated weights, the binomial mass below and above them, the standard error;
+ *                      -A, -X and -W do not apply)]
  *                  [-c scale (with -Q 8: quantiser steps per LLR unit, default 8; 1 for LLRs that are integers already, as -A gives them)]
  */
 #include <math.h>
@@ -80,6 +86,8 @@ int main(int argc, char **argv)
     int frames_per_pattern = 64;
     int awgn = 0, awgn_maxq = 31, awgn_punct = 0, zero_source = 0, sweep = 0;      /* -A, -u, -z, -W */
     double ebno_db = 0.0, awgn_rmax = 3.0, quant_scale = 0.0;
+    int strata = 0, w_lo = 0, w_hi = 0, w_step = 1;      /* -w */
+    double design_qber = 0.0;
     const char *pattern_out = NULL;
     double parity_ber = 0.0;      /* > 0: the disclosed parity bits are themselves wrong with this probability (main.cpp (test effect of dirty parities)) */
     double target_eff = 0.0;      /* > 0: puncture parity bits up to min_cr(ber, f), as BS/src/main.cpp:235-333 does */
@@ -88,7 +96,7 @@ int main(int argc, char **argv)
     double ber_min = 0.01, ber_max = 0.03, ber_step = 0.005;
     uint64_t seed = 0;
     const char *g_method = NULL;
-    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:u:c:DRWlvnz")) != -1) {
+    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:u:c:w:DRWlvnz")) != -1) {
         switch (opt) {
         case 'N': N = atoi(optarg); break;
         case 'K': K = atoi(optarg); break;
@@ -114,6 +122,7 @@ int main(int argc, char **argv)
         case 'u': awgn_punct = atoi(optarg); break;
         case 'z': zero_source = 1; break;
         case 'W': sweep = 1; break;
+        case 'w': { const int got = sscanf(optarg, "%d:%d:%d:%lf", &w_lo, &w_hi, &w_step, &design_qber); if (got != 3 && got != 4) { fprintf(stderr, "-w lo:hi:step[:design_qber]\n"); return 2; } strata = 1; break; }
         case 'c': quant_scale = atof(optarg); break;
         case 'o': pattern_out = optarg; break;
         case 'G': g_method = optarg; break;      /* p.G_method (VAR/main.cpp (alist-v1.0.1):135): IDENTITY | LU_DEC; QC = Encoder_LDPC_from_QC ((qc):145) */
@@ -129,6 +138,9 @@ int main(int argc, char **argv)
     if (rule < 0) { fprintf(stderr, "unknown rule %s\n", rule_name); return 2; }
     if (sweep && !on_device) { fprintf(stderr, "qldpc_sim: -W is the sweep on the device and needs -D\n"); return 2; }
     if (sweep && (search_eff != 0.0 || awgn)) { fprintf(stderr, "qldpc_sim: -W sweeps the BSC rows of -s and runs neither with the pattern search (-X) nor with -A\n"); return 2; }
+    if (strata && !on_device) { fprintf(stderr, "qldpc_sim: -w runs the error strata on the device and needs -D\n"); return 2; }
+    if (strata && (search_eff != 0.0 || awgn || sweep)) { fprintf(stderr, "qldpc_sim: -w runs fixed error weights on the BSC's words and runs neither with -X, -A nor -W\n"); return 2; }
+    if (strata && (w_step < 1 || w_lo < 0 || w_hi < w_lo)) { fprintf(stderr, "qldpc_sim: -w lo:hi:step with 0 <= lo <= hi and step >= 1\n"); return 2; }
     if (on_device && ((target_eff > 0.0 && !sweep) || search)) { fprintf(stderr, "qldpc_sim: -e and -R draw a puncture pattern per batch on the host and do not run with -D\n"); return 2; }
     if (max_fe && !on_device) { fprintf(stderr, "qldpc_sim: -E needs -D\n"); return 2; }
     if (search_eff != 0.0 && !on_device) { fprintf(stderr, "qldpc_sim: -X is the pattern search on the device and needs -D\n"); return 2; }
@@ -195,6 +207,38 @@ int main(int argc, char **argv)
                    (unsigned long long)r.frame_errors, (double)r.bit_errors / ((double)r.frames * K), (double)r.frame_errors / (double)r.frames,
                    (double)r.frames * K / (r.decode_ms * 1e-3) / 1e6);
             ber_min = 1.0; ber_max = 0.0;      /* no BSC rows */
+        }
+        if (strata) {      /* one qldpc_mc_strata over the weights, then FER(q) for the QBERs of -s from its rows */
+            const int P = (w_hi - w_lo) / w_step + 1;
+            if (P > QLDPC_MC_SWEEP_MAX_POINTS) { fprintf(stderr, "qldpc_sim: -w gives %d weights, at most %d\n", P, QLDPC_MC_SWEEP_MAX_POINTS); return 2; }
+            int *weights = (int *)malloc(sizeof(int) * (size_t)P);
+            qldpc_mc_stratum_stat *rows = (qldpc_mc_stratum_stat *)malloc(sizeof(*rows) * (size_t)P);
+            uint64_t *fr = (uint64_t *)malloc(sizeof(uint64_t) * 2 * (size_t)P), *fe = fr ? fr + P : NULL;
+            if (!weights || !rows || !fr) return die("mc_strata", QLDPC_ENOMEM);
+            for (int i = 0; i < P; i++) weights[i] = w_lo + i * w_step;
+            qldpc_mc_strata_cfg tcfg;
+            memset(&tcfg, 0, sizeof(tcfg));
+            tcfg.weights = weights; tcfg.n_strata = P; tcfg.design_qber = design_qber > 0.0 ? design_qber : ber_min;
+            tcfg.max_frames = (uint64_t)(frames > 0 ? frames : 0); tcfg.max_frame_errors = max_fe;
+            qldpc_mc_strata_result t;
+            if ((rc = qldpc_mc_strata(mc, &tcfg, &t))) return die("mc_strata", rc);
+            if ((rc = qldpc_mc_strata_stats(mc, rows, P)) < 0) return die("mc_strata_stats", rc);
+            printf("# strata: %d weights in %llu rounds, %llu frames, |LLR| of QBER %.4f; EP = the error weight\n", P, (unsigned long long)t.rounds,
+                   (unsigned long long)t.frames, tcfg.design_qber);
+            for (int i = 0; i < P; i++) {      /* SIM_THR: the run's decode time is shared by the rows, as under -W */
+                printf("  %8d | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", rows[i].weight, (unsigned long long)rows[i].frames, (unsigned long long)rows[i].bit_errors,
+                       (unsigned long long)rows[i].frame_errors, (double)rows[i].bit_errors / ((double)rows[i].frames * K),
+                       (double)rows[i].frame_errors / (double)rows[i].frames, (double)t.frames * K / (t.decode_ms * 1e-3) / 1e6);
+                fr[i] = rows[i].frames; fe[i] = rows[i].frame_errors;
+            }
+            for (double ber = ber_min; ber <= ber_max + 1e-12; ber += ber_step) {
+                double est[4];
+                if ((rc = qldpc_mc_strata_fer_host(K, P, weights, fr, fe, ber, est))) return die("mc_strata_fer_host", rc);
+                printf("# strata ber %.4f: FER %.6e over weights %d .. %d, binomial mass below %.6e, above %.6e, standard error %.6e\n", ber, est[0], w_lo,
+                       weights[P - 1], est[1], est[2], est[3]);
+            }
+            free(weights); free(rows); free(fr);
+            ber_min = 1.0; ber_max = 0.0;      /* the rows are printed */
         }
         if (sweep) {      /* the same table from ONE qldpc_mc_sweep: a point per row */
             const int n_par = N - K;
