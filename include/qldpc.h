@@ -162,6 +162,11 @@ int qldpc_code_e(const qldpc_code *code);
 int qldpc_code_max_cn_degree(const qldpc_code *code);
 int qldpc_code_max_vn_degree(const qldpc_code *code);
 int qldpc_code_is_ira(const qldpc_code *code);     /* 1 if parity VNs K..N-1 form a dual diagonal */
+/* The chain of an IRA code as the posterior form of the flooding run uses it (see qldpc_decoder_flood_post): one word per check c,
+ * byte 0 / 1 = positions of VN K + c - 1 / K + c in the row of check c, byte 2 = position of VN K + c - 1 in the row of check c - 1,
+ * byte 3 = position of VN K + c in the row of check c + 1 (0xff: no such edge).  Verified edge by edge; check degrees <= 27.
+ * Returns 1 and fills tab[M] (NULL: only the verdict), 0 if the graph does not qualify. */
+int qldpc_code_chain_table(const qldpc_code *code, uint32_t *tab);
 /* CN-major edge list, E entries each (pass NULL to skip one). */
 int qldpc_code_export_edges(const qldpc_code *code, int *var, int *chk);
 /* Number of conflict-free layers of the horizontal-layered order, and that order (M entries). */
@@ -231,6 +236,12 @@ void qldpc_decoder_free(qldpc_decoder *dec);
 int qldpc_decoder_set_stream(qldpc_decoder *dec, void *hip_stream);
 int qldpc_decoder_reset(qldpc_decoder *dec);
 size_t qldpc_decoder_device_bytes(const qldpc_decoder *dec);   /* HBM held by this decoder        */
+/* 1 if fixed-iteration flooding runs of this decoder take the posterior form: the variable-node passes write one posterior row per information VN,
+ * the checks rebuild their previous messages from three state rows each and fold the IRA chain in (0.83 x the rows of an iteration, bit-identical
+ * results).  Decided once at creation: FRAMES engine, flooding, fp32 messages, 64-frame groups, MS / OMS / NMS, enable_syndrome = 0, check degrees <= 27
+ * in register-resident buckets, and a graph for which qldpc_code_chain_table returns 1.  Everything else -- early exit included -- runs on explicit
+ * messages.  Environment: QLDPC_FLOOD_POST=0 keeps the explicit messages (A/B measurements and tests). */
+int qldpc_decoder_flood_post(const qldpc_decoder *dec);
 /* Allocate now the buffers the load calls would otherwise allocate on first use (per-frame erasure ballots). */
 int qldpc_decoder_reserve(qldpc_decoder *dec);
 

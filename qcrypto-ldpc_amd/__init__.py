@@ -98,12 +98,14 @@ _sig("qldpc_code_export_edges", C.c_int, [_vp, _ip, _ip])
 _sig("qldpc_code_layer_order", C.c_int, [_vp, _ip, _ip])
 _sig("qldpc_code_vlayer_order", C.c_int, [_vp, _ip, _ip])
 _sig("qldpc_code_syndrome_host", C.c_int, [_vp, _ip, _ip])
+_sig("qldpc_code_chain_table", C.c_int, [_vp, _vp])
 _sig("qldpc_decoder_cfg_default", None, [C.POINTER(DecoderCfg)])
 _sig("qldpc_decoder_create", C.c_int, [_vp, C.c_int, _ip, C.POINTER(DecoderCfg), C.POINTER(_vp)])
 _sig("qldpc_decoder_free", None, [_vp])
 _sig("qldpc_decoder_set_stream", C.c_int, [_vp, _vp])
 _sig("qldpc_decoder_reset", C.c_int, [_vp])
 _sig("qldpc_decoder_device_bytes", C.c_size_t, [_vp])
+_sig("qldpc_decoder_flood_post", C.c_int, [_vp])
 _sig("qldpc_decoder_reserve", C.c_int, [_vp])
 _sig("qldpc_decode_siho", C.c_int, [_vp, _fp, _ip, C.c_int])
 _sig("qldpc_load_llr_dev", C.c_int, [_vp, _vp, C.c_int])
@@ -282,6 +284,15 @@ class Code:
         nat = _chk(_L.qldpc_code_vlayer_order(self._h, order.ctypes.data_as(_ip), ptr.ctypes.data_as(_ip)), "Code.vlayer_order")
         return order, ptr, bool(nat)
 
+    def chain_table(self):
+        """The IRA chain as the posterior form of the flooding run uses it: uint8 [M, 4] = positions of VN K + c - 1 and K + c in the row of check c,
+        of VN K + c - 1 in the row of check c - 1 and of VN K + c in the row of check c + 1 (255: no such edge); None if the graph does not qualify."""
+        tab = np.empty(self.M, np.uint32)
+        ok = _chk(_L.qldpc_code_chain_table(self._h, _vp(tab.ctypes.data)), "Code.chain_table")
+        if not ok:
+            return None
+        return np.stack([(tab >> s) & 0xff for s in (0, 8, 16, 24)], axis=1).astype(np.uint8)
+
     def syndrome(self, x):
         x = _np_i32(x)
         s = np.empty(self.M, np.int32)
@@ -444,6 +455,11 @@ class Decoder:
     @property
     def device_bytes(self):
         return _L.qldpc_decoder_device_bytes(self._h)
+
+    @property
+    def flood_post(self):
+        """fixed-iteration flooding runs of this decoder take the posterior form (qldpc_decoder_flood_post)"""
+        return bool(_chk(_L.qldpc_decoder_flood_post(self._h), "flood_post"))
 
     @property
     def last_run_iterations(self):

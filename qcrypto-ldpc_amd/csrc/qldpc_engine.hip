@@ -22,6 +22,7 @@
 #include "qldpc_kernels_edge.h"
 #include "qldpc_kernels_chain.h"
 #include "qldpc_kernels_compact.h"
+#include "qldpc_kernels_fpost.h"
 
 extern "C" int qldpc_device_count(void)
 {
@@ -186,6 +187,8 @@ extern "C" void qldpc_decoder_free(qldpc_decoder *d)
     for (auto &b : d->vn_buckets) (void)hipFree(b.d_list);
     for (auto &l : d->layer_buckets) for (auto &b : l) { (void)hipFree(b.d_list); (void)hipFree(b.d_rec); }
     for (auto &b : d->vlayer_classes) (void)hipFree(b.d_list);
+    for (auto &b : d->fp_vn_buckets) (void)hipFree(b.d_list);
+    (void)hipFree(d->d_fp_chain); (void)hipFree(d->d_fp_mem);
     (void)hipFree(d->d_vn_chk); (void)hipFree(d->d_gang);
     (void)hipFree(d->d_cn_ptr); (void)hipFree(d->d_cn_tr); (void)hipFree(d->d_cn_var); (void)hipFree(d->d_vn_ptr); (void)hipFree(d->d_info_pos); (void)hipFree(d->d_cn_var_t); (void)hipFree(d->d_vn_tr);
     (void)hipFree(d->d_chain_order); (void)hipFree(d->d_chain_dep); (void)hipFree(d->d_chain_ver); (void)hipFree(d->d_chain_ctl);
@@ -436,6 +439,28 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
         }
         if ((rc = dev_alloc(d, &d->d_a, elems))) return rc;
         if ((rc = dev_alloc(d, &d->d_b, elems))) return rc;
+        /* The posterior form of a fixed-iteration min-sum run (qldpc_kernels_fpost.h): 0.83 x the rows of an iteration, the same floats.  fp32 messages,
+         * 64-frame groups, MS / OMS / NMS, no syndrome test (early exit needs the ballots of every VN after every iteration and stays on the kernels
+         * above), every check in a register-resident bucket with degree <= 27, and the IRA chain verified edge by edge.  QLDPC_FLOOD_POST=0 keeps the
+         * explicit messages (A/B measurements, tests).  var_to_chk is not used by this form: posteriors and state live in its allocation where they fit. */
+        {
+            bool ok = !d->msg_i8 && !d->msg_half && d->V == 1 && family_of(cfg->rule) == QK_FAM_MS && !cfg->enable_syndrome && code->max_dc <= QK_FP_DCMAX;
+            for (auto &b : d->cn_buckets) ok = ok && b.cap > 0;
+            if (const char *e = getenv("QLDPC_FLOOD_POST")) ok = ok && atoi(e) != 0;
+            std::vector<uint32_t> tab;
+            if (ok) { tab.resize((size_t)d->M); ok = qldpc_code_chain_table(code, tab.data()) == 1; }
+            if (ok) {
+                d->ira_K = code->ira_K;
+                if ((rc = make_buckets(d, code->vn_ptr, nullptr, d->ira_K, VN_CAPS, 2, d->fp_vn_buckets))) return rc;
+                if ((rc = dev_alloc(d, &d->d_fp_chain, (size_t)d->M))) return rc;
+                HIPCHK(hipMemcpy(d->d_fp_chain, tab.data(), sizeof(uint32_t) * (size_t)d->M, hipMemcpyHostToDevice));
+                const size_t post_n = G * d->N * 64, st_n = G * d->M * (64 * QK_FP_ROWS);
+                float *base = d->d_a;
+                if (post_n + 2 * st_n > elems) { if ((rc = dev_alloc(d, &d->d_fp_mem, post_n + 2 * st_n))) return rc; base = d->d_fp_mem; }
+                d->fp_post = base; d->fp_st[0] = base + post_n; d->fp_st[1] = base + post_n + st_n;
+                d->fpost = 1;
+            }
+        }
     } else if (d->msg_i8) {
         if ((rc = dev_alloc(d, &d->d_llr8, G * d->N * 64))) return rc;
         if ((rc = dev_alloc(d, &d->d_a, G * d->N * 64))) return rc;      /* post8 */
@@ -538,6 +563,7 @@ static int ensure_llr(qldpc_decoder *d)
 
 extern "C" int qldpc_decoder_set_stream(qldpc_decoder *d, void *s) { if (!d) return QLDPC_EINVAL; d->stream = (hipStream_t)s; return QLDPC_OK; }
 extern "C" size_t qldpc_decoder_device_bytes(const qldpc_decoder *d) { return d ? d->bytes : 0; }
+extern "C" int qldpc_decoder_flood_post(const qldpc_decoder *d) { return d ? d->fpost : (int)QLDPC_EINVAL; }
 extern "C" int qldpc_last_run_iterations(const qldpc_decoder *d) { return d ? d->last_iters : (int)QLDPC_EINVAL; }
 
 /* early-exit bookkeeping of the last run (FRAMES engine): out[0] = lane-iterations executed (groups that ran an iteration x frames
@@ -689,6 +715,61 @@ static int cn_pass(qldpc_decoder *d, bool first = false)
     d->remap_src = nullptr;      /* chk_to_var is in the current generation's layout now, and so is everything after it */
     return QLDPC_OK;
 }
+/* ---- the posterior form of the flooding run (qldpc_kernels_fpost.h) ----
+ * Algorithmic bytes stay what DESIGN section 4 prices: 2 E rows for a check pass, E + N for a _compute_post.  Moved is what the kernels move: a check pass
+ * gathers one posterior row and writes one message row per information edge and reads and writes its own three state rows (the neighbours' rows, cache
+ * hits for three waves in four, are not counted); the first one reads channel values instead of posteriors and no state.  A posterior pass reads the
+ * information edges' message rows and writes one row per information VN (in between) or only ballots (closing the run). */
+static double fp_info_edges(const qldpc_decoder *d) { return (double)d->E - (2.0 * d->M - 1.0); }
+static double fp_chan(const qldpc_decoder *d, double vns) { return d->llr_coded ? vns / 8.0 : vns * 4.0; }
+static double moved_cn_fpost(const qldpc_decoder *d, bool first)
+{
+    const double Ei = fp_info_edges(d), st = (double)QK_FP_ROWS * d->M * 4.0;
+    if (first) return (Ei * 4.0 + st + fp_chan(d, d->N)) * live_frames(d);
+    return (2.0 * Ei * 4.0 + 2.0 * st + fp_chan(d, d->M)) * live_frames(d);
+}
+static double moved_vn_fpost(const qldpc_decoder *d, bool rows_out, bool ballots)
+{
+    return (fp_info_edges(d) * 4.0 + fp_chan(d, d->ira_K) + (rows_out ? d->ira_K * 4.0 : 0.0) + (ballots ? d->ira_K / 4.0 : 0.0)) * live_frames(d);
+}
+static int cn_pass_fpost(qldpc_decoder *d, int ite)
+{
+    prof_scope ps(d, KS_CN, bytes_cn(d), moved_cn_fpost(d, ite == 0));
+    for (auto &b : d->cn_buckets) { qldpc_launch_cn_fpost(d, b, ite); LAUNCHCHK(); }
+    d->fp_last = ite & 1;
+    return QLDPC_OK;
+}
+/* _compute_post over the information VNs: in between iterations it leaves the posterior rows the next check pass gathers and no ballots */
+static int vn_pass_fpost(qldpc_decoder *d, float *post_out, bool between)
+{
+    prof_scope ps(d, KS_VN, bytes_vn(d, QK_VN_POST), moved_vn_fpost(d, post_out != nullptr, !between));
+    d->fp_between = between ? 1 : 0;
+    for (auto &b : d->fp_vn_buckets) { qldpc_launch_vn<1, QK_VN_POST>(d, b, post_out); LAUNCHCHK(); }
+    d->fp_between = 0;
+    return QLDPC_OK;
+}
+/* ... and over the chain VNs, from the final check state (own rows counted, as in the check pass) */
+static int close_fpost(qldpc_decoder *d, float *post_out)
+{
+    const double b = ((double)QK_FP_ROWS * d->M * 4.0 + fp_chan(d, d->M) + (post_out ? d->M * 4.0 : 0.0) + d->M / 4.0) * live_frames(d);
+    prof_scope ps(d, KS_VN, b, b);
+    qldpc_launch_fpost_close(d, post_out);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+static int run_flooding_post(qldpc_decoder *d)
+{
+    int rc;
+    const int n_ite = d->cfg.n_ite;
+    for (int ite = 0; ite < n_ite; ite++) {
+        if ((rc = cn_pass_fpost(d, ite))) return rc;      /* iteration 0 rebuilds (Y + 0) - 0 itself: no _initialize_var_to_chk in front of it */
+        if (ite < n_ite - 1 && (rc = vn_pass_fpost(d, d->fp_post, true))) return rc;
+    }
+    d->last_iters = n_ite;
+    if ((rc = vn_pass_fpost(d, nullptr, false))) return rc;
+    return close_fpost(d, nullptr);
+}
+
 template <int V>
 static int synd_pass(qldpc_decoder *d, const u64 *mask, int skip_done)
 {
@@ -886,6 +967,7 @@ static int early_exit_step(qldpc_decoder *d, int ite_done, bool track_live, bool
 template <int V>
 static int run_flooding(qldpc_decoder *d)
 {
+    if constexpr (V == 1) { if (d->fpost) return run_flooding_post(d); }
     int rc;
     const int n_ite = d->cfg.n_ite;
     /* coded LLRs (fp32 / binary16 messages): the first check pass rebuilds its inputs itself, so _initialize_var_to_chk of
@@ -1825,7 +1907,8 @@ extern "C" int qldpc_fetch_post_dev(qldpc_decoder *d, float *d_post_out)
     const float *src;
     if (d->cfg.schedule == QLDPC_SCHED_FLOODING) {
         if (!d->d_post) { if ((rc = dev_alloc(d, &d->d_post, (size_t)d->G * d->N * d->FG))) return rc; }
-        if ((rc = with_v(d, [&](auto v) { return vn_pass<v(), QK_VN_POST>(d, d->d_post); }))) return rc;
+        if (d->fpost) { if ((rc = vn_pass_fpost(d, d->d_post, false)) || (rc = close_fpost(d, d->d_post))) return rc; }
+        else if ((rc = with_v(d, [&](auto v) { return vn_pass<v(), QK_VN_POST>(d, d->d_post); }))) return rc;
         src = d->d_post;
     } else if (d->msg_i8) {
         if (!d->d_post) { if ((rc = dev_alloc(d, &d->d_post, (size_t)d->G * d->N * d->FG))) return rc; }

@@ -67,6 +67,15 @@ struct qldpc_decoder {
     /* decoder gangs (qldpc_kernels_gang.h): what a solo layer launch passes as arguments, once per (layer, bucket), written when the decoder first
      * joins a gang; the entry of layer_buckets[l][k] is d_gang[gang_off[l] + k] */
     qk_gang_entry *d_gang; std::vector<int> gang_off;
+    /* the posterior form of a fixed-iteration flooding min-sum run (qldpc_kernels_fpost.h), decided once at creation: the VN passes write one
+     * posterior row per information VN, the checks keep three state rows each (two buffers, ping-pong by iteration parity) and fold the IRA chain in */
+    int fpost, ira_K;
+    std::vector<bucket> fp_vn_buckets;   /* the information VNs 0 .. ira_K - 1 */
+    uint32_t *d_fp_chain;            /* [M] chain table (qldpc_code_chain_table) */
+    float *fp_post, *fp_st[2];       /* [G][N][64] posteriors, 2 x [G][M][3][64] check state: carved out of d_a (var_to_chk is not used) where they fit, else d_fp_mem */
+    float *d_fp_mem;
+    int fp_last;                     /* the state buffer the last check pass of the run wrote */
+    int fp_between;                  /* set around the in-between posterior passes: nobody reads their ballots */
     int layer_first;                 /* layered fp32 run, sweep 0, messages not frozen: the layer kernels treat the messages as zero instead of reading a cleared array */
     /* state */
     float *d_llr, *d_a, *d_b;        /* flooding: a = v2c, b = c2v ; layered: a = post, b = msg */
@@ -160,6 +169,7 @@ static inline qk_coded_llr coded_llr_of(const qldpc_decoder *d) { return qk_code
 /* the in-between variable-node passes only need to leave ballots when the syndrome test reads them; _compute_post always does */
 static inline int want_ballots(const qldpc_decoder *d, int mode)
 {
+    if (mode == QK_VN_POST && d->fp_between) return 0;
     if (mode == QK_VN_POST) return 1 | (d->post_closes_run ? 2 : 0);      /* bit 1: skip groups that converged as a whole (their ballots are final) */
     return d->cfg.enable_syndrome ? 1 : 0;
 }
@@ -195,6 +205,9 @@ template <int V> void qldpc_launch_cn(qldpc_decoder *d, const bucket &b, bool fi
 template <int V> void qldpc_launch_layer(qldpc_decoder *d, const bucket &b);
 template <int V> void qldpc_launch_vlayer(qldpc_decoder *d, const bucket &b);
 void qldpc_launch_layer_chain(qldpc_decoder *d, int sweep);      /* V = 1 only */
+/* posterior form of the flooding run (V = 1 only): the check pass of iteration `ite` over one bucket, and the closing pass over the chain VNs */
+void qldpc_launch_cn_fpost(qldpc_decoder *d, const bucket &b, int ite);
+void qldpc_launch_fpost_close(qldpc_decoder *d, float *post_out);
 int qldpc_chain_resident_blocks(qldpc_decoder *d);
 template <int V, int MODE> void qldpc_launch_vn(qldpc_decoder *d, const bucket &b, float *post_out);
 #define QLDPC_DECLARE_LAUNCH(V)                                                                   \

@@ -595,6 +595,47 @@ int qldpc_code_max_cn_degree(const qldpc_code *c) { return c ? c->max_dc : QLDPC
 int qldpc_code_max_vn_degree(const qldpc_code *c) { return c ? c->max_dv : QLDPC_EINVAL; }
 int qldpc_code_is_ira(const qldpc_code *c) { return c ? (c->ira_K > 0) : QLDPC_EINVAL; }
 
+/*
+ * The accumulator chain as the posterior form of the flooding run needs it (qldpc_kernels_fpost.h): one word per check c,
+ *   byte 0 = position of VN K + c - 1 in the row of check c (0xff: none, check 0), byte 1 = position of VN K + c in it,
+ *   byte 2 = position of VN K + c - 1 in the row of check c - 1, byte 3 = position of VN K + c in the row of check c + 1 (0xff: none),
+ * with K = ira_K.  The structure is verified here and not taken from the flag: VN K + c on exactly checks c (slot 0) and c + 1 (slot 1),
+ * VN K + M - 1 on check M - 1 only, no other VN >= K in a row, every check degree <= 27 (the packed state word: 27 sign bits + 5 index bits).
+ * Returns 1 and fills tab[M] (may be NULL), 0 if the graph does not qualify.
+ */
+int qldpc_code_chain_table(const qldpc_code *g, uint32_t *tab)
+{
+    if (!g) return QLDPC_EINVAL;
+    const int K = g->ira_K, M = g->M;
+    if (K <= 0 || K + M != g->N || g->max_dc > 27) return 0;
+    for (int c = 0; c < M; c++) {
+        const int v = K + c, d = g->vn_ptr[v + 1] - g->vn_ptr[v];
+        const int *s = g->vn_chk + g->vn_ptr[v];
+        if (c < M - 1 ? (d != 2 || s[0] != c || s[1] != c + 1) : (d != 1 || s[0] != c)) return 0;
+    }
+    int prev_r = 0xff;      /* position of VN K + c - 1 in the row of check c - 1 */
+    for (int c = 0; c < M; c++) {
+        const int b = g->cn_ptr[c], deg = g->cn_ptr[c + 1] - b;
+        int l = 0xff, r = 0xff, nr = 0xff;
+        for (int k = 0; k < deg; k++) {
+            const int v = g->cn_var[b + k];
+            if (v < K) continue;
+            if (c > 0 && v == K + c - 1 && l == 0xff) l = k;
+            else if (v == K + c && r == 0xff) r = k;
+            else return 0;
+        }
+        if (r == 0xff || (c > 0 && l == 0xff)) return 0;
+        if (c + 1 < M) {
+            const int b1 = g->cn_ptr[c + 1], d1 = g->cn_ptr[c + 2] - b1;
+            for (int k = 0; k < d1; k++) if (g->cn_var[b1 + k] == K + c) { nr = k; break; }
+            if (nr == 0xff) return 0;
+        }
+        if (tab) tab[c] = (uint32_t)l | ((uint32_t)r << 8) | ((uint32_t)(c > 0 ? prev_r : 0xff) << 16) | ((uint32_t)nr << 24);
+        prev_r = r;
+    }
+    return 1;
+}
+
 int qldpc_code_export_edges(const qldpc_code *c, int *var, int *chk)
 {
     if (!c) return QLDPC_EINVAL;

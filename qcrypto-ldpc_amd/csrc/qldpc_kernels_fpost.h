@@ -1,0 +1,202 @@
+/*
+ * qldpc_kernels_fpost.h -- the posterior form of a fixed-iteration flooding min-sum run (fp32, 64-frame groups, IRA codes).
+ *
+ * The flooding recursion (Decoder_LDPC_BP_flooding::_decode_single_ite / _initialize_var_to_chk) moves 4 E message rows per
+ * iteration: var_to_chk written and read, chk_to_var written and read.  Three facts let a run move fewer rows and still compute
+ * the very same floats:
+ *
+ *  1. var_to_chk[slot] = tmp - chk_to_var[slot] with tmp = Y + sum of the VN's messages in slot order.  The variable-node pass
+ *     therefore only writes tmp (qk_vn_flood in QK_VN_POST mode: one row per VN); the check forms tmp - (its own previous message)
+ *     itself: the same subtraction on the same operands.
+ *  2. A check rebuilds its own previous messages from a compressed state, as the layered sweeps do (qldpc_kernels_cst.h).  For
+ *     MS / OMS / NMS a tie min1 == min2 makes cst1 and cst2 the same float (qk_acc<QK_FAM_MS>::finish), so "which edges took
+ *     cst1" shrinks to the index of ONE edge whose magnitude was min1: every other edge takes cst2, which on a tie is the same
+ *     value.  Index (5 bits) and the dc sign bits share one word for dc <= 27: THREE 256-byte rows per check,
+ *         {cst1, cst2, packed}[64]     packed: bit k = message of edge k is negative, bits 27..31 = the edge that took cst1.
+ *     Nobody but the owner needs a check's state -- except:
+ *  3. The accumulator chain of an IRA code: VN K + c sits on checks c and c + 1 only (VN K + M - 1 on check M - 1 only).  Its two
+ *     messages belong to two adjacent checks, which adjacent wavefronts of one workgroup work on at the same time, so check c
+ *     works out the totals of its two chain VNs from its own state and the states of checks c - 1 and c + 1 (cache hits, apart
+ *     from the first and last wave of a workgroup).  The variable-node pass skips the chain VNs altogether: their posterior rows
+ *     and their chk_to_var rows are never written or read.
+ *
+ * The state is read from one buffer and written to another (ping-pong by iteration parity): a neighbour may still be reading the
+ * old one.  State loads are ordinary cached loads -- the neighbour's copy in the cache is the point.  The first iteration takes all
+ * state as zero without reading it (every message +0.0), which gives (Y + 0) - 0 on every edge as qk_cn_flood<FIRST> does.
+ *
+ * After the last check pass qk_fpost_close gives the chain VNs their ballots (and posterior rows on request) from the final state.
+ */
+#ifndef QLDPC_KERNELS_FPOST_H
+#define QLDPC_KERNELS_FPOST_H
+
+#include "qldpc_kernels.h"
+
+#define QK_FP_ROWS 3           /* {cst1, cst2, packed} */
+#define QK_FP_DCMAX 27         /* sign bits 0..26, index in bits 27..31 */
+#define QK_FP_NONE 0xffu       /* chain table: no such edge */
+/* chain table, one word per check c (qldpc_code_chain_table): byte 0 = position of VN K + c - 1 in the row of check c, byte 1 = position of
+ * VN K + c in it, byte 2 = position of VN K + c - 1 in the row of check c - 1, byte 3 = position of VN K + c in the row of check c + 1 */
+
+/* the message of edge k for this lane's frame, rebuilt from a check's state: same magnitude bits, same sign bit (a -0.0 stays a -0.0) */
+__device__ __forceinline__ float qk_fp_msg(uint32_t w, int k, float c1, float c2)
+{
+    return qk_withsign(((int)(w >> 27) == k) ? c1 : c2, (w >> k) << 31);
+}
+
+/* Y of VN v for this lane's frame: rebuilt from the coded form or read from the LLR array (a row other checks gather too: cached) */
+template <bool CODED>
+__device__ __forceinline__ float qk_fp_y(const float *__restrict__ yin, const qk_coded_llr &coded, int g, int v, int N, int lane, const float (&mg)[1], const int (&nc)[1])
+{
+    if constexpr (CODED) {
+        float y[1];
+        qk_coded_y<1>(y, coded, g, v, N, lane, mg, nc);
+        return y[0];
+    } else return yin[(size_t)v * 64];
+}
+
+/*
+ * The check pass.  One wavefront per check, indices prefetched with back-to-back scalar loads as in qk_cn_flood.
+ *   info edge k:   x = post[v_k] - (own previous message k)
+ *   chain edges:   tmp = Y + ((0.0f + m[slot 0]) + m[slot 1]) in the VN's slot order (ascending check: the lower check is slot 0),
+ *                  exactly as qk_vn_flood sums; x = tmp - own.  The last VN has degree 1: tmp = Y + (0.0f + own).
+ * then the fold of qk_acc<QK_FAM_MS>, the info edges' outputs CN-major as qk_cn_flood stores them, and the new state.
+ */
+template <int DCMAX, bool FIRST, bool CODED>
+__global__ __launch_bounds__(QK_THREADS) void qk_cn_fpost(const float *__restrict__ post, const float *__restrict__ llr, float *__restrict__ c2v,
+                                                          const float *st_in, float *st_out,
+                                                          const int *__restrict__ list, int n_list,
+                                                          const int *__restrict__ cn_ptr, const int *__restrict__ cn_var, const uint32_t *__restrict__ chain,
+                                                          size_t group_stride, const u64 *__restrict__ done, qk_rule rule, const u64 *__restrict__ synd, int M, int N,
+                                                          qk_coded_llr coded)
+{
+    static_assert(DCMAX > 0 && DCMAX <= QK_FP_DCMAX, "sign bits and the index share one word");
+    const int g = blockIdx.y;
+    if (qk_group_done<1>(done, g)) return;      /* a group of padding frames only */
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int i = blockIdx.x * QK_WAVES + wave;
+    if (i >= n_list) return;
+    const int c = list[i];
+    const int b = cn_ptr[c];
+    const int deg = cn_ptr[c + 1] - b;
+    const uint32_t ch = chain[c];
+    const int lpos = (int)(ch & 0xffu), rpos = (int)((ch >> 8) & 0xffu), lnb = (int)((ch >> 16) & 0xffu), rnb = (int)(ch >> 24);
+    int vid[DCMAX];
+#pragma unroll
+    for (int k = 0; k < DCMAX; k++) vid[k] = cn_var[b + k];      /* padded by QK_IDX_PAD */
+
+    const float *pg = post + (size_t)g * N * 64 + lane;
+    const float *yin = llr + (size_t)g * N * 64 + lane;
+    const size_t srow = ((size_t)g * M + c) * (64 * QK_FP_ROWS) + lane;
+    float x[DCMAX];
+    if constexpr (!FIRST) {
+#pragma unroll
+        for (int k = 0; k < DCMAX; k++)
+            if (k < deg && k != lpos && k != rpos) x[k] = pg[(size_t)vid[k] * 64];
+    }
+    /* own state, and the states of checks c - 1 and c + 1 where a chain VN is shared with them */
+    float c1 = 0.0f, c2 = 0.0f, lc1 = 0.0f, lc2 = 0.0f, rc1 = 0.0f, rc2 = 0.0f;
+    uint32_t w = 0u, lw = 0u, rw = 0u;
+    if constexpr (!FIRST) {
+        const float *s = st_in + srow;
+        const uint32_t *sw = reinterpret_cast<const uint32_t *>(s);
+        c1 = s[0]; c2 = s[64]; w = sw[128];
+        if (lpos != (int)QK_FP_NONE && c > 0) { lc1 = s[-192]; lc2 = s[-128]; lw = sw[-64]; }         /* the rows of check c - 1 */
+        if (rnb != (int)QK_FP_NONE && c + 1 < M) { rc1 = s[192]; rc2 = s[256]; rw = sw[320]; }        /* the rows of check c + 1 */
+    }
+    float mg[1] = {0.0f};
+    int nc[1] = {0};
+    if constexpr (CODED) { mg[0] = coded.fmag[(size_t)g * 64 + lane]; nc[0] = coded.fnch[(size_t)g * 64 + lane]; }
+    if constexpr (FIRST) {
+#pragma unroll
+        for (int k = 0; k < DCMAX; k++)
+            if (k < deg && k != lpos && k != rpos) x[k] = qk_first_v2c(qk_fp_y<CODED>(yin, coded, g, vid[k], N, lane, mg, nc), (const float *)nullptr);
+    } else {
+#pragma unroll
+        for (int k = 0; k < DCMAX; k++)
+            if (k < deg && k != lpos && k != rpos) x[k] = x[k] - qk_fp_msg(w, k, c1, c2);
+    }
+    /* the two chain VNs (wave-uniform positions; a position DCMAX or beyond never matches below) */
+    float xl = 0.0f, xr = 0.0f;
+    if (lpos != (int)QK_FP_NONE) {      /* VN K + c - 1: slot 0 = check c - 1, slot 1 = this check */
+        int vl = 0;
+#pragma unroll
+        for (int k = 0; k < DCMAX; k++) vl = (k == lpos) ? vid[k] : vl;
+        const float y = qk_fp_y<CODED>(yin, coded, g, vl, N, lane, mg, nc);
+        const float own = qk_fp_msg(w, lpos, c1, c2), nb = qk_fp_msg(lw, lnb, lc1, lc2);
+        const float tmp = y + ((0.0f + nb) + own);
+        xl = tmp - own;
+    }
+    if (rpos != (int)QK_FP_NONE) {      /* VN K + c: slot 0 = this check, slot 1 = check c + 1 (none for the last VN) */
+        int vr = 0;
+#pragma unroll
+        for (int k = 0; k < DCMAX; k++) vr = (k == rpos) ? vid[k] : vr;
+        const float y = qk_fp_y<CODED>(yin, coded, g, vr, N, lane, mg, nc);
+        const float own = qk_fp_msg(w, rpos, c1, c2);
+        float sum = 0.0f + own;
+        if (rnb != (int)QK_FP_NONE) sum = sum + qk_fp_msg(rw, rnb, rc1, rc2);
+        const float tmp = y + sum;
+        xr = tmp - own;
+    }
+    qk_acc<QK_FAM_MS> acc;
+    acc.begin();
+    if (synd) acc.sign = (uint32_t)((synd[(size_t)g * M + c] >> lane) & 1ull) << 31;
+#pragma unroll
+    for (int k = 0; k < DCMAX; k++)
+        if (k < deg) {
+            if (k == lpos) x[k] = xl;
+            if (k == rpos) x[k] = xr;
+            acc.in(x[k]);
+        }
+    acc.finish(rule);
+    float *cout = c2v + (size_t)g * group_stride + lane;
+    uint32_t nw = 0u, idx = 0u;
+#pragma unroll
+    for (int k = 0; k < DCMAX; k++)
+        if (k < deg) {
+            const float o = acc.out(x[k], rule);
+            if (k != lpos && k != rpos) __builtin_nontemporal_store(o, cout + (size_t)(b + k) * 64);      /* CN-major, streamed: read once by the variable-node pass */
+            nw |= (qk_bits(o) >> 31) << k;
+        }
+#pragma unroll
+    for (int k = DCMAX - 1; k >= 0; k--)
+        if (k < deg) idx = (fabsf(x[k]) == acc.min1) ? (uint32_t)k : idx;      /* descending k: the first edge at the minimum stays */
+    float *so = st_out + srow;
+    so[0] = acc.cst1; so[64] = acc.cst2; reinterpret_cast<uint32_t *>(so)[128] = nw | (idx << 27);
+}
+
+/*
+ * _compute_post of the chain VNs after the last check pass: tmp from the final state of checks c and c + 1, the sgn / hard ballots
+ * qk_vn_flood leaves (padding frames keep the bits they had) and, on request, the posterior row.  One wavefront per chain VN.
+ */
+template <bool CODED>
+__global__ __launch_bounds__(QK_THREADS) void qk_fpost_close(const float *__restrict__ st, const float *__restrict__ llr, const uint32_t *__restrict__ chain,
+                                                             u64 *__restrict__ sgn, u64 *__restrict__ hard, float *__restrict__ post_out,
+                                                             int M, int N, int K, const u64 *__restrict__ done, qk_coded_llr coded)
+{
+    const int g = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = blockIdx.x * QK_WAVES + wave;
+    if (c >= M) return;
+    const int v = K + c;
+    const int rpos = (int)((chain[c] >> 8) & 0xffu);
+    const int npos = (c + 1 < M) ? (int)(chain[c + 1] & 0xffu) : (int)QK_FP_NONE;
+    const float *s = st + ((size_t)g * M + c) * (64 * QK_FP_ROWS) + lane;
+    const uint32_t *sw = reinterpret_cast<const uint32_t *>(s);
+    float sum = 0.0f + qk_fp_msg(sw[128], rpos, s[0], s[64]);
+    if (npos != (int)QK_FP_NONE) sum = sum + qk_fp_msg(sw[320], npos, s[192], s[256]);
+    float mg[1] = {0.0f};
+    int nc[1] = {0};
+    if constexpr (CODED) { mg[0] = coded.fmag[(size_t)g * 64 + lane]; nc[0] = coded.fnch[(size_t)g * 64 + lane]; }
+    const float tmp = qk_fp_y<CODED>(llr + (size_t)g * N * 64 + lane, coded, g, v, N, lane, mg, nc) + sum;
+    u64 sb = __ballot((qk_bits(tmp) >> 31) != 0);
+    u64 hb = __ballot(!(tmp >= 0.0f));
+    const size_t bi = (size_t)g * N + v;
+    const u64 dm = done[g];
+    if (dm) { sb = (sb & ~dm) | (sgn[bi] & dm); hb = (hb & ~dm) | (hard[bi] & dm); }
+    if (lane == 0) { sgn[bi] = sb; hard[bi] = hb; }
+    if (post_out) post_out[((size_t)g * N + v) * 64 + lane] = tmp;
+}
+
+#endif /* QLDPC_KERNELS_FPOST_H */

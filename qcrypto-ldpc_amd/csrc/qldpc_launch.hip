@@ -213,6 +213,43 @@ template void qldpc_launch_vn<QL_V, QK_VN_NORMAL>(qldpc_decoder *, const bucket 
 template void qldpc_launch_vn<QL_V, QK_VN_POST>(qldpc_decoder *, const bucket &, float *);
 
 #if QL_V == 1
+#include "qldpc_kernels_fpost.h"
+
+/* the posterior form of the flooding run (qldpc_kernels_fpost.h): iteration `ite` reads the state buffer of the other parity and writes its own */
+template <int DCMAX, bool FIRST>
+static void launch_cn_fpost_one(qldpc_decoder *d, const bucket &b, int ite)
+{
+    dim3 grid((unsigned)grid_x(b.n, 1), (unsigned)d->G);
+    const float *st_in = d->fp_st[(ite & 1) ^ 1];
+    float *st_out = d->fp_st[ite & 1];
+    if (d->llr_coded)
+        hipLaunchKernelGGL((qk_cn_fpost<DCMAX, FIRST, true>), grid, dim3(QK_THREADS), 0, d->stream, (const float *)d->fp_post, (const float *)nullptr, d->d_b, st_in, st_out, b.d_list, b.n,
+                           d->d_cn_ptr, d->d_cn_var, d->d_fp_chain, (size_t)d->E * 64, d->d_done, rule_of(d), target_synd(d), d->M, d->N, coded_llr_of(d));
+    else
+        hipLaunchKernelGGL((qk_cn_fpost<DCMAX, FIRST, false>), grid, dim3(QK_THREADS), 0, d->stream, (const float *)d->fp_post, (const float *)d->d_llr, d->d_b, st_in, st_out, b.d_list, b.n,
+                           d->d_cn_ptr, d->d_cn_var, d->d_fp_chain, (size_t)d->E * 64, d->d_done, rule_of(d), target_synd(d), d->M, d->N, qk_coded_llr{});
+}
+void qldpc_launch_cn_fpost(qldpc_decoder *d, const bucket &b, int ite)
+{
+    /* the host admitted only register-resident buckets and degrees <= QK_FP_DCMAX: the bucket of cap 40 holds degrees 21 .. 27 here */
+    switch (b.cap) {
+    case 8: ite == 0 ? launch_cn_fpost_one<8, true>(d, b, ite) : launch_cn_fpost_one<8, false>(d, b, ite); break;
+    case 12: ite == 0 ? launch_cn_fpost_one<12, true>(d, b, ite) : launch_cn_fpost_one<12, false>(d, b, ite); break;
+    case 20: ite == 0 ? launch_cn_fpost_one<20, true>(d, b, ite) : launch_cn_fpost_one<20, false>(d, b, ite); break;
+    default: ite == 0 ? launch_cn_fpost_one<QK_FP_DCMAX, true>(d, b, ite) : launch_cn_fpost_one<QK_FP_DCMAX, false>(d, b, ite); break;
+    }
+}
+void qldpc_launch_fpost_close(qldpc_decoder *d, float *post_out)
+{
+    dim3 grid((unsigned)grid_x(d->M, 1), (unsigned)d->G);
+    if (d->llr_coded)
+        hipLaunchKernelGGL((qk_fpost_close<true>), grid, dim3(QK_THREADS), 0, d->stream, (const float *)d->fp_st[d->fp_last], (const float *)nullptr, d->d_fp_chain, d->d_sgn, d->d_hard, post_out,
+                           d->M, d->N, d->ira_K, d->d_done, coded_llr_of(d));
+    else
+        hipLaunchKernelGGL((qk_fpost_close<false>), grid, dim3(QK_THREADS), 0, d->stream, (const float *)d->fp_st[d->fp_last], (const float *)d->d_llr, d->d_fp_chain, d->d_sgn, d->d_hard, post_out,
+                           d->M, d->N, d->ira_K, d->d_done, qk_coded_llr{});
+}
+
 #include "qldpc_kernels_chain.h"
 
 /* one sweep of the horizontal-layered schedule as ONE launch (qldpc_kernels_chain.h); compiled with the V = 1 instances only */
