@@ -1,49 +1,47 @@
 /*
  * qldpc_mc.hip -- the Monte-Carlo loop of the reference harness (source -> encoder -> BSC -> decoder -> monitor, BS/src/main.cpp:335-393)
- * with nothing per bit crossing the host (qldpc_mc_*).  The frame definition is qldpc_mc_core.h: frame i is a pure function of (seed, i).
+ * with nothing per bit crossing the host (qldpc_mc_*), and what runs around it: the puncture-pattern search, the quantised soft-output channels, the
+ * QBER sweep and the fixed-weight error strata.  The frame definition is qldpc_mc_core.h: frame i is a pure function of (seed, i).
+ *
+ * Three things are stated once and used by every path:
+ *   mc_slots           how the slots of a launch get their frame index and their row {threshold or weight, |LLR|}: frame first + f and one row by value
+ *                      (qldpc_mc_run, the search, the frame calls), or the slot tables and the rows of a round (qldpc_mc_sweep, qldpc_mc_strata:
+ *                      P rows of 8 bytes, L2-resident).  mc_source, mc_channel, mc_expand_rows and mc_channel_weight take it.
+ *   mc_frame_verdict,  the work of a monitor wave on one frame: be = popcount((out ^ cw) & info_mask) and, where wanted, the flips at channel VNs summed
+ *   mc_tally           over the lanes by shuffles, the clamped iteration count, the syndrome verdict; and the verdicts of a wave's frames summed in
+ *                      (wave-uniform) registers, then ONE atomic per wave and counter from lane 0 onto a counter row.  One counter enum: a pattern's
+ *                      row is a prefix of a point's, a point's a prefix of the run's.
+ *   mc_select,         the radix select of qldpc_mc_core.h by one workgroup: per key digit a histogram in LDS over keys recomputed on the fly (the pass is
+ *   mc_equal_scan      the caller's, nothing is stored), lane 0 picks the bucket; and for the final pass, which walks the keys in index order a trip of 256
+ *                      lanes at a time, the rank among equal keys = a running count + a shuffle prefix over the trip.
  *
  * mc_source:  one lane per info word of the packed [frame][word] layout, consecutive lanes = consecutive words of a row (the last lanes of a
  *     row run on into the next one), one Philox call per word.
  * mc_channel: one lane per codeword word: 8 Philox calls, the 32 classes of the word by two 16-byte loads from the padded class map (32 N
- *     bytes shared by all frames: L2-resident), the two thresholds wave-uniform kernel arguments; rx = cw ^ flips.  The lanes of word 0 also
- *     write the frame's |LLR| for qldpc_load_bits_dev.
+ *     bytes shared by all frames: L2-resident), the channel threshold from the slot's row; rx = cw ^ flips.  The lanes of word 0 also write the
+ *     slot's |LLR| for qldpc_load_bits_dev.
  * mc_soft_channel: the quantised soft-output channel of a threshold table (qldpc_mc_core.h), one lane per four VNs: one Philox call, one class
  *     word, both threshold rows and the value row in LDS (3 KB, loaded once per workgroup), a halving search per VN, one 16-byte store of the
  *     four LLRs where the address allows it (scalars where N % 4 != 0 shifts a row or cuts its last quad); the rx word = the OR of the flip
  *     nibbles of the 8 lanes of a codeword word by xor-shuffles, stored by the first of them.  No atomics, no floating-point arithmetic.
- * mc_monitor: one wave per frame (a wave strides over the frames): be = popcount((out ^ cw) & info_mask) and the flips at channel VNs summed
- *     over the lanes by shuffles, the per-frame verdicts summed in (wave-uniform) registers over the wave's frames, then ONE atomicAdd per
- *     wave and counter from lane 0 -- plus, per frame, one on the iteration histogram and, for a failed frame, one returning add on the
- *     slot counter of the failed-frame list.
- *
- * mc_patterns: one workgroup per puncture pattern (the definition and the radix select are qldpc_mc_core.h): per key digit a histogram in LDS
- *     over keys recomputed on the fly (n_cand / 4 Philox calls per pass, nothing stored), lane 0 picks the bucket; the final pass walks the
- *     candidates in index order in chunks of 4 x 256, the rank among equal keys = a running count + a shuffle prefix over the chunk, and sets
- *     the erase bits of the row it zeroed at its start.
- * mc_expand_rows: a pattern row -> the F frame rows of its slots, the layout qldpc_load_erasures_dev reads; 16-byte stores.
- * mc_monitor_patterns: the arithmetic of mc_monitor, the waves dealt out per pattern (every frame of a wave belongs to one pattern), so ONE
- *     atomicAdd per wave and counter onto the counter row of that pattern.
- *
- * mc_source_points / mc_channel_points: the lane layouts of mc_source / mc_channel for the QBER sweep (qldpc_mc_sweep): the frame index of a slot
- *     comes from the slot table of the round instead of first + f, the channel threshold and the |LLR| of the slot from the row {threshold,
- *     |LLR|} of the slot's point (P rows of 8 bytes: L2-resident); mc_info_word and mc_flip_word unchanged, so a frame is the frame of
- *     qldpc_mc_frames_host.
- * mc_expand_points: mc_expand_rows with the erase row of a slot looked up through the slot's point.
- * mc_monitor_points: the arithmetic of mc_monitor, flips included, the waves dealt out per chunk (every frame of a wave belongs to one point):
- *     ONE atomicAdd per wave and counter onto the counter row of that point and one atomicMax for iter_max, per frame one add on the point's
- *     histogram row; no failed-frame list.
- *
- * mc_channel_weight: the fixed-weight channel of the error strata (qldpc_mc_strata, the definition is qldpc_mc_core.h), one workgroup per frame
- *     slot: per key digit a histogram in LDS over the keys of the channel-class VNs, recomputed on the fly from the padded class map (N / 4
- *     Philox calls per pass, nothing stored: at N = 65 536 the keys of a frame do not fit in LDS), lane 0 picks the bucket.  The final pass
- *     gives a lane a whole codeword word, 256 words per trip: 8 Philox calls, the 32 classes as mc_channel reads them, three masks (keys below
- *     the threshold key, keys equal to it, pinned flips); the rank of the word among equal keys = a running count + a shuffle prefix over the
- *     trip; rx = cw ^ (selected | pinned) is one plain store per word, no global atomics.  The weight, the |LLR| and the frame index of a slot
- *     come from the tables of the round ({weight, |LLR|} rows in the layout of mc_channel_points' {threshold, |LLR|}), or from the arguments
- *     for qldpc_mc_weight_frames_dev.
+ * mc_channel_weight: the fixed-weight channel of the error strata (the definition is qldpc_mc_core.h), one workgroup per frame slot: the select over
+ *     the keys of the channel-class VNs, recomputed from the padded class map (N / 4 Philox calls per pass: at N = 65 536 the keys of a frame do not
+ *     fit in LDS).  The final pass gives a lane a whole codeword word: 8 Philox calls, the 32 classes as mc_channel reads them, three masks (keys
+ *     below the threshold key, keys equal to it, pinned flips); rx = cw ^ (selected | pinned) is one plain store per word, no global atomics.
+ * mc_patterns: one workgroup per puncture pattern (the definition is qldpc_mc_core.h): the select over the keys of the candidates (n_cand / 4 Philox
+ *     calls per pass); the final pass walks the candidates in chunks of 4 x 256 and sets the erase bits of the row it zeroed at its start.
+ * mc_expand_rows: the erase row of every slot -> the frame rows qldpc_load_erasures_dev reads; 16-byte stores.  The row of a slot is row slot / F
+ *     (a pattern row covers the F frames of its slots) or comes from the slot's entry in the row table of a round.
+ * mc_monitor: one wave per frame (a wave strides over the frames), flips included -- plus, per frame, one add on the iteration histogram and, for a
+ *     failed frame, one returning add on the slot counter of the failed-frame list.
+ * mc_monitor_patterns: the waves dealt out per pattern (every frame of a wave belongs to one pattern), so the tally of a wave goes onto the counter
+ *     row of that pattern; no flips, rx is not read.
+ * mc_monitor_points: the waves dealt out per chunk (every frame of a wave belongs to one point or stratum), flips included: the tally onto the counter
+ *     row of that point, per frame one add on the point's histogram row; no failed-frame list.
  *
  * No kernel waits on another wave.  The decoder and the encoder are driven through their public calls only; qldpc_engine_int.h is read for
- * the decoder's sizes, device and stream.
+ * the decoder's sizes, device and stream.  On the host every buffer is recorded where it is allocated (mc_alloc, mc_alloc_pinned) and freed from that
+ * record; the three loops share the event array, the generate + load, fetch and expand helpers and the end of a round (mc_round_end).
  */
 #include <hip/hip_runtime.h>
 
@@ -60,30 +58,49 @@
 
 #define MC_LANES 256
 #define MC_MAX_WAVES 2048          /* of a monitor launch */
-enum { MC_FRAMES = 0, MC_BIT_ERRORS, MC_FRAME_ERRORS, MC_UNDETECTED, MC_NOT_CONVERGED, MC_ITER_SUM, MC_ITER_MAX, MC_FLIPS, MC_CHANNEL_BITS, MC_FAIL_SLOTS,
-       MC_COUNTERS };
+/* one counter row for every monitor: a pattern's row is the first MC_PATTERN_COUNTERS of it, a point's or a stratum's the first MC_POINT_COUNTERS, the
+ * run's all of it */
+enum { MC_FRAMES = 0, MC_FRAME_ERRORS, MC_BIT_ERRORS, MC_UNDETECTED, MC_NOT_CONVERGED, MC_ITER_SUM, MC_PATTERN_COUNTERS,
+       MC_ITER_MAX = MC_PATTERN_COUNTERS, MC_FLIPS, MC_CHANNEL_BITS, MC_POINT_COUNTERS,
+       MC_FAIL_SLOTS = MC_POINT_COUNTERS, MC_COUNTERS };
 
 typedef unsigned long long mc_u64;
 
-__global__ __launch_bounds__(MC_LANES) void mc_source(uint32_t *__restrict__ info, unsigned total, unsigned Wk, int K, uint64_t seed, uint64_t first)
+/* the row of an operating point {floor(qber 2^32), qldpc_bsc_llr(qber)} or of a stratum {its weight, qldpc_bsc_llr(design_qber)} */
+struct mc_row { uint32_t t; float mag; };
+
+/* how the slots of a launch get their frame index and their row: from the tables of a round (P rows of 8 bytes: L2-resident) where there are
+ * tables, else frame first + f and the one row handed over by value */
+struct mc_slots {
+    const uint64_t *frame; uint64_t first;      /* frame != NULL: frame[f] */
+    const uint32_t *row; const mc_row *rows;    /* row != NULL: rows[row[f]] */
+    mc_row one;
+    __device__ uint64_t frame_of(unsigned f) const { return frame ? frame[f] : first + f; }
+    __device__ mc_row row_of(unsigned f) const { return row ? rows[row[f]] : one; }
+    /* for mc_expand_rows, which needs the index alone: without a table F consecutive slots share a row */
+    __device__ unsigned row_index(unsigned f, unsigned F) const { return row ? row[f] : f / F; }
+};
+
+__global__ __launch_bounds__(MC_LANES) void mc_source(uint32_t *__restrict__ info, unsigned total, unsigned Wk, int K, uint64_t seed, mc_slots sl)
 {
     const unsigned i = blockIdx.x * MC_LANES + threadIdx.x;
     if (i >= total) return;
     const unsigned f = i / Wk, j = i - f * Wk;
-    info[i] = mc_info_word(seed, first + f, j, K);
+    info[i] = mc_info_word(seed, sl.frame_of(f), j, K);
 }
 
+/* the BSC of the slot's row: its threshold for the channel VNs, its |LLR| for qldpc_load_bits_dev (llr_mag may be NULL) */
 __global__ __launch_bounds__(MC_LANES) void mc_channel(const uint32_t *__restrict__ cw, uint32_t *__restrict__ rx, const uint4 *__restrict__ cls,
-                                                       unsigned total, unsigned Wn, uint64_t seed, uint64_t first, uint32_t t_channel, uint32_t t_pinned,
-                                                       float *__restrict__ llr_mag, float mag)
+                                                       unsigned total, unsigned Wn, uint64_t seed, mc_slots sl, uint32_t t_pinned, float *__restrict__ llr_mag)
 {
     const unsigned i = blockIdx.x * MC_LANES + threadIdx.x;
     if (i >= total) return;
     const unsigned f = i / Wn, w = i - f * Wn;
+    const mc_row r = sl.row_of(f);
     const uint4 a = cls[2u * w], b = cls[2u * w + 1u];
     const uint32_t cls4[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    rx[i] = cw[i] ^ mc_flip_word(seed, first + f, w, cls4, t_channel, t_pinned);
-    if (w == 0 && llr_mag) llr_mag[f] = mag;
+    rx[i] = cw[i] ^ mc_flip_word(seed, sl.frame_of(f), w, cls4, r.t, t_pinned);
+    if (w == 0 && llr_mag) llr_mag[f] = r.mag;
 }
 
 /* rows of 8 Wn quads (the padding past N is QLDPC_VN_PUNCTURED: LLR 0, no flip, nothing stored), total = n 8 Wn lanes: a multiple of 8, as the
@@ -124,292 +141,244 @@ __device__ static inline unsigned mc_wave_sum(unsigned x)
     return x;
 }
 
-__global__ __launch_bounds__(MC_LANES) void mc_monitor(const uint32_t *__restrict__ out, const uint32_t *__restrict__ cw, const uint32_t *__restrict__ rx,
-                                                       const uint32_t *__restrict__ info_mask, const uint32_t *__restrict__ chan_mask,
-                                                       const int *__restrict__ iters, const int *__restrict__ ok, unsigned n, unsigned Wn, int n_ite,
-                                                       uint64_t first, unsigned channel_vns, mc_u64 *__restrict__ ctr, mc_u64 *__restrict__ hist,
-                                                       mc_u64 *__restrict__ fails, unsigned fail_cap)
+/* ---- the monitors: one verdict per frame, one tally per wave ---- */
+
+/* what a monitor reads of a decoded batch, the same for all three */
+struct mc_decoded {
+    const uint32_t *out, *cw, *rx, *info_mask, *chan_mask;      /* [n][Wn] decoded, sent and received rows; [Wn] masks of the info and the channel VNs */
+    const int *iters, *ok;
+    unsigned Wn; int n_ite;
+};
+
+struct mc_verdict { unsigned be, fl; int it; bool good; };
+
+/* frame f by one wave, the result in every lane: be = popcount((out ^ cw) & info_mask), FLIPS: fl = the flips at channel VNs (else rx is not read
+ * and fl = 0), the iteration count clamped to the histogram */
+template <bool FLIPS> __device__ static inline mc_verdict mc_frame_verdict(const mc_decoded &d, unsigned f)
+{
+    const size_t row = (size_t)f * d.Wn;
+    unsigned be = 0, fl = 0;
+    for (unsigned w = threadIdx.x & 63u; w < d.Wn; w += 64u) {
+        const uint32_t c = d.cw[row + w];
+        be += (unsigned)__popc((d.out[row + w] ^ c) & d.info_mask[w]);
+        if (FLIPS) fl += (unsigned)__popc((d.rx[row + w] ^ c) & d.chan_mask[w]);
+    }
+    be = mc_wave_sum(be);
+    if (FLIPS) fl = mc_wave_sum(fl);
+    return {be, fl, min(max(d.iters[f], 0), d.n_ite), d.ok[f] != 0};
+}
+
+/* the verdicts of a wave's frames summed in (wave-uniform) registers, then ONE atomic per wave and counter from lane 0 onto a counter row:
+ * FLIPS = false the MC_PATTERN_COUNTERS of a pattern, true the MC_POINT_COUNTERS of a point or of the run */
+template <bool FLIPS> struct mc_tally {
+    mc_u64 frames = 0, be = 0, fe = 0, ud = 0, nc = 0, it = 0, mx = 0, fl = 0;
+    __device__ void add(const mc_verdict &v)
+    {
+        frames++; be += v.be; fl += v.fl; it += (mc_u64)v.it;
+        mx = max(mx, (mc_u64)v.it);
+        fe += v.be > 0; ud += v.good && v.be > 0; nc += !v.good;
+    }
+    __device__ void flush(mc_u64 *row, unsigned channel_vns = 0) const
+    {
+        if ((threadIdx.x & 63u) != 0 || frames == 0) return;
+        atomicAdd(row + MC_FRAMES, frames);
+        atomicAdd(row + MC_ITER_SUM, it);
+        if (FLIPS) {
+            atomicMax(row + MC_ITER_MAX, mx);
+            atomicAdd(row + MC_CHANNEL_BITS, frames * channel_vns);
+            if (fl) atomicAdd(row + MC_FLIPS, fl);
+        }
+        if (be) atomicAdd(row + MC_BIT_ERRORS, be);
+        if (fe) atomicAdd(row + MC_FRAME_ERRORS, fe);
+        if (ud) atomicAdd(row + MC_UNDETECTED, ud);
+        if (nc) atomicAdd(row + MC_NOT_CONVERGED, nc);
+    }
+};
+
+/* one wave per frame (a wave strides over the n frames); per frame one add on the histogram and, for a failed frame, one returning add on the
+ * slot counter of the failed-frame list */
+__global__ __launch_bounds__(MC_LANES) void mc_monitor(mc_decoded d, unsigned n, uint64_t first, unsigned channel_vns, mc_u64 *__restrict__ ctr,
+                                                       mc_u64 *__restrict__ hist, mc_u64 *__restrict__ fails, unsigned fail_cap)
 {
     const unsigned lane = threadIdx.x & 63u, waves = gridDim.x * (MC_LANES / 64);
-    mc_u64 s_frames = 0, s_be = 0, s_fe = 0, s_ud = 0, s_nc = 0, s_it = 0, s_mx = 0, s_fl = 0;
+    mc_tally<true> sum;
     for (unsigned f = blockIdx.x * (MC_LANES / 64) + (threadIdx.x >> 6); f < n; f += waves) {
-        const size_t row = (size_t)f * Wn;
-        unsigned be = 0, fl = 0;
-        for (unsigned w = lane; w < Wn; w += 64u) {
-            const uint32_t c = cw[row + w];
-            be += (unsigned)__popc((out[row + w] ^ c) & info_mask[w]);
-            fl += (unsigned)__popc((rx[row + w] ^ c) & chan_mask[w]);
-        }
-        be = mc_wave_sum(be);
-        fl = mc_wave_sum(fl);
-        const int it = min(max(iters[f], 0), n_ite);
-        const bool good = ok[f] != 0;
-        s_frames++; s_be += be; s_fl += fl; s_it += (mc_u64)it;
-        s_mx = max(s_mx, (mc_u64)it);
-        s_fe += be > 0; s_ud += good && be > 0; s_nc += !good;
+        const mc_verdict v = mc_frame_verdict<true>(d, f);
+        sum.add(v);
         if (lane == 0) {
-            atomicAdd(hist + it, 1ull);
-            if (be > 0) {
+            atomicAdd(hist + v.it, 1ull);
+            if (v.be > 0) {
                 const mc_u64 slot = atomicAdd(ctr + MC_FAIL_SLOTS, 1ull);
                 if (slot < fail_cap) fails[slot] = first + f;
             }
         }
     }
-    if (lane != 0 || s_frames == 0) return;
-    atomicAdd(ctr + MC_FRAMES, s_frames);
-    atomicAdd(ctr + MC_ITER_SUM, s_it);
-    atomicMax(ctr + MC_ITER_MAX, s_mx);
-    atomicAdd(ctr + MC_CHANNEL_BITS, s_frames * channel_vns);
-    if (s_fl) atomicAdd(ctr + MC_FLIPS, s_fl);
-    if (s_be) atomicAdd(ctr + MC_BIT_ERRORS, s_be);
-    if (s_fe) atomicAdd(ctr + MC_FRAME_ERRORS, s_fe);
-    if (s_ud) atomicAdd(ctr + MC_UNDETECTED, s_ud);
-    if (s_nc) atomicAdd(ctr + MC_NOT_CONVERGED, s_nc);
+    sum.flush(ctr, channel_vns);
 }
 
-/* ---- puncture patterns ---- */
+/* wpp waves per pattern (<= F): wave (pat, sub) takes frames sub, sub + wpp, ... of the F frames of pattern slot pat, so every frame of a wave
+ * belongs to one pattern, whose counter row [MC_PATTERN_COUNTERS] the wave adds to; rx is not read */
+__global__ __launch_bounds__(MC_LANES) void mc_monitor_patterns(mc_decoded d, unsigned n_pat, unsigned F, unsigned wpp, mc_u64 *__restrict__ rows)
+{
+    const unsigned wid = blockIdx.x * (MC_LANES / 64) + (threadIdx.x >> 6);
+    if (wid >= n_pat * wpp) return;
+    const unsigned pat = wid / wpp, sub = wid - pat * wpp;
+    mc_tally<false> sum;
+    for (unsigned k = sub; k < F; k += wpp) sum.add(mc_frame_verdict<false>(d, pat * F + k));
+    sum.flush(rows + (size_t)pat * MC_PATTERN_COUNTERS);
+}
+
+/* wpc waves per chunk: wave (chunk, sub) takes frames sub, sub + wpc, ... of the chunk_len frames that start at slot chunk_start; a chunk
+ * belongs to one point, whose counter row [MC_POINT_COUNTERS] and histogram row [n_ite + 1] the wave adds to; no failed-frame list */
+__global__ __launch_bounds__(MC_LANES) void mc_monitor_points(mc_decoded d, unsigned n_chunks, unsigned wpc, const uint32_t *__restrict__ chunk_point,
+                                                              const uint32_t *__restrict__ chunk_start, const uint32_t *__restrict__ chunk_len,
+                                                              unsigned channel_vns, mc_u64 *__restrict__ rows, mc_u64 *__restrict__ hists)
+{
+    const unsigned lane = threadIdx.x & 63u, wid = blockIdx.x * (MC_LANES / 64) + (threadIdx.x >> 6);
+    if (wid >= n_chunks * wpc) return;
+    const unsigned c = wid / wpc, sub = wid - c * wpc, point = chunk_point[c], start = chunk_start[c], len = chunk_len[c];
+    mc_u64 *hist = hists + (size_t)point * (size_t)(d.n_ite + 1);
+    mc_tally<true> sum;
+    for (unsigned k = sub; k < len; k += wpc) {
+        const mc_verdict v = mc_frame_verdict<true>(d, start + k);
+        sum.add(v);
+        if (lane == 0) atomicAdd(hist + v.it, 1ull);
+    }
+    sum.flush(rows + (size_t)point * MC_POINT_COUNTERS, channel_vns);
+}
+
+/* ---- the radix select of qldpc_mc_core.h by one workgroup of MC_PAT_LANES lanes ---- */
 #define MC_PAT_LANES 256
-static_assert(MC_PAT_LANES == MC_SEL_BINS, "mc_patterns clears one histogram bin per lane");
-enum { MCP_FRAMES = 0, MCP_FRAME_ERRORS, MCP_BIT_ERRORS, MCP_UNDETECTED, MCP_NOT_CONVERGED, MCP_ITER_SUM, MCP_COUNTERS };
+static_assert(MC_PAT_LANES == MC_SEL_BINS, "mc_select clears one histogram bin per lane");
+
+struct mc_selected { uint32_t T, r; };      /* the threshold key, and how many of the keys equal to it are taken */
+
+/* rank k (1-based) among keys of key_bits bits, in every lane: per digit a histogram in LDS, lane 0 picks the bucket, the choice goes round through
+ * LDS.  pass(count) is one histogram pass of the whole workgroup: it calls count(key) once for every key, recomputed on the fly (nothing is
+ * stored).  k = 0, uniform over the workgroup: no pass, T = 0, r = 0.  Every lane of the workgroup calls it; it ends behind a barrier. */
+template <typename Pass> __device__ static inline mc_selected mc_select(int key_bits, uint32_t k, Pass pass)
+{
+    __shared__ uint32_t hist[MC_SEL_BINS];
+    __shared__ uint32_t sel[2];
+    const unsigned t = threadIdx.x;
+    uint32_t prefix = 0, mask = 0;
+    if (k == 0) return {0u, 0u};
+    for (int shift = mc_select_top_shift(key_bits); shift >= 0; shift -= MC_SEL_BITS) {
+        hist[t] = 0u;
+        __syncthreads();
+        pass([&](uint32_t key) { if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & (MC_SEL_BINS - 1)], 1u); });
+        __syncthreads();
+        if (t == 0) { uint32_t kk = k; sel[0] = mc_select_digit(hist, &kk); sel[1] = kk; }
+        __syncthreads();
+        prefix |= sel[0] << shift; k = sel[1];
+        mask |= (uint32_t)(MC_SEL_BINS - 1) << shift;
+    }
+    return {prefix, k};
+}
+
+/* the final pass walks the keys in index order, MC_PAT_LANES lanes per trip: before(mine) = the keys equal to T that precede this lane's `mine`
+ * of them, over all the trips so far = a running count + a shuffle prefix over the trip.  Every lane calls it once per trip. */
+struct mc_equal_scan {
+    unsigned base = 0;
+    __device__ unsigned before(unsigned mine)
+    {
+        __shared__ unsigned wave_eq[MC_PAT_LANES / 64];
+        const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        unsigned incl = mine;
+        for (unsigned s = 1; s < 64u; s <<= 1) { const unsigned v = __shfl_up(incl, s, 64); if (lane >= s) incl += v; }
+        __syncthreads();      /* the trip before has read wave_eq */
+        if (lane == 63u) wave_eq[wave] = incl;
+        __syncthreads();
+        unsigned b = base + incl - mine;
+        for (unsigned w = 0; w < MC_PAT_LANES / 64; w++) { if (w < wave) b += wave_eq[w]; base += wave_eq[w]; }
+        return b;
+    }
+};
+
+/* ---- puncture patterns ---- */
 
 /* rows[blockIdx.x][Wn] = the erase row of pattern first + blockIdx.x; cand[n_cand] ascending VNs below 32 Wn; n_punct <= n_cand; key_bits 1 .. 32 */
 __global__ __launch_bounds__(MC_PAT_LANES) void mc_patterns(uint32_t *__restrict__ rows, const int *__restrict__ cand, unsigned n_cand, unsigned n_punct,
                                                             int key_bits, unsigned Wn, uint64_t seed, uint64_t first)
 {
-    __shared__ uint32_t hist[MC_SEL_BINS];
-    __shared__ uint32_t sel[2];
-    __shared__ unsigned wave_eq[MC_PAT_LANES / 64];
-    const unsigned t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const unsigned t = threadIdx.x;
     const uint64_t p = first + blockIdx.x;
     uint32_t *row = rows + (size_t)blockIdx.x * Wn;
     for (unsigned w = t; w < Wn; w += MC_PAT_LANES) row[w] = 0u;
     if (n_punct == 0) return;
     const unsigned blocks = (n_cand + 3u) / 4u;
-    uint32_t prefix = 0, mask = 0, k = n_punct, u[4];
-    for (int shift = mc_select_top_shift(key_bits); shift >= 0; shift -= MC_SEL_BITS) {
-        hist[t] = 0u;
-        __syncthreads();
+    uint32_t u[4];
+    const mc_selected s = mc_select(key_bits, n_punct, [&](auto count) {      /* n_cand / 4 Philox calls per pass */
         for (unsigned q = t; q < blocks; q += MC_PAT_LANES) {
             mc_pattern_keys(seed, p, q, key_bits, u);
             for (unsigned b = 0; b < 4; b++)
-                if (4u * q + b < n_cand && (u[b] & mask) == prefix) atomicAdd(&hist[(u[b] >> shift) & (MC_SEL_BINS - 1)], 1u);
+                if (4u * q + b < n_cand) count(u[b]);
         }
-        __syncthreads();
-        if (t == 0) { uint32_t kk = k; sel[0] = mc_select_digit(hist, &kk); sel[1] = kk; }
-        __syncthreads();
-        prefix |= sel[0] << shift; k = sel[1];
-        mask |= (uint32_t)(MC_SEL_BINS - 1) << shift;
-    }
-    /* T = prefix, r = k.  The barriers above also order the zeroing of the row before the bits set below. */
-    unsigned equal_base = 0;
+    });
+    /* the barriers of the select also order the zeroing of the row before the bits set below */
+    mc_equal_scan scan;
     for (unsigned q0 = 0; q0 < blocks; q0 += MC_PAT_LANES) {
         const unsigned q = q0 + t;
         unsigned mine = 0;
         if (q < blocks) {
             mc_pattern_keys(seed, p, q, key_bits, u);
-            for (unsigned b = 0; b < 4; b++) mine += 4u * q + b < n_cand && u[b] == prefix;
+            for (unsigned b = 0; b < 4; b++) mine += 4u * q + b < n_cand && u[b] == s.T;
         }
-        unsigned incl = mine;
-        for (unsigned s = 1; s < 64u; s <<= 1) { const unsigned v = __shfl_up(incl, s, 64); if (lane >= s) incl += v; }
-        if (lane == 63u) wave_eq[wave] = incl;
-        __syncthreads();
-        unsigned before = equal_base + incl - mine;
-        for (unsigned w = 0; w < MC_PAT_LANES / 64; w++) { if (w < wave) before += wave_eq[w]; equal_base += wave_eq[w]; }
+        unsigned before = scan.before(mine);
         if (q < blocks)
             for (unsigned b = 0; b < 4; b++) {
                 if (4u * q + b >= n_cand) break;
-                if (mc_pattern_takes(u[b], prefix, k, before)) { const unsigned v = (unsigned)cand[4u * q + b]; atomicOr(&row[v >> 5], 0x80000000u >> (v & 31u)); }
-                before += u[b] == prefix;
+                if (mc_pattern_takes(u[b], s.T, s.r, before)) { const unsigned v = (unsigned)cand[4u * q + b]; atomicOr(&row[v >> 5], 0x80000000u >> (v & 31u)); }
+                before += u[b] == s.T;
             }
-        __syncthreads();
     }
 }
 
-/* frames[slot][Wn] = pat[slot / F][Wn] for the `total` words of the slots, four words per lane */
-__global__ __launch_bounds__(MC_LANES) void mc_expand_rows(const uint32_t *__restrict__ pat, uint32_t *__restrict__ frames, unsigned total, unsigned Wn, unsigned F)
+/* frames[slot][Wn] = pat[the slot's row][Wn] for the `total` words of the slots, four words per lane; without a row table F slots per row */
+__global__ __launch_bounds__(MC_LANES) void mc_expand_rows(const uint32_t *__restrict__ pat, uint32_t *__restrict__ frames, unsigned total, unsigned Wn, mc_slots sl,
+                                                           unsigned F)
 {
     const unsigned i = (blockIdx.x * MC_LANES + threadIdx.x) * 4u;
     if (i >= total) return;
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     for (unsigned j = 0; j < 4; j++)
-        if (i + j < total) { const unsigned slot = (i + j) / Wn, word = (i + j) - slot * Wn; w[j] = pat[(size_t)(slot / F) * Wn + word]; }
+        if (i + j < total) { const unsigned slot = (i + j) / Wn, word = (i + j) - slot * Wn; w[j] = pat[(size_t)sl.row_index(slot, F) * Wn + word]; }
     if (i + 4u <= total) *(uint4 *)(frames + i) = make_uint4(w[0], w[1], w[2], w[3]);
     else for (unsigned j = 0; i + j < total; j++) frames[i + j] = w[j];
-}
-
-/* wpp waves per pattern (<= F): wave (pat, sub) takes frames sub, sub + wpp, ... of the F frames of pattern slot pat */
-__global__ __launch_bounds__(MC_LANES) void mc_monitor_patterns(const uint32_t *__restrict__ out, const uint32_t *__restrict__ cw, const uint32_t *__restrict__ info_mask,
-                                                                const int *__restrict__ iters, const int *__restrict__ ok, unsigned n_pat, unsigned F, unsigned wpp,
-                                                                unsigned Wn, int n_ite, mc_u64 *__restrict__ rows)
-{
-    const unsigned lane = threadIdx.x & 63u, wid = blockIdx.x * (MC_LANES / 64) + (threadIdx.x >> 6);
-    if (wid >= n_pat * wpp) return;
-    const unsigned pat = wid / wpp, sub = wid - pat * wpp;
-    mc_u64 s_frames = 0, s_be = 0, s_fe = 0, s_ud = 0, s_nc = 0, s_it = 0;
-    for (unsigned k = sub; k < F; k += wpp) {
-        const unsigned f = pat * F + k;
-        const size_t row = (size_t)f * Wn;
-        unsigned be = 0;
-        for (unsigned w = lane; w < Wn; w += 64u) be += (unsigned)__popc((out[row + w] ^ cw[row + w]) & info_mask[w]);
-        be = mc_wave_sum(be);
-        const int it = min(max(iters[f], 0), n_ite);
-        const bool good = ok[f] != 0;
-        s_frames++; s_be += be; s_it += (mc_u64)it;
-        s_fe += be > 0; s_ud += good && be > 0; s_nc += !good;
-    }
-    if (lane != 0 || s_frames == 0) return;
-    mc_u64 *r = rows + (size_t)pat * MCP_COUNTERS;
-    atomicAdd(r + MCP_FRAMES, s_frames);
-    atomicAdd(r + MCP_ITER_SUM, s_it);
-    if (s_be) atomicAdd(r + MCP_BIT_ERRORS, s_be);
-    if (s_fe) atomicAdd(r + MCP_FRAME_ERRORS, s_fe);
-    if (s_ud) atomicAdd(r + MCP_UNDETECTED, s_ud);
-    if (s_nc) atomicAdd(r + MCP_NOT_CONVERGED, s_nc);
-}
-
-/* ---- QBER sweep: operating points side by side in one batch ---- */
-struct mc_point_row { uint32_t t_channel; float mag; };      /* of a point: floor(qber 2^32), qldpc_bsc_llr(qber) */
-#define MCW_COUNTERS MC_FAIL_SLOTS                            /* a point's counter row: MC_FRAMES .. MC_CHANNEL_BITS */
-
-__global__ __launch_bounds__(MC_LANES) void mc_source_points(uint32_t *__restrict__ info, unsigned total, unsigned Wk, int K, uint64_t seed,
-                                                             const uint64_t *__restrict__ slot_frame)
-{
-    const unsigned i = blockIdx.x * MC_LANES + threadIdx.x;
-    if (i >= total) return;
-    const unsigned f = i / Wk, j = i - f * Wk;
-    info[i] = mc_info_word(seed, slot_frame[f], j, K);
-}
-
-__global__ __launch_bounds__(MC_LANES) void mc_channel_points(const uint32_t *__restrict__ cw, uint32_t *__restrict__ rx, const uint4 *__restrict__ cls,
-                                                              unsigned total, unsigned Wn, uint64_t seed, const uint64_t *__restrict__ slot_frame,
-                                                              const uint32_t *__restrict__ slot_point, const mc_point_row *__restrict__ points,
-                                                              uint32_t t_pinned, float *__restrict__ llr_mag)
-{
-    const unsigned i = blockIdx.x * MC_LANES + threadIdx.x;
-    if (i >= total) return;
-    const unsigned f = i / Wn, w = i - f * Wn;
-    const mc_point_row pt = points[slot_point[f]];
-    const uint4 a = cls[2u * w], b = cls[2u * w + 1u];
-    const uint32_t cls4[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    rx[i] = cw[i] ^ mc_flip_word(seed, slot_frame[f], w, cls4, pt.t_channel, t_pinned);
-    if (w == 0) llr_mag[f] = pt.mag;
-}
-
-/* frames[slot][Wn] = rows[slot_point[slot]][Wn] for the `total` words of the slots, four words per lane */
-__global__ __launch_bounds__(MC_LANES) void mc_expand_points(const uint32_t *__restrict__ rows, uint32_t *__restrict__ frames, unsigned total, unsigned Wn,
-                                                             const uint32_t *__restrict__ slot_point)
-{
-    const unsigned i = (blockIdx.x * MC_LANES + threadIdx.x) * 4u;
-    if (i >= total) return;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-    for (unsigned j = 0; j < 4; j++)
-        if (i + j < total) { const unsigned slot = (i + j) / Wn, word = (i + j) - slot * Wn; w[j] = rows[(size_t)slot_point[slot] * Wn + word]; }
-    if (i + 4u <= total) *(uint4 *)(frames + i) = make_uint4(w[0], w[1], w[2], w[3]);
-    else for (unsigned j = 0; i + j < total; j++) frames[i + j] = w[j];
-}
-
-/* wpc waves per chunk: wave (chunk, sub) takes frames sub, sub + wpc, ... of the chunk_len frames that start at slot chunk_start; a chunk
- * belongs to one point, whose counter row [MCW_COUNTERS] and histogram row [n_ite + 1] the wave adds to */
-__global__ __launch_bounds__(MC_LANES) void mc_monitor_points(const uint32_t *__restrict__ out, const uint32_t *__restrict__ cw, const uint32_t *__restrict__ rx,
-                                                              const uint32_t *__restrict__ info_mask, const uint32_t *__restrict__ chan_mask,
-                                                              const int *__restrict__ iters, const int *__restrict__ ok, unsigned n_chunks, unsigned wpc,
-                                                              const uint32_t *__restrict__ chunk_point, const uint32_t *__restrict__ chunk_start,
-                                                              const uint32_t *__restrict__ chunk_len, unsigned Wn, int n_ite, unsigned channel_vns,
-                                                              mc_u64 *__restrict__ rows, mc_u64 *__restrict__ hists)
-{
-    const unsigned lane = threadIdx.x & 63u, wid = blockIdx.x * (MC_LANES / 64) + (threadIdx.x >> 6);
-    if (wid >= n_chunks * wpc) return;
-    const unsigned c = wid / wpc, sub = wid - c * wpc, point = chunk_point[c], start = chunk_start[c], len = chunk_len[c];
-    mc_u64 *hist = hists + (size_t)point * (size_t)(n_ite + 1);
-    mc_u64 s_frames = 0, s_be = 0, s_fe = 0, s_ud = 0, s_nc = 0, s_it = 0, s_mx = 0, s_fl = 0;
-    for (unsigned k = sub; k < len; k += wpc) {
-        const unsigned f = start + k;
-        const size_t row = (size_t)f * Wn;
-        unsigned be = 0, fl = 0;
-        for (unsigned w = lane; w < Wn; w += 64u) {
-            const uint32_t x = cw[row + w];
-            be += (unsigned)__popc((out[row + w] ^ x) & info_mask[w]);
-            fl += (unsigned)__popc((rx[row + w] ^ x) & chan_mask[w]);
-        }
-        be = mc_wave_sum(be);
-        fl = mc_wave_sum(fl);
-        const int it = min(max(iters[f], 0), n_ite);
-        const bool good = ok[f] != 0;
-        s_frames++; s_be += be; s_fl += fl; s_it += (mc_u64)it;
-        s_mx = max(s_mx, (mc_u64)it);
-        s_fe += be > 0; s_ud += good && be > 0; s_nc += !good;
-        if (lane == 0) atomicAdd(hist + it, 1ull);
-    }
-    if (lane != 0 || s_frames == 0) return;
-    mc_u64 *r = rows + (size_t)point * MCW_COUNTERS;
-    atomicAdd(r + MC_FRAMES, s_frames);
-    atomicAdd(r + MC_ITER_SUM, s_it);
-    atomicMax(r + MC_ITER_MAX, s_mx);
-    atomicAdd(r + MC_CHANNEL_BITS, s_frames * channel_vns);
-    if (s_fl) atomicAdd(r + MC_FLIPS, s_fl);
-    if (s_be) atomicAdd(r + MC_BIT_ERRORS, s_be);
-    if (s_fe) atomicAdd(r + MC_FRAME_ERRORS, s_fe);
-    if (s_ud) atomicAdd(r + MC_UNDETECTED, s_ud);
-    if (s_nc) atomicAdd(r + MC_NOT_CONVERGED, s_nc);
 }
 
 /* ---- fixed-weight error strata ---- */
-struct mc_stratum_row { uint32_t weight; float mag; };       /* of a stratum: its weight, qldpc_bsc_llr(design_qber) */
-static_assert(sizeof(mc_stratum_row) == sizeof(mc_point_row), "a stratum row travels in the point rows of the sweep");
 
-/* rx[slot][Wn] = cw[slot][Wn] ^ the flips of the fixed-weight frame of the slot; gridDim.x = the slots.  slot_frame == NULL: frame first + slot;
- * slot_stratum == NULL: every slot is `one`.  cls = the padded class map (past N: QLDPC_VN_PUNCTURED, never selected); key_bits 1 .. 32;
- * weight <= the channel VNs of cls */
+/* rx[slot][Wn] = cw[slot][Wn] ^ the flips of the fixed-weight frame of the slot, its weight = the t of the slot's row; gridDim.x = the slots.
+ * cls = the padded class map (past N: QLDPC_VN_PUNCTURED, never selected); key_bits 1 .. 32; weight <= the channel VNs of cls */
 __global__ __launch_bounds__(MC_PAT_LANES) void mc_channel_weight(const uint32_t *__restrict__ cw, uint32_t *__restrict__ rx, const uint4 *__restrict__ cls, unsigned Wn,
-                                                                  uint64_t seed, uint64_t first, const uint64_t *__restrict__ slot_frame,
-                                                                  const uint32_t *__restrict__ slot_stratum, const mc_stratum_row *__restrict__ strata,
-                                                                  mc_stratum_row one, int key_bits, uint32_t t_pinned, float *__restrict__ llr_mag)
+                                                                  uint64_t seed, mc_slots sl, int key_bits, uint32_t t_pinned, float *__restrict__ llr_mag)
 {
-    __shared__ uint32_t hist[MC_SEL_BINS];
-    __shared__ uint32_t sel[2];
-    __shared__ unsigned wave_eq[MC_PAT_LANES / 64];
-    const unsigned t = threadIdx.x, lane = t & 63u, wave = t >> 6, slot = blockIdx.x;
-    const uint64_t frame = slot_frame ? slot_frame[slot] : first + slot;
-    const mc_stratum_row st = slot_stratum ? strata[slot_stratum[slot]] : one;
+    const unsigned t = threadIdx.x, slot = blockIdx.x;
+    const uint64_t frame = sl.frame_of(slot);
+    const mc_row st = sl.row_of(slot);
     const uint32_t *cls4 = (const uint32_t *)cls;
     const unsigned quads = 8u * Wn;
-    uint32_t prefix = 0, mask = 0, k = st.weight, u[4];
-    for (int shift = mc_select_top_shift(key_bits); shift >= 0 && st.weight; shift -= MC_SEL_BITS) {      /* uniform over the workgroup; weight 0: T = 0, r = 0 */
-        hist[t] = 0u;
-        __syncthreads();
+    const mc_selected s = mc_select(key_bits, st.t, [&](auto count) {      /* the keys of the channel VNs: N / 4 Philox calls per pass */
+        uint32_t u[4];
         for (unsigned g = t; g < quads; g += MC_PAT_LANES) {
             const uint32_t m = mc_weight_quad(seed, frame, g, cls4[g], 0u, u);
-            for (unsigned b = 0; b < 4; b++) {
-                const uint32_t key = u[b] >> (32 - key_bits);
-                if (((m >> b) & 1u) && (key & mask) == prefix) atomicAdd(&hist[(key >> shift) & (MC_SEL_BINS - 1)], 1u);
-            }
+            for (unsigned b = 0; b < 4; b++)
+                if ((m >> b) & 1u) count(u[b] >> (32 - key_bits));
         }
-        __syncthreads();
-        if (t == 0) { uint32_t kk = k; sel[0] = mc_select_digit(hist, &kk); sel[1] = kk; }
-        __syncthreads();
-        prefix |= sel[0] << shift; k = sel[1];
-        mask |= (uint32_t)(MC_SEL_BINS - 1) << shift;
-    }
-    /* T = prefix, r = k */
+    });
     const size_t row = (size_t)slot * Wn;
-    unsigned equal_base = 0;
+    mc_equal_scan scan;
     for (unsigned w0 = 0; w0 < Wn; w0 += MC_PAT_LANES) {
         const unsigned w = w0 + t;
         uint32_t less = 0, eq = 0, pin = 0;
         if (w < Wn) {
             const uint4 a = cls[2u * w], b = cls[2u * w + 1u];
             const uint32_t c4[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-            mc_weight_masks(seed, frame, w, c4, key_bits, prefix, t_pinned, &less, &eq, &pin);
+            mc_weight_masks(seed, frame, w, c4, key_bits, s.T, t_pinned, &less, &eq, &pin);
         }
-        const unsigned mine = (unsigned)__popc(eq);
-        unsigned incl = mine;
-        for (unsigned s = 1; s < 64u; s <<= 1) { const unsigned v = __shfl_up(incl, s, 64); if (lane >= s) incl += v; }
-        if (lane == 63u) wave_eq[wave] = incl;
-        __syncthreads();
-        unsigned before = equal_base + incl - mine;
-        for (unsigned x = 0; x < MC_PAT_LANES / 64; x++) { if (x < wave) before += wave_eq[x]; equal_base += wave_eq[x]; }
-        if (w < Wn) rx[row + w] = cw[row + w] ^ (mc_weight_take(less, eq, prefix, k, before) | pin);
-        __syncthreads();
+        const unsigned before = scan.before((unsigned)__popc(eq));
+        if (w < Wn) rx[row + w] = cw[row + w] ^ (mc_weight_take(less, eq, s.T, s.r, before) | pin);
     }
     if (t == 0 && llr_mag) llr_mag[slot] = st.mag;
 }
@@ -421,13 +390,14 @@ struct qldpc_mc {
     int N, K, Wn, Wk, n_ite, batch, fail_cap, device;
     unsigned channel_vns;
     uint64_t seed; double parity_ber;
+    std::vector<void *> dev_owned, pinned_owned;   /* everything mc_alloc and mc_alloc_pinned handed out: what qldpc_mc_free frees */
+    size_t dev_bytes;
     uint8_t *d_cls;                    /* [32 Wn] padded class map: qldpc_load_bits_dev reads its first N bytes, mc_channel all of it */
     uint32_t *d_info_mask, *d_chan_mask, *d_info, *d_cw, *d_rx, *d_out;
     float *d_mag; int *d_iters, *d_ok;
     mc_u64 *d_ctr;                     /* MC_COUNTERS counters, n_ite + 1 histogram bins, fail_cap frame indices */
     mc_u64 *h_ctr;                     /* pinned, MC_COUNTERS */
-    hipEvent_t ev[7];                  /* the stage boundaries of a batch: source | encode | channel | load | run | fetch + monitor */
-    size_t dev_bytes;
+    hipEvent_t ev[8];                  /* the stage boundaries of a batch or a round, in the order of the loop's stage list */
     /* puncture patterns and the search over them; the device side is allocated at first use (mc_search_reserve) */
     std::vector<uint8_t> h_cls;        /* [N] the class map, for the default candidates */
     std::vector<int> cand;             /* the candidate VNs, ascending */
@@ -435,8 +405,7 @@ struct qldpc_mc {
     int n_fixed;                       /* VNs of the fixed puncture set of qldpc_mc_run (0 = none) */
     int *d_cand;                       /* [N] */
     uint32_t *d_pat, *d_erase, *d_fixed;   /* [batch][Wn] pattern rows, [batch][Wn] frame rows, [Wn] the fixed set */
-    mc_u64 *d_rows, *h_rows;           /* [batch][MCP_COUNTERS] counter rows of a round; pinned copy */
-    hipEvent_t sev[8];                 /* of a search round: patterns | expand | generate | load | erase | run | fetch + monitor */
+    mc_u64 *d_rows, *h_rows;           /* [batch][MC_PATTERN_COUNTERS] counter rows of a round; pinned copy */
     std::vector<qldpc_mc_pattern_stat> stats;   /* of the last search */
     /* a quantised soft-output channel in place of the BSC; the device side is allocated by the first accepted qldpc_mc_set_channel */
     bool soft;                         /* a table is in force */
@@ -448,10 +417,9 @@ struct qldpc_mc {
     std::vector<uint32_t> h_fixed;     /* [Wn] the fixed set of qldpc_mc_set_puncture (empty = none): a point's erase row = this OR its prefix */
     mc_u64 *d_slots, *h_slots;         /* the tables of a round and their pinned copy: [batch] 64-bit frame indices, then [batch] 32-bit words each
                                           of slot -> point, chunk -> point, chunk -> first slot, chunk -> frames */
-    mc_point_row *d_points;            /* [QLDPC_MC_SWEEP_MAX_POINTS] */
+    mc_row *d_points;                  /* [QLDPC_MC_SWEEP_MAX_POINTS] */
     uint32_t *d_prows;                 /* [QLDPC_MC_SWEEP_MAX_POINTS][Wn] the erase rows of the points */
-    mc_u64 *d_wctr, *h_wctr, *d_whist; /* [QLDPC_MC_SWEEP_MAX_POINTS][MCW_COUNTERS] counter rows, pinned copy; [..][n_ite + 1] histogram rows */
-    hipEvent_t wev[8];                 /* of a sweep round: source | encode | channel | load | erase | run | fetch + monitor */
+    mc_u64 *d_wctr, *h_wctr, *d_whist; /* [QLDPC_MC_SWEEP_MAX_POINTS][MC_POINT_COUNTERS] counter rows, pinned copy; [..][n_ite + 1] histogram rows */
     std::vector<qldpc_mc_point_stat> wstats;    /* of the last sweep */
     /* the error strata run the sweep's rounds on the sweep's tables and device rows; rows_owner says whose counters and histograms those hold */
     int rows_owner;                    /* MC_ROWS_* */
@@ -470,24 +438,28 @@ extern "C" void qldpc_mc_free(qldpc_mc *mc)
 {
     if (!mc) return;
     (void)hipSetDevice(mc->device);
-    void *dev[] = {mc->d_cls, mc->d_info_mask, mc->d_chan_mask, mc->d_info, mc->d_cw, mc->d_rx, mc->d_out, mc->d_mag, mc->d_iters, mc->d_ok, mc->d_ctr,
-                   mc->d_cand, mc->d_pat, mc->d_erase, mc->d_fixed, mc->d_rows, mc->d_tab, mc->d_llr,
-                   mc->d_slots, mc->d_points, mc->d_prows, mc->d_wctr, mc->d_whist};
-    for (void *p : dev) if (p) (void)hipFree(p);
-    if (mc->h_ctr) (void)hipHostFree(mc->h_ctr);
-    if (mc->h_rows) (void)hipHostFree(mc->h_rows);
-    if (mc->h_slots) (void)hipHostFree(mc->h_slots);
-    if (mc->h_wctr) (void)hipHostFree(mc->h_wctr);
+    for (void *p : mc->dev_owned) (void)hipFree(p);
+    for (void *p : mc->pinned_owned) (void)hipHostFree(p);
     for (hipEvent_t e : mc->ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : mc->sev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : mc->wev) if (e) (void)hipEventDestroy(e);
     delete mc;
 }
 
+/* *p = count elements on the device, owned by mc; a buffer that is already there stays (the reserves are lazy and share d_erase) */
 template <typename T> static int mc_alloc(qldpc_mc *mc, T **p, size_t count)
 {
+    if (*p) return QLDPC_OK;
     if (hipMalloc((void **)p, sizeof(T) * count) != hipSuccess) { *p = nullptr; qldpc_set_error("mc_create: device allocation of %zu bytes failed", sizeof(T) * count); return QLDPC_ENOMEM; }
+    mc->dev_owned.push_back(*p);
     mc->dev_bytes += sizeof(T) * count;
+    return QLDPC_OK;
+}
+
+/* the pinned counterpart */
+template <typename T> static int mc_alloc_pinned(qldpc_mc *mc, T **p, size_t count)
+{
+    if (*p) return QLDPC_OK;
+    if (hipHostMalloc((void **)p, sizeof(T) * count, hipHostMallocDefault) != hipSuccess) { *p = nullptr; return QLDPC_ENOMEM; }
+    mc->pinned_owned.push_back(*p);
     return QLDPC_OK;
 }
 
@@ -519,9 +491,8 @@ static int mc_build(qldpc_mc *mc, const uint8_t *vn_class)
     if ((rc = mc_alloc(mc, &mc->d_cls, 32 * Wn)) || (rc = mc_alloc(mc, &mc->d_info_mask, Wn)) || (rc = mc_alloc(mc, &mc->d_chan_mask, Wn)) ||
         (rc = mc_alloc(mc, &mc->d_info, B * (size_t)mc->Wk)) || (rc = mc_alloc(mc, &mc->d_cw, B * Wn)) || (rc = mc_alloc(mc, &mc->d_rx, B * Wn)) ||
         (rc = mc_alloc(mc, &mc->d_out, B * Wn)) || (rc = mc_alloc(mc, &mc->d_mag, B)) || (rc = mc_alloc(mc, &mc->d_iters, B)) || (rc = mc_alloc(mc, &mc->d_ok, B)) ||
-        (rc = mc_alloc(mc, &mc->d_ctr, (size_t)MC_COUNTERS + (size_t)mc->n_ite + 1 + (size_t)mc->fail_cap)))
+        (rc = mc_alloc(mc, &mc->d_ctr, (size_t)MC_COUNTERS + (size_t)mc->n_ite + 1 + (size_t)mc->fail_cap)) || (rc = mc_alloc_pinned(mc, &mc->h_ctr, MC_COUNTERS)))
         return rc;
-    if (hipHostMalloc((void **)&mc->h_ctr, sizeof(mc_u64) * MC_COUNTERS, hipHostMallocDefault) != hipSuccess) { mc->h_ctr = nullptr; return QLDPC_ENOMEM; }
     HIPCHK(hipMemcpy(mc->d_cls, cls.data(), 32 * Wn, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(mc->d_info_mask, info_mask.data(), 4 * Wn, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(mc->d_chan_mask, chan_mask.data(), 4 * Wn, hipMemcpyHostToDevice));
@@ -559,16 +530,25 @@ extern "C" size_t qldpc_mc_device_bytes(const qldpc_mc *mc) { return mc ? mc->de
 
 static unsigned mc_blocks(size_t lanes) { return (unsigned)((lanes + MC_LANES - 1) / MC_LANES); }
 
-/* source -> encoder -> channel for frames [first, first + n) on stream s; d_cw / d_rx / d_mag may be NULL from the right; ev != NULL: ev[1] after the
- * source, ev[2] after the encoder.  d_llr != NULL: the channel of the table instead of the BSC, LLR rows into d_llr (d_rx may then be NULL alone,
- * qber and d_mag are not used); the caller has checked n 8 Wn < 2^31 */
-static int mc_generate(qldpc_mc *mc, uint64_t first, int n, double qber, uint32_t *d_info, uint32_t *d_cw, uint32_t *d_rx, float *d_mag, hipStream_t s,
-                       hipEvent_t *ev = nullptr, float *d_llr = nullptr)
+/* the slots of frames first, first + 1, ... with one row {t, mag} for all of them */
+static mc_slots mc_range(uint64_t first, uint32_t t = 0u, float mag = 0.0f) { return {nullptr, first, nullptr, nullptr, {t, mag}}; }
+static mc_slots mc_bsc_range(uint64_t first, double qber) { return mc_range(first, mc_threshold(qber), qldpc_bsc_llr((float)qber)); }
+
+/* source -> encoder -> channel for the n frames of sl on stream s; d_cw / d_rx / d_mag may be NULL from the right; ev != NULL: ev[1] after the
+ * source, ev[2] after the encoder.  The channel: d_llr != NULL the table's, LLR rows into d_llr (d_rx may then be NULL alone; sl gives frame
+ * first + f, its row and d_mag are not used; the caller has checked n 8 Wn < 2^31); else weight_bits != 0 the fixed weights of sl's rows with
+ * keys of weight_bits bits; else the BSC of sl's rows */
+static int mc_generate(qldpc_mc *mc, const mc_slots &sl, int n, uint32_t *d_info, uint32_t *d_cw, uint32_t *d_rx, float *d_mag, hipStream_t s,
+                       hipEvent_t *ev = nullptr, float *d_llr = nullptr, int weight_bits = 0)
 {
-    const unsigned ti = (unsigned)n * (unsigned)mc->Wk, tn = (unsigned)n * (unsigned)mc->Wn;
+    const unsigned ti = (unsigned)n * (unsigned)mc->Wk, tn = (unsigned)n * (unsigned)mc->Wn, Wn = (unsigned)mc->Wn;
+    if (weight_bits < 0 || weight_bits > 32 || (d_llr && (sl.frame || sl.row || weight_bits))) {      /* a caller's mistake, not the user's */
+        qldpc_set_error("mc_generate: weight_bits=%d outside 0 .. 32, or the table's channel with slot tables or a weight", weight_bits);
+        return QLDPC_EINVAL;
+    }
     if (mc->source == QLDPC_MC_SOURCE_ZERO) HIPCHK(hipMemsetAsync(d_info, 0, sizeof(uint32_t) * ti, s));
     else {
-        hipLaunchKernelGGL(mc_source, dim3(mc_blocks(ti)), dim3(MC_LANES), 0, s, d_info, ti, (unsigned)mc->Wk, mc->K, mc->seed, first);
+        hipLaunchKernelGGL(mc_source, dim3(mc_blocks(ti)), dim3(MC_LANES), 0, s, d_info, ti, (unsigned)mc->Wk, mc->K, mc->seed, sl);
         LAUNCHCHK();
     }
     if (ev) HIPCHK(hipEventRecord(ev[1], s));
@@ -576,14 +556,16 @@ static int mc_generate(qldpc_mc *mc, uint64_t first, int n, double qber, uint32_
     const int rc = qldpc_encode_packed_dev(mc->enc, d_info, d_cw, n, (void *)s);
     if (rc || (!d_rx && !d_llr)) return rc;
     if (ev) HIPCHK(hipEventRecord(ev[2], s));
-    if (d_llr) {
+    const uint32_t t_pinned = mc_threshold(mc->parity_ber);
+    if (d_llr)
         hipLaunchKernelGGL(mc_soft_channel, dim3(mc_blocks(8 * (size_t)tn)), dim3(MC_LANES), 0, s, (const uint32_t *)d_cw, d_rx, d_llr, (const uint32_t *)mc->d_cls,
-                           (const mc_soft_table *)mc->d_tab, 8u * tn, 8u * (unsigned)mc->Wn, (unsigned)mc->N, mc->seed, first, mc_threshold(mc->parity_ber));
-        LAUNCHCHK();
-        return QLDPC_OK;
-    }
-    hipLaunchKernelGGL(mc_channel, dim3(mc_blocks(tn)), dim3(MC_LANES), 0, s, (const uint32_t *)d_cw, d_rx, (const uint4 *)mc->d_cls, tn, (unsigned)mc->Wn,
-                       mc->seed, first, mc_threshold(qber), mc_threshold(mc->parity_ber), d_mag, qldpc_bsc_llr((float)qber));
+                           (const mc_soft_table *)mc->d_tab, 8u * tn, 8u * Wn, (unsigned)mc->N, mc->seed, sl.first, t_pinned);
+    else if (weight_bits)
+        hipLaunchKernelGGL(mc_channel_weight, dim3((unsigned)n), dim3(MC_PAT_LANES), 0, s, (const uint32_t *)d_cw, d_rx, (const uint4 *)mc->d_cls, Wn, mc->seed, sl,
+                           weight_bits, t_pinned, d_mag);
+    else
+        hipLaunchKernelGGL(mc_channel, dim3(mc_blocks(tn)), dim3(MC_LANES), 0, s, (const uint32_t *)d_cw, d_rx, (const uint4 *)mc->d_cls, tn, Wn, mc->seed, sl, t_pinned,
+                           d_mag);
     LAUNCHCHK();
     return QLDPC_OK;
 }
@@ -595,13 +577,14 @@ extern "C" int qldpc_mc_frames_dev(qldpc_mc *mc, uint64_t first_frame, int n_fra
     if ((uint64_t)n_frames * (uint64_t)mc->Wn >= (1ull << 31)) { qldpc_set_error("mc_frames_dev: %d frames of N = %d pass 2^31 words", n_frames, mc->N); return QLDPC_ESIZE; }
     if (n_frames == 0) return QLDPC_OK;
     HIPCHK(hipSetDevice(mc->device));
-    return mc_generate(mc, first_frame, n_frames, qber, d_info, d_cw, d_rx, nullptr, mc->dec->stream);
+    return mc_generate(mc, mc_bsc_range(first_frame, qber), n_frames, d_info, d_cw, d_rx, nullptr, mc->dec->stream);
 }
 
-/* the frames of a batch into the decoder, by the channel in force: generate (ev as mc_generate takes it), ev_channel, load */
-static int mc_generate_load(qldpc_mc *mc, uint64_t first, int n, double qber, hipStream_t s, hipEvent_t *ev, hipEvent_t ev_channel)
+/* the frames of a batch into the decoder, by the channel in force (a table, else weight_bits as mc_generate takes it): generate (ev as mc_generate
+ * takes it), ev_channel, load */
+static int mc_generate_load(qldpc_mc *mc, const mc_slots &sl, int n, hipStream_t s, hipEvent_t *ev, hipEvent_t ev_channel, int weight_bits = 0)
 {
-    const int rc = mc_generate(mc, first, n, qber, mc->d_info, mc->d_cw, mc->d_rx, mc->d_mag, s, ev, mc->soft ? mc->d_llr : nullptr);
+    const int rc = mc_generate(mc, sl, n, mc->d_info, mc->d_cw, mc->d_rx, mc->d_mag, s, ev, mc->soft ? mc->d_llr : nullptr, weight_bits);
     if (rc) return rc;
     HIPCHK(hipEventRecord(ev_channel, s));
     return mc->soft ? qldpc_load_llr_dev(mc->dec, mc->d_llr, n) : qldpc_load_bits_dev(mc->dec, mc->d_rx, mc->d_mag, mc->d_cls, n);
@@ -634,7 +617,7 @@ extern "C" int qldpc_mc_set_channel(qldpc_mc *mc, const qldpc_mc_channel *table)
     if (rc) { qldpc_set_error("mc_set_channel: a missing array, a row that decreases or an entry above 2^32"); return QLDPC_EINVAL; }
     if ((rc = mc_soft_lanes_check(mc, "mc_set_channel", mc->batch))) return rc;
     HIPCHK(hipSetDevice(mc->device));
-    if ((!mc->d_tab && (rc = mc_alloc(mc, &mc->d_tab, 1))) || (!mc->d_llr && (rc = mc_alloc(mc, &mc->d_llr, (size_t)mc->batch * (size_t)mc->N)))) return rc;
+    if ((rc = mc_alloc(mc, &mc->d_tab, 1)) || (rc = mc_alloc(mc, &mc->d_llr, (size_t)mc->batch * (size_t)mc->N))) return rc;
     HIPCHK(hipStreamSynchronize(mc->dec->stream));      /* a queued channel kernel may still read the old table */
     HIPCHK(hipMemcpy(mc->d_tab, &tab, sizeof(tab), hipMemcpyHostToDevice));
     mc->soft = true;
@@ -649,25 +632,77 @@ extern "C" int qldpc_mc_llr_dev(qldpc_mc *mc, uint64_t first_frame, int n_frames
     if (rc) return rc;
     if (n_frames == 0) return QLDPC_OK;
     HIPCHK(hipSetDevice(mc->device));
-    return mc_generate(mc, first_frame, n_frames, 0.0, d_info, d_cw, d_rx, nullptr, mc->dec->stream, nullptr, d_llr);
+    return mc_generate(mc, mc_range(first_frame), n_frames, d_info, d_cw, d_rx, nullptr, mc->dec->stream, nullptr, d_llr);
 }
 
-static void mc_result(const qldpc_mc *mc, uint64_t first, qldpc_mc_result *r)
-{
-    const mc_u64 *c = mc->h_ctr;
-    r->frames = c[MC_FRAMES]; r->bit_errors = c[MC_BIT_ERRORS]; r->frame_errors = c[MC_FRAME_ERRORS]; r->undetected = c[MC_UNDETECTED];
-    r->not_converged = c[MC_NOT_CONVERGED]; r->iter_sum = c[MC_ITER_SUM]; r->iter_max = c[MC_ITER_MAX];
-    r->channel_flips = c[MC_FLIPS]; r->channel_bits = c[MC_CHANNEL_BITS];
-    r->next_frame = first + r->frames;
-}
-
-/* the erase rows of n frames from pattern rows that cover F slots each, into the decoder: after qldpc_load_bits_dev */
-static int mc_erase(qldpc_mc *mc, const uint32_t *d_rows, int n, int F, hipStream_t s)
+/* the erase rows of n frames into mc->d_erase, the layout qldpc_load_erasures_dev reads: the row of a slot by sl's row table, or d_rows[slot / F] */
+static int mc_expand(qldpc_mc *mc, const uint32_t *d_rows, const mc_slots &sl, int n, int F, hipStream_t s)
 {
     const unsigned total = (unsigned)n * (unsigned)mc->Wn;
-    hipLaunchKernelGGL(mc_expand_rows, dim3(mc_blocks(((size_t)total + 3) / 4)), dim3(MC_LANES), 0, s, d_rows, mc->d_erase, total, (unsigned)mc->Wn, (unsigned)F);
+    hipLaunchKernelGGL(mc_expand_rows, dim3(mc_blocks(((size_t)total + 3) / 4)), dim3(MC_LANES), 0, s, d_rows, mc->d_erase, total, (unsigned)mc->Wn, sl, (unsigned)F);
     LAUNCHCHK();
-    return qldpc_load_erasures_dev(mc->dec, mc->d_erase, n);
+    return QLDPC_OK;
+}
+
+/* ... and into the decoder: after qldpc_load_bits_dev */
+static int mc_erase(qldpc_mc *mc, const uint32_t *d_rows, const mc_slots &sl, int n, int F, hipStream_t s)
+{
+    const int rc = mc_expand(mc, d_rows, sl, n, F, s);
+    return rc ? rc : qldpc_load_erasures_dev(mc->dec, mc->d_erase, n);
+}
+
+/* the decoder's words and verdicts of the n frames it holds, where the monitors read them */
+static int mc_fetch(qldpc_mc *mc)
+{
+    const int rc = qldpc_fetch_packed_dev(mc->dec, mc->d_out);
+    return rc ? rc : qldpc_fetch_status_dev(mc->dec, mc->d_iters, mc->d_ok);
+}
+
+static mc_decoded mc_decoded_of(const qldpc_mc *mc)
+{
+    return {mc->d_out, mc->d_cw, mc->d_rx, mc->d_info_mask, mc->d_chan_mask, mc->d_iters, mc->d_ok, (unsigned)mc->Wn, mc->n_ite};
+}
+
+/* the end of a batch or a round, behind its monitor: ev[n], the ONE read-back (`words` counters from d to the pinned h), and the time between
+ * ev[k] and ev[k + 1] added to *stage[k] for the n stages */
+static int mc_round_end(qldpc_mc *mc, mc_u64 *h, const mc_u64 *d, size_t words, double *const *stage, int n, hipStream_t s)
+{
+    HIPCHK(hipEventRecord(mc->ev[n], s));
+    HIPCHK(hipMemcpyAsync(h, d, sizeof(mc_u64) * words, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int k = 0; k < n; k++) {
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, mc->ev[k], mc->ev[k + 1]));
+        *stage[k] += (double)ms;
+    }
+    return QLDPC_OK;
+}
+
+/* frames .. channel_bits of a result or a stat row from a counter row of MC_POINT_COUNTERS */
+template <typename S> static void mc_counters_out(S *st, const mc_u64 *c)
+{
+    st->frames = c[MC_FRAMES]; st->bit_errors = c[MC_BIT_ERRORS]; st->frame_errors = c[MC_FRAME_ERRORS]; st->undetected = c[MC_UNDETECTED];
+    st->not_converged = c[MC_NOT_CONVERGED]; st->iter_sum = c[MC_ITER_SUM]; st->iter_max = c[MC_ITER_MAX];
+    st->channel_flips = c[MC_FLIPS]; st->channel_bits = c[MC_CHANNEL_BITS];
+}
+
+/* the stat rows of the last call, for the *_stats getters: copies min(cap, their number), returns their number */
+template <typename S> static int mc_stats_out(const std::vector<S> &all, S *rows, int cap)
+{
+    if (cap < 0 || (cap && !rows)) return QLDPC_EINVAL;
+    const size_t n = std::min((size_t)cap, all.size());
+    if (n) memcpy(rows, all.data(), sizeof(S) * n);
+    return (int)all.size();
+}
+
+/* a histogram row [n_ite + 1] on the device, for the *_hist getters: copies min(cap, n_ite + 1) bins, returns n_ite + 1 */
+static int mc_hist_out(qldpc_mc *mc, const mc_u64 *d_hist, uint64_t *hist, int cap)
+{
+    const int bins = std::min(cap, mc->n_ite + 1);
+    HIPCHK(hipSetDevice(mc->device));
+    HIPCHK(hipStreamSynchronize(mc->dec->stream));
+    if (bins) HIPCHK(hipMemcpy(hist, d_hist, sizeof(mc_u64) * (size_t)bins, hipMemcpyDeviceToHost));
+    return mc->n_ite + 1;
 }
 
 extern "C" int qldpc_mc_run(qldpc_mc *mc, double qber, uint64_t first_frame, uint64_t max_frames, uint64_t max_frame_errors, qldpc_mc_result *result)
@@ -682,50 +717,38 @@ extern "C" int qldpc_mc_run(qldpc_mc *mc, double qber, uint64_t first_frame, uin
     mc_u64 *hist = mc->d_ctr + MC_COUNTERS, *fails = hist + mc->n_ite + 1;
     HIPCHK(hipMemsetAsync(mc->d_ctr, 0, sizeof(mc_u64) * ctr_words, s));
     memset(mc->h_ctr, 0, sizeof(mc_u64) * MC_COUNTERS);
+    double *const stage[6] = {&result->source_ms, &result->encode_ms, &result->channel_ms, &result->load_ms, &result->decode_ms, &result->monitor_ms};
     const auto t_start = std::chrono::steady_clock::now();
     for (uint64_t done = 0; done < max_frames;) {
         const int nb = (int)std::min<uint64_t>((uint64_t)mc->batch, max_frames - done);
         const uint64_t first = first_frame + done;
         HIPCHK(hipEventRecord(mc->ev[0], s));
-        int rc = mc_generate_load(mc, first, nb, qber, s, mc->ev, mc->ev[3]);
+        int rc = mc_generate_load(mc, mc_bsc_range(first, qber), nb, s, mc->ev, mc->ev[3]);
         if (rc) return rc;
-        if (mc->n_fixed && (rc = mc_erase(mc, mc->d_fixed, nb, nb, s))) return rc;      /* the fixed puncture set: one row for all nb frames */
+        if (mc->n_fixed && (rc = mc_erase(mc, mc->d_fixed, mc_range(0), nb, nb, s))) return rc;      /* the fixed puncture set: one row for all nb frames */
         HIPCHK(hipEventRecord(mc->ev[4], s));
         if ((rc = qldpc_run(mc->dec))) return rc;
         HIPCHK(hipEventRecord(mc->ev[5], s));
-        if ((rc = qldpc_fetch_packed_dev(mc->dec, mc->d_out))) return rc;
-        if ((rc = qldpc_fetch_status_dev(mc->dec, mc->d_iters, mc->d_ok))) return rc;
+        if ((rc = mc_fetch(mc))) return rc;
         const unsigned waves = (unsigned)std::min(nb, MC_MAX_WAVES);
-        hipLaunchKernelGGL(mc_monitor, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_out, (const uint32_t *)mc->d_cw, (const uint32_t *)mc->d_rx,
-                           (const uint32_t *)mc->d_info_mask, (const uint32_t *)mc->d_chan_mask, (const int *)mc->d_iters, (const int *)mc->d_ok, (unsigned)nb,
-                           (unsigned)mc->Wn, mc->n_ite, first, mc->channel_vns, mc->d_ctr, hist, fails, (unsigned)mc->fail_cap);
+        hipLaunchKernelGGL(mc_monitor, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, mc_decoded_of(mc), (unsigned)nb, first, mc->channel_vns, mc->d_ctr, hist, fails,
+                           (unsigned)mc->fail_cap);
         LAUNCHCHK();
-        HIPCHK(hipEventRecord(mc->ev[6], s));
-        HIPCHK(hipMemcpyAsync(mc->h_ctr, mc->d_ctr, sizeof(mc_u64) * MC_COUNTERS, hipMemcpyDeviceToHost, s));      /* the one read-back of a batch */
-        HIPCHK(hipStreamSynchronize(s));
-        double *const stage[6] = {&result->source_ms, &result->encode_ms, &result->channel_ms, &result->load_ms, &result->decode_ms, &result->monitor_ms};
-        for (int k = 0; k < 6; k++) {
-            float ms = 0.0f;
-            HIPCHK(hipEventElapsedTime(&ms, mc->ev[k], mc->ev[k + 1]));
-            *stage[k] += (double)ms;
-        }
+        if ((rc = mc_round_end(mc, mc->h_ctr, mc->d_ctr, MC_COUNTERS, stage, 6, s))) return rc;
         result->batches++;
         done += (uint64_t)nb;
         if (max_frame_errors && mc->h_ctr[MC_FRAME_ERRORS] >= max_frame_errors) break;
     }
     result->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    mc_result(mc, first_frame, result);
+    mc_counters_out(result, mc->h_ctr);
+    result->next_frame = first_frame + result->frames;
     return QLDPC_OK;
 }
 
 extern "C" int qldpc_mc_iter_hist(qldpc_mc *mc, uint64_t *hist, int cap)
 {
     if (!mc || !hist || cap < 0) return QLDPC_EINVAL;
-    const int bins = std::min(cap, mc->n_ite + 1);
-    HIPCHK(hipSetDevice(mc->device));
-    HIPCHK(hipStreamSynchronize(mc->dec->stream));
-    if (bins) HIPCHK(hipMemcpy(hist, mc->d_ctr + MC_COUNTERS, sizeof(mc_u64) * (size_t)bins, hipMemcpyDeviceToHost));
-    return mc->n_ite + 1;
+    return mc_hist_out(mc, mc->d_ctr + MC_COUNTERS, hist, cap);
 }
 
 extern "C" int qldpc_mc_failed_frames(qldpc_mc *mc, uint64_t *frames, int cap)
@@ -754,13 +777,10 @@ static int mc_search_reserve(qldpc_mc *mc)
     if (!mc->search_ready) {
         const size_t Wn = (size_t)mc->Wn, B = (size_t)mc->batch;
         int rc = QLDPC_OK;
-        if ((!mc->d_cand && (rc = mc_alloc(mc, &mc->d_cand, (size_t)mc->N))) || (!mc->d_pat && (rc = mc_alloc(mc, &mc->d_pat, B * Wn))) ||
-            (!mc->d_erase && (rc = mc_alloc(mc, &mc->d_erase, B * Wn))) || (!mc->d_fixed && (rc = mc_alloc(mc, &mc->d_fixed, Wn))) ||
-            (!mc->d_rows && (rc = mc_alloc(mc, &mc->d_rows, B * MCP_COUNTERS))))
+        if ((rc = mc_alloc(mc, &mc->d_cand, (size_t)mc->N)) || (rc = mc_alloc(mc, &mc->d_pat, B * Wn)) || (rc = mc_alloc(mc, &mc->d_erase, B * Wn)) ||
+            (rc = mc_alloc(mc, &mc->d_fixed, Wn)) || (rc = mc_alloc(mc, &mc->d_rows, B * MC_PATTERN_COUNTERS)) ||
+            (rc = mc_alloc_pinned(mc, &mc->h_rows, B * MC_PATTERN_COUNTERS)) || (rc = qldpc_decoder_reserve(mc->dec)))      /* the decoder's erasure ballots */
             return rc;
-        if (!mc->h_rows && hipHostMalloc((void **)&mc->h_rows, sizeof(mc_u64) * B * MCP_COUNTERS, hipHostMallocDefault) != hipSuccess) { mc->h_rows = nullptr; return QLDPC_ENOMEM; }
-        for (hipEvent_t &e : mc->sev) if (!e) HIPCHK(hipEventCreate(&e));
-        if ((rc = qldpc_decoder_reserve(mc->dec))) return rc;      /* the decoder's erasure ballots */
         mc->search_ready = true;
     }
     if (mc->cand_dirty) {
@@ -850,46 +870,35 @@ extern "C" int qldpc_mc_search(qldpc_mc *mc, double qber, const qldpc_mc_search_
     int rc = mc_pattern_args(mc, "mc_search", cfg->n_punct, cfg->key_bits);
     if (rc || (rc = mc_search_reserve(mc))) return rc;
     const hipStream_t s = mc->dec->stream;
-    const unsigned F = (unsigned)cfg->frames_per_pattern, Wn = (unsigned)mc->Wn;
+    const unsigned F = (unsigned)cfg->frames_per_pattern;
     const uint64_t per_round = (uint64_t)mc->batch / F;
     mc->stats.clear();
+    double *const stage[7] = {&res->pattern_ms, &res->expand_ms, &res->generate_ms, &res->load_ms, &res->erase_ms, &res->decode_ms, &res->monitor_ms};
     const auto t_start = std::chrono::steady_clock::now();
     for (uint64_t done = 0; done < max_patterns;) {
         const int np = (int)std::min<uint64_t>(per_round, max_patterns - done), nb = np * (int)F;
         const uint64_t p0 = first_pattern + done, frame0 = cfg->first_frame + p0 * F;      /* frame k of pattern p = first_frame + p F + k */
-        HIPCHK(hipEventRecord(mc->sev[0], s));
+        HIPCHK(hipEventRecord(mc->ev[0], s));
         mc_launch_patterns(mc, p0, np, cfg->n_punct, cfg->key_bits, mc->d_pat, s);
         LAUNCHCHK();
-        HIPCHK(hipEventRecord(mc->sev[1], s));
-        const unsigned total = (unsigned)nb * Wn;
-        hipLaunchKernelGGL(mc_expand_rows, dim3(mc_blocks(((size_t)total + 3) / 4)), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_pat, mc->d_erase, total, Wn, F);
-        LAUNCHCHK();
-        HIPCHK(hipEventRecord(mc->sev[2], s));
-        if ((rc = mc_generate_load(mc, frame0, nb, qber, s, nullptr, mc->sev[3]))) return rc;
-        HIPCHK(hipEventRecord(mc->sev[4], s));
+        HIPCHK(hipEventRecord(mc->ev[1], s));
+        if ((rc = mc_expand(mc, mc->d_pat, mc_range(0), nb, (int)F, s))) return rc;
+        HIPCHK(hipEventRecord(mc->ev[2], s));
+        if ((rc = mc_generate_load(mc, mc_bsc_range(frame0, qber), nb, s, nullptr, mc->ev[3]))) return rc;
+        HIPCHK(hipEventRecord(mc->ev[4], s));
         if ((rc = qldpc_load_erasures_dev(mc->dec, mc->d_erase, nb))) return rc;
-        HIPCHK(hipEventRecord(mc->sev[5], s));
+        HIPCHK(hipEventRecord(mc->ev[5], s));
         if ((rc = qldpc_run(mc->dec))) return rc;
-        HIPCHK(hipEventRecord(mc->sev[6], s));
-        if ((rc = qldpc_fetch_packed_dev(mc->dec, mc->d_out))) return rc;
-        if ((rc = qldpc_fetch_status_dev(mc->dec, mc->d_iters, mc->d_ok))) return rc;
-        HIPCHK(hipMemsetAsync(mc->d_rows, 0, sizeof(mc_u64) * (size_t)np * MCP_COUNTERS, s));
+        HIPCHK(hipEventRecord(mc->ev[6], s));
+        if ((rc = mc_fetch(mc))) return rc;
+        HIPCHK(hipMemsetAsync(mc->d_rows, 0, sizeof(mc_u64) * (size_t)np * MC_PATTERN_COUNTERS, s));
         const unsigned wpp = std::min(F, std::max(1u, (unsigned)MC_MAX_WAVES / (unsigned)np)), waves = (unsigned)np * wpp;
-        hipLaunchKernelGGL(mc_monitor_patterns, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_out, (const uint32_t *)mc->d_cw,
-                           (const uint32_t *)mc->d_info_mask, (const int *)mc->d_iters, (const int *)mc->d_ok, (unsigned)np, F, wpp, Wn, mc->n_ite, mc->d_rows);
+        hipLaunchKernelGGL(mc_monitor_patterns, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, mc_decoded_of(mc), (unsigned)np, F, wpp, mc->d_rows);
         LAUNCHCHK();
-        HIPCHK(hipEventRecord(mc->sev[7], s));
-        HIPCHK(hipMemcpyAsync(mc->h_rows, mc->d_rows, sizeof(mc_u64) * (size_t)np * MCP_COUNTERS, hipMemcpyDeviceToHost, s));      /* the one read-back of a round */
-        HIPCHK(hipStreamSynchronize(s));
-        double *const stage[7] = {&res->pattern_ms, &res->expand_ms, &res->generate_ms, &res->load_ms, &res->erase_ms, &res->decode_ms, &res->monitor_ms};
-        for (int k = 0; k < 7; k++) {
-            float ms = 0.0f;
-            HIPCHK(hipEventElapsedTime(&ms, mc->sev[k], mc->sev[k + 1]));
-            *stage[k] += (double)ms;
-        }
+        if ((rc = mc_round_end(mc, mc->h_rows, mc->d_rows, (size_t)np * MC_PATTERN_COUNTERS, stage, 7, s))) return rc;
         for (int i = 0; i < np; i++) {
-            const mc_u64 *c = mc->h_rows + (size_t)i * MCP_COUNTERS;
-            qldpc_mc_pattern_stat st = {p0 + (uint64_t)i, c[MCP_FRAMES], c[MCP_FRAME_ERRORS], c[MCP_BIT_ERRORS], c[MCP_UNDETECTED], c[MCP_NOT_CONVERGED], c[MCP_ITER_SUM]};
+            const mc_u64 *c = mc->h_rows + (size_t)i * MC_PATTERN_COUNTERS;
+            qldpc_mc_pattern_stat st = {p0 + (uint64_t)i, c[MC_FRAMES], c[MC_FRAME_ERRORS], c[MC_BIT_ERRORS], c[MC_UNDETECTED], c[MC_NOT_CONVERGED], c[MC_ITER_SUM]};
             mc->stats.push_back(st);
             if (st.frame_errors == 0 && res->goal == UINT64_MAX) res->goal = st.pattern;
             if (res->best == UINT64_MAX || st.frame_errors < res->best_frame_errors || (st.frame_errors == res->best_frame_errors && st.bit_errors < res->best_bit_errors)) {
@@ -908,41 +917,49 @@ extern "C" int qldpc_mc_search(qldpc_mc *mc, double qber, const qldpc_mc_search_
 
 extern "C" int qldpc_mc_search_stats(qldpc_mc *mc, qldpc_mc_pattern_stat *rows, int cap)
 {
-    if (!mc || cap < 0 || (cap && !rows)) return QLDPC_EINVAL;
-    const size_t n = std::min((size_t)cap, mc->stats.size());
-    if (n) memcpy(rows, mc->stats.data(), sizeof(qldpc_mc_pattern_stat) * n);
-    return (int)mc->stats.size();
+    if (!mc) return QLDPC_EINVAL;
+    return mc_stats_out(mc->stats, rows, cap);
 }
 
-/* ------------------------------------------------------------------ QBER sweep ---- */
+/* ------------------------------------------------------------------ QBER sweep and error strata: rows side by side in one batch ---- */
 
-/* everything the sweep needs on the device, once */
+/* everything the rounds need on the device, once */
 static int mc_sweep_reserve(qldpc_mc *mc)
 {
     HIPCHK(hipSetDevice(mc->device));
     if (mc->sweep_ready) return QLDPC_OK;
     const size_t Wn = (size_t)mc->Wn, B = (size_t)mc->batch, P = QLDPC_MC_SWEEP_MAX_POINTS, bins = (size_t)mc->n_ite + 1;
     int rc = QLDPC_OK;
-    if ((!mc->d_slots && (rc = mc_alloc(mc, &mc->d_slots, 3 * B))) || (!mc->d_points && (rc = mc_alloc(mc, &mc->d_points, P))) ||
-        (!mc->d_prows && (rc = mc_alloc(mc, &mc->d_prows, P * Wn))) || (!mc->d_erase && (rc = mc_alloc(mc, &mc->d_erase, B * Wn))) ||
-        (!mc->d_wctr && (rc = mc_alloc(mc, &mc->d_wctr, P * MCW_COUNTERS))) || (!mc->d_whist && (rc = mc_alloc(mc, &mc->d_whist, P * bins))))
+    if ((rc = mc_alloc(mc, &mc->d_slots, 3 * B)) || (rc = mc_alloc(mc, &mc->d_points, P)) || (rc = mc_alloc(mc, &mc->d_prows, P * Wn)) ||
+        (rc = mc_alloc(mc, &mc->d_erase, B * Wn)) || (rc = mc_alloc(mc, &mc->d_wctr, P * MC_POINT_COUNTERS)) || (rc = mc_alloc(mc, &mc->d_whist, P * bins)) ||
+        (rc = mc_alloc_pinned(mc, &mc->h_slots, 3 * B)) || (rc = mc_alloc_pinned(mc, &mc->h_wctr, P * MC_POINT_COUNTERS)) ||
+        (rc = qldpc_decoder_reserve(mc->dec)))      /* the decoder's erasure ballots */
         return rc;
-    if (!mc->h_slots && hipHostMalloc((void **)&mc->h_slots, sizeof(mc_u64) * 3 * B, hipHostMallocDefault) != hipSuccess) { mc->h_slots = nullptr; return QLDPC_ENOMEM; }
-    if (!mc->h_wctr && hipHostMalloc((void **)&mc->h_wctr, sizeof(mc_u64) * P * MCW_COUNTERS, hipHostMallocDefault) != hipSuccess) { mc->h_wctr = nullptr; return QLDPC_ENOMEM; }
-    for (hipEvent_t &e : mc->wev) if (!e) HIPCHK(hipEventCreate(&e));
-    if ((rc = qldpc_decoder_reserve(mc->dec))) return rc;      /* the decoder's erasure ballots */
     mc->sweep_ready = true;
+    return QLDPC_OK;
+}
+
+/* what qldpc_mc_sweep and qldpc_mc_strata check of their cfg in common, in the order both check it.  refused_soft = the caller's whole error text
+ * for a channel table in force; design_qber: the strata have one, the sweep passes NULL */
+static int mc_rounds_args(const qldpc_mc *mc, const char *who, const int reserved[2], const char *refused_soft, const char *n_name, int n,
+                          const double *design_qber, int chunk, uint64_t max_frames)
+{
+    if (reserved[0] || reserved[1]) { qldpc_set_error("%s: reserved fields %d, %d must be zero", who, reserved[0], reserved[1]); return QLDPC_EINVAL; }
+    if (mc->soft) { qldpc_set_error("%s", refused_soft); return QLDPC_ESTATE; }
+    if (n < 1 || n > QLDPC_MC_SWEEP_MAX_POINTS) { qldpc_set_error("%s: %s=%d outside 1 .. %d", who, n_name, n, QLDPC_MC_SWEEP_MAX_POINTS); return QLDPC_ESIZE; }
+    if (design_qber && !(*design_qber > 0.0 && *design_qber < 0.5)) { qldpc_set_error("%s: design_qber=%g outside (0, 0.5)", who, *design_qber); return QLDPC_ESIZE; }
+    if (chunk < 0 || chunk > mc->batch) { qldpc_set_error("%s: chunk=%d outside [0, batch=%d]", who, chunk, mc->batch); return QLDPC_ESIZE; }
+    if (max_frames == 0) { qldpc_set_error("%s: max_frames=0", who); return QLDPC_ESIZE; }
     return QLDPC_OK;
 }
 
 /* every argument check of qldpc_mc_sweep: nothing is touched before all of them pass */
 static int mc_sweep_args(const qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg)
 {
-    if (cfg->reserved[0] || cfg->reserved[1]) { qldpc_set_error("mc_sweep: reserved fields %d, %d must be zero", cfg->reserved[0], cfg->reserved[1]); return QLDPC_EINVAL; }
-    if (mc->soft) { qldpc_set_error("mc_sweep: a channel table is in force (qldpc_mc_set_channel); the sweep's points are points of the BSC"); return QLDPC_ESTATE; }
-    if (cfg->n_points < 1 || cfg->n_points > QLDPC_MC_SWEEP_MAX_POINTS) { qldpc_set_error("mc_sweep: n_points=%d outside 1 .. %d", cfg->n_points, QLDPC_MC_SWEEP_MAX_POINTS); return QLDPC_ESIZE; }
-    if (cfg->chunk < 0 || cfg->chunk > mc->batch) { qldpc_set_error("mc_sweep: chunk=%d outside [0, batch=%d]", cfg->chunk, mc->batch); return QLDPC_ESIZE; }
-    if (cfg->max_frames == 0) { qldpc_set_error("mc_sweep: max_frames=0"); return QLDPC_ESIZE; }
+    const int rc = mc_rounds_args(mc, "mc_sweep", cfg->reserved,
+                                  "mc_sweep: a channel table is in force (qldpc_mc_set_channel); the sweep's points are points of the BSC", "n_points",
+                                  cfg->n_points, nullptr, cfg->chunk, cfg->max_frames);
+    if (rc) return rc;
     if (!cfg->points || cfg->n_order < 0 || (cfg->n_order > 0 && !cfg->punct_order)) { qldpc_set_error("mc_sweep: a missing array (points, or punct_order with n_order=%d)", cfg->n_order); return QLDPC_EINVAL; }
     std::vector<bool> seen((size_t)mc->N, false);
     for (int i = 0; i < cfg->n_order; i++) {
@@ -965,9 +982,9 @@ static int mc_sweep_args(const qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg)
 struct mc_rounds_job {
     int P, C;
     uint64_t first_frame, max_frames, max_fe;
-    const mc_point_row *rows;          /* [P] {threshold, |LLR|} of the sweep's points, or the strata's {weight, |LLR|} in the same layout */
+    const mc_row *rows;                /* [P] {threshold, |LLR|} of the sweep's points, or {weight, |LLR|} of the strata */
     const uint32_t *erows;             /* [P][Wn] the erase rows, NULL = nothing is erased */
-    int weight_key_bits;               /* 0: the BSC of the rows' thresholds (mc_channel_points); 1 .. 32: the rows' fixed weights (mc_channel_weight) */
+    int weight_key_bits;               /* 0: the BSC of the rows' thresholds (mc_channel); 1 .. 32: the rows' fixed weights (mc_channel_weight) */
     int owner;                         /* MC_ROWS_*: whose rows the device holds from here on */
 };
 
@@ -975,27 +992,25 @@ static int mc_rounds(qldpc_mc *mc, const mc_rounds_job &job, uint64_t *last_roun
 {
     const hipStream_t s = mc->dec->stream;
     const int P = job.P, C = job.C, S = mc->batch / C;
-    const unsigned Wn = (unsigned)mc->Wn, Wk = (unsigned)mc->Wk;
-    const size_t B = (size_t)mc->batch, bins = (size_t)mc->n_ite + 1;
+    const size_t B = (size_t)mc->batch, Wn = (size_t)mc->Wn, bins = (size_t)mc->n_ite + 1;
     const uint64_t max_frames = job.max_frames, max_fe = job.max_fe;
-    const bool any_erase = job.erows != nullptr;
-    const mc_stratum_row no_row = {0u, 0.0f};      /* mc_channel_weight reads the rows of the round */
     /* the tables of a round inside the one buffer */
     uint64_t *const h_frame = (uint64_t *)mc->h_slots;
     uint32_t *const h_point = (uint32_t *)(mc->h_slots + B), *const h_cpoint = h_point + B, *const h_cstart = h_cpoint + B, *const h_clen = h_cstart + B;
-    const uint64_t *const d_frame = (const uint64_t *)mc->d_slots;
     const uint32_t *const d_point = (const uint32_t *)(mc->d_slots + B), *const d_cpoint = d_point + B, *const d_cstart = d_cpoint + B, *const d_clen = d_cstart + B;
+    const mc_slots sl = {(const uint64_t *)mc->d_slots, 0, d_point, mc->d_points, {0u, 0.0f}};
 
     HIPCHK(hipStreamSynchronize(s));      /* a queued kernel may still read the rows of an earlier call */
-    HIPCHK(hipMemcpy(mc->d_points, job.rows, sizeof(mc_point_row) * (size_t)P, hipMemcpyHostToDevice));
-    if (any_erase) HIPCHK(hipMemcpy(mc->d_prows, job.erows, sizeof(uint32_t) * (size_t)P * Wn, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(mc->d_points, job.rows, sizeof(mc_row) * (size_t)P, hipMemcpyHostToDevice));
+    if (job.erows) HIPCHK(hipMemcpy(mc->d_prows, job.erows, sizeof(uint32_t) * (size_t)P * Wn, hipMemcpyHostToDevice));
     mc->rows_owner = job.owner;
-    HIPCHK(hipMemsetAsync(mc->d_wctr, 0, sizeof(mc_u64) * (size_t)P * MCW_COUNTERS, s));
+    HIPCHK(hipMemsetAsync(mc->d_wctr, 0, sizeof(mc_u64) * (size_t)P * MC_POINT_COUNTERS, s));
     HIPCHK(hipMemsetAsync(mc->d_whist, 0, sizeof(mc_u64) * (size_t)P * bins, s));
 
     std::vector<uint64_t> done((size_t)P, 0), fe((size_t)P, 0);
     std::vector<int> give((size_t)P);
     int rc = QLDPC_OK;
+    double *const stage[7] = {&res->source_ms, &res->encode_ms, &res->channel_ms, &res->load_ms, &res->erase_ms, &res->decode_ms, &res->monitor_ms};
     const auto t_start = std::chrono::steady_clock::now();
     for (uint64_t round = 0;; round++) {
         const int n_chunks = mc_sweep_deal(P, C, S, max_frames, max_fe, done.data(), fe.data(), give.data());
@@ -1009,57 +1024,40 @@ static int mc_rounds(qldpc_mc *mc, const mc_rounds_job &job, uint64_t *last_roun
                 for (unsigned i = 0; i < len; i++, nb++) { h_frame[nb] = job.first_frame + k0 + i; h_point[nb] = (uint32_t)q; }
                 last_round[q] = round;
             }
-        const unsigned ti = nb * Wk, tn = nb * Wn;
-        HIPCHK(hipEventRecord(mc->wev[0], s));
+        HIPCHK(hipEventRecord(mc->ev[0], s));
         HIPCHK(hipMemcpyAsync(mc->d_slots, mc->h_slots, sizeof(mc_u64) * 3 * B, hipMemcpyHostToDevice, s));      /* pinned: the host rewrites it after the sync below */
-        if (mc->source == QLDPC_MC_SOURCE_ZERO) HIPCHK(hipMemsetAsync(mc->d_info, 0, sizeof(uint32_t) * ti, s));
-        else {
-            hipLaunchKernelGGL(mc_source_points, dim3(mc_blocks(ti)), dim3(MC_LANES), 0, s, mc->d_info, ti, Wk, mc->K, mc->seed, d_frame);
-            LAUNCHCHK();
-        }
-        HIPCHK(hipEventRecord(mc->wev[1], s));
-        if ((rc = qldpc_encode_packed_dev(mc->enc, mc->d_info, mc->d_cw, (int)nb, (void *)s))) return rc;
-        HIPCHK(hipEventRecord(mc->wev[2], s));
-        if (job.weight_key_bits)
-            hipLaunchKernelGGL(mc_channel_weight, dim3(nb), dim3(MC_PAT_LANES), 0, s, (const uint32_t *)mc->d_cw, mc->d_rx, (const uint4 *)mc->d_cls, Wn, mc->seed, (uint64_t)0,
-                               d_frame, d_point, (const mc_stratum_row *)mc->d_points, no_row, job.weight_key_bits, mc_threshold(mc->parity_ber), mc->d_mag);
-        else
-            hipLaunchKernelGGL(mc_channel_points, dim3(mc_blocks(tn)), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_cw, mc->d_rx, (const uint4 *)mc->d_cls, tn, Wn, mc->seed,
-                               d_frame, d_point, (const mc_point_row *)mc->d_points, mc_threshold(mc->parity_ber), mc->d_mag);
-        LAUNCHCHK();
-        HIPCHK(hipEventRecord(mc->wev[3], s));
-        if ((rc = qldpc_load_bits_dev(mc->dec, mc->d_rx, mc->d_mag, mc->d_cls, (int)nb))) return rc;
-        HIPCHK(hipEventRecord(mc->wev[4], s));
-        if (any_erase) {
-            hipLaunchKernelGGL(mc_expand_points, dim3(mc_blocks(((size_t)tn + 3) / 4)), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_prows, mc->d_erase, tn, Wn, d_point);
-            LAUNCHCHK();
-            if ((rc = qldpc_load_erasures_dev(mc->dec, mc->d_erase, (int)nb))) return rc;
-        }
-        HIPCHK(hipEventRecord(mc->wev[5], s));
+        if ((rc = mc_generate_load(mc, sl, (int)nb, s, mc->ev, mc->ev[3], job.weight_key_bits))) return rc;
+        HIPCHK(hipEventRecord(mc->ev[4], s));
+        if (job.erows && (rc = mc_erase(mc, mc->d_prows, sl, (int)nb, 1, s))) return rc;
+        HIPCHK(hipEventRecord(mc->ev[5], s));
         if ((rc = qldpc_run(mc->dec))) return rc;
-        HIPCHK(hipEventRecord(mc->wev[6], s));
-        if ((rc = qldpc_fetch_packed_dev(mc->dec, mc->d_out))) return rc;
-        if ((rc = qldpc_fetch_status_dev(mc->dec, mc->d_iters, mc->d_ok))) return rc;
+        HIPCHK(hipEventRecord(mc->ev[6], s));
+        if ((rc = mc_fetch(mc))) return rc;
         const unsigned wpc = std::min((unsigned)C, std::max(1u, (unsigned)MC_MAX_WAVES / nc)), waves = nc * wpc;
-        hipLaunchKernelGGL(mc_monitor_points, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_out, (const uint32_t *)mc->d_cw, (const uint32_t *)mc->d_rx,
-                           (const uint32_t *)mc->d_info_mask, (const uint32_t *)mc->d_chan_mask, (const int *)mc->d_iters, (const int *)mc->d_ok, nc, wpc, d_cpoint, d_cstart,
-                           d_clen, Wn, mc->n_ite, mc->channel_vns, mc->d_wctr, mc->d_whist);
+        hipLaunchKernelGGL(mc_monitor_points, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, mc_decoded_of(mc), nc, wpc, d_cpoint, d_cstart, d_clen, mc->channel_vns,
+                           mc->d_wctr, mc->d_whist);
         LAUNCHCHK();
-        HIPCHK(hipEventRecord(mc->wev[7], s));
-        HIPCHK(hipMemcpyAsync(mc->h_wctr, mc->d_wctr, sizeof(mc_u64) * (size_t)P * MCW_COUNTERS, hipMemcpyDeviceToHost, s));      /* the one read-back of a round */
-        HIPCHK(hipStreamSynchronize(s));
-        double *const stage[7] = {&res->source_ms, &res->encode_ms, &res->channel_ms, &res->load_ms, &res->erase_ms, &res->decode_ms, &res->monitor_ms};
-        for (int k = 0; k < 7; k++) {
-            float ms = 0.0f;
-            HIPCHK(hipEventElapsedTime(&ms, mc->wev[k], mc->wev[k + 1]));
-            *stage[k] += (double)ms;
-        }
-        for (int q = 0; q < P; q++) { done[(size_t)q] = mc->h_wctr[(size_t)q * MCW_COUNTERS + MC_FRAMES]; fe[(size_t)q] = mc->h_wctr[(size_t)q * MCW_COUNTERS + MC_FRAME_ERRORS]; }
+        if ((rc = mc_round_end(mc, mc->h_wctr, mc->d_wctr, (size_t)P * MC_POINT_COUNTERS, stage, 7, s))) return rc;
+        for (int q = 0; q < P; q++) { done[(size_t)q] = mc->h_wctr[(size_t)q * MC_POINT_COUNTERS + MC_FRAMES]; fe[(size_t)q] = mc->h_wctr[(size_t)q * MC_POINT_COUNTERS + MC_FRAME_ERRORS]; }
         res->rounds++; res->batches++;
     }
-    for (int q = 0; q < P; q++) res->frames += mc->h_wctr[(size_t)q * MCW_COUNTERS + MC_FRAMES];
+    for (int q = 0; q < P; q++) res->frames += mc->h_wctr[(size_t)q * MC_POINT_COUNTERS + MC_FRAMES];
     res->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     return QLDPC_OK;
+}
+
+/* row q of the last rounds into the stat row of a point or a stratum */
+template <typename S> static void mc_row_out(const qldpc_mc *mc, int q, uint64_t max_frames, uint64_t last_round, S *st)
+{
+    mc_counters_out(st, mc->h_wctr + (size_t)q * MC_POINT_COUNTERS);
+    st->closed_by = st->frames >= max_frames ? QLDPC_MC_CLOSED_MAX_FRAMES : QLDPC_MC_CLOSED_MAX_FE;
+    st->last_round = last_round;
+}
+
+/* histogram row `row` of the last rounds, for qldpc_mc_sweep_hist and qldpc_mc_strata_hist */
+static int mc_row_hist(qldpc_mc *mc, int row, uint64_t *hist, int cap)
+{
+    return mc_hist_out(mc, mc->d_whist + (size_t)row * (size_t)(mc->n_ite + 1), hist, cap);
 }
 
 extern "C" int qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc_mc_sweep_result *res)
@@ -1071,12 +1069,11 @@ extern "C" int qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc
     const int P = cfg->n_points;
     const size_t Wn = (size_t)mc->Wn;
     /* per sweep: the point rows and the erase rows (fixed set OR prefix), built here once */
-    std::vector<mc_point_row> prow((size_t)P);
+    std::vector<mc_row> prow((size_t)P);
     std::vector<uint32_t> erows((size_t)P * Wn, 0u);
     bool any_erase = false;
     for (int q = 0; q < P; q++) {
-        prow[(size_t)q].t_channel = mc_threshold(cfg->points[q].qber);
-        prow[(size_t)q].mag = qldpc_bsc_llr((float)cfg->points[q].qber);
+        prow[(size_t)q] = {mc_threshold(cfg->points[q].qber), qldpc_bsc_llr((float)cfg->points[q].qber)};
         uint32_t *row = erows.data() + (size_t)q * Wn;
         if (mc->n_fixed) memcpy(row, mc->h_fixed.data(), sizeof(uint32_t) * Wn);
         for (int i = 0; i < cfg->points[q].n_punct; i++) { const int v = cfg->punct_order[i]; row[v >> 5] |= 0x80000000u >> (v & 31); }
@@ -1088,24 +1085,14 @@ extern "C" int qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc
                                any_erase ? erows.data() : nullptr, 0, MC_ROWS_SWEEP};
     std::vector<uint64_t> last((size_t)P, 0);
     if ((rc = mc_rounds(mc, job, last.data(), res))) return rc;
-    for (int q = 0; q < P; q++) {
-        const mc_u64 *c = mc->h_wctr + (size_t)q * MCW_COUNTERS;
-        qldpc_mc_point_stat &st = mc->wstats[(size_t)q];
-        st.frames = c[MC_FRAMES]; st.frame_errors = c[MC_FRAME_ERRORS]; st.bit_errors = c[MC_BIT_ERRORS]; st.undetected = c[MC_UNDETECTED];
-        st.not_converged = c[MC_NOT_CONVERGED]; st.iter_sum = c[MC_ITER_SUM]; st.iter_max = c[MC_ITER_MAX];
-        st.channel_flips = c[MC_FLIPS]; st.channel_bits = c[MC_CHANNEL_BITS];
-        st.closed_by = st.frames >= cfg->max_frames ? QLDPC_MC_CLOSED_MAX_FRAMES : QLDPC_MC_CLOSED_MAX_FE;
-        st.last_round = last[(size_t)q];
-    }
+    for (int q = 0; q < P; q++) mc_row_out(mc, q, cfg->max_frames, last[(size_t)q], &mc->wstats[(size_t)q]);
     return QLDPC_OK;
 }
 
 extern "C" int qldpc_mc_sweep_stats(qldpc_mc *mc, qldpc_mc_point_stat *rows, int cap)
 {
-    if (!mc || cap < 0 || (cap && !rows)) return QLDPC_EINVAL;
-    const size_t n = std::min((size_t)cap, mc->wstats.size());
-    if (n) memcpy(rows, mc->wstats.data(), sizeof(qldpc_mc_point_stat) * n);
-    return (int)mc->wstats.size();
+    if (!mc) return QLDPC_EINVAL;
+    return mc_stats_out(mc->wstats, rows, cap);
 }
 
 extern "C" int qldpc_mc_sweep_hist(qldpc_mc *mc, int point, uint64_t *hist, int cap)
@@ -1113,11 +1100,7 @@ extern "C" int qldpc_mc_sweep_hist(qldpc_mc *mc, int point, uint64_t *hist, int 
     if (!mc || cap < 0 || (cap && !hist)) return QLDPC_EINVAL;
     if (point < 0 || (size_t)point >= mc->wstats.size()) { qldpc_set_error("mc_sweep_hist: point=%d, the last sweep had %d", point, (int)mc->wstats.size()); return QLDPC_ESIZE; }
     if (mc->rows_owner != MC_ROWS_SWEEP) { qldpc_set_error("mc_sweep_hist: the device rows hold a later qldpc_mc_strata run"); return QLDPC_ESTATE; }
-    const int bins = std::min(cap, mc->n_ite + 1);
-    HIPCHK(hipSetDevice(mc->device));
-    HIPCHK(hipStreamSynchronize(mc->dec->stream));
-    if (bins) HIPCHK(hipMemcpy(hist, mc->d_whist + (size_t)point * (size_t)(mc->n_ite + 1), sizeof(mc_u64) * (size_t)bins, hipMemcpyDeviceToHost));
-    return mc->n_ite + 1;
+    return mc_row_hist(mc, point, hist, cap);
 }
 
 /* ------------------------------------------------------------------ fixed-weight error strata ---- */
@@ -1137,30 +1120,19 @@ extern "C" int qldpc_mc_weight_frames_dev(qldpc_mc *mc, uint64_t first_frame, in
     if ((uint64_t)n_frames * (uint64_t)mc->Wn >= (1ull << 31)) { qldpc_set_error("mc_weight_frames_dev: %d frames of N = %d pass 2^31 words", n_frames, mc->N); return QLDPC_ESIZE; }
     if (n_frames == 0) return QLDPC_OK;
     HIPCHK(hipSetDevice(mc->device));
-    const hipStream_t s = mc->dec->stream;
-    if ((rc = mc_generate(mc, first_frame, n_frames, 0.0, d_info, d_cw, nullptr, nullptr, s)) || !d_rx) return rc;      /* source and encoder */
-    const mc_stratum_row one = {(uint32_t)weight, 0.0f};
-    hipLaunchKernelGGL(mc_channel_weight, dim3((unsigned)n_frames), dim3(MC_PAT_LANES), 0, s, (const uint32_t *)d_cw, d_rx, (const uint4 *)mc->d_cls, (unsigned)mc->Wn, mc->seed,
-                       first_frame, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (const mc_stratum_row *)nullptr, one,
-                       mc_key_bits(key_bits), mc_threshold(mc->parity_ber), (float *)nullptr);
-    LAUNCHCHK();
-    return QLDPC_OK;
+    return mc_generate(mc, mc_range(first_frame, (uint32_t)weight), n_frames, d_info, d_cw, d_rx, nullptr, mc->dec->stream, nullptr, nullptr, mc_key_bits(key_bits));
 }
 
 /* every argument check of qldpc_mc_strata: nothing is touched before all of them pass */
 static int mc_strata_args(const qldpc_mc *mc, const qldpc_mc_strata_cfg *cfg)
 {
-    if (cfg->reserved[0] || cfg->reserved[1]) { qldpc_set_error("mc_strata: reserved fields %d, %d must be zero", cfg->reserved[0], cfg->reserved[1]); return QLDPC_EINVAL; }
-    if (mc->soft) { qldpc_set_error("mc_strata: a channel table is in force (qldpc_mc_set_channel); error weights are weights of the BSC"); return QLDPC_ESTATE; }
-    if (cfg->n_strata < 1 || cfg->n_strata > QLDPC_MC_SWEEP_MAX_POINTS) { qldpc_set_error("mc_strata: n_strata=%d outside 1 .. %d", cfg->n_strata, QLDPC_MC_SWEEP_MAX_POINTS); return QLDPC_ESIZE; }
-    if (!(cfg->design_qber > 0.0 && cfg->design_qber < 0.5)) { qldpc_set_error("mc_strata: design_qber=%g outside (0, 0.5)", cfg->design_qber); return QLDPC_ESIZE; }
-    if (cfg->chunk < 0 || cfg->chunk > mc->batch) { qldpc_set_error("mc_strata: chunk=%d outside [0, batch=%d]", cfg->chunk, mc->batch); return QLDPC_ESIZE; }
-    if (cfg->max_frames == 0) { qldpc_set_error("mc_strata: max_frames=0"); return QLDPC_ESIZE; }
+    int rc = mc_rounds_args(mc, "mc_strata", cfg->reserved,
+                            "mc_strata: a channel table is in force (qldpc_mc_set_channel); error weights are weights of the BSC", "n_strata", cfg->n_strata,
+                            &cfg->design_qber, cfg->chunk, cfg->max_frames);
+    if (rc) return rc;
     if (!cfg->weights) { qldpc_set_error("mc_strata: a missing array (weights)"); return QLDPC_EINVAL; }
-    for (int q = 0; q < cfg->n_strata; q++) {
-        const int rc = mc_weight_args(mc, "mc_strata", cfg->weights[q], cfg->key_bits);
-        if (rc) return rc;
-    }
+    for (int q = 0; q < cfg->n_strata; q++)
+        if ((rc = mc_weight_args(mc, "mc_strata", cfg->weights[q], cfg->key_bits))) return rc;
     return QLDPC_OK;
 }
 
@@ -1172,11 +1144,11 @@ extern "C" int qldpc_mc_strata(qldpc_mc *mc, const qldpc_mc_strata_cfg *cfg, qld
     if (rc || (rc = mc_sweep_reserve(mc))) return rc;
     const int P = cfg->n_strata;
     const size_t Wn = (size_t)mc->Wn;
-    /* per call: the stratum rows in the layout of the point rows, and the fixed set as every stratum's erase row */
-    std::vector<mc_point_row> prow((size_t)P);
+    /* per call: the stratum rows, and the fixed set as every stratum's erase row */
+    std::vector<mc_row> prow((size_t)P);
     std::vector<uint32_t> erows;
     const float mag = qldpc_bsc_llr((float)cfg->design_qber);
-    for (int q = 0; q < P; q++) { prow[(size_t)q].t_channel = (uint32_t)cfg->weights[q]; prow[(size_t)q].mag = mag; }
+    for (int q = 0; q < P; q++) prow[(size_t)q] = {(uint32_t)cfg->weights[q], mag};
     if (mc->n_fixed) for (int q = 0; q < P; q++) erows.insert(erows.end(), mc->h_fixed.begin(), mc->h_fixed.begin() + (ptrdiff_t)Wn);
     mc->tstats.assign((size_t)P, qldpc_mc_stratum_stat());
     for (int q = 0; q < P; q++) mc->tstats[(size_t)q].weight = cfg->weights[q];
@@ -1184,24 +1156,14 @@ extern "C" int qldpc_mc_strata(qldpc_mc *mc, const qldpc_mc_strata_cfg *cfg, qld
                                mc->n_fixed ? erows.data() : nullptr, mc_key_bits(cfg->key_bits), MC_ROWS_STRATA};
     std::vector<uint64_t> last((size_t)P, 0);
     if ((rc = mc_rounds(mc, job, last.data(), res))) return rc;
-    for (int q = 0; q < P; q++) {
-        const mc_u64 *c = mc->h_wctr + (size_t)q * MCW_COUNTERS;
-        qldpc_mc_stratum_stat &st = mc->tstats[(size_t)q];
-        st.frames = c[MC_FRAMES]; st.frame_errors = c[MC_FRAME_ERRORS]; st.bit_errors = c[MC_BIT_ERRORS]; st.undetected = c[MC_UNDETECTED];
-        st.not_converged = c[MC_NOT_CONVERGED]; st.iter_sum = c[MC_ITER_SUM]; st.iter_max = c[MC_ITER_MAX];
-        st.channel_flips = c[MC_FLIPS]; st.channel_bits = c[MC_CHANNEL_BITS];
-        st.closed_by = st.frames >= cfg->max_frames ? QLDPC_MC_CLOSED_MAX_FRAMES : QLDPC_MC_CLOSED_MAX_FE;
-        st.last_round = last[(size_t)q];
-    }
+    for (int q = 0; q < P; q++) mc_row_out(mc, q, cfg->max_frames, last[(size_t)q], &mc->tstats[(size_t)q]);
     return QLDPC_OK;
 }
 
 extern "C" int qldpc_mc_strata_stats(qldpc_mc *mc, qldpc_mc_stratum_stat *rows, int cap)
 {
-    if (!mc || cap < 0 || (cap && !rows)) return QLDPC_EINVAL;
-    const size_t n = std::min((size_t)cap, mc->tstats.size());
-    if (n) memcpy(rows, mc->tstats.data(), sizeof(qldpc_mc_stratum_stat) * n);
-    return (int)mc->tstats.size();
+    if (!mc) return QLDPC_EINVAL;
+    return mc_stats_out(mc->tstats, rows, cap);
 }
 
 extern "C" int qldpc_mc_strata_hist(qldpc_mc *mc, int stratum, uint64_t *hist, int cap)
@@ -1209,9 +1171,5 @@ extern "C" int qldpc_mc_strata_hist(qldpc_mc *mc, int stratum, uint64_t *hist, i
     if (!mc || cap < 0 || (cap && !hist)) return QLDPC_EINVAL;
     if (stratum < 0 || (size_t)stratum >= mc->tstats.size()) { qldpc_set_error("mc_strata_hist: stratum=%d, the last run had %d", stratum, (int)mc->tstats.size()); return QLDPC_ESIZE; }
     if (mc->rows_owner != MC_ROWS_STRATA) { qldpc_set_error("mc_strata_hist: the device rows hold a later qldpc_mc_sweep"); return QLDPC_ESTATE; }
-    const int bins = std::min(cap, mc->n_ite + 1);
-    HIPCHK(hipSetDevice(mc->device));
-    HIPCHK(hipStreamSynchronize(mc->dec->stream));
-    if (bins) HIPCHK(hipMemcpy(hist, mc->d_whist + (size_t)stratum * (size_t)(mc->n_ite + 1), sizeof(mc_u64) * (size_t)bins, hipMemcpyDeviceToHost));
-    return mc->n_ite + 1;
+    return mc_row_hist(mc, stratum, hist, cap);
 }

@@ -19,6 +19,28 @@ int qldpc_mc_philox_host(const uint32_t counter[4], const uint32_t key[2], uint3
     return QLDPC_OK;
 }
 
+/* *out = the padded class map of (K, N, info_bits_pos, vn_class) in the four-per-word form of mc_flip_word: 8 ceil(N / 32) words that the caller
+ * frees; *channel_vns (optional) grows by the number of QLDPC_VN_CHANNEL VNs.  On an error *out = NULL and the text goes under the caller's name */
+static int mc_class_words(const char *who, int K, int N, const int *info_bits_pos, const uint8_t *vn_class, uint32_t **out, int *channel_vns)
+{
+    const int Wn = (N + 31) / 32;
+    uint8_t *cls = (uint8_t *)malloc(32 * (size_t)Wn);
+    uint32_t *cls4 = (uint32_t *)malloc(4 * 8 * (size_t)Wn);
+    int rc = QLDPC_OK;
+    if (!cls || !cls4) rc = QLDPC_ENOMEM;
+    else if (mc_classes(K, N, info_bits_pos, vn_class, cls, NULL)) {
+        qldpc_set_error("%s: info_bits_pos outside [0, %d) or repeated, or a VN class above 2", who, N);
+        rc = QLDPC_EINVAL;
+    } else {
+        mc_pack_classes(cls, Wn, cls4);
+        for (int v = 0; v < N && channel_vns; v++) *channel_vns += cls[v] == 0;
+    }
+    free(cls);
+    if (rc) { free(cls4); cls4 = NULL; }
+    *out = cls4;
+    return rc;
+}
+
 int qldpc_mc_frames_host(int K, int N, const int *info_bits_pos, const uint8_t *vn_class, uint64_t seed, double qber, double parity_ber,
                          uint64_t first_frame, int n_frames, uint32_t *info_words, uint32_t *flip_words)
 {
@@ -34,22 +56,15 @@ int qldpc_mc_frames_host(int K, int N, const int *info_bits_pos, const uint8_t *
         for (int f = 0; f < n_frames; f++)
             for (int j = 0; j < Wk; j++) info_words[(size_t)f * Wk + j] = mc_info_word(seed, first_frame + (uint64_t)f, (uint32_t)j, K);
     if (!flip_words) return QLDPC_OK;
-    uint8_t *cls = (uint8_t *)malloc(32 * (size_t)Wn);
-    uint32_t *cls4 = (uint32_t *)malloc(4 * 8 * (size_t)Wn);
-    int rc = QLDPC_OK;
-    if (!cls || !cls4) rc = QLDPC_ENOMEM;
-    else if (mc_classes(K, N, info_bits_pos, vn_class, cls, NULL)) {
-        qldpc_set_error("mc_frames_host: info_bits_pos outside [0, %d) or repeated, or a VN class above 2", N);
-        rc = QLDPC_EINVAL;
-    } else {
-        mc_pack_classes(cls, Wn, cls4);
-        const uint32_t tc = mc_threshold(qber), tp = mc_threshold(parity_ber);
-        for (int f = 0; f < n_frames; f++)
-            for (int w = 0; w < Wn; w++)
-                flip_words[(size_t)f * Wn + w] = mc_flip_word(seed, first_frame + (uint64_t)f, (uint32_t)w, cls4 + 8 * (size_t)w, tc, tp);
-    }
-    free(cls); free(cls4);
-    return rc;
+    uint32_t *cls4;
+    const int rc = mc_class_words("mc_frames_host", K, N, info_bits_pos, vn_class, &cls4, NULL);
+    if (rc) return rc;
+    const uint32_t tc = mc_threshold(qber), tp = mc_threshold(parity_ber);
+    for (int f = 0; f < n_frames; f++)
+        for (int w = 0; w < Wn; w++)
+            flip_words[(size_t)f * Wn + w] = mc_flip_word(seed, first_frame + (uint64_t)f, (uint32_t)w, cls4 + 8 * (size_t)w, tc, tp);
+    free(cls4);
+    return QLDPC_OK;
 }
 
 int qldpc_mc_awgn_table(double sigma, double rmax, int maxq, uint64_t *cum0, uint64_t *cum1, float *value)
@@ -79,18 +94,13 @@ int qldpc_mc_llr_host(int K, int N, const int *info_bits_pos, const uint8_t *vn_
     if (table->reserved[0] || table->reserved[1]) { qldpc_set_error("mc_llr_host: reserved words of the table must be zero"); return QLDPC_EINVAL; }
     const int Wn = (N + 31) / 32;
     mc_soft_table *t = (mc_soft_table *)malloc(sizeof(*t));
-    uint8_t *cls = (uint8_t *)malloc(32 * (size_t)Wn);
-    uint32_t *cls4 = (uint32_t *)malloc(4 * 8 * (size_t)Wn);
+    uint32_t *cls4 = NULL;
     int rc = QLDPC_OK;
-    if (!t || !cls || !cls4) rc = QLDPC_ENOMEM;
+    if (!t) rc = QLDPC_ENOMEM;
     else if ((rc = mc_soft_table_build(table->levels, table->cum[0], table->cum[1], table->value, t))) {
         qldpc_set_error("mc_llr_host: levels=%d outside 2 .. %d, or a row that decreases or passes 2^32", table->levels, MC_SOFT_MAX_LEVELS);
         rc = rc == -1 ? QLDPC_ESIZE : QLDPC_EINVAL;
-    } else if (mc_classes(K, N, info_bits_pos, vn_class, cls, NULL)) {
-        qldpc_set_error("mc_llr_host: info_bits_pos outside [0, %d) or repeated, or a VN class above 2", N);
-        rc = QLDPC_EINVAL;
-    } else {
-        mc_pack_classes(cls, Wn, cls4);
+    } else if (!(rc = mc_class_words("mc_llr_host", K, N, info_bits_pos, vn_class, &cls4, NULL))) {
         const uint32_t tp = mc_threshold(parity_ber);
         for (int f = 0; f < n_frames; f++)
             for (int w = 0; w < Wn; w++) {
@@ -108,7 +118,7 @@ int qldpc_mc_llr_host(int K, int N, const int *info_bits_pos, const uint8_t *vn_
                 if (flip_words) flip_words[(size_t)f * Wn + w] = flips;
             }
     }
-    free(t); free(cls); free(cls4);
+    free(t); free(cls4);
     return rc;
 }
 
@@ -168,24 +178,14 @@ int qldpc_mc_weight_frames_host(int K, int N, const int *info_bits_pos, const ui
     if (n_frames < 0 || (!info_words && !flip_words) || (n_frames > 0 && flip_words && !weights)) return QLDPC_EINVAL;
     if (n_frames == 0) return QLDPC_OK;
     const int Wk = (K + 31) / 32, Wn = (N + 31) / 32, kb = mc_key_bits(key_bits);
-    uint8_t *cls = (uint8_t *)malloc(32 * (size_t)Wn);
-    uint32_t *cls4 = (uint32_t *)malloc(4 * 8 * (size_t)Wn);
-    int rc = QLDPC_OK, channel_vns = 0;
-    if (!cls || !cls4) rc = QLDPC_ENOMEM;
-    else if (mc_classes(K, N, info_bits_pos, vn_class, cls, NULL)) {
-        qldpc_set_error("mc_weight_frames_host: info_bits_pos outside [0, %d) or repeated, or a VN class above 2", N);
-        rc = QLDPC_EINVAL;
-    } else {
-        for (int v = 0; v < N; v++) channel_vns += cls[v] == 0;
-        for (int f = 0; f < n_frames && flip_words; f++)
-            if (weights[f] < 0 || weights[f] > channel_vns) {
-                qldpc_set_error("mc_weight_frames_host: weights[%d]=%d outside [0, %d channel VNs]", f, weights[f], channel_vns);
-                rc = QLDPC_ESIZE;
-                break;
-            }
-    }
-    if (rc) { free(cls); free(cls4); return rc; }      /* nothing is written by a refused call */
-    mc_pack_classes(cls, Wn, cls4);
+    uint32_t *cls4;
+    int channel_vns = 0, rc = mc_class_words("mc_weight_frames_host", K, N, info_bits_pos, vn_class, &cls4, &channel_vns);
+    for (int f = 0; f < n_frames && flip_words && !rc; f++)
+        if (weights[f] < 0 || weights[f] > channel_vns) {
+            qldpc_set_error("mc_weight_frames_host: weights[%d]=%d outside [0, %d channel VNs]", f, weights[f], channel_vns);
+            rc = QLDPC_ESIZE;
+        }
+    if (rc) { free(cls4); return rc; }      /* nothing is written by a refused call */
     if (info_words)
         for (int f = 0; f < n_frames; f++)
             for (int j = 0; j < Wk; j++) info_words[(size_t)f * Wk + j] = mc_info_word(seed, first_frame + (uint64_t)f, (uint32_t)j, K);
@@ -213,7 +213,7 @@ int qldpc_mc_weight_frames_host(int K, int N, const int *info_bits_pos, const ui
             equal += (uint32_t)__builtin_popcount(eq);
         }
     }
-    free(cls); free(cls4);
+    free(cls4);
     return QLDPC_OK;
 }
 

@@ -102,6 +102,18 @@ def counters(res):
     return {k: int(res[k]) for k in COUNTERS}
 
 
+RUN_STAGES = ("source", "encode", "channel", "load", "decode", "monitor")      # every stage of run, sweep and strata that launches a kernel in every call
+
+
+def stage_times(res, launched=RUN_STAGES):
+    """every stage time of a result is finite and not negative, and positive where the stage launched a kernel in that call"""
+    for k, v in res.items():
+        if k.endswith("_ms"):
+            assert np.isfinite(v) and v >= 0, (k, v)
+    for k in launched:
+        assert res[k + "_ms"] > 0, (k, res)
+
+
 @pytest.mark.parametrize("name", ["peg", "ira"])
 @pytest.mark.parametrize("first,n", [(0, 192), (FAR, 192), (3, 70)])
 def test_device_frames_equal_the_host_mirror(q, setups, name, first, n):
@@ -152,9 +164,76 @@ def test_run_equals_the_oracle_counter_for_counter(q, setups, name, kind):
     mc = q.MonteCarlo(s.decoder(kind), s.enc, seed=SEED)
     res = mc.run(QBER[name], 0, 192)
     assert counters(res) == ctr
-    assert res["batches"] == 1 and res["next_frame"] == 192 and res["decode_ms"] > 0
+    assert res["batches"] == 1 and res["next_frame"] == 192 and res["decode_ms"] > 0 and res["total_ms"] > 0
+    stage_times(res)
     assert (mc.iter_hist() == hist).all() and int(hist.sum()) == 192
     assert (mc.failed_frames() == failed).all()
+
+
+def test_monitor_rows_in_several_trips(q, O):
+    """N = 8300: 260 codeword words, so the word loop of a monitor wave (64 lanes) takes four full trips and a fifth with four live lanes, and the
+    last word holds 12 VNs; every other monitor test stays inside one trip.  The class map of test_mc_strata_gpu.test_final_pass_in_several_trips
+    (every fifth VN pinned, parity_ber 0.05) spreads the channel VNs over the whole frame.  16 frames across the carry of the frame index, two
+    NMS iterations, through all three monitor kernels: run over the 16, search as 2 patterns x 8 frames (nothing punctured, so the frames are
+    those of the run), sweep as 2 points x 8 frames in chunks of 4 (both points at the same QBER: each holds frames 0 .. 7); every counter row,
+    histogram and the failed-frame list against mc_frames_host -> encoder -> LLRs -> CPU oracle.
+    Asserted on the reference alone, among the first 8 frames, which all three paths see: a frame with info-bit errors beyond the first trip and
+    in the last word that holds info bits, and a frame with channel flips beyond the first trip and in word 259.  The IRA encoder's info bits
+    are VNs 0 .. 6599, so that last word is 206 (fourth trip) and no info bit lies in the fifth; the flips reach it.  The fifth trip is therefore
+    seen through channel_flips alone: mc_monitor and mc_monitor_points count them, mc_monitor_patterns does not read rx, so a pattern monitor that
+    stopped after four trips would still pass here (one that stopped after one, two or three would not).
+    QBER 0.03 by a scan with the oracle on the CPU over these 16 frames (two iterations leave 390 .. 483 info-bit errors in every frame; of
+    frames 0 .. 7, five have errors in word 206 and two have channel flips in word 259; 0.02 and 0.04 do as well)."""
+    code = q.Code.ira(8300, 6600)
+    enc = q.Encoder(code, "IRA")
+    K, N, pos, first, qber, n_ite = enc.K, code.N, enc.info_bits_pos, FAR + 90, 0.03, 2
+    Wn, last_info = (N + 31) // 32, (K - 1) // 32
+    assert (K, N, Wn) == (6600, 8300, 260) and (pos == np.arange(K)).all() and last_info == 206
+    cls = np.where(np.arange(N) % 5 == 4, 1, 0).astype(np.uint8)
+    var, chk = code.edges()
+    info_w, flip_w = q.mc_frames_host(K, N, SEED, qber, first, 16, vn_class=cls, parity_ber=0.05)
+    info = mc_ref.unpack(info_w, K)
+    cw = enc.encode(info)
+    assert (cw[:, pos] == info).all()
+    flips = mc_ref.unpack(flip_w, N)
+    y = cw ^ flips
+    mag, pin = np.float32(q.bsc_llr(qber)), np.float32(q.CONFIRMED_BIT_LLR)
+    llr = np.where(y == 1, -mag, mag).astype(np.float32)
+    llr[:, cls == 1] = np.where(y[:, cls == 1] == 1, -pin, pin)
+    r = O.decode(O.Graph.from_edges(N, code.M, var, chk), llr, "NMS", 0.75, n_ite, n_threads=8)
+    err = np.zeros((16, N), bool)
+    err[:, pos] = r["hard"][:, pos] != cw[:, pos]
+    be, ok, it, chan = err.sum(1), r["synd_ok"] != 0, r["iters"], flips.astype(bool) & (cls == 0)
+    print(be.tolist(), ok.tolist(), it.tolist(), chan.sum(1).tolist())
+    assert (err[:8, 64 * 32:].any(1) & err[:8, last_info * 32:].any(1)).any()                # info-bit errors past the first trip and in the last info word
+    assert (chan[:8, 64 * 32:259 * 32].any(1) & chan[:8, 259 * 32:].any(1)).any()          # channel flips past the first trip and in the last word
+
+    def row(a, b):
+        return dict(frames=b - a, bit_errors=int(be[a:b].sum()), frame_errors=int((be[a:b] > 0).sum()), undetected=int(((be[a:b] > 0) & ok[a:b]).sum()),
+                    not_converged=int((~ok[a:b]).sum()), iter_sum=int(it[a:b].sum()), iter_max=int(it[a:b].max()),
+                    channel_flips=int(chan[a:b].sum()), channel_bits=(b - a) * int((cls == 0).sum()))
+
+    def hist(a, b):
+        return np.bincount(it[a:b], minlength=n_ite + 1).astype(np.uint64)
+
+    dec = q.Decoder(code, K, n_ite, info_bits_pos=pos, rule="NMS", rule_param=0.75, n_frames=16)
+    mc = q.MonteCarlo(dec, enc, vn_class=cls, seed=SEED, parity_ber=0.05)
+    res = mc.run(qber, first, 16)
+    assert counters(res) == row(0, 16) and (mc.iter_hist() == hist(0, 16)).all()
+    assert (mc.failed_frames() == (first + np.nonzero(be > 0)[0]).astype(np.uint64)).all()
+    stage_times(res)
+    res = mc.search(qber, 0, 8, max_patterns=2, stop_at_goal=False, first_frame=first)
+    assert res["patterns"] == 2 and res["batches"] == 1
+    stage_times(res, ("pattern", "expand", "generate", "load", "decode", "monitor"))
+    for p, (a, b) in enumerate(((0, 8), (8, 16))):
+        ref = dict(row(a, b), pattern=p)
+        assert {k: int(res["stats"][k][p]) for k in res["stats"].dtype.names} == {k: ref[k] for k in res["stats"].dtype.names}, p
+    res = mc.sweep((qber, qber), first_frame=first, max_frames=8, chunk=4)
+    sweep_hist = mc.sweep_hist()
+    assert res["rounds"] == 1 and res["frames"] == 16
+    stage_times(res)
+    for p in range(2):
+        assert {k: int(res["points"][k][p]) for k in COUNTERS} == row(0, 8) and (sweep_hist[p] == hist(0, 8)).all(), p
 
 
 def test_spa_is_a_tolerance_class_frames_and_flips_only(q, setups):

@@ -9,7 +9,7 @@ import pytest
 
 import mc_ref
 import mc_search_ref
-from test_mc_gpu import KINDS, N_ITE, SEED, SIM, _Setup, counters
+from test_mc_gpu import KINDS, N_ITE, SEED, SIM, _Setup, counters, stage_times
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -147,6 +147,7 @@ def test_search_equals_the_oracle_row_for_row(q, setups, name, kind):
     res = mc.search(qber, n_punct, F, first_pattern=p0, max_patterns=N_PAT, stop_at_goal=False)
     same(res, ref)
     assert res["patterns"] == N_PAT and res["frames"] == N_PAT * F and res["batches"] == 1 and res["next_pattern"] == p0 + N_PAT and res["decode_ms"] > 0
+    stage_times(res, ("pattern", "expand", "generate", "load", "decode", "monitor"))
     assert int(res["stats"]["frames"].sum()) == N_PAT * F and ref["goal"] not in (p0, NONE)
 
 

@@ -11,7 +11,7 @@ import pytest
 import mc_ref
 import mc_strata_ref
 import mc_sweep_ref
-from test_mc_gpu import KINDS, N_ITE, QBER, SEED, _Setup
+from test_mc_gpu import KINDS, N_ITE, QBER, SEED, _Setup, stage_times
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,6 +94,7 @@ def same_rows(res, hist, sch, rows, weights):
         assert (st["last_round"] == sch["last_round"]).all() and (st["closed_by"] == sch["closed_by"]).all(), (st, sch)
         assert res["rounds"] == res["batches"] == sch["rounds"] and res["frames"] == int(sch["frames"].sum())
     assert res["decode_ms"] > 0 and res["channel_ms"] > 0 and res["total_ms"] > 0
+    stage_times(res)
 
 
 @pytest.mark.parametrize("name", ["peg", "ira"])

@@ -10,7 +10,7 @@ import pytest
 
 import mc_ref
 import mc_sweep_ref
-from test_mc_gpu import KINDS, N_ITE, SEED, _Setup
+from test_mc_gpu import KINDS, N_ITE, SEED, _Setup, stage_times
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -91,6 +91,7 @@ def same_rows(res, hist, sch, rows, qbers, n_punct=None):
         assert (pts["last_round"] == sch["last_round"]).all() and (pts["closed_by"] == sch["closed_by"]).all(), (pts, sch)
         assert res["rounds"] == res["batches"] == sch["rounds"] and res["frames"] == int(sch["frames"].sum())
     assert res["decode_ms"] > 0 and res["total_ms"] > 0
+    stage_times(res)
 
 
 def run_row(mc, qber, first, n):

@@ -7,7 +7,7 @@
 strata: one strata call over --points weights (evenly spaced over --weights lo:hi) with --max-frames per weight and no stop rule, |LLR| of
         --design-qber: wall time, rounds, frames and the hipEvent time of every stage per round.
 sweep:  one qldpc_mc_sweep over as many QBER points (weight / K each) on the same frames: the same stages; its channel stage is the BSC kernel
-        mc_channel_points, the baseline.
+        mc_channel over the slot tables of the round, the baseline.
 ratio:  channel_ms / decode_ms of both, and the strata's channel_ms over the sweep's (about 5 x the generator work is expected).
 No threshold and no claim: the file is the measurement.
 """
