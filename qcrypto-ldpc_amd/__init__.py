@@ -950,8 +950,9 @@ class McSweepResult(C.Structure):
         (n, C.c_double) for n in ("decode_ms", "source_ms", "encode_ms", "channel_ms", "load_ms", "erase_ms", "monitor_ms", "total_ms")]
 
 
-MC_POINT_STAT = np.dtype([("qber", np.float64), ("n_punct", np.int32), ("closed_by", np.int32)] + [(n, np.uint64) for n in (
-    "frames", "frame_errors", "bit_errors", "undetected", "not_converged", "iter_sum", "iter_max", "channel_flips", "channel_bits", "last_round")])
+_MC_ROW_COUNTERS = [(n, np.uint64) for n in ("frames", "frame_errors", "bit_errors", "undetected", "not_converged", "iter_sum", "iter_max", "channel_flips",
+                                              "channel_bits", "last_round")]          # the tail of a point row and of a stratum row
+MC_POINT_STAT = np.dtype([("qber", np.float64), ("n_punct", np.int32), ("closed_by", np.int32)] + _MC_ROW_COUNTERS)
 MC_SWEEP_MAX_POINTS = 4096
 MC_CLOSED_MAX_FE, MC_CLOSED_MAX_FRAMES = 1, 2          # closed_by of a point row
 
@@ -967,8 +968,7 @@ class McStrataCfg(C.Structure):
 
 
 McStrataResult = McSweepResult          # rounds, frames, batches, the stage times; channel_ms is the fixed-weight channel
-MC_STRATUM_STAT = np.dtype([("weight", np.int32), ("closed_by", np.int32)] + [(n, np.uint64) for n in (
-    "frames", "frame_errors", "bit_errors", "undetected", "not_converged", "iter_sum", "iter_max", "channel_flips", "channel_bits", "last_round")])
+MC_STRATUM_STAT = np.dtype([("weight", np.int32), ("closed_by", np.int32)] + _MC_ROW_COUNTERS)
 
 _dp = C.POINTER(C.c_double)
 _sig("qldpc_mc_weight_frames_host", C.c_int, [C.c_int, C.c_int, _ip, _u8p, C.c_uint64, C.c_double, C.c_uint64, C.c_int, _ip, C.c_int, _up, _up])
@@ -1012,21 +1012,36 @@ def _mc_class_arg(vn_class, N, where):
     return cls
 
 
-def mc_frames_host(K, N, seed, qber, first_frame, n_frames, info_bits_pos=None, vn_class=None, parity_ber=0.0):
-    """Frames [first_frame, first_frame + n_frames) of the Monte-Carlo frame definition on the host, no device needed ->
-    (info words [n, ceil(K/32)], flip words [n, ceil(N/32)]), uint32, MSB-first.  vn_class None: QLDPC_VN_CHANNEL at info_bits_pos
-    (None = 0 .. K-1), QLDPC_VN_PINNED elsewhere."""
+def _u64(x):
+    return int(x) & 0xFFFFFFFFFFFFFFFF
+
+
+def _fields(res):
+    return {name: getattr(res, name) for name, _ in res._fields_}
+
+
+def _ptr(a, typ):
+    return a.ctypes.data_as(typ) if a is not None else None
+
+
+def _mc_host_args(K, N, n_frames, info_bits_pos, vn_class, where):
+    """the prologue of the host mirrors -> (K, N, n, pos, cls, zeroed info words [n, ceil(K/32)], zeroed word rows [n, ceil(N/32)])"""
     K, N, n = int(K), int(N), int(n_frames)
     pos = None
     if info_bits_pos is not None:
         pos = _np_i32(info_bits_pos).ravel()
         if pos.size != K:
-            raise QldpcError(-6, "mc_frames_host: len(info_bits_pos) != K")
-    cls = _mc_class_arg(vn_class, N, "mc_frames_host")
-    info = np.zeros((max(n, 0), (max(K, 0) + 31) // 32), np.uint32)
-    flips = np.zeros((max(n, 0), (max(N, 0) + 31) // 32), np.uint32)
-    _chk(_L.qldpc_mc_frames_host(K, N, pos.ctypes.data_as(_ip) if pos is not None else None, cls.ctypes.data_as(_u8p) if cls is not None else None,
-                                 int(seed) & 0xFFFFFFFFFFFFFFFF, float(qber), float(parity_ber), int(first_frame) & 0xFFFFFFFFFFFFFFFF, n,
+            raise QldpcError(-6, "%s: len(info_bits_pos) != K" % where)
+    cls = _mc_class_arg(vn_class, N, where)
+    return K, N, n, pos, cls, np.zeros((max(n, 0), (max(K, 0) + 31) // 32), np.uint32), np.zeros((max(n, 0), (max(N, 0) + 31) // 32), np.uint32)
+
+
+def mc_frames_host(K, N, seed, qber, first_frame, n_frames, info_bits_pos=None, vn_class=None, parity_ber=0.0):
+    """Frames [first_frame, first_frame + n_frames) of the Monte-Carlo frame definition on the host, no device needed ->
+    (info words [n, ceil(K/32)], flip words [n, ceil(N/32)]), uint32, MSB-first.  vn_class None: QLDPC_VN_CHANNEL at info_bits_pos
+    (None = 0 .. K-1), QLDPC_VN_PINNED elsewhere."""
+    K, N, n, pos, cls, info, flips = _mc_host_args(K, N, n_frames, info_bits_pos, vn_class, "mc_frames_host")
+    _chk(_L.qldpc_mc_frames_host(K, N, _ptr(pos, _ip), _ptr(cls, _u8p), _u64(seed), float(qber), float(parity_ber), _u64(first_frame), n,
                                  info.ctypes.data_as(_up), flips.ctypes.data_as(_up)), "mc_frames_host")
     return info, flips
 
@@ -1035,7 +1050,7 @@ def mc_pattern_host(seed, pattern, n_cand, n_punct, key_bits=32):
     """Puncture pattern `pattern` of the Monte-Carlo pattern definition on the host, no device needed -> the n_punct chosen candidate
     indices (into an ascending candidate list of n_cand entries), ascending, int32.  key_bits below 32 coarsens the keys (tests only)."""
     idx = np.full(max(int(n_punct), 0), -1, np.int32)
-    _chk(_L.qldpc_mc_pattern_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(pattern) & 0xFFFFFFFFFFFFFFFF, int(n_cand), int(n_punct), int(key_bits),
+    _chk(_L.qldpc_mc_pattern_host(_u64(seed), _u64(pattern), int(n_cand), int(n_punct), int(key_bits),
                                   idx.ctypes.data_as(_ip)), "mc_pattern_host")
     return idx
 
@@ -1058,20 +1073,11 @@ def mc_weight_frames_host(K, N, seed, weights, first_frame, n_frames, key_bits=0
     """Frames [first_frame, first_frame + n_frames) of the fixed-weight frame definition on the host, no device needed: frame f flips the
     weights[f] channel VNs with the smallest stream-1 words (a scalar `weights` stands for every frame) -> (info words [n, ceil(K/32)],
     flip words [n, ceil(N/32)]), uint32, MSB-first.  key_bits below 32 coarsens the keys (tests only); the classes as mc_frames_host."""
-    K, N, n = int(K), int(N), int(n_frames)
-    pos = None
-    if info_bits_pos is not None:
-        pos = _np_i32(info_bits_pos).ravel()
-        if pos.size != K:
-            raise QldpcError(-6, "mc_weight_frames_host: len(info_bits_pos) != K")
-    cls = _mc_class_arg(vn_class, N, "mc_weight_frames_host")
+    K, N, n, pos, cls, info, flips = _mc_host_args(K, N, n_frames, info_bits_pos, vn_class, "mc_weight_frames_host")
     w = np.full(max(n, 0), int(weights), np.int32) if np.ndim(weights) == 0 else _np_i32(weights).ravel()
     if w.size != max(n, 0):
         raise QldpcError(-6, "mc_weight_frames_host: %d weights for %d frames" % (w.size, n))
-    info = np.zeros((max(n, 0), (max(K, 0) + 31) // 32), np.uint32)
-    flips = np.zeros((max(n, 0), (max(N, 0) + 31) // 32), np.uint32)
-    _chk(_L.qldpc_mc_weight_frames_host(K, N, pos.ctypes.data_as(_ip) if pos is not None else None, cls.ctypes.data_as(_u8p) if cls is not None else None,
-                                        int(seed) & 0xFFFFFFFFFFFFFFFF, float(parity_ber), int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, w.ctypes.data_as(_ip),
+    _chk(_L.qldpc_mc_weight_frames_host(K, N, _ptr(pos, _ip), _ptr(cls, _u8p), _u64(seed), float(parity_ber), _u64(first_frame), n, w.ctypes.data_as(_ip),
                                         int(key_bits), info.ctypes.data_as(_up), flips.ctypes.data_as(_up)), "mc_weight_frames_host")
     return info, flips
 
@@ -1121,25 +1127,16 @@ def mc_llr_host(K, N, seed, table, first_frame, n_frames, cw_words=None, info_bi
     """Frames [first_frame, first_frame + n_frames) of the quantised-channel definition on the host, no device needed: table =
     (cum0, cum1, value), cw_words [n, ceil(N/32)] the packed codewords (None = all-zero) -> (LLRs [n, N] float32, flip words
     [n, ceil(N/32)] uint32: the VNs whose LLR sign contradicts the codeword bit)"""
-    K, N, n = int(K), int(N), int(n_frames)
-    pos = None
-    if info_bits_pos is not None:
-        pos = _np_i32(info_bits_pos).ravel()
-        if pos.size != K:
-            raise QldpcError(-6, "mc_llr_host: len(info_bits_pos) != K")
-    cls = _mc_class_arg(vn_class, N, "mc_llr_host")
+    K, N, n, pos, cls, _, flips = _mc_host_args(K, N, n_frames, info_bits_pos, vn_class, "mc_llr_host")
     t, keep = _mc_channel_arg(*table, "mc_llr_host")
-    Wn = (max(N, 0) + 31) // 32
     cw = None
     if cw_words is not None:
         cw = np.ascontiguousarray(cw_words, dtype=np.uint32)
-        if cw.shape != (max(n, 0), Wn):
-            raise QldpcError(-6, "mc_llr_host: codeword words %s, expected (%d, %d)" % (cw.shape, n, Wn))
+        if cw.shape != flips.shape:
+            raise QldpcError(-6, "mc_llr_host: codeword words %s, expected (%d, %d)" % (cw.shape, n, flips.shape[1]))
     llr = np.zeros((max(n, 0), max(N, 0)), np.float32)
-    flips = np.zeros((max(n, 0), Wn), np.uint32)
-    _chk(_L.qldpc_mc_llr_host(K, N, pos.ctypes.data_as(_ip) if pos is not None else None, cls.ctypes.data_as(_u8p) if cls is not None else None,
-                              int(seed) & 0xFFFFFFFFFFFFFFFF, float(parity_ber), C.byref(t), cw.ctypes.data_as(_up) if cw is not None else None,
-                              int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, llr.ctypes.data_as(_fp), flips.ctypes.data_as(_up)), "mc_llr_host")
+    _chk(_L.qldpc_mc_llr_host(K, N, _ptr(pos, _ip), _ptr(cls, _u8p), _u64(seed), float(parity_ber), C.byref(t), _ptr(cw, _up), _u64(first_frame), n,
+                              llr.ctypes.data_as(_fp), flips.ctypes.data_as(_up)), "mc_llr_host")
     del keep
     return llr, flips
 
@@ -1152,10 +1149,10 @@ class MonteCarlo:
     def __init__(self, decoder, encoder, vn_class=None, seed=0, batch=0, parity_ber=0.0, fail_cap=1024):
         cfg = McCfg()
         _L.qldpc_mc_cfg_default(C.byref(cfg))
-        cfg.seed, cfg.batch, cfg.fail_cap, cfg.parity_ber = int(seed) & 0xFFFFFFFFFFFFFFFF, int(batch), int(fail_cap), float(parity_ber)
+        cfg.seed, cfg.batch, cfg.fail_cap, cfg.parity_ber = _u64(seed), int(batch), int(fail_cap), float(parity_ber)
         cls = _mc_class_arg(vn_class, decoder.N, "MonteCarlo")
         h = _vp()
-        _chk(_L.qldpc_mc_create(decoder._h, encoder._h, cls.ctypes.data_as(_u8p) if cls is not None else None, C.byref(cfg), C.byref(h)), "MonteCarlo")
+        _chk(_L.qldpc_mc_create(decoder._h, encoder._h, _ptr(cls, _u8p), C.byref(cfg), C.byref(h)), "MonteCarlo")
         self._h = h
         self.decoder, self.encoder = decoder, encoder
         self.N, self.K, self.device = decoder.N, decoder.K, decoder.device
@@ -1171,19 +1168,23 @@ class MonteCarlo:
         (0 = never) or after max_frames (None = one batch)."""
         res = McResult()
         n = self.batch if max_frames is None else int(max_frames)
-        _chk(_L.qldpc_mc_run(self._h, float(qber), int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, int(max_frame_errors), C.byref(res)), "MonteCarlo.run")
-        return {name: getattr(res, name) for name, _ in McResult._fields_}
+        _chk(_L.qldpc_mc_run(self._h, float(qber), _u64(first_frame), n, int(max_frame_errors), C.byref(res)), "MonteCarlo.run")
+        return _fields(res)
+
+    def _frame_tensors(self, n):
+        """-> empty device int32 tensors info [n, ceil(K/32)], cw [n, ceil(N/32)], rx [n, ceil(N/32)]"""
+        torch = _torch()
+        dev = "cuda:%d" % self.device
+        info = torch.empty((n, (self.K + 31) // 32), dtype=torch.int32, device=dev)
+        cw = torch.empty((n, (self.N + 31) // 32), dtype=torch.int32, device=dev)
+        return info, cw, torch.empty_like(cw)
 
     def frames(self, first_frame, n_frames, qber):
         """the source alone -> device int32 tensors (info [n, ceil(K/32)], cw [n, ceil(N/32)], rx [n, ceil(N/32)]): what
         mc_frames_host gives, the codeword by the encoder, rx = cw ^ flips"""
-        torch = _torch()
         n = int(n_frames)
-        dev = "cuda:%d" % self.device
-        info = torch.empty((n, (self.K + 31) // 32), dtype=torch.int32, device=dev)
-        cw = torch.empty((n, (self.N + 31) // 32), dtype=torch.int32, device=dev)
-        rx = torch.empty_like(cw)
-        _chk(_L.qldpc_mc_frames_dev(self._h, int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, float(qber), _vp(info.data_ptr()), _vp(cw.data_ptr()),
+        info, cw, rx = self._frame_tensors(n)
+        _chk(_L.qldpc_mc_frames_dev(self._h, _u64(first_frame), n, float(qber), _vp(info.data_ptr()), _vp(cw.data_ptr()),
                                     _vp(rx.data_ptr())), "MonteCarlo.frames")
         self.decoder.sync()
         return info, cw, rx
@@ -1216,14 +1217,10 @@ class MonteCarlo:
     def llr_frames(self, first_frame, n_frames):
         """the frames of the table that is set -> device tensors (info [n, ceil(K/32)], cw [n, ceil(N/32)], rx [n, ceil(N/32)] int32 and
         llr [n, N] float32): the LLR rows and rx ^ cw are what mc_llr_host gives for the encoder's codewords"""
-        torch = _torch()
         n = int(n_frames)
-        dev = "cuda:%d" % self.device
-        info = torch.empty((n, (self.K + 31) // 32), dtype=torch.int32, device=dev)
-        cw = torch.empty((n, (self.N + 31) // 32), dtype=torch.int32, device=dev)
-        rx = torch.empty_like(cw)
-        llr = torch.empty((n, self.N), dtype=torch.float32, device=dev)
-        _chk(_L.qldpc_mc_llr_dev(self._h, int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, _vp(info.data_ptr()), _vp(cw.data_ptr()), _vp(rx.data_ptr()),
+        info, cw, rx = self._frame_tensors(n)
+        llr = _torch().empty((n, self.N), dtype=_torch().float32, device=cw.device)
+        _chk(_L.qldpc_mc_llr_dev(self._h, _u64(first_frame), n, _vp(info.data_ptr()), _vp(cw.data_ptr()), _vp(rx.data_ptr()),
                                  _vp(llr.data_ptr())), "MonteCarlo.llr_frames")
         self.decoder.sync()
         return info, cw, rx, llr
@@ -1256,7 +1253,7 @@ class MonteCarlo:
         torch = _torch()
         n = int(n_patterns)
         rows = torch.empty((max(n, 0), (self.N + 31) // 32), dtype=torch.int32, device="cuda:%d" % self.device)
-        _chk(_L.qldpc_mc_patterns_dev(self._h, int(first_pattern) & 0xFFFFFFFFFFFFFFFF, n, int(n_punct), int(key_bits), _vp(rows.data_ptr())),
+        _chk(_L.qldpc_mc_patterns_dev(self._h, _u64(first_pattern), n, int(n_punct), int(key_bits), _vp(rows.data_ptr())),
              "MonteCarlo.patterns")
         self.decoder.sync()
         return rows
@@ -1264,7 +1261,7 @@ class MonteCarlo:
     def pattern_vns(self, pattern, n_punct, key_bits=32):
         """the VNs pattern `pattern` punctures, ascending (int32)"""
         vn = np.full(max(int(n_punct), 0), -1, np.int32)
-        _chk(_L.qldpc_mc_pattern_vns(self._h, int(pattern) & 0xFFFFFFFFFFFFFFFF, int(n_punct), int(key_bits), vn.ctypes.data_as(_ip)), "MonteCarlo.pattern_vns")
+        _chk(_L.qldpc_mc_pattern_vns(self._h, _u64(pattern), int(n_punct), int(key_bits), vn.ctypes.data_as(_ip)), "MonteCarlo.pattern_vns")
         return vn
 
     def set_puncture(self, vn):
@@ -1280,12 +1277,12 @@ class MonteCarlo:
         pattern without frame errors."""
         cfg = McSearchCfg()
         cfg.n_punct, cfg.frames_per_pattern, cfg.key_bits, cfg.stop_at_goal = int(n_punct), int(frames_per_pattern), int(key_bits), int(bool(stop_at_goal))
-        cfg.first_frame = int(first_frame) & 0xFFFFFFFFFFFFFFFF
+        cfg.first_frame = _u64(first_frame)
         if max_patterns is None:
             max_patterns = self.batch // max(int(frames_per_pattern), 1) if 1 <= int(frames_per_pattern) <= self.batch else 1
         res = McSearchResult()
-        _chk(_L.qldpc_mc_search(self._h, float(qber), C.byref(cfg), int(first_pattern) & 0xFFFFFFFFFFFFFFFF, int(max_patterns), C.byref(res)), "MonteCarlo.search")
-        out = {name: getattr(res, name) for name, _ in McSearchResult._fields_}
+        _chk(_L.qldpc_mc_search(self._h, float(qber), C.byref(cfg), _u64(first_pattern), int(max_patterns), C.byref(res)), "MonteCarlo.search")
+        out = _fields(res)
         stats = np.zeros(int(res.patterns), MC_PATTERN_STAT)
         n = _chk(_L.qldpc_mc_search_stats(self._h, _vp(stats.ctypes.data), stats.size), "MonteCarlo.search")
         assert n == stats.size
@@ -1309,45 +1306,47 @@ class MonteCarlo:
         cfg = McSweepCfg()
         cfg.points, cfg.n_points = pts, qb.size
         cfg.punct_order, cfg.n_order = (order.ctypes.data_as(_ip) if order.size else None), order.size
-        cfg.chunk, cfg.first_frame = int(chunk), int(first_frame) & 0xFFFFFFFFFFFFFFFF
+        cfg.chunk, cfg.first_frame = int(chunk), _u64(first_frame)
         cfg.max_frames, cfg.max_frame_errors = (self.batch if max_frames is None else int(max_frames)), int(max_frame_errors)
         res = McSweepResult()
         _chk(_L.qldpc_mc_sweep(self._h, C.byref(cfg), C.byref(res)), "MonteCarlo.sweep")
-        out = {name: getattr(res, name) for name, _ in McSweepResult._fields_}
+        out = _fields(res)
         out["points"] = self.sweep_stats()
         assert out["points"].size == qb.size
         return out
 
-    def sweep_stats(self):
-        """the point rows of the last sweep (MC_POINT_STAT), in point order"""
-        n = _chk(_L.qldpc_mc_sweep_stats(self._h, None, 0), "MonteCarlo.sweep_stats")
-        rows = np.zeros(n, MC_POINT_STAT)
+    def _last_rows(self, stats_fn, dtype, where):
+        n = _chk(stats_fn(self._h, None, 0), where)
+        rows = np.zeros(n, dtype)
         if n:
-            _chk(_L.qldpc_mc_sweep_stats(self._h, _vp(rows.ctypes.data), n), "MonteCarlo.sweep_stats")
+            _chk(stats_fn(self._h, _vp(rows.ctypes.data), n), where)
         return rows
 
-    def sweep_hist(self):
-        """frames per iteration count of every point of the last sweep -> uint64 [P, n_ite + 1]"""
-        P = _chk(_L.qldpc_mc_sweep_stats(self._h, None, 0), "MonteCarlo.sweep_hist")
+    def _last_hists(self, stats_fn, hist_fn, where):
+        P = _chk(stats_fn(self._h, None, 0), where)
         if P == 0:
             return np.zeros((0, 0), np.uint64)
         one = np.zeros(1, np.uint64)
-        bins = _chk(_L.qldpc_mc_sweep_hist(self._h, 0, one.ctypes.data_as(_u64p), 1), "MonteCarlo.sweep_hist")      # the call returns n_ite + 1
+        bins = _chk(hist_fn(self._h, 0, one.ctypes.data_as(_u64p), 1), where)      # the call returns n_ite + 1
         out = np.zeros((P, bins), np.uint64)
         for q in range(P):
-            _chk(_L.qldpc_mc_sweep_hist(self._h, q, out[q].ctypes.data_as(_u64p), bins), "MonteCarlo.sweep_hist")
+            _chk(hist_fn(self._h, q, out[q].ctypes.data_as(_u64p), bins), where)
         return out
+
+    def sweep_stats(self):
+        """the point rows of the last sweep (MC_POINT_STAT), in point order"""
+        return self._last_rows(_L.qldpc_mc_sweep_stats, MC_POINT_STAT, "MonteCarlo.sweep_stats")
+
+    def sweep_hist(self):
+        """frames per iteration count of every point of the last sweep -> uint64 [P, n_ite + 1]"""
+        return self._last_hists(_L.qldpc_mc_sweep_stats, _L.qldpc_mc_sweep_hist, "MonteCarlo.sweep_hist")
 
     def weight_frames(self, first_frame, n_frames, weight, key_bits=0):
         """the source alone at one fixed error weight -> device int32 tensors (info [n, ceil(K/32)], cw [n, ceil(N/32)], rx [n, ceil(N/32)]):
         what mc_weight_frames_host gives, the codeword by the encoder, rx = cw ^ flips"""
-        torch = _torch()
         n = int(n_frames)
-        dev = "cuda:%d" % self.device
-        info = torch.empty((max(n, 0), (self.K + 31) // 32), dtype=torch.int32, device=dev)
-        cw = torch.empty((max(n, 0), (self.N + 31) // 32), dtype=torch.int32, device=dev)
-        rx = torch.empty_like(cw)
-        _chk(_L.qldpc_mc_weight_frames_dev(self._h, int(first_frame) & 0xFFFFFFFFFFFFFFFF, n, int(weight), int(key_bits), _vp(info.data_ptr()), _vp(cw.data_ptr()),
+        info, cw, rx = self._frame_tensors(max(n, 0))
+        _chk(_L.qldpc_mc_weight_frames_dev(self._h, _u64(first_frame), n, int(weight), int(key_bits), _vp(info.data_ptr()), _vp(cw.data_ptr()),
                                            _vp(rx.data_ptr())), "MonteCarlo.weight_frames")
         self.decoder.sync()
         return info, cw, rx
@@ -1362,34 +1361,22 @@ class MonteCarlo:
         cfg = McStrataCfg()
         cfg.weights, cfg.n_strata = (w.ctypes.data_as(_ip) if w.size else None), w.size
         cfg.design_qber, cfg.key_bits, cfg.chunk = float(design_qber), int(key_bits), int(chunk)
-        cfg.first_frame = int(first_frame) & 0xFFFFFFFFFFFFFFFF
+        cfg.first_frame = _u64(first_frame)
         cfg.max_frames, cfg.max_frame_errors = (self.batch if max_frames is None else int(max_frames)), int(max_frame_errors)
         res = McStrataResult()
         _chk(_L.qldpc_mc_strata(self._h, C.byref(cfg), C.byref(res)), "MonteCarlo.strata")
-        out = {name: getattr(res, name) for name, _ in McStrataResult._fields_}
+        out = _fields(res)
         out["strata"] = self.strata_stats()
         assert out["strata"].size == w.size
         return out
 
     def strata_stats(self):
         """the stratum rows of the last strata run (MC_STRATUM_STAT), in the caller's order"""
-        n = _chk(_L.qldpc_mc_strata_stats(self._h, None, 0), "MonteCarlo.strata_stats")
-        rows = np.zeros(n, MC_STRATUM_STAT)
-        if n:
-            _chk(_L.qldpc_mc_strata_stats(self._h, _vp(rows.ctypes.data), n), "MonteCarlo.strata_stats")
-        return rows
+        return self._last_rows(_L.qldpc_mc_strata_stats, MC_STRATUM_STAT, "MonteCarlo.strata_stats")
 
     def strata_hist(self):
         """frames per iteration count of every stratum of the last strata run -> uint64 [n_strata, n_ite + 1]"""
-        P = _chk(_L.qldpc_mc_strata_stats(self._h, None, 0), "MonteCarlo.strata_hist")
-        if P == 0:
-            return np.zeros((0, 0), np.uint64)
-        one = np.zeros(1, np.uint64)
-        bins = _chk(_L.qldpc_mc_strata_hist(self._h, 0, one.ctypes.data_as(_u64p), 1), "MonteCarlo.strata_hist")      # the call returns n_ite + 1
-        out = np.zeros((P, bins), np.uint64)
-        for q in range(P):
-            _chk(_L.qldpc_mc_strata_hist(self._h, q, out[q].ctypes.data_as(_u64p), bins), "MonteCarlo.strata_hist")
-        return out
+        return self._last_hists(_L.qldpc_mc_strata_stats, _L.qldpc_mc_strata_hist, "MonteCarlo.strata_hist")
 
     def __del__(self):
         try:

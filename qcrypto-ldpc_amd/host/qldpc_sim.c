@@ -77,25 +77,65 @@ static int die(const char *what, int rc)
     fprintf(stderr, "qldpc_sim: %s: %s (%d) %s\n", what, qldpc_strerror(rc), rc, qldpc_last_error());
     return 1;
 }
+static int usage(const char *msg) { fprintf(stderr, "%s\n", msg); return 2; }
 
-int main(int argc, char **argv)
+/* the command line (parse); setup() replaces N and K by the code's and the encoder's */
+static int N = 8192, K = 6554, n_ite = 50, frames = 256, batch = 256, layered = 0, synd = 1, peg = 0, msg_bits = 32, search = 0, on_device = 0, rule = -1;
+static uint64_t max_fe = 0, seed = 0;
+static double search_eff = 0.0;      /* -X: > 0 = the pattern search on the device towards this efficiency */
+static int frames_per_pattern = 64;
+static int awgn = 0, awgn_maxq = 31, awgn_punct = 0, zero_source = 0, sweep = 0;      /* -A, -u, -z, -W */
+static double ebno_db = 0.0, awgn_rmax = 3.0, quant_scale = 0.0;
+static int strata = 0, w_lo = 0, w_hi = 0, w_step = 1;      /* -w */
+static double design_qber = 0.0;
+static double parity_ber = 0.0;      /* > 0: the disclosed parity bits are themselves wrong with this probability (main.cpp (test effect of dirty parities)) */
+static double target_eff = 0.0;      /* > 0: puncture parity bits up to min_cr(ber, f), as BS/src/main.cpp:235-333 does */
+static const char *alist = NULL, *qc = NULL, *rule_name = "NMS", *g_method = NULL, *pattern_out = NULL;
+static float param = 0.75f;
+static double ber_min = 0.01, ber_max = 0.03, ber_step = 0.005;
+#define FOR_EACH_BER(ber) for (double ber = ber_min; ber <= ber_max + 1e-12; ber += ber_step)
+#define MAX_FRAMES ((uint64_t)(frames > 0 ? frames : 0))
+
+/* what setup() builds; mc only with -D */
+static qldpc_code *H; static qldpc_encoder *enc; static qldpc_decoder *dec; static qldpc_mc *mc;
+static int *pos; static char *is_info;
+
+/* the result row: EP, already formatted, | FRA | BE | FE | BER | FER | SIM_THR, the last from thr_frames frames decoded in sec seconds */
+static void row(const char *ep, uint64_t fra, uint64_t be, uint64_t fe, double thr_frames, double sec)
 {
-    int N = 8192, K = 6554, n_ite = 50, frames = 256, batch = 256, layered = 0, synd = 1, peg = 0, msg_bits = 32, search = 0, on_device = 0, opt;
-    uint64_t max_fe = 0;
-    double search_eff = 0.0;      /* -X: > 0 = the pattern search on the device towards this efficiency */
-    int frames_per_pattern = 64;
-    int awgn = 0, awgn_maxq = 31, awgn_punct = 0, zero_source = 0, sweep = 0;      /* -A, -u, -z, -W */
-    double ebno_db = 0.0, awgn_rmax = 3.0, quant_scale = 0.0;
-    int strata = 0, w_lo = 0, w_hi = 0, w_step = 1;      /* -w */
-    double design_qber = 0.0;
-    const char *pattern_out = NULL;
-    double parity_ber = 0.0;      /* > 0: the disclosed parity bits are themselves wrong with this probability (main.cpp (test effect of dirty parities)) */
-    double target_eff = 0.0;      /* > 0: puncture parity bits up to min_cr(ber, f), as BS/src/main.cpp:235-333 does */
-    const char *alist = NULL, *qc = NULL, *rule_name = "NMS";
-    float param = 0.75f;
-    double ber_min = 0.01, ber_max = 0.03, ber_step = 0.005;
-    uint64_t seed = 0;
-    const char *g_method = NULL;
+    printf("  %s | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", ep, (unsigned long long)fra, (unsigned long long)be, (unsigned long long)fe,
+           (double)be / ((double)fra * K), (double)fe / (double)fra, thr_frames * K / sec / 1e6);
+}
+static void row_f(double ep, uint64_t fra, uint64_t be, uint64_t fe, double thr_frames, double sec) { char s[64]; snprintf(s, sizeof(s), "%8.4f", ep); row(s, fra, be, fe, thr_frames, sec); }
+static void row_d(int ep, uint64_t fra, uint64_t be, uint64_t fe, double thr_frames, double sec) { char s[64]; snprintf(s, sizeof(s), "%8d", ep); row(s, fra, be, fe, thr_frames, sec); }
+
+/* parity_bits_to_punct(INFO_B, TTL_B, GOAL_CR) with GOAL_CR = min_cr(QBER, EFF) (BS/src/main.cpp:29,34,280), at most all the parity bits, and its
+ * lines.  Where the count is negative, the mother code's rate being above the goal already: puncture nothing, or with `skip` return -1. */
+static int punct_count(double ber, double eff, int skip)
+{
+    const int n_par = N - K;
+    int n_punct = qldpc_parity_bits_to_punct(N, K, qldpc_min_code_rate((float)ber, (float)eff));
+    if (n_punct < 0) printf("# ber %.4f: mother code rate already above the goal, nothing to puncture\n", ber);
+    if (n_punct < 0 && skip) return -1;
+    n_punct = n_punct < 0 ? 0 : n_punct > n_par ? n_par : n_punct;
+    printf("# ber %.4f: puncturing %d of %d parity bits -> rate %.4f, efficiency f = %.3f\n", ber, n_punct, n_par, (double)K / (N - n_punct),
+           ((double)(n_par - n_punct) / K) / (double)qldpc_binary_entropy((float)ber));
+    return n_punct;
+}
+
+static int write_pattern(double ber, int n_punct, const int *vn, long long fe)
+{
+    FILE *fo = fopen(pattern_out, "w");
+    if (!fo) { perror(pattern_out); return 1; }
+    fprintf(fo, "# qldpc_sim puncture pattern: N %d K %d ber %.4f punctured %d FE %lld\n", N, K, ber, n_punct, fe);
+    for (int i = 0; i < n_punct; i++) fprintf(fo, "%d\n", vn[i]);
+    fclose(fo);
+    return 0;
+}
+
+static int parse(int argc, char **argv)
+{
+    int opt;
     while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:u:c:w:DRWlvnz")) != -1) {
         switch (opt) {
         case 'N': N = atoi(optarg); break;
@@ -107,7 +147,7 @@ int main(int argc, char **argv)
         case 'i': n_ite = atoi(optarg); break;
         case 'f': frames = atoi(optarg); break;
         case 'b': batch = atoi(optarg); break;
-        case 's': if (sscanf(optarg, "%lf:%lf:%lf", &ber_min, &ber_max, &ber_step) != 3) { fprintf(stderr, "-s min:max:step\n"); return 2; } break;
+        case 's': if (sscanf(optarg, "%lf:%lf:%lf", &ber_min, &ber_max, &ber_step) != 3) return usage("-s min:max:step"); break;
         case 'S': seed = strtoull(optarg, NULL, 0); break;
         case 'P': peg = atoi(optarg); break;
         case 'e': target_eff = atof(optarg); break;
@@ -118,58 +158,60 @@ int main(int argc, char **argv)
         case 'E': max_fe = strtoull(optarg, NULL, 0); break;
         case 'X': search_eff = atof(optarg); break;
         case 'F': frames_per_pattern = atoi(optarg); break;
-        case 'A': { const int got = sscanf(optarg, "%lf:%lf:%d", &ebno_db, &awgn_rmax, &awgn_maxq); if (got != 1 && got != 3) { fprintf(stderr, "-A ebno_db[:rmax:maxq]\n"); return 2; } awgn = 1; break; }
+        case 'A': { const int got = sscanf(optarg, "%lf:%lf:%d", &ebno_db, &awgn_rmax, &awgn_maxq); if (got != 1 && got != 3) return usage("-A ebno_db[:rmax:maxq]"); awgn = 1; break; }
         case 'u': awgn_punct = atoi(optarg); break;
         case 'z': zero_source = 1; break;
         case 'W': sweep = 1; break;
-        case 'w': { const int got = sscanf(optarg, "%d:%d:%d:%lf", &w_lo, &w_hi, &w_step, &design_qber); if (got != 3 && got != 4) { fprintf(stderr, "-w lo:hi:step[:design_qber]\n"); return 2; } strata = 1; break; }
+        case 'w': { const int got = sscanf(optarg, "%d:%d:%d:%lf", &w_lo, &w_hi, &w_step, &design_qber); if (got != 3 && got != 4) return usage("-w lo:hi:step[:design_qber]"); strata = 1; break; }
         case 'c': quant_scale = atof(optarg); break;
         case 'o': pattern_out = optarg; break;
         case 'G': g_method = optarg; break;      /* p.G_method (VAR/main.cpp (alist-v1.0.1):135): IDENTITY | LU_DEC; QC = Encoder_LDPC_from_QC ((qc):145) */
         case 'l': layered = 1; break;
         case 'v': layered = 2; break;      /* Decoder_LDPC_BP_vertical_layered, VAR/main.cpp (alist-v1.0.1):240-256 */
         case 'n': synd = 0; break;
-        default: fprintf(stderr, "see the header of qldpc_sim.c for usage\n"); return 2;
+        default: return usage("see the header of qldpc_sim.c for usage");
         }
     }
     static const char *names[] = {"MS", "OMS", "NMS", "SPA", "LSPA", "AMS_MIN", "AMS_MINSTAR_L2", "AMS_MINSTAR"};
-    int rule = -1;
     for (int i = 0; i < 8; i++) if (!strcmp(rule_name, names[i])) rule = i;
     if (rule < 0) { fprintf(stderr, "unknown rule %s\n", rule_name); return 2; }
-    if (sweep && !on_device) { fprintf(stderr, "qldpc_sim: -W is the sweep on the device and needs -D\n"); return 2; }
-    if (sweep && (search_eff != 0.0 || awgn)) { fprintf(stderr, "qldpc_sim: -W sweeps the BSC rows of -s and runs neither with the pattern search (-X) nor with -A\n"); return 2; }
-    if (strata && !on_device) { fprintf(stderr, "qldpc_sim: -w runs the error strata on the device and needs -D\n"); return 2; }
-    if (strata && (search_eff != 0.0 || awgn || sweep)) { fprintf(stderr, "qldpc_sim: -w runs fixed error weights on the BSC's words and runs neither with -X, -A nor -W\n"); return 2; }
-    if (strata && (w_step < 1 || w_lo < 0 || w_hi < w_lo)) { fprintf(stderr, "qldpc_sim: -w lo:hi:step with 0 <= lo <= hi and step >= 1\n"); return 2; }
-    if (on_device && ((target_eff > 0.0 && !sweep) || search)) { fprintf(stderr, "qldpc_sim: -e and -R draw a puncture pattern per batch on the host and do not run with -D\n"); return 2; }
-    if (max_fe && !on_device) { fprintf(stderr, "qldpc_sim: -E needs -D\n"); return 2; }
-    if (search_eff != 0.0 && !on_device) { fprintf(stderr, "qldpc_sim: -X is the pattern search on the device and needs -D\n"); return 2; }
-    if (search_eff != 0.0 && max_fe) { fprintf(stderr, "qldpc_sim: -E does not apply to the pattern search (-X), which stops at the first pattern without frame errors\n"); return 2; }
-    if (search_eff < 0.0) { fprintf(stderr, "qldpc_sim: -X f with f > 0\n"); return 2; }
-    if ((awgn || zero_source) && !on_device) { fprintf(stderr, "qldpc_sim: -A and -z belong to the loop on the device and need -D\n"); return 2; }
-    if (awgn && search_eff != 0.0) { fprintf(stderr, "qldpc_sim: -A does not run with the pattern search (-X)\n"); return 2; }
-    if (awgn_punct && !awgn) { fprintf(stderr, "qldpc_sim: -u needs -A\n"); return 2; }
+    const int search_x = search_eff != 0.0;
+    if (sweep && !on_device) return usage("qldpc_sim: -W is the sweep on the device and needs -D");
+    if (sweep && (search_x || awgn)) return usage("qldpc_sim: -W sweeps the BSC rows of -s and runs neither with the pattern search (-X) nor with -A");
+    if (strata && !on_device) return usage("qldpc_sim: -w runs the error strata on the device and needs -D");
+    if (strata && (search_x || awgn || sweep)) return usage("qldpc_sim: -w runs fixed error weights on the BSC's words and runs neither with -X, -A nor -W");
+    if (strata && (w_step < 1 || w_lo < 0 || w_hi < w_lo)) return usage("qldpc_sim: -w lo:hi:step with 0 <= lo <= hi and step >= 1");
+    if (on_device && ((target_eff > 0.0 && !sweep) || search)) return usage("qldpc_sim: -e and -R draw a puncture pattern per batch on the host and do not run with -D");
+    if (max_fe && !on_device) return usage("qldpc_sim: -E needs -D");
+    if (search_x && !on_device) return usage("qldpc_sim: -X is the pattern search on the device and needs -D");
+    if (search_x && max_fe) return usage("qldpc_sim: -E does not apply to the pattern search (-X), which stops at the first pattern without frame errors");
+    if (search_eff < 0.0) return usage("qldpc_sim: -X f with f > 0");
+    if ((awgn || zero_source) && !on_device) return usage("qldpc_sim: -A and -z belong to the loop on the device and need -D");
+    if (awgn && search_x) return usage("qldpc_sim: -A does not run with the pattern search (-X)");
+    if (awgn_punct && !awgn) return usage("qldpc_sim: -u needs -A");
+    return 0;
+}
 
-    qldpc_code *H = NULL;
+/* code, encoder and decoder, the head of the table, and with -D the loop object */
+static int setup(void)
+{
     int rc = alist ? qldpc_code_from_alist(alist, &H) : qc ? qldpc_code_from_qc(qc, &H) : peg ? qldpc_code_ira_peg(N, K, 0.125f, 11, 3, peg, 7, &H) : qldpc_code_ira(N, K, 0.125f, 11, 3, 7, &H);
     if (rc) return die("code", rc);
     N = qldpc_code_n(H);
-    qldpc_encoder *enc = NULL;
     if ((rc = qldpc_encoder_create(H, g_method ? g_method : qldpc_code_is_ira(H) ? "IRA" : "IDENTITY", 0, &enc))) return die("encoder", rc);
     K = qldpc_encoder_k(enc);
-    int *pos = (int *)malloc(sizeof(int) * (size_t)K);
+    pos = (int *)malloc(sizeof(int) * (size_t)K);
     qldpc_encoder_info_bits_pos(enc, pos);
-    char *is_info = (char *)calloc((size_t)N, 1);
+    is_info = (char *)calloc((size_t)N, 1);
     for (int i = 0; i < K; i++) is_info[pos[i]] = 1;
 
     qldpc_decoder_cfg cfg;
     qldpc_decoder_cfg_default(&cfg);
     cfg.schedule = layered == 2 ? QLDPC_SCHED_VLAYERED : (layered ? QLDPC_SCHED_HLAYERED : QLDPC_SCHED_FLOODING);
     cfg.rule = rule; cfg.rule_param = param; cfg.n_ite = n_ite; cfg.enable_syndrome = synd; cfg.syndrome_depth = 1; cfg.max_frames = batch;
-    if (msg_bits != 32 && msg_bits != 16 && msg_bits != 8) { fprintf(stderr, "-Q 32 | 16 | 8\n"); return 2; }
+    if (msg_bits != 32 && msg_bits != 16 && msg_bits != 8) return usage("-Q 32 | 16 | 8");
     cfg.msg_dtype = msg_bits == 16 ? 1 : (msg_bits == 8 ? 2 : 0);      /* 16: binary16 message storage; 8: fixed-point min-sum */
     cfg.quant_scale = (float)quant_scale;
-    qldpc_decoder *dec = NULL;
     if ((rc = qldpc_decoder_create(H, K, pos, &cfg, &dec))) return die("decoder", rc);
 
     printf("# * libqldpc %d on HIP device 0; Decoder_LDPC_BP_%s_Update_rule_%s (param %g), n_ite %d, syndrome %d, %d-bit messages\n", qldpc_version(),
@@ -178,170 +220,170 @@ int main(int argc, char **argv)
     printf("#    ** Est. QKD Key Rate After Priv Amp = %f\n", (double)(K - (N - K)) / (double)K);
     printf("# %8s | %8s | %8s | %8s | %9s | %9s | %10s\n", "EP", "FRA", "BE", "FE", "BER", "FER", "SIM_THR");
     printf("# %8s | %8s | %8s | %8s | %9s | %9s | %10s\n", "", "", "", "", "", "", "(Mb/s)");
+    if (!on_device) return 0;
 
-    if (on_device) {      /* the same table, every row one qldpc_mc_run */
-        qldpc_mc_cfg mcfg;
-        qldpc_mc_cfg_default(&mcfg);
-        mcfg.seed = seed; mcfg.batch = batch; mcfg.parity_ber = parity_ber;
-        qldpc_mc *mc = NULL;
-        if (awgn && (awgn_punct < 0 || awgn_punct >= N)) { fprintf(stderr, "qldpc_sim: -u %d outside [0, N = %d)\n", awgn_punct, N); return 2; }
-        uint8_t *cls = awgn ? (uint8_t *)calloc((size_t)N, 1) : NULL;      /* -A: every VN through the channel (class 0) but the punctured ones */
-        for (int v = 0; cls && v < awgn_punct; v++) cls[v] = QLDPC_VN_PUNCTURED;
-        if ((rc = qldpc_mc_create(dec, enc, cls, &mcfg, &mc))) return die("mc_create", rc);      /* NULL: info VNs through the BSC, the others pinned, as below */
-        free(cls);
-        if (zero_source && (rc = qldpc_mc_set_source(mc, QLDPC_MC_SOURCE_ZERO))) return die("mc_set_source", rc);
-        if (awgn) {      /* one row: the loop at this Eb/N0 */
-            const double rate = (double)K / (double)(N - awgn_punct), sigma = sqrt(1.0 / (2.0 * rate * pow(10.0, ebno_db / 10.0)));
-            const int Q = 2 * awgn_maxq + 2;
-            uint64_t *cum = (uint64_t *)malloc(sizeof(uint64_t) * 2 * 256);
-            float *value = (float *)malloc(sizeof(float) * 256);
-            if (!cum || !value) return die("mc_awgn_table", QLDPC_ENOMEM);
-            if ((rc = qldpc_mc_awgn_table(sigma, awgn_rmax, awgn_maxq, cum, cum + 256, value))) return die("mc_awgn_table", rc);
-            const qldpc_mc_channel table = {Q, {cum, cum + 256}, value, {0, 0}};
-            if ((rc = qldpc_mc_set_channel(mc, &table))) return die("mc_set_channel", rc);
-            free(cum); free(value);
-            printf("# Eb/N0 %.4f dB at rate %d / %d: sigma %.6f, %d levels, rmax %g\n", ebno_db, K, N - awgn_punct, sigma, Q, awgn_rmax);
-            qldpc_mc_result r;
-            if ((rc = qldpc_mc_run(mc, 0.25 /* not used with a table */, 0, (uint64_t)(frames > 0 ? frames : 0), max_fe, &r))) return die("mc_run", rc);
-            printf("  %8.4f | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", ebno_db, (unsigned long long)r.frames, (unsigned long long)r.bit_errors,
-                   (unsigned long long)r.frame_errors, (double)r.bit_errors / ((double)r.frames * K), (double)r.frame_errors / (double)r.frames,
-                   (double)r.frames * K / (r.decode_ms * 1e-3) / 1e6);
-            ber_min = 1.0; ber_max = 0.0;      /* no BSC rows */
-        }
-        if (strata) {      /* one qldpc_mc_strata over the weights, then FER(q) for the QBERs of -s from its rows */
-            const int P = (w_hi - w_lo) / w_step + 1;
-            if (P > QLDPC_MC_SWEEP_MAX_POINTS) { fprintf(stderr, "qldpc_sim: -w gives %d weights, at most %d\n", P, QLDPC_MC_SWEEP_MAX_POINTS); return 2; }
-            int *weights = (int *)malloc(sizeof(int) * (size_t)P);
-            qldpc_mc_stratum_stat *rows = (qldpc_mc_stratum_stat *)malloc(sizeof(*rows) * (size_t)P);
-            uint64_t *fr = (uint64_t *)malloc(sizeof(uint64_t) * 2 * (size_t)P), *fe = fr ? fr + P : NULL;
-            if (!weights || !rows || !fr) return die("mc_strata", QLDPC_ENOMEM);
-            for (int i = 0; i < P; i++) weights[i] = w_lo + i * w_step;
-            qldpc_mc_strata_cfg tcfg;
-            memset(&tcfg, 0, sizeof(tcfg));
-            tcfg.weights = weights; tcfg.n_strata = P; tcfg.design_qber = design_qber > 0.0 ? design_qber : ber_min;
-            tcfg.max_frames = (uint64_t)(frames > 0 ? frames : 0); tcfg.max_frame_errors = max_fe;
-            qldpc_mc_strata_result t;
-            if ((rc = qldpc_mc_strata(mc, &tcfg, &t))) return die("mc_strata", rc);
-            if ((rc = qldpc_mc_strata_stats(mc, rows, P)) < 0) return die("mc_strata_stats", rc);
-            printf("# strata: %d weights in %llu rounds, %llu frames, |LLR| of QBER %.4f; EP = the error weight\n", P, (unsigned long long)t.rounds,
-                   (unsigned long long)t.frames, tcfg.design_qber);
-            for (int i = 0; i < P; i++) {      /* SIM_THR: the run's decode time is shared by the rows, as under -W */
-                printf("  %8d | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", rows[i].weight, (unsigned long long)rows[i].frames, (unsigned long long)rows[i].bit_errors,
-                       (unsigned long long)rows[i].frame_errors, (double)rows[i].bit_errors / ((double)rows[i].frames * K),
-                       (double)rows[i].frame_errors / (double)rows[i].frames, (double)t.frames * K / (t.decode_ms * 1e-3) / 1e6);
-                fr[i] = rows[i].frames; fe[i] = rows[i].frame_errors;
-            }
-            for (double ber = ber_min; ber <= ber_max + 1e-12; ber += ber_step) {
-                double est[4];
-                if ((rc = qldpc_mc_strata_fer_host(K, P, weights, fr, fe, ber, est))) return die("mc_strata_fer_host", rc);
-                printf("# strata ber %.4f: FER %.6e over weights %d .. %d, binomial mass below %.6e, above %.6e, standard error %.6e\n", ber, est[0], w_lo,
-                       weights[P - 1], est[1], est[2], est[3]);
-            }
-            free(weights); free(rows); free(fr);
-            ber_min = 1.0; ber_max = 0.0;      /* the rows are printed */
-        }
-        if (sweep) {      /* the same table from ONE qldpc_mc_sweep: a point per row */
-            const int n_par = N - K;
-            int n_rows = 0, bits = 0, n_order = 0;
-            for (double ber = ber_min; ber <= ber_max + 1e-12; ber += ber_step) n_rows++;
-            qldpc_mc_point *pts = (qldpc_mc_point *)calloc((size_t)(n_rows ? n_rows : 1), sizeof(*pts));
-            int *order = (int *)malloc(sizeof(int) * (size_t)(n_par ? n_par : 1)), *par = (int *)malloc(sizeof(int) * (size_t)(n_par ? n_par : 1));
-            if (!pts || !order || !par) return die("mc_sweep", QLDPC_ENOMEM);
-            if (target_eff > 0.0) {      /* parity VN j along the accumulator, visited in bit-reversed j: every prefix is evenly spaced */
-                int m = 0;
-                for (int v = 0; v < N; v++) if (!is_info[v]) par[m++] = v;
-                while ((1 << bits) < n_par) bits++;
-                for (int i = 0; i < (1 << bits); i++) {
-                    int j = 0;
-                    for (int b = 0; b < bits; b++) j |= ((i >> b) & 1) << (bits - 1 - b);
-                    if (j < n_par) order[n_order++] = par[j];
-                }
-            }
-            int P = 0;
-            for (double ber = ber_min; ber <= ber_max + 1e-12; ber += ber_step) {
-                int n_punct = 0;
-                if (target_eff > 0.0) {
-                    n_punct = qldpc_parity_bits_to_punct(N, K, qldpc_min_code_rate((float)ber, (float)target_eff));
-                    if (n_punct < 0) { printf("# ber %.4f: mother code rate already above the goal, nothing to puncture\n", ber); continue; }
-                    if (n_punct > n_par) n_punct = n_par;
-                    printf("# ber %.4f: puncturing %d of %d parity bits -> rate %.4f, efficiency f = %.3f\n", ber, n_punct, n_par, (double)K / (N - n_punct),
-                           ((double)(n_par - n_punct) / K) / (double)qldpc_binary_entropy((float)ber));
-                }
-                pts[P].qber = ber; pts[P].n_punct = n_punct; P++;
-            }
-            if (P > 0) {
-                qldpc_mc_sweep_cfg wcfg;
-                memset(&wcfg, 0, sizeof(wcfg));
-                wcfg.points = pts; wcfg.n_points = P; wcfg.punct_order = n_order ? order : NULL; wcfg.n_order = n_order;
-                wcfg.max_frames = (uint64_t)(frames > 0 ? frames : 0); wcfg.max_frame_errors = max_fe;
-                qldpc_mc_sweep_result w;
-                if ((rc = qldpc_mc_sweep(mc, &wcfg, &w))) return die("mc_sweep", rc);
-                qldpc_mc_point_stat *rows = (qldpc_mc_point_stat *)malloc(sizeof(*rows) * (size_t)P);
-                if (!rows || (rc = qldpc_mc_sweep_stats(mc, rows, P)) < 0) return die("mc_sweep_stats", rows ? rc : QLDPC_ENOMEM);
-                printf("# sweep: %d points in %llu rounds, %llu frames\n", P, (unsigned long long)w.rounds, (unsigned long long)w.frames);
-                for (int q = 0; q < P; q++)      /* SIM_THR: the sweep's decode time is shared by the rows, so it is the sweep's throughput in every row */
-                    printf("  %8.4f | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", rows[q].qber, (unsigned long long)rows[q].frames, (unsigned long long)rows[q].bit_errors,
-                           (unsigned long long)rows[q].frame_errors, (double)rows[q].bit_errors / ((double)rows[q].frames * K),
-                           (double)rows[q].frame_errors / (double)rows[q].frames, (double)w.frames * K / (w.decode_ms * 1e-3) / 1e6);
-                free(rows);
-            }
-            free(pts); free(order); free(par);
-            ber_min = 1.0; ber_max = 0.0;      /* the rows are printed */
-        }
-        for (double ber = ber_min; search_eff > 0.0 && ber <= ber_max + 1e-12; ber += ber_step) {      /* every row one qldpc_mc_search */
-            const int n_par = N - K;
-            int n_punct = qldpc_parity_bits_to_punct(N, K, qldpc_min_code_rate((float)ber, (float)search_eff));      /* as -e computes it */
-            if (n_punct < 0) { printf("# ber %.4f: mother code rate already above the goal, nothing to puncture\n", ber); n_punct = 0; }
-            if (n_punct > n_par) n_punct = n_par;
-            printf("# ber %.4f: puncturing %d of %d parity bits -> rate %.4f, efficiency f = %.3f\n", ber, n_punct, n_par, (double)K / (N - n_punct),
-                   ((double)(n_par - n_punct) / K) / (double)qldpc_binary_entropy((float)ber));
-            qldpc_mc_search_cfg scfg;
-            memset(&scfg, 0, sizeof(scfg));
-            scfg.n_punct = n_punct; scfg.frames_per_pattern = frames_per_pattern; scfg.stop_at_goal = 1;
-            qldpc_mc_search_result r;
-            if ((rc = qldpc_mc_search(mc, ber, &scfg, 0, (uint64_t)(frames > 0 ? frames : 0), &r))) return die("mc_search", rc);
-            qldpc_mc_pattern_stat *rows = (qldpc_mc_pattern_stat *)malloc(sizeof(*rows) * (size_t)(r.patterns ? r.patterns : 1));
-            if (!rows || (rc = qldpc_mc_search_stats(mc, rows, (int)r.patterns)) < 0) return die("mc_search_stats", rows ? rc : QLDPC_ENOMEM);
-            uint64_t be = 0, fe = 0;
-            for (uint64_t i = 0; i < r.patterns; i++) {
-                printf("#   pattern %3llu: FE %llu / %d, BE %llu\n", (unsigned long long)rows[i].pattern, (unsigned long long)rows[i].frame_errors, frames_per_pattern,
-                       (unsigned long long)rows[i].bit_errors);
-                be += rows[i].bit_errors; fe += rows[i].frame_errors;
-            }
-            free(rows);
-            if (r.goal != UINT64_MAX) printf("# ber %.4f: goal puncture pattern %llu (FER = 0 / %d)\n", ber, (unsigned long long)r.goal, frames_per_pattern);
-            if (r.patterns) {
-                printf("# ber %.4f: best of %llu patterns: FE %llu, BE %llu per %d frames\n", ber, (unsigned long long)r.patterns, (unsigned long long)r.best_frame_errors,
-                       (unsigned long long)r.best_bit_errors, frames_per_pattern);
-                if (pattern_out) {
-                    int *vn = (int *)malloc(sizeof(int) * (size_t)(n_punct ? n_punct : 1));
-                    if (!vn || (rc = qldpc_mc_pattern_vns(mc, r.best, n_punct, 0, vn))) return die("mc_pattern_vns", vn ? rc : QLDPC_ENOMEM);
-                    FILE *fo = fopen(pattern_out, "w");
-                    if (!fo) { perror(pattern_out); return 1; }
-                    fprintf(fo, "# qldpc_sim puncture pattern: N %d K %d ber %.4f punctured %d FE %llu\n", N, K, ber, n_punct, (unsigned long long)r.best_frame_errors);
-                    for (int i = 0; i < n_punct; i++) fprintf(fo, "%d\n", vn[i]);
-                    fclose(fo);
-                    free(vn);
-                }
-                printf("  %8.4f | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", ber, (unsigned long long)r.frames, (unsigned long long)be, (unsigned long long)fe,
-                       (double)be / ((double)r.frames * K), (double)fe / (double)r.frames, (double)r.frames * K / (r.decode_ms * 1e-3) / 1e6);
-            }
-            fflush(stdout);
-        }
-        for (double ber = ber_min; search_eff == 0.0 && ber <= ber_max + 1e-12; ber += ber_step) {
-            qldpc_mc_result r;
-            if ((rc = qldpc_mc_run(mc, ber, 0, (uint64_t)(frames > 0 ? frames : 0), max_fe, &r))) return die("mc_run", rc);
-            printf("  %8.4f | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", ber, (unsigned long long)r.frames, (unsigned long long)r.bit_errors,
-                   (unsigned long long)r.frame_errors, (double)r.bit_errors / ((double)r.frames * K), (double)r.frame_errors / (double)r.frames,
-                   (double)r.frames * K / (r.decode_ms * 1e-3) / 1e6);
-            fflush(stdout);
-        }
-        qldpc_mc_free(mc);
-        qldpc_decoder_free(dec); qldpc_encoder_free(enc); qldpc_code_free(H);
-        free(pos); free(is_info);
-        return 0;
+    qldpc_mc_cfg mcfg;
+    qldpc_mc_cfg_default(&mcfg);
+    mcfg.seed = seed; mcfg.batch = batch; mcfg.parity_ber = parity_ber;
+    if (awgn && (awgn_punct < 0 || awgn_punct >= N)) { fprintf(stderr, "qldpc_sim: -u %d outside [0, N = %d)\n", awgn_punct, N); return 2; }
+    uint8_t *cls = awgn ? (uint8_t *)calloc((size_t)N, 1) : NULL;      /* -A: every VN through the channel (class 0) but the punctured ones */
+    for (int v = 0; cls && v < awgn_punct; v++) cls[v] = QLDPC_VN_PUNCTURED;
+    if ((rc = qldpc_mc_create(dec, enc, cls, &mcfg, &mc))) return die("mc_create", rc);      /* NULL: info VNs through the BSC, the others pinned, as in run_host */
+    free(cls);
+    if (zero_source && (rc = qldpc_mc_set_source(mc, QLDPC_MC_SOURCE_ZERO))) return die("mc_set_source", rc);
+    return 0;
+}
+
+/* -A: one row, the loop at this Eb/N0 */
+static int mode_awgn(void)
+{
+    const double rate = (double)K / (double)(N - awgn_punct), sigma = sqrt(1.0 / (2.0 * rate * pow(10.0, ebno_db / 10.0)));
+    const int Q = 2 * awgn_maxq + 2;
+    int rc;
+    uint64_t *cum = (uint64_t *)malloc(sizeof(uint64_t) * 2 * 256);
+    float *value = (float *)malloc(sizeof(float) * 256);
+    if (!cum || !value) return die("mc_awgn_table", QLDPC_ENOMEM);
+    if ((rc = qldpc_mc_awgn_table(sigma, awgn_rmax, awgn_maxq, cum, cum + 256, value))) return die("mc_awgn_table", rc);
+    const qldpc_mc_channel table = {Q, {cum, cum + 256}, value, {0, 0}};
+    if ((rc = qldpc_mc_set_channel(mc, &table))) return die("mc_set_channel", rc);
+    free(cum); free(value);
+    printf("# Eb/N0 %.4f dB at rate %d / %d: sigma %.6f, %d levels, rmax %g\n", ebno_db, K, N - awgn_punct, sigma, Q, awgn_rmax);
+    qldpc_mc_result r;
+    if ((rc = qldpc_mc_run(mc, 0.25 /* not used with a table */, 0, MAX_FRAMES, max_fe, &r))) return die("mc_run", rc);
+    row_f(ebno_db, r.frames, r.bit_errors, r.frame_errors, (double)r.frames, r.decode_ms * 1e-3);
+    return 0;
+}
+
+/* -w: one qldpc_mc_strata over the weights, then FER(q) for the QBERs of -s from its rows */
+static int mode_strata(void)
+{
+    const int P = (w_hi - w_lo) / w_step + 1;
+    int rc;
+    if (P > QLDPC_MC_SWEEP_MAX_POINTS) { fprintf(stderr, "qldpc_sim: -w gives %d weights, at most %d\n", P, QLDPC_MC_SWEEP_MAX_POINTS); return 2; }
+    int *weights = (int *)malloc(sizeof(int) * (size_t)P);
+    qldpc_mc_stratum_stat *rows = (qldpc_mc_stratum_stat *)malloc(sizeof(*rows) * (size_t)P);
+    uint64_t *fr = (uint64_t *)malloc(sizeof(uint64_t) * 2 * (size_t)P), *fe = fr ? fr + P : NULL;
+    if (!weights || !rows || !fr) return die("mc_strata", QLDPC_ENOMEM);
+    for (int i = 0; i < P; i++) weights[i] = w_lo + i * w_step;
+    qldpc_mc_strata_cfg tcfg;
+    memset(&tcfg, 0, sizeof(tcfg));
+    tcfg.weights = weights; tcfg.n_strata = P; tcfg.design_qber = design_qber > 0.0 ? design_qber : ber_min;
+    tcfg.max_frames = MAX_FRAMES; tcfg.max_frame_errors = max_fe;
+    qldpc_mc_strata_result t;
+    if ((rc = qldpc_mc_strata(mc, &tcfg, &t))) return die("mc_strata", rc);
+    if ((rc = qldpc_mc_strata_stats(mc, rows, P)) < 0) return die("mc_strata_stats", rc);
+    printf("# strata: %d weights in %llu rounds, %llu frames, |LLR| of QBER %.4f; EP = the error weight\n", P, (unsigned long long)t.rounds,
+           (unsigned long long)t.frames, tcfg.design_qber);
+    for (int i = 0; i < P; i++) {      /* SIM_THR: the run's decode time is shared by the rows, as under -W */
+        row_d(rows[i].weight, rows[i].frames, rows[i].bit_errors, rows[i].frame_errors, (double)t.frames, t.decode_ms * 1e-3);
+        fr[i] = rows[i].frames; fe[i] = rows[i].frame_errors;
     }
+    FOR_EACH_BER(ber) {
+        double est[4];
+        if ((rc = qldpc_mc_strata_fer_host(K, P, weights, fr, fe, ber, est))) return die("mc_strata_fer_host", rc);
+        printf("# strata ber %.4f: FER %.6e over weights %d .. %d, binomial mass below %.6e, above %.6e, standard error %.6e\n", ber, est[0], w_lo,
+               weights[P - 1], est[1], est[2], est[3]);
+    }
+    free(weights); free(rows); free(fr);
+    return 0;
+}
 
+/* -W: the table from ONE qldpc_mc_sweep, a point per row */
+static int mode_sweep(void)
+{
+    const int n_par = N - K;
+    int n_rows = 0, bits = 0, n_order = 0, P = 0, rc;
+    FOR_EACH_BER(ber) n_rows++;
+    qldpc_mc_point *pts = (qldpc_mc_point *)calloc((size_t)(n_rows ? n_rows : 1), sizeof(*pts));
+    int *order = (int *)malloc(sizeof(int) * (size_t)(n_par ? n_par : 1)), *par = (int *)malloc(sizeof(int) * (size_t)(n_par ? n_par : 1));
+    if (!pts || !order || !par) return die("mc_sweep", QLDPC_ENOMEM);
+    if (target_eff > 0.0) {      /* parity VN j along the accumulator, visited in bit-reversed j: every prefix is evenly spaced */
+        int m = 0;
+        for (int v = 0; v < N; v++) if (!is_info[v]) par[m++] = v;
+        while ((1 << bits) < n_par) bits++;
+        for (int i = 0; i < (1 << bits); i++) {
+            int j = 0;
+            for (int b = 0; b < bits; b++) j |= ((i >> b) & 1) << (bits - 1 - b);
+            if (j < n_par) order[n_order++] = par[j];
+        }
+    }
+    FOR_EACH_BER(ber) {
+        const int n_punct = target_eff > 0.0 ? punct_count(ber, target_eff, 1) : 0;
+        if (n_punct < 0) continue;
+        pts[P].qber = ber; pts[P].n_punct = n_punct; P++;
+    }
+    if (P > 0) {
+        qldpc_mc_sweep_cfg wcfg;
+        memset(&wcfg, 0, sizeof(wcfg));
+        wcfg.points = pts; wcfg.n_points = P; wcfg.punct_order = n_order ? order : NULL; wcfg.n_order = n_order;
+        wcfg.max_frames = MAX_FRAMES; wcfg.max_frame_errors = max_fe;
+        qldpc_mc_sweep_result w;
+        if ((rc = qldpc_mc_sweep(mc, &wcfg, &w))) return die("mc_sweep", rc);
+        qldpc_mc_point_stat *rows = (qldpc_mc_point_stat *)malloc(sizeof(*rows) * (size_t)P);
+        if (!rows || (rc = qldpc_mc_sweep_stats(mc, rows, P)) < 0) return die("mc_sweep_stats", rows ? rc : QLDPC_ENOMEM);
+        printf("# sweep: %d points in %llu rounds, %llu frames\n", P, (unsigned long long)w.rounds, (unsigned long long)w.frames);
+        for (int q = 0; q < P; q++)      /* SIM_THR: the sweep's decode time is shared by the rows, so it is the sweep's throughput in every row */
+            row_f(rows[q].qber, rows[q].frames, rows[q].bit_errors, rows[q].frame_errors, (double)w.frames, w.decode_ms * 1e-3);
+        free(rows);
+    }
+    free(pts); free(order); free(par);
+    return 0;
+}
+
+/* -X: every row one qldpc_mc_search */
+static int mode_search(void)
+{
+    int rc;
+    FOR_EACH_BER(ber) {
+        const int n_punct = punct_count(ber, search_eff, 0);      /* as -e computes it */
+        qldpc_mc_search_cfg scfg;
+        memset(&scfg, 0, sizeof(scfg));
+        scfg.n_punct = n_punct; scfg.frames_per_pattern = frames_per_pattern; scfg.stop_at_goal = 1;
+        qldpc_mc_search_result r;
+        if ((rc = qldpc_mc_search(mc, ber, &scfg, 0, MAX_FRAMES, &r))) return die("mc_search", rc);
+        qldpc_mc_pattern_stat *rows = (qldpc_mc_pattern_stat *)malloc(sizeof(*rows) * (size_t)(r.patterns ? r.patterns : 1));
+        if (!rows || (rc = qldpc_mc_search_stats(mc, rows, (int)r.patterns)) < 0) return die("mc_search_stats", rows ? rc : QLDPC_ENOMEM);
+        uint64_t be = 0, fe = 0;
+        for (uint64_t i = 0; i < r.patterns; i++) {
+            printf("#   pattern %3llu: FE %llu / %d, BE %llu\n", (unsigned long long)rows[i].pattern, (unsigned long long)rows[i].frame_errors, frames_per_pattern,
+                   (unsigned long long)rows[i].bit_errors);
+            be += rows[i].bit_errors; fe += rows[i].frame_errors;
+        }
+        free(rows);
+        if (r.goal != UINT64_MAX) printf("# ber %.4f: goal puncture pattern %llu (FER = 0 / %d)\n", ber, (unsigned long long)r.goal, frames_per_pattern);
+        if (r.patterns) {
+            printf("# ber %.4f: best of %llu patterns: FE %llu, BE %llu per %d frames\n", ber, (unsigned long long)r.patterns, (unsigned long long)r.best_frame_errors,
+                   (unsigned long long)r.best_bit_errors, frames_per_pattern);
+            if (pattern_out) {
+                int *vn = (int *)malloc(sizeof(int) * (size_t)(n_punct ? n_punct : 1));
+                if (!vn || (rc = qldpc_mc_pattern_vns(mc, r.best, n_punct, 0, vn))) return die("mc_pattern_vns", vn ? rc : QLDPC_ENOMEM);
+                if (write_pattern(ber, n_punct, vn, (long long)r.best_frame_errors)) return 1;
+                free(vn);
+            }
+            row_f(ber, r.frames, be, fe, (double)r.frames, r.decode_ms * 1e-3);
+        }
+        fflush(stdout);
+    }
+    return 0;
+}
+
+/* -D alone: the same table, every row one qldpc_mc_run */
+static int mode_rows(void)
+{
+    FOR_EACH_BER(ber) {
+        qldpc_mc_result r;
+        const int rc = qldpc_mc_run(mc, ber, 0, MAX_FRAMES, max_fe, &r);
+        if (rc) return die("mc_run", rc);
+        row_f(ber, r.frames, r.bit_errors, r.frame_errors, (double)r.frames, r.decode_ms * 1e-3);
+        fflush(stdout);
+    }
+    return 0;
+}
+
+/* the harness's own loop: source, BSC and monitor on the host, one decode_siho per batch */
+static int run_host(void)
+{
+    int rc;
     int *ref_bits = (int *)malloc(sizeof(int) * (size_t)batch * K), *enc_bits = (int *)malloc(sizeof(int) * (size_t)batch * N);
     int *dec_bits = (int *)malloc(sizeof(int) * (size_t)batch * K);
     float *llr = (float *)malloc(sizeof(float) * (size_t)batch * N);
@@ -349,17 +391,9 @@ int main(int argc, char **argv)
     int *par_pos = (int *)malloc(sizeof(int) * (size_t)(N - K + 1));
     int n_par = 0;
     for (int v = 0; v < N; v++) if (!is_info[v]) par_pos[n_par++] = v;
-    for (double ber = ber_min; ber <= ber_max + 1e-12; ber += ber_step) {
+    FOR_EACH_BER(ber) {
         const float L = qldpc_bsc_llr((float)ber);
-        /* parity_bits_to_punct(INFO_B, TTL_B, GOAL_CR) with GOAL_CR = min_cr(QBER, EFF)   (BS/src/main.cpp:29,34,280) */
-        int n_punct = 0;
-        if (target_eff > 0.0) {
-            n_punct = qldpc_parity_bits_to_punct(N, K, qldpc_min_code_rate((float)ber, (float)target_eff));
-            if (n_punct < 0) { printf("# ber %.4f: mother code rate already above the goal, nothing to puncture\n", ber); n_punct = 0; }
-            if (n_punct > n_par) n_punct = n_par;
-            printf("# ber %.4f: puncturing %d of %d parity bits -> rate %.4f, efficiency f = %.3f\n", ber, n_punct, n_par, (double)K / (N - n_punct),
-                   ((double)(n_par - n_punct) / K) / (double)qldpc_binary_entropy((float)ber));
-        }
+        const int n_punct = target_eff > 0.0 ? punct_count(ber, target_eff, 0) : 0;
         long fra = 0, be = 0, fe = 0, best_fe = -1, best_be = -1, n_pat = 0;
         int *best_pat = (search && n_punct > 0) ? (int *)malloc(sizeof(int) * (size_t)n_punct) : NULL;
         double t_dec = 0.0;
@@ -396,20 +430,24 @@ int main(int argc, char **argv)
         }
         if (best_pat) {
             printf("# ber %.4f: best of %ld patterns: FE %ld, BE %ld per %d frames\n", ber, n_pat, best_fe, best_be, batch);
-            if (pattern_out) {
-                FILE *fo = fopen(pattern_out, "w");
-                if (!fo) { perror(pattern_out); return 1; }
-                fprintf(fo, "# qldpc_sim puncture pattern: N %d K %d ber %.4f punctured %d FE %ld\n", N, K, ber, n_punct, best_fe);
-                for (int i = 0; i < n_punct; i++) fprintf(fo, "%d\n", best_pat[i]);
-                fclose(fo);
-            }
+            if (pattern_out && write_pattern(ber, n_punct, best_pat, best_fe)) return 1;
             free(best_pat);
         }
-        printf("  %8.4f | %8ld | %8ld | %8ld | %9.2e | %9.2e | %10.3f\n", ber, fra, be, fe, (double)be / ((double)fra * K), (double)fe / (double)fra,
-               (double)fra * K / t_dec / 1e6);
+        row_f(ber, (uint64_t)fra, (uint64_t)be, (uint64_t)fe, (double)fra, t_dec);
         fflush(stdout);
     }
+    free(par_pos); free(ref_bits); free(enc_bits); free(dec_bits); free(llr);
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    int rc = parse(argc, argv);
+    if (!rc) rc = setup();
+    if (!rc) rc = !on_device ? run_host() : awgn ? mode_awgn() : strata ? mode_strata() : sweep ? mode_sweep() : search_eff > 0.0 ? mode_search() : mode_rows();
+    if (rc) return rc;
+    qldpc_mc_free(mc);
     qldpc_decoder_free(dec); qldpc_encoder_free(enc); qldpc_code_free(H);
-    free(par_pos); free(pos); free(is_info); free(ref_bits); free(enc_bits); free(dec_bits); free(llr);
+    free(pos); free(is_info);
     return 0;
 }

@@ -4,27 +4,17 @@ import subprocess
 
 import pytest
 
+from mc_oracle import ROOT, SIM, sim_rows, table_rows
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "qcrypto-ldpc_amd", "host", "qldpc_sim")
 
 
 def rows(out):
-    r = []
-    for line in out.splitlines():
-        if line.startswith("#") or "|" not in line:
-            continue
-        f = [x.strip() for x in line.split("|")]
-        r.append(dict(ep=float(f[0]), fra=int(f[1]), be=int(f[2]), fe=int(f[3]), ber=float(f[4]), fer=float(f[5]), thr=float(f[6])))
-    return r
+    return [dict(ep=float(f[0]), fra=int(f[1]), be=int(f[2]), fe=int(f[3]), ber=float(f[4]), fer=float(f[5]), thr=float(f[6])) for f in table_rows(out)]
 
 
 def run(*args):
-    if not os.path.exists(SIM):
-        subprocess.check_call(["make", "-C", os.path.dirname(SIM)])
-    p = subprocess.run([SIM] + list(args), capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr
-    return p.stdout
+    return sim_rows(args, timeout=600)[1]
 
 
 def test_rate08_threshold_matches_the_reference_tables():

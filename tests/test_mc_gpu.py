@@ -7,111 +7,12 @@ import numpy as np
 import pytest
 
 import mc_ref
+from mc_oracle import COUNTERS, KINDS, N_ITE, QBER, ROOT, SEED, SIM, bsc_llrs, counters, setups, sim_rows, stage_times, tally, u32, verdicts  # noqa: F401 (setups is a fixture)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "qcrypto-ldpc_amd", "host", "qldpc_sim")
-SEED = 0x0123456789ABCDEF
 FAR = 2 ** 32 - 100
-N_ITE = 20
 # chosen by the scan recorded in the docstring of test_run_equals_the_oracle_counter_for_counter
-QBER = {"peg": 0.26, "ira": 0.03}          # every class fails between 10 % and 90 % of 192 frames
 QBER_DEAD = {"peg": 0.40, "ira": 0.06}     # every frame fails
-KINDS = {"flood": dict(schedule="flooding"), "hlay": dict(schedule="hlayered"), "i8": dict(schedule="flooding", msg_dtype="i8")}
-COUNTERS = ("frames", "bit_errors", "frame_errors", "undetected", "not_converged", "iter_sum", "iter_max", "channel_flips", "channel_bits")
-
-
-class _Setup:
-    def __init__(self, q, O, name):
-        self.name = name
-        self.code = q.Code.from_alist(os.path.join(ROOT, "tests", "golden", "PEGReg504x1008.alist")) if name == "peg" else q.Code.ira(2000, 1590)
-        self.enc = q.Encoder(self.code, "IDENTITY" if name == "peg" else "IRA")
-        self.K, self.N, self.pos = self.enc.K, self.code.N, self.enc.info_bits_pos
-        assert (self.K, self.N) == ((504, 1008) if name == "peg" else (1590, 2000))
-        self.cls = mc_ref.classes(self.K, self.N, self.pos)
-        var, chk = self.code.edges()
-        self.og = O.Graph.from_edges(self.N, self.code.M, var, chk)
-        order, _, _ = self.code.layer_order()                        # the layered oracle visits the checks in the code's layer order
-        inv = np.empty(self.code.M, np.int32)
-        inv[order] = np.arange(self.code.M, dtype=np.int32)
-        newc = inv[chk]
-        idx = np.argsort(newc, kind="stable")
-        self.ogl = O.Graph.from_edges(self.N, self.code.M, var[idx], newc[idx])
-        self._ref, self._dec, self.q, self.O = {}, {}, q, O
-
-    def decoder(self, kind, n_frames=192):
-        key = (kind, n_frames)
-        if key not in self._dec:
-            self._dec[key] = self.q.Decoder(self.code, self.K, N_ITE, info_bits_pos=self.pos, rule="NMS", rule_param=0.75, n_frames=n_frames, **KINDS[kind])
-        return self._dec[key]
-
-    def codewords(self, info_words):
-        info = mc_ref.unpack(info_words, self.K)
-        cw = self.enc.encode(info)
-        assert (cw[:, self.pos] == info).all()
-        for x in cw[:3]:
-            assert self.og.syndrome(x)[0] == 0
-        return cw
-
-    def reference(self, kind, qber, first, n):
-        """counters, histogram and failed frames of frames [first, first + n) by numpy: mc_frames_host -> oracle -> compare; computed once"""
-        key = (kind, qber, first, n)
-        if key in self._ref:
-            return self._ref[key]
-        q, O = self.q, self.O
-        info_w, flip_w = q.mc_frames_host(self.K, self.N, SEED, qber, first, n, info_bits_pos=self.pos)
-        cw = self.codewords(info_w)
-        flips = mc_ref.unpack(flip_w, self.N)
-        y = cw ^ flips
-        mag, pin = np.float32(q.bsc_llr(qber)), np.float32(q.CONFIRMED_BIT_LLR)
-        llr = np.where(y == 1, -mag, mag).astype(np.float32)
-        llr[:, self.cls == 1] = np.where(y[:, self.cls == 1] == 1, -pin, pin)
-        if kind == "flood":
-            r = O.decode(self.og, llr, "NMS", 0.75, N_ITE, n_threads=8)
-        elif kind == "hlay":
-            r = O.decode(self.ogl, llr, "NMS", 0.75, N_ITE, "hlayered", n_threads=8)
-        else:
-            r = O.decode(self.og, llr, "NMS", 0.75, N_ITE, n_threads=8, msg_i8=True, quant_scale=8.0)
-        be = (r["hard"][:, self.pos] != cw[:, self.pos]).sum(1)
-        ok, it = r["synd_ok"] != 0, r["iters"]
-        ctr = dict(frames=n, bit_errors=int(be.sum()), frame_errors=int((be > 0).sum()), undetected=int(((be > 0) & ok).sum()),
-                   not_converged=int((~ok).sum()), iter_sum=int(it.sum()), iter_max=int(it.max()),
-                   channel_flips=int(flips[:, self.cls == 0].sum()), channel_bits=n * int((self.cls == 0).sum()))
-        assert ctr["channel_flips"] == mc_ref.popcount(flip_w)             # parity_ber = 0: every flip is a channel flip
-        out = (ctr, np.bincount(it, minlength=N_ITE + 1).astype(np.uint64), (first + np.nonzero(be > 0)[0]).astype(np.uint64))
-        self._ref[key] = out
-        return out
-
-
-@pytest.fixture(scope="module")
-def setups(q, O):
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = _Setup(q, O, name)
-        return cache[name]
-    return get
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def counters(res):
-    return {k: int(res[k]) for k in COUNTERS}
-
-
-RUN_STAGES = ("source", "encode", "channel", "load", "decode", "monitor")      # every stage of run, sweep and strata that launches a kernel in every call
-
-
-def stage_times(res, launched=RUN_STAGES):
-    """every stage time of a result is finite and not negative, and positive where the stage launched a kernel in that call"""
-    for k, v in res.items():
-        if k.endswith("_ms"):
-            assert np.isfinite(v) and v >= 0, (k, v)
-    for k in launched:
-        assert res[k + "_ms"] > 0, (k, res)
 
 
 @pytest.mark.parametrize("name", ["peg", "ira"])
@@ -196,25 +97,21 @@ def test_monitor_rows_in_several_trips(q, O):
     cw = enc.encode(info)
     assert (cw[:, pos] == info).all()
     flips = mc_ref.unpack(flip_w, N)
-    y = cw ^ flips
-    mag, pin = np.float32(q.bsc_llr(qber)), np.float32(q.CONFIRMED_BIT_LLR)
-    llr = np.where(y == 1, -mag, mag).astype(np.float32)
-    llr[:, cls == 1] = np.where(y[:, cls == 1] == 1, -pin, pin)
-    r = O.decode(O.Graph.from_edges(N, code.M, var, chk), llr, "NMS", 0.75, n_ite, n_threads=8)
+    r = O.decode(O.Graph.from_edges(N, code.M, var, chk), bsc_llrs(q, cw ^ flips, cls, qber), "NMS", 0.75, n_ite, n_threads=8)
     err = np.zeros((16, N), bool)
     err[:, pos] = r["hard"][:, pos] != cw[:, pos]
-    be, ok, it, chan = err.sum(1), r["synd_ok"] != 0, r["iters"], flips.astype(bool) & (cls == 0)
+    f, chan = verdicts(r, cw, pos, flips, cls == 0), flips.astype(bool) & (cls == 0)
+    be, ok, it = f["be"], f["ok"], f["it"]
+    assert (be == err.sum(1)).all() and (f["fl"] == chan.sum(1)).all()
     print(be.tolist(), ok.tolist(), it.tolist(), chan.sum(1).tolist())
     assert (err[:8, 64 * 32:].any(1) & err[:8, last_info * 32:].any(1)).any()                # info-bit errors past the first trip and in the last info word
     assert (chan[:8, 64 * 32:259 * 32].any(1) & chan[:8, 259 * 32:].any(1)).any()          # channel flips past the first trip and in the last word
 
-    def row(a, b):
-        return dict(frames=b - a, bit_errors=int(be[a:b].sum()), frame_errors=int((be[a:b] > 0).sum()), undetected=int(((be[a:b] > 0) & ok[a:b]).sum()),
-                    not_converged=int((~ok[a:b]).sum()), iter_sum=int(it[a:b].sum()), iter_max=int(it[a:b].max()),
-                    channel_flips=int(chan[a:b].sum()), channel_bits=(b - a) * int((cls == 0).sum()))
+    def row(a, b, part=0):
+        return tally({k: v[a:b] for k, v in f.items()}, int((cls == 0).sum()), n_ite=n_ite)[part]
 
     def hist(a, b):
-        return np.bincount(it[a:b], minlength=n_ite + 1).astype(np.uint64)
+        return row(a, b, 1)
 
     dec = q.Decoder(code, K, n_ite, info_bits_pos=pos, rule="NMS", rule_param=0.75, n_frames=16)
     mc = q.MonteCarlo(dec, enc, vn_class=cls, seed=SEED, parity_ber=0.05)
@@ -288,17 +185,13 @@ def test_stop_rule(q, setups):
 
 def test_qldpc_sim_device_loop_prints_the_same_row(q, setups):
     s = setups("peg")
-    if not os.path.exists(SIM):
-        subprocess.check_call(["make", "-C", os.path.dirname(SIM)])
     alist = os.path.join(ROOT, "tests", "golden", "PEGReg504x1008.alist")
-    args = [SIM, "-a", alist, "-r", "NMS", "-p", "0.75", "-i", str(N_ITE), "-b", "192", "-s", "0.26:0.26:0.01", "-S", str(SEED), "-D"]
+    args = ["-a", alist, "-r", "NMS", "-p", "0.75", "-i", str(N_ITE), "-b", "192", "-s", "0.26:0.26:0.01", "-S", str(SEED), "-D"]
 
     def row(extra):
-        p = subprocess.run(args + extra, capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, p.stdout + p.stderr
-        rows = [l for l in p.stdout.splitlines() if not l.startswith("#") and "|" in l]
+        rows, _ = sim_rows(args + extra)
         assert len(rows) == 1
-        f = [x.strip() for x in rows[0].split("|")]
+        f = rows[0]
         return dict(fra=int(f[1]), be=int(f[2]), fe=int(f[3]), thr=float(f[6]))
 
     mc = q.MonteCarlo(s.decoder("flood"), s.enc, seed=SEED)
@@ -309,7 +202,7 @@ def test_qldpc_sim_device_loop_prints_the_same_row(q, setups):
     got = row(["-f", "1920", "-E", "1"])
     assert (got["fra"], got["be"], got["fe"]) == (res["frames"], res["bit_errors"], res["frame_errors"]) and got["fra"] == 192
     for refused in (["-e", "1.6"], ["-e", "1.6", "-R"]):                   # a random puncture pattern per batch stays host-only
-        p = subprocess.run(args + ["-f", "192"] + refused, capture_output=True, text=True, timeout=60)
+        p = subprocess.run([SIM] + args + ["-f", "192"] + refused, capture_output=True, text=True, timeout=60)
         assert p.returncode != 0 and "-D" in p.stderr
 
 

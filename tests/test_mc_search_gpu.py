@@ -9,15 +9,13 @@ import pytest
 
 import mc_ref
 import mc_search_ref
-from test_mc_gpu import KINDS, N_ITE, SEED, SIM, _Setup, counters, stage_times
+from mc_oracle import KINDS, N_ITE, PATTERN_ROW as ROW, ROOT, SEED, SIM, counters, frames_reference, setups, sim_rows, stage_times, u32  # noqa: F401 (setups is a fixture)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F, N_PAT = 8, 24
 # (n_punct, QBER) and the first of the 24 patterns per setup, chosen by the scan recorded in the docstring of test_search_equals_the_oracle_row_for_row
 POINT = {"peg": (60, 0.17), "ira": (100, 0.013)}
 FIRST = {"peg": 47, "ira": 16}
-ROW = ("pattern", "frames", "frame_errors", "bit_errors", "undetected", "not_converged", "iter_sum")
 NONE = 2 ** 64 - 1
 
 
@@ -27,26 +25,10 @@ def search_reference(s, kind, qber, n_punct, first_pattern, n_pat=N_PAT, first_f
     key = ("search", kind, qber, n_punct, first_pattern, n_pat, first_frame, None if cand is None else tuple(cand))
     if key in s._ref:
         return s._ref[key]
-    q, O = s.q, s.O
     cand = np.nonzero(s.cls == 1)[0] if cand is None else np.asarray(cand)
-    n, first = n_pat * F, first_frame + first_pattern * F
-    info_w, flip_w = q.mc_frames_host(s.K, s.N, SEED, qber, first, n, info_bits_pos=s.pos)
-    cw = s.codewords(info_w)
-    y = cw ^ mc_ref.unpack(flip_w, s.N)
-    mag, pin = np.float32(q.bsc_llr(qber)), np.float32(q.CONFIRMED_BIT_LLR)
-    llr = np.where(y == 1, -mag, mag).astype(np.float32)
-    llr[:, s.cls == 1] = np.where(y[:, s.cls == 1] == 1, -pin, pin)
-    for i in range(n_pat):
-        vns = cand[mc_search_ref.pattern(SEED, first_pattern + i, cand.size, n_punct)]
-        llr[i * F:(i + 1) * F, vns] = 0.0                                    # LLRs[pattern[i]] = 0
-    if kind == "flood":
-        r = O.decode(s.og, llr, "NMS", 0.75, N_ITE, n_threads=8)
-    elif kind == "hlay":
-        r = O.decode(s.ogl, llr, "NMS", 0.75, N_ITE, "hlayered", n_threads=8)
-    else:
-        r = O.decode(s.og, llr, "NMS", 0.75, N_ITE, n_threads=8, msg_i8=True, quant_scale=8.0)
-    be = (r["hard"][:, s.pos] != cw[:, s.pos]).sum(1).reshape(n_pat, F)
-    ok, it = (r["synd_ok"] != 0).reshape(n_pat, F), r["iters"].reshape(n_pat, F)
+    vns = [cand[mc_search_ref.pattern(SEED, first_pattern + i, cand.size, n_punct)] for i in range(n_pat)]      # LLRs[pattern[i]] = 0 in its F frames
+    f = frames_reference(s, kind, ("bsc", qber), first_frame + first_pattern * F, n_pat * F, vns, block=F)
+    be, ok, it = (f[k].reshape(n_pat, F) for k in ("be", "ok", "it"))
     rows = np.zeros(n_pat, [(k, np.uint64) for k in ROW])
     rows["pattern"] = first_pattern + np.arange(n_pat)
     rows["frames"] = F
@@ -71,21 +53,6 @@ def same(res, ref):
         assert (res["stats"][k] == ref["stats"][k]).all(), (k, res["stats"][k], ref["stats"][k])
     for k in ("goal", "best", "best_frame_errors", "best_bit_errors"):
         assert int(res[k]) == ref[k], (k, res[k], ref[k])
-
-
-@pytest.fixture(scope="module")
-def setups(q, O):
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = _Setup(q, O, name)
-        return cache[name]
-    return get
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 @pytest.mark.parametrize("name", ["peg", "ira"])
@@ -205,28 +172,25 @@ def test_fixed_puncture_set_in_run(q, setups, name, kind):
 
 def test_qldpc_sim_device_search_prints_the_same_best(q, setups, tmp_path):
     s = setups("peg")
-    if not os.path.exists(SIM):
-        subprocess.check_call(["make", "-C", os.path.dirname(SIM)])
     alist = os.path.join(ROOT, "tests", "golden", "PEGReg504x1008.alist")
     out = str(tmp_path / "pattern.txt")
     eff, qber = 1.3, 0.18
     n_punct = min(max(q.parity_bits_to_punct(s.N, s.K, q.min_code_rate(qber, eff)), 0), s.N - s.K)
     assert 0 < n_punct < s.N - s.K
-    args = [SIM, "-a", alist, "-r", "NMS", "-p", "0.75", "-i", str(N_ITE), "-b", "192", "-s", "%g:%g:0.01" % (qber, qber), "-S", str(SEED), "-D",
+    args = ["-a", alist, "-r", "NMS", "-p", "0.75", "-i", str(N_ITE), "-b", "192", "-s", "%g:%g:0.01" % (qber, qber), "-S", str(SEED), "-D",
             "-X", str(eff), "-F", str(F), "-f", "40", "-o", out]
-    p = subprocess.run(args, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    _, text = sim_rows(args)
     res = q.MonteCarlo(s.decoder("flood"), s.enc, seed=SEED).search(qber, n_punct, F, max_patterns=40, stop_at_goal=True)
-    lines = p.stdout.splitlines()
+    lines = text.splitlines()
     assert "# ber %.4f: best of %d patterns: FE %d, BE %d per %d frames" % (qber, res["patterns"], res["best_frame_errors"], res["best_bit_errors"], F) in lines
     pats = [l for l in lines if l.startswith("#   pattern")]
     assert pats == ["#   pattern %3d: FE %d / %d, BE %d" % (int(r["pattern"]), int(r["frame_errors"]), F, int(r["bit_errors"])) for r in res["stats"]]
     written = [int(l) for l in open(out).read().splitlines() if not l.startswith("#")]
     mc = q.MonteCarlo(s.decoder("flood"), s.enc, seed=SEED)
     assert written == mc.pattern_vns(res["best"], n_punct).tolist()
-    refused = subprocess.run(args[:-2] + ["-E", "3"], capture_output=True, text=True, timeout=60)      # -E does not apply to the search
+    refused = subprocess.run([SIM] + args[:-2] + ["-E", "3"], capture_output=True, text=True, timeout=60)      # -E does not apply to the search
     assert refused.returncode != 0 and "-E" in refused.stderr
-    refused = subprocess.run([a for a in args if a != "-D"], capture_output=True, text=True, timeout=60)
+    refused = subprocess.run([SIM] + [a for a in args if a != "-D"], capture_output=True, text=True, timeout=60)
     assert refused.returncode != 0 and "-D" in refused.stderr
 
 

@@ -12,38 +12,25 @@ import matlab_fp
 import mc_ref
 import mc_search_ref
 import mc_soft_ref
-from test_mc_gpu import COUNTERS, N_ITE, SEED, SIM, _Setup, counters
+from mc_oracle import N_ITE, PATTERN_ROW, ROOT, SEED, SIM, counters, oracle, setups, sim_rows, tally, u32, verdicts  # noqa: F401 (setups is a fixture)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 FAR = 2 ** 32 - 100
 SIGMA, SIGMA_DEAD = 0.8414, 1.0            # Eb/N0 1.5 dB at rate 1/2; the scan is in the docstring of test_run_equals_the_oracle_counter_for_counter
 KINDS = {"flood": dict(schedule="flooding"), "hlay": dict(schedule="hlayered"), "i8": dict(schedule="flooding", msg_dtype="i8", quant_scale=1.0)}
-ROW = ("frames", "frame_errors", "bit_errors", "undetected", "not_converged", "iter_sum")
+ROW = PATTERN_ROW[1:]
 NR = "NR_2_6_52"
 
 
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
+class _Peg:
+    """PEGReg504x1008 with the IDENTITY encoder, every VN through the channel: the shared setup "peg" with another class map"""
 
+    def __init__(self, s):
+        self.s, self.chan = s, np.zeros(s.N, np.uint8)
 
-def tally(r, cw, pos, flips, chan, first, n, n_ite):
-    """counters, iteration histogram and failed frames of an oracle result, as qldpc_mc_run defines them"""
-    be = (r["hard"][:, pos] != cw[:, pos]).sum(1)
-    ok, it = r["synd_ok"] != 0, r["iters"]
-    ctr = dict(frames=n, bit_errors=int(be.sum()), frame_errors=int((be > 0).sum()), undetected=int(((be > 0) & ok).sum()),
-               not_converged=int((~ok).sum()), iter_sum=int(it.sum()), iter_max=int(it.max()),
-               channel_flips=int(flips[:, chan].sum()), channel_bits=n * int(chan.sum()))
-    return ctr, np.bincount(it, minlength=n_ite + 1).astype(np.uint64), (first + np.nonzero(be > 0)[0]).astype(np.uint64), be, ok, it
-
-
-class _Peg(_Setup):
-    """PEGReg504x1008 with the IDENTITY encoder, every VN through the channel"""
-
-    def __init__(self, q, O):
-        super().__init__(q, O, "peg")
-        self.chan = np.zeros(self.N, np.uint8)
+    def __getattr__(self, name):
+        return getattr(self.s, name)
 
     def soft_decoder(self, kind, n_frames=64):
         key = ("soft", kind, n_frames)
@@ -52,16 +39,11 @@ class _Peg(_Setup):
         return self._dec[key]
 
     def oracle(self, kind, llr):
-        O = self.O
-        if kind == "flood":
-            return O.decode(self.og, llr, "NMS", 0.75, N_ITE, n_threads=8)
-        if kind == "hlay":
-            return O.decode(self.ogl, llr, "NMS", 0.75, N_ITE, "hlayered", n_threads=8)
-        return O.decode(self.og, llr, "NMS", 0.75, N_ITE, n_threads=8, msg_i8=True, quant_scale=1.0)
+        return oracle(self.s, kind, llr, quant_scale=1.0)
 
     def frames(self, sigma, first, n):
         """(codeword bits, LLRs, flip bits) of frames [first, first + n) through the 6-bit AWGN table at sigma; computed once"""
-        key = ("frames", sigma, first, n)
+        key = ("awgn", sigma, first, n)
         if key not in self._ref:
             q = self.q
             cw = self.codewords(q.mc_frames_host(self.K, self.N, SEED, 0.1, first, n, info_bits_pos=self.pos)[0])
@@ -73,13 +55,13 @@ class _Peg(_Setup):
         key = ("soft", kind, sigma, first, n)
         if key not in self._ref:
             cw, llr, flips = self.frames(sigma, first, n)
-            self._ref[key] = tally(self.oracle(kind, llr), cw, self.pos, flips, self.chan == 0, first, n, N_ITE)[:3]
+            self._ref[key] = tally(verdicts(self.oracle(kind, llr), cw, self.pos, flips, self.chan == 0), self.N, first)
         return self._ref[key]
 
 
 @pytest.fixture(scope="module")
-def peg(q, O):
-    return _Peg(q, O)
+def peg(setups):
+    return _Peg(setups("peg"))
 
 
 @pytest.fixture(scope="module")
@@ -220,7 +202,8 @@ def test_matlab_experiment_exact_at_1p5_db(q, O, nr):
     # the all-zero codeword sends +1 everywhere: the top level (r >= 3, 2.4 sigma) occurs, the bottom one (r < -3, 4.8 sigma) need not
     assert (llr[:, :2 * s.z] == 0).all() and (llr == np.rint(llr)).all() and -32 <= llr.min() < 0 and llr.max() == 31
     r = O.decode(s.og, llr, "OMS", matlab_fp.OFFSET, matlab_fp.MAX_ITRS, "hlayered", enable_syndrome=False, n_threads=8, msg_i8=True, quant_scale=1.0)
-    ctr, hist, failed, _, _, _ = tally(r, np.zeros((192, s.N), np.uint8), s.pos, mc_ref.unpack(flip_w, s.N), s.cls == 0, 0, 192, matlab_fp.MAX_ITRS)
+    f = verdicts(r, np.zeros((192, s.N), np.uint8), s.pos, mc_ref.unpack(flip_w, s.N), s.cls == 0)
+    ctr, hist, failed = tally(f, int((s.cls == 0).sum()), n_ite=matlab_fp.MAX_ITRS)
     print("NR_2_6_52 @ 1.5 dB:", ctr)
     assert 0.1 * 192 <= ctr["frame_errors"] <= 0.9 * 192
     res = s.mc.run(0.1, 0, 192)
@@ -245,16 +228,12 @@ def test_matlab_experiment_published_fer_at_2p35_db(q, nr):
 
 def test_qldpc_sim_awgn_rows(q, nr):
     s = nr
-    if not os.path.exists(SIM):
-        subprocess.check_call(["make", "-C", os.path.dirname(SIM)])
-    args = [SIM, "-q", s.path, "-G", "QC", "-r", "OMS", "-p", "2", "-i", "20", "-l", "-n", "-Q", "8", "-c", "1", "-S", str(SEED), "-D", "-z", "-u", str(2 * s.z)]
+    args = ["-q", s.path, "-G", "QC", "-r", "OMS", "-p", "2", "-i", "20", "-l", "-n", "-Q", "8", "-c", "1", "-S", str(SEED), "-D", "-z", "-u", str(2 * s.z)]
 
     def row(extra):
-        p = subprocess.run(args + extra, capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, p.stdout + p.stderr
-        rows = [l for l in p.stdout.splitlines() if not l.startswith("#") and "|" in l]
-        assert len(rows) == 1, p.stdout
-        f = [x.strip() for x in rows[0].split("|")]
+        rows, text = sim_rows(args + extra)
+        assert len(rows) == 1, text
+        f = rows[0]
         return dict(ep=float(f[0]), fra=int(f[1]), be=int(f[2]), fe=int(f[3]))
 
     s.mc.set_awgn(ebno_db=1.5, rate=s.rate)
@@ -267,7 +246,7 @@ def test_qldpc_sim_awgn_rows(q, nr):
     print("qldpc_sim -D -A 2.35 -z:", got)
     assert got["fra"] == 20000 and lo <= got["fe"] / 20000.0 <= hi
     for refused in ([a for a in args if a != "-D"] + ["-A", "1.5"], args + ["-A", "1.5", "-X", "1.3"], [a for a in args if a != "-D"]):
-        p = subprocess.run(refused + ["-f", "192", "-b", "192"], capture_output=True, text=True, timeout=60)
+        p = subprocess.run([SIM] + refused + ["-f", "192", "-b", "192"], capture_output=True, text=True, timeout=60)
         assert p.returncode != 0 and ("-A" in p.stderr or "-u" in p.stderr)
 
 
@@ -286,8 +265,8 @@ def test_search_with_a_table_equals_the_oracle_row_for_row(q, peg):
     vns = [cand[mc_search_ref.pattern(SEED, p, cand.size, n_punct)] for p in range(n_pat)]
     for p in range(n_pat):
         llr[p * F:(p + 1) * F, vns[p]] = 0.0
-    _, _, _, be, ok, it = tally(s.oracle("i8", llr), cw, s.pos, np.zeros_like(cw), s.chan == 0, 0, n_pat * F, N_ITE)
-    be, ok, it = be.reshape(n_pat, F), ok.reshape(n_pat, F), it.reshape(n_pat, F)
+    f = verdicts(s.oracle("i8", llr), cw, s.pos, np.zeros_like(cw), s.chan == 0)
+    be, ok, it = (f[k].reshape(n_pat, F) for k in ("be", "ok", "it"))
     ref = dict(frames=np.full(n_pat, F), frame_errors=(be > 0).sum(1), bit_errors=be.sum(1), undetected=((be > 0) & ok).sum(1),
                not_converged=(~ok).sum(1), iter_sum=it.sum(1))
     print(ref)

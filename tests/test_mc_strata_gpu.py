@@ -11,90 +11,30 @@ import pytest
 import mc_ref
 import mc_strata_ref
 import mc_sweep_ref
-from test_mc_gpu import KINDS, N_ITE, QBER, SEED, _Setup, stage_times
+from mc_oracle import COUNTERS as ROW, KINDS, N_ITE, QBER, ROOT, SEED, SIM, frames_reference, row_of, same_rows, setups, sim_rows, u32  # noqa: F401 (setups is a fixture)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "qcrypto-ldpc_amd", "host", "qldpc_sim")
 FAR = 2 ** 32 - 100
 # six weights per code across the step of P_f(w), chosen by the scan recorded in the docstring of test_rows_equal_the_oracle_and_the_schedule;
 # every stratum is decoded with |LLR| = bsc_llr(QBER[name]), the operating points of test_mc_gpu
 WEIGHTS = {"peg": (100, 124, 128, 132, 136, 170), "ira": (20, 40, 46, 52, 58, 90)}
 MAX_FRAMES = 192
-ROW = ("frames", "frame_errors", "bit_errors", "undetected", "not_converged", "iter_sum", "iter_max", "channel_flips", "channel_bits")
-
-
-@pytest.fixture(scope="module")
-def setups(q, O):
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = _Setup(q, O, name)
-        return cache[name]
-    return get
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def frames_reference(s, kind, weight, first, n, erased=()):
-    """per frame of [first, first + n) at one weight: bit errors, syndrome verdict, iterations, channel flips, by numpy: mc_weight_frames_host ->
-    encoder -> LLRs of QBER[s.name], the erased VNs at 0 -> oracle -> compare; computed once per argument set and left unchanged"""
-    key = ("strata", kind, int(weight), first, n, tuple(int(v) for v in erased))
-    if key in s._ref:
-        return s._ref[key]
-    q, O = s.q, s.O
-    info_w, flip_w = q.mc_weight_frames_host(s.K, s.N, SEED, weight, first, n, info_bits_pos=s.pos)
-    cw = s.codewords(info_w)
-    flips = mc_ref.unpack(flip_w, s.N)
-    y = cw ^ flips
-    mag, pin = np.float32(q.bsc_llr(QBER[s.name])), np.float32(q.CONFIRMED_BIT_LLR)
-    llr = np.where(y == 1, -mag, mag).astype(np.float32)
-    llr[:, s.cls == 1] = np.where(y[:, s.cls == 1] == 1, -pin, pin)
-    llr[:, list(key[5])] = 0.0
-    if kind == "flood":
-        r = O.decode(s.og, llr, "NMS", 0.75, N_ITE, n_threads=8)
-    elif kind == "hlay":
-        r = O.decode(s.ogl, llr, "NMS", 0.75, N_ITE, "hlayered", n_threads=8)
-    else:
-        r = O.decode(s.og, llr, "NMS", 0.75, N_ITE, n_threads=8, msg_i8=True, quant_scale=8.0)
-    out = dict(be=(r["hard"][:, s.pos] != cw[:, s.pos]).sum(1), ok=r["synd_ok"] != 0, it=r["iters"], fl=flips[:, s.cls == 0].sum(1))
-    for a in out.values():
-        a.setflags(write=False)
-    s._ref[key] = out
-    return out
-
-
-def row_of(s, f, n):
-    """the counter row and the histogram of the first n frames of a frames_reference"""
-    be, ok, it = f["be"][:n], f["ok"][:n], f["it"][:n]
-    row = dict(frames=n, frame_errors=int((be > 0).sum()), bit_errors=int(be.sum()), undetected=int(((be > 0) & ok).sum()), not_converged=int((~ok).sum()),
-               iter_sum=int(it.sum()), iter_max=int(it.max()) if n else 0, channel_flips=int(f["fl"][:n].sum()), channel_bits=n * int((s.cls == 0).sum()))
-    return row, np.bincount(it, minlength=N_ITE + 1).astype(np.uint64)
 
 
 def strata_reference(s, kind, weights, C_, S, max_frames, max_fe, first=0, erased=()):
     """the schedule of mc_sweep_ref over the oracle's failures of frames [first, first + max_frames) of every weight, and the rows it leads to"""
-    per = [frames_reference(s, kind, w, first, max_frames, erased) for w in weights]
+    per = [frames_reference(s, kind, ("weight", w, QBER[s.name]), first, max_frames, erased) for w in weights]
     sch = mc_sweep_ref.schedule(np.array([f["be"] > 0 for f in per]), C_, S, max_frames, max_fe)
     rows = [row_of(s, f, int(n)) for f, n in zip(per, sch["frames"])]
     return sch, rows
 
 
-def same_rows(res, hist, sch, rows, weights):
-    st = res["strata"]
-    assert st.shape == (len(weights),) and (st["weight"] == np.array(weights)).all()
-    for i, (row, h) in enumerate(rows):
-        assert {k: int(st[k][i]) for k in ROW} == row, (i, st[i], row)
-        assert (hist[i] == h).all() and int(hist[i].sum()) == row["frames"], i
-    assert (st["channel_flips"] == st["frames"] * st["weight"].astype(np.uint64)).all()      # the kernel's weight, counted by the monitor kernel
-    if sch is not None:
-        assert (st["last_round"] == sch["last_round"]).all() and (st["closed_by"] == sch["closed_by"]).all(), (st, sch)
-        assert res["rounds"] == res["batches"] == sch["rounds"] and res["frames"] == int(sch["frames"].sum())
-    assert res["decode_ms"] > 0 and res["channel_ms"] > 0 and res["total_ms"] > 0
-    stage_times(res)
+def same_strata(res, hist, sch, rows, weights):
+    def strata(st):
+        assert st.shape == (len(weights),) and (st["weight"] == np.array(weights)).all()
+        assert (st["channel_flips"] == st["frames"] * st["weight"].astype(np.uint64)).all()      # the kernel's weight, counted by the monitor kernel
+        assert res["channel_ms"] > 0
+    same_rows(res, "strata", hist, sch, rows, strata)
 
 
 @pytest.mark.parametrize("name", ["peg", "ira"])
@@ -175,7 +115,7 @@ def test_rows_equal_the_oracle_and_the_schedule(q, setups, name, kind, batch, ch
     at least two in between; the conditions are asserted on the test's own reference."""
     s = setups(name)
     weights = WEIGHTS[name]
-    full = [row_of(s, frames_reference(s, kind, w, 0, MAX_FRAMES), MAX_FRAMES)[0]["frame_errors"] for w in weights]
+    full = [row_of(s, frames_reference(s, kind, ("weight", w, QBER[s.name]), 0, MAX_FRAMES), MAX_FRAMES)[0]["frame_errors"] for w in weights]
     print(name, kind, "frame errors of 192 per weight:", dict(zip(weights, full)))
     assert min(full) == 0 and max(full) == MAX_FRAMES and sum(0 < fe < MAX_FRAMES for fe in full) >= 2      # the rows are not trivial
     sch, rows = strata_reference(s, kind, weights, chunk, batch // chunk, MAX_FRAMES, max_fe)
@@ -183,10 +123,10 @@ def test_rows_equal_the_oracle_and_the_schedule(q, setups, name, kind, batch, ch
         assert set(sch["closed_by"].tolist()) == {mc_sweep_ref.CLOSED_MAX_FE, mc_sweep_ref.CLOSED_MAX_FRAMES} and len(set(sch["frames"].tolist())) >= 2
     mc = q.MonteCarlo(s.decoder(kind), s.enc, seed=SEED, batch=batch)
     res = mc.strata(weights, QBER[name], max_frames=MAX_FRAMES, max_frame_errors=max_fe, chunk=chunk)
-    same_rows(res, mc.strata_hist(), sch, rows, weights)
+    same_strata(res, mc.strata_hist(), sch, rows, weights)
     before = mc.device_bytes
     res = mc.strata(weights, QBER[name], max_frames=MAX_FRAMES, max_frame_errors=max_fe, chunk=chunk)      # again: the same, and nothing allocated
-    same_rows(res, mc.strata_hist(), sch, rows, weights)
+    same_strata(res, mc.strata_hist(), sch, rows, weights)
     assert mc.device_bytes == before
 
 
@@ -197,7 +137,7 @@ def test_a_row_does_not_depend_on_its_neighbours(q, setups, name, kind):
     s = setups(name)
     weights = WEIGHTS[name]
     w = weights[2]
-    ref = row_of(s, frames_reference(s, kind, w, 0, 100), 100)
+    ref = row_of(s, frames_reference(s, kind, ("weight", w, QBER[s.name]), 0, 100), 100)
     mc = q.MonteCarlo(s.decoder(kind), s.enc, seed=SEED, batch=192)
 
     def rows(ws, **kw):
@@ -205,7 +145,7 @@ def test_a_row_does_not_depend_on_its_neighbours(q, setups, name, kind):
         return res, mc.strata_hist()
 
     res, hist = rows([w])
-    same_rows(res, hist, None, [ref], [w])
+    same_strata(res, hist, None, [ref], [w])
     assert res["rounds"] == 1 and res["strata"]["closed_by"][0] == q.MC_CLOSED_MAX_FRAMES      # chunk 0 = 64: 3 slots, the stratum needs 2
     res, hist = rows(weights, chunk=16)
     assert {k: int(res["strata"][k][2]) for k in ROW} == ref[0] and (hist[2] == ref[1]).all()
@@ -224,7 +164,7 @@ def test_a_row_does_not_depend_on_its_neighbours(q, setups, name, kind):
     mc.set_puncture(fixed)
     res, hist = rows([weights[1], w], first_frame=FAR + 60, chunk=16)
     mc.set_puncture(None)
-    far = row_of(s, frames_reference(s, kind, w, FAR + 60, 100, fixed), 100)
+    far = row_of(s, frames_reference(s, kind, ("weight", w, QBER[s.name]), FAR + 60, 100, fixed), 100)
     assert {k: int(res["strata"][k][1]) for k in ROW} == far[0] and (hist[1] == far[1]).all()
     assert far[0] != ref[0]
 
@@ -238,7 +178,7 @@ def test_refusals_leave_the_last_rows_readable(q, setups):
     assert mc.strata_stats().size == 0
     res = mc.strata(weights, 0.26, **good)
     hist = mc.strata_hist()
-    same_rows(res, hist, sch, rows, weights)
+    same_strata(res, hist, sch, rows, weights)
 
     def refused(status, *args, **kw):
         with pytest.raises(q.QldpcError) as e:
@@ -278,7 +218,7 @@ def test_refusals_leave_the_last_rows_readable(q, setups):
             mc.weight_frames(*bad)
         assert e.value.status == status, bad
     again = mc.strata(weights, 0.26, **good)
-    same_rows(again, mc.strata_hist(), sch, rows, weights)
+    same_strata(again, mc.strata_hist(), sch, rows, weights)
 
 
 def test_sweep_and_strata_keep_their_rows_apart(q, setups):
@@ -312,28 +252,25 @@ def test_sweep_and_strata_keep_their_rows_apart(q, setups):
 
 
 def test_qldpc_sim_strata_prints_the_same_rows(q, setups):
-    if not os.path.exists(SIM):
-        subprocess.check_call(["make", "-C", os.path.dirname(SIM)])
     alist = os.path.join(ROOT, "tests", "golden", "PEGReg504x1008.alist")
-    args = [SIM, "-a", alist, "-r", "NMS", "-p", "0.75", "-i", str(N_ITE), "-b", "192", "-S", str(SEED), "-f", "192", "-D"]
-    p = subprocess.run(args + ["-w", "120:140:4:0.26", "-E", "40", "-s", "0.20:0.26:0.03"], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
-    got = [[x.strip() for x in l.split("|")][:4] for l in p.stdout.splitlines() if not l.startswith("#") and "|" in l]      # EP FRA BE FE
+    args = ["-a", alist, "-r", "NMS", "-p", "0.75", "-i", str(N_ITE), "-b", "192", "-S", str(SEED), "-f", "192", "-D"]
+    got, text = sim_rows(args + ["-w", "120:140:4:0.26", "-E", "40", "-s", "0.20:0.26:0.03"])
+    got = [r[:4] for r in got]                                                            # EP FRA BE FE
     s = setups("peg")
     mc = q.MonteCarlo(s.decoder("flood"), s.enc, seed=SEED)
     weights = list(range(120, 141, 4))
     res = mc.strata(weights, 0.26, max_frames=192, max_frame_errors=40)
     st = res["strata"]
     assert [tuple(int(x) for x in r) for r in got] == [(int(r["weight"]), int(r["frames"]), int(r["bit_errors"]), int(r["frame_errors"])) for r in st]
-    assert len(set(r[1] for r in got)) > 1 and "# strata: 6 weights" in p.stdout
-    lines = [l for l in p.stdout.splitlines() if l.startswith("# strata ber")]
+    assert len(set(r[1] for r in got)) > 1 and "# strata: 6 weights" in text
+    lines = [l for l in text.splitlines() if l.startswith("# strata ber")]
     assert len(lines) == 3
     for l, qber in zip(lines, (0.20, 0.23, 0.26)):
         est = q.mc_strata_fer(s.K, weights, st["frames"], st["frame_errors"], qber)
         nums = [float(x.split()[0].rstrip(",")) for x in (l.split("FER ")[1], l.split("below ")[1], l.split("above ")[1], l.split("standard error ")[1])]
         assert nums == pytest.approx(list(est), rel=1e-5)                                 # the line prints seven digits
     for refused in (["-w", "120:140:4", "-W"], ["-w", "120:140:4", "-X", "1.6"], ["-w", "120:140:4", "-A", "2.0"], ["-w", "140:120:4"], ["-w", "1:2"]):
-        r = subprocess.run(args + refused, capture_output=True, text=True, timeout=60)
+        r = subprocess.run([SIM] + args + refused, capture_output=True, text=True, timeout=60)
         assert r.returncode == 2 and "-w" in r.stderr, refused
-    r = subprocess.run([a for a in args if a != "-D"] + ["-w", "120:140:4"], capture_output=True, text=True, timeout=60)
+    r = subprocess.run([SIM] + [a for a in args if a != "-D"] + ["-w", "120:140:4"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 2 and "-w" in r.stderr

@@ -10,11 +10,9 @@ import pytest
 
 import mc_ref
 import mc_sweep_ref
-from test_mc_gpu import KINDS, N_ITE, SEED, _Setup, stage_times
+from mc_oracle import COUNTERS as ROW, KINDS, N_ITE, ROOT, SEED, SIM, frames_reference, row_of, same_rows, setups, sim_rows  # noqa: F401 (setups is a fixture)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "qcrypto-ldpc_amd", "host", "qldpc_sim")
 FAR = 2 ** 32 - 100
 # four points per code from the ladders scanned in the docstring of test_mc_gpu.test_run_equals_the_oracle_counter_for_counter
 POINTS = {"peg": (0.22, 0.26, 0.30, 0.36), "ira": (0.020, 0.030, 0.040, 0.045)}
@@ -22,76 +20,21 @@ POINTS = {"peg": (0.22, 0.26, 0.30, 0.36), "ira": (0.020, 0.030, 0.040, 0.045)}
 MAX_FE = {"flood": 75, "hlay": 55, "i8": 75}
 MAX_FRAMES = 250
 N_PUNCT = {"peg": (0, 20, 40, 60), "ira": (0, 30, 60, 100)}
-ROW = ("frames", "frame_errors", "bit_errors", "undetected", "not_converged", "iter_sum", "iter_max", "channel_flips", "channel_bits")
-
-
-@pytest.fixture(scope="module")
-def setups(q, O):
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = _Setup(q, O, name)
-        return cache[name]
-    return get
-
-
-def frames_reference(s, kind, qber, first, n, erased=()):
-    """per frame of [first, first + n): bit errors, syndrome verdict, iterations, channel flips, by numpy as _Setup.reference does it
-    (mc_frames_host -> encoder -> LLRs, the erased VNs at 0 -> oracle -> compare); computed once per argument set and left unchanged"""
-    key = ("sweep", kind, qber, first, n, tuple(int(v) for v in erased))
-    if key in s._ref:
-        return s._ref[key]
-    q, O = s.q, s.O
-    info_w, flip_w = q.mc_frames_host(s.K, s.N, SEED, qber, first, n, info_bits_pos=s.pos)
-    cw = s.codewords(info_w)
-    flips = mc_ref.unpack(flip_w, s.N)
-    y = cw ^ flips
-    mag, pin = np.float32(q.bsc_llr(qber)), np.float32(q.CONFIRMED_BIT_LLR)
-    llr = np.where(y == 1, -mag, mag).astype(np.float32)
-    llr[:, s.cls == 1] = np.where(y[:, s.cls == 1] == 1, -pin, pin)
-    llr[:, list(key[5])] = 0.0
-    if kind == "flood":
-        r = O.decode(s.og, llr, "NMS", 0.75, N_ITE, n_threads=8)
-    elif kind == "hlay":
-        r = O.decode(s.ogl, llr, "NMS", 0.75, N_ITE, "hlayered", n_threads=8)
-    else:
-        r = O.decode(s.og, llr, "NMS", 0.75, N_ITE, n_threads=8, msg_i8=True, quant_scale=8.0)
-    out = dict(be=(r["hard"][:, s.pos] != cw[:, s.pos]).sum(1), ok=r["synd_ok"] != 0, it=r["iters"], fl=flips[:, s.cls == 0].sum(1))
-    for a in out.values():
-        a.setflags(write=False)
-    s._ref[key] = out
-    return out
-
-
-def row_of(s, f, n):
-    """the counter row and the histogram of the first n frames of a frames_reference"""
-    be, ok, it = f["be"][:n], f["ok"][:n], f["it"][:n]
-    row = dict(frames=n, frame_errors=int((be > 0).sum()), bit_errors=int(be.sum()), undetected=int(((be > 0) & ok).sum()), not_converged=int((~ok).sum()),
-               iter_sum=int(it.sum()), iter_max=int(it.max()) if n else 0, channel_flips=int(f["fl"][:n].sum()), channel_bits=n * int((s.cls == 0).sum()))
-    return row, np.bincount(it, minlength=N_ITE + 1).astype(np.uint64)
 
 
 def sweep_reference(s, kind, qbers, C_, S, max_frames, max_fe):
     """the schedule of mc_sweep_ref over the oracle's failures of frames [0, max_frames) of every point, and the rows it leads to"""
-    per = [frames_reference(s, kind, qb, 0, max_frames) for qb in qbers]
+    per = [frames_reference(s, kind, ("bsc", qb), 0, max_frames) for qb in qbers]
     sch = mc_sweep_ref.schedule(np.array([f["be"] > 0 for f in per]), C_, S, max_frames, max_fe)
     rows = [row_of(s, f, int(n)) for f, n in zip(per, sch["frames"])]
     return sch, rows
 
 
-def same_rows(res, hist, sch, rows, qbers, n_punct=None):
-    pts = res["points"]
-    assert pts.shape == (len(qbers),) and (pts["qber"] == np.array(qbers)).all()
-    assert (pts["n_punct"] == (np.zeros(len(qbers)) if n_punct is None else np.array(n_punct))).all()
-    for i, (row, h) in enumerate(rows):
-        assert {k: int(pts[k][i]) for k in ROW} == row, (i, pts[i], row)
-        assert (hist[i] == h).all() and int(hist[i].sum()) == row["frames"], i
-    if sch is not None:
-        assert (pts["last_round"] == sch["last_round"]).all() and (pts["closed_by"] == sch["closed_by"]).all(), (pts, sch)
-        assert res["rounds"] == res["batches"] == sch["rounds"] and res["frames"] == int(sch["frames"].sum())
-    assert res["decode_ms"] > 0 and res["total_ms"] > 0
-    stage_times(res)
+def same_points(res, hist, sch, rows, qbers, n_punct=None):
+    def points(pts):
+        assert pts.shape == (len(qbers),) and (pts["qber"] == np.array(qbers)).all()
+        assert (pts["n_punct"] == (np.zeros(len(qbers)) if n_punct is None else np.array(n_punct))).all()
+    same_rows(res, "points", hist, sch, rows, points)
 
 
 def run_row(mc, qber, first, n):
@@ -133,10 +76,10 @@ def test_rows_equal_the_oracle_and_the_schedule(q, setups, name, kind):
     assert any(int(g.sum()) != 12 or len(set(g[g > 0].tolist())) > 1 for g in sch["gives"])  # a round that is not 12 slots in equal shares
     mc = q.MonteCarlo(s.decoder(kind), s.enc, seed=SEED, batch=192)
     res = mc.sweep(qbers, max_frames=MAX_FRAMES, max_frame_errors=max_fe, chunk=16)
-    same_rows(res, mc.sweep_hist(), sch, rows, qbers)
+    same_points(res, mc.sweep_hist(), sch, rows, qbers)
     before = mc.device_bytes
     res = mc.sweep(qbers, max_frames=MAX_FRAMES, max_frame_errors=max_fe, chunk=16)          # again: the same, and nothing allocated
-    same_rows(res, mc.sweep_hist(), sch, rows, qbers)
+    same_points(res, mc.sweep_hist(), sch, rows, qbers)
     assert mc.device_bytes == before
 
 
@@ -150,7 +93,7 @@ def test_rows_with_unequal_shares(q, setups, name, kind):
     assert any(len(set(g[g > 0].tolist())) > 1 for g in sch["gives"]) and len(set(sch["frames"].tolist())) >= 3
     mc = q.MonteCarlo(s.decoder(kind), s.enc, seed=SEED, batch=160)
     res = mc.sweep(qbers, max_frames=MAX_FRAMES, max_frame_errors=max_fe, chunk=16)
-    same_rows(res, mc.sweep_hist(), sch, rows, qbers)
+    same_points(res, mc.sweep_hist(), sch, rows, qbers)
 
 
 @pytest.mark.parametrize("name,kind", [("peg", "flood"), ("ira", "i8"), ("peg", "hlay")])
@@ -181,11 +124,11 @@ def test_a_row_is_the_points_own_run(q, setups, name, kind):
     for i in range(4):
         row, h, _ = own(i, int(pts["frames"][i]))
         rows.append((row, h))
-    same_rows(res, hist, None, rows, qbers, n_punct)
+    same_points(res, hist, None, rows, qbers, n_punct)
     after = own(1, 100)
     assert before[0] == after[0] and (before[1] == after[1]).all() and (before[2] == after[2]).all()
     erased = np.sort(np.concatenate([fixed, order[:n_punct[1]]]))
-    row, h = row_of(s, frames_reference(s, kind, qbers[1], first, 100, erased), int(pts["frames"][1]))
+    row, h = row_of(s, frames_reference(s, kind, ("bsc", qbers[1]), first, 100, erased), int(pts["frames"][1]))
     assert {k: int(pts[k][1]) for k in ROW} == row and (hist[1] == h).all()
 
 
@@ -196,10 +139,10 @@ def test_frame_index_carry(q, setups):
     res = mc.sweep(qbers, first_frame=FAR, max_frames=170, max_frame_errors=0, chunk=16)      # frames 2^32 - 100 .. 2^32 + 69
     hist = mc.sweep_hist()
     rows = [run_row(mc, qb, FAR, 170)[:2] for qb in qbers]
-    same_rows(res, hist, None, rows, qbers)
+    same_points(res, hist, None, rows, qbers)
     for i, qb in enumerate(qbers):
         assert res["points"]["channel_flips"][i] == mc_ref.popcount(q.mc_frames_host(s.K, s.N, SEED, qb, FAR, 170, info_bits_pos=s.pos)[1])
-    row, h = row_of(s, frames_reference(s, "flood", qbers[1], FAR, 170), 170)
+    row, h = row_of(s, frames_reference(s, "flood", ("bsc", qbers[1]), FAR, 170), 170)
     assert {k: int(res["points"][k][1]) for k in ROW} == row and (hist[1] == h).all()
 
 
@@ -208,7 +151,7 @@ def test_point_counts(q, setups):
     mc = q.MonteCarlo(s.decoder("flood", 96), s.enc, seed=SEED, batch=32)
     # P = 1 equals run
     res = mc.sweep([0.26], max_frames=70, chunk=8)
-    same_rows(res, mc.sweep_hist(), None, [run_row(mc, 0.26, 0, 70)[:2]], [0.26])
+    same_points(res, mc.sweep_hist(), None, [run_row(mc, 0.26, 0, 70)[:2]], [0.26])
     assert res["rounds"] == 3 and res["points"]["closed_by"][0] == q.MC_CLOSED_MAX_FRAMES
     # P = 7 on 4 slots: the failure table of every point from its own run over [0, 44), the schedule from mc_sweep_ref
     qbers = (0.20, 0.24, 0.26, 0.28, 0.30, 0.33, 0.36)
@@ -224,11 +167,11 @@ def test_point_counts(q, setups):
     res = mc.sweep(qbers, max_frames=44, max_frame_errors=12, chunk=8)
     hist = mc.sweep_hist()
     rows = [run_row(mc, qb, 0, int(n))[:2] for qb, n in zip(qbers, sch["frames"])]
-    same_rows(res, hist, sch, rows, qbers)
+    same_points(res, hist, sch, rows, qbers)
     assert ((res["points"]["frames"] == 44) | (res["points"]["frame_errors"] >= 12)).all()      # every point closed
     # chunk = batch: one slot, the points one after the other
     res = mc.sweep(qbers[2:5], max_frames=40, max_frame_errors=0, chunk=32)
-    same_rows(res, mc.sweep_hist(), None, [run_row(mc, qb, 0, 40)[:2] for qb in qbers[2:5]], qbers[2:5])
+    same_points(res, mc.sweep_hist(), None, [run_row(mc, qb, 0, 40)[:2] for qb in qbers[2:5]], qbers[2:5])
     assert res["rounds"] == 6 and res["points"]["last_round"].tolist() == [1, 3, 5]
 
 
@@ -255,7 +198,7 @@ def test_refusals_leave_the_last_rows_readable(q, setups):
     assert mc.sweep_stats().size == 0
     res = mc.sweep(qbers, **good)
     hist = mc.sweep_hist()
-    same_rows(res, hist, sch, rows, qbers)
+    same_points(res, hist, sch, rows, qbers)
     order = np.nonzero(s.cls == 1)[0][:10].astype(np.int32)
 
     def refused(status, *args, **kw):
@@ -295,19 +238,16 @@ def test_refusals_leave_the_last_rows_readable(q, setups):
         q._chk(q._L.qldpc_mc_sweep_hist(mc._h, 4, None, 0), "sweep_hist")                  # a point the last sweep did not have
     assert e.value.status == -6
     again = mc.sweep(qbers, **good)
-    same_rows(again, mc.sweep_hist(), sch, rows, qbers)
+    same_points(again, mc.sweep_hist(), sch, rows, qbers)
 
 
 def test_qldpc_sim_sweep_prints_the_same_rows(q, setups):
-    if not os.path.exists(SIM):
-        subprocess.check_call(["make", "-C", os.path.dirname(SIM)])
     alist = os.path.join(ROOT, "tests", "golden", "PEGReg504x1008.alist")
-    args = [SIM, "-a", alist, "-r", "NMS", "-p", "0.75", "-i", str(N_ITE), "-b", "192", "-S", str(SEED), "-f", "250"]
+    args = ["-a", alist, "-r", "NMS", "-p", "0.75", "-i", str(N_ITE), "-b", "192", "-S", str(SEED), "-f", "250"]
 
     def rows(extra):
-        p = subprocess.run(args + extra, capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, p.stdout + p.stderr
-        return [[x.strip() for x in l.split("|")][:6] for l in p.stdout.splitlines() if not l.startswith("#") and "|" in l], p.stdout
+        got, text = sim_rows(args + extra)
+        return [r[:6] for r in got], text
 
     table = ["-s", "0.22:0.30:0.04", "-E", "0"]
     one, _ = rows(["-D"] + table)
@@ -323,5 +263,5 @@ def test_qldpc_sim_sweep_prints_the_same_rows(q, setups):
     punct, text = rows(["-D", "-W", "-e", "1.05", "-s", "0.02:0.04:0.01", "-E", "0"])
     assert len(punct) == text.count(": puncturing ") >= 1 and len(punct) + text.count("nothing to puncture") == 3
     for refused in (["-W"], ["-D", "-W", "-X", "1.6"], ["-D", "-W", "-A", "2.0"]):
-        p = subprocess.run(args + refused + table, capture_output=True, text=True, timeout=60)
+        p = subprocess.run([SIM] + args + refused + table, capture_output=True, text=True, timeout=60)
         assert p.returncode == 2 and "-W" in p.stderr, refused

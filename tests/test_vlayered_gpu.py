@@ -8,16 +8,14 @@ rules (test_transcendental_rules_tolerance): of the frames the reference converg
 """
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import vlayered_ref as R
+from mc_oracle import ROOT, sim_rows
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "qcrypto-ldpc_amd", "host", "qldpc_sim")
 
 EXACT = [("MS", 0.0), ("OMS", 0.35), ("NMS", 0.75), ("AMS_MIN", 0.0)]
 SOFT = [("SPA", 0.0), ("LSPA", 0.0), ("AMS_MINSTAR", 0.0), ("AMS_MINSTAR_L2", 0.0)]
@@ -266,11 +264,7 @@ def test_vlayered_refused_combinations(q, O, torch, peg, kw):
 def test_c_harness_vertical_layered_runs():
     """host/qldpc_sim -v on the arguments of test_alist_layered_minsum_runs, with that test's own bound (the numpy reference gives 0
     failures in 2 000 such frames, mean 2.0 iterations, so the bound hides nothing)"""
-    if not os.path.exists(SIM):
-        subprocess.check_call(["make", "-C", os.path.dirname(SIM)])
-    p = subprocess.run([SIM, "-a", os.path.join(ROOT, "tests", "golden", "PEGReg504x1008.alist"), "-r", "NMS", "-p", "0.75", "-v", "-i", "20", "-f", "200", "-b", "100",
-                        "-s", "0.02:0.02:0.01"], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr
-    rows = [[x.strip() for x in line.split("|")] for line in p.stdout.splitlines() if "|" in line and not line.startswith("#")]
+    rows, text = sim_rows(["-a", os.path.join(ROOT, "tests", "golden", "PEGReg504x1008.alist"), "-r", "NMS", "-p", "0.75", "-v", "-i", "20", "-f", "200", "-b", "100",
+                           "-s", "0.02:0.02:0.01"], timeout=600)
     assert len(rows) == 1 and int(rows[0][1]) == 200 and int(rows[0][3]) <= 2
-    assert "vertical_layered" in p.stdout and "Info. bits (K) = 504" in p.stdout
+    assert "vertical_layered" in text and "Info. bits (K) = 504" in text
