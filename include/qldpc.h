@@ -278,6 +278,16 @@ int qldpc_load_syndrome_dev(qldpc_decoder *dec, const uint32_t *d_synd_bits, int
  * qldpc_load_bits_* / qldpc_load_llr_dev for the frames just loaded; the next load clears it.
  */
 int qldpc_load_erasures_dev(qldpc_decoder *dec, const uint32_t *d_erase_bits, int n_frames);
+/*
+ * Known bits (blind reconciliation, see qldpc_recon_decode_blind): the mirror of qldpc_load_erasures_dev.  d_known_bits / d_value_bits
+ * [n_frames][ceil(N/32)] packed MSB-first, a set known bit makes that VN of that frame a known bit: its channel LLR becomes +23.03 for value bit 0
+ * and -23.03 for value bit 1 (QLDPC_CONFIRMED_BIT_LLR, what the loads give a pinned VN; msg_dtype 2: what that quantises to) whatever its class.
+ * Call after qldpc_load_* for the frames just loaded; the next load clears it.  The order relative to qldpc_load_syndrome_dev and
+ * qldpc_load_erasures_dev is free, and where a VN is both erased and known, known wins.  Works wherever qldpc_load_erasures_dev works (both
+ * engines, every schedule and message type).  Frames loaded by qldpc_load_bits_* into the coded form (flooding) are written out as the LLR array
+ * they stand for and run on it: the results are bit-identical, the run reads 4 N instead of N / 8 channel bytes per frame and pass.
+ */
+int qldpc_load_known_dev(qldpc_decoder *dec, const uint32_t *d_known_bits, const uint32_t *d_value_bits, int n_frames);
 /* s = H x for packed words d_bits[n_frames][ceil(N/32)] -> d_synd_bits[n_frames][ceil(M/32)] (Alice's side). */
 int qldpc_syndrome_dev(qldpc_decoder *dec, const uint32_t *d_bits, uint32_t *d_synd_bits, int n_frames);
 /* run the BP iterations on what was loaded. */
@@ -290,6 +300,20 @@ int qldpc_fetch_info_dev(qldpc_decoder *dec, int *d_V_K);
 int qldpc_fetch_status_dev(qldpc_decoder *dec, int *d_iters, int *d_ok);
 /* fetch: a-posteriori LLRs [n_frames][N] (debug / parity tests; costs one extra pass). */
 int qldpc_fetch_post_dev(qldpc_decoder *dec, float *d_post);
+/*
+ * fetch: the least reliable VNs of every frame (blind reconciliation).  Row f of d_weak_bits[n_frames][ceil(N/32)], packed MSB-first, has a bit
+ * set for the min(d, candidates) candidates of frame f that come first in ascending (key, v) order, key = the bit pattern of |posterior| as
+ * uint32 (bits & 0x7fffffff; -0 equals +0), over exactly the floats qldpc_fetch_post_dev returns for f (msg_dtype 2: the integer posteriors).
+ * d_cand_bits[n_frames][ceil(N/32)] = the candidates of each frame (NULL = every VN), d_take[n_frames] non-zero = the frame is wanted (NULL =
+ * every frame); rows of frames not taken are zero.  d = 0 gives zero rows, d < 0 is QLDPC_EINVAL.  Preconditions as qldpc_fetch_post_dev:
+ * QLDPC_ESTATE without a completed run, QLDPC_EUNSUPPORTED after a run that compacted.  FRAMES engine, every schedule, message type and
+ * frames_per_lane; the EDGES engine returns QLDPC_EUNSUPPORTED.  The posterior rows are read where they lie (flooding: after the posterior pass
+ * qldpc_fetch_post_dev runs, in the same buffer); beyond that buffer only the output rows are written.
+ */
+int qldpc_fetch_weakest_dev(qldpc_decoder *dec, const uint32_t *d_cand_bits, const int *d_take, int d, uint32_t *d_weak_bits);
+/* Host mirror of the select, no device needed: one frame, post[N], cand_bits[ceil(N/32)] (NULL = every v < N; bits at v >= N are ignored),
+ * weak_bits[ceil(N/32)], *n_taken (optional) = bits set.  The kernel's lanes run the same functions (csrc/qldpc_weakest_core.h). */
+int qldpc_weakest_host(const float *post, int N, const uint32_t *cand_bits, int d, uint32_t *weak_bits, int *n_taken);
 /* block until everything queued on the decoder's stream is done. */
 int qldpc_sync(qldpc_decoder *dec);
 
@@ -477,6 +501,35 @@ int qldpc_recon_decode_batch(qldpc_recon *r, int n_blocks, uint32_t *key_words, 
 int qldpc_recon_decode_blocks(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber,
                               const qldpc_recon_msg *msgs, const uint32_t *const *parity_words, int *status, int *corrected,
                               int *iterations);
+/*
+ * Blind (interactive) reconciliation: after a failed decode Bob names the few key positions with the smallest |a-posteriori LLR|, Alice answers with
+ * her bits there (qldpc_recon_disclose_host), and Bob decodes again with those bits known -- a few bits of leak per failed block instead of the
+ * withheld parity or the cascade, so that plans may sit closer to capacity.  One call = one round = qldpc_recon_decode_blocks with the positions of
+ * blind[i] pinned to Alice's bits (qldpc_load_known_dev): same grouping, lanes, CRC verification, key untouched on failure; with n_known = 0 for every
+ * block status, keys, corrected counts and iterations are those of qldpc_recon_decode_blocks.  The call keeps no state: the caller owns the record of
+ * every block, appends the answers to pos / bit and calls again with the same messages and parity words.
+ *   For a block that ends QLDPC_EDECODE, ask[0 .. n_ask) = the min(ask_bits, candidates) weakest positions (qldpc_fetch_weakest_dev) among the key
+ *   positions below key_bits that are not known yet, ascending, out of that block's failed decode; every other block gets n_ask = 0.
+ *   leaked[i] = qldpc_recon_leaked_bits(&msgs[i]) + n_known.  corrected[i] counts the bits that differ from the key handed in, at disclosed positions too.
+ *   The key returned is the full corrected key, disclosed positions included: removing them or accounting for them is privacy amplification's business.
+ * QLDPC_EINVAL: a known position repeated or not in 0 .. key_bits - 1, ask_bits < 0 (nothing is decoded).  QLDPC_EUNSUPPORTED: a session whose decoders
+ * run on the edge-parallel engine (max_blocks <= 8 with the flooding schedule), or a flooding run that compacted its frames.  With QLDPC_RECON_GANG=1
+ * these calls decode on the ordinary path, not through a gang.  qldpc_recon_msg and the wire format are unchanged: the request and the answer are two
+ * new packets of the binding.
+ */
+typedef struct qldpc_recon_blind {
+    int n_known, cap;      /* in: positions disclosed so far; cap = room in pos / bit (the caller's bookkeeping, not read) */
+    int *pos;              /* in: distinct key positions < key_bits */
+    uint8_t *bit;          /* in: Alice's bits there */
+    int n_ask;             /* out */
+    int *ask;              /* out on QLDPC_EDECODE: ascending positions to ask for, room for ask_bits */
+} qldpc_recon_blind;
+int qldpc_recon_decode_blind(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber,
+                             const qldpc_recon_msg *msgs, const uint32_t *const *parity_words, qldpc_recon_blind *blind, int ask_bits,
+                             int *status, int *corrected, int *iterations, int *leaked);
+/* Alice's answer to a request for key bits (blind reconciliation): bit[i] = bit pos[i] of her key.  Host only.  A position outside
+ * 0 .. key_bits - 1: QLDPC_EINVAL. */
+int qldpc_recon_disclose_host(const uint32_t *key_words, int key_bits, const int *pos, int n, uint8_t *bit);
 uint32_t qldpc_crc32_words(const uint32_t *words, int n_bits);
 /* The same CRC-32 the way the device verification computes it (rk_verify / rk_crc in qldpc_recon.hip): `lanes` (a power of two) equal
  * chunks, each run through the byte-wise recurrence from a zero register, folded pairwise with x^len multipliers mod the CRC polynomial,

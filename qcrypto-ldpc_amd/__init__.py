@@ -119,6 +119,9 @@ _sig("qldpc_fetch_packed_dev", C.c_int, [_vp, _vp])
 _sig("qldpc_fetch_info_dev", C.c_int, [_vp, _vp])
 _sig("qldpc_fetch_status_dev", C.c_int, [_vp, _vp, _vp])
 _sig("qldpc_fetch_post_dev", C.c_int, [_vp, _vp])
+_sig("qldpc_load_known_dev", C.c_int, [_vp, _vp, _vp, C.c_int])
+_sig("qldpc_fetch_weakest_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp])
+_sig("qldpc_weakest_host", C.c_int, [_fp, C.c_int, _vp, C.c_int, _vp, _ip])
 _sig("qldpc_sync", C.c_int, [_vp])
 _sig("qldpc_profile_enable", C.c_int, [_vp, C.c_int])
 _sig("qldpc_profile_read", C.c_int, [_vp, C.POINTER(KernelStat), C.c_int])
@@ -403,6 +406,16 @@ class Decoder:
         assert erase_bits.is_cuda and erase_bits.dtype == torch.int32 and erase_bits.is_contiguous() and erase_bits.shape[1] == (self.N + 31) // 32
         _chk(_L.qldpc_load_erasures_dev(self._h, _vp(erase_bits.data_ptr()), erase_bits.shape[0]), "load_erasures")
 
+    def load_known(self, known_bits, value_bits):
+        """blind reconciliation: packed masks [n_frames, ceil(N/32)], a set known bit pins that VN of that frame to its value bit (+-23.03);
+        known wins over erased, the next load clears it"""
+        torch = _torch()
+        W = (self.N + 31) // 32
+        for t in (known_bits, value_bits):
+            assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == W
+        assert known_bits.shape[0] == value_bits.shape[0]
+        _chk(_L.qldpc_load_known_dev(self._h, _vp(known_bits.data_ptr()), _vp(value_bits.data_ptr()), known_bits.shape[0]), "load_known")
+
     def load_syndrome(self, synd_bits):
         """syndrome form: packed target syndromes [n_frames, ceil(M/32)] for the frames just loaded"""
         torch = _torch()
@@ -447,6 +460,21 @@ class Decoder:
         torch = _torch()
         out = torch.empty((self.n_frames, self.N), dtype=torch.float32, device="cuda:%d" % self.device)
         _chk(_L.qldpc_fetch_post_dev(self._h, _vp(out.data_ptr())), "fetch_post")
+        return out
+
+    def fetch_weakest(self, d, cand_bits=None, take=None):
+        """blind reconciliation: packed rows [n_frames, ceil(N/32)] with a bit set for the min(d, candidates) smallest |posterior| of each
+        frame in (key, v) order (weakest_host); cand_bits [n_frames, ceil(N/32)] int32 = the candidates (None: every VN), take [n_frames]
+        int32, non-zero = wanted (None: every frame; rows of the others are zero)"""
+        torch = _torch()
+        W = (self.N + 31) // 32
+        if cand_bits is not None:
+            assert cand_bits.is_cuda and cand_bits.dtype == torch.int32 and cand_bits.is_contiguous() and tuple(cand_bits.shape) == (self.n_frames, W)
+        if take is not None:
+            assert take.is_cuda and take.dtype == torch.int32 and take.is_contiguous() and take.numel() == self.n_frames
+        out = torch.empty((self.n_frames, W), dtype=torch.int32, device="cuda:%d" % self.device)
+        _chk(_L.qldpc_fetch_weakest_dev(self._h, _vp(cand_bits.data_ptr()) if cand_bits is not None else None,
+                                        _vp(take.data_ptr()) if take is not None else None, int(d), _vp(out.data_ptr())), "fetch_weakest")
         return out
 
     def sync(self):
@@ -612,6 +640,23 @@ def unpack_bits(words, n):
     return bits[..., :n]
 
 
+def weakest_host(post, d, cand_bits=None):
+    """the select of blind reconciliation on the host (qldpc_weakest_host): post[N] float32 -> (packed row of ceil(N/32) uint32 words with a
+    bit set for the min(d, candidates) smallest |post| in (bit pattern of |post|, v) order, number of bits set)"""
+    x = np.ascontiguousarray(post, dtype=np.float32).ravel()
+    W = (x.size + 31) // 32
+    c = None
+    if cand_bits is not None:
+        c = np.ascontiguousarray(cand_bits, dtype=np.uint32).ravel()
+        if c.size != W:
+            raise QldpcError(-6, "weakest_host: cand_bits has %d words, ceil(N/32) = %d" % (c.size, W))
+    out = np.zeros(max(W, 1), np.uint32)
+    n = C.c_int(0)
+    _chk(_L.qldpc_weakest_host(x.ctypes.data_as(_fp), x.size, c.ctypes.data_as(_vp) if c is not None else None, int(d), out.ctypes.data_as(_vp), C.byref(n)),
+         "weakest_host")
+    return out[:W], n.value
+
+
 # ---- reconciliation sessions (engine of the ecd2 LDPC handler) ---------------------------------
 
 class ReconCfg(C.Structure):
@@ -638,6 +683,12 @@ _sig("qldpc_recon_decode_batch", C.c_int, [_vp, C.c_int, _up, C.c_int, _fp, C.PO
 _sig("qldpc_recon_encode_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _fp, C.POINTER(ReconMsg), C.POINTER(_up), _ip])
 _sig("qldpc_recon_decode_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _fp, C.POINTER(ReconMsg), C.POINTER(_up), _ip, _ip, _ip])
 _sig("qldpc_crc32_words", C.c_uint32, [_up, C.c_int])
+class ReconBlind(C.Structure):
+    _fields_ = [("n_known", C.c_int), ("cap", C.c_int), ("pos", _ip), ("bit", C.POINTER(C.c_uint8)), ("n_ask", C.c_int), ("ask", _ip)]
+
+
+_sig("qldpc_recon_decode_blind", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _fp, C.POINTER(ReconMsg), C.POINTER(_up), C.POINTER(ReconBlind), C.c_int, _ip, _ip, _ip, _ip])
+_sig("qldpc_recon_disclose_host", C.c_int, [_up, C.c_int, _ip, C.c_int, C.POINTER(C.c_uint8)])
 _sig("qldpc_crc32_words_chunked", C.c_uint32, [_up, C.c_int, C.c_int])
 _sig("qldpc_recon_parity_words", C.c_int, [C.POINTER(ReconMsg)])
 _sig("qldpc_recon_leaked_bits", C.c_int, [C.POINTER(ReconMsg)])
@@ -1393,6 +1444,15 @@ def crc32_words(words, n_bits, lanes=0):
     return int(_L.qldpc_crc32_words(w.ctypes.data_as(_up), int(n_bits)))
 
 
+def recon_disclose(key_words, key_bits, pos):
+    """Alice's answer to a request for key bits (qldpc_recon_disclose_host): uint8 array, bit pos[i] of her key"""
+    kw = np.ascontiguousarray(key_words, dtype=np.uint32)
+    p_ = _np_i32(pos)
+    out = np.zeros(max(p_.size, 1), np.uint8)
+    _chk(_L.qldpc_recon_disclose_host(kw.ctypes.data_as(_up), int(key_bits), p_.ctypes.data_as(_ip), p_.size, out.ctypes.data_as(_u8p)), "recon_disclose")
+    return out[:p_.size]
+
+
 class Recon:
     """One side's reconciliation engine: what an ecd2 LDPC handler calls (qber_estim.c:337-340,420-423)."""
 
@@ -1530,6 +1590,32 @@ class Recon:
         _chk(_L.qldpc_recon_decode_blocks(self._h, n, kp, kb.ctypes.data_as(_ip), qb.ctypes.data_as(_fp), arr, pp, st.ctypes.data_as(_ip),
                                           co.ctypes.data_as(_ip), it.ctypes.data_as(_ip)), "Recon.decode_blocks")
         return st, kws, co, it
+
+    def decode_blind(self, keys, key_bits, qber, msgs, parities, known, ask_bits):
+        """one round of blind reconciliation (qldpc_recon_decode_blind): decode_blocks with known[i] = (positions, Alice's bits there) pinned;
+        returns (status[], corrected keys, corrected[], iterations[], leaked[], asks) where asks[i] = the ascending positions block i asks for
+        next (empty unless its status is QLDPC_EDECODE)"""
+        n = len(keys)
+        kws = [np.array(k, dtype=np.uint32, copy=True) for k in keys]
+        pars = [np.ascontiguousarray(p, dtype=np.uint32) for p in parities]
+        kp = (_up * n)(*[k.ctypes.data_as(_up) for k in kws])
+        pp = (_up * n)(*[p.ctypes.data_as(_up) for p in pars])
+        kb = np.ascontiguousarray(key_bits, dtype=np.int32)
+        qb = np.ascontiguousarray(qber, dtype=np.float32)
+        arr = (ReconMsg * n)(*msgs)
+        pos = [_np_i32(k[0]).ravel() for k in known]
+        bit = [np.ascontiguousarray(k[1], dtype=np.uint8).ravel() for k in known]
+        ask = [np.zeros(max(1, int(ask_bits)), np.int32) for _ in range(n)]
+        bl = (ReconBlind * n)()
+        for i in range(n):
+            if pos[i].size != bit[i].size:
+                raise QldpcError(-1, "Recon.decode_blind: block %d has %d positions and %d bits" % (i, pos[i].size, bit[i].size))
+            bl[i].n_known = bl[i].cap = pos[i].size
+            bl[i].pos, bl[i].bit, bl[i].ask = pos[i].ctypes.data_as(_ip), bit[i].ctypes.data_as(C.POINTER(C.c_uint8)), ask[i].ctypes.data_as(_ip)
+        st, co, it, lk = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+        _chk(_L.qldpc_recon_decode_blind(self._h, n, kp, kb.ctypes.data_as(_ip), qb.ctypes.data_as(_fp), arr, pp, bl, int(ask_bits), st.ctypes.data_as(_ip),
+                                         co.ctypes.data_as(_ip), it.ctypes.data_as(_ip), lk.ctypes.data_as(_ip)), "Recon.decode_blind")
+        return st, kws, co, it, lk, [ask[i][:bl[i].n_ask].copy() for i in range(n)]
 
     def prepare_decode(self, keys, key_bits, qber, msgs, parities):
         """decode_blocks with the argument marshalling done once: returns an object whose run() is the one C call

@@ -23,6 +23,7 @@
 #include "qldpc_kernels_chain.h"
 #include "qldpc_kernels_compact.h"
 #include "qldpc_kernels_fpost.h"
+#include "qldpc_kernels_weakest.h"
 
 extern "C" int qldpc_device_count(void)
 {
@@ -192,7 +193,7 @@ extern "C" void qldpc_decoder_free(qldpc_decoder *d)
     (void)hipFree(d->d_vn_chk); (void)hipFree(d->d_gang);
     (void)hipFree(d->d_cn_ptr); (void)hipFree(d->d_cn_tr); (void)hipFree(d->d_cn_var); (void)hipFree(d->d_vn_ptr); (void)hipFree(d->d_info_pos); (void)hipFree(d->d_cn_var_t); (void)hipFree(d->d_vn_tr);
     (void)hipFree(d->d_chain_order); (void)hipFree(d->d_chain_dep); (void)hipFree(d->d_chain_ver); (void)hipFree(d->d_chain_ctl);
-    (void)hipFree(d->d_llr); (void)hipFree(d->d_llr8); (void)hipFree(d->d_ybits); (void)hipFree(d->d_ebits); (void)hipFree(d->d_fmag); (void)hipFree(d->d_fnch); (void)hipFree(d->d_vcls); (void)hipFree(d->d_a); (void)hipFree(d->d_b); (void)hipFree(d->d_post);
+    (void)hipFree(d->d_llr); (void)hipFree(d->d_llr8); (void)hipFree(d->d_ybits); (void)hipFree(d->d_ebits); (void)hipFree(d->d_known); (void)hipFree(d->d_fmag); (void)hipFree(d->d_fnch); (void)hipFree(d->d_vcls); (void)hipFree(d->d_a); (void)hipFree(d->d_b); (void)hipFree(d->d_post);
     (void)hipFree(d->d_sgn); if (d->d_hard != d->d_sgn) (void)hipFree(d->d_hard); (void)hipFree(d->d_unsat); (void)hipFree(d->d_done);
     (void)hipFree(d->d_depth); (void)hipFree(d->d_iters); (void)hipFree(d->d_active); (void)hipFree(d->h_in); (void)hipFree(d->h_out); (void)hipFree(d->d_synd); (void)hipFree(d->e_synd);
     (void)hipFree(d->e_c2v1); (void)hipFree(d->e_ctl); (void)hipFree(d->e_sgn); (void)hipFree(d->e_hard); (void)hipFree(d->e_unsat); (void)hipFree(d->e_done_at);
@@ -1654,6 +1655,7 @@ extern "C" int qldpc_load_llr_dev(qldpc_decoder *d, const float *d_llr, int n_fr
     d->n_frames = n_frames;
     d->has_synd = 0;
     d->has_erase = 0;
+    d->has_known = 0;
     d->llr_coded = 0;
     if (d->engine == QLDPC_ENGINE_EDGES) {
         prof_scope ps(d, KS_LOAD, 2.0 * d->N * 4.0 * n_frames);
@@ -1694,6 +1696,7 @@ extern "C" int qldpc_load_bits_short_dev(qldpc_decoder *d, const uint32_t *d_bit
     d->n_frames = n_frames;
     d->has_synd = 0;
     d->has_erase = 0;
+    d->has_known = 0;
     const int W = (d->N + 31) / 32;
     if (d->engine == QLDPC_ENGINE_EDGES) {
         prof_scope ps(d, KS_LOAD, ((double)W * 4.0 + d->N * 4.0) * n_frames);
@@ -1761,6 +1764,8 @@ extern "C" int qldpc_load_syndrome_dev(qldpc_decoder *d, const uint32_t *d_synd_
     return QLDPC_OK;
 }
 
+static int apply_known(qldpc_decoder *d);      /* the known bits of qldpc_load_known_dev, below */
+
 /*
  * Per-frame puncturing: d_erase_bits[n_frames][ceil(N/32)] packed MSB-first, a set bit makes that VN of that frame an erasure
  * (channel LLR 0, BS/src/main.cpp:359-362) whatever its class.  For the frames just loaded (cleared again by the next qldpc_load_*).
@@ -1777,7 +1782,7 @@ extern "C" int qldpc_load_erasures_dev(qldpc_decoder *d, const uint32_t *d_erase
         hipLaunchKernelGGL(qe_erase, dim3((unsigned)std::min((d->N + 255) / 256, 256), (unsigned)n_frames), dim3(256), 0, d->stream, d_erase_bits, d->d_llr, d->N, W);
         LAUNCHCHK();
         d->ran = 0;
-        return QLDPC_OK;
+        return d->has_known ? apply_known(d) : (int)QLDPC_OK;      /* known wins over erased */
     }
     const dim3 grid = grid_4k(d, W);
     if (d->llr_coded) {
@@ -1793,6 +1798,61 @@ extern "C" int qldpc_load_erasures_dev(qldpc_decoder *d, const uint32_t *d_erase
     }
     LAUNCHCHK();
     d->ran = 0;
+    return d->has_known ? apply_known(d) : (int)QLDPC_OK;      /* known wins over erased */
+}
+
+/*
+ * Known bits (blind reconciliation): d_known_bits / d_value_bits[n_frames][ceil(N/32)] packed MSB-first, a set known bit pins that VN of that frame
+ * to its value bit (channel LLR +-23.03, the 8-bit form what that quantises to) whatever its class and whether or not it is erased.  For the frames
+ * just loaded (cleared again by the next qldpc_load_*).  A frame set in the coded-LLR form is written out as the LLR array it stands for and runs
+ * on that: the same floats reach the passes.  The masks are kept so that erasures loaded afterwards leave the known bits standing.
+ */
+static int apply_known(qldpc_decoder *d)
+{
+    const int W = (d->N + 31) / 32;
+    const uint32_t *kn = d->d_known, *val = d->d_known + (size_t)d->cfg.max_frames * W;
+    if (d->engine == QLDPC_ENGINE_EDGES) {
+        hipLaunchKernelGGL(qe_known, dim3((unsigned)std::min((d->N + 255) / 256, 256), (unsigned)d->n_frames), dim3(256), 0, d->stream, kn, val, d->d_llr, d->N, W);
+        LAUNCHCHK();
+        return QLDPC_OK;
+    }
+    const dim3 grid = grid_4k(d, W);
+    if (d->msg_i8) {
+        const int q = (int)lrintf(std::min(127.0f, QLDPC_CONFIRMED_BIT_LLR * d->quant_scale));      /* qi_quant1 of the pin */
+        hipLaunchKernelGGL((qk_known_rows<4, uint8_t>), grid, dim3(QK_THREADS), 0, d->stream, kn, val, (uint8_t *)d->d_llr8, d->N, W, d->n_frames, (uint8_t)q, (uint8_t)(-q));
+    } else {
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_known_rows<v(), float>), grid, dim3(QK_THREADS), 0, d->stream, kn, val, d->d_llr, d->N, W, d->n_frames, QLDPC_CONFIRMED_BIT_LLR, -QLDPC_CONFIRMED_BIT_LLR); });
+    }
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_load_known_dev(qldpc_decoder *d, const uint32_t *d_known_bits, const uint32_t *d_value_bits, int n_frames)
+{
+    if (!d || !d_known_bits || !d_value_bits) return QLDPC_EINVAL;
+    if (!d->loaded || n_frames != d->n_frames) { qldpc_set_error("qldpc_load_known_dev: load %d frames first (have %d)", n_frames, d->loaded ? d->n_frames : 0); return QLDPC_ESTATE; }
+    HIPCHK(hipSetDevice(d->device));
+    view_reset(d);
+    const int W = (d->N + 31) / 32;
+    int rc;
+    if (!d->d_known && (rc = dev_alloc(d, &d->d_known, (size_t)d->cfg.max_frames * W * 2))) return rc;
+    HIPCHK(hipMemcpyAsync(d->d_known, d_known_bits, sizeof(uint32_t) * (size_t)n_frames * W, hipMemcpyDeviceToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_known + (size_t)d->cfg.max_frames * W, d_value_bits, sizeof(uint32_t) * (size_t)n_frames * W, hipMemcpyDeviceToDevice, d->stream));
+    if (d->engine != QLDPC_ENGINE_EDGES && d->llr_coded) {
+        if ((rc = ensure_llr(d))) return rc;
+        const qk_coded_llr coded = coded_llr_of(d);
+        const dim3 grid((unsigned)std::max(1, std::min((d->N + QK_WAVES - 1) / QK_WAVES, 4096)), (unsigned)d->G);
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_decode_llr<v()>), grid, dim3(QK_THREADS), 0, d->stream, coded, d->d_llr, d->N); });
+        LAUNCHCHK();
+        if (d->msg_i8) {
+            const size_t n_dwords = (size_t)d->G * d->N * 64;
+            hipLaunchKernelGGL(qi_quant_llr, dim3((unsigned)std::min<size_t>((n_dwords + 255) / 256, 16384)), dim3(256), 0, d->stream, d->d_llr, d->d_llr8, n_dwords, d->quant_scale);
+            LAUNCHCHK();
+        }
+        d->llr_coded = 0; d->has_erase = 0;      /* the erasures are in the array now */
+    }
+    if ((rc = apply_known(d))) return rc;
+    d->has_known = 1; d->ran = 0;
     return QLDPC_OK;
 }
 
@@ -1889,19 +1949,13 @@ extern "C" int qldpc_fetch_status_dev(qldpc_decoder *d, int *d_iters, int *d_ok)
     });
 }
 
-extern "C" int qldpc_fetch_post_dev(qldpc_decoder *d, float *d_post_out)
+/* the a-posteriori rows of the last run, frame-interleaved [G][N][FG] floats, where they lie or after the pass that makes them (FRAMES engine) */
+static int post_rows(qldpc_decoder *d, const char *who, const float **rows)
 {
-    if (!d || !d_post_out) return QLDPC_EINVAL;
-    int rc = need_ran(d, "qldpc_fetch_post_dev");
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        /* posterior of the last executed check pass, written frame-major directly (exact in fixed-iteration mode) */
-        return edge_vn<QK_VN_POST>(d, 0, 0, 1, d_post_out, -1);
-    }
+    int rc;
     if (d->cur_gen != 0) {
-        qldpc_set_error("qldpc_fetch_post_dev: the run compacted its active frames (%d times), the messages of frames that converged earlier are gone; "
-                        "create the decoder with compact = 2 (or freeze_messages = 1) to read posteriors", d->compactions);
+        qldpc_set_error("%s: the run compacted its active frames (%d times), the messages of frames that converged earlier are gone; "
+                        "create the decoder with compact = 2 (or freeze_messages = 1) to read posteriors", who, d->compactions);
         return QLDPC_EUNSUPPORTED;
     }
     const float *src;
@@ -1919,8 +1973,49 @@ extern "C" int qldpc_fetch_post_dev(qldpc_decoder *d, float *d_post_out)
     } else {
         src = d->d_a;
     }
+    *rows = src;
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_fetch_post_dev(qldpc_decoder *d, float *d_post_out)
+{
+    if (!d || !d_post_out) return QLDPC_EINVAL;
+    int rc = need_ran(d, "qldpc_fetch_post_dev");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    if (d->engine == QLDPC_ENGINE_EDGES) {
+        /* posterior of the last executed check pass, written frame-major directly (exact in fixed-iteration mode) */
+        return edge_vn<QK_VN_POST>(d, 0, 0, 1, d_post_out, -1);
+    }
+    const float *src;
+    if ((rc = post_rows(d, "qldpc_fetch_post_dev", &src))) return rc;
     dim3 grid((unsigned)((d->N + 63) / 64), (unsigned)d->G);
     with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_unload_f32<v()>), grid, dim3(256), 0, d->stream, src, d_post_out, d->N, d->n_frames); });
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+/*
+ * Blind reconciliation: row f of d_weak_bits = the select of qldpc_weakest_core.h (the min(d, candidates) smallest |posterior| in (key, v) order)
+ * over the floats qldpc_fetch_post_dev returns for frame f, read where they lie (qk_weakest).  Rows of frames not taken are zero.
+ */
+extern "C" int qldpc_fetch_weakest_dev(qldpc_decoder *d, const uint32_t *d_cand_bits, const int *d_take, int n_weak, uint32_t *d_weak_bits)
+{
+    if (!d || !d_weak_bits || n_weak < 0) return QLDPC_EINVAL;
+    int rc = need_ran(d, "qldpc_fetch_weakest_dev");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    if (d->engine == QLDPC_ENGINE_EDGES) {
+        qldpc_set_error("qldpc_fetch_weakest_dev: not built for the edge-parallel engine (create the decoder with engine = FRAMES)");
+        return QLDPC_EUNSUPPORTED;
+    }
+    const float *src;
+    if ((rc = post_rows(d, "qldpc_fetch_weakest_dev", &src))) return rc;
+    const int W = (d->N + 31) / 32;
+    prof_scope ps(d, KS_FETCH, ((double)d->N * 4.0 * (WK_DIGITS + 1) + (double)W * 4.0) * d->n_frames);
+    HIPCHK(hipMemsetAsync(d_weak_bits, 0, sizeof(uint32_t) * (size_t)d->n_frames * W, d->stream));
+    if (n_weak == 0) return QLDPC_OK;
+    hipLaunchKernelGGL(qk_weakest, dim3((unsigned)d->V, (unsigned)d->G), dim3(WK_THREADS), 0, d->stream, src, d->N, d->FG, d->n_frames, d_cand_bits, d_take, (uint32_t)n_weak, d_weak_bits, W);
     LAUNCHCHK();
     return QLDPC_OK;
 }

@@ -110,6 +110,7 @@ struct qldpc_decoder {
     /* coded channel LLRs (flooding, fp32 / binary16 messages, after qldpc_load_bits_*): no LLR array is read, see qk_coded_llr */
     u64 *d_ybits; float *d_fmag; int *d_fnch; uint8_t *d_vcls; int llr_coded;
     u64 *d_ebits; int has_erase;     /* [G][N][V] per-frame erasure ballots of the coded form (allocated on first use), set by qldpc_load_erasures_dev */
+    uint32_t *d_known; int has_known; /* [2][max_frames][ceil(N/32)] known / value masks of qldpc_load_known_dev (allocated on first use): kept so that erasures loaded later leave them standing */
     int post_closes_run;             /* set around the _compute_post that ends an early-exit run (not for posterior read-back) */
     int packed_h16;                  /* binary16 variant: use the packed check-node kernel when V == 2 (QLDPC_PACKED_H16=0 turns it off) */
     int msg_i8;                      /* 1: 8-bit fixed-point messages and integer arithmetic (flooding min-sum family, frames engine, V = 4) */

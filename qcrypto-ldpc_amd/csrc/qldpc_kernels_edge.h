@@ -423,6 +423,15 @@ __global__ void qe_erase(const uint32_t *__restrict__ erase, float *__restrict__
         if ((erase[(size_t)f * W + (v >> 5)] >> (31 - (v & 31))) & 1u) llr[(size_t)f * N + v] = 0.0f;
 }
 
+/* known bits for the frame-major floats (qldpc_load_known_dev): a set known bit pins that LLR to +-23.03 by its value bit */
+__global__ void qe_known(const uint32_t *__restrict__ known, const uint32_t *__restrict__ value, float *__restrict__ llr, int N, int W)
+{
+    const int f = blockIdx.y;
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < N; v += gridDim.x * blockDim.x)
+        if ((known[(size_t)f * W + (v >> 5)] >> (31 - (v & 31))) & 1u)
+            llr[(size_t)f * N + v] = ((value[(size_t)f * W + (v >> 5)] >> (31 - (v & 31))) & 1u) ? -23.025850929840455f : 23.025850929840455f;
+}
+
 __global__ void qe_fetch_info(const uint32_t *__restrict__ hard, const int *__restrict__ info_pos, int *__restrict__ out, int K, int W)
 {
     const int f = blockIdx.y;

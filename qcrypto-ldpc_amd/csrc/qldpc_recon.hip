@@ -49,6 +49,7 @@ struct recon_entry {
     int *d_iters, *d_ok;  /* [max_blocks] */
     stage_set set[2];
     int next_set;
+    uint32_t *d_blind;    /* blind rounds (allocated by the first one): known | value | candidate | weakest rows, [4][max_blocks][Wn] */
 };
 
 /* a lane = one host worker with a compute stream and a copy stream: the rate groups of a call run side by side, one lane each */
@@ -334,7 +335,7 @@ static void entry_free(recon_entry &e)
     qldpc_decoder_free(e.dec);
     qldpc_encoder_free(e.enc);
     qldpc_code_free(e.code);
-    (void)hipFree(e.d_cls); (void)hipFree(e.d_out); (void)hipFree(e.d_iters); (void)hipFree(e.d_ok);
+    (void)hipFree(e.d_cls); (void)hipFree(e.d_out); (void)hipFree(e.d_iters); (void)hipFree(e.d_ok); (void)hipFree(e.d_blind);
     for (auto &st : e.set) {
         (void)hipFree(st.d_in); (void)hipFree(st.d_res); (void)hipFree(st.d_bits); (void)hipFree(st.d_erase);
         if (st.h_in) (void)hipHostFree(st.h_in);
@@ -690,6 +691,7 @@ struct recon_job {
     std::vector<int> idx;       /* the job's blocks in the caller's arrays */
     stage_set *st;
     bool any_punct;
+    std::vector<uint32_t> h_blind, h_weak;   /* blind rounds: the job's known | value | candidate rows on their way in, its weakest rows on their way back */
 };
 
 struct recon_call {
@@ -698,6 +700,7 @@ struct recon_call {
     const int *key_bits;
     /* Bob */
     uint32_t *const *key; const float *qber; const qldpc_recon_msg *msgs; const uint32_t *const *parity; int *status, *corrected, *iterations;
+    qldpc_recon_blind *blind; int ask_bits;      /* != NULL: a blind round (qldpc_recon_decode_blind) */
     /* Alice */
     const uint32_t *const *akey; qldpc_recon_msg *amsgs; uint32_t *const *aparity;
 };
@@ -758,6 +761,44 @@ static int job_stage(lane_run *L, recon_job &j, hipStream_t cs)
     return QLDPC_OK;
 }
 
+/*
+ * A blind round (qldpc_recon_decode_blind): the positions disclosed so far become known bits of the job's frames (qldpc_load_known_dev, after the
+ * erasures: known wins), and the candidates of a later request are the key positions below the block's length that are not known yet.  The rows
+ * travel on the compute stream from the job's own host vectors; a job without a known position loads nothing and decodes as in qldpc_recon_decode_blocks.
+ */
+static int job_load_blind(lane_run *L, recon_job &j)
+{
+    recon_entry *e = j.e;
+    const recon_call &c = *L->call;
+    hipStream_t s = L->lane->stream;
+    const int n = (int)j.idx.size(), B = L->r->cfg.max_blocks;
+    const size_t Wn = (size_t)(e->K + e->M + 31) / 32;
+    if (!e->d_blind && hipMalloc((void **)&e->d_blind, sizeof(uint32_t) * 4 * (size_t)B * Wn) != hipSuccess) { qldpc_set_error("recon_decode_blind: device allocation failed"); return QLDPC_ENOMEM; }
+    j.h_blind.assign(3 * (size_t)n * Wn, 0u);
+    uint32_t *known = j.h_blind.data(), *value = known + (size_t)n * Wn, *cand = value + (size_t)n * Wn;
+    bool any = false;
+    for (int t = 0; t < n; t++) {
+        const int i = j.idx[(size_t)t], kb = c.key_bits[i];
+        const qldpc_recon_blind &b = c.blind[i];
+        uint32_t *kn = known + (size_t)t * Wn, *va = value + (size_t)t * Wn, *ca = cand + (size_t)t * Wn;
+        for (int w = 0; w < kb / 32; w++) ca[w] = 0xFFFFFFFFu;
+        if (kb & 31) ca[kb / 32] = 0xFFFFFFFFu << (32 - (kb & 31));
+        for (int k = 0; k < b.n_known; k++) {
+            const uint32_t bit = 0x80000000u >> (b.pos[k] & 31);
+            kn[b.pos[k] >> 5] |= bit; ca[b.pos[k] >> 5] &= ~bit;
+            if (b.bit[k]) va[b.pos[k] >> 5] |= bit;
+            any = true;
+        }
+    }
+    uint32_t *d_known = e->d_blind, *d_value = d_known + (size_t)B * Wn, *d_cand = d_value + (size_t)B * Wn;
+    if (any) {
+        HIPCHK(hipMemcpyAsync(d_known, known, sizeof(uint32_t) * (size_t)n * Wn, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_value, value, sizeof(uint32_t) * (size_t)n * Wn, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipMemcpyAsync(d_cand, cand, sizeof(uint32_t) * (size_t)n * Wn, hipMemcpyHostToDevice, s));
+    return any ? qldpc_load_known_dev(e->dec, d_known, d_value, n) : (int)QLDPC_OK;
+}
+
 /* the three parts of a job on the compute stream: load (after its staging has arrived), run, fetch + verify + results on their way back.  job_launch is
  * the three in order; a gang round (run_call_gang) loads every member, makes one gang run in place of the members' job_run, and fetches every member. */
 static int job_load(lane_run *L, recon_job &j, hipStream_t cs)
@@ -776,6 +817,7 @@ static int job_load(lane_run *L, recon_job &j, hipStream_t cs)
         if ((rc = qldpc_decoder_set_stream(e->dec, (void *)s))) return rc;
         if ((rc = qldpc_load_bits_short_dev(e->dec, st->d_bits, d_mag, e->d_cls, d_nch, n))) return rc;
         if (j.any_punct && (rc = qldpc_load_erasures_dev(e->dec, st->d_erase, n))) return rc;
+        if (L->call->blind && (rc = job_load_blind(L, j))) return rc;
     }
     return QLDPC_OK;
 }
@@ -807,6 +849,17 @@ static int job_fetch(lane_run *L, recon_job &j, hipStream_t cs)
         hipLaunchKernelGGL(rk_verify, dim3((unsigned)n), dim3(RK_LANES), 0, s, e->d_out, d_keys, d_nch, d_crc, e->d_ok, e->d_iters, res_keys, res, n, Wk, Wn);
         HIPCHK(hipGetLastError());
         res_words = (size_t)n * (Wk + RECON_RES_SCALARS);
+        if (L->call->blind) {
+            /* the request of every block that failed: its ask_bits weakest candidates, out of the posteriors of this decode.  The status column
+             * rk_verify just wrote is the take column (QLDPC_OK = 0 = not wanted).  The rows are waited for here: a blind round gives up the
+             * overlap of neighbouring jobs, it is the recovery path */
+            const int B = L->r->cfg.max_blocks;
+            uint32_t *d_cand = e->d_blind + 2 * (size_t)B * Wn, *d_weak = d_cand + (size_t)B * Wn;
+            if ((rc = qldpc_fetch_weakest_dev(e->dec, d_cand, res, L->call->ask_bits, d_weak))) return rc;
+            j.h_weak.assign((size_t)n * Wn, 0u);
+            HIPCHK(hipMemcpyAsync(j.h_weak.data(), d_weak, sizeof(uint32_t) * (size_t)n * Wn, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
     } else {
         if ((rc = qldpc_encode_packed_dev(e->enc, d_keys, e->d_out, n, (void *)s))) return rc;
         uint32_t *res_disc = st->d_res, *res_crc = res_disc + (size_t)n * Wm;
@@ -848,6 +901,14 @@ static int job_finish(lane_run *L, recon_job &j)
             if (c.corrected) c.corrected[i] = res[n + t];
             if (c.iterations) c.iterations[i] = res[2 * n + t];
             if (res[t] == QLDPC_OK) memcpy(c.key[i], keys + (size_t)t * Wk, sizeof(uint32_t) * (size_t)Wkey);      /* a failed block keeps its key untouched */
+            if (c.blind) {
+                qldpc_recon_blind &b = c.blind[i];
+                b.n_ask = 0;
+                const size_t Wn = (size_t)(K + M + 31) / 32;
+                const uint32_t *row = j.h_weak.data() + (size_t)t * Wn;
+                for (int v = 0; res[t] != QLDPC_OK && v < c.key_bits[i] && b.n_ask < c.ask_bits; v++)
+                    if ((row[v >> 5] >> (31 - (v & 31))) & 1u) b.ask[b.n_ask++] = v;
+            }
         }
     } else {
         const uint32_t *disc = st->h_res, *crc = disc + (size_t)n * Wm;
@@ -997,7 +1058,7 @@ static int run_call(qldpc_recon *r, const recon_call &call, const std::vector<ch
     if (const char *env = getenv("QLDPC_RECON_LANES")) n_lanes = std::max(1, std::min(RECON_LANES, atoi(env)));
     n_lanes = std::min(n_lanes, (int)groups.size());
     std::sort(groups.begin(), groups.end(), [](const group &a, const group &b) { return a.cost > b.cost; });
-    if (r->gang && call.bob && groups.size() >= 2 && groups.size() <= (size_t)QLDPC_GANG_MAX_MEMBERS) {
+    if (r->gang && call.bob && !call.blind && groups.size() >= 2 && groups.size() <= (size_t)QLDPC_GANG_MAX_MEMBERS) {
         /* only when every group's decoder can be a member (layered sessions); otherwise today's path */
         std::vector<qldpc_decoder *> decs;
         for (auto &g : groups) decs.push_back(g.e->dec);
@@ -1107,6 +1168,50 @@ extern "C" int qldpc_recon_decode_blocks(qldpc_recon *r, int n, uint32_t *const 
     memset(&c, 0, sizeof(c));
     c.bob = true; c.n = n; c.key_bits = key_bits; c.key = key_words; c.qber = qber; c.msgs = msgs; c.parity = parity_words;
     c.status = status; c.corrected = corrected; c.iterations = iterations;
+    return run_call(r, c, skip);
+}
+
+/*
+ * One round of blind reconciliation: qldpc_recon_decode_blocks with the positions of blind[i] pinned to Alice's bits; a block that fails comes
+ * back with the positions to ask for next.  Stateless across rounds: the caller appends Alice's answers to pos / bit and calls again with the
+ * same messages.  The gang path is not taken by these calls.
+ */
+extern "C" int qldpc_recon_decode_blind(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber, const qldpc_recon_msg *msgs,
+                                        const uint32_t *const *parity_words, qldpc_recon_blind *blind, int ask_bits, int *status, int *corrected, int *iterations,
+                                        int *leaked)
+{
+    if (!r || !key_words || !key_bits || !qber || !msgs || !parity_words || !blind || !status || n <= 0 || ask_bits < 0) return QLDPC_EINVAL;
+    const bool layered = r->cfg.schedule == QLDPC_SCHED_HLAYERED || (r->cfg.schedule == QLDPC_RECON_SCHED_AUTO && r->cfg.max_blocks > 8);
+    if (!layered && r->cfg.max_blocks <= 8) {
+        qldpc_set_error("recon_decode_blind: the decoders of a session with max_blocks <= 8 and the flooding schedule run on the edge-parallel engine, which has no weakest-VN select");
+        return QLDPC_EUNSUPPORTED;
+    }
+    std::vector<char> skip((size_t)n, 0);
+    std::vector<uint32_t> seen;
+    for (int i = 0; i < n; i++) {
+        if (!key_words[i] || !parity_words[i]) return QLDPC_EINVAL;
+        qldpc_recon_blind &b = blind[i];
+        if (b.n_known < 0 || (b.n_known && (!b.pos || !b.bit)) || (ask_bits && !b.ask) || key_bits[i] <= 0) return QLDPC_EINVAL;
+        seen.assign((size_t)(key_bits[i] + 31) / 32, 0u);
+        for (int k = 0; k < b.n_known; k++) {
+            const int p = b.pos[k];
+            if (p < 0 || p >= key_bits[i] || ((seen[(size_t)p >> 5] >> (31 - (p & 31))) & 1u)) {
+                qldpc_set_error("recon_decode_blind: block %d, known position %d (entry %d) is repeated or not below key_bits = %d", i, p, k, key_bits[i]);
+                return QLDPC_EINVAL;
+            }
+            seen[(size_t)p >> 5] |= 0x80000000u >> (p & 31);
+        }
+        b.n_ask = 0;
+        status[i] = QLDPC_EDECODE;
+        if (corrected) corrected[i] = 0;
+        if (iterations) iterations[i] = 0;
+        if (leaked) leaked[i] = qldpc_recon_leaked_bits(&msgs[i]) + b.n_known;
+        if (check_msg(r, &msgs[i], key_bits[i]) || !(qber[i] >= 0.0f && qber[i] < 0.5f)) { status[i] = QLDPC_ESIZE; skip[(size_t)i] = 1; }
+    }
+    recon_call c;
+    memset(&c, 0, sizeof(c));
+    c.bob = true; c.n = n; c.key_bits = key_bits; c.key = key_words; c.qber = qber; c.msgs = msgs; c.parity = parity_words;
+    c.status = status; c.corrected = corrected; c.iterations = iterations; c.blind = blind; c.ask_bits = ask_bits;
     return run_call(r, c, skip);
 }
 
