@@ -963,6 +963,87 @@ int    qldpc_mc_strata_hist(qldpc_mc *mc, int stratum, uint64_t *hist, int cap);
 int    qldpc_mc_strata_fer_host(int n_channel, int n_strata, const int *weights, const uint64_t *frames, const uint64_t *frame_errors, double qber,
                                 double out[4]);
 
+/*
+ * Blind reconciliation rounds inside the Monte-Carlo loop: what asking for the weakest key bits after a failed decode buys at a code, a rule,
+ * a QBER and a puncture set -- the FER that remains, the key bits disclosed and the decodes it costs.  The BSC at `qber`, the loop's classes
+ * and the fixed set of qldpc_mc_set_puncture; per frame i:
+ *
+ *   round 0    the decode qldpc_mc_run does
+ *   closing    a frame CLOSES in the first round whose decode ends with a zero syndrome (`ok` of qldpc_fetch_status_dev; Bob sees nothing
+ *              else): a frame that closes wrong counts as frame_errors and undetected
+ *   asking     a frame still open after round r < R = max_rounds asks for its min(ask_bits, candidates) weakest positions (the select of
+ *              qldpc_fetch_weakest_dev: ascending (bits of |posterior|, VN) over the posteriors of that very decode) among the
+ *              QLDPC_VN_CHANNEL VNs it does not know yet; known <- known | asked, the values are Alice's codeword bits
+ *   round r+1  the same frame -- the same channel word, the same |LLR| -- loaded again with the known bits pinned (qldpc_load_known_dev,
+ *              +-QLDPC_CONFIRMED_BIT_LLR) and decoded from scratch
+ *   open       a frame still open after round R stays open
+ *
+ * Everything about a frame -- its round of closure, its ask sets, its verdict -- is a pure function of (seed, i, qber, ask_bits, max_rounds,
+ * decoder configuration, class map, puncture set): nothing depends on the batch, on the frames that share a launch with it or on how a run is
+ * split into calls.
+ *
+ *   pools      only the frames still open are decoded again.  Level r = 1 .. R has a pool of {frame index, known row} entries, used as a
+ *              stack of capacity 2 batch - 1; a launch decodes n <= batch frames of ONE level: fresh frames (level 0) or the last n entries of
+ *              pool r, whose channel words are generated again from their indices.  Its open frames are appended to pool r + 1 in ascending
+ *              slot order (a scan over the open flags: the content of a pool is reproducible)
+ *   schedule   qldpc_mc_blind_next_host, a pure function of the pool counts: the DEEPEST level with pool >= batch, `batch` of it; else, while
+ *              input is left, level 0 with min(batch, input_left); else the LOWEST non-empty level, all of it (the flush).  Deepest-first keeps
+ *              every pool below 2 batch (csrc/qldpc_mc_core.h has the argument)
+ *   input      ends at max_frames, and at the first launch boundary at which the frame errors tallied so far reach max_frame_errors (0 =
+ *              never).  The pools are then FLUSHED, never dropped: the frames in flight are the hard ones, and abandoning them would bias
+ *              every figure.  `frames` of the result is therefore exactly the frames drawn
+ *   rows       row r <= R: the frames that closed in round r; row R + 1: the frames still open after round R.  The counters are those of
+ *              qldpc_mc_result over the frame's LAST decode; disclosed = the key bits those frames asked for, in total
+ *
+ * One launch is generate / encode / channel / load (+ the fixed set, + the known bits) / qldpc_run / fetch + select / advance and ends with ONE
+ * read-back of the R + 2 counter rows and the pool counts.  Status codes: QLDPC_ESIZE for qber outside (0, 0.5), ask_bits < 1, max_rounds outside
+ * 0 .. QLDPC_MC_BLIND_MAX_ROUNDS; QLDPC_EINVAL for non-zero reserved words; QLDPC_EUNSUPPORTED while a table of qldpc_mc_set_channel is in
+ * force (clear it with qldpc_mc_set_channel(mc, NULL)), for a decoder on the EDGES engine (create it with engine = FRAMES) and for a decoder
+ * whose configuration can compact its active frames (flooding with compact = 0 and >= 4 groups does; create it with compact = 2), after which
+ * qldpc_fetch_weakest_dev is refused.  A refused call queues nothing and leaves the rows of the last call readable.  The first call allocates
+ * what the rounds need -- the pools, the candidate and ask rows, the list of open frames (fail_cap entries with their known rows), the counter
+ * rows -- counted by qldpc_mc_device_bytes; later calls with the same or a smaller max_rounds allocate nothing.  A call touches neither the
+ * counters of the last qldpc_mc_run nor the rows of a search, a sweep or a strata run.  Measured once at the headline shape at the foot of
+ * the waterfall (tools/mc_blind_cost.py, profiles/mc_blind_cost.json: 124 of 16 384 first decodes fail): 1.0078 decodes per frame and 1.14 x the wall
+ * time of qldpc_mc_run over the same frames, most of the difference in the select stage; deeper in the waterfall: not measured yet.
+ * Not built: continuing BP from the failed run's messages; asking among punctured parity VNs; table channels; blind rounds inside sweep /
+ * strata points; sessions or gangs as the decoder; the schedule on the device.
+ */
+#define QLDPC_MC_BLIND_MAX_ROUNDS 64
+typedef struct qldpc_mc_blind_cfg {
+    double qber;
+    int ask_bits;              /* >= 1                                                                                                 */
+    int max_rounds;            /* R, 0 .. QLDPC_MC_BLIND_MAX_ROUNDS; 0: qldpc_mc_run's decode with its frames split by the syndrome verdict */
+    uint64_t first_frame, max_frames, max_frame_errors;   /* max_frame_errors = 0: no stop rule                                        */
+    int reserved[2];           /* must be zero                                                                                         */
+} qldpc_mc_blind_cfg;
+typedef struct qldpc_mc_blind_round_stat {   /* row r <= R: the frames that closed in round r; row R + 1: still open after round R    */
+    uint64_t frames, bit_errors, frame_errors, undetected, not_converged, iter_sum, iter_max, channel_flips, channel_bits;   /* of the frame's LAST decode */
+    uint64_t disclosed;        /* key bits those frames asked for, in total                                                            */
+} qldpc_mc_blind_round_stat;
+typedef struct qldpc_mc_blind_result {
+    uint64_t frames, frame_errors, undetected, open, disclosed;   /* sums over the rows; open = the frames of row R + 1                */
+    uint64_t decodes;          /* frame-decodes run: the sum over the launches of n                                                    */
+    uint64_t launches, next_frame;
+    double source_ms, encode_ms, channel_ms, load_ms, decode_ms, select_ms, advance_ms;   /* the stages of the launches, by hipEvents: info
+                                  words, encoder, BSC, load + fixed set + known bits, qldpc_run, fetch + candidate rows + select, verdicts +
+                                  pool append                                                                                          */
+    double total_ms;           /* the whole call on the host's clock                                                                   */
+} qldpc_mc_blind_result;
+int    qldpc_mc_blind(qldpc_mc *mc, const qldpc_mc_blind_cfg *cfg, qldpc_mc_blind_result *res);
+/* of the last call: its max_rounds + 2 rows; writes min(cap, their number) and returns their number (or a status) */
+int    qldpc_mc_blind_stats(qldpc_mc *mc, qldpc_mc_blind_round_stat *rows, int cap);
+/* of the last call: the frames that ended open (the first fail_cap of them, ascending index) with everything they disclosed,
+   known_words[cap][ceil(N/32)] packed MSB-first or NULL; writes min(cap, their number) and returns their number (or a status) */
+int    qldpc_mc_blind_open(qldpc_mc *mc, uint64_t *frames, uint32_t *known_words, int cap);
+/* host mirror, no device needed: the next launch by the schedule above from pool[max_rounds + 1] (pool[0] is not read) and the input that is
+   left; returns 0 when nothing is left, 1 with *level and *n written (or a status: QLDPC_ESIZE for max_rounds outside its range or batch < 1,
+   QLDPC_EINVAL for a missing pointer) */
+int    qldpc_mc_blind_next_host(int max_rounds, int batch, const uint64_t *pool, uint64_t input_left, int *level, int *n);
+/* host only: the efficiency a stream ends at, f = (n_disclosed_parity + disclosed / frames) / (n_channel h2(qber)) in double; QLDPC_ESIZE
+   for n_channel < 1, n_disclosed_parity < 0, frames == 0 or qber outside (0, 0.5) */
+int    qldpc_mc_blind_efficiency_host(int n_channel, int n_disclosed_parity, uint64_t frames, uint64_t disclosed, double qber, double *f);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1030,6 +1030,27 @@ _sig("qldpc_mc_strata_hist", C.c_int, [_vp, C.c_int, _u64p, C.c_int])
 _sig("qldpc_mc_strata_fer_host", C.c_int, [C.c_int, C.c_int, _ip, _u64p, _u64p, C.c_double, _dp])
 
 
+class McBlindCfg(C.Structure):
+    _fields_ = [("qber", C.c_double), ("ask_bits", C.c_int), ("max_rounds", C.c_int), ("first_frame", C.c_uint64), ("max_frames", C.c_uint64),
+                ("max_frame_errors", C.c_uint64), ("reserved", C.c_int * 2)]
+
+
+class McBlindResult(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("frames", "frame_errors", "undetected", "open", "disclosed", "decodes", "launches", "next_frame")] + [
+        (n, C.c_double) for n in ("source_ms", "encode_ms", "channel_ms", "load_ms", "decode_ms", "select_ms", "advance_ms", "total_ms")]
+
+
+# a round's row: the counters of a run's result, in its order, and the key bits asked for
+MC_BLIND_ROUND_STAT = np.dtype([(n, np.uint64) for n, _ in McResult._fields_[:9]] + [("disclosed", np.uint64)])
+MC_BLIND_MAX_ROUNDS = 64
+
+_sig("qldpc_mc_blind", C.c_int, [_vp, C.POINTER(McBlindCfg), C.POINTER(McBlindResult)])
+_sig("qldpc_mc_blind_stats", C.c_int, [_vp, _vp, C.c_int])
+_sig("qldpc_mc_blind_open", C.c_int, [_vp, _u64p, _up, C.c_int])
+_sig("qldpc_mc_blind_next_host", C.c_int, [C.c_int, C.c_int, _u64p, C.c_uint64, _ip, _ip])
+_sig("qldpc_mc_blind_efficiency_host", C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_double, _dp])
+
+
 class McChannel(C.Structure):
     _fields_ = [("levels", C.c_int), ("cum", _u64p * 2), ("value", C.POINTER(C.c_float)), ("reserved", C.c_int * 2)]
 
@@ -1146,6 +1167,25 @@ def mc_strata_fer(n_channel, weights, frames, frame_errors, qber):
     _chk(_L.qldpc_mc_strata_fer_host(int(n_channel), w.size, w.ctypes.data_as(_ip), fr.ctypes.data_as(_u64p), fe.ctypes.data_as(_u64p), float(qber),
                                      out.ctypes.data_as(_dp)), "mc_strata_fer")
     return out
+
+
+def mc_blind_next(pool, input_left, batch):
+    """the next launch of MonteCarlo.blind (qldpc_mc_blind_next_host, no device needed): pool[max_rounds + 1] = the entries waiting per level
+    (pool[0] is not read) -> (level, n), or None when nothing is left.  The deepest level with pool >= batch, else fresh input, else the
+    lowest non-empty level, all of it."""
+    pl = np.ascontiguousarray(pool, dtype=np.uint64).ravel()
+    if pl.size < 1:
+        raise QldpcError(-6, "mc_blind_next: an empty pool vector (max_rounds + 1 counts)")
+    level, n = C.c_int(-1), C.c_int(0)
+    got = _chk(_L.qldpc_mc_blind_next_host(pl.size - 1, int(batch), pl.ctypes.data_as(_u64p), _u64(input_left), C.byref(level), C.byref(n)), "mc_blind_next")
+    return (level.value, n.value) if got else None
+
+
+def mc_blind_efficiency(n_channel, n_disclosed_parity, frames, disclosed, qber):
+    """f = (n_disclosed_parity + disclosed / frames) / (n_channel h2(qber)) (qldpc_mc_blind_efficiency_host, no device needed)"""
+    f = C.c_double(0.0)
+    _chk(_L.qldpc_mc_blind_efficiency_host(int(n_channel), int(n_disclosed_parity), _u64(frames), _u64(disclosed), float(qber), C.byref(f)), "mc_blind_efficiency")
+    return f.value
 
 
 def _mc_channel_arg(cum0, cum1, value, where):
@@ -1428,6 +1468,35 @@ class MonteCarlo:
     def strata_hist(self):
         """frames per iteration count of every stratum of the last strata run -> uint64 [n_strata, n_ite + 1]"""
         return self._last_hists(_L.qldpc_mc_strata_stats, _L.qldpc_mc_strata_hist, "MonteCarlo.strata_hist")
+
+    def blind(self, qber, ask_bits, max_rounds, first_frame=0, max_frames=None, max_frame_errors=0):
+        """Blind reconciliation rounds over the loop's frames (qldpc_mc_blind): a frame whose decode ends with a non-zero syndrome asks for its
+        ask_bits weakest unknown channel VNs, gets Alice's bits there and is decoded again, up to max_rounds times; only the frames still open
+        are decoded again, pooled per round across batches.  The input ends at max_frames (None = one batch) or at the first launch boundary
+        with frame_errors >= max_frame_errors (0 = never); the frames in flight are finished either way.  -> dict of the result (frames,
+        frame_errors, undetected, open, disclosed, decodes, launches, next_frame, the stage times) plus `rounds`, max_rounds + 2
+        MC_BLIND_ROUND_STAT rows: row r = the frames that closed in round r, the last row = those still open after round max_rounds."""
+        cfg = McBlindCfg()
+        cfg.qber, cfg.ask_bits, cfg.max_rounds, cfg.first_frame = float(qber), int(ask_bits), int(max_rounds), _u64(first_frame)
+        cfg.max_frames, cfg.max_frame_errors = (self.batch if max_frames is None else int(max_frames)), int(max_frame_errors)
+        res = McBlindResult()
+        _chk(_L.qldpc_mc_blind(self._h, C.byref(cfg), C.byref(res)), "MonteCarlo.blind")
+        out = _fields(res)
+        out["rounds"] = self.blind_stats()
+        assert out["rounds"].size == int(max_rounds) + 2
+        return out
+
+    def blind_stats(self):
+        """the round rows of the last blind() (MC_BLIND_ROUND_STAT)"""
+        return self._last_rows(_L.qldpc_mc_blind_stats, MC_BLIND_ROUND_STAT, "MonteCarlo.blind_stats")
+
+    def blind_open(self):
+        """the frames of the last blind() that ended open (the first fail_cap of them), ascending -> (indices uint64 [n], known rows uint32
+        [n, ceil(N/32)] MSB-first: everything each of them disclosed)"""
+        frames = np.zeros(self.fail_cap, np.uint64)
+        known = np.zeros((self.fail_cap, (self.N + 31) // 32), np.uint32)
+        n = _chk(_L.qldpc_mc_blind_open(self._h, frames.ctypes.data_as(_u64p), known.ctypes.data_as(_up), self.fail_cap), "MonteCarlo.blind_open")
+        return frames[:n].copy(), known[:n].copy()
 
     def __del__(self):
         try:

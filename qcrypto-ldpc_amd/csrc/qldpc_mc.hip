@@ -38,6 +38,10 @@
  *     row of that pattern; no flips, rx is not read.
  * mc_monitor_points: the waves dealt out per chunk (every frame of a wave belongs to one point or stratum), flips included: the tally onto the counter
  *     row of that point, per frame one add on the point's histogram row; no failed-frame list.
+ * mc_blind_cand, mc_blind_advance, mc_blind_advance_append: the blind reconciliation rounds (qldpc_mc_blind).  One lane per word of the candidate rows
+ *     chan_mask & ~known; one wave per frame for the verdict, tallied onto the counter row of the round (or of the frames that end open) together with
+ *     popcount(known), and the open flag of every slot; then the open slots appended to the next pool in slot order: a workgroup takes 64 slots, counts the
+ *     open flags before them, ballots its own and copies {frame index, known | asked} row by row, a wave per entry.  Plain stores, no returning atomics.
  *
  * No kernel waits on another wave.  The decoder and the encoder are driven through their public calls only; qldpc_engine_int.h is read for
  * the decoder's sizes, device and stream.  On the host every buffer is recorded where it is allocated (mc_alloc, mc_alloc_pinned) and freed from that
@@ -247,6 +251,86 @@ __global__ __launch_bounds__(MC_LANES) void mc_monitor_points(mc_decoded d, unsi
     sum.flush(rows + (size_t)point * MC_POINT_COUNTERS, channel_vns);
 }
 
+/* ---- blind reconciliation rounds: candidate rows, verdicts per round, ordered append to the next pool ---- */
+
+/* the counter row of a round: a point's row and the key bits its frames asked for */
+enum { MC_DISCLOSED = MC_POINT_COUNTERS, MC_BLIND_COUNTERS };
+#define MC_APPEND_SLOTS 64         /* slots of a launch per workgroup of mc_blind_advance_append: one ballot */
+
+/* cand[f][w] = chan_mask[w] & ~known[f][w]: the channel VNs frame f does not know yet (known == NULL: it knows none); take[f] = the frame is open */
+__global__ __launch_bounds__(MC_LANES) void mc_blind_cand(const uint32_t *__restrict__ chan_mask, const uint32_t *__restrict__ known, const int *__restrict__ ok,
+                                                          uint32_t *__restrict__ cand, int *__restrict__ take, unsigned total, unsigned Wn)
+{
+    const unsigned i = blockIdx.x * MC_LANES + threadIdx.x;
+    if (i >= total) return;
+    const unsigned f = i / Wn, w = i - f * Wn;
+    cand[i] = chan_mask[w] & ~(known ? known[i] : 0u);
+    if (w == 0) take[f] = !ok[f];
+}
+
+/* one wave per frame (a wave strides over the n frames of a launch at one level).  A frame that closed is tallied onto row_closed; an open one onto
+ * row_open where this was the last round (row_open != NULL), else it goes on and is tallied when it ends.  The tally of a row includes the known bits
+ * of its frames (known == NULL: none).  open[f] = the frame is open, for mc_blind_advance_append.  level_count != NULL: the pool this launch was taken from
+ * now holds `left` entries */
+__global__ __launch_bounds__(MC_LANES) void mc_blind_advance(mc_decoded d, unsigned n, const uint32_t *__restrict__ known, unsigned channel_vns,
+                                                             mc_u64 *__restrict__ row_closed, mc_u64 *__restrict__ row_open, int *__restrict__ open,
+                                                             mc_u64 *__restrict__ level_count, mc_u64 left)
+{
+    const unsigned lane = threadIdx.x & 63u, waves = gridDim.x * (MC_LANES / 64);
+    mc_tally<true> closed, ended;
+    mc_u64 asked_closed = 0, asked_ended = 0;
+    for (unsigned f = blockIdx.x * (MC_LANES / 64) + (threadIdx.x >> 6); f < n; f += waves) {
+        const mc_verdict v = mc_frame_verdict<true>(d, f);      /* the same in every lane */
+        if (lane == 0) open[f] = !v.good;
+        if (!v.good && !row_open) continue;
+        unsigned k = 0;
+        if (known) {
+            for (unsigned w = lane; w < d.Wn; w += 64u) k += (unsigned)__popc(known[(size_t)f * d.Wn + w]);
+            k = mc_wave_sum(k);
+        }
+        if (v.good) { closed.add(v); asked_closed += k; }
+        else { ended.add(v); asked_ended += k; }
+    }
+    closed.flush(row_closed, channel_vns);
+    if (row_open) ended.flush(row_open, channel_vns);
+    if (lane == 0 && asked_closed) atomicAdd(row_closed + MC_DISCLOSED, asked_closed);
+    if (lane == 0 && asked_ended) atomicAdd(row_open + MC_DISCLOSED, asked_ended);
+    if (level_count && blockIdx.x == 0 && threadIdx.x == 0) *level_count = left;
+}
+
+/* the open slots of a launch, in ascending slot order, become entries base, base + 1, ... of a pool (or of the list of the frames that end open):
+ * dst_frame[e] = the slot's frame index, dst_known[e][Wn] = known | weak of the slot (either may be NULL: no bits).  Workgroup b takes slots
+ * 64 b .. 64 b + 63: its lanes count the open flags before them, every wave ballots the 64 flags, and wave j copies the open slots number j, j + 4, ...
+ * of them.  Entries at `cap` and beyond are not written (the pools never get there, see mc_blind_next; the list keeps the first cap).  The last
+ * workgroup writes the new count, base + the open slots of the launch */
+__global__ __launch_bounds__(MC_LANES) void mc_blind_advance_append(const int *__restrict__ open, unsigned n, mc_slots sl, const uint32_t *__restrict__ known,
+                                                                    const uint32_t *__restrict__ weak, unsigned Wn, uint64_t *__restrict__ dst_frame,
+                                                                    uint32_t *__restrict__ dst_known, mc_u64 base, mc_u64 cap, mc_u64 *__restrict__ dst_count)
+{
+    static_assert(MC_APPEND_SLOTS == 64, "mc_blind_advance_append ballots one wave of flags");
+    __shared__ unsigned part[MC_LANES / 64];
+    const unsigned t = threadIdx.x, lane = t & 63u, wave = t >> 6, f0 = blockIdx.x * MC_APPEND_SLOTS;
+    unsigned c = 0;
+    for (unsigned i = t; i < f0; i += MC_LANES) c += open[i] != 0;
+    c = mc_wave_sum(c);
+    if (lane == 0) part[wave] = c;
+    __syncthreads();
+    unsigned before = 0;
+    for (unsigned w = 0; w < MC_LANES / 64; w++) before += part[w];
+    const unsigned long long flags = __ballot(f0 + lane < n && open[min(f0 + lane, n - 1u)] != 0);
+    unsigned k = 0;
+    for (unsigned long long m = flags; m; m &= m - 1ull, k++) {
+        if ((k & (MC_LANES / 64 - 1u)) != wave) continue;
+        const unsigned f = f0 + (unsigned)__ffsll(m) - 1u;
+        const mc_u64 e = base + before + k;
+        if (e >= cap) continue;
+        const size_t src = (size_t)f * Wn, dst = (size_t)e * Wn;
+        for (unsigned w = lane; w < Wn; w += 64u) dst_known[dst + w] = (known ? known[src + w] : 0u) | (weak ? weak[src + w] : 0u);
+        if (lane == 0) dst_frame[e] = sl.frame_of(f);
+    }
+    if (blockIdx.x == gridDim.x - 1 && t == 0) *dst_count = base + before + (unsigned)__popcll(flags);
+}
+
 /* ---- the radix select of qldpc_mc_core.h by one workgroup of MC_PAT_LANES lanes ---- */
 #define MC_PAT_LANES 256
 static_assert(MC_PAT_LANES == MC_SEL_BINS, "mc_select clears one histogram bin per lane");
@@ -424,7 +508,19 @@ struct qldpc_mc {
     /* the error strata run the sweep's rounds on the sweep's tables and device rows; rows_owner says whose counters and histograms those hold */
     int rows_owner;                    /* MC_ROWS_* */
     std::vector<qldpc_mc_stratum_stat> tstats;  /* of the last strata run */
+    /* the blind reconciliation rounds; the device side is allocated by the first qldpc_mc_blind (mc_blind_reserve), the pools for the deepest max_rounds so far */
+    bool blind_ready;
+    int blind_levels;                  /* the levels the pools are allocated for */
+    uint64_t *d_pframe;                /* [blind_levels][2 batch - 1] frame indices, pool r at row r - 1 */
+    uint32_t *d_pknown;                /* [blind_levels][2 batch - 1][Wn] known rows */
+    uint64_t *d_oframe; uint32_t *d_oknown;   /* [fail_cap], [fail_cap][Wn]: the frames that ended open, in the order of the launches */
+    uint32_t *d_bcand, *d_bweak;       /* [batch][Wn] candidate rows, asked rows */
+    int *d_btake, *d_bopen;            /* [batch] what qldpc_fetch_weakest_dev takes, the open flags of a launch */
+    mc_u64 *d_bctr, *h_bctr;           /* MC_BLIND_WORDS: the counter rows of a call [R + 2][MC_BLIND_COUNTERS], then R + 2 counts: [r] = the entries of pool r
+                                          (1 .. R), [R + 1] = the frames that ended open; pinned copy */
+    std::vector<qldpc_mc_blind_round_stat> bstats;   /* of the last blind call */
 };
+#define MC_BLIND_WORDS ((size_t)(MC_BLIND_MAX_ROUNDS + 2) * (MC_BLIND_COUNTERS + 1))
 enum { MC_ROWS_NONE = 0, MC_ROWS_SWEEP, MC_ROWS_STRATA };
 
 extern "C" void qldpc_mc_cfg_default(qldpc_mc_cfg *cfg)
@@ -1172,4 +1268,166 @@ extern "C" int qldpc_mc_strata_hist(qldpc_mc *mc, int stratum, uint64_t *hist, i
     if (stratum < 0 || (size_t)stratum >= mc->tstats.size()) { qldpc_set_error("mc_strata_hist: stratum=%d, the last run had %d", stratum, (int)mc->tstats.size()); return QLDPC_ESIZE; }
     if (mc->rows_owner != MC_ROWS_STRATA) { qldpc_set_error("mc_strata_hist: the device rows hold a later qldpc_mc_sweep"); return QLDPC_ESTATE; }
     return mc_row_hist(mc, stratum, hist, cap);
+}
+
+/* ------------------------------------------------------------------ blind reconciliation rounds ---- */
+
+/* the counterpart of mc_alloc for a buffer that has to grow: frees *p (count elements) and takes it off the record */
+template <typename T> static void mc_release(qldpc_mc *mc, T **p, size_t count)
+{
+    if (!*p) return;
+    const auto it = std::find(mc->dev_owned.begin(), mc->dev_owned.end(), (void *)*p);
+    if (it != mc->dev_owned.end()) mc->dev_owned.erase(it);
+    (void)hipFree(*p);
+    mc->dev_bytes -= sizeof(T) * count;
+    *p = nullptr;
+}
+
+/* everything the rounds need on the device: the launch buffers and the open list once, the pools for `levels` levels unless they hold as many already */
+static int mc_blind_reserve(qldpc_mc *mc, int levels)
+{
+    HIPCHK(hipSetDevice(mc->device));
+    const size_t Wn = (size_t)mc->Wn, B = (size_t)mc->batch, cap = MC_BLIND_POOL_CAP(mc->batch);
+    int rc = QLDPC_OK;
+    if (!mc->blind_ready) {
+        if ((rc = mc_alloc(mc, &mc->d_bcand, B * Wn)) || (rc = mc_alloc(mc, &mc->d_bweak, B * Wn)) || (rc = mc_alloc(mc, &mc->d_btake, B)) ||
+            (rc = mc_alloc(mc, &mc->d_bopen, B)) || (rc = mc_alloc(mc, &mc->d_oframe, (size_t)mc->fail_cap)) ||
+            (rc = mc_alloc(mc, &mc->d_oknown, (size_t)mc->fail_cap * Wn)) || (rc = mc_alloc(mc, &mc->d_bctr, MC_BLIND_WORDS)) ||
+            (rc = mc_alloc_pinned(mc, &mc->h_bctr, MC_BLIND_WORDS)))
+            return rc;
+        mc->blind_ready = true;
+    }
+    if (levels <= mc->blind_levels) return QLDPC_OK;
+    HIPCHK(hipStreamSynchronize(mc->dec->stream));      /* nothing queued reads the pools that go */
+    mc_release(mc, &mc->d_pframe, (size_t)mc->blind_levels * cap);
+    mc_release(mc, &mc->d_pknown, (size_t)mc->blind_levels * cap * Wn);
+    mc->blind_levels = 0;
+    if ((rc = mc_alloc(mc, &mc->d_pframe, (size_t)levels * cap)) || (rc = mc_alloc(mc, &mc->d_pknown, (size_t)levels * cap * Wn))) return rc;
+    mc->blind_levels = levels;
+    return QLDPC_OK;
+}
+
+/* every argument check of qldpc_mc_blind: nothing is touched before all of them pass */
+static int mc_blind_args(const qldpc_mc *mc, const qldpc_mc_blind_cfg *cfg)
+{
+    if (cfg->reserved[0] || cfg->reserved[1]) { qldpc_set_error("mc_blind: reserved fields %d, %d must be zero", cfg->reserved[0], cfg->reserved[1]); return QLDPC_EINVAL; }
+    if (!(cfg->qber > 0.0 && cfg->qber < 0.5)) { qldpc_set_error("mc_blind: qber=%g outside (0, 0.5)", cfg->qber); return QLDPC_ESIZE; }
+    if (cfg->ask_bits < 1) { qldpc_set_error("mc_blind: ask_bits=%d (at least 1)", cfg->ask_bits); return QLDPC_ESIZE; }
+    if (cfg->max_rounds < 0 || cfg->max_rounds > QLDPC_MC_BLIND_MAX_ROUNDS) { qldpc_set_error("mc_blind: max_rounds=%d outside 0 .. %d", cfg->max_rounds, QLDPC_MC_BLIND_MAX_ROUNDS); return QLDPC_ESIZE; }
+    if (mc->soft) { qldpc_set_error("mc_blind: a channel table is in force; the rounds run on the BSC: clear it with qldpc_mc_set_channel(mc, NULL)"); return QLDPC_EUNSUPPORTED; }
+    if (mc->dec->engine == QLDPC_ENGINE_EDGES) { qldpc_set_error("mc_blind: the select of the weakest VNs is not built for the edge-parallel engine: create the decoder with engine = FRAMES"); return QLDPC_EUNSUPPORTED; }
+    if (mc->dec->compact_mode != 2) {      /* the engine's own rule, resolved when the decoder was created */
+        qldpc_set_error("mc_blind: the decoder may compact its active frames (compact = %d), after which the posteriors of the frames that converged earlier are gone: "
+                        "create it with compact = 2", mc->dec->cfg.compact);
+        return QLDPC_EUNSUPPORTED;
+    }
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_blind(qldpc_mc *mc, const qldpc_mc_blind_cfg *cfg, qldpc_mc_blind_result *res)
+{
+    if (!mc || !cfg || !res) return QLDPC_EINVAL;
+    memset(res, 0, sizeof(*res));
+    res->next_frame = cfg->first_frame;
+    int rc = mc_blind_args(mc, cfg);
+    if (rc || (rc = mc_blind_reserve(mc, cfg->max_rounds))) return rc;
+    const hipStream_t s = mc->dec->stream;
+    const int R = cfg->max_rounds;
+    const size_t Wn = (size_t)mc->Wn, cap = MC_BLIND_POOL_CAP(mc->batch), words = (size_t)(R + 2) * (MC_BLIND_COUNTERS + 1);
+    mc_u64 *const d_count = mc->d_bctr + (size_t)(R + 2) * MC_BLIND_COUNTERS;
+    const mc_u64 *const h_count = mc->h_bctr + (size_t)(R + 2) * MC_BLIND_COUNTERS;
+    const mc_row row = {mc_threshold(cfg->qber), qldpc_bsc_llr((float)cfg->qber)};
+    HIPCHK(hipMemsetAsync(mc->d_bctr, 0, sizeof(mc_u64) * words, s));
+    memset(mc->h_bctr, 0, sizeof(mc_u64) * words);
+    mc->bstats.assign((size_t)R + 2, qldpc_mc_blind_round_stat());
+
+    uint64_t pool[QLDPC_MC_BLIND_MAX_ROUNDS + 1] = {0}, done = 0, input_left = cfg->max_frames;
+    int level = 0, n = 0;
+    double *const stage[7] = {&res->source_ms, &res->encode_ms, &res->channel_ms, &res->load_ms, &res->decode_ms, &res->select_ms, &res->advance_ms};
+    const auto t_start = std::chrono::steady_clock::now();
+    while (mc_blind_next(R, mc->batch, pool, input_left, &level, &n)) {
+        /* level r >= 1: the last n entries of pool r, a contiguous frame table and a contiguous [n][Wn] array of known rows */
+        const size_t top = level ? (size_t)(level - 1) * cap + (size_t)pool[level] - (size_t)n : 0;
+        const uint32_t *known = level ? mc->d_pknown + top * Wn : nullptr;
+        const mc_slots sl = {level ? mc->d_pframe + top : nullptr, cfg->first_frame + done, nullptr, nullptr, row};
+        HIPCHK(hipEventRecord(mc->ev[0], s));
+        if ((rc = mc_generate_load(mc, sl, n, s, mc->ev, mc->ev[3]))) return rc;
+        if (mc->n_fixed && (rc = mc_erase(mc, mc->d_fixed, mc_range(0), n, n, s))) return rc;      /* the fixed puncture set: one row for all n frames */
+        if (known && (rc = qldpc_load_known_dev(mc->dec, known, mc->d_cw, n))) return rc;          /* Alice's answer: her codeword is on the device */
+        HIPCHK(hipEventRecord(mc->ev[4], s));
+        if ((rc = qldpc_run(mc->dec))) return rc;
+        HIPCHK(hipEventRecord(mc->ev[5], s));
+        if ((rc = mc_fetch(mc))) return rc;
+        const unsigned total = (unsigned)n * (unsigned)mc->Wn;
+        if (level < R) {
+            hipLaunchKernelGGL(mc_blind_cand, dim3(mc_blocks(total)), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_chan_mask, known, (const int *)mc->d_ok, mc->d_bcand,
+                               mc->d_btake, total, (unsigned)mc->Wn);
+            LAUNCHCHK();
+            if ((rc = qldpc_fetch_weakest_dev(mc->dec, mc->d_bcand, mc->d_btake, cfg->ask_bits, mc->d_bweak))) return rc;
+        }
+        HIPCHK(hipEventRecord(mc->ev[6], s));
+        const unsigned waves = (unsigned)std::min(n, MC_MAX_WAVES);
+        hipLaunchKernelGGL(mc_blind_advance, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, mc_decoded_of(mc), (unsigned)n, known, mc->channel_vns,
+                           mc->d_bctr + (size_t)level * MC_BLIND_COUNTERS, level == R ? mc->d_bctr + (size_t)(R + 1) * MC_BLIND_COUNTERS : nullptr, mc->d_bopen,
+                           level ? d_count + level : nullptr, (mc_u64)(pool[level] - (uint64_t)n));
+        LAUNCHCHK();
+        /* the open frames go on to pool level + 1 with what they asked for, or after the last round onto the list of the frames that ended open */
+        const unsigned groups = ((unsigned)n + MC_APPEND_SLOTS - 1u) / MC_APPEND_SLOTS;
+        if (level < R)
+            hipLaunchKernelGGL(mc_blind_advance_append, dim3(groups), dim3(MC_LANES), 0, s, (const int *)mc->d_bopen, (unsigned)n, sl, known, (const uint32_t *)mc->d_bweak,
+                               (unsigned)mc->Wn, mc->d_pframe + (size_t)level * cap, mc->d_pknown + (size_t)level * cap * Wn, (mc_u64)pool[level + 1], (mc_u64)cap,
+                               d_count + level + 1);
+        else
+            hipLaunchKernelGGL(mc_blind_advance_append, dim3(groups), dim3(MC_LANES), 0, s, (const int *)mc->d_bopen, (unsigned)n, sl, known, (const uint32_t *)nullptr,
+                               (unsigned)mc->Wn, mc->d_oframe, mc->d_oknown, h_count[R + 1], (mc_u64)mc->fail_cap, d_count + R + 1);
+        LAUNCHCHK();
+        if ((rc = mc_round_end(mc, mc->h_bctr, mc->d_bctr, words, stage, 7, s))) return rc;
+        res->launches++; res->decodes += (uint64_t)n;
+        if (level == 0) { done += (uint64_t)n; input_left -= (uint64_t)n; }
+        uint64_t fe = 0;
+        for (int r = 0; r <= R + 1; r++) fe += mc->h_bctr[(size_t)r * MC_BLIND_COUNTERS + MC_FRAME_ERRORS];
+        for (int r = 1; r <= R; r++) {
+            pool[r] = h_count[r];
+            if (pool[r] > cap) { qldpc_set_error("mc_blind: pool %d holds %llu entries of %zu", r, (unsigned long long)pool[r], cap); return QLDPC_ESTATE; }
+        }
+        if (cfg->max_frame_errors && fe >= cfg->max_frame_errors) input_left = 0;      /* the input ends here; the pools are flushed, never dropped */
+    }
+    res->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    for (int r = 0; r <= R + 1; r++) {
+        const mc_u64 *c = mc->h_bctr + (size_t)r * MC_BLIND_COUNTERS;
+        qldpc_mc_blind_round_stat *st = &mc->bstats[(size_t)r];
+        mc_counters_out(st, c);
+        st->disclosed = c[MC_DISCLOSED];
+        res->frames += st->frames; res->frame_errors += st->frame_errors; res->undetected += st->undetected; res->disclosed += st->disclosed;
+    }
+    res->open = mc->bstats[(size_t)R + 1].frames;
+    res->next_frame = cfg->first_frame + done;
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_blind_stats(qldpc_mc *mc, qldpc_mc_blind_round_stat *rows, int cap)
+{
+    if (!mc) return QLDPC_EINVAL;
+    return mc_stats_out(mc->bstats, rows, cap);
+}
+
+extern "C" int qldpc_mc_blind_open(qldpc_mc *mc, uint64_t *frames, uint32_t *known_words, int cap)
+{
+    if (!mc || cap < 0 || (cap && !frames)) return QLDPC_EINVAL;
+    if (mc->bstats.empty()) return 0;
+    const size_t Wn = (size_t)mc->Wn;
+    const int listed = (int)std::min<uint64_t>(mc->bstats.back().frames, (uint64_t)mc->fail_cap), n = std::min(listed, cap);
+    if (n == 0) return listed;
+    HIPCHK(hipSetDevice(mc->device));
+    HIPCHK(hipStreamSynchronize(mc->dec->stream));
+    std::vector<uint64_t> all((size_t)listed);
+    HIPCHK(hipMemcpy(all.data(), mc->d_oframe, sizeof(uint64_t) * all.size(), hipMemcpyDeviceToHost));
+    std::vector<int> order((size_t)listed);      /* the list is in the order of the launches */
+    for (int i = 0; i < listed; i++) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return all[(size_t)a] < all[(size_t)b]; });
+    for (int i = 0; i < n; i++) {
+        frames[i] = all[(size_t)order[(size_t)i]];
+        if (known_words) HIPCHK(hipMemcpy(known_words + (size_t)i * Wn, mc->d_oknown + (size_t)order[(size_t)i] * Wn, sizeof(uint32_t) * Wn, hipMemcpyDeviceToHost));
+    }
+    return listed;
 }

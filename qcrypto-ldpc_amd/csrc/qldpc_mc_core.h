@@ -306,6 +306,34 @@ static inline int mc_sweep_deal(int P, int C, int S, uint64_t max_frames, uint64
 }
 
 /*
+ * Blind reconciliation rounds (qldpc_mc_blind): the schedule, a pure function of the pool counts.  A frame that is still open after round r - 1
+ * waits in pool r (1 <= r <= R = max_rounds) as {frame index, known row}; a launch decodes n <= batch frames of ONE level: level 0 = fresh frames,
+ * level r = the last n entries of pool r.  A launch at level r < R appends its open frames to pool r + 1.  In order:
+ *
+ *   1. the DEEPEST level with pool >= batch, `batch` of it
+ *   2. else, while input is left, level 0 with min(batch, input_left)
+ *   3. else the LOWEST non-empty level, all of it (the flush: ragged, and what it opens lands in a deeper pool that is flushed after it)
+ *
+ * Why no pool reaches 2 batch: pool r + 1 grows only by a launch at level r, of at most batch frames, and rules 1 - 3 pick level r only when no
+ * deeper level holds batch or more (rule 1 would have taken the deepest such level; rules 2 and 3 apply when there is none at all).  So pool r + 1
+ * holds at most batch - 1 before that launch and at most 2 batch - 1 after it, which is the capacity MC_BLIND_POOL_CAP.  Every launch either
+ * consumes input or moves frames strictly deeper or out, so the loop ends, with every pool empty.  pool[0] is not read.
+ */
+#define MC_BLIND_MAX_ROUNDS 64                     /* QLDPC_MC_BLIND_MAX_ROUNDS of include/qldpc.h */
+#define MC_BLIND_POOL_CAP(batch) (2 * (size_t)(batch) - 1)
+
+/* returns 0 when nothing is left, else 1 with the level and the frames of the next launch */
+static inline int mc_blind_next(int R, int batch, const uint64_t *pool, uint64_t input_left, int *level, int *n)
+{
+    for (int r = R; r >= 1; r--)
+        if (pool[r] >= (uint64_t)batch) { *level = r; *n = batch; return 1; }
+    if (input_left) { *level = 0; *n = input_left < (uint64_t)batch ? (int)input_left : batch; return 1; }
+    for (int r = 1; r <= R; r++)
+        if (pool[r]) { *level = r; *n = (int)pool[r]; return 1; }
+    return 0;
+}
+
+/*
  * Host side.  The padded class map cls[32 ceil(N / 32)] of a (K, N, info_bits_pos, vn_class): vn_class != NULL is copied (every entry 0 .. 2), else the
  * harness's classes (BS/src/main.cpp:348-354): QLDPC_VN_CHANNEL at info_bits_pos (NULL = 0 .. K-1), QLDPC_VN_PINNED elsewhere.  mask
  * (optional, ceil(N / 32) words) = the packed mask of info_bits_pos.  Returns 0, or -1 for a position outside [0, N), a repeated position or

@@ -3,7 +3,9 @@
  * qldpc_mc_llr_host, qldpc_mc_pattern_host, qldpc_mc_weight_frames_host): the functions of qldpc_mc_core.h that the kernels of qldpc_mc.hip
  * run per lane, here in a loop over frames and words, or over candidates; the table builder of the quantised AWGN channel
  * (qldpc_mc_awgn_table); the deal of one round of the QBER sweep (qldpc_mc_sweep_deal_host), the function qldpc_mc_sweep itself calls per
- * round; and the FER estimate over fixed-weight strata (qldpc_mc_strata_fer_host).  Plain C, no device.
+ * round; the FER estimate over fixed-weight strata (qldpc_mc_strata_fer_host); and the schedule of the blind reconciliation rounds
+ * (qldpc_mc_blind_next_host, the function qldpc_mc_blind itself calls per launch) with the efficiency they end at
+ * (qldpc_mc_blind_efficiency_host).  Plain C, no device.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -255,5 +257,28 @@ int qldpc_mc_strata_fer_host(int n_channel, int n_strata, const int *weights, co
         var += c * c * p * (1.0 - p) / (double)frames[s];
     }
     out[0] = fer; out[1] = below; out[2] = above; out[3] = sqrt(var);
+    return QLDPC_OK;
+}
+
+int qldpc_mc_blind_next_host(int max_rounds, int batch, const uint64_t *pool, uint64_t input_left, int *level, int *n)
+{
+    if (max_rounds < 0 || max_rounds > MC_BLIND_MAX_ROUNDS || batch < 1) {
+        qldpc_set_error("mc_blind_next_host: max_rounds=%d (0 .. %d), batch=%d (at least 1)", max_rounds, MC_BLIND_MAX_ROUNDS, batch);
+        return QLDPC_ESIZE;
+    }
+    if (!pool || !level || !n) return QLDPC_EINVAL;
+    return mc_blind_next(max_rounds, batch, pool, input_left, level, n);
+}
+
+int qldpc_mc_blind_efficiency_host(int n_channel, int n_disclosed_parity, uint64_t frames, uint64_t disclosed, double qber, double *f)
+{
+    if (n_channel < 1 || n_disclosed_parity < 0 || frames == 0 || !(qber > 0.0 && qber < 0.5)) {
+        qldpc_set_error("mc_blind_efficiency_host: n_channel=%d (at least 1), n_disclosed_parity=%d (not negative), frames=%llu (at least 1), qber=%g (inside (0, 0.5))",
+                        n_channel, n_disclosed_parity, (unsigned long long)frames, qber);
+        return QLDPC_ESIZE;
+    }
+    if (!f) return QLDPC_EINVAL;
+    const double h2 = -qber * log2(qber) - (1.0 - qber) * log2(1.0 - qber);
+    *f = ((double)n_disclosed_parity + (double)disclosed / (double)frames) / ((double)n_channel * h2);
     return QLDPC_OK;
 }

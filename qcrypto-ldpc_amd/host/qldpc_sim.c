@@ -43,6 +43,12 @@
  *                      column, -E as the stop rule of each row; then one `# strata ber` line per QBER of the -s table with the four numbers of
  *                      qldpc_mc_strata_fer_host: FER over the simulated weights, the binomial mass below and above them, the standard error;
  *                      -A, -X and -W do not apply)]
+ *                  [-B ask:rounds (with -D: blind reconciliation rounds, ONE qldpc_mc_blind per row of -s: a frame whose decode ends with a non-zero syndrome
+ *                      asks for its `ask` weakest unknown key VNs, gets Alice's bits there and is decoded again, up to `rounds` times; only the frames
+ *                      still open are decoded again, pooled per round.  Per BER one row per round (EP = the round in which those frames closed, `open`
+ *                      = still open after the last round) with the key bits those frames asked for in a last column ASKED, then a `# blind` line with
+ *                      the sums, the decodes per frame and the efficiency f = (N - K + asked / frames) / (K h2(ber)); -E as the stop rule of the input;
+ *                      the decoder is created with compact = 2; -A, -X, -W and -w do not apply)]
  *                  [-c scale (with -Q 8: quantiser steps per LLR unit, default 8; 1 for LLRs that are integers already, as -A gives them)]
  */
 #include <math.h>
@@ -88,6 +94,7 @@ static int awgn = 0, awgn_maxq = 31, awgn_punct = 0, zero_source = 0, sweep = 0;
 static double ebno_db = 0.0, awgn_rmax = 3.0, quant_scale = 0.0;
 static int strata = 0, w_lo = 0, w_hi = 0, w_step = 1;      /* -w */
 static double design_qber = 0.0;
+static int blind = 0, ask_bits = 0, max_rounds = 0;      /* -B */
 static double parity_ber = 0.0;      /* > 0: the disclosed parity bits are themselves wrong with this probability (main.cpp (test effect of dirty parities)) */
 static double target_eff = 0.0;      /* > 0: puncture parity bits up to min_cr(ber, f), as BS/src/main.cpp:235-333 does */
 static const char *alist = NULL, *qc = NULL, *rule_name = "NMS", *g_method = NULL, *pattern_out = NULL;
@@ -136,7 +143,7 @@ static int write_pattern(double ber, int n_punct, const int *vn, long long fe)
 static int parse(int argc, char **argv)
 {
     int opt;
-    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:u:c:w:DRWlvnz")) != -1) {
+    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:u:c:w:B:DRWlvnz")) != -1) {
         switch (opt) {
         case 'N': N = atoi(optarg); break;
         case 'K': K = atoi(optarg); break;
@@ -163,6 +170,7 @@ static int parse(int argc, char **argv)
         case 'z': zero_source = 1; break;
         case 'W': sweep = 1; break;
         case 'w': { const int got = sscanf(optarg, "%d:%d:%d:%lf", &w_lo, &w_hi, &w_step, &design_qber); if (got != 3 && got != 4) return usage("-w lo:hi:step[:design_qber]"); strata = 1; break; }
+        case 'B': if (sscanf(optarg, "%d:%d", &ask_bits, &max_rounds) != 2) return usage("-B ask:rounds"); blind = 1; break;
         case 'c': quant_scale = atof(optarg); break;
         case 'o': pattern_out = optarg; break;
         case 'G': g_method = optarg; break;      /* p.G_method (VAR/main.cpp (alist-v1.0.1):135): IDENTITY | LU_DEC; QC = Encoder_LDPC_from_QC ((qc):145) */
@@ -181,6 +189,8 @@ static int parse(int argc, char **argv)
     if (strata && !on_device) return usage("qldpc_sim: -w runs the error strata on the device and needs -D");
     if (strata && (search_x || awgn || sweep)) return usage("qldpc_sim: -w runs fixed error weights on the BSC's words and runs neither with -X, -A nor -W");
     if (strata && (w_step < 1 || w_lo < 0 || w_hi < w_lo)) return usage("qldpc_sim: -w lo:hi:step with 0 <= lo <= hi and step >= 1");
+    if (blind && !on_device) return usage("qldpc_sim: -B runs the blind reconciliation rounds on the device and needs -D");
+    if (blind && (search_x || awgn || sweep || strata)) return usage("qldpc_sim: -B runs on the BSC rows of -s and runs neither with -X, -A, -W nor -w");
     if (on_device && ((target_eff > 0.0 && !sweep) || search)) return usage("qldpc_sim: -e and -R draw a puncture pattern per batch on the host and do not run with -D");
     if (max_fe && !on_device) return usage("qldpc_sim: -E needs -D");
     if (search_x && !on_device) return usage("qldpc_sim: -X is the pattern search on the device and needs -D");
@@ -212,6 +222,7 @@ static int setup(void)
     if (msg_bits != 32 && msg_bits != 16 && msg_bits != 8) return usage("-Q 32 | 16 | 8");
     cfg.msg_dtype = msg_bits == 16 ? 1 : (msg_bits == 8 ? 2 : 0);      /* 16: binary16 message storage; 8: fixed-point min-sum */
     cfg.quant_scale = (float)quant_scale;
+    if (blind) cfg.compact = 2;      /* the select of the weakest VNs needs every frame's posteriors: no active-frame compaction */
     if ((rc = qldpc_decoder_create(H, K, pos, &cfg, &dec))) return die("decoder", rc);
 
     printf("# * libqldpc %d on HIP device 0; Decoder_LDPC_BP_%s_Update_rule_%s (param %g), n_ite %d, syndrome %d, %d-bit messages\n", qldpc_version(),
@@ -367,6 +378,41 @@ static int mode_search(void)
     return 0;
 }
 
+/* -B: every row of -s one qldpc_mc_blind, a row per round */
+static int mode_blind(void)
+{
+    int rc;
+    if (max_rounds < 0 || max_rounds > QLDPC_MC_BLIND_MAX_ROUNDS) { fprintf(stderr, "qldpc_sim: -B rounds=%d outside 0 .. %d\n", max_rounds, QLDPC_MC_BLIND_MAX_ROUNDS); return 2; }
+    qldpc_mc_blind_round_stat *rows = (qldpc_mc_blind_round_stat *)malloc(sizeof(*rows) * (size_t)(max_rounds + 2));
+    if (!rows) return die("mc_blind", QLDPC_ENOMEM);
+    FOR_EACH_BER(ber) {
+        qldpc_mc_blind_cfg bcfg;
+        memset(&bcfg, 0, sizeof(bcfg));
+        bcfg.qber = ber; bcfg.ask_bits = ask_bits; bcfg.max_rounds = max_rounds; bcfg.max_frames = MAX_FRAMES; bcfg.max_frame_errors = max_fe;
+        qldpc_mc_blind_result b;
+        if ((rc = qldpc_mc_blind(mc, &bcfg, &b))) return die("mc_blind", rc);
+        if ((rc = qldpc_mc_blind_stats(mc, rows, max_rounds + 2)) < 0) return die("mc_blind_stats", rc);
+        printf("# ber %.4f: blind rounds, %d bits asked per round, at most %d rounds; EP = the round in which the frames closed; last column = key bits asked\n", ber,
+               ask_bits, max_rounds);
+        for (int r = 0; r <= max_rounds + 1; r++) {      /* SIM_THR: the call's decode time is shared by the rows, as under -W */
+            char ep[64];
+            if (r <= max_rounds) snprintf(ep, sizeof(ep), "%8d", r); else snprintf(ep, sizeof(ep), "%8s", "open");
+            const double fra = rows[r].frames ? (double)rows[r].frames : 1.0;
+            printf("  %s | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f | %8llu\n", ep, (unsigned long long)rows[r].frames, (unsigned long long)rows[r].bit_errors,
+                   (unsigned long long)rows[r].frame_errors, (double)rows[r].bit_errors / (fra * K), (double)rows[r].frame_errors / fra,
+                   (double)b.frames * K / (b.decode_ms * 1e-3) / 1e6, (unsigned long long)rows[r].disclosed);
+        }
+        double f = 0.0;
+        if (b.frames && (rc = qldpc_mc_blind_efficiency_host(K, N - K, b.frames, b.disclosed, ber, &f))) return die("mc_blind_efficiency_host", rc);
+        printf("# blind: %llu frames, %llu open, %llu key bits disclosed, %llu decodes in %llu launches = %.4f per frame; FER %.3e; f = %.4f\n",
+               (unsigned long long)b.frames, (unsigned long long)b.open, (unsigned long long)b.disclosed, (unsigned long long)b.decodes, (unsigned long long)b.launches,
+               b.frames ? (double)b.decodes / (double)b.frames : 0.0, b.frames ? (double)b.frame_errors / (double)b.frames : 0.0, f);
+        fflush(stdout);
+    }
+    free(rows);
+    return 0;
+}
+
 /* -D alone: the same table, every row one qldpc_mc_run */
 static int mode_rows(void)
 {
@@ -444,7 +490,7 @@ int main(int argc, char **argv)
 {
     int rc = parse(argc, argv);
     if (!rc) rc = setup();
-    if (!rc) rc = !on_device ? run_host() : awgn ? mode_awgn() : strata ? mode_strata() : sweep ? mode_sweep() : search_eff > 0.0 ? mode_search() : mode_rows();
+    if (!rc) rc = !on_device ? run_host() : awgn ? mode_awgn() : strata ? mode_strata() : blind ? mode_blind() : sweep ? mode_sweep() : search_eff > 0.0 ? mode_search() : mode_rows();
     if (rc) return rc;
     qldpc_mc_free(mc);
     qldpc_decoder_free(dec); qldpc_encoder_free(enc); qldpc_code_free(H);
