@@ -623,6 +623,50 @@ int    qldpc_toeplitz_blocks_dev(qldpc_toeplitz_ctx *tz, int n, const uint32_t *
    (0 = the kernel's tile; every tile size gives the same words) */
 int    qldpc_toeplitz_host(const uint32_t *key_words, int key_bits, const uint32_t *seed_words, int out_bits, int tile_words, uint32_t *out_words);
 
+/*
+ * The sub-quadratic method.  The product above is a correlation: over the integers c_i = SUM_j x_j t_(i+j) <= n <= 2^24 and y_i = c_i mod 2,
+ * so a number-theoretic transform over the prime p = 15 * 2^27 + 1 = 2 013 265 921 > 2^24 computes it exactly: three transforms of length
+ * L = qldpc_toeplitz_ntt_length(n, m) in place of n m bit-products, and the SAME WORDS as the direct method, bit for bit
+ * (csrc/qldpc_toeplitz_ntt.hip, csrc/qldpc_toeplitz_ntt_core.h).  A context is built for one method by qldpc_toeplitz_create_cfg and
+ * is then used through qldpc_toeplitz_blocks / _blocks_dev with the checks, refusals and stream semantics stated above; with
+ * QLDPC_TOEPLITZ_NTT the blocks of a call are grouped by their L, blocks of equal L share launches, and a seed the call shares (all
+ * seed_words pointers equal, or seed_stride == 0) is transformed once per distinct L from the first min(L, 32 x the longest
+ * qldpc_toeplitz_seed_words of the call) bits of its row.  The words do not depend on the grouping, on rounds or on pass_log2.
+ *
+ * There is no automatic choice of method: where the two cross has not been decided in the library (tools/toeplitz_cost.py measures both in
+ * one process; README).  qldpc_toeplitz_create builds the direct method.
+ */
+#define QLDPC_TOEPLITZ_DIRECT 0
+#define QLDPC_TOEPLITZ_NTT 1
+#define QLDPC_TOEPLITZ_PASS_LOG2 9         /* B of the production pass kernels: a transform of length 2^k runs as ceil(k / B) passes */
+#define QLDPC_TOEPLITZ_PASS_LOG2_SMALL 5   /* B of the small instance, which reaches every pass structure at test sizes */
+typedef struct {
+    int device, max_blocks, max_key_bits, max_out_bits;      /* as qldpc_toeplitz_create takes them */
+    int method;                /* QLDPC_TOEPLITZ_DIRECT / QLDPC_TOEPLITZ_NTT; anything else QLDPC_EINVAL */
+    int pass_log2;             /* NTT: 0 = the production instance, QLDPC_TOEPLITZ_PASS_LOG2_SMALL = the small one; anything else QLDPC_EINVAL */
+    size_t work_bytes;         /* NTT: the work area, two arrays of L 32-bit residues per block in flight (key and seed spectrum).  0 = room for all
+                                  max_blocks at L = qldpc_toeplitz_ntt_length(max_key_bits, max_out_bits) where that is <= 1 GiB, else as many
+                                  blocks as fit in 1 GiB, and never less than one; a value below one block (8 L bytes) is QLDPC_ESIZE.  A call
+                                  with more blocks of one L than fit runs them in rounds */
+} qldpc_toeplitz_cfg;
+/* max_blocks 64, 2^16 key and output bits, the direct method, device 0 */
+void   qldpc_toeplitz_cfg_default(qldpc_toeplitz_cfg *cfg);
+/* allocates everything, the work area and the twiddle tables included (qldpc_toeplitz_device_bytes counts them); no call afterwards allocates.
+   qldpc_toeplitz_create is this with the defaults and its four arguments */
+int    qldpc_toeplitz_create_cfg(const qldpc_toeplitz_cfg *cfg, qldpc_toeplitz_ctx **out);
+/* the transform length of a block: the smallest power of two >= key_bits + out_bits - 1, and at least 32 (an output word is stored whole);
+   0 where qldpc_toeplitz_seed_words gives 0, and for sizes over 2^24 */
+size_t qldpc_toeplitz_ntt_length(int key_bits, int out_bits);
+/* the last call of the context: out[0] kernel launches, [1] forward transforms, [2] inverse transforms, [3] rounds, [4] distinct L,
+   [5] the largest L, [6..7] 0.  A direct context reports one launch and zeros */
+int    qldpc_toeplitz_stats(const qldpc_toeplitz_ctx *tz, uint64_t out[8]);
+/* host mirror of the NTT method, for tests: no device; the core header's functions over the same tiles and passes as the kernels, with
+   B = pass_log2 (0 = QLDPC_TOEPLITZ_PASS_LOG2; every value 1 .. 25 gives the same words; anything else QLDPC_EINVAL) */
+int    qldpc_toeplitz_ntt_host(const uint32_t *key_words, int key_bits, const uint32_t *seed_words, int out_bits, int pass_log2, uint32_t *out_words);
+/* the field arithmetic, for tests: a b mod p, and a primitive 2^log2_len-th root of unity (log2_len 0 .. 25, else 0) */
+uint32_t qldpc_toeplitz_ntt_mul_host(uint32_t a, uint32_t b);
+uint32_t qldpc_toeplitz_ntt_root_host(int log2_len);
+
 /* ------------------------------------------------------------------ Monte-Carlo FER loop ---- */
 /*
  * The loop of the reference harness -- source -> encoder -> BSC -> decoder -> monitor (BS/src/main.cpp:335-393, Monitor_BFER's max_fe stop

@@ -820,6 +820,23 @@ _sig("qldpc_toeplitz_blocks_dev", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _ip, 
 _sig("qldpc_toeplitz_host", C.c_int, [_up, C.c_int, _up, C.c_int, C.c_int, _up])
 
 
+class _ToeplitzCfg(C.Structure):
+    _fields_ = [("device", C.c_int), ("max_blocks", C.c_int), ("max_key_bits", C.c_int), ("max_out_bits", C.c_int),
+                ("method", C.c_int), ("pass_log2", C.c_int), ("work_bytes", C.c_size_t)]
+
+
+_sig("qldpc_toeplitz_cfg_default", None, [C.POINTER(_ToeplitzCfg)])
+_sig("qldpc_toeplitz_create_cfg", C.c_int, [C.POINTER(_ToeplitzCfg), C.POINTER(_vp)])
+_sig("qldpc_toeplitz_ntt_length", C.c_size_t, [C.c_int, C.c_int])
+_sig("qldpc_toeplitz_stats", C.c_int, [_vp, C.POINTER(C.c_uint64)])
+_sig("qldpc_toeplitz_ntt_host", C.c_int, [_up, C.c_int, _up, C.c_int, C.c_int, _up])
+_sig("qldpc_toeplitz_ntt_mul_host", C.c_uint32, [C.c_uint32, C.c_uint32])
+_sig("qldpc_toeplitz_ntt_root_host", C.c_uint32, [C.c_int])
+TOEPLITZ_METHODS = {"direct": 0, "ntt": 1}
+TOEPLITZ_NTT_PRIME = 2013265921
+TOEPLITZ_PASS_LOG2, TOEPLITZ_PASS_LOG2_SMALL = 9, 5
+
+
 def toeplitz_seed_words(key_bits, out_bits):
     """words of a seed of key_bits + out_bits - 1 bits; 0 for key_bits <= 0 or out_bits <= 0"""
     return int(_L.qldpc_toeplitz_seed_words(int(key_bits), int(out_bits)))
@@ -839,16 +856,67 @@ def toeplitz_host(key_words, key_bits, seed_words, out_bits, tile_words=0):
     return out
 
 
+def toeplitz_ntt_length(key_bits, out_bits):
+    """the transform length L of the NTT method for a block: the smallest power of two >= key_bits + out_bits - 1, at least 32; 0 where
+    toeplitz_seed_words gives 0"""
+    return int(_L.qldpc_toeplitz_ntt_length(int(key_bits), int(out_bits)))
+
+
+def toeplitz_ntt_mul(a, b):
+    """a b mod TOEPLITZ_NTT_PRIME with the core header's Montgomery multiply"""
+    return int(_L.qldpc_toeplitz_ntt_mul_host(int(a), int(b)))
+
+
+def toeplitz_ntt_root(log2_len):
+    """a primitive 2^log2_len-th root of unity mod TOEPLITZ_NTT_PRIME, log2_len 0 .. 25"""
+    if not 0 <= int(log2_len) <= 25:
+        raise QldpcError(-6, "toeplitz_ntt_root: log2_len = %d" % log2_len)
+    return int(_L.qldpc_toeplitz_ntt_root_host(int(log2_len)))
+
+
+def toeplitz_ntt_host(key_words, key_bits, seed_words, out_bits, pass_log2=0):
+    """toeplitz_host by the NTT method on the host: the pass kernels' own functions over the same tiles, the transform in passes of
+    pass_log2 index bits (0: the production kernels' 9; every value 1 .. 25 gives the same words)"""
+    kw = np.ascontiguousarray(key_words, dtype=np.uint32)
+    sw = np.ascontiguousarray(seed_words, dtype=np.uint32)
+    key_bits, out_bits = int(key_bits), int(out_bits)
+    if key_bits <= 0 or out_bits < 0 or kw.size < (key_bits + 31) // 32 or sw.size < toeplitz_seed_words(key_bits, out_bits):
+        raise QldpcError(-6, "toeplitz_ntt_host: %d key words, key_bits = %d, %d seed words, out_bits = %d" % (kw.size, key_bits, sw.size, out_bits))
+    out = np.zeros((out_bits + 31) // 32, np.uint32)
+    _chk(_L.qldpc_toeplitz_ntt_host(kw.ctypes.data_as(_up), key_bits, sw.ctypes.data_as(_up), out_bits, int(pass_log2), out.ctypes.data_as(_up)),
+         "toeplitz_ntt_host")
+    return out
+
+
 class Toeplitz:
     """Toeplitz hashing for batches of blocks of any mix of lengths, one launch per call (qldpc_toeplitz_blocks*).  The seeds are the
     caller's: key_bits + out_bits - 1 uniformly random bits per block, which may be public and shared by the blocks of a call.
-    Everything is allocated here; blocks() / blocks_dev() allocate nothing on the device."""
+    Everything is allocated here; blocks() / blocks_dev() allocate nothing on the device.  method "direct" is the n x m product;
+    "ntt" gives the same words by three number-theoretic transforms per block, for long keys (pass_log2: 0 = the production pass kernels,
+    TOEPLITZ_PASS_LOG2_SMALL = the small instance; work_bytes: the work area, 0 = the library's default).  Nothing picks the method for
+    the caller."""
 
-    def __init__(self, max_blocks=64, max_key_bits=1 << 16, max_out_bits=1 << 16, device=0):
+    def __init__(self, max_blocks=64, max_key_bits=1 << 16, max_out_bits=1 << 16, device=0, method="direct", pass_log2=0, work_bytes=0):
+        if method not in TOEPLITZ_METHODS:
+            raise QldpcError(-1, "Toeplitz: method %r (one of %s)" % (method, sorted(TOEPLITZ_METHODS)))
+        if int(work_bytes) < 0:
+            raise QldpcError(-6, "Toeplitz: work_bytes = %d" % work_bytes)
+        cfg = _ToeplitzCfg()
+        _L.qldpc_toeplitz_cfg_default(C.byref(cfg))
+        cfg.device, cfg.max_blocks, cfg.max_key_bits, cfg.max_out_bits = int(device), int(max_blocks), int(max_key_bits), int(max_out_bits)
+        cfg.method, cfg.pass_log2, cfg.work_bytes = TOEPLITZ_METHODS[method], int(pass_log2), int(work_bytes)
         h = _vp()
-        _chk(_L.qldpc_toeplitz_create(int(device), int(max_blocks), int(max_key_bits), int(max_out_bits), C.byref(h)), "Toeplitz")
+        _chk(_L.qldpc_toeplitz_create_cfg(C.byref(cfg), C.byref(h)), "Toeplitz")
         self._h = h
         self.device, self.max_blocks, self.max_key_bits, self.max_out_bits = int(device), int(max_blocks), int(max_key_bits), int(max_out_bits)
+        self.method = method
+
+    def stats(self):
+        """the last call: kernel launches, forward and inverse transforms, rounds, distinct transform lengths and the largest one (a
+        direct context: one launch and zeros)"""
+        v = (C.c_uint64 * 8)()
+        _chk(_L.qldpc_toeplitz_stats(self._h, v), "Toeplitz.stats")
+        return dict(launches=int(v[0]), forward=int(v[1]), inverse=int(v[2]), rounds=int(v[3]), lengths=int(v[4]), largest_length=int(v[5]))
 
     @property
     def device_bytes(self):

@@ -27,16 +27,12 @@
 #include "qldpc_graph.h"
 #include "qldpc_hip.h"
 #include "qldpc_toeplitz_core.h"
+#include "qldpc_toeplitz_int.h"
 
 #define TZ_MAX_BLOCKS 65535        /* blocks are the y dimension of the grid */
 #define TZ_LANES 256
 #define TZ_TILE 2048               /* key words per staged seed tile; a multiple of 8 */
 #define TZ_SPAN 32                 /* seed words past the tile that the 8 halves of a workgroup reach (28 + 1, and 3 of padding in front) */
-
-struct tz_desc {                   /* one row per block, written by the host */
-    uint32_t key_words, tail_mask, out_bits, seed_words;
-    uint64_t key_off, seed_off, out_off;      /* in words from the key / seed / output base of the call */
-};
 
 __global__ __launch_bounds__(TZ_LANES) void tz_hash(const tz_desc *__restrict__ descs, const uint32_t *__restrict__ keys,
                                                     const uint32_t *__restrict__ seeds, uint32_t *__restrict__ outs)
@@ -122,16 +118,6 @@ extern "C" int qldpc_toeplitz_host(const uint32_t *key_words, int key_bits, cons
 
 extern "C" size_t qldpc_toeplitz_seed_words(int key_bits, int out_bits) { return tz_seed_words(key_bits, out_bits); }
 
-struct qldpc_toeplitz_ctx {
-    int device, max_blocks, max_key_bits, max_out_bits;
-    size_t key_cap, seed_cap, out_cap;    /* words of the packed key / seed / output areas of the host form */
-    size_t in_words;                      /* descriptor rows, packed keys and packed seeds of a full call: one upload per host call */
-    uint32_t *h_in, *d_in, *h_out, *d_out;
-    hipEvent_t done;                      /* after the last call's launch: the staging is reused only once that call has run */
-    hipStream_t stream;                   /* of the host form */
-    size_t dev_bytes;
-};
-
 static size_t tz_desc_words(int n) { return (size_t)n * (sizeof(tz_desc) / 4); }
 
 extern "C" void qldpc_toeplitz_free(qldpc_toeplitz_ctx *tz)
@@ -140,6 +126,7 @@ extern "C" void qldpc_toeplitz_free(qldpc_toeplitz_ctx *tz)
     (void)hipSetDevice(tz->device);
     if (tz->done) { (void)hipEventSynchronize(tz->done); (void)hipEventDestroy(tz->done); }
     if (tz->stream) (void)hipStreamDestroy(tz->stream);
+    tzn_free(tz);
     if (tz->h_in) (void)hipHostFree(tz->h_in);
     if (tz->h_out) (void)hipHostFree(tz->h_out);
     if (tz->d_in) (void)hipFree(tz->d_in);
@@ -167,10 +154,25 @@ static int tz_create(qldpc_toeplitz_ctx *tz)
     return QLDPC_OK;
 }
 
-extern "C" int qldpc_toeplitz_create(int device, int max_blocks, int max_key_bits, int max_out_bits, qldpc_toeplitz_ctx **out)
+extern "C" void qldpc_toeplitz_cfg_default(qldpc_toeplitz_cfg *cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof(*cfg));
+    cfg->max_blocks = 64; cfg->max_key_bits = 1 << 16; cfg->max_out_bits = 1 << 16;
+    cfg->method = QLDPC_TOEPLITZ_DIRECT;
+}
+
+extern "C" int qldpc_toeplitz_create_cfg(const qldpc_toeplitz_cfg *cfg, qldpc_toeplitz_ctx **out)
 {
     if (!out) return QLDPC_EINVAL;
     *out = nullptr;
+    if (!cfg) return QLDPC_EINVAL;
+    const int device = cfg->device, max_blocks = cfg->max_blocks, max_key_bits = cfg->max_key_bits, max_out_bits = cfg->max_out_bits;
+    if (cfg->method != QLDPC_TOEPLITZ_DIRECT && cfg->method != QLDPC_TOEPLITZ_NTT) { qldpc_set_error("toeplitz_create_cfg: method=%d", cfg->method); return QLDPC_EINVAL; }
+    if (cfg->pass_log2 != 0 && cfg->pass_log2 != QLDPC_TOEPLITZ_PASS_LOG2_SMALL) {
+        qldpc_set_error("toeplitz_create_cfg: pass_log2=%d (0 or %d)", cfg->pass_log2, QLDPC_TOEPLITZ_PASS_LOG2_SMALL);
+        return QLDPC_EINVAL;
+    }
     if (max_blocks > TZ_MAX_BLOCKS) { qldpc_set_error("toeplitz_create: max_blocks=%d (up to %d)", max_blocks, TZ_MAX_BLOCKS); return QLDPC_ESIZE; }
     if (max_blocks < 1 || max_key_bits < 1 || max_out_bits < 0 || max_key_bits > TZ_MAX_BITS || max_out_bits > TZ_MAX_BITS) {
         qldpc_set_error("toeplitz_create: max_blocks=%d max_key_bits=%d max_out_bits=%d (bits up to %d)", max_blocks, max_key_bits, max_out_bits, TZ_MAX_BITS);
@@ -187,9 +189,26 @@ extern "C" int qldpc_toeplitz_create(int device, int max_blocks, int max_key_bit
     qldpc_toeplitz_ctx *tz = new (std::nothrow) qldpc_toeplitz_ctx();
     if (!tz) return QLDPC_ENOMEM;
     tz->device = device; tz->max_blocks = max_blocks; tz->max_key_bits = max_key_bits; tz->max_out_bits = max_out_bits;
-    const int rc = tz_create(tz);
+    tz->method = cfg->method;
+    int rc = tz_create(tz);
+    if (!rc && tz->method == QLDPC_TOEPLITZ_NTT) rc = tzn_create(tz, cfg->pass_log2, cfg->work_bytes);
     if (rc) { qldpc_toeplitz_free(tz); return rc; }
     *out = tz;
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_toeplitz_create(int device, int max_blocks, int max_key_bits, int max_out_bits, qldpc_toeplitz_ctx **out)
+{
+    qldpc_toeplitz_cfg cfg;
+    qldpc_toeplitz_cfg_default(&cfg);
+    cfg.device = device; cfg.max_blocks = max_blocks; cfg.max_key_bits = max_key_bits; cfg.max_out_bits = max_out_bits;
+    return qldpc_toeplitz_create_cfg(&cfg, out);
+}
+
+extern "C" int qldpc_toeplitz_stats(const qldpc_toeplitz_ctx *tz, uint64_t out[8])
+{
+    if (!tz || !out) return QLDPC_EINVAL;
+    memcpy(out, tz->stats, sizeof(tz->stats));
     return QLDPC_OK;
 }
 
@@ -237,8 +256,12 @@ static void tz_fill(qldpc_toeplitz_ctx *tz, int n, const int *key_bits, const in
     *grid_x = gx; *key_words = koff; *seed_words = one_seed ? smax : soff; *out_words = ooff;
 }
 
-static int tz_launch(qldpc_toeplitz_ctx *tz, int n, unsigned grid_x, const uint32_t *d_keys, const uint32_t *d_seeds, uint32_t *d_out, hipStream_t s)
+/* the blocks of a call, laid out by tz_fill, by the context's method; shared: every block reads one seed row */
+static int tz_launch(qldpc_toeplitz_ctx *tz, int n, unsigned grid_x, const int *key_bits, int shared, const uint32_t *d_keys, const uint32_t *d_seeds, uint32_t *d_out, hipStream_t s)
 {
+    if (tz->method == QLDPC_TOEPLITZ_NTT) return tzn_blocks(tz, n, (const tz_desc *)tz->h_in, key_bits, shared, d_keys, d_seeds, d_out, s);
+    memset(tz->stats, 0, sizeof(tz->stats));
+    tz->stats[0] = 1;
     hipLaunchKernelGGL(tz_hash, dim3(grid_x, (unsigned)n), dim3(TZ_LANES), 0, s, (const tz_desc *)tz->d_in, d_keys, d_seeds, d_out);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { qldpc_set_error("toeplitz_blocks launch: %s", hipGetErrorString(e)); return QLDPC_EHIP; }
@@ -272,7 +295,7 @@ extern "C" int qldpc_toeplitz_blocks(qldpc_toeplitz_ctx *tz, int n, const uint32
     if (one_seed) memcpy(h_seeds, seed_words[0], 4 * sw);        /* the caller's one row covers the longest key_bits + out_bits - 1 of the call */
     else for (int i = 0; i < n; i++) memcpy(h_seeds + descs[i].seed_off, seed_words[i], 4 * (size_t)descs[i].seed_words);
     HIPCHK(hipMemcpyAsync(tz->d_in, tz->h_in, 4 * (head + kw + sw), hipMemcpyHostToDevice, tz->stream));
-    rc = tz_launch(tz, n, grid_x, tz->d_in + head, tz->d_in + head + kw, tz->d_out, tz->stream);
+    rc = tz_launch(tz, n, grid_x, key_bits, one_seed, tz->d_in + head, tz->d_in + head + kw, tz->d_out, tz->stream);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(tz->h_out, tz->d_out, 4 * ow, hipMemcpyDeviceToHost, tz->stream));
     HIPCHK(hipEventRecord(tz->done, tz->stream));
@@ -301,8 +324,8 @@ extern "C" int qldpc_toeplitz_blocks_dev(qldpc_toeplitz_ctx *tz, int n, const ui
     tz_fill(tz, n, key_bits, out_bits, key_stride, seed_stride, out_stride, 0, 0, &grid_x, &kw, &sw, &ow);
     if (grid_x == 0) return QLDPC_OK;
     const hipStream_t s = (hipStream_t)hip_stream;
-    HIPCHK(hipMemcpyAsync(tz->d_in, tz->h_in, 4 * tz_desc_words(n), hipMemcpyHostToDevice, s));
-    rc = tz_launch(tz, n, grid_x, d_keys, d_seeds, d_out, s);
+    if (tz->method == QLDPC_TOEPLITZ_DIRECT) HIPCHK(hipMemcpyAsync(tz->d_in, tz->h_in, 4 * tz_desc_words(n), hipMemcpyHostToDevice, s));
+    rc = tz_launch(tz, n, grid_x, key_bits, seed_stride == 0, d_keys, d_seeds, d_out, s);
     if (rc) return rc;
     HIPCHK(hipEventRecord(tz->done, s));
     return QLDPC_OK;

@@ -15,6 +15,9 @@
  *                          key_bits - leaked bits, one seed of 2 key_bits - 1 bits shared by the call.  The seed comes from this tool's own
  *                          deterministic generator: a MEASUREMENT seed, not a random one, and nothing to deploy.  Adds tpa_ms_mean,
  *                          tpa_ms_best, tdistill_Mbit_s_mean; may be given together with -H)]
+ *                     [-N (the -U stage on an NTT context, qldpc_toeplitz_create_cfg with QLDPC_TOEPLITZ_NTT; implies -U.  After every timed call
+ *                          the same blocks go through a direct context, untimed, and the words are compared: adds tpa_method,
+ *                          tpa_equals_direct (1 when every word of every call was equal) and tpa_checksum (FNV-1a of the last call's words))]
  *                     (defaults: 512 epochs x 52 429 bits, max_blocks 512, PEG depth 2 = the library's default)
  * prints one JSON object on stdout.
  */
@@ -62,10 +65,10 @@ static void *part_main(void *arg)
 
 int main(int argc, char **argv)
 {
-    int epochs = 512, key_bits = 52429, batch = 512, reps = 3, layered = -1, profile = 0, peg = 2, opt, a_lanes = 0, b_lanes = 0, verbose = 0, split = 1, gap_profile = 0, hash = 0, toeplitz = 0;
+    int epochs = 512, key_bits = 52429, batch = 512, reps = 3, layered = -1, profile = 0, peg = 2, opt, a_lanes = 0, b_lanes = 0, verbose = 0, split = 1, gap_profile = 0, hash = 0, toeplitz = 0, ntt = 0;
     uint64_t seed = 42;
     double qmin = 0.005, qmax = 0.06, gap = 0.0;
-    while ((opt = getopt(argc, argv, "e:k:b:S:r:q:lfpP:g:A:B:vT:G:HU")) != -1) {
+    while ((opt = getopt(argc, argv, "e:k:b:S:r:q:lfpP:g:A:B:vT:G:HUN")) != -1) {
         switch (opt) {
         case 'e': epochs = atoi(optarg); break;
         case 'k': key_bits = atoi(optarg); break;
@@ -84,6 +87,7 @@ int main(int argc, char **argv)
         case 'G': gap_profile = atoi(optarg); break;      /* qldpc_recon_cfg.gap_profile */
         case 'H': hash = 1; break;
         case 'U': toeplitz = 1; break;
+        case 'N': toeplitz = 1; ntt = 1; break;
         case 'T': split = atoi(optarg); break;      /* experiment: T sessions on T host threads, each decoding every T-th epoch */
         default: fprintf(stderr, "usage: see the head of qldpc_stream.c\n"); return 2;
         }
@@ -210,13 +214,24 @@ int main(int argc, char **argv)
         if (!pa_keys || !pa_out || !pa_seed || !pa_wb || !pa_fb || !pa_buf) return 1;
     }
     /* -U: the same stage with the Toeplitz hash, one measurement seed shared by the blocks of the call */
-    qldpc_toeplitz_ctx *tz = NULL;
+    qldpc_toeplitz_ctx *tz = NULL, *tz_direct = NULL;
+    uint32_t **tz_out2 = NULL, *tz_buf2 = NULL;
+    int tz_equal = 1;
+    uint64_t tz_checksum = 0;
     const uint32_t **tz_keys = NULL, **tz_seeds = NULL;
     uint32_t **tz_out = NULL, *tz_seed = NULL, *tz_buf = NULL;
     int *tz_kb = NULL, *tz_ob = NULL;
     double tz_best = 1e30, tz_sum = 0.0, tz_final_sum = 0.0;
     if (toeplitz) {
-        if ((rc = qldpc_toeplitz_create(cfg.device, epochs, key_bits, key_bits, &tz))) return die("toeplitz_create", rc);
+        if (ntt) {
+            qldpc_toeplitz_cfg tc;
+            qldpc_toeplitz_cfg_default(&tc);
+            tc.device = cfg.device; tc.max_blocks = epochs; tc.max_key_bits = key_bits; tc.max_out_bits = key_bits; tc.method = QLDPC_TOEPLITZ_NTT;
+            if ((rc = qldpc_toeplitz_create_cfg(&tc, &tz))) return die("toeplitz_create_cfg", rc);
+            if ((rc = qldpc_toeplitz_create(cfg.device, epochs, key_bits, key_bits, &tz_direct))) return die("toeplitz_create", rc);
+            tz_out2 = calloc((size_t)epochs, sizeof(*tz_out2)); tz_buf2 = calloc((size_t)epochs * W, 4);
+            if (!tz_out2 || !tz_buf2) return 1;
+        } else if ((rc = qldpc_toeplitz_create(cfg.device, epochs, key_bits, key_bits, &tz))) return die("toeplitz_create", rc);
         const size_t sw = qldpc_toeplitz_seed_words(key_bits, key_bits);
         tz_keys = calloc((size_t)epochs, sizeof(*tz_keys)); tz_seeds = calloc((size_t)epochs, sizeof(*tz_seeds)); tz_out = calloc((size_t)epochs, sizeof(*tz_out));
         tz_kb = calloc((size_t)epochs, sizeof(int)); tz_ob = calloc((size_t)epochs, sizeof(int)); tz_buf = calloc((size_t)epochs * W, 4); tz_seed = calloc(sw, 4);
@@ -271,6 +286,16 @@ int main(int argc, char **argv)
             const double dp = now_s() - t0;
             if (rc) return die("toeplitz_blocks", rc);
             if (rep >= 0) { tz_sum += dp; tz_final_sum += (double)bits; if (dp < tz_best) tz_best = dp; }
+            if (ntt) {
+                for (int i = 0; i < m; i++) tz_out2[i] = tz_buf2 + (tz_out[i] - tz_buf);
+                if ((rc = qldpc_toeplitz_blocks(tz_direct, m, tz_keys, tz_kb, tz_seeds, tz_ob, tz_out2))) return die("toeplitz_blocks (direct)", rc);
+                tz_checksum = 0xcbf29ce484222325ull;
+                for (int i = 0; i < m; i++) {
+                    const size_t ow = ((size_t)tz_ob[i] + 31) / 32;
+                    if (memcmp(tz_out[i], tz_out2[i], 4 * ow)) tz_equal = 0;
+                    for (size_t w = 0; w < ow; w++) tz_checksum = (tz_checksum ^ tz_out[i][w]) * 0x100000001b3ull;
+                }
+            }
         }
         if (rep < 0) continue;
         sum += dt;
@@ -303,6 +328,8 @@ int main(int argc, char **argv)
         printf(", \"pa_ms_mean\": %.3f, \"pa_ms_best\": %.3f, \"distill_Mbit_s_mean\": %.1f", pa_sum / reps * 1e3, pa_best * 1e3, final_sum / (sum + pa_sum) / 1e6);
     if (toeplitz)
         printf(", \"tpa_ms_mean\": %.3f, \"tpa_ms_best\": %.3f, \"tdistill_Mbit_s_mean\": %.1f", tz_sum / reps * 1e3, tz_best * 1e3, tz_final_sum / (sum + tz_sum) / 1e6);
+    if (ntt)
+        printf(", \"tpa_method\": \"ntt\", \"tpa_equals_direct\": %d, \"tpa_checksum\": \"%016llx\"", tz_equal, (unsigned long long)tz_checksum);
     if (profile) {
         qldpc_kernel_stat st[16];
         qldpc_recon_profile_enable(rb, 1);
@@ -317,6 +344,7 @@ int main(int argc, char **argv)
     printf("}\n");
     qldpc_privamp_free(pa);
     qldpc_toeplitz_free(tz);
+    qldpc_toeplitz_free(tz_direct);
     qldpc_recon_free(ra);
     qldpc_recon_free(rb);
     return good == epochs ? 0 : 3;
