@@ -240,7 +240,8 @@ size_t qldpc_decoder_device_bytes(const qldpc_decoder *dec);   /* HBM held by th
  * the checks rebuild their previous messages from three state rows each and fold the IRA chain in (0.83 x the rows of an iteration, bit-identical
  * results).  Decided once at creation: FRAMES engine, flooding, fp32 messages, 64-frame groups, MS / OMS / NMS, enable_syndrome = 0, check degrees <= 27
  * in register-resident buckets, and a graph for which qldpc_code_chain_table returns 1.  Everything else -- early exit included -- runs on explicit
- * messages.  Environment: QLDPC_FLOOD_POST=0 keeps the explicit messages (A/B measurements and tests). */
+ * messages.  Environment: QLDPC_FLOOD_POST=0 keeps the explicit messages, QLDPC_FLOOD_POST_VN=0 keeps the posterior pass between two iterations
+ * on the general variable-node kernel instead of its own one-launch kernel (both: A/B measurements and tests). */
 int qldpc_decoder_flood_post(const qldpc_decoder *dec);
 /* Allocate now the buffers the load calls would otherwise allocate on first use (per-frame erasure ballots). */
 int qldpc_decoder_reserve(qldpc_decoder *dec);

@@ -102,7 +102,8 @@ QLDPC_DECLARE_LAUNCH(2)
 QLDPC_DECLARE_LAUNCH(4)
 
 static const int CN_CAPS[] = {8, 12, 20, 40};
-static const int VN_CAPS[] = {4, 12};
+static constexpr int VN_CAPS[] = {4, 12};
+static_assert(VN_CAPS[1] == QK_FPV_DMAX, "qk_vn_fpost has a body for every degree of the register-resident VN buckets, the cap-0 bucket holds the rest");
 
 template <typename T> static int dev_alloc(qldpc_decoder *d, T **p, size_t n)
 {
@@ -152,6 +153,32 @@ static int make_buckets(qldpc_decoder *d, const int *ptr, const int *ids, int n_
     return QLDPC_OK;
 }
 
+/* the VNs 0 .. n_vn - 1 of degree <= QK_FPV_DMAX (the register-resident buckets of VN_CAPS) by exact degree, as the records of qk_vn_fpost
+ * (engine_int.h: fp_vn_class); vn_row = vn_tr.  VNs of a higher degree stay with the cap-0 bucket of the caller's list */
+static int make_fp_vn_classes(qldpc_decoder *d, const int *vn_ptr, int n_vn, const int *vn_row, std::vector<fp_vn_class> &out)
+{
+    std::vector<std::vector<int>> recs(QK_FPV_DMAX + 1);
+    for (int v = 0; v < n_vn; v++) {
+        const int b = vn_ptr[v], deg = vn_ptr[v + 1] - b;
+        if (deg > QK_FPV_DMAX) continue;
+        std::vector<int> &r = recs[(size_t)deg];
+        const size_t at = r.size();
+        r.resize(at + (size_t)QK_FPV_STRIDE(deg), 0);      /* padding: row 0, never asked for */
+        r[at] = v;
+        for (int e = 0; e < deg; e++) r[at + 1 + (size_t)e] = vn_row[b + e];
+    }
+    for (int deg = 0; deg <= QK_FPV_DMAX; deg++) {
+        const std::vector<int> &r = recs[(size_t)deg];
+        if (r.empty()) continue;
+        fp_vn_class c{deg, (int)(r.size() / (size_t)QK_FPV_STRIDE(deg)), nullptr};
+        int rc = dev_alloc(d, &c.d_rec, r.size());
+        if (rc != QLDPC_OK) return rc;
+        out.push_back(c);      /* owned by the decoder from here on */
+        HIPCHK(hipMemcpy(c.d_rec, r.data(), r.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    return QLDPC_OK;
+}
+
 extern "C" void qldpc_decoder_cfg_default(qldpc_decoder_cfg *cfg)
 {
     if (!cfg) return;
@@ -189,6 +216,7 @@ extern "C" void qldpc_decoder_free(qldpc_decoder *d)
     for (auto &l : d->layer_buckets) for (auto &b : l) { (void)hipFree(b.d_list); (void)hipFree(b.d_rec); }
     for (auto &b : d->vlayer_classes) (void)hipFree(b.d_list);
     for (auto &b : d->fp_vn_buckets) (void)hipFree(b.d_list);
+    for (auto &c : d->fp_vn_classes) (void)hipFree(c.d_rec);
     (void)hipFree(d->d_fp_chain); (void)hipFree(d->d_fp_mem);
     (void)hipFree(d->d_vn_chk); (void)hipFree(d->d_gang);
     (void)hipFree(d->d_cn_ptr); (void)hipFree(d->d_cn_tr); (void)hipFree(d->d_cn_var); (void)hipFree(d->d_vn_ptr); (void)hipFree(d->d_info_pos); (void)hipFree(d->d_cn_var_t); (void)hipFree(d->d_vn_tr);
@@ -452,7 +480,15 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
             if (ok) { tab.resize((size_t)d->M); ok = qldpc_code_chain_table(code, tab.data()) == 1; }
             if (ok) {
                 d->ira_K = code->ira_K;
+                /* QLDPC_FLOOD_POST_VN=0 keeps the in-between posterior passes on qk_vn_flood, a launch per bucket (A/B measurements, tests) */
+                d->fp_vn = 1;
+                if (const char *e = getenv("QLDPC_FLOOD_POST_VN")) d->fp_vn = atoi(e) != 0;
                 if ((rc = make_buckets(d, code->vn_ptr, nullptr, d->ira_K, VN_CAPS, 2, d->fp_vn_buckets))) return rc;
+                if (d->fp_vn) {
+                    std::vector<int> vt((size_t)d->E);
+                    for (int k = 0; k < d->E; k++) vt[(size_t)code->transpose[k]] = k;
+                    if ((rc = make_fp_vn_classes(d, code->vn_ptr, d->ira_K, vt.data(), d->fp_vn_classes))) return rc;
+                }
                 if ((rc = dev_alloc(d, &d->d_fp_chain, (size_t)d->M))) return rc;
                 HIPCHK(hipMemcpy(d->d_fp_chain, tab.data(), sizeof(uint32_t) * (size_t)d->M, hipMemcpyHostToDevice));
                 const size_t post_n = G * d->N * 64, st_n = G * d->M * (64 * QK_FP_ROWS);
@@ -733,6 +769,13 @@ static double moved_vn_fpost(const qldpc_decoder *d, bool rows_out, bool ballots
 {
     return (fp_info_edges(d) * 4.0 + fp_chan(d, d->ira_K) + (rows_out ? d->ira_K * 4.0 : 0.0) + (ballots ? d->ira_K / 4.0 : 0.0)) * live_frames(d);
 }
+/* the records of qk_vn_fpost: every 64-frame group reads them once per pass */
+static double fp_vn_rec_bytes(const qldpc_decoder *d)
+{
+    double b = 0.0;
+    for (auto &c : d->fp_vn_classes) b += (double)c.n * QK_FPV_STRIDE(c.deg) * 4.0;
+    return b * (live_frames(d) / 64.0);
+}
 static int cn_pass_fpost(qldpc_decoder *d, int ite)
 {
     prof_scope ps(d, KS_CN, bytes_cn(d), moved_cn_fpost(d, ite == 0));
@@ -743,9 +786,12 @@ static int cn_pass_fpost(qldpc_decoder *d, int ite)
 /* _compute_post over the information VNs: in between iterations it leaves the posterior rows the next check pass gathers and no ballots */
 static int vn_pass_fpost(qldpc_decoder *d, float *post_out, bool between)
 {
-    prof_scope ps(d, KS_VN, bytes_vn(d, QK_VN_POST), moved_vn_fpost(d, post_out != nullptr, !between));
+    const bool own = between && d->fp_vn;      /* qk_vn_fpost: every register-resident bucket in one launch, on the records */
+    prof_scope ps(d, KS_VN, bytes_vn(d, QK_VN_POST), moved_vn_fpost(d, post_out != nullptr, !between) + (own ? fp_vn_rec_bytes(d) : 0.0));
     d->fp_between = between ? 1 : 0;
-    for (auto &b : d->fp_vn_buckets) { qldpc_launch_vn<1, QK_VN_POST>(d, b, post_out); LAUNCHCHK(); }
+    if (own) { qldpc_launch_vn_fpost(d); LAUNCHCHK(); }
+    for (auto &b : d->fp_vn_buckets)
+        if (!own || b.cap == 0) { qldpc_launch_vn<1, QK_VN_POST>(d, b, post_out); LAUNCHCHK(); }
     d->fp_between = 0;
     return QLDPC_OK;
 }

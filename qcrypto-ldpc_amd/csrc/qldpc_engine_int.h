@@ -28,6 +28,11 @@ struct bucket { int cap; int n; int *d_list; int *d_rec; };   /* cap = register-
  * (list -> cn_ptr -> cn_var); the launches of a layered sweep are small and bound by the latency of that chain (DESIGN section 8 #6h);
  * QK_REC_HDR (qldpc_kernels.h) = 4 header words */
 
+/* The information VNs of ONE degree (<= QK_FPV_DMAX) as qk_vn_fpost reads them (qldpc_kernels_fpost.h): entry i is the aligned record
+ * {v, row[0 .. deg)}, row[k] = vn_tr[vn_ptr[v] + k], QK_FPV_STRIDE(deg) ints.  Classes by exact degree, not by bucket: the cap-4 bucket of
+ * an IRA code holds its degree-3 VNs and, where the edge count does not divide, one of degree 4 */
+struct fp_vn_class { int deg; int n; int *d_rec; };
+
 /*
  * Per-frame state of one generation of the early-exit run (qldpc_kernels_compact.h).  Generation 0 is the batch as loaded (its
  * pointers alias the decoder's base arrays); every compaction opens the next one with fewer groups.  A retired generation
@@ -71,11 +76,13 @@ struct qldpc_decoder {
      * posterior row per information VN, the checks keep three state rows each (two buffers, ping-pong by iteration parity) and fold the IRA chain in */
     int fpost, ira_K;
     std::vector<bucket> fp_vn_buckets;   /* the information VNs 0 .. ira_K - 1 */
+    std::vector<fp_vn_class> fp_vn_classes;   /* the same VNs by degree, for the in-between pass (empty with QLDPC_FLOOD_POST_VN=0) */
     uint32_t *d_fp_chain;            /* [M] chain table (qldpc_code_chain_table) */
     float *fp_post, *fp_st[2];       /* [G][N][64] posteriors, 2 x [G][M][3][64] check state: carved out of d_a (var_to_chk is not used) where they fit, else d_fp_mem */
     float *d_fp_mem;
     int fp_last;                     /* the state buffer the last check pass of the run wrote */
     int fp_between;                  /* set around the in-between posterior passes: nobody reads their ballots */
+    int fp_vn;                       /* the in-between posterior passes run on qk_vn_fpost (QLDPC_FLOOD_POST_VN=0: on qk_vn_flood, a launch per bucket) */
     int layer_first;                 /* layered fp32 run, sweep 0, messages not frozen: the layer kernels treat the messages as zero instead of reading a cleared array */
     /* state */
     float *d_llr, *d_a, *d_b;        /* flooding: a = v2c, b = c2v ; layered: a = post, b = msg */
@@ -209,6 +216,8 @@ void qldpc_launch_layer_chain(qldpc_decoder *d, int sweep);      /* V = 1 only *
 /* posterior form of the flooding run (V = 1 only): the check pass of iteration `ite` over one bucket, and the closing pass over the chain VNs */
 void qldpc_launch_cn_fpost(qldpc_decoder *d, const bucket &b, int ite);
 void qldpc_launch_fpost_close(qldpc_decoder *d, float *post_out);
+/* the posterior pass between two iterations over fp_vn_classes (qk_vn_fpost: QK_FPV_CLASSES degree classes per launch) */
+void qldpc_launch_vn_fpost(qldpc_decoder *d);
 int qldpc_chain_resident_blocks(qldpc_decoder *d);
 template <int V, int MODE> void qldpc_launch_vn(qldpc_decoder *d, const bucket &b, float *post_out);
 #define QLDPC_DECLARE_LAUNCH(V)                                                                   \

@@ -6,7 +6,8 @@
  * the very same floats:
  *
  *  1. var_to_chk[slot] = tmp - chk_to_var[slot] with tmp = Y + sum of the VN's messages in slot order.  The variable-node pass
- *     therefore only writes tmp (qk_vn_flood in QK_VN_POST mode: one row per VN); the check forms tmp - (its own previous message)
+ *     therefore only writes tmp (qk_vn_fpost below, one row per VN; qk_vn_flood in QK_VN_POST mode where the run closes, for degrees
+ *     above QK_FPV_DMAX and with QLDPC_FLOOD_POST_VN=0); the check forms tmp - (its own previous message)
  *     itself: the same subtraction on the same operands.
  *  2. A check rebuilds its own previous messages from a compressed state, as the layered sweeps do (qldpc_kernels_cst.h).  For
  *     MS / OMS / NMS a tie min1 == min2 makes cst1 and cst2 the same float (qk_acc<QK_FAM_MS>::finish), so "which edges took
@@ -163,6 +164,102 @@ __global__ __launch_bounds__(QK_THREADS) void qk_cn_fpost(const float *__restric
         if (k < deg) idx = (fabsf(x[k]) == acc.min1) ? (uint32_t)k : idx;      /* descending k: the first edge at the minimum stays */
     float *so = st_out + srow;
     so[0] = acc.cst1; so[64] = acc.cst2; reinterpret_cast<uint32_t *>(so)[128] = nw | (idx << 27);
+}
+
+/*
+ * The posterior pass between two iterations: tmp = Y + (((0.0f + m[0]) + m[1]) + ...) in slot order, exactly as qk_vn_flood sums, one
+ * posterior row stored per information VN and nothing else (no ballots: nobody reads them before the run closes).
+ *
+ * The VNs come in classes of ONE degree each (fp_vn_class, qldpc_engine_int.h), and one launch covers up to QK_FPV_CLASSES of them: the
+ * workgroups of class k are blk_end[k - 1] .. blk_end[k] - 1.  Class and degree are found by comparing blockIdx.x and one switch, all
+ * wave-uniform, and each degree runs its own fully unrolled body without a per-row predicate.
+ *
+ * A wave learns everything in one scalar round trip: entry i of a class is one aligned record {v, row[0 .. D)} with
+ * row[k] = vn_tr[vn_ptr[v] + k] (QK_FPV_STRIDE(D) ints: one dwordx4 for degree 3), asked for together with the group's `done` word.
+ * Then the message rows (non-temporal: the check pass streamed them out, they are read once), the channel values behind them as in
+ * qk_vn_flood, the sum, and a non-temporal store: the next check pass gathers a posterior row once per edge of its VN, but a pass of rows
+ * later -- a plain store only parks the row in a cache it is evicted from before anybody asks (measured, DESIGN section 8 #1a).
+ */
+#define QK_FPV_DMAX 12         /* the degrees with a body (VN_CAPS of the engine: the register-resident buckets) */
+#define QK_FPV_CLASSES 4       /* degree classes per launch */
+#define QK_FPV_STRIDE(D) (((D) + 1 + 3) & ~3)      /* ints per record: {v, row[0 .. D)} padded to 16 bytes */
+#define QK_FPV_UN(D) ((D) <= 4 ? 4 : 2)      /* VNs per wave: 12 rows in flight at degree 3, 22 at degree 11 */
+struct qk_fpv_args {
+    const int *rec[QK_FPV_CLASSES];
+    int n[QK_FPV_CLASSES], deg[QK_FPV_CLASSES], blk_end[QK_FPV_CLASSES];      /* unused classes: n = 0, blk_end = the grid */
+};
+template <int D, int UN, bool CODED>
+__device__ __forceinline__ void qk_vn_fpost_deg(const float *__restrict__ cin, const float *__restrict__ yin, float *__restrict__ pout,
+                                                const int *__restrict__ rec, int n_list, int i0, int g, int lane, int N,
+                                                const u64 *__restrict__ done, const qk_coded_llr &coded)
+{
+    constexpr int S = QK_FPV_STRIDE(D);
+    if (i0 >= n_list) return;
+    int w[UN][S];
+#pragma unroll
+    for (int u = 0; u < UN; u++) {
+        const int i = (i0 + u < n_list) ? i0 + u : i0;      /* the tail repeats entry i0 (idempotent) */
+        const int4 *r = reinterpret_cast<const int4 *>(rec) + (size_t)i * (S / 4);
+#pragma unroll
+        for (int q = 0; q < S / 4; q++) {
+            const int4 t = r[q];
+            w[u][4 * q] = t.x; w[u][4 * q + 1] = t.y; w[u][4 * q + 2] = t.z; w[u][4 * q + 3] = t.w;
+        }
+    }
+    if (qk_group_done<1>(done, g)) return;      /* a group of padding frames only */
+    float m[UN][D > 0 ? D : 1];
+#pragma unroll
+    for (int u = 0; u < UN; u++) {
+#pragma unroll
+        for (int k = 0; k < D; k++) m[u][k] = __builtin_nontemporal_load(cin + (size_t)w[u][1 + k] * 64);
+    }
+    float y[UN];
+    if constexpr (CODED) {
+        const float mg[1] = {coded.fmag[(size_t)g * 64 + lane]};
+        const int nc[1] = {coded.fnch[(size_t)g * 64 + lane]};
+#pragma unroll
+        for (int u = 0; u < UN; u++) {
+            float t[1];
+            qk_coded_y<1>(t, coded, g, w[u][0], N, lane, mg, nc);
+            y[u] = t[0];
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < UN; u++) y[u] = __builtin_nontemporal_load(yin + (size_t)w[u][0] * 64);
+    }
+#pragma unroll
+    for (int u = 0; u < UN; u++) {
+        float sum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < D; k++) sum += m[u][k];
+        __builtin_nontemporal_store(y[u] + sum, pout + (size_t)w[u][0] * 64);
+    }
+}
+
+template <bool CODED>
+__global__ __launch_bounds__(QK_THREADS) void qk_vn_fpost(const float *__restrict__ c2v, const float *__restrict__ llr, float *__restrict__ post, qk_fpv_args a,
+                                                          int N, size_t group_stride, const u64 *__restrict__ done, qk_coded_llr coded)
+{
+    const int g = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float *cin = c2v + (size_t)g * group_stride + lane;
+    const float *yin = llr + (size_t)g * N * 64 + lane;
+    float *pout = post + (size_t)g * N * 64 + lane;
+    const int blk = (int)blockIdx.x;
+    const int *rec = a.rec[0];
+    int n = a.n[0], deg = a.deg[0], blk0 = 0;
+#pragma unroll
+    for (int k = 1; k < QK_FPV_CLASSES; k++)
+        if (blk >= a.blk_end[k - 1]) { rec = a.rec[k]; n = a.n[k]; deg = a.deg[k]; blk0 = a.blk_end[k - 1]; }
+    const int wi = (blk - blk0) * QK_WAVES + wave;      /* this wave within its class */
+#define QK_FPV_CASE(D) case D: qk_vn_fpost_deg<D, QK_FPV_UN(D), CODED>(cin, yin, pout, rec, n, wi * QK_FPV_UN(D), g, lane, N, done, coded); break;
+    switch (deg) {
+        QK_FPV_CASE(0) QK_FPV_CASE(1) QK_FPV_CASE(2) QK_FPV_CASE(3) QK_FPV_CASE(4) QK_FPV_CASE(5) QK_FPV_CASE(6)
+        QK_FPV_CASE(7) QK_FPV_CASE(8) QK_FPV_CASE(9) QK_FPV_CASE(10) QK_FPV_CASE(11) QK_FPV_CASE(12)
+    default: break;
+    }
+#undef QK_FPV_CASE
 }
 
 /*

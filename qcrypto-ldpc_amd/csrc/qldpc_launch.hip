@@ -239,6 +239,31 @@ void qldpc_launch_cn_fpost(qldpc_decoder *d, const bucket &b, int ite)
     default: ite == 0 ? launch_cn_fpost_one<QK_FP_DCMAX, true>(d, b, ite) : launch_cn_fpost_one<QK_FP_DCMAX, false>(d, b, ite); break;
     }
 }
+/* the posterior pass between two iterations (qk_vn_fpost): QK_FPV_CLASSES degree classes per launch, so ONE launch for the two or three
+ * information-VN degrees of an IRA code */
+void qldpc_launch_vn_fpost(qldpc_decoder *d)
+{
+    const size_t nc = d->fp_vn_classes.size();
+    for (size_t c0 = 0; c0 < nc; c0 += QK_FPV_CLASSES) {
+        qk_fpv_args a{};
+        int blocks = 0;
+        for (size_t k = 0; k < QK_FPV_CLASSES; k++) {
+            if (c0 + k < nc) {
+                const fp_vn_class &c = d->fp_vn_classes[c0 + k];
+                a.rec[k] = c.d_rec; a.n[k] = c.n; a.deg[k] = c.deg;
+                blocks += grid_x(c.n, QK_FPV_UN(c.deg));
+            }
+            a.blk_end[k] = blocks;
+        }
+        dim3 grid((unsigned)blocks, (unsigned)d->G);
+        if (d->llr_coded)
+            hipLaunchKernelGGL((qk_vn_fpost<true>), grid, dim3(QK_THREADS), 0, d->stream, (const float *)d->d_b, (const float *)nullptr, d->fp_post, a,
+                               d->N, (size_t)d->E * 64, d->d_done, coded_llr_of(d));
+        else
+            hipLaunchKernelGGL((qk_vn_fpost<false>), grid, dim3(QK_THREADS), 0, d->stream, (const float *)d->d_b, (const float *)d->d_llr, d->fp_post, a,
+                               d->N, (size_t)d->E * 64, d->d_done, qk_coded_llr{});
+    }
+}
 void qldpc_launch_fpost_close(qldpc_decoder *d, float *post_out)
 {
     dim3 grid((unsigned)grid_x(d->M, 1), (unsigned)d->G);
