@@ -224,7 +224,20 @@ typedef struct qldpc_decoder_cfg {
                             check degree <= 32, freeze_messages = 0) otherwise keep a COMPRESSED CHECK STATE -- the two magnitudes a check's messages
                             take and two dc-bit masks per frame instead of the dc messages (csrc/qldpc_kernels_cst.h): the same floats, 0.61 x the
                             bytes on the N = 10^6 code -- so for those rules auto never picks the one-launch sweep, and 1 gives up the state for it */
-    int reserved[1];     /* must be zero                                                         */
+    int giveup_patience; /* FRAMES engine, enable_syndrome = 1, flooding or horizontal layered: 0 = off (the run launches what it always did);
+                            p >= 1 = give a frame up once its syndrome weight has not reached a new minimum for p tests in a row.  The weight of a
+                            frame at a test is the number of checks with (H x + s)_c = 1 over the sign ballots the test reads; the tests are the
+                            ones the early exit makes anyway (flooding: after iterations 1 .. n_ite - 1, layered: after every sweep).  At the
+                            first test, or when w < best: best = w, since = 0; otherwise since += 1.  The convergence logic (syndrome_depth) is
+                            untouched and wins; a frame that is not done, has w > 0 and since >= p is given up: its done bit is set, its
+                            iteration count is the iterations executed, and from there it is a finished frame in every respect (ballots, hard
+                            decisions and iteration count frozen, messages frozen with freeze_messages = 1, its group skipped once all its frames
+                            are done, left behind by a compaction).  Its success flag, the syndrome of the hard decisions it stopped with, is 0.
+                            p >= n_ite never gives up and only counts (qldpc_fetch_giveup_dev).  The rule is stated once, in
+                            csrc/qldpc_giveup_core.h; qldpc_giveup_host is its mirror.  Negative: QLDPC_EINVAL; enable_syndrome = 0:
+                            QLDPC_EINVAL; engine = EDGES or the vertical-layered schedule: QLDPC_EUNSUPPORTED; engine auto picks FRAMES.
+                            qldpc_gang_create refuses such a member; qldpc_mc_blind asks for freeze_messages = 1 with it; the sessions
+                            (qldpc_recon_*) create their decoders without it.  (This word was reserved[1], must be zero, before.)   */
 } qldpc_decoder_cfg;
 
 void qldpc_decoder_cfg_default(qldpc_decoder_cfg *cfg);
@@ -315,6 +328,25 @@ int qldpc_fetch_weakest_dev(qldpc_decoder *dec, const uint32_t *d_cand_bits, con
 /* Host mirror of the select, no device needed: one frame, post[N], cand_bits[ceil(N/32)] (NULL = every v < N; bits at v >= N are ignored),
  * weak_bits[ceil(N/32)], *n_taken (optional) = bits set.  The kernel's lanes run the same functions (csrc/qldpc_weakest_core.h). */
 int qldpc_weakest_host(const float *post, int N, const uint32_t *cand_bits, int d, uint32_t *weak_bits, int *n_taken);
+/*
+ * fetch: what the give-up rule saw (decoders created with giveup_patience >= 1; QLDPC_EUNSUPPORTED otherwise, QLDPC_ESTATE without a completed run).
+ * Each array is [n_frames] ints in the caller's frame order and may be NULL; valid after a run that compacted, as qldpc_fetch_status_dev is.
+ *   d_gave         1 if the frame was given up, else 0
+ *   d_last_weight  the syndrome weight at the frame's last test: 0 for a converged frame, > 0 for one given up; for a frame that ran out the last test
+ *                  of the run -- on the flooding schedule the one after iteration n_ite - 1, NOT the weight of the final hard decision
+ *   d_best_weight  the smallest weight the frame showed at a test (-1: the run made no test, n_ite = 1 on the flooding schedule)
+ * qldpc_fetch_post_dev / qldpc_fetch_weakest_dev are exact for a frame given up under the condition that makes them exact for a converged frame:
+ * freeze_messages = 1 (otherwise its messages ran on after it stopped).
+ */
+int qldpc_fetch_giveup_dev(qldpc_decoder *dec, int *d_gave, int *d_last_weight, int *d_best_weight);
+/* *frames = the frames given up by all runs of this decoder since it was created, counted on the device (0 with giveup_patience = 0): what a loop that
+ * runs the decoder many times -- qldpc_mc_run, qldpc_mc_blind, qldpc_sim -g -- reports.  Synchronises the decoder's stream. */
+int qldpc_giveup_total(qldpc_decoder *dec, uint64_t *frames);
+/* Host mirror of the give-up rule for one frame, no device needed: weights[t] = the syndrome weight at test t + 1 (t < n_tests) of a run that never
+ * stops the frame.  *stop_test (optional) = the 1-based test at which it converged or was given up, 0 if it ran out; *outcome (optional) one of
+ * QLDPC_GIVEUP_*.  patience = 0: the rule is off.  QLDPC_EINVAL: n_tests < 1, syndrome_depth < 1, patience < 0, a negative weight. */
+enum { QLDPC_GIVEUP_CONVERGED = 0, QLDPC_GIVEUP_GAVE_UP = 1, QLDPC_GIVEUP_RAN_OUT = 2 };
+int qldpc_giveup_host(const int *weights, int n_tests, int syndrome_depth, int patience, int *stop_test, int *outcome);
 /* block until everything queued on the decoder's stream is done. */
 int qldpc_sync(qldpc_decoder *dec);
 

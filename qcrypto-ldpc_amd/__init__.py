@@ -61,7 +61,7 @@ _vp = C.c_void_p
 class DecoderCfg(C.Structure):
     _fields_ = [("schedule", C.c_int), ("rule", C.c_int), ("rule_param", C.c_float), ("n_ite", C.c_int),
                 ("enable_syndrome", C.c_int), ("syndrome_depth", C.c_int), ("max_frames", C.c_int),
-                ("device", C.c_int), ("frames_per_lane", C.c_int), ("engine", C.c_int), ("freeze_messages", C.c_int), ("msg_dtype", C.c_int), ("quant_scale", C.c_float), ("compact", C.c_int), ("layer_chain", C.c_int), ("reserved", C.c_int * 1)]
+                ("device", C.c_int), ("frames_per_lane", C.c_int), ("engine", C.c_int), ("freeze_messages", C.c_int), ("msg_dtype", C.c_int), ("quant_scale", C.c_float), ("compact", C.c_int), ("layer_chain", C.c_int), ("giveup_patience", C.c_int)]
 
 
 class KernelStat(C.Structure):
@@ -122,6 +122,9 @@ _sig("qldpc_fetch_post_dev", C.c_int, [_vp, _vp])
 _sig("qldpc_load_known_dev", C.c_int, [_vp, _vp, _vp, C.c_int])
 _sig("qldpc_fetch_weakest_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp])
 _sig("qldpc_weakest_host", C.c_int, [_fp, C.c_int, _vp, C.c_int, _vp, _ip])
+_sig("qldpc_fetch_giveup_dev", C.c_int, [_vp, _vp, _vp, _vp])
+_sig("qldpc_giveup_total", C.c_int, [_vp, C.POINTER(C.c_uint64)])
+_sig("qldpc_giveup_host", C.c_int, [_ip, C.c_int, C.c_int, C.c_int, _ip, _ip])
 _sig("qldpc_sync", C.c_int, [_vp])
 _sig("qldpc_profile_enable", C.c_int, [_vp, C.c_int])
 _sig("qldpc_profile_read", C.c_int, [_vp, C.POINTER(KernelStat), C.c_int])
@@ -323,7 +326,7 @@ class Decoder:
 
     def __init__(self, code, K, n_ite, info_bits_pos=None, rule="SPA", rule_param=0.0, enable_syndrome=True,
                  syndrome_depth=1, n_frames=1, schedule="flooding", device=0, frames_per_lane=0, engine="auto",
-                 freeze_messages=False, msg_dtype="f32", quant_scale=0.0, compact="auto", layer_chain="auto"):
+                 freeze_messages=False, msg_dtype="f32", quant_scale=0.0, compact="auto", layer_chain="auto", giveup=0):
         cfg = DecoderCfg()
         _L.qldpc_decoder_cfg_default(C.byref(cfg))
         cfg.schedule = SCHEDULES[schedule]
@@ -341,6 +344,7 @@ class Decoder:
         cfg.quant_scale = float(quant_scale)
         cfg.compact = {"auto": 0, "on": 1, "off": 2}[compact]
         cfg.layer_chain = {"auto": 0, "on": 1, "off": 2}[layer_chain]
+        cfg.giveup_patience = int(giveup)
         pos = None
         if info_bits_pos is not None:
             pos = _np_i32(info_bits_pos)
@@ -352,6 +356,7 @@ class Decoder:
         self._h = h
         self.code, self.K, self.N = code, int(K), code.N
         self.max_frames, self.device = int(n_frames), int(device)
+        self.giveup = int(giveup)
         self.n_frames = 0
 
     # -- AFF3CT mirror (host vectors) --------------------------------------------------------
@@ -476,6 +481,20 @@ class Decoder:
         _chk(_L.qldpc_fetch_weakest_dev(self._h, _vp(cand_bits.data_ptr()) if cand_bits is not None else None,
                                         _vp(take.data_ptr()) if take is not None else None, int(d), _vp(out.data_ptr())), "fetch_weakest")
         return out
+
+    def fetch_giveup(self):
+        """decoders created with giveup >= 1: (gave, last, best) int32 [n_frames] -- 1 for a frame the run gave up, its syndrome weight at its
+        last test, the smallest weight it showed at a test (qldpc_fetch_giveup_dev)"""
+        torch = _torch()
+        gave, last, best = (torch.empty(self.n_frames, dtype=torch.int32, device="cuda:%d" % self.device) for _ in range(3))
+        _chk(_L.qldpc_fetch_giveup_dev(self._h, _vp(gave.data_ptr()), _vp(last.data_ptr()), _vp(best.data_ptr())), "fetch_giveup")
+        return gave, last, best
+
+    def giveup_total(self):
+        """frames given up by all runs of this decoder since it was created (qldpc_giveup_total; 0 with giveup = 0)"""
+        n = C.c_uint64(0)
+        _chk(_L.qldpc_giveup_total(self._h, C.byref(n)), "giveup_total")
+        return int(n.value)
 
     def sync(self):
         _chk(_L.qldpc_sync(self._h), "sync")
@@ -638,6 +657,19 @@ def unpack_bits(words, n):
     by = np.stack([(w >> 24) & 255, (w >> 16) & 255, (w >> 8) & 255, w & 255], axis=-1).astype(np.uint8)
     bits = np.unpackbits(by.reshape(w.shape[:-1] + (-1,)), axis=-1, bitorder="big")
     return bits[..., :n]
+
+
+GIVEUP_CONVERGED, GIVEUP_GAVE_UP, GIVEUP_RAN_OUT = 0, 1, 2
+
+
+def giveup_host(weights, patience, syndrome_depth=1):
+    """the give-up rule of the early-exit run on the host (qldpc_giveup_host): weights[n_tests] = the syndrome weights of one frame at the tests
+    of a run that never stops it -> (stop_test, outcome): the 1-based test at which it converged or was given up (0: it ran out) and one of
+    GIVEUP_CONVERGED / GIVEUP_GAVE_UP / GIVEUP_RAN_OUT.  patience = 0: the rule is off"""
+    w = _np_i32(weights).reshape(-1)
+    stop, what = C.c_int(0), C.c_int(0)
+    _chk(_L.qldpc_giveup_host(w.ctypes.data_as(_ip), w.size, int(syndrome_depth), int(patience), C.byref(stop), C.byref(what)), "giveup_host")
+    return stop.value, what.value
 
 
 def weakest_host(post, d, cand_bits=None):

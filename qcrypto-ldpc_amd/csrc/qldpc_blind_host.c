@@ -1,11 +1,13 @@
 /*
  * qldpc_blind_host.c -- the host side of blind reconciliation that needs no device: the mirror of the weakest-VN select
- * (qldpc_weakest_core.h, the functions the lanes of qk_weakest run) and Alice's answer to a request for key bits.
+ * (qldpc_weakest_core.h, the functions the lanes of qk_weakest run), Alice's answer to a request for key bits, and the mirror of the give-up rule
+ * of the early-exit run (qldpc_giveup_core.h, the functions the lanes of qk_status_count run).
  */
 #include <stdlib.h>
 
 #include "../../include/qldpc.h"
 #include "qldpc_weakest_core.h"
+#include "qldpc_giveup_core.h"
 
 int qldpc_weakest_host(const float *post, int N, const uint32_t *cand_bits, int d, uint32_t *weak_bits, int *n_taken)
 {
@@ -58,5 +60,23 @@ int qldpc_recon_disclose_host(const uint32_t *key_words, int key_bits, const int
     for (int i = 0; i < n; i++)
         if (pos[i] < 0 || pos[i] >= key_bits) return QLDPC_EINVAL;
     for (int i = 0; i < n; i++) bit[i] = (uint8_t)((key_words[pos[i] >> 5] >> (31 - (pos[i] & 31))) & 1u);
+    return QLDPC_OK;
+}
+
+/* one frame: weights[t] = its syndrome weight at test t + 1 of a run that never stops it */
+int qldpc_giveup_host(const int *weights, int n_tests, int syndrome_depth, int patience, int *stop_test, int *outcome)
+{
+    if (!weights || n_tests < 1 || syndrome_depth < 1 || patience < 0) return QLDPC_EINVAL;
+    for (int t = 0; t < n_tests; t++) if (weights[t] < 0) return QLDPC_EINVAL;
+    int best, since, depth = 0, stop = 0, what = GU_RAN_OUT;
+    gu_reset(&best, &since);
+    for (int t = 0; t < n_tests && !stop; t++) {
+        const int now = gu_converges(&depth, weights[t] == 0, syndrome_depth);
+        gu_observe(&best, &since, weights[t]);
+        if (now) { stop = t + 1; what = GU_CONVERGED; }
+        else if (patience > 0 && gu_gives_up(weights[t], since, patience, now)) { stop = t + 1; what = GU_GAVE_UP; }
+    }
+    if (stop_test) *stop_test = stop;
+    if (outcome) *outcome = what;
     return QLDPC_OK;
 }

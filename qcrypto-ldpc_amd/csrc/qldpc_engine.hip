@@ -201,6 +201,7 @@ static void gen_release(gen_state &n)
 {
     (void)hipFree(n.sgn); if (n.hard != n.sgn) (void)hipFree(n.hard); (void)hipFree(n.unsat); (void)hipFree(n.done); (void)hipFree(n.ybits); (void)hipFree(n.synd); (void)hipFree(n.ebits);
     (void)hipFree(n.depth); (void)hipFree(n.iters); (void)hipFree(n.origin); (void)hipFree(n.src); (void)hipFree(n.fmag); (void)hipFree(n.fnch);
+    (void)hipFree(n.gu_last); (void)hipFree(n.gu_best); (void)hipFree(n.gu_since); (void)hipFree(n.gu_gave);
     n = gen_state{};
 }
 
@@ -223,6 +224,7 @@ extern "C" void qldpc_decoder_free(qldpc_decoder *d)
     (void)hipFree(d->d_chain_order); (void)hipFree(d->d_chain_dep); (void)hipFree(d->d_chain_ver); (void)hipFree(d->d_chain_ctl);
     (void)hipFree(d->d_llr); (void)hipFree(d->d_llr8); (void)hipFree(d->d_ybits); (void)hipFree(d->d_ebits); (void)hipFree(d->d_known); (void)hipFree(d->d_fmag); (void)hipFree(d->d_fnch); (void)hipFree(d->d_vcls); (void)hipFree(d->d_a); (void)hipFree(d->d_b); (void)hipFree(d->d_post);
     (void)hipFree(d->d_sgn); if (d->d_hard != d->d_sgn) (void)hipFree(d->d_hard); (void)hipFree(d->d_unsat); (void)hipFree(d->d_done);
+    (void)hipFree(d->gu.weight); (void)hipFree(d->gu.last); (void)hipFree(d->gu.best); (void)hipFree(d->gu.since); (void)hipFree(d->gu.gave); (void)hipFree(d->gu.total);
     (void)hipFree(d->d_depth); (void)hipFree(d->d_iters); (void)hipFree(d->d_active); (void)hipFree(d->h_in); (void)hipFree(d->h_out); (void)hipFree(d->d_synd); (void)hipFree(d->e_synd);
     (void)hipFree(d->e_c2v1); (void)hipFree(d->e_ctl); (void)hipFree(d->e_sgn); (void)hipFree(d->e_hard); (void)hipFree(d->e_unsat); (void)hipFree(d->e_done_at);
     if (d->h_done) (void)hipHostFree(d->h_done);
@@ -302,6 +304,10 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
         if (eng == QLDPC_ENGINE_EDGES && !edge_ok) {
             qldpc_set_error("edge-parallel engine needs flooding, MS/OMS/NMS/SPA, check degree <= 64 (have %d) and VN degree <= 64 (have %d)", code->max_dc, code->max_dv);
             return QLDPC_EUNSUPPORTED;
+        }
+        if (cfg->giveup_patience > 0) {      /* the syndrome weights are counted by the FRAMES engine's test */
+            if (eng == QLDPC_ENGINE_EDGES) { qldpc_set_error("giveup_patience needs the FRAMES engine: create the decoder with engine = FRAMES (or auto)"); return QLDPC_EUNSUPPORTED; }
+            eng = QLDPC_ENGINE_FRAMES;
         }
         if (eng == QLDPC_ENGINE_AUTO) eng = (edge_ok && cfg->max_frames <= 8) ? QLDPC_ENGINE_EDGES : QLDPC_ENGINE_FRAMES;
         d->engine = eng;
@@ -513,6 +519,10 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
     if ((rc = dev_alloc(d, &d->d_done, G * V))) return rc;
     if ((rc = dev_alloc(d, &d->d_depth, G * FG))) return rc;
     if ((rc = dev_alloc(d, &d->d_iters, G * FG))) return rc;
+    d->gu.patience = cfg->giveup_patience;
+    if (d->gu.patience > 0 && ((rc = dev_alloc(d, &d->gu.weight, G * FG)) || (rc = dev_alloc(d, &d->gu.last, G * FG)) || (rc = dev_alloc(d, &d->gu.best, G * FG)) ||
+                               (rc = dev_alloc(d, &d->gu.since, G * FG)) || (rc = dev_alloc(d, &d->gu.gave, G * V)) || (rc = dev_alloc(d, &d->gu.total, 1)))) return rc;
+    if (d->gu.total) HIPCHK(hipMemset(d->gu.total, 0, sizeof(*d->gu.total)));
     if ((rc = dev_alloc(d, &d->d_active, 4))) return rc;
     HIPCHK(hipMemset(d->d_active, 0, 4 * sizeof(int)));
     if ((rc = dev_alloc(d, &d->d_work, 1))) return rc;
@@ -551,7 +561,13 @@ extern "C" int qldpc_decoder_create(const qldpc_code *code, int K, const int *in
     if (cfg->enable_syndrome && cfg->syndrome_depth < 1) { qldpc_set_error("decoder_create: syndrome_depth=%d", cfg->syndrome_depth); return QLDPC_EINVAL; }
     if (cfg->frames_per_lane != 0 && cfg->frames_per_lane != 1 && cfg->frames_per_lane != 2 && cfg->frames_per_lane != 4) { qldpc_set_error("decoder_create: frames_per_lane=%d", cfg->frames_per_lane); return QLDPC_EINVAL; }
     if (cfg->msg_dtype < 0 || cfg->msg_dtype > 2) { qldpc_set_error("decoder_create: msg_dtype=%d", cfg->msg_dtype); return QLDPC_EINVAL; }
-    if (cfg->compact < 0 || cfg->compact > 2 || cfg->layer_chain < 0 || cfg->layer_chain > 2 || cfg->reserved[0]) { qldpc_set_error("decoder_create: compact=%d, layer_chain=%d (0 auto, 1 on, 2 off), reserved words must be zero", cfg->compact, cfg->layer_chain); return QLDPC_EINVAL; }
+    if (cfg->compact < 0 || cfg->compact > 2 || cfg->layer_chain < 0 || cfg->layer_chain > 2) { qldpc_set_error("decoder_create: compact=%d, layer_chain=%d (0 auto, 1 on, 2 off)", cfg->compact, cfg->layer_chain); return QLDPC_EINVAL; }
+    if (cfg->giveup_patience < 0) { qldpc_set_error("decoder_create: giveup_patience=%d (0 = off, >= 1 = tests without a new minimum of the syndrome weight)", cfg->giveup_patience); return QLDPC_EINVAL; }
+    if (cfg->giveup_patience > 0 && !cfg->enable_syndrome) { qldpc_set_error("decoder_create: giveup_patience=%d works on the syndrome tests of the early exit: set enable_syndrome = 1", cfg->giveup_patience); return QLDPC_EINVAL; }
+    if (cfg->giveup_patience > 0 && cfg->schedule == QLDPC_SCHED_VLAYERED) {
+        qldpc_set_error("giveup_patience is not built for the vertical-layered schedule: use QLDPC_SCHED_FLOODING or QLDPC_SCHED_HLAYERED, or giveup_patience = 0");
+        return QLDPC_EUNSUPPORTED;
+    }
     if (!(cfg->quant_scale >= 0.0f) || cfg->quant_scale > 64.0f) { qldpc_set_error("decoder_create: quant_scale=%g", (double)cfg->quant_scale); return QLDPC_EINVAL; }
     if (cfg->schedule == QLDPC_SCHED_VLAYERED && (cfg->engine == QLDPC_ENGINE_EDGES || cfg->msg_dtype != 0 || cfg->layer_chain == 1 || cfg->compact == 1)) {
         qldpc_set_error("the vertical-layered schedule runs on the FRAMES engine with fp32 messages, one launch per class and no compaction "
@@ -574,6 +590,7 @@ static void use_gen(qldpc_decoder *d, int k)
     d->G = n.G;
     d->d_sgn = n.sgn; d->d_hard = n.hard; d->d_unsat = n.unsat; d->d_done = n.done; d->d_ybits = n.ybits; d->d_synd = n.synd; d->d_ebits = n.ebits;
     d->d_depth = n.depth; d->d_iters = n.iters; d->d_fmag = n.fmag; d->d_fnch = n.fnch; d->d_llr = n.llr; d->d_llr8 = n.llr8;
+    d->gu.last = n.gu_last; d->gu.best = n.gu_best; d->gu.since = n.gu_since; d->gu.gave = n.gu_gave;
     if (n.post) { d->d_a = n.post; d->d_b = n.msg; }      /* layered: each generation has its own posteriors and messages */
 }
 /* back to the batch as loaded (generation 0 = the decoder's base arrays) */
@@ -589,6 +606,7 @@ static void gen0_capture(qldpc_decoder *d)
     n.G = n.cap = d->G0;
     n.sgn = d->d_sgn; n.hard = d->d_hard; n.unsat = d->d_unsat; n.done = d->d_done; n.ybits = d->d_ybits; n.synd = d->d_synd; n.ebits = d->d_ebits;
     n.depth = d->d_depth; n.iters = d->d_iters; n.origin = nullptr; n.src = nullptr; n.fmag = d->d_fmag; n.fnch = d->d_fnch; n.llr = d->d_llr; n.llr8 = d->d_llr8;
+    n.gu_last = d->gu.last; n.gu_best = d->gu.best; n.gu_since = d->gu.since; n.gu_gave = d->gu.gave;
     n.post = d->d_a; n.msg = d->d_b;
 }
 
@@ -844,6 +862,27 @@ static int status_pass(qldpc_decoder *d, int ite_done)
     LAUNCHCHK();
     return QLDPC_OK;
 }
+/* the same two passes with giveup_patience > 0 (qldpc_kernels_giveup.h): every check counted in one launch, and the status pass that runs the rule */
+template <int V>
+static int synd_count_pass(qldpc_decoder *d)
+{
+    prof_scope ps(d, KS_SYND, (double)d->E * 8.0 * d->G * V);
+    const int g8 = (d->G + 7) / 8 * 8;
+    const int bx = std::max(1, std::min((d->M + 255) / 256, 4096 / std::max(1, d->G)));
+    hipLaunchKernelGGL((qk_syndrome_count<V>), dim3((unsigned)((d->G < 8 ? d->G : g8) * bx)), dim3(256), 0, d->stream, d->d_sgn, d->d_cn_var_t, d->max_dc, d->M, d->N,
+                       d->d_unsat, d->d_done, target_synd(d), d->G, bx, d->gu.weight);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+template <int V>
+static int status_count_pass(qldpc_decoder *d, int ite_done)
+{
+    prof_scope ps(d, KS_STATUS, 0.0);
+    hipLaunchKernelGGL((qk_status_count<V>), dim3((unsigned)d->G), dim3(64), 0, d->stream, d->d_unsat, d->d_done, d->d_depth, d->d_iters, d->G,
+                       d->cfg.syndrome_depth, ite_done, d->d_active, d->d_work, (volatile int *)d->h_active_dev, ++d->poll_seq, d->gu);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
 /* blocking: how many groups still have unconverged frames after the status pass launched last, and how many frames those are.
  * The kernel writes the counts and then its sequence number into mapped pinned memory; the host spins on the sequence word. */
 static int poll_active(qldpc_decoder *d, int *active, int *active_frames)
@@ -896,6 +935,7 @@ static int compact(qldpc_decoder *d, int active_frames)
     if ((rc = gen_alloc(d, &n.unsat, C * V)) || (rc = gen_alloc(d, &n.done, C * V))) return rc;
     if ((rc = gen_alloc(d, &n.depth, C * FG)) || (rc = gen_alloc(d, &n.iters, C * FG)) || (rc = gen_alloc(d, &n.origin, C * FG)) || (rc = gen_alloc(d, &n.src, C * FG))) return rc;
     if (o.fmag && ((rc = gen_alloc(d, &n.fmag, C * FG)) || (rc = gen_alloc(d, &n.fnch, C * FG)))) return rc;
+    if (d->gu.patience > 0 && ((rc = gen_alloc(d, &n.gu_last, C * FG)) || (rc = gen_alloc(d, &n.gu_best, C * FG)) || (rc = gen_alloc(d, &n.gu_since, C * FG)) || (rc = gen_alloc(d, &n.gu_gave, C * V)))) return rc;
     if (d->llr_coded && (rc = gen_alloc(d, &n.ybits, C * d->N * V))) return rc;
     if (d->has_synd && (rc = gen_alloc(d, &n.synd, C * d->M * V))) return rc;
     if (d->llr_coded && d->has_erase && (rc = gen_alloc(d, &n.ebits, C * d->N * V))) return rc;
@@ -937,7 +977,8 @@ static int compact(qldpc_decoder *d, int active_frames)
     hipLaunchKernelGGL(qk_compact_scan, dim3(1), dim3(256), 0, d->stream, d->d_gcount, d->d_goff, o.G);
     hipLaunchKernelGGL((qk_compact_scatter<V>), dim3((unsigned)o.G), dim3(64), 0, d->stream, o.done, d->d_goff, n.src);
     hipLaunchKernelGGL((qk_compact_fill<V>), dim3((unsigned)Gn), dim3(64), 0, d->stream, n.src, d->d_goff + o.G, o.origin, n.origin, o.fmag, n.fmag, o.fnch, n.fnch,
-                       o.depth, n.depth, n.iters, n.done, n.unsat, d->cfg.n_ite, d->N);
+                       o.depth, n.depth, n.iters, n.done, n.unsat, d->cfg.n_ite, d->N, qk_giveup{nullptr, o.gu_last, o.gu_best, o.gu_since, o.gu_gave, nullptr, 0},
+                       qk_giveup{nullptr, n.gu_last, n.gu_best, n.gu_since, n.gu_gave, nullptr, 0});
     LAUNCHCHK();
     if (d->llr_coded) hipLaunchKernelGGL((qk_compact_ballots<V>), dim3((unsigned)((d->N + 64 * QK_WAVES - 1) / (64 * QK_WAVES)), (unsigned)Gn), dim3(QK_THREADS), 0, d->stream, o.ybits, n.ybits, n.src, d->N);
     if (d->has_synd) hipLaunchKernelGGL((qk_compact_ballots<V>), dim3((unsigned)((d->M + 64 * QK_WAVES - 1) / (64 * QK_WAVES)), (unsigned)Gn), dim3(QK_THREADS), 0, d->stream, o.synd, n.synd, n.src, d->M);
@@ -982,6 +1023,7 @@ template <int V>
 static int early_exit_launch(qldpc_decoder *d, int ite_done)
 {
     int rc;
+    if (d->gu.patience > 0) return (rc = synd_count_pass<V>(d)) ? rc : status_count_pass<V>(d, ite_done);
     if ((rc = synd_pass<V>(d, d->d_sgn, 1)) || (rc = status_pass<V>(d, ite_done))) return rc;
     return QLDPC_OK;
 }
@@ -1196,7 +1238,10 @@ static int run_begin(qldpc_decoder *d)
     d->live_lanes = 0;
     {
         prof_scope ps(d, KS_STATUS, 0.0);
-        hipLaunchKernelGGL((qk_status_init<V>), dim3((unsigned)d->G), dim3(64), 0, d->stream, d->d_unsat, d->d_done, d->d_depth, d->d_iters, d->n_frames, d->cfg.n_ite, d->d_work, d->d_active);
+        if (d->gu.patience > 0)
+            hipLaunchKernelGGL((qk_status_init_count<V>), dim3((unsigned)d->G), dim3(64), 0, d->stream, d->d_unsat, d->d_done, d->d_depth, d->d_iters, d->n_frames, d->cfg.n_ite, d->d_work, d->d_active, d->gu);
+        else
+            hipLaunchKernelGGL((qk_status_init<V>), dim3((unsigned)d->G), dim3(64), 0, d->stream, d->d_unsat, d->d_done, d->d_depth, d->d_iters, d->n_frames, d->cfg.n_ite, d->d_work, d->d_active);
         LAUNCHCHK();
     }
     return QLDPC_OK;
@@ -1495,6 +1540,7 @@ extern "C" int qldpc_gang_create(qldpc_decoder *const *members, int n, qldpc_gan
         else if (d->V != 1) why = "frame groups are not 64 wide (frames_per_lane != 1)";
         else if (d->compact_mode != 2) why = "active-frame compaction is enabled";
         else if (d->chain || d->cfg.layer_chain == 1) why = "the one-launch sweep (layer_chain) is in use";
+        else if (d->gu.patience > 0) why = "giveup_patience is set (a gang has no give-up rule: create the member with giveup_patience = 0)";
         if (why) { qldpc_set_error("qldpc_gang_create: member %d: %s", i, why); return QLDPC_EUNSUPPORTED; }
         if (d->device != members[0]->device) { qldpc_set_error("qldpc_gang_create: member %d is on device %d, member 0 on device %d", i, d->device, members[0]->device); return QLDPC_EINVAL; }
         if (d->cfg.n_ite != members[0]->cfg.n_ite || !d->cfg.enable_syndrome != !members[0]->cfg.enable_syndrome) {
@@ -1993,6 +2039,36 @@ extern "C" int qldpc_fetch_status_dev(qldpc_decoder *d, int *d_iters, int *d_ok)
         LAUNCHCHK();
         return (int)QLDPC_OK;
     });
+}
+
+/* per frame: 1 if the run gave the frame up, its syndrome weight at its last test and the smallest one it showed (qldpc.h) */
+extern "C" int qldpc_fetch_giveup_dev(qldpc_decoder *d, int *d_gave, int *d_last_weight, int *d_best_weight)
+{
+    if (!d) return QLDPC_EINVAL;
+    if (d->gu.patience <= 0) { qldpc_set_error("qldpc_fetch_giveup_dev: the decoder counts no syndrome weights: create it with giveup_patience >= 1"); return QLDPC_EUNSUPPORTED; }
+    int rc = need_ran(d, "qldpc_fetch_giveup_dev");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) -> int {
+        dim3 gs((unsigned)((n_slots + 255) / 256));
+        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_giveup_out<v()>), gs, dim3(256), 0, d->stream, d->gu, d_gave, d_last_weight, d_best_weight, n_slots, origin, fin); });
+        LAUNCHCHK();
+        return (int)QLDPC_OK;
+    });
+}
+
+/* frames given up by every run since the decoder was created: qk_status_count adds them up on the device.  Synchronises the stream. */
+extern "C" int qldpc_giveup_total(qldpc_decoder *d, uint64_t *frames)
+{
+    if (!d || !frames) return QLDPC_EINVAL;
+    *frames = 0;
+    if (d->gu.patience <= 0) return QLDPC_OK;
+    HIPCHK(hipSetDevice(d->device));
+    unsigned long long n = 0;
+    HIPCHK(hipMemcpyAsync(&n, d->gu.total, sizeof(n), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    *frames = n;
+    return QLDPC_OK;
 }
 
 /* the a-posteriori rows of the last run, frame-interleaved [G][N][FG] floats, where they lie or after the pass that makes them (FRAMES engine) */

@@ -16,6 +16,7 @@
 #include "qldpc_kernels.h"
 #include "qldpc_kernels_i8.h"
 #include "qldpc_kernels_gang.h"
+#include "qldpc_kernels_giveup.h"
 
 enum { KS_CN = 0, KS_VN, KS_LAYER, KS_SYND, KS_STATUS, KS_LOAD, KS_FETCH, KS_VLAYER, KS_LAYER_REMAP, KS_COMPACT_ROWS, KS_LAYER_GANG, KS_COUNT };
 static const char *const ks_names[KS_COUNT] = {"cn_update", "vn_update", "layer_update", "syndrome", "status", "load", "fetch", "vn_vlayer", "layer_update_remap", "compact_rows", "layer_update_gang"};
@@ -44,6 +45,7 @@ struct gen_state {
     int *depth, *iters, *origin, *src;   /* origin[slot] = frame index in the caller's batch (-1: padding); src[slot] = slot in the previous generation */
     float *fmag; int *fnch;
     float *llr; uint32_t *llr8;          /* channel LLR rows in this generation's layout (NULL with coded LLRs, and in a layered run: not read after var_nodes = Y_N) */
+    int *gu_last, *gu_best, *gu_since; u64 *gu_gave;   /* give-up state of this generation's frames (NULL with giveup_patience = 0) */
     float *post, *msg;                   /* layered schedule: posteriors and messages / check state of this generation (flooding: NULL past generation 0, its arrays are re-used in place) */
 };
 #define QLDPC_MAX_GENS 6
@@ -92,6 +94,9 @@ struct qldpc_decoder {
     int *h_active, *h_active_dev;    /* mapped pinned memory {groups, frames, sequence number} and its device address: qk_status reports, the host spins */
     int poll_seq;
     unsigned long long *d_work;      /* group-iterations executed in the current run (qk_status) */
+    /* cfg.giveup_patience > 0 (qldpc_kernels_giveup.h): the current generation's give-up state; gu.weight [G0][FG] serves every generation.  All NULL with
+     * the option off, and the run launches qk_syndrome / qk_status / qk_status_init as ever */
+    qk_giveup gu;
     /* active-frame compaction: generations of the per-frame state; the d_* pointers above and G are the CURRENT generation's */
     int G0;
     std::vector<gen_state> gens;     /* [0] aliases the base arrays */

@@ -973,6 +973,26 @@ __global__ __launch_bounds__(256) void qk_syndrome(const u64 *__restrict__ mask,
     }
 }
 
+/* What lane 0 of every workgroup of a status pass ends with.  all: no frame of the group is left to decode; was_all: that was so before this pass;
+ * left: the frames still to decode. */
+__device__ __forceinline__ void qk_status_report(bool all, bool was_all, int left, int G, int *__restrict__ active_groups, unsigned long long *__restrict__ work,
+                                                 volatile int *__restrict__ host_report, int seq)
+{
+    /* active_groups[0] = groups with unconverged frames, [1] = those frames; work += 1 per group that ran this iteration */
+    if (!all) { atomicAdd(active_groups, 1); atomicAdd(active_groups + 1, left); }
+    if (!was_all) atomicAdd(work, 1ull);
+    /* the workgroup that finishes last hands the two counts to the host through mapped pinned memory (the host spins on the sequence
+     * word: no copy, no stream synchronisation in the early-exit loop) and clears them for the next pass */
+    __threadfence();
+    if (atomicAdd(active_groups + 2, 1) == G - 1) {
+        const int a0 = atomicExch(active_groups, 0), a1 = atomicExch(active_groups + 1, 0);
+        atomicExch(active_groups + 2, 0);
+        host_report[0] = a0; host_report[1] = a1;
+        __threadfence_system();
+        __hip_atomic_store(const_cast<int *>(host_report) + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 /* per-frame bookkeeping after a syndrome pass: AFF3CT's cur_syndrome_depth logic, done bits,
  * iteration counts; clears unsat for the next pass; counts groups still active. */
 template <int V>
@@ -1006,26 +1026,12 @@ __global__ void qk_status(u64 *__restrict__ unsat, u64 *__restrict__ done, int *
         left += __popcll(~nd);
         if (lane == 0) { done[(size_t)g * V + j] = nd; unsat[(size_t)g * V + j] = 0; }
     }
-    /* active_groups[0] = groups with unconverged frames, [1] = those frames; work += 1 per group that ran this iteration */
-    if (lane == 0 && !all) { atomicAdd(active_groups, 1); atomicAdd(active_groups + 1, left); }
-    if (lane == 0 && !was_all) atomicAdd(work, 1ull);
-    /* the workgroup that finishes last hands the two counts to the host through mapped pinned memory (the host spins on the sequence
-     * word: no copy, no stream synchronisation in the early-exit loop) and clears them for the next pass */
-    if (lane == 0) {
-        __threadfence();
-        if (atomicAdd(active_groups + 2, 1) == G - 1) {
-            const int a0 = atomicExch(active_groups, 0), a1 = atomicExch(active_groups + 1, 0);
-            atomicExch(active_groups + 2, 0);
-            host_report[0] = a0; host_report[1] = a1;
-            __threadfence_system();
-            __hip_atomic_store(const_cast<int *>(host_report) + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    if (lane == 0) qk_status_report(all, was_all, left, G, active_groups, work, host_report, seq);
 }
 
 template <int V>
-__global__ void qk_status_init(u64 *__restrict__ unsat, u64 *__restrict__ done, int *__restrict__ depth, int *__restrict__ iters,
-                               int n_frames, int n_ite, unsigned long long *__restrict__ work, int *__restrict__ active_groups)
+__device__ __forceinline__ void qk_status_init_body(u64 *__restrict__ unsat, u64 *__restrict__ done, int *__restrict__ depth, int *__restrict__ iters,
+                                                    int n_frames, int n_ite, unsigned long long *__restrict__ work, int *__restrict__ active_groups)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) { *work = 0ull; active_groups[0] = 0; active_groups[1] = 0; active_groups[2] = 0; }
     constexpr int FG = 64 * V;
@@ -1040,8 +1046,14 @@ __global__ void qk_status_init(u64 *__restrict__ unsat, u64 *__restrict__ done, 
         if (lane == 0) { done[(size_t)g * V + j] = pad; unsat[(size_t)g * V + j] = 0; }
     }
 }
+template <int V>
+__global__ void qk_status_init(u64 *__restrict__ unsat, u64 *__restrict__ done, int *__restrict__ depth, int *__restrict__ iters,
+                               int n_frames, int n_ite, unsigned long long *__restrict__ work, int *__restrict__ active_groups)
+{
+    qk_status_init_body<V>(unsat, done, depth, iters, n_frames, n_ite, work, active_groups);
+}
 
-/* ok[f] = !(unsat bit) after a syndrome pass over the hard ballots; iters copied out */
+/* ok[f] =!(unsat bit) after a syndrome pass over the hard ballots; iters copied out */
 /*
  * Where slot f of a generation belongs in the caller's batch, or -1 if this generation does not hold the frame's result:
  * origin == NULL: slot f is frame f (generation 0); final_mask (the generation's done words) != NULL: only frames that

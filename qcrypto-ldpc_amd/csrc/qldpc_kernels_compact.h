@@ -8,7 +8,7 @@
  *
  *   plan     : src[d] = slot (frame position g*FG + lane*V + j) in the old generation that moves to slot d of the new one,
  *              active frames in slot order (qk_compact_count / _scan / _scatter / _fill); origin[d] = index of the frame
- *              in the caller's batch; the small per-frame arrays (|LLR|, shortening length, syndrome depth) move with it
+ *              in the caller's batch; the small per-frame arrays (|LLR|, shortening length, syndrome depth, the give-up state) move with it
  *   ballots  : the received-bit ballots (coded LLRs) and the target-syndrome ballots are re-dealt bit by bit
  *   rows     : an LLR array (float or 8-bit), when the decoder reads one, is gathered into the new layout
  *   messages : NOT copied.  The next check-node pass reads var_to_chk through src[] (REMAP variants of the check kernels:
@@ -36,6 +36,7 @@
 #define QLDPC_KERNELS_COMPACT_H
 
 #include "qldpc_kernels.h"
+#include "qldpc_kernels_giveup.h"
 
 /* gcount[g] = frames of group g still active (done is [G][V], bit = lane) */
 template <int V>
@@ -90,13 +91,14 @@ __global__ __launch_bounds__(64) void qk_compact_scatter(const u64 *__restrict__
  * per new slot: padding (d >= total) gets src = -1 and its done bit set; origin / |LLR| / shortening / depth follow the frame;
  * iteration counts start at n_ite (the value of a frame that never converges), unsat words are cleared.
  * origin_old == NULL: the old generation is the caller's order itself (slot f = frame f).
+ * Give-up on (gu_new.best != NULL): last / best / since follow the frame as depth does, nobody has been given up in the new generation yet.
  */
 template <int V>
 __global__ __launch_bounds__(64) void qk_compact_fill(int *__restrict__ src, const int *__restrict__ goff_total, const int *__restrict__ origin_old,
                                                       int *__restrict__ origin_new, const float *__restrict__ fmag_old, float *__restrict__ fmag_new,
                                                       const int *__restrict__ fnch_old, int *__restrict__ fnch_new, const int *__restrict__ depth_old,
                                                       int *__restrict__ depth_new, int *__restrict__ iters_new, u64 *__restrict__ done_new,
-                                                      u64 *__restrict__ unsat_new, int n_ite, int N)
+                                                      u64 *__restrict__ unsat_new, int n_ite, int N, qk_giveup gu_old, qk_giveup gu_new)
 {
     constexpr int FG = 64 * V;
     const int g = blockIdx.x, lane = threadIdx.x;
@@ -110,9 +112,10 @@ __global__ __launch_bounds__(64) void qk_compact_fill(int *__restrict__ src, con
         origin_new[d] = pad ? -1 : (origin_old ? origin_old[s] : s);
         if (fmag_new) { fmag_new[d] = pad ? 1.0f : fmag_old[s]; fnch_new[d] = pad ? N : fnch_old[s]; }
         depth_new[d] = pad ? 0 : depth_old[s];
+        if (gu_new.best) { gu_new.last[d] = pad ? 0 : gu_old.last[s]; gu_new.best[d] = pad ? -1 : gu_old.best[s]; gu_new.since[d] = pad ? 0 : gu_old.since[s]; }
         iters_new[d] = n_ite;
         const u64 padmask = __ballot(pad);
-        if (lane == 0) { done_new[(size_t)g * V + j] = padmask; unsat_new[(size_t)g * V + j] = 0; }
+        if (lane == 0) { done_new[(size_t)g * V + j] = padmask; unsat_new[(size_t)g * V + j] = 0; if (gu_new.best) gu_new.gave[(size_t)g * V + j] = 0; }
     }
 }
 

@@ -1321,6 +1321,11 @@ static int mc_blind_args(const qldpc_mc *mc, const qldpc_mc_blind_cfg *cfg)
                         "create it with compact = 2", mc->dec->cfg.compact);
         return QLDPC_EUNSUPPORTED;
     }
+    if (mc->dec->gu.patience > 0 && !mc->dec->freeze) {      /* a frame given up asks with the posteriors it stopped at: exact only with frozen messages */
+        qldpc_set_error("mc_blind: the decoder gives frames up (giveup_patience = %d) and lets their messages run on, so the posteriors a failed frame asks with "
+                        "are not the ones it stopped at: create it with freeze_messages = 1", mc->dec->gu.patience);
+        return QLDPC_EUNSUPPORTED;
+    }
     return QLDPC_OK;
 }
 

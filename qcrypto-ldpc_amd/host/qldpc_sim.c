@@ -50,6 +50,10 @@
  *                      the sums, the decodes per frame and the efficiency f = (N - K + asked / frames) / (K h2(ber)); -E as the stop rule of the input;
  *                      the decoder is created with compact = 2; -A, -X, -W and -w do not apply)]
  *                  [-c scale (with -Q 8: quantiser steps per LLR unit, default 8; 1 for LLRs that are integers already, as -A gives them)]
+ *                  [-g patience (give a frame up once its syndrome weight has not reached a new minimum for `patience` syndrome tests in a row,
+ *                      qldpc_decoder_cfg.giveup_patience; flooding and -l, needs the syndrome test; on the host loop and with -D.  Every row -- with -B
+ *                      the `# blind` line -- is followed by a `# given up` line with the frames given up in the decodes of that row.  With -D -B the
+ *                      decoder is created with freeze_messages = 1, which the rounds ask for, and the head of the table says so)]
  */
 #include <math.h>
 #include <stdint.h>
@@ -95,6 +99,8 @@ static double ebno_db = 0.0, awgn_rmax = 3.0, quant_scale = 0.0;
 static int strata = 0, w_lo = 0, w_hi = 0, w_step = 1;      /* -w */
 static double design_qber = 0.0;
 static int blind = 0, ask_bits = 0, max_rounds = 0;      /* -B */
+static int giveup = 0;      /* -g */
+static uint64_t gave_before = 0;
 static double parity_ber = 0.0;      /* > 0: the disclosed parity bits are themselves wrong with this probability (main.cpp (test effect of dirty parities)) */
 static double target_eff = 0.0;      /* > 0: puncture parity bits up to min_cr(ber, f), as BS/src/main.cpp:235-333 does */
 static const char *alist = NULL, *qc = NULL, *rule_name = "NMS", *g_method = NULL, *pattern_out = NULL;
@@ -115,6 +121,18 @@ static void row(const char *ep, uint64_t fra, uint64_t be, uint64_t fe, double t
 }
 static void row_f(double ep, uint64_t fra, uint64_t be, uint64_t fe, double thr_frames, double sec) { char s[64]; snprintf(s, sizeof(s), "%8.4f", ep); row(s, fra, be, fe, thr_frames, sec); }
 static void row_d(int ep, uint64_t fra, uint64_t be, uint64_t fe, double thr_frames, double sec) { char s[64]; snprintf(s, sizeof(s), "%8d", ep); row(s, fra, be, fe, thr_frames, sec); }
+
+/* -g: the `# given up` line of a row: the frames given up since the line before */
+static int gave_line(double ber)
+{
+    if (!giveup) return 0;
+    uint64_t now = 0;
+    const int rc = qldpc_giveup_total(dec, &now);
+    if (rc) return die("giveup_total", rc);
+    printf("# ber %.4f: given up %llu frames (patience %d)\n", ber, (unsigned long long)(now - gave_before), giveup);
+    gave_before = now;
+    return 0;
+}
 
 /* parity_bits_to_punct(INFO_B, TTL_B, GOAL_CR) with GOAL_CR = min_cr(QBER, EFF) (BS/src/main.cpp:29,34,280), at most all the parity bits, and its
  * lines.  Where the count is negative, the mother code's rate being above the goal already: puncture nothing, or with `skip` return -1. */
@@ -143,7 +161,7 @@ static int write_pattern(double ber, int n_punct, const int *vn, long long fe)
 static int parse(int argc, char **argv)
 {
     int opt;
-    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:u:c:w:B:DRWlvnz")) != -1) {
+    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:u:c:w:B:g:DRWlvnz")) != -1) {
         switch (opt) {
         case 'N': N = atoi(optarg); break;
         case 'K': K = atoi(optarg); break;
@@ -172,6 +190,7 @@ static int parse(int argc, char **argv)
         case 'w': { const int got = sscanf(optarg, "%d:%d:%d:%lf", &w_lo, &w_hi, &w_step, &design_qber); if (got != 3 && got != 4) return usage("-w lo:hi:step[:design_qber]"); strata = 1; break; }
         case 'B': if (sscanf(optarg, "%d:%d", &ask_bits, &max_rounds) != 2) return usage("-B ask:rounds"); blind = 1; break;
         case 'c': quant_scale = atof(optarg); break;
+        case 'g': giveup = atoi(optarg); break;
         case 'o': pattern_out = optarg; break;
         case 'G': g_method = optarg; break;      /* p.G_method (VAR/main.cpp (alist-v1.0.1):135): IDENTITY | LU_DEC; QC = Encoder_LDPC_from_QC ((qc):145) */
         case 'l': layered = 1; break;
@@ -199,6 +218,8 @@ static int parse(int argc, char **argv)
     if ((awgn || zero_source) && !on_device) return usage("qldpc_sim: -A and -z belong to the loop on the device and need -D");
     if (awgn && search_x) return usage("qldpc_sim: -A does not run with the pattern search (-X)");
     if (awgn_punct && !awgn) return usage("qldpc_sim: -u needs -A");
+    if (giveup < 0) return usage("qldpc_sim: -g patience with patience >= 1 (0 = off)");
+    if (giveup && (!synd || layered == 2)) return usage("qldpc_sim: -g works on the syndrome tests of the flooding and the horizontal-layered (-l) schedule: drop -n / -v");
     return 0;
 }
 
@@ -223,10 +244,14 @@ static int setup(void)
     cfg.msg_dtype = msg_bits == 16 ? 1 : (msg_bits == 8 ? 2 : 0);      /* 16: binary16 message storage; 8: fixed-point min-sum */
     cfg.quant_scale = (float)quant_scale;
     if (blind) cfg.compact = 2;      /* the select of the weakest VNs needs every frame's posteriors: no active-frame compaction */
+    cfg.giveup_patience = giveup;
+    if (giveup && blind) cfg.freeze_messages = 1;      /* a frame given up asks with the posteriors it stopped at */
     if ((rc = qldpc_decoder_create(H, K, pos, &cfg, &dec))) return die("decoder", rc);
 
     printf("# * libqldpc %d on HIP device 0; Decoder_LDPC_BP_%s_Update_rule_%s (param %g), n_ite %d, syndrome %d, %d-bit messages\n", qldpc_version(),
            layered == 2 ? "vertical_layered" : (layered ? "horizontal_layered" : "flooding"), rule_name, (double)param, n_ite, synd, msg_bits);
+    if (giveup) printf("#    ** frames are given up after %d syndrome tests without a new minimum of the syndrome weight%s\n", giveup,
+                       blind ? " (-B: decoder created with freeze_messages = 1)" : "");
     printf("#    ** Info. bits (K) = %d\n#    ** Frame size (N) = %d\n#    ** Code rate  (R) = %f\n#    ** max CN degree   = %d\n", K, N, (double)K / N, qldpc_code_max_cn_degree(H));
     printf("#    ** Est. QKD Key Rate After Priv Amp = %f\n", (double)(K - (N - K)) / (double)K);
     printf("# %8s | %8s | %8s | %8s | %9s | %9s | %10s\n", "EP", "FRA", "BE", "FE", "BER", "FER", "SIM_THR");
@@ -407,6 +432,7 @@ static int mode_blind(void)
         printf("# blind: %llu frames, %llu open, %llu key bits disclosed, %llu decodes in %llu launches = %.4f per frame; FER %.3e; f = %.4f\n",
                (unsigned long long)b.frames, (unsigned long long)b.open, (unsigned long long)b.disclosed, (unsigned long long)b.decodes, (unsigned long long)b.launches,
                b.frames ? (double)b.decodes / (double)b.frames : 0.0, b.frames ? (double)b.frame_errors / (double)b.frames : 0.0, f);
+        if (gave_line(ber)) return 1;
         fflush(stdout);
     }
     free(rows);
@@ -421,6 +447,7 @@ static int mode_rows(void)
         const int rc = qldpc_mc_run(mc, ber, 0, MAX_FRAMES, max_fe, &r);
         if (rc) return die("mc_run", rc);
         row_f(ber, r.frames, r.bit_errors, r.frame_errors, (double)r.frames, r.decode_ms * 1e-3);
+        if (gave_line(ber)) return 1;
         fflush(stdout);
     }
     return 0;
@@ -480,6 +507,7 @@ static int run_host(void)
             free(best_pat);
         }
         row_f(ber, (uint64_t)fra, (uint64_t)be, (uint64_t)fe, (double)fra, t_dec);
+        if (gave_line(ber)) return 1;
         fflush(stdout);
     }
     free(par_pos); free(ref_bits); free(enc_bits); free(dec_bits); free(llr);
