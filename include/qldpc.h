@@ -34,6 +34,7 @@
  *                                         qcrypto-ldpc_amd/host/ldpc_reconcile.c (packet handlers, cascade fallback, batched ingest)
  *   qldpc_privamp*                        the hash loop of privAmp_doPrivAmp         subcomponents/priv_amp.c:190-218
  *   qldpc_toeplitz*                       (not in the reference) Toeplitz hashing, the sound replacement of that loop
+ *   qldpc_qber_* / _recon_estimate_blocks (not in the reference, which samples disclosed bits: subcomponents/qber_estim.c) the QBER out of the parity message
  *   qldpc_mc_*                            the simulation loop itself: source, encoder, BSC, decoder, Monitor_BFER   BS/src/main.cpp:335-393
  *   qldpc_mc_search / _patterns_dev       the puncture-pattern search around it: shuffle, erase, first FER = 0 / n  BS/src/main.cpp:235-411
  *   qldpc_mc_sweep                        the BER loop around both, with its puncture count per BER                BS/src/main.cpp:233-272
@@ -563,11 +564,83 @@ int qldpc_recon_decode_blind(qldpc_recon *r, int n, uint32_t *const *key_words, 
 /* Alice's answer to a request for key bits (blind reconciliation): bit[i] = bit pos[i] of her key.  Host only.  A position outside
  * 0 .. key_bits - 1: QLDPC_EINVAL. */
 int qldpc_recon_disclose_host(const uint32_t *key_words, int key_bits, const int *pos, int n, uint8_t *bit);
+/*
+ * Bob's QBER estimate of every block out of its parity message (qldpc_qber_* below), before anything is decoded: the blocks are validated, grouped by
+ * code and assembled into frames exactly as qldpc_recon_decode_blocks does it (key VNs channel, shortened past key_bits, disclosed parity pinned,
+ * punctured parity erased), and each group goes through the estimator of its session entry (one per entry, created with the entry when the session
+ * preloads, else at the first call that needs it) in launches of up to max_blocks frames.  qber_out[i] = the estimate of block i (0 for a block with
+ * no informative check, or whose header does not match: those are left out), usable as the `qber` of the decode calls; counts_out (optional) =
+ * [n][QLDPC_QBER_MAX_DEGREE + 1][2] uint32, block i's counts by effective degree, rows past its code's largest check degree zero; *pool_qber_out
+ * (optional) = the estimate from the counts of all blocks of the call summed, whatever their codes (0 if there is none).  Keys are not touched; the
+ * grid is the default one of qldpc_qber_cfg_default.  The call returns when the results are in place.
+ */
+int qldpc_recon_estimate_blocks(qldpc_recon *r, int n, const uint32_t *const *key_words, const int *key_bits, const qldpc_recon_msg *msgs,
+                                const uint32_t *const *parity_words, float *qber_out, uint32_t *counts_out, float *pool_qber_out);
 uint32_t qldpc_crc32_words(const uint32_t *words, int n_bits);
 /* The same CRC-32 the way the device verification computes it (rk_verify / rk_crc in qldpc_recon.hip): `lanes` (a power of two) equal
  * chunks, each run through the byte-wise recurrence from a zero register, folded pairwise with x^len multipliers mod the CRC polynomial,
  * start value and final inversion applied at the end.  Host mirror for tests: equals qldpc_crc32_words for every length. */
 uint32_t qldpc_crc32_words_chunked(const uint32_t *words, int n_bits, int lanes);
+
+/* ------------------------------------------------------------------ QBER from the syndrome weight ---- */
+/*
+ * Bob's own estimate of a frame's QBER out of the parity message, at no extra disclosed bit and before the first BP iteration (no reference counterpart:
+ * the reference samples disclosed bits, subcomponents/qber_estim.c).  The rule is stated once, in csrc/qldpc_qber_core.h:
+ *
+ *   A VN of a frame is KNOWN-EXACT (its known bit is set -- value from the value row, known wins over erased --, or class QLDPC_VN_PINNED, or class
+ *   QLDPC_VN_CHANNEL at index >= n_channel[f]), ERASED (class QLDPC_VN_PUNCTURED or its erase bit set, and not known) or NOISY (the rest): what
+ *   qldpc_load_bits_short_dev, qldpc_load_erasures_dev and qldpc_load_known_dev mean.  A check is INFORMATIVE iff none of its VNs is erased; its
+ *   effective degree d = the number of its noisy VNs, its outcome u = s_c ^ XOR of the values of all its VNs (s_c = 0 without a syndrome row).
+ *   counts[f][d][0] = informative checks of frame f with effective degree d, counts[f][d][1] = those with u = 1; d = 0 .. D = qldpc_code_max_cn_degree
+ *   (row 0: an unsatisfied check without a noisy VN is an inconsistency; the score ignores the row).
+ *   With d noisy neighbours of flip probability q a check comes out 1 with p_d(q) = (1 - (1 - 2 q)^d) / 2.  On the grid q_k = q_lo (q_hi / q_lo)^(k / (n_grid - 1))
+ *   the score is S_k = SUM_{d >= 1} u_d L1[d][k] + (n_d - u_d) L0[d][k] in int64 with L1 = llround(log p_d(q_k) 2^24), L0 = llround(log(1 - p_d(q_k)) 2^24)
+ *   (int32 tables built on the host in double; the device takes no logarithm).  The estimate is the smallest k with maximal S_k, a full scan: integer scores
+ *   make host and device agree exactly.  A frame without an informative check of degree >= 1: index -1, QBER 0, |LLR| 0; every check satisfied: k = 0.
+ *   The POOLED estimate of a call is the same argmax over the sum of its frames' counts.
+ *
+ * A check next to an erased VN is left out (runs of checks across a punctured parity VN are not merged into one observation); noisy disclosed parity,
+ * table / soft channels and estimates from a decoder's ballots mid-run are not built.
+ *
+ * qldpc_qber_create: QLDPC_EINVAL for n_grid outside 2 .. 1 024, q_lo < 1e-6, q_lo >= q_hi, q_hi >= 0.5, max_frames outside 1 .. 65 535; QLDPC_EUNSUPPORTED
+ * for a check degree above QLDPC_QBER_MAX_DEGREE or max_frames x M >= 2^35 (the pooled score could overflow); QLDPC_ENODEV without a device.
+ * checks_per_block: checks a workgroup of the counting kernel covers (256 threads, a thread per check and pass; 0 = chosen per call from the frame count) -- tests
+ * force many partial histograms per frame with it.  The counting kernel stages a frame's rows in LDS while 3 ceil(N / 32) words fit (N up to about
+ * 390 000) and gathers from memory above; QLDPC_QBER_STAGE=0 in the environment at creation takes the memory path whatever the size (tests, A/B).
+ */
+#define QLDPC_QBER_MAX_DEGREE 63
+typedef struct qldpc_qber qldpc_qber;
+typedef struct qldpc_qber_cfg {
+    int device;
+    int max_frames;        /* capacity of one call */
+    int n_grid;            /* 256 */
+    float q_lo, q_hi;      /* 0.001, 0.25: the clamp qldpc_recon_plan applies */
+    int checks_per_block;  /* 0 = auto */
+} qldpc_qber_cfg;
+void   qldpc_qber_cfg_default(qldpc_qber_cfg *cfg);
+int    qldpc_qber_create(const qldpc_code *code, const qldpc_qber_cfg *cfg, qldpc_qber **out);
+void   qldpc_qber_free(qldpc_qber *est);
+size_t qldpc_qber_device_bytes(const qldpc_qber *est);
+int    qldpc_qber_set_stream(qldpc_qber *est, void *hip_stream);      /* NULL = the null stream */
+/* q[n_grid] / llr[n_grid] (either may be NULL) = the grid and qldpc_bsc_llr of it; returns n_grid */
+int    qldpc_qber_grid(const qldpc_qber *est, float *q, float *llr);
+/*
+ * Asynchronous on the estimator's stream.  Inputs as the loads take them: d_bits[n_frames][ceil(N/32)], d_vn_class[N] (NULL = all channel), d_n_channel[n_frames]
+ * (NULL = N), d_synd_bits[n_frames][ceil(M/32)] (NULL = zero syndrome), d_erase_bits / d_known_bits / d_value_bits [n_frames][ceil(N/32)] (NULL = none; known
+ * needs value).  Outputs, each may be NULL: d_counts[n_frames][D + 1][2] uint32 (cleared on the stream first), d_index[n_frames] (grid index or -1),
+ * d_qber[n_frames] (q_k), d_llr_mag[n_frames] (qldpc_bsc_llr(q_k): can be handed to qldpc_load_bits_dev / _short_dev on the same stream),
+ * d_pool_counts[D + 1][2] uint64, d_pool_index[1].  An estimator is not re-entrant.  QLDPC_EINVAL: n_frames < 1 or > max_frames.
+ */
+int    qldpc_qber_estimate_dev(qldpc_qber *est, const uint32_t *d_bits, const uint8_t *d_vn_class, const int *d_n_channel, const uint32_t *d_synd_bits,
+                               const uint32_t *d_erase_bits, const uint32_t *d_known_bits, const uint32_t *d_value_bits, int n_frames,
+                               uint32_t *d_counts, int *d_index, float *d_qber, float *d_llr_mag, uint64_t *d_pool_counts, int *d_pool_index);
+/* Host mirrors, no device needed (csrc/qldpc_qber_host.c over the functions the kernels run).  Tables: L1 / L0 [max_degree + 1][n_grid] (row 0 zero),
+ * q / llr [n_grid]; each may be NULL.  Counts of ONE frame: rows of that frame, n_channel its count (N = none), counts[D + 1][2].  Argmax: counts as
+ * uint64 [max_degree + 1][2], *index = the estimate or -1. */
+int    qldpc_qber_table_host(int max_degree, int n_grid, float q_lo, float q_hi, int32_t *L1, int32_t *L0, float *q, float *llr);
+int    qldpc_qber_counts_host(const qldpc_code *code, const uint32_t *bits, const uint8_t *vn_class, int n_channel, const uint32_t *synd,
+                              const uint32_t *erase, const uint32_t *known, const uint32_t *value, uint32_t *counts);
+int    qldpc_qber_argmax_host(const uint64_t *counts, int max_degree, int n_grid, const int32_t *L1, const int32_t *L0, int *index);
 
 /* ------------------------------------------------------------------ privacy amplification ---- */
 /*

@@ -689,6 +689,138 @@ def weakest_host(post, d, cand_bits=None):
     return out[:W], n.value
 
 
+# ---- QBER from the syndrome weight (qldpc_qber_*) -----------------------------------------------
+
+QBER_MAX_DEGREE = 63
+
+
+class QberCfg(C.Structure):
+    _fields_ = [("device", C.c_int), ("max_frames", C.c_int), ("n_grid", C.c_int), ("q_lo", C.c_float), ("q_hi", C.c_float), ("checks_per_block", C.c_int)]
+
+
+_sig("qldpc_qber_cfg_default", None, [C.POINTER(QberCfg)])
+_sig("qldpc_qber_create", C.c_int, [_vp, C.POINTER(QberCfg), C.POINTER(_vp)])
+_sig("qldpc_qber_free", None, [_vp])
+_sig("qldpc_qber_device_bytes", C.c_size_t, [_vp])
+_sig("qldpc_qber_set_stream", C.c_int, [_vp, _vp])
+_sig("qldpc_qber_grid", C.c_int, [_vp, _fp, _fp])
+_sig("qldpc_qber_estimate_dev", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp])
+_sig("qldpc_qber_table_host", C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp, _fp, _fp])
+_sig("qldpc_qber_counts_host", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp])
+_sig("qldpc_qber_argmax_host", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _ip])
+
+
+def qber_table_host(max_degree, n_grid=256, q_lo=0.001, q_hi=0.25):
+    """the grid and score tables of the estimator (qldpc_qber_table_host): -> (L1, L0, q, llr) with L1 / L0 int32 [max_degree + 1, n_grid]
+    (row 0 zero) = round(log p_d(q_k) 2^24) / round(log(1 - p_d(q_k)) 2^24), q / llr float32 [n_grid]"""
+    D, G = int(max_degree), int(n_grid)
+    L1, L0 = np.zeros((max(D, 0) + 1, max(G, 1)), np.int32), np.zeros((max(D, 0) + 1, max(G, 1)), np.int32)
+    q_, llr = np.zeros(max(G, 1), np.float32), np.zeros(max(G, 1), np.float32)
+    _chk(_L.qldpc_qber_table_host(D, G, float(q_lo), float(q_hi), L1.ctypes.data_as(_vp), L0.ctypes.data_as(_vp), q_.ctypes.data_as(_fp), llr.ctypes.data_as(_fp)),
+         "qber_table_host")
+    return L1, L0, q_, llr
+
+
+def qber_counts_host(code, bits, vn_class=None, n_channel=None, syndrome=None, erase=None, known=None, value=None):
+    """the counting kernel's mirror for ONE frame (qldpc_qber_counts_host): packed uint32 rows (bits / erase / known / value: ceil(N/32) words, syndrome:
+    ceil(M/32)), vn_class uint8 [N], n_channel int (None = N) -> counts uint32 [D + 1, 2]"""
+    Wn, Wm = (code.N + 31) // 32, (code.M + 31) // 32
+
+    def row(a, W, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.uint32).ravel()
+        if a.size != W:
+            raise QldpcError(-6, "qber_counts_host: %s has %d words, need %d" % (name, a.size, W))
+        return a
+    b, s, e, k, v = row(bits, Wn, "bits"), row(syndrome, Wm, "syndrome"), row(erase, Wn, "erase"), row(known, Wn, "known"), row(value, Wn, "value")
+    cls = None
+    if vn_class is not None:
+        cls = np.ascontiguousarray(vn_class, dtype=np.uint8).ravel()
+        if cls.size != code.N:
+            raise QldpcError(-6, "qber_counts_host: vn_class has %d entries, N = %d" % (cls.size, code.N))
+    counts = np.zeros((_L.qldpc_code_max_cn_degree(code._h) + 1, 2), np.uint32)
+    p = lambda a: a.ctypes.data_as(_vp) if a is not None else None
+    _chk(_L.qldpc_qber_counts_host(code._h, p(b), p(cls), code.N if n_channel is None else int(n_channel), p(s), p(e), p(k), p(v), p(counts)), "qber_counts_host")
+    return counts
+
+
+def qber_argmax_host(counts, L1, L0):
+    """the argmax kernel's mirror (qldpc_qber_argmax_host): counts [D + 1, 2] (any integer type; a frame's or a pool's) -> grid index, -1 without an
+    informative check of degree >= 1"""
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    a, b = np.ascontiguousarray(L1, dtype=np.int32), np.ascontiguousarray(L0, dtype=np.int32)
+    if c.ndim != 2 or c.shape[1] != 2 or a.shape != b.shape or a.ndim != 2 or a.shape[0] != c.shape[0]:
+        raise QldpcError(-6, "qber_argmax_host: counts [D + 1, 2] and tables [D + 1, n_grid] are required")
+    k = C.c_int(0)
+    _chk(_L.qldpc_qber_argmax_host(c.ctypes.data_as(_vp), c.shape[0] - 1, a.shape[1], a.ctypes.data_as(_vp), b.ctypes.data_as(_vp), C.byref(k)), "qber_argmax_host")
+    return k.value
+
+
+class QberEstimator:
+    """QBER of every frame from the weight of its syndrome, on the device (qldpc_qber_estimate_dev): needs no decoder, reads the packed rows the
+    loads take.  estimate() returns torch tensors; llr_mag can go straight into Decoder.load_bits on the same stream."""
+
+    def __init__(self, code, n_frames, n_grid=256, q_lo=0.001, q_hi=0.25, checks_per_block=0, device=0):
+        cfg = QberCfg()
+        _L.qldpc_qber_cfg_default(C.byref(cfg))
+        cfg.device, cfg.max_frames, cfg.n_grid, cfg.q_lo, cfg.q_hi, cfg.checks_per_block = int(device), int(n_frames), int(n_grid), float(q_lo), float(q_hi), int(checks_per_block)
+        h = _vp()
+        _chk(_L.qldpc_qber_create(code._h, C.byref(cfg), C.byref(h)), "QberEstimator")
+        self._h = h
+        self.code, self.N, self.M, self.D = code, code.N, code.M, _L.qldpc_code_max_cn_degree(code._h)
+        self.max_frames, self.n_grid, self.device = int(n_frames), int(n_grid), int(device)
+        self.q, self.llr = np.zeros(self.n_grid, np.float32), np.zeros(self.n_grid, np.float32)
+        _chk(_L.qldpc_qber_grid(h, self.q.ctypes.data_as(_fp), self.llr.ctypes.data_as(_fp)), "QberEstimator.grid")
+
+    def set_stream(self, stream=None):
+        torch = _torch()
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _chk(_L.qldpc_qber_set_stream(self._h, _vp(s.cuda_stream)), "QberEstimator.set_stream")
+
+    def device_bytes(self):
+        return int(_L.qldpc_qber_device_bytes(self._h))
+
+    def estimate(self, bits, vn_class=None, n_channel=None, syndrome=None, erase=None, known=None, value=None, out=None, index=True, pool=True):
+        """bits / erase / known / value int32 [F, ceil(N/32)], syndrome int32 [F, ceil(M/32)], vn_class uint8 [N], n_channel int32 [F] (device tensors)
+        -> dict(index int32 [F], qber float32 [F], llr_mag float32 [F], counts int32 [F, D + 1, 2], pool_counts int64 [D + 1, 2], pool_index int32 [1]);
+        asynchronous on the estimator's stream.  out = the dict of an earlier call of the same size: its tensors are written again (nothing is
+        allocated); index / pool = False: the per-frame estimates / the pool are not asked for (their tensors are left alone)"""
+        torch = _torch()
+        Wn, Wm = (self.N + 31) // 32, (self.M + 31) // 32
+        F = bits.shape[0]
+
+        def chk(t, W, name):
+            if t is None:
+                return None
+            assert t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() and t.dim() == 2 and tuple(t.shape) == (F, W), name
+            return _vp(t.data_ptr())
+        pb, ps, pe, pk, pv = chk(bits, Wn, "bits"), chk(syndrome, Wm, "syndrome"), chk(erase, Wn, "erase"), chk(known, Wn, "known"), chk(value, Wn, "value")
+        pc = pn = None
+        if vn_class is not None:
+            assert vn_class.is_cuda and vn_class.dtype == torch.uint8 and vn_class.is_contiguous() and vn_class.numel() == self.N
+            pc = _vp(vn_class.data_ptr())
+        if n_channel is not None:
+            assert n_channel.is_cuda and n_channel.dtype == torch.int32 and n_channel.is_contiguous() and n_channel.numel() == F
+            pn = _vp(n_channel.data_ptr())
+        dev = bits.device
+        if out is None:
+            out = dict(index=torch.empty(F, dtype=torch.int32, device=dev), qber=torch.empty(F, dtype=torch.float32, device=dev),
+                       llr_mag=torch.empty(F, dtype=torch.float32, device=dev), counts=torch.empty((F, self.D + 1, 2), dtype=torch.int32, device=dev),
+                       pool_counts=torch.empty((self.D + 1, 2), dtype=torch.int64, device=dev), pool_index=torch.empty(1, dtype=torch.int32, device=dev))
+        assert out["counts"].shape[0] == F
+        ptr = lambda name, on: _vp(out[name].data_ptr()) if on else None
+        _chk(_L.qldpc_qber_estimate_dev(self._h, pb, pc, pn, ps, pe, pk, pv, F, ptr("counts", True), ptr("index", index), ptr("qber", index),
+                                        ptr("llr_mag", index), ptr("pool_counts", pool), ptr("pool_index", pool)), "QberEstimator.estimate")
+        return out
+
+    def __del__(self):
+        try:
+            _L.qldpc_qber_free(self._h)
+        except Exception:
+            pass
+
+
 # ---- reconciliation sessions (engine of the ecd2 LDPC handler) ---------------------------------
 
 class ReconCfg(C.Structure):
@@ -715,6 +847,7 @@ _sig("qldpc_recon_decode_batch", C.c_int, [_vp, C.c_int, _up, C.c_int, _fp, C.PO
 _sig("qldpc_recon_encode_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _fp, C.POINTER(ReconMsg), C.POINTER(_up), _ip])
 _sig("qldpc_recon_decode_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _fp, C.POINTER(ReconMsg), C.POINTER(_up), _ip, _ip, _ip])
 _sig("qldpc_crc32_words", C.c_uint32, [_up, C.c_int])
+_sig("qldpc_recon_estimate_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, C.POINTER(ReconMsg), C.POINTER(_up), _fp, _up, _fp])
 class ReconBlind(C.Structure):
     _fields_ = [("n_known", C.c_int), ("cap", C.c_int), ("pos", _ip), ("bit", C.POINTER(C.c_uint8)), ("n_ask", C.c_int), ("ask", _ip)]
 
@@ -1759,6 +1892,21 @@ class Recon:
         _chk(_L.qldpc_recon_decode_blocks(self._h, n, kp, kb.ctypes.data_as(_ip), qb.ctypes.data_as(_fp), arr, pp, st.ctypes.data_as(_ip),
                                           co.ctypes.data_as(_ip), it.ctypes.data_as(_ip)), "Recon.decode_blocks")
         return st, kws, co, it
+
+    def estimate_blocks(self, keys, key_bits, msgs, parities):
+        """Bob's QBER estimate of every block out of its parity message (qldpc_recon_estimate_blocks), before any decode: returns (qber float32 [n],
+        counts uint32 [n, QBER_MAX_DEGREE + 1, 2], pooled qber over the call); keys are not touched"""
+        n = len(keys)
+        kws = [np.ascontiguousarray(k, dtype=np.uint32) for k in keys]
+        pars = [np.ascontiguousarray(p, dtype=np.uint32) for p in parities]
+        kp = (_up * n)(*[k.ctypes.data_as(_up) for k in kws])
+        pp = (_up * n)(*[p.ctypes.data_as(_up) for p in pars])
+        kb = np.ascontiguousarray(key_bits, dtype=np.int32)
+        arr = (ReconMsg * n)(*msgs)
+        qb, counts, pool = np.zeros(n, np.float32), np.zeros((n, QBER_MAX_DEGREE + 1, 2), np.uint32), C.c_float(0.0)
+        _chk(_L.qldpc_recon_estimate_blocks(self._h, n, kp, kb.ctypes.data_as(_ip), arr, pp, qb.ctypes.data_as(_fp), counts.ctypes.data_as(_up), C.byref(pool)),
+             "Recon.estimate_blocks")
+        return qb, counts, float(pool.value)
 
     def decode_blind(self, keys, key_bits, qber, msgs, parities, known, ask_bits):
         """one round of blind reconciliation (qldpc_recon_decode_blind): decode_blocks with known[i] = (positions, Alice's bits there) pinned;

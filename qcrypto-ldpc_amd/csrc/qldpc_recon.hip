@@ -50,6 +50,8 @@ struct recon_entry {
     stage_set set[2];
     int next_set;
     uint32_t *d_blind;    /* blind rounds (allocated by the first one): known | value | candidate | weakest rows, [4][max_blocks][Wn] */
+    qldpc_qber *qest;     /* qldpc_recon_estimate_blocks: the entry's estimator (with the entry when the session preloads, else at the first such call) */
+    uint32_t *d_est;      /* its outputs: counts [max_blocks][D + 1][2] | QBER [max_blocks] */
 };
 
 /* a lane = one host worker with a compute stream and a copy stream: the rate groups of a call run side by side, one lane each */
@@ -332,9 +334,11 @@ __global__ __launch_bounds__(256) void rk_disclose(const uint32_t *__restrict__ 
 
 static void entry_free(recon_entry &e)
 {
+    qldpc_qber_free(e.qest);
     qldpc_decoder_free(e.dec);
     qldpc_encoder_free(e.enc);
     qldpc_code_free(e.code);
+    (void)hipFree(e.d_est);
     (void)hipFree(e.d_cls); (void)hipFree(e.d_out); (void)hipFree(e.d_iters); (void)hipFree(e.d_ok); (void)hipFree(e.d_blind);
     for (auto &st : e.set) {
         (void)hipFree(st.d_in); (void)hipFree(st.d_res); (void)hipFree(st.d_bits); (void)hipFree(st.d_erase);
@@ -592,6 +596,24 @@ static int build_code(const qldpc_recon_cfg &cfg, int K, int M, qldpc_code **out
     return cfg.peg_depth > 0 ? qldpc_code_ira_peg(N, K, 0.125f, 11, 3, cfg.peg_depth, cfg.seed, out) : qldpc_code_ira(N, K, 0.125f, 11, 3, cfg.seed, out);
 }
 
+/* the estimator of an entry and its output rows (qldpc_recon_estimate_blocks) */
+static int entry_estimator(const qldpc_recon *r, recon_entry &e)
+{
+    if (e.qest) return QLDPC_OK;
+    qldpc_qber_cfg qc;
+    qldpc_qber_cfg_default(&qc);
+    qc.device = r->cfg.device; qc.max_frames = r->cfg.max_blocks;
+    int rc = qldpc_qber_create(e.code, &qc, &e.qest);
+    if (rc) return rc;
+    const size_t bins = 2 * (size_t)(qldpc_code_max_cn_degree(e.code) + 1);
+    if (!e.d_est && hipMalloc((void **)&e.d_est, sizeof(uint32_t) * (size_t)r->cfg.max_blocks * (bins + 1)) != hipSuccess) {
+        qldpc_qber_free(e.qest); e.qest = nullptr;
+        qldpc_set_error("recon: device allocation for the QBER estimator failed");
+        return QLDPC_ENOMEM;
+    }
+    return QLDPC_OK;
+}
+
 static int get_entry(qldpc_recon *r, int K, int M, recon_entry **out, qldpc_code *prebuilt)
 {
     for (auto it = r->cache.begin(); it != r->cache.end(); ++it)
@@ -638,6 +660,7 @@ static int get_entry(qldpc_recon *r, int K, int M, recon_entry **out, qldpc_code
         for (int i = 0; i < K; i++) cls[(size_t)i] = (uint8_t)QLDPC_VN_CHANNEL;
         if (hipMemcpy(e.d_cls, cls.data(), (size_t)N, hipMemcpyHostToDevice) != hipSuccess) rc = QLDPC_EHIP;
     }
+    if (!rc && r->cfg.preload) rc = entry_estimator(r, e);      /* nothing is allocated per block later */
     if (rc) { entry_free(e); return rc; }
     if (r->profiling) qldpc_profile_enable(e.dec, 1);
     r->cache.push_front(e);      /* the cache is trimmed to `keep` entries at the end of the call (cache_trim): nothing in use is evicted */
@@ -736,7 +759,7 @@ static int job_stage(lane_run *L, recon_job &j, hipStream_t cs)
             memcpy(f, c.key[i], sizeof(uint32_t) * (size_t)Wkey);
             h_np[t] = (int)c.msgs[i].n_punct;
             memcpy(h_disc + (size_t)t * Wm, c.parity[i], sizeof(uint32_t) * (size_t)((M - h_np[t] + 31) / 32));
-            h_mag[t] = qldpc_bsc_llr(clamp_qber(c.qber[i]));
+            h_mag[t] = c.qber ? qldpc_bsc_llr(clamp_qber(c.qber[i])) : 0.0f;      /* no QBER yet: qldpc_recon_estimate_blocks */
             h_crc[t] = c.msgs[i].crc32;
         } else {
             /* information word of the mother code: the key, then zeros (shortened positions) */
@@ -1169,6 +1192,87 @@ extern "C" int qldpc_recon_decode_blocks(qldpc_recon *r, int n, uint32_t *const 
     c.bob = true; c.n = n; c.key_bits = key_bits; c.key = key_words; c.qber = qber; c.msgs = msgs; c.parity = parity_words;
     c.status = status; c.corrected = corrected; c.iterations = iterations;
     return run_call(r, c, skip);
+}
+
+/*
+ * The QBER every block's parity message shows (qldpc_qber_estimate_dev on the frames qldpc_recon_decode_blocks would decode): same validation, grouping,
+ * staging and assembly (job_stage), then the entry's estimator in place of the decoder, one job at a time on the first lane.  The pooled estimate is
+ * taken on the host from the counts of all blocks summed by effective degree (the codes of a call differ in their largest check degree).
+ */
+extern "C" int qldpc_recon_estimate_blocks(qldpc_recon *r, int n, const uint32_t *const *key_words, const int *key_bits, const qldpc_recon_msg *msgs,
+                                           const uint32_t *const *parity_words, float *qber_out, uint32_t *counts_out, float *pool_qber_out)
+{
+    if (!r || !key_words || !key_bits || !msgs || !parity_words || !qber_out || n <= 0) return QLDPC_EINVAL;
+    const size_t BINS = 2 * (QLDPC_QBER_MAX_DEGREE + 1);
+    std::vector<char> taken((size_t)n, 0);
+    for (int i = 0; i < n; i++) {
+        if (!key_words[i] || !parity_words[i]) return QLDPC_EINVAL;
+        qber_out[i] = 0.0f;
+        if (check_msg(r, &msgs[i], key_bits[i])) taken[(size_t)i] = 1;
+    }
+    if (counts_out) memset(counts_out, 0, sizeof(uint32_t) * (size_t)n * BINS);
+    if (pool_qber_out) *pool_qber_out = 0.0f;
+    HIPCHK(hipSetDevice(r->cfg.device));
+    recon_call call;
+    memset(&call, 0, sizeof(call));
+    call.bob = true; call.n = n; call.key_bits = key_bits; call.key = const_cast<uint32_t *const *>(key_words); call.msgs = msgs; call.parity = parity_words;
+    lane_run L;
+    L.r = r; L.lane = &r->lane[0]; L.call = &call; L.rc = QLDPC_OK;
+    hipStream_t s = L.lane->stream;
+    const size_t B = (size_t)r->cfg.max_blocks;
+    std::vector<uint64_t> pool(BINS, 0);
+    std::vector<uint32_t> h_est;
+    int rc = QLDPC_OK, max_d = 0;
+    for (int i = 0; i < n && !rc; i++) {
+        if (taken[(size_t)i]) continue;
+        std::vector<int> idx;
+        for (int j = i; j < n; j++)
+            if (!taken[(size_t)j] && msgs[j].code_k == msgs[i].code_k && msgs[j].code_m == msgs[i].code_m) { idx.push_back(j); taken[(size_t)j] = 1; }
+        recon_entry *e;
+        if ((rc = get_entry(r, (int)msgs[i].code_k, (int)msgs[i].code_m, &e)) || (rc = entry_estimator(r, *e))) break;
+        const int D = qldpc_code_max_cn_degree(e->code);
+        const size_t bins = 2 * (size_t)(D + 1);
+        max_d = std::max(max_d, D);
+        if ((rc = qldpc_qber_set_stream(e->qest, (void *)s))) break;
+        for (size_t at = 0; at < idx.size() && !rc; at += B) {
+            recon_job j;
+            j.e = e; j.st = nullptr; j.any_punct = false;
+            j.idx.assign(idx.begin() + (long)at, idx.begin() + (long)std::min(idx.size(), at + B));
+            const int nb = (int)j.idx.size(), Wk = e->K / 32, Wm = (e->M + 31) / 32;
+            if ((rc = job_stage(&L, j, s))) break;
+            int *d_nch = reinterpret_cast<int *>(j.st->d_in + (size_t)nb * (Wk + Wm) + nb);
+            uint32_t *d_counts = e->d_est;
+            float *d_q = reinterpret_cast<float *>(d_counts + B * bins);
+            rc = qldpc_qber_estimate_dev(e->qest, j.st->d_bits, e->d_cls, d_nch, nullptr, j.any_punct ? j.st->d_erase : nullptr, nullptr, nullptr, nb,
+                                         d_counts, nullptr, d_q, nullptr, nullptr, nullptr);
+            if (rc) break;
+            h_est.resize((size_t)nb * (bins + 1));
+            hipError_t he = hipMemcpyAsync(h_est.data(), d_counts, sizeof(uint32_t) * (size_t)nb * bins, hipMemcpyDeviceToHost, s);
+            if (he == hipSuccess) he = hipMemcpyAsync(h_est.data() + (size_t)nb * bins, d_q, sizeof(float) * (size_t)nb, hipMemcpyDeviceToHost, s);
+            if (he == hipSuccess) he = hipStreamSynchronize(s);      /* the staging set's pinned block is free again as well */
+            if (he != hipSuccess) { qldpc_set_error("recon_estimate_blocks: %s", hipGetErrorString(he)); rc = QLDPC_EHIP; break; }
+            for (int t = 0; t < nb; t++) {
+                const int b = j.idx[(size_t)t];
+                memcpy(&qber_out[b], h_est.data() + (size_t)nb * bins + t, sizeof(float));
+                const uint32_t *row = h_est.data() + (size_t)t * bins;
+                if (counts_out) memcpy(counts_out + (size_t)b * BINS, row, sizeof(uint32_t) * bins);
+                for (size_t k = 0; k < bins; k++) pool[k] += row[k];
+            }
+        }
+    }
+    if (rc) (void)hipStreamSynchronize(s);
+    if (!rc && pool_qber_out && max_d > 0) {
+        qldpc_qber_cfg qc;
+        qldpc_qber_cfg_default(&qc);
+        std::vector<int32_t> L1((size_t)(max_d + 1) * (size_t)qc.n_grid), L0(L1.size());
+        std::vector<float> q((size_t)qc.n_grid);
+        int k = -1;
+        rc = qldpc_qber_table_host(max_d, qc.n_grid, qc.q_lo, qc.q_hi, L1.data(), L0.data(), q.data(), nullptr);
+        if (!rc) rc = qldpc_qber_argmax_host(pool.data(), max_d, qc.n_grid, L1.data(), L0.data(), &k);
+        if (!rc && k >= 0) *pool_qber_out = q[(size_t)k];
+    }
+    cache_trim(r);
+    return rc;
 }
 
 /*
