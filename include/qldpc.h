@@ -459,9 +459,9 @@ typedef struct qldpc_recon_cfg {
     float efficiency;      /* f in min_cr(q, f); 1.4                        */
     int n_rates;           /* <= 8                                                               */
     float rates[8];        /* ascending; default {0.5, 0.7, 0.8, 0.9}                            */
-    int n_ite;             /* 50                                                                 */
-    int rule;              /* QLDPC_RULE_NMS                                                     */
-    float rule_param;      /* 0.75                                                               */
+    int n_ite;             /* 60                                                                 */
+    int rule;              /* QLDPC_RULE_SPA                                                     */
+    float rule_param;      /* 0 (SPA takes none)                                                 */
     int key_quantum;       /* 1024 (multiple of 32)                                              */
     int max_blocks;        /* blocks decoded concurrently by qldpc_recon_decode_batch            */
     uint64_t seed;         /* IRA construction seed shared by both sides (7)                     */

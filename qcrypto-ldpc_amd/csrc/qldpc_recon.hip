@@ -26,14 +26,15 @@
 #include "../../include/qldpc.h"
 #include "qldpc_graph.h"
 #include "qldpc_hip.h"
+#include "qldpc_recon_core.h"
 
 /*
  * One of the two staging sets of an entry: while batch i decodes, batch i + 1 is copied into the other set's pinned block, sent to
  * the device and assembled into frames on the lane's copy stream, and batch i - 1's results travel back.
  */
 struct stage_set {
-    uint32_t *h_in, *d_in;     /* keys [n][Wk] | disclosed parity [n][Wm] | |LLR| [n] | block length [n] | punctured [n] | Alice's CRC [n] */
-    uint32_t *h_res, *d_res;   /* verified key words [n][Wk] | status [n] | bits flipped [n] | iterations [n] | CRC found [n] */
+    uint32_t *h_in, *d_in;     /* the input block, pinned and on the device: recon_in_layout (qldpc_recon_core.h) */
+    uint32_t *h_res, *d_res;   /* the result block: recon_bob_layout / recon_alice_layout */
     uint32_t *d_bits;          /* [max_blocks][Wn]  assembled frames */
     uint32_t *d_erase;         /* [max_blocks][Wn]  per-frame puncturing masks */
     hipEvent_t ev_in, ev_out, ev_done;
@@ -71,97 +72,26 @@ struct qldpc_recon {
     int gang;                       /* QLDPC_RECON_GANG=1 when the session was made: Bob-side calls with several layered rate groups decode in rounds, one gang run each (run_call_gang) */
 };
 
-#define CRC_POLY 0xEDB88320u      /* CRC-32 (IEEE 802.3), reflected */
-
 static const uint32_t *crc_table()
 {
     /* built once behind the compiler's guard of a function-local static: the lanes' host workers may get here together */
     struct table {
         uint32_t t[256];
-        table()
-        {
-            for (uint32_t i = 0; i < 256; i++) {
-                uint32_t c = i;
-                for (int k = 0; k < 8; k++) c = (c & 1) ? CRC_POLY ^ (c >> 1) : c >> 1;
-                t[i] = c;
-            }
-        }
+        table() { for (uint32_t i = 0; i < 256; i++) t[i] = crc_table_entry(i); }
     };
     static const table tab;
     return tab.t;
 }
 
 /* CRC-32 (IEEE 802.3) over the key bits, fed MSB-first word by word, bits past n_bits masked to 0 */
-extern "C" uint32_t qldpc_crc32_words(const uint32_t *w, int n_bits)
-{
-    const uint32_t *t = crc_table();
-    uint32_t c = 0xFFFFFFFFu;
-    const int nw = (n_bits + 31) / 32;
-    for (int i = 0; i < nw; i++) {
-        uint32_t x = w[i];
-        if (i == nw - 1 && (n_bits & 31)) x &= 0xFFFFFFFFu << (32 - (n_bits & 31));
-        for (int b = 3; b >= 0; b--) c = t[(c ^ (x >> (8 * b))) & 0xFF] ^ (c >> 8);
-    }
-    return c ^ 0xFFFFFFFFu;
-}
-
-/*
- * The same CRC computed in parallel: the register is linear over GF(2) in (start value, message), so with start value 0 the
- * register after A || B is reg(A) x^|B| + reg(B) (polynomials mod the CRC polynomial) and the start value 0xFFFFFFFF adds
- * 0xFFFFFFFF x^|message|.  Every lane runs the byte-wise recurrence over its own chunk (chunks of equal length; zero words in
- * front of the message leave a zero register alone), the partial registers are folded in a tree -- the same jump-ahead idea the
- * privacy-amplification kernel uses for the LFSR -- and the two constants are applied at the end.  In the reflected form bit 31
- * is the coefficient of x^0 and multiplying by x is a right shift.
- */
-__host__ __device__ static inline uint32_t gf_mulmod(uint32_t a, uint32_t b)
-{
-    uint32_t p = 0;
-    for (int i = 0; i < 32; i++) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b & 1u) ? (b >> 1) ^ CRC_POLY : (b >> 1);
-    }
-    return p;
-}
-/* x^n mod the CRC polynomial */
-__host__ __device__ static inline uint32_t gf_xpow(unsigned long long n)
-{
-    uint32_t r = 0x80000000u, sq = 0x40000000u;      /* 1, x */
-    while (n) {
-        if (n & 1ull) r = gf_mulmod(r, sq);
-        sq = gf_mulmod(sq, sq);
-        n >>= 1;
-    }
-    return r;
-}
-__host__ __device__ static inline uint32_t crc_word_step(uint32_t c, uint32_t x, const uint32_t *t)
-{
-    for (int b = 3; b >= 0; b--) c = t[(c ^ (x >> (8 * b))) & 0xFF] ^ (c >> 8);
-    return c;
-}
-__host__ __device__ static inline uint32_t tail_mask(int i, int nw, int n_bits)
-{
-    return (i == nw - 1 && (n_bits & 31)) ? 0xFFFFFFFFu << (32 - (n_bits & 31)) : 0xFFFFFFFFu;
-}
+extern "C" uint32_t qldpc_crc32_words(const uint32_t *w, int n_bits) { return crc_serial(w, n_bits, crc_table()); }
 
 /* host mirror of the device verification (rk_verify / rk_crc): `lanes` chunks folded in a tree; equals qldpc_crc32_words */
 extern "C" uint32_t qldpc_crc32_words_chunked(const uint32_t *w, int n_bits, int lanes)
 {
     if (!w || n_bits <= 0 || lanes < 1 || (lanes & (lanes - 1))) return 0;
-    const uint32_t *t = crc_table();
-    const int nw = (n_bits + 31) / 32;
-    const int c = (nw + lanes - 1) / lanes, pad = c * lanes - nw;
-    std::vector<uint32_t> reg((size_t)lanes, 0u);
-    for (int l = 0; l < lanes; l++)
-        for (int v = l * c; v < (l + 1) * c; v++) {
-            const int i = v - pad;
-            if (i >= 0) reg[(size_t)l] = crc_word_step(reg[(size_t)l], w[i] & tail_mask(i, nw, n_bits), t);
-        }
-    uint32_t X = gf_xpow(32ull * (unsigned long long)c);
-    for (int s = 1; s < lanes; s <<= 1) {
-        for (int l = 0; l + s < lanes; l += 2 * s) reg[(size_t)l] = gf_mulmod(reg[(size_t)l], X) ^ reg[(size_t)(l + s)];
-        X = gf_mulmod(X, X);
-    }
-    return reg[0] ^ gf_mulmod(0xFFFFFFFFu, gf_xpow(32ull * (unsigned long long)nw)) ^ 0xFFFFFFFFu;
+    std::vector<uint32_t> reg((size_t)lanes);
+    return crc_chunked(w, n_bits, lanes, crc_table(), reg.data());
 }
 
 /* one workgroup of 256 lanes per block: CRC-32 of words[0 .. ceil(n_bits / 32)) (tail bits masked) by the chunked fold; with `old` also
@@ -171,14 +101,11 @@ __device__ static uint32_t rk_block_crc(const uint32_t *__restrict__ words, int 
                                         int *flips_out, uint32_t *s_tab, uint32_t *s_reg, int *s_cnt)
 {
     const int t = (int)threadIdx.x;
-    {
-        uint32_t c = (uint32_t)t;
-        for (int k = 0; k < 8; k++) c = (c & 1u) ? CRC_POLY ^ (c >> 1) : c >> 1;
-        s_tab[t] = c;
-    }
+    s_tab[t] = crc_table_entry((uint32_t)t);
     __syncthreads();
     const int nw = (n_bits + 31) / 32;
-    const int c = (nw + RK_LANES - 1) / RK_LANES, pad = c * RK_LANES - nw;
+    int pad;
+    const int c = crc_chunk_words(nw, RK_LANES, &pad);
     uint32_t reg = 0;
     int flips = 0;
     for (int v = t * c; v < (t + 1) * c; v++) {
@@ -203,7 +130,7 @@ __device__ static uint32_t rk_block_crc(const uint32_t *__restrict__ words, int 
         __syncthreads();
     }
     if (flips_out) *flips_out = s_cnt[0];
-    return s_reg[0] ^ gf_mulmod(0xFFFFFFFFu, gf_xpow(32ull * (unsigned long long)nw)) ^ 0xFFFFFFFFu;
+    return crc_close(s_reg[0], nw);
 }
 
 /*
@@ -259,22 +186,12 @@ extern "C" void qldpc_recon_cfg_default(qldpc_recon_cfg *c)
     c->schedule = QLDPC_RECON_SCHED_AUTO;
     c->mother_step = 8192;
     c->mother_max = 65536;
-    c->rate_gap = 0.0f;             /* 0 = by rule: 0.03 for SPA, 0.05 for the min-sum family */
+    c->rate_gap = 0.0f;             /* 0 = by rule: 0.035 for SPA / LSPA, 0.05 for the min-sum family (qldpc_recon_create) */
     c->puncture = 1;
     c->preload = 0;
     c->gap_profile = 0;
     c->peg_depth = 2;               /* mother codes by progressive edge growth, no 4-cycles */
 }
-
-/*
- * Punctured parity positions of a block: p of the M accumulator bits, evenly spaced (position j is punctured iff
- * floor((j + 1) p / M) > floor(j p / M)), so no check loses both of its parity neighbours while p <= M / 2 and the pattern needs
- * no table or seed: both sides compute it from (M, p).  The reference shuffles the parity positions at random and searches for
- * good patterns (BS/src/main.cpp:305-333); on this accumulator structure random patterns fail where the even one decodes
- * (tools/punct_probe.py: 37 % punctured at QBER 4 %: FER 0.07 random, 0 even; 49 % at 3 %: 1.0 vs 0).
- */
-__host__ __device__ static inline int punct_before(int j, int p, int M) { return (int)(((long long)j * p) / M); }      /* punctured positions in [0, j) */
-__host__ __device__ static inline bool punct_at(int j, int p, int M) { return punct_before(j + 1, p, M) > punct_before(j, p, M); }
 
 /* Bob: frame words + puncturing mask of every block from its key words and the disclosed parity bits */
 __global__ __launch_bounds__(256) void rk_assemble(const uint32_t *__restrict__ key, const uint32_t *__restrict__ disc, const int *__restrict__ key_bits,
@@ -298,7 +215,7 @@ __global__ __launch_bounds__(256) void rk_assemble(const uint32_t *__restrict__ 
                 if (j >= M) break;
                 if (punct_at(j, p, M)) er |= 1u << (31 - t);
                 else {
-                    const int r = j - punct_before(j, p, M);
+                    const int r = punct_rank(j, p, M);
                     word |= ((dw[r >> 5] >> (31 - (r & 31))) & 1u) << (31 - t);
                 }
             }
@@ -320,13 +237,8 @@ __global__ __launch_bounds__(256) void rk_disclose(const uint32_t *__restrict__ 
         for (int t = 0; t < 32; t++) {
             const int r = w * 32 + t;
             if (r >= d) break;
-            /* the r-th disclosed position: smallest j with (j + 1) - punct_before(j + 1) == r + 1 */
-            int lo = r, hi = r + p;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (mid + 1 - punct_before(mid + 1, p, M) >= r + 1) hi = mid; else lo = mid + 1;
-            }
-            word |= ((par[lo >> 5] >> (31 - (lo & 31))) & 1u) << (31 - t);
+            const int j = punct_position(r, p, M);
+            word |= ((par[j >> 5] >> (31 - (j & 31))) & 1u) << (31 - t);
         }
         disc[(size_t)b * Wm + w] = word;
     }
@@ -382,8 +294,10 @@ static void cache_trim(qldpc_recon *r)
     (void)hipDeviceSynchronize();
     while (r->cache.size() > r->keep) { entry_free(r->cache.back()); r->cache.pop_back(); }
 }
-#define RECON_IN_SCALARS 4      /* |LLR|, block length, punctured, Alice's CRC */
-#define RECON_RES_SCALARS 4     /* status, bits flipped, iterations, CRC found */
+/* is this a session whose decoders run the horizontal-layered schedule?  Batches do unless told otherwise: half the iterations for the same bytes per
+ * sweep (config-3 stream 16.1 -> 14.4 ms, 0 instead of 0 - 1 first-round failures per 2 048 epochs); a decoder for <= 8 blocks is the edge-parallel
+ * engine, which is flooding */
+static bool cfg_layered(const qldpc_recon_cfg &c) { return c.schedule == QLDPC_SCHED_HLAYERED || (c.schedule == QLDPC_RECON_SCHED_AUTO && c.max_blocks > 8); }
 
 extern "C" int qldpc_recon_create(const qldpc_recon_cfg *cfg, qldpc_recon **out)
 {
@@ -419,12 +333,8 @@ extern "C" int qldpc_recon_create(const qldpc_recon_cfg *cfg, qldpc_recon **out)
      * created back to back so that the lanes land on different queues (interleaved with the copy streams, four lanes shared two queues
      * and at most two kernels ever ran side by side: rocprofv3 kernel trace, profiles/r03_config3_*) */
     bool ok = true;
-    const bool interleave = getenv("QLDPC_RECON_STREAMS_INTERLEAVED") != nullptr;      /* A/B: the old order */
-    if (interleave) { for (auto &l : r->lane) ok = ok && hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&l.copy, hipStreamNonBlocking) == hipSuccess; }
-    else {
-        for (auto &l : r->lane) ok = ok && hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking) == hipSuccess;
-        for (auto &l : r->lane) ok = ok && hipStreamCreateWithFlags(&l.copy, hipStreamNonBlocking) == hipSuccess;
-    }
+    for (auto &l : r->lane) ok = ok && hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking) == hipSuccess;
+    for (auto &l : r->lane) ok = ok && hipStreamCreateWithFlags(&l.copy, hipStreamNonBlocking) == hipSuccess;
     if (!ok) {
         qldpc_set_error("recon_create: hipStreamCreate failed");
         qldpc_recon_free(r);
@@ -630,10 +540,7 @@ static int get_entry(qldpc_recon *r, int K, int M, recon_entry **out, qldpc_code
     if (!rc) {
         qldpc_decoder_cfg dc;
         qldpc_decoder_cfg_default(&dc);
-        /* batches run the horizontal-layered schedule unless told otherwise: half the iterations for the same bytes per sweep (config-3 stream 16.1 -> 14.4 ms, 0 instead of 0 - 1 first-round
-         * failures per 2 048 epochs); a decoder for <= 8 blocks is the edge-parallel engine, which is flooding */
-        const bool layered = r->cfg.schedule == QLDPC_SCHED_HLAYERED || (r->cfg.schedule == QLDPC_RECON_SCHED_AUTO && B > 8);
-        dc.schedule = layered ? QLDPC_SCHED_HLAYERED : QLDPC_SCHED_FLOODING; dc.rule = r->cfg.rule; dc.rule_param = r->cfg.rule_param; dc.n_ite = r->cfg.n_ite;
+        dc.schedule = cfg_layered(r->cfg) ? QLDPC_SCHED_HLAYERED : QLDPC_SCHED_FLOODING; dc.rule = r->cfg.rule; dc.rule_param = r->cfg.rule_param; dc.n_ite = r->cfg.n_ite;
         dc.enable_syndrome = 1; dc.syndrome_depth = 1; dc.max_frames = B; dc.device = r->cfg.device;
         dc.layer_chain = 2;      /* the session's decoders run side by side (lanes): persistent one-launch sweeps would fight for the chip (measured 19.0 -> 23.9 ms) */
         rc = qldpc_decoder_create(e.code, K, nullptr, &dc, &e.dec);
@@ -644,14 +551,16 @@ static int get_entry(qldpc_recon *r, int K, int M, recon_entry **out, qldpc_code
     alloc((void **)&e.d_out, sizeof(uint32_t) * (size_t)B * Wn);
     alloc((void **)&e.d_iters, sizeof(int) * (size_t)B);
     alloc((void **)&e.d_ok, sizeof(int) * (size_t)B);
+    /* a full job's staging blocks; an entry serves both sides, so the result block holds the larger of the two layouts */
+    const size_t in_words = recon_in_layout(nullptr, B, Wk, Wm).words;
+    const size_t res_words = std::max(recon_bob_layout(nullptr, B, Wk).words, recon_alice_layout(nullptr, B, Wm).words);
     for (auto &st : e.set) {
-        const size_t in_words = (size_t)B * (Wk + Wm + RECON_IN_SCALARS), res_words = (size_t)B * (Wk + RECON_RES_SCALARS);
         alloc((void **)&st.d_in, sizeof(uint32_t) * in_words);
-        alloc((void **)&st.d_res, sizeof(uint32_t) * std::max(res_words, (size_t)B * (Wm + 1)));      /* Alice's side: disclosed parity [n][Wm] | CRC [n] */
+        alloc((void **)&st.d_res, sizeof(uint32_t) * res_words);
         alloc((void **)&st.d_bits, sizeof(uint32_t) * (size_t)B * Wn);
         alloc((void **)&st.d_erase, sizeof(uint32_t) * (size_t)B * Wn);
         if (!rc && hipHostMalloc((void **)&st.h_in, sizeof(uint32_t) * in_words) != hipSuccess) rc = QLDPC_ENOMEM;
-        if (!rc && hipHostMalloc((void **)&st.h_res, sizeof(uint32_t) * std::max(res_words, (size_t)B * (Wm + 1))) != hipSuccess) rc = QLDPC_ENOMEM;
+        if (!rc && hipHostMalloc((void **)&st.h_res, sizeof(uint32_t) * res_words) != hipSuccess) rc = QLDPC_ENOMEM;
         if (!rc && (hipEventCreateWithFlags(&st.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&st.ev_out, hipEventDisableTiming) != hipSuccess ||
                     hipEventCreateWithFlags(&st.ev_done, hipEventDisableTiming) != hipSuccess)) rc = QLDPC_EHIP;
     }
@@ -737,6 +646,32 @@ struct lane_run {
     std::string err;
 };
 
+static recon_call call_bob(int n, uint32_t *const *key, const int *key_bits, const float *qber, const qldpc_recon_msg *msgs, const uint32_t *const *parity,
+                           int *status, int *corrected, int *iterations, qldpc_recon_blind *blind = nullptr, int ask_bits = 0)
+{
+    recon_call c = {};
+    c.bob = true; c.n = n; c.key_bits = key_bits; c.key = key; c.qber = qber; c.msgs = msgs; c.parity = parity;
+    c.status = status; c.corrected = corrected; c.iterations = iterations; c.blind = blind; c.ask_bits = ask_bits;
+    return c;
+}
+static recon_call call_alice(int n, const uint32_t *const *key, const int *key_bits, qldpc_recon_msg *msgs, uint32_t *const *parity)
+{
+    recon_call c = {};
+    c.bob = false; c.n = n; c.key_bits = key_bits; c.akey = key; c.amsgs = msgs; c.aparity = parity;
+    return c;
+}
+static lane_run lane_of(qldpc_recon *r, int l, const recon_call &call)
+{
+    lane_run L;
+    L.r = r; L.lane = &r->lane[l]; L.call = &call; L.rc = QLDPC_OK;
+    return L;
+}
+
+/* the staging blocks of a job at `base` (a set's pinned or device block) */
+static recon_in_view job_in(const recon_job &j, uint32_t *base) { return recon_in_layout(base, (int)j.idx.size(), j.e->K / 32, (j.e->M + 31) / 32); }
+static recon_bob_view job_bob_res(const recon_job &j, uint32_t *base) { return recon_bob_layout(base, (int)j.idx.size(), j.e->K / 32); }
+static recon_alice_view job_alice_res(const recon_job &j, uint32_t *base) { return recon_alice_layout(base, (int)j.idx.size(), (j.e->M + 31) / 32); }
+
 static int job_stage(lane_run *L, recon_job &j, hipStream_t cs)
 {
     recon_entry *e = j.e;
@@ -747,37 +682,31 @@ static int job_stage(lane_run *L, recon_job &j, hipStream_t cs)
     e->next_set ^= 1;
     j.st = st;
     j.any_punct = false;
-    uint32_t *h_keys = st->h_in, *h_disc = h_keys + (size_t)n * Wk;
-    float *h_mag = reinterpret_cast<float *>(h_disc + (size_t)n * Wm);
-    int *h_nch = reinterpret_cast<int *>(h_mag + n), *h_np = h_nch + n;
-    uint32_t *h_crc = reinterpret_cast<uint32_t *>(h_np + n);
+    const recon_in_view h = job_in(j, st->h_in), d = job_in(j, st->d_in);
     for (int t = 0; t < n; t++) {
         const int i = j.idx[(size_t)t], kb = c.key_bits[i], Wkey = (kb + 31) / 32;
-        uint32_t *f = h_keys + (size_t)t * Wk;
+        uint32_t *f = h.keys + (size_t)t * Wk;
         if (c.bob) {
             /* only the words the kernels read are copied: rk_assemble masks the tail and never looks past the block's length */
             memcpy(f, c.key[i], sizeof(uint32_t) * (size_t)Wkey);
-            h_np[t] = (int)c.msgs[i].n_punct;
-            memcpy(h_disc + (size_t)t * Wm, c.parity[i], sizeof(uint32_t) * (size_t)((M - h_np[t] + 31) / 32));
-            h_mag[t] = c.qber ? qldpc_bsc_llr(clamp_qber(c.qber[i])) : 0.0f;      /* no QBER yet: qldpc_recon_estimate_blocks */
-            h_crc[t] = c.msgs[i].crc32;
+            h.n_punct[t] = (int)c.msgs[i].n_punct;
+            memcpy(h.disc + (size_t)t * Wm, c.parity[i], sizeof(uint32_t) * (size_t)((M - h.n_punct[t] + 31) / 32));
+            h.mag[t] = c.qber ? qldpc_bsc_llr(clamp_qber(c.qber[i])) : 0.0f;      /* no QBER yet: qldpc_recon_estimate_blocks */
+            h.crc[t] = c.msgs[i].crc32;
         } else {
             /* information word of the mother code: the key, then zeros (shortened positions) */
             memcpy(f, c.akey[i], sizeof(uint32_t) * (size_t)Wkey);
             if (kb & 31) f[Wkey - 1] &= 0xFFFFFFFFu << (32 - (kb & 31));
             memset(f + Wkey, 0, sizeof(uint32_t) * (size_t)(Wk - Wkey));
-            h_np[t] = (int)c.amsgs[i].n_punct;
-            h_mag[t] = 0.0f; h_crc[t] = 0;
+            h.n_punct[t] = (int)c.amsgs[i].n_punct;
+            h.mag[t] = 0.0f; h.crc[t] = 0;
         }
-        h_nch[t] = kb;
-        j.any_punct = j.any_punct || h_np[t] != 0;
+        h.key_bits[t] = kb;
+        j.any_punct = j.any_punct || h.n_punct[t] != 0;
     }
-    const size_t in_words = (size_t)n * (Wk + Wm + RECON_IN_SCALARS);
-    HIPCHK(hipMemcpyAsync(st->d_in, st->h_in, sizeof(uint32_t) * in_words, hipMemcpyHostToDevice, cs));
+    HIPCHK(hipMemcpyAsync(st->d_in, st->h_in, sizeof(uint32_t) * h.words, hipMemcpyHostToDevice, cs));
     if (c.bob) {
-        uint32_t *d_keys = st->d_in, *d_disc = d_keys + (size_t)n * Wk;
-        int *d_nch = reinterpret_cast<int *>(d_disc + (size_t)n * Wm + n), *d_np = d_nch + n;
-        hipLaunchKernelGGL(rk_assemble, dim3((unsigned)((Wn + 255) / 256), (unsigned)n), dim3(256), 0, cs, d_keys, d_disc, d_nch, d_np, st->d_bits, st->d_erase, Wk, Wn, Wm, M);
+        hipLaunchKernelGGL(rk_assemble, dim3((unsigned)((Wn + 255) / 256), (unsigned)n), dim3(256), 0, cs, d.keys, d.disc, d.key_bits, d.n_punct, st->d_bits, st->d_erase, Wk, Wn, Wm, M);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(st->ev_in, cs));
@@ -829,16 +758,13 @@ static int job_load(lane_run *L, recon_job &j, hipStream_t cs)
     recon_entry *e = j.e;
     stage_set *st = j.st;
     hipStream_t s = L->lane->stream;
-    const int n = (int)j.idx.size(), K = e->K, M = e->M;
-    const int Wk = K / 32, Wm = (M + 31) / 32;
+    const int n = (int)j.idx.size();
+    const recon_in_view d = job_in(j, st->d_in);
     int rc;
-    uint32_t *d_keys = st->d_in, *d_disc = d_keys + (size_t)n * Wk;
-    float *d_mag = reinterpret_cast<float *>(d_disc + (size_t)n * Wm);
-    int *d_nch = reinterpret_cast<int *>(d_mag + n);
     if (cs != s) HIPCHK(hipStreamWaitEvent(s, st->ev_in, 0));
     if (L->call->bob) {
         if ((rc = qldpc_decoder_set_stream(e->dec, (void *)s))) return rc;
-        if ((rc = qldpc_load_bits_short_dev(e->dec, st->d_bits, d_mag, e->d_cls, d_nch, n))) return rc;
+        if ((rc = qldpc_load_bits_short_dev(e->dec, st->d_bits, d.mag, e->d_cls, d.key_bits, n))) return rc;
         if (j.any_punct && (rc = qldpc_load_erasures_dev(e->dec, st->d_erase, n))) return rc;
         if (L->call->blind && (rc = job_load_blind(L, j))) return rc;
     }
@@ -859,37 +785,33 @@ static int job_fetch(lane_run *L, recon_job &j, hipStream_t cs)
     const int n = (int)j.idx.size(), K = e->K, M = e->M, N = K + M;
     const int Wk = K / 32, Wn = (N + 31) / 32, Wm = (M + 31) / 32;
     int rc;
-    uint32_t *d_keys = st->d_in, *d_disc = d_keys + (size_t)n * Wk;
-    float *d_mag = reinterpret_cast<float *>(d_disc + (size_t)n * Wm);
-    int *d_nch = reinterpret_cast<int *>(d_mag + n), *d_np = d_nch + n;
-    uint32_t *d_crc = reinterpret_cast<uint32_t *>(d_np + n);
+    const recon_in_view d = job_in(j, st->d_in);
     size_t res_words;
     if (L->call->bob) {
         if ((rc = qldpc_fetch_packed_dev(e->dec, e->d_out))) return rc;
         if ((rc = qldpc_fetch_status_dev(e->dec, e->d_iters, e->d_ok))) return rc;
-        uint32_t *res_keys = st->d_res;
-        int *res = reinterpret_cast<int *>(res_keys + (size_t)n * Wk);
-        hipLaunchKernelGGL(rk_verify, dim3((unsigned)n), dim3(RK_LANES), 0, s, e->d_out, d_keys, d_nch, d_crc, e->d_ok, e->d_iters, res_keys, res, n, Wk, Wn);
+        const recon_bob_view res = job_bob_res(j, st->d_res);
+        hipLaunchKernelGGL(rk_verify, dim3((unsigned)n), dim3(RK_LANES), 0, s, e->d_out, d.keys, d.key_bits, d.crc, e->d_ok, e->d_iters, res.keys, res.status, n, Wk, Wn);
         HIPCHK(hipGetLastError());
-        res_words = (size_t)n * (Wk + RECON_RES_SCALARS);
+        res_words = res.words;
         if (L->call->blind) {
             /* the request of every block that failed: its ask_bits weakest candidates, out of the posteriors of this decode.  The status column
              * rk_verify just wrote is the take column (QLDPC_OK = 0 = not wanted).  The rows are waited for here: a blind round gives up the
              * overlap of neighbouring jobs, it is the recovery path */
             const int B = L->r->cfg.max_blocks;
             uint32_t *d_cand = e->d_blind + 2 * (size_t)B * Wn, *d_weak = d_cand + (size_t)B * Wn;
-            if ((rc = qldpc_fetch_weakest_dev(e->dec, d_cand, res, L->call->ask_bits, d_weak))) return rc;
+            if ((rc = qldpc_fetch_weakest_dev(e->dec, d_cand, res.status, L->call->ask_bits, d_weak))) return rc;
             j.h_weak.assign((size_t)n * Wn, 0u);
             HIPCHK(hipMemcpyAsync(j.h_weak.data(), d_weak, sizeof(uint32_t) * (size_t)n * Wn, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
         }
     } else {
-        if ((rc = qldpc_encode_packed_dev(e->enc, d_keys, e->d_out, n, (void *)s))) return rc;
-        uint32_t *res_disc = st->d_res, *res_crc = res_disc + (size_t)n * Wm;
-        hipLaunchKernelGGL(rk_disclose, dim3((unsigned)((Wm + 255) / 256), (unsigned)n), dim3(256), 0, s, e->d_out, d_np, res_disc, Wk, Wn, Wm, M);
-        hipLaunchKernelGGL(rk_crc, dim3((unsigned)n), dim3(RK_LANES), 0, s, d_keys, d_nch, res_crc, Wk);
+        if ((rc = qldpc_encode_packed_dev(e->enc, d.keys, e->d_out, n, (void *)s))) return rc;
+        const recon_alice_view res = job_alice_res(j, st->d_res);
+        hipLaunchKernelGGL(rk_disclose, dim3((unsigned)((Wm + 255) / 256), (unsigned)n), dim3(256), 0, s, e->d_out, d.n_punct, res.disc, Wk, Wn, Wm, M);
+        hipLaunchKernelGGL(rk_crc, dim3((unsigned)n), dim3(RK_LANES), 0, s, d.keys, d.key_bits, res.crc, Wk);
         HIPCHK(hipGetLastError());
-        res_words = (size_t)n * (Wm + 1);
+        res_words = res.words;
     }
     if (cs != s) {
         HIPCHK(hipEventRecord(st->ev_out, s));
@@ -916,66 +838,126 @@ static int job_finish(lane_run *L, recon_job &j)
     const int Wk = K / 32, Wm = (M + 31) / 32;
     HIPCHK(hipEventSynchronize(st->ev_done));
     if (c.bob) {
-        const uint32_t *keys = st->h_res;
-        const int *res = reinterpret_cast<const int *>(keys + (size_t)n * Wk);
+        const recon_bob_view res = job_bob_res(j, st->h_res);
         for (int t = 0; t < n; t++) {
             const int i = j.idx[(size_t)t], Wkey = (c.key_bits[i] + 31) / 32;
-            c.status[i] = res[t];
-            if (c.corrected) c.corrected[i] = res[n + t];
-            if (c.iterations) c.iterations[i] = res[2 * n + t];
-            if (res[t] == QLDPC_OK) memcpy(c.key[i], keys + (size_t)t * Wk, sizeof(uint32_t) * (size_t)Wkey);      /* a failed block keeps its key untouched */
+            c.status[i] = res.status[t];
+            if (c.corrected) c.corrected[i] = res.flips[t];
+            if (c.iterations) c.iterations[i] = res.iters[t];
+            if (res.status[t] == QLDPC_OK) memcpy(c.key[i], res.keys + (size_t)t * Wk, sizeof(uint32_t) * (size_t)Wkey);      /* a failed block keeps its key untouched */
             if (c.blind) {
                 qldpc_recon_blind &b = c.blind[i];
                 b.n_ask = 0;
                 const size_t Wn = (size_t)(K + M + 31) / 32;
                 const uint32_t *row = j.h_weak.data() + (size_t)t * Wn;
-                for (int v = 0; res[t] != QLDPC_OK && v < c.key_bits[i] && b.n_ask < c.ask_bits; v++)
+                for (int v = 0; res.status[t] != QLDPC_OK && v < c.key_bits[i] && b.n_ask < c.ask_bits; v++)
                     if ((row[v >> 5] >> (31 - (v & 31))) & 1u) b.ask[b.n_ask++] = v;
             }
         }
     } else {
-        const uint32_t *disc = st->h_res, *crc = disc + (size_t)n * Wm;
+        const recon_alice_view res = job_alice_res(j, st->h_res);
         for (int t = 0; t < n; t++) {
             const int i = j.idx[(size_t)t];
-            memcpy(c.aparity[i], disc + (size_t)t * Wm, sizeof(uint32_t) * (size_t)qldpc_recon_parity_words(&c.amsgs[i]));
-            c.amsgs[i].crc32 = crc[t];
+            memcpy(c.aparity[i], res.disc + (size_t)t * Wm, sizeof(uint32_t) * (size_t)qldpc_recon_parity_words(&c.amsgs[i]));
+            c.amsgs[i].crc32 = res.crc[t];
         }
     }
     return QLDPC_OK;
 }
 
+/*
+ * The software pipeline of one host worker, over rounds (a round = the jobs that are launched together; a lane's rounds hold one job each, a gang
+ * round one job per group): round k + 1 is staged, round k launched, round k - 1 finished, and at the end the rounds still under way are finished.
+ * On an error both streams of the lane are synchronised and L->err keeps the text of the first one.
+ * The two staging sets of an entry alternate between its jobs, and the host writes a set's pinned block while the job two back may still be on its way.
+ * wait_for_set (the gang rounds): with three jobs per code the set's previous user is waited for (its ev_done) before job_stage writes h_in.  The lanes
+ * do not wait: their order (stage k + 1, launch k, finish k - 1) has the set free by then, and a wait would put a host stall in front of Alice's staging.
+ */
+typedef std::vector<recon_job *> recon_round;
+
+template <class Launch>
+static int run_rounds(lane_run *L, const std::vector<recon_round> &rounds, hipStream_t cs, bool wait_for_set, Launch launch)
+{
+    auto stage = [&](const recon_round &rd) -> int {
+        for (recon_job *j : rd) {
+            if (wait_for_set) HIPCHK(hipEventSynchronize(j->e->set[j->e->next_set].ev_done));
+            if (int rc = job_stage(L, *j, cs)) return rc;
+        }
+        return QLDPC_OK;
+    };
+    auto finish = [&](const recon_round &rd) -> int {
+        for (recon_job *j : rd)
+            if (int rc = job_finish(L, *j)) return rc;
+        return QLDPC_OK;
+    };
+    const size_t nr = rounds.size();
+    size_t launched = 0, finished = 0;
+    int rc = stage(rounds[0]);
+    for (size_t k = 0; k < nr && !rc; k++) {
+        if (k + 1 < nr) rc = stage(rounds[k + 1]);
+        if (!rc) { rc = launch(rounds[k]); if (!rc) launched = k + 1; }
+        if (!rc && k > 0) { rc = finish(rounds[k - 1]); if (!rc) finished = k; }
+    }
+    for (size_t k = finished; k < launched && !rc; k++) rc = finish(rounds[k]);
+    if (rc) {
+        L->err = qldpc_last_error();
+        (void)hipStreamSynchronize(L->lane->stream);
+        (void)hipStreamSynchronize(L->lane->copy);
+    }
+    return rc;
+}
+
 static void lane_main(lane_run *L)
 {
-    int rc = QLDPC_OK;
     const bool dbg = getenv("QLDPC_DEBUG") != nullptr;
     const auto t_start = std::chrono::steady_clock::now();
     if (hipSetDevice(L->r->cfg.device) != hipSuccess) { L->rc = QLDPC_EHIP; L->err = "hipSetDevice failed"; return; }
     const size_t nj = L->jobs.size();
     /* one job: everything in order on the compute stream (no cross-stream hand-offs on the daemon's one-block path) */
     hipStream_t cs = nj > 1 ? L->lane->copy : L->lane->stream;
-    size_t launched = 0, finished = 0;
-    rc = job_stage(L, L->jobs[0], cs);
-    for (size_t i = 0; i < nj && !rc; i++) {
-        if (i + 1 < nj) rc = job_stage(L, L->jobs[i + 1], cs);
-        if (!rc) { rc = job_launch(L, L->jobs[i], cs); if (!rc) launched = i + 1; }
-        if (!rc && i > 0) { rc = job_finish(L, L->jobs[i - 1]); if (!rc) finished = i; }
-    }
-    for (size_t i = finished; i < launched && !rc; i++) rc = job_finish(L, L->jobs[i]);
+    std::vector<recon_round> rounds;
+    for (auto &j : L->jobs) rounds.push_back(recon_round(1, &j));
+    L->rc = run_rounds(L, rounds, cs, false, [&](const recon_round &rd) { return job_launch(L, *rd[0], cs); });
     if (dbg) {
         size_t blocks = 0;
         for (auto &j : L->jobs) blocks += j.idx.size();
         fprintf(stderr, "libqldpc: recon lane %d: %zu job(s), %zu blocks, first code K %d M %d, %.3f ms\n", (int)(L->lane - L->r->lane), nj, blocks, L->jobs[0].e->K, L->jobs[0].e->M,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
     }
-    if (rc) {
-        L->err = qldpc_last_error();
-        (void)hipStreamSynchronize(L->lane->stream);
-        (void)hipStreamSynchronize(L->lane->copy);
-    }
-    L->rc = rc;
 }
 
+/* groups: the blocks of a call that are not skipped, by code.  Entries are looked up / built here, in the calling thread. */
 struct recon_group { recon_entry *e; std::vector<int> idx; double cost; };
+
+static int call_groups(qldpc_recon *r, const recon_call &call, const std::vector<char> &skip, std::vector<recon_group> &groups)
+{
+    const qldpc_recon_msg *msgs = call.bob ? call.msgs : call.amsgs;
+    std::vector<char> taken(skip);
+    for (int i = 0; i < call.n; i++) {
+        if (taken[(size_t)i]) continue;
+        recon_group g;
+        for (int j = i; j < call.n; j++)
+            if (!taken[(size_t)j] && msgs[j].code_k == msgs[i].code_k && msgs[j].code_m == msgs[i].code_m) { g.idx.push_back(j); taken[(size_t)j] = 1; }
+        if (int rc = get_entry(r, (int)msgs[i].code_k, (int)msgs[i].code_m, &g.e)) return rc;
+        g.cost = (double)g.idx.size() * (double)(msgs[i].code_k + msgs[i].code_m);
+        groups.push_back(std::move(g));
+    }
+    return QLDPC_OK;
+}
+
+/* the jobs of a group: its blocks in batches of up to max_blocks */
+static std::vector<recon_job> group_jobs(const qldpc_recon *r, const recon_group &g)
+{
+    const size_t B = (size_t)r->cfg.max_blocks;
+    std::vector<recon_job> jobs;
+    for (size_t at = 0; at < g.idx.size(); at += B) {
+        recon_job j;
+        j.e = g.e; j.st = nullptr; j.any_punct = false;
+        j.idx.assign(g.idx.begin() + (long)at, g.idx.begin() + (long)std::min(g.idx.size(), at + B));
+        jobs.push_back(std::move(j));
+    }
+    return jobs;
+}
 
 /*
  * QLDPC_RECON_GANG=1, Bob's side, two or more rate groups with layered decoders: the call runs on ONE host thread and one lane, in rounds.  Round k
@@ -983,104 +965,52 @@ struct recon_group { recon_entry *e; std::vector<int> idx; double cost; };
  * per colour step and kernel class for all of them instead of a launch per group on its own stream), every member is fetched and verified.  A round
  * that only one group still takes part in runs as a job of today's path.  What a block reports is what job_launch gives: the gang run is bit-identical
  * to the members' own runs.
- * The two staging sets of an entry alternate between its jobs, and the host writes a set's pinned block while the job two back may still be on its way:
- * with three jobs per code the set's previous user is waited for (its ev_done) before job_stage writes h_in.
  */
 static int run_call_gang(qldpc_recon *r, const recon_call &call, std::vector<recon_group> &groups)
 {
-    int rc = QLDPC_OK;
-    lane_run L;
-    L.r = r; L.lane = &r->lane[0]; L.call = &call; L.rc = QLDPC_OK;
+    lane_run L = lane_of(r, 0, call);
     hipStream_t s = L.lane->stream, cs = L.lane->copy;
-    const size_t B = (size_t)r->cfg.max_blocks, ng = groups.size();
-    std::vector<std::vector<recon_job>> jobs(ng);
-    size_t rounds = 0;
-    for (size_t g = 0; g < ng; g++) {
-        for (size_t at = 0; at < groups[g].idx.size(); at += B) {
-            recon_job j;
-            j.e = groups[g].e; j.st = nullptr; j.any_punct = false;
-            j.idx.assign(groups[g].idx.begin() + (long)at, groups[g].idx.begin() + (long)std::min(groups[g].idx.size(), at + B));
-            jobs[g].push_back(std::move(j));
-        }
-        rounds = std::max(rounds, jobs[g].size());
+    std::vector<std::vector<recon_job>> jobs;
+    std::vector<recon_round> rounds;
+    for (auto &g : groups) jobs.push_back(group_jobs(r, g));
+    for (auto &gj : jobs) {
+        if (rounds.size() < gj.size()) rounds.resize(gj.size());
+        for (size_t k = 0; k < gj.size(); k++) rounds[k].push_back(&gj[k]);
     }
-    auto stage_round = [&](size_t k) -> int {
-        for (size_t g = 0; g < ng; g++) {
-            if (k >= jobs[g].size()) continue;
-            recon_entry *e = jobs[g][k].e;
-            HIPCHK(hipEventSynchronize(e->set[e->next_set].ev_done));      /* the set's previous user has left its pinned block */
-            int rc2 = job_stage(&L, jobs[g][k], cs);
-            if (rc2) return rc2;
-        }
-        return QLDPC_OK;
-    };
-    auto finish_round = [&](size_t k) -> int {
-        for (size_t g = 0; g < ng; g++) {
-            if (k >= jobs[g].size()) continue;
-            int rc2 = job_finish(&L, jobs[g][k]);
-            if (rc2) return rc2;
-        }
-        return QLDPC_OK;
-    };
     qldpc_gang *gang = nullptr;
     std::vector<qldpc_decoder *> members, have;
-    size_t launched = 0, finished = 0;
-    rc = stage_round(0);
-    for (size_t k = 0; k < rounds && !rc; k++) {
-        if (k + 1 < rounds) rc = stage_round(k + 1);
-        std::vector<size_t> in;
-        for (size_t g = 0; g < ng; g++) if (k < jobs[g].size()) in.push_back(g);
-        if (!rc && in.size() == 1) rc = job_launch(&L, jobs[in[0]][k], cs);
-        else if (!rc) {
-            members.clear();
-            for (size_t g : in) members.push_back(groups[g].e->dec);
-            if (members != have) {      /* groups drop out as their jobs run out: a gang per set of members, at most one per group and call */
-                qldpc_gang_free(gang); gang = nullptr; have.clear();
-                rc = qldpc_gang_create(members.data(), (int)members.size(), &gang);
-                if (!rc) { have = members; rc = qldpc_gang_set_stream(gang, (void *)s); }
-            }
-            for (size_t t = 0; t < in.size() && !rc; t++) rc = job_load(&L, jobs[in[t]][k], cs);
-            if (!rc) rc = qldpc_gang_run(gang, nullptr);
-            for (size_t t = 0; t < in.size() && !rc; t++) rc = job_fetch(&L, jobs[in[t]][k], cs);
+    int rc = run_rounds(&L, rounds, cs, true, [&](const recon_round &rd) -> int {
+        if (rd.size() == 1) return job_launch(&L, *rd[0], cs);
+        int rc = QLDPC_OK;
+        members.clear();
+        for (recon_job *j : rd) members.push_back(j->e->dec);
+        if (members != have) {      /* groups drop out as their jobs run out: a gang per set of members, at most one per group and call */
+            qldpc_gang_free(gang); gang = nullptr; have.clear();
+            rc = qldpc_gang_create(members.data(), (int)members.size(), &gang);
+            if (!rc) { have = members; rc = qldpc_gang_set_stream(gang, (void *)s); }
         }
-        if (!rc) launched = k + 1;
-        if (!rc && k > 0) { rc = finish_round(k - 1); if (!rc) finished = k; }
-    }
-    for (size_t k = finished; k < launched && !rc; k++) rc = finish_round(k);
-    std::string err = rc ? qldpc_last_error() : "";
-    if (rc) { (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(cs); }
+        for (size_t t = 0; t < rd.size() && !rc; t++) rc = job_load(&L, *rd[t], cs);
+        if (!rc) rc = qldpc_gang_run(gang, nullptr);
+        for (size_t t = 0; t < rd.size() && !rc; t++) rc = job_fetch(&L, *rd[t], cs);
+        return rc;
+    });
     qldpc_gang_free(gang);
-    if (rc) qldpc_set_error("%s", err.c_str());
+    if (rc) qldpc_set_error("%s", L.err.c_str());
     return rc;
 }
 
-/* groups: blocks by code.  Entries are looked up / built here, in the calling thread; jobs of one entry stay on one lane, the
- * entries are dealt onto the lanes largest first. */
+/* jobs of one entry stay on one lane, the entries are dealt onto the lanes largest first */
 static int run_call(qldpc_recon *r, const recon_call &call, const std::vector<char> &skip)
 {
     int rc;
     HIPCHK(hipSetDevice(r->cfg.device));
-    typedef recon_group group;
-    std::vector<group> groups;
-    const int n = call.n;
-    std::vector<char> taken(skip);
-    for (int i = 0; i < n; i++) {
-        if (taken[(size_t)i]) continue;
-        const qldpc_recon_msg &mi = call.bob ? call.msgs[i] : call.amsgs[i];
-        group g;
-        for (int j = i; j < n; j++) {
-            const qldpc_recon_msg &mj = call.bob ? call.msgs[j] : call.amsgs[j];
-            if (!taken[(size_t)j] && mj.code_k == mi.code_k && mj.code_m == mi.code_m) { g.idx.push_back(j); taken[(size_t)j] = 1; }
-        }
-        if ((rc = get_entry(r, (int)mi.code_k, (int)mi.code_m, &g.e))) { cache_trim(r); return rc; }
-        g.cost = (double)g.idx.size() * (double)(mi.code_k + mi.code_m);
-        groups.push_back(std::move(g));
-    }
+    std::vector<recon_group> groups;
+    if ((rc = call_groups(r, call, skip, groups))) { cache_trim(r); return rc; }
     if (groups.empty()) return QLDPC_OK;
     int n_lanes = RECON_LANES;
     if (const char *env = getenv("QLDPC_RECON_LANES")) n_lanes = std::max(1, std::min(RECON_LANES, atoi(env)));
     n_lanes = std::min(n_lanes, (int)groups.size());
-    std::sort(groups.begin(), groups.end(), [](const group &a, const group &b) { return a.cost > b.cost; });
+    std::sort(groups.begin(), groups.end(), [](const recon_group &a, const recon_group &b) { return a.cost > b.cost; });
     if (r->gang && call.bob && !call.blind && groups.size() >= 2 && groups.size() <= (size_t)QLDPC_GANG_MAX_MEMBERS) {
         /* only when every group's decoder can be a member (layered sessions); otherwise today's path */
         std::vector<qldpc_decoder *> decs;
@@ -1093,19 +1023,13 @@ static int run_call(qldpc_recon *r, const recon_call &call, const std::vector<ch
             return rc;
         }
     }
-    std::vector<lane_run> runs((size_t)n_lanes);
+    std::vector<lane_run> runs;
     std::vector<double> load((size_t)n_lanes, 0.0);
-    for (int l = 0; l < n_lanes; l++) { runs[(size_t)l].r = r; runs[(size_t)l].lane = &r->lane[l]; runs[(size_t)l].call = &call; runs[(size_t)l].rc = QLDPC_OK; }
-    const size_t B = (size_t)r->cfg.max_blocks;
+    for (int l = 0; l < n_lanes; l++) runs.push_back(lane_of(r, l, call));
     for (auto &g : groups) {
         const size_t l = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
         load[l] += g.cost;
-        for (size_t at = 0; at < g.idx.size(); at += B) {
-            recon_job j;
-            j.e = g.e; j.st = nullptr; j.any_punct = false;
-            j.idx.assign(g.idx.begin() + (long)at, g.idx.begin() + (long)std::min(g.idx.size(), at + B));
-            runs[l].jobs.push_back(std::move(j));
-        }
+        for (auto &j : group_jobs(r, g)) runs[l].jobs.push_back(std::move(j));
     }
     if (n_lanes == 1) lane_main(&runs[0]);
     else {
@@ -1136,10 +1060,7 @@ extern "C" int qldpc_recon_encode_blocks(qldpc_recon *r, int n, const uint32_t *
         if ((rc = qldpc_recon_plan(r, key_bits[i], qber[i], &msgs[i]))) return rc;
         if (parity_cap[i] < qldpc_recon_parity_words(&msgs[i])) { qldpc_set_error("recon_encode_blocks: parity buffer %d holds %d words, need %d", i, parity_cap[i], qldpc_recon_parity_words(&msgs[i])); return QLDPC_ESIZE; }
     }
-    recon_call c;
-    memset(&c, 0, sizeof(c));
-    c.bob = false; c.n = n; c.key_bits = key_bits; c.akey = key_words; c.amsgs = msgs; c.aparity = parity_words;
-    return run_call(r, c, std::vector<char>((size_t)n, 0));
+    return run_call(r, call_alice(n, key_words, key_bits, msgs, parity_words), std::vector<char>((size_t)n, 0));
 }
 
 extern "C" int qldpc_recon_encode(qldpc_recon *r, const uint32_t *key_words, int key_bits, float qber, qldpc_recon_msg *msg, uint32_t *parity_words, int cap)
@@ -1161,10 +1082,27 @@ extern "C" int qldpc_recon_encode_planned(qldpc_recon *r, const uint32_t *key_wo
     int rc;
     if ((rc = check_msg(r, msg, key_bits))) return rc;
     if (cap < qldpc_recon_parity_words(msg)) { qldpc_set_error("recon_encode_planned: parity buffer holds %d words, need %d", cap, qldpc_recon_parity_words(msg)); return QLDPC_ESIZE; }
-    recon_call c;
-    memset(&c, 0, sizeof(c));
-    c.bob = false; c.n = 1; c.key_bits = &key_bits; c.akey = &key_words; c.amsgs = msg; c.aparity = &parity_words;
-    return run_call(r, c, std::vector<char>(1, 0));
+    return run_call(r, call_alice(1, &key_words, &key_bits, msg, &parity_words), std::vector<char>(1, 0));
+}
+
+/*
+ * The Bob-side prologue of block i, shared by qldpc_recon_decode_blocks, qldpc_recon_decode_blind and qldpc_recon_estimate_blocks: QLDPC_EINVAL for a NULL
+ * key or parity pointer (nothing of the block is written), else the block's outputs at their failure values and *skip = is it left out of the call: its
+ * header does not match the block or the local plan, or its QBER is out of range (status QLDPC_ESIZE).  qber_out != NULL is a call that estimates: it has
+ * no QBER to check and no status, and zeroes qber_out[i] instead.
+ */
+static int bob_block_begin(const qldpc_recon *r, const recon_call &c, int i, float *qber_out, char *skip)
+{
+    if (!c.key[i] || !c.parity[i]) return QLDPC_EINVAL;
+    if (qber_out) qber_out[i] = 0.0f;
+    else {
+        c.status[i] = QLDPC_EDECODE;
+        if (c.corrected) c.corrected[i] = 0;
+        if (c.iterations) c.iterations[i] = 0;
+    }
+    *skip = check_msg(r, &c.msgs[i], c.key_bits[i]) || (!qber_out && !(c.qber[i] >= 0.0f && c.qber[i] < 0.5f));
+    if (*skip && !qber_out) c.status[i] = QLDPC_ESIZE;
+    return QLDPC_OK;
 }
 
 /*
@@ -1179,18 +1117,10 @@ extern "C" int qldpc_recon_decode_blocks(qldpc_recon *r, int n, uint32_t *const 
                                          const qldpc_recon_msg *msgs, const uint32_t *const *parity_words, int *status, int *corrected, int *iterations)
 {
     if (!r || !key_words || !key_bits || !qber || !msgs || !parity_words || !status || n <= 0) return QLDPC_EINVAL;
+    const recon_call c = call_bob(n, key_words, key_bits, qber, msgs, parity_words, status, corrected, iterations);
     std::vector<char> skip((size_t)n, 0);
-    for (int i = 0; i < n; i++) {
-        if (!key_words[i] || !parity_words[i]) return QLDPC_EINVAL;
-        status[i] = QLDPC_EDECODE;
-        if (corrected) corrected[i] = 0;
-        if (iterations) iterations[i] = 0;
-        if (check_msg(r, &msgs[i], key_bits[i]) || !(qber[i] >= 0.0f && qber[i] < 0.5f)) { status[i] = QLDPC_ESIZE; skip[(size_t)i] = 1; }
-    }
-    recon_call c;
-    memset(&c, 0, sizeof(c));
-    c.bob = true; c.n = n; c.key_bits = key_bits; c.key = key_words; c.qber = qber; c.msgs = msgs; c.parity = parity_words;
-    c.status = status; c.corrected = corrected; c.iterations = iterations;
+    for (int i = 0; i < n; i++)
+        if (int rc = bob_block_begin(r, c, i, nullptr, &skip[(size_t)i])) return rc;
     return run_call(r, c, skip);
 }
 
@@ -1204,46 +1134,34 @@ extern "C" int qldpc_recon_estimate_blocks(qldpc_recon *r, int n, const uint32_t
 {
     if (!r || !key_words || !key_bits || !msgs || !parity_words || !qber_out || n <= 0) return QLDPC_EINVAL;
     const size_t BINS = 2 * (QLDPC_QBER_MAX_DEGREE + 1);
-    std::vector<char> taken((size_t)n, 0);
-    for (int i = 0; i < n; i++) {
-        if (!key_words[i] || !parity_words[i]) return QLDPC_EINVAL;
-        qber_out[i] = 0.0f;
-        if (check_msg(r, &msgs[i], key_bits[i])) taken[(size_t)i] = 1;
-    }
+    const recon_call call = call_bob(n, const_cast<uint32_t *const *>(key_words), key_bits, nullptr, msgs, parity_words, nullptr, nullptr, nullptr);
+    std::vector<char> skip((size_t)n, 0);
+    int rc = QLDPC_OK, max_d = 0;
+    for (int i = 0; i < n; i++)
+        if ((rc = bob_block_begin(r, call, i, qber_out, &skip[(size_t)i]))) return rc;
     if (counts_out) memset(counts_out, 0, sizeof(uint32_t) * (size_t)n * BINS);
     if (pool_qber_out) *pool_qber_out = 0.0f;
     HIPCHK(hipSetDevice(r->cfg.device));
-    recon_call call;
-    memset(&call, 0, sizeof(call));
-    call.bob = true; call.n = n; call.key_bits = key_bits; call.key = const_cast<uint32_t *const *>(key_words); call.msgs = msgs; call.parity = parity_words;
-    lane_run L;
-    L.r = r; L.lane = &r->lane[0]; L.call = &call; L.rc = QLDPC_OK;
+    lane_run L = lane_of(r, 0, call);
     hipStream_t s = L.lane->stream;
     const size_t B = (size_t)r->cfg.max_blocks;
     std::vector<uint64_t> pool(BINS, 0);
     std::vector<uint32_t> h_est;
-    int rc = QLDPC_OK, max_d = 0;
-    for (int i = 0; i < n && !rc; i++) {
-        if (taken[(size_t)i]) continue;
-        std::vector<int> idx;
-        for (int j = i; j < n; j++)
-            if (!taken[(size_t)j] && msgs[j].code_k == msgs[i].code_k && msgs[j].code_m == msgs[i].code_m) { idx.push_back(j); taken[(size_t)j] = 1; }
-        recon_entry *e;
-        if ((rc = get_entry(r, (int)msgs[i].code_k, (int)msgs[i].code_m, &e)) || (rc = entry_estimator(r, *e))) break;
+    std::vector<recon_group> groups;
+    rc = call_groups(r, call, skip, groups);
+    for (size_t g = 0; g < groups.size() && !rc; g++) {
+        recon_entry *e = groups[g].e;
+        if ((rc = entry_estimator(r, *e))) break;
         const int D = qldpc_code_max_cn_degree(e->code);
         const size_t bins = 2 * (size_t)(D + 1);
         max_d = std::max(max_d, D);
         if ((rc = qldpc_qber_set_stream(e->qest, (void *)s))) break;
-        for (size_t at = 0; at < idx.size() && !rc; at += B) {
-            recon_job j;
-            j.e = e; j.st = nullptr; j.any_punct = false;
-            j.idx.assign(idx.begin() + (long)at, idx.begin() + (long)std::min(idx.size(), at + B));
-            const int nb = (int)j.idx.size(), Wk = e->K / 32, Wm = (e->M + 31) / 32;
+        for (recon_job &j : group_jobs(r, groups[g])) {
+            const int nb = (int)j.idx.size();
             if ((rc = job_stage(&L, j, s))) break;
-            int *d_nch = reinterpret_cast<int *>(j.st->d_in + (size_t)nb * (Wk + Wm) + nb);
             uint32_t *d_counts = e->d_est;
             float *d_q = reinterpret_cast<float *>(d_counts + B * bins);
-            rc = qldpc_qber_estimate_dev(e->qest, j.st->d_bits, e->d_cls, d_nch, nullptr, j.any_punct ? j.st->d_erase : nullptr, nullptr, nullptr, nb,
+            rc = qldpc_qber_estimate_dev(e->qest, j.st->d_bits, e->d_cls, job_in(j, j.st->d_in).key_bits, nullptr, j.any_punct ? j.st->d_erase : nullptr, nullptr, nullptr, nb,
                                          d_counts, nullptr, d_q, nullptr, nullptr, nullptr);
             if (rc) break;
             h_est.resize((size_t)nb * (bins + 1));
@@ -1285,15 +1203,14 @@ extern "C" int qldpc_recon_decode_blind(qldpc_recon *r, int n, uint32_t *const *
                                         int *leaked)
 {
     if (!r || !key_words || !key_bits || !qber || !msgs || !parity_words || !blind || !status || n <= 0 || ask_bits < 0) return QLDPC_EINVAL;
-    const bool layered = r->cfg.schedule == QLDPC_SCHED_HLAYERED || (r->cfg.schedule == QLDPC_RECON_SCHED_AUTO && r->cfg.max_blocks > 8);
-    if (!layered && r->cfg.max_blocks <= 8) {
+    if (!cfg_layered(r->cfg) && r->cfg.max_blocks <= 8) {
         qldpc_set_error("recon_decode_blind: the decoders of a session with max_blocks <= 8 and the flooding schedule run on the edge-parallel engine, which has no weakest-VN select");
         return QLDPC_EUNSUPPORTED;
     }
+    const recon_call c = call_bob(n, key_words, key_bits, qber, msgs, parity_words, status, corrected, iterations, blind, ask_bits);
     std::vector<char> skip((size_t)n, 0);
     std::vector<uint32_t> seen;
     for (int i = 0; i < n; i++) {
-        if (!key_words[i] || !parity_words[i]) return QLDPC_EINVAL;
         qldpc_recon_blind &b = blind[i];
         if (b.n_known < 0 || (b.n_known && (!b.pos || !b.bit)) || (ask_bits && !b.ask) || key_bits[i] <= 0) return QLDPC_EINVAL;
         seen.assign((size_t)(key_bits[i] + 31) / 32, 0u);
@@ -1305,17 +1222,10 @@ extern "C" int qldpc_recon_decode_blind(qldpc_recon *r, int n, uint32_t *const *
             }
             seen[(size_t)p >> 5] |= 0x80000000u >> (p & 31);
         }
+        if (int rc = bob_block_begin(r, c, i, nullptr, &skip[(size_t)i])) return rc;
         b.n_ask = 0;
-        status[i] = QLDPC_EDECODE;
-        if (corrected) corrected[i] = 0;
-        if (iterations) iterations[i] = 0;
         if (leaked) leaked[i] = qldpc_recon_leaked_bits(&msgs[i]) + b.n_known;
-        if (check_msg(r, &msgs[i], key_bits[i]) || !(qber[i] >= 0.0f && qber[i] < 0.5f)) { status[i] = QLDPC_ESIZE; skip[(size_t)i] = 1; }
     }
-    recon_call c;
-    memset(&c, 0, sizeof(c));
-    c.bob = true; c.n = n; c.key_bits = key_bits; c.key = key_words; c.qber = qber; c.msgs = msgs; c.parity = parity_words;
-    c.status = status; c.corrected = corrected; c.iterations = iterations; c.blind = blind; c.ask_bits = ask_bits;
     return run_call(r, c, skip);
 }
 

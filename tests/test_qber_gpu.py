@@ -121,11 +121,11 @@ def informative_checks(M, n_punct):
 
 
 def test_sessions_estimate_blocks(q, torch):
-    """qldpc_recon_estimate_blocks on blocks of mixed lengths and rates (two batches in the largest group): a block's estimate and counts alone and in the
+    """qldpc_recon_estimate_blocks on blocks of mixed lengths and rates (three batches in the largest group: the third reuses the first one's staging set): a block's estimate and counts alone and in the
     mix, the number of informative checks from (M, n_punct), the pooled estimate against the true flip rate, keys untouched, the decode unchanged"""
     qtrue = 0.02
     rng = np.random.default_rng(404)
-    spec = [(14500, 0.015)] * 5 + [(15000, 0.05), (3000, 0.02), (14337, 0.014), (14900, 0.016), (14999, 0.015), (15360, 0.015), (14800, 0.048), (15100, 0.015)]
+    spec = [(14500, 0.015)] * 5 + [(15000, 0.05), (3000, 0.02), (14337, 0.014), (14900, 0.016), (14999, 0.015), (15360, 0.015), (14800, 0.048), (15100, 0.015)] + [(14500, 0.015)] * 8
     r = q.Recon(max_blocks=8)
     keys, bobs, msgs, pars, flips = [], [], [], [], 0
     for kb, plan_q in spec:
@@ -135,7 +135,7 @@ def test_sessions_estimate_blocks(q, torch):
         m, par = r.encode(q.pack_bits(alice), kb, plan_q)
         keys.append(q.pack_bits(alice)); bobs.append(q.pack_bits(bob)); msgs.append(m); pars.append(par)
     kbs = [s[0] for s in spec]
-    assert len({(m.code_k, m.code_m) for m in msgs}) >= 3 and sum(1 for m in msgs if (m.code_k, m.code_m) == (msgs[0].code_k, msgs[0].code_m)) > 8
+    assert len({(m.code_k, m.code_m) for m in msgs}) >= 3 and sum(1 for m in msgs if (m.code_k, m.code_m) == (msgs[0].code_k, msgs[0].code_m)) > 16
     assert any(m.n_punct for m in msgs)
     before = [b.copy() for b in bobs]
     qb, counts, pool_q = r.estimate_blocks(bobs, kbs, msgs, pars)
