@@ -576,6 +576,11 @@ int qldpc_recon_disclose_host(const uint32_t *key_words, int key_bits, const int
  */
 int qldpc_recon_estimate_blocks(qldpc_recon *r, int n, const uint32_t *const *key_words, const int *key_bits, const qldpc_recon_msg *msgs,
                                 const uint32_t *const *parity_words, float *qber_out, uint32_t *counts_out, float *pool_qber_out);
+/* The same with runs of checks across punctured parity bits merged into one observation each (qldpc_qber_set_merge below): every session entry keeps a
+ * merged estimator beside its plain one.  A block whose plan punctures half of its parity or more gets 0 from the call above (one informative check
+ * is left at most) and an estimate from this one.  counts_out rows run to QLDPC_QBER_MAX_DEGREE for every code. */
+int qldpc_recon_estimate_blocks_merged(qldpc_recon *r, int n, const uint32_t *const *key_words, const int *key_bits, const qldpc_recon_msg *msgs,
+                                       const uint32_t *const *parity_words, float *qber_out, uint32_t *counts_out, float *pool_qber_out);
 uint32_t qldpc_crc32_words(const uint32_t *words, int n_bits);
 /* The same CRC-32 the way the device verification computes it (rk_verify / rk_crc in qldpc_recon.hip): `lanes` (a power of two) equal
  * chunks, each run through the byte-wise recurrence from a zero register, folded pairwise with x^len multipliers mod the CRC polynomial,
@@ -599,8 +604,17 @@ uint32_t qldpc_crc32_words_chunked(const uint32_t *words, int n_bits, int lanes)
  *   make host and device agree exactly.  A frame without an informative check of degree >= 1: index -1, QBER 0, |LLR| 0; every check satisfied: k = 0.
  *   The POOLED estimate of a call is the same argmax over the sum of its frames' counts.
  *
- * A check next to an erased VN is left out (runs of checks across a punctured parity VN are not merged into one observation); noisy disclosed parity,
- * table / soft channels and estimates from a decoder's ballots mid-run are not built.
+ * A check next to an erased VN is left out -- unless MERGING is turned on (qldpc_qber_set_merge; off by default, and then nothing changes).  It needs a
+ * code whose parity part is an accumulator chain: K = N - M, VN K + c on exactly checks c and c + 1 for c < M - 1, VN K + M - 1 on check M - 1 only, no
+ * other VN >= K in any row (verified edge by edge; QLDPC_EUNSUPPORTED otherwise, the reason in qldpc_last_error()).  VN K + c, c < M - 1, of a frame is a
+ * LINK iff it is erased in that frame; a RUN is a maximal set of consecutive checks h .. t joined by links.  A run of one check is counted as above.  A run
+ * of two or more is one observation: the checks on the two sides of an erased chain VN add up to a parity equation without it, so u = XOR over the run's
+ * checks of s_c and of the values of all their VNs but the links, d = the number of noisy VNs with an odd number of edges into the run (a VN shared by two
+ * checks of the run cancels in u and does not count).  A run is left out when it holds an erased VN other than its own links (an erased VN K + M - 1
+ * included; an erased VN that occurs twice in the run is not cancelled), when it has more than 16 checks, or when d > QLDPC_QBER_MAX_DEGREE.  With merging
+ * on the counts have QLDPC_QBER_MAX_DEGREE + 1 rows whatever D (qldpc_qber_count_rows) and the score tables run to that degree; score, argmax and pool are
+ * the same.  With half of the parity punctured at even spacing the unmerged rule is left with one check and the merged one with M / 2 runs of two.
+ * Noisy disclosed parity, table / soft channels, non-chain codes and estimates from a decoder's ballots mid-run are not built.
  *
  * qldpc_qber_create: QLDPC_EINVAL for n_grid outside 2 .. 1 024, q_lo < 1e-6, q_lo >= q_hi, q_hi >= 0.5, max_frames outside 1 .. 65 535; QLDPC_EUNSUPPORTED
  * for a check degree above QLDPC_QBER_MAX_DEGREE or max_frames x M >= 2^35 (the pooled score could overflow); QLDPC_ENODEV without a device.
@@ -622,14 +636,21 @@ int    qldpc_qber_create(const qldpc_code *code, const qldpc_qber_cfg *cfg, qldp
 void   qldpc_qber_free(qldpc_qber *est);
 size_t qldpc_qber_device_bytes(const qldpc_qber *est);
 int    qldpc_qber_set_stream(qldpc_qber *est, void *hip_stream);      /* NULL = the null stream */
+/* Merging on (non-zero) or off, between calls.  The first call that turns it on verifies the chain (QLDPC_EUNSUPPORTED for any other code), builds and
+ * uploads the repeat table (a byte per edge) and replaces the score tables and the estimator's own count rows by ones of QLDPC_QBER_MAX_DEGREE + 1 rows; it
+ * synchronises the device.  qldpc_qber_count_rows = the rows of d_counts / d_pool_counts as the estimator stands: D + 1, with merging on
+ * QLDPC_QBER_MAX_DEGREE + 1. */
+int    qldpc_qber_set_merge(qldpc_qber *est, int on);
+int    qldpc_qber_count_rows(const qldpc_qber *est);
 /* q[n_grid] / llr[n_grid] (either may be NULL) = the grid and qldpc_bsc_llr of it; returns n_grid */
 int    qldpc_qber_grid(const qldpc_qber *est, float *q, float *llr);
 /*
  * Asynchronous on the estimator's stream.  Inputs as the loads take them: d_bits[n_frames][ceil(N/32)], d_vn_class[N] (NULL = all channel), d_n_channel[n_frames]
  * (NULL = N), d_synd_bits[n_frames][ceil(M/32)] (NULL = zero syndrome), d_erase_bits / d_known_bits / d_value_bits [n_frames][ceil(N/32)] (NULL = none; known
- * needs value).  Outputs, each may be NULL: d_counts[n_frames][D + 1][2] uint32 (cleared on the stream first), d_index[n_frames] (grid index or -1),
+ * needs value).  Outputs, each may be NULL: d_counts[n_frames][rows][2] uint32 (cleared on the stream first; rows = qldpc_qber_count_rows: D + 1, merged
+ * QLDPC_QBER_MAX_DEGREE + 1), d_index[n_frames] (grid index or -1),
  * d_qber[n_frames] (q_k), d_llr_mag[n_frames] (qldpc_bsc_llr(q_k): can be handed to qldpc_load_bits_dev / _short_dev on the same stream),
- * d_pool_counts[D + 1][2] uint64, d_pool_index[1].  An estimator is not re-entrant.  QLDPC_EINVAL: n_frames < 1 or > max_frames.
+ * d_pool_counts[rows][2] uint64, d_pool_index[1].  An estimator is not re-entrant.  QLDPC_EINVAL: n_frames < 1 or > max_frames.
  */
 int    qldpc_qber_estimate_dev(qldpc_qber *est, const uint32_t *d_bits, const uint8_t *d_vn_class, const int *d_n_channel, const uint32_t *d_synd_bits,
                                const uint32_t *d_erase_bits, const uint32_t *d_known_bits, const uint32_t *d_value_bits, int n_frames,
@@ -641,6 +662,13 @@ int    qldpc_qber_table_host(int max_degree, int n_grid, float q_lo, float q_hi,
 int    qldpc_qber_counts_host(const qldpc_code *code, const uint32_t *bits, const uint8_t *vn_class, int n_channel, const uint32_t *synd,
                               const uint32_t *erase, const uint32_t *known, const uint32_t *value, uint32_t *counts);
 int    qldpc_qber_argmax_host(const uint64_t *counts, int max_degree, int n_grid, const int32_t *L1, const int32_t *L0, int *index);
+/* The merged count of ONE frame, arguments as qldpc_qber_counts_host, counts[QLDPC_QBER_MAX_DEGREE + 1][2]; QLDPC_EUNSUPPORTED for a code that is no chain.
+ * qldpc_qber_repeat_table_host: the chain test and the repeat table both sides use, on the transposed check table tab[D][M] (tab[j][c] = VN of slot j of
+ * check c, -1 past its degree): rep[D][M] (NULL = test only) = for every edge the distance back to the nearest earlier check within 15 that holds the
+ * same VN, or 0. */
+int    qldpc_qber_counts_merged_host(const qldpc_code *code, const uint32_t *bits, const uint8_t *vn_class, int n_channel, const uint32_t *synd,
+                                     const uint32_t *erase, const uint32_t *known, const uint32_t *value, uint32_t *counts);
+int    qldpc_qber_repeat_table_host(const int *tab, int N, int M, int D, uint8_t *rep);
 
 /* ------------------------------------------------------------------ privacy amplification ---- */
 /*

@@ -708,6 +708,9 @@ _sig("qldpc_qber_estimate_dev", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp
 _sig("qldpc_qber_table_host", C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp, _fp, _fp])
 _sig("qldpc_qber_counts_host", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp])
 _sig("qldpc_qber_argmax_host", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _ip])
+_sig("qldpc_qber_counts_merged_host", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp])
+_sig("qldpc_qber_set_merge", C.c_int, [_vp, C.c_int])
+_sig("qldpc_qber_count_rows", C.c_int, [_vp])
 
 
 def qber_table_host(max_degree, n_grid=256, q_lo=0.001, q_hi=0.25):
@@ -721,9 +724,10 @@ def qber_table_host(max_degree, n_grid=256, q_lo=0.001, q_hi=0.25):
     return L1, L0, q_, llr
 
 
-def qber_counts_host(code, bits, vn_class=None, n_channel=None, syndrome=None, erase=None, known=None, value=None):
+def qber_counts_host(code, bits, vn_class=None, n_channel=None, syndrome=None, erase=None, known=None, value=None, _merged=False):
     """the counting kernel's mirror for ONE frame (qldpc_qber_counts_host): packed uint32 rows (bits / erase / known / value: ceil(N/32) words, syndrome:
     ceil(M/32)), vn_class uint8 [N], n_channel int (None = N) -> counts uint32 [D + 1, 2]"""
+    fn, what = (_L.qldpc_qber_counts_merged_host, "qber_counts_merged_host") if _merged else (_L.qldpc_qber_counts_host, "qber_counts_host")
     Wn, Wm = (code.N + 31) // 32, (code.M + 31) // 32
 
     def row(a, W, name):
@@ -731,18 +735,24 @@ def qber_counts_host(code, bits, vn_class=None, n_channel=None, syndrome=None, e
             return None
         a = np.ascontiguousarray(a, dtype=np.uint32).ravel()
         if a.size != W:
-            raise QldpcError(-6, "qber_counts_host: %s has %d words, need %d" % (name, a.size, W))
+            raise QldpcError(-6, "%s: %s has %d words, need %d" % (what, name, a.size, W))
         return a
     b, s, e, k, v = row(bits, Wn, "bits"), row(syndrome, Wm, "syndrome"), row(erase, Wn, "erase"), row(known, Wn, "known"), row(value, Wn, "value")
     cls = None
     if vn_class is not None:
         cls = np.ascontiguousarray(vn_class, dtype=np.uint8).ravel()
         if cls.size != code.N:
-            raise QldpcError(-6, "qber_counts_host: vn_class has %d entries, N = %d" % (cls.size, code.N))
-    counts = np.zeros((_L.qldpc_code_max_cn_degree(code._h) + 1, 2), np.uint32)
+            raise QldpcError(-6, "%s: vn_class has %d entries, N = %d" % (what, cls.size, code.N))
+    counts = np.zeros((QBER_MAX_DEGREE + 1 if _merged else _L.qldpc_code_max_cn_degree(code._h) + 1, 2), np.uint32)
     p = lambda a: a.ctypes.data_as(_vp) if a is not None else None
-    _chk(_L.qldpc_qber_counts_host(code._h, p(b), p(cls), code.N if n_channel is None else int(n_channel), p(s), p(e), p(k), p(v), p(counts)), "qber_counts_host")
+    _chk(fn(code._h, p(b), p(cls), code.N if n_channel is None else int(n_channel), p(s), p(e), p(k), p(v), p(counts)), what)
     return counts
+
+
+def qber_counts_merged_host(code, bits, vn_class=None, n_channel=None, syndrome=None, erase=None, known=None, value=None):
+    """the merged counting kernel's mirror for ONE frame (qldpc_qber_counts_merged_host): the arguments of qber_counts_host -> counts uint32
+    [QBER_MAX_DEGREE + 1, 2], runs of checks across erased accumulator VNs counted as one observation each; status -7 for a code that is no chain"""
+    return qber_counts_host(code, bits, vn_class, n_channel, syndrome, erase, known, value, _merged=True)
 
 
 def qber_argmax_host(counts, L1, L0):
@@ -761,7 +771,7 @@ class QberEstimator:
     """QBER of every frame from the weight of its syndrome, on the device (qldpc_qber_estimate_dev): needs no decoder, reads the packed rows the
     loads take.  estimate() returns torch tensors; llr_mag can go straight into Decoder.load_bits on the same stream."""
 
-    def __init__(self, code, n_frames, n_grid=256, q_lo=0.001, q_hi=0.25, checks_per_block=0, device=0):
+    def __init__(self, code, n_frames, n_grid=256, q_lo=0.001, q_hi=0.25, checks_per_block=0, device=0, merge=False):
         cfg = QberCfg()
         _L.qldpc_qber_cfg_default(C.byref(cfg))
         cfg.device, cfg.max_frames, cfg.n_grid, cfg.q_lo, cfg.q_hi, cfg.checks_per_block = int(device), int(n_frames), int(n_grid), float(q_lo), float(q_hi), int(checks_per_block)
@@ -772,6 +782,15 @@ class QberEstimator:
         self.max_frames, self.n_grid, self.device = int(n_frames), int(n_grid), int(device)
         self.q, self.llr = np.zeros(self.n_grid, np.float32), np.zeros(self.n_grid, np.float32)
         _chk(_L.qldpc_qber_grid(h, self.q.ctypes.data_as(_fp), self.llr.ctypes.data_as(_fp)), "QberEstimator.grid")
+        self.rows = self.D + 1
+        if merge:
+            self.set_merge(True)
+
+    def set_merge(self, on=True):
+        """merging on or off (qldpc_qber_set_merge): runs of checks across erased accumulator VNs become one observation each, and the counts get
+        QBER_MAX_DEGREE + 1 rows (self.rows); status -7 for a code whose parity part is no accumulator chain"""
+        _chk(_L.qldpc_qber_set_merge(self._h, int(bool(on))), "QberEstimator.set_merge")
+        self.rows = int(_L.qldpc_qber_count_rows(self._h))
 
     def set_stream(self, stream=None):
         torch = _torch()
@@ -783,7 +802,8 @@ class QberEstimator:
 
     def estimate(self, bits, vn_class=None, n_channel=None, syndrome=None, erase=None, known=None, value=None, out=None, index=True, pool=True):
         """bits / erase / known / value int32 [F, ceil(N/32)], syndrome int32 [F, ceil(M/32)], vn_class uint8 [N], n_channel int32 [F] (device tensors)
-        -> dict(index int32 [F], qber float32 [F], llr_mag float32 [F], counts int32 [F, D + 1, 2], pool_counts int64 [D + 1, 2], pool_index int32 [1]);
+        -> dict(index int32 [F], qber float32 [F], llr_mag float32 [F], counts int32 [F, rows, 2], pool_counts int64 [rows, 2], pool_index int32 [1]), rows = D + 1,
+        merged QBER_MAX_DEGREE + 1;
         asynchronous on the estimator's stream.  out = the dict of an earlier call of the same size: its tensors are written again (nothing is
         allocated); index / pool = False: the per-frame estimates / the pool are not asked for (their tensors are left alone)"""
         torch = _torch()
@@ -806,9 +826,9 @@ class QberEstimator:
         dev = bits.device
         if out is None:
             out = dict(index=torch.empty(F, dtype=torch.int32, device=dev), qber=torch.empty(F, dtype=torch.float32, device=dev),
-                       llr_mag=torch.empty(F, dtype=torch.float32, device=dev), counts=torch.empty((F, self.D + 1, 2), dtype=torch.int32, device=dev),
-                       pool_counts=torch.empty((self.D + 1, 2), dtype=torch.int64, device=dev), pool_index=torch.empty(1, dtype=torch.int32, device=dev))
-        assert out["counts"].shape[0] == F
+                       llr_mag=torch.empty(F, dtype=torch.float32, device=dev), counts=torch.empty((F, self.rows, 2), dtype=torch.int32, device=dev),
+                       pool_counts=torch.empty((self.rows, 2), dtype=torch.int64, device=dev), pool_index=torch.empty(1, dtype=torch.int32, device=dev))
+        assert out["counts"].shape[0] == F and out["counts"].shape[1] == self.rows
         ptr = lambda name, on: _vp(out[name].data_ptr()) if on else None
         _chk(_L.qldpc_qber_estimate_dev(self._h, pb, pc, pn, ps, pe, pk, pv, F, ptr("counts", True), ptr("index", index), ptr("qber", index),
                                         ptr("llr_mag", index), ptr("pool_counts", pool), ptr("pool_index", pool)), "QberEstimator.estimate")
@@ -848,6 +868,7 @@ _sig("qldpc_recon_encode_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _
 _sig("qldpc_recon_decode_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _fp, C.POINTER(ReconMsg), C.POINTER(_up), _ip, _ip, _ip])
 _sig("qldpc_crc32_words", C.c_uint32, [_up, C.c_int])
 _sig("qldpc_recon_estimate_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, C.POINTER(ReconMsg), C.POINTER(_up), _fp, _up, _fp])
+_sig("qldpc_recon_estimate_blocks_merged", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, C.POINTER(ReconMsg), C.POINTER(_up), _fp, _up, _fp])
 class ReconBlind(C.Structure):
     _fields_ = [("n_known", C.c_int), ("cap", C.c_int), ("pos", _ip), ("bit", C.POINTER(C.c_uint8)), ("n_ask", C.c_int), ("ask", _ip)]
 
@@ -1893,9 +1914,10 @@ class Recon:
                                           co.ctypes.data_as(_ip), it.ctypes.data_as(_ip)), "Recon.decode_blocks")
         return st, kws, co, it
 
-    def estimate_blocks(self, keys, key_bits, msgs, parities):
+    def estimate_blocks(self, keys, key_bits, msgs, parities, merge=False):
         """Bob's QBER estimate of every block out of its parity message (qldpc_recon_estimate_blocks), before any decode: returns (qber float32 [n],
-        counts uint32 [n, QBER_MAX_DEGREE + 1, 2], pooled qber over the call); keys are not touched"""
+        counts uint32 [n, QBER_MAX_DEGREE + 1, 2], pooled qber over the call); keys are not touched.  merge=True (qldpc_recon_estimate_blocks_merged):
+        runs of checks across punctured parity bits count as one observation each, so a block with half of its parity punctured or more has an estimate"""
         n = len(keys)
         kws = [np.ascontiguousarray(k, dtype=np.uint32) for k in keys]
         pars = [np.ascontiguousarray(p, dtype=np.uint32) for p in parities]
@@ -1904,8 +1926,8 @@ class Recon:
         kb = np.ascontiguousarray(key_bits, dtype=np.int32)
         arr = (ReconMsg * n)(*msgs)
         qb, counts, pool = np.zeros(n, np.float32), np.zeros((n, QBER_MAX_DEGREE + 1, 2), np.uint32), C.c_float(0.0)
-        _chk(_L.qldpc_recon_estimate_blocks(self._h, n, kp, kb.ctypes.data_as(_ip), arr, pp, qb.ctypes.data_as(_fp), counts.ctypes.data_as(_up), C.byref(pool)),
-             "Recon.estimate_blocks")
+        fn = _L.qldpc_recon_estimate_blocks_merged if merge else _L.qldpc_recon_estimate_blocks
+        _chk(fn(self._h, n, kp, kb.ctypes.data_as(_ip), arr, pp, qb.ctypes.data_as(_fp), counts.ctypes.data_as(_up), C.byref(pool)), "Recon.estimate_blocks")
         return qb, counts, float(pool.value)
 
     def decode_blind(self, keys, key_bits, qber, msgs, parities, known, ask_bits):

@@ -8,6 +8,8 @@
  *                       tab[j][c] (-1 past the check's degree), a wavefront folds its checks by effective degree with ballots, one LDS atomic per
  *                       degree present, and the workgroup's histogram [D + 1][2] leaves in one no-return atomic per non-zero bin to the frame's row
  *                       and to the pool's.
+ *   qk_qber_count_merged  the same with runs of checks across erased chain VNs merged into one observation each (qldpc_qber_set_merge): the passes find
+ *                       the heads of the runs and queue them, a thread per queued head gathers its run
  *   qk_qber_argmax      a workgroup per frame, one more for the pool: threads stride over the grid, int64 scores, the reduction keeps the larger
  *                       score and among equals the lower index.
  */
@@ -19,6 +21,7 @@
 #include "qldpc_qber_core.h"
 
 #define QBK_THREADS 256
+#define QBK_AHEAD 4            /* slots of a check's row the merged count loads at a time */
 
 struct qbk_frame_rows {
     const uint32_t *bits;      /* [n_frames][Wn] */
@@ -46,6 +49,33 @@ __device__ static inline void qbk_word(const qbk_frame_rows &in, size_t row, int
     const uint32_t kn = in.known ? in.known[row + w] : 0u;
     qb_collapse_word(in.bits[row + w], in.erase ? in.erase[row + w] : 0u, kn, kn ? in.value[row + w] : 0u, in.cls_rows ? in.cls_rows[w] : 0u,
                      in.cls_rows ? in.cls_rows[(size_t)Wn + w] : 0u, qb_below_word(w, nch), val, noisy, erased);
+}
+
+/* the wavefront's observations (inf: this lane has one, of effective degree d and outcome u) into the workgroup's histogram, one degree at a time */
+__device__ __forceinline__ static void qbk_fold(bool inf, int d, uint32_t u, int lane, uint32_t *hist)
+{
+    unsigned long long todo = __ballot(inf);
+    while (todo) {
+        const int lead = __ffsll(todo) - 1;
+        const int dl = __shfl(d, lead);
+        const unsigned long long same = __ballot(inf && d == dl), odd = __ballot(inf && d == dl && u);
+        if (lane == lead) {
+            atomicAdd(&hist[2 * dl], (uint32_t)__popcll(same));
+            if (odd) atomicAdd(&hist[2 * dl + 1], (uint32_t)__popcll(odd));
+        }
+        todo &= ~same;
+    }
+}
+
+/* the workgroup's histogram to the frame's row and to the pool's, one no-return atomic per non-zero bin */
+__device__ __forceinline__ static void qbk_flush(const uint32_t *hist, int bins, int tid, int f, uint32_t *__restrict__ counts, unsigned long long *__restrict__ pool)
+{
+    for (int i = tid; i < bins; i += QBK_THREADS) {
+        const uint32_t h = hist[i];
+        if (!h) continue;
+        if (counts) atomicAdd(&counts[(size_t)f * bins + i], h);
+        if (pool) atomicAdd(&pool[i], (unsigned long long)h);
+    }
 }
 
 template <bool STAGED>
@@ -81,27 +111,116 @@ __global__ __launch_bounds__(QBK_THREADS) void qk_qber_count(qbk_frame_rows in, 
                 er |= (e >> sh) & 1u;
             }
         }
-        /* the wavefront's informative checks, one degree at a time */
-        const bool inf = c < c1 && !er;
-        unsigned long long todo = __ballot(inf);
-        while (todo) {
-            const int lead = __ffsll(todo) - 1;
-            const int dl = __shfl(d, lead);
-            const unsigned long long same = __ballot(inf && d == dl), odd = __ballot(inf && d == dl && u);
-            if (lane == lead) {
-                atomicAdd(&hist[2 * dl], (uint32_t)__popcll(same));
-                if (odd) atomicAdd(&hist[2 * dl + 1], (uint32_t)__popcll(odd));
+        qbk_fold(c < c1 && !er, d, u, lane, hist);
+    }
+    __syncthreads();
+    qbk_flush(hist, bins, tid, f, counts, pool);
+}
+
+/*
+ * The merged count (qldpc_qber_core.h, MERGING).  A pass of 256 threads looks at 256 checks, a thread per check, and only finds the heads: one or two
+ * erased words, no gather.  The heads go to a queue in LDS; whenever it holds 256 of them a thread per head walks the link bits after it and gathers the
+ * checks of its run, which may reach past the chunk's last check (the staged rows hold the whole frame).  So the lanes that gather are dense however
+ * many checks are no heads -- with half of the parity erased a thread per check would leave every other lane idle through a walk twice as long.  A VN
+ * met before in the run is one byte of the repeat table per edge.  The histogram has QB_MAX_DEGREE + 1 rows whatever D.
+ */
+template <bool STAGED>
+__global__ __launch_bounds__(QBK_THREADS) void qk_qber_count_merged(qbk_frame_rows in, const int *__restrict__ tab, const uint8_t *__restrict__ rep, int N, int M, int D,
+                                                                   int Wn, int Wm, int cpb, uint32_t *__restrict__ counts, unsigned long long *__restrict__ pool)
+{
+    extern __shared__ uint32_t s_qb[];      /* histogram [QB_MAX_DEGREE + 1][2], then (STAGED) rows [3][Wn] */
+    __shared__ int s_q[2 * QBK_THREADS];    /* the queue of heads: fewer than 256 left over plus at most 256 of a pass */
+    __shared__ int s_wn[QBK_THREADS / 64];  /* heads per wavefront of a pass */
+    const int bins = 2 * (QB_MAX_DEGREE + 1), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = blockIdx.y, K = N - M;
+    const size_t row = (size_t)f * Wn;
+    uint32_t *hist = s_qb, *s_val = s_qb + bins, *s_noisy = s_val + Wn, *s_erased = s_noisy + Wn;
+    const int nch = in.n_channel ? in.n_channel[f] : N;
+    for (int i = tid; i < bins; i += QBK_THREADS) hist[i] = 0;
+    if (STAGED)
+        for (int w = tid; w < Wn; w += QBK_THREADS) qbk_word(in, row, w, Wn, nch, &s_val[w], &s_noisy[w], &s_erased[w]);
+    __syncthreads();
+    auto erased_word = [&](int w) -> uint32_t {
+        if (w >= Wn) return 0u;
+        if (STAGED) return s_erased[w];
+        uint32_t a, b, e;
+        qbk_word(in, row, w, Wn, nch, &a, &b, &e);
+        return e;
+    };
+    /* the run of head h into the histogram; every lane of the workgroup calls it, on = this lane has a head */
+    auto count_run = [&](int h, bool on) {
+        uint32_t u = 0, er = 0;
+        int d = 0;
+        bool counted = false;
+        if (on) {
+            const int w0 = (K + h) >> 5;
+            const int len = qb_run_checks(erased_word(w0), erased_word(w0 + 1), K, h, M), t = h + len - 1;
+            counted = len <= QB_MAX_RUN;
+            for (int c = h; counted && c <= t; c++) {
+                if (in.synd) u ^= qb_bit(in.synd + (size_t)f * Wm, c);
+                /* QBK_AHEAD slots of the row and their repeat bytes are loaded before the first of them is looked at: the walk waits for memory once
+                 * per group, not twice per edge (a slot's VN decides whether the next one is read at all) */
+                bool more = true;
+                for (int j0 = 0; more && j0 < D; j0 += QBK_AHEAD) {
+                    int vs[QBK_AHEAD];
+                    uint8_t rs[QBK_AHEAD];
+#pragma unroll
+                    for (int i = 0; i < QBK_AHEAD; i++) {
+                        const size_t at = (size_t)min(j0 + i, D - 1) * M + c;
+                        vs[i] = j0 + i < D ? tab[at] : -1;
+                        rs[i] = rep[at];
+                    }
+#pragma unroll
+                    for (int i = 0; i < QBK_AHEAD; i++) {
+                        const int v = vs[i];
+                        if (v < 0) { more = false; break; }
+                        if (qb_is_link(v, K, h, t)) continue;
+                        const int w = v >> 5, sh = 31 - (v & 31);
+                        uint32_t a, b, e;
+                        if (STAGED) { a = s_val[w]; b = s_noisy[w]; e = s_erased[w]; }
+                        else qbk_word(in, row, w, Wn, nch, &a, &b, &e);
+                        u ^= (a >> sh) & 1u;
+                        er |= (e >> sh) & 1u;
+                        if ((b >> sh) & 1u) d += (qb_earlier_in_run(tab, rep, M, D, rs[i], c, v, h) & 1) ? -1 : 1;
+                    }
+                }
             }
-            todo &= ~same;
+        }
+        qbk_fold(counted && !er && d <= QB_MAX_DEGREE, d, u, lane, hist);
+    };
+    const int c0 = blockIdx.x * cpb, c1 = min(M, c0 + cpb);
+    int qn = 0;      /* heads in the queue, the same in every thread */
+    for (int base = c0; base < c1; base += QBK_THREADS) {
+        const int c = base + tid;
+        bool head = false;
+        if (c < c1 && c > 0) {      /* VN K + c - 1 no link */
+            const int v = K + c - 1;
+            head = !((erased_word(v >> 5) >> (31 - (v & 31))) & 1u);
+        }
+        else head = c < c1;
+        const unsigned long long heads = __ballot(head);
+        if (lane == 0) s_wn[wave] = __popcll(heads);
+        __syncthreads();
+        int at = qn;
+        for (int w = 0; w < QBK_THREADS / 64; w++) {
+            const int n = s_wn[w];
+            if (w < wave) at += n;
+            qn += n;
+        }
+        if (head) s_q[at + __popcll(heads & ((1ull << lane) - 1ull))] = c;
+        __syncthreads();
+        if (qn >= QBK_THREADS) {
+            count_run(s_q[tid], true);
+            const int rest = qn - QBK_THREADS, keep = tid < rest ? s_q[QBK_THREADS + tid] : 0;
+            __syncthreads();
+            if (tid < rest) s_q[tid] = keep;
+            qn = rest;
         }
     }
     __syncthreads();
-    for (int i = tid; i < bins; i += QBK_THREADS) {
-        const uint32_t h = hist[i];
-        if (!h) continue;
-        if (counts) atomicAdd(&counts[(size_t)f * bins + i], h);
-        if (pool) atomicAdd(&pool[i], (unsigned long long)h);
-    }
+    count_run(tid < qn ? s_q[tid] : 0, tid < qn);
+    __syncthreads();
+    qbk_flush(hist, bins, tid, f, counts, pool);
 }
 
 /* block f < n_frames: the frame's counts; block n_frames (launched only when the pool is wanted): the pool's */

@@ -20,16 +20,22 @@ struct qldpc_qber {
     int N, M, D, Wn, Wm, bins;
     int cpb;               /* cfg.checks_per_block (below 256: part of a workgroup idles); 0 = per call from the frame count */
     int staged;            /* the rows of a frame fit the LDS (QLDPC_QBER_STAGE=0: gather from memory all the same) */
+    int no_stage;          /* QLDPC_QBER_STAGE=0 was set at creation */
+    int merge;             /* qldpc_qber_set_merge: runs across erased chain VNs are one observation, counts have QB_MAX_DEGREE + 1 rows */
+    int mstaged;           /* `staged` for the merged kernel's larger histogram */
+    size_t mlds_bytes;
+    uint8_t *d_rep;        /* [D][M] repeat table (qb_earlier_in_run); its presence = the merged tables and buffers are in place */
     int cus;
     size_t lds_bytes, dev_bytes;
     hipStream_t stream;
     int *d_tab;            /* [D][M] transposed check table, -1 past a check's degree */
-    int32_t *d_L1, *d_L0;  /* [D + 1][n_grid] */
+    int32_t *d_L1, *d_L0;  /* [D + 1][n_grid]; after the first qldpc_qber_set_merge(1) [QB_MAX_DEGREE + 1][n_grid], the same rows and more */
     float *d_q, *d_llr;    /* [n_grid] */
     uint32_t *d_cls_rows;  /* [2][Wn] */
-    uint32_t *d_counts;    /* [max_frames][D + 1][2]: used when the caller takes no counts */
-    unsigned long long *d_pool;      /* [D + 1][2] */
+    uint32_t *d_counts;    /* [max_frames][rows][2]: used when the caller takes no counts */
+    unsigned long long *d_pool;      /* [rows][2] */
     std::vector<float> h_q, h_llr;
+    std::vector<int> h_tab;          /* d_tab on the host: qldpc_qber_set_merge verifies the chain and builds the repeat table from it */
 };
 
 extern "C" void qldpc_qber_cfg_default(qldpc_qber_cfg *cfg)
@@ -49,7 +55,7 @@ extern "C" void qldpc_qber_free(qldpc_qber *est)
     if (!est) return;
     (void)hipSetDevice(est->cfg.device);
     (void)hipFree(est->d_tab); (void)hipFree(est->d_L1); (void)hipFree(est->d_L0); (void)hipFree(est->d_q); (void)hipFree(est->d_llr);
-    (void)hipFree(est->d_cls_rows); (void)hipFree(est->d_counts); (void)hipFree(est->d_pool);
+    (void)hipFree(est->d_cls_rows); (void)hipFree(est->d_counts); (void)hipFree(est->d_pool); (void)hipFree(est->d_rep);
     delete est;
 }
 
@@ -84,7 +90,8 @@ extern "C" int qldpc_qber_create(const qldpc_code *code, const qldpc_qber_cfg *c
     e->h_q = q; e->h_llr = llr;
     const size_t staged_bytes = sizeof(uint32_t) * ((size_t)e->bins + 3 * (size_t)e->Wn);
     e->staged = staged_bytes <= QBER_LDS_MAX;
-    if (const char *env = getenv("QLDPC_QBER_STAGE")) if (atoi(env) == 0) e->staged = 0;
+    if (const char *env = getenv("QLDPC_QBER_STAGE")) if (atoi(env) == 0) e->no_stage = 1;
+    if (e->no_stage) e->staged = 0;
     e->lds_bytes = e->staged ? staged_bytes : sizeof(uint32_t) * (size_t)e->bins;
     e->cus = 256;
     (void)hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, cfg->device);
@@ -105,6 +112,7 @@ extern "C" int qldpc_qber_create(const qldpc_code *code, const qldpc_qber_cfg *c
     alloc((void **)&e->d_counts, cbytes);
     alloc((void **)&e->d_pool, sizeof(unsigned long long) * (size_t)e->bins);
     if (rc) { qldpc_set_error("qber_create: device allocation failed"); qldpc_qber_free(e); return rc; }
+    e->h_tab = tab;
     hipError_t he = hipMemcpy(e->d_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(e->d_L1, L1.data(), tbytes, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(e->d_L0, L0.data(), tbytes, hipMemcpyHostToDevice);
@@ -126,6 +134,58 @@ extern "C" int qldpc_qber_set_stream(qldpc_qber *est, void *hip_stream)
     return QLDPC_OK;
 }
 
+extern "C" int qldpc_qber_count_rows(const qldpc_qber *est) { return est ? (est->merge ? QB_MAX_DEGREE + 1 : est->D + 1) : QLDPC_EINVAL; }
+
+/*
+ * Merging on or off (qldpc_qber_core.h, MERGING).  The first call that turns it on verifies the chain, uploads the repeat table and replaces the score
+ * tables and the estimator's own count rows by ones of QB_MAX_DEGREE + 1 rows (the first D + 1 table rows are the ones they replace, so the unmerged
+ * call reads what it read before).  Not to be called while a call of the estimator is in flight.
+ */
+extern "C" int qldpc_qber_set_merge(qldpc_qber *est, int on)
+{
+    if (!est) return QLDPC_EINVAL;
+    if (!on || est->d_rep) { est->merge = on != 0; return QLDPC_OK; }
+    const qldpc_qber_cfg &cfg = est->cfg;
+    const int M = est->M, D = est->D, R = QB_MAX_DEGREE + 1;
+    std::vector<uint8_t> rep((size_t)D * (size_t)M);
+    int rc = qldpc_qber_repeat_table_host(est->h_tab.data(), est->N, M, D, rep.data());
+    if (rc) return rc;
+    std::vector<int32_t> L1((size_t)R * (size_t)cfg.n_grid), L0(L1.size());
+    if ((rc = qldpc_qber_table_host(QB_MAX_DEGREE, cfg.n_grid, cfg.q_lo, cfg.q_hi, L1.data(), L0.data(), nullptr, nullptr))) return rc;
+    HIPCHK(hipSetDevice(cfg.device));
+    const size_t tbytes = sizeof(int32_t) * L1.size(), cbytes = sizeof(uint32_t) * (size_t)cfg.max_frames * 2 * (size_t)R, pbytes = sizeof(unsigned long long) * 2 * (size_t)R;
+    int32_t *d_L1 = nullptr, *d_L0 = nullptr;
+    uint32_t *d_counts = nullptr;
+    unsigned long long *d_pool = nullptr;
+    uint8_t *d_rep = nullptr;
+    hipError_t he = hipMalloc((void **)&d_L1, tbytes);
+    if (he == hipSuccess) he = hipMalloc((void **)&d_L0, tbytes);
+    if (he == hipSuccess) he = hipMalloc((void **)&d_counts, cbytes);
+    if (he == hipSuccess) he = hipMalloc((void **)&d_pool, pbytes);
+    if (he == hipSuccess) he = hipMalloc((void **)&d_rep, rep.size());
+    if (he == hipSuccess) he = hipMemcpy(d_L1, L1.data(), tbytes, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(d_L0, L0.data(), tbytes, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(d_rep, rep.data(), rep.size(), hipMemcpyHostToDevice);
+    const size_t staged_bytes = sizeof(uint32_t) * (2 * (size_t)R + 3 * (size_t)est->Wn);
+    const int mstaged = staged_bytes <= QBER_LDS_MAX && !est->no_stage;
+    const size_t mlds = mstaged ? staged_bytes : sizeof(uint32_t) * 2 * (size_t)R;
+    if (he == hipSuccess && mlds > 48 * 1024)
+        he = hipFuncSetAttribute((const void *)&qk_qber_count_merged<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds);
+    if (he == hipSuccess) he = hipDeviceSynchronize();      /* no call reads the rows that are freed below */
+    if (he != hipSuccess) {
+        (void)hipFree(d_L1); (void)hipFree(d_L0); (void)hipFree(d_counts); (void)hipFree(d_pool); (void)hipFree(d_rep);
+        qldpc_set_error("qber_set_merge: %s", hipGetErrorString(he));
+        return QLDPC_EHIP;
+    }
+    (void)hipFree(est->d_L1); (void)hipFree(est->d_L0); (void)hipFree(est->d_counts); (void)hipFree(est->d_pool);
+    est->dev_bytes += 2 * (tbytes - sizeof(int32_t) * (size_t)(D + 1) * (size_t)cfg.n_grid) + (cbytes - sizeof(uint32_t) * (size_t)cfg.max_frames * (size_t)est->bins)
+                      + (pbytes - sizeof(unsigned long long) * (size_t)est->bins) + rep.size();
+    est->d_L1 = d_L1; est->d_L0 = d_L0; est->d_counts = d_counts; est->d_pool = d_pool; est->d_rep = d_rep;
+    est->mstaged = mstaged; est->mlds_bytes = mlds;
+    est->merge = 1;
+    return QLDPC_OK;
+}
+
 extern "C" int qldpc_qber_grid(const qldpc_qber *est, float *q, float *llr)
 {
     if (!est) return QLDPC_EINVAL;
@@ -143,12 +203,13 @@ extern "C" int qldpc_qber_estimate_dev(qldpc_qber *est, const uint32_t *d_bits, 
     HIPCHK(hipSetDevice(est->cfg.device));
     hipStream_t s = est->stream;
     const int M = est->M, Wn = est->Wn;
+    const int bins = est->merge ? 2 * (QB_MAX_DEGREE + 1) : est->bins, Dsc = bins / 2 - 1;      /* count rows in use, and the score's largest degree */
     const bool want_index = d_index || d_qber || d_llr_mag, want_pool = d_pool_counts || d_pool_index;
     if (!d_counts && !want_index && !want_pool) return QLDPC_OK;
     uint32_t *counts = d_counts ? d_counts : est->d_counts;
     unsigned long long *pool = want_pool ? (d_pool_counts ? reinterpret_cast<unsigned long long *>(d_pool_counts) : est->d_pool) : nullptr;
-    HIPCHK(hipMemsetAsync(counts, 0, sizeof(uint32_t) * (size_t)n_frames * (size_t)est->bins, s));
-    if (pool) HIPCHK(hipMemsetAsync(pool, 0, sizeof(unsigned long long) * (size_t)est->bins, s));
+    HIPCHK(hipMemsetAsync(counts, 0, sizeof(uint32_t) * (size_t)n_frames * (size_t)bins, s));
+    if (pool) HIPCHK(hipMemsetAsync(pool, 0, sizeof(unsigned long long) * (size_t)bins, s));
     qbk_frame_rows in = {d_bits, d_erase_bits, d_known_bits, d_value_bits, d_synd_bits, d_n_channel, nullptr};
     if (d_vn_class) {
         hipLaunchKernelGGL(qk_qber_class_rows, dim3((unsigned)((Wn + QBK_THREADS - 1) / QBK_THREADS)), dim3(QBK_THREADS), 0, s, d_vn_class, est->d_cls_rows, est->N, Wn);
@@ -163,7 +224,11 @@ extern "C" int qldpc_qber_estimate_dev(qldpc_qber *est, const uint32_t *d_bits, 
         cpb = (passes + chunks - 1) / chunks * QBK_THREADS;
     }
     const dim3 grid((unsigned)((M + cpb - 1) / cpb), (unsigned)n_frames);
-    if (est->staged)
+    if (est->merge && est->mstaged)
+        hipLaunchKernelGGL(qk_qber_count_merged<true>, grid, dim3(QBK_THREADS), est->mlds_bytes, s, in, est->d_tab, est->d_rep, est->N, M, est->D, Wn, est->Wm, cpb, counts, pool);
+    else if (est->merge)
+        hipLaunchKernelGGL(qk_qber_count_merged<false>, grid, dim3(QBK_THREADS), est->mlds_bytes, s, in, est->d_tab, est->d_rep, est->N, M, est->D, Wn, est->Wm, cpb, counts, pool);
+    else if (est->staged)
         hipLaunchKernelGGL(qk_qber_count<true>, grid, dim3(QBK_THREADS), est->lds_bytes, s, in, est->d_tab, est->N, M, est->D, Wn, est->Wm, cpb, counts, pool);
     else
         hipLaunchKernelGGL(qk_qber_count<false>, grid, dim3(QBK_THREADS), est->lds_bytes, s, in, est->d_tab, est->N, M, est->D, Wn, est->Wm, cpb, counts, pool);
@@ -171,7 +236,7 @@ extern "C" int qldpc_qber_estimate_dev(qldpc_qber *est, const uint32_t *d_bits, 
     if (want_index || d_pool_index) {
         /* without per-frame outputs only the pool's workgroup runs: it is block n_frames of a launch of n_frames + 1, so the frames' blocks are kept and write nothing */
         const unsigned blocks = (unsigned)n_frames + (d_pool_index ? 1u : 0u);
-        hipLaunchKernelGGL(qk_qber_argmax, dim3(blocks), dim3(QBK_THREADS), 0, s, counts, pool, est->D, est->cfg.n_grid, est->d_L1, est->d_L0, est->d_q, est->d_llr, n_frames,
+        hipLaunchKernelGGL(qk_qber_argmax, dim3(blocks), dim3(QBK_THREADS), 0, s, counts, pool, Dsc, est->cfg.n_grid, est->d_L1, est->d_L0, est->d_q, est->d_llr, n_frames,
                            d_index, d_qber, d_llr_mag, d_pool_index);
         LAUNCHCHK();
     }

@@ -14,6 +14,19 @@
  *            p_d(q) = (1 - (1 - 2 q)^d) / 2, q_k = q_lo (q_hi / q_lo)^(k / (n_grid - 1)); tables [D + 1][n_grid], row 0 zero
  *   estimate the smallest k with maximal S_k over a full scan; -1 when no informative check has d >= 1
  *
+ * MERGING (opt-in, qldpc_qber_set_merge; off = everything above and nothing else), for a code whose parity part is an accumulator chain: K = N - M, VN K + c
+ * lies on exactly checks c and c + 1 for c < M - 1, VN K + M - 1 on check M - 1 only, no other VN >= K in any row (qldpc_qber_repeat_table_host verifies it edge by
+ * edge).  The checks on the two sides of an erased chain VN add up to one parity equation without it:
+ *   link     VN K + c, c < M - 1, of frame f is a link iff its state in that frame is erased (by class or by erase bit; known wins, so a known one is exact)
+ *   run      a maximal set of consecutive checks h .. t joined by links; check c is a head iff c = 0 or VN K + c - 1 is no link (qb_run_checks)
+ *   one check   counted exactly as above
+ *   two or more one observation: u = XOR over the run's checks of s_c and of the values of all their VNs but the links (each occurs twice and cancels),
+ *            d = the number of noisy VNs with an odd number of edges into the run -- a VN shared by two checks of the run cancels in u and does not
+ *            count in d (qb_earlier_in_run over the repeat table; the graph layer admits no VN twice in one row)
+ *   left out a run with an erased VN other than its own links (an erased VN K + M - 1 included; an erased VN that occurs twice is not cancelled), with
+ *            more than QB_MAX_RUN checks, or with d > QB_MAX_DEGREE
+ *   counts   [QB_MAX_DEGREE + 1][2] whatever D; tables to degree QB_MAX_DEGREE; score, argmax and pool as above
+ *
  * The state is resolved 32 VNs at a time on the packed rows (qb_collapse_word); the class map enters as two packed rows (pinned, punctured) that
  * are built once per call (qb_class_word).  Integer scores make host and device agree exactly whatever the order of summation.
  */
@@ -29,6 +42,7 @@
 #endif
 
 #define QB_MAX_DEGREE 63          /* D above this: QLDPC_EUNSUPPORTED */
+#define QB_MAX_RUN 16             /* merging: a run of more checks is left out (bounds a thread's walk) */
 #define QB_MAX_GRID 1024
 #define QB_SCALE 16777216.0       /* 2^24 table units per nat */
 #define QB_MIN_Q_LO 1e-6          /* |log p_1(q_lo)| 2^24 < 2^28, so that a score over fewer than 2^35 checks fits int64 */
@@ -61,6 +75,30 @@ QB_FN void qb_collapse_word(uint32_t bits, uint32_t erase, uint32_t known, uint3
     *val = (bits & ~known) | (value & known);
     *erased = (punct | erase) & ~known;
     *noisy = ~pinned & ~punct & below & ~erase & ~known;
+}
+/* merging: the number of checks of the run that starts at head h, QB_MAX_RUN + 1 for any longer one.  e0 / e1 = the erased words that hold VN K + h and
+ * the 32 VNs after that word (0 past the row): the at most QB_MAX_RUN link bits looked at lie in them */
+QB_FN int qb_run_checks(uint32_t e0, uint32_t e1, int K, int h, int M)
+{
+    const uint64_t win = (((uint64_t)e0 << 32) | (uint64_t)e1) << ((K + h) & 31);
+    int n = 0;
+    while (n < QB_MAX_RUN && h + n < M - 1 && ((win >> (63 - n)) & 1u)) n++;
+    return n + 1;
+}
+/* merging: is VN v one of the links K + h .. K + t - 1 of the run h .. t? */
+QB_FN int qb_is_link(int v, int K, int h, int t) { return v >= K + h && v < K + t; }
+/* merging: how many checks h .. c - 1 of the run hold VN v = tab[j][c], r = rep[j][c].  tab[D][M] = the transposed check table (-1 past a check's
+ * degree), rep[D][M] = for every edge the distance back to the nearest earlier check within QB_MAX_RUN - 1 that holds the same VN, or 0 */
+QB_FN int qb_earlier_in_run(const int *tab, const uint8_t *rep, int M, int D, int r, int c, int v, int h)
+{
+    int n = 0;
+    while (r && c - r >= h) {
+        n++; c -= r;
+        int j = 0;
+        while (j < D - 1 && tab[(size_t)j * M + c] != v) j++;      /* the rare third occurrence: v's slot in that row */
+        r = rep[(size_t)j * M + c];
+    }
+    return n;
 }
 /* S_k of counts cnt[D + 1][2] (uint64: a frame's counts widened, or the pool) */
 QB_FN int64_t qb_score(const uint64_t *cnt, int D, const int32_t *L1, const int32_t *L0, int n_grid, int k)

@@ -52,7 +52,8 @@ struct recon_entry {
     int next_set;
     uint32_t *d_blind;    /* blind rounds (allocated by the first one): known | value | candidate | weakest rows, [4][max_blocks][Wn] */
     qldpc_qber *qest;     /* qldpc_recon_estimate_blocks: the entry's estimator (with the entry when the session preloads, else at the first such call) */
-    uint32_t *d_est;      /* its outputs: counts [max_blocks][D + 1][2] | QBER [max_blocks] */
+    qldpc_qber *qest_m;   /* qldpc_recon_estimate_blocks_merged: a second one with merging on (qldpc_qber_set_merge) */
+    uint32_t *d_est;      /* their outputs: counts [max_blocks][rows][2] | QBER [max_blocks], sized for the merged rows */
 };
 
 /* a lane = one host worker with a compute stream and a copy stream: the rate groups of a call run side by side, one lane each */
@@ -247,6 +248,7 @@ __global__ __launch_bounds__(256) void rk_disclose(const uint32_t *__restrict__ 
 static void entry_free(recon_entry &e)
 {
     qldpc_qber_free(e.qest);
+    qldpc_qber_free(e.qest_m);
     qldpc_decoder_free(e.dec);
     qldpc_encoder_free(e.enc);
     qldpc_code_free(e.code);
@@ -506,18 +508,20 @@ static int build_code(const qldpc_recon_cfg &cfg, int K, int M, qldpc_code **out
     return cfg.peg_depth > 0 ? qldpc_code_ira_peg(N, K, 0.125f, 11, 3, cfg.peg_depth, cfg.seed, out) : qldpc_code_ira(N, K, 0.125f, 11, 3, cfg.seed, out);
 }
 
-/* the estimator of an entry and its output rows (qldpc_recon_estimate_blocks) */
-static int entry_estimator(const qldpc_recon *r, recon_entry &e)
+/* an estimator of an entry, plain or merged, and the output rows the two share (qldpc_recon_estimate_blocks, _merged) */
+static int entry_estimator(const qldpc_recon *r, recon_entry &e, bool merge)
 {
-    if (e.qest) return QLDPC_OK;
+    qldpc_qber *&est = merge ? e.qest_m : e.qest;
+    if (est) return QLDPC_OK;
     qldpc_qber_cfg qc;
     qldpc_qber_cfg_default(&qc);
     qc.device = r->cfg.device; qc.max_frames = r->cfg.max_blocks;
-    int rc = qldpc_qber_create(e.code, &qc, &e.qest);
+    int rc = qldpc_qber_create(e.code, &qc, &est);
+    if (!rc && merge && (rc = qldpc_qber_set_merge(est, 1))) { qldpc_qber_free(est); est = nullptr; }
     if (rc) return rc;
-    const size_t bins = 2 * (size_t)(qldpc_code_max_cn_degree(e.code) + 1);
+    const size_t bins = 2 * (size_t)(QLDPC_QBER_MAX_DEGREE + 1);
     if (!e.d_est && hipMalloc((void **)&e.d_est, sizeof(uint32_t) * (size_t)r->cfg.max_blocks * (bins + 1)) != hipSuccess) {
-        qldpc_qber_free(e.qest); e.qest = nullptr;
+        qldpc_qber_free(est); est = nullptr;
         qldpc_set_error("recon: device allocation for the QBER estimator failed");
         return QLDPC_ENOMEM;
     }
@@ -569,7 +573,8 @@ static int get_entry(qldpc_recon *r, int K, int M, recon_entry **out, qldpc_code
         for (int i = 0; i < K; i++) cls[(size_t)i] = (uint8_t)QLDPC_VN_CHANNEL;
         if (hipMemcpy(e.d_cls, cls.data(), (size_t)N, hipMemcpyHostToDevice) != hipSuccess) rc = QLDPC_EHIP;
     }
-    if (!rc && r->cfg.preload) rc = entry_estimator(r, e);      /* nothing is allocated per block later */
+    if (!rc && r->cfg.preload) rc = entry_estimator(r, e, false);      /* nothing is allocated per block later */
+    if (!rc && r->cfg.preload) rc = entry_estimator(r, e, true);
     if (rc) { entry_free(e); return rc; }
     if (r->profiling) qldpc_profile_enable(e.dec, 1);
     r->cache.push_front(e);      /* the cache is trimmed to `keep` entries at the end of the call (cache_trim): nothing in use is evicted */
@@ -1129,8 +1134,8 @@ extern "C" int qldpc_recon_decode_blocks(qldpc_recon *r, int n, uint32_t *const 
  * staging and assembly (job_stage), then the entry's estimator in place of the decoder, one job at a time on the first lane.  The pooled estimate is
  * taken on the host from the counts of all blocks summed by effective degree (the codes of a call differ in their largest check degree).
  */
-extern "C" int qldpc_recon_estimate_blocks(qldpc_recon *r, int n, const uint32_t *const *key_words, const int *key_bits, const qldpc_recon_msg *msgs,
-                                           const uint32_t *const *parity_words, float *qber_out, uint32_t *counts_out, float *pool_qber_out)
+static int estimate_blocks(qldpc_recon *r, bool merge, int n, const uint32_t *const *key_words, const int *key_bits, const qldpc_recon_msg *msgs,
+                           const uint32_t *const *parity_words, float *qber_out, uint32_t *counts_out, float *pool_qber_out)
 {
     if (!r || !key_words || !key_bits || !msgs || !parity_words || !qber_out || n <= 0) return QLDPC_EINVAL;
     const size_t BINS = 2 * (QLDPC_QBER_MAX_DEGREE + 1);
@@ -1151,17 +1156,18 @@ extern "C" int qldpc_recon_estimate_blocks(qldpc_recon *r, int n, const uint32_t
     rc = call_groups(r, call, skip, groups);
     for (size_t g = 0; g < groups.size() && !rc; g++) {
         recon_entry *e = groups[g].e;
-        if ((rc = entry_estimator(r, *e))) break;
-        const int D = qldpc_code_max_cn_degree(e->code);
+        if ((rc = entry_estimator(r, *e, merge))) break;
+        qldpc_qber *est = merge ? e->qest_m : e->qest;
+        const int D = qldpc_qber_count_rows(est) - 1;
         const size_t bins = 2 * (size_t)(D + 1);
         max_d = std::max(max_d, D);
-        if ((rc = qldpc_qber_set_stream(e->qest, (void *)s))) break;
+        if ((rc = qldpc_qber_set_stream(est, (void *)s))) break;
         for (recon_job &j : group_jobs(r, groups[g])) {
             const int nb = (int)j.idx.size();
             if ((rc = job_stage(&L, j, s))) break;
             uint32_t *d_counts = e->d_est;
             float *d_q = reinterpret_cast<float *>(d_counts + B * bins);
-            rc = qldpc_qber_estimate_dev(e->qest, j.st->d_bits, e->d_cls, job_in(j, j.st->d_in).key_bits, nullptr, j.any_punct ? j.st->d_erase : nullptr, nullptr, nullptr, nb,
+            rc = qldpc_qber_estimate_dev(est, j.st->d_bits, e->d_cls, job_in(j, j.st->d_in).key_bits, nullptr, j.any_punct ? j.st->d_erase : nullptr, nullptr, nullptr, nb,
                                          d_counts, nullptr, d_q, nullptr, nullptr, nullptr);
             if (rc) break;
             h_est.resize((size_t)nb * (bins + 1));
@@ -1191,6 +1197,19 @@ extern "C" int qldpc_recon_estimate_blocks(qldpc_recon *r, int n, const uint32_t
     }
     cache_trim(r);
     return rc;
+}
+
+extern "C" int qldpc_recon_estimate_blocks(qldpc_recon *r, int n, const uint32_t *const *key_words, const int *key_bits, const qldpc_recon_msg *msgs,
+                                           const uint32_t *const *parity_words, float *qber_out, uint32_t *counts_out, float *pool_qber_out)
+{
+    return estimate_blocks(r, false, n, key_words, key_bits, msgs, parity_words, qber_out, counts_out, pool_qber_out);
+}
+
+/* the same through the entries' merged estimators: runs of checks across punctured parity bits are one observation each */
+extern "C" int qldpc_recon_estimate_blocks_merged(qldpc_recon *r, int n, const uint32_t *const *key_words, const int *key_bits, const qldpc_recon_msg *msgs,
+                                                  const uint32_t *const *parity_words, float *qber_out, uint32_t *counts_out, float *pool_qber_out)
+{
+    return estimate_blocks(r, true, n, key_words, key_bits, msgs, parity_words, qber_out, counts_out, pool_qber_out);
 }
 
 /*

@@ -15,6 +15,15 @@ BSC, the parity VNs disclosed (class map: pinned); the all-zero codeword -- in o
   spread      per-frame estimate minus the frame's empirical flip rate over its noisy VNs: mean and standard deviation, grids of 256 and 1 024 points, and
               the pooled estimate
 
+With --merge the tool measures the merged form instead (qldpc_qber_set_merge: runs of checks across erased parity VNs are one observation each) and
+writes profiles/qber_merge_cost.json:
+
+    timeout -k 10 600 python tools/qber_cost.py --merge
+
+The same shape and frames, one process, hipEvent ms, median of 7: (1) the unmerged call, (2) the merged call with nothing erased, (3) / (4) the merged call
+with 25 % / 49 % of the parity erased, evenly spaced; for (3) and (4) also the unmerged call on the same inputs.  Every leg: the whole call, the counting kernel
+alone, the observations per frame and the spread of the per-frame estimate against the frame's empirical flip rate.  Expected: at most 2 x leg 1 at 49 %.
+
 No threshold: the file is the measurement.
 """
 import argparse
@@ -43,12 +52,58 @@ def timed(torch, fn, reps):
     return dict(ms=float(np.median(ms)), ms_all=[float(x) for x in ms])
 
 
+def spaced(M, p):
+    """the sessions' evenly spaced puncture pattern: position j of M is erased iff floor((j + 1) p / M) > floor(j p / M)"""
+    j = np.arange(M, dtype=np.int64)
+    return ((j + 1) * p // M > j * p // M).astype(np.uint8)
+
+
+def merge_legs(q, torch, args, code, bits, d_cls, d_nch, emp_key, dev):
+    F, M = args.frames, N - K
+    plain, merged = q.QberEstimator(code, F), q.QberEstimator(code, F, merge=True)
+    plain.set_stream(); merged.set_stream()
+    k0 = int(np.searchsorted(plain.q, QBER))
+    out = dict(workload="N %d K %d IRA (M %d, check degrees <= %d), %d frames, q = %g, all-zero codeword; key VNs through the BSC, parity pinned, erased parity by "
+                        "an erase row per frame" % (N, K, M, code.max_cn_degree, F, QBER), grid_step_at_q=float(plain.q[k0] - plain.q[k0 - 1]),
+               device_bytes=dict(unmerged=plain.device_bytes(), merged=merged.device_bytes()))
+
+    def leg(est, a):
+        res = est.estimate(*a)
+        t = dict(call=timed(torch, lambda: est.estimate(*a, out=res), args.reps),
+                 counting=timed(torch, lambda: est.estimate(*a, out=res, index=False, pool=False), args.reps))
+        est.estimate(*a, out=res)
+        torch.cuda.synchronize()
+        k = res["index"].cpu().numpy()
+        err = res["qber"].cpu().numpy().astype(np.float64)[k >= 0] - emp_key[k >= 0]
+        t.update(observations_per_frame=float(res["counts"][:, 1:, 0].sum().item() / F), frames_without_estimate=int((k < 0).sum()),
+                 mean_error=float(err.mean()) if err.size else None, sigma=float(err.std()) if err.size else None,
+                 pooled=float(est.q[int(res["pool_index"].cpu()[0])]), empirical=float(emp_key.mean()))
+        return t
+    out["1_unmerged"] = leg(plain, (bits, d_cls))
+    out["2_merged_nothing_erased"] = leg(merged, (bits, d_cls))
+    for n, pct in ((3, 25), (4, 49)):
+        row = np.zeros(N, np.uint8)
+        row[K:] = spaced(M, M * pct // 100)
+        d_erase = dev(row)[None, :].repeat(F, 1).contiguous()
+        a = (bits, d_cls, d_nch, None, d_erase)
+        out["%d_merged_%d_percent_erased" % (n, pct)] = leg(merged, a)
+        out["%d_unmerged_%d_percent_erased" % (n, pct)] = leg(plain, a)
+    base = out["1_unmerged"]
+    out["ratio_to_leg_1"] = {k: dict(call=v["call"]["ms"] / base["call"]["ms"], counting=v["counting"]["ms"] / base["counting"]["ms"])
+                             for k, v in out.items() if isinstance(v, dict) and "call" in v}
+    print(json.dumps({k: (v["call"]["ms"], v["counting"]["ms"], v["observations_per_frame"], v["sigma"]) for k, v in out.items() if isinstance(v, dict) and "call" in v}), flush=True)
+    json.dump(out, open(args.out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "qber_cost.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--merge", action="store_true", help="measure the merged form instead: profiles/qber_merge_cost.json")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--frames", type=int, default=FRAMES)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "qber_merge_cost.json" if args.merge else "qber_cost.json")
     import torch
 
     import _qldpc_loader
@@ -66,6 +121,8 @@ def main():
     erase_row = np.zeros(N, np.uint8); erase_row[K::4] = 1
     d_cls = torch.from_numpy(cls).cuda()
     d_nch = torch.full((F,), K, dtype=torch.int32, device="cuda")
+    if args.merge:
+        return merge_legs(q, torch, args, code, bits, d_cls, d_nch, emp_key, dev)
     d_erase = dev(erase_row)[None, :].repeat(F, 1).contiguous()
     forms = dict(headline=(bits, d_cls), bits_only=(all_bits,), punctured=(bits, d_cls, d_nch, None, d_erase))
     truth = dict(headline=emp_key, bits_only=emp_all, punctured=emp_key)
