@@ -922,6 +922,61 @@ def privamp_expand_host(v, workbits, seed, final_bits):
     return out
 
 
+# ---- what the batch contexts of the two hashes (PrivAmp, Toeplitz) do with the arguments of a call ---------------------------------
+
+def _hb_words(bits):
+    return [(b + 31) >> 5 if b > 0 else 0 for b in bits.tolist()]
+
+
+def _hb_args(who, n, **arrays):
+    """the per-block argument arrays of a call of n blocks: int32, `seeds` uint32 from any integers"""
+    got = [(np.asarray(v, dtype=np.int64).ravel() & 0xFFFFFFFF).astype(np.uint32) if k == "seeds" else np.ascontiguousarray(v, dtype=np.int32).ravel()
+           for k, v in arrays.items()]
+    for a in got:
+        if a.size != n:
+            raise QldpcError(-6, "%s: %d blocks, %s" % (who, n, ", ".join("%d %s" % (a.size, k) for a, k in zip(got, arrays))))
+    return got
+
+
+def _hb_ptr(a, ctype):
+    """an argument array as its pointer argument; from_buffer costs a third of data_as, which a call of one block notices"""
+    return (ctype * a.size).from_buffer(a) if a.size and a.flags.writeable else a.ctypes.data_as(C.POINTER(ctype))
+
+
+def _hb_rows(who, what, n, rows, need):
+    """host rows as uint32 arrays (such an array stays the same object; what "out": the caller's as they are, or made here) of the words `need`, and their pointers"""
+    if what == "out":
+        rows = [np.zeros(w, np.uint32) for w in need] if rows is None else rows
+    else:
+        rows = [np.ascontiguousarray(r, dtype=np.uint32) for r in rows]
+    for i, r in enumerate(rows):
+        if r.dtype != np.uint32 or not r.flags.c_contiguous or r.size < need[i]:
+            raise QldpcError(-6, "%s: %s[%d] must be a contiguous uint32 array of at least %d words" % (who, what, i, need[i]) if what == "out" else
+                             "%s: block %d has %d %s words, needs %d" % (who, i, r.size, what, need[i]))
+    return rows, (_up * max(n, 1))(*[r.ctypes.data_as(_up) for r in rows])
+
+
+def _hb_dev_rows(torch, who, device, rows, stream):
+    """the device rows of a call, rows = [(name, tensor, rows it must have, words each block needs, note)] with the output rows last (None: made
+    here, as wide as the longest) -> (the output rows, the row stride of every tensor, the stream: torch's current one by default)"""
+    if rows[-1][1] is None:
+        name, _, n, need, note = rows[-1]
+        rows[-1] = (name, torch.zeros((n, max(need, default=1) or 1), dtype=torch.int32, device=rows[0][1].device), n, need, note)
+    strides = []
+    for name, t, count, need, note in rows:
+        if t.dtype != torch.int32 or t.dim() != 2 or t.stride(1) != 1 or not t.is_cuda or t.shape[0] != count:
+            raise QldpcError(-6, "%s: %s must be a device int32 [n, stride] tensor with unit column stride%s" % (who, name, note))
+        strides.append(int(t.stride(0)) if count > 1 else int(t.shape[1]))
+    for name, t, count, need, note in rows:
+        if t.device.index != device:
+            raise QldpcError(-1, "%s: %s are on %s, the context is on device %d" % (who, " / ".join(r[0] for r in rows), " / ".join(str(r[1].device) for r in rows), device))
+    # a row holds shape[1] words even where the rows lie further apart, so the library's row checks use the shape
+    for name, t, count, need, note in rows:
+        if need and max(need) > t.shape[1]:
+            raise QldpcError(-6, "%s: block %d does not fit its rows" % (who, min(i for r in rows for i, w in enumerate(r[3]) if w > r[1].shape[1])))
+    return rows[-1][1], strides, stream if stream is not None else torch.cuda.current_stream(device)
+
+
 class PrivAmp:
     """privAmp_doPrivAmp's hash for batches of blocks of any mix of lengths, one launch per call (qldpc_privamp_blocks*).
     Everything is allocated here; blocks() / blocks_dev() allocate nothing on the device."""
@@ -936,56 +991,25 @@ class PrivAmp:
     def device_bytes(self):
         return int(_L.qldpc_privamp_device_bytes(self._h))
 
-    @staticmethod
-    def _args(n, workbits, seeds, final_bits):
-        wb = np.ascontiguousarray(workbits, dtype=np.int32).ravel()
-        sd = (np.asarray(seeds, dtype=np.int64).ravel() & 0xFFFFFFFF).astype(np.uint32)
-        fb = np.ascontiguousarray(final_bits, dtype=np.int32).ravel()
-        if not (wb.size == sd.size == fb.size == n):
-            raise QldpcError(-6, "PrivAmp: %d blocks, %d workbits, %d seeds, %d final_bits" % (n, wb.size, sd.size, fb.size))
-        return wb, sd, fb
-
     def blocks(self, keys, workbits, seeds, final_bits, out=None):
         """keys: list of uint32 word arrays (bits past workbits[i] are ignored) -> list of ceil(final_bits[i]/32)-word arrays.
         out: arrays to write into instead (a refused call leaves them untouched)"""
         n = len(keys)
-        wb, sd, fb = self._args(n, workbits, seeds, final_bits)
-        kws = [np.ascontiguousarray(k, dtype=np.uint32) for k in keys]
-        for i, k in enumerate(kws):
-            if wb[i] > 0 and k.size < (int(wb[i]) + 31) // 32:
-                raise QldpcError(-6, "PrivAmp.blocks: block %d has %d words, workbits = %d" % (i, k.size, wb[i]))
-        if out is None:
-            out = [np.zeros((max(int(f), 0) + 31) // 32, np.uint32) for f in fb]
-        for i, o in enumerate(out):
-            if o.dtype != np.uint32 or not o.flags.c_contiguous or o.size < (max(int(fb[i]), 0) + 31) // 32:
-                raise QldpcError(-6, "PrivAmp.blocks: out[%d] must be a contiguous uint32 array of ceil(final_bits/32) words" % i)
-        kp = (_up * max(n, 1))(*[k.ctypes.data_as(_up) for k in kws])
-        op = (_up * max(n, 1))(*[o.ctypes.data_as(_up) for o in out])
-        _chk(_L.qldpc_privamp_blocks(self._h, n, kp, wb.ctypes.data_as(_ip), sd.ctypes.data_as(_up), fb.ctypes.data_as(_ip), op), "PrivAmp.blocks")
+        wb, sd, fb = _hb_args("PrivAmp", n, workbits=workbits, seeds=seeds, final_bits=final_bits)
+        kws, kp = _hb_rows("PrivAmp.blocks", "key", n, keys, _hb_words(wb))
+        out, op = _hb_rows("PrivAmp.blocks", "out", n, out, _hb_words(fb))
+        _chk(_L.qldpc_privamp_blocks(self._h, n, kp, _hb_ptr(wb, C.c_int), _hb_ptr(sd, C.c_uint32), _hb_ptr(fb, C.c_int), op), "PrivAmp.blocks")
         return out
 
     def blocks_dev(self, keys_t, workbits, seeds, final_bits, out_t=None, stream=None):
         """keys_t: torch int32 [n, key_stride] on the device -> out_t int32 [n, out_stride] (row i: ceil(final_bits[i]/32) words written,
         the rest left as it is); asynchronous on `stream` (default: torch's current stream)"""
-        torch = _torch()
         n = int(keys_t.shape[0])
-        wb, sd, fb = self._args(n, workbits, seeds, final_bits)
-        if keys_t.dtype != torch.int32 or keys_t.dim() != 2 or keys_t.stride(1) != 1 or not keys_t.is_cuda:
-            raise QldpcError(-6, "PrivAmp.blocks_dev: keys_t must be a device int32 [n, stride] tensor with unit column stride")
-        if out_t is None:
-            out_t = torch.zeros((n, max(1, (int(fb.max(initial=0)) + 31) // 32)), dtype=torch.int32, device=keys_t.device)
-        if out_t.dtype != torch.int32 or out_t.dim() != 2 or out_t.stride(1) != 1 or not out_t.is_cuda or out_t.shape[0] != n:
-            raise QldpcError(-6, "PrivAmp.blocks_dev: out_t must be a device int32 [n, stride] tensor with unit column stride")
-        if keys_t.device.index != self.device or out_t.device.index != self.device:
-            raise QldpcError(-1, "PrivAmp.blocks_dev: keys_t / out_t are on %s / %s, the context is on device %d" % (keys_t.device, out_t.device, self.device))
-        # a row holds shape[1] words even where the rows lie further apart, so the library's row checks use the shape
-        for i in range(n):
-            if (int(wb[i]) + 31) // 32 > keys_t.shape[1] or (int(fb[i]) + 31) // 32 > out_t.shape[1]:
-                raise QldpcError(-6, "PrivAmp.blocks_dev: block %d does not fit its rows" % i)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _chk(_L.qldpc_privamp_blocks_dev(self._h, n, keys_t.data_ptr(), int(keys_t.stride(0)) if n > 1 else int(keys_t.shape[1]), wb.ctypes.data_as(_ip),
-                                         sd.ctypes.data_as(_up), fb.ctypes.data_as(_ip), out_t.data_ptr(),
-                                         int(out_t.stride(0)) if n > 1 else int(out_t.shape[1]), s.cuda_stream), "PrivAmp.blocks_dev")
+        wb, sd, fb = _hb_args("PrivAmp", n, workbits=workbits, seeds=seeds, final_bits=final_bits)
+        out_t, (ks, os_), s = _hb_dev_rows(_torch(), "PrivAmp.blocks_dev", self.device,
+                                           [("keys_t", keys_t, n, _hb_words(wb), ""), ("out_t", out_t, n, _hb_words(fb), "")], stream)
+        _chk(_L.qldpc_privamp_blocks_dev(self._h, n, keys_t.data_ptr(), ks, _hb_ptr(wb, C.c_int), _hb_ptr(sd, C.c_uint32), _hb_ptr(fb, C.c_int),
+                                         out_t.data_ptr(), os_, s.cuda_stream), "PrivAmp.blocks_dev")
         return out_t
 
     def __del__(self):
@@ -1028,18 +1052,21 @@ def toeplitz_seed_words(key_bits, out_bits):
     return int(_L.qldpc_toeplitz_seed_words(int(key_bits), int(out_bits)))
 
 
-def toeplitz_host(key_words, key_bits, seed_words, out_bits, tile_words=0):
-    """y_i = XOR_{j < key_bits} x_j t_(i+j) on the host with the kernel's own window / fold functions, the key consumed in tiles of
-    tile_words (0: the kernel's tile) -> ceil(out_bits/32) words, MSB-first"""
+def _toeplitz_mirror(fn, who, key_words, key_bits, seed_words, out_bits, how):
     kw = np.ascontiguousarray(key_words, dtype=np.uint32)
     sw = np.ascontiguousarray(seed_words, dtype=np.uint32)
     key_bits, out_bits = int(key_bits), int(out_bits)
     if key_bits <= 0 or out_bits < 0 or kw.size < (key_bits + 31) // 32 or sw.size < toeplitz_seed_words(key_bits, out_bits):
-        raise QldpcError(-6, "toeplitz_host: %d key words, key_bits = %d, %d seed words, out_bits = %d" % (kw.size, key_bits, sw.size, out_bits))
+        raise QldpcError(-6, "%s: %d key words, key_bits = %d, %d seed words, out_bits = %d" % (who, kw.size, key_bits, sw.size, out_bits))
     out = np.zeros((out_bits + 31) // 32, np.uint32)
-    _chk(_L.qldpc_toeplitz_host(kw.ctypes.data_as(_up), key_bits, sw.ctypes.data_as(_up), out_bits, int(tile_words), out.ctypes.data_as(_up)),
-         "toeplitz_host")
+    _chk(fn(kw.ctypes.data_as(_up), key_bits, sw.ctypes.data_as(_up), out_bits, int(how), out.ctypes.data_as(_up)), who)
     return out
+
+
+def toeplitz_host(key_words, key_bits, seed_words, out_bits, tile_words=0):
+    """y_i = XOR_{j < key_bits} x_j t_(i+j) on the host with the kernel's own window / fold functions, the key consumed in tiles of
+    tile_words (0: the kernel's tile) -> ceil(out_bits/32) words, MSB-first"""
+    return _toeplitz_mirror(_L.qldpc_toeplitz_host, "toeplitz_host", key_words, key_bits, seed_words, out_bits, tile_words)
 
 
 def toeplitz_ntt_length(key_bits, out_bits):
@@ -1063,15 +1090,7 @@ def toeplitz_ntt_root(log2_len):
 def toeplitz_ntt_host(key_words, key_bits, seed_words, out_bits, pass_log2=0):
     """toeplitz_host by the NTT method on the host: the pass kernels' own functions over the same tiles, the transform in passes of
     pass_log2 index bits (0: the production kernels' 9; every value 1 .. 25 gives the same words)"""
-    kw = np.ascontiguousarray(key_words, dtype=np.uint32)
-    sw = np.ascontiguousarray(seed_words, dtype=np.uint32)
-    key_bits, out_bits = int(key_bits), int(out_bits)
-    if key_bits <= 0 or out_bits < 0 or kw.size < (key_bits + 31) // 32 or sw.size < toeplitz_seed_words(key_bits, out_bits):
-        raise QldpcError(-6, "toeplitz_ntt_host: %d key words, key_bits = %d, %d seed words, out_bits = %d" % (kw.size, key_bits, sw.size, out_bits))
-    out = np.zeros((out_bits + 31) // 32, np.uint32)
-    _chk(_L.qldpc_toeplitz_ntt_host(kw.ctypes.data_as(_up), key_bits, sw.ctypes.data_as(_up), out_bits, int(pass_log2), out.ctypes.data_as(_up)),
-         "toeplitz_ntt_host")
-    return out
+    return _toeplitz_mirror(_L.qldpc_toeplitz_ntt_host, "toeplitz_ntt_host", key_words, key_bits, seed_words, out_bits, pass_log2)
 
 
 class Toeplitz:
@@ -1108,83 +1127,38 @@ class Toeplitz:
     def device_bytes(self):
         return int(_L.qldpc_toeplitz_device_bytes(self._h))
 
-    @staticmethod
-    def _args(n, key_bits, out_bits):
-        kb = np.ascontiguousarray(key_bits, dtype=np.int32).ravel()
-        ob = np.ascontiguousarray(out_bits, dtype=np.int32).ravel()
-        if not (kb.size == ob.size == n):
-            raise QldpcError(-6, "Toeplitz: %d blocks, %d key_bits, %d out_bits" % (n, kb.size, ob.size))
-        return kb, ob
-
     def blocks(self, keys, key_bits, seeds, out_bits, out=None):
         """keys, seeds: lists of uint32 word arrays (key bits past key_bits[i] and seed bits past key_bits[i] + out_bits[i] - 1 are
         ignored) -> list of ceil(out_bits[i]/32)-word arrays.  seeds may also be ONE array: it is uploaded once and shared by the blocks.
         out: arrays to write into instead (a refused call leaves them untouched)"""
         n = len(keys)
-        kb, ob = self._args(n, key_bits, out_bits)
-        kws = [np.ascontiguousarray(k, dtype=np.uint32) for k in keys]
+        kb, ob = _hb_args("Toeplitz", n, key_bits=key_bits, out_bits=out_bits)
         if isinstance(seeds, np.ndarray) and seeds.ndim == 1:
-            one = np.ascontiguousarray(seeds, dtype=np.uint32)
-            sws = [one] * n
-        else:
-            if len(seeds) != n:
-                raise QldpcError(-6, "Toeplitz.blocks: %d blocks, %d seeds" % (n, len(seeds)))
-            same = n > 0 and all(s is seeds[0] for s in seeds)
-            first = np.ascontiguousarray(seeds[0], dtype=np.uint32) if same else None
-            sws = [first if same else np.ascontiguousarray(s, dtype=np.uint32) for s in seeds]
-        for i in range(n):
-            if kb[i] > 0 and kws[i].size < (int(kb[i]) + 31) // 32:
-                raise QldpcError(-6, "Toeplitz.blocks: block %d has %d key words, key_bits = %d" % (i, kws[i].size, kb[i]))
-            if sws[i].size < toeplitz_seed_words(kb[i], ob[i]):
-                raise QldpcError(-6, "Toeplitz.blocks: block %d has %d seed words, %d -> %d bits need %d" %
-                                 (i, sws[i].size, kb[i], ob[i], toeplitz_seed_words(kb[i], ob[i])))
-        if out is None:
-            out = [np.zeros((max(int(f), 0) + 31) // 32, np.uint32) for f in ob]
-        for i, o in enumerate(out):
-            if o.dtype != np.uint32 or not o.flags.c_contiguous or o.size < (max(int(ob[i]), 0) + 31) // 32:
-                raise QldpcError(-6, "Toeplitz.blocks: out[%d] must be a contiguous uint32 array of ceil(out_bits/32) words" % i)
-        kp = (_up * max(n, 1))(*[k.ctypes.data_as(_up) for k in kws])
-        sp = (_up * max(n, 1))(*[s.ctypes.data_as(_up) for s in sws])
-        op = (_up * max(n, 1))(*[o.ctypes.data_as(_up) for o in out])
-        _chk(_L.qldpc_toeplitz_blocks(self._h, n, kp, kb.ctypes.data_as(_ip), sp, ob.ctypes.data_as(_ip), op), "Toeplitz.blocks")
+            seeds = [seeds] * n
+        elif len(seeds) != n:
+            raise QldpcError(-6, "Toeplitz.blocks: %d blocks, %d seeds" % (n, len(seeds)))
+        if n > 0 and all(s is seeds[0] for s in seeds):           # one object: one row for the library, whatever it converts to
+            seeds = [np.ascontiguousarray(seeds[0], dtype=np.uint32)] * n
+        kws, kp = _hb_rows("Toeplitz.blocks", "key", n, keys, _hb_words(kb))
+        sws, sp = _hb_rows("Toeplitz.blocks", "seed", n, seeds, [toeplitz_seed_words(k, o) for k, o in zip(kb.tolist(), ob.tolist())])
+        out, op = _hb_rows("Toeplitz.blocks", "out", n, out, _hb_words(ob))
+        _chk(_L.qldpc_toeplitz_blocks(self._h, n, kp, _hb_ptr(kb, C.c_int), sp, _hb_ptr(ob, C.c_int), op), "Toeplitz.blocks")
         return out
 
     def blocks_dev(self, keys_t, key_bits, seeds_t, out_bits, seed_shared=False, out_t=None, stream=None):
         """keys_t: torch int32 [n, key_stride] on the device; seeds_t: int32 [n, seed_stride], or with seed_shared a 1-D tensor or
         one row that every block reads -> out_t int32 [n, out_stride] (row i: ceil(out_bits[i]/32) words written, the rest left as it
         is); asynchronous on `stream` (default: torch's current stream)"""
-        torch = _torch()
         n = int(keys_t.shape[0])
-        kb, ob = self._args(n, key_bits, out_bits)
-
-        def rows(t, count):
-            return t.dtype == torch.int32 and t.dim() == 2 and t.stride(1) == 1 and t.is_cuda and t.shape[0] == count
-
-        if not rows(keys_t, n):
-            raise QldpcError(-6, "Toeplitz.blocks_dev: keys_t must be a device int32 [n, stride] tensor with unit column stride")
+        kb, ob = _hb_args("Toeplitz", n, key_bits=key_bits, out_bits=out_bits)
         if seed_shared and seeds_t.dim() == 1:
             seeds_t = seeds_t.unsqueeze(0)
-        if not rows(seeds_t, 1 if seed_shared else n):
-            raise QldpcError(-6, "Toeplitz.blocks_dev: seeds_t must be a device int32 [n, stride] tensor with unit column stride (one row with seed_shared)")
-        if out_t is None:
-            out_t = torch.zeros((n, max(1, (int(ob.max(initial=0)) + 31) // 32)), dtype=torch.int32, device=keys_t.device)
-        if not rows(out_t, n):
-            raise QldpcError(-6, "Toeplitz.blocks_dev: out_t must be a device int32 [n, stride] tensor with unit column stride")
-        if keys_t.device.index != self.device or seeds_t.device.index != self.device or out_t.device.index != self.device:
-            raise QldpcError(-1, "Toeplitz.blocks_dev: keys_t / seeds_t / out_t are on %s / %s / %s, the context is on device %d" %
-                             (keys_t.device, seeds_t.device, out_t.device, self.device))
-        # a row holds shape[1] words even where the rows lie further apart, so the library's row checks use the shape
-        for i in range(n):
-            if (int(kb[i]) + 31) // 32 > keys_t.shape[1] or (int(ob[i]) + 31) // 32 > out_t.shape[1] or toeplitz_seed_words(kb[i], ob[i]) > seeds_t.shape[1]:
-                raise QldpcError(-6, "Toeplitz.blocks_dev: block %d does not fit its rows" % i)
-
-        def stride(t):
-            return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
-
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _chk(_L.qldpc_toeplitz_blocks_dev(self._h, n, keys_t.data_ptr(), stride(keys_t), kb.ctypes.data_as(_ip),
-                                          seeds_t.data_ptr(), 0 if seed_shared else stride(seeds_t), ob.ctypes.data_as(_ip),
-                                          out_t.data_ptr(), stride(out_t), s.cuda_stream), "Toeplitz.blocks_dev")
+        rows = [("keys_t", keys_t, n, _hb_words(kb), ""),
+                ("seeds_t", seeds_t, 1 if seed_shared else n, [toeplitz_seed_words(k, o) for k, o in zip(kb.tolist(), ob.tolist())], " (one row with seed_shared)"),
+                ("out_t", out_t, n, _hb_words(ob), "")]
+        out_t, (ks, ss, os_), s = _hb_dev_rows(_torch(), "Toeplitz.blocks_dev", self.device, rows, stream)
+        _chk(_L.qldpc_toeplitz_blocks_dev(self._h, n, keys_t.data_ptr(), ks, _hb_ptr(kb, C.c_int), seeds_t.data_ptr(), 0 if seed_shared else ss,
+                                          _hb_ptr(ob, C.c_int), out_t.data_ptr(), os_, s.cuda_stream), "Toeplitz.blocks_dev")
         return out_t
 
     def __del__(self):

@@ -25,15 +25,12 @@
 #include <cstring>
 #include <new>
 
-#include "../../include/qldpc.h"
-#include "qldpc_graph.h"
+#include "qldpc_hashbatch.h"
 #include "qldpc_hip.h"
 
 #define PAB_FEEDBACK 0xe0000200u
-#define PAB_MAX_BITS (1 << 24)     /* max_key_bits and max_final_bits of a context (qldpc.h states it) */
 #define PAB_AT_LEVELS 19           /* chunk start < 2^24 / 32 words */
 #define PAB_R_LEVELS 20            /* a block's table: level 0 = R (the u_k), level 1 + k = R^(32 2^k), k < 19: the jump to output word w < 2^19 */
-#define PAB_MAX_BLOCKS 65535       /* blocks are the y dimension of the grid */
 #define PAB_LANES 256
 
 /* forward LFSR, c <= 10 bit steps at once (as qldpc_privamp.hip): state = (state << 1) + parity(state & 0xe0000200) */
@@ -79,7 +76,6 @@ __host__ __device__ static inline uint32_t pab_parity(uint32_t x)
     return (uint32_t)__builtin_parity(x);
 #endif
 }
-__host__ __device__ static inline uint32_t pab_tail_mask(int workbits) { return (workbits & 31) ? 0xFFFFFFFFu << (32 - (workbits & 31)) : 0xFFFFFFFFu; }
 __host__ __device__ static inline int pab_bits(uint32_t x)            /* number of table levels that reach x: smallest n with x < 2^n */
 {
     int n = 0;
@@ -183,7 +179,7 @@ __global__ __launch_bounds__(PAB_LANES) void pab_hash(const pab_desc *__restrict
     const uint32_t w = w0 + (uint32_t)t;
     if (w >= outwords) return;
     uint32_t word = pab_out_word(w, d.seed, s_u, s_r);
-    if (w == outwords - 1u) word &= pab_tail_mask((int)d.final_bits);
+    if (w == outwords - 1u) word &= hb_tail_mask((int)d.final_bits);
     outs[d.out_off + w] = word;
 }
 
@@ -225,7 +221,7 @@ extern "C" uint32_t qldpc_privamp_key_functional(const uint32_t *key_words, int 
         const int64_t s64 = (int64_t)l * c;
         if (s64 >= numwords) break;
         const int start = (int)s64, end = start + c < numwords ? start + c : numwords;
-        v ^= pab_fold_chunk(key_words, start, end, numwords, pab_tail_mask(workbits), at_pow);
+        v ^= pab_fold_chunk(key_words, start, end, numwords, hb_tail_mask(workbits), at_pow);
     }
     return v;
 }
@@ -233,7 +229,7 @@ extern "C" uint32_t qldpc_privamp_key_functional(const uint32_t *key_words, int 
 /* host mirror of part (b) */
 extern "C" int qldpc_privamp_expand_host(uint32_t functional, int workbits, uint32_t seed, int final_bits, uint32_t *final_words)
 {
-    if (workbits <= 0 || final_bits < 0 || final_bits > PAB_MAX_BITS) { qldpc_set_error("privamp_expand_host: workbits=%d final_bits=%d", workbits, final_bits); return QLDPC_ESIZE; }
+    if (workbits <= 0 || final_bits < 0 || final_bits > HB_MAX_BITS) { qldpc_set_error("privamp_expand_host: workbits=%d final_bits=%d", workbits, final_bits); return QLDPC_ESIZE; }
     if (final_bits == 0) return QLDPC_OK;
     if (!final_words) return QLDPC_EINVAL;
     const int numwords = (int)(((int64_t)workbits + 31) / 32);
@@ -248,64 +244,43 @@ extern "C" int qldpc_privamp_expand_host(uint32_t functional, int workbits, uint
         for (int b = 0; b < 32; b++) u[k] |= pab_parity(r_pow[b] & u[k - 1]) << b;
     }
     for (uint32_t w = 0; w < outwords; w++) final_words[w] = pab_out_word(w, seed, u, r_pow);
-    final_words[outwords - 1] &= pab_tail_mask(final_bits);
+    final_words[outwords - 1] &= hb_tail_mask(final_bits);
     return QLDPC_OK;
 }
 
 struct qldpc_privamp_ctx {
-    int device, max_blocks, max_key_bits, max_final_bits;
-    size_t key_cap, out_cap;       /* words of the packed key / output areas */
-    size_t in_words;               /* descriptor rows, table numwords and packed keys of a full call: one upload per host call */
-    uint32_t *h_in, *d_in, *h_out, *d_out, *d_at, *d_rtabs;
+    hb_stage st;                   /* the head of a call of n blocks: [n descriptor rows][n table numwords] */
+    uint32_t *d_at, *d_rtabs;
     uint32_t *sort_buf;            /* max_blocks numwords, to number the distinct ones */
-    hipEvent_t done;               /* after the last call's launch: the staging is reused only once that call has run */
-    hipStream_t stream;            /* of the host form */
-    size_t dev_bytes;
 };
 
-/* staging of a call of n blocks: [n descriptor rows][n table numwords][packed keys (host form)] */
+static const hb_names pab_names = {"workbits", "final_bits"};
 static size_t pab_desc_words(int n) { return (size_t)n * (sizeof(pab_desc) / 4); }
 static size_t pab_head_words(int n) { return pab_desc_words(n) + (size_t)n; }
 
 extern "C" void qldpc_privamp_free(qldpc_privamp_ctx *pa)
 {
     if (!pa) return;
-    (void)hipSetDevice(pa->device);
-    if (pa->done) { (void)hipEventSynchronize(pa->done); (void)hipEventDestroy(pa->done); }
-    if (pa->stream) (void)hipStreamDestroy(pa->stream);
-    if (pa->h_in) (void)hipHostFree(pa->h_in);
-    if (pa->h_out) (void)hipHostFree(pa->h_out);
-    if (pa->d_in) (void)hipFree(pa->d_in);
-    if (pa->d_out) (void)hipFree(pa->d_out);
+    hb_free(&pa->st);
     if (pa->d_at) (void)hipFree(pa->d_at);
     if (pa->d_rtabs) (void)hipFree(pa->d_rtabs);
     free(pa->sort_buf);
     delete pa;
 }
 
-static int pab_create(qldpc_privamp_ctx *pa)
+static int pab_create(qldpc_privamp_ctx *pa, int device, const hb_limits *lim)
 {
-    HIPCHK(hipSetDevice(pa->device));
-    const size_t kw = ((size_t)pa->max_key_bits + 31) / 32, ow = ((size_t)pa->max_final_bits + 31) / 32;
-    pa->key_cap = (size_t)pa->max_blocks * kw;
-    pa->out_cap = (size_t)pa->max_blocks * ow;
-    pa->in_words = pab_head_words(pa->max_blocks) + pa->key_cap;
-    const size_t rtab_words = (size_t)pa->max_blocks * PAB_R_LEVELS * 32, at_words = (size_t)PAB_AT_LEVELS * 32;
-    pa->sort_buf = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)pa->max_blocks);
+    const int rc = hb_create(&pa->st, device, lim, pab_head_words(1), 0, "privamp_create", &pab_names);
+    if (rc) return rc;
+    const size_t rtab_words = (size_t)lim->max_blocks * PAB_R_LEVELS * 32, at_words = (size_t)PAB_AT_LEVELS * 32;
+    pa->sort_buf = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)lim->max_blocks);
     if (!pa->sort_buf) return QLDPC_ENOMEM;
-    if (hipHostMalloc((void **)&pa->h_in, 4 * pa->in_words, hipHostMallocDefault) != hipSuccess) return QLDPC_ENOMEM;
-    if (hipHostMalloc((void **)&pa->h_out, 4 * (pa->out_cap ? pa->out_cap : 1), hipHostMallocDefault) != hipSuccess) return QLDPC_ENOMEM;
-    if (hipMalloc((void **)&pa->d_in, 4 * pa->in_words) != hipSuccess) return QLDPC_ENOMEM;
-    if (hipMalloc((void **)&pa->d_out, 4 * (pa->out_cap ? pa->out_cap : 1)) != hipSuccess) return QLDPC_ENOMEM;
     if (hipMalloc((void **)&pa->d_at, 4 * at_words) != hipSuccess) return QLDPC_ENOMEM;
     if (hipMalloc((void **)&pa->d_rtabs, 4 * rtab_words) != hipSuccess) return QLDPC_ENOMEM;
-    pa->dev_bytes = 4 * (pa->in_words + (pa->out_cap ? pa->out_cap : 1) + at_words + rtab_words);
-    HIPCHK(hipStreamCreateWithFlags(&pa->stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&pa->done, hipEventDisableTiming));
+    pa->st.dev_bytes += 4 * (at_words + rtab_words);
     uint32_t at_pow[PAB_AT_LEVELS * 32];
     pab_host_at_pow(at_pow);
     HIPCHK(hipMemcpy(pa->d_at, at_pow, sizeof(at_pow), hipMemcpyHostToDevice));
-    HIPCHK(hipEventRecord(pa->done, pa->stream));
     return QLDPC_OK;
 }
 
@@ -313,28 +288,16 @@ extern "C" int qldpc_privamp_create(int device, int max_blocks, int max_key_bits
 {
     if (!out) return QLDPC_EINVAL;
     *out = nullptr;
-    if (max_blocks > PAB_MAX_BLOCKS) { qldpc_set_error("privamp_create: max_blocks=%d (up to %d)", max_blocks, PAB_MAX_BLOCKS); return QLDPC_ESIZE; }
-    if (max_blocks < 1 || max_key_bits < 1 || max_final_bits < 0 || max_key_bits > PAB_MAX_BITS || max_final_bits > PAB_MAX_BITS) {
-        qldpc_set_error("privamp_create: max_blocks=%d max_key_bits=%d max_final_bits=%d (bits up to %d)", max_blocks, max_key_bits, max_final_bits, PAB_MAX_BITS);
-        return QLDPC_ESIZE;
-    }
-    if ((uint64_t)max_blocks * (((uint64_t)max_key_bits + 31) / 32 + ((uint64_t)max_final_bits + 31) / 32 + 16) >= (1ull << 31)) {
-        qldpc_set_error("privamp_create: %d blocks of %d -> %d bits pass 2^31 staged words", max_blocks, max_key_bits, max_final_bits);
-        return QLDPC_ESIZE;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { qldpc_set_error("no HIP device visible: libqldpc has no CPU fallback"); return QLDPC_ENODEV; }
-    if (device < 0 || device >= ndev) return QLDPC_ENODEV;
     qldpc_privamp_ctx *pa = new (std::nothrow) qldpc_privamp_ctx();
     if (!pa) return QLDPC_ENOMEM;
-    pa->device = device; pa->max_blocks = max_blocks; pa->max_key_bits = max_key_bits; pa->max_final_bits = max_final_bits;
-    const int rc = pab_create(pa);
+    const hb_limits lim = {max_blocks, max_key_bits, max_final_bits};
+    const int rc = pab_create(pa, device, &lim);
     if (rc) { qldpc_privamp_free(pa); return rc; }
     *out = pa;
     return QLDPC_OK;
 }
 
-extern "C" size_t qldpc_privamp_device_bytes(const qldpc_privamp_ctx *pa) { return pa ? pa->dev_bytes : 0; }
+extern "C" size_t qldpc_privamp_device_bytes(const qldpc_privamp_ctx *pa) { return pa ? pa->st.dev_bytes : 0; }
 
 static int pab_cmp_u32(const void *a, const void *b)
 {
@@ -342,61 +305,33 @@ static int pab_cmp_u32(const void *a, const void *b)
     return x < y ? -1 : x > y;
 }
 
-/* argument checks of both forms; nothing is written before every block has passed */
-static int pab_check(const qldpc_privamp_ctx *pa, int n, const int *workbits, const uint32_t *seeds, const int *final_bits, const char *who)
+/* the layout of the call as descriptor rows, and the numbering of the distinct numwords, into the pinned staging; *n_tabs out */
+static hb_sums pab_fill(qldpc_privamp_ctx *pa, int n, const int *workbits, const uint32_t *seeds, const int *final_bits, const hb_strides *strides, int *n_tabs)
 {
-    if (!pa) return QLDPC_EINVAL;
-    if (n < 0) return QLDPC_EINVAL;
-    if (n > pa->max_blocks) { qldpc_set_error("%s: %d blocks, the context holds %d", who, n, pa->max_blocks); return QLDPC_ESIZE; }
-    if (n == 0) return QLDPC_OK;
-    if (!workbits || !seeds || !final_bits) { qldpc_set_error("%s: NULL argument array", who); return QLDPC_EINVAL; }
-    for (int i = 0; i < n; i++) {
-        if (workbits[i] <= 0 || final_bits[i] < 0) { qldpc_set_error("%s: block %d: workbits=%d final_bits=%d", who, i, workbits[i], final_bits[i]); return QLDPC_ESIZE; }
-        if (workbits[i] > pa->max_key_bits) { qldpc_set_error("%s: block %d: workbits=%d, the context holds %d", who, i, workbits[i], pa->max_key_bits); return QLDPC_ESIZE; }
-        if (final_bits[i] > pa->max_final_bits) { qldpc_set_error("%s: block %d: final_bits=%d, the context holds %d", who, i, final_bits[i], pa->max_final_bits); return QLDPC_ESIZE; }
-    }
-    return QLDPC_OK;
-}
-
-/* descriptor rows and the numbering of the distinct numwords into the pinned staging; *n_tabs, *grid_x out */
-static void pab_fill(qldpc_privamp_ctx *pa, int n, const int *workbits, const uint32_t *seeds, const int *final_bits,
-                     size_t key_stride, size_t out_stride, int packed, int *n_tabs, unsigned *grid_x, size_t *key_words, size_t *out_words)
-{
-    pab_desc *descs = (pab_desc *)pa->h_in;
-    uint32_t *tab_nw = pa->h_in + pab_desc_words(n);
+    const hb_row *rows = pa->st.rows;
+    const hb_sums sums = hb_layout(n, workbits, final_bits, nullptr, strides, 0, pa->st.rows);
+    pab_desc *descs = (pab_desc *)pa->st.h_in;
+    uint32_t *tab_nw = pa->st.h_in + pab_desc_words(n);
     int nt = 0;
-    for (int i = 0; i < n; i++) pa->sort_buf[i] = ((uint32_t)workbits[i] + 31u) / 32u;
+    for (int i = 0; i < n; i++) pa->sort_buf[i] = rows[i].key_words;
     qsort(pa->sort_buf, (size_t)n, sizeof(uint32_t), pab_cmp_u32);
     for (int i = 0; i < n; i++)
         if (!i || pa->sort_buf[i] != pa->sort_buf[i - 1]) tab_nw[nt++] = pa->sort_buf[i];
-    size_t koff = 0, ooff = 0;
-    unsigned gx = 0;
     for (int i = 0; i < n; i++) {
-        pab_desc &d = descs[i];
-        d.numwords = ((uint32_t)workbits[i] + 31u) / 32u;
-        d.tail_mask = pab_tail_mask(workbits[i]);
-        d.seed = seeds[i];
-        d.final_bits = (uint32_t)final_bits[i];
-        const uint32_t ow = (d.final_bits + 31u) / 32u;
-        d.key_off = packed ? koff : (uint64_t)i * key_stride;
-        d.out_off = packed ? ooff : (uint64_t)i * out_stride;
         int lo = 0, hi = nt - 1;                                 /* tab_nw is ascending */
-        while (lo < hi) { const int mid = (lo + hi) / 2; if (tab_nw[mid] < d.numwords) lo = mid + 1; else hi = mid; }
-        d.tab = (uint32_t)lo;
-        d.pad = 0;
-        koff += d.numwords; ooff += ow;
-        const unsigned g = (ow + PAB_LANES - 1) / PAB_LANES;
-        if (g > gx) gx = g;
+        while (lo < hi) { const int mid = (lo + hi) / 2; if (tab_nw[mid] < rows[i].key_words) lo = mid + 1; else hi = mid; }
+        descs[i] = pab_desc{rows[i].key_words, hb_tail_mask(workbits[i]), seeds[i], (uint32_t)final_bits[i], rows[i].key_off, rows[i].out_off, (uint32_t)lo, 0};
     }
-    *n_tabs = nt; *grid_x = gx; *key_words = koff; *out_words = ooff;
+    *n_tabs = nt;
+    return sums;
 }
 
-static int pab_launch(qldpc_privamp_ctx *pa, int n, int n_tabs, unsigned grid_x, const uint32_t *d_keys, uint32_t *d_out, hipStream_t s)
+/* widest: the words of the call's longest output row, > 0 */
+static int pab_launch(qldpc_privamp_ctx *pa, int n, int n_tabs, uint32_t widest, const uint32_t *d_keys, uint32_t *d_out, hipStream_t s)
 {
-    if (grid_x == 0) return QLDPC_OK;                            /* every block asks for 0 bits */
-    const uint32_t *d_tab_nw = pa->d_in + pab_desc_words(n);
-    hipLaunchKernelGGL(pab_tables, dim3((unsigned)n_tabs), dim3(64), 0, s, d_tab_nw, pa->d_rtabs);
-    hipLaunchKernelGGL(pab_hash, dim3(grid_x, (unsigned)n), dim3(PAB_LANES), 0, s, (const pab_desc *)pa->d_in, d_keys, d_out, (const uint32_t *)pa->d_at, (const uint32_t *)pa->d_rtabs);
+    const uint32_t *d_in = pa->st.d_in;
+    hipLaunchKernelGGL(pab_tables, dim3((unsigned)n_tabs), dim3(64), 0, s, d_in + pab_desc_words(n), pa->d_rtabs);
+    hipLaunchKernelGGL(pab_hash, dim3((widest + PAB_LANES - 1) / PAB_LANES, (unsigned)n), dim3(PAB_LANES), 0, s, (const pab_desc *)d_in, d_keys, d_out, (const uint32_t *)pa->d_at, (const uint32_t *)pa->d_rtabs);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { qldpc_set_error("privamp_blocks launch: %s", hipGetErrorString(e)); return QLDPC_EHIP; }
     return QLDPC_OK;
@@ -405,54 +340,30 @@ static int pab_launch(qldpc_privamp_ctx *pa, int n, int n_tabs, unsigned grid_x,
 extern "C" int qldpc_privamp_blocks(qldpc_privamp_ctx *pa, int n, const uint32_t *const *key_words, const int *workbits,
                                     const uint32_t *seeds, const int *final_bits, uint32_t *const *final_words)
 {
-    int rc = pab_check(pa, n, workbits, seeds, final_bits, "privamp_blocks");
+    int rc = pa ? hb_check_blocks(&pa->st.lim, n, workbits, final_bits, !seeds, "privamp_blocks", &pab_names) : QLDPC_EINVAL;
     if (rc || n == 0) return rc;
     if (!key_words || !final_words) { qldpc_set_error("privamp_blocks: NULL argument array"); return QLDPC_EINVAL; }
-    for (int i = 0; i < n; i++)
-        if (!key_words[i] || (!final_words[i] && final_bits[i] > 0)) { qldpc_set_error("privamp_blocks: block %d: NULL %s row", i, key_words[i] ? "output" : "key"); return QLDPC_EINVAL; }
-    HIPCHK(hipSetDevice(pa->device));
-    HIPCHK(hipEventSynchronize(pa->done));
+    hb_stage *st = &pa->st;
+    if ((rc = hb_check_rows(n, final_bits, key_words, nullptr, final_words, "privamp_blocks")) || (rc = hb_begin(st))) return rc;
     int n_tabs = 0;
-    unsigned grid_x = 0;
-    size_t kw = 0, ow = 0;
-    pab_fill(pa, n, workbits, seeds, final_bits, 0, 0, 1, &n_tabs, &grid_x, &kw, &ow);
-    if (grid_x == 0) return QLDPC_OK;
+    const hb_sums sums = pab_fill(pa, n, workbits, seeds, final_bits, nullptr, &n_tabs);
+    if (sums.widest_out == 0) return QLDPC_OK;                   /* every block asks for 0 bits */
     const size_t head = pab_head_words(n);
-    const pab_desc *descs = (const pab_desc *)pa->h_in;
-    for (int i = 0; i < n; i++) memcpy(pa->h_in + head + descs[i].key_off, key_words[i], 4 * (size_t)descs[i].numwords);
-    HIPCHK(hipMemcpyAsync(pa->d_in, pa->h_in, 4 * (head + kw), hipMemcpyHostToDevice, pa->stream));
-    rc = pab_launch(pa, n, n_tabs, grid_x, pa->d_in + head, pa->d_out, pa->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(pa->h_out, pa->d_out, 4 * ow, hipMemcpyDeviceToHost, pa->stream));
-    HIPCHK(hipEventRecord(pa->done, pa->stream));
-    HIPCHK(hipStreamSynchronize(pa->stream));
-    for (int i = 0; i < n; i++)
-        if (final_bits[i] > 0) memcpy(final_words[i], pa->h_out + descs[i].out_off, 4 * (size_t)((descs[i].final_bits + 31u) / 32u));
-    return QLDPC_OK;
+    return hb_run_host(st, n, key_words, st->h_in + head, head + sums.key_words, sums.out_words, final_words,
+                       [&](hipStream_t s) { return pab_launch(pa, n, n_tabs, sums.widest_out, st->d_in + head, st->d_out, s); });
 }
 
 extern "C" int qldpc_privamp_blocks_dev(qldpc_privamp_ctx *pa, int n, const uint32_t *d_keys, size_t key_stride, const int *workbits,
                                         const uint32_t *seeds, const int *final_bits, uint32_t *d_out, size_t out_stride, void *hip_stream)
 {
-    int rc = pab_check(pa, n, workbits, seeds, final_bits, "privamp_blocks_dev");
+    int rc = pa ? hb_check_blocks(&pa->st.lim, n, workbits, final_bits, !seeds, "privamp_blocks_dev", &pab_names) : QLDPC_EINVAL;
     if (rc || n == 0) return rc;
     if (!d_keys || !d_out) { qldpc_set_error("privamp_blocks_dev: NULL device pointer"); return QLDPC_EINVAL; }
-    for (int i = 0; i < n; i++) {
-        if (((size_t)workbits[i] + 31) / 32 > key_stride) { qldpc_set_error("privamp_blocks_dev: block %d: workbits=%d pass a key row of %zu words", i, workbits[i], key_stride); return QLDPC_ESIZE; }
-        if (((size_t)final_bits[i] + 31) / 32 > out_stride) { qldpc_set_error("privamp_blocks_dev: block %d: final_bits=%d pass an output row of %zu words", i, final_bits[i], out_stride); return QLDPC_ESIZE; }
-    }
-    HIPCHK(hipSetDevice(pa->device));
-    HIPCHK(hipEventSynchronize(pa->done));                       /* the previous call's descriptors and tables are free again */
+    const hb_strides strides = {key_stride, out_stride, 0};
+    if ((rc = hb_check_strides(n, workbits, final_bits, nullptr, &strides, "privamp_blocks_dev", &pab_names)) || (rc = hb_begin(&pa->st))) return rc;
     int n_tabs = 0;
-    unsigned grid_x = 0;
-    size_t kw = 0, ow = 0;
-    pab_fill(pa, n, workbits, seeds, final_bits, key_stride, out_stride, 0, &n_tabs, &grid_x, &kw, &ow);
-    if (grid_x == 0) return QLDPC_OK;
-    const hipStream_t s = (hipStream_t)hip_stream;
-    const size_t head = pab_head_words(n);
-    HIPCHK(hipMemcpyAsync(pa->d_in, pa->h_in, 4 * head, hipMemcpyHostToDevice, s));
-    rc = pab_launch(pa, n, n_tabs, grid_x, d_keys, d_out, s);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(pa->done, s));
-    return QLDPC_OK;
+    const hb_sums sums = pab_fill(pa, n, workbits, seeds, final_bits, &strides, &n_tabs);
+    if (sums.widest_out == 0) return QLDPC_OK;
+    return hb_run_dev(&pa->st, pab_head_words(n), (hipStream_t)hip_stream,
+                      [&](hipStream_t s) { return pab_launch(pa, n, n_tabs, sums.widest_out, d_keys, d_out, s); });
 }

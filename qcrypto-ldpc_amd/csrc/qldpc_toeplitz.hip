@@ -23,13 +23,10 @@
 #include <cstring>
 #include <new>
 
-#include "../../include/qldpc.h"
-#include "qldpc_graph.h"
 #include "qldpc_hip.h"
 #include "qldpc_toeplitz_core.h"
 #include "qldpc_toeplitz_int.h"
 
-#define TZ_MAX_BLOCKS 65535        /* blocks are the y dimension of the grid */
 #define TZ_LANES 256
 #define TZ_TILE 2048               /* key words per staged seed tile; a multiple of 8 */
 #define TZ_SPAN 32                 /* seed words past the tile that the 8 halves of a workgroup reach (28 + 1, and 3 of padding in front) */
@@ -96,7 +93,7 @@ extern "C" int qldpc_toeplitz_host(const uint32_t *key_words, int key_bits, cons
     if (out_bits == 0) return QLDPC_OK;
     if (!key_words || !seed_words || !out_words) return QLDPC_EINVAL;
     const uint32_t nw = ((uint32_t)key_bits + 31u) / 32u, ow = ((uint32_t)out_bits + 31u) / 32u, sw = tz_seed_words(key_bits, out_bits);
-    const uint32_t tile = tile_words ? (uint32_t)tile_words : (uint32_t)TZ_TILE, mask = tz_tail_mask(key_bits);
+    const uint32_t tile = tile_words ? (uint32_t)tile_words : (uint32_t)TZ_TILE, mask = hb_tail_mask(key_bits);
     uint32_t *win = (uint32_t *)malloc(4 * ((size_t)(tile < nw ? tile : nw) + 1));
     if (!win) return QLDPC_ENOMEM;
     for (uint32_t w = 0; w < ow; w++) {
@@ -118,40 +115,15 @@ extern "C" int qldpc_toeplitz_host(const uint32_t *key_words, int key_bits, cons
 
 extern "C" size_t qldpc_toeplitz_seed_words(int key_bits, int out_bits) { return tz_seed_words(key_bits, out_bits); }
 
+static const hb_names tz_names = {"key_bits", "out_bits"};
 static size_t tz_desc_words(int n) { return (size_t)n * (sizeof(tz_desc) / 4); }
 
 extern "C" void qldpc_toeplitz_free(qldpc_toeplitz_ctx *tz)
 {
     if (!tz) return;
-    (void)hipSetDevice(tz->device);
-    if (tz->done) { (void)hipEventSynchronize(tz->done); (void)hipEventDestroy(tz->done); }
-    if (tz->stream) (void)hipStreamDestroy(tz->stream);
+    hb_free(&tz->st);                                            /* waits for the last call first */
     tzn_free(tz);
-    if (tz->h_in) (void)hipHostFree(tz->h_in);
-    if (tz->h_out) (void)hipHostFree(tz->h_out);
-    if (tz->d_in) (void)hipFree(tz->d_in);
-    if (tz->d_out) (void)hipFree(tz->d_out);
     delete tz;
-}
-
-static int tz_create(qldpc_toeplitz_ctx *tz)
-{
-    HIPCHK(hipSetDevice(tz->device));
-    const size_t kw = ((size_t)tz->max_key_bits + 31) / 32, ow = ((size_t)tz->max_out_bits + 31) / 32;
-    tz->key_cap = (size_t)tz->max_blocks * kw;
-    tz->seed_cap = (size_t)tz->max_blocks * tz_seed_words(tz->max_key_bits, tz->max_out_bits);
-    tz->out_cap = (size_t)tz->max_blocks * ow;
-    tz->in_words = tz_desc_words(tz->max_blocks) + tz->key_cap + tz->seed_cap;
-    const size_t out_words = tz->out_cap ? tz->out_cap : 1;
-    if (hipHostMalloc((void **)&tz->h_in, 4 * tz->in_words, hipHostMallocDefault) != hipSuccess) return QLDPC_ENOMEM;
-    if (hipHostMalloc((void **)&tz->h_out, 4 * out_words, hipHostMallocDefault) != hipSuccess) return QLDPC_ENOMEM;
-    if (hipMalloc((void **)&tz->d_in, 4 * tz->in_words) != hipSuccess) return QLDPC_ENOMEM;
-    if (hipMalloc((void **)&tz->d_out, 4 * out_words) != hipSuccess) return QLDPC_ENOMEM;
-    tz->dev_bytes = 4 * (tz->in_words + out_words);
-    HIPCHK(hipStreamCreateWithFlags(&tz->stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&tz->done, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(tz->done, tz->stream));
-    return QLDPC_OK;
 }
 
 extern "C" void qldpc_toeplitz_cfg_default(qldpc_toeplitz_cfg *cfg)
@@ -167,30 +139,16 @@ extern "C" int qldpc_toeplitz_create_cfg(const qldpc_toeplitz_cfg *cfg, qldpc_to
     if (!out) return QLDPC_EINVAL;
     *out = nullptr;
     if (!cfg) return QLDPC_EINVAL;
-    const int device = cfg->device, max_blocks = cfg->max_blocks, max_key_bits = cfg->max_key_bits, max_out_bits = cfg->max_out_bits;
     if (cfg->method != QLDPC_TOEPLITZ_DIRECT && cfg->method != QLDPC_TOEPLITZ_NTT) { qldpc_set_error("toeplitz_create_cfg: method=%d", cfg->method); return QLDPC_EINVAL; }
     if (cfg->pass_log2 != 0 && cfg->pass_log2 != QLDPC_TOEPLITZ_PASS_LOG2_SMALL) {
         qldpc_set_error("toeplitz_create_cfg: pass_log2=%d (0 or %d)", cfg->pass_log2, QLDPC_TOEPLITZ_PASS_LOG2_SMALL);
         return QLDPC_EINVAL;
     }
-    if (max_blocks > TZ_MAX_BLOCKS) { qldpc_set_error("toeplitz_create: max_blocks=%d (up to %d)", max_blocks, TZ_MAX_BLOCKS); return QLDPC_ESIZE; }
-    if (max_blocks < 1 || max_key_bits < 1 || max_out_bits < 0 || max_key_bits > TZ_MAX_BITS || max_out_bits > TZ_MAX_BITS) {
-        qldpc_set_error("toeplitz_create: max_blocks=%d max_key_bits=%d max_out_bits=%d (bits up to %d)", max_blocks, max_key_bits, max_out_bits, TZ_MAX_BITS);
-        return QLDPC_ESIZE;
-    }
-    const uint64_t row = ((uint64_t)max_key_bits + 31) / 32 + tz_seed_words(max_key_bits, max_out_bits) + ((uint64_t)max_out_bits + 31) / 32 + 16;
-    if ((uint64_t)max_blocks * row >= (1ull << 31)) {
-        qldpc_set_error("toeplitz_create: %d blocks of %d -> %d bits pass 2^31 staged words", max_blocks, max_key_bits, max_out_bits);
-        return QLDPC_ESIZE;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { qldpc_set_error("no HIP device visible: libqldpc has no CPU fallback"); return QLDPC_ENODEV; }
-    if (device < 0 || device >= ndev) return QLDPC_ENODEV;
     qldpc_toeplitz_ctx *tz = new (std::nothrow) qldpc_toeplitz_ctx();
     if (!tz) return QLDPC_ENOMEM;
-    tz->device = device; tz->max_blocks = max_blocks; tz->max_key_bits = max_key_bits; tz->max_out_bits = max_out_bits;
     tz->method = cfg->method;
-    int rc = tz_create(tz);
+    const hb_limits lim = {cfg->max_blocks, cfg->max_key_bits, cfg->max_out_bits};
+    int rc = hb_create(&tz->st, cfg->device, &lim, tz_desc_words(1), tz_seed_words(lim.max_key_bits, lim.max_out_bits), "toeplitz_create", &tz_names);
     if (!rc && tz->method == QLDPC_TOEPLITZ_NTT) rc = tzn_create(tz, cfg->pass_log2, cfg->work_bytes);
     if (rc) { qldpc_toeplitz_free(tz); return rc; }
     *out = tz;
@@ -212,57 +170,26 @@ extern "C" int qldpc_toeplitz_stats(const qldpc_toeplitz_ctx *tz, uint64_t out[8
     return QLDPC_OK;
 }
 
-extern "C" size_t qldpc_toeplitz_device_bytes(const qldpc_toeplitz_ctx *tz) { return tz ? tz->dev_bytes : 0; }
+extern "C" size_t qldpc_toeplitz_device_bytes(const qldpc_toeplitz_ctx *tz) { return tz ? tz->st.dev_bytes : 0; }
 
-/* argument checks of both forms; nothing is written before every block has passed */
-static int tz_check(const qldpc_toeplitz_ctx *tz, int n, const int *key_bits, const int *out_bits, const char *who)
+/* the layout of the call as descriptor rows into the pinned staging.  strides NULL: the host form (one_seed: every block reads the seed at 0) */
+static hb_sums tz_fill(qldpc_toeplitz_ctx *tz, int n, const int *key_bits, const int *out_bits, const hb_strides *strides, int one_seed)
 {
-    if (!tz) return QLDPC_EINVAL;
-    if (n < 0) return QLDPC_EINVAL;
-    if (n > tz->max_blocks) { qldpc_set_error("%s: %d blocks, the context holds %d", who, n, tz->max_blocks); return QLDPC_ESIZE; }
-    if (n == 0) return QLDPC_OK;
-    if (!key_bits || !out_bits) { qldpc_set_error("%s: NULL argument array", who); return QLDPC_EINVAL; }
-    for (int i = 0; i < n; i++) {
-        if (key_bits[i] <= 0 || out_bits[i] < 0) { qldpc_set_error("%s: block %d: key_bits=%d out_bits=%d", who, i, key_bits[i], out_bits[i]); return QLDPC_ESIZE; }
-        if (key_bits[i] > tz->max_key_bits) { qldpc_set_error("%s: block %d: key_bits=%d, the context holds %d", who, i, key_bits[i], tz->max_key_bits); return QLDPC_ESIZE; }
-        if (out_bits[i] > tz->max_out_bits) { qldpc_set_error("%s: block %d: out_bits=%d, the context holds %d", who, i, out_bits[i], tz->max_out_bits); return QLDPC_ESIZE; }
-    }
-    return QLDPC_OK;
+    const hb_row *rows = tz->st.rows;
+    const hb_sums sums = hb_layout(n, key_bits, out_bits, tz_seed_words, strides, one_seed, tz->st.rows);
+    tz_desc *descs = (tz_desc *)tz->st.h_in;
+    for (int i = 0; i < n; i++)
+        descs[i] = tz_desc{rows[i].key_words, hb_tail_mask(key_bits[i]), (uint32_t)out_bits[i], rows[i].extra_words, rows[i].key_off, rows[i].extra_off, rows[i].out_off};
+    return sums;
 }
 
-/* descriptor rows into the pinned staging.  packed: rows one after the other (host form; one_seed: every block reads the seed at 0);
- * else rows key_stride / seed_stride / out_stride words apart.  *grid_x and the words of the three areas out */
-static void tz_fill(qldpc_toeplitz_ctx *tz, int n, const int *key_bits, const int *out_bits, size_t key_stride, size_t seed_stride, size_t out_stride,
-                    int packed, int one_seed, unsigned *grid_x, size_t *key_words, size_t *seed_words, size_t *out_words)
+/* the blocks of a call, laid out by tz_fill, by the context's method; widest: the words of the call's longest output row, > 0; shared: one seed row */
+static int tz_launch(qldpc_toeplitz_ctx *tz, int n, uint32_t widest, const int *key_bits, int shared, const uint32_t *d_keys, const uint32_t *d_seeds, uint32_t *d_out, hipStream_t s)
 {
-    tz_desc *descs = (tz_desc *)tz->h_in;
-    size_t koff = 0, soff = 0, ooff = 0, smax = 0;
-    unsigned gx = 0;
-    for (int i = 0; i < n; i++) {
-        tz_desc &d = descs[i];
-        d.key_words = ((uint32_t)key_bits[i] + 31u) / 32u;
-        d.tail_mask = tz_tail_mask(key_bits[i]);
-        d.out_bits = (uint32_t)out_bits[i];
-        d.seed_words = tz_seed_words(key_bits[i], out_bits[i]);
-        const uint32_t ow = (d.out_bits + 31u) / 32u;
-        d.key_off = packed ? koff : (uint64_t)i * key_stride;
-        d.seed_off = packed ? (one_seed ? 0 : soff) : (uint64_t)i * seed_stride;
-        d.out_off = packed ? ooff : (uint64_t)i * out_stride;
-        koff += d.key_words; soff += d.seed_words; ooff += ow;
-        if (d.seed_words > smax) smax = d.seed_words;
-        const unsigned g = 4u * ((ow + 31u) / 32u);
-        if (g > gx) gx = g;
-    }
-    *grid_x = gx; *key_words = koff; *seed_words = one_seed ? smax : soff; *out_words = ooff;
-}
-
-/* the blocks of a call, laid out by tz_fill, by the context's method; shared: every block reads one seed row */
-static int tz_launch(qldpc_toeplitz_ctx *tz, int n, unsigned grid_x, const int *key_bits, int shared, const uint32_t *d_keys, const uint32_t *d_seeds, uint32_t *d_out, hipStream_t s)
-{
-    if (tz->method == QLDPC_TOEPLITZ_NTT) return tzn_blocks(tz, n, (const tz_desc *)tz->h_in, key_bits, shared, d_keys, d_seeds, d_out, s);
+    if (tz->method == QLDPC_TOEPLITZ_NTT) return tzn_blocks(tz, n, (const tz_desc *)tz->st.h_in, key_bits, shared, d_keys, d_seeds, d_out, s);
     memset(tz->stats, 0, sizeof(tz->stats));
     tz->stats[0] = 1;
-    hipLaunchKernelGGL(tz_hash, dim3(grid_x, (unsigned)n), dim3(TZ_LANES), 0, s, (const tz_desc *)tz->d_in, d_keys, d_seeds, d_out);
+    hipLaunchKernelGGL(tz_hash, dim3(4u * ((widest + 31u) / 32u), (unsigned)n), dim3(TZ_LANES), 0, s, (const tz_desc *)tz->st.d_in, d_keys, d_seeds, d_out);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { qldpc_set_error("toeplitz_blocks launch: %s", hipGetErrorString(e)); return QLDPC_EHIP; }
     return QLDPC_OK;
@@ -271,62 +198,38 @@ static int tz_launch(qldpc_toeplitz_ctx *tz, int n, unsigned grid_x, const int *
 extern "C" int qldpc_toeplitz_blocks(qldpc_toeplitz_ctx *tz, int n, const uint32_t *const *key_words, const int *key_bits,
                                      const uint32_t *const *seed_words, const int *out_bits, uint32_t *const *out_words)
 {
-    int rc = tz_check(tz, n, key_bits, out_bits, "toeplitz_blocks");
+    int rc = tz ? hb_check_blocks(&tz->st.lim, n, key_bits, out_bits, 0, "toeplitz_blocks", &tz_names) : QLDPC_EINVAL;
     if (rc || n == 0) return rc;
     if (!key_words || !seed_words || !out_words) { qldpc_set_error("toeplitz_blocks: NULL argument array"); return QLDPC_EINVAL; }
+    hb_stage *st = &tz->st;
+    if ((rc = hb_check_rows(n, out_bits, key_words, seed_words, out_words, "toeplitz_blocks")) || (rc = hb_begin(st))) return rc;
     int one_seed = 1;
-    for (int i = 0; i < n; i++) {
-        if (!key_words[i] || !seed_words[i] || (!out_words[i] && out_bits[i] > 0)) {
-            qldpc_set_error("toeplitz_blocks: block %d: NULL %s row", i, !key_words[i] ? "key" : !seed_words[i] ? "seed" : "output");
-            return QLDPC_EINVAL;
-        }
+    for (int i = 1; i < n; i++)
         if (seed_words[i] != seed_words[0]) one_seed = 0;
-    }
-    HIPCHK(hipSetDevice(tz->device));
-    HIPCHK(hipEventSynchronize(tz->done));
-    unsigned grid_x = 0;
-    size_t kw = 0, sw = 0, ow = 0;
-    tz_fill(tz, n, key_bits, out_bits, 0, 0, 0, 1, one_seed, &grid_x, &kw, &sw, &ow);
-    if (grid_x == 0) return QLDPC_OK;                            /* every block asks for 0 bits */
-    const size_t head = tz_desc_words(n);
-    const tz_desc *descs = (const tz_desc *)tz->h_in;
-    uint32_t *h_keys = tz->h_in + head, *h_seeds = h_keys + kw;
-    for (int i = 0; i < n; i++) memcpy(h_keys + descs[i].key_off, key_words[i], 4 * (size_t)descs[i].key_words);
+    const hb_sums sums = tz_fill(tz, n, key_bits, out_bits, nullptr, one_seed);
+    if (sums.widest_out == 0) return QLDPC_OK;                   /* every block asks for 0 bits */
+    const size_t head = tz_desc_words(n), kw = sums.key_words, sw = sums.extra_words;
+    uint32_t *h_seeds = st->h_in + head + kw;
     if (one_seed) memcpy(h_seeds, seed_words[0], 4 * sw);        /* the caller's one row covers the longest key_bits + out_bits - 1 of the call */
-    else for (int i = 0; i < n; i++) memcpy(h_seeds + descs[i].seed_off, seed_words[i], 4 * (size_t)descs[i].seed_words);
-    HIPCHK(hipMemcpyAsync(tz->d_in, tz->h_in, 4 * (head + kw + sw), hipMemcpyHostToDevice, tz->stream));
-    rc = tz_launch(tz, n, grid_x, key_bits, one_seed, tz->d_in + head, tz->d_in + head + kw, tz->d_out, tz->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(tz->h_out, tz->d_out, 4 * ow, hipMemcpyDeviceToHost, tz->stream));
-    HIPCHK(hipEventRecord(tz->done, tz->stream));
-    HIPCHK(hipStreamSynchronize(tz->stream));
-    for (int i = 0; i < n; i++)
-        if (out_bits[i] > 0) memcpy(out_words[i], tz->h_out + descs[i].out_off, 4 * (size_t)((descs[i].out_bits + 31u) / 32u));
-    return QLDPC_OK;
+    else for (int i = 0; i < n; i++) memcpy(h_seeds + st->rows[i].extra_off, seed_words[i], 4 * (size_t)st->rows[i].extra_words);
+    return hb_run_host(st, n, key_words, st->h_in + head, head + kw + sw, sums.out_words, out_words, [&](hipStream_t s) {
+        return tz_launch(tz, n, sums.widest_out, key_bits, one_seed, st->d_in + head, st->d_in + head + kw, st->d_out, s);
+    });
 }
 
 extern "C" int qldpc_toeplitz_blocks_dev(qldpc_toeplitz_ctx *tz, int n, const uint32_t *d_keys, size_t key_stride, const int *key_bits,
                                          const uint32_t *d_seeds, size_t seed_stride, const int *out_bits,
                                          uint32_t *d_out, size_t out_stride, void *hip_stream)
 {
-    int rc = tz_check(tz, n, key_bits, out_bits, "toeplitz_blocks_dev");
+    int rc = tz ? hb_check_blocks(&tz->st.lim, n, key_bits, out_bits, 0, "toeplitz_blocks_dev", &tz_names) : QLDPC_EINVAL;
     if (rc || n == 0) return rc;
     if (!d_keys || !d_seeds || !d_out) { qldpc_set_error("toeplitz_blocks_dev: NULL device pointer"); return QLDPC_EINVAL; }
-    for (int i = 0; i < n; i++) {
-        if (((size_t)key_bits[i] + 31) / 32 > key_stride) { qldpc_set_error("toeplitz_blocks_dev: block %d: key_bits=%d pass a key row of %zu words", i, key_bits[i], key_stride); return QLDPC_ESIZE; }
-        if (seed_stride && tz_seed_words(key_bits[i], out_bits[i]) > seed_stride) { qldpc_set_error("toeplitz_blocks_dev: block %d: %d -> %d bits pass a seed row of %zu words", i, key_bits[i], out_bits[i], seed_stride); return QLDPC_ESIZE; }
-        if (((size_t)out_bits[i] + 31) / 32 > out_stride) { qldpc_set_error("toeplitz_blocks_dev: block %d: out_bits=%d pass an output row of %zu words", i, out_bits[i], out_stride); return QLDPC_ESIZE; }
-    }
-    HIPCHK(hipSetDevice(tz->device));
-    HIPCHK(hipEventSynchronize(tz->done));                       /* the previous call's descriptors are free again */
-    unsigned grid_x = 0;
-    size_t kw = 0, sw = 0, ow = 0;
-    tz_fill(tz, n, key_bits, out_bits, key_stride, seed_stride, out_stride, 0, 0, &grid_x, &kw, &sw, &ow);
-    if (grid_x == 0) return QLDPC_OK;
-    const hipStream_t s = (hipStream_t)hip_stream;
-    if (tz->method == QLDPC_TOEPLITZ_DIRECT) HIPCHK(hipMemcpyAsync(tz->d_in, tz->h_in, 4 * tz_desc_words(n), hipMemcpyHostToDevice, s));
-    rc = tz_launch(tz, n, grid_x, key_bits, seed_stride == 0, d_keys, d_seeds, d_out, s);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(tz->done, s));
-    return QLDPC_OK;
+    const hb_strides strides = {key_stride, out_stride, seed_stride};
+    if ((rc = hb_check_strides(n, key_bits, out_bits, tz_seed_words, &strides, "toeplitz_blocks_dev", &tz_names)) || (rc = hb_begin(&tz->st))) return rc;
+    const hb_sums sums = tz_fill(tz, n, key_bits, out_bits, &strides, 0);
+    if (sums.widest_out == 0) return QLDPC_OK;
+    /* the NTT method reads the rows on the host and uploads rows of its own */
+    return hb_run_dev(&tz->st, tz->method == QLDPC_TOEPLITZ_DIRECT ? tz_desc_words(n) : 0, (hipStream_t)hip_stream, [&](hipStream_t s) {
+        return tz_launch(tz, n, sums.widest_out, key_bits, seed_stride == 0, d_keys, d_seeds, d_out, s);
+    });
 }

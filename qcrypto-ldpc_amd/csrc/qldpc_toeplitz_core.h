@@ -15,13 +15,16 @@
 
 #include <stdint.h>
 
+#include "qldpc_hashbatch_core.h"      /* hb_tail_mask: the bits of the last word of a row */
+
 #if defined(__HIPCC__)
 #define TZ_FN __host__ __device__ static inline
 #else
 #define TZ_FN static inline
 #endif
 
-#define TZ_MAX_BITS (1 << 24)      /* key_bits and out_bits of a block */
+#define TZ_MAX_BITS HB_MAX_BITS    /* key_bits and out_bits of a block */
+#define tz_tail_mask hb_tail_mask  /* the one tail mask under the name this header gave it: tests/c/toeplitz_sanitize.c checks it by that name */
 
 TZ_FN uint32_t tz_brev(uint32_t x)
 {
@@ -64,9 +67,6 @@ TZ_FN uint32_t tz_parity(uint32_t x)
     return (uint32_t)__builtin_parity(x);
 #endif
 }
-
-/* the bits of the last word of a row of `bits` bits, MSB-first */
-TZ_FN uint32_t tz_tail_mask(int bits) { return (bits & 31) ? 0xFFFFFFFFu << (32 - (bits & 31)) : 0xFFFFFFFFu; }
 
 /* words of a seed of key_bits + out_bits - 1 bits */
 TZ_FN uint32_t tz_seed_words(int key_bits, int out_bits)

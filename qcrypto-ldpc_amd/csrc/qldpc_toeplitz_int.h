@@ -1,17 +1,15 @@
 /*
- * qldpc_toeplitz_int.h -- what the two methods of a Toeplitz context share: the context (qldpc_toeplitz.hip owns it, the staging and the
- * direct kernel) and the entry points of the NTT method (qldpc_toeplitz_ntt.hip), which qldpc_toeplitz_blocks / _blocks_dev call in
- * place of the one direct launch once the rows of a call have been checked and laid out.
+ * qldpc_toeplitz_int.h -- what the two methods of a Toeplitz context share: the context (qldpc_toeplitz.hip owns it and the direct kernel;
+ * its staging and the reuse rule of that staging are qldpc_hashbatch.h's) and the entry points of the NTT method (qldpc_toeplitz_ntt.hip),
+ * which qldpc_toeplitz_blocks / _blocks_dev call in place of the one direct launch once the rows of a call have been checked and laid out.
  */
 #ifndef QLDPC_TOEPLITZ_INT_H
 #define QLDPC_TOEPLITZ_INT_H
 
-#include <hip/hip_runtime.h>
-
 #include <cstddef>
 #include <cstdint>
 
-#include "../../include/qldpc.h"
+#include "qldpc_hashbatch.h"
 
 struct tz_desc {                   /* one row per block, written by the host */
     uint32_t key_words, tail_mask, out_bits, seed_words;
@@ -21,19 +19,13 @@ struct tz_desc {                   /* one row per block, written by the host */
 struct tzn_state;                  /* tables, work area and descriptor rows of the NTT method */
 
 struct qldpc_toeplitz_ctx {
-    int device, max_blocks, max_key_bits, max_out_bits;
+    hb_stage st;                          /* the head of a call of n blocks: n descriptor rows; the payload: packed keys, then packed seeds */
     int method;                           /* QLDPC_TOEPLITZ_DIRECT / _NTT */
-    size_t key_cap, seed_cap, out_cap;    /* words of the packed key / seed / output areas of the host form */
-    size_t in_words;                      /* descriptor rows, packed keys and packed seeds of a full call: one upload per host call */
-    uint32_t *h_in, *d_in, *h_out, *d_out;
-    hipEvent_t done;                      /* after the last call's launch: the staging is reused only once that call has run */
-    hipStream_t stream;                   /* of the host form */
-    size_t dev_bytes;
     uint64_t stats[8];                    /* of the last call (qldpc_toeplitz_stats) */
     tzn_state *ntt;
 };
 
-/* allocates everything the method needs and adds it to tz->dev_bytes; pass_log2 and work_bytes as in qldpc_toeplitz_cfg */
+/* allocates everything the method needs and adds it to tz->st.dev_bytes; pass_log2 and work_bytes as in qldpc_toeplitz_cfg */
 int tzn_create(qldpc_toeplitz_ctx *tz, int pass_log2, size_t work_bytes);
 void tzn_free(qldpc_toeplitz_ctx *tz);
 /* the n blocks of a call whose rows `rows` describe (key_off / seed_off / out_off from d_keys / d_seeds / d_out), queued on s;

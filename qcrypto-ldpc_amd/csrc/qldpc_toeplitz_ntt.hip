@@ -24,8 +24,6 @@
 #include <cstring>
 #include <new>
 
-#include "../../include/qldpc.h"
-#include "qldpc_graph.h"
 #include "qldpc_hip.h"
 #include "qldpc_toeplitz_core.h"
 #include "qldpc_toeplitz_int.h"
@@ -270,7 +268,7 @@ void tzn_free(qldpc_toeplitz_ctx *tz)
 
 static uint32_t tzn_ctx_log2(const qldpc_toeplitz_ctx *tz)
 {
-    const int k = tzn_log2_len(tz->max_key_bits, tz->max_out_bits);
+    const int k = tzn_log2_len(tz->st.lim.max_key_bits, tz->st.lim.max_out_bits);
     return k < 0 ? (uint32_t)TZN_MIN_LOG2 : (uint32_t)k;
 }
 
@@ -284,14 +282,14 @@ int tzn_create(qldpc_toeplitz_ctx *tz, int pass_log2, size_t work_bytes)
     const size_t one = (size_t)8 << st->kmax;                    /* two arrays of L residues */
     if (work_bytes == 0) {
         size_t blocks = TZN_DEFAULT_WORK / one;
-        if (blocks > (size_t)tz->max_blocks) blocks = (size_t)tz->max_blocks;
+        if (blocks > (size_t)tz->st.lim.max_blocks) blocks = (size_t)tz->st.lim.max_blocks;
         work_bytes = one * (blocks ? blocks : 1);
     }
     if (work_bytes < one) { qldpc_set_error("toeplitz_create_cfg: work_bytes=%zu, one block of the context's sizes takes %zu", work_bytes, one); return QLDPC_ESIZE; }
     st->work_res = work_bytes / 4;
-    const size_t tw = tzn_table_words(st->B, st->kmax), rows = (size_t)tz->max_blocks + TZN_MAX_LOG2 + 1;
+    const size_t tw = tzn_table_words(st->B, st->kmax), rows = (size_t)tz->st.lim.max_blocks + TZN_MAX_LOG2 + 1;
     uint32_t *h_tab = (uint32_t *)malloc(4 * tw);
-    st->order = (int *)malloc(sizeof(int) * (size_t)tz->max_blocks);
+    st->order = (int *)malloc(sizeof(int) * (size_t)tz->st.lim.max_blocks);
     if (!h_tab || !st->order) { free(h_tab); return QLDPC_ENOMEM; }
     int rc = QLDPC_OK;
     if (hipMalloc((void **)&st->d_work, 4 * st->work_res) != hipSuccess || hipMalloc((void **)&st->d_tab, 4 * tw) != hipSuccess ||
@@ -305,7 +303,7 @@ int tzn_create(qldpc_toeplitz_ctx *tz, int pass_log2, size_t work_bytes)
         if (hipMemcpy(st->d_tab, h_tab, 4 * tw, hipMemcpyHostToDevice) != hipSuccess) { qldpc_set_error("toeplitz_create_cfg: the tables did not reach the device"); rc = QLDPC_EHIP; }
     }
     free(h_tab);
-    if (!rc) tz->dev_bytes += 4 * st->work_res + 4 * tw + rows * sizeof(tzn_desc);
+    if (!rc) tz->st.dev_bytes += 4 * st->work_res + 4 * tw + rows * sizeof(tzn_desc);
     return rc;
 }
 
