@@ -348,6 +348,11 @@ struct qk_coded_llr {
 };
 
 
+/* |Y| of a VN of class cls at index v for a frame of channel magnitude mg and shortening length nc, erasures aside */
+__device__ __forceinline__ float qk_coded_mag(int cls, int v, float mg, int nc)
+{
+    return (cls == 0) ? (v < nc ? mg : 23.025850929840455f) : (cls == 1 ? 23.025850929840455f : 0.0f);
+}
 /* Y of VN v for the V frames of this lane, rebuilt from the coded form (the float the LLR array would hold) */
 template <int V> __device__ __forceinline__ void qk_coded_y(float (&y)[V], const qk_coded_llr &c, int g, int v, int N, int lane, const float (&mg)[V], const int (&nc)[V])
 {
@@ -356,10 +361,56 @@ template <int V> __device__ __forceinline__ void qk_coded_y(float (&y)[V], const
 #pragma unroll
     for (int j = 0; j < V; j++) {
         const bool bit = (c.ybits[((size_t)g * N + v) * V + j] >> lane) & 1ull;
-        float m = (cls == 0) ? (v < nc[j] ? mg[j] : 23.025850929840455f) : (cls == 1 ? 23.025850929840455f : 0.0f);
+        float m = qk_coded_mag(cls, v, mg[j], nc[j]);
         if (c.ebits && ((c.ebits[((size_t)g * N + v) * V + j] >> lane) & 1ull)) m = 0.0f;      /* punctured for this frame: LLR 0 (BS/src/main.cpp:359-362) */
         y[j] = bit ? -m : m;
     }
+}
+
+/*
+ * The same Y in two steps, for the kernels that must not wait once per VN (64-frame groups, V = 1): qk_coded_fetch asks for a VN's three
+ * channel words and nothing else -- no branch, no use, so a caller can put any number of them in front of one wait -- and qk_coded_y_of
+ * forms Y from them by the expressions of qk_coded_y.  Without erasures the third load repeats the received-bit word (a cache hit) and
+ * its result is masked away: a uniform select instead of a branch around a load.  v may be wave-uniform (scalar loads) or differ by
+ * lane (three vector loads by the lane's own addresses).
+ */
+struct qk_coded_w {
+    uint32_t cls;      /* the class byte */
+    u64 yb, eb;        /* received bits and erasures of the 64 frames, bit = lane */
+};
+__device__ __forceinline__ qk_coded_w qk_coded_fetch(const qk_coded_llr &c, int g, int v, int N)
+{
+    const size_t at = (size_t)g * N + v;
+    qk_coded_w w;
+    w.cls = (reinterpret_cast<const uint32_t *>(c.vcls)[v >> 2] >> ((v & 3) * 8)) & 0xffu;
+    w.yb = c.ybits[at];
+    w.eb = (c.ebits ? c.ebits : c.ybits)[at] & (c.ebits ? ~0ull : 0ull);
+    return w;
+}
+/* w and v wave-uniform here: a ballot word in scalar registers IS the lane mask of "(word >> lane) & 1", no shift per lane */
+__device__ __forceinline__ float qk_coded_y_of(const qk_coded_w &w, int v, float mg, int nc)
+{
+    const bool bit = __builtin_amdgcn_inverse_ballot_w64(w.yb);
+    float m = qk_coded_mag((int)w.cls, v, mg, nc);
+    if (__builtin_amdgcn_inverse_ballot_w64(w.eb)) m = 0.0f;
+    return bit ? -m : m;
+}
+/* The compiler moves a load whose result is used only further down into the block of that use, behind whatever wait stands in between.  An
+ * empty statement that reads the results keeps the loads above it: put after the last load a kernel issues, it costs the wait that follows anyway */
+__device__ __forceinline__ void qk_coded_pin(const qk_coded_w &w) { asm volatile("" ::"s"(w.cls), "s"(w.yb), "s"(w.eb)); }      /* wave-uniform words */
+__device__ __forceinline__ void qk_pin_lane(float a, int b) { asm volatile("" ::"v"(a), "v"(b)); }
+/* lane k's words (and its VN index) handed to every lane: k is wave-uniform, a constant after unrolling */
+__device__ __forceinline__ u64 qk_readlane64(u64 x, int k)
+{
+    return (u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, k) | ((u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), k) << 32);
+}
+__device__ __forceinline__ qk_coded_w qk_coded_w_of_lane(const qk_coded_w &w, int k)
+{
+    qk_coded_w e;
+    e.cls = (uint32_t)__builtin_amdgcn_readlane((int)w.cls, k);
+    e.yb = qk_readlane64(w.yb, k);
+    e.eb = qk_readlane64(w.eb, k);
+    return e;
 }
 /* what _initialize_var_to_chk leaves in var_to_chk before the first check pass: (Y + 0) - 0, through the message type */
 __device__ __forceinline__ float qk_first_v2c(float y, const float *) { return (y + 0.0f) - 0.0f; }

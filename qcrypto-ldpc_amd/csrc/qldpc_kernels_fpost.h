@@ -44,23 +44,19 @@ __device__ __forceinline__ float qk_fp_msg(uint32_t w, int k, float c1, float c2
     return qk_withsign(((int)(w >> 27) == k) ? c1 : c2, (w >> k) << 31);
 }
 
-/* Y of VN v for this lane's frame: rebuilt from the coded form or read from the LLR array (a row other checks gather too: cached) */
-template <bool CODED>
-__device__ __forceinline__ float qk_fp_y(const float *__restrict__ yin, const qk_coded_llr &coded, int g, int v, int N, int lane, const float (&mg)[1], const int (&nc)[1])
-{
-    if constexpr (CODED) {
-        float y[1];
-        qk_coded_y<1>(y, coded, g, v, N, lane, mg, nc);
-        return y[0];
-    } else return yin[(size_t)v * 64];
-}
-
 /*
  * The check pass.  One wavefront per check, indices prefetched with back-to-back scalar loads as in qk_cn_flood.
  *   info edge k:   x = post[v_k] - (own previous message k)
  *   chain edges:   tmp = Y + ((0.0f + m[slot 0]) + m[slot 1]) in the VN's slot order (ascending check: the lower check is slot 0),
  *                  exactly as qk_vn_flood sums; x = tmp - own.  The last VN has degree 1: tmp = Y + (0.0f + own).
  * then the fold of qk_acc<QK_FAM_MS>, the info edges' outputs CN-major as qk_cn_flood stores them, and the new state.
+ *
+ * Everything a wave reads is asked for before it waits for any of it.  The frame constants depend on g and lane only and go first.  The
+ * first pass (coded) has no rows to gather, only channel words: lane k loads the VN index of edge k and then that VN's words by its own
+ * address (qk_coded_fetch), two vector round trips for a check of any degree, and edge k's words reach every lane through readlane.  A
+ * steady pass needs channel words for its two chain VNs only: their scalar loads are issued in front of the gathers and travel with them.
+ * The posterior gathers and the state stores stay plain: non-temporal gathers, non-temporal state stores and both together were measured
+ * and none stood clear of the run-to-run spread (DESIGN section 8 #1a); the gathers then fetch 1.08 x as many bytes.
  */
 template <int DCMAX, bool FIRST, bool CODED>
 __global__ __launch_bounds__(QK_THREADS) void qk_cn_fpost(const float *__restrict__ post, const float *__restrict__ llr, float *__restrict__ c2v,
@@ -72,8 +68,11 @@ __global__ __launch_bounds__(QK_THREADS) void qk_cn_fpost(const float *__restric
 {
     static_assert(DCMAX > 0 && DCMAX <= QK_FP_DCMAX, "sign bits and the index share one word");
     const int g = blockIdx.y;
-    if (qk_group_done<1>(done, g)) return;      /* a group of padding frames only */
     const int lane = threadIdx.x & 63;
+    float mg = 0.0f;
+    int nc = 0;
+    if constexpr (CODED) { mg = coded.fmag[(size_t)g * 64 + lane]; nc = coded.fnch[(size_t)g * 64 + lane]; }
+    if (qk_group_done<1>(done, g)) return;      /* a group of padding frames only */
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = blockIdx.x * QK_WAVES + wave;
     if (i >= n_list) return;
@@ -82,61 +81,77 @@ __global__ __launch_bounds__(QK_THREADS) void qk_cn_fpost(const float *__restric
     const int deg = cn_ptr[c + 1] - b;
     const uint32_t ch = chain[c];
     const int lpos = (int)(ch & 0xffu), rpos = (int)((ch >> 8) & 0xffu), lnb = (int)((ch >> 16) & 0xffu), rnb = (int)(ch >> 24);
-    int vid[DCMAX];
-#pragma unroll
-    for (int k = 0; k < DCMAX; k++) vid[k] = cn_var[b + k];      /* padded by QK_IDX_PAD */
-
     const float *pg = post + (size_t)g * N * 64 + lane;
     const float *yin = llr + (size_t)g * N * 64 + lane;
     const size_t srow = ((size_t)g * M + c) * (64 * QK_FP_ROWS) + lane;
+    int vid[DCMAX];
     float x[DCMAX];
-    if constexpr (!FIRST) {
-#pragma unroll
-        for (int k = 0; k < DCMAX; k++)
-            if (k < deg && k != lpos && k != rpos) x[k] = pg[(size_t)vid[k] * 64];
-    }
+    float yl = 0.0f, yr = 0.0f;      /* Y of the chain VNs at positions lpos and rpos */
     /* own state, and the states of checks c - 1 and c + 1 where a chain VN is shared with them */
     float c1 = 0.0f, c2 = 0.0f, lc1 = 0.0f, lc2 = 0.0f, rc1 = 0.0f, rc2 = 0.0f;
     uint32_t w = 0u, lw = 0u, rw = 0u;
-    if constexpr (!FIRST) {
+    if constexpr (FIRST) {      /* x[k] holds Y of edge k first */
+        if constexpr (CODED) {
+            /* lanes as edges: lane k holds the words of the VN of edge k (lanes past the degree repeat the last edge: no further cache line) */
+            const int kl = lane < deg ? lane : (deg > 0 ? deg - 1 : 0);
+            const int vlane = cn_var[b + kl];
+            const qk_coded_w wl = qk_coded_fetch(coded, g, vlane, N);
+#pragma unroll
+            for (int k = 0; k < DCMAX; k++) {      /* no test of the degree: past it, the last edge again */
+                vid[k] = __builtin_amdgcn_readlane(vlane, k);
+                x[k] = qk_coded_y_of(qk_coded_w_of_lane(wl, k), vid[k], mg, nc);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < DCMAX; k++) vid[k] = cn_var[b + k];      /* padded by QK_IDX_PAD */
+#pragma unroll
+            for (int k = 0; k < DCMAX; k++)
+                x[k] = (k < deg) ? yin[(size_t)vid[k] * 64] : 0.0f;      /* a row other checks gather too: cached */
+        }
+#pragma unroll
+        for (int k = 0; k < DCMAX; k++) {
+            yl = (k == lpos) ? x[k] : yl;
+            yr = (k == rpos) ? x[k] : yr;
+            x[k] = qk_first_v2c(x[k], (const float *)nullptr);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < DCMAX; k++) vid[k] = cn_var[b + k];      /* padded by QK_IDX_PAD */
+        /* the two chain VNs (wave-uniform positions; a position DCMAX or beyond never matches; VN 0 stands in where there is none) */
+        int vl = 0, vr = 0;
+#pragma unroll
+        for (int k = 0; k < DCMAX; k++) { vl = (k == lpos) ? vid[k] : vl; vr = (k == rpos) ? vid[k] : vr; }
+        qk_coded_w wcl, wcr;
+        if constexpr (CODED) { wcl = qk_coded_fetch(coded, g, vl, N); wcr = qk_coded_fetch(coded, g, vr, N); }
+        else { yl = yin[(size_t)vl * 64]; yr = yin[(size_t)vr * 64]; }
+#pragma unroll
+        for (int k = 0; k < DCMAX; k++)
+            if (k < deg && k != lpos && k != rpos) x[k] = pg[(size_t)vid[k] * 64];
         const float *s = st_in + srow;
         const uint32_t *sw = reinterpret_cast<const uint32_t *>(s);
         c1 = s[0]; c2 = s[64]; w = sw[128];
         if (lpos != (int)QK_FP_NONE && c > 0) { lc1 = s[-192]; lc2 = s[-128]; lw = sw[-64]; }         /* the rows of check c - 1 */
         if (rnb != (int)QK_FP_NONE && c + 1 < M) { rc1 = s[192]; rc2 = s[256]; rw = sw[320]; }        /* the rows of check c + 1 */
-    }
-    float mg[1] = {0.0f};
-    int nc[1] = {0};
-    if constexpr (CODED) { mg[0] = coded.fmag[(size_t)g * 64 + lane]; nc[0] = coded.fnch[(size_t)g * 64 + lane]; }
-    if constexpr (FIRST) {
-#pragma unroll
-        for (int k = 0; k < DCMAX; k++)
-            if (k < deg && k != lpos && k != rpos) x[k] = qk_first_v2c(qk_fp_y<CODED>(yin, coded, g, vid[k], N, lane, mg, nc), (const float *)nullptr);
-    } else {
+        if constexpr (CODED) { qk_coded_pin(wcl); qk_coded_pin(wcr); qk_pin_lane(mg, nc); yl = qk_coded_y_of(wcl, vl, mg, nc); yr = qk_coded_y_of(wcr, vr, mg, nc); }
 #pragma unroll
         for (int k = 0; k < DCMAX; k++)
             if (k < deg && k != lpos && k != rpos) x[k] = x[k] - qk_fp_msg(w, k, c1, c2);
     }
-    /* the two chain VNs (wave-uniform positions; a position DCMAX or beyond never matches below) */
-    float xl = 0.0f, xr = 0.0f;
-    if (lpos != (int)QK_FP_NONE) {      /* VN K + c - 1: slot 0 = check c - 1, slot 1 = this check */
-        int vl = 0;
-#pragma unroll
-        for (int k = 0; k < DCMAX; k++) vl = (k == lpos) ? vid[k] : vl;
-        const float y = qk_fp_y<CODED>(yin, coded, g, vl, N, lane, mg, nc);
-        const float own = qk_fp_msg(w, lpos, c1, c2), nb = qk_fp_msg(lw, lnb, lc1, lc2);
-        const float tmp = y + ((0.0f + nb) + own);
+    /* the chain edges: slot 0 is the lower check.  In the first pass every message is +0.0: (Y + 0) - 0 as on the other edges.  Both are worked out
+     * whether the check has them or not (a position QK_FP_NONE matches no edge below, what it gives is dropped): under a branch of their own the
+     * compiler moves the loads of yl and yr into that branch, behind the wait for the gathers */
+    const int lp = lpos & 31, rp = rpos & 31;
+    float xl, xr;
+    {      /* VN K + c - 1: slot 0 = check c - 1, slot 1 = this check */
+        const float own = qk_fp_msg(w, lp, c1, c2), nb = qk_fp_msg(lw, lnb & 31, lc1, lc2);
+        const float tmp = yl + ((0.0f + nb) + own);
         xl = tmp - own;
     }
-    if (rpos != (int)QK_FP_NONE) {      /* VN K + c: slot 0 = this check, slot 1 = check c + 1 (none for the last VN) */
-        int vr = 0;
-#pragma unroll
-        for (int k = 0; k < DCMAX; k++) vr = (k == rpos) ? vid[k] : vr;
-        const float y = qk_fp_y<CODED>(yin, coded, g, vr, N, lane, mg, nc);
-        const float own = qk_fp_msg(w, rpos, c1, c2);
-        float sum = 0.0f + own;
-        if (rnb != (int)QK_FP_NONE) sum = sum + qk_fp_msg(rw, rnb, rc1, rc2);
-        const float tmp = y + sum;
+    {      /* VN K + c: slot 0 = this check, slot 1 = check c + 1 (none for the last VN) */
+        const float own = qk_fp_msg(w, rp, c1, c2);
+        const float sum0 = 0.0f + own;
+        const float sum = (rnb != (int)QK_FP_NONE) ? sum0 + qk_fp_msg(rw, rnb & 31, rc1, rc2) : sum0;
+        const float tmp = yr + sum;
         xr = tmp - own;
     }
     qk_acc<QK_FAM_MS> acc;
@@ -265,6 +280,8 @@ __global__ __launch_bounds__(QK_THREADS) void qk_vn_fpost(const float *__restric
 /*
  * _compute_post of the chain VNs after the last check pass: tmp from the final state of checks c and c + 1, the sgn / hard ballots
  * qk_vn_flood leaves (padding frames keep the bits they had) and, on request, the posterior row.  One wavefront per chain VN.
+ * The state rows stay cached loads (the wave of check c - 1 reads the rows of check c too); the rows of check c + 1 are asked for
+ * whenever it exists, not only once the chain word has said that it shares the VN, so that no row load waits for a scalar one.
  */
 template <bool CODED>
 __global__ __launch_bounds__(QK_THREADS) void qk_fpost_close(const float *__restrict__ st, const float *__restrict__ llr, const uint32_t *__restrict__ chain,
@@ -277,16 +294,27 @@ __global__ __launch_bounds__(QK_THREADS) void qk_fpost_close(const float *__rest
     const int c = blockIdx.x * QK_WAVES + wave;
     if (c >= M) return;
     const int v = K + c;
-    const int rpos = (int)((chain[c] >> 8) & 0xffu);
-    const int npos = (c + 1 < M) ? (int)(chain[c + 1] & 0xffu) : (int)QK_FP_NONE;
+    /* the channel words, the two chain words and both checks' rows are asked for together: none of the addresses waits for another load */
+    qk_coded_w wc;
+    float y = 0.0f, mg = 0.0f;
+    int nc = 0;
+    if constexpr (CODED) { mg = coded.fmag[(size_t)g * 64 + lane]; nc = coded.fnch[(size_t)g * 64 + lane]; wc = qk_coded_fetch(coded, g, v, N); }
+    else y = llr[((size_t)g * N + v) * 64 + lane];
+    const bool more = c + 1 < M;      /* the last chain VN has degree 1 */
+    const uint32_t ch0 = chain[c], ch1 = chain[more ? c + 1 : c];
     const float *s = st + ((size_t)g * M + c) * (64 * QK_FP_ROWS) + lane;
     const uint32_t *sw = reinterpret_cast<const uint32_t *>(s);
-    float sum = 0.0f + qk_fp_msg(sw[128], rpos, s[0], s[64]);
-    if (npos != (int)QK_FP_NONE) sum = sum + qk_fp_msg(sw[320], npos, s[192], s[256]);
-    float mg[1] = {0.0f};
-    int nc[1] = {0};
-    if constexpr (CODED) { mg[0] = coded.fmag[(size_t)g * 64 + lane]; nc[0] = coded.fnch[(size_t)g * 64 + lane]; }
-    const float tmp = qk_fp_y<CODED>(llr + (size_t)g * N * 64 + lane, coded, g, v, N, lane, mg, nc) + sum;
+    const float c1 = s[0], c2 = s[64];
+    const uint32_t w = sw[128];
+    float n1 = 0.0f, n2 = 0.0f;
+    uint32_t nw = 0u;
+    if (more) { n1 = s[192]; n2 = s[256]; nw = sw[320]; }
+    const int rpos = (int)((ch0 >> 8) & 0xffu);
+    const int npos = more ? (int)(ch1 & 0xffu) : (int)QK_FP_NONE;
+    float sum = 0.0f + qk_fp_msg(w, rpos, c1, c2);
+    if (npos != (int)QK_FP_NONE) sum = sum + qk_fp_msg(nw, npos, n1, n2);
+    if constexpr (CODED) y = qk_coded_y_of(wc, v, mg, nc);
+    const float tmp = y + sum;
     u64 sb = __ballot((qk_bits(tmp) >> 31) != 0);
     u64 hb = __ballot(!(tmp >= 0.0f));
     const size_t bi = (size_t)g * N + v;
