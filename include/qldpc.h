@@ -34,6 +34,7 @@
  *                                         qcrypto-ldpc_amd/host/ldpc_reconcile.c (packet handlers, cascade fallback, batched ingest)
  *   qldpc_privamp*                        the hash loop of privAmp_doPrivAmp         subcomponents/priv_amp.c:190-218
  *   qldpc_toeplitz*                       (not in the reference) Toeplitz hashing, the sound replacement of that loop
+ *   qldpc_polyhash*                       (not in the reference) error verification by a universal hash, beside the sessions' CRC-32
  *   qldpc_qber_* / _recon_estimate_blocks (not in the reference, which samples disclosed bits: subcomponents/qber_estim.c) the QBER out of the parity message
  *   qldpc_mc_*                            the simulation loop itself: source, encoder, BSC, decoder, Monitor_BFER   BS/src/main.cpp:335-393
  *   qldpc_mc_search / _patterns_dev       the puncture-pattern search around it: shuffle, erase, first FER = 0 / n  BS/src/main.cpp:235-411
@@ -800,6 +801,71 @@ int    qldpc_toeplitz_ntt_host(const uint32_t *key_words, int key_bits, const ui
 /* the field arithmetic, for tests: a b mod p, and a primitive 2^log2_len-th root of unity (log2_len 0 .. 25, else 0) */
 uint32_t qldpc_toeplitz_ntt_mul_host(uint32_t a, uint32_t b);
 uint32_t qldpc_toeplitz_ntt_root_host(int log2_len);
+
+/* ------------------------------------------------------------------ error verification by a universal hash ---- */
+/*
+ * After a decode the two sides must learn whether their keys are equal.  The CRC-32 of the sessions (qldpc_recon_*) is a cheap pre-check with
+ * a fixed public polynomial: it has no key and bounds nothing.  This is the hash the correctness term of a security statement needs:
+ * polynomial evaluation over the Mersenne prime p = 2^61 - 1 (csrc/qldpc_polyhash_core.h, csrc/qldpc_polyhash.hip).  A block of
+ * key_bits = n >= 1 bits in W = ceil(n / 32) words (MSB-first; the bits past n in the last word are ignored) has the coefficients
+ * c_0 .. c_(W-1), its words with the tail masked, and c_W = n, and
+ *
+ *     tag = SUM_{j = 0 .. W} c_j k^(W+1-j) mod p          (as Horner: h = 0; for every c: h = (h + c) k mod p)
+ *
+ * canonical in [0, p), written as two words: hi (29 bits), then lo.  The length is a coefficient, so zero padding cannot collide.  With
+ * n_keys = r in 1 .. 4 independent keys per block the tag is r such values, 2 r words, key after key.
+ *
+ * THE KEY IS THE CALLER'S.  The library makes none: the caller supplies two words (hi, lo) per key, k = ((hi << 32) | lo) & p with the
+ * value p itself taken as 0, so every 64-bit pattern is a valid key.  The guarantee is the quality of those bits and the moment they are
+ * chosen (after the adversary can no longer influence the blocks) and nothing the library can check.  Two different (n, message) pairs give
+ * equal tags with probability at most (W + 2) 2^-61 per key, W of the longer one (a non-zero polynomial of degree <= W + 1; field value 0
+ * has probability 2^-60 and every other 2^-61), to the power r for r keys: qldpc_polyhash_bound_log2.  A tag discloses at most 61 r bits of
+ * the block: qldpc_polyhash_leaked_bits.
+ *
+ * Conventions as qldpc_toeplitz_create_cfg / _blocks / _blocks_dev: creation allocates everything (pinned staging, device rows, descriptor
+ * rows and the work area of the blocks that span several tiles) and no call afterwards allocates; max_blocks up to 65 535, max_key_bits up
+ * to 2^24 (QLDPC_ESIZE above, for values < 1, and when max_blocks x the row lengths pass 2^31 words); n_keys outside 1 .. 4 and a
+ * tile_words other than 0 and the two values below are QLDPC_EINVAL.  A bad argument in any block (NULL row: QLDPC_EINVAL; key_bits <= 0 or
+ * over the context's, n > max_blocks, a device row shorter than its block: QLDPC_ESIZE) refuses the whole call before any work is queued,
+ * and qldpc_last_error() names the block.  n == 0 is QLDPC_OK.  A context is not re-entrant; a call first waits for the previous call on
+ * the same context to have run.  All blocks of a call go in one launch; a block of more than tile_words coefficients is split over
+ * several workgroups, and a second launch on the same stream then folds their partials.  The tag does not depend on tile_words.
+ *
+ * Not built: the tag inside the sessions' verify step (which would hash Bob's decoded rows where they lie), qldpc_recon_msg carrying a
+ * tag, the daemon packet, a one-time pad of the tag, GF(2^128) families, truncated tags.
+ */
+#define QLDPC_POLYHASH_PRIME 0x1FFFFFFFFFFFFFFFull
+#define QLDPC_POLYHASH_TILE_WORDS 8192         /* coefficients per workgroup of the production instance */
+#define QLDPC_POLYHASH_TILE_WORDS_SMALL 1024   /* of the small instance, which reaches every multi-tile structure at test sizes */
+typedef struct qldpc_polyhash_ctx qldpc_polyhash_ctx;
+typedef struct {
+    int device, max_blocks, max_key_bits;
+    int n_keys;                /* independent keys per block, 1 .. 4 */
+    int tile_words;            /* 0 = QLDPC_POLYHASH_TILE_WORDS; QLDPC_POLYHASH_TILE_WORDS_SMALL = the small instance */
+} qldpc_polyhash_cfg;
+/* max_blocks 64, 2^16 key bits, one key, the production tile, device 0 */
+void   qldpc_polyhash_cfg_default(qldpc_polyhash_cfg *cfg);
+int    qldpc_polyhash_create_cfg(const qldpc_polyhash_cfg *cfg, qldpc_polyhash_ctx **out);
+void   qldpc_polyhash_free(qldpc_polyhash_ctx *ph);
+size_t qldpc_polyhash_device_bytes(const qldpc_polyhash_ctx *ph);
+/* host buffers, n <= max_blocks blocks of any mix of lengths; hash_keys[i]: the 2 n_keys words of block i's keys, tag_words[i]: 2 n_keys
+   words.  When all n hash_keys pointers are equal the row is uploaded once and shared */
+int    qldpc_polyhash_blocks(qldpc_polyhash_ctx *ph, int n, const uint32_t *const *key_words, const int *key_bits,
+                             const uint32_t *const *hash_keys, uint32_t *const *tag_words);
+/* device-resident rows key_stride / hash_key_stride / tag_stride words apart (hash_key_stride 0: every block reads row 0); key_bits is a
+   host array; asynchronous on hip_stream; writes exactly 2 n_keys words of row i */
+int    qldpc_polyhash_blocks_dev(qldpc_polyhash_ctx *ph, int n, const uint32_t *d_keys, size_t key_stride, const int *key_bits,
+                                 const uint32_t *d_hash_keys, size_t hash_key_stride, uint32_t *d_tags, size_t tag_stride, void *hip_stream);
+/* n_keys (log2(W + 2) - 61): log2 of the bound above; 0 on a bad argument */
+double qldpc_polyhash_bound_log2(int key_bits, int n_keys);
+/* 61 n_keys; 0 on a bad argument */
+int    qldpc_polyhash_leaked_bits(int n_keys);
+/* host mirror, for tests: no device; the core header's functions over the kernels' own decomposition with `lanes` lanes per workgroup (the
+   kernels: 256) and tiles of tile_words (as in the configuration).  Every lanes >= 1 and either tile give the same tag */
+int    qldpc_polyhash_host(const uint32_t *key_words, int key_bits, const uint32_t hash_key[2], int lanes, int tile_words, uint32_t tag[2]);
+/* the field arithmetic, for tests: a b mod p for any a, b, and the field element of a key's two words */
+uint64_t qldpc_polyhash_mul_host(uint64_t a, uint64_t b);
+uint64_t qldpc_polyhash_key_host(uint32_t hi, uint32_t lo);
 
 /* ------------------------------------------------------------------ Monte-Carlo FER loop ---- */
 /*

@@ -922,7 +922,7 @@ def privamp_expand_host(v, workbits, seed, final_bits):
     return out
 
 
-# ---- what the batch contexts of the two hashes (PrivAmp, Toeplitz) do with the arguments of a call ---------------------------------
+# ---- what the batch contexts of the hashes (PrivAmp, Toeplitz, PolyHash) do with the arguments of a call ---------------------------------
 
 def _hb_words(bits):
     return [(b + 31) >> 5 if b > 0 else 0 for b in bits.tolist()]
@@ -1164,6 +1164,130 @@ class Toeplitz:
     def __del__(self):
         try:
             _L.qldpc_toeplitz_free(self._h)
+        except Exception:
+            pass
+
+
+# ---- error verification by a universal hash (qldpc_polyhash_*): tag = SUM_j c_j k^(W+1-j) mod 2^61 - 1, the caller's keys ---------------
+
+class _PolyHashCfg(C.Structure):
+    _fields_ = [("device", C.c_int), ("max_blocks", C.c_int), ("max_key_bits", C.c_int), ("n_keys", C.c_int), ("tile_words", C.c_int)]
+
+
+_sig("qldpc_polyhash_cfg_default", None, [C.POINTER(_PolyHashCfg)])
+_sig("qldpc_polyhash_create_cfg", C.c_int, [C.POINTER(_PolyHashCfg), C.POINTER(_vp)])
+_sig("qldpc_polyhash_free", None, [_vp])
+_sig("qldpc_polyhash_device_bytes", C.c_size_t, [_vp])
+_sig("qldpc_polyhash_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, C.POINTER(_up), C.POINTER(_up)])
+_sig("qldpc_polyhash_blocks_dev", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _ip, _vp, C.c_size_t, _vp, C.c_size_t, _vp])
+_sig("qldpc_polyhash_bound_log2", C.c_double, [C.c_int, C.c_int])
+_sig("qldpc_polyhash_leaked_bits", C.c_int, [C.c_int])
+_sig("qldpc_polyhash_host", C.c_int, [_up, C.c_int, _up, C.c_int, C.c_int, _up])
+_sig("qldpc_polyhash_mul_host", C.c_uint64, [C.c_uint64, C.c_uint64])
+_sig("qldpc_polyhash_key_host", C.c_uint64, [C.c_uint32, C.c_uint32])
+POLYHASH_PRIME = (1 << 61) - 1
+POLYHASH_TILE_WORDS, POLYHASH_TILE_WORDS_SMALL = 8192, 1024
+POLYHASH_LANES = 256
+
+
+def polyhash_mul(a, b):
+    """a b mod POLYHASH_PRIME with the core header's multiply, for any 64-bit a, b"""
+    return int(_L.qldpc_polyhash_mul_host(int(a) & 0xFFFFFFFFFFFFFFFF, int(b) & 0xFFFFFFFFFFFFFFFF))
+
+
+def polyhash_key(hi, lo):
+    """the field element of a key's two words: ((hi << 32) | lo) & POLYHASH_PRIME, the prime itself taken as 0"""
+    return int(_L.qldpc_polyhash_key_host(int(hi) & 0xFFFFFFFF, int(lo) & 0xFFFFFFFF))
+
+
+def polyhash_bound_log2(key_bits, n_keys=1):
+    """log2 of the probability bound that two different blocks of up to key_bits bits give equal tags: n_keys (log2(W + 2) - 61)"""
+    if int(key_bits) <= 0 or not 1 <= int(n_keys) <= 4:
+        raise QldpcError(-6, "polyhash_bound_log2: key_bits = %d, n_keys = %d" % (key_bits, n_keys))
+    return float(_L.qldpc_polyhash_bound_log2(int(key_bits), int(n_keys)))
+
+
+def polyhash_leaked_bits(n_keys=1):
+    """bits of a block that its tag discloses at the most: 61 n_keys"""
+    if not 1 <= int(n_keys) <= 4:
+        raise QldpcError(-6, "polyhash_leaked_bits: n_keys = %d" % n_keys)
+    return int(_L.qldpc_polyhash_leaked_bits(int(n_keys)))
+
+
+def polyhash_host(key_words, key_bits, hash_key, lanes=POLYHASH_LANES, tile_words=0):
+    """the tag of one block under one key (hash_key: its two words hi, lo) on the host, by the kernels' own decomposition with `lanes` lanes
+    per workgroup and tiles of tile_words (0: the production tile) -> the tag's two words (hi, lo); every lanes >= 1 and either tile
+    give the same tag"""
+    kw = np.ascontiguousarray(key_words, dtype=np.uint32)
+    hk = np.ascontiguousarray(hash_key, dtype=np.uint32)
+    key_bits = int(key_bits)
+    if key_bits <= 0 or kw.size < (key_bits + 31) // 32 or hk.size < 2:
+        raise QldpcError(-6, "polyhash_host: %d key words, key_bits = %d, %d hash key words" % (kw.size, key_bits, hk.size))
+    out = np.zeros(2, np.uint32)
+    _chk(_L.qldpc_polyhash_host(kw.ctypes.data_as(_up), key_bits, hk.ctypes.data_as(_up), int(lanes), int(tile_words), out.ctypes.data_as(_up)), "polyhash_host")
+    return out
+
+
+class PolyHash:
+    """Error verification for batches of blocks of any mix of lengths, one launch per call (qldpc_polyhash_blocks*): polynomial evaluation
+    over 2^61 - 1 with the length as a coefficient, n_keys independent keys per block.  The keys are the caller's: two uniformly random words
+    (hi, lo) per key, chosen after the blocks are fixed; the blocks of a call may share them.  A tag is 2 n_keys words.  Everything is
+    allocated here; blocks() / blocks_dev() allocate nothing on the device.  tile_words: 0 = the production tile,
+    POLYHASH_TILE_WORDS_SMALL = the small instance; the tags do not depend on it."""
+
+    def __init__(self, max_blocks=64, max_key_bits=1 << 16, n_keys=1, device=0, tile_words=0):
+        cfg = _PolyHashCfg()
+        _L.qldpc_polyhash_cfg_default(C.byref(cfg))
+        cfg.device, cfg.max_blocks, cfg.max_key_bits, cfg.n_keys, cfg.tile_words = int(device), int(max_blocks), int(max_key_bits), int(n_keys), int(tile_words)
+        h = _vp()
+        _chk(_L.qldpc_polyhash_create_cfg(C.byref(cfg), C.byref(h)), "PolyHash")
+        self._h = h
+        self.device, self.max_blocks, self.max_key_bits, self.n_keys = int(device), int(max_blocks), int(max_key_bits), int(n_keys)
+        self.tile_words = int(tile_words) or POLYHASH_TILE_WORDS
+
+    @property
+    def device_bytes(self):
+        return int(_L.qldpc_polyhash_device_bytes(self._h))
+
+    def blocks(self, keys, key_bits, hash_keys, out=None):
+        """keys: list of uint32 word arrays (bits past key_bits[i] are ignored); hash_keys: list of arrays of 2 n_keys words (hi, lo per
+        key), or ONE such array, uploaded once and shared by the blocks -> list of 2 n_keys-word tags.
+        out: arrays to write into instead (a refused call leaves them untouched)"""
+        n = len(keys)
+        kb, = _hb_args("PolyHash", n, key_bits=key_bits)
+        if isinstance(hash_keys, np.ndarray) and hash_keys.ndim == 1:
+            hash_keys = [hash_keys] * n
+        elif len(hash_keys) != n:
+            raise QldpcError(-6, "PolyHash.blocks: %d blocks, %d hash keys" % (n, len(hash_keys)))
+        if n > 0 and all(s is hash_keys[0] for s in hash_keys):     # one object: one row for the library, whatever it converts to
+            hash_keys = [np.ascontiguousarray(hash_keys[0], dtype=np.uint32)] * n
+        tag = [2 * self.n_keys] * n
+        kws, kp = _hb_rows("PolyHash.blocks", "key", n, keys, _hb_words(kb))
+        hws, hp = _hb_rows("PolyHash.blocks", "hash key", n, hash_keys, tag)
+        out, op = _hb_rows("PolyHash.blocks", "out", n, out, tag)
+        _chk(_L.qldpc_polyhash_blocks(self._h, n, kp, _hb_ptr(kb, C.c_int), hp, op), "PolyHash.blocks")
+        return out
+
+    def blocks_dev(self, keys_t, key_bits, hash_keys_t, key_shared=False, out_t=None, stream=None):
+        """keys_t: torch int32 [n, key_stride] on the device; hash_keys_t: int32 [n, >= 2 n_keys], or with key_shared a 1-D tensor or one
+        row that every block reads -> out_t int32 [n, tag_stride] (row i: 2 n_keys words written, the rest left as it is); asynchronous
+        on `stream` (default: torch's current stream)"""
+        n = int(keys_t.shape[0])
+        kb, = _hb_args("PolyHash", n, key_bits=key_bits)
+        if key_shared and hash_keys_t.dim() == 1:
+            hash_keys_t = hash_keys_t.unsqueeze(0)
+        tag = [2 * self.n_keys] * n
+        rows = [("keys_t", keys_t, n, _hb_words(kb), ""),
+                ("hash_keys_t", hash_keys_t, 1 if key_shared else n, tag, " (one row with key_shared)"),
+                ("out_t", out_t, n, tag, "")]
+        out_t, (ks, hs, os_), s = _hb_dev_rows(_torch(), "PolyHash.blocks_dev", self.device, rows, stream)
+        _chk(_L.qldpc_polyhash_blocks_dev(self._h, n, keys_t.data_ptr(), ks, _hb_ptr(kb, C.c_int), hash_keys_t.data_ptr(), 0 if key_shared else hs,
+                                          out_t.data_ptr(), os_, s.cuda_stream), "PolyHash.blocks_dev")
+        return out_t
+
+    def __del__(self):
+        try:
+            _L.qldpc_polyhash_free(self._h)
         except Exception:
             pass
 

@@ -18,6 +18,13 @@
  *                     [-N (the -U stage on an NTT context, qldpc_toeplitz_create_cfg with QLDPC_TOEPLITZ_NTT; implies -U.  After every timed call
  *                          the same blocks go through a direct context, untimed, and the words are compared: adds tpa_method,
  *                          tpa_equals_direct (1 when every word of every call was equal) and tpa_checksum (FNV-1a of the last call's words))]
+ *                     [-V (error verification after every timed decode: Alice's tags of her keys and Bob's tags of what he now holds, the
+ *                          blocks that failed included, are each ONE qldpc_polyhash_blocks call over all epochs under one key shared by the
+ *                          call.  The key comes from this tool's own deterministic generator: a MEASUREMENT key, not a random one, and
+ *                          nothing to deploy.  Adds vt_ms_mean, vt_ms_best (Bob's call), vt_agree (blocks with status OK whose tags are
+ *                          equal: must equal reconciled), vt_failed_differ (failed blocks whose tags differ) beside vt_failed_words_differ
+ *                          (failed blocks whose words differ from Alice's: the two must be equal), vt_equals_host (1 when every device tag
+ *                          of the last call equals qldpc_polyhash_host, untimed) and vt_leak_bits; may be given together with -H / -U / -N)]
  *                     (defaults: 512 epochs x 52 429 bits, max_blocks 512, PEG depth 2 = the library's default)
  * prints one JSON object on stdout.
  */
@@ -65,10 +72,10 @@ static void *part_main(void *arg)
 
 int main(int argc, char **argv)
 {
-    int epochs = 512, key_bits = 52429, batch = 512, reps = 3, layered = -1, profile = 0, peg = 2, opt, a_lanes = 0, b_lanes = 0, verbose = 0, split = 1, gap_profile = 0, hash = 0, toeplitz = 0, ntt = 0;
+    int epochs = 512, key_bits = 52429, batch = 512, reps = 3, layered = -1, profile = 0, peg = 2, opt, a_lanes = 0, b_lanes = 0, verbose = 0, split = 1, gap_profile = 0, hash = 0, toeplitz = 0, ntt = 0, verify = 0;
     uint64_t seed = 42;
     double qmin = 0.005, qmax = 0.06, gap = 0.0;
-    while ((opt = getopt(argc, argv, "e:k:b:S:r:q:lfpP:g:A:B:vT:G:HUN")) != -1) {
+    while ((opt = getopt(argc, argv, "e:k:b:S:r:q:lfpP:g:A:B:vT:G:HUNV")) != -1) {
         switch (opt) {
         case 'e': epochs = atoi(optarg); break;
         case 'k': key_bits = atoi(optarg); break;
@@ -88,6 +95,7 @@ int main(int argc, char **argv)
         case 'H': hash = 1; break;
         case 'U': toeplitz = 1; break;
         case 'N': toeplitz = 1; ntt = 1; break;
+        case 'V': verify = 1; break;
         case 'T': split = atoi(optarg); break;      /* experiment: T sessions on T host threads, each decoding every T-th epoch */
         default: fprintf(stderr, "usage: see the head of qldpc_stream.c\n"); return 2;
         }
@@ -238,6 +246,23 @@ int main(int argc, char **argv)
         if (!tz_keys || !tz_seeds || !tz_out || !tz_kb || !tz_ob || !tz_buf || !tz_seed) return 1;
         for (size_t w = 0; w < sw; w++) tz_seed[w] = (uint32_t)rng_next();
     }
+    /* -V: error verification of every block, one measurement key shared by the call */
+    qldpc_polyhash_ctx *vt = NULL;
+    const uint32_t **vt_hk = NULL;
+    uint32_t **vt_a = NULL, **vt_b = NULL, *vt_buf = NULL, vt_key[2] = {0, 0};
+    double vt_best = 1e30, vt_sum = 0.0;
+    int vt_agree = 0, vt_failed_differ = 0, vt_failed_words_differ = 0, vt_equals_host = 1;
+    if (verify) {
+        qldpc_polyhash_cfg vc;
+        qldpc_polyhash_cfg_default(&vc);
+        vc.device = cfg.device; vc.max_blocks = epochs; vc.max_key_bits = key_bits;
+        if ((rc = qldpc_polyhash_create_cfg(&vc, &vt))) return die("polyhash_create_cfg", rc);
+        vt_hk = calloc((size_t)epochs, sizeof(*vt_hk)); vt_a = calloc((size_t)epochs, sizeof(*vt_a)); vt_b = calloc((size_t)epochs, sizeof(*vt_b));
+        vt_buf = calloc((size_t)epochs * 4, 4);
+        if (!vt_hk || !vt_a || !vt_b || !vt_buf) return 1;
+        vt_key[0] = (uint32_t)rng_next(); vt_key[1] = (uint32_t)rng_next();
+        for (int e = 0; e < epochs; e++) { vt_hk[e] = vt_key; vt_a[e] = vt_buf + (size_t)e * 4; vt_b[e] = vt_a[e] + 2; }
+    }
     for (int rep = -1; rep < reps; rep++) {
         memcpy(work, bob, (size_t)epochs * W * 4);
         t0 = now_s();
@@ -297,6 +322,26 @@ int main(int argc, char **argv)
                 }
             }
         }
+        if (verify) {
+            if ((rc = qldpc_polyhash_blocks(vt, epochs, akeys, kb, vt_hk, vt_a))) return die("polyhash_blocks (alice)", rc);
+            t0 = now_s();
+            rc = qldpc_polyhash_blocks(vt, epochs, (const uint32_t *const *)bkeys, kb, vt_hk, vt_b);
+            const double dv = now_s() - t0;
+            if (rc) return die("polyhash_blocks (bob)", rc);
+            if (rep >= 0) { vt_sum += dv; if (dv < vt_best) vt_best = dv; }
+            vt_agree = 0; vt_failed_differ = 0; vt_failed_words_differ = 0;
+            for (int e = 0; e < epochs; e++) {
+                const int same = !memcmp(vt_a[e], vt_b[e], 8);
+                if (status[e] == QLDPC_OK) vt_agree += same;
+                else { vt_failed_differ += !same; vt_failed_words_differ += memcmp(work + (size_t)e * W, alice + (size_t)e * W, (size_t)W * 4) != 0; }
+            }
+            if (rep == reps - 1)
+                for (int e = 0; e < epochs; e++) {
+                    uint32_t tag[2];
+                    if ((rc = qldpc_polyhash_host(bkeys[e], key_bits, vt_key, 256, 0, tag))) return die("polyhash_host", rc);
+                    if (memcmp(tag, vt_b[e], 8)) vt_equals_host = 0;
+                }
+        }
         if (rep < 0) continue;
         sum += dt;
         if (dt < best) best = dt;
@@ -330,6 +375,9 @@ int main(int argc, char **argv)
         printf(", \"tpa_ms_mean\": %.3f, \"tpa_ms_best\": %.3f, \"tdistill_Mbit_s_mean\": %.1f", tz_sum / reps * 1e3, tz_best * 1e3, tz_final_sum / (sum + tz_sum) / 1e6);
     if (ntt)
         printf(", \"tpa_method\": \"ntt\", \"tpa_equals_direct\": %d, \"tpa_checksum\": \"%016llx\"", tz_equal, (unsigned long long)tz_checksum);
+    if (verify)
+        printf(", \"vt_ms_mean\": %.3f, \"vt_ms_best\": %.3f, \"vt_agree\": %d, \"vt_failed_differ\": %d, \"vt_failed_words_differ\": %d, \"vt_equals_host\": %d, \"vt_leak_bits\": %d",
+               vt_sum / reps * 1e3, vt_best * 1e3, vt_agree, vt_failed_differ, vt_failed_words_differ, vt_equals_host, qldpc_polyhash_leaked_bits(1));
     if (profile) {
         qldpc_kernel_stat st[16];
         qldpc_recon_profile_enable(rb, 1);
@@ -345,6 +393,7 @@ int main(int argc, char **argv)
     qldpc_privamp_free(pa);
     qldpc_toeplitz_free(tz);
     qldpc_toeplitz_free(tz_direct);
+    qldpc_polyhash_free(vt);
     qldpc_recon_free(ra);
     qldpc_recon_free(rb);
     return good == epochs ? 0 : 3;
