@@ -41,6 +41,7 @@
  *   qldpc_mc_sweep                        the BER loop around both, with its puncture count per BER                BS/src/main.cpp:233-272
  *   qldpc_mc_strata / _weight_frames_*    the same loop over fixed error weights instead of BERs: FER(q) for every q   (no counterpart)
  *   qldpc_mc_set_channel / _awgn_table   the channel of the fixed-point sims: BPSK over AWGN, 6-bit received values  ML/BPSK_nrldpc_sim_RM_FP.m
+ *   qldpc_mc_sweep_tables                 the Eb/N0 points of those sims side by side in one batch, a table per point    ML/sim_results.m
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -1084,7 +1085,7 @@ int    qldpc_mc_search_stats(qldpc_mc *mc, qldpc_mc_pattern_stat *rows, int cap)
  * has not made them, the counter and histogram rows and the pinned copies of slot tables and counter rows), counted by
  * qldpc_mc_device_bytes; later sweeps allocate nothing.  A sweep touches neither the counters, histogram and failed-frame list of the last
  * qldpc_mc_run nor the rows of the last search.  Its gain over one qldpc_mc_run per point is not measured yet (tools/mc_sweep_cost.py).
- * Not built: points of a table channel (a table per point); failed-frame lists per point (a failed frame of a point is regenerated with
+ * Points of a table channel (a table per point) are qldpc_mc_sweep_tables below.  Not built: failed-frame lists per point (a failed frame of a point is regenerated with
  * qldpc_mc_run over its index); a puncture pattern drawn per point (qldpc_mc_search does that at one QBER); one encode shared by the points
  * that sit on the same frame; a multi-GPU driver; the deal on the device.
  */
@@ -1123,6 +1124,44 @@ int    qldpc_mc_sweep_hist(qldpc_mc *mc, int point, uint64_t *hist, int cap);
    slots < 1 or max_frames == 0, QLDPC_EINVAL for a missing array) */
 int    qldpc_mc_sweep_deal_host(int n_points, int chunk, int slots, uint64_t max_frames, uint64_t max_frame_errors, const uint64_t *done,
                                 const uint64_t *frame_errors, int *give);
+
+/*
+ * The sweep over operating points of a TABLE channel (an Eb/N0 sweep: the four points per matrix of the reference's fixed-point AWGN experiment,
+ * ML/sim_results.m, in one call).  Everything of qldpc_mc_sweep above holds -- the points side by side in one batch, frame k of every point = frame
+ * first_frame + k, the nested puncture prefixes on top of the fixed set, chunks, the deal, one read-back per round -- with one change: point q draws
+ * its frames through its OWN threshold table table_q ("Quantised soft-output channels" above; the tables of one sweep may differ in levels and
+ * in everything else) and the decoder is loaded with qldpc_load_llr_dev.  The row of point q is exactly what
+ * qldpc_mc_set_channel(table_q) + qldpc_mc_set_puncture(fixed set + prefix_q) + qldpc_mc_run(., first_frame, frames_q, 0) give for that point
+ * alone, for any batch, any chunk and any set of neighbouring points.  `label` is the caller's name for the point -- Eb/N0 in dB, say --; it is
+ * not interpreted and comes back in the `qber` field of the point's qldpc_mc_point_stat.  Rows and histograms are read with
+ * qldpc_mc_sweep_stats / qldpc_mc_sweep_hist: the call is a sweep to them and to qldpc_mc_strata_hist (QLDPC_ESTATE after it).
+ *
+ * The call neither needs nor changes the table of qldpc_mc_set_channel: with one in force or without, qldpc_mc_run afterwards runs as before
+ * (and qldpc_mc_sweep keeps returning QLDPC_ESTATE while one is in force).  Status codes: per table those of qldpc_mc_set_channel (QLDPC_ESIZE for
+ * levels outside 2 .. 256, QLDPC_EINVAL for a missing array, a decreasing row, an entry above 2^32, non-zero reserved words), for the rest those
+ * of qldpc_mc_sweep, and QLDPC_ESIZE for a batch whose quads pass 2^31 lanes.  A refused call queues nothing and leaves the last rows readable.
+ * qldpc_mc_sweep_tables_check_host is every one of these checks without a device; the device call runs it first.  On the device the call adds the P
+ * tables (3 076 bytes each, allocated for the call's P and grown when a later call has more) and, where qldpc_mc_set_channel has not made
+ * them, the LLR rows [batch][N]; both are counted by qldpc_mc_device_bytes.  Against one qldpc_mc_set_channel + qldpc_mc_run per point it is measured on one
+ * configuration only (tools/mc_sweep_cost.py --tables: four points of 20 000 frames on a batch of 20 000, no stop rule: 12.5 ms against 12.3 ms, no gain).  Not built: strata or blind rounds of a table channel, a table per VN class, a frame budget per
+ * point.
+ */
+typedef struct qldpc_mc_table_point {
+    qldpc_mc_channel table;    /* levels 2 .. 256 (0 is no point), cum[2], value; HOST arrays, read during the call only                  */
+    double label;              /* the caller's; returned in qldpc_mc_point_stat.qber                                                      */
+    int n_punct;               /* the first n_punct VNs of punct_order are erased in this point's frames                                  */
+    int reserved;              /* must be zero                                                                                            */
+} qldpc_mc_table_point;
+typedef struct qldpc_mc_sweep_tables_cfg {   /* as qldpc_mc_sweep_cfg, points of tables */
+    const qldpc_mc_table_point *points; int n_points;
+    const int *punct_order; int n_order;
+    int chunk;
+    uint64_t first_frame, max_frames, max_frame_errors;
+    int reserved[2];
+} qldpc_mc_sweep_tables_cfg;
+int    qldpc_mc_sweep_tables(qldpc_mc *mc, const qldpc_mc_sweep_tables_cfg *cfg, qldpc_mc_sweep_result *res);
+/* every argument check of qldpc_mc_sweep_tables for an object of a code of N VNs and this batch, no device: QLDPC_OK or the status the call returns */
+int    qldpc_mc_sweep_tables_check_host(int N, int batch, const qldpc_mc_sweep_tables_cfg *cfg);
 
 /*
  * Fixed-weight error strata: the step that makes a deep FER affordable on the BSC, and there it is exact.  Conditioned on the number W of

@@ -1416,6 +1416,19 @@ _sig("qldpc_mc_llr_host", C.c_int, [C.c_int, C.c_int, _ip, _u8p, C.c_uint64, C.c
 _sig("qldpc_mc_llr_dev", C.c_int, [_vp, C.c_uint64, C.c_int, _vp, _vp, _vp, _vp])
 
 
+class McTablePoint(C.Structure):
+    _fields_ = [("table", McChannel), ("label", C.c_double), ("n_punct", C.c_int), ("reserved", C.c_int)]
+
+
+class McSweepTablesCfg(C.Structure):
+    _fields_ = [("points", C.POINTER(McTablePoint)), ("n_points", C.c_int), ("punct_order", _ip), ("n_order", C.c_int), ("chunk", C.c_int),
+                ("first_frame", C.c_uint64), ("max_frames", C.c_uint64), ("max_frame_errors", C.c_uint64), ("reserved", C.c_int * 2)]
+
+
+_sig("qldpc_mc_sweep_tables", C.c_int, [_vp, C.POINTER(McSweepTablesCfg), C.POINTER(McSweepResult)])
+_sig("qldpc_mc_sweep_tables_check_host", C.c_int, [C.c_int, C.c_int, C.POINTER(McSweepTablesCfg)])
+
+
 def mc_philox_host(counter, key):
     """Philox4x32-10 of a (counter[4], key[2]) -> 4 uint32 words (host mirror of the kernels' generator)"""
     c = np.ascontiguousarray(counter, dtype=np.uint32).ravel()
@@ -1582,6 +1595,36 @@ def mc_llr_host(K, N, seed, table, first_frame, n_frames, cw_words=None, info_bi
                               llr.ctypes.data_as(_fp), flips.ctypes.data_as(_up)), "mc_llr_host")
     del keep
     return llr, flips
+
+
+def _mc_sweep_tables_cfg(tables, labels, n_punct, punct_order, first_frame, max_frames, max_frame_errors, chunk, where):
+    """-> (McSweepTablesCfg, everything it points into): tables = a sequence of (cum0, cum1, value), labels and n_punct one entry per table
+    (None = 0.0 / 0)"""
+    tables = list(tables)
+    P = len(tables)
+    lab = np.zeros(P, np.float64) if labels is None else np.ascontiguousarray(labels, dtype=np.float64).ravel()
+    npn = np.zeros(P, np.int32) if n_punct is None else _np_i32(n_punct).ravel()
+    if lab.size != P or npn.size != P:
+        raise QldpcError(-6, "%s: %d tables, %d labels, %d n_punct" % (where, P, lab.size, npn.size))
+    pts, keep = (McTablePoint * max(P, 1))(), []
+    for i, t in enumerate(tables):
+        ch, arrays = _mc_channel_arg(*t, where)
+        pts[i].table, pts[i].label, pts[i].n_punct = ch, float(lab[i]), int(npn[i])
+        keep.append(arrays)
+    order = _np_i32(punct_order).ravel() if punct_order is not None else np.zeros(0, np.int32)
+    cfg = McSweepTablesCfg()
+    cfg.points, cfg.n_points = pts, P
+    cfg.punct_order, cfg.n_order = (order.ctypes.data_as(_ip) if order.size else None), order.size
+    cfg.chunk, cfg.first_frame = int(chunk), _u64(first_frame)
+    cfg.max_frames, cfg.max_frame_errors = int(max_frames), int(max_frame_errors)
+    return cfg, (pts, keep, order)
+
+
+def mc_sweep_tables_check(N, batch, tables, labels=None, n_punct=None, punct_order=None, first_frame=0, max_frames=1, max_frame_errors=0, chunk=0):
+    """every argument check of MonteCarlo.sweep_tables for a code of N VNs and this batch, no device needed: raises what the call would raise"""
+    cfg, keep = _mc_sweep_tables_cfg(tables, labels, n_punct, punct_order, first_frame, max_frames, max_frame_errors, chunk, "mc_sweep_tables_check")
+    _chk(_L.qldpc_mc_sweep_tables_check_host(int(N), int(batch), C.byref(cfg)), "mc_sweep_tables_check")
+    del keep
 
 
 class MonteCarlo:
@@ -1757,6 +1800,28 @@ class MonteCarlo:
         out["points"] = self.sweep_stats()
         assert out["points"].size == qb.size
         return out
+
+    def sweep_tables(self, tables, labels=None, n_punct=None, punct_order=None, first_frame=0, max_frames=None, max_frame_errors=0, chunk=0):
+        """P operating points of table channels side by side in one batch (qldpc_mc_sweep_tables): point q draws its frames through
+        tables[q] = (cum0, cum1, value), as set_channel takes them, and erases the first n_punct[q] VNs of punct_order on top of set_puncture's
+        set; everything else is sweep()'s.  labels[q] (None = 0.0) is the caller's name of the point and comes back in the `qber` field of its
+        row.  -> dict of the result plus `points`: exactly the counters of set_channel(*tables[q]) + run(., first_frame, frames_q) with that
+        point's puncture set.  The table of set_channel, in force or not, is neither needed nor changed."""
+        cfg, keep = _mc_sweep_tables_cfg(tables, labels, n_punct, punct_order, first_frame, self.batch if max_frames is None else max_frames,
+                                         max_frame_errors, chunk, "MonteCarlo.sweep_tables")
+        res = McSweepResult()
+        _chk(_L.qldpc_mc_sweep_tables(self._h, C.byref(cfg), C.byref(res)), "MonteCarlo.sweep_tables")
+        out = _fields(res)
+        out["points"] = self.sweep_stats()
+        assert out["points"].size == cfg.n_points
+        del keep
+        return out
+
+    def sweep_awgn(self, ebno_dbs, rate, rmax=3.0, maxq=31, **kw):
+        """sweep_tables over BPSK over AWGN at the Eb/N0 values ebno_dbs (dB) and code rate `rate`, each quantised to 2 maxq + 2 levels
+        (mc_awgn_sigma, mc_awgn_table), labelled with its Eb/N0; kw = the other arguments of sweep_tables"""
+        db = np.ascontiguousarray(ebno_dbs, dtype=np.float64).ravel()
+        return self.sweep_tables([mc_awgn_table(mc_awgn_sigma(e, rate), rmax, maxq) for e in db], labels=db, **kw)
 
     def _last_rows(self, stats_fn, dtype, where):
         n = _chk(stats_fn(self._h, None, 0), where)

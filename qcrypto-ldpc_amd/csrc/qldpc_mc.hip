@@ -1,7 +1,7 @@
 /*
  * qldpc_mc.hip -- the Monte-Carlo loop of the reference harness (source -> encoder -> BSC -> decoder -> monitor, BS/src/main.cpp:335-393)
  * with nothing per bit crossing the host (qldpc_mc_*), and what runs around it: the puncture-pattern search, the quantised soft-output channels, the
- * QBER sweep and the fixed-weight error strata.  The frame definition is qldpc_mc_core.h: frame i is a pure function of (seed, i).
+ * QBER sweep, the same sweep over points of a table channel and the fixed-weight error strata.  The frame definition is qldpc_mc_core.h: frame i is a pure function of (seed, i).
  *
  * Three things are stated once and used by every path:
  *   mc_slots           how the slots of a launch get their frame index and their row {threshold or weight, |LLR|}: frame first + f and one row by value
@@ -24,6 +24,12 @@
  *     word, both threshold rows and the value row in LDS (3 KB, loaded once per workgroup), a halving search per VN, one 16-byte store of the
  *     four LLRs where the address allows it (scalars where N % 4 != 0 shifts a row or cuts its last quad); the rx word = the OR of the flip
  *     nibbles of the 8 lanes of a codeword word by xor-shuffles, stored by the first of them.  No atomics, no floating-point arithmetic.
+ * mc_soft_channel_slots: the same lane (mc_soft_lane) on the slots of a round of qldpc_mc_sweep_tables: slot f is frame sl.frame_of(f) and draws
+ *     through table sl.row[f] of the P tables of the call, so a workgroup must stay inside ONE slot to load that table into LDS once:
+ *     grid = (slots, ceil(8 Wn / 256)), blockIdx.x the slot.  What the shape costs for short codes: the last workgroup of a slot is ragged (N = 1 008:
+ *     8 Wn = 256 quads, one full workgroup per frame; N = 1 998: 504 quads, two workgroups, 8 lanes of the second idle; the worst case, 8 Wn = 264,
+ *     leaves 248 of 512 lanes idle), and every workgroup loads its 3 KB table for at most 1 024 VNs = 4 KB of LLRs, as the workgroups of
+ *     mc_soft_channel do -- but from one of P tables (P x 3 KB, L2-resident up to a thousand points) instead of always the same one.
  * mc_channel_weight: the fixed-weight channel of the error strata (the definition is qldpc_mc_core.h), one workgroup per frame slot: the select over
  *     the keys of the channel-class VNs, recomputed from the padded class map (N / 4 Philox calls per pass: at N = 65 536 the keys of a frame do not
  *     fit in LDS).  The final pass gives a lane a whole codeword word: 8 Philox calls, the 32 classes as mc_channel reads them, three masks (keys
@@ -107,27 +113,34 @@ __global__ __launch_bounds__(MC_LANES) void mc_channel(const uint32_t *__restric
     if (w == 0 && llr_mag) llr_mag[f] = r.mag;
 }
 
-/* rows of 8 Wn quads (the padding past N is QLDPC_VN_PUNCTURED: LLR 0, no flip, nothing stored), total = n 8 Wn lanes: a multiple of 8, as the
- * block size is, so the 8 lanes of a codeword word leave or stay together and the shuffles below see all of them.  rx may be NULL. */
-__global__ __launch_bounds__(MC_LANES) void mc_soft_channel(const uint32_t *__restrict__ cw, uint32_t *__restrict__ rx, float *__restrict__ llr,
-                                                            const uint32_t *__restrict__ cls4, const mc_soft_table *__restrict__ tab, unsigned total,
-                                                            unsigned Qn, unsigned N, uint64_t seed, uint64_t first, uint32_t t_pinned)
+/* the table of a workgroup of the two soft channels, in LDS; load() is called by every lane of the workgroup and ends behind a barrier */
+struct mc_soft_lds {
+    uint32_t thr[2][MC_SOFT_MAX_LEVELS];
+    float value[MC_SOFT_MAX_LEVELS];
+    uint32_t live[2];
+    __device__ void load(const mc_soft_table *__restrict__ tab)
+    {
+        static_assert(MC_LANES == MC_SOFT_MAX_LEVELS, "the soft channels load one table entry per lane");
+        const unsigned t = threadIdx.x;
+        thr[0][t] = t < MC_SOFT_MAX_LEVELS - 1 ? tab->thr[0][t] : 0xFFFFFFFFu;
+        thr[1][t] = t < MC_SOFT_MAX_LEVELS - 1 ? tab->thr[1][t] : 0xFFFFFFFFu;
+        value[t] = tab->value[t];
+        if (t < 2) live[t] = tab->live[t];
+        __syncthreads();
+    }
+};
+
+/* quad q (of Qn = 8 Wn: the padding past N is QLDPC_VN_PUNCTURED: LLR 0, no flip, nothing stored) of frame slot f, which is frame `frame`: the
+ * four LLRs by ONE 16-byte store where the address allows it, scalars where N % 4 != 0 shifts the row or cuts its last quad; the rx word (rx may be
+ * NULL) = the OR of the flip nibbles of the 8 lanes of a codeword word, stored by the first of them.  The 8 lanes of a word call it together. */
+__device__ static inline void mc_soft_lane(const mc_soft_lds &tab, const uint32_t *__restrict__ cw, uint32_t *__restrict__ rx, float *__restrict__ llr,
+                                           const uint32_t *__restrict__ cls4, unsigned f, unsigned q, unsigned Qn, unsigned N, uint64_t seed, uint64_t frame,
+                                           uint32_t t_pinned)
 {
-    static_assert(MC_LANES == MC_SOFT_MAX_LEVELS, "mc_soft_channel loads one table entry per lane");
-    __shared__ uint32_t thr[2][MC_SOFT_MAX_LEVELS];
-    __shared__ float value[MC_SOFT_MAX_LEVELS];
-    const unsigned t = threadIdx.x;
-    thr[0][t] = t < MC_SOFT_MAX_LEVELS - 1 ? tab->thr[0][t] : 0xFFFFFFFFu;
-    thr[1][t] = t < MC_SOFT_MAX_LEVELS - 1 ? tab->thr[1][t] : 0xFFFFFFFFu;
-    value[t] = tab->value[t];
-    const uint32_t live0 = tab->live[0], live1 = tab->live[1];
-    __syncthreads();
-    const unsigned i = blockIdx.x * MC_LANES + t;
-    if (i >= total) return;
-    const unsigned f = i / Qn, q = i - f * Qn, sh = 28u - 4u * (q & 7u);
-    const uint32_t c = cw[i >> 3];
+    const unsigned w = (f * Qn + q) >> 3, sh = 28u - 4u * (q & 7u);
+    const uint32_t c = cw[w];
     float l[4];
-    uint32_t flips = mc_soft_quad(seed, first + f, q, cls4[q], (c >> sh) & 0xfu, thr[0], live0, thr[1], live1, value, t_pinned, l) << sh;
+    uint32_t flips = mc_soft_quad(seed, frame, q, cls4[q], (c >> sh) & 0xfu, tab.thr[0], tab.live[0], tab.thr[1], tab.live[1], tab.value, t_pinned, l) << sh;
     const unsigned v = 4u * q;
     if (v < N) {
         float *p = llr + (size_t)f * N + v;
@@ -136,7 +149,35 @@ __global__ __launch_bounds__(MC_LANES) void mc_soft_channel(const uint32_t *__re
     }
     if (!rx) return;
     for (int s = 1; s < 8; s <<= 1) flips |= (uint32_t)__shfl_xor((int)flips, s, 64);
-    if ((q & 7u) == 0) rx[i >> 3] = c ^ flips;
+    if ((q & 7u) == 0) rx[w] = c ^ flips;
+}
+
+/* one table for every frame: rows of 8 Wn quads, total = n 8 Wn lanes: a multiple of 8, as the block size is, so the 8 lanes of a codeword
+ * word leave or stay together and the shuffles of mc_soft_lane see all of them.  rx may be NULL. */
+__global__ __launch_bounds__(MC_LANES) void mc_soft_channel(const uint32_t *__restrict__ cw, uint32_t *__restrict__ rx, float *__restrict__ llr,
+                                                            const uint32_t *__restrict__ cls4, const mc_soft_table *__restrict__ tab, unsigned total,
+                                                            unsigned Qn, unsigned N, uint64_t seed, uint64_t first, uint32_t t_pinned)
+{
+    __shared__ mc_soft_lds lds;
+    lds.load(tab);
+    const unsigned i = blockIdx.x * MC_LANES + threadIdx.x;
+    if (i >= total) return;
+    const unsigned f = i / Qn;
+    mc_soft_lane(lds, cw, rx, llr, cls4, f, i - f * Qn, Qn, N, seed, first + f, t_pinned);
+}
+
+/* a table per slot: grid = (slots, ceil(Qn / MC_LANES)) -- the slots in x, whose limit a batch cannot reach; y stays below 65 536 up to N = 2^26 --;
+ * slot blockIdx.x is frame sl.frame_of(slot) through table tabs[sl.row[slot]] (sl has both tables).  Qn = 8 Wn is a multiple of 8, so the 8 lanes
+ * of a codeword word leave or stay together here too. */
+__global__ __launch_bounds__(MC_LANES) void mc_soft_channel_slots(const uint32_t *__restrict__ cw, uint32_t *__restrict__ rx, float *__restrict__ llr,
+                                                                  const uint32_t *__restrict__ cls4, const mc_soft_table *__restrict__ tabs, unsigned Qn,
+                                                                  unsigned N, uint64_t seed, mc_slots sl, uint32_t t_pinned)
+{
+    __shared__ mc_soft_lds lds;
+    const unsigned f = blockIdx.x, q = blockIdx.y * MC_LANES + threadIdx.x;
+    lds.load(tabs + sl.row[f]);
+    if (q >= Qn) return;
+    mc_soft_lane(lds, cw, rx, llr, cls4, f, q, Qn, N, seed, sl.frame_of(f), t_pinned);
 }
 
 __device__ static inline unsigned mc_wave_sum(unsigned x)
@@ -495,7 +536,9 @@ struct qldpc_mc {
     bool soft;                         /* a table is in force */
     int source;                        /* QLDPC_MC_SOURCE_* */
     mc_soft_table *d_tab;
-    float *d_llr;                      /* [batch][N], what qldpc_load_llr_dev takes */
+    float *d_llr;                      /* [batch][N], what qldpc_load_llr_dev takes; shared with the table sweep, allocated by whichever comes first */
+    mc_soft_table *d_tabs;             /* [tabs_cap] the tables of the points of a qldpc_mc_sweep_tables call, grown to the largest P so far */
+    int tabs_cap;
     /* the QBER sweep; the device side is allocated by the first qldpc_mc_sweep (mc_sweep_reserve) */
     bool sweep_ready;
     std::vector<uint32_t> h_fixed;     /* [Wn] the fixed set of qldpc_mc_set_puncture (empty = none): a point's erase row = this OR its prefix */
@@ -547,6 +590,23 @@ template <typename T> static int mc_alloc(qldpc_mc *mc, T **p, size_t count)
     if (hipMalloc((void **)p, sizeof(T) * count) != hipSuccess) { *p = nullptr; qldpc_set_error("mc_create: device allocation of %zu bytes failed", sizeof(T) * count); return QLDPC_ENOMEM; }
     mc->dev_owned.push_back(*p);
     mc->dev_bytes += sizeof(T) * count;
+    return QLDPC_OK;
+}
+
+/* *p holds *cap elements (0: none yet) and is to hold `count`: where it is too small it is replaced by a new buffer of `count`, whose contents are
+ * undefined; the caller has made sure that nothing queued still reads the old one */
+template <typename T> static int mc_grow(qldpc_mc *mc, T **p, int *cap, size_t count)
+{
+    if (*p && (size_t)*cap >= count) return QLDPC_OK;
+    T *fresh = nullptr;
+    const int rc = mc_alloc(mc, &fresh, count);
+    if (rc) return rc;
+    if (*p) {
+        mc->dev_owned.erase(std::find(mc->dev_owned.begin(), mc->dev_owned.end(), (void *)*p));
+        mc->dev_bytes -= sizeof(T) * (size_t)*cap;
+        (void)hipFree(*p);
+    }
+    *p = fresh; *cap = (int)count;
     return QLDPC_OK;
 }
 
@@ -631,15 +691,15 @@ static mc_slots mc_range(uint64_t first, uint32_t t = 0u, float mag = 0.0f) { re
 static mc_slots mc_bsc_range(uint64_t first, double qber) { return mc_range(first, mc_threshold(qber), qldpc_bsc_llr((float)qber)); }
 
 /* source -> encoder -> channel for the n frames of sl on stream s; d_cw / d_rx / d_mag may be NULL from the right; ev != NULL: ev[1] after the
- * source, ev[2] after the encoder.  The channel: d_llr != NULL the table's, LLR rows into d_llr (d_rx may then be NULL alone; sl gives frame
- * first + f, its row and d_mag are not used; the caller has checked n 8 Wn < 2^31); else weight_bits != 0 the fixed weights of sl's rows with
- * keys of weight_bits bits; else the BSC of sl's rows */
+ * source, ev[2] after the encoder.  The channel: d_llr != NULL a table's, LLR rows into d_llr (d_rx may then be NULL alone; d_mag is not used; the
+ * caller has checked n 8 Wn < 2^31): the one table d_tab where sl gives frame first + f, the slot's of d_tabs where sl has both slot tables; else
+ * weight_bits != 0 the fixed weights of sl's rows with keys of weight_bits bits; else the BSC of sl's rows */
 static int mc_generate(qldpc_mc *mc, const mc_slots &sl, int n, uint32_t *d_info, uint32_t *d_cw, uint32_t *d_rx, float *d_mag, hipStream_t s,
                        hipEvent_t *ev = nullptr, float *d_llr = nullptr, int weight_bits = 0)
 {
     const unsigned ti = (unsigned)n * (unsigned)mc->Wk, tn = (unsigned)n * (unsigned)mc->Wn, Wn = (unsigned)mc->Wn;
-    if (weight_bits < 0 || weight_bits > 32 || (d_llr && (sl.frame || sl.row || weight_bits))) {      /* a caller's mistake, not the user's */
-        qldpc_set_error("mc_generate: weight_bits=%d outside 0 .. 32, or the table's channel with slot tables or a weight", weight_bits);
+    if (weight_bits < 0 || weight_bits > 32 || (d_llr && (!sl.frame != !sl.row || weight_bits))) {      /* a caller's mistake, not the user's */
+        qldpc_set_error("mc_generate: weight_bits=%d outside 0 .. 32, or a table channel with one slot table of two or with a weight", weight_bits);
         return QLDPC_EINVAL;
     }
     if (mc->source == QLDPC_MC_SOURCE_ZERO) HIPCHK(hipMemsetAsync(d_info, 0, sizeof(uint32_t) * ti, s));
@@ -653,7 +713,10 @@ static int mc_generate(qldpc_mc *mc, const mc_slots &sl, int n, uint32_t *d_info
     if (rc || (!d_rx && !d_llr)) return rc;
     if (ev) HIPCHK(hipEventRecord(ev[2], s));
     const uint32_t t_pinned = mc_threshold(mc->parity_ber);
-    if (d_llr)
+    if (d_llr && sl.row)
+        hipLaunchKernelGGL(mc_soft_channel_slots, dim3((unsigned)n, mc_blocks(8 * (size_t)Wn)), dim3(MC_LANES), 0, s, (const uint32_t *)d_cw, d_rx, d_llr,
+                           (const uint32_t *)mc->d_cls, (const mc_soft_table *)mc->d_tabs, 8u * Wn, (unsigned)mc->N, mc->seed, sl, t_pinned);
+    else if (d_llr)
         hipLaunchKernelGGL(mc_soft_channel, dim3(mc_blocks(8 * (size_t)tn)), dim3(MC_LANES), 0, s, (const uint32_t *)d_cw, d_rx, d_llr, (const uint32_t *)mc->d_cls,
                            (const mc_soft_table *)mc->d_tab, 8u * tn, 8u * Wn, (unsigned)mc->N, mc->seed, sl.first, t_pinned);
     else if (weight_bits)
@@ -676,14 +739,15 @@ extern "C" int qldpc_mc_frames_dev(qldpc_mc *mc, uint64_t first_frame, int n_fra
     return mc_generate(mc, mc_bsc_range(first_frame, qber), n_frames, d_info, d_cw, d_rx, nullptr, mc->dec->stream);
 }
 
-/* the frames of a batch into the decoder, by the channel in force (a table, else weight_bits as mc_generate takes it): generate (ev as mc_generate
- * takes it), ev_channel, load */
-static int mc_generate_load(qldpc_mc *mc, const mc_slots &sl, int n, hipStream_t s, hipEvent_t *ev, hipEvent_t ev_channel, int weight_bits = 0)
+/* the frames of a batch into the decoder, by the channel in force (a table, else weight_bits as mc_generate takes it) or, `tables`, by the slots'
+ * tables whatever is in force: generate (ev as mc_generate takes it), ev_channel, load */
+static int mc_generate_load(qldpc_mc *mc, const mc_slots &sl, int n, hipStream_t s, hipEvent_t *ev, hipEvent_t ev_channel, int weight_bits = 0, bool tables = false)
 {
-    const int rc = mc_generate(mc, sl, n, mc->d_info, mc->d_cw, mc->d_rx, mc->d_mag, s, ev, mc->soft ? mc->d_llr : nullptr, weight_bits);
+    const bool soft = mc->soft || tables;
+    const int rc = mc_generate(mc, sl, n, mc->d_info, mc->d_cw, mc->d_rx, mc->d_mag, s, ev, soft ? mc->d_llr : nullptr, weight_bits);
     if (rc) return rc;
     HIPCHK(hipEventRecord(ev_channel, s));
-    return mc->soft ? qldpc_load_llr_dev(mc->dec, mc->d_llr, n) : qldpc_load_bits_dev(mc->dec, mc->d_rx, mc->d_mag, mc->d_cls, n);
+    return soft ? qldpc_load_llr_dev(mc->dec, mc->d_llr, n) : qldpc_load_bits_dev(mc->dec, mc->d_rx, mc->d_mag, mc->d_cls, n);
 }
 
 /* mc_soft_channel runs n 8 Wn lanes */
@@ -1057,12 +1121,9 @@ static int mc_sweep_args(const qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg)
                                   cfg->n_points, nullptr, cfg->chunk, cfg->max_frames);
     if (rc) return rc;
     if (!cfg->points || cfg->n_order < 0 || (cfg->n_order > 0 && !cfg->punct_order)) { qldpc_set_error("mc_sweep: a missing array (points, or punct_order with n_order=%d)", cfg->n_order); return QLDPC_EINVAL; }
-    std::vector<bool> seen((size_t)mc->N, false);
-    for (int i = 0; i < cfg->n_order; i++) {
-        const int v = cfg->punct_order[i];
-        if (v < 0 || v >= mc->N || seen[(size_t)v]) { qldpc_set_error("mc_sweep: punct_order[%d] = %d is repeated or outside [0, %d)", i, v, mc->N); return QLDPC_EINVAL; }
-        seen[(size_t)v] = true;
-    }
+    std::vector<uint8_t> seen((size_t)mc->N, 0);
+    const int bad = mc_punct_order_check(cfg->punct_order, cfg->n_order, mc->N, seen.data());
+    if (bad >= 0) { qldpc_set_error("mc_sweep: punct_order[%d] = %d is repeated or outside [0, %d)", bad, cfg->punct_order[bad], mc->N); return QLDPC_EINVAL; }
     for (int q = 0; q < cfg->n_points; q++) {
         const qldpc_mc_point &pt = cfg->points[q];
         if (pt.reserved) { qldpc_set_error("mc_sweep: reserved field %d of point %d must be zero", pt.reserved, q); return QLDPC_EINVAL; }
@@ -1078,10 +1139,11 @@ static int mc_sweep_args(const qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg)
 struct mc_rounds_job {
     int P, C;
     uint64_t first_frame, max_frames, max_fe;
-    const mc_row *rows;                /* [P] {threshold, |LLR|} of the sweep's points, or {weight, |LLR|} of the strata */
+    const mc_row *rows;                /* [P] {threshold, |LLR|} of the sweep's points, or {weight, |LLR|} of the strata; NULL with tabs */
     const uint32_t *erows;             /* [P][Wn] the erase rows, NULL = nothing is erased */
     int weight_key_bits;               /* 0: the BSC of the rows' thresholds (mc_channel); 1 .. 32: the rows' fixed weights (mc_channel_weight) */
     int owner;                         /* MC_ROWS_*: whose rows the device holds from here on */
+    const mc_soft_table *tabs;         /* [P] the tables of the points of a table sweep (mc_soft_channel_slots; d_tabs holds P, d_llr is there), else NULL */
 };
 
 static int mc_rounds(qldpc_mc *mc, const mc_rounds_job &job, uint64_t *last_round /* [P] */, qldpc_mc_sweep_result *res)
@@ -1097,7 +1159,8 @@ static int mc_rounds(qldpc_mc *mc, const mc_rounds_job &job, uint64_t *last_roun
     const mc_slots sl = {(const uint64_t *)mc->d_slots, 0, d_point, mc->d_points, {0u, 0.0f}};
 
     HIPCHK(hipStreamSynchronize(s));      /* a queued kernel may still read the rows of an earlier call */
-    HIPCHK(hipMemcpy(mc->d_points, job.rows, sizeof(mc_row) * (size_t)P, hipMemcpyHostToDevice));
+    if (job.rows) HIPCHK(hipMemcpy(mc->d_points, job.rows, sizeof(mc_row) * (size_t)P, hipMemcpyHostToDevice));
+    if (job.tabs) HIPCHK(hipMemcpy(mc->d_tabs, job.tabs, sizeof(mc_soft_table) * (size_t)P, hipMemcpyHostToDevice));
     if (job.erows) HIPCHK(hipMemcpy(mc->d_prows, job.erows, sizeof(uint32_t) * (size_t)P * Wn, hipMemcpyHostToDevice));
     mc->rows_owner = job.owner;
     HIPCHK(hipMemsetAsync(mc->d_wctr, 0, sizeof(mc_u64) * (size_t)P * MC_POINT_COUNTERS, s));
@@ -1122,7 +1185,7 @@ static int mc_rounds(qldpc_mc *mc, const mc_rounds_job &job, uint64_t *last_roun
             }
         HIPCHK(hipEventRecord(mc->ev[0], s));
         HIPCHK(hipMemcpyAsync(mc->d_slots, mc->h_slots, sizeof(mc_u64) * 3 * B, hipMemcpyHostToDevice, s));      /* pinned: the host rewrites it after the sync below */
-        if ((rc = mc_generate_load(mc, sl, (int)nb, s, mc->ev, mc->ev[3], job.weight_key_bits))) return rc;
+        if ((rc = mc_generate_load(mc, sl, (int)nb, s, mc->ev, mc->ev[3], job.weight_key_bits, job.tabs != nullptr))) return rc;
         HIPCHK(hipEventRecord(mc->ev[4], s));
         if (job.erows && (rc = mc_erase(mc, mc->d_prows, sl, (int)nb, 1, s))) return rc;
         HIPCHK(hipEventRecord(mc->ev[5], s));
@@ -1156,6 +1219,22 @@ static int mc_row_hist(qldpc_mc *mc, int row, uint64_t *hist, int cap)
     return mc_hist_out(mc, mc->d_whist + (size_t)row * (size_t)(mc->n_ite + 1), hist, cap);
 }
 
+/* erows[P][Wn] = the erase rows of the points of a sweep, BSC points or table points: the fixed set of qldpc_mc_set_puncture OR the first n_punct
+ * VNs of the order.  Returns whether any row erases anything */
+template <typename Pt> static bool mc_point_erows(const qldpc_mc *mc, const Pt *points, int P, const int *punct_order, std::vector<uint32_t> *erows)
+{
+    const size_t Wn = (size_t)mc->Wn;
+    bool any = mc->n_fixed != 0;
+    erows->assign((size_t)P * Wn, 0u);
+    for (int q = 0; q < P; q++) {
+        uint32_t *row = erows->data() + (size_t)q * Wn;
+        if (mc->n_fixed) memcpy(row, mc->h_fixed.data(), sizeof(uint32_t) * Wn);
+        for (int i = 0; i < points[q].n_punct; i++) { const int v = punct_order[i]; row[v >> 5] |= 0x80000000u >> (v & 31); }
+        any = any || points[q].n_punct > 0;
+    }
+    return any;
+}
+
 extern "C" int qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc_mc_sweep_result *res)
 {
     if (!mc || !cfg || !res) return QLDPC_EINVAL;
@@ -1163,22 +1242,42 @@ extern "C" int qldpc_mc_sweep(qldpc_mc *mc, const qldpc_mc_sweep_cfg *cfg, qldpc
     int rc = mc_sweep_args(mc, cfg);
     if (rc || (rc = mc_sweep_reserve(mc))) return rc;
     const int P = cfg->n_points;
-    const size_t Wn = (size_t)mc->Wn;
-    /* per sweep: the point rows and the erase rows (fixed set OR prefix), built here once */
+    /* per sweep: the point rows and the erase rows, built here once */
     std::vector<mc_row> prow((size_t)P);
-    std::vector<uint32_t> erows((size_t)P * Wn, 0u);
-    bool any_erase = false;
-    for (int q = 0; q < P; q++) {
-        prow[(size_t)q] = {mc_threshold(cfg->points[q].qber), qldpc_bsc_llr((float)cfg->points[q].qber)};
-        uint32_t *row = erows.data() + (size_t)q * Wn;
-        if (mc->n_fixed) memcpy(row, mc->h_fixed.data(), sizeof(uint32_t) * Wn);
-        for (int i = 0; i < cfg->points[q].n_punct; i++) { const int v = cfg->punct_order[i]; row[v >> 5] |= 0x80000000u >> (v & 31); }
-        any_erase = any_erase || mc->n_fixed || cfg->points[q].n_punct > 0;
-    }
+    std::vector<uint32_t> erows;
+    for (int q = 0; q < P; q++) prow[(size_t)q] = {mc_threshold(cfg->points[q].qber), qldpc_bsc_llr((float)cfg->points[q].qber)};
+    const bool any_erase = mc_point_erows(mc, cfg->points, P, cfg->punct_order, &erows);
     mc->wstats.assign((size_t)P, qldpc_mc_point_stat());
     for (int q = 0; q < P; q++) { mc->wstats[(size_t)q].qber = cfg->points[q].qber; mc->wstats[(size_t)q].n_punct = cfg->points[q].n_punct; }
     const mc_rounds_job job = {P, cfg->chunk ? cfg->chunk : std::min(64, mc->batch), cfg->first_frame, cfg->max_frames, cfg->max_frame_errors, prow.data(),
-                               any_erase ? erows.data() : nullptr, 0, MC_ROWS_SWEEP};
+                               any_erase ? erows.data() : nullptr, 0, MC_ROWS_SWEEP, nullptr};
+    std::vector<uint64_t> last((size_t)P, 0);
+    if ((rc = mc_rounds(mc, job, last.data(), res))) return rc;
+    for (int q = 0; q < P; q++) mc_row_out(mc, q, cfg->max_frames, last[(size_t)q], &mc->wstats[(size_t)q]);
+    return QLDPC_OK;
+}
+
+/* the sweep over points of table channels: the rounds of qldpc_mc_sweep with the slot's table in place of the slot's threshold */
+extern "C" int qldpc_mc_sweep_tables(qldpc_mc *mc, const qldpc_mc_sweep_tables_cfg *cfg, qldpc_mc_sweep_result *res)
+{
+    if (!mc || !cfg || !res) return QLDPC_EINVAL;
+    memset(res, 0, sizeof(*res));
+    int rc = qldpc_mc_sweep_tables_check_host(mc->N, mc->batch, cfg);      /* every argument check, mc_soft_lanes_check's among them */
+    if (rc || (rc = mc_sweep_reserve(mc))) return rc;
+    const int P = cfg->n_points;
+    std::vector<mc_soft_table> tabs((size_t)P);
+    for (int q = 0; q < P; q++) {
+        const qldpc_mc_channel &t = cfg->points[q].table;
+        if (mc_soft_table_build(t.levels, t.cum[0], t.cum[1], t.value, &tabs[(size_t)q])) return QLDPC_EINVAL;      /* not reached: the check has built it */
+    }
+    HIPCHK(hipStreamSynchronize(mc->dec->stream));      /* a queued channel kernel may still read the tables that mc_grow replaces */
+    if ((rc = mc_alloc(mc, &mc->d_llr, (size_t)mc->batch * (size_t)mc->N)) || (rc = mc_grow(mc, &mc->d_tabs, &mc->tabs_cap, (size_t)P))) return rc;
+    std::vector<uint32_t> erows;
+    const bool any_erase = mc_point_erows(mc, cfg->points, P, cfg->punct_order, &erows);
+    mc->wstats.assign((size_t)P, qldpc_mc_point_stat());
+    for (int q = 0; q < P; q++) { mc->wstats[(size_t)q].qber = cfg->points[q].label; mc->wstats[(size_t)q].n_punct = cfg->points[q].n_punct; }
+    const mc_rounds_job job = {P, cfg->chunk ? cfg->chunk : std::min(64, mc->batch), cfg->first_frame, cfg->max_frames, cfg->max_frame_errors, nullptr,
+                               any_erase ? erows.data() : nullptr, 0, MC_ROWS_SWEEP, tabs.data()};
     std::vector<uint64_t> last((size_t)P, 0);
     if ((rc = mc_rounds(mc, job, last.data(), res))) return rc;
     for (int q = 0; q < P; q++) mc_row_out(mc, q, cfg->max_frames, last[(size_t)q], &mc->wstats[(size_t)q]);
@@ -1249,7 +1348,7 @@ extern "C" int qldpc_mc_strata(qldpc_mc *mc, const qldpc_mc_strata_cfg *cfg, qld
     mc->tstats.assign((size_t)P, qldpc_mc_stratum_stat());
     for (int q = 0; q < P; q++) mc->tstats[(size_t)q].weight = cfg->weights[q];
     const mc_rounds_job job = {P, cfg->chunk ? cfg->chunk : std::min(64, mc->batch), cfg->first_frame, cfg->max_frames, cfg->max_frame_errors, prow.data(),
-                               mc->n_fixed ? erows.data() : nullptr, mc_key_bits(cfg->key_bits), MC_ROWS_STRATA};
+                               mc->n_fixed ? erows.data() : nullptr, mc_key_bits(cfg->key_bits), MC_ROWS_STRATA, nullptr};
     std::vector<uint64_t> last((size_t)P, 0);
     if ((rc = mc_rounds(mc, job, last.data(), res))) return rc;
     for (int q = 0; q < P; q++) mc_row_out(mc, q, cfg->max_frames, last[(size_t)q], &mc->tstats[(size_t)q]);

@@ -305,6 +305,17 @@ static inline int mc_sweep_deal(int P, int C, int S, uint64_t max_frames, uint64
     return used;
 }
 
+/* the puncture order of a sweep: distinct VNs inside [0, N), in any order.  seen[N] comes in zeroed.  Returns -1, or the index of the first
+ * offending entry */
+static inline int mc_punct_order_check(const int *order, int n, int N, uint8_t *seen)
+{
+    for (int i = 0; i < n; i++) {
+        if (order[i] < 0 || order[i] >= N || seen[order[i]]) return i;
+        seen[order[i]] = 1;
+    }
+    return -1;
+}
+
 /*
  * Blind reconciliation rounds (qldpc_mc_blind): the schedule, a pure function of the pool counts.  A frame that is still open after round r - 1
  * waits in pool r (1 <= r <= R = max_rounds) as {frame index, known row}; a launch decodes n <= batch frames of ONE level: level 0 = fresh frames,

@@ -3,7 +3,7 @@
  * qldpc_mc_llr_host, qldpc_mc_pattern_host, qldpc_mc_weight_frames_host): the functions of qldpc_mc_core.h that the kernels of qldpc_mc.hip
  * run per lane, here in a loop over frames and words, or over candidates; the table builder of the quantised AWGN channel
  * (qldpc_mc_awgn_table); the deal of one round of the QBER sweep (qldpc_mc_sweep_deal_host), the function qldpc_mc_sweep itself calls per
- * round; the FER estimate over fixed-weight strata (qldpc_mc_strata_fer_host); and the schedule of the blind reconciliation rounds
+ * round; the argument checks of the sweep over table channels (qldpc_mc_sweep_tables_check_host), which qldpc_mc_sweep_tables runs first; the FER estimate over fixed-weight strata (qldpc_mc_strata_fer_host); and the schedule of the blind reconciliation rounds
  * (qldpc_mc_blind_next_host, the function qldpc_mc_blind itself calls per launch) with the efficiency they end at
  * (qldpc_mc_blind_efficiency_host).  Plain C, no device.
  */
@@ -167,6 +167,37 @@ int qldpc_mc_sweep_deal_host(int n_points, int chunk, int slots, uint64_t max_fr
     }
     if (!done || !frame_errors || !give) return QLDPC_EINVAL;
     return mc_sweep_deal(n_points, chunk, slots, max_frames, max_frame_errors, done, frame_errors, give);
+}
+
+/* every argument check of qldpc_mc_sweep_tables, which runs it first: the codes of qldpc_mc_sweep in its order, per table those of
+ * qldpc_mc_set_channel (every table is built once into a scratch table, as qldpc_mc_set_channel builds its own) */
+int qldpc_mc_sweep_tables_check_host(int N, int batch, const qldpc_mc_sweep_tables_cfg *cfg)
+{
+    const char *who = "mc_sweep_tables";
+    if (!cfg) return QLDPC_EINVAL;
+    if (N < 1 || batch < 1) { qldpc_set_error("%s: N=%d batch=%d", who, N, batch); return QLDPC_ESIZE; }
+    if (cfg->reserved[0] || cfg->reserved[1]) { qldpc_set_error("%s: reserved fields %d, %d must be zero", who, cfg->reserved[0], cfg->reserved[1]); return QLDPC_EINVAL; }
+    if (cfg->n_points < 1 || cfg->n_points > MC_SWEEP_MAX_POINTS) { qldpc_set_error("%s: n_points=%d outside 1 .. %d", who, cfg->n_points, MC_SWEEP_MAX_POINTS); return QLDPC_ESIZE; }
+    if (cfg->chunk < 0 || cfg->chunk > batch) { qldpc_set_error("%s: chunk=%d outside [0, batch=%d]", who, cfg->chunk, batch); return QLDPC_ESIZE; }
+    if (cfg->max_frames == 0) { qldpc_set_error("%s: max_frames=0", who); return QLDPC_ESIZE; }
+    if ((uint64_t)batch * 8u * (uint64_t)((N + 31) / 32) >= (1ull << 31)) { qldpc_set_error("%s: %d frames of N = %d pass 2^31 lanes of four VNs", who, batch, N); return QLDPC_ESIZE; }
+    if (!cfg->points || cfg->n_order < 0 || (cfg->n_order > 0 && !cfg->punct_order)) { qldpc_set_error("%s: a missing array (points, or punct_order with n_order=%d)", who, cfg->n_order); return QLDPC_EINVAL; }
+    uint8_t *seen = (uint8_t *)calloc((size_t)N, 1);
+    mc_soft_table *t = (mc_soft_table *)malloc(sizeof(*t));
+    int rc = seen && t ? QLDPC_OK : QLDPC_ENOMEM;
+    const int bad = rc ? -1 : mc_punct_order_check(cfg->punct_order, cfg->n_order, N, seen);
+    if (bad >= 0) { qldpc_set_error("%s: punct_order[%d] = %d is repeated or outside [0, %d)", who, bad, cfg->punct_order[bad], N); rc = QLDPC_EINVAL; }
+    for (int q = 0; q < cfg->n_points && !rc; q++) {
+        const qldpc_mc_table_point *pt = &cfg->points[q];
+        const int dirty = pt->reserved || pt->table.reserved[0] || pt->table.reserved[1];
+        const int built = dirty ? 0 : mc_soft_table_build(pt->table.levels, pt->table.cum[0], pt->table.cum[1], pt->table.value, t);
+        if (dirty) { qldpc_set_error("%s: reserved fields of point %d or of its table must be zero", who, q); rc = QLDPC_EINVAL; }
+        else if (built == -1) { qldpc_set_error("%s: levels=%d of point %d outside 2 .. %d", who, pt->table.levels, q, MC_SOFT_MAX_LEVELS); rc = QLDPC_ESIZE; }
+        else if (built) { qldpc_set_error("%s: the table of point %d has a missing array, a row that decreases or an entry above 2^32", who, q); rc = QLDPC_EINVAL; }
+        else if (pt->n_punct < 0 || pt->n_punct > cfg->n_order) { qldpc_set_error("%s: n_punct=%d of point %d outside [0, n_order=%d]", who, pt->n_punct, q, cfg->n_order); rc = QLDPC_ESIZE; }
+    }
+    free(seen); free(t);
+    return rc;
 }
 
 /* the radix select of a fixed-weight frame (qldpc_mc_core.h) in a loop over the quads: per digit one pass that recomputes the keys of the

@@ -30,7 +30,10 @@
  *                      defaults 3 and 31, in place of the BSC -- the experiment of the reference's fixed-point MATLAB sims -- through
  *                      qldpc_mc_set_channel; every VN goes through the channel but the -u first ones; sigma from the rate K / (N - u); one row, with
  *                      Eb/N0 in place of the QBER; -s and -X do not apply)]
- *                  [-u n (with -A: the first n VNs are punctured, LLR 0: the 2 z of the 5G NR matrices)]
+ *                  [-T lo:hi:step[:rmax:maxq] (with -D: the Eb/N0 points lo, lo + step, .. <= hi of the channel of -A from ONE qldpc_mc_sweep_tables, a table per
+ *                      point, the rows side by side in every batch, in the format of the -A rows; -u and -z as with -A, -E as the stop rule of each
+ *                      row; -A, -W, -X, -w and -B do not apply)]
+ *                  [-u n (with -A or -T: the first n VNs are punctured, LLR 0: the 2 z of the 5G NR matrices)]
  *                  [-z (with -D: the all-zero codeword instead of random info words, qldpc_mc_set_source)]
  *                  [-W (with -D: the -s table from ONE qldpc_mc_sweep instead of one qldpc_mc_run per row: the rows side by side in every batch,
  *                      -E as the stop rule of each row, the lanes of a finished row passing to the others; with -W, -e f is legal under -D: the
@@ -96,6 +99,8 @@ static double search_eff = 0.0;      /* -X: > 0 = the pattern search on the devi
 static int frames_per_pattern = 64;
 static int awgn = 0, awgn_maxq = 31, awgn_punct = 0, zero_source = 0, sweep = 0;      /* -A, -u, -z, -W */
 static double ebno_db = 0.0, awgn_rmax = 3.0, quant_scale = 0.0;
+static int tsweep = 0;      /* -T */
+static double t_lo = 0.0, t_hi = 0.0, t_step = 0.0;
 static int strata = 0, w_lo = 0, w_hi = 0, w_step = 1;      /* -w */
 static double design_qber = 0.0;
 static int blind = 0, ask_bits = 0, max_rounds = 0;      /* -B */
@@ -161,7 +166,7 @@ static int write_pattern(double ber, int n_punct, const int *vn, long long fe)
 static int parse(int argc, char **argv)
 {
     int opt;
-    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:u:c:w:B:g:DRWlvnz")) != -1) {
+    while ((opt = getopt(argc, argv, "N:K:a:q:r:p:i:f:b:s:S:P:e:d:Q:o:G:E:X:F:A:T:u:c:w:B:g:DRWlvnz")) != -1) {
         switch (opt) {
         case 'N': N = atoi(optarg); break;
         case 'K': K = atoi(optarg); break;
@@ -184,6 +189,7 @@ static int parse(int argc, char **argv)
         case 'X': search_eff = atof(optarg); break;
         case 'F': frames_per_pattern = atoi(optarg); break;
         case 'A': { const int got = sscanf(optarg, "%lf:%lf:%d", &ebno_db, &awgn_rmax, &awgn_maxq); if (got != 1 && got != 3) return usage("-A ebno_db[:rmax:maxq]"); awgn = 1; break; }
+        case 'T': { const int got = sscanf(optarg, "%lf:%lf:%lf:%lf:%d", &t_lo, &t_hi, &t_step, &awgn_rmax, &awgn_maxq); if (got != 3 && got != 5) return usage("-T lo:hi:step[:rmax:maxq]"); tsweep = 1; break; }
         case 'u': awgn_punct = atoi(optarg); break;
         case 'z': zero_source = 1; break;
         case 'W': sweep = 1; break;
@@ -203,6 +209,9 @@ static int parse(int argc, char **argv)
     for (int i = 0; i < 8; i++) if (!strcmp(rule_name, names[i])) rule = i;
     if (rule < 0) { fprintf(stderr, "unknown rule %s\n", rule_name); return 2; }
     const int search_x = search_eff != 0.0;
+    if (tsweep && !on_device) return usage("qldpc_sim: -T is the Eb/N0 sweep on the device and needs -D");
+    if (tsweep && (awgn || sweep || search_x || strata || blind)) return usage("qldpc_sim: -T sweeps Eb/N0 points of the table channel and runs with none of -A, -W, -X, -w and -B");
+    if (tsweep && !(t_step > 0.0 && t_lo <= t_hi)) return usage("qldpc_sim: -T lo:hi:step with lo <= hi and step > 0");
     if (sweep && !on_device) return usage("qldpc_sim: -W is the sweep on the device and needs -D");
     if (sweep && (search_x || awgn)) return usage("qldpc_sim: -W sweeps the BSC rows of -s and runs neither with the pattern search (-X) nor with -A");
     if (strata && !on_device) return usage("qldpc_sim: -w runs the error strata on the device and needs -D");
@@ -217,7 +226,7 @@ static int parse(int argc, char **argv)
     if (search_eff < 0.0) return usage("qldpc_sim: -X f with f > 0");
     if ((awgn || zero_source) && !on_device) return usage("qldpc_sim: -A and -z belong to the loop on the device and need -D");
     if (awgn && search_x) return usage("qldpc_sim: -A does not run with the pattern search (-X)");
-    if (awgn_punct && !awgn) return usage("qldpc_sim: -u needs -A");
+    if (awgn_punct && !awgn && !tsweep) return usage("qldpc_sim: -u needs -A or -T");
     if (giveup < 0) return usage("qldpc_sim: -g patience with patience >= 1 (0 = off)");
     if (giveup && (!synd || layered == 2)) return usage("qldpc_sim: -g works on the syndrome tests of the flooding and the horizontal-layered (-l) schedule: drop -n / -v");
     return 0;
@@ -261,8 +270,8 @@ static int setup(void)
     qldpc_mc_cfg mcfg;
     qldpc_mc_cfg_default(&mcfg);
     mcfg.seed = seed; mcfg.batch = batch; mcfg.parity_ber = parity_ber;
-    if (awgn && (awgn_punct < 0 || awgn_punct >= N)) { fprintf(stderr, "qldpc_sim: -u %d outside [0, N = %d)\n", awgn_punct, N); return 2; }
-    uint8_t *cls = awgn ? (uint8_t *)calloc((size_t)N, 1) : NULL;      /* -A: every VN through the channel (class 0) but the punctured ones */
+    if ((awgn || tsweep) && (awgn_punct < 0 || awgn_punct >= N)) { fprintf(stderr, "qldpc_sim: -u %d outside [0, N = %d)\n", awgn_punct, N); return 2; }
+    uint8_t *cls = awgn || tsweep ? (uint8_t *)calloc((size_t)N, 1) : NULL;      /* -A, -T: every VN through the channel (class 0) but the punctured ones */
     for (int v = 0; cls && v < awgn_punct; v++) cls[v] = QLDPC_VN_PUNCTURED;
     if ((rc = qldpc_mc_create(dec, enc, cls, &mcfg, &mc))) return die("mc_create", rc);      /* NULL: info VNs through the BSC, the others pinned, as in run_host */
     free(cls);
@@ -287,6 +296,40 @@ static int mode_awgn(void)
     qldpc_mc_result r;
     if ((rc = qldpc_mc_run(mc, 0.25 /* not used with a table */, 0, MAX_FRAMES, max_fe, &r))) return die("mc_run", rc);
     row_f(ebno_db, r.frames, r.bit_errors, r.frame_errors, (double)r.frames, r.decode_ms * 1e-3);
+    return 0;
+}
+
+/* -T: the Eb/N0 points from ONE qldpc_mc_sweep_tables, a table per row */
+static int mode_tsweep(void)
+{
+    const double rate = (double)K / (double)(N - awgn_punct);
+    const int Q = 2 * awgn_maxq + 2;
+    int P = 0, rc;
+    while (t_lo + (double)P * t_step <= t_hi + 1e-9 && P <= QLDPC_MC_SWEEP_MAX_POINTS) P++;
+    if (P > QLDPC_MC_SWEEP_MAX_POINTS) { fprintf(stderr, "qldpc_sim: -T gives more than %d points\n", QLDPC_MC_SWEEP_MAX_POINTS); return 2; }
+    qldpc_mc_table_point *pts = (qldpc_mc_table_point *)calloc((size_t)P, sizeof(*pts));
+    qldpc_mc_point_stat *rows = (qldpc_mc_point_stat *)malloc(sizeof(*rows) * (size_t)P);
+    uint64_t *cum = (uint64_t *)malloc(sizeof(uint64_t) * 2 * 256 * (size_t)P);
+    float *value = (float *)malloc(sizeof(float) * 256 * (size_t)P);
+    if (!pts || !rows || !cum || !value) return die("mc_sweep_tables", QLDPC_ENOMEM);
+    for (int q = 0; q < P; q++) {
+        const double db = t_lo + (double)q * t_step, sigma = sqrt(1.0 / (2.0 * rate * pow(10.0, db / 10.0)));
+        uint64_t *c = cum + 512 * (size_t)q;
+        if ((rc = qldpc_mc_awgn_table(sigma, awgn_rmax, awgn_maxq, c, c + 256, value + 256 * (size_t)q))) return die("mc_awgn_table", rc);
+        pts[q].table.levels = Q; pts[q].table.cum[0] = c; pts[q].table.cum[1] = c + 256; pts[q].table.value = value + 256 * (size_t)q;
+        pts[q].label = db;
+        printf("# Eb/N0 %.4f dB at rate %d / %d: sigma %.6f, %d levels, rmax %g\n", db, K, N - awgn_punct, sigma, Q, awgn_rmax);
+    }
+    qldpc_mc_sweep_tables_cfg tcfg;
+    memset(&tcfg, 0, sizeof(tcfg));
+    tcfg.points = pts; tcfg.n_points = P; tcfg.max_frames = MAX_FRAMES; tcfg.max_frame_errors = max_fe;
+    qldpc_mc_sweep_result w;
+    if ((rc = qldpc_mc_sweep_tables(mc, &tcfg, &w))) return die("mc_sweep_tables", rc);
+    if ((rc = qldpc_mc_sweep_stats(mc, rows, P)) < 0) return die("mc_sweep_stats", rc);
+    printf("# table sweep: %d points in %llu rounds, %llu frames\n", P, (unsigned long long)w.rounds, (unsigned long long)w.frames);
+    for (int q = 0; q < P; q++)      /* SIM_THR: the sweep's decode time is shared by the rows, as under -W */
+        row_f(rows[q].qber, rows[q].frames, rows[q].bit_errors, rows[q].frame_errors, (double)w.frames, w.decode_ms * 1e-3);
+    free(pts); free(rows); free(cum); free(value);
     return 0;
 }
 
@@ -518,7 +561,7 @@ int main(int argc, char **argv)
 {
     int rc = parse(argc, argv);
     if (!rc) rc = setup();
-    if (!rc) rc = !on_device ? run_host() : awgn ? mode_awgn() : strata ? mode_strata() : blind ? mode_blind() : sweep ? mode_sweep() : search_eff > 0.0 ? mode_search() : mode_rows();
+    if (!rc) rc = !on_device ? run_host() : awgn ? mode_awgn() : tsweep ? mode_tsweep() : strata ? mode_strata() : blind ? mode_blind() : sweep ? mode_sweep() : search_eff > 0.0 ? mode_search() : mode_rows();
     if (rc) return rc;
     qldpc_mc_free(mc);
     qldpc_decoder_free(dec); qldpc_encoder_free(enc); qldpc_code_free(H);

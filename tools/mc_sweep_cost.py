@@ -12,11 +12,20 @@ runs:   the host loop the sweep replaces, one qldpc_mc_run per point with the sa
 same:   one qldpc_mc_run per point over exactly the frames_q frames the sweep gave the point (the same frames, no stop rule): wall time and
         batches; its counters must equal the sweep's rows, which the tool asserts.
 No threshold and no claim: the file is the measurement.
+
+--tables: the sweep over points of a table channel (qldpc_mc_sweep_tables) instead, on the reference's fixed-point AWGN experiment (NR_2_6_52, first
+2 z VNs punctured, all-zero codeword, layered 8-bit OMS offset 2, 20 iterations): ONE MonteCarlo.sweep_awgn over the four published Eb/N0 points
+against four set_awgn + run calls over the same --max-frames frames in the same process, both on the host's clock (the four calls include their
+table uploads and stream syncs, which is what a caller pays), with the sweep's per-round stage times; the rows must be equal, which the tool
+asserts.  Writes profiles/mc_sweep_tables_cost.json.
+
+    timeout -k 10 600 python tools/mc_sweep_cost.py --tables
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -74,6 +83,42 @@ def measure(q, qbers, max_frames, max_fe):
                 device_bytes=mc.device_bytes)
 
 
+def measure_tables(q, frames, reps):
+    pins = json.load(open(os.path.join(ROOT, "tests", "golden", "matlab_fp_fer.json")))["NR_2_6_52"]
+    code = q.Code.from_qc(os.path.join(ROOT, "tests", "golden", pins["qc"]))
+    enc = q.Encoder(code, "QC")
+    cls = np.zeros(code.N, np.uint8)
+    cls[:2 * pins["z"]] = q.VN_PUNCTURED
+    rate, ebno = enc.K / (code.N - 2 * pins["z"]), [row[0] for row in pins["rows"]]
+    dec = q.Decoder(code, enc.K, 20, info_bits_pos=enc.info_bits_pos, rule="OMS", rule_param=2.0, n_frames=frames, schedule="hlayered", enable_syndrome=False,
+                    msg_dtype="i8", quant_scale=1.0)
+    mc = q.MonteCarlo(dec, enc, vn_class=cls, seed=1)
+    mc.set_source("zero")
+    mc.sweep_awgn(ebno[:1], rate, max_frames=frames)                                       # warm-up: first launches, allocations
+    mc.set_awgn(ebno_db=ebno[0], rate=rate)
+    mc.run(0.1, 0, frames)
+    sweeps, calls = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        w = mc.sweep_awgn(ebno, rate, max_frames=frames)
+        sweeps.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        runs = []
+        for e in ebno:
+            mc.set_awgn(ebno_db=e, rate=rate)
+            runs.append(mc.run(0.1, 0, frames))
+        calls.append((time.perf_counter() - t0) * 1e3)
+        for i, r in enumerate(runs):
+            assert all(int(r[k]) == int(w["points"][k][i]) for k in ROW), (i, r, w["points"][i])
+    return dict(workload="NR_2_6_52 N %d K %d, first %d VNs punctured, all-zero codeword, layered 8-bit OMS offset 2, 20 iterations, batch %d, Eb/N0 %s dB, "
+                         "%d frames per point, %d repetitions" % (code.N, enc.K, 2 * pins["z"], frames, ebno, frames, reps),
+                sweep=dict(wall_ms=sweeps, median_wall_ms=float(np.median(sweeps)), rounds=w["rounds"], frames=w["frames"],
+                           per_round_ms={k: w[k] / w["rounds"] for k in SWEEP_STAGES}, frame_errors_per_point=[int(x) for x in w["points"]["frame_errors"]]),
+                calls=dict(wall_ms=calls, median_wall_ms=float(np.median(calls)), batches=sum(r["batches"] for r in runs), frames=sum(r["frames"] for r in runs),
+                           decode_ms=sum(r["decode_ms"] for r in runs), channel_ms=sum(r["channel_ms"] for r in runs)),
+                calls_over_sweep=float(np.median(calls) / np.median(sweeps)), device_bytes=mc.device_bytes)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mc_sweep_cost.json"))
@@ -81,9 +126,21 @@ def main():
     ap.add_argument("--qber", default="0.02:0.034")
     ap.add_argument("--max-frames", type=int, default=4 * BATCH)
     ap.add_argument("--max-fe", type=int, default=100)
+    ap.add_argument("--tables", action="store_true", help="the table-channel leg: sweep_awgn over the published points against set_awgn + run per point")
+    ap.add_argument("--reps", type=int, default=5)
     args = ap.parse_args()
     lo, hi = (float(x) for x in args.qber.split(":"))
     import _qldpc_loader
+    if args.tables:
+        out = measure_tables(_qldpc_loader.load(), 20000 if args.max_frames == 4 * BATCH else args.max_frames, args.reps)
+        out["what"] = ("the sweep over points of a table channel on the reference's fixed-point AWGN experiment: one sweep_awgn over the four published Eb/N0 "
+                       "points against four set_awgn + run calls over the same frames, wall times on the host's clock, and the sweep's per-round stage times")
+        path = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "mc_sweep_tables_cost.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(json.dumps(out))
+        return
     out = measure(_qldpc_loader.load(), [float(x) for x in np.linspace(lo, hi, args.points)], args.max_frames, args.max_fe)
     out["what"] = ("the device-resident QBER sweep on the headline code: one sweep of P points against P calls of qldpc_mc_run (with the same stop rule, and over "
                    "exactly the sweep's frames), the sweep's per-round stage times by hipEvents and its lane occupancy per round")
