@@ -4,7 +4,8 @@
  * Mirrors module::Decoder_LDPC_BP_flooding / _horizontal_layered / _vertical_layered as the reference harness drives
  * them (BS/src/main.cpp:193,365,389; VAR/main.cpp (alist-v1.0.1):179-256,438): create(K, N, n_ite,
  * H, info_bits_pos, rule, enable_syndrome, syndrome_depth, n_frames), decode_siho(Y_N, V_K), reset().
- * Everything heavy is a HIP kernel from qldpc_kernels.h; there is no CPU fallback.
+ * Everything heavy is a HIP kernel from qldpc_kernels.h; there is no CPU fallback.  The FRAMES engine (lanes over frames) lives here; a
+ * decoder of the edge-parallel engine leaves every entry point for qldpc_engine_edge.hip after the argument and state checks.
  */
 #include <hip/hip_runtime.h>
 
@@ -19,7 +20,6 @@
 #include <vector>
 
 #include "qldpc_engine_int.h"
-#include "qldpc_kernels_edge.h"
 #include "qldpc_kernels_chain.h"
 #include "qldpc_kernels_compact.h"
 #include "qldpc_kernels_fpost.h"
@@ -105,16 +105,6 @@ static const int CN_CAPS[] = {8, 12, 20, 40};
 static constexpr int VN_CAPS[] = {4, 12};
 static_assert(VN_CAPS[1] == QK_FPV_DMAX, "qk_vn_fpost has a body for every degree of the register-resident VN buckets, the cap-0 bucket holds the rest");
 
-template <typename T> static int dev_alloc(qldpc_decoder *d, T **p, size_t n)
-{
-    *p = nullptr;
-    if (n == 0) n = 1;
-    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
-    if (e != hipSuccess) { qldpc_set_error("hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e)); return QLDPC_ENOMEM; }
-    d->bytes += n * sizeof(T);
-    return QLDPC_OK;
-}
-
 static int make_buckets(qldpc_decoder *d, const int *ptr, const int *ids, int n_ids, const int *caps, int n_caps, std::vector<bucket> &out, const int *var = nullptr)
 {
     std::vector<std::vector<int>> lists(n_caps + 1);
@@ -133,7 +123,7 @@ static int make_buckets(qldpc_decoder *d, const int *ptr, const int *ids, int n_
         bk.d_rec = nullptr;
         int rc = dev_alloc(d, &bk.d_list, lists[k].size());
         if (rc != QLDPC_OK) return rc;
-        out.push_back(bk);      /* owned by the decoder from here on: an error below leaves nothing behind that decoder_free does not release */
+        out.push_back(bk);
         HIPCHK(hipMemcpy(bk.d_list, lists[k].data(), lists[k].size() * sizeof(int), hipMemcpyHostToDevice));
         if (var && bk.cap > 0) {      /* the list once more as records {id, first edge, degree, 0, var[0 .. cap)} (padding: VN 0, never asked for) */
             const size_t stride = (size_t)(QK_REC_HDR + bk.cap);
@@ -173,7 +163,7 @@ static int make_fp_vn_classes(qldpc_decoder *d, const int *vn_ptr, int n_vn, con
         fp_vn_class c{deg, (int)(r.size() / (size_t)QK_FPV_STRIDE(deg)), nullptr};
         int rc = dev_alloc(d, &c.d_rec, r.size());
         if (rc != QLDPC_OK) return rc;
-        out.push_back(c);      /* owned by the decoder from here on */
+        out.push_back(c);
         HIPCHK(hipMemcpy(c.d_rec, r.data(), r.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     return QLDPC_OK;
@@ -196,48 +186,20 @@ extern "C" void qldpc_decoder_cfg_default(qldpc_decoder_cfg *cfg)
 
 static void view_reset(qldpc_decoder *d);
 
-/* everything a generation past 0 owns (hard aliases sgn with 8-bit messages; llr / llr8 / post / msg are views into the decoder's side buffers) */
-static void gen_release(gen_state &n)
-{
-    (void)hipFree(n.sgn); if (n.hard != n.sgn) (void)hipFree(n.hard); (void)hipFree(n.unsat); (void)hipFree(n.done); (void)hipFree(n.ybits); (void)hipFree(n.synd); (void)hipFree(n.ebits);
-    (void)hipFree(n.depth); (void)hipFree(n.iters); (void)hipFree(n.origin); (void)hipFree(n.src); (void)hipFree(n.fmag); (void)hipFree(n.fnch);
-    (void)hipFree(n.gu_last); (void)hipFree(n.gu_best); (void)hipFree(n.gu_since); (void)hipFree(n.gu_gave);
-    n = gen_state{};
-}
-
 extern "C" void qldpc_decoder_free(qldpc_decoder *d)
 {
     if (!d) return;
     (void)hipSetDevice(d->device);
-    view_reset(d);      /* the d_* pointers freed below are the base arrays */
+    view_reset(d);
     if (d->stream) (void)hipStreamSynchronize(d->stream); else (void)hipDeviceSynchronize();
     for (auto &r : d->prof_pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    for (auto &b : d->cn_buckets) (void)hipFree(b.d_list);
-    for (auto &b : d->vn_buckets) (void)hipFree(b.d_list);
-    for (auto &l : d->layer_buckets) for (auto &b : l) { (void)hipFree(b.d_list); (void)hipFree(b.d_rec); }
-    for (auto &b : d->vlayer_classes) (void)hipFree(b.d_list);
-    for (auto &b : d->fp_vn_buckets) (void)hipFree(b.d_list);
-    for (auto &c : d->fp_vn_classes) (void)hipFree(c.d_rec);
-    (void)hipFree(d->d_fp_chain); (void)hipFree(d->d_fp_mem);
-    (void)hipFree(d->d_vn_chk); (void)hipFree(d->d_gang);
-    (void)hipFree(d->d_cn_ptr); (void)hipFree(d->d_cn_tr); (void)hipFree(d->d_cn_var); (void)hipFree(d->d_vn_ptr); (void)hipFree(d->d_info_pos); (void)hipFree(d->d_cn_var_t); (void)hipFree(d->d_vn_tr);
-    (void)hipFree(d->d_chain_order); (void)hipFree(d->d_chain_dep); (void)hipFree(d->d_chain_ver); (void)hipFree(d->d_chain_ctl);
-    (void)hipFree(d->d_llr); (void)hipFree(d->d_llr8); (void)hipFree(d->d_ybits); (void)hipFree(d->d_ebits); (void)hipFree(d->d_known); (void)hipFree(d->d_fmag); (void)hipFree(d->d_fnch); (void)hipFree(d->d_vcls); (void)hipFree(d->d_a); (void)hipFree(d->d_b); (void)hipFree(d->d_post);
-    (void)hipFree(d->d_sgn); if (d->d_hard != d->d_sgn) (void)hipFree(d->d_hard); (void)hipFree(d->d_unsat); (void)hipFree(d->d_done);
-    (void)hipFree(d->gu.weight); (void)hipFree(d->gu.last); (void)hipFree(d->gu.best); (void)hipFree(d->gu.since); (void)hipFree(d->gu.gave); (void)hipFree(d->gu.total);
-    (void)hipFree(d->d_depth); (void)hipFree(d->d_iters); (void)hipFree(d->d_active); (void)hipFree(d->h_in); (void)hipFree(d->h_out); (void)hipFree(d->d_synd); (void)hipFree(d->e_synd);
-    (void)hipFree(d->e_c2v1); (void)hipFree(d->e_ctl); (void)hipFree(d->e_sgn); (void)hipFree(d->e_hard); (void)hipFree(d->e_unsat); (void)hipFree(d->e_done_at);
-    if (d->h_done) (void)hipHostFree(d->h_done);
-    for (auto &g : d->e_graphs) if (g) (void)hipGraphExecDestroy(g);
-    if (d->cap_stream) (void)hipStreamDestroy(d->cap_stream);
-    if (d->e_ev[0]) (void)hipEventDestroy(d->e_ev[0]);
-    if (d->e_ev[1]) (void)hipEventDestroy(d->e_ev[1]);
+    edge_destroy(d);
     if (d->h_active) (void)hipHostFree(d->h_active);
-    (void)hipFree(d->d_work); (void)hipFree(d->d_gcount); (void)hipFree(d->d_goff); (void)hipFree(d->d_llr_alt[0]); (void)hipFree(d->d_llr_alt[1]); (void)hipFree(d->d_llr8_alt[0]); (void)hipFree(d->d_llr8_alt[1]);
-    (void)hipFree(d->d_post_alt[0]); (void)hipFree(d->d_post_alt[1]); (void)hipFree(d->d_msg_alt[0]); (void)hipFree(d->d_msg_alt[1]);
-    for (size_t k = 1; k < d->gens.size(); k++) gen_release(d->gens[k]);
+    for (auto &b : d->ledger) (void)hipFree(b.p);
     delete d;
 }
+
+static int frames_create(qldpc_decoder *d, const qldpc_code *code);
 
 static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, const qldpc_decoder_cfg *cfg, qldpc_decoder *d)
 {
@@ -254,11 +216,11 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
     if (cfg->msg_dtype == 2) V = QI_V;                   /* 8-bit messages: the four frames of a lane are the four bytes of a dword */
     d->V = V; d->FG = 64 * V; d->G = (cfg->max_frames + d->FG - 1) / d->FG;
     d->freeze = cfg->freeze_messages ? 1 : 0;
-    if (const char *e = getenv("QLDPC_FREEZE")) d->freeze = atoi(e) ? 1 : 0;
+    env_flag("QLDPC_FREEZE", &d->freeze);
     /* early exit: the host looks at the active-group counter every 2 iterations once an iteration is long enough to hide the
      * ~30 us round trip (>= 2e7 message updates); small decodes run their iterations as early-returning launches instead */
     d->poll_every = (d->G >= 8 || (double)d->E * d->G * d->FG >= 2e7) ? 2 : 0;
-    if (const char *e = getenv("QLDPC_POLL_EVERY")) d->poll_every = atoi(e);
+    env_int("QLDPC_POLL_EVERY", &d->poll_every);
 
     int rc;
     if ((rc = dev_alloc(d, &d->d_cn_ptr, (size_t)d->M + 1))) return rc;
@@ -297,8 +259,7 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
     for (int k = 0; k < KS_COUNT; k++) { memset(&d->stats[k], 0, sizeof(d->stats[k])); snprintf(d->stats[k].name, sizeof(d->stats[k].name), "%s", ks_names[k]); }
     /* engine choice: lanes over frames (batch) or lanes over edges (one block at a time) */
     {
-        const bool edge_ok = cfg->schedule == QLDPC_SCHED_FLOODING && cfg->rule <= QLDPC_RULE_SPA && code->max_dc <= 64 &&
-                             (size_t)QE_THREADS * (size_t)code->max_dv * sizeof(float) <= 64 * 1024;
+        const bool edge_ok = edge_supports(cfg, code);
         int eng = cfg->engine;
         if (const char *e = getenv("QLDPC_ENGINE")) { int x = atoi(e); if (x >= 0 && x <= 2) eng = x; }
         if (eng == QLDPC_ENGINE_EDGES && !edge_ok) {
@@ -312,9 +273,9 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
         if (eng == QLDPC_ENGINE_AUTO) eng = (edge_ok && cfg->max_frames <= 8) ? QLDPC_ENGINE_EDGES : QLDPC_ENGINE_FRAMES;
         d->engine = eng;
         d->msg_half = cfg->msg_dtype == 1;
-        if (const char *e = getenv("QLDPC_MSG_HALF")) d->msg_half = atoi(e) ? 1 : 0;
+        env_flag("QLDPC_MSG_HALF", &d->msg_half);
         d->packed_h16 = 1;
-        if (const char *e = getenv("QLDPC_PACKED_H16")) d->packed_h16 = atoi(e) ? 1 : 0;
+        env_flag("QLDPC_PACKED_H16", &d->packed_h16);
         d->msg_i8 = cfg->msg_dtype == 2;
         d->quant_scale = cfg->quant_scale > 0.0f ? cfg->quant_scale : 8.0f;      /* measured on the config-2 code: FER at QBER 3.0 % 0.097 (fp32) / 0.119 (scale 8) / 0.168 (scale 4) */
         if (d->msg_i8) {
@@ -332,38 +293,15 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
             else { qldpc_set_error("fp16 message storage is implemented for the flooding schedule on the FRAMES engine"); return QLDPC_EUNSUPPORTED; }
         }
     }
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        const size_t F = (size_t)cfg->max_frames;
-        d->eW = (d->N + 31) / 32;
-        d->eS = code->max_dc <= 8 ? 8 : (code->max_dc <= 16 ? 16 : (code->max_dc <= 32 ? 32 : 64));
-        d->e_lds = (size_t)QE_THREADS * (size_t)code->max_dv * sizeof(float);
-        d->e_stride = cfg->n_ite + 2;
-        if ((rc = dev_alloc(d, &d->d_llr, F * d->N))) return rc;
-        if ((rc = dev_alloc(d, &d->d_a, F * d->E))) return rc;
-        if ((rc = dev_alloc(d, &d->d_b, F * d->E))) return rc;
-        if ((rc = dev_alloc(d, &d->e_c2v1, F * d->E))) return rc;
-        if ((rc = dev_alloc(d, &d->e_sgn, F * d->eW))) return rc;
-        if ((rc = dev_alloc(d, &d->e_hard, F * d->eW))) return rc;
-        if ((rc = dev_alloc(d, &d->e_unsat, F * d->e_stride))) return rc;
-        if ((rc = dev_alloc(d, &d->e_done_at, F))) return rc;
-        HIPCHK(hipHostMalloc((void **)&d->h_done, sizeof(int) * F * 2));
-        HIPCHK(hipEventCreateWithFlags(&d->e_ev[0], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&d->e_ev[1], hipEventDisableTiming));
-        d->poll_every = 2;
-        if (const char *e = getenv("QLDPC_POLL_EVERY")) d->poll_every = atoi(e);
-        /* measured: replaying the chunks as hipGraphs is not faster than plain launches here (345 vs 321 us per
-         * 65 536-VN block; the 2 x ~8 us kernels per iteration are latency-bound on the GPU, not launch-bound on
-         * the host), so graphs stay opt-in */
-        d->use_graphs = 0; d->graph_frames = -1;
-        if (const char *e = getenv("QLDPC_GRAPH")) d->use_graphs = atoi(e) ? 1 : 0;
-        /* QLDPC_EDGE_PERSIST=1: the whole decode of up to 8 blocks as ONE launch, one XCD per block (qe_xcd).  Off by default: measured
-         * 964 us per 65 536-VN block against 325 us with a launch per pass (a chunk of 64 checks is a chain of dependent L2 round trips,
-         * ~8 us, and one XCD has a fifth of the workgroup slots the chunks of a block would fill) */
-        d->persist = 0;
-        if (const char *e = getenv("QLDPC_EDGE_PERSIST")) d->persist = (atoi(e) && cfg->max_frames <= QE_PERSIST_MAX_FRAMES) ? 1 : 0;
-        if ((rc = dev_alloc(d, &d->e_ctl, QE_CTL_WORDS))) return rc;      /* claim / rank / barrier / fault words of qe_xcd */
-        return QLDPC_OK;
-    }
+    return d->engine == QLDPC_ENGINE_EDGES ? edge_create(d, code) : frames_create(d, code);
+}
+
+/* the FRAMES engine's share of create_impl: the lists of its schedule, the message and per-frame arrays [G][..][FG], early exit and compaction */
+static int frames_create(qldpc_decoder *d, const qldpc_code *code)
+{
+    const qldpc_decoder_cfg *cfg = &d->cfg;
+    const int V = d->V;
+    int rc;
     bool chain_asked = false;      /* horizontal layered: the one-launch sweep was asked for */
     if (cfg->schedule == QLDPC_SCHED_FLOODING) {
         if ((rc = make_buckets(d, code->cn_ptr, nullptr, d->M, CN_CAPS, 4, d->cn_buckets))) return rc;
@@ -488,7 +426,7 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
                 d->ira_K = code->ira_K;
                 /* QLDPC_FLOOD_POST_VN=0 keeps the in-between posterior passes on qk_vn_flood, a launch per bucket (A/B measurements, tests) */
                 d->fp_vn = 1;
-                if (const char *e = getenv("QLDPC_FLOOD_POST_VN")) d->fp_vn = atoi(e) != 0;
+                env_flag("QLDPC_FLOOD_POST_VN", &d->fp_vn);
                 if ((rc = make_buckets(d, code->vn_ptr, nullptr, d->ira_K, VN_CAPS, 2, d->fp_vn_buckets))) return rc;
                 if (d->fp_vn) {
                     std::vector<int> vt((size_t)d->E);
@@ -534,7 +472,7 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
      * The horizontal-layered schedule compacts only when told to (1), with fp32 messages and a launch per layer; the vertical-layered one never does. */
     d->G0 = d->G;
     d->compact_mode = cfg->compact;
-    if (const char *e = getenv("QLDPC_COMPACT")) d->compact_mode = atoi(e);
+    env_int("QLDPC_COMPACT", &d->compact_mode);
     d->compact_ratio = 0.6f;
     if (const char *e = getenv("QLDPC_COMPACT_RATIO")) { const float x = (float)atof(e); if (x > 0.0f && x <= 1.0f) d->compact_ratio = x; }
     const bool layered_compact = cfg->schedule == QLDPC_SCHED_HLAYERED && d->compact_mode == 1 && !d->msg_i8 && !chain_asked && !d->chain;
@@ -615,6 +553,12 @@ static int ensure_llr(qldpc_decoder *d)
     if (d->d_llr) return QLDPC_OK;
     return dev_alloc(d, &d->d_llr, (size_t)d->G * d->N * d->FG);
 }
+/* the frame-interleaved posteriors [G][N][FG] fetch_post and fetch_weakest read, on first use */
+static int ensure_post(qldpc_decoder *d)
+{
+    if (d->d_post) return QLDPC_OK;
+    return dev_alloc(d, &d->d_post, (size_t)d->G * d->N * d->FG);
+}
 
 extern "C" int qldpc_decoder_set_stream(qldpc_decoder *d, void *s) { if (!d) return QLDPC_EINVAL; d->stream = (hipStream_t)s; return QLDPC_OK; }
 extern "C" size_t qldpc_decoder_device_bytes(const qldpc_decoder *d) { return d ? d->bytes : 0; }
@@ -656,18 +600,6 @@ extern "C" int qldpc_sync(qldpc_decoder *d)
 }
 
 /* ------------------------------------------------------------------ profiling ---------------- */
-
-struct prof_scope {
-    qldpc_decoder *d; int kind; double bytes, moved; hipEvent_t a, b; bool on;
-    prof_scope(qldpc_decoder *d_, int kind_, double bytes_, double moved_ = -1.0) : d(d_), kind(kind_), bytes(bytes_), moved(moved_ < 0.0 ? bytes_ : moved_), a(nullptr), b(nullptr), on(d_->prof_on != 0)
-    {
-        if (on) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, d->stream); }
-    }
-    ~prof_scope()
-    {
-        if (on) { (void)hipEventRecord(b, d->stream); d->prof_pending.push_back({kind, bytes, moved, a, b}); }
-    }
-};
 
 extern "C" int qldpc_profile_enable(qldpc_decoder *d, int on) { if (!d) return QLDPC_EINVAL; d->prof_on = on; return QLDPC_OK; }
 
@@ -711,18 +643,8 @@ extern "C" int qldpc_profile_clear(qldpc_decoder *d)
 
 /* ------------------------------------------------------------------ launch helpers ----------- */
 
-/* algorithmic bytes: only live (non-padding) frames are counted */
-static double msg_b(const qldpc_decoder *d) { return d->msg_i8 ? 1.0 : (d->msg_half ? 2.0 : 4.0); }
-static double llr_b(const qldpc_decoder *d) { return d->msg_i8 ? 1.0 : 4.0; }
-/* frames the next launches work on: all loaded frames, or -- once the early-exit loop has polled -- the lanes of the groups still active */
-static double live_frames(const qldpc_decoder *d) { return (double)(d->live_lanes > 0 && d->live_lanes < d->n_frames ? d->live_lanes : d->n_frames); }
-static double bytes_cn(const qldpc_decoder *d) { return 2.0 * d->E * msg_b(d) * live_frames(d); }
-static double bytes_vn(const qldpc_decoder *d, int mode)
-{
-    if (mode != QK_VN_NORMAL) return ((double)d->E * msg_b(d) + d->N * llr_b(d)) * live_frames(d);      /* FIRST writes the messages only, POST reads them only */
-    return (2.0 * d->E * msg_b(d) + d->N * llr_b(d)) * live_frames(d);
-}
-/* what a variable-node pass has to fetch in the data form in use: with coded LLRs the channel values are N/8 bytes of received-bit
+/* algorithmic bytes beyond bytes_cn / bytes_vn of qldpc_engine_int.h, and what the passes move.
+ * What a variable-node pass has to fetch in the data form in use: with coded LLRs the channel values are N/8 bytes of received-bit
  * ballots per frame (plus a class byte per VN, shared by all frames) instead of an N * llr_b array */
 static double moved_vn(const qldpc_decoder *d, int mode)
 {
@@ -925,7 +847,10 @@ static int compact(qldpc_decoder *d, int active_frames)
     gen_state &n = d->gens[(size_t)k];
     if (n.cap < Gn) {      /* first use (or a larger need than any run before): sized for the largest batch this generation can get */
         (void)hipStreamSynchronize(d->stream);
-        gen_release(n);
+        /* everything a generation past 0 owns (llr / llr8 / post / msg are views into the decoder's side buffers) */
+        dev_release(d, &n.sgn); dev_release(d, &n.hard); dev_release(d, &n.unsat); dev_release(d, &n.done); dev_release(d, &n.ybits); dev_release(d, &n.synd); dev_release(d, &n.ebits);
+        dev_release(d, &n.depth); dev_release(d, &n.iters); dev_release(d, &n.origin); dev_release(d, &n.src); dev_release(d, &n.fmag); dev_release(d, &n.fnch);
+        dev_release(d, &n.gu_last); dev_release(d, &n.gu_best); dev_release(d, &n.gu_since); dev_release(d, &n.gu_gave);
         n.cap = std::max(Gn, std::min(o.cap, (int)(d->compact_ratio * (float)o.cap) + 1));
     }
     const size_t C = (size_t)n.cap;
@@ -947,14 +872,9 @@ static int compact(qldpc_decoder *d, int active_frames)
         const int side = k & 1;
         if (d->lay_alt_cap[side] < n.cap) {      /* sized by the first generation that uses it; grows if a later batch needs more */
             (void)hipStreamSynchronize(d->stream);
-            if (d->d_post_alt[side]) d->bytes -= (size_t)d->lay_alt_cap[side] * ((size_t)d->N + d->E) * FG * sizeof(float);
-            (void)hipFree(d->d_post_alt[side]); (void)hipFree(d->d_msg_alt[side]);
-            d->d_post_alt[side] = nullptr; d->d_msg_alt[side] = nullptr;
+            dev_release(d, &d->d_post_alt[side]); dev_release(d, &d->d_msg_alt[side]);
             d->lay_alt_cap[side] = 0;
-            if ((rc = dev_alloc(d, &d->d_post_alt[side], C * d->N * FG)) || (rc = dev_alloc(d, &d->d_msg_alt[side], C * d->E * FG))) {
-                if (d->d_post_alt[side]) { d->bytes -= C * d->N * FG * sizeof(float); (void)hipFree(d->d_post_alt[side]); d->d_post_alt[side] = nullptr; }
-                return rc;
-            }
+            if ((rc = dev_alloc(d, &d->d_post_alt[side], C * d->N * FG)) || (rc = dev_alloc(d, &d->d_msg_alt[side], C * d->E * FG))) { dev_release(d, &d->d_post_alt[side]); return rc; }
             d->lay_alt_cap[side] = n.cap;
         }
         n.post = d->d_post_alt[side]; n.msg = d->d_msg_alt[side];
@@ -963,8 +883,7 @@ static int compact(qldpc_decoder *d, int active_frames)
         const int side = k & 1;
         if (d->llr_alt_cap[side] < n.cap) {      /* sized by the first generation that uses it (later ones are smaller); grows if a later batch needs more */
             (void)hipStreamSynchronize(d->stream);
-            (void)hipFree(d->d_llr_alt[side]); (void)hipFree(d->d_llr8_alt[side]);
-            d->d_llr_alt[side] = nullptr; d->d_llr8_alt[side] = nullptr;
+            dev_release(d, &d->d_llr_alt[side]); dev_release(d, &d->d_llr8_alt[side]);
             d->llr_alt_cap[side] = n.cap;
         }
         const size_t need = (size_t)d->llr_alt_cap[side] * d->N * (rows8 ? 64 : (size_t)FG);
@@ -1271,8 +1190,8 @@ static int run_v(qldpc_decoder *d)
     return run_end<V>(d);
 }
 
-/* fn(origin, final_mask, n_slots) once per generation, with that generation's view in place: which slots hold a frame's result
- * and where it belongs in the caller's batch (qk_result_frame) */
+/* fn(origin, final_mask, n_slots) launches once per generation, with that generation's view in place: which slots hold a frame's result
+ * and where it belongs in the caller's batch (qk_result_frame).  The launch is checked here */
 template <typename F>
 static int for_each_gen(qldpc_decoder *d, F fn)
 {
@@ -1281,203 +1200,10 @@ static int for_each_gen(qldpc_decoder *d, F fn)
     for (int k = 0; k <= last && !rc; k++) {
         use_gen(d, k);
         const gen_state &n = d->gens[(size_t)k];
-        rc = fn(n.origin, k < last ? (const u64 *)n.done : (const u64 *)nullptr, k == 0 ? d->n_frames : n.G * d->FG);
+        rc = [&]() -> int { fn(n.origin, k < last ? (const u64 *)n.done : (const u64 *)nullptr, k == 0 ? d->n_frames : n.G * d->FG); LAUNCHCHK(); return QLDPC_OK; }();
     }
     use_gen(d, last);
     return rc;
-}
-
-/* ---- edge-parallel engine ----------------------------------------------------------------- */
-
-template <int S>
-static void launch_qe_cn(qldpc_decoder *d, const uint32_t *bits, int slot, int syndrome_only)
-{
-    dim3 grid((unsigned)((d->M + QE_CPB - 1) / QE_CPB), (unsigned)d->n_frames);
-    float *c2v_out = (slot & 1) ? d->e_c2v1 : d->d_b;        /* ping-pong by iteration parity */
-    const auto kernel = d->cfg.rule == QLDPC_RULE_SPA ? qe_cn<S, QK_FAM_SPA> : qe_cn<S, QK_FAM_MS>;
-    hipLaunchKernelGGL(kernel, grid, dim3(QE_THREADS), 0, d->stream, d->d_a, c2v_out, d->d_cn_ptr, d->d_cn_tr, d->d_cn_var, bits,
-                       d->M, d->E, d->eW, d->e_unsat, d->e_stride, slot, d->e_done_at, rule_of(d), syndrome_only, d->has_synd ? d->e_synd : nullptr, (d->M + 31) / 32);
-}
-static int edge_cn(qldpc_decoder *d, const uint32_t *bits, int slot, int syndrome_only)
-{
-    prof_scope ps(d, syndrome_only ? KS_SYND : KS_CN, syndrome_only ? (double)d->E * 4.0 * d->n_frames : bytes_cn(d));
-    switch (d->eS) {
-    case 8: launch_qe_cn<8>(d, bits, slot, syndrome_only); break;
-    case 16: launch_qe_cn<16>(d, bits, slot, syndrome_only); break;
-    case 32: launch_qe_cn<32>(d, bits, slot, syndrome_only); break;
-    default: launch_qe_cn<64>(d, bits, slot, syndrome_only); break;
-    }
-    LAUNCHCHK();
-    return QLDPC_OK;
-}
-/* ite = index of the check pass whose messages are consumed (its parity selects the buffer); sel < 0: per-frame choice */
-template <int MODE>
-static int edge_vn(qldpc_decoder *d, int ite, int check, int force, float *post_out, int sel)
-{
-    prof_scope ps(d, KS_VN, bytes_vn(d, MODE));
-    dim3 grid((unsigned)((d->N + QE_THREADS - 1) / QE_THREADS), (unsigned)d->n_frames);
-    hipLaunchKernelGGL((qe_vn<MODE>), grid, dim3(QE_THREADS), d->e_lds, d->stream, d->d_b, d->e_c2v1, sel, d->cfg.n_ite, d->d_llr, d->d_a, d->e_sgn, d->e_hard, post_out, d->d_vn_ptr,
-                       d->N, d->E, d->eW, d->e_unsat, d->e_stride, ite, d->cfg.syndrome_depth, check, d->e_done_at, force);
-    LAUNCHCHK();
-    return QLDPC_OK;
-}
-
-/* launches of iterations [ite0, ite1) on d->stream (+ the decoder-reset prologue in front of iteration 0) */
-static int edge_emit(qldpc_decoder *d, int ite0, int ite1)
-{
-    int rc;
-    const int n_ite = d->cfg.n_ite, synd = d->cfg.enable_syndrome;
-    if (ite0 == 0) {
-        hipLaunchKernelGGL(qe_init, dim3((unsigned)d->n_frames), dim3(64), 0, d->stream, d->e_unsat, d->e_stride, d->e_done_at, d->n_frames);
-        LAUNCHCHK();
-        if ((rc = edge_vn<QK_VN_FIRST>(d, 0, 0, 0, nullptr, 0))) return rc;
-    }
-    for (int ite = ite0; ite < ite1; ite++) {
-        if ((rc = edge_cn(d, d->e_sgn, ite, 0))) return rc;
-        if (ite == n_ite - 1) rc = edge_vn<QK_VN_POST>(d, ite, synd, 0, nullptr, ite & 1);
-        else rc = edge_vn<QK_VN_NORMAL>(d, ite, synd, 0, nullptr, ite & 1);
-        if (rc) return rc;
-    }
-    if (ite1 == n_ite + 1) return edge_cn(d, d->e_hard, n_ite + 1, 1);   /* epilogue chunk: success flag of the final hard decisions */
-    return QLDPC_OK;
-}
-
-/*
- * The launch-bound inner loop as hipGraphs: one instantiated graph per chunk of `poll_every` iterations
- * (kernel arguments differ per iteration, so each chunk has its own graph), captured once per frame count
- * on a private stream and replayed on the caller's stream.  The host only polls between chunks.
- */
-static int edge_chunk_graph(qldpc_decoder *d, int chunk, int ite0, int ite1, hipGraphExec_t *out)
-{
-    if (d->graph_frames != d->n_frames) {
-        for (auto &g : d->e_graphs) if (g) (void)hipGraphExecDestroy(g);
-        d->e_graphs.clear();
-        d->graph_frames = d->n_frames;
-    }
-    if ((int)d->e_graphs.size() <= chunk) d->e_graphs.resize((size_t)chunk + 1, nullptr);
-    if (!d->e_graphs[(size_t)chunk]) {
-        if (!d->cap_stream) HIPCHK(hipStreamCreateWithFlags(&d->cap_stream, hipStreamNonBlocking));
-        hipStream_t user = d->stream;
-        d->stream = d->cap_stream;
-        hipGraph_t g = nullptr;
-        hipError_t e = hipStreamBeginCapture(d->cap_stream, hipStreamCaptureModeRelaxed);
-        int rc = QLDPC_EHIP;
-        if (e == hipSuccess) {
-            rc = edge_emit(d, ite0, ite1);
-            e = hipStreamEndCapture(d->cap_stream, &g);
-        }
-        d->stream = user;
-        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-        if (e != hipSuccess || !g) { qldpc_set_error("graph capture: %s", hipGetErrorString(e)); return QLDPC_EHIP; }
-        hipGraphExec_t x = nullptr;
-        e = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e != hipSuccess) { qldpc_set_error("graph instantiate: %s", hipGetErrorString(e)); return QLDPC_EHIP; }
-        d->e_graphs[(size_t)chunk] = x;
-    }
-    *out = d->e_graphs[(size_t)chunk];
-    return QLDPC_OK;
-}
-
-template <int S, int FAM>
-static int launch_persist(qldpc_decoder *d)
-{
-    const void *fn = (const void *)&qe_xcd<S, FAM>;
-    const size_t lds = std::max((size_t)(2 * QE_MAX_EDGES + 16 + QE_CPB) * sizeof(float), d->e_lds);
-    if (d->persist_blocks == 0) {
-        int per_cu = 0, cus = 0;
-        if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, QE_THREADS, lds));
-        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d->device));
-        /* workgroups that can be resident on ONE XCD (an eighth of the CUs); the occupancy query is advisory (it can over-report by one
-         * workgroup per CU), so one per CU is given away and at most 4 are counted on */
-        const int reported = per_cu;
-        per_cu = std::min(4, per_cu - 1);
-        d->persist_blocks = per_cu * (cus / 8);
-        if (const char *e = getenv("QLDPC_EDGE_WGS")) d->persist_blocks = atoi(e);      /* workgroups per block (experiments) */
-        if (getenv("QLDPC_DEBUG")) fprintf(stderr, "libqldpc: one-launch edge decode: occupancy query %d workgroups per CU, %d CUs, %d workgroups per block, %zu B LDS\n", reported, cus, d->persist_blocks, lds);
-        if (d->persist_blocks < 1 || cus < 8) { d->persist = 0; return QLDPC_EUNSUPPORTED; }
-    }
-    const int nCN = (d->M + QE_CPB - 1) / QE_CPB, nVN = (d->N + QE_THREADS - 1) / QE_THREADS;
-    int nb = std::max(1, std::min(d->persist_blocks, std::max(nCN, nVN)));
-    qk_rule r = rule_of(d);
-    float *v2c = d->d_a, *c2v0 = d->d_b, *c2v1 = d->e_c2v1;
-    const float *llr = d->d_llr;
-    const int *cn_ptr = d->d_cn_ptr, *cn_tr = d->d_cn_tr, *cn_var = d->d_cn_var, *vn_ptr = d->d_vn_ptr;
-    uint32_t *sgn = d->e_sgn, *hard = d->e_hard;
-    int N = d->N, M = d->M, E = d->E, W = d->eW, F = d->n_frames, n_ite = d->cfg.n_ite, synd_on = d->cfg.enable_syndrome, depth = d->cfg.syndrome_depth, stride = d->e_stride;
-    int Wm = (d->M + 31) / 32;
-    int *unsat = d->e_unsat, *done_at = d->e_done_at, *ctl = d->e_ctl;
-    const uint32_t *synd = d->has_synd ? d->e_synd : nullptr;
-    static const int ctl_init[QE_CTL_WORDS] = {-1, -1, -1, -1, -1, -1, -1, -1};      /* the rest zero */
-    HIPCHK(hipMemcpyAsync(d->e_ctl, ctl_init, sizeof(ctl_init), hipMemcpyHostToDevice, d->stream));
-    /* twice the workgroups the 8 XCDs could use: the surplus (and the whole share of an XCD that got no block) exits at once */
-    const unsigned grid = (unsigned)(8 * nb * 2);
-    hipLaunchKernelGGL((qe_xcd<S, FAM>), dim3(grid), dim3(QE_THREADS), lds, d->stream, v2c, c2v0, c2v1, llr, cn_ptr, cn_tr, cn_var, vn_ptr, sgn, hard,
-                       N, M, E, W, F, nb, n_ite, synd_on, depth, unsat, stride, done_at, r, synd, Wm, ctl);
-    LAUNCHCHK();
-    /* the host needs the verdict now anyway (the launch-per-pass path polls as well): read the control words back; a decode that did
-     * not complete (a workgroup that never became resident: the grid drains on its bounded waits and says so) is repeated with a
-     * launch per pass by the caller, and the one-launch path is switched off for this decoder */
-    int ctl_h[QE_CTL_WORDS];
-    HIPCHK(hipMemcpyAsync(ctl_h, d->e_ctl, sizeof(ctl_h), hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    if (ctl_h[QE_CTL_FAULT] || ctl_h[QE_CTL_NEXT] < F) {
-        fprintf(stderr, "libqldpc: one-launch edge decode did not complete (barrier time-out %d, %d of %d blocks claimed): falling back to a launch per pass\n",
-                ctl_h[QE_CTL_FAULT], ctl_h[QE_CTL_NEXT], F);
-        d->persist = 0;
-        return QLDPC_EUNSUPPORTED;
-    }
-    d->last_iters = ctl_h[QE_CTL_ITERS];
-    return QLDPC_OK;
-}
-
-static int run_edges_persist(qldpc_decoder *d)
-{
-    const bool spa = d->cfg.rule == QLDPC_RULE_SPA;
-    switch (d->eS) {
-    case 8: return spa ? launch_persist<8, QK_FAM_SPA>(d) : launch_persist<8, QK_FAM_MS>(d);
-    case 16: return spa ? launch_persist<16, QK_FAM_SPA>(d) : launch_persist<16, QK_FAM_MS>(d);
-    case 32: return spa ? launch_persist<32, QK_FAM_SPA>(d) : launch_persist<32, QK_FAM_MS>(d);
-    default: return spa ? launch_persist<64, QK_FAM_SPA>(d) : launch_persist<64, QK_FAM_MS>(d);
-    }
-}
-
-static int run_edges(qldpc_decoder *d)
-{
-    int rc;
-    if (d->persist && !d->prof_on && d->n_frames <= QE_PERSIST_MAX_FRAMES) {
-        rc = run_edges_persist(d);
-        if (rc != QLDPC_EUNSUPPORTED) return rc;      /* not co-resident on this device: the launch-per-pass path below */
-    }
-    const int n_ite = d->cfg.n_ite, F = d->n_frames, synd = d->cfg.enable_syndrome;
-    const int P = (synd && d->poll_every > 0) ? d->poll_every : n_ite;
-    const bool graphs = d->use_graphs && !d->prof_on;
-    int ite = 0, pending = -1, flip = 0, chunk = 0;
-    while (ite < n_ite) {
-        const int ite1 = std::min(n_ite, ite + P);
-        if (graphs) {
-            hipGraphExec_t x;
-            if ((rc = edge_chunk_graph(d, chunk, ite, ite1, &x))) return rc;
-            HIPCHK(hipGraphLaunch(x, d->stream));
-        } else if ((rc = edge_emit(d, ite, ite1))) return rc;
-        ite = ite1; chunk++;
-        if (synd && ite < n_ite) {
-            /* look-ahead polling: wait for the snapshot queued one chunk ago, so the GPU always has work queued */
-            if (pending >= 0) {
-                HIPCHK(hipEventSynchronize(d->e_ev[pending]));
-                bool all = true;
-                for (int f = 0; f < F; f++) all = all && d->h_done[(size_t)pending * F + f] >= 0;
-                if (all) break;
-            }
-            HIPCHK(hipMemcpyAsync(d->h_done + (size_t)flip * F, d->e_done_at, sizeof(int) * (size_t)F, hipMemcpyDeviceToHost, d->stream));
-            HIPCHK(hipEventRecord(d->e_ev[flip], d->stream));
-            pending = flip; flip ^= 1;
-        }
-    }
-    d->last_iters = ite;
-    /* success flag: syndrome of the final hard decisions into the last slot */
-    return edge_cn(d, d->e_hard, n_ite + 1, 1);
 }
 
 extern "C" int qldpc_run(qldpc_decoder *d)
@@ -1485,13 +1211,7 @@ extern "C" int qldpc_run(qldpc_decoder *d)
     if (!d) return QLDPC_EINVAL;
     if (!d->loaded) { qldpc_set_error("qldpc_run: nothing loaded"); return QLDPC_ESTATE; }
     HIPCHK(hipSetDevice(d->device));
-    int rc;
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        rc = run_edges(d);
-        if (rc == QLDPC_OK) d->ran = 1;
-        return rc;
-    }
-    rc = with_v(d, [&](auto v) { return run_v<v()>(d); });
+    const int rc = d->engine == QLDPC_ENGINE_EDGES ? edge_run(d) : with_v(d, [&](auto v) { return run_v<v()>(d); });
     if (rc == QLDPC_OK) d->ran = 1;
     return rc;
 }
@@ -1737,37 +1457,53 @@ static int check_frames(qldpc_decoder *d, int n_frames, const char *who)
     return QLDPC_OK;
 }
 
-extern "C" int qldpc_load_llr_dev(qldpc_decoder *d, const float *d_llr, int n_frames)
+/* what every load of a batch opens with: the frame count checked, the device, the view of the batch as loaded, and the state of the batch
+ * before it (target syndromes, erasures, known bits, the coded form) gone.  end_load (qldpc_engine_int.h) closes the call */
+static int begin_load(qldpc_decoder *d, int n_frames, const char *who)
 {
-    if (!d || !d_llr) return QLDPC_EINVAL;
-    int rc = check_frames(d, n_frames, "qldpc_load_llr_dev");
+    int rc = check_frames(d, n_frames, who);
     if (rc) return rc;
     HIPCHK(hipSetDevice(d->device));
     view_reset(d);
     d->n_frames = n_frames;
-    d->has_synd = 0;
-    d->has_erase = 0;
-    d->has_known = 0;
-    d->llr_coded = 0;
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        prof_scope ps(d, KS_LOAD, 2.0 * d->N * 4.0 * n_frames);
-        HIPCHK(hipMemcpyAsync(d->d_llr, d_llr, sizeof(float) * (size_t)n_frames * d->N, hipMemcpyDeviceToDevice, d->stream));
-        d->loaded = 1; d->ran = 0;
-        return QLDPC_OK;
-    }
+    d->has_synd = d->has_erase = d->has_known = d->llr_coded = 0;
+    return QLDPC_OK;
+}
+
+/* the loads that add to a batch (target syndromes, erasures, known bits) take the frame count of the batch in place */
+static int need_loaded(qldpc_decoder *d, int n_frames, const char *who)
+{
+    if (!d->loaded || n_frames != d->n_frames) { qldpc_set_error("%s: load %d frames first (have %d)", who, n_frames, d->loaded ? d->n_frames : 0); return QLDPC_ESTATE; }
+    HIPCHK(hipSetDevice(d->device));
+    view_reset(d);
+    return QLDPC_OK;
+}
+
+/* 8-bit messages: dword-wise passes over the [G][N][64] dwords of the quantised LLRs / posteriors */
+static inline size_t i8_dwords(const qldpc_decoder *d) { return (size_t)d->G * d->N * 64; }
+static inline dim3 i8_grid(const qldpc_decoder *d) { return dim3((unsigned)std::min<size_t>((i8_dwords(d) + 255) / 256, 16384)); }
+static int quantise_llr(qldpc_decoder *d)
+{
+    hipLaunchKernelGGL(qi_quant_llr, i8_grid(d), dim3(256), 0, d->stream, d->d_llr, d->d_llr8, i8_dwords(d), d->quant_scale);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_load_llr_dev(qldpc_decoder *d, const float *d_llr, int n_frames)
+{
+    if (!d || !d_llr) return QLDPC_EINVAL;
+    int rc = begin_load(d, n_frames, "qldpc_load_llr_dev");
+    if (rc) return rc;
+    if (d->engine == QLDPC_ENGINE_EDGES) return edge_load_llr(d, d_llr);
     if ((rc = ensure_llr(d))) return rc;
     {
         prof_scope ps(d, KS_LOAD, 2.0 * d->N * 4.0 * n_frames);
         dim3 grid((unsigned)((d->N + 63) / 64), (unsigned)d->G);
         with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_llr<v()>), grid, dim3(256), 0, d->stream, d_llr, d->d_llr, d->N, n_frames); });
         LAUNCHCHK();
-        if (d->msg_i8) {
-            const size_t n_dwords = (size_t)d->G * d->N * 64;
-            hipLaunchKernelGGL(qi_quant_llr, dim3((unsigned)std::min<size_t>((n_dwords + 255) / 256, 16384)), dim3(256), 0, d->stream, d->d_llr, d->d_llr8, n_dwords, d->quant_scale);
-            LAUNCHCHK();
-        }
+        if (d->msg_i8 && (rc = quantise_llr(d))) return rc;
     }
-    d->loaded = 1; d->ran = 0;
+    end_load(d);
     return QLDPC_OK;
 }
 
@@ -1781,28 +1517,14 @@ extern "C" int qldpc_load_bits_dev(qldpc_decoder *d, const uint32_t *d_bits, con
 extern "C" int qldpc_load_bits_short_dev(qldpc_decoder *d, const uint32_t *d_bits, const float *d_llr_mag, const uint8_t *d_vn_class, const int *d_n_channel, int n_frames)
 {
     if (!d || !d_bits || !d_llr_mag) return QLDPC_EINVAL;
-    int rc = check_frames(d, n_frames, "qldpc_load_bits_dev");
+    int rc = begin_load(d, n_frames, "qldpc_load_bits_dev");
     if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
-    view_reset(d);
-    d->n_frames = n_frames;
-    d->has_synd = 0;
-    d->has_erase = 0;
-    d->has_known = 0;
-    const int W = (d->N + 31) / 32;
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        prof_scope ps(d, KS_LOAD, ((double)W * 4.0 + d->N * 4.0) * n_frames);
-        hipLaunchKernelGGL(qe_load_bits, dim3((unsigned)std::min((d->N + 255) / 256, 256), (unsigned)n_frames), dim3(256), 0, d->stream, d_bits, d_llr_mag, d_vn_class,
-                           d->d_llr, d->N, W, d_n_channel);
-        LAUNCHCHK();
-        d->loaded = 1; d->ran = 0;
-        return QLDPC_OK;
-    }
-    d->llr_coded = 0;
+    if (d->engine == QLDPC_ENGINE_EDGES) return edge_load_bits(d, d_bits, d_llr_mag, d_vn_class, d_n_channel);
+    const int W = words32(d->N);
+    const dim3 grid = grid_4k(d, W);
     if (d->d_ybits) {
         /* flooding, fp32 / binary16 messages: keep the received bits as ballots and rebuild Y in the VN passes (qk_coded_llr) */
         prof_scope ps(d, KS_LOAD, ((double)W * 4.0 + d->N / 8.0) * n_frames);
-        const dim3 grid = grid_4k(d, W);
         with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_syndrome<v()>), grid, dim3(QK_THREADS), 0, d->stream, d_bits, d->d_ybits, d->N, W, n_frames); });
         LAUNCHCHK();
         const int total = d->G * d->FG;
@@ -1811,26 +1533,18 @@ extern "C" int qldpc_load_bits_short_dev(qldpc_decoder *d, const uint32_t *d_bit
         if (d_vn_class) HIPCHK(hipMemcpyAsync(d->d_vcls, d_vn_class, (size_t)d->N, hipMemcpyDeviceToDevice, d->stream));
         else HIPCHK(hipMemsetAsync(d->d_vcls, 0, (size_t)d->N, d->stream));
         d->llr_coded = 1;
-        d->loaded = 1; d->ran = 0;
-        return QLDPC_OK;
-    }
-    if (d->msg_i8) {
+    } else if (d->msg_i8) {
         /* 8-bit variant: straight into the quantised array, no fp32 LLRs in between */
         prof_scope ps(d, KS_LOAD, ((double)W * 4.0 + d->N) * n_frames);
-        const dim3 grid = grid_4k(d, W);
         hipLaunchKernelGGL(qi_load_bits, grid, dim3(QK_THREADS), 0, d->stream, d_bits, d_llr_mag, d_vn_class, d->d_llr8, d->N, W, n_frames, d_n_channel, d->quant_scale);
         LAUNCHCHK();
-        d->loaded = 1; d->ran = 0;
-        return QLDPC_OK;
-    }
-    if ((rc = ensure_llr(d))) return rc;
-    {
+    } else {
+        if ((rc = ensure_llr(d))) return rc;
         prof_scope ps(d, KS_LOAD, ((double)W * 4.0 + d->N * 4.0) * n_frames);
-        const dim3 grid = grid_4k(d, W);
         with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_bits<v()>), grid, dim3(QK_THREADS), 0, d->stream, d_bits, d_llr_mag, d_vn_class, d->d_llr, d->N, W, n_frames, d_n_channel); });
         LAUNCHCHK();
     }
-    d->loaded = 1; d->ran = 0;
+    end_load(d);
     return QLDPC_OK;
 }
 
@@ -1838,20 +1552,14 @@ extern "C" int qldpc_load_bits_short_dev(qldpc_decoder *d, const uint32_t *d_bit
 extern "C" int qldpc_load_syndrome_dev(qldpc_decoder *d, const uint32_t *d_synd_bits, int n_frames)
 {
     if (!d || !d_synd_bits) return QLDPC_EINVAL;
-    if (!d->loaded || n_frames != d->n_frames) { qldpc_set_error("qldpc_load_syndrome_dev: load %d frames first (have %d)", n_frames, d->loaded ? d->n_frames : 0); return QLDPC_ESTATE; }
-    HIPCHK(hipSetDevice(d->device));
-    view_reset(d);
-    const int Wm = (d->M + 31) / 32;
-    int rc;
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        if (!d->e_synd && (rc = dev_alloc(d, &d->e_synd, (size_t)d->cfg.max_frames * Wm))) return rc;
-        HIPCHK(hipMemcpyAsync(d->e_synd, d_synd_bits, sizeof(uint32_t) * (size_t)n_frames * Wm, hipMemcpyDeviceToDevice, d->stream));
-    } else {
-        if (!d->d_synd && (rc = dev_alloc(d, &d->d_synd, (size_t)d->G * d->M * d->V))) return rc;
-        const dim3 grid = grid_4k(d, Wm);
-        with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_syndrome<v()>), grid, dim3(QK_THREADS), 0, d->stream, d_synd_bits, d->d_synd, d->M, Wm, n_frames); });
-        LAUNCHCHK();
-    }
+    int rc = need_loaded(d, n_frames, "qldpc_load_syndrome_dev");
+    if (rc) return rc;
+    if (d->engine == QLDPC_ENGINE_EDGES) return edge_load_syndrome(d, d_synd_bits);
+    const int Wm = words32(d->M);
+    if (!d->d_synd && (rc = dev_alloc(d, &d->d_synd, (size_t)d->G * d->M * d->V))) return rc;
+    const dim3 grid = grid_4k(d, Wm);
+    with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_syndrome<v()>), grid, dim3(QK_THREADS), 0, d->stream, d_synd_bits, d->d_synd, d->M, Wm, n_frames); });
+    LAUNCHCHK();
     d->has_synd = 1; d->ran = 0;
     return QLDPC_OK;
 }
@@ -1865,17 +1573,10 @@ static int apply_known(qldpc_decoder *d);      /* the known bits of qldpc_load_k
 extern "C" int qldpc_load_erasures_dev(qldpc_decoder *d, const uint32_t *d_erase_bits, int n_frames)
 {
     if (!d || !d_erase_bits) return QLDPC_EINVAL;
-    if (!d->loaded || n_frames != d->n_frames) { qldpc_set_error("qldpc_load_erasures_dev: load %d frames first (have %d)", n_frames, d->loaded ? d->n_frames : 0); return QLDPC_ESTATE; }
-    HIPCHK(hipSetDevice(d->device));
-    view_reset(d);
-    const int W = (d->N + 31) / 32;
-    int rc;
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        hipLaunchKernelGGL(qe_erase, dim3((unsigned)std::min((d->N + 255) / 256, 256), (unsigned)n_frames), dim3(256), 0, d->stream, d_erase_bits, d->d_llr, d->N, W);
-        LAUNCHCHK();
-        d->ran = 0;
-        return d->has_known ? apply_known(d) : (int)QLDPC_OK;      /* known wins over erased */
-    }
+    int rc = need_loaded(d, n_frames, "qldpc_load_erasures_dev");
+    if (rc) return rc;
+    if (d->engine == QLDPC_ENGINE_EDGES) return edge_erase(d, d_erase_bits);
+    const int W = words32(d->N);
     const dim3 grid = grid_4k(d, W);
     if (d->llr_coded) {
         if (!d->d_ebits && (rc = dev_alloc(d, &d->d_ebits, (size_t)d->G * d->N * d->V))) return rc;
@@ -1901,13 +1602,9 @@ extern "C" int qldpc_load_erasures_dev(qldpc_decoder *d, const uint32_t *d_erase
  */
 static int apply_known(qldpc_decoder *d)
 {
-    const int W = (d->N + 31) / 32;
+    if (d->engine == QLDPC_ENGINE_EDGES) return edge_known(d);
+    const int W = words32(d->N);
     const uint32_t *kn = d->d_known, *val = d->d_known + (size_t)d->cfg.max_frames * W;
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        hipLaunchKernelGGL(qe_known, dim3((unsigned)std::min((d->N + 255) / 256, 256), (unsigned)d->n_frames), dim3(256), 0, d->stream, kn, val, d->d_llr, d->N, W);
-        LAUNCHCHK();
-        return QLDPC_OK;
-    }
     const dim3 grid = grid_4k(d, W);
     if (d->msg_i8) {
         const int q = (int)lrintf(std::min(127.0f, QLDPC_CONFIRMED_BIT_LLR * d->quant_scale));      /* qi_quant1 of the pin */
@@ -1922,25 +1619,19 @@ static int apply_known(qldpc_decoder *d)
 extern "C" int qldpc_load_known_dev(qldpc_decoder *d, const uint32_t *d_known_bits, const uint32_t *d_value_bits, int n_frames)
 {
     if (!d || !d_known_bits || !d_value_bits) return QLDPC_EINVAL;
-    if (!d->loaded || n_frames != d->n_frames) { qldpc_set_error("qldpc_load_known_dev: load %d frames first (have %d)", n_frames, d->loaded ? d->n_frames : 0); return QLDPC_ESTATE; }
-    HIPCHK(hipSetDevice(d->device));
-    view_reset(d);
-    const int W = (d->N + 31) / 32;
-    int rc;
+    int rc = need_loaded(d, n_frames, "qldpc_load_known_dev");
+    if (rc) return rc;
+    const int W = words32(d->N);
     if (!d->d_known && (rc = dev_alloc(d, &d->d_known, (size_t)d->cfg.max_frames * W * 2))) return rc;
     HIPCHK(hipMemcpyAsync(d->d_known, d_known_bits, sizeof(uint32_t) * (size_t)n_frames * W, hipMemcpyDeviceToDevice, d->stream));
     HIPCHK(hipMemcpyAsync(d->d_known + (size_t)d->cfg.max_frames * W, d_value_bits, sizeof(uint32_t) * (size_t)n_frames * W, hipMemcpyDeviceToDevice, d->stream));
-    if (d->engine != QLDPC_ENGINE_EDGES && d->llr_coded) {
+    if (d->llr_coded) {      /* the FRAMES engine's coded form (the edge engine has none) */
         if ((rc = ensure_llr(d))) return rc;
         const qk_coded_llr coded = coded_llr_of(d);
         const dim3 grid((unsigned)std::max(1, std::min((d->N + QK_WAVES - 1) / QK_WAVES, 4096)), (unsigned)d->G);
         with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_decode_llr<v()>), grid, dim3(QK_THREADS), 0, d->stream, coded, d->d_llr, d->N); });
         LAUNCHCHK();
-        if (d->msg_i8) {
-            const size_t n_dwords = (size_t)d->G * d->N * 64;
-            hipLaunchKernelGGL(qi_quant_llr, dim3((unsigned)std::min<size_t>((n_dwords + 255) / 256, 16384)), dim3(256), 0, d->stream, d->d_llr, d->d_llr8, n_dwords, d->quant_scale);
-            LAUNCHCHK();
-        }
+        if (d->msg_i8 && (rc = quantise_llr(d))) return rc;
         d->llr_coded = 0; d->has_erase = 0;      /* the erasures are in the array now */
     }
     if ((rc = apply_known(d))) return rc;
@@ -1955,9 +1646,7 @@ extern "C" int qldpc_decoder_reserve(qldpc_decoder *d)
     if (!d) return QLDPC_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     view_reset(d);
-    int rc;
-    if (d->engine != QLDPC_ENGINE_EDGES && d->d_ybits && !d->d_ebits && (rc = dev_alloc(d, &d->d_ebits, (size_t)d->G0 * d->N * d->V))) return rc;
-    return QLDPC_OK;
+    return d->d_ybits && !d->d_ebits ? dev_alloc(d, &d->d_ebits, (size_t)d->G0 * d->N * d->V) : (int)QLDPC_OK;
 }
 
 /* s = H x on the device for packed words (Alice's side of the syndrome form; also a codeword test) */
@@ -1965,7 +1654,7 @@ extern "C" int qldpc_syndrome_dev(qldpc_decoder *d, const uint32_t *d_bits, uint
 {
     if (!d || !d_bits || !d_synd_bits || n_frames <= 0) return QLDPC_EINVAL;
     HIPCHK(hipSetDevice(d->device));
-    const int Wn = (d->N + 31) / 32, Wm = (d->M + 31) / 32;
+    const int Wn = words32(d->N), Wm = words32(d->M);
     hipLaunchKernelGGL(qk_syndrome_of_bits, dim3((unsigned)((Wm + 255) / 256), (unsigned)n_frames), dim3(256), 0, d->stream, d_bits, d->d_cn_ptr, d->d_cn_var, d_synd_bits,
                        d->M, Wn, Wm);
     LAUNCHCHK();
@@ -1974,9 +1663,11 @@ extern "C" int qldpc_syndrome_dev(qldpc_decoder *d, const uint32_t *d_bits, uint
 
 /* ------------------------------------------------------------------ fetch -------------------- */
 
+/* what every fetch opens with: a completed run, the device */
 static int need_ran(qldpc_decoder *d, const char *who)
 {
     if (!d->ran) { qldpc_set_error("%s: no completed qldpc_run", who); return QLDPC_ESTATE; }
+    HIPCHK(hipSetDevice(d->device));
     return QLDPC_OK;
 }
 
@@ -1985,18 +1676,12 @@ extern "C" int qldpc_fetch_packed_dev(qldpc_decoder *d, uint32_t *d_out)
     if (!d || !d_out) return QLDPC_EINVAL;
     int rc = need_ran(d, "qldpc_fetch_packed_dev");
     if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
-    const int W = (d->N + 31) / 32;
+    const int W = words32(d->N);
     prof_scope ps(d, KS_FETCH, (double)W * 4.0 * d->n_frames);
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        HIPCHK(hipMemcpyAsync(d_out, d->e_hard, sizeof(uint32_t) * (size_t)d->n_frames * W, hipMemcpyDeviceToDevice, d->stream));
-        return QLDPC_OK;
-    }
-    return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) -> int {
+    if (d->engine == QLDPC_ENGINE_EDGES) return edge_fetch_packed(d, d_out);
+    return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) {
         const dim3 grid = grid_4k(d, W);
         with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_fetch_packed<v()>), grid, dim3(QK_THREADS), 0, d->stream, d->d_hard, d_out, d->N, W, n_slots, origin, fin); });
-        LAUNCHCHK();
-        return (int)QLDPC_OK;
     });
 }
 
@@ -2005,19 +1690,11 @@ extern "C" int qldpc_fetch_info_dev(qldpc_decoder *d, int *d_V_K)
     if (!d || !d_V_K) return QLDPC_EINVAL;
     int rc = need_ran(d, "qldpc_fetch_info_dev");
     if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
     prof_scope ps(d, KS_FETCH, (double)d->K * 4.0 * d->n_frames);
-    dim3 grid((unsigned)std::max(1, std::min((d->K + 255) / 256, 64)), (unsigned)d->n_frames);
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        hipLaunchKernelGGL(qe_fetch_info, grid, dim3(256), 0, d->stream, d->e_hard, d->d_info_pos, d_V_K, d->K, d->eW);
-        LAUNCHCHK();
-        return QLDPC_OK;
-    }
-    return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) -> int {
+    if (d->engine == QLDPC_ENGINE_EDGES) return edge_fetch_info(d, d_V_K);
+    return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) {
         dim3 gk((unsigned)std::max(1, std::min((d->K + 255) / 256, 64)), (unsigned)n_slots);
         with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_fetch_info<v()>), gk, dim3(256), 0, d->stream, d->d_hard, d->d_info_pos, d_V_K, d->N, d->K, n_slots, origin, fin); });
-        LAUNCHCHK();
-        return (int)QLDPC_OK;
     });
 }
 
@@ -2026,18 +1703,10 @@ extern "C" int qldpc_fetch_status_dev(qldpc_decoder *d, int *d_iters, int *d_ok)
     if (!d) return QLDPC_EINVAL;
     int rc = need_ran(d, "qldpc_fetch_status_dev");
     if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
-    dim3 grid((unsigned)((d->n_frames + 255) / 256));
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        hipLaunchKernelGGL(qe_status_out, grid, dim3(256), 0, d->stream, d->e_unsat, d->e_stride, d->cfg.n_ite + 1, d->e_done_at, d->cfg.n_ite, d_iters, d_ok, d->n_frames);
-        LAUNCHCHK();
-        return QLDPC_OK;
-    }
-    return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) -> int {
+    if (d->engine == QLDPC_ENGINE_EDGES) return edge_fetch_status(d, d_iters, d_ok);
+    return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) {
         dim3 gs((unsigned)((n_slots + 255) / 256));
         with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_status_out<v()>), gs, dim3(256), 0, d->stream, d->d_unsat, d->d_iters, d_iters, d_ok, n_slots, origin, fin); });
-        LAUNCHCHK();
-        return (int)QLDPC_OK;
     });
 }
 
@@ -2048,12 +1717,9 @@ extern "C" int qldpc_fetch_giveup_dev(qldpc_decoder *d, int *d_gave, int *d_last
     if (d->gu.patience <= 0) { qldpc_set_error("qldpc_fetch_giveup_dev: the decoder counts no syndrome weights: create it with giveup_patience >= 1"); return QLDPC_EUNSUPPORTED; }
     int rc = need_ran(d, "qldpc_fetch_giveup_dev");
     if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
-    return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) -> int {
+    return for_each_gen(d, [&](const int *origin, const u64 *fin, int n_slots) {
         dim3 gs((unsigned)((n_slots + 255) / 256));
         with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_giveup_out<v()>), gs, dim3(256), 0, d->stream, d->gu, d_gave, d_last_weight, d_best_weight, n_slots, origin, fin); });
-        LAUNCHCHK();
-        return (int)QLDPC_OK;
     });
 }
 
@@ -2080,22 +1746,19 @@ static int post_rows(qldpc_decoder *d, const char *who, const float **rows)
                         "create the decoder with compact = 2 (or freeze_messages = 1) to read posteriors", who, d->compactions);
         return QLDPC_EUNSUPPORTED;
     }
-    const float *src;
     if (d->cfg.schedule == QLDPC_SCHED_FLOODING) {
-        if (!d->d_post) { if ((rc = dev_alloc(d, &d->d_post, (size_t)d->G * d->N * d->FG))) return rc; }
+        if ((rc = ensure_post(d))) return rc;
         if (d->fpost) { if ((rc = vn_pass_fpost(d, d->d_post, false)) || (rc = close_fpost(d, d->d_post))) return rc; }
         else if ((rc = with_v(d, [&](auto v) { return vn_pass<v(), QK_VN_POST>(d, d->d_post); }))) return rc;
-        src = d->d_post;
+        *rows = d->d_post;
     } else if (d->msg_i8) {
-        if (!d->d_post) { if ((rc = dev_alloc(d, &d->d_post, (size_t)d->G * d->N * d->FG))) return rc; }
-        const size_t n_dwords = (size_t)d->G * d->N * 64;
-        hipLaunchKernelGGL(qi_post_to_f32, dim3((unsigned)std::min<size_t>((n_dwords + 255) / 256, 16384)), dim3(256), 0, d->stream, (const uint32_t *)d->d_a, d->d_post, n_dwords);
+        if ((rc = ensure_post(d))) return rc;
+        hipLaunchKernelGGL(qi_post_to_f32, i8_grid(d), dim3(256), 0, d->stream, (const uint32_t *)d->d_a, d->d_post, i8_dwords(d));
         LAUNCHCHK();
-        src = d->d_post;
+        *rows = d->d_post;
     } else {
-        src = d->d_a;
+        *rows = d->d_a;
     }
-    *rows = src;
     return QLDPC_OK;
 }
 
@@ -2104,11 +1767,7 @@ extern "C" int qldpc_fetch_post_dev(qldpc_decoder *d, float *d_post_out)
     if (!d || !d_post_out) return QLDPC_EINVAL;
     int rc = need_ran(d, "qldpc_fetch_post_dev");
     if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
-    if (d->engine == QLDPC_ENGINE_EDGES) {
-        /* posterior of the last executed check pass, written frame-major directly (exact in fixed-iteration mode) */
-        return edge_vn<QK_VN_POST>(d, 0, 0, 1, d_post_out, -1);
-    }
+    if (d->engine == QLDPC_ENGINE_EDGES) return edge_fetch_post(d, d_post_out);
     const float *src;
     if ((rc = post_rows(d, "qldpc_fetch_post_dev", &src))) return rc;
     dim3 grid((unsigned)((d->N + 63) / 64), (unsigned)d->G);
@@ -2126,14 +1785,13 @@ extern "C" int qldpc_fetch_weakest_dev(qldpc_decoder *d, const uint32_t *d_cand_
     if (!d || !d_weak_bits || n_weak < 0) return QLDPC_EINVAL;
     int rc = need_ran(d, "qldpc_fetch_weakest_dev");
     if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
     if (d->engine == QLDPC_ENGINE_EDGES) {
         qldpc_set_error("qldpc_fetch_weakest_dev: not built for the edge-parallel engine (create the decoder with engine = FRAMES)");
         return QLDPC_EUNSUPPORTED;
     }
     const float *src;
     if ((rc = post_rows(d, "qldpc_fetch_weakest_dev", &src))) return rc;
-    const int W = (d->N + 31) / 32;
+    const int W = words32(d->N);
     prof_scope ps(d, KS_FETCH, ((double)d->N * 4.0 * (WK_DIGITS + 1) + (double)W * 4.0) * d->n_frames);
     HIPCHK(hipMemsetAsync(d_weak_bits, 0, sizeof(uint32_t) * (size_t)d->n_frames * W, d->stream));
     if (n_weak == 0) return QLDPC_OK;

@@ -1,6 +1,7 @@
 /*
- * qldpc_engine_int.h -- internals shared by the translation units of the decoder (not part of the C ABI): the decoder object,
- * the per-generation state of the early-exit run, and the kernel-launch dispatchers.  The dispatchers instantiate every
+ * qldpc_engine_int.h -- internals shared by the translation units of the decoder (not part of the C ABI): the decoder object with its
+ * allocation ledger, the per-generation state of the early-exit run, the state and the entry points of the edge-parallel engine
+ * (qldpc_engine_edge.hip), and the kernel-launch dispatchers.  The dispatchers instantiate every
  * (frames per lane, degree cap, rule family, message type) variant of the hot kernels; they are compiled once per frames-per-lane
  * value (qldpc_launch.hip with -DQL_V=1|2|4) so that the build runs in parallel.
  */
@@ -10,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <vector>
 
 #include "qldpc_hip.h"
@@ -49,6 +51,27 @@ struct gen_state {
     float *post, *msg;                   /* layered schedule: posteriors and messages / check state of this generation (flooding: NULL past generation 0, its arrays are re-used in place) */
 };
 #define QLDPC_MAX_GENS 6
+
+/* one device allocation of a decoder (dev_alloc below).  Hidden: the std::vector instances over it stay out of the library's dynamic symbols */
+struct __attribute__((visibility("hidden"))) dev_block { void *p; size_t bytes; };
+
+/* What the edge-parallel engine (one block at a time, lanes over edges: qldpc_engine_edge.hip) keeps beside the decoder's shared fields.  It reads the
+ * graph arrays and d_llr [F][N], d_a = v2c / d_b = c2v [F][E] (the frames engine lays the same three names out as [G][..][FG]) */
+struct edge_state {
+    int eW, eS, e_stride;
+    size_t e_lds;
+    uint32_t *e_sgn, *e_hard;
+    float *e_c2v1;                   /* odd-iteration chk_to_var buffer (d_b is the even one) */
+    int *e_unsat, *e_done_at;
+    uint32_t *e_synd;                /* packed target syndromes [F][Wm], NULL until used */
+    int *h_done;
+    hipEvent_t e_ev[2];
+    int use_graphs, graph_frames;
+    int persist, persist_blocks;     /* one cooperative launch per decode (qe_persist): enabled / co-resident workgroups (0 = not probed yet) */
+    int *e_ctl;                      /* control words of the one-launch decode (qe_xcd): claim / rank / barrier / fault words and its iteration count */
+    hipStream_t cap_stream;
+    std::vector<hipGraphExec_t> e_graphs;   /* one per chunk of poll_every iterations */
+};
 
 struct qldpc_decoder {
     qldpc_decoder_cfg cfg;
@@ -109,13 +132,13 @@ struct qldpc_decoder {
     int llr_alt_cap[2]; float *d_llr_alt[2]; uint32_t *d_llr8_alt[2];   /* side buffers for compacted LLR rows (generations ping-pong between them; capacity in groups) */
     int lay_alt_cap[2]; float *d_post_alt[2], *d_msg_alt[2];            /* layered: side buffers of the posteriors and messages of generations >= 1 (ping-pong by generation parity: the
                                                                          * layer kernels update in place, so a generation cannot be written over the one it is read from) */
+    std::vector<dev_block> ledger;   /* every live device allocation; bytes = their sum (dev_alloc / dev_release) */
     size_t bytes;
     int n_frames;                    /* loaded */
     int loaded, ran;
     int last_iters;
     int poll_every;
     u64 *d_synd;                     /* [G][M][V] target-syndrome ballots (syndrome form), NULL until used */
-    uint32_t *e_synd;                /* edge engine: packed target syndromes [F][Wm] */
     int has_synd;
     float *h_in; int *h_out;         /* device staging of qldpc_decode_siho's host vectors */
     int msg_half;                    /* 1: v2c / c2v stored as binary16 (flooding, frames engine) */
@@ -129,24 +152,43 @@ struct qldpc_decoder {
     uint32_t *d_llr8;                /* [G][N][256] quantised channel LLRs, four frames of a lane per dword */
     float quant_scale;
     int freeze;                      /* 1: lane-masked stores keep converged frames' messages bit-frozen (exact posteriors, slower) */
-    /* edge-parallel engine (one block at a time): llr [F][N], d_a = v2c / d_b = c2v [F][E] */
-    int engine, eW, eS, e_stride;
-    size_t e_lds;
-    uint32_t *e_sgn, *e_hard;
-    float *e_c2v1;                   /* odd-iteration chk_to_var buffer (d_b is the even one) */
-    int *e_unsat, *e_done_at;
-    int *h_done;
-    hipEvent_t e_ev[2];
-    int use_graphs, graph_frames;
-    int persist, persist_blocks;     /* one cooperative launch per decode (qe_persist): enabled / co-resident workgroups (0 = not probed yet) */
-    int *e_ctl;                      /* control words of the one-launch decode (qe_xcd): claim / rank / barrier / fault words and its iteration count */
-    hipStream_t cap_stream;
-    std::vector<hipGraphExec_t> e_graphs;   /* one per chunk of poll_every iterations */
+    int engine;
+    edge_state edge;
     /* profiling */
     int prof_on;
     std::vector<prof_rec> prof_pending;
     qldpc_kernel_stat stats[KS_COUNT];
 };
+
+/*
+ * The decoder's device memory: dev_alloc enters every allocation into the ledger, dev_release takes one out again, qldpc_decoder_free releases
+ * what the ledger still holds.  A pointer the ledger does not hold is a second name of one it does (d_hard with 8-bit messages): only cleared.
+ */
+template <typename T> static int dev_alloc(qldpc_decoder *d, T **p, size_t n)
+{
+    *p = nullptr;
+    if (n == 0) n = 1;
+    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
+    if (e != hipSuccess) { qldpc_set_error("hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e)); return QLDPC_ENOMEM; }
+    d->ledger.push_back(dev_block{(void *)*p, n * sizeof(T)});
+    d->bytes += n * sizeof(T);
+    return QLDPC_OK;
+}
+template <typename T> static void dev_release(qldpc_decoder *d, T **p)
+{
+    for (auto it = d->ledger.begin(); *p && it != d->ledger.end(); ++it)
+        if (it->p == (void *)*p) { (void)hipFree(it->p); d->bytes -= it->bytes; d->ledger.erase(it); break; }
+    *p = nullptr;
+}
+
+static inline int words32(int n) { return (n + 31) / 32; }
+
+/* a batch is in place (qldpc_load_llr_dev, qldpc_load_bits_*; begin_load in qldpc_engine.hip opens the call) */
+static inline void end_load(qldpc_decoder *d) { d->loaded = 1; d->ran = 0; }
+
+/* the plain environment overrides of a decoder: *y = the variable's value where it is set, as it stands or as a flag */
+static inline void env_int(const char *name, int *y) { if (const char *e = getenv(name)) *y = atoi(e); }
+static inline void env_flag(const char *name, int *y) { if (const char *e = getenv(name)) *y = atoi(e) ? 1 : 0; }
 
 static inline int grid_x(int n_items, int per_wave)
 {
@@ -186,6 +228,53 @@ static inline int want_ballots(const qldpc_decoder *d, int mode)
     if (mode == QK_VN_POST) return 1 | (d->post_closes_run ? 2 : 0);      /* bit 1: skip groups that converged as a whole (their ballots are final) */
     return d->cfg.enable_syndrome ? 1 : 0;
 }
+
+/* one profile record around the launches of a scope (qldpc_profile_read folds them) */
+struct prof_scope {
+    qldpc_decoder *d; int kind; double bytes, moved; hipEvent_t a, b; bool on;
+    prof_scope(qldpc_decoder *d_, int kind_, double bytes_, double moved_ = -1.0) : d(d_), kind(kind_), bytes(bytes_), moved(moved_ < 0.0 ? bytes_ : moved_), a(nullptr), b(nullptr), on(d_->prof_on != 0)
+    {
+        if (on) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, d->stream); }
+    }
+    ~prof_scope()
+    {
+        if (on) { (void)hipEventRecord(b, d->stream); d->prof_pending.push_back({kind, bytes, moved, a, b}); }
+    }
+};
+
+/* algorithmic bytes: only live (non-padding) frames are counted */
+static inline double msg_b(const qldpc_decoder *d) { return d->msg_i8 ? 1.0 : (d->msg_half ? 2.0 : 4.0); }
+static inline double llr_b(const qldpc_decoder *d) { return d->msg_i8 ? 1.0 : 4.0; }
+/* frames the next launches work on: all loaded frames, or -- once the early-exit loop has polled -- the lanes of the groups still active */
+static inline double live_frames(const qldpc_decoder *d) { return (double)(d->live_lanes > 0 && d->live_lanes < d->n_frames ? d->live_lanes : d->n_frames); }
+static inline double bytes_cn(const qldpc_decoder *d) { return 2.0 * d->E * msg_b(d) * live_frames(d); }
+static inline double bytes_vn(const qldpc_decoder *d, int mode)
+{
+    if (mode != QK_VN_NORMAL) return ((double)d->E * msg_b(d) + d->N * llr_b(d)) * live_frames(d);      /* FIRST writes the messages only, POST reads them only */
+    return (2.0 * d->E * msg_b(d) + d->N * llr_b(d)) * live_frames(d);
+}
+
+/*
+ * The edge-parallel engine (qldpc_engine_edge.hip): its half of the entry points of the C ABI.  Each entry point of qldpc_engine.hip checks its
+ * arguments and the call sequence, then hands a decoder with engine == QLDPC_ENGINE_EDGES over.  edge_create allocates the engine's arrays,
+ * edge_destroy releases what is not device memory (events, capture stream, graph execs, the pinned h_done); the loads take the packed rows of
+ * d->n_frames frames; edge_erase and edge_known rewrite rows of d_llr in place.  Hidden: calls between two units of one library, no dynamic symbols.
+ */
+#pragma GCC visibility push(hidden)
+bool edge_supports(const qldpc_decoder_cfg *cfg, const qldpc_code *code);      /* flooding, MS / OMS / NMS / SPA, degrees its kernels hold */
+int edge_create(qldpc_decoder *d, const qldpc_code *code);
+void edge_destroy(qldpc_decoder *d);
+int edge_load_llr(qldpc_decoder *d, const float *d_llr);
+int edge_load_bits(qldpc_decoder *d, const uint32_t *d_bits, const float *d_llr_mag, const uint8_t *d_vn_class, const int *d_n_channel);
+int edge_load_syndrome(qldpc_decoder *d, const uint32_t *d_synd_bits);
+int edge_erase(qldpc_decoder *d, const uint32_t *d_erase_bits);
+int edge_known(qldpc_decoder *d);
+int edge_run(qldpc_decoder *d);
+int edge_fetch_packed(qldpc_decoder *d, uint32_t *d_out);
+int edge_fetch_info(qldpc_decoder *d, int *d_V_K);
+int edge_fetch_status(qldpc_decoder *d, int *d_iters, int *d_ok);
+int edge_fetch_post(qldpc_decoder *d, float *d_post_out);
+#pragma GCC visibility pop
 
 /*
  * A gang of horizontal-layered decoders (qldpc.h "decoder gangs").  steps[s] = the kernel classes of colour step s, each with the members'
