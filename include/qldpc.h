@@ -1327,6 +1327,111 @@ int    qldpc_mc_blind_next_host(int max_rounds, int batch, const uint64_t *pool,
    for n_channel < 1, n_disclosed_parity < 0, frames == 0 or qber outside (0, 0.5) */
 int    qldpc_mc_blind_efficiency_host(int n_channel, int n_disclosed_parity, uint64_t frames, uint64_t disclosed, double qber, double *f);
 
+/*
+ * Guessing rounds: a third remedy for a failed decode, and the only one that discloses nothing.  Bob pins the g least reliable VNs of the failed
+ * frame to each of the T = 2^g possible values himself, decodes the T trial frames side by side and keeps a trial whose syndrome comes out zero
+ * ("BP with bit guessing", a Chase-style list step).  The rule is stated once in csrc/qldpc_guess_core.h, which the kernels and the host mirrors share:
+ *
+ *   guess set  the row qldpc_fetch_weakest_dev(cand, take, d = g) gives for the frame, a packed set of at most g VNs, ceil(N/32) words MSB-first;
+ *              `hard` is the frame's packed hard-decision row (qldpc_fetch_packed_dev) of the same run
+ *   trial t    0 <= t < T pins the VN of rank j to hard[v] ^ ((t >> j) & 1); the rank counts the set bits of the guess row in ascending VN order, so
+ *              only the set matters; ranks >= popcount(row) do not exist and the bits of t above them are ignored; trial 0 pins the frame's own decisions
+ *   winner     the lowest t whose decode ends with ok = 1, or -1; n_ok = the number of such trials; the frame is `ambiguous` when some ok trial's
+ *              hard row differs from the winner's in any of the N valid bits: the only sign of a risky rescue that Bob can see
+ *
+ * qldpc_guess_expand_dev: d_weak, d_hard [n_src][ceil(N/32)] -> the known and value rows of the n_src T trial slots, slot s T + t, as
+ *   qldpc_load_known_dev reads them: known row = the guess row, value row = the pinned values on the set bits and 0 elsewhere.
+ * qldpc_guess_pick_dev: d_ok [n_src T] and d_trial_hard [n_src T][ceil(N/32)] of the trials' decode (qldpc_fetch_status_dev, qldpc_fetch_packed_dev)
+ *   -> d_winner, d_n_ok, d_ambiguous [n_src] and the winner's row in d_out_hard [n_src][ceil(N/32)]; the row of a source without a winner is not
+ *   touched.  d_out_hard must not overlap d_trial_hard.
+ * Both take no decoder: device pointers of the current device and a stream (NULL = the default stream), and return once the kernel is queued.
+ * QLDPC_EINVAL for a missing pointer; QLDPC_ESIZE for g outside 0 .. QLDPC_GUESS_MAX_BITS, N < 1, n_src < 0 or n_src T above 2^24.  With g = 0
+ * there is one trial per source and it pins nothing; n_src = 0 queues nothing.  The host mirrors need no device and work on ONE trial and ONE source:
+ * known_out, value_out [ceil(N/32)]; ok [T], trial_hard [T][ceil(N/32)] (and QLDPC_ESIZE for a trial outside 0 .. T - 1).
+ */
+#define QLDPC_GUESS_MAX_BITS 10
+int    qldpc_guess_expand_dev(int N, int g, int n_src, const uint32_t *d_weak, const uint32_t *d_hard, uint32_t *d_known_out, uint32_t *d_value_out,
+                              void *hip_stream);
+int    qldpc_guess_pick_dev(int N, int g, int n_src, const int *d_ok, const uint32_t *d_trial_hard, int *d_winner, int *d_n_ok, int *d_ambiguous,
+                            uint32_t *d_out_hard, void *hip_stream);
+int    qldpc_guess_trial_host(int N, int g, int t, const uint32_t *weak, const uint32_t *hard, uint32_t *known_out, uint32_t *value_out);
+int    qldpc_guess_pick_host(int N, int g, const int *ok, const uint32_t *trial_hard, int *winner, int *n_ok, int *ambiguous);
+
+/*
+ * Guessing rounds inside the Monte-Carlo loop: what they buy at a code, a rule, a QBER and a puncture set -- the FER that remains and the decodes it
+ * costs -- at no leak.  The BSC at `qber`, the loop's classes and the fixed set of qldpc_mc_set_puncture; per frame i:
+ *
+ *   round 0    the decode qldpc_mc_run does; a frame with ok = 1 closes in row 0
+ *   guess set  a failed frame takes its min(g, channel VNs) weakest positions among the QLDPC_VN_CHANNEL VNs (the select of qldpc_fetch_weakest_dev
+ *              over the posteriors of that decode)
+ *   trials     its T = 2^g trials are the same channel word, generated again from the index, each loaded with the trial's known and value rows
+ *              (qldpc_guess_expand_dev, qldpc_load_known_dev) and decoded from scratch
+ *   rescued    (row 1) iff a trial ends with a zero syndrome: the counters of row 1 are those of qldpc_mc_result over the WINNER's decode against
+ *              Alice's codeword, so a winner that is wrong counts as frame_errors and undetected
+ *   open       (row 2) otherwise, the counters over its FIRST decode
+ *
+ * Everything about a frame is a pure function of (seed, i, qber, g, decoder configuration, classes, puncture set): nothing depends on the batch, on
+ * the neighbours in a launch or on how a run is split into calls.
+ *
+ *   pool       ONE pool of {frame index, guess row, hard row, the verdict of the first decode} entries; the failed frames of a fresh launch are
+ *              appended in ascending slot order (the scan of the blind rounds).  A trial launch takes the LAST S = floor(batch / T) entries and
+ *              runs S T trial frames
+ *   schedule   qldpc_mc_guess_next_host, a pure function of the counts: a trial launch of S sources while pool >= S; else a fresh launch of
+ *              min(batch, input_left) frames; else the flush, all remaining sources.  The pool stays below S + batch (csrc/qldpc_mc_core.h has
+ *              the argument)
+ *   input      ends at max_frames, and at the first launch boundary at which the errors tallied so far reach max_frame_errors (0 = never): the
+ *              frame_errors of rows 0 and 1 (closed or rescued wrong) plus the frames of row 2 (open).  Failed first decodes that are still pooled
+ *              do not count until they are resolved.  The pool is FLUSHED, never dropped
+ *   rows       three qldpc_mc_blind_round_stat rows with disclosed = 0 (nothing is disclosed): closed at once, rescued, open
+ *
+ * Every launch ends with ONE read-back: the three counter rows, the pool and open counts and the sums.  guess_bits = 0 is qldpc_mc_run split by the
+ * syndrome verdict: no trial launch, row 1 empty.  Status codes: QLDPC_ESIZE for guess_bits outside 0 .. QLDPC_GUESS_MAX_BITS, T above the batch,
+ * guess_bits above the number of channel VNs, qber outside (0, 0.5); QLDPC_EINVAL for non-zero reserved words; QLDPC_EUNSUPPORTED, as
+ * qldpc_mc_blind, while a table of qldpc_mc_set_channel is in force (clear it with qldpc_mc_set_channel(mc, NULL)), for a decoder on the EDGES
+ * engine (create it with engine = FRAMES), for a decoder that may compact its active frames (create it with compact = 2) and for giveup_patience
+ * without freeze_messages = 1.  A refused call queues nothing and leaves the rows of the last call readable.  The first call allocates the pool, the
+ * trial rows and the list of open frames (fail_cap entries with their guess rows), sized for every g and counted by qldpc_mc_device_bytes; later
+ * calls allocate nothing.  A call touches neither the counters of the last qldpc_mc_run nor the rows of a search, a sweep, a strata run or a blind
+ * call (the launch scratch of the blind rounds -- candidate rows, selected rows, flags -- is shared, the result rows are not).
+ * Measured once at the headline shape at the foot of the waterfall (tools/mc_guess_cost.py, profiles/mc_guess_cost.json: 124 of 16 384 first decodes
+ * fail): g = 4 rescues 34 of them for 1.23 x the wall time of qldpc_mc_run over the same frames, g = 8 rescues 60 for 3.30 x (2.94 decodes per frame: the
+ * trials are hopeless ones that run to n_ite); no rescue wrong, none ambiguous; deeper in the waterfall: not measured.
+ * Not built: sessions (qldpc_recon_*) and the daemon binding; guesses among punctured parity VNs; pattern subsets (weight <= w); a
+ * minimum-distance winner rule; guessing after or inside blind rounds; sweep / strata points; the schedule on the device.
+ */
+typedef struct qldpc_mc_guess_cfg {
+    double qber;
+    int guess_bits;            /* g, 0 .. QLDPC_GUESS_MAX_BITS, 2^g <= batch                                                            */
+    uint64_t first_frame, max_frames, max_frame_errors;   /* max_frame_errors = 0: no stop rule                                        */
+    int reserved[2];           /* must be zero                                                                                         */
+} qldpc_mc_guess_cfg;
+typedef struct qldpc_mc_guess_result {
+    uint64_t frames, frame_errors, undetected;   /* sums over the rows                                                                 */
+    uint64_t rescued, open;    /* the frames of rows 1 and 2                                                                           */
+    uint64_t trials;           /* frame-decodes in trial launches                                                                      */
+    uint64_t trial_iter_sum;   /* their iterations, each clamped to n_ite                                                              */
+    uint64_t n_ok_sum;         /* trials that ended with a zero syndrome, over all sources                                             */
+    uint64_t ambiguous;        /* rescued frames with two ok trials that differ                                                        */
+    uint64_t decodes;          /* frame-decodes run: fresh frames + trials                                                             */
+    uint64_t launches, next_frame;
+    double source_ms, encode_ms, channel_ms, load_ms, decode_ms, select_ms, advance_ms;   /* as qldpc_mc_blind_result; of a trial launch the
+                                  load includes the known bits and `advance` is the resolve + the append to the open list             */
+    double expand_ms, pick_ms; /* trial launches: slot table + qldpc_guess_expand_dev; fetch + qldpc_guess_pick_dev                   */
+    double total_ms;           /* the whole call on the host's clock                                                                   */
+} qldpc_mc_guess_result;
+int    qldpc_mc_guess(qldpc_mc *mc, const qldpc_mc_guess_cfg *cfg, qldpc_mc_guess_result *res);
+/* of the last call: its 3 rows (disclosed = 0); writes min(cap, 3) and returns 3, or 0 before the first call (or a status) */
+int    qldpc_mc_guess_stats(qldpc_mc *mc, qldpc_mc_blind_round_stat *rows, int cap);
+/* of the last call: the frames that ended open (the first fail_cap of them, ascending index) with their guess rows, weak_words[cap][ceil(N/32)]
+   packed MSB-first or NULL; writes min(cap, their number) and returns their number (or a status) */
+int    qldpc_mc_guess_open(qldpc_mc *mc, uint64_t *frames, uint32_t *weak_words, int cap);
+/* host mirror, no device needed: the next launch by the schedule above; returns 0 when nothing is left, 1 with *kind = QLDPC_MC_GUESS_FRESH and
+   *n frames or QLDPC_MC_GUESS_TRIALS and *n SOURCES (n 2^g trial frames) (or a status: QLDPC_ESIZE for guess_bits outside its range, batch < 1 or
+   2^guess_bits above the batch, QLDPC_EINVAL for a missing pointer) */
+#define QLDPC_MC_GUESS_FRESH 1
+#define QLDPC_MC_GUESS_TRIALS 2
+int    qldpc_mc_guess_next_host(int guess_bits, int batch, uint64_t pool, uint64_t input_left, int *kind, int *n);
+
 #ifdef __cplusplus
 }
 #endif

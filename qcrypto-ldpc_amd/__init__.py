@@ -1403,6 +1403,31 @@ _sig("qldpc_mc_blind_next_host", C.c_int, [C.c_int, C.c_int, _u64p, C.c_uint64, 
 _sig("qldpc_mc_blind_efficiency_host", C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_double, _dp])
 
 
+class McGuessCfg(C.Structure):
+    _fields_ = [("qber", C.c_double), ("guess_bits", C.c_int), ("first_frame", C.c_uint64), ("max_frames", C.c_uint64), ("max_frame_errors", C.c_uint64),
+                ("reserved", C.c_int * 2)]
+
+
+class McGuessResult(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("frames", "frame_errors", "undetected", "rescued", "open", "trials", "trial_iter_sum", "n_ok_sum", "ambiguous", "decodes",
+                                          "launches", "next_frame")] + [
+        (n, C.c_double) for n in ("source_ms", "encode_ms", "channel_ms", "load_ms", "decode_ms", "select_ms", "advance_ms", "expand_ms", "pick_ms", "total_ms")]
+
+
+GUESS_MAX_BITS = 10
+MC_GUESS_FRESH, MC_GUESS_TRIALS = 1, 2          # kind of a launch of mc_guess_next
+MC_GUESS_ROWS = ("closed", "rescued", "open")   # the three MC_BLIND_ROUND_STAT rows of MonteCarlo.guess, disclosed = 0
+
+_sig("qldpc_guess_expand_dev", C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp])
+_sig("qldpc_guess_pick_dev", C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+_sig("qldpc_guess_trial_host", C.c_int, [C.c_int, C.c_int, C.c_int, _up, _up, _up, _up])
+_sig("qldpc_guess_pick_host", C.c_int, [C.c_int, C.c_int, _ip, _up, _ip, _ip, _ip])
+_sig("qldpc_mc_guess", C.c_int, [_vp, C.POINTER(McGuessCfg), C.POINTER(McGuessResult)])
+_sig("qldpc_mc_guess_stats", C.c_int, [_vp, _vp, C.c_int])
+_sig("qldpc_mc_guess_open", C.c_int, [_vp, _u64p, _up, C.c_int])
+_sig("qldpc_mc_guess_next_host", C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint64, _ip, _ip])
+
+
 class McChannel(C.Structure):
     _fields_ = [("levels", C.c_int), ("cum", _u64p * 2), ("value", C.POINTER(C.c_float)), ("reserved", C.c_int * 2)]
 
@@ -1551,6 +1576,84 @@ def mc_blind_efficiency(n_channel, n_disclosed_parity, frames, disclosed, qber):
     f = C.c_double(0.0)
     _chk(_L.qldpc_mc_blind_efficiency_host(int(n_channel), int(n_disclosed_parity), _u64(frames), _u64(disclosed), float(qber), C.byref(f)), "mc_blind_efficiency")
     return f.value
+
+
+def mc_guess_next(guess_bits, batch, pool, input_left):
+    """the next launch of MonteCarlo.guess (qldpc_mc_guess_next_host, no device needed): pool = the failed first decodes waiting ->
+    (MC_GUESS_FRESH, frames) or (MC_GUESS_TRIALS, sources), or None when nothing is left.  A trial launch of S = batch >> guess_bits sources while
+    pool >= S, else fresh input, else the flush."""
+    kind, n = C.c_int(0), C.c_int(0)
+    got = _chk(_L.qldpc_mc_guess_next_host(int(guess_bits), int(batch), _u64(pool), _u64(input_left), C.byref(kind), C.byref(n)), "mc_guess_next")
+    return (kind.value, n.value) if got else None
+
+
+def _guess_row(a, N, where, name):
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    if int(N) >= 1 and a.shape[-1:] != ((int(N) + 31) // 32,):
+        raise QldpcError(-6, "%s: %s has rows of %s words, ceil(N/32) = %d" % (where, name, a.shape[-1:], (int(N) + 31) // 32))
+    return a
+
+
+def guess_trial_host(N, g, t, weak, hard):
+    """the known and value rows of trial t of one failed frame on the host (qldpc_guess_trial_host): weak = its guess row, hard = its
+    hard-decision row, ceil(N/32) uint32 words MSB-first -> (known row, value row)"""
+    weak, hard = _guess_row(weak, N, "guess_trial_host", "weak").ravel(), _guess_row(hard, N, "guess_trial_host", "hard").ravel()
+    known, value = np.zeros_like(weak), np.zeros_like(weak)
+    _chk(_L.qldpc_guess_trial_host(int(N), int(g), int(t), weak.ctypes.data_as(_up), hard.ctypes.data_as(_up), known.ctypes.data_as(_up),
+                                   value.ctypes.data_as(_up)), "guess_trial_host")
+    return known, value
+
+
+def guess_pick_host(N, g, ok, trial_hard):
+    """the verdict over the 2^g trials of one failed frame on the host (qldpc_guess_pick_host): ok [2^g], trial_hard [2^g, ceil(N/32)] ->
+    (winner or -1, n_ok, ambiguous)"""
+    ok = np.ascontiguousarray(ok, dtype=np.int32).ravel()
+    rows = _guess_row(trial_hard, N, "guess_pick_host", "trial_hard")
+    if 0 <= int(g) <= GUESS_MAX_BITS and (ok.size != 1 << int(g) or rows.ndim != 2 or rows.shape[0] != ok.size):
+        raise QldpcError(-6, "guess_pick_host: %d flags and rows %s for %d trials" % (ok.size, rows.shape, 1 << int(g)))
+    w, n, a = C.c_int(-2), C.c_int(-2), C.c_int(-2)
+    _chk(_L.qldpc_guess_pick_host(int(N), int(g), ok.ctypes.data_as(_ip), rows.ctypes.data_as(_up), C.byref(w), C.byref(n), C.byref(a)), "guess_pick_host")
+    return w.value, n.value, a.value
+
+
+def _guess_dev(t, rows, cols, where, name):
+    torch = _torch()
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == ((rows, cols) if cols else (rows,))):
+        raise QldpcError(-6, "%s: %s must be a contiguous device int32 tensor of shape %s" % (where, name, (rows, cols) if cols else (rows,)))
+    return _vp(t.data_ptr())
+
+
+def guess_expand(N, g, weak, hard, stream=None):
+    """qldpc_guess_expand_dev: weak, hard device int32 [n_src, ceil(N/32)] -> (known, value) device int32 [n_src 2^g, ceil(N/32)], trial slot
+    s 2^g + t, what Decoder.load_known takes; asynchronous on `stream` (default: torch's current stream)"""
+    torch = _torch()
+    N, g, n, W = int(N), int(g), int(weak.shape[0]), (int(N) + 31) // 32
+    _guess_dev(weak, n, W, "guess_expand", "weak"), _guess_dev(hard, n, W, "guess_expand", "hard")
+    slots = n << g if 0 <= g <= GUESS_MAX_BITS and n << g <= 1 << 24 else 0      # a refused call writes nothing
+    known = torch.zeros((slots, W), dtype=torch.int32, device=weak.device)
+    value = torch.zeros_like(known)
+    spare = torch.zeros(1, dtype=torch.int32, device=weak.device)                # an empty tensor has no address, and the call checks its pointers first
+    ptr = lambda t: _vp(t.data_ptr() if t.numel() else spare.data_ptr())
+    s = stream if stream is not None else torch.cuda.current_stream(weak.device)
+    with torch.cuda.device(weak.device):
+        _chk(_L.qldpc_guess_expand_dev(N, g, n, ptr(weak), ptr(hard), ptr(known), ptr(value), _vp(s.cuda_stream)), "guess_expand")
+    return known, value
+
+
+def guess_pick(N, g, ok, trial_hard, out_hard, stream=None):
+    """qldpc_guess_pick_dev: ok device int32 [n_src 2^g], trial_hard device int32 [n_src 2^g, ceil(N/32)] -> (winner, n_ok, ambiguous) device
+    int32 [n_src]; the winner's row is copied into out_hard [n_src, ceil(N/32)], the row of a source without a winner is left as it is;
+    asynchronous on `stream` (default: torch's current stream)"""
+    torch = _torch()
+    N, g, n, W = int(N), int(g), int(out_hard.shape[0]), (int(N) + 31) // 32
+    slots = n << g if 0 <= g <= GUESS_MAX_BITS else int(ok.shape[0])
+    op, rp = _guess_dev(ok, slots, 0, "guess_pick", "ok"), _guess_dev(trial_hard, slots, W, "guess_pick", "trial_hard")
+    hp = _guess_dev(out_hard, n, W, "guess_pick", "out_hard")
+    win, nok, amb = (torch.full((n,), -2, dtype=torch.int32, device=out_hard.device) for _ in range(3))
+    s = stream if stream is not None else torch.cuda.current_stream(out_hard.device)
+    with torch.cuda.device(out_hard.device):
+        _chk(_L.qldpc_guess_pick_dev(N, g, n, op, rp, _vp(win.data_ptr()), _vp(nok.data_ptr()), _vp(amb.data_ptr()), hp, _vp(s.cuda_stream)), "guess_pick")
+    return win, nok, amb
 
 
 def _mc_channel_arg(cum0, cum1, value, where):
@@ -1914,6 +2017,36 @@ class MonteCarlo:
         known = np.zeros((self.fail_cap, (self.N + 31) // 32), np.uint32)
         n = _chk(_L.qldpc_mc_blind_open(self._h, frames.ctypes.data_as(_u64p), known.ctypes.data_as(_up), self.fail_cap), "MonteCarlo.blind_open")
         return frames[:n].copy(), known[:n].copy()
+
+    def guess(self, qber, guess_bits, first_frame=0, max_frames=None, max_frame_errors=0):
+        """Guessing rounds over the loop's frames (qldpc_mc_guess): a frame whose decode ends with a non-zero syndrome is decoded again with its
+        guess_bits weakest channel VNs pinned to each of the 2^guess_bits possible values, and is rescued iff a trial ends with a zero syndrome;
+        nothing is disclosed.  Failed frames are pooled across batches.  The input ends at max_frames (None = one batch) or at the first launch
+        boundary at which the frames closed or rescued wrong plus the open ones reach max_frame_errors (0 = never); the pool is flushed either way.
+        -> dict of the result (frames, frame_errors, undetected, rescued, open, trials, trial_iter_sum, n_ok_sum, ambiguous, decodes, launches,
+        next_frame, the stage times) plus `rows`, three MC_BLIND_ROUND_STAT rows (MC_GUESS_ROWS: closed at once, rescued -- the winner's decode --,
+        open -- the first decode), disclosed = 0."""
+        cfg = McGuessCfg()
+        cfg.qber, cfg.guess_bits, cfg.first_frame = float(qber), int(guess_bits), _u64(first_frame)
+        cfg.max_frames, cfg.max_frame_errors = (self.batch if max_frames is None else int(max_frames)), int(max_frame_errors)
+        res = McGuessResult()
+        _chk(_L.qldpc_mc_guess(self._h, C.byref(cfg), C.byref(res)), "MonteCarlo.guess")
+        out = _fields(res)
+        out["rows"] = self.guess_stats()
+        assert out["rows"].size == 3
+        return out
+
+    def guess_stats(self):
+        """the three rows of the last guess() (MC_BLIND_ROUND_STAT)"""
+        return self._last_rows(_L.qldpc_mc_guess_stats, MC_BLIND_ROUND_STAT, "MonteCarlo.guess_stats")
+
+    def guess_open(self):
+        """the frames of the last guess() that ended open (the first fail_cap of them), ascending -> (indices uint64 [n], guess rows uint32
+        [n, ceil(N/32)] MSB-first; all zero with guess_bits = 0)"""
+        frames = np.zeros(self.fail_cap, np.uint64)
+        weak = np.zeros((self.fail_cap, (self.N + 31) // 32), np.uint32)
+        n = _chk(_L.qldpc_mc_guess_open(self._h, frames.ctypes.data_as(_u64p), weak.ctypes.data_as(_up), self.fail_cap), "MonteCarlo.guess_open")
+        return frames[:n].copy(), weak[:n].copy()
 
     def __del__(self):
         try:

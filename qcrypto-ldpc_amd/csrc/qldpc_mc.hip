@@ -48,6 +48,10 @@
  *     chan_mask & ~known; one wave per frame for the verdict, tallied onto the counter row of the round (or of the frames that end open) together with
  *     popcount(known), and the open flag of every slot; then the open slots appended to the next pool in slot order: a workgroup takes 64 slots, counts the
  *     open flags before them, ballots its own and copies {frame index, known | asked} row by row, a wave per entry.  Plain stores, no returning atomics.
+ * mc_guess_keep, mc_guess_slots, mc_guess_resolve: the guessing rounds (qldpc_mc_guess), around the two kernels of qldpc_kernels_guess.h and the blind rounds'
+ *     candidate rows, verdicts and ordered append, which they reuse.  One wave per failed frame keeps the verdict of its first decode with its pool entry; one
+ *     lane per trial slot writes the slot's frame index; one wave per source of a trial launch tallies the winner's decode (or, without a winner, the verdict
+ *     kept) onto the row of the rescued (or open) frames and sums the trials' iterations.
  *
  * No kernel waits on another wave.  The decoder and the encoder are driven through their public calls only; qldpc_engine_int.h is read for
  * the decoder's sizes, device and stream.  On the host every buffer is recorded where it is allocated (mc_alloc, mc_alloc_pinned) and freed from that
@@ -65,6 +69,7 @@
 #include "../../include/qldpc.h"
 #include "qldpc_engine_int.h"
 #include "qldpc_mc_core.h"
+#include "qldpc_guess_core.h"
 
 #define MC_LANES 256
 #define MC_MAX_WAVES 2048          /* of a monitor launch */
@@ -372,6 +377,67 @@ __global__ __launch_bounds__(MC_LANES) void mc_blind_advance_append(const int *_
     if (blockIdx.x == gridDim.x - 1 && t == 0) *dst_count = base + before + (unsigned)__popcll(flags);
 }
 
+/* ---- guessing rounds: the verdicts kept with a pooled frame, the slot table of a trial launch, the verdicts of its sources ---- */
+
+/* the counter rows of a call [MC_GUESS_ROWS][MC_BLIND_COUNTERS] (closed at once, rescued, open; nothing is disclosed), then the counts and sums */
+enum { MC_GUESS_ROWS = 3, MC_G_POOL = MC_GUESS_ROWS * MC_BLIND_COUNTERS, MC_G_OPEN, MC_G_N_OK, MC_G_AMBIGUOUS, MC_G_TRIAL_ITER, MC_GUESS_WORDS };
+#define MC_GUESS_VERDICT 4         /* words of the verdict kept with a pooled frame: be, fl, it, spare */
+static_assert(MC_GUESS_MAX_BITS == QLDPC_GUESS_MAX_BITS && GS_MAX_BITS == QLDPC_GUESS_MAX_BITS, "one limit on the guess bits");
+
+/* one wave per frame of a fresh launch: verd[f] = the verdict of a failed frame's decode, what its row shows should it stay open */
+__global__ __launch_bounds__(MC_LANES) void mc_guess_keep(mc_decoded d, unsigned n, uint32_t *__restrict__ verd)
+{
+    const unsigned lane = threadIdx.x & 63u, waves = gridDim.x * (MC_LANES / 64);
+    for (unsigned f = blockIdx.x * (MC_LANES / 64) + (threadIdx.x >> 6); f < n; f += waves) {
+        if (d.ok[f] != 0) continue;      /* the same in every lane */
+        const mc_verdict v = mc_frame_verdict<true>(d, f);
+        if (lane == 0) *(uint4 *)(verd + (size_t)f * MC_GUESS_VERDICT) = make_uint4(v.be, v.fl, (unsigned)v.it, 0u);
+    }
+}
+
+/* trial slot s T + t is the frame of source s */
+__global__ __launch_bounds__(MC_LANES) void mc_guess_slots(const uint64_t *__restrict__ src_frame, uint64_t *__restrict__ slot_frame, unsigned total, int g)
+{
+    const unsigned i = blockIdx.x * MC_LANES + threadIdx.x;
+    if (i < total) slot_frame[i] = src_frame[i >> g];
+}
+
+/* one wave per source of a trial launch (a wave strides over the n_src sources), behind qk_guess_pick: a source with a winner is tallied onto
+ * row_rescued by the verdict of the winner's decode, with its n_ok and its ambiguity flag onto the sums; one without onto row_open by the verdict
+ * kept from its first decode (verd[s]).  The clamped iterations of all its T trials go onto the sums.  open[s] = no winner, for
+ * mc_blind_advance_append; the pool the sources were taken from now holds `left` entries */
+__global__ __launch_bounds__(MC_LANES) void mc_guess_resolve(mc_decoded d, unsigned n_src, int g, const int *__restrict__ winner, const int *__restrict__ n_ok,
+                                                             const int *__restrict__ ambiguous, const uint32_t *__restrict__ verd, unsigned channel_vns,
+                                                             mc_u64 *__restrict__ row_rescued, mc_u64 *__restrict__ row_open, mc_u64 *__restrict__ sums,
+                                                             int *__restrict__ open, mc_u64 left)
+{
+    const unsigned lane = threadIdx.x & 63u, waves = gridDim.x * (MC_LANES / 64), T = 1u << g;
+    mc_tally<true> rescued, ended;
+    mc_u64 nok = 0, amb = 0, it = 0;
+    for (unsigned s = blockIdx.x * (MC_LANES / 64) + (threadIdx.x >> 6); s < n_src; s += waves) {
+        unsigned its = 0;
+        for (unsigned t = lane; t < T; t += 64u) its += (unsigned)min(max(d.iters[s * T + t], 0), d.n_ite);
+        it += mc_wave_sum(its);
+        const int w = winner[s];      /* the same in every lane */
+        if (lane == 0) open[s] = w < 0;
+        if (w >= 0) {
+            rescued.add(mc_frame_verdict<true>(d, s * T + (unsigned)w));
+            nok += (mc_u64)n_ok[s]; amb += ambiguous[s] != 0;
+        } else {
+            const uint4 k = *(const uint4 *)(verd + (size_t)s * MC_GUESS_VERDICT);
+            ended.add(mc_verdict{k.x, k.y, (int)k.z, false});
+        }
+    }
+    rescued.flush(row_rescued, channel_vns);
+    ended.flush(row_open, channel_vns);
+    if (lane == 0) {
+        if (nok) atomicAdd(sums + (MC_G_N_OK - MC_G_POOL), nok);
+        if (amb) atomicAdd(sums + (MC_G_AMBIGUOUS - MC_G_POOL), amb);
+        if (it) atomicAdd(sums + (MC_G_TRIAL_ITER - MC_G_POOL), it);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) sums[0] = left;
+}
+
 /* ---- the radix select of qldpc_mc_core.h by one workgroup of MC_PAT_LANES lanes ---- */
 #define MC_PAT_LANES 256
 static_assert(MC_PAT_LANES == MC_SEL_BINS, "mc_select clears one histogram bin per lane");
@@ -522,7 +588,7 @@ struct qldpc_mc {
     float *d_mag; int *d_iters, *d_ok;
     mc_u64 *d_ctr;                     /* MC_COUNTERS counters, n_ite + 1 histogram bins, fail_cap frame indices */
     mc_u64 *h_ctr;                     /* pinned, MC_COUNTERS */
-    hipEvent_t ev[8];                  /* the stage boundaries of a batch or a round, in the order of the loop's stage list */
+    hipEvent_t ev[9];                  /* the stage boundaries of a batch or a round, in the order of the loop's stage list */
     /* puncture patterns and the search over them; the device side is allocated at first use (mc_search_reserve) */
     std::vector<uint8_t> h_cls;        /* [N] the class map, for the default candidates */
     std::vector<int> cand;             /* the candidate VNs, ascending */
@@ -562,6 +628,19 @@ struct qldpc_mc {
     mc_u64 *d_bctr, *h_bctr;           /* MC_BLIND_WORDS: the counter rows of a call [R + 2][MC_BLIND_COUNTERS], then R + 2 counts: [r] = the entries of pool r
                                           (1 .. R), [R + 1] = the frames that ended open; pinned copy */
     std::vector<qldpc_mc_blind_round_stat> bstats;   /* of the last blind call */
+    /* the guessing rounds; the device side is allocated by the first qldpc_mc_guess (mc_guess_reserve), for every g.  The launch scratch d_bcand, d_bweak,
+       d_btake, d_bopen is shared with the blind rounds, allocated by whichever comes first */
+    bool guess_ready;
+    uint64_t *d_gframe;                /* [MC_GUESS_POOL_CAP] the pool: frame indices, ... */
+    uint32_t *d_gweak, *d_ghard, *d_gverd;   /* ... [cap][Wn] guess rows, [cap][Wn] hard rows, [cap][MC_GUESS_VERDICT] the verdicts of the first decodes */
+    uint32_t *d_gkeep;                 /* [batch][MC_GUESS_VERDICT] the verdicts of a fresh launch */
+    uint64_t *d_gslot;                 /* [batch] the frame of every trial slot */
+    uint32_t *d_gknown, *d_gvalue;     /* [batch][Wn] the trial rows */
+    int *d_gwin, *d_gnok, *d_gamb;     /* [batch / 2 + 1] per source of a trial launch */
+    uint32_t *d_gout;                  /* [batch / 2 + 1][Wn] the winners' rows */
+    uint64_t *d_goframe; uint32_t *d_goweak;   /* [fail_cap], [fail_cap][Wn]: the frames that ended open, in the order of the launches */
+    mc_u64 *d_gctr, *h_gctr;           /* MC_GUESS_WORDS; pinned copy */
+    std::vector<qldpc_mc_blind_round_stat> gstats;   /* of the last guess call */
 };
 #define MC_BLIND_WORDS ((size_t)(MC_BLIND_MAX_ROUNDS + 2) * (MC_BLIND_COUNTERS + 1))
 enum { MC_ROWS_NONE = 0, MC_ROWS_SWEEP, MC_ROWS_STRATA };
@@ -1515,23 +1594,203 @@ extern "C" int qldpc_mc_blind_stats(qldpc_mc *mc, qldpc_mc_blind_round_stat *row
     return mc_stats_out(mc->bstats, rows, cap);
 }
 
-extern "C" int qldpc_mc_blind_open(qldpc_mc *mc, uint64_t *frames, uint32_t *known_words, int cap)
+/* the list of the frames that ended open, `ended` of them, in the order of the launches: the first fail_cap of them by ascending index with their
+ * rows (rows may be NULL); writes min(cap, their number) and returns their number */
+static int mc_open_out(qldpc_mc *mc, uint64_t ended, const uint64_t *d_frame, const uint32_t *d_rows, uint64_t *frames, uint32_t *rows, int cap)
 {
-    if (!mc || cap < 0 || (cap && !frames)) return QLDPC_EINVAL;
-    if (mc->bstats.empty()) return 0;
     const size_t Wn = (size_t)mc->Wn;
-    const int listed = (int)std::min<uint64_t>(mc->bstats.back().frames, (uint64_t)mc->fail_cap), n = std::min(listed, cap);
+    const int listed = (int)std::min<uint64_t>(ended, (uint64_t)mc->fail_cap), n = std::min(listed, cap);
     if (n == 0) return listed;
     HIPCHK(hipSetDevice(mc->device));
     HIPCHK(hipStreamSynchronize(mc->dec->stream));
     std::vector<uint64_t> all((size_t)listed);
-    HIPCHK(hipMemcpy(all.data(), mc->d_oframe, sizeof(uint64_t) * all.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(all.data(), d_frame, sizeof(uint64_t) * all.size(), hipMemcpyDeviceToHost));
     std::vector<int> order((size_t)listed);      /* the list is in the order of the launches */
     for (int i = 0; i < listed; i++) order[(size_t)i] = i;
     std::sort(order.begin(), order.end(), [&](int a, int b) { return all[(size_t)a] < all[(size_t)b]; });
     for (int i = 0; i < n; i++) {
         frames[i] = all[(size_t)order[(size_t)i]];
-        if (known_words) HIPCHK(hipMemcpy(known_words + (size_t)i * Wn, mc->d_oknown + (size_t)order[(size_t)i] * Wn, sizeof(uint32_t) * Wn, hipMemcpyDeviceToHost));
+        if (rows) HIPCHK(hipMemcpy(rows + (size_t)i * Wn, d_rows + (size_t)order[(size_t)i] * Wn, sizeof(uint32_t) * Wn, hipMemcpyDeviceToHost));
     }
     return listed;
+}
+
+extern "C" int qldpc_mc_blind_open(qldpc_mc *mc, uint64_t *frames, uint32_t *known_words, int cap)
+{
+    if (!mc || cap < 0 || (cap && !frames)) return QLDPC_EINVAL;
+    if (mc->bstats.empty()) return 0;
+    return mc_open_out(mc, mc->bstats.back().frames, mc->d_oframe, mc->d_oknown, frames, known_words, cap);
+}
+
+/* ------------------------------------------------------------------ guessing rounds ---- */
+
+/* everything the guessing rounds need on the device, once and for every g */
+static int mc_guess_reserve(qldpc_mc *mc)
+{
+    HIPCHK(hipSetDevice(mc->device));
+    if (mc->guess_ready) return QLDPC_OK;
+    const size_t Wn = (size_t)mc->Wn, B = (size_t)mc->batch, cap = MC_GUESS_POOL_CAP(mc->batch), S = B / 2 + 1;
+    int rc = QLDPC_OK;
+    if ((rc = mc_alloc(mc, &mc->d_bcand, B * Wn)) || (rc = mc_alloc(mc, &mc->d_bweak, B * Wn)) || (rc = mc_alloc(mc, &mc->d_btake, B)) ||
+        (rc = mc_alloc(mc, &mc->d_bopen, B)) || (rc = mc_alloc(mc, &mc->d_gframe, cap)) || (rc = mc_alloc(mc, &mc->d_gweak, cap * Wn)) ||
+        (rc = mc_alloc(mc, &mc->d_ghard, cap * Wn)) || (rc = mc_alloc(mc, &mc->d_gverd, cap * MC_GUESS_VERDICT)) ||
+        (rc = mc_alloc(mc, &mc->d_gkeep, B * MC_GUESS_VERDICT)) || (rc = mc_alloc(mc, &mc->d_gslot, B)) || (rc = mc_alloc(mc, &mc->d_gknown, B * Wn)) ||
+        (rc = mc_alloc(mc, &mc->d_gvalue, B * Wn)) || (rc = mc_alloc(mc, &mc->d_gwin, S)) || (rc = mc_alloc(mc, &mc->d_gnok, S)) ||
+        (rc = mc_alloc(mc, &mc->d_gamb, S)) || (rc = mc_alloc(mc, &mc->d_gout, S * Wn)) || (rc = mc_alloc(mc, &mc->d_goframe, (size_t)mc->fail_cap)) ||
+        (rc = mc_alloc(mc, &mc->d_goweak, (size_t)mc->fail_cap * Wn)) || (rc = mc_alloc(mc, &mc->d_gctr, (size_t)MC_GUESS_WORDS)) ||
+        (rc = mc_alloc_pinned(mc, &mc->h_gctr, (size_t)MC_GUESS_WORDS)))
+        return rc;
+    mc->guess_ready = true;
+    return QLDPC_OK;
+}
+
+/* every argument check of qldpc_mc_guess: nothing is touched before all of them pass */
+static int mc_guess_args(const qldpc_mc *mc, const qldpc_mc_guess_cfg *cfg)
+{
+    if (cfg->reserved[0] || cfg->reserved[1]) { qldpc_set_error("mc_guess: reserved fields %d, %d must be zero", cfg->reserved[0], cfg->reserved[1]); return QLDPC_EINVAL; }
+    if (!(cfg->qber > 0.0 && cfg->qber < 0.5)) { qldpc_set_error("mc_guess: qber=%g outside (0, 0.5)", cfg->qber); return QLDPC_ESIZE; }
+    if (cfg->guess_bits < 0 || cfg->guess_bits > QLDPC_GUESS_MAX_BITS) { qldpc_set_error("mc_guess: guess_bits=%d outside 0 .. %d", cfg->guess_bits, QLDPC_GUESS_MAX_BITS); return QLDPC_ESIZE; }
+    if ((1 << cfg->guess_bits) > mc->batch) { qldpc_set_error("mc_guess: the %d trials of guess_bits=%d do not fit the batch of %d frames: create the loop with a larger batch", 1 << cfg->guess_bits, cfg->guess_bits, mc->batch); return QLDPC_ESIZE; }
+    if ((unsigned)cfg->guess_bits > mc->channel_vns) { qldpc_set_error("mc_guess: guess_bits=%d above the %u channel VNs", cfg->guess_bits, mc->channel_vns); return QLDPC_ESIZE; }
+    if (mc->soft) { qldpc_set_error("mc_guess: a channel table is in force; the trials run on the BSC: clear it with qldpc_mc_set_channel(mc, NULL)"); return QLDPC_EUNSUPPORTED; }
+    if (mc->dec->engine == QLDPC_ENGINE_EDGES) { qldpc_set_error("mc_guess: the select of the weakest VNs is not built for the edge-parallel engine: create the decoder with engine = FRAMES"); return QLDPC_EUNSUPPORTED; }
+    if (mc->dec->compact_mode != 2) {      /* the engine's own rule, resolved when the decoder was created */
+        qldpc_set_error("mc_guess: the decoder may compact its active frames (compact = %d), after which the posteriors of the frames that converged earlier are gone: "
+                        "create it with compact = 2", mc->dec->cfg.compact);
+        return QLDPC_EUNSUPPORTED;
+    }
+    if (mc->dec->gu.patience > 0 && !mc->dec->freeze) {      /* a frame given up guesses with the posteriors it stopped at: exact only with frozen messages */
+        qldpc_set_error("mc_guess: the decoder gives frames up (giveup_patience = %d) and lets their messages run on, so the posteriors a failed frame guesses with "
+                        "are not the ones it stopped at: create it with freeze_messages = 1", mc->dec->gu.patience);
+        return QLDPC_EUNSUPPORTED;
+    }
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_guess(qldpc_mc *mc, const qldpc_mc_guess_cfg *cfg, qldpc_mc_guess_result *res)
+{
+    if (!mc || !cfg || !res) return QLDPC_EINVAL;
+    memset(res, 0, sizeof(*res));
+    res->next_frame = cfg->first_frame;
+    int rc = mc_guess_args(mc, cfg);
+    if (rc || (rc = mc_guess_reserve(mc))) return rc;
+    const hipStream_t s = mc->dec->stream;
+    const int g = cfg->guess_bits, T = 1 << g;
+    const size_t Wn = (size_t)mc->Wn, cap = MC_GUESS_POOL_CAP(mc->batch);
+    const mc_row row = {mc_threshold(cfg->qber), qldpc_bsc_llr((float)cfg->qber)};
+    mc_u64 *const d_rows = mc->d_gctr, *const d_sums = mc->d_gctr + MC_G_POOL;
+    const mc_u64 *const h = mc->h_gctr;
+    HIPCHK(hipMemsetAsync(mc->d_gctr, 0, sizeof(mc_u64) * MC_GUESS_WORDS, s));
+    memset(mc->h_gctr, 0, sizeof(mc_u64) * MC_GUESS_WORDS);
+    mc->gstats.assign((size_t)MC_GUESS_ROWS, qldpc_mc_blind_round_stat());
+
+    uint64_t pool = 0, done = 0, input_left = cfg->max_frames;
+    int kind = 0, n = 0;
+    double *const fresh_stage[7] = {&res->source_ms, &res->encode_ms, &res->channel_ms, &res->load_ms, &res->decode_ms, &res->select_ms, &res->advance_ms};
+    double *const trial_stage[8] = {&res->expand_ms, &res->source_ms, &res->encode_ms, &res->channel_ms, &res->load_ms, &res->decode_ms, &res->pick_ms, &res->advance_ms};
+    const auto t_start = std::chrono::steady_clock::now();
+    while (mc_guess_next(g, mc->batch, pool, input_left, &kind, &n)) {
+        HIPCHK(hipEventRecord(mc->ev[0], s));
+        if (kind == MC_GUESS_FRESH) {
+            const mc_slots sl = {nullptr, cfg->first_frame + done, nullptr, nullptr, row};
+            if ((rc = mc_generate_load(mc, sl, n, s, mc->ev, mc->ev[3]))) return rc;
+            if (mc->n_fixed && (rc = mc_erase(mc, mc->d_fixed, mc_range(0), n, n, s))) return rc;      /* the fixed puncture set: one row for all n frames */
+            HIPCHK(hipEventRecord(mc->ev[4], s));
+            if ((rc = qldpc_run(mc->dec))) return rc;
+            HIPCHK(hipEventRecord(mc->ev[5], s));
+            if ((rc = mc_fetch(mc))) return rc;
+            const unsigned total = (unsigned)n * (unsigned)mc->Wn, waves = (unsigned)std::min(n, MC_MAX_WAVES);
+            if (g) {
+                hipLaunchKernelGGL(mc_blind_cand, dim3(mc_blocks(total)), dim3(MC_LANES), 0, s, (const uint32_t *)mc->d_chan_mask, (const uint32_t *)nullptr,
+                                   (const int *)mc->d_ok, mc->d_bcand, mc->d_btake, total, (unsigned)mc->Wn);
+                LAUNCHCHK();
+                if ((rc = qldpc_fetch_weakest_dev(mc->dec, mc->d_bcand, mc->d_btake, g, mc->d_bweak))) return rc;
+            }
+            HIPCHK(hipEventRecord(mc->ev[6], s));
+            /* the frames that closed onto row 0; with g = 0 the others end open here, else they are pooled and tallied when their trials are through */
+            hipLaunchKernelGGL(mc_blind_advance, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, mc_decoded_of(mc), (unsigned)n, (const uint32_t *)nullptr, mc->channel_vns,
+                               d_rows, g ? (mc_u64 *)nullptr : d_rows + 2 * MC_BLIND_COUNTERS, mc->d_bopen, (mc_u64 *)nullptr, (mc_u64)0);
+            LAUNCHCHK();
+            const unsigned groups = ((unsigned)n + MC_APPEND_SLOTS - 1u) / MC_APPEND_SLOTS;
+            if (g) {
+                hipLaunchKernelGGL(mc_guess_keep, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, mc_decoded_of(mc), (unsigned)n, mc->d_gkeep);
+                LAUNCHCHK();
+                /* one entry is {frame index, guess row, hard row, verdict}: the ordered append of the blind rounds, once per row array */
+                const struct { const uint32_t *src; unsigned words; uint32_t *dst; } part[3] = {
+                    {mc->d_bweak, (unsigned)mc->Wn, mc->d_gweak}, {mc->d_out, (unsigned)mc->Wn, mc->d_ghard}, {mc->d_gkeep, MC_GUESS_VERDICT, mc->d_gverd}};
+                for (const auto &p : part) {
+                    hipLaunchKernelGGL(mc_blind_advance_append, dim3(groups), dim3(MC_LANES), 0, s, (const int *)mc->d_bopen, (unsigned)n, sl, (const uint32_t *)nullptr, p.src,
+                                       p.words, mc->d_gframe, p.dst, (mc_u64)pool, (mc_u64)cap, d_sums + (MC_G_POOL - MC_G_POOL));
+                    LAUNCHCHK();
+                }
+            } else {
+                hipLaunchKernelGGL(mc_blind_advance_append, dim3(groups), dim3(MC_LANES), 0, s, (const int *)mc->d_bopen, (unsigned)n, sl, (const uint32_t *)nullptr,
+                                   (const uint32_t *)nullptr, (unsigned)mc->Wn, mc->d_goframe, mc->d_goweak, h[MC_G_OPEN], (mc_u64)mc->fail_cap, d_sums + (MC_G_OPEN - MC_G_POOL));
+                LAUNCHCHK();
+            }
+            if ((rc = mc_round_end(mc, mc->h_gctr, mc->d_gctr, MC_GUESS_WORDS, fresh_stage, 7, s))) return rc;
+            res->decodes += (uint64_t)n;
+            done += (uint64_t)n; input_left -= (uint64_t)n;
+        } else {
+            /* the last n entries of the pool: a contiguous frame table and contiguous row arrays */
+            const size_t top = (size_t)pool - (size_t)n;
+            const int slots = n * T;
+            const mc_slots sl = {mc->d_gslot, 0, nullptr, nullptr, row};
+            hipLaunchKernelGGL(mc_guess_slots, dim3(mc_blocks((size_t)slots)), dim3(MC_LANES), 0, s, (const uint64_t *)(mc->d_gframe + top), mc->d_gslot, (unsigned)slots, g);
+            LAUNCHCHK();
+            if ((rc = qldpc_guess_expand_dev(mc->N, g, n, mc->d_gweak + top * Wn, mc->d_ghard + top * Wn, mc->d_gknown, mc->d_gvalue, (void *)s))) return rc;
+            HIPCHK(hipEventRecord(mc->ev[1], s));
+            if ((rc = mc_generate_load(mc, sl, slots, s, mc->ev + 1, mc->ev[4]))) return rc;
+            if (mc->n_fixed && (rc = mc_erase(mc, mc->d_fixed, mc_range(0), slots, slots, s))) return rc;
+            if ((rc = qldpc_load_known_dev(mc->dec, mc->d_gknown, mc->d_gvalue, slots))) return rc;      /* Bob's own guesses: nothing of Alice's is read */
+            HIPCHK(hipEventRecord(mc->ev[5], s));
+            if ((rc = qldpc_run(mc->dec))) return rc;
+            HIPCHK(hipEventRecord(mc->ev[6], s));
+            if ((rc = mc_fetch(mc))) return rc;
+            if ((rc = qldpc_guess_pick_dev(mc->N, g, n, mc->d_ok, mc->d_out, mc->d_gwin, mc->d_gnok, mc->d_gamb, mc->d_gout, (void *)s))) return rc;
+            HIPCHK(hipEventRecord(mc->ev[7], s));
+            const unsigned waves = (unsigned)std::min(n, MC_MAX_WAVES);
+            hipLaunchKernelGGL(mc_guess_resolve, dim3((waves + 3u) / 4u), dim3(MC_LANES), 0, s, mc_decoded_of(mc), (unsigned)n, g, (const int *)mc->d_gwin, (const int *)mc->d_gnok,
+                               (const int *)mc->d_gamb, (const uint32_t *)(mc->d_gverd + top * MC_GUESS_VERDICT), mc->channel_vns, d_rows + MC_BLIND_COUNTERS,
+                               d_rows + 2 * MC_BLIND_COUNTERS, d_sums, mc->d_bopen, (mc_u64)top);
+            LAUNCHCHK();
+            const mc_slots src = {mc->d_gframe + top, 0, nullptr, nullptr, row};
+            hipLaunchKernelGGL(mc_blind_advance_append, dim3(((unsigned)n + MC_APPEND_SLOTS - 1u) / MC_APPEND_SLOTS), dim3(MC_LANES), 0, s, (const int *)mc->d_bopen, (unsigned)n, src,
+                               (const uint32_t *)nullptr, (const uint32_t *)(mc->d_gweak + top * Wn), (unsigned)mc->Wn, mc->d_goframe, mc->d_goweak, h[MC_G_OPEN],
+                               (mc_u64)mc->fail_cap, d_sums + (MC_G_OPEN - MC_G_POOL));
+            LAUNCHCHK();
+            if ((rc = mc_round_end(mc, mc->h_gctr, mc->d_gctr, MC_GUESS_WORDS, trial_stage, 8, s))) return rc;
+            res->decodes += (uint64_t)slots; res->trials += (uint64_t)slots;
+        }
+        res->launches++;
+        pool = h[MC_G_POOL];
+        if (pool > cap) { qldpc_set_error("mc_guess: the pool holds %llu entries of %zu", (unsigned long long)pool, cap); return QLDPC_ESTATE; }
+        /* an error = a frame closed or rescued wrong, or one that ended open; the input ends here, the pool is flushed, never dropped */
+        const uint64_t fe = h[MC_FRAME_ERRORS] + h[MC_BLIND_COUNTERS + MC_FRAME_ERRORS] + h[2 * MC_BLIND_COUNTERS + MC_FRAMES];
+        if (cfg->max_frame_errors && fe >= cfg->max_frame_errors) input_left = 0;
+    }
+    res->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    for (int r = 0; r < MC_GUESS_ROWS; r++) {
+        qldpc_mc_blind_round_stat *st = &mc->gstats[(size_t)r];
+        mc_counters_out(st, h + (size_t)r * MC_BLIND_COUNTERS);
+        st->disclosed = 0;
+        res->frames += st->frames; res->frame_errors += st->frame_errors; res->undetected += st->undetected;
+    }
+    res->rescued = mc->gstats[1].frames; res->open = mc->gstats[2].frames;
+    res->trial_iter_sum = h[MC_G_TRIAL_ITER]; res->n_ok_sum = h[MC_G_N_OK]; res->ambiguous = h[MC_G_AMBIGUOUS];
+    res->next_frame = cfg->first_frame + done;
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_mc_guess_stats(qldpc_mc *mc, qldpc_mc_blind_round_stat *rows, int cap)
+{
+    if (!mc) return QLDPC_EINVAL;
+    return mc_stats_out(mc->gstats, rows, cap);
+}
+
+extern "C" int qldpc_mc_guess_open(qldpc_mc *mc, uint64_t *frames, uint32_t *weak_words, int cap)
+{
+    if (!mc || cap < 0 || (cap && !frames)) return QLDPC_EINVAL;
+    if (mc->gstats.empty()) return 0;
+    return mc_open_out(mc, mc->gstats.back().frames, mc->d_goframe, mc->d_goweak, frames, weak_words, cap);
 }

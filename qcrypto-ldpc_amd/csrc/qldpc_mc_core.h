@@ -345,6 +345,33 @@ static inline int mc_blind_next(int R, int batch, const uint64_t *pool, uint64_t
 }
 
 /*
+ * The schedule of qldpc_mc_guess, a pure function of the pool count.  Failed first decodes wait in ONE pool as {frame index, guess row, hard row, first verdict}; a
+ * trial launch takes the last S = floor(batch / T) entries and decodes their S T trial frames.  In order:
+ *
+ *   1. a trial launch of S sources while pool >= S
+ *   2. else a fresh launch of min(batch, input_left) frames
+ *   3. else the flush: a trial launch of all remaining sources
+ *
+ * Why the pool stays below S + batch: only a fresh launch appends, at most batch entries, and rule 2 applies only while pool < S, i.e. pool <= S - 1
+ * before it and <= S - 1 + batch after it.  Trial launches only take entries away.  Every launch either consumes input or removes at least one
+ * entry (S >= 1 because T <= batch), so the loop ends with the pool empty.  With g = 0 nothing is ever pooled (the caller appends nothing).
+ */
+#define MC_GUESS_MAX_BITS 10                      /* QLDPC_GUESS_MAX_BITS of include/qldpc.h */
+enum { MC_GUESS_FRESH = 1, MC_GUESS_TRIALS = 2 };   /* QLDPC_MC_GUESS_FRESH, QLDPC_MC_GUESS_TRIALS */
+/* the capacity for every g >= 1 (S <= batch / 2); g = 0 pools nothing */
+#define MC_GUESS_POOL_CAP(batch) ((size_t)(batch) / 2 + (size_t)(batch))
+
+/* returns 0 when nothing is left, else 1 with the kind and n = the frames of a fresh launch or the SOURCES of a trial launch */
+static inline int mc_guess_next(int g, int batch, uint64_t pool, uint64_t input_left, int *kind, int *n)
+{
+    const uint64_t S = (uint64_t)batch >> g;
+    if (pool >= S && pool) { *kind = MC_GUESS_TRIALS; *n = (int)S; return 1; }
+    if (input_left) { *kind = MC_GUESS_FRESH; *n = input_left < (uint64_t)batch ? (int)input_left : batch; return 1; }
+    if (pool) { *kind = MC_GUESS_TRIALS; *n = (int)pool; return 1; }
+    return 0;
+}
+
+/*
  * Host side.  The padded class map cls[32 ceil(N / 32)] of a (K, N, info_bits_pos, vn_class): vn_class != NULL is copied (every entry 0 .. 2), else the
  * harness's classes (BS/src/main.cpp:348-354): QLDPC_VN_CHANNEL at info_bits_pos (NULL = 0 .. K-1), QLDPC_VN_PINNED elsewhere.  mask
  * (optional, ceil(N / 32) words) = the packed mask of info_bits_pos.  Returns 0, or -1 for a position outside [0, N), a repeated position or

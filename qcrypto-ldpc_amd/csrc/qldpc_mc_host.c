@@ -5,7 +5,8 @@
  * (qldpc_mc_awgn_table); the deal of one round of the QBER sweep (qldpc_mc_sweep_deal_host), the function qldpc_mc_sweep itself calls per
  * round; the argument checks of the sweep over table channels (qldpc_mc_sweep_tables_check_host), which qldpc_mc_sweep_tables runs first; the FER estimate over fixed-weight strata (qldpc_mc_strata_fer_host); and the schedule of the blind reconciliation rounds
  * (qldpc_mc_blind_next_host, the function qldpc_mc_blind itself calls per launch) with the efficiency they end at
- * (qldpc_mc_blind_efficiency_host).  Plain C, no device.
+ * (qldpc_mc_blind_efficiency_host); and the schedule of the guessing rounds (qldpc_mc_guess_next_host, the function qldpc_mc_guess itself calls per
+ * launch).  Plain C, no device.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -299,6 +300,16 @@ int qldpc_mc_blind_next_host(int max_rounds, int batch, const uint64_t *pool, ui
     }
     if (!pool || !level || !n) return QLDPC_EINVAL;
     return mc_blind_next(max_rounds, batch, pool, input_left, level, n);
+}
+
+int qldpc_mc_guess_next_host(int guess_bits, int batch, uint64_t pool, uint64_t input_left, int *kind, int *n)
+{
+    if (guess_bits < 0 || guess_bits > MC_GUESS_MAX_BITS || batch < 1 || (1 << guess_bits) > batch) {
+        qldpc_set_error("mc_guess_next_host: guess_bits=%d (0 .. %d), batch=%d (at least 1 and at least 2^guess_bits)", guess_bits, MC_GUESS_MAX_BITS, batch);
+        return QLDPC_ESIZE;
+    }
+    if (!kind || !n) return QLDPC_EINVAL;
+    return mc_guess_next(guess_bits, batch, pool, input_left, kind, n);
 }
 
 int qldpc_mc_blind_efficiency_host(int n_channel, int n_disclosed_parity, uint64_t frames, uint64_t disclosed, double qber, double *f)

@@ -52,6 +52,11 @@
  *                      = still open after the last round) with the key bits those frames asked for in a last column ASKED, then a `# blind` line with
  *                      the sums, the decodes per frame and the efficiency f = (N - K + asked / frames) / (K h2(ber)); -E as the stop rule of the input;
  *                      the decoder is created with compact = 2; -A, -X, -W and -w do not apply)]
+ *                  [-G g (a NUMBER, with -D: guessing rounds, ONE qldpc_mc_guess per row of -s: a frame whose decode ends with a non-zero syndrome is
+ *                      decoded again with its g weakest key VNs pinned to each of the 2^g possible values and is rescued iff a trial ends with a zero
+ *                      syndrome; nothing is disclosed.  Per BER three rows (EP = closed at once / rescued / open) with the undetected errors in a last
+ *                      column UNDET, then a `# guess` line with the sums and a `# guess stages` line with the stage times; -E as the stop rule of the
+ *                      input; the decoder is created with compact = 2; -A, -X, -W, -w and -B do not apply.  A NAME after -G stays the encoder's method)]
  *                  [-c scale (with -Q 8: quantiser steps per LLR unit, default 8; 1 for LLRs that are integers already, as -A gives them)]
  *                  [-g patience (give a frame up once its syndrome weight has not reached a new minimum for `patience` syndrome tests in a row,
  *                      qldpc_decoder_cfg.giveup_patience; flooding and -l, needs the syndrome test; on the host loop and with -D.  Every row -- with -B
@@ -104,6 +109,7 @@ static double t_lo = 0.0, t_hi = 0.0, t_step = 0.0;
 static int strata = 0, w_lo = 0, w_hi = 0, w_step = 1;      /* -w */
 static double design_qber = 0.0;
 static int blind = 0, ask_bits = 0, max_rounds = 0;      /* -B */
+static int guess = 0, guess_bits = 0;      /* -G with a number */
 static int giveup = 0;      /* -g */
 static uint64_t gave_before = 0;
 static double parity_ber = 0.0;      /* > 0: the disclosed parity bits are themselves wrong with this probability (main.cpp (test effect of dirty parities)) */
@@ -198,7 +204,9 @@ static int parse(int argc, char **argv)
         case 'c': quant_scale = atof(optarg); break;
         case 'g': giveup = atoi(optarg); break;
         case 'o': pattern_out = optarg; break;
-        case 'G': g_method = optarg; break;      /* p.G_method (VAR/main.cpp (alist-v1.0.1):135): IDENTITY | LU_DEC; QC = Encoder_LDPC_from_QC ((qc):145) */
+        case 'G':      /* a number: the guess bits of the guessing rounds; a name: the encoder's method */
+            if (optarg[0] >= '0' && optarg[0] <= '9' && optarg[strspn(optarg, "0123456789")] == 0) { guess = 1; guess_bits = atoi(optarg); break; }
+            g_method = optarg; break;      /* p.G_method (VAR/main.cpp (alist-v1.0.1):135): IDENTITY | LU_DEC; QC = Encoder_LDPC_from_QC ((qc):145) */
         case 'l': layered = 1; break;
         case 'v': layered = 2; break;      /* Decoder_LDPC_BP_vertical_layered, VAR/main.cpp (alist-v1.0.1):240-256 */
         case 'n': synd = 0; break;
@@ -219,6 +227,8 @@ static int parse(int argc, char **argv)
     if (strata && (w_step < 1 || w_lo < 0 || w_hi < w_lo)) return usage("qldpc_sim: -w lo:hi:step with 0 <= lo <= hi and step >= 1");
     if (blind && !on_device) return usage("qldpc_sim: -B runs the blind reconciliation rounds on the device and needs -D");
     if (blind && (search_x || awgn || sweep || strata)) return usage("qldpc_sim: -B runs on the BSC rows of -s and runs neither with -X, -A, -W nor -w");
+    if (guess && !on_device) return usage("qldpc_sim: -G g runs the guessing rounds on the device and needs -D");
+    if (guess && (search_x || awgn || sweep || strata || blind || tsweep)) return usage("qldpc_sim: -G g runs on the BSC rows of -s and runs neither with -X, -A, -W, -w, -T nor -B");
     if (on_device && ((target_eff > 0.0 && !sweep) || search)) return usage("qldpc_sim: -e and -R draw a puncture pattern per batch on the host and do not run with -D");
     if (max_fe && !on_device) return usage("qldpc_sim: -E needs -D");
     if (search_x && !on_device) return usage("qldpc_sim: -X is the pattern search on the device and needs -D");
@@ -252,15 +262,15 @@ static int setup(void)
     if (msg_bits != 32 && msg_bits != 16 && msg_bits != 8) return usage("-Q 32 | 16 | 8");
     cfg.msg_dtype = msg_bits == 16 ? 1 : (msg_bits == 8 ? 2 : 0);      /* 16: binary16 message storage; 8: fixed-point min-sum */
     cfg.quant_scale = (float)quant_scale;
-    if (blind) cfg.compact = 2;      /* the select of the weakest VNs needs every frame's posteriors: no active-frame compaction */
+    if (blind || guess) cfg.compact = 2;      /* the select of the weakest VNs needs every frame's posteriors: no active-frame compaction */
     cfg.giveup_patience = giveup;
-    if (giveup && blind) cfg.freeze_messages = 1;      /* a frame given up asks with the posteriors it stopped at */
+    if (giveup && (blind || guess)) cfg.freeze_messages = 1;      /* a frame given up asks, or guesses, with the posteriors it stopped at */
     if ((rc = qldpc_decoder_create(H, K, pos, &cfg, &dec))) return die("decoder", rc);
 
     printf("# * libqldpc %d on HIP device 0; Decoder_LDPC_BP_%s_Update_rule_%s (param %g), n_ite %d, syndrome %d, %d-bit messages\n", qldpc_version(),
            layered == 2 ? "vertical_layered" : (layered ? "horizontal_layered" : "flooding"), rule_name, (double)param, n_ite, synd, msg_bits);
     if (giveup) printf("#    ** frames are given up after %d syndrome tests without a new minimum of the syndrome weight%s\n", giveup,
-                       blind ? " (-B: decoder created with freeze_messages = 1)" : "");
+                       blind ? " (-B: decoder created with freeze_messages = 1)" : guess ? " (-G: decoder created with freeze_messages = 1)" : "");
     printf("#    ** Info. bits (K) = %d\n#    ** Frame size (N) = %d\n#    ** Code rate  (R) = %f\n#    ** max CN degree   = %d\n", K, N, (double)K / N, qldpc_code_max_cn_degree(H));
     printf("#    ** Est. QKD Key Rate After Priv Amp = %f\n", (double)(K - (N - K)) / (double)K);
     printf("# %8s | %8s | %8s | %8s | %9s | %9s | %10s\n", "EP", "FRA", "BE", "FE", "BER", "FER", "SIM_THR");
@@ -482,6 +492,41 @@ static int mode_blind(void)
     return 0;
 }
 
+/* -G g: every row of -s one qldpc_mc_guess, three rows */
+static int mode_guess(void)
+{
+    int rc;
+    static const char *const name[3] = {"closed", "rescued", "open"};
+    FOR_EACH_BER(ber) {
+        qldpc_mc_guess_cfg gcfg;
+        memset(&gcfg, 0, sizeof(gcfg));
+        gcfg.qber = ber; gcfg.guess_bits = guess_bits; gcfg.max_frames = MAX_FRAMES; gcfg.max_frame_errors = max_fe;
+        qldpc_mc_guess_result r;
+        qldpc_mc_blind_round_stat rows[3];
+        if ((rc = qldpc_mc_guess(mc, &gcfg, &r))) return die("mc_guess", rc);
+        if ((rc = qldpc_mc_guess_stats(mc, rows, 3)) < 0) return die("mc_guess_stats", rc);
+        printf("# ber %.4f: guessing rounds, %d guess bits = %d trials per failed frame; EP = how the frames ended; last column = undetected errors\n", ber, guess_bits,
+               1 << guess_bits);
+        for (int i = 0; i < 3; i++) {      /* SIM_THR: the call's decode time is shared by the rows, as under -W */
+            const double fra = rows[i].frames ? (double)rows[i].frames : 1.0;
+            printf("  %8s | %8llu | %8llu | %8llu | %8llu | %9.2e | %9.2e | %10.3f\n", name[i], (unsigned long long)rows[i].frames, (unsigned long long)rows[i].bit_errors,
+                   (unsigned long long)rows[i].frame_errors, (unsigned long long)rows[i].undetected, (double)rows[i].bit_errors / (fra * K), (double)rows[i].frame_errors / fra,
+                   (double)r.frames * K / (r.decode_ms * 1e-3) / 1e6);
+        }
+        printf("# guess: %llu frames, %llu rescued, %llu open, %llu ambiguous, %llu trials (%llu ok) in %llu launches = %.4f decodes per frame, %.2f iterations per trial; "
+               "FER %.3e, rescued wrong %llu\n",
+               (unsigned long long)r.frames, (unsigned long long)r.rescued, (unsigned long long)r.open, (unsigned long long)r.ambiguous, (unsigned long long)r.trials,
+               (unsigned long long)r.n_ok_sum, (unsigned long long)r.launches, r.frames ? (double)r.decodes / (double)r.frames : 0.0,
+               r.trials ? (double)r.trial_iter_sum / (double)r.trials : 0.0, r.frames ? (double)(r.open + rows[0].frame_errors + rows[1].frame_errors) / (double)r.frames : 0.0,
+               (unsigned long long)rows[1].frame_errors);
+        printf("# guess stages (ms): source %.3f, encode %.3f, channel %.3f, load %.3f, decode %.3f, select %.3f, expand %.3f, pick %.3f, advance %.3f; total %.3f\n",
+               r.source_ms, r.encode_ms, r.channel_ms, r.load_ms, r.decode_ms, r.select_ms, r.expand_ms, r.pick_ms, r.advance_ms, r.total_ms);
+        if (gave_line(ber)) return 1;
+        fflush(stdout);
+    }
+    return 0;
+}
+
 /* -D alone: the same table, every row one qldpc_mc_run */
 static int mode_rows(void)
 {
@@ -561,7 +606,7 @@ int main(int argc, char **argv)
 {
     int rc = parse(argc, argv);
     if (!rc) rc = setup();
-    if (!rc) rc = !on_device ? run_host() : awgn ? mode_awgn() : tsweep ? mode_tsweep() : strata ? mode_strata() : blind ? mode_blind() : sweep ? mode_sweep() : search_eff > 0.0 ? mode_search() : mode_rows();
+    if (!rc) rc = !on_device ? run_host() : awgn ? mode_awgn() : tsweep ? mode_tsweep() : strata ? mode_strata() : blind ? mode_blind() : guess ? mode_guess() : sweep ? mode_sweep() : search_eff > 0.0 ? mode_search() : mode_rows();
     if (rc) return rc;
     qldpc_mc_free(mc);
     qldpc_decoder_free(dec); qldpc_encoder_free(enc); qldpc_code_free(H);
