@@ -567,6 +567,62 @@ int qldpc_recon_decode_blind(qldpc_recon *r, int n, uint32_t *const *key_words, 
  * 0 .. key_bits - 1: QLDPC_EINVAL. */
 int qldpc_recon_disclose_host(const uint32_t *key_words, int key_bits, const int *pos, int n, uint8_t *bit);
 /*
+ * Guessing rounds in a session (the rule of qldpc_guess_* below, with the session's CRC as the verdict; stated once in csrc/qldpc_recon_guess_core.h).
+ * Local to Bob: nothing is disclosed, no packet is needed, qldpc_recon_msg and the wire format are unchanged.  Stateless and opt-in.
+ *   first pass  exactly qldpc_recon_decode_blocks: same validation, grouping, lanes, staging and verification.  A block that ends QLDPC_OK there has the
+ *               status, key, corrected and iterations of that call and guess[i] = {0, -1, 0, 0, 0, 0}.  With guess_bits = 0 (guess may be NULL), or
+ *               with no failed block, the call is qldpc_recon_decode_blocks: nothing more is launched.
+ *   source      a block whose first decode ends QLDPC_EDECODE (syndrome or CRC).  Its guess set is what qldpc_fetch_weakest_dev(cand, take, d =
+ *               guess_bits) gives out of that failed decode, the candidates being the key positions below key_bits; its hard row is that of the
+ *               same run; ranks, trials and the known / value rows are those of qldpc_guess_expand_dev.
+ *   trials      the T = 2^guess_bits trial frames of a source are its own frame decoded from scratch -- the same bits, erasures, |LLR|, shortening and
+ *               class map as its first decode -- plus qldpc_load_known_dev with the trial's rows.  The failed blocks of a code are pooled across the
+ *               call and decoded floor(max_blocks / T) sources a launch, in ascending block index, after the ordinary launches of that code, on its
+ *               lane and decoder.
+ *   verdict     pass(t) = the trial's syndrome is zero && the CRC-32 of its key bits below key_bits equals msgs[i].crc32 -- what verifies a first
+ *               decode.  winner = the lowest passing t; n_ok, n_pass count the zero-syndrome and the passing trials; ambiguous = some passing trial's
+ *               key differs from the winner's in a bit below key_bits.  With a winner: status QLDPC_OK, the winner's key written in place, corrected
+ *               counted against the key handed in, iterations = the first decode's + the winner's.  Without: QLDPC_EDECODE, the key untouched,
+ *               iterations = the first decode's, corrected = 0.
+ *   invariance  everything about a block is a function of the block, the session configuration and guess_bits: not of the other blocks of the call,
+ *               of max_blocks (while T <= max_blocks) or of how the sources fall into trial launches.
+ *   leak        qldpc_recon_leaked_bits(&msgs[i]) is unchanged: nothing is disclosed.  But the CRC now selects among up to n_ok zero-syndrome
+ *               candidates, so the chance of accepting a wrong key is at most n_ok 2^-32 per block instead of 2^-32; qldpc_polyhash_* is the check
+ *               for callers who need a bound.
+ * Refused before anything is decoded: QLDPC_EINVAL for a missing pointer, or guess == NULL with guess_bits > 0; QLDPC_ESIZE for guess_bits outside
+ * 0 .. QLDPC_GUESS_MAX_BITS or 2^guess_bits > max_blocks (lower guess_bits or raise max_blocks); QLDPC_EUNSUPPORTED, as qldpc_recon_decode_blind, for a
+ * session on the edge-parallel engine (max_blocks <= 8 with the flooding schedule) -- and, from the run, for a flooding run that compacted its frames.
+ * A block with a bad header gets QLDPC_ESIZE alone.  With QLDPC_RECON_GANG=1 these calls decode on the ordinary path.  The pool of a code (sources of
+ * a call and their trial frames) is device memory of its session entry, allocated by the first guessing call that uses the code and freed with it.
+ *
+ * qldpc_recon_guess_settle_dev is the verdict alone over device pointers (the two kernels a trial launch ends with), so that synthetic rows can be
+ * settled without a decode: d_trial_rows [n_src 2^g][Wn] (qldpc_fetch_packed_dev), d_ok, d_iters [n_src 2^g] (qldpc_fetch_status_dev), d_keys
+ * [n_src][Wk] the keys handed in, d_key_bits (1 .. 32 Wk: the caller's business, the kernels clamp), d_crc_want, d_first_iters [n_src] -> d_pass_out,
+ * d_crc_out [n_src 2^g] = pass(t) and the CRC of every trial, d_res_keys [n_src][Wk] (words past a key's length are not written), d_res [4][n_src] =
+ * status | corrected | iterations | CRC of the winner's key (of trial 0's without a winner), d_guess [n_src][6] = the ints of qldpc_recon_guess.
+ * Asynchronous on hip_stream, on the current device.  qldpc_recon_guess_settle_host is its mirror on host pointers, no device needed; it also
+ * refuses a key_bits outside 1 .. 32 Wk (QLDPC_ESIZE).  Both: QLDPC_EINVAL for a missing pointer, QLDPC_ESIZE for g outside 0 ..
+ * QLDPC_GUESS_MAX_BITS, n_src < 0, n_src 2^g above 2^24, Wk < 1 or Wn < Wk.
+ * Not built: the daemon binding (its one-block path is on the edge engine), guessing inside qldpc_recon_decode_blind, giveup_patience on the trial
+ * launches, gangs, the edge engine.
+ */
+typedef struct qldpc_recon_guess {      /* out, per block */
+    int tried;              /* 1: the block's first decode failed and its 2^g trials were decoded */
+    int winner;             /* the trial kept, or -1 */
+    int n_ok;               /* trials that ended with a zero syndrome */
+    int n_pass;             /* of those, trials whose key bits match msgs[i].crc32 */
+    int ambiguous;          /* some passing trial differs from the winner in a key bit below key_bits */
+    int trial_iterations;   /* sum over the block's trials */
+} qldpc_recon_guess;
+int qldpc_recon_decode_guess(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber, const qldpc_recon_msg *msgs,
+                             const uint32_t *const *parity_words, int guess_bits, qldpc_recon_guess *guess, int *status, int *corrected, int *iterations);
+int qldpc_recon_guess_settle_dev(int g, int n_src, int Wk, int Wn, const uint32_t *d_trial_rows, const int *d_ok, const int *d_iters, const uint32_t *d_keys,
+                                 const int *d_key_bits, const uint32_t *d_crc_want, const int *d_first_iters, int *d_pass_out, uint32_t *d_crc_out,
+                                 uint32_t *d_res_keys, int *d_res, int *d_guess, void *hip_stream);
+int qldpc_recon_guess_settle_host(int g, int n_src, int Wk, int Wn, const uint32_t *trial_rows, const int *ok, const int *iters, const uint32_t *keys,
+                                  const int *key_bits, const uint32_t *crc_want, const int *first_iters, int *pass_out, uint32_t *crc_out, uint32_t *res_keys,
+                                  int *res, int *guess);
+/*
  * Bob's QBER estimate of every block out of its parity message (qldpc_qber_* below), before anything is decoded: the blocks are validated, grouped by
  * code and assembled into frames exactly as qldpc_recon_decode_blocks does it (key VNs channel, shortened past key_bits, disclosed parity pinned,
  * punctured parity erased), and each group goes through the estimator of its session entry (one per entry, created with the entry when the session
@@ -1396,7 +1452,7 @@ int    qldpc_guess_pick_host(int N, int g, const int *ok, const uint32_t *trial_
  * Measured once at the headline shape at the foot of the waterfall (tools/mc_guess_cost.py, profiles/mc_guess_cost.json: 124 of 16 384 first decodes
  * fail): g = 4 rescues 34 of them for 1.23 x the wall time of qldpc_mc_run over the same frames, g = 8 rescues 60 for 3.30 x (2.94 decodes per frame: the
  * trials are hopeless ones that run to n_ite); no rescue wrong, none ambiguous; deeper in the waterfall: not measured.
- * Not built: sessions (qldpc_recon_*) and the daemon binding; guesses among punctured parity VNs; pattern subsets (weight <= w); a
+ * The sessions have them as qldpc_recon_decode_guess (above), with the CRC in the verdict.  Not built: the daemon binding; guesses among punctured parity VNs; pattern subsets (weight <= w); a
  * minimum-distance winner rule; guessing after or inside blind rounds; sweep / strata points; the schedule on the device.
  */
 typedef struct qldpc_mc_guess_cfg {

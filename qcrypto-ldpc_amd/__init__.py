@@ -875,6 +875,11 @@ class ReconBlind(C.Structure):
 
 _sig("qldpc_recon_decode_blind", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _fp, C.POINTER(ReconMsg), C.POINTER(_up), C.POINTER(ReconBlind), C.c_int, _ip, _ip, _ip, _ip])
 _sig("qldpc_recon_disclose_host", C.c_int, [_up, C.c_int, _ip, C.c_int, C.POINTER(C.c_uint8)])
+# a qldpc_recon_guess per block, as a structured array
+RECON_GUESS_DTYPE = np.dtype([(f, np.int32) for f in ("tried", "winner", "n_ok", "n_pass", "ambiguous", "trial_iterations")])
+_sig("qldpc_recon_decode_guess", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _fp, C.POINTER(ReconMsg), C.POINTER(_up), C.c_int, _vp, _ip, _ip, _ip])
+_sig("qldpc_recon_guess_settle_dev", C.c_int, [C.c_int] * 4 + [_vp] * 12 + [_vp])
+_sig("qldpc_recon_guess_settle_host", C.c_int, [C.c_int] * 4 + [_up, _ip, _ip, _up, _ip, _up, _ip, _ip, _up, _up, _ip, _ip])
 _sig("qldpc_crc32_words_chunked", C.c_uint32, [_up, C.c_int, C.c_int])
 _sig("qldpc_recon_parity_words", C.c_int, [C.POINTER(ReconMsg)])
 _sig("qldpc_recon_leaked_bits", C.c_int, [C.POINTER(ReconMsg)])
@@ -2072,6 +2077,53 @@ def recon_disclose(key_words, key_bits, pos):
     return out[:p_.size]
 
 
+def _settle_result(n, res_keys, res, guess, passed, crc):
+    return dict(status=res[0], corrected=res[1], iterations=res[2], crc=res[3], keys=res_keys, guess=guess.view(RECON_GUESS_DTYPE).reshape(n) if n else
+                np.zeros(0, RECON_GUESS_DTYPE), passed=passed, trial_crc=crc)
+
+
+def recon_guess_settle_host(g, trial_rows, ok, iters, keys, key_bits, crc_want, first_iters):
+    """the verdict of a guessing round of a session on the host (qldpc_recon_guess_settle_host): trial_rows uint32 [n_src 2^g, Wn], ok and iters
+    [n_src 2^g], keys uint32 [n_src, Wk] (the keys handed in), key_bits, crc_want, first_iters [n_src] -> dict(status, corrected, iterations, crc [n_src],
+    keys uint32 [n_src, Wk] (words past a key's length stay 0), guess (RECON_GUESS_DTYPE [n_src]), passed int32 and trial_crc uint32 [n_src 2^g])"""
+    rows, kw = np.ascontiguousarray(trial_rows, dtype=np.uint32), np.ascontiguousarray(keys, dtype=np.uint32)
+    if rows.ndim != 2 or kw.ndim != 2:
+        raise QldpcError(-6, "recon_guess_settle_host: trial_rows and keys are 2-D arrays")
+    n, slots = kw.shape[0], rows.shape[0]
+    ok, it = np.ascontiguousarray(ok, dtype=np.int32).ravel(), np.ascontiguousarray(iters, dtype=np.int32).ravel()
+    kb, want, first = _np_i32(key_bits).ravel(), np.ascontiguousarray(crc_want, dtype=np.uint32).ravel(), _np_i32(first_iters).ravel()
+    if 0 <= int(g) <= GUESS_MAX_BITS and (slots != n << int(g) or ok.size != slots or it.size != slots or kb.size != n or want.size != n or first.size != n):
+        raise QldpcError(-6, "recon_guess_settle_host: %d sources of %d trials with %d rows, %d / %d flags and counts, %d / %d / %d scalars" %
+                         (n, 1 << int(g), slots, ok.size, it.size, kb.size, want.size, first.size))
+    passed, crc = np.zeros(max(slots, 1), np.int32), np.zeros(max(slots, 1), np.uint32)
+    res_keys, res, guess = np.zeros((n, kw.shape[1]), np.uint32), np.zeros((4, max(n, 1)), np.int32), np.zeros((max(n, 1), 6), np.int32)
+    _chk(_L.qldpc_recon_guess_settle_host(int(g), n, kw.shape[1], rows.shape[1], _ptr(rows, _up), _ptr(ok, _ip), _ptr(it, _ip), _ptr(kw, _up), _ptr(kb, _ip), _ptr(want, _up),
+                                          _ptr(first, _ip), _ptr(passed, _ip), _ptr(crc, _up), _ptr(res_keys, _up), _ptr(res, _ip), _ptr(guess, _ip)),
+         "recon_guess_settle_host")
+    return _settle_result(n, res_keys, res[:, :n], guess[:n], passed[:slots], crc[:slots])
+
+
+def recon_guess_settle(g, trial_rows, ok, iters, keys, key_bits, crc_want, first_iters, stream=None):
+    """qldpc_recon_guess_settle_dev: the same over contiguous device int32 tensors (trial_rows [n_src 2^g, Wn], ok, iters [n_src 2^g], keys [n_src, Wk], key_bits,
+    crc_want, first_iters [n_src]) -> the dict of recon_guess_settle_host as numpy arrays (the call is asynchronous on `stream`; the copies back wait for it)"""
+    torch = _torch()
+    g, n, slots, Wk, Wn = int(g), int(keys.shape[0]), int(trial_rows.shape[0]), int(keys.shape[1]), int(trial_rows.shape[1])
+    if 0 <= g <= GUESS_MAX_BITS and slots != n << g:
+        raise QldpcError(-6, "recon_guess_settle: %d sources of %d trials with %d rows" % (n, 1 << g, slots))
+    ptrs = [_guess_dev(trial_rows, slots, Wn, "recon_guess_settle", "trial_rows"), _guess_dev(ok, slots, 0, "recon_guess_settle", "ok"),
+            _guess_dev(iters, slots, 0, "recon_guess_settle", "iters"), _guess_dev(keys, n, Wk, "recon_guess_settle", "keys")]
+    ptrs += [_guess_dev(t, n, 0, "recon_guess_settle", name) for t, name in ((key_bits, "key_bits"), (crc_want, "crc_want"), (first_iters, "first_iters"))]
+    dev = keys.device
+    passed, crc = (torch.zeros(max(slots, 1), dtype=torch.int32, device=dev) for _ in range(2))
+    res_keys, res, guess = torch.zeros((n, Wk), dtype=torch.int32, device=dev), torch.zeros((4, max(n, 1)), dtype=torch.int32, device=dev), torch.zeros((max(n, 1), 6), dtype=torch.int32, device=dev)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        _chk(_L.qldpc_recon_guess_settle_dev(g, n, Wk, Wn, *ptrs, _vp(passed.data_ptr()), _vp(crc.data_ptr()), _vp(res_keys.data_ptr()), _vp(res.data_ptr()),
+                                             _vp(guess.data_ptr()), _vp(s.cuda_stream)), "recon_guess_settle")
+        host = [t.cpu().numpy() for t in (res_keys, res, guess, passed, crc)]
+    return _settle_result(n, host[0].view(np.uint32), host[1][:, :n], np.ascontiguousarray(host[2][:n]), host[3][:slots], host[4][:slots].view(np.uint32))
+
+
 class Recon:
     """One side's reconciliation engine: what an ecd2 LDPC handler calls (qber_estim.c:337-340,420-423)."""
 
@@ -2251,6 +2303,25 @@ class Recon:
         _chk(_L.qldpc_recon_decode_blind(self._h, n, kp, kb.ctypes.data_as(_ip), qb.ctypes.data_as(_fp), arr, pp, bl, int(ask_bits), st.ctypes.data_as(_ip),
                                          co.ctypes.data_as(_ip), it.ctypes.data_as(_ip), lk.ctypes.data_as(_ip)), "Recon.decode_blind")
         return st, kws, co, it, lk, [ask[i][:bl[i].n_ask].copy() for i in range(n)]
+
+    def decode_guess(self, keys, key_bits, qber, msgs, parities, guess_bits):
+        """decode_blocks with guessing rounds (qldpc_recon_decode_guess): a block whose first decode fails is decoded again with its guess_bits weakest key
+        positions pinned to each of the 2^guess_bits values, and the lowest trial with a zero syndrome and Alice's CRC is kept; nothing is disclosed.
+        Returns (status[], corrected keys, corrected[], iterations[], guess) with guess a RECON_GUESS_DTYPE array, one row per block"""
+        n = len(keys)
+        kws = [np.array(k, dtype=np.uint32, copy=True) for k in keys]
+        pars = [np.ascontiguousarray(p, dtype=np.uint32) for p in parities]
+        kp = (_up * n)(*[k.ctypes.data_as(_up) for k in kws])
+        pp = (_up * n)(*[p.ctypes.data_as(_up) for p in pars])
+        kb = np.ascontiguousarray(key_bits, dtype=np.int32)
+        qb = np.ascontiguousarray(qber, dtype=np.float32)
+        arr = (ReconMsg * n)(*msgs)
+        st, co, it = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+        guess = np.zeros(n, RECON_GUESS_DTYPE)
+        guess["winner"] = -1
+        _chk(_L.qldpc_recon_decode_guess(self._h, n, kp, kb.ctypes.data_as(_ip), qb.ctypes.data_as(_fp), arr, pp, int(guess_bits), _vp(guess.ctypes.data),
+                                         st.ctypes.data_as(_ip), co.ctypes.data_as(_ip), it.ctypes.data_as(_ip)), "Recon.decode_guess")
+        return st, kws, co, it, guess
 
     def prepare_decode(self, keys, key_bits, qber, msgs, parities):
         """decode_blocks with the argument marshalling done once: returns an object whose run() is the one C call

@@ -53,6 +53,9 @@ struct recon_entry {
     uint32_t *d_blind;    /* blind rounds (allocated by the first one): known | value | candidate | weakest rows, [4][max_blocks][Wn] */
     qldpc_qber *qest;     /* qldpc_recon_estimate_blocks: the entry's estimator (with the entry when the session preloads, else at the first such call) */
     qldpc_qber *qest_m;   /* qldpc_recon_estimate_blocks_merged: a second one with merging on (qldpc_qber_set_merge) */
+    uint32_t *d_gpool;    /* guessing rounds (allocated by the first guessing call): the sources of a call, gpool_cap of them (recon_guess_pool_layout), then their results (recon_bob_layout | guess ints) */
+    int gpool_cap;
+    uint32_t *d_gtrial;   /* ... and the frames of a trial launch: known | value | bits | erase rows [4][max_blocks][Wn], then |LLR| | key_bits | pass | CRC [4][max_blocks] */
     uint32_t *d_est;      /* their outputs: counts [max_blocks][rows][2] | QBER [max_blocks], sized for the merged rows */
 };
 
@@ -170,6 +173,8 @@ __global__ __launch_bounds__(RK_LANES) void rk_crc(const uint32_t *__restrict__ 
     if (threadIdx.x == 0) crc_out[b] = crc;
 }
 
+#include "qldpc_kernels_recon_guess.h"
+
 extern "C" void qldpc_recon_cfg_default(qldpc_recon_cfg *c)
 {
     if (!c) return;
@@ -254,6 +259,7 @@ static void entry_free(recon_entry &e)
     qldpc_code_free(e.code);
     (void)hipFree(e.d_est);
     (void)hipFree(e.d_cls); (void)hipFree(e.d_out); (void)hipFree(e.d_iters); (void)hipFree(e.d_ok); (void)hipFree(e.d_blind);
+    (void)hipFree(e.d_gpool); (void)hipFree(e.d_gtrial);
     for (auto &st : e.set) {
         (void)hipFree(st.d_in); (void)hipFree(st.d_res); (void)hipFree(st.d_bits); (void)hipFree(st.d_erase);
         if (st.h_in) (void)hipHostFree(st.h_in);
@@ -638,8 +644,16 @@ struct recon_call {
     /* Bob */
     uint32_t *const *key; const float *qber; const qldpc_recon_msg *msgs; const uint32_t *const *parity; int *status, *corrected, *iterations;
     qldpc_recon_blind *blind; int ask_bits;      /* != NULL: a blind round (qldpc_recon_decode_blind) */
+    qldpc_recon_guess *guess; int guess_bits;    /* guess_bits > 0: a call with guessing rounds (qldpc_recon_decode_guess) */
     /* Alice */
     const uint32_t *const *akey; qldpc_recon_msg *amsgs; uint32_t *const *aparity;
+};
+
+/* guessing rounds: the blocks of an entry whose first decode failed, in pool order (slot k of the entry's pool holds block idx[k]) */
+struct guess_sources {
+    recon_entry *e;
+    std::vector<int> idx;
+    bool any_punct;
 };
 
 struct lane_run {
@@ -647,6 +661,7 @@ struct lane_run {
     recon_lane *lane;
     const recon_call *call;
     std::vector<recon_job> jobs;
+    std::vector<guess_sources> guess;      /* one per entry of the lane that had a failure */
     int rc;
     std::string err;
 };
@@ -782,6 +797,127 @@ static int job_run(lane_run *L, recon_job &j)
     return QLDPC_OK;                                   /* Alice: the encoder runs in job_fetch, with what reads its codewords */
 }
 
+/* the pool and the trial frames of an entry for a guessing call with `sources` blocks on it: allocated by the first such call, the pool again when a
+ * call brings more blocks than it holds (it is empty between calls, and every call ends synchronised) */
+static int entry_guess_pool(const qldpc_recon *r, recon_entry &e, int sources)
+{
+    const size_t B = (size_t)r->cfg.max_blocks, Wk = (size_t)e.K / 32, Wn = (size_t)(e.K + e.M + 31) / 32;
+    const int cap = std::max(sources, r->cfg.max_blocks);
+    if (!e.d_gtrial && hipMalloc((void **)&e.d_gtrial, sizeof(uint32_t) * 4 * (B * Wn + B)) != hipSuccess) { qldpc_set_error("recon_decode_guess: device allocation failed"); return QLDPC_ENOMEM; }
+    if (e.gpool_cap >= cap) return QLDPC_OK;
+    (void)hipFree(e.d_gpool);
+    e.d_gpool = nullptr; e.gpool_cap = 0;
+    const size_t words = recon_guess_pool_layout(nullptr, cap, (int)Wk, (int)Wn).words + recon_bob_layout(nullptr, cap, (int)Wk).words + (size_t)cap * RG_FIELDS;
+    if (hipMalloc((void **)&e.d_gpool, sizeof(uint32_t) * words) != hipSuccess) { qldpc_set_error("recon_decode_guess: device allocation failed"); return QLDPC_ENOMEM; }
+    e.gpool_cap = cap;
+    return QLDPC_OK;
+}
+
+/* the rows of a trial launch in d_gtrial */
+struct guess_trial_view { uint32_t *known, *value, *bits, *erase; float *mag; int *key_bits, *pass; uint32_t *crc; };
+static guess_trial_view guess_trial_layout(const qldpc_recon *r, const recon_entry *e)
+{
+    const size_t B = (size_t)r->cfg.max_blocks, rows = B * ((size_t)(e->K + e->M + 31) / 32);
+    uint32_t *b = e->d_gtrial;
+    guess_trial_view v;
+    v.known = b; v.value = b + rows; v.bits = b + 2 * rows; v.erase = b + 3 * rows;
+    v.mag = reinterpret_cast<float *>(b + 4 * rows); v.key_bits = reinterpret_cast<int *>(b + 4 * rows + B); v.pass = reinterpret_cast<int *>(b + 4 * rows + 2 * B);
+    v.crc = b + 4 * rows + 3 * B;
+    return v;
+}
+
+/*
+ * A guessing call, after the results of a job are on their way: they are waited for here (the wait job_finish makes anyway, made before the next job
+ * is launched, because the posteriors of this decode are gone once the decoder is loaded again), and only a job with a failed block does more: the
+ * select of the g weakest key positions of every failed block (the status column rk_verify wrote is the take column) and rk_guess_capture, which
+ * keeps what the trials need in the entry's pool, device to device.  A job without a failure queues nothing.
+ */
+static int job_capture(lane_run *L, recon_job &j)
+{
+    recon_entry *e = j.e;
+    stage_set *st = j.st;
+    hipStream_t s = L->lane->stream;
+    const int n = (int)j.idx.size(), Wk = e->K / 32, Wn = (e->K + e->M + 31) / 32;
+    HIPCHK(hipEventSynchronize(st->ev_done));
+    const recon_bob_view h = job_bob_res(j, st->h_res);
+    int failed = 0;
+    for (int t = 0; t < n; t++) failed += h.status[t] != QLDPC_OK;
+    if (!failed) return QLDPC_OK;
+    guess_sources *gs = nullptr;
+    for (auto &x : L->guess) if (x.e == e) gs = &x;
+    if (!gs) { L->guess.push_back(guess_sources{e, std::vector<int>(), false}); gs = &L->guess.back(); }
+    const int base = (int)gs->idx.size();
+    if (base + failed > e->gpool_cap) { qldpc_set_error("recon_decode_guess: %d failed blocks pass the pool of %d", base + failed, e->gpool_cap); return QLDPC_ESTATE; }
+    const recon_in_view d = job_in(j, st->d_in);
+    const recon_bob_view res = job_bob_res(j, st->d_res);
+    const guess_trial_view tv = guess_trial_layout(L->r, e);
+    uint32_t *d_cand = tv.value, *d_weak = tv.known;      /* free until the trial launches */
+    hipLaunchKernelGGL(rk_guess_cand, dim3((unsigned)((Wn + RK_LANES - 1) / RK_LANES), (unsigned)n), dim3(RK_LANES), 0, s, d.key_bits, d_cand, Wk, Wn);
+    HIPCHK(hipGetLastError());
+    if (int rc = qldpc_fetch_weakest_dev(e->dec, d_cand, res.status, L->call->guess_bits, d_weak)) return rc;
+    hipLaunchKernelGGL(rk_guess_capture, dim3((unsigned)n), dim3(RK_LANES), 0, s, res.status, e->d_iters, d_weak, e->d_out, st->d_bits, st->d_erase, d,
+                       recon_guess_pool_layout(e->d_gpool, e->gpool_cap, Wk, Wn), base, e->gpool_cap, Wk, Wn);
+    HIPCHK(hipGetLastError());
+    for (int t = 0; t < n; t++) if (h.status[t] != QLDPC_OK) gs->idx.push_back(j.idx[(size_t)t]);
+    gs->any_punct = gs->any_punct || j.any_punct;
+    HIPCHK(hipStreamSynchronize(s));      /* the job's staging set may be written again; this is the recovery path */
+    return QLDPC_OK;
+}
+
+/*
+ * The trial launches of an entry, after the lane's ordinary jobs: S = floor(max_blocks / T) sources a launch in pool order (ascending block index).
+ * Per launch: the known / value rows of the n_src T slots (qk_guess_expand, unchanged), the frame rows replicated onto them (rk_guess_sources), the
+ * loads of a first decode plus qldpc_load_known_dev, the run, rk_guess_crc and rk_guess_settle.  One copy brings the results of all sources back.
+ */
+static int guess_drain(lane_run *L, guess_sources &gs)
+{
+    recon_entry *e = gs.e;
+    const recon_call &c = *L->call;
+    hipStream_t s = L->lane->stream;
+    const int g = c.guess_bits, T = 1 << g, S = L->r->cfg.max_blocks / T, count = (int)gs.idx.size();
+    const int N = e->K + e->M, Wk = e->K / 32, Wn = (N + 31) / 32;
+    const recon_guess_pool_view pool = recon_guess_pool_layout(e->d_gpool, e->gpool_cap, Wk, Wn);
+    uint32_t *res_base = e->d_gpool + pool.words;
+    const recon_bob_view res = recon_bob_layout(res_base, count, Wk);
+    int *d_guess = reinterpret_cast<int *>(res_base + res.words);
+    const guess_trial_view tv = guess_trial_layout(L->r, e);
+    int rc;
+    if ((rc = qldpc_decoder_set_stream(e->dec, (void *)s))) return rc;
+    for (int s0 = 0; s0 < count; s0 += S) {
+        const int ns = std::min(S, count - s0), nf = ns * T;
+        if ((rc = qldpc_guess_expand_dev(N, g, ns, pool.weak + (size_t)s0 * Wn, pool.hard + (size_t)s0 * Wn, tv.known, tv.value, (void *)s))) return rc;
+        hipLaunchKernelGGL(rk_guess_sources, dim3((unsigned)((Wn + RK_LANES - 1) / RK_LANES), (unsigned)ns, (unsigned)std::min(T, 16)), dim3(RK_LANES), 0, s,
+                           pool.bits + (size_t)s0 * Wn, pool.erase + (size_t)s0 * Wn, pool.mag + s0, pool.key_bits + s0, tv.bits, tv.erase, tv.mag, tv.key_bits, Wn, g);
+        HIPCHK(hipGetLastError());
+        if ((rc = qldpc_load_bits_short_dev(e->dec, tv.bits, tv.mag, e->d_cls, tv.key_bits, nf))) return rc;
+        if (gs.any_punct && (rc = qldpc_load_erasures_dev(e->dec, tv.erase, nf))) return rc;
+        if ((rc = qldpc_load_known_dev(e->dec, tv.known, tv.value, nf))) return rc;
+        if ((rc = qldpc_run(e->dec))) return rc;
+        if ((rc = qldpc_fetch_packed_dev(e->dec, e->d_out))) return rc;
+        if ((rc = qldpc_fetch_status_dev(e->dec, e->d_iters, e->d_ok))) return rc;
+        hipLaunchKernelGGL(rk_guess_crc, dim3((unsigned)ns, (unsigned)T), dim3(RK_LANES), 0, s, e->d_out, e->d_ok, pool.key_bits + s0, pool.crc + s0, tv.pass, tv.crc, Wk, Wn);
+        hipLaunchKernelGGL(rk_guess_settle, dim3((unsigned)ns), dim3(RK_LANES), 0, s, e->d_out, e->d_ok, tv.pass, tv.crc, e->d_iters, pool.keys + (size_t)s0 * Wk,
+                           pool.key_bits + s0, pool.iters + s0, res.keys + (size_t)s0 * Wk, res.status + s0, count, d_guess + (size_t)s0 * RG_FIELDS, Wk, Wn, g);
+        HIPCHK(hipGetLastError());
+    }
+    std::vector<uint32_t> back(res.words + (size_t)count * RG_FIELDS);
+    HIPCHK(hipMemcpyAsync(back.data(), res_base, sizeof(uint32_t) * back.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const recon_bob_view h = recon_bob_layout(back.data(), count, Wk);
+    const int *hg = reinterpret_cast<const int *>(back.data() + h.words);
+    for (int k = 0; k < count; k++) {
+        const int i = gs.idx[(size_t)k];
+        c.status[i] = h.status[k];
+        if (c.corrected) c.corrected[i] = h.flips[k];
+        if (c.iterations) c.iterations[i] = h.iters[k];
+        if (h.status[k] == QLDPC_OK) memcpy(c.key[i], h.keys + (size_t)k * Wk, sizeof(uint32_t) * (size_t)((c.key_bits[i] + 31) / 32));      /* without a winner the key stays untouched */
+        const int *f = hg + (size_t)k * RG_FIELDS;
+        qldpc_recon_guess &out = c.guess[i];
+        out.tried = f[0]; out.winner = f[1]; out.n_ok = f[2]; out.n_pass = f[3]; out.ambiguous = f[4]; out.trial_iterations = f[5];
+    }
+    return QLDPC_OK;
+}
+
 static int job_fetch(lane_run *L, recon_job &j, hipStream_t cs)
 {
     recon_entry *e = j.e;
@@ -824,6 +960,7 @@ static int job_fetch(lane_run *L, recon_job &j, hipStream_t cs)
     }
     HIPCHK(hipMemcpyAsync(st->h_res, st->d_res, sizeof(uint32_t) * res_words, hipMemcpyDeviceToHost, cs));
     HIPCHK(hipEventRecord(st->ev_done, cs));
+    if (L->call->bob && L->call->guess_bits) return job_capture(L, j);
     return QLDPC_OK;
 }
 
@@ -923,6 +1060,11 @@ static void lane_main(lane_run *L)
     std::vector<recon_round> rounds;
     for (auto &j : L->jobs) rounds.push_back(recon_round(1, &j));
     L->rc = run_rounds(L, rounds, cs, false, [&](const recon_round &rd) { return job_launch(L, *rd[0], cs); });
+    /* guessing rounds: every ordinary job has reported by now, the trial launches of the entries that had a failure overwrite what they reported */
+    for (auto &gs : L->guess) {
+        if (L->rc) break;
+        if ((L->rc = guess_drain(L, gs))) { L->err = qldpc_last_error(); (void)hipStreamSynchronize(L->lane->stream); }
+    }
     if (dbg) {
         size_t blocks = 0;
         for (auto &j : L->jobs) blocks += j.idx.size();
@@ -1016,7 +1158,10 @@ static int run_call(qldpc_recon *r, const recon_call &call, const std::vector<ch
     if (const char *env = getenv("QLDPC_RECON_LANES")) n_lanes = std::max(1, std::min(RECON_LANES, atoi(env)));
     n_lanes = std::min(n_lanes, (int)groups.size());
     std::sort(groups.begin(), groups.end(), [](const recon_group &a, const recon_group &b) { return a.cost > b.cost; });
-    if (r->gang && call.bob && !call.blind && groups.size() >= 2 && groups.size() <= (size_t)QLDPC_GANG_MAX_MEMBERS) {
+    if (call.bob && call.guess_bits)
+        for (auto &g : groups)
+            if ((rc = entry_guess_pool(r, *g.e, (int)g.idx.size()))) { cache_trim(r); return rc; }
+    if (r->gang && call.bob && !call.blind && !call.guess_bits && groups.size() >= 2 && groups.size() <= (size_t)QLDPC_GANG_MAX_MEMBERS) {
         /* only when every group's decoder can be a member (layered sessions); otherwise today's path */
         std::vector<qldpc_decoder *> decs;
         for (auto &g : groups) decs.push_back(g.e->dec);
@@ -1091,7 +1236,7 @@ extern "C" int qldpc_recon_encode_planned(qldpc_recon *r, const uint32_t *key_wo
 }
 
 /*
- * The Bob-side prologue of block i, shared by qldpc_recon_decode_blocks, qldpc_recon_decode_blind and qldpc_recon_estimate_blocks: QLDPC_EINVAL for a NULL
+ * The Bob-side prologue of block i, shared by qldpc_recon_decode_blocks, qldpc_recon_decode_blind, qldpc_recon_decode_guess and qldpc_recon_estimate_blocks: QLDPC_EINVAL for a NULL
  * key or parity pointer (nothing of the block is written), else the block's outputs at their failure values and *skip = is it left out of the call: its
  * header does not match the block or the local plan, or its QBER is out of range (status QLDPC_ESIZE).  qber_out != NULL is a call that estimates: it has
  * no QBER to check and no status, and zeroes qber_out[i] instead.
@@ -1246,6 +1391,62 @@ extern "C" int qldpc_recon_decode_blind(qldpc_recon *r, int n, uint32_t *const *
         if (leaked) leaked[i] = qldpc_recon_leaked_bits(&msgs[i]) + b.n_known;
     }
     return run_call(r, c, skip);
+}
+
+/*
+ * qldpc_recon_decode_blocks with guessing rounds: a block whose first decode ends QLDPC_EDECODE is decoded again with its guess_bits weakest key
+ * positions pinned to each of the 2^guess_bits values, and the lowest trial with a zero syndrome and Alice's CRC is kept (qldpc_recon_guess_core.h).
+ * Local to Bob, nothing is disclosed.  guess_bits = 0, or a call without a failed block, is qldpc_recon_decode_blocks: a guessing call waits for the
+ * results of a job before it launches the next one of the lane (the wait job_finish makes), and only a job with a failure queues anything more
+ * (job_capture); the trial launches follow the lane's ordinary jobs (guess_drain).  The gang path is not taken by these calls.
+ */
+extern "C" int qldpc_recon_decode_guess(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber, const qldpc_recon_msg *msgs,
+                                        const uint32_t *const *parity_words, int guess_bits, qldpc_recon_guess *guess, int *status, int *corrected, int *iterations)
+{
+    if (!r || !key_words || !key_bits || !qber || !msgs || !parity_words || !status || n <= 0) return QLDPC_EINVAL;
+    if (guess_bits > 0 && !guess) { qldpc_set_error("recon_decode_guess: guess_bits = %d needs the guess array (one qldpc_recon_guess per block)", guess_bits); return QLDPC_EINVAL; }
+    if (guess_bits < 0 || guess_bits > QLDPC_GUESS_MAX_BITS) {
+        qldpc_set_error("recon_decode_guess: guess_bits = %d, outside 0 .. %d", guess_bits, QLDPC_GUESS_MAX_BITS);
+        return QLDPC_ESIZE;
+    }
+    if ((1 << guess_bits) > r->cfg.max_blocks) {
+        qldpc_set_error("recon_decode_guess: the %d trials of a block do not fit a launch of max_blocks = %d frames: lower guess_bits or make the session with max_blocks >= %d",
+                        1 << guess_bits, r->cfg.max_blocks, 1 << guess_bits);
+        return QLDPC_ESIZE;
+    }
+    if (!cfg_layered(r->cfg) && r->cfg.max_blocks <= 8) {
+        qldpc_set_error("recon_decode_guess: the decoders of a session with max_blocks <= 8 and the flooding schedule run on the edge-parallel engine, which has no weakest-VN select: make the session with max_blocks > 8 or the horizontal-layered schedule");
+        return QLDPC_EUNSUPPORTED;
+    }
+    recon_call c = call_bob(n, key_words, key_bits, qber, msgs, parity_words, status, corrected, iterations);
+    c.guess = guess; c.guess_bits = guess_bits;
+    std::vector<char> skip((size_t)n, 0);
+    for (int i = 0; i < n; i++) {
+        if (int rc = bob_block_begin(r, c, i, nullptr, &skip[(size_t)i])) return rc;
+        if (guess) { const qldpc_recon_guess none = {0, -1, 0, 0, 0, 0}; guess[i] = none; }
+    }
+    return run_call(r, c, skip);
+}
+
+/* the verdict over trial rows that lie on the device (rk_guess_crc + rk_guess_settle), what guess_drain queues per trial launch: synthetic rows can be settled without a decode */
+extern "C" int qldpc_recon_guess_settle_dev(int g, int n_src, int Wk, int Wn, const uint32_t *d_trial_rows, const int *d_ok, const int *d_iters, const uint32_t *d_keys,
+                                            const int *d_key_bits, const uint32_t *d_crc_want, const int *d_first_iters, int *d_pass_out, uint32_t *d_crc_out,
+                                            uint32_t *d_res_keys, int *d_res, int *d_guess, void *hip_stream)
+{
+    if (!d_trial_rows || !d_ok || !d_iters || !d_keys || !d_key_bits || !d_crc_want || !d_first_iters || !d_pass_out || !d_crc_out || !d_res_keys || !d_res || !d_guess)
+        return QLDPC_EINVAL;
+    if (g < 0 || g > GS_MAX_BITS || n_src < 0 || Wk < 1 || Wn < Wk || ((uint64_t)n_src << g) > GS_MAX_SLOTS) {
+        qldpc_set_error("recon_guess_settle: guess bits=%d (0 .. %d), n_src=%d (not negative, n_src 2^g <= %u), key row of %d words (at least 1) in trial rows of %d",
+                        g, GS_MAX_BITS, n_src, GS_MAX_SLOTS, Wk, Wn);
+        return QLDPC_ESIZE;
+    }
+    if (n_src == 0) return QLDPC_OK;
+    hipStream_t s = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(rk_guess_crc, dim3((unsigned)n_src, 1u << g), dim3(RK_LANES), 0, s, d_trial_rows, d_ok, d_key_bits, d_crc_want, d_pass_out, d_crc_out, Wk, Wn);
+    hipLaunchKernelGGL(rk_guess_settle, dim3((unsigned)n_src), dim3(RK_LANES), 0, s, d_trial_rows, d_ok, d_pass_out, d_crc_out, d_iters, d_keys, d_key_bits, d_first_iters,
+                       d_res_keys, d_res, n_src, d_guess, Wk, Wn, g);
+    HIPCHK(hipGetLastError());
+    return QLDPC_OK;
 }
 
 /* n blocks of ONE length, contiguous arrays (the config-3 stream driver's call); parity_words rows are ceil(code_m / 32) words apart */
