@@ -512,6 +512,12 @@ extern "C" int qldpc_decoder_create(const qldpc_code *code, int K, const int *in
                         "(have engine=%d, msg_dtype=%d, layer_chain=%d, compact=%d)", cfg->engine, cfg->msg_dtype, cfg->layer_chain, cfg->compact);
         return QLDPC_EUNSUPPORTED;
     }
+    /* the SPA fold of the FRAMES engine keeps prod (1 + e^-|x_j|) <= 2^dc in fp32 (qldpc_kernels.h): from degree 128 on it overflows and every edge of the check
+     * gets the clamp.  The edge engine stops at degree 64, so such a code always comes here. */
+    if (cfg->rule == QLDPC_RULE_SPA && code->max_dc >= 128) {
+        qldpc_set_error("SPA is built for check degrees below 128 (have %d): its product of dc factors overflows fp32 beyond that; use QLDPC_RULE_LSPA, which has no product", code->max_dc);
+        return QLDPC_EUNSUPPORTED;
+    }
     qldpc_decoder *d = new (std::nothrow) qldpc_decoder();
     if (!d) return QLDPC_ENOMEM;
     int rc = create_impl(code, K, info_bits_pos, cfg, d);

@@ -123,7 +123,7 @@ __device__ __forceinline__ void qe_cn_chunk(int f, int chunk, int *s_idx, float 
                 s_val[off + s] = qk_withsign((fabsf(x) == m1) ? cst1 : cst2, sg ^ qk_bits(x));      /* sg already folds s_c in */
             }
         } else {   /* SPA: the product is reduced as a tree, so it is tolerance-class (not order-exact) */
-            const float t = act ? qk_tanh_half(fabsf(x)) : 1.0f;
+            const float t = act ? qk_tanh_half(fabsf(x)) : 1.0f;      /* domain x = 0 or |x| >= 2^-24: below that t is 0, an erased edge (qldpc_kernels.h, "SPA on exponentials") */
             float prod = t;
             uint32_t sg = (act ? (qk_bits(x) & 0x80000000u) : 0u) ^ (sc << 31);
 #pragma unroll
