@@ -98,7 +98,7 @@ typedef enum qldpc_schedule {
  *   FRAMES  frame-interleaved: a wavefront lane = a frame; thousands of frames per launch (HBM-bound)
  *   EDGES   edge-parallel: lanes run over the edges of ONE frame, check groups staged in LDS, min/sign
  *           fold by wavefront shuffles; the daemon's one-block-at-a-time case (flooding; MS/OMS/NMS/SPA;
- *           check degree <= 64)
+ *           check degree <= 64, VN degree <= 32)
  */
 typedef enum qldpc_engine { QLDPC_ENGINE_AUTO = 0, QLDPC_ENGINE_FRAMES = 1, QLDPC_ENGINE_EDGES = 2 } qldpc_engine;
 

@@ -263,7 +263,7 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
         int eng = cfg->engine;
         if (const char *e = getenv("QLDPC_ENGINE")) { int x = atoi(e); if (x >= 0 && x <= 2) eng = x; }
         if (eng == QLDPC_ENGINE_EDGES && !edge_ok) {
-            qldpc_set_error("edge-parallel engine needs flooding, MS/OMS/NMS/SPA, check degree <= 64 (have %d) and VN degree <= 64 (have %d)", code->max_dc, code->max_dv);
+            qldpc_set_error("edge-parallel engine needs flooding, MS/OMS/NMS/SPA, check degree <= 64 (have %d) and VN degree <= %d (have %d)", code->max_dc, edge_max_dv(), code->max_dv);
             return QLDPC_EUNSUPPORTED;
         }
         if (cfg->giveup_patience > 0) {      /* the syndrome weights are counted by the FRAMES engine's test */

@@ -15,10 +15,12 @@
 #include "qldpc_engine_int.h"
 #include "qldpc_kernels_edge.h"
 
+/* the largest VN degree: a chunk of QE_THREADS VNs stages QE_THREADS * max_dv messages in 64 KiB of LDS */
+int edge_max_dv(void) { return (int)(64 * 1024 / (QE_THREADS * sizeof(float))); }
+
 bool edge_supports(const qldpc_decoder_cfg *cfg, const qldpc_code *code)
 {
-    return cfg->schedule == QLDPC_SCHED_FLOODING && cfg->rule <= QLDPC_RULE_SPA && code->max_dc <= 64 &&
-           (size_t)QE_THREADS * (size_t)code->max_dv * sizeof(float) <= 64 * 1024;
+    return cfg->schedule == QLDPC_SCHED_FLOODING && cfg->rule <= QLDPC_RULE_SPA && code->max_dc <= 64 && code->max_dv <= edge_max_dv();
 }
 
 int edge_create(qldpc_decoder *d, const qldpc_code *code)

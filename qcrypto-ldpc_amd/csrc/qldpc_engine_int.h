@@ -262,6 +262,7 @@ static inline double bytes_vn(const qldpc_decoder *d, int mode)
  */
 #pragma GCC visibility push(hidden)
 bool edge_supports(const qldpc_decoder_cfg *cfg, const qldpc_code *code);      /* flooding, MS / OMS / NMS / SPA, degrees its kernels hold */
+int edge_max_dv(void);                                                         /* the largest VN degree among them (the refusal names it) */
 int edge_create(qldpc_decoder *d, const qldpc_code *code);
 void edge_destroy(qldpc_decoder *d);
 int edge_load_llr(qldpc_decoder *d, const float *d_llr);
