@@ -35,6 +35,7 @@
  *   qldpc_privamp*                        the hash loop of privAmp_doPrivAmp         subcomponents/priv_amp.c:190-218
  *   qldpc_toeplitz*                       (not in the reference) Toeplitz hashing, the sound replacement of that loop
  *   qldpc_polyhash*                       (not in the reference) error verification by a universal hash, beside the sessions' CRC-32
+ *   qldpc_recon_*_tagged / _tag_blocks    (not in the reference) the same tag inside Bob's verify step, over his decoded rows on the device
  *   qldpc_qber_* / _recon_estimate_blocks (not in the reference, which samples disclosed bits: subcomponents/qber_estim.c) the QBER out of the parity message
  *   qldpc_mc_*                            the simulation loop itself: source, encoder, BSC, decoder, Monitor_BFER   BS/src/main.cpp:335-393
  *   qldpc_mc_search / _patterns_dev       the puncture-pattern search around it: shuffle, erase, first FER = 0 / n  BS/src/main.cpp:235-411
@@ -587,8 +588,8 @@ int qldpc_recon_disclose_host(const uint32_t *key_words, int key_bits, const int
  *   invariance  everything about a block is a function of the block, the session configuration and guess_bits: not of the other blocks of the call,
  *               of max_blocks (while T <= max_blocks) or of how the sources fall into trial launches.
  *   leak        qldpc_recon_leaked_bits(&msgs[i]) is unchanged: nothing is disclosed.  But the CRC now selects among up to n_ok zero-syndrome
- *               candidates, so the chance of accepting a wrong key is at most n_ok 2^-32 per block instead of 2^-32; qldpc_polyhash_* is the check
- *               for callers who need a bound.
+ *               candidates, so the chance of accepting a wrong key is at most n_ok 2^-32 per block instead of 2^-32; the keyed tag is the check
+ *               for callers who need a bound: qldpc_recon_decode_guess_tagged below computes it in the same call.
  * Refused before anything is decoded: QLDPC_EINVAL for a missing pointer, or guess == NULL with guess_bits > 0; QLDPC_ESIZE for guess_bits outside
  * 0 .. QLDPC_GUESS_MAX_BITS or 2^guess_bits > max_blocks (lower guess_bits or raise max_blocks); QLDPC_EUNSUPPORTED, as qldpc_recon_decode_blind, for a
  * session on the edge-parallel engine (max_blocks <= 8 with the flooding schedule) -- and, from the run, for a flooding run that compacted its frames.
@@ -622,6 +623,61 @@ int qldpc_recon_guess_settle_dev(int g, int n_src, int Wk, int Wn, const uint32_
 int qldpc_recon_guess_settle_host(int g, int n_src, int Wk, int Wn, const uint32_t *trial_rows, const int *ok, const int *iters, const uint32_t *keys,
                                   const int *key_bits, const uint32_t *crc_want, const int *first_iters, int *pass_out, uint32_t *crc_out, uint32_t *res_keys,
                                   int *res, int *guess);
+/*
+ * Keyed universal-hash tags inside Bob's verify step.  The CRC-32 that accepts a decoded block has no key and bounds nothing (and a guessing call lets
+ * it choose among up to n_ok candidates); the hash that gives a bound is the one of qldpc_polyhash_* below, (W + 2) 2^-61 per key.  These calls
+ * compute exactly that tag -- tag = k (k H + n) mod 2^61 - 1 with H the Horner value of the masked words, hi word then lo word, n_keys = r in 1 .. 4
+ * values key after key -- over Bob's decoded rows where they lie on the device, in the pass that computes the CRC (csrc/qldpc_recon_tag_core.h,
+ * csrc/qldpc_kernels_recon_tag.h).  Equal tags on both sides bound the chance that the keys differ; the CRC stays what it was, a cheap pre-check.
+ *
+ * THE HASH KEY IS THE CALLER'S AND MUST BE DRAWN AFTER THE PARITY MESSAGE HAS ARRIVED.  The library cannot check that.  Passing the key into the
+ * decode call is sound for this reason: Bob holds Alice's message when he calls, so the blocks are fixed before he draws the key; he then sends the
+ * key (and his tags, or their comparison) to Alice, who tags her keys with qldpc_recon_tag_blocks.
+ *
+ *   qldpc_recon_decode_blocks_tagged   qldpc_recon_decode_blocks -- the same validation, grouping, lanes, staging sets and pipeline, on either engine
+ *               -- with the verdict kernel also hashing.  hash_keys[i] = block i's 2 n_keys key words (when all n pointers are equal the row is
+ *               uploaded once a launch and shared), tag_words[i] = 2 n_keys words out.  status, keys, corrected and iterations are those of
+ *               qldpc_recon_decode_blocks.  A block that ends QLDPC_OK gets the tag of the key returned; every other block (failed, or left out with
+ *               QLDPC_ESIZE) gets zeros: nothing is disclosed for it.  The hash keys travel with a launch's input block and the tags with its result
+ *               block; the staging of a session entry has the room from its creation, so a preloaded session allocates nothing in a call.
+ *   qldpc_recon_decode_guess_tagged    qldpc_recon_decode_guess likewise (every field of qldpc_recon_guess as there): a block decoded at once is tagged
+ *               by the verdict kernel, a rescued block gets the tag of the winner's key, a block still failed zeros.  guess_bits = 0 is
+ *               qldpc_recon_decode_blocks_tagged.  Refusals: those of qldpc_recon_decode_guess, then those below.
+ *   qldpc_recon_tag_blocks             the tags of host keys, for either side; only the length of a block matters (1 .. 2^18 bits, QLDPC_ESIZE
+ *               outside), there is no plan and no message.  Launches of at most max_blocks rows through a staging block of the session (allocated
+ *               with a preloaded session for blocks of up to mother_max bits, else by the first call that needs it, again when a call needs more).
+ *   qldpc_recon_verify_tag_dev         the verdict kernel alone over device pointers, so that synthetic rows can be verified without a decode:
+ *               d_out_rows [n][Wn] decoded rows, d_keys [n][Wk] the keys handed in, d_key_bits (1 .. 32 Wk: the caller's business, the kernel
+ *               clamps), d_crc_want, d_ok, d_iters [n], d_hash_keys rows of 2 n_keys words hash_key_stride words apart (0: every block reads row
+ *               0) -> d_res_keys [n][Wk] (words past a key's length are not written), d_res [4][n] = status | corrected | iterations | CRC found,
+ *               d_tags [n][2 n_keys].  Asynchronous on hip_stream, on the current device.  qldpc_recon_verify_tag_host is its mirror on host
+ *               pointers, no device needed; it also refuses a key_bits outside 1 .. 32 Wk.  Both: QLDPC_ESIZE for n < 0, Wk < 1, Wn < Wk or a
+ *               stride in 1 .. 2 n_keys - 1.
+ *   qldpc_recon_tag_host               one tag of one block under one key by the kernels' decomposition with `lanes` lanes (a power of two; the
+ *               kernels: 256): equal to qldpc_polyhash_host for every such lanes.
+ *   qldpc_recon_leaked_bits_tagged     qldpc_recon_leaked_bits(msg) + 61 n_keys: the conservative account, charging both the CRC and the tags;
+ *               0 on a bad argument.
+ * Argument checks run before anything is queued or written, and qldpc_last_error() names the block: n_keys outside 1 .. 4, a NULL hash_keys[i] or
+ * tag_words[i] (or array) are QLDPC_EINVAL.
+ * Left out on purpose: tags in qldpc_recon_decode_blind, qldpc_recon_decode_batch and the one-block qldpc_recon_decode; a tag field in qldpc_recon_msg;
+ * the daemon packet; a one-time pad of the tag; gangs (with QLDPC_RECON_GANG=1 a tagged call decodes on the ordinary lanes, as the blind and guessing
+ * calls do).
+ */
+int qldpc_recon_decode_blocks_tagged(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber, const qldpc_recon_msg *msgs,
+                                     const uint32_t *const *parity_words, int n_keys, const uint32_t *const *hash_keys, uint32_t *const *tag_words,
+                                     int *status, int *corrected, int *iterations);
+int qldpc_recon_decode_guess_tagged(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber, const qldpc_recon_msg *msgs,
+                                    const uint32_t *const *parity_words, int guess_bits, qldpc_recon_guess *guess, int n_keys,
+                                    const uint32_t *const *hash_keys, uint32_t *const *tag_words, int *status, int *corrected, int *iterations);
+int qldpc_recon_tag_blocks(qldpc_recon *r, int n, const uint32_t *const *key_words, const int *key_bits, int n_keys, const uint32_t *const *hash_keys,
+                           uint32_t *const *tag_words);
+int qldpc_recon_verify_tag_dev(int n, int n_keys, int Wk, int Wn, const uint32_t *d_out_rows, const uint32_t *d_keys, const int *d_key_bits,
+                               const uint32_t *d_crc_want, const int *d_ok, const int *d_iters, const uint32_t *d_hash_keys, size_t hash_key_stride,
+                               uint32_t *d_res_keys, int *d_res, uint32_t *d_tags, void *hip_stream);
+int qldpc_recon_verify_tag_host(int n, int n_keys, int Wk, int Wn, const uint32_t *out_rows, const uint32_t *keys, const int *key_bits, const uint32_t *crc_want,
+                                const int *ok, const int *iters, const uint32_t *hash_keys, size_t hash_key_stride, uint32_t *res_keys, int *res, uint32_t *tags);
+int qldpc_recon_tag_host(const uint32_t *key_words, int key_bits, const uint32_t hash_key[2], int lanes, uint32_t tag[2]);
+int qldpc_recon_leaked_bits_tagged(const qldpc_recon_msg *msg, int n_keys);
 /*
  * Bob's QBER estimate of every block out of its parity message (qldpc_qber_* below), before anything is decoded: the blocks are validated, grouped by
  * code and assembled into frames exactly as qldpc_recon_decode_blocks does it (key VNs channel, shortened past key_bits, disclosed parity pinned,
@@ -888,8 +944,9 @@ uint32_t qldpc_toeplitz_ntt_root_host(int log2_len);
  * the same context to have run.  All blocks of a call go in one launch; a block of more than tile_words coefficients is split over
  * several workgroups, and a second launch on the same stream then folds their partials.  The tag does not depend on tile_words.
  *
- * Not built: the tag inside the sessions' verify step (which would hash Bob's decoded rows where they lie), qldpc_recon_msg carrying a
- * tag, the daemon packet, a one-time pad of the tag, GF(2^128) families, truncated tags.
+ * The sessions compute the same tag inside Bob's verify step, over his decoded rows where they lie on the device: qldpc_recon_decode_blocks_tagged,
+ * qldpc_recon_decode_guess_tagged and qldpc_recon_tag_blocks above.
+ * Not built: qldpc_recon_msg carrying a tag, the daemon packet, a one-time pad of the tag, GF(2^128) families, truncated tags.
  */
 #define QLDPC_POLYHASH_PRIME 0x1FFFFFFFFFFFFFFFull
 #define QLDPC_POLYHASH_TILE_WORDS 8192         /* coefficients per workgroup of the production instance */

@@ -73,6 +73,8 @@ struct qldpc_recon {
     long created;                   /* entries built so far (tests: nothing is built after a preload) */
     recon_lane lane[RECON_LANES];
     int profiling;
+    uint32_t *h_tag, *d_tag;        /* qldpc_recon_tag_blocks: the staging block of a launch (recon_tag_layout), pinned and on the device: with the session when it preloads, else at the first such call */
+    size_t tag_words;               /* ... and the words each holds */
     int gang;                       /* QLDPC_RECON_GANG=1 when the session was made: Bob-side calls with several layered rate groups decode in rounds, one gang run each (run_call_gang) */
 };
 
@@ -174,6 +176,7 @@ __global__ __launch_bounds__(RK_LANES) void rk_crc(const uint32_t *__restrict__ 
 }
 
 #include "qldpc_kernels_recon_guess.h"
+#include "qldpc_kernels_recon_tag.h"
 
 extern "C" void qldpc_recon_cfg_default(qldpc_recon_cfg *c)
 {
@@ -275,6 +278,8 @@ extern "C" void qldpc_recon_free(qldpc_recon *r)
     if (!r) return;
     (void)hipSetDevice(r->cfg.device);
     for (auto &e : r->cache) entry_free(e);
+    (void)hipFree(r->d_tag);
+    if (r->h_tag) (void)hipHostFree(r->h_tag);
     for (auto &l : r->lane) {
         if (l.stream) (void)hipStreamDestroy(l.stream);
         if (l.copy) (void)hipStreamDestroy(l.copy);
@@ -296,6 +301,7 @@ static void code_dims(const qldpc_recon_cfg &c, int key_bits, double R, int *K, 
 
 static int get_entry(qldpc_recon *r, int K, int M, recon_entry **out, qldpc_code *prebuilt = nullptr);
 static int build_code(const qldpc_recon_cfg &cfg, int K, int M, qldpc_code **out);
+static int tag_stage_reserve(qldpc_recon *r, size_t words);
 static void cache_trim(qldpc_recon *r)
 {
     if (r->cache.size() <= r->keep) return;
@@ -332,6 +338,7 @@ extern "C" int qldpc_recon_create(const qldpc_recon_cfg *cfg, qldpc_recon **out)
     r->created = 0;
     r->profiling = 0;
     r->gang = 0;
+    r->h_tag = r->d_tag = nullptr; r->tag_words = 0;
     if (const char *env = getenv("QLDPC_RECON_GANG")) r->gang = atoi(env) == 1;
     memset(r->lane, 0, sizeof(r->lane));
     if (hipSetDevice(cfg->device) != hipSuccess) { delete r; return QLDPC_EHIP; }
@@ -388,6 +395,8 @@ extern "C" int qldpc_recon_create(const qldpc_recon_cfg *cfg, qldpc_recon **out)
             recon_entry *e;
             rc = get_entry(r, t.K, t.M, &e, t.code);      /* takes the code over (also on failure: entry_free) */
         }
+        /* ... and the staging of qldpc_recon_tag_blocks for launches of max_blocks keys of up to mother_max bits under RT_MAX_KEYS keys */
+        if (!rc) rc = tag_stage_reserve(r, recon_tag_layout(nullptr, cfg->max_blocks, cfg->mother_max / 32, RT_MAX_KEYS).words);
         if (rc) { qldpc_recon_free(r); return rc; }
     }
     *out = r;
@@ -562,8 +571,10 @@ static int get_entry(qldpc_recon *r, int K, int M, recon_entry **out, qldpc_code
     alloc((void **)&e.d_iters, sizeof(int) * (size_t)B);
     alloc((void **)&e.d_ok, sizeof(int) * (size_t)B);
     /* a full job's staging blocks; an entry serves both sides, so the result block holds the larger of the two layouts */
-    const size_t in_words = recon_in_layout(nullptr, B, Wk, Wm).words;
-    const size_t res_words = std::max(recon_bob_layout(nullptr, B, Wk).words, recon_alice_layout(nullptr, B, Wm).words);
+    /* a tagged call appends the hash-key rows of its blocks to the input block and receives their tags behind the result block: room for RT_MAX_KEYS keys a block */
+    const size_t tag_room = (size_t)B * 2 * RT_MAX_KEYS;
+    const size_t in_words = recon_in_layout(nullptr, B, Wk, Wm).words + tag_room;
+    const size_t res_words = std::max(recon_bob_layout(nullptr, B, Wk).words, recon_alice_layout(nullptr, B, Wm).words) + tag_room;
     for (auto &st : e.set) {
         alloc((void **)&st.d_in, sizeof(uint32_t) * in_words);
         alloc((void **)&st.d_res, sizeof(uint32_t) * res_words);
@@ -615,6 +626,11 @@ extern "C" int qldpc_recon_check_header(const qldpc_recon *r, const qldpc_recon_
 
 extern "C" int qldpc_recon_parity_words(const qldpc_recon_msg *msg) { return msg ? (int)((msg->code_m - msg->n_punct + 31) / 32) : QLDPC_EINVAL; }
 extern "C" int qldpc_recon_leaked_bits(const qldpc_recon_msg *msg) { return msg ? (int)(msg->code_m - msg->n_punct) + 32 : QLDPC_EINVAL; }
+/* the conservative account of a tagged block: the CRC and every key's tag are both charged; 0 on a bad argument */
+extern "C" int qldpc_recon_leaked_bits_tagged(const qldpc_recon_msg *msg, int n_keys)
+{
+    return msg && n_keys >= 1 && n_keys <= RT_MAX_KEYS ? qldpc_recon_leaked_bits(msg) + RT_TAG_BITS * n_keys : 0;
+}
 
 /* ------------------------------------------------------------------ the pipeline ------------------------------------------------
  *
@@ -645,6 +661,7 @@ struct recon_call {
     uint32_t *const *key; const float *qber; const qldpc_recon_msg *msgs; const uint32_t *const *parity; int *status, *corrected, *iterations;
     qldpc_recon_blind *blind; int ask_bits;      /* != NULL: a blind round (qldpc_recon_decode_blind) */
     qldpc_recon_guess *guess; int guess_bits;    /* guess_bits > 0: a call with guessing rounds (qldpc_recon_decode_guess) */
+    int n_keys; const uint32_t *const *hash_keys; uint32_t *const *tags; bool hash_shared;      /* n_keys > 0: a tagged call (qldpc_recon_decode_blocks_tagged, _decode_guess_tagged); hash_shared: one key row for all blocks */
     /* Alice */
     const uint32_t *const *akey; qldpc_recon_msg *amsgs; uint32_t *const *aparity;
 };
@@ -724,7 +741,13 @@ static int job_stage(lane_run *L, recon_job &j, hipStream_t cs)
         h.key_bits[t] = kb;
         j.any_punct = j.any_punct || h.n_punct[t] != 0;
     }
-    HIPCHK(hipMemcpyAsync(st->d_in, st->h_in, sizeof(uint32_t) * h.words, hipMemcpyHostToDevice, cs));
+    size_t in_words = h.words;
+    if (c.bob && c.n_keys) {      /* the hash-key rows travel behind the block, in the same copy: one row when the blocks share it */
+        const size_t row = 2 * (size_t)c.n_keys;
+        for (int t = 0; t < (c.hash_shared ? 1 : n); t++) memcpy(st->h_in + h.words + (size_t)t * row, c.hash_keys[j.idx[(size_t)t]], sizeof(uint32_t) * row);
+        in_words += (c.hash_shared ? 1 : (size_t)n) * row;
+    }
+    HIPCHK(hipMemcpyAsync(st->d_in, st->h_in, sizeof(uint32_t) * in_words, hipMemcpyHostToDevice, cs));
     if (c.bob) {
         hipLaunchKernelGGL(rk_assemble, dim3((unsigned)((Wn + 255) / 256), (unsigned)n), dim3(256), 0, cs, d.keys, d.disc, d.key_bits, d.n_punct, st->d_bits, st->d_erase, Wk, Wn, Wm, M);
         HIPCHK(hipGetLastError());
@@ -807,7 +830,8 @@ static int entry_guess_pool(const qldpc_recon *r, recon_entry &e, int sources)
     if (e.gpool_cap >= cap) return QLDPC_OK;
     (void)hipFree(e.d_gpool);
     e.d_gpool = nullptr; e.gpool_cap = 0;
-    const size_t words = recon_guess_pool_layout(nullptr, cap, (int)Wk, (int)Wn).words + recon_bob_layout(nullptr, cap, (int)Wk).words + (size_t)cap * RG_FIELDS;
+    /* ... then, for a tagged call, the tags and the hash-key rows of the sources: room for RT_MAX_KEYS keys each */
+    const size_t words = recon_guess_pool_layout(nullptr, cap, (int)Wk, (int)Wn).words + recon_bob_layout(nullptr, cap, (int)Wk).words + (size_t)cap * RG_FIELDS + (size_t)cap * 4 * RT_MAX_KEYS;
     if (hipMalloc((void **)&e.d_gpool, sizeof(uint32_t) * words) != hipSuccess) { qldpc_set_error("recon_decode_guess: device allocation failed"); return QLDPC_ENOMEM; }
     e.gpool_cap = cap;
     return QLDPC_OK;
@@ -900,7 +924,19 @@ static int guess_drain(lane_run *L, guess_sources &gs)
                            pool.key_bits + s0, pool.iters + s0, res.keys + (size_t)s0 * Wk, res.status + s0, count, d_guess + (size_t)s0 * RG_FIELDS, Wk, Wn, g);
         HIPCHK(hipGetLastError());
     }
-    std::vector<uint32_t> back(res.words + (size_t)count * RG_FIELDS);
+    const size_t tag_row = 2 * (size_t)c.n_keys;
+    if (c.n_keys) {
+        /* the tag of every rescued block, over the winners' keys where rk_guess_settle left them: the status column is the skip column, so a block
+         * still failed gets zeros.  The tags lie behind the guess ints and travel back with them, the hash-key rows of the sources behind the tags */
+        uint32_t *d_tags = res_base + res.words + (size_t)count * RG_FIELDS, *d_hk = d_tags + (size_t)count * tag_row;
+        std::vector<uint32_t> hk((c.hash_shared ? 1 : (size_t)count) * tag_row);
+        for (size_t k = 0; k * tag_row < hk.size(); k++) memcpy(hk.data() + k * tag_row, c.hash_keys[gs.idx[k]], sizeof(uint32_t) * tag_row);
+        HIPCHK(hipMemcpyAsync(d_hk, hk.data(), sizeof(uint32_t) * hk.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));      /* hk is this scope's */
+        rk_tag_launch(c.n_keys, count, s, res.keys, pool.key_bits, res.status, d_hk, c.hash_shared ? 0 : tag_row, d_tags, Wk);
+        HIPCHK(hipGetLastError());
+    }
+    std::vector<uint32_t> back(res.words + (size_t)count * RG_FIELDS + (size_t)count * tag_row);
     HIPCHK(hipMemcpyAsync(back.data(), res_base, sizeof(uint32_t) * back.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     const recon_bob_view h = recon_bob_layout(back.data(), count, Wk);
@@ -914,6 +950,7 @@ static int guess_drain(lane_run *L, guess_sources &gs)
         const int *f = hg + (size_t)k * RG_FIELDS;
         qldpc_recon_guess &out = c.guess[i];
         out.tried = f[0]; out.winner = f[1]; out.n_ok = f[2]; out.n_pass = f[3]; out.ambiguous = f[4]; out.trial_iterations = f[5];
+        if (c.n_keys) memcpy(c.tags[i], back.data() + h.words + (size_t)count * RG_FIELDS + (size_t)k * tag_row, sizeof(uint32_t) * tag_row);
     }
     return QLDPC_OK;
 }
@@ -932,9 +969,14 @@ static int job_fetch(lane_run *L, recon_job &j, hipStream_t cs)
         if ((rc = qldpc_fetch_packed_dev(e->dec, e->d_out))) return rc;
         if ((rc = qldpc_fetch_status_dev(e->dec, e->d_iters, e->d_ok))) return rc;
         const recon_bob_view res = job_bob_res(j, st->d_res);
-        hipLaunchKernelGGL(rk_verify, dim3((unsigned)n), dim3(RK_LANES), 0, s, e->d_out, d.keys, d.key_bits, d.crc, e->d_ok, e->d_iters, res.keys, res.status, n, Wk, Wn);
-        HIPCHK(hipGetLastError());
         res_words = res.words;
+        if (const int r = L->call->n_keys) {      /* the same verdict with the tags of the good blocks, behind the result block: they travel back with it */
+            rk_verify_tag_launch(r, n, s, e->d_out, d.keys, d.key_bits, d.crc, e->d_ok, e->d_iters, st->d_in + d.words, L->call->hash_shared ? 0 : 2 * (size_t)r,
+                                 res.keys, res.status, st->d_res + res.words, Wk, Wn);
+            res_words += (size_t)n * 2 * (size_t)r;
+        } else
+            hipLaunchKernelGGL(rk_verify, dim3((unsigned)n), dim3(RK_LANES), 0, s, e->d_out, d.keys, d.key_bits, d.crc, e->d_ok, e->d_iters, res.keys, res.status, n, Wk, Wn);
+        HIPCHK(hipGetLastError());
         if (L->call->blind) {
             /* the request of every block that failed: its ask_bits weakest candidates, out of the posteriors of this decode.  The status column
              * rk_verify just wrote is the take column (QLDPC_OK = 0 = not wanted).  The rows are waited for here: a blind round gives up the
@@ -987,6 +1029,7 @@ static int job_finish(lane_run *L, recon_job &j)
             if (c.corrected) c.corrected[i] = res.flips[t];
             if (c.iterations) c.iterations[i] = res.iters[t];
             if (res.status[t] == QLDPC_OK) memcpy(c.key[i], res.keys + (size_t)t * Wk, sizeof(uint32_t) * (size_t)Wkey);      /* a failed block keeps its key untouched */
+            if (c.n_keys) memcpy(c.tags[i], st->h_res + res.words + (size_t)t * 2 * (size_t)c.n_keys, sizeof(uint32_t) * 2 * (size_t)c.n_keys);      /* zeros for a failed block */
             if (c.blind) {
                 qldpc_recon_blind &b = c.blind[i];
                 b.n_ask = 0;
@@ -1161,7 +1204,7 @@ static int run_call(qldpc_recon *r, const recon_call &call, const std::vector<ch
     if (call.bob && call.guess_bits)
         for (auto &g : groups)
             if ((rc = entry_guess_pool(r, *g.e, (int)g.idx.size()))) { cache_trim(r); return rc; }
-    if (r->gang && call.bob && !call.blind && !call.guess_bits && groups.size() >= 2 && groups.size() <= (size_t)QLDPC_GANG_MAX_MEMBERS) {
+    if (r->gang && call.bob && !call.blind && !call.guess_bits && !call.n_keys && groups.size() >= 2 && groups.size() <= (size_t)QLDPC_GANG_MAX_MEMBERS) {
         /* only when every group's decoder can be a member (layered sessions); otherwise today's path */
         std::vector<qldpc_decoder *> decs;
         for (auto &g : groups) decs.push_back(g.e->dec);
@@ -1256,22 +1299,63 @@ static int bob_block_begin(const qldpc_recon *r, const recon_call &c, int i, flo
 }
 
 /*
+ * The tag arguments of a tagged Bob-side call, checked before anything is queued or written: n_keys outside 1 .. RT_MAX_KEYS and a NULL hash-key or tag
+ * row are QLDPC_EINVAL, and the error names the block (a NULL key or parity row is refused here as well, before a tag row is written).  Then the call
+ * carries them, with hash_shared = every block points to one row; every block's tag starts as zeros, which is what a block that is left out or fails keeps.
+ */
+static int call_take_tags(const char *who, recon_call &c, int n_keys, const uint32_t *const *hash_keys, uint32_t *const *tag_words)
+{
+    if (n_keys < 1 || n_keys > RT_MAX_KEYS) { qldpc_set_error("%s: n_keys = %d, outside 1 .. %d", who, n_keys, RT_MAX_KEYS); return QLDPC_EINVAL; }
+    if (!hash_keys || !tag_words) { qldpc_set_error("%s: the hash_keys and tag_words arrays are needed", who); return QLDPC_EINVAL; }
+    bool shared = true;
+    for (int i = 0; i < c.n; i++) {
+        if (!c.key[i] || !c.parity[i]) return QLDPC_EINVAL;
+        if (!hash_keys[i] || !tag_words[i]) { qldpc_set_error("%s: block %d has no %s row", who, i, !hash_keys[i] ? "hash-key" : "tag"); return QLDPC_EINVAL; }
+        shared = shared && hash_keys[i] == hash_keys[0];
+    }
+    for (int i = 0; i < c.n; i++) memset(tag_words[i], 0, sizeof(uint32_t) * 2 * (size_t)n_keys);
+    c.n_keys = n_keys; c.hash_keys = hash_keys; c.tags = tag_words; c.hash_shared = shared;
+    return QLDPC_OK;
+}
+
+/*
  * Blocks of any mix of lengths, rates and puncturing in one call ("let many blocks queue and decode in one
  * launch"): blocks are grouped by code (code_k, code_m), every group goes through its decoder in batches of up to max_blocks
  * frames, and the groups of a call run side by side (the pipeline above); within a group the blocks may differ in length
  * (shortening per frame) and in efficiency (puncturing per frame).  keys are decoded in place.
  * Every message is validated on its own: status[i] = QLDPC_OK | QLDPC_EDECODE | QLDPC_ESIZE (header does not match the block /
- * the local plan -- that block is not decoded, the others are).
+ * the local plan -- that block is not decoded, the others are).  `tagged`: qldpc_recon_decode_blocks_tagged, the same call with the tag arguments.
  */
-extern "C" int qldpc_recon_decode_blocks(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber,
-                                         const qldpc_recon_msg *msgs, const uint32_t *const *parity_words, int *status, int *corrected, int *iterations)
+static int decode_blocks_call(const char *who, bool tagged, qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber,
+                              const qldpc_recon_msg *msgs, const uint32_t *const *parity_words, int n_keys, const uint32_t *const *hash_keys,
+                              uint32_t *const *tag_words, int *status, int *corrected, int *iterations)
 {
     if (!r || !key_words || !key_bits || !qber || !msgs || !parity_words || !status || n <= 0) return QLDPC_EINVAL;
-    const recon_call c = call_bob(n, key_words, key_bits, qber, msgs, parity_words, status, corrected, iterations);
+    recon_call c = call_bob(n, key_words, key_bits, qber, msgs, parity_words, status, corrected, iterations);
+    if (tagged)
+        if (int rc = call_take_tags(who, c, n_keys, hash_keys, tag_words)) return rc;
     std::vector<char> skip((size_t)n, 0);
     for (int i = 0; i < n; i++)
         if (int rc = bob_block_begin(r, c, i, nullptr, &skip[(size_t)i])) return rc;
     return run_call(r, c, skip);
+}
+
+extern "C" int qldpc_recon_decode_blocks(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber,
+                                         const qldpc_recon_msg *msgs, const uint32_t *const *parity_words, int *status, int *corrected, int *iterations)
+{
+    return decode_blocks_call("recon_decode_blocks", false, r, n, key_words, key_bits, qber, msgs, parity_words, 0, nullptr, nullptr, status, corrected, iterations);
+}
+
+/*
+ * qldpc_recon_decode_blocks with the keyed tag of every verified block (qldpc_recon_tag_core.h): the same first pass -- validation, grouping, lanes,
+ * staging sets and pipeline -- with rk_verify_tag in the place of rk_verify, so the decoded rows are hashed where they lie on the device.  The hash-key
+ * rows travel with the input block of a job and the tags come back with its result block; an entry's staging has the room from its creation on.
+ */
+extern "C" int qldpc_recon_decode_blocks_tagged(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber, const qldpc_recon_msg *msgs,
+                                                const uint32_t *const *parity_words, int n_keys, const uint32_t *const *hash_keys, uint32_t *const *tag_words,
+                                                int *status, int *corrected, int *iterations)
+{
+    return decode_blocks_call("recon_decode_blocks_tagged", true, r, n, key_words, key_bits, qber, msgs, parity_words, n_keys, hash_keys, tag_words, status, corrected, iterations);
 }
 
 /*
@@ -1400,8 +1484,9 @@ extern "C" int qldpc_recon_decode_blind(qldpc_recon *r, int n, uint32_t *const *
  * results of a job before it launches the next one of the lane (the wait job_finish makes), and only a job with a failure queues anything more
  * (job_capture); the trial launches follow the lane's ordinary jobs (guess_drain).  The gang path is not taken by these calls.
  */
-extern "C" int qldpc_recon_decode_guess(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber, const qldpc_recon_msg *msgs,
-                                        const uint32_t *const *parity_words, int guess_bits, qldpc_recon_guess *guess, int *status, int *corrected, int *iterations)
+static int decode_guess_call(const char *who, bool tagged, qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber,
+                             const qldpc_recon_msg *msgs, const uint32_t *const *parity_words, int guess_bits, qldpc_recon_guess *guess, int n_keys,
+                             const uint32_t *const *hash_keys, uint32_t *const *tag_words, int *status, int *corrected, int *iterations)
 {
     if (!r || !key_words || !key_bits || !qber || !msgs || !parity_words || !status || n <= 0) return QLDPC_EINVAL;
     if (guess_bits > 0 && !guess) { qldpc_set_error("recon_decode_guess: guess_bits = %d needs the guess array (one qldpc_recon_guess per block)", guess_bits); return QLDPC_EINVAL; }
@@ -1420,12 +1505,116 @@ extern "C" int qldpc_recon_decode_guess(qldpc_recon *r, int n, uint32_t *const *
     }
     recon_call c = call_bob(n, key_words, key_bits, qber, msgs, parity_words, status, corrected, iterations);
     c.guess = guess; c.guess_bits = guess_bits;
+    if (tagged)
+        if (int rc = call_take_tags(who, c, n_keys, hash_keys, tag_words)) return rc;
     std::vector<char> skip((size_t)n, 0);
     for (int i = 0; i < n; i++) {
         if (int rc = bob_block_begin(r, c, i, nullptr, &skip[(size_t)i])) return rc;
         if (guess) { const qldpc_recon_guess none = {0, -1, 0, 0, 0, 0}; guess[i] = none; }
     }
     return run_call(r, c, skip);
+}
+
+extern "C" int qldpc_recon_decode_guess(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber, const qldpc_recon_msg *msgs,
+                                        const uint32_t *const *parity_words, int guess_bits, qldpc_recon_guess *guess, int *status, int *corrected, int *iterations)
+{
+    return decode_guess_call("recon_decode_guess", false, r, n, key_words, key_bits, qber, msgs, parity_words, guess_bits, guess, 0, nullptr, nullptr, status, corrected, iterations);
+}
+
+/*
+ * qldpc_recon_decode_guess with the keyed tag of every block that ends QLDPC_OK: a block decoded at once gets its tag from rk_verify_tag, a rescued
+ * block the tag of the winner's key from rk_tag (guess_drain), a block still failed zeros.  The refusals are those of qldpc_recon_decode_guess, then
+ * those of the tag arguments.
+ */
+extern "C" int qldpc_recon_decode_guess_tagged(qldpc_recon *r, int n, uint32_t *const *key_words, const int *key_bits, const float *qber, const qldpc_recon_msg *msgs,
+                                               const uint32_t *const *parity_words, int guess_bits, qldpc_recon_guess *guess, int n_keys,
+                                               const uint32_t *const *hash_keys, uint32_t *const *tag_words, int *status, int *corrected, int *iterations)
+{
+    return decode_guess_call("recon_decode_guess_tagged", true, r, n, key_words, key_bits, qber, msgs, parity_words, guess_bits, guess, n_keys, hash_keys, tag_words,
+                             status, corrected, iterations);
+}
+
+/* the staging block of qldpc_recon_tag_blocks, pinned and on the device, of at least `words` words */
+static int tag_stage_reserve(qldpc_recon *r, size_t words)
+{
+    if (r->tag_words >= words) return QLDPC_OK;
+    (void)hipFree(r->d_tag);
+    if (r->h_tag) (void)hipHostFree(r->h_tag);
+    r->h_tag = r->d_tag = nullptr; r->tag_words = 0;
+    if (hipHostMalloc((void **)&r->h_tag, sizeof(uint32_t) * words) != hipSuccess || hipMalloc((void **)&r->d_tag, sizeof(uint32_t) * words) != hipSuccess) {
+        if (r->h_tag) (void)hipHostFree(r->h_tag);
+        r->h_tag = nullptr;
+        qldpc_set_error("recon_tag_blocks: staging of %zu words could not be allocated", words);
+        return QLDPC_ENOMEM;
+    }
+    r->tag_words = words;
+    return QLDPC_OK;
+}
+
+/*
+ * The tags of host keys, for either side (Alice: her keys, once Bob's hash key has arrived): only a block's length matters, there is no plan and no
+ * message.  The keys go through the session's tag staging block (recon_tag_layout) in launches of at most max_blocks rows of rk_tag on the first
+ * lane's stream; the rows of a launch are as wide as the longest key of the call.
+ */
+extern "C" int qldpc_recon_tag_blocks(qldpc_recon *r, int n, const uint32_t *const *key_words, const int *key_bits, int n_keys, const uint32_t *const *hash_keys,
+                                      uint32_t *const *tag_words)
+{
+    if (!r || !key_words || !key_bits || !hash_keys || !tag_words || n <= 0) return QLDPC_EINVAL;
+    if (n_keys < 1 || n_keys > RT_MAX_KEYS) { qldpc_set_error("recon_tag_blocks: n_keys = %d, outside 1 .. %d", n_keys, RT_MAX_KEYS); return QLDPC_EINVAL; }
+    int W = 1;
+    bool shared = true;
+    for (int i = 0; i < n; i++) {
+        if (!key_words[i] || !hash_keys[i] || !tag_words[i]) { qldpc_set_error("recon_tag_blocks: block %d has no %s row", i, !key_words[i] ? "key" : !hash_keys[i] ? "hash-key" : "tag"); return QLDPC_EINVAL; }
+        if (key_bits[i] < 1 || key_bits[i] > RT_MAX_BITS) { qldpc_set_error("recon_tag_blocks: block %d has key_bits = %d, outside 1 .. %d", i, key_bits[i], RT_MAX_BITS); return QLDPC_ESIZE; }
+        W = std::max(W, (key_bits[i] + 31) / 32);
+        shared = shared && hash_keys[i] == hash_keys[0];
+    }
+    HIPCHK(hipSetDevice(r->cfg.device));
+    const int B = r->cfg.max_blocks;
+    const size_t row = 2 * (size_t)n_keys;
+    if (int rc = tag_stage_reserve(r, recon_tag_layout(nullptr, std::min(n, B), W, n_keys).words)) return rc;
+    hipStream_t s = r->lane[0].stream;
+    for (int at = 0; at < n; at += B) {
+        const int nb = std::min(B, n - at);
+        const recon_tag_view h = recon_tag_layout(r->h_tag, nb, W, n_keys), d = recon_tag_layout(r->d_tag, nb, W, n_keys);
+        for (int t = 0; t < nb; t++) {
+            const int i = at + t;
+            memcpy(h.keys + (size_t)t * W, key_words[i], sizeof(uint32_t) * (size_t)((key_bits[i] + 31) / 32));      /* rk_tag reads no word past a block's length */
+            h.key_bits[t] = key_bits[i];
+            if (!shared || t == 0) memcpy(h.hash_keys + (size_t)t * row, hash_keys[i], sizeof(uint32_t) * row);
+        }
+        const size_t in_words = (size_t)(h.tags - h.keys);
+        hipError_t he = hipMemcpyAsync(r->d_tag, r->h_tag, sizeof(uint32_t) * in_words, hipMemcpyHostToDevice, s);
+        if (he == hipSuccess) {
+            rk_tag_launch(n_keys, nb, s, d.keys, d.key_bits, nullptr, d.hash_keys, shared ? 0 : row, d.tags, W);
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess) he = hipMemcpyAsync(h.tags, d.tags, sizeof(uint32_t) * (size_t)nb * row, hipMemcpyDeviceToHost, s);
+        const hipError_t hs = hipStreamSynchronize(s);      /* the pinned block is written again by the next launch */
+        if (he == hipSuccess) he = hs;
+        if (he != hipSuccess) { qldpc_set_error("recon_tag_blocks: %s", hipGetErrorString(he)); return QLDPC_EHIP; }
+        for (int t = 0; t < nb; t++) memcpy(tag_words[at + t], h.tags + (size_t)t * row, sizeof(uint32_t) * row);
+    }
+    return QLDPC_OK;
+}
+
+/* the verdict kernel alone over rows that lie on the device (rk_verify_tag), what a tagged job queues after its decode: synthetic rows can be verified without a decode */
+extern "C" int qldpc_recon_verify_tag_dev(int n, int n_keys, int Wk, int Wn, const uint32_t *d_out_rows, const uint32_t *d_keys, const int *d_key_bits,
+                                          const uint32_t *d_crc_want, const int *d_ok, const int *d_iters, const uint32_t *d_hash_keys, size_t hash_key_stride,
+                                          uint32_t *d_res_keys, int *d_res, uint32_t *d_tags, void *hip_stream)
+{
+    if (!d_out_rows || !d_keys || !d_key_bits || !d_crc_want || !d_ok || !d_iters || !d_hash_keys || !d_res_keys || !d_res || !d_tags) return QLDPC_EINVAL;
+    if (n_keys < 1 || n_keys > RT_MAX_KEYS) { qldpc_set_error("recon_verify_tag: n_keys=%d, outside 1 .. %d", n_keys, RT_MAX_KEYS); return QLDPC_EINVAL; }
+    if (n < 0 || Wk < 1 || Wn < Wk || (hash_key_stride && hash_key_stride < 2 * (size_t)n_keys)) {
+        qldpc_set_error("recon_verify_tag: n=%d (not negative), key row of %d words (at least 1) in decoded rows of %d, hash-key rows %zu words apart (0 or at least %d)",
+                        n, Wk, Wn, hash_key_stride, 2 * n_keys);
+        return QLDPC_ESIZE;
+    }
+    if (n == 0) return QLDPC_OK;
+    rk_verify_tag_launch(n_keys, n, (hipStream_t)hip_stream, d_out_rows, d_keys, d_key_bits, d_crc_want, d_ok, d_iters, d_hash_keys, hash_key_stride, d_res_keys, d_res,
+                         d_tags, Wk, Wn);
+    HIPCHK(hipGetLastError());
+    return QLDPC_OK;
 }
 
 /* the verdict over trial rows that lie on the device (rk_guess_crc + rk_guess_settle), what guess_drain queues per trial launch: synthetic rows can be settled without a decode */

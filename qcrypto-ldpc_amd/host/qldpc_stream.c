@@ -25,6 +25,12 @@
  *                          equal: must equal reconciled), vt_failed_differ (failed blocks whose tags differ) beside vt_failed_words_differ
  *                          (failed blocks whose words differ from Alice's: the two must be equal), vt_equals_host (1 when every device tag
  *                          of the last call equals qldpc_polyhash_host, untimed) and vt_leak_bits; may be given together with -H / -U / -N)]
+ *                     [-Y (verification inside the decode call: the timed call is ONE qldpc_recon_decode_blocks_tagged under the measurement key of -V,
+ *                          which hashes Bob's decoded rows where they lie on the device, and Alice's tags come from ONE qldpc_recon_tag_blocks
+ *                          call on her session.  Adds yt_equal (blocks with status OK whose tag is Alice's: must equal reconciled), yt_failed_zero
+ *                          (failed blocks, whose tag must be zeros), yt_leak_bits, and a line "tags equal: a / b" on stderr; ms_mean and ms_best
+ *                          are then the tagged call's wall time.  With -V as well both stages run and yt_equals_vt says whether every tag of a
+ *                          reconciled block equals the polyhash context's: it must be 1)]
  *                     (defaults: 512 epochs x 52 429 bits, max_blocks 512, PEG depth 2 = the library's default)
  * prints one JSON object on stdout.
  */
@@ -72,10 +78,10 @@ static void *part_main(void *arg)
 
 int main(int argc, char **argv)
 {
-    int epochs = 512, key_bits = 52429, batch = 512, reps = 3, layered = -1, profile = 0, peg = 2, opt, a_lanes = 0, b_lanes = 0, verbose = 0, split = 1, gap_profile = 0, hash = 0, toeplitz = 0, ntt = 0, verify = 0;
+    int epochs = 512, key_bits = 52429, batch = 512, reps = 3, layered = -1, profile = 0, peg = 2, opt, a_lanes = 0, b_lanes = 0, verbose = 0, split = 1, gap_profile = 0, hash = 0, toeplitz = 0, ntt = 0, verify = 0, intag = 0;
     uint64_t seed = 42;
     double qmin = 0.005, qmax = 0.06, gap = 0.0;
-    while ((opt = getopt(argc, argv, "e:k:b:S:r:q:lfpP:g:A:B:vT:G:HUNV")) != -1) {
+    while ((opt = getopt(argc, argv, "e:k:b:S:r:q:lfpP:g:A:B:vT:G:HUNVY")) != -1) {
         switch (opt) {
         case 'e': epochs = atoi(optarg); break;
         case 'k': key_bits = atoi(optarg); break;
@@ -96,6 +102,7 @@ int main(int argc, char **argv)
         case 'U': toeplitz = 1; break;
         case 'N': toeplitz = 1; ntt = 1; break;
         case 'V': verify = 1; break;
+        case 'Y': intag = 1; break;
         case 'T': split = atoi(optarg); break;      /* experiment: T sessions on T host threads, each decoding every T-th epoch */
         default: fprintf(stderr, "usage: see the head of qldpc_stream.c\n"); return 2;
         }
@@ -252,6 +259,18 @@ int main(int argc, char **argv)
     uint32_t **vt_a = NULL, **vt_b = NULL, *vt_buf = NULL, vt_key[2] = {0, 0};
     double vt_best = 1e30, vt_sum = 0.0;
     int vt_agree = 0, vt_failed_differ = 0, vt_failed_words_differ = 0, vt_equals_host = 1;
+    if (verify || intag) { vt_key[0] = (uint32_t)rng_next(); vt_key[1] = (uint32_t)rng_next(); }      /* one measurement key for both stages */
+    /* -Y: the tags of the decode call itself, and Alice's from her session */
+    const uint32_t **yt_hk = NULL;
+    uint32_t **yt_a = NULL, **yt_b = NULL, *yt_buf = NULL;
+    int yt_equal = 0, yt_failed_zero = 0, yt_failed = 0, yt_equals_vt = 1;
+    if (intag) {
+        yt_hk = calloc((size_t)epochs, sizeof(*yt_hk)); yt_a = calloc((size_t)epochs, sizeof(*yt_a)); yt_b = calloc((size_t)epochs, sizeof(*yt_b));
+        yt_buf = calloc((size_t)epochs * 4, 4);
+        if (!yt_hk || !yt_a || !yt_b || !yt_buf) return 1;
+        for (int e = 0; e < epochs; e++) { yt_hk[e] = vt_key; yt_a[e] = yt_buf + (size_t)e * 4; yt_b[e] = yt_a[e] + 2; }
+        if ((rc = qldpc_recon_tag_blocks(ra, epochs, akeys, kb, 1, yt_hk, yt_a))) return die("recon_tag_blocks", rc);
+    }
     if (verify) {
         qldpc_polyhash_cfg vc;
         qldpc_polyhash_cfg_default(&vc);
@@ -260,15 +279,22 @@ int main(int argc, char **argv)
         vt_hk = calloc((size_t)epochs, sizeof(*vt_hk)); vt_a = calloc((size_t)epochs, sizeof(*vt_a)); vt_b = calloc((size_t)epochs, sizeof(*vt_b));
         vt_buf = calloc((size_t)epochs * 4, 4);
         if (!vt_hk || !vt_a || !vt_b || !vt_buf) return 1;
-        vt_key[0] = (uint32_t)rng_next(); vt_key[1] = (uint32_t)rng_next();
         for (int e = 0; e < epochs; e++) { vt_hk[e] = vt_key; vt_a[e] = vt_buf + (size_t)e * 4; vt_b[e] = vt_a[e] + 2; }
     }
     for (int rep = -1; rep < reps; rep++) {
         memcpy(work, bob, (size_t)epochs * W * 4);
         t0 = now_s();
-        rc = qldpc_recon_decode_blocks(rb, epochs, bkeys, kb, qber, msgs, (const uint32_t *const *)pars, status, corrected, iters);
+        if (intag) rc = qldpc_recon_decode_blocks_tagged(rb, epochs, bkeys, kb, qber, msgs, (const uint32_t *const *)pars, 1, yt_hk, yt_b, status, corrected, iters);
+        else rc = qldpc_recon_decode_blocks(rb, epochs, bkeys, kb, qber, msgs, (const uint32_t *const *)pars, status, corrected, iters);
         const double dt = now_s() - t0;
-        if (rc) return die("recon_decode_blocks", rc);
+        if (rc) return die(intag ? "recon_decode_blocks_tagged" : "recon_decode_blocks", rc);
+        if (intag) {
+            yt_equal = 0; yt_failed_zero = 0; yt_failed = 0;
+            for (int e = 0; e < epochs; e++) {
+                if (status[e] == QLDPC_OK) yt_equal += !memcmp(yt_a[e], yt_b[e], 8);
+                else { yt_failed++; yt_failed_zero += yt_b[e][0] == 0 && yt_b[e][1] == 0; }
+            }
+        }
         if (verbose) {
             int bad = 0, pos[8] = {0};
             fprintf(stderr, "bob rep %d:", rep);
@@ -335,6 +361,9 @@ int main(int argc, char **argv)
                 if (status[e] == QLDPC_OK) vt_agree += same;
                 else { vt_failed_differ += !same; vt_failed_words_differ += memcmp(work + (size_t)e * W, alice + (size_t)e * W, (size_t)W * 4) != 0; }
             }
+            if (intag)      /* both stages: the tag of the decode call is the context's tag of the same key */
+                for (int e = 0; e < epochs; e++)
+                    if (status[e] == QLDPC_OK && (memcmp(yt_b[e], vt_b[e], 8) || memcmp(yt_a[e], vt_a[e], 8))) yt_equals_vt = 0;
             if (rep == reps - 1)
                 for (int e = 0; e < epochs; e++) {
                     uint32_t tag[2];
@@ -361,11 +390,11 @@ int main(int argc, char **argv)
         if (iters[e] >= cfg.n_ite) maxed[msgs[e].rate_index & 7]++;
     }
     const double mean = sum / reps;
-    printf("{\"workload\": \"%d epochs x %d bits, QBER ~ U[%.3f, %.3f] seed %llu, batches of <= %d blocks, %s, one decode_blocks call\", "
+    printf("{\"workload\": \"%d epochs x %d bits, QBER ~ U[%.3f, %.3f] seed %llu, batches of <= %d blocks, %s, one %s call\", "
            "\"reconciled\": %d, \"epochs\": %d, \"ms_mean\": %.3f, \"ms_best\": %.3f, \"Mbit_s_mean\": %.1f, \"Mbit_s_best\": %.1f, "
            "\"leaked_fraction\": %.4f, \"avg_iterations\": %.2f, \"alice_encode_ms\": %.3f, \"epochs_per_rate\": [%d, %d, %d, %d], \"failed_per_rate\": [%d, %d, %d, %d], "
            "\"at_max_iterations_per_rate\": [%d, %d, %d, %d], \"mean_iterations_per_rate\": [%.1f, %.1f, %.1f, %.1f], \"max_iterations_per_rate\": [%d, %d, %d, %d]",
-           epochs, key_bits, qmin, qmax, (unsigned long long)seed, batch, layered ? "layered" : "flooding", good, epochs, mean * 1e3, best * 1e3,
+           epochs, key_bits, qmin, qmax, (unsigned long long)seed, batch, layered ? "layered" : "flooding", intag ? "decode_blocks_tagged" : "decode_blocks", good, epochs, mean * 1e3, best * 1e3,
            (double)good * key_bits / mean / 1e6, (double)good * key_bits / best / 1e6, (double)leaked / fmax(1.0, (double)good * key_bits), it_sum / epochs,
            t_enc * 1e3, per_rate[0], per_rate[1], per_rate[2], per_rate[3], fail_rate[0], fail_rate[1], fail_rate[2], fail_rate[3], maxed[0], maxed[1], maxed[2], maxed[3],
            it_mean[0] / fmax(1, per_rate[0]), it_mean[1] / fmax(1, per_rate[1]), it_mean[2] / fmax(1, per_rate[2]), it_mean[3] / fmax(1, per_rate[3]), it_max[0], it_max[1], it_max[2], it_max[3]);
@@ -378,6 +407,11 @@ int main(int argc, char **argv)
     if (verify)
         printf(", \"vt_ms_mean\": %.3f, \"vt_ms_best\": %.3f, \"vt_agree\": %d, \"vt_failed_differ\": %d, \"vt_failed_words_differ\": %d, \"vt_equals_host\": %d, \"vt_leak_bits\": %d",
                vt_sum / reps * 1e3, vt_best * 1e3, vt_agree, vt_failed_differ, vt_failed_words_differ, vt_equals_host, qldpc_polyhash_leaked_bits(1));
+    if (intag) {
+        printf(", \"yt_equal\": %d, \"yt_failed\": %d, \"yt_failed_zero\": %d, \"yt_leak_bits\": %d", yt_equal, yt_failed, yt_failed_zero, qldpc_recon_leaked_bits_tagged(&msgs[0], 1) - qldpc_recon_leaked_bits(&msgs[0]));
+        if (verify) printf(", \"yt_equals_vt\": %d", yt_equals_vt);
+        fprintf(stderr, "qldpc_stream: tags equal: %d / %d, decode_blocks_tagged %.3f ms mean, %.3f ms best\n", yt_equal, epochs, mean * 1e3, best * 1e3);
+    }
     if (profile) {
         qldpc_kernel_stat st[16];
         qldpc_recon_profile_enable(rb, 1);
@@ -396,5 +430,6 @@ int main(int argc, char **argv)
     qldpc_polyhash_free(vt);
     qldpc_recon_free(ra);
     qldpc_recon_free(rb);
+    if (intag && (yt_equal != good || yt_failed_zero != yt_failed || !yt_equals_vt)) return 4;
     return good == epochs ? 0 : 3;
 }

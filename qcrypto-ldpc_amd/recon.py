@@ -47,7 +47,19 @@ _sig("qldpc_recon_disclose_host", C.c_int, [_up, C.c_int, _ip, C.c_int, _u8p])
 _sig("qldpc_recon_decode_guess", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _fp, C.POINTER(ReconMsg), C.POINTER(_up), C.c_int, _vp, _ip, _ip, _ip])
 _sig("qldpc_recon_guess_settle_dev", C.c_int, [C.c_int] * 4 + [_vp] * 12 + [_vp])
 _sig("qldpc_recon_guess_settle_host", C.c_int, [C.c_int] * 4 + [_up, _ip, _ip, _up, _ip, _up, _ip, _ip, _up, _up, _ip, _ip])
+_sig("qldpc_recon_decode_blocks_tagged", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _fp, C.POINTER(ReconMsg), C.POINTER(_up), C.c_int, C.POINTER(_up), C.POINTER(_up),
+                                                   _ip, _ip, _ip])
+_sig("qldpc_recon_decode_guess_tagged", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, _fp, C.POINTER(ReconMsg), C.POINTER(_up), C.c_int, _vp, C.c_int, C.POINTER(_up),
+                                                  C.POINTER(_up), _ip, _ip, _ip])
+_sig("qldpc_recon_tag_blocks", C.c_int, [_vp, C.c_int, C.POINTER(_up), _ip, C.c_int, C.POINTER(_up), C.POINTER(_up)])
+_sig("qldpc_recon_verify_tag_dev", C.c_int, [C.c_int] * 4 + [_vp] * 7 + [C.c_size_t] + [_vp] * 3 + [_vp])
+_sig("qldpc_recon_verify_tag_host", C.c_int, [C.c_int] * 4 + [_up, _up, _ip, _up, _ip, _ip, _up, C.c_size_t, _up, _ip, _up])
+_sig("qldpc_recon_tag_host", C.c_int, [_up, C.c_int, _up, C.c_int, _up])
+_sig("qldpc_recon_leaked_bits_tagged", C.c_int, [C.POINTER(ReconMsg), C.c_int])
 _sig("qldpc_crc32_words_chunked", C.c_uint32, [_up, C.c_int, C.c_int])
+RECON_TAG_MAX_KEYS = 4
+RECON_TAG_MAX_BITS = 1 << 18
+RECON_TAG_LANES = 256
 _sig("qldpc_recon_parity_words", C.c_int, [C.POINTER(ReconMsg)])
 _sig("qldpc_recon_leaked_bits", C.c_int, [C.POINTER(ReconMsg)])
 _sig("qldpc_recon_entries_created", C.c_long, [_vp])
@@ -118,6 +130,92 @@ def recon_guess_settle(g, trial_rows, ok, iters, keys, key_bits, crc_want, first
                                              _vp(guess.data_ptr()), _vp(s.cuda_stream)), "recon_guess_settle")
         host = [t.cpu().numpy() for t in (res_keys, res, guess, passed, crc)]
     return _settle_result(n, host[0].view(np.uint32), host[1][:, :n], np.ascontiguousarray(host[2][:n]), host[3][:slots], host[4][:slots].view(np.uint32))
+
+
+def recon_tag_host(key_words, key_bits, hash_key, lanes=RECON_TAG_LANES):
+    """the sessions' keyed tag of one block under one key (hash_key: its two words hi, lo) on the host (qldpc_recon_tag_host), by the kernels' chunked
+    Horner and fold with `lanes` lanes (a power of two) -> the tag's two words (hi, lo): polyhash_host's tag for every such lanes"""
+    kw, hk = np.ascontiguousarray(key_words, dtype=np.uint32), np.ascontiguousarray(hash_key, dtype=np.uint32)
+    key_bits = int(key_bits)
+    if key_bits <= 0 or kw.size < (key_bits + 31) // 32 or hk.size < 2:
+        raise QldpcError(-6, "recon_tag_host: %d key words, key_bits = %d, %d hash key words" % (kw.size, key_bits, hk.size))
+    out = np.zeros(2, np.uint32)
+    _chk(_L.qldpc_recon_tag_host(_ptr(kw, _up), key_bits, _ptr(hk, _up), int(lanes), _ptr(out, _up)), "recon_tag_host")
+    return out
+
+
+def recon_leaked_bits_tagged(msg, n_keys=1):
+    """what a tagged block discloses at the most: Recon.leaked_bits(msg) + 61 n_keys (the CRC and the tags are both charged)"""
+    if not 1 <= int(n_keys) <= RECON_TAG_MAX_KEYS:
+        raise QldpcError(-6, "recon_leaked_bits_tagged: n_keys = %d" % n_keys)
+    return int(_L.qldpc_recon_leaked_bits_tagged(C.byref(msg), int(n_keys)))
+
+
+def _verify_tag_result(n, res_keys, res, tags):
+    return dict(status=res[0], corrected=res[1], iterations=res[2], crc=res[3].view(np.uint32), keys=res_keys, tags=tags)
+
+
+def _hash_key_rows(who, n, hash_keys):
+    """hash_keys of a call over n blocks: ONE row of 2 r words, shared, or n rows -> (rows uint32 [1 or n, 2 r], r, shared)"""
+    hk = np.ascontiguousarray(hash_keys, dtype=np.uint32)
+    shared = hk.ndim == 1
+    hk = hk.reshape(1, -1) if shared else hk
+    if hk.ndim != 2 or hk.shape[1] % 2 or (not shared and hk.shape[0] != n):
+        raise QldpcError(-6, "%s: hash_keys of shape %s for %d blocks: one row of 2 r words or one row per block" % (who, hk.shape, n))
+    return hk, hk.shape[1] // 2, shared
+
+
+def recon_verify_tag_host(out_rows, keys, key_bits, crc_want, ok, iters, hash_keys):
+    """the verdict of a tagged verify step on the host (qldpc_recon_verify_tag_host): out_rows uint32 [n, Wn] decoded rows, keys uint32 [n, Wk] the keys
+    handed in, key_bits, crc_want, ok, iters [n], hash_keys one shared row of 2 r words or [n, 2 r] -> dict(status, corrected, iterations, crc [n], keys
+    uint32 [n, Wk] (words past a key's length stay 0), tags uint32 [n, 2 r], zeros for a block that is not ok with the wanted CRC)"""
+    rows, kw = np.ascontiguousarray(out_rows, dtype=np.uint32), np.ascontiguousarray(keys, dtype=np.uint32)
+    if rows.ndim != 2 or kw.ndim != 2 or rows.shape[0] != kw.shape[0]:
+        raise QldpcError(-6, "recon_verify_tag_host: out_rows and keys are 2-D arrays of as many rows")
+    n = kw.shape[0]
+    hk, r, shared = _hash_key_rows("recon_verify_tag_host", n, hash_keys)
+    kb, want = _np_i32(key_bits).ravel(), np.ascontiguousarray(crc_want, dtype=np.uint32).ravel()
+    ok, it = _np_i32(ok).ravel(), _np_i32(iters).ravel()
+    if not kb.size == want.size == ok.size == it.size == n:
+        raise QldpcError(-6, "recon_verify_tag_host: %d blocks with %d / %d / %d / %d scalars" % (n, kb.size, want.size, ok.size, it.size))
+    res_keys, res, tags = np.zeros((n, kw.shape[1]), np.uint32), np.zeros((4, max(n, 1)), np.int32), np.zeros((max(n, 1), max(2 * r, 1)), np.uint32)
+    _chk(_L.qldpc_recon_verify_tag_host(n, r, kw.shape[1], rows.shape[1], _ptr(rows, _up), _ptr(kw, _up), _ptr(kb, _ip), _ptr(want, _up), _ptr(ok, _ip), _ptr(it, _ip),
+                                        _ptr(hk, _up), 0 if shared else hk.shape[1], _ptr(res_keys, _up), _ptr(res, _ip), _ptr(tags, _up)), "recon_verify_tag_host")
+    return _verify_tag_result(n, res_keys, res[:, :n], tags[:n])
+
+
+def recon_verify_tag(out_rows, keys, key_bits, crc_want, ok, iters, hash_keys, stream=None):
+    """qldpc_recon_verify_tag_dev: the same over contiguous device int32 tensors (out_rows [n, Wn], keys [n, Wk], key_bits, crc_want, ok, iters [n],
+    hash_keys 1-D of 2 r words, shared, or [n, 2 r]) -> the dict of recon_verify_tag_host as numpy arrays (the call is asynchronous on `stream`; the
+    copies back wait for it)"""
+    torch = _torch()
+    n, Wk, Wn = int(keys.shape[0]), int(keys.shape[1]), int(out_rows.shape[1])
+    shared = hash_keys.dim() == 1
+    hk = hash_keys.unsqueeze(0) if shared else hash_keys
+    if hk.dim() != 2 or hk.shape[1] % 2 or (not shared and hk.shape[0] != n):
+        raise QldpcError(-6, "recon_verify_tag: hash_keys of shape %s for %d blocks" % (tuple(hk.shape), n))
+    r = int(hk.shape[1]) // 2
+    ptrs = [_guess_dev(out_rows, n, Wn, "recon_verify_tag", "out_rows"), _guess_dev(keys, n, Wk, "recon_verify_tag", "keys")]
+    ptrs += [_guess_dev(t, n, 0, "recon_verify_tag", name) for t, name in ((key_bits, "key_bits"), (crc_want, "crc_want"), (ok, "ok"), (iters, "iters"))]
+    ptrs.append(_guess_dev(hk, int(hk.shape[0]), 2 * r, "recon_verify_tag", "hash_keys"))
+    dev = keys.device
+    res_keys, res = torch.zeros((n, Wk), dtype=torch.int32, device=dev), torch.zeros((4, max(n, 1)), dtype=torch.int32, device=dev)
+    tags = torch.zeros((max(n, 1), max(2 * r, 1)), dtype=torch.int32, device=dev)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)      # the stream itself: the copies back are put on it
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        _chk(_L.qldpc_recon_verify_tag_dev(n, r, Wk, Wn, *ptrs, 0 if shared else 2 * r, _vp(res_keys.data_ptr()), _vp(res.data_ptr()), _vp(tags.data_ptr()),
+                                           _vp(s.cuda_stream)), "recon_verify_tag")
+        host = [t.cpu().numpy() for t in (res_keys, res, tags)]
+    return _verify_tag_result(n, host[0].view(np.uint32), host[1][:, :n], np.ascontiguousarray(host[2][:n]).view(np.uint32))
+
+
+def _tag_args(who, n, hash_keys):
+    """the tag arguments of a session call over n blocks -> (what the caller keeps alive, r, hp, tags uint32 [n, 2 r], tp); a shared row is ONE pointer n times"""
+    hk, r, shared = _hash_key_rows(who, n, hash_keys)
+    tags = np.zeros((n, 2 * r), np.uint32)
+    hp = (_up * n)(*[hk[0 if shared else i].ctypes.data_as(_up) for i in range(n)])
+    tp = (_up * n)(*[tags[i].ctypes.data_as(_up) for i in range(n)])
+    return hk, r, hp, tags, tp
 
 
 def _block_args(keys, key_bits, qber, msgs, parities, copy_keys):
@@ -300,6 +398,48 @@ class Recon(_Handle):
         _chk(_L.qldpc_recon_decode_guess(self._h, n, kp, kb.ctypes.data_as(_ip), qb.ctypes.data_as(_fp), arr, pp, int(guess_bits), _vp(guess.ctypes.data),
                                          st.ctypes.data_as(_ip), co.ctypes.data_as(_ip), it.ctypes.data_as(_ip)), "Recon.decode_guess")
         return st, kws, co, it, guess
+
+    def decode_blocks_tagged(self, keys, key_bits, qber, msgs, parities, hash_keys):
+        """decode_blocks with the keyed tag of every verified block, hashed on the device in the verify step (qldpc_recon_decode_blocks_tagged).
+        hash_keys: ONE row of 2 r words (hi, lo per key, r = 1 .. 4), shared by the blocks, or one row per block; the caller draws them after the
+        parity messages have arrived.  Returns (status[], corrected keys, corrected[], iterations[], tags) with tags uint32 [n, 2 r]: polyhash_host's
+        tag of the key returned for a block that ends QLDPC_OK, zeros for every other"""
+        (kws, pars), kp, kb, qb, arr, pp = _block_args(keys, key_bits, qber, msgs, parities, True)
+        n = len(kws)
+        hk, r, hp, tags, tp = _tag_args("Recon.decode_blocks_tagged", n, hash_keys)
+        st, co, it = _block_results(n)
+        _chk(_L.qldpc_recon_decode_blocks_tagged(self._h, n, kp, kb.ctypes.data_as(_ip), qb.ctypes.data_as(_fp), arr, pp, r, hp, tp, st.ctypes.data_as(_ip),
+                                                 co.ctypes.data_as(_ip), it.ctypes.data_as(_ip)), "Recon.decode_blocks_tagged")
+        return st, kws, co, it, tags
+
+    def decode_guess_tagged(self, keys, key_bits, qber, msgs, parities, guess_bits, hash_keys):
+        """decode_guess with the keyed tags (qldpc_recon_decode_guess_tagged): a block decoded at once as in decode_blocks_tagged, a rescued block the
+        tag of the winner's key, a block still failed zeros.  Returns (status[], corrected keys, corrected[], iterations[], guess, tags)"""
+        (kws, pars), kp, kb, qb, arr, pp = _block_args(keys, key_bits, qber, msgs, parities, True)
+        n = len(kws)
+        hk, r, hp, tags, tp = _tag_args("Recon.decode_guess_tagged", n, hash_keys)
+        st, co, it = _block_results(n)
+        guess = np.zeros(n, RECON_GUESS_DTYPE)
+        guess["winner"] = -1
+        _chk(_L.qldpc_recon_decode_guess_tagged(self._h, n, kp, kb.ctypes.data_as(_ip), qb.ctypes.data_as(_fp), arr, pp, int(guess_bits), _vp(guess.ctypes.data), r, hp, tp,
+                                                st.ctypes.data_as(_ip), co.ctypes.data_as(_ip), it.ctypes.data_as(_ip)), "Recon.decode_guess_tagged")
+        return st, kws, co, it, guess, tags
+
+    def tag_blocks(self, keys, key_bits, hash_keys):
+        """the keyed tags of host keys (qldpc_recon_tag_blocks), for either side -- Alice tags her keys once Bob's hash key has arrived: keys a list of
+        uint32 word arrays of 1 .. 2^18 bits (bits past key_bits[i] are ignored), hash_keys as in decode_blocks_tagged -> tags uint32 [n, 2 r]"""
+        n = len(keys)
+        kb = np.ascontiguousarray(key_bits, dtype=np.int32).ravel()
+        if kb.size != n:
+            raise QldpcError(-6, "Recon.tag_blocks: %d blocks, %d lengths" % (n, kb.size))
+        kws = [np.ascontiguousarray(k, dtype=np.uint32) for k in keys]
+        for i, k in enumerate(kws):
+            if 0 < int(kb[i]) <= RECON_TAG_MAX_BITS and k.size < (int(kb[i]) + 31) // 32:
+                raise QldpcError(-6, "Recon.tag_blocks: block %d has %d words for key_bits = %d" % (i, k.size, kb[i]))
+        hk, r, hp, tags, tp = _tag_args("Recon.tag_blocks", n, hash_keys)
+        kp = (_up * n)(*[k.ctypes.data_as(_up) for k in kws])
+        _chk(_L.qldpc_recon_tag_blocks(self._h, n, kp, kb.ctypes.data_as(_ip), r, hp, tp), "Recon.tag_blocks")
+        return tags
 
     def prepare_decode(self, keys, key_bits, qber, msgs, parities):
         """decode_blocks with the argument marshalling done once: returns an object whose run() is the one C call
