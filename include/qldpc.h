@@ -43,6 +43,7 @@
  *   qldpc_mc_strata / _weight_frames_*    the same loop over fixed error weights instead of BERs: FER(q) for every q   (no counterpart)
  *   qldpc_mc_set_channel / _awgn_table   the channel of the fixed-point sims: BPSK over AWGN, 6-bit received values  ML/BPSK_nrldpc_sim_RM_FP.m
  *   qldpc_mc_sweep_tables                 the Eb/N0 points of those sims side by side in one batch, a table per point    ML/sim_results.m
+ *   qldpc_polar_*                         the polar encoder and SC decoder of the fourth curve of that figure   ML/nrpolar_encode.m, nrpolar_scdecode.m, nrpolar_scdecode_FP.m
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -1544,6 +1545,47 @@ int    qldpc_mc_guess_open(qldpc_mc *mc, uint64_t *frames, uint32_t *weak_words,
 #define QLDPC_MC_GUESS_FRESH 1
 #define QLDPC_MC_GUESS_TRIALS 2
 int    qldpc_mc_guess_next_host(int guess_bits, int batch, uint64_t pool, uint64_t input_left, int *kind, int *n);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Polar codes: a batched encoder and successive-cancellation (SC) decoder (qldpc_polar_*).  The definition is csrc/qldpc_polar_core.h, shared by
+ * the kernels (csrc/qldpc_kernels_polar.h) and the host mirrors (csrc/qldpc_polar_host.c), which agree bit for bit in both message types.
+ *
+ *   size      N = 2^log2_n, 1 <= log2_n <= 20 (QLDPC_ESIZE).  Index i is natural order, no bit reversal.  Rows are packed MSB-first,
+ *             ceil(N / 32) words; bits past N are ignored on input and zero on output.
+ *   code      info_pos[n_info]: the positions that carry information, distinct (QLDPC_EINVAL) and below N (QLDPC_ESIZE), 0 <= n_info <= N
+ *             (QLDPC_ESIZE); every other position is frozen.  The construction is the caller's: the library ships no reliability table.
+ *   encode    for m = 1, 2, .., N/2: in every block of 2m bits the first half becomes first ^ second.  An involution.
+ *   decode    at a node with beliefs [a, b]: the left child gets f(a, b) = sgn(a) sgn(b) min(|a|, |b|) (sgn(v) = -1 iff v < 0), the right child
+ *             g(a, b, c) = sat(b + (1 - 2c) a) with c the RE-ENCODED decisions of the left child; the node returns [c_left ^ c_right, c_right].
+ *             Leaf: frozen -> its frozen value (0 without one), else bit = (L < 0).
+ *   messages  QLDPC_POLAR_I8: int8 levels, clamped into [-(maxq + 1), maxq] on load; sat clamps to the same range and f is NOT saturated
+ *             (f(-32, -32) = +32 at maxq = 31), so beliefs reach maxq + 1 and maxq is 1 .. 126 (QLDPC_ESIZE: 127 + 1 does not fit an int8).
+ *             QLDPC_POLAR_F32: floats, sat is the identity, g one add or subtract; inputs must be finite (pin a bit with
+ *             +-QLDPC_CONFIRMED_BIT_LLR, not with an infinity).  maxq is ignored.
+ *   outputs   each may be NULL: u[n_frames][ceil(N/32)] all N decisions; info[n_frames][ceil(n_info/32)] bit m = u[info_pos[m]], the caller's
+ *             order; x[n_frames][ceil(N/32)] the root's re-encoded word (= encode(u): Bob's corrected key when the frozen values are Alice's
+ *             encode(key) on the frozen positions); leaf[n_frames][N] the leaf beliefs, int8 or float as the messages.
+ *   inputs    llr[n_frames][N] frame-major, int8 or float by `messages`; frozen_u[n_frames][ceil(N/32)] the frozen values (bits at other
+ *             positions are ignored), NULL = zeros.
+ *
+ * A context owns its scratch (qldpc_polar_device_bytes: about (2N - 64) x 64 beliefs and 16N bytes of rows per group of 64 frames); a call allocates
+ * nothing, is asynchronous on the context's stream (qldpc_polar_set_stream, NULL = the null stream) and a context is not re-entrant.
+ * QLDPC_ESIZE: n_frames > max_frames; QLDPC_EINVAL: n_frames < 0, a missing pointer, max_frames outside 1 .. 2^24, messages neither value.
+ * n_frames = 0 is a no-op.  Every argument check runs before the first HIP call.  qldpc_polar_encode_dev may run in place (d_x = d_u).
+ */
+typedef struct qldpc_polar qldpc_polar;
+enum { QLDPC_POLAR_I8 = 0, QLDPC_POLAR_F32 = 1 };
+int    qldpc_polar_create(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int max_frames, int device, qldpc_polar **out);
+void   qldpc_polar_free(qldpc_polar *p);
+size_t qldpc_polar_device_bytes(const qldpc_polar *p);
+int    qldpc_polar_set_stream(qldpc_polar *p, void *hip_stream);
+int    qldpc_polar_encode_dev(qldpc_polar *p, int n_frames, const uint32_t *d_u, uint32_t *d_x);
+int    qldpc_polar_decode_dev(qldpc_polar *p, int n_frames, const void *d_llr, const uint32_t *d_frozen_u,
+                              uint32_t *d_u, uint32_t *d_info, uint32_t *d_x, void *d_leaf);
+/* host mirrors, no device needed */
+int    qldpc_polar_encode_host(int log2_n, int n_frames, const uint32_t *u, uint32_t *x);
+int    qldpc_polar_decode_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
+                               const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf);
 
 #ifdef __cplusplus
 }

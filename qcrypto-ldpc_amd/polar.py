@@ -1,0 +1,129 @@
+"""Polar codes (qldpc_polar_*): the batched encoder and successive-cancellation decoder on the device, their host mirrors, and a
+polarization-weight order for callers without a standard's reliability table."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import _L, _Handle, _chk, _create, _dev_empty, _dev_rows, _ip, _sig, _stream_arg, _torch, _up, _vp, QldpcError
+
+POLAR_I8, POLAR_F32 = 0, 1
+POLAR_MAX_LOG2N = 20
+
+_sig("qldpc_polar_create", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)])
+_sig("qldpc_polar_free", None, [_vp])
+_sig("qldpc_polar_device_bytes", C.c_size_t, [_vp])
+_sig("qldpc_polar_set_stream", C.c_int, [_vp, _vp])
+_sig("qldpc_polar_encode_dev", C.c_int, [_vp, C.c_int, _vp, _vp])
+_sig("qldpc_polar_decode_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp])
+_sig("qldpc_polar_encode_host", C.c_int, [C.c_int, C.c_int, _up, _up])
+_sig("qldpc_polar_decode_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _vp, _up, _up, _up, _up, _vp])
+
+
+def _messages(messages):
+    if messages in ("i8", POLAR_I8):
+        return POLAR_I8, np.int8
+    if messages in ("f32", POLAR_F32):
+        return POLAR_F32, np.float32
+    raise QldpcError(-1, "polar: messages=%r ('i8' or 'f32')" % (messages,))
+
+
+def _words(log2_n):
+    return max(1, (1 << max(int(log2_n), 0)) // 32) if int(log2_n) <= POLAR_MAX_LOG2N else 1
+
+
+def polar_pw_order(n):
+    """the positions 0 .. 2^n - 1 in ascending polarization weight sum_j b_j 2^(j/4) (b_j = bit j of the position), ties by index: the least
+    reliable first, so a code of K information bits takes the last K.  Pure numpy; not part of the C ABI."""
+    n = int(n)
+    i = np.arange(1 << n, dtype=np.int64)
+    w = np.zeros(1 << n, np.float64)
+    for j in range(n):
+        w += ((i >> j) & 1) * 2.0 ** (j / 4.0)
+    return np.argsort(w, kind="stable").astype(np.int32)
+
+
+def polar_encode_host(log2_n, u):
+    """the encoder's mirror (qldpc_polar_encode_host): packed rows uint32 [F, ceil(N/32)] (or one row) -> x of the same shape"""
+    u = np.ascontiguousarray(u, dtype=np.uint32)
+    rows = u.reshape(-1, u.shape[-1]) if u.ndim else u.reshape(1, 1)
+    if rows.shape[1] != _words(log2_n):
+        raise QldpcError(-6, "polar_encode_host: rows have %d words, need %d" % (rows.shape[1], _words(log2_n)))
+    x = np.zeros_like(rows)
+    _chk(_L.qldpc_polar_encode_host(int(log2_n), rows.shape[0], rows.ctypes.data_as(_up), x.ctypes.data_as(_up)), "polar_encode_host")
+    return x.reshape(u.shape)
+
+
+def polar_decode_host(log2_n, info_pos, llr, frozen=None, messages="i8", maxq=31, leaf=False):
+    """the SC decoder's mirror (qldpc_polar_decode_host): llr [F, N] int8 or float32 by `messages`, frozen uint32 [F, ceil(N/32)] or None
+    -> dict(u uint32 [F, W], info uint32 [F, ceil(K/32)], x uint32 [F, W]) and, with leaf=True, leaf [F, N] of the messages' type"""
+    kind, dt = _messages(messages)
+    pos = np.ascontiguousarray(info_pos, dtype=np.int32).ravel()
+    llr = np.ascontiguousarray(llr, dtype=dt)
+    n = int(log2_n)
+    N, W = (1 << n) if 0 <= n <= POLAR_MAX_LOG2N else 0, _words(n)
+    if N and (llr.ndim != 2 or llr.shape[1] != N):
+        raise QldpcError(-6, "polar_decode_host: llr must be [frames, N = %d]" % N)
+    F = llr.shape[0] if llr.ndim == 2 else 0
+    fz = None
+    if frozen is not None:
+        fz = np.ascontiguousarray(frozen, dtype=np.uint32)
+        if fz.shape != (F, W):
+            raise QldpcError(-6, "polar_decode_host: frozen must be [frames, %d] words" % W)
+    out = dict(u=np.zeros((F, W), np.uint32), info=np.zeros((F, (pos.size + 31) // 32), np.uint32), x=np.zeros((F, W), np.uint32))
+    if leaf:
+        out["leaf"] = np.zeros((F, N), dt)
+    p = lambda a: a.ctypes.data_as(_up) if a is not None else None
+    _chk(_L.qldpc_polar_decode_host(n, pos.size, pos.ctypes.data_as(_ip), kind, int(maxq), F, llr.ctypes.data_as(_vp), p(fz), p(out["u"]), p(out["info"]),
+                                    p(out["x"]), out["leaf"].ctypes.data_as(_vp) if leaf else None), "polar_decode_host")
+    return out
+
+
+class Polar(_Handle):
+    """A polar code of N = 2^log2_n bits with information at `info_pos` (every other position frozen) on the device: encode() and the
+    successive-cancellation decode() of up to max_frames frames a call, 64 frames to a wave.  Device tensors in, device tensors out, asynchronous
+    on torch's current stream."""
+    _free = _L.qldpc_polar_free
+
+    def __init__(self, log2_n, info_pos, messages="i8", maxq=31, max_frames=4096, device=0):
+        self.messages, self._np_dtype = _messages(messages)
+        pos = np.ascontiguousarray(info_pos, dtype=np.int32).ravel()
+        self._h = _create("Polar", _L.qldpc_polar_create, int(log2_n), pos.size, pos.ctypes.data_as(_ip), self.messages, int(maxq), int(max_frames), int(device))
+        self.log2_n, self.N, self.K, self.W, self.Wi = int(log2_n), 1 << int(log2_n), pos.size, _words(log2_n), (pos.size + 31) // 32
+        self.info_pos, self.maxq, self.max_frames, self.device = pos, int(maxq), int(max_frames), int(device)
+
+    def device_bytes(self):
+        return int(_L.qldpc_polar_device_bytes(self._h))
+
+    def _on_current_stream(self):
+        _chk(_L.qldpc_polar_set_stream(self._h, _stream_arg(None, self.device)), "Polar.set_stream")
+
+    def encode(self, u, out=None):
+        """u int32 / uint32 [F, W] packed rows on the device -> x of the same shape; out=u encodes in place"""
+        torch = _torch()
+        words = (torch.int32, torch.uint32)
+        pu = _dev_rows(u, None, self.W, words, "u")
+        x = _dev_empty(u.device, tuple(u.shape), u.dtype) if out is None else out
+        px = _dev_rows(x, u.shape[0], self.W, words, "out")
+        self._on_current_stream()
+        _chk(_L.qldpc_polar_encode_dev(self._h, u.shape[0], pu, px), "Polar.encode")
+        return x
+
+    def decode(self, llr, frozen=None, leaf=False, want=("u", "info", "x")):
+        """llr [F, N] int8 or float32 (the context's messages), frozen int32 / uint32 [F, W] frozen values or None (zeros)
+        -> dict of device tensors: u int32 [F, W], info int32 [F, ceil(K/32)], x int32 [F, W] (those named in `want`) and, with leaf=True,
+        leaf [F, N] of the messages' type"""
+        torch = _torch()
+        words = (torch.int32, torch.uint32)
+        pl = _dev_rows(llr, None, self.N, (torch.int8 if self.messages == POLAR_I8 else torch.float32,), "llr")
+        F = llr.shape[0]
+        pf = _dev_rows(frozen, F, self.W, words, "frozen")
+        out = {}
+        for name, cols in (("u", self.W), ("info", self.Wi), ("x", self.W)):
+            if name in want:
+                out[name] = _dev_empty(llr.device, (F, cols), torch.int32)
+        if leaf:
+            out["leaf"] = _dev_empty(llr.device, (F, self.N), llr.dtype)
+        ptr = lambda name: _vp(out[name].data_ptr()) if name in out and out[name].numel() else None
+        self._on_current_stream()
+        _chk(_L.qldpc_polar_decode_dev(self._h, F, pl, pf, ptr("u"), ptr("info"), ptr("x"), ptr("leaf")), "Polar.decode")
+        return out
