@@ -44,6 +44,7 @@
  *   qldpc_mc_set_channel / _awgn_table   the channel of the fixed-point sims: BPSK over AWGN, 6-bit received values  ML/BPSK_nrldpc_sim_RM_FP.m
  *   qldpc_mc_sweep_tables                 the Eb/N0 points of those sims side by side in one batch, a table per point    ML/sim_results.m
  *   qldpc_polar_*                         the polar encoder and SC decoder of the fourth curve of that figure   ML/nrpolar_encode.m, nrpolar_scdecode.m, nrpolar_scdecode_FP.m
+ *   qldpc_polar_list_* / _crc_host        the list decoder with a CRC of the fifth curve (list 4, CRC 11)          ML/nrpolar_sclistdecode_FP.m
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -1586,6 +1587,49 @@ int    qldpc_polar_decode_dev(qldpc_polar *p, int n_frames, const void *d_llr, c
 int    qldpc_polar_encode_host(int log2_n, int n_frames, const uint32_t *u, uint32_t *x);
 int    qldpc_polar_decode_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
                                const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Polar codes: the CRC-aided successive-cancellation LIST decoder (qldpc_polar_list_*), beside the SC decoder above and with its sizes, rows,
+ * code, messages and inputs.  The definition is csrc/qldpc_polar_list_core.h, shared by the kernels (csrc/qldpc_kernels_polar_list.h) and the
+ * host mirror (csrc/qldpc_polar_list_host.c), which agree bit for bit in both message types.  This is the reference's
+ * nrpolar_sclistdecode_FP.m (list 4, CRC 11) without its paths of infinite metric, which never change a result.
+ *
+ *   size      1 <= log2_n <= 16 (QLDPC_ESIZE: the scratch grows with list_size x N); list_size 1, 2, 4 or 8 (QLDPC_ESIZE).
+ *   paths     a list holds up to list_size paths, each with a metric >= 0: an exact uint32 with QLDPC_POLAR_I8, a float with QLDPC_POLAR_F32.
+ *             One path of metric 0 at the start; leaves in natural order, every path's leaf belief D computed as the SC decoder computes it.
+ *   frozen    bit = the frozen value; metric += |D| if (D < 0) != bit.  Nothing is reordered.
+ *   info      P live paths give 2P candidates: c < P is path c with bit (D_c < 0) and metric m_c, P + c is path c with the other bit and metric
+ *             m_c + |D_c| (one float add).  The new list is the min(list_size, 2P) smallest in the order (metric, candidate index), new path k
+ *             the k-th of them, so the list is sorted at every information leaf and only there.
+ *   CRC       crc_len 0 .. 32, at most n_info; crc_poly holds the low crc_len coefficients, x^crc_len is implied (QLDPC_ESIZE otherwise).
+ *             Register form, zero start, MSB first, no reflection, no final XOR: top = msb(r) ^ bit; r = (r << 1) & mask; if top: r ^= poly.
+ *             It runs over a path's n_info information bits in the caller's order (bit m = u[info_pos[m]]).  The reference's CRC11 is
+ *             crc_len = 11, crc_poly = 0x621; a word with its CRC appended has remainder 0.
+ *   pick      the first path in list order whose remainder is crc[frame] (0 where crc is NULL), or path 0 where none matches; pick[frame] is its
+ *             index, or -1.  crc_len = 0: every path matches, pick = 0, and a crc row is refused (QLDPC_EINVAL).  list_size = 1 with
+ *             crc_len = 0 is qldpc_polar_decode_* bit for bit in u, info and x.
+ *   outputs   each may be NULL: u, info and x of the picked path, shaped and packed as the SC calls'; pick[n_frames]; metric[n_frames][list_size]
+ *             the final metrics in list order, uint32 or float, 0xffffffff or +inf past the live paths (2^n_info of them where that is below
+ *             list_size); list_x[n_frames][list_size][ceil(N/32)] every path's re-encoded word, zeros past the live paths.
+ *
+ * A context owns its scratch (qldpc_polar_list_device_bytes: per frame about list_size x (N beliefs + N/4 bytes of bit levels) + N beliefs, and
+ * 2 list_size rows); QLDPC_ENOMEM where it does not fit.  A call allocates nothing, is asynchronous on the context's stream and a context is not
+ * re-entrant; n_frames = 0 is a no-op; every argument check runs before the first HIP call.  Other refusals as the SC calls'.
+ * qldpc_polar_crc_host: Alice's remainder of packed rows of n_bits bits each, rows[n_frames][ceil(n_bits/32)] -> crc[n_frames].
+ */
+typedef struct qldpc_polar_list qldpc_polar_list;
+int    qldpc_polar_list_create(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int list_size,
+                               int crc_len, uint32_t crc_poly, int max_frames, int device, qldpc_polar_list **out);
+void   qldpc_polar_list_free(qldpc_polar_list *p);
+size_t qldpc_polar_list_device_bytes(const qldpc_polar_list *p);
+int    qldpc_polar_list_set_stream(qldpc_polar_list *p, void *hip_stream);
+int    qldpc_polar_list_decode_dev(qldpc_polar_list *p, int n_frames, const void *d_llr, const uint32_t *d_frozen_u, const uint32_t *d_crc,
+                                   uint32_t *d_u, uint32_t *d_info, uint32_t *d_x, int32_t *d_pick, void *d_metric, uint32_t *d_list_x);
+/* host mirrors, no device needed */
+int    qldpc_polar_list_decode_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int list_size, int crc_len,
+                                    uint32_t crc_poly, int n_frames, const void *llr, const uint32_t *frozen_u, const uint32_t *crc,
+                                    uint32_t *u, uint32_t *info, uint32_t *x, int32_t *pick, void *metric, uint32_t *list_x);
+int    qldpc_polar_crc_host(int crc_len, uint32_t crc_poly, int n_bits, int n_frames, const uint32_t *rows, uint32_t *crc);
 
 #ifdef __cplusplus
 }

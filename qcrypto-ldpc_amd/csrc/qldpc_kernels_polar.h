@@ -20,7 +20,8 @@
  *
  * ENCODER.  pl_encode_tiles: a workgroup takes PL_ENC_TILE words of one row into LDS, the stages below 32 inside each word on the way in
  * (pl_enc_word), the word stages up to the tile in LDS.  pl_encode_columns: the stages above a tile, a thread per column of words PL_ENC_TILE
- * apart, in place (nobody else touches its column).
+ * apart, in place (nobody else touches its column).  The kernels that are no templates are static: the list decoder's unit
+ * (qldpc_kernels_polar_list.h) includes this file too.
  */
 #ifndef QLDPC_KERNELS_POLAR_H
 #define QLDPC_KERNELS_POLAR_H
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(PL_GROUP) void pl_decode(M m, int n, int n_frames, 
 }
 
 /* the rows the caller asked for, from the scratch: a thread per (group, word, lane), lanes fastest; info bit m = u[info_pos[m]] */
-__global__ __launch_bounds__(256) void pl_outputs(int n, int n_frames, int n_info, const int *__restrict__ info_pos, const uint32_t *__restrict__ Us,
+static __global__ __launch_bounds__(256) void pl_outputs(int n, int n_frames, int n_info, const int *__restrict__ info_pos, const uint32_t *__restrict__ Us,
                                                   const uint32_t *__restrict__ Xs, uint32_t *__restrict__ d_u, uint32_t *__restrict__ d_info, uint32_t *__restrict__ d_x)
 {
     const size_t W = (size_t)pl_words(n), Wi = ((size_t)n_info + 31u) / 32u;
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(256) void pl_outputs(int n, int n_frames, int n_inf
 
 /* grid = frames x tiles of a row (a row's tiles together), PL_ENC_LANES lanes: T = min(W, PL_ENC_TILE) words of a row, the stages inside a word and the word stages below T.
    In place allowed: a workgroup reads its tile whole before it writes it */
-__global__ __launch_bounds__(PL_ENC_LANES) void pl_encode_tiles(int n, const uint32_t *u, uint32_t *x)
+static __global__ __launch_bounds__(PL_ENC_LANES) void pl_encode_tiles(int n, const uint32_t *u, uint32_t *x)
 {
     __shared__ uint32_t s[PL_ENC_TILE];
     const size_t W = (size_t)pl_words(n), T = W < PL_ENC_TILE ? W : PL_ENC_TILE;
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(PL_ENC_LANES) void pl_encode_tiles(int n, const uin
 
 /* the stages h = PL_ENC_TILE, 2 PL_ENC_TILE, .. of rows of W > PL_ENC_TILE words: a thread per (frame, column o < PL_ENC_TILE), in place on the words
    o + r PL_ENC_TILE, r < R = W / PL_ENC_TILE */
-__global__ __launch_bounds__(PL_ENC_LANES) void pl_encode_columns(int n, int n_frames, uint32_t *x)
+static __global__ __launch_bounds__(PL_ENC_LANES) void pl_encode_columns(int n, int n_frames, uint32_t *x)
 {
     const size_t W = (size_t)pl_words(n), R = W >> PL_ENC_TILE_LOG;
     const size_t idx = (size_t)blockIdx.x * PL_ENC_LANES + threadIdx.x, o = idx & (PL_ENC_TILE - 1u), frame = idx >> PL_ENC_TILE_LOG;

@@ -1,5 +1,5 @@
-"""Polar codes (qldpc_polar_*): the batched encoder and successive-cancellation decoder on the device, their host mirrors, and a
-polarization-weight order for callers without a standard's reliability table."""
+"""Polar codes (qldpc_polar_*): the batched encoder, the successive-cancellation decoder and the CRC-aided list decoder on the device, their
+host mirrors, and a polarization-weight order for callers without a standard's reliability table."""
 import ctypes as C
 
 import numpy as np
@@ -8,6 +8,8 @@ from ._lib import _L, _Handle, _chk, _create, _dev_empty, _dev_rows, _ip, _sig, 
 
 POLAR_I8, POLAR_F32 = 0, 1
 POLAR_MAX_LOG2N = 20
+POLAR_LIST_MAX_LOG2N = 16
+POLAR_CRC11 = (11, 0x621)          # the CRC of the reference's list decoder: crc_len, crc_poly
 
 _sig("qldpc_polar_create", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)])
 _sig("qldpc_polar_free", None, [_vp])
@@ -17,6 +19,14 @@ _sig("qldpc_polar_encode_dev", C.c_int, [_vp, C.c_int, _vp, _vp])
 _sig("qldpc_polar_decode_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp])
 _sig("qldpc_polar_encode_host", C.c_int, [C.c_int, C.c_int, _up, _up])
 _sig("qldpc_polar_decode_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _vp, _up, _up, _up, _up, _vp])
+_sig("qldpc_polar_list_create", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.POINTER(_vp)])
+_sig("qldpc_polar_list_free", None, [_vp])
+_sig("qldpc_polar_list_device_bytes", C.c_size_t, [_vp])
+_sig("qldpc_polar_list_set_stream", C.c_int, [_vp, _vp])
+_sig("qldpc_polar_list_decode_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+_sig("qldpc_polar_list_decode_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, _vp, _up, _up, _up, _up, _up,
+                                               _ip, _vp, _up])
+_sig("qldpc_polar_crc_host", C.c_int, [C.c_int, C.c_uint32, C.c_int, C.c_int, _up, _up])
 
 
 def _messages(messages):
@@ -126,4 +136,93 @@ class Polar(_Handle):
         ptr = lambda name: _vp(out[name].data_ptr()) if name in out and out[name].numel() else None
         self._on_current_stream()
         _chk(_L.qldpc_polar_decode_dev(self._h, F, pl, pf, ptr("u"), ptr("info"), ptr("x"), ptr("leaf")), "Polar.decode")
+        return out
+
+
+# ---- the CRC-aided list decoder ------------------------------------------------------------------------------------------------------------
+
+LIST_OUTPUTS = ("u", "info", "x", "pick", "metric", "list_x")
+
+
+def polar_crc_host(crc_len, crc_poly, bits_rows, n_bits):
+    """Alice's CRC (qldpc_polar_crc_host): packed rows uint32 [F, ceil(n_bits/32)] -> the remainders uint32 [F] of the first n_bits bits of each"""
+    rows = np.ascontiguousarray(bits_rows, dtype=np.uint32)
+    if rows.ndim != 2 or rows.shape[1] != (max(int(n_bits), 0) + 31) // 32:
+        raise QldpcError(-6, "polar_crc_host: rows must be [frames, ceil(n_bits / 32)] words")
+    crc = np.zeros(rows.shape[0], np.uint32)
+    _chk(_L.qldpc_polar_crc_host(int(crc_len), int(crc_poly) & 0xffffffff, int(n_bits), rows.shape[0], rows.ctypes.data_as(_up), crc.ctypes.data_as(_up)),
+         "polar_crc_host")
+    return crc
+
+
+def polar_list_decode_host(log2_n, info_pos, llr, frozen=None, crc=None, messages="i8", maxq=31, list_size=4, crc_len=0, crc_poly=0, want=LIST_OUTPUTS):
+    """the list decoder's mirror (qldpc_polar_list_decode_host): llr [F, N] int8 or float32 by `messages`, frozen uint32 [F, W] or None, crc uint32
+    [F] the expected remainders or None (zeros) -> dict of those of u, info, x uint32 rows of the picked path, pick int32 [F] (-1: no path
+    matched), metric [F, L] uint32 or float32, list_x uint32 [F, L, W] that `want` names"""
+    kind, dt = _messages(messages)
+    pos = np.ascontiguousarray(info_pos, dtype=np.int32).ravel()
+    llr = np.ascontiguousarray(llr, dtype=dt)
+    n, L = int(log2_n), int(list_size)
+    N, W = (1 << n) if 0 <= n <= POLAR_LIST_MAX_LOG2N else 0, _words(n)
+    if N and (llr.ndim != 2 or llr.shape[1] != N):
+        raise QldpcError(-6, "polar_list_decode_host: llr must be [frames, N = %d]" % N)
+    F = llr.shape[0] if llr.ndim == 2 else 0
+    fz = cr = None
+    if frozen is not None:
+        fz = np.ascontiguousarray(frozen, dtype=np.uint32)
+        if fz.shape != (F, W):
+            raise QldpcError(-6, "polar_list_decode_host: frozen must be [frames, %d] words" % W)
+    if crc is not None:
+        cr = np.ascontiguousarray(crc, dtype=np.uint32)
+        if cr.shape != (F,):
+            raise QldpcError(-6, "polar_list_decode_host: crc must be [frames]")
+    Ls = L if 1 <= L <= 8 else 1
+    shapes = dict(u=((F, W), np.uint32), info=((F, (pos.size + 31) // 32), np.uint32), x=((F, W), np.uint32), pick=((F,), np.int32),
+                  metric=((F, Ls), np.uint32 if kind == POLAR_I8 else np.float32), list_x=((F, Ls, W), np.uint32))
+    out = {k: np.zeros(*shapes[k]) for k in LIST_OUTPUTS if k in want}
+    p = lambda a, t=_up: a.ctypes.data_as(t) if a is not None else None
+    _chk(_L.qldpc_polar_list_decode_host(n, pos.size, pos.ctypes.data_as(_ip), kind, int(maxq), L, int(crc_len), int(crc_poly) & 0xffffffff, F,
+                                         llr.ctypes.data_as(_vp), p(fz), p(cr), p(out.get("u")), p(out.get("info")), p(out.get("x")),
+                                         p(out.get("pick"), _ip), p(out.get("metric"), _vp), p(out.get("list_x"))), "polar_list_decode_host")
+    return out
+
+
+class PolarList(_Handle):
+    """The CRC-aided successive-cancellation list decoder of a polar code on the device: up to `list_size` (1, 2, 4, 8) paths a frame, a lane of a
+    wave holding all paths of its frame, and the pick of the first path in list order whose CRC over the information bits is the expected one.
+    Device tensors in, device tensors out, asynchronous on torch's current stream."""
+    _free = _L.qldpc_polar_list_free
+
+    def __init__(self, log2_n, info_pos, messages="i8", maxq=31, list_size=4, crc_len=0, crc_poly=0, max_frames=4096, device=0):
+        self.messages, self._np_dtype = _messages(messages)
+        pos = np.ascontiguousarray(info_pos, dtype=np.int32).ravel()
+        self._h = _create("PolarList", _L.qldpc_polar_list_create, int(log2_n), pos.size, pos.ctypes.data_as(_ip), self.messages, int(maxq), int(list_size),
+                          int(crc_len), int(crc_poly) & 0xffffffff, int(max_frames), int(device))
+        self.log2_n, self.N, self.K, self.W, self.Wi = int(log2_n), 1 << int(log2_n), pos.size, _words(log2_n), (pos.size + 31) // 32
+        self.info_pos, self.maxq, self.max_frames, self.device = pos, int(maxq), int(max_frames), int(device)
+        self.list_size, self.crc_len, self.crc_poly = int(list_size), int(crc_len), int(crc_poly)
+
+    def device_bytes(self):
+        return int(_L.qldpc_polar_list_device_bytes(self._h))
+
+    def decode(self, llr, frozen=None, crc=None, want=LIST_OUTPUTS):
+        """llr [F, N] int8 or float32 (the context's messages), frozen int32 / uint32 [F, W] or None (zeros), crc int32 / uint32 [F] the expected
+        remainders or None (zeros) -> dict of device tensors, those `want` names: u, info, x int32 rows of the picked path as Polar.decode gives
+        them, pick int32 [F], metric [F, L] int32 (the uint32's bits) or float32, list_x int32 [F, L, W]"""
+        torch = _torch()
+        words = (torch.int32, torch.uint32)
+        pl = _dev_rows(llr, None, self.N, (torch.int8 if self.messages == POLAR_I8 else torch.float32,), "llr")
+        F, L = llr.shape[0], self.list_size
+        pf = _dev_rows(frozen, F, self.W, words, "frozen")
+        pc = None
+        if crc is not None:
+            assert crc.is_cuda and crc.dtype in words and crc.is_contiguous() and tuple(crc.shape) == (F,), "crc"
+            pc = _vp(crc.data_ptr())
+        shapes = dict(u=((F, self.W), torch.int32), info=((F, self.Wi), torch.int32), x=((F, self.W), torch.int32), pick=((F,), torch.int32),
+                      metric=((F, L), torch.int32 if self.messages == POLAR_I8 else torch.float32), list_x=((F, L, self.W), torch.int32))
+        out = {k: _dev_empty(llr.device, *shapes[k]) for k in LIST_OUTPUTS if k in want}
+        ptr = lambda name: _vp(out[name].data_ptr()) if name in out and out[name].numel() else None
+        _chk(_L.qldpc_polar_list_set_stream(self._h, _stream_arg(None, self.device)), "PolarList.set_stream")
+        _chk(_L.qldpc_polar_list_decode_dev(self._h, F, pl, pf, pc, ptr("u"), ptr("info"), ptr("x"), ptr("pick"), ptr("metric"), ptr("list_x")),
+             "PolarList.decode")
         return out
