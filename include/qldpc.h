@@ -1573,10 +1573,22 @@ int    qldpc_mc_guess_next_host(int guess_bits, int batch, uint64_t pool, uint64
  * nothing, is asynchronous on the context's stream (qldpc_polar_set_stream, NULL = the null stream) and a context is not re-entrant.
  * QLDPC_ESIZE: n_frames > max_frames; QLDPC_EINVAL: n_frames < 0, a missing pointer, max_frames outside 1 .. 2^24, messages neither value.
  * n_frames = 0 is a no-op.  Every argument check runs before the first HIP call.  qldpc_polar_encode_dev may run in place (d_x = d_u).
+ *
+ * The decoder has two forms, the same function bit for bit in all four outputs; the library does not choose, `form` is the caller's.
+ *   QLDPC_POLAR_LANES  a frame is one lane, a wave decodes 64 frames: for batches (N = 1 024 x 20 000 frames).  qldpc_polar_create means this.
+ *   QLDPC_POLAR_WIDE   a workgroup per frame, lanes over the beliefs of a node, the levels up to 2^12 beliefs in LDS, a 32-leaf block on 32 lanes
+ *                      (csrc/qldpc_kernels_polar_wide.h; the memory plan is csrc/qldpc_polar_wide_core.h, which qldpc_polar_decode_wide_host
+ *                      walks one element at a time on the host, with the arguments and results of qldpc_polar_decode_host): for few long frames.
+ *                      Such a context owns less than N beliefs and 8N / 32 bytes of rows per frame of max_frames, and every call above serves it
+ *                      with the same contract.
+ * qldpc_polar_create_form: a form that is neither is QLDPC_EINVAL; every other refusal is qldpc_polar_create's.
  */
 typedef struct qldpc_polar qldpc_polar;
 enum { QLDPC_POLAR_I8 = 0, QLDPC_POLAR_F32 = 1 };
+enum { QLDPC_POLAR_LANES = 0, QLDPC_POLAR_WIDE = 1 };
 int    qldpc_polar_create(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int max_frames, int device, qldpc_polar **out);
+int    qldpc_polar_create_form(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int max_frames, int form, int device,
+                               qldpc_polar **out);
 void   qldpc_polar_free(qldpc_polar *p);
 size_t qldpc_polar_device_bytes(const qldpc_polar *p);
 int    qldpc_polar_set_stream(qldpc_polar *p, void *hip_stream);
@@ -1587,6 +1599,8 @@ int    qldpc_polar_decode_dev(qldpc_polar *p, int n_frames, const void *d_llr, c
 int    qldpc_polar_encode_host(int log2_n, int n_frames, const uint32_t *u, uint32_t *x);
 int    qldpc_polar_decode_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
                                const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf);
+int    qldpc_polar_decode_wide_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
+                                    const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf);
 
 /* ------------------------------------------------------------------------------------------------------------------------------------------
  * Polar codes: the CRC-aided successive-cancellation LIST decoder (qldpc_polar_list_*), beside the SC decoder above and with its sizes, rows,

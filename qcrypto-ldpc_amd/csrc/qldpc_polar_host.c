@@ -98,29 +98,41 @@ static size_t pl_off(int n, int l) { return ((size_t)2 << n) - ((size_t)2 << l);
 PL_HOST_DECODER(i8, int8_t, int, PL_I8_LOAD, pl_i8_f, PL_I8_G)
 PL_HOST_DECODER(f32, float, float, PL_F32_LOAD, pl_f32_f, pl_f32_g)
 
-int qldpc_polar_decode_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
-                            const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf)
+/* the argument checks of a host decode (`who` names it in the messages) and, where they pass, the code's frozen mask: a row the caller frees */
+int pl_host_decode_args(const char *who, int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr, uint32_t **frozen_mask)
 {
-    if (pl_check_size(log2_n)) { qldpc_set_error("polar_decode_host: log2_n=%d (1 .. %d)", log2_n, PL_MAX_LOG2N); return QLDPC_ESIZE; }
-    if (messages != QLDPC_POLAR_I8 && messages != QLDPC_POLAR_F32) { qldpc_set_error("polar_decode_host: messages=%d (QLDPC_POLAR_I8 or QLDPC_POLAR_F32)", messages); return QLDPC_EINVAL; }
+    *frozen_mask = NULL;
+    if (pl_check_size(log2_n)) { qldpc_set_error("%s: log2_n=%d (1 .. %d)", who, log2_n, PL_MAX_LOG2N); return QLDPC_ESIZE; }
+    if (messages != QLDPC_POLAR_I8 && messages != QLDPC_POLAR_F32) { qldpc_set_error("%s: messages=%d (QLDPC_POLAR_I8 or QLDPC_POLAR_F32)", who, messages); return QLDPC_EINVAL; }
     if (pl_check_maxq(messages, maxq)) {
-        qldpc_set_error("polar_decode_host: maxq=%d (1 .. %d: f is not saturated and gives maxq + 1, which an int8 holds up to 127; use maxq <= %d)", maxq, PL_MAX_MAXQ, PL_MAX_MAXQ);
+        qldpc_set_error("%s: maxq=%d (1 .. %d: f is not saturated and gives maxq + 1, which an int8 holds up to 127; use maxq <= %d)", who, maxq, PL_MAX_MAXQ, PL_MAX_MAXQ);
         return QLDPC_ESIZE;
     }
-    if (n_frames < 0) { qldpc_set_error("polar_decode_host: n_frames=%d is negative", n_frames); return QLDPC_EINVAL; }
-    const long N = 1l << log2_n, W = pl_words(log2_n), Wi = (n_info + 31) / 32;
+    if (n_frames < 0) { qldpc_set_error("%s: n_frames=%d is negative", who, n_frames); return QLDPC_EINVAL; }
+    const long W = pl_words(log2_n);
     uint32_t *mask = (uint32_t *)calloc((size_t)W, sizeof(uint32_t));
     if (!mask) return QLDPC_ENOMEM;
     int rc = pl_mark_info(log2_n, n_info, info_pos, mask);
     if (rc) {
-        qldpc_set_error(rc == PL_EINVAL ? "polar_decode_host: info_pos names a position twice (positions must be distinct)"
-                                        : "polar_decode_host: n_info=%d positions, each in 0 .. N - 1, are required (0 <= n_info <= N)", n_info);
+        if (rc == PL_EINVAL) qldpc_set_error("%s: info_pos names a position twice (positions must be distinct)", who);
+        else qldpc_set_error("%s: n_info=%d positions, each in 0 .. N - 1, are required (0 <= n_info <= N)", who, n_info);
         free(mask);
         return rc;
     }
-    if (n_frames > 0 && !llr) { qldpc_set_error("polar_decode_host: llr is NULL"); free(mask); return QLDPC_EINVAL; }
+    if (n_frames > 0 && !llr) { qldpc_set_error("%s: llr is NULL", who); free(mask); return QLDPC_EINVAL; }
     const uint32_t valid = pl_row_mask(log2_n);
     for (long w = 0; w < W; w++) mask[w] = ~mask[w] & valid;      /* the frozen mask */
+    *frozen_mask = mask;
+    return QLDPC_OK;
+}
+
+int qldpc_polar_decode_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
+                            const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf)
+{
+    uint32_t *mask;
+    const int rc = pl_host_decode_args("polar_decode_host", log2_n, n_info, info_pos, messages, maxq, n_frames, llr, &mask);
+    if (rc) return rc;
+    const long N = 1l << log2_n, W = pl_words(log2_n), Wi = (n_info + 31) / 32;
     const size_t esz = messages == QLDPC_POLAR_I8 ? sizeof(int) : sizeof(float), lsz = messages == QLDPC_POLAR_I8 ? 1 : sizeof(float);
     void *B = malloc(esz * 2 * (size_t)N);
     uint32_t *rows = (uint32_t *)malloc(sizeof(uint32_t) * 2 * (size_t)W);

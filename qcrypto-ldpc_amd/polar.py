@@ -7,11 +7,13 @@ import numpy as np
 from ._lib import _L, _Handle, _chk, _create, _dev_empty, _dev_rows, _ip, _sig, _stream_arg, _torch, _up, _vp, QldpcError
 
 POLAR_I8, POLAR_F32 = 0, 1
+POLAR_FORMS = {"lanes": 0, "wide": 1}
 POLAR_MAX_LOG2N = 20
 POLAR_LIST_MAX_LOG2N = 16
 POLAR_CRC11 = (11, 0x621)          # the CRC of the reference's list decoder: crc_len, crc_poly
 
 _sig("qldpc_polar_create", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)])
+_sig("qldpc_polar_create_form", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)])
 _sig("qldpc_polar_free", None, [_vp])
 _sig("qldpc_polar_device_bytes", C.c_size_t, [_vp])
 _sig("qldpc_polar_set_stream", C.c_int, [_vp, _vp])
@@ -19,6 +21,7 @@ _sig("qldpc_polar_encode_dev", C.c_int, [_vp, C.c_int, _vp, _vp])
 _sig("qldpc_polar_decode_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp])
 _sig("qldpc_polar_encode_host", C.c_int, [C.c_int, C.c_int, _up, _up])
 _sig("qldpc_polar_decode_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _vp, _up, _up, _up, _up, _vp])
+_sig("qldpc_polar_decode_wide_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _vp, _up, _up, _up, _up, _vp])
 _sig("qldpc_polar_list_create", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.POINTER(_vp)])
 _sig("qldpc_polar_list_free", None, [_vp])
 _sig("qldpc_polar_list_device_bytes", C.c_size_t, [_vp])
@@ -35,6 +38,15 @@ def _messages(messages):
     if messages in ("f32", POLAR_F32):
         return POLAR_F32, np.float32
     raise QldpcError(-1, "polar: messages=%r ('i8' or 'f32')" % (messages,))
+
+
+def _form(form):
+    """'lanes' or 'wide'; a number goes to the library as it is, which refuses what is neither"""
+    if isinstance(form, str):
+        if form not in POLAR_FORMS:
+            raise QldpcError(-1, "polar: form=%r ('lanes' or 'wide')" % (form,))
+        return POLAR_FORMS[form]
+    return int(form)
 
 
 def _words(log2_n):
@@ -63,41 +75,54 @@ def polar_encode_host(log2_n, u):
     return x.reshape(u.shape)
 
 
-def polar_decode_host(log2_n, info_pos, llr, frozen=None, messages="i8", maxq=31, leaf=False):
-    """the SC decoder's mirror (qldpc_polar_decode_host): llr [F, N] int8 or float32 by `messages`, frozen uint32 [F, ceil(N/32)] or None
-    -> dict(u uint32 [F, W], info uint32 [F, ceil(K/32)], x uint32 [F, W]) and, with leaf=True, leaf [F, N] of the messages' type"""
+def _decode_host(fn, who, log2_n, info_pos, llr, frozen, messages, maxq, leaf):
+    """the marshalling of the two host decodes, which take the same arguments"""
     kind, dt = _messages(messages)
     pos = np.ascontiguousarray(info_pos, dtype=np.int32).ravel()
     llr = np.ascontiguousarray(llr, dtype=dt)
     n = int(log2_n)
     N, W = (1 << n) if 0 <= n <= POLAR_MAX_LOG2N else 0, _words(n)
     if N and (llr.ndim != 2 or llr.shape[1] != N):
-        raise QldpcError(-6, "polar_decode_host: llr must be [frames, N = %d]" % N)
+        raise QldpcError(-6, "%s: llr must be [frames, N = %d]" % (who, N))
     F = llr.shape[0] if llr.ndim == 2 else 0
     fz = None
     if frozen is not None:
         fz = np.ascontiguousarray(frozen, dtype=np.uint32)
         if fz.shape != (F, W):
-            raise QldpcError(-6, "polar_decode_host: frozen must be [frames, %d] words" % W)
+            raise QldpcError(-6, "%s: frozen must be [frames, %d] words" % (who, W))
     out = dict(u=np.zeros((F, W), np.uint32), info=np.zeros((F, (pos.size + 31) // 32), np.uint32), x=np.zeros((F, W), np.uint32))
     if leaf:
         out["leaf"] = np.zeros((F, N), dt)
     p = lambda a: a.ctypes.data_as(_up) if a is not None else None
-    _chk(_L.qldpc_polar_decode_host(n, pos.size, pos.ctypes.data_as(_ip), kind, int(maxq), F, llr.ctypes.data_as(_vp), p(fz), p(out["u"]), p(out["info"]),
-                                    p(out["x"]), out["leaf"].ctypes.data_as(_vp) if leaf else None), "polar_decode_host")
+    _chk(fn(n, pos.size, pos.ctypes.data_as(_ip), kind, int(maxq), F, llr.ctypes.data_as(_vp), p(fz), p(out["u"]), p(out["info"]), p(out["x"]),
+            out["leaf"].ctypes.data_as(_vp) if leaf else None), who)
     return out
+
+
+def polar_decode_host(log2_n, info_pos, llr, frozen=None, messages="i8", maxq=31, leaf=False):
+    """the SC decoder's mirror (qldpc_polar_decode_host): llr [F, N] int8 or float32 by `messages`, frozen uint32 [F, ceil(N/32)] or None
+    -> dict(u uint32 [F, W], info uint32 [F, ceil(K/32)], x uint32 [F, W]) and, with leaf=True, leaf [F, N] of the messages' type"""
+    return _decode_host(_L.qldpc_polar_decode_host, "polar_decode_host", log2_n, info_pos, llr, frozen, messages, maxq, leaf)
+
+
+def polar_decode_wide_host(log2_n, info_pos, llr, frozen=None, messages="i8", maxq=31, leaf=False):
+    """the host walk of the wide form's memory plan (qldpc_polar_decode_wide_host): the arguments and the results of polar_decode_host, bit for bit"""
+    return _decode_host(_L.qldpc_polar_decode_wide_host, "polar_decode_wide_host", log2_n, info_pos, llr, frozen, messages, maxq, leaf)
 
 
 class Polar(_Handle):
     """A polar code of N = 2^log2_n bits with information at `info_pos` (every other position frozen) on the device: encode() and the
-    successive-cancellation decode() of up to max_frames frames a call, 64 frames to a wave.  Device tensors in, device tensors out, asynchronous
-    on torch's current stream."""
+    successive-cancellation decode() of up to max_frames frames a call.  form="lanes": 64 frames to a wave, for batches; form="wide": a workgroup
+    to a frame, for few long frames.  The same function bit for bit, and the choice is the caller's.  Device tensors in, device tensors out,
+    asynchronous on torch's current stream."""
     _free = _L.qldpc_polar_free
 
-    def __init__(self, log2_n, info_pos, messages="i8", maxq=31, max_frames=4096, device=0):
+    def __init__(self, log2_n, info_pos, messages="i8", maxq=31, max_frames=4096, device=0, form="lanes"):
         self.messages, self._np_dtype = _messages(messages)
         pos = np.ascontiguousarray(info_pos, dtype=np.int32).ravel()
-        self._h = _create("Polar", _L.qldpc_polar_create, int(log2_n), pos.size, pos.ctypes.data_as(_ip), self.messages, int(maxq), int(max_frames), int(device))
+        self.form = _form(form)
+        self._h = _create("Polar", _L.qldpc_polar_create_form, int(log2_n), pos.size, pos.ctypes.data_as(_ip), self.messages, int(maxq), int(max_frames),
+                          self.form, int(device))
         self.log2_n, self.N, self.K, self.W, self.Wi = int(log2_n), 1 << int(log2_n), pos.size, _words(log2_n), (pos.size + 31) // 32
         self.info_pos, self.maxq, self.max_frames, self.device = pos, int(maxq), int(max_frames), int(device)
 
