@@ -9,8 +9,8 @@
  *              context's scratch.  Four neighbouring elements of a lane lie together and the lanes' quads follow each other (element e of lane t at
  *              (e / 4 * 64 + t) * 4 + e % 4), so that a wave reads or writes 64 quads in a row with one dword (int8) or dwordx4 (float) per lane.
  *              pl_load transposes the caller's frame-major rows into level n (and clamps int8 levels).
- *   levels >= 6  pl_decode produces level l from level l + 1 in steps of 32 elements: 16 quad loads issued together, 32 f or g, 8 quad stores.
- *              g reads its 32 re-encoded bits from one word of the lane's x row.
+ *   levels >= 6  pl_decode produces level l from level l + 1 in steps of 32 elements: 16 quad loads issued together, 32 f or g (pl_pair32), 8 quad stores
+ *              (pl_store32); the list decoder's levels >= 5 take the same step.  g reads its 32 re-encoded bits from one word of the lane's x row.
  *   levels <= 5  a leaf block (32 leaves; all N where N < 32, then read from the caller's rows directly) lives in registers: 32 + 16 + .. + 1
  *              beliefs, the recursion unrolled by templates, the frozen flags of the block one wave-uniform word and its frozen values one word of
  *              the frame's frozen row.
@@ -101,6 +101,19 @@ __device__ __forceinline__ void pl_pair32(const M &m, const pl_quad<typename M::
     }
 }
 
+/* the 32 beliefs R[] of a level step -> the quads q0 .. q0 + 7 of the lane */
+template <class M>
+__device__ __forceinline__ void pl_store32(pl_quad<typename M::mem> *V, size_t q0, const typename M::reg *R)
+{
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        pl_quad<typename M::mem> v;
+#pragma unroll
+        for (int e = 0; e < 4; e++) v.v[e] = (typename M::mem)R[4 * i + e];
+        V[(q0 + i) * PL_GROUP] = v;
+    }
+}
+
 /* a node of S leaves whose first leaf is bit POS (MSB-first) of the block's words: beliefs L[S] in registers -> decisions into u, the re-encoded
    bits of every finished node into x, leaf beliefs into leaf[] */
 template <int S, int POS, class M>
@@ -156,13 +169,7 @@ __global__ __launch_bounds__(PL_GROUP) void pl_decode(M m, int n, int n_frames, 
                 for (size_t k = 0; k < h; k += 32u) {
                     const uint32_t cw = is_g ? X[(w0 + (k >> 5)) * PL_GROUP] : 0u;
                     pl_pair32(m, V, qs + k / 4u, qs + (h + k) / 4u, is_g, cw, R);
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        pl_quad<mem> v;
-#pragma unroll
-                        for (int e = 0; e < 4; e++) v.v[e] = (mem)R[4 * i + e];
-                        Vw[(qd + k / 4u + i) * PL_GROUP] = v;
-                    }
+                    pl_store32<M>(Vw, qd + k / 4u, R);
                 }
             }
             const bool is_g = j != 0 && top == PL_SUB_LOG;
@@ -191,14 +198,7 @@ static __global__ __launch_bounds__(256) void pl_outputs(int n, int n_frames, in
     const uint32_t *U = Us + g * W * PL_GROUP + lane;
     if (d_u) d_u[frame * W + w] = U[w * PL_GROUP];
     if (d_x) d_x[frame * W + w] = Xs[(g * W + w) * PL_GROUP + lane];
-    if (d_info && w < Wi) {
-        uint32_t word = 0u;
-        for (size_t b = 0; b < 32u && w * 32u + b < (size_t)n_info; b++) {
-            const int p = info_pos[w * 32u + b];
-            word |= pl_bit(U[(size_t)(p >> 5) * PL_GROUP], p) << (31 - b);
-        }
-        d_info[frame * Wi + w] = word;
-    }
+    if (d_info && w < Wi) d_info[frame * Wi + w] = pl_info_word(U, PL_GROUP, info_pos, n_info, w);
 }
 
 /* grid = frames x tiles of a row (a row's tiles together), PL_ENC_LANES lanes: T = min(W, PL_ENC_TILE) words of a row, the stages inside a word and the word stages below T.

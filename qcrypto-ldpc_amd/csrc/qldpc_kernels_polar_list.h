@@ -125,13 +125,7 @@ __global__ __launch_bounds__(PL_GROUP) void pll_decode(M m, int n, int n_frames,
                     for (size_t q = 0; q < hq; q += 8u) {
                         reg R[32];
                         pl_pair32(m, V, src + q, src + hq + q, is_g, is_g ? cw[(q >> 3) * PL_GROUP] : 0u, R);
-#pragma unroll
-                        for (int o = 0; o < 8; o++) {
-                            pl_quad<mem> v;
-#pragma unroll
-                            for (int e = 0; e < 4; e++) v.v[e] = (mem)R[4 * o + e];
-                            V[(dst + q + o) * PL_GROUP] = v;
-                        }
+                        pl_store32<M>(V, dst + q, R);
                     }
                 } else if (l >= 2) {                              /* 4, 8 or 16 elements; g reads the h places before p of the open block */
                     const size_t hq = (size_t)1 << (l - 2), dst = pll_quad_off(n, L, l) + (size_t)k * hq;
@@ -272,14 +266,7 @@ __global__ __launch_bounds__(256) void pll_outputs(int n, int L, int P, int n_fr
     if (d_x) d_x[frame * W + w] = LX[row * W + w];
     if (d_list_x)
         for (size_t k = 0; k < (size_t)L; k++) d_list_x[(frame * (size_t)L + k) * W + w] = LX[(frame * (size_t)L + k) * W + w];
-    if (d_info && w < Wi) {
-        uint32_t word = 0u;
-        for (size_t b = 0; b < 32u && w * 32u + b < (size_t)n_info; b++) {
-            const int pos = info_pos[w * 32u + b];
-            word |= pl_bit(U[pos >> 5], pos) << (31 - b);
-        }
-        d_info[frame * Wi + w] = word;
-    }
+    if (d_info && w < Wi) d_info[frame * Wi + w] = pl_info_word(U, 1, info_pos, n_info, w);
     if (w == 0) {
         if (d_pick) d_pick[frame] = first;
         if (d_metric)

@@ -59,6 +59,17 @@ __device__ __forceinline__ void plw_level(const M &m, const typename M::mem *src
     }
 }
 
+/* belief k of level 5 of a leaf block from a and b, the beliefs k and 32 + k of level 6 as they lie in memory (RAW: in the caller's row, to be
+   clamped; else in LDS): a g with bit k of cw, the re-encoded word of the block before, or an f.  The loads are the caller's: a lane of the
+   32-lane block reads its two beliefs, the one-lane block reads level 6 by quads, which holds its instruction count */
+template <class M, bool RAW>
+__device__ __forceinline__ typename M::reg plw_level5(const M &m, typename M::mem a, typename M::mem b, bool is_g, uint32_t cw, unsigned k)
+{
+    typedef typename M::reg reg;
+    const reg ra = RAW ? m.load(a) : (reg)a, rb = RAW ? m.load(b) : (reg)b;
+    return is_g ? m.g(ra, rb, (cw >> (31u - k)) & 1u) : m.f(ra, rb);
+}
+
 /* lane t's copy of the value of lane t ^ (1 << log) among the first 32 lanes of a wave, all 32 at work: moves inside a row of 16 lanes
    (quad permutes; a quad reverse and a half-row mirror make t ^ 4; a row rotation by 8), a swizzle across the two rows */
 __device__ __forceinline__ int plw_xor_lane(int v, int log)
@@ -156,16 +167,16 @@ __global__ __launch_bounds__(LANES) void plw_decode(M m, int n, int C, int leaf_
             }
             __syncthreads();
         }
-        if (leaf_lanes) {                                         /* the leaf block, leaf t on lane t */
+        /* the leaf block: level 5 is a g after a block with no level above to renew; level 6 is the caller's row or the lowest level in LDS */
+        const bool is_g5 = j != 0 && top == PL_SUB_LOG, raw6 = n == PL_SUB_LOG + 1;
+        const mem *l6 = lds + plw_lds_off(C, PL_SUB_LOG + 1);
+        if (leaf_lanes) {                                         /* leaf t on lane t */
             if (tid < 32u) {
-                const bool is_g = j != 0 && top == PL_SUB_LOG;
-                const unsigned c = is_g ? (xw[jw - 1u] >> (31u - tid)) & 1u : 0u;
-                const mem *V = lds + plw_lds_off(C, PL_SUB_LOG + 1);
-                const bool raw = n == PL_SUB_LOG + 1;             /* level 6 is the caller's row */
-                const reg a = raw ? m.load(in[tid]) : (reg)V[tid], b = raw ? m.load(in[32u + tid]) : (reg)V[32u + tid];
                 uint32_t u, x;
                 reg leaf;
-                plw_leaf_lanes(m, is_g ? m.g(a, b, c) : m.f(a, b), tid, fmw[jw], fvw[jw], u, x, leaf);
+                const uint32_t cw = is_g5 ? xw[jw - 1u] : 0u;
+                const reg b5 = raw6 ? plw_level5<M, true>(m, in[tid], in[32u + tid], is_g5, cw, tid) : plw_level5<M, false>(m, l6[tid], l6[32u + tid], is_g5, cw, tid);
+                plw_leaf_lanes(m, b5, tid, fmw[jw], fvw[jw], u, x, leaf);
                 if (leaf_out) leaf_out[frame * N + j * 32u + tid] = (mem)leaf;
                 if (tid == 0) {
                     uw[jw] = u;
@@ -181,24 +192,17 @@ __global__ __launch_bounds__(LANES) void plw_decode(M m, int n, int C, int leaf_
             }
         } else if (tid == 0) {                                    /* the leaf block on one lane */
             reg R[32], leaf[32];
-            const bool is_g = j != 0 && top == PL_SUB_LOG;
-            const uint32_t cw = is_g ? xw[jw - 1u] : 0u;
-            if (n == PL_SUB_LOG + 1) {                            /* level 6 is the caller's row */
+            const uint32_t cw = is_g5 ? xw[jw - 1u] : 0u;
+            if (raw6) {
 #pragma unroll
-                for (int k = 0; k < 32; k++) {
-                    const reg a = m.load(in[k]), b = m.load(in[32 + k]);
-                    R[k] = is_g ? m.g(a, b, (cw >> (31 - k)) & 1u) : m.f(a, b);
-                }
+                for (int k = 0; k < 32; k++) R[k] = plw_level5<M, true>(m, in[k], in[32 + k], is_g5, cw, (unsigned)k);
             } else {
-                const pl_quad<mem> *V = (const pl_quad<mem> *)(lds + plw_lds_off(C, PL_SUB_LOG + 1));
+                const pl_quad<mem> *V = (const pl_quad<mem> *)l6;
 #pragma unroll
                 for (int i = 0; i < 8; i++) {
                     const pl_quad<mem> a = V[i], b = V[8 + i];
 #pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const int k = 4 * i + e;
-                        R[k] = is_g ? m.g((reg)a.v[e], (reg)b.v[e], (cw >> (31 - k)) & 1u) : m.f((reg)a.v[e], (reg)b.v[e]);
-                    }
+                    for (int e = 0; e < 4; e++) R[4 * i + e] = plw_level5<M, false>(m, a.v[e], b.v[e], is_g5, cw, (unsigned)(4 * i + e));
                 }
             }
             uint32_t u = 0u, x = 0u;
@@ -225,14 +229,7 @@ __global__ __launch_bounds__(LANES) void plw_decode(M m, int n, int C, int leaf_
     __syncthreads();
     if (d_info) {                                                 /* info bit i = u[info_pos[i]], the caller's order */
         const size_t Wi = ((size_t)n_info + 31u) / 32u;
-        for (size_t w = tid; w < Wi; w += LANES) {
-            uint32_t word = 0u;
-            for (size_t b = 0; b < 32u && w * 32u + b < (size_t)n_info; b++) {
-                const int p = info_pos[w * 32u + b];
-                word |= pl_bit(U[(size_t)(p >> 5)], p) << (31 - b);
-            }
-            d_info[frame * Wi + w] = word;
-        }
+        for (size_t w = tid; w < Wi; w += LANES) d_info[frame * Wi + w] = pl_info_word(U, 1, info_pos, n_info, w);
     }
 }
 

@@ -14,7 +14,8 @@
  *   I8         sat clamps to [-(maxq + 1), maxq]; f is NOT saturated (f(-32, -32) = +32 at maxq = 31), so beliefs live in [-(maxq + 1), maxq + 1]
  *              and maxq <= PL_MAX_MAXQ = 126 keeps them in an int8.  Inputs are int8 levels, clamped into [-(maxq + 1), maxq] on load.
  *   F32        sat is the identity, g is ONE float add or subtract (compile with -ffp-contract=off), inputs finite.
- *   outputs    u (all N decisions), info (bit m = u[info_pos[m]], the caller's order), x (the root's re-encoded word), leaf (the N leaf beliefs).
+ *   outputs    u (all N decisions), info (bit m = u[info_pos[m]], the caller's order: pl_info_word), x (the root's re-encoded word), leaf (the N
+ *              leaf beliefs).
  *
  * The traversal is the same for every frame; only the values differ.  Both sides run it by leaf blocks of PL_SUB = min(N, 32) leaves: the decisions of
  * a block are one packed word, its re-encoded word is pl_enc_word of that, and everything above a block is word XORs (pl_combine_words).
@@ -22,6 +23,7 @@
 #ifndef QLDPC_POLAR_CORE_H
 #define QLDPC_POLAR_CORE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -79,10 +81,22 @@ PL_FN void pl_combine_words(uint32_t *x, long j, long stride)
 /* the level whose beliefs g produces before leaf block j > 0, in blocks: 2^t blocks, t = the trailing zeros of j */
 PL_FN int pl_ctz(long j) { return __builtin_ctzl((unsigned long)j); }
 
-/* ---- argument checks, shared by qldpc_polar_create and the host calls; 0 or a qldpc_status value (QLDPC_EINVAL -1, QLDPC_ESIZE -6) ---- */
+/* ---- the outputs ---- */
+/* packed word w of a frame's info row: bit b = u[info_pos[32 w + b]], u the words U[k * stride] (stride 64 where a wave interleaves its frames) */
+PL_FN uint32_t pl_info_word(const uint32_t *U, size_t stride, const int *info_pos, int n_info, size_t w)
+{
+    uint32_t word = 0u;
+    for (size_t b = 0; b < 32u && w * 32u + b < (size_t)n_info; b++) {
+        const int p = info_pos[w * 32u + b];
+        word |= pl_bit(U[(size_t)(p >> 5) * stride], p) << (31 - b);
+    }
+    return word;
+}
+
+/* ---- argument checks: 0 or a qldpc_status value (QLDPC_EINVAL -1, QLDPC_ESIZE -6); qldpc_polar_int.h's helpers word the refusals ---- */
 #define PL_EINVAL (-1)
 #define PL_ESIZE (-6)
-PL_FN int pl_check_size(int log2_n) { return log2_n >= 1 && log2_n <= PL_MAX_LOG2N ? 0 : PL_ESIZE; }
+PL_FN int pl_check_size(int log2_n, int max_log2_n) { return log2_n >= 1 && log2_n <= max_log2_n ? 0 : PL_ESIZE; }
 PL_FN int pl_check_maxq(int messages, int maxq) { return messages != 0 || (maxq >= 1 && maxq <= PL_MAX_MAXQ) ? 0 : PL_ESIZE; }
 /* info_pos[n_info] distinct and below N, marked in `info_mask` (ceil(N / 32) zeroed words, MSB-first) */
 PL_FN int pl_mark_info(int log2_n, int n_info, const int *info_pos, uint32_t *info_mask)
@@ -98,5 +112,36 @@ PL_FN int pl_mark_info(int log2_n, int n_info, const int *info_pos, uint32_t *in
     }
     return 0;
 }
+
+/* ---- what the host mirrors are made of: each is a macro X(SUF, TIN, T, LOAD, F, G) that defines the functions of one message type, with
+ * TIN the type of the caller's rows, T the type a belief is computed in, and LOAD / G used where an `int maxq` is in scope ---- */
+#define PL_I8_LOAD(v) pl_i8_load((int)(v), maxq)
+#define PL_I8_G(a, b, c) pl_i8_g((a), (b), (c), maxq)
+#define PL_F32_LOAD(v) (v)
+#define PL_HOST_MESSAGES(X)                                \
+    X(i8, int8_t, int, PL_I8_LOAD, pl_i8_f, PL_I8_G)       \
+    X(f32, float, float, PL_F32_LOAD, pl_f32_f, pl_f32_g)
+
+/* The recursion inside a leaf block, as a lane holds it in registers: a node of s <= 32 leaves whose first leaf is bit pos (MSB-first) of the
+ * block's words, beliefs L[s] -> decisions into *u, the re-encoded bits of every finished node into *x, leaf beliefs into leaf[] (or NULL) */
+#define PL_HOST_LEAF_BLOCK(SUF, TIN, T, LOAD, F, G)                                                                                        \
+    static void pl_node_##SUF(int maxq, const T *L, int s, int pos, uint32_t frozen, uint32_t value, uint32_t *u, uint32_t *x, TIN *leaf)  \
+    {                                                                                                                                      \
+        (void)maxq;                                                                                                                        \
+        if (s == 1) {                                                                                                                      \
+            const uint32_t bit = pl_leaf_bit(L[0] < 0, pl_bit(frozen, pos), pl_bit(value, pos));                                           \
+            *u |= bit << (31 - pos);                                                                                                       \
+            *x |= bit << (31 - pos);                                                                                                       \
+            if (leaf) leaf[pos] = (TIN)L[0];                                                                                               \
+            return;                                                                                                                        \
+        }                                                                                                                                  \
+        const int h = s / 2;                                                                                                               \
+        T l[16] = {0};                                                                                                                     \
+        for (int k = 0; k < h; k++) l[k] = F(L[k], L[k + h]);                                                                              \
+        pl_node_##SUF(maxq, l, h, pos, frozen, value, u, x, leaf);                                                                         \
+        for (int k = 0; k < h; k++) l[k] = G(L[k], L[k + h], pl_bit(*x, pos + k));                                                         \
+        pl_node_##SUF(maxq, l, h, pos + h, frozen, value, u, x, leaf);                                                                     \
+        *x ^= (*x << h) & ((0xffffffffu << (32 - h)) >> pos);                                                                              \
+    }
 
 #endif /* QLDPC_POLAR_CORE_H */

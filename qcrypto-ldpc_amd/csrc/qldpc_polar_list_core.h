@@ -97,8 +97,7 @@ PLL_FN int pll_done_level(long j) { return pl_ctz(j + 1); }
 PLL_FN size_t pll_bit_off(int L, int b) { return (size_t)L * (((size_t)1 << b) - 1u); }
 PLL_FN size_t pll_bit_words(int L, int log2_n) { return (size_t)L * (2u * (size_t)pl_words(log2_n) - 1u); }
 
-/* ---- argument checks, before the first HIP call; 0 or a qldpc_status value ---- */
-PLL_FN int pll_check_size(int log2_n) { return log2_n >= 1 && log2_n <= PLL_MAX_LOG2N ? 0 : PL_ESIZE; }
+/* ---- argument checks on top of the SC decoder's (the size against PLL_MAX_LOG2N), before the first HIP call; 0 or a qldpc_status value ---- */
 PLL_FN int pll_check_list(int list_size) { return list_size == 1 || list_size == 2 || list_size == 4 || list_size == 8 ? 0 : PL_ESIZE; }
 /* n_info < 0: a CRC without a code (qldpc_polar_crc_host) */
 PLL_FN int pll_check_crc(int crc_len, uint32_t crc_poly, int n_info)

@@ -7,8 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "../../include/qldpc.h"
-#include "qldpc_graph.h"
+#include "qldpc_polar_int.h"
 #include "qldpc_polar_list_core.h"
 
 /* what a frame's decode works on */
@@ -49,15 +48,18 @@ static void pll_close_block(pll_frame *fr, long j, int P)
     fr->ptr_b[t] = PLL_IDENT;
 }
 
-/* the decoder of one frame for one message type: T the belief type, TIN the input's, MT the metric's; returns the live paths */
-#define PLL_HOST_DECODER(SUF, TIN, T, MT, LOAD, F, G, PEN, SELECT)                                                                        \
-    static int pll_decode_##SUF(pll_frame *fr, const TIN *llr, MT *metric)                                                                \
+/* the decoder of one frame for one message type: T the belief type, TIN the input's; the metric's type, the penalty and the select go by the
+   suffix (pll_met_, pll_*_pen, pll_select_); returns the live paths */
+typedef uint32_t pll_met_i8;
+typedef float pll_met_f32;
+#define PLL_HOST_DECODER(SUF, TIN, T, LOAD, F, G)                                                                                         \
+    static int pll_decode_##SUF(pll_frame *fr, const TIN *llr, pll_met_##SUF *metric)                                                     \
     {                                                                                                                                     \
         const int n = fr->n, L = fr->L, maxq = fr->maxq;                                                                                  \
         (void)maxq;                                                                                                                       \
         const long N = fr->N;                                                                                                             \
         T *in = (T *)fr->in, *A = (T *)fr->A, D[PLL_MAX_L];                                                                               \
-        MT m[PLL_MAX_L], mf[PLL_MAX_L];                                                                                                   \
+        pll_met_##SUF m[PLL_MAX_L], mf[PLL_MAX_L];                                                                                        \
         uint32_t nx[PLL_MAX_L];                                                                                                           \
         int P = 1;                                                                                                                        \
         for (long k = 0; k < N; k++) in[k] = LOAD(llr[k]);                                                                                \
@@ -88,13 +90,13 @@ static void pll_close_block(pll_frame *fr, long j, int P)
             if (pl_bit(fr->frozen[j], p)) {                                                                                               \
                 const unsigned bit = fr->fval ? pl_bit(fr->fval[j], p) : 0u;                                                              \
                 for (int k = 0; k < P; k++) {                                                                                             \
-                    if ((unsigned)(D[k] < 0) != bit) metric[k] += PEN(D[k]);                                                              \
+                    if ((unsigned)(D[k] < 0) != bit) metric[k] += pll_##SUF##_pen(D[k]);                                                  \
                     fr->xw[k] |= bit << (31 - p);                                                                                         \
                 }                                                                                                                         \
             } else {                                                                                                                      \
                 const int n_new = 2 * P < L ? 2 * P : L;                                                                                  \
-                for (int k = 0; k < P; k++) { m[k] = metric[k]; mf[k] = metric[k] + PEN(D[k]); }                                          \
-                const uint32_t sel = SELECT(PLL_MAX_L, P, n_new, m, mf);                                                                  \
+                for (int k = 0; k < P; k++) { m[k] = metric[k]; mf[k] = metric[k] + pll_##SUF##_pen(D[k]); }                              \
+                const uint32_t sel = pll_select_##SUF(PLL_MAX_L, P, n_new, m, mf);                                                        \
                 uint32_t par = 0u;                                                                                                        \
                 for (int r = 0; r < n_new; r++) {                                                                                         \
                     const unsigned c = pll_nib(sel, r) & 7u, flip = pll_nib(sel, r) >> 3;                                                 \
@@ -113,11 +115,7 @@ static void pll_close_block(pll_frame *fr, long j, int P)
         return P;                                                                                                                         \
     }
 
-#define PLL_I8_LOAD(v) pl_i8_load((int)(v), maxq)
-#define PLL_I8_G(a, b, c) pl_i8_g((a), (b), (c), maxq)
-#define PLL_F32_LOAD(v) (v)
-PLL_HOST_DECODER(i8, int8_t, int, uint32_t, PLL_I8_LOAD, pl_i8_f, PLL_I8_G, pll_i8_pen, pll_select_i8)
-PLL_HOST_DECODER(f32, float, float, float, PLL_F32_LOAD, pl_f32_f, pl_f32_g, pll_f32_pen, pll_select_f32)
+PL_HOST_MESSAGES(PLL_HOST_DECODER)
 
 static int pll_crc_args(const char *who, int crc_len, uint32_t crc_poly, int n_info)
 {
@@ -146,27 +144,19 @@ int qldpc_polar_list_decode_host(int log2_n, int n_info, const int *info_pos, in
                                  int n_frames, const void *llr, const uint32_t *frozen_u, const uint32_t *crc, uint32_t *u, uint32_t *info,
                                  uint32_t *x, int32_t *pick, void *metric, uint32_t *list_x)
 {
-    if (pll_check_size(log2_n)) { qldpc_set_error("polar_list_decode_host: log2_n=%d (1 .. %d)", log2_n, PLL_MAX_LOG2N); return QLDPC_ESIZE; }
-    if (messages != QLDPC_POLAR_I8 && messages != QLDPC_POLAR_F32) { qldpc_set_error("polar_list_decode_host: messages=%d (QLDPC_POLAR_I8 or QLDPC_POLAR_F32)", messages); return QLDPC_EINVAL; }
-    if (pl_check_maxq(messages, maxq)) { qldpc_set_error("polar_list_decode_host: maxq=%d (1 .. %d: f gives maxq + 1, which has to fit an int8)", maxq, PL_MAX_MAXQ); return QLDPC_ESIZE; }
-    if (pll_check_list(list_size)) { qldpc_set_error("polar_list_decode_host: list_size=%d (1, 2, 4 or 8)", list_size); return QLDPC_ESIZE; }
-    if (n_frames < 0) { qldpc_set_error("polar_list_decode_host: n_frames=%d is negative", n_frames); return QLDPC_EINVAL; }
+    const char *who = "polar_list_decode_host";
+    uint32_t *mask;
+    int rc = pl_args_scalars(who, log2_n, PLL_MAX_LOG2N, messages, maxq);
+    if (rc) return rc;
+    if (pll_check_list(list_size)) { qldpc_set_error("%s: list_size=%d (1, 2, 4 or 8)", who, list_size); return QLDPC_ESIZE; }
+    if (n_frames < 0) { qldpc_set_error("%s: n_frames=%d is negative", who, n_frames); return QLDPC_EINVAL; }
+    rc = pl_args_frozen_mask(who, log2_n, n_info, info_pos, &mask);
+    if (rc) return rc;
+    if (pll_crc_args(who, crc_len, crc_poly, n_info)) { free(mask); return QLDPC_ESIZE; }
+    if (crc && crc_len == 0) { qldpc_set_error("%s: a crc row with crc_len = 0", who); free(mask); return QLDPC_EINVAL; }
+    if (n_frames > 0 && !llr) { qldpc_set_error("%s: llr is NULL", who); free(mask); return QLDPC_EINVAL; }
     const long N = 1l << log2_n, W = pl_words(log2_n), Wi = ((long)n_info + 31) / 32;
     const int L = list_size;
-    uint32_t *mask = (uint32_t *)calloc((size_t)W, sizeof(uint32_t));
-    if (!mask) return QLDPC_ENOMEM;
-    int rc = pl_mark_info(log2_n, n_info, info_pos, mask);
-    if (rc) {
-        qldpc_set_error(rc == PL_EINVAL ? "polar_list_decode_host: info_pos names a position twice (positions must be distinct)"
-                                        : "polar_list_decode_host: n_info=%d positions, each in 0 .. N - 1, are required (0 <= n_info <= N)", n_info);
-        free(mask);
-        return rc;
-    }
-    if (pll_crc_args("polar_list_decode_host", crc_len, crc_poly, n_info)) { free(mask); return QLDPC_ESIZE; }
-    if (crc && crc_len == 0) { qldpc_set_error("polar_list_decode_host: a crc row with crc_len = 0"); free(mask); return QLDPC_EINVAL; }
-    if (n_frames > 0 && !llr) { qldpc_set_error("polar_list_decode_host: llr is NULL"); free(mask); return QLDPC_EINVAL; }
-    const uint32_t valid = pl_row_mask(log2_n);
-    for (long w = 0; w < W; w++) mask[w] = ~mask[w] & valid;      /* the frozen mask */
     const size_t esz = messages == QLDPC_POLAR_I8 ? sizeof(int) : sizeof(float);
     pll_frame fr;
     memset(&fr, 0, sizeof(fr));
@@ -197,11 +187,8 @@ int qldpc_polar_list_decode_host(int log2_n, int n_info, const int *info_pos, in
         if (pick) pick[f] = first;
         if (u) memcpy(u + f * W, us, sizeof(uint32_t) * (size_t)W);
         if (x) memcpy(x + f * W, xs, sizeof(uint32_t) * (size_t)W);
-        if (info) {
-            uint32_t *row = info + f * Wi;
-            memset(row, 0, sizeof(uint32_t) * (size_t)Wi);
-            for (int m = 0; m < n_info; m++) row[m >> 5] |= pl_bit(us[info_pos[m] >> 5], info_pos[m]) << (31 - (m & 31));
-        }
+        if (info)
+            for (long w = 0; w < Wi; w++) info[f * Wi + w] = pl_info_word(us, 1, info_pos, n_info, (size_t)w);
         if (metric) {
             for (int k = 0; k < L; k++) {
                 if (messages == QLDPC_POLAR_I8) ((uint32_t *)metric)[f * L + k] = k < P ? mi[k] : 0xffffffffu;

@@ -8,12 +8,8 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "../../include/qldpc.h"
-#include "qldpc_graph.h"
+#include "qldpc_polar_int.h"
 #include "qldpc_polar_wide_core.h"
-
-/* qldpc_polar_host.c */
-int pl_host_decode_args(const char *who, int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr, uint32_t **frozen_mask);
 
 /* what a frame's walk works on: the arrays of the plan, each at its exact size */
 typedef struct plw_frame {
@@ -26,27 +22,10 @@ typedef struct plw_frame {
     void *leaf;                    /* the frame's leaf beliefs or NULL */
 } plw_frame;
 
-/* the walk of one frame for one message type: T the type in memory, R the type a lane computes with, LOAD / F / G the core's functions.
-   plw_node_: a node of s leaves of the leaf block, its first leaf bit pos of the block's words, beliefs L[s] (the lane's registers) */
+/* the walk of one frame for one message type: T the type in memory, R the type a lane computes with, LOAD / F / G the core's functions; the leaf
+   block is the core's recursion over the lane's registers */
 #define PLW_HOST_WALK(SUF, T, R, LOAD, F, G)                                                                                               \
-    static void plw_node_##SUF(int maxq, const R *L, int s, int pos, uint32_t frozen, uint32_t value, uint32_t *u, uint32_t *x, T *leaf)   \
-    {                                                                                                                                      \
-        (void)maxq;                                                                                                                        \
-        if (s == 1) {                                                                                                                      \
-            const uint32_t bit = pl_leaf_bit(L[0] < 0, pl_bit(frozen, pos), pl_bit(value, pos));                                           \
-            *u |= bit << (31 - pos);                                                                                                       \
-            *x |= bit << (31 - pos);                                                                                                       \
-            if (leaf) leaf[pos] = (T)L[0];                                                                                                 \
-            return;                                                                                                                        \
-        }                                                                                                                                  \
-        const int h = s / 2;                                                                                                               \
-        R l[16] = {0};                                                                                                                     \
-        for (int k = 0; k < h; k++) l[k] = F(L[k], L[k + h]);                                                                              \
-        plw_node_##SUF(maxq, l, h, pos, frozen, value, u, x, leaf);                                                                        \
-        for (int k = 0; k < h; k++) l[k] = G(L[k], L[k + h], pl_bit(*x, pos + k));                                                         \
-        plw_node_##SUF(maxq, l, h, pos + h, frozen, value, u, x, leaf);                                                                    \
-        *x ^= (*x << h) & ((0xffffffffu << (32 - h)) >> pos);                                                                              \
-    }                                                                                                                                      \
+    PL_HOST_LEAF_BLOCK(SUF, T, R, LOAD, F, G)                                                                                              \
     static void plw_walk_##SUF(const plw_frame *fr, const T *in)                                                                           \
     {                                                                                                                                      \
         const int n = fr->n, C = fr->C, maxq = fr->maxq;                                                                                   \
@@ -80,7 +59,7 @@ typedef struct plw_frame {
                 L[k] = is_g ? G(a, b, pl_bit(cw, k)) : F(a, b);                                                                            \
             }                                                                                                                              \
             uint32_t u = 0u, x = 0u;                                                                                                       \
-            plw_node_##SUF(maxq, L, 32, 0, fr->fmw[jw], fr->fvw[jw], &u, &x, fr->leaf ? (T *)fr->leaf + j * 32u : NULL);                   \
+            pl_node_##SUF(maxq, L, 32, 0, fr->fmw[jw], fr->fvw[jw], &u, &x, fr->leaf ? (T *)fr->leaf + j * 32u : NULL);                   \
             fr->uw[jw] = u;                                                                                                                \
             fr->xw[jw] = x;                                                                                                                \
             for (size_t h = 1; h < PLW_WIN && (j & h); h <<= 1)  /* the combines inside the window */                                      \
@@ -101,16 +80,12 @@ typedef struct plw_frame {
         R L[32];                                                                                                                           \
         for (int k = 0; k < s; k++) L[k] = LOAD(in[k]);                                                                                    \
         uint32_t u = 0u, x = 0u;                                                                                                           \
-        plw_node_##SUF(maxq, L, s, 0, fr->fmask[0], fr->fval ? fr->fval[0] : 0u, &u, &x, (T *)fr->leaf);                                    \
+        pl_node_##SUF(maxq, L, s, 0, fr->fmask[0], fr->fval ? fr->fval[0] : 0u, &u, &x, (T *)fr->leaf);                                    \
         fr->U[0] = u;                                                                                                                      \
         fr->X[0] = x;                                                                                                                      \
     }
 
-#define PLW_I8_LOAD(v) pl_i8_load((int)(v), maxq)
-#define PLW_I8_G(a, b, c) pl_i8_g((a), (b), (c), maxq)
-#define PLW_F32_LOAD(v) (v)
-PLW_HOST_WALK(i8, int8_t, int, PLW_I8_LOAD, pl_i8_f, PLW_I8_G)
-PLW_HOST_WALK(f32, float, float, PLW_F32_LOAD, pl_f32_f, pl_f32_g)
+PL_HOST_MESSAGES(PLW_HOST_WALK)
 
 int qldpc_polar_decode_wide_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
                                  const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf)
@@ -141,11 +116,8 @@ int qldpc_polar_decode_wide_host(int log2_n, int n_info, const int *info_pos, in
         }
         if (u) memcpy(u + f * W, fr.U, sizeof(uint32_t) * W);
         if (x) memcpy(x + f * W, fr.X, sizeof(uint32_t) * W);
-        if (info) {
-            uint32_t *row = info + f * Wi;
-            memset(row, 0, sizeof(uint32_t) * Wi);
-            for (int m = 0; m < n_info; m++) row[m >> 5] |= pl_bit(fr.U[info_pos[m] >> 5], info_pos[m]) << (31 - (m & 31));
-        }
+        if (info)
+            for (size_t w = 0; w < Wi; w++) info[f * Wi + w] = pl_info_word(fr.U, 1, info_pos, n_info, w);
     }
     free(fr.S); free(fr.lds); free(wins); free(rows); free(mask);
     return QLDPC_OK;

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import _L, _Handle, _chk, _create, _dev_empty, _dev_rows, _ip, _sig, _stream_arg, _torch, _up, _vp, QldpcError
+from ._lib import _L, _Handle, _chk, _create, _dev_empty, _dev_rows, _ip, _ptr, _sig, _stream_arg, _torch, _up, _vp, QldpcError
 
 POLAR_I8, POLAR_F32 = 0, 1
 POLAR_FORMS = {"lanes": 0, "wide": 1}
@@ -75,13 +75,14 @@ def polar_encode_host(log2_n, u):
     return x.reshape(u.shape)
 
 
-def _decode_host(fn, who, log2_n, info_pos, llr, frozen, messages, maxq, leaf):
-    """the marshalling of the two host decodes, which take the same arguments"""
+def _host_rows(who, log2_n, max_log2_n, info_pos, llr, frozen, messages):
+    """the marshalling of (info_pos, llr, frozen) of the host decodes, which take them the same way
+    -> kind, dt (the messages), pos int32 [K], llr [F, N] of dt, fz uint32 [F, W] or None, n, N (0: a size the library will refuse), W, F"""
     kind, dt = _messages(messages)
     pos = np.ascontiguousarray(info_pos, dtype=np.int32).ravel()
     llr = np.ascontiguousarray(llr, dtype=dt)
     n = int(log2_n)
-    N, W = (1 << n) if 0 <= n <= POLAR_MAX_LOG2N else 0, _words(n)
+    N, W = (1 << n) if 0 <= n <= max_log2_n else 0, _words(n)
     if N and (llr.ndim != 2 or llr.shape[1] != N):
         raise QldpcError(-6, "%s: llr must be [frames, N = %d]" % (who, N))
     F = llr.shape[0] if llr.ndim == 2 else 0
@@ -90,12 +91,17 @@ def _decode_host(fn, who, log2_n, info_pos, llr, frozen, messages, maxq, leaf):
         fz = np.ascontiguousarray(frozen, dtype=np.uint32)
         if fz.shape != (F, W):
             raise QldpcError(-6, "%s: frozen must be [frames, %d] words" % (who, W))
+    return kind, dt, pos, llr, fz, n, N, W, F
+
+
+def _decode_host(fn, who, log2_n, info_pos, llr, frozen, messages, maxq, leaf):
+    """the two host SC decodes, which take the same arguments"""
+    kind, dt, pos, llr, fz, n, N, W, F = _host_rows(who, log2_n, POLAR_MAX_LOG2N, info_pos, llr, frozen, messages)
     out = dict(u=np.zeros((F, W), np.uint32), info=np.zeros((F, (pos.size + 31) // 32), np.uint32), x=np.zeros((F, W), np.uint32))
     if leaf:
         out["leaf"] = np.zeros((F, N), dt)
-    p = lambda a: a.ctypes.data_as(_up) if a is not None else None
-    _chk(fn(n, pos.size, pos.ctypes.data_as(_ip), kind, int(maxq), F, llr.ctypes.data_as(_vp), p(fz), p(out["u"]), p(out["info"]), p(out["x"]),
-            out["leaf"].ctypes.data_as(_vp) if leaf else None), who)
+    _chk(fn(n, pos.size, pos.ctypes.data_as(_ip), kind, int(maxq), F, llr.ctypes.data_as(_vp), _ptr(fz, _up), _ptr(out["u"], _up), _ptr(out["info"], _up),
+            _ptr(out["x"], _up), _ptr(out.get("leaf"), _vp)), who)
     return out
 
 
@@ -110,27 +116,48 @@ def polar_decode_wide_host(log2_n, info_pos, llr, frozen=None, messages="i8", ma
     return _decode_host(_L.qldpc_polar_decode_wide_host, "polar_decode_wide_host", log2_n, info_pos, llr, frozen, messages, maxq, leaf)
 
 
-class Polar(_Handle):
-    """A polar code of N = 2^log2_n bits with information at `info_pos` (every other position frozen) on the device: encode() and the
-    successive-cancellation decode() of up to max_frames frames a call.  form="lanes": 64 frames to a wave, for batches; form="wide": a workgroup
-    to a frame, for few long frames.  The same function bit for bit, and the choice is the caller's.  Device tensors in, device tensors out,
-    asynchronous on torch's current stream."""
-    _free = _L.qldpc_polar_free
+class _PolarCode(_Handle):
+    """what Polar and PolarList share: the code's attributes, the input checks of decode, its output dict and the stream"""
 
-    def __init__(self, log2_n, info_pos, messages="i8", maxq=31, max_frames=4096, device=0, form="lanes"):
+    def _create_code(self, create, log2_n, info_pos, messages, maxq, before, max_frames, after, device):
+        """create(log2_n, K, info_pos, messages, maxq, *before, max_frames, *after, device) -> the handle, and the attributes both classes have"""
         self.messages, self._np_dtype = _messages(messages)
         pos = np.ascontiguousarray(info_pos, dtype=np.int32).ravel()
-        self.form = _form(form)
-        self._h = _create("Polar", _L.qldpc_polar_create_form, int(log2_n), pos.size, pos.ctypes.data_as(_ip), self.messages, int(maxq), int(max_frames),
-                          self.form, int(device))
+        self._h = _create(type(self).__name__, create, int(log2_n), pos.size, pos.ctypes.data_as(_ip), self.messages, int(maxq), *before, int(max_frames), *after,
+                          int(device))
         self.log2_n, self.N, self.K, self.W, self.Wi = int(log2_n), 1 << int(log2_n), pos.size, _words(log2_n), (pos.size + 31) // 32
         self.info_pos, self.maxq, self.max_frames, self.device = pos, int(maxq), int(max_frames), int(device)
 
     def device_bytes(self):
-        return int(_L.qldpc_polar_device_bytes(self._h))
+        return int(self._device_bytes(self._h))
 
     def _on_current_stream(self):
-        _chk(_L.qldpc_polar_set_stream(self._h, _stream_arg(None, self.device)), "Polar.set_stream")
+        _chk(self._set_stream(self._h, _stream_arg(None, self.device)), "polar.set_stream")
+
+    def _decode_inputs(self, llr, frozen):
+        """llr [F, N] of the context's messages and frozen [F, W] words or None, checked -> torch, F and their pointers"""
+        torch = _torch()
+        pl = _dev_rows(llr, None, self.N, (torch.int8 if self.messages == POLAR_I8 else torch.float32,), "llr")
+        return torch, llr.shape[0], pl, _dev_rows(frozen, llr.shape[0], self.W, (torch.int32, torch.uint32), "frozen")
+
+    @staticmethod
+    def _outputs(device, shapes, want):
+        """a fresh device tensor for every name of `shapes` (name -> (shape, dtype)) that `want` names -> the dict, and ptr(name): the pointer the
+        library gets for it, None where it was not asked for or is empty"""
+        out = {k: _dev_empty(device, *v) for k, v in shapes.items() if k in want}
+        return out, lambda name: _vp(out[name].data_ptr()) if name in out and out[name].numel() else None
+
+
+class Polar(_PolarCode):
+    """A polar code of N = 2^log2_n bits with information at `info_pos` (every other position frozen) on the device: encode() and the
+    successive-cancellation decode() of up to max_frames frames a call.  form="lanes": 64 frames to a wave, for batches; form="wide": a workgroup
+    to a frame, for few long frames.  The same function bit for bit, and the choice is the caller's.  Device tensors in, device tensors out,
+    asynchronous on torch's current stream."""
+    _free, _device_bytes, _set_stream = _L.qldpc_polar_free, _L.qldpc_polar_device_bytes, _L.qldpc_polar_set_stream
+
+    def __init__(self, log2_n, info_pos, messages="i8", maxq=31, max_frames=4096, device=0, form="lanes"):
+        self.form = _form(form)
+        self._create_code(_L.qldpc_polar_create_form, log2_n, info_pos, messages, maxq, (), max_frames, (self.form,), device)
 
     def encode(self, u, out=None):
         """u int32 / uint32 [F, W] packed rows on the device -> x of the same shape; out=u encodes in place"""
@@ -147,18 +174,10 @@ class Polar(_Handle):
         """llr [F, N] int8 or float32 (the context's messages), frozen int32 / uint32 [F, W] frozen values or None (zeros)
         -> dict of device tensors: u int32 [F, W], info int32 [F, ceil(K/32)], x int32 [F, W] (those named in `want`) and, with leaf=True,
         leaf [F, N] of the messages' type"""
-        torch = _torch()
-        words = (torch.int32, torch.uint32)
-        pl = _dev_rows(llr, None, self.N, (torch.int8 if self.messages == POLAR_I8 else torch.float32,), "llr")
-        F = llr.shape[0]
-        pf = _dev_rows(frozen, F, self.W, words, "frozen")
-        out = {}
-        for name, cols in (("u", self.W), ("info", self.Wi), ("x", self.W)):
-            if name in want:
-                out[name] = _dev_empty(llr.device, (F, cols), torch.int32)
+        torch, F, pl, pf = self._decode_inputs(llr, frozen)
+        out, ptr = self._outputs(llr.device, dict(u=((F, self.W), torch.int32), info=((F, self.Wi), torch.int32), x=((F, self.W), torch.int32)), want)
         if leaf:
             out["leaf"] = _dev_empty(llr.device, (F, self.N), llr.dtype)
-        ptr = lambda name: _vp(out[name].data_ptr()) if name in out and out[name].numel() else None
         self._on_current_stream()
         _chk(_L.qldpc_polar_decode_dev(self._h, F, pl, pf, ptr("u"), ptr("info"), ptr("x"), ptr("leaf")), "Polar.decode")
         return out
@@ -184,19 +203,9 @@ def polar_list_decode_host(log2_n, info_pos, llr, frozen=None, crc=None, message
     """the list decoder's mirror (qldpc_polar_list_decode_host): llr [F, N] int8 or float32 by `messages`, frozen uint32 [F, W] or None, crc uint32
     [F] the expected remainders or None (zeros) -> dict of those of u, info, x uint32 rows of the picked path, pick int32 [F] (-1: no path
     matched), metric [F, L] uint32 or float32, list_x uint32 [F, L, W] that `want` names"""
-    kind, dt = _messages(messages)
-    pos = np.ascontiguousarray(info_pos, dtype=np.int32).ravel()
-    llr = np.ascontiguousarray(llr, dtype=dt)
-    n, L = int(log2_n), int(list_size)
-    N, W = (1 << n) if 0 <= n <= POLAR_LIST_MAX_LOG2N else 0, _words(n)
-    if N and (llr.ndim != 2 or llr.shape[1] != N):
-        raise QldpcError(-6, "polar_list_decode_host: llr must be [frames, N = %d]" % N)
-    F = llr.shape[0] if llr.ndim == 2 else 0
-    fz = cr = None
-    if frozen is not None:
-        fz = np.ascontiguousarray(frozen, dtype=np.uint32)
-        if fz.shape != (F, W):
-            raise QldpcError(-6, "polar_list_decode_host: frozen must be [frames, %d] words" % W)
+    who = "polar_list_decode_host"
+    kind, dt, pos, llr, fz, n, N, W, F = _host_rows(who, log2_n, POLAR_LIST_MAX_LOG2N, info_pos, llr, frozen, messages)
+    L, cr = int(list_size), None
     if crc is not None:
         cr = np.ascontiguousarray(crc, dtype=np.uint32)
         if cr.shape != (F,):
@@ -205,49 +214,35 @@ def polar_list_decode_host(log2_n, info_pos, llr, frozen=None, crc=None, message
     shapes = dict(u=((F, W), np.uint32), info=((F, (pos.size + 31) // 32), np.uint32), x=((F, W), np.uint32), pick=((F,), np.int32),
                   metric=((F, Ls), np.uint32 if kind == POLAR_I8 else np.float32), list_x=((F, Ls, W), np.uint32))
     out = {k: np.zeros(*shapes[k]) for k in LIST_OUTPUTS if k in want}
-    p = lambda a, t=_up: a.ctypes.data_as(t) if a is not None else None
     _chk(_L.qldpc_polar_list_decode_host(n, pos.size, pos.ctypes.data_as(_ip), kind, int(maxq), L, int(crc_len), int(crc_poly) & 0xffffffff, F,
-                                         llr.ctypes.data_as(_vp), p(fz), p(cr), p(out.get("u")), p(out.get("info")), p(out.get("x")),
-                                         p(out.get("pick"), _ip), p(out.get("metric"), _vp), p(out.get("list_x"))), "polar_list_decode_host")
+                                         llr.ctypes.data_as(_vp), _ptr(fz, _up), _ptr(cr, _up), _ptr(out.get("u"), _up), _ptr(out.get("info"), _up),
+                                         _ptr(out.get("x"), _up), _ptr(out.get("pick"), _ip), _ptr(out.get("metric"), _vp), _ptr(out.get("list_x"), _up)), who)
     return out
 
 
-class PolarList(_Handle):
+class PolarList(_PolarCode):
     """The CRC-aided successive-cancellation list decoder of a polar code on the device: up to `list_size` (1, 2, 4, 8) paths a frame, a lane of a
     wave holding all paths of its frame, and the pick of the first path in list order whose CRC over the information bits is the expected one.
     Device tensors in, device tensors out, asynchronous on torch's current stream."""
-    _free = _L.qldpc_polar_list_free
+    _free, _device_bytes, _set_stream = _L.qldpc_polar_list_free, _L.qldpc_polar_list_device_bytes, _L.qldpc_polar_list_set_stream
 
     def __init__(self, log2_n, info_pos, messages="i8", maxq=31, list_size=4, crc_len=0, crc_poly=0, max_frames=4096, device=0):
-        self.messages, self._np_dtype = _messages(messages)
-        pos = np.ascontiguousarray(info_pos, dtype=np.int32).ravel()
-        self._h = _create("PolarList", _L.qldpc_polar_list_create, int(log2_n), pos.size, pos.ctypes.data_as(_ip), self.messages, int(maxq), int(list_size),
-                          int(crc_len), int(crc_poly) & 0xffffffff, int(max_frames), int(device))
-        self.log2_n, self.N, self.K, self.W, self.Wi = int(log2_n), 1 << int(log2_n), pos.size, _words(log2_n), (pos.size + 31) // 32
-        self.info_pos, self.maxq, self.max_frames, self.device = pos, int(maxq), int(max_frames), int(device)
+        self._create_code(_L.qldpc_polar_list_create, log2_n, info_pos, messages, maxq, (int(list_size), int(crc_len), int(crc_poly) & 0xffffffff), max_frames, (), device)
         self.list_size, self.crc_len, self.crc_poly = int(list_size), int(crc_len), int(crc_poly)
-
-    def device_bytes(self):
-        return int(_L.qldpc_polar_list_device_bytes(self._h))
 
     def decode(self, llr, frozen=None, crc=None, want=LIST_OUTPUTS):
         """llr [F, N] int8 or float32 (the context's messages), frozen int32 / uint32 [F, W] or None (zeros), crc int32 / uint32 [F] the expected
         remainders or None (zeros) -> dict of device tensors, those `want` names: u, info, x int32 rows of the picked path as Polar.decode gives
         them, pick int32 [F], metric [F, L] int32 (the uint32's bits) or float32, list_x int32 [F, L, W]"""
-        torch = _torch()
-        words = (torch.int32, torch.uint32)
-        pl = _dev_rows(llr, None, self.N, (torch.int8 if self.messages == POLAR_I8 else torch.float32,), "llr")
-        F, L = llr.shape[0], self.list_size
-        pf = _dev_rows(frozen, F, self.W, words, "frozen")
-        pc = None
+        torch, F, pl, pf = self._decode_inputs(llr, frozen)
+        L, pc = self.list_size, None
         if crc is not None:
-            assert crc.is_cuda and crc.dtype in words and crc.is_contiguous() and tuple(crc.shape) == (F,), "crc"
+            assert crc.is_cuda and crc.dtype in (torch.int32, torch.uint32) and crc.is_contiguous() and tuple(crc.shape) == (F,), "crc"
             pc = _vp(crc.data_ptr())
-        shapes = dict(u=((F, self.W), torch.int32), info=((F, self.Wi), torch.int32), x=((F, self.W), torch.int32), pick=((F,), torch.int32),
-                      metric=((F, L), torch.int32 if self.messages == POLAR_I8 else torch.float32), list_x=((F, L, self.W), torch.int32))
-        out = {k: _dev_empty(llr.device, *shapes[k]) for k in LIST_OUTPUTS if k in want}
-        ptr = lambda name: _vp(out[name].data_ptr()) if name in out and out[name].numel() else None
-        _chk(_L.qldpc_polar_list_set_stream(self._h, _stream_arg(None, self.device)), "PolarList.set_stream")
+        out, ptr = self._outputs(llr.device, dict(u=((F, self.W), torch.int32), info=((F, self.Wi), torch.int32), x=((F, self.W), torch.int32),
+                                                  pick=((F,), torch.int32), metric=((F, L), torch.int32 if self.messages == POLAR_I8 else torch.float32),
+                                                  list_x=((F, L, self.W), torch.int32)), want)
+        self._on_current_stream()
         _chk(_L.qldpc_polar_list_decode_dev(self._h, F, pl, pf, pc, ptr("u"), ptr("info"), ptr("x"), ptr("pick"), ptr("metric"), ptr("list_x")),
              "PolarList.decode")
         return out

@@ -4,33 +4,12 @@
  * against the bit loop of its definition, and every refusal.
  * Built with -fsanitize=address,undefined by tests/test_polar_list_host.py */
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include "qldpc.h"
 #include "qldpc_polar_list_core.h"
 
-#define CHECK(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); return 1; } } while (0)
+#include "polar_sanitize_common.h"
 
-static char msg[256];
-void qldpc_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, sizeof(msg), fmt, ap);
-    va_end(ap);
-}
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd(void)
-{
-    rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17;
-    return rng_state;
-}
-
-static int get(const uint32_t *row, long i) { return (int)((row[i >> 5] >> (31 - (i & 31))) & 1u); }
 
 /* the CRC by its definition, a bit at a time over a row of unpacked bits */
 static uint32_t crc_def(const unsigned char *bits, int n_bits, int crc_len, uint32_t poly)
@@ -48,10 +27,7 @@ static int run(int n, int f32, int maxq, int L, int n_info, int crc_len, uint32_
 {
     const long N = 1l << n, W = pl_words(n), Wi = (n_info + 31) / 32;
     const int F = 3, kind = f32 ? QLDPC_POLAR_F32 : QLDPC_POLAR_I8;
-    int *pos = (int *)malloc(sizeof(int) * (size_t)(n_info ? n_info : 1)), *perm = (int *)malloc(sizeof(int) * (size_t)N);
-    for (long i = 0; i < N; i++) perm[i] = (int)i;
-    for (long i = N - 1; i > 0; i--) { const long j = (long)(rnd() % (uint64_t)(i + 1)); const int t = perm[i]; perm[i] = perm[j]; perm[j] = t; }
-    for (int m = 0; m < n_info; m++) pos[m] = perm[m];
+    int *pos = draw_info_pos(N, n_info);
     const size_t esz = f32 ? sizeof(float) : 1, row = 4 * (size_t)(F * W);
     void *llr = malloc(esz * (size_t)(F * N));
     uint32_t *fv = (uint32_t *)malloc(row), *crc = (uint32_t *)malloc(4 * (size_t)F), *u = (uint32_t *)malloc(row), *x = (uint32_t *)malloc(row),
@@ -60,10 +36,7 @@ static int run(int n, int f32, int maxq, int L, int n_info, int crc_len, uint32_
              *lx1 = (uint32_t *)malloc(row * (size_t)L), *metric1 = (uint32_t *)malloc(4 * (size_t)(F * L)), *enc = (uint32_t *)malloc(row);
     int32_t *pick = (int32_t *)malloc(4 * (size_t)F), *pick1 = (int32_t *)malloc(4 * (size_t)F);
     unsigned char *ib = (unsigned char *)malloc((size_t)(n_info ? n_info : 1));
-    for (long i = 0; i < F * N; i++) {
-        if (f32) ((float *)llr)[i] = (float)((double)(int64_t)(rnd() % 17) - 8.0) / 4.0f;      /* few values: ties in the metrics */
-        else ((int8_t *)llr)[i] = (int8_t)(rnd() & 0xff);
-    }
+    fill_llr(llr, F * N, f32, 8, 4.0f);                           /* few float values: ties in the metrics */
     for (long i = 0; i < F * W; i++) fv[i] = (uint32_t)rnd();
     for (int f = 0; f < F; f++) crc[f] = (uint32_t)rnd() & pll_crc_mask(crc_len);
     const uint32_t *fvp = with_rows ? fv : NULL, *crcp = with_rows && crc_len ? crc : NULL;
@@ -107,7 +80,7 @@ static int run(int n, int f32, int maxq, int L, int n_info, int crc_len, uint32_
             CHECK(crc[f] == crc_def(ib, n_info, crc_len, poly));
         }
     }
-    free(pos); free(perm); free(llr); free(fv); free(crc); free(u); free(x); free(info); free(lx); free(metric); free(u1); free(x1); free(info1); free(lx1);
+    free(pos); free(llr); free(fv); free(crc); free(u); free(x); free(info); free(lx); free(metric); free(u1); free(x1); free(info1); free(lx1);
     free(metric1); free(enc); free(pick); free(pick1); free(ib);
     return 0;
 }

@@ -2,33 +2,11 @@
  * up to 2^12 in both message types, every row malloc'ed at its exact size, each output asked for alone and all together, the decoder against a
  * plain recursion of the definition on unpacked bits, the encoder against the bit loop of the definition, and every refusal.
  * Built with -fsanitize=address,undefined by tests/test_polar_host.py */
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include "qldpc.h"
 #include "qldpc_polar_core.h"
 
-#define CHECK(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); return 1; } } while (0)
+#include "polar_sanitize_common.h"
 
-static char msg[256];
-void qldpc_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, sizeof(msg), fmt, ap);
-    va_end(ap);
-}
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd(void)
-{
-    rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17;
-    return rng_state;
-}
-
-static int get(const uint32_t *row, long i) { return (int)((row[i >> 5] >> (31 - (i & 31))) & 1u); }
 static void put(uint32_t *row, long i, int b) { if (b) row[i >> 5] |= 1u << (31 - (i & 31)); }
 
 /* the definition on unpacked values, in floats (exact for both message types: small integers, or single float additions); c = the re-encoded
@@ -62,23 +40,17 @@ static int run(int n, int f32, int maxq, int n_info, int with_fval)
 {
     const long N = 1l << n, W = pl_words(n), Wi = (n_info + 31) / 32;
     const int F = 3;
-    int *pos = (int *)malloc(sizeof(int) * (size_t)(n_info ? n_info : 1));
+    int *pos = draw_info_pos(N, n_info);
     unsigned char *frozen = (unsigned char *)malloc((size_t)N), *fvb = (unsigned char *)calloc((size_t)N, 1), *ub = (unsigned char *)malloc((size_t)N),
                   *cb = (unsigned char *)malloc((size_t)N);
-    int *perm = (int *)malloc(sizeof(int) * (size_t)N);
-    for (long i = 0; i < N; i++) perm[i] = (int)i;
-    for (long i = N - 1; i > 0; i--) { const long j = (long)(rnd() % (uint64_t)(i + 1)); const int t = perm[i]; perm[i] = perm[j]; perm[j] = t; }
     memset(frozen, 1, (size_t)N);
-    for (int m = 0; m < n_info; m++) { pos[m] = perm[m]; frozen[perm[m]] = 0; }
+    for (int m = 0; m < n_info; m++) frozen[pos[m]] = 0;
     const size_t esz = f32 ? sizeof(float) : 1;
     void *llr = malloc(esz * (size_t)(F * N)), *leaf = malloc(esz * (size_t)(F * N));
     uint32_t *fv = (uint32_t *)calloc((size_t)(F * W), 4), *u = (uint32_t *)malloc(4 * (size_t)(F * W)), *x = (uint32_t *)malloc(4 * (size_t)(F * W)),
              *info = (uint32_t *)malloc(4 * (size_t)(Wi ? F * Wi : 1)), *u1 = (uint32_t *)malloc(4 * (size_t)(F * W)), *x2 = (uint32_t *)malloc(4 * (size_t)(F * W));
     float *Lf = (float *)malloc(sizeof(float) * (size_t)N), *leaf_ref = (float *)malloc(sizeof(float) * (size_t)N);
-    for (long i = 0; i < F * N; i++) {
-        if (f32) ((float *)llr)[i] = (float)((double)(int64_t)(rnd() % 2001) - 1000.0) / 64.0f;
-        else ((int8_t *)llr)[i] = (int8_t)(rnd() & 0xff);
-    }
+    fill_llr(llr, F * N, f32, 1000, 64.0f);
     if (with_fval) for (long i = 0; i < F * W; i++) fv[i] = (uint32_t)rnd();
     const int kind = f32 ? QLDPC_POLAR_F32 : QLDPC_POLAR_I8;
     CHECK(qldpc_polar_decode_host(n, n_info, pos, kind, maxq, F, llr, with_fval ? fv : NULL, u, info, x, leaf) == QLDPC_OK);
@@ -114,7 +86,7 @@ static int run(int n, int f32, int maxq, int n_info, int with_fval)
         for (long i = 0; i < N; i++) put(x2, i, cb[i]);
         CHECK(!memcmp(x2, x + f * W, 4 * (size_t)W));
     }
-    free(pos); free(frozen); free(fvb); free(ub); free(cb); free(perm); free(llr); free(leaf); free(fv); free(u); free(x); free(info); free(u1); free(x2);
+    free(pos); free(frozen); free(fvb); free(ub); free(cb); free(llr); free(leaf); free(fv); free(u); free(x); free(info); free(u1); free(x2);
     free(Lf); free(leaf_ref);
     return 0;
 }

@@ -2,49 +2,22 @@
  * 2^13 in both message types, every row malloc'ed at its exact size, each output asked for alone and all together, against the host mirror
  * (qldpc_polar_host.c) bit for bit.  The walk itself allocates the scratch, the LDS stand-in and the windows at exactly the sizes the core
  * header states, so an index outside the plan is an error here.  Built with -fsanitize=address,undefined by tests/test_polar_wide_host.py */
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include "qldpc.h"
 #include "qldpc_polar_wide_core.h"
 
-#define CHECK(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); return 1; } } while (0)
-
-static char msg[256];
-void qldpc_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, sizeof(msg), fmt, ap);
-    va_end(ap);
-}
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd(void)
-{
-    rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17;
-    return rng_state;
-}
+#include "polar_sanitize_common.h"
 
 static int run(int n, int f32, int maxq, int n_info, int with_fval)
 {
     const long N = 1l << n, W = pl_words(n), Wi = (n_info + 31) / 32;
     const int F = 3;
-    int *pos = (int *)malloc(sizeof(int) * (size_t)(n_info ? n_info : 1)), *perm = (int *)malloc(sizeof(int) * (size_t)N);
-    for (long i = 0; i < N; i++) perm[i] = (int)i;
-    for (long i = N - 1; i > 0; i--) { const long j = (long)(rnd() % (uint64_t)(i + 1)); const int t = perm[i]; perm[i] = perm[j]; perm[j] = t; }
-    for (int m = 0; m < n_info; m++) pos[m] = perm[m];
+    int *pos = draw_info_pos(N, n_info);
     const size_t esz = f32 ? sizeof(float) : 1, rows = 4 * (size_t)(F * W), irow = 4 * (size_t)(Wi ? F * Wi : 1), beliefs = esz * (size_t)(F * N);
     void *llr = malloc(beliefs), *leaf = malloc(beliefs), *leaf_m = malloc(beliefs), *leaf1 = malloc(beliefs);
     uint32_t *fv = (uint32_t *)calloc((size_t)(F * W), 4), *u = (uint32_t *)malloc(rows), *x = (uint32_t *)malloc(rows), *info = (uint32_t *)malloc(irow),
              *u_m = (uint32_t *)malloc(rows), *x_m = (uint32_t *)malloc(rows), *info_m = (uint32_t *)malloc(irow), *u1 = (uint32_t *)malloc(rows),
              *x1 = (uint32_t *)malloc(rows), *info1 = (uint32_t *)malloc(irow);
-    for (long i = 0; i < F * N; i++) {
-        if (f32) ((float *)llr)[i] = (float)((double)(int64_t)(rnd() % 2001) - 1000.0) / 64.0f;
-        else ((int8_t *)llr)[i] = (int8_t)(rnd() & 0xff);
-    }
+    fill_llr(llr, F * N, f32, 1000, 64.0f);
     if (with_fval) for (long i = 0; i < F * W; i++) fv[i] = (uint32_t)rnd();
     const uint32_t *fz = with_fval ? fv : NULL;
     const int kind = f32 ? QLDPC_POLAR_F32 : QLDPC_POLAR_I8;
@@ -58,7 +31,7 @@ static int run(int n, int f32, int maxq, int n_info, int with_fval)
     CHECK(qldpc_polar_decode_wide_host(n, n_info, pos, kind, maxq, F, llr, fz, NULL, NULL, x1, NULL) == QLDPC_OK && !memcmp(x1, x_m, rows));
     CHECK(qldpc_polar_decode_wide_host(n, n_info, pos, kind, maxq, F, llr, fz, NULL, NULL, NULL, leaf1) == QLDPC_OK && !memcmp(leaf1, leaf_m, beliefs));
     CHECK(qldpc_polar_decode_wide_host(n, n_info, pos, kind, maxq, F, llr, fz, NULL, NULL, NULL, NULL) == QLDPC_OK);
-    free(pos); free(perm); free(llr); free(leaf); free(leaf_m); free(leaf1); free(fv); free(u); free(x); free(info); free(u_m); free(x_m); free(info_m);
+    free(pos); free(llr); free(leaf); free(leaf_m); free(leaf1); free(fv); free(u); free(x); free(info); free(u_m); free(x_m); free(info_m);
     free(u1); free(x1); free(info1);
     return 0;
 }

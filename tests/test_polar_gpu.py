@@ -78,6 +78,37 @@ def test_all_frozen_and_rate_one(q, torch, messages, K):
     R.check_outputs(out, R.decode(llr, mask, fv, messages, 31), pos, N, mask, K)
 
 
+def _same(a, b, what):
+    """two decodes' dicts bit for bit: words as uint32, floats by their bit patterns"""
+    assert set(a) == set(b), what
+    for k in a:
+        x, y = np.asarray(a[k]), np.asarray(b[k])
+        bits = lambda v: v.view(np.uint32) if v.dtype.itemsize == 4 else v
+        assert x.shape == y.shape and np.array_equal(bits(x), bits(y)), what + ": " + k
+
+
+@pytest.mark.parametrize("messages", ["i8", "f32"])
+@pytest.mark.parametrize("K", [0, 33])
+@pytest.mark.parametrize("n", [5, 7])
+def test_small_shape_edges_are_the_mirror(q, torch, n, K, messages):
+    """the edges of what the three decoders share (the info row, the level step, the context): 65 frames (two groups, one live lane in the
+    second), no information bit, and 33 of them (an info row whose second word holds one bit; N = 32 has no 33 positions, so n = 5 takes all
+    32: one full word).  Each output alone, then all together, against the host mirror.  n = 5: the frame is a leaf block read from the
+    caller's row"""
+    rng = np.random.default_rng([n, K, messages == "i8", 15])
+    N, F = 1 << n, 65
+    pos, _ = R.random_code(rng, N, min(K, N))
+    llr = _inputs(rng, messages, F, N, 31)
+    fz = R.pack(rng.integers(0, 2, (F, N), dtype=np.uint8))
+    host = q.polar_decode_host(n, pos, llr, fz, messages, 31, leaf=True)
+    dec = q.Polar(n, pos, messages, 31, max_frames=F)
+    d_llr, d_fz = _dev(torch, llr), _dev(torch, fz)
+    for name in ("u", "info", "x", "leaf"):
+        out = _host(dec.decode(d_llr, d_fz, leaf=name == "leaf", want=() if name == "leaf" else (name,)))
+        _same(out, {name: host[name]}, "n=%d K=%d %s alone" % (n, len(pos), messages))
+    _same(_host(dec.decode(d_llr, d_fz, leaf=True)), host, "n=%d K=%d %s all" % (n, len(pos), messages))
+
+
 @pytest.mark.parametrize("n,messages", [(14, "i8"), (14, "f32"), (16, "i8"), (16, "f32")])
 def test_sizes_above_what_stays_on_chip(q, torch, n, messages):
     """levels 6 .. n live in the scratch; 65 frames: a full group and a group of one"""

@@ -111,6 +111,24 @@ def test_each_output_alone(q, torch):
 
 
 @pytest.mark.parametrize("messages", ["i8", "f32"])
+@pytest.mark.parametrize("K", [0, 33])
+@pytest.mark.parametrize("L", [1, 4])
+@pytest.mark.parametrize("n", [5, 7])
+def test_small_shape_edges_are_the_mirror(q, torch, n, L, K, messages):
+    """the edges of what the three decoders share (the info row, the level step, the context): 65 frames (two groups, one live lane in the
+    second), no information bit, and 33 of them (an info row whose second word holds one bit; N = 32 has no 33 positions, so n = 5 takes all
+    32: one full word), with CRC 11 wherever the information word holds one.  Each output alone, then all together, against the host mirror"""
+    rng = np.random.default_rng([n, L, K, messages == "i8", 17])
+    pos, llr, fz, crc, crc_len, crc_poly = _case(rng, n, messages, 65, 31, min(K, 1 << n))
+    dec = q.PolarList(n, pos, messages, 31, L, crc_len, crc_poly, max_frames=65)
+    host = q.polar_list_decode_host(n, pos, llr, fz, crc, messages, 31, L, crc_len, crc_poly)
+    d = [_dev(torch, a) for a in (llr, fz, crc)]
+    for name in q.LIST_OUTPUTS:
+        _same(_host(dec.decode(*d, want=(name,))), {name: host[name]}, "n=%d L=%d K=%d %s %s alone" % (n, L, len(pos), messages, name))
+    _same(_host(dec.decode(*d)), host, "n=%d L=%d K=%d %s all" % (n, L, len(pos), messages))
+
+
+@pytest.mark.parametrize("messages", ["i8", "f32"])
 def test_context_reuse(q, torch, messages):
     """calls of 130, 3 and 64 frames on one context: a later call leaves no trace of an earlier one, and the context does not grow"""
     rng = np.random.default_rng(9)

@@ -95,6 +95,27 @@ def test_all_frozen_and_rate_one(q, torch, messages, K):
     R.check_outputs(out, R.decode(llr, mask, fv, messages, 31), pos, N, mask, K)
 
 
+@pytest.mark.parametrize("messages", ["i8", "f32"])
+@pytest.mark.parametrize("K", [0, 33])
+@pytest.mark.parametrize("n", [6, 11, 12])
+def test_small_shape_edges_are_the_mirror(q, torch, n, K, messages):
+    """the edges of what the three decoders share (the info row, level 5 of a leaf block, the context): 65 frames, no information bit, and 33
+    of them (an info row whose second word holds one bit).  Each output alone, then all together, against the host mirror.  n = 6: level 6 is
+    the caller's row; n = 11: exactly one window; n = 12: two windows and the first combine on the row"""
+    rng = np.random.default_rng([n, K, messages == "i8", 16])
+    N, F = 1 << n, 65
+    pos, _ = R.random_code(rng, N, K)
+    llr = _inputs(rng, messages, F, N, 31)
+    fz = R.pack(rng.integers(0, 2, (F, N), dtype=np.uint8))
+    host = q.polar_decode_host(n, pos, llr, fz, messages, 31, leaf=True)
+    dec = q.Polar(n, pos, messages, 31, max_frames=F, form="wide")
+    d_llr, d_fz = _dev(torch, llr), _dev(torch, fz)
+    for name in ("u", "info", "x", "leaf"):
+        out = _host(dec.decode(d_llr, d_fz, leaf=name == "leaf", want=() if name == "leaf" else (name,)))
+        _same(out, {name: host[name]}, "n=%d K=%d %s alone" % (n, K, messages))
+    _same(_host(dec.decode(d_llr, d_fz, leaf=True)), host, "n=%d K=%d %s all" % (n, K, messages))
+
+
 @pytest.mark.parametrize("n,messages", [(16, "i8"), (16, "f32"), (18, "i8"), (18, "f32")])
 def test_wide_is_the_lanes_form_and_the_mirror(q, torch, n, messages):
     rng = np.random.default_rng([n, messages == "i8", 8])

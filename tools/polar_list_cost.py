@@ -15,23 +15,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import _qldpc_loader  # noqa: E402
+from polar_common import awgn_frames, event_ms  # noqa: E402
 
 SHAPES = [(10, 20000, "i8", (1, 2, 4, 8)), (10, 20000, "f32", (1, 2, 4, 8)), (14, 4096, "i8", (4,))]
 CRC11 = (11, 0x621)
-
-
-def event_ms(torch, fn, runs):
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b))
-    return {"median": float(np.median(out)), "best": float(min(out)), "runs": [round(v, 4) for v in out]}
 
 
 def main():
@@ -47,10 +34,7 @@ def main():
     for n, F, messages, lists in SHAPES:
         N = 1 << n
         pos = np.sort(q.polar_pw_order(n)[N // 2:]).astype(np.int32)
-        if messages == "i8":
-            llr = np.clip(np.floor((1.0 + 0.7 * rng.standard_normal((F, N), dtype=np.float32)) * 7.75), -32, 31).astype(np.int8)
-        else:
-            llr = (2.0 * (1.0 + 0.7 * rng.standard_normal((F, N), dtype=np.float32)) / 0.49).astype(np.float32)
+        llr = awgn_frames(rng, n, F, messages)
         d_llr = torch.from_numpy(llr).cuda()
         sc = q.Polar(n, pos, messages, 31, max_frames=F)
         sc_ms = event_ms(torch, lambda: sc.decode(d_llr), args.runs)

@@ -19,6 +19,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import _qldpc_loader  # noqa: E402
+from polar_common import awgn_frames, event_ms  # noqa: E402
 
 SIZES = (10, 14, 16, 18, 20)
 FRAMES = (1, 8, 64, 4096)
@@ -34,26 +35,11 @@ def core_define(name):
     return int(re.search(r"#define\s+%s\s+(\d+)" % name, text).group(1))
 
 
-def event_ms(torch, fn, runs):
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b))
-    return {"median": float(np.median(out)), "best": float(min(out)), "worst": float(max(out)), "runs": [round(v, 4) for v in out]}
-
-
 def frames_of(torch, rng, n, F, messages):
     """F frames of a half-rate code on AWGN: at most 64 distinct ones on the host, repeated on the device (a decode's time does not depend on the
     values) -> (the distinct frames, the device tensor [F, N])"""
-    N, Fd = 1 << n, min(F, 64)
-    noise = 1.0 + 0.7 * rng.standard_normal((Fd, N), dtype=np.float32)
-    llr = np.clip(np.floor(noise * 7.75), -32, 31).astype(np.int8) if messages == "i8" else (2.0 * noise / 0.49).astype(np.float32)
+    Fd = min(F, 64)
+    llr = awgn_frames(rng, n, Fd, messages)
     return llr, torch.from_numpy(llr).cuda().repeat((F + Fd - 1) // Fd, 1)[:F].contiguous()
 
 
