@@ -45,6 +45,7 @@
  *   qldpc_mc_sweep_tables                 the Eb/N0 points of those sims side by side in one batch, a table per point    ML/sim_results.m
  *   qldpc_polar_*                         the polar encoder and SC decoder of the fourth curve of that figure   ML/nrpolar_encode.m, nrpolar_scdecode.m, nrpolar_scdecode_FP.m
  *   qldpc_polar_list_* / _crc_host        the list decoder with a CRC of the fifth curve (list 4, CRC 11)          ML/nrpolar_sclistdecode_FP.m
+ *   qldpc_polar_mc_*                      the frame loop of those two scripts around either decoder, on the device   the while loops of the same scripts
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -1644,6 +1645,67 @@ int    qldpc_polar_list_decode_host(int log2_n, int n_info, const int *info_pos,
                                     uint32_t crc_poly, int n_frames, const void *llr, const uint32_t *frozen_u, const uint32_t *crc,
                                     uint32_t *u, uint32_t *info, uint32_t *x, int32_t *pick, void *metric, uint32_t *list_x);
 int    qldpc_polar_crc_host(int crc_len, uint32_t crc_poly, int n_bits, int n_frames, const uint32_t *rows, uint32_t *crc);
+
+/*
+ * Polar codes: a device-resident Monte-Carlo FER loop (qldpc_polar_mc_*) around an existing qldpc_polar context (either form) or an existing
+ * qldpc_polar_list context: source -> (CRC) -> u -> encode -> table channel -> SC or list decode -> monitor, everything queued on the context's
+ * stream, ONE small counter read-back per batch.  The definition is csrc/qldpc_polar_mc_core.h, shared by the kernels
+ * (csrc/qldpc_kernels_polar_mc.h) and the host mirror (qldpc_polar_mc_frames_host), which agree bit for bit.
+ *
+ * Frame i (a 64-bit global index) is a pure function of (seed, i, code, CRC, frozen mode, table), whatever the batch, the launch shape or the
+ * split of a run into calls:
+ *   message   A = n_info - crc_len bits, word j = the LDPC loop's info word (stream 0) of (seed, i, j, A); QLDPC_MC_SOURCE_ZERO: zeros
+ *   info row  n_info bits: the message, then its CRC remainder (the list decoder's register form) MSB first, so the row's remainder is 0 and the
+ *             list decoder gets no crc row.  An SC context has crc_len = 0.
+ *   u         u[info_pos[m]] = info bit m.  QLDPC_POLAR_MC_FROZEN_ZERO: frozen positions 0, no frozen row for the decoder.
+ *             QLDPC_POLAR_MC_FROZEN_RANDOM: frozen word w = Philox output word w % 4 at counter (w / 4, 4, i_lo, i_hi), masked to the frozen
+ *             positions, and the u row is the decoder's frozen row: the reconciliation form (x is a uniformly random key, the frozen values Alice's).
+ *   x         encode(u)
+ *   channel   ONE threshold table of 2 .. 256 levels with the semantics of qldpc_mc_set_channel (cum0, cum1 [levels - 1], value [levels]):
+ *             position v draws output word v % 4 at counter (v / 4, 3, i_lo, i_hi), level = #{k : u >= cum[x_v][k]}, LLR = value[level].  A
+ *             QLDPC_POLAR_I8 context stores (int8)value[level]: every value must be an integer in [-128, 127] (QLDPC_EINVAL otherwise).  A BSC is
+ *             the 2-level table {+mag, -mag}.  flips of a frame = positions whose LLR's sign contradicts x_v (an LLR of 0 contradicts nothing).
+ *   verdict   be = the wrong bits among the A message bits of the decoder's info row; frame error iff be > 0; crc_fail iff the list decoder's pick
+ *             is -1 (never with SC or crc_len = 0); undetected iff a frame error that is no crc_fail.
+ *
+ * qldpc_polar_mc_create: exactly one of sc and list (not owned: it must outlive the object); batch = 0 means the context's max_frames, more than
+ * that is QLDPC_ESIZE; the object allocates everything here, no later call allocates.  qldpc_polar_mc_set_channel: QLDPC_ESIZE for levels outside
+ * 2 .. 256, QLDPC_EINVAL for a missing array, a decreasing row, an entry above 2^32 or a value an int8 context cannot store; a refused call leaves
+ * the previous table in force.  qldpc_polar_mc_run and _frames_dev without a table: QLDPC_ESTATE.
+ * qldpc_polar_mc_frames_dev: frames first_frame .. + n_frames - 1 into d_info [n][ceil(n_info/32)], d_u, d_x [n][ceil(N/32)], d_llr [n][N] int8 or
+ * float (16-byte aligned), d_flips [n]; each may be NULL; asynchronous.
+ * qldpc_polar_mc_run: batches of `batch` frames (the last ragged) from first_frame until max_frames are done or, checked at a batch boundary,
+ * max_frame_errors (0: no such rule) are reached.  counters[QLDPC_POLAR_MC_COUNTERS] by the enum below; ms (optional) [8] by QLDPC_POLAR_MC_MS_*:
+ * hipEvent times of the stages summed over the batches, and the wall time of the call.
+ * qldpc_polar_mc_failed_frames: the first fail_cap failed global indices of the last run, ascending; copies min(cap, their number), returns their
+ * number.  Every argument check runs before the first HIP call; the object is not re-entrant; there is no CPU fallback.
+ *
+ * qldpc_polar_mc_awgn_table (host only) -> the level count, or a status: BPSK over AWGN of deviation sigma, received value r quantised with
+ * rounding = 0: floor(r / rmax maxq) clamped to [-maxq - 1, maxq], 2 maxq + 2 levels, qldpc_mc_awgn_table bit for bit (the SC scripts);
+ * rounding = 1: round(clip(r, -rmax, rmax) / rmax maxq), 2 maxq + 1 levels, boundaries (k - maxq + 1/2) rmax / maxq, value[l] = l - maxq (the list
+ * script).  cum0, cum1 hold levels - 1 entries, value levels.
+ * qldpc_polar_mc_frames_host: the mirror; every output optional; levels = 0 (no table) allows neither llr nor flips (QLDPC_ESTATE).
+ */
+typedef struct qldpc_polar_mc qldpc_polar_mc;
+enum { QLDPC_POLAR_MC_FROZEN_ZERO = 0, QLDPC_POLAR_MC_FROZEN_RANDOM = 1 };
+enum { QLDPC_POLAR_MC_FRAMES = 0, QLDPC_POLAR_MC_BIT_ERRORS, QLDPC_POLAR_MC_FRAME_ERRORS, QLDPC_POLAR_MC_UNDETECTED, QLDPC_POLAR_MC_CRC_FAILS,
+       QLDPC_POLAR_MC_CHANNEL_FLIPS, QLDPC_POLAR_MC_CHANNEL_BITS, QLDPC_POLAR_MC_BATCHES, QLDPC_POLAR_MC_NEXT_FRAME, QLDPC_POLAR_MC_COUNTERS = 16 };
+enum { QLDPC_POLAR_MC_MS_SOURCE = 0, QLDPC_POLAR_MC_MS_ENCODE, QLDPC_POLAR_MC_MS_CHANNEL, QLDPC_POLAR_MC_MS_DECODE, QLDPC_POLAR_MC_MS_MONITOR,
+       QLDPC_POLAR_MC_MS_TOTAL };
+int    qldpc_polar_mc_create(qldpc_polar *sc, qldpc_polar_list *list, uint64_t seed, int batch, int fail_cap, int frozen_mode, qldpc_polar_mc **out);
+void   qldpc_polar_mc_free(qldpc_polar_mc *mc);
+size_t qldpc_polar_mc_device_bytes(const qldpc_polar_mc *mc);
+int    qldpc_polar_mc_set_source(qldpc_polar_mc *mc, int mode);
+int    qldpc_polar_mc_set_channel(qldpc_polar_mc *mc, int levels, const uint64_t *cum0, const uint64_t *cum1, const float *value);
+int    qldpc_polar_mc_frames_dev(qldpc_polar_mc *mc, uint64_t first_frame, int n_frames, uint32_t *d_info, uint32_t *d_u, uint32_t *d_x, void *d_llr,
+                                 uint32_t *d_flips);
+int    qldpc_polar_mc_run(qldpc_polar_mc *mc, uint64_t first_frame, uint64_t max_frames, uint64_t max_frame_errors, uint64_t *counters, double *ms);
+int    qldpc_polar_mc_failed_frames(qldpc_polar_mc *mc, uint64_t *frames, int cap);
+/* host only, no device needed */
+int    qldpc_polar_mc_awgn_table(double sigma, double rmax, int maxq, int rounding, uint64_t *cum0, uint64_t *cum1, float *value);
+int    qldpc_polar_mc_frames_host(int log2_n, int n_info, const int *info_pos, int messages, int crc_len, uint32_t crc_poly, int frozen_mode,
+                                  int source_mode, uint64_t seed, int levels, const uint64_t *cum0, const uint64_t *cum1, const float *value,
+                                  uint64_t first_frame, int n_frames, uint32_t *info, uint32_t *u, uint32_t *x, void *llr, uint32_t *flips);
 
 #ifdef __cplusplus
 }

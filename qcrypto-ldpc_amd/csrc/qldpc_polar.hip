@@ -30,6 +30,8 @@ struct qldpc_polar {
     uint32_t *d_U, *d_X;           /* groups x W x 64 each; wide: max_frames x W each */
 };
 
+const pl_ctx *pl_ctx_of_sc(const qldpc_polar *p) { return &p->c; }
+
 extern "C" void qldpc_polar_free(qldpc_polar *p)
 {
     if (!p) return;

@@ -21,6 +21,12 @@ int pl_args_frozen_mask(const char *who, int log2_n, int n_info, const int *info
 /* the argument checks of a host SC decode and, where they pass, the frozen mask */
 int pl_host_decode_args(const char *who, int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr, uint32_t **frozen_mask);
 
+/* The Monte-Carlo loop's own (defined in qldpc_polar_mc_host.c; called by the mirror of its frames and by the device object): the two modes, and
+   a threshold table -- qldpc_mc_set_channel's rules and, with int8 messages, integer values in [-128, 127] -- built into *t where it passes */
+struct mc_soft_table;
+int pmc_args_modes(const char *who, int frozen_mode, int source_mode);
+int pmc_args_table(const char *who, int messages, int levels, const uint64_t *cum0, const uint64_t *cum1, const float *value, struct mc_soft_table *t);
+
 #ifdef __cplusplus
 }
 #endif

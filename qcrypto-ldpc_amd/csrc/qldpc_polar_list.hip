@@ -25,6 +25,12 @@ struct qldpc_polar_list {
     uint32_t *d_M, *d_rem;         /* max_frames x L each: the metrics (uint32 or float) and the remainders */
 };
 
+const pl_ctx *pl_ctx_of_list(const qldpc_polar_list *p, int *crc_len, uint32_t *crc_poly)
+{
+    *crc_len = p->crc_len; *crc_poly = p->crc_poly;
+    return &p->c;
+}
+
 extern "C" void qldpc_polar_list_free(qldpc_polar_list *p)
 {
     if (!p) return;
