@@ -46,6 +46,7 @@
  *   qldpc_polar_*                         the polar encoder and SC decoder of the fourth curve of that figure   ML/nrpolar_encode.m, nrpolar_scdecode.m, nrpolar_scdecode_FP.m
  *   qldpc_polar_list_* / _crc_host        the list decoder with a CRC of the fifth curve (list 4, CRC 11)          ML/nrpolar_sclistdecode_FP.m
  *   qldpc_polar_mc_*                      the frame loop of those two scripts around either decoder, on the device   the while loops of the same scripts
+ *   qldpc_polar_tally_* / _construct_*    (not in the reference, which reads the 5G sequence) the information set fitted to a channel by genie-aided Monte Carlo
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -1555,7 +1556,8 @@ int    qldpc_mc_guess_next_host(int guess_bits, int batch, uint64_t pool, uint64
  *   size      N = 2^log2_n, 1 <= log2_n <= 20 (QLDPC_ESIZE).  Index i is natural order, no bit reversal.  Rows are packed MSB-first,
  *             ceil(N / 32) words; bits past N are ignored on input and zero on output.
  *   code      info_pos[n_info]: the positions that carry information, distinct (QLDPC_EINVAL) and below N (QLDPC_ESIZE), 0 <= n_info <= N
- *             (QLDPC_ESIZE); every other position is frozen.  The construction is the caller's: the library ships no reliability table.
+ *             (QLDPC_ESIZE); every other position is frozen.  The library ships no reliability table; qldpc_polar_tally_* and
+ *             qldpc_polar_construct_* below fit an information set to a channel.
  *   encode    for m = 1, 2, .., N/2: in every block of 2m bits the first half becomes first ^ second.  An involution.
  *   decode    at a node with beliefs [a, b]: the left child gets f(a, b) = sgn(a) sgn(b) min(|a|, |b|) (sgn(v) = -1 iff v < 0), the right child
  *             g(a, b, c) = sat(b + (1 - 2c) a) with c the RE-ENCODED decisions of the left child; the node returns [c_left ^ c_right, c_right].
@@ -1706,6 +1708,43 @@ int    qldpc_polar_mc_awgn_table(double sigma, double rmax, int maxq, int roundi
 int    qldpc_polar_mc_frames_host(int log2_n, int n_info, const int *info_pos, int messages, int crc_len, uint32_t crc_poly, int frozen_mode,
                                   int source_mode, uint64_t seed, int levels, const uint64_t *cum0, const uint64_t *cum1, const float *value,
                                   uint64_t first_frame, int n_frames, uint32_t *info, uint32_t *u, uint32_t *x, void *llr, uint32_t *flips);
+
+/*
+ * Polar codes: genie-aided code construction (qldpc_polar_tally_*, qldpc_polar_mc_construct, qldpc_polar_construct_*): which positions should
+ * carry information on a given channel, by Arikan's Monte-Carlo method.  The rule is csrc/qldpc_polar_tally_core.h, shared by the kernel
+ * (csrc/qldpc_kernels_polar_tally.h), the mirror and the helpers (csrc/qldpc_polar_tally_host.c), which agree count for count.
+ *
+ *   genie     for a frame with true row u_true, L_p is the leaf belief of the SC decoder above with EVERY position frozen to u_true.
+ *   tally     position p of the frame is a TIE iff L_p == 0 (a float -0.0 too) and WRONG iff L_p != 0 and (L_p < 0) != u_p.
+ *             tally[0][p] counts the wrong frames, tally[1][p] the ties: a row of [2][N] uint64.  Integers only: any order of addition agrees.
+ *   score     score[p] = 2 wrong + ties; score / (2 frames) estimates the error probability of position p under a uniformly random bit (a tie
+ *             decides 0 and is wrong half the time; counting it as 1/2 takes that coin's variance out).  u_true must be uniformly random.
+ *
+ * qldpc_polar_tally_dev: d_llr and d_u_true as qldpc_polar_decode_dev's d_llr and d_frozen_u; the counts of the n_frames frames are ADDED to
+ * d_tally [2][N] on the device, which is the caller's (zero it first).  Any QLDPC_POLAR_LANES context of the size and the messages; its own
+ * information set is ignored.  Asynchronous on the context's stream, allocates nothing, one or two launches, no u, x or leaf row is written.
+ * n_frames = 0 is a no-op; a QLDPC_POLAR_WIDE context (n > 5) is QLDPC_EUNSUPPORTED: create a lanes context for the tally; a missing pointer is
+ * QLDPC_EINVAL; the other refusals are qldpc_polar_decode_dev's.  Every check runs before the first HIP call.
+ * qldpc_polar_tally_host: the mirror, tally ADDED to as well; refusals as qldpc_polar_decode_host's.
+ * qldpc_polar_mc_construct: frames first_frame .. + n_frames - 1 of a Monte-Carlo object (the frames qldpc_polar_mc_frames_host mirrors), per
+ * batch source -> encode -> channel -> tally against the sent u row, into a [2][N] row the object owns (allocated by create, zeroed here), and
+ * ONE read-back at the end of the call into tally (host, overwritten).  Ranges add up and the batch size does not matter.  It needs an SC
+ * context of the lanes' form and QLDPC_POLAR_MC_FROZEN_RANDOM (QLDPC_EUNSUPPORTED otherwise), and the random source and a channel table
+ * (QLDPC_ESTATE otherwise), so that u is uniformly random at every position.  ms (optional) [8] by QLDPC_POLAR_MC_MS_*: the tally in the
+ * decode slot, 0 in the monitor's.
+ * qldpc_polar_construct_order_host: order[N] = the positions in ascending reliability (a code of K bits takes the LAST K): the key is (score
+ * descending, rank in `prior` ascending); prior[N] is an order of ascending reliability itself, NULL = 0, 1, .., N - 1; QLDPC_EINVAL where it is
+ * no permutation.
+ * qldpc_polar_construct_k_host: *k = the largest K whose last K positions of `order` (a permutation, QLDPC_EINVAL otherwise) have a score sum
+ * <= max_score_sum; for a union bound eps on the frame error rate over `frames` tallied frames that is floor(2 frames eps).
+ * Both helpers refuse a count above 2^40 (QLDPC_ESIZE) instead of overflowing.
+ */
+int    qldpc_polar_tally_dev(qldpc_polar *p, int n_frames, const void *d_llr, const uint32_t *d_u_true, uint64_t *d_tally);
+int    qldpc_polar_mc_construct(qldpc_polar_mc *mc, uint64_t first_frame, uint64_t n_frames, uint64_t *tally, double *ms);
+/* host only, no device needed */
+int    qldpc_polar_tally_host(int log2_n, int messages, int maxq, int n_frames, const void *llr, const uint32_t *u_true, uint64_t *tally);
+int    qldpc_polar_construct_order_host(int log2_n, const uint64_t *tally, const int *prior, int *order);
+int    qldpc_polar_construct_k_host(int log2_n, const uint64_t *tally, const int *order, uint64_t max_score_sum, int *k);
 
 #ifdef __cplusplus
 }

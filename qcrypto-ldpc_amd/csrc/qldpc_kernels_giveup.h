@@ -10,7 +10,7 @@
  *   qk_status_init_count / qk_giveup_out    reset at the start of every run / results in the caller's frame order, generation by generation.
  *
  * The count is a vertical popcount: a lane holds one 64-bit word per check, bit = frame lane, and wanted are the 64 column sums.  A wave transposes
- * the 64 x 64 bit matrix of 64 consecutive checks across its lanes (six butterfly stages: exchange with lane ^ d, keep one half, shift the other in),
+ * the 64 x 64 bit matrix of 64 consecutive checks across its lanes (qldpc_wave_transpose.h: six butterfly stages, exchange with lane ^ d, keep one half, shift the other in),
  * after which lane f holds the bits of frame lane f and ONE popcount gives its sum over those 64 checks.  That is 6 lane exchanges of a 64-bit word
  * and ~6 bit operations each per 64 checks and j; 64 ballots of bit f with a scalar count each, the alternative, cost ~4 instructions per frame lane,
  * about four times as many.  The waves of a workgroup add their sums in LDS (ds_add), then one no-return atomicAdd per frame slot and workgroup goes
@@ -22,25 +22,12 @@
 
 #include "qldpc_kernels.h"
 #include "qldpc_giveup_core.h"
+#include "qldpc_wave_transpose.h"
 
 /* the give-up state of one generation as the kernels take it: weight [G][FG] (shared by all generations: cleared after every test), the per-frame
  * arrays [G][FG], the mask of frames given up [G][V], the frames given up since the decoder was created (qldpc_giveup_total).  best == NULL: the
  * option is off */
 struct qk_giveup { int *weight, *last, *best, *since; u64 *gave; unsigned long long *total; int patience; };
-
-/* stage d of the 64 x 64 bit transpose: x = this lane's word, y = the word of lane ^ d */
-__device__ __forceinline__ u64 qk_transpose_stage(u64 x, u64 y, int lane, int d)
-{
-    const u64 m = ~0ull / ((1ull << d) + 1ull);      /* the bit positions with bit d clear */
-    return (lane & d) ? ((x & ~m) | ((y >> d) & m)) : ((x & m) | ((y & m) << d));
-}
-/* bit b of the result in lane l = bit l of x in lane b; every lane of the wave must take part */
-__device__ __forceinline__ u64 qk_transpose64(u64 x, int lane)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x = qk_transpose_stage(x, __shfl_xor(x, d), lane, d);
-    return x;
-}
 
 template <int V>
 __global__ __launch_bounds__(256) void qk_syndrome_count(const u64 *__restrict__ mask, const int *__restrict__ cn_var_t, int max_dc, int M, int N,

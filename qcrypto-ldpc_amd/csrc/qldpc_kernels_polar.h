@@ -11,6 +11,7 @@
  *              pl_load transposes the caller's frame-major rows into level n (and clamps int8 levels).
  *   levels >= 6  pl_decode produces level l from level l + 1 in steps of 32 elements: 16 quad loads issued together, 32 f or g (pl_pair32), 8 quad stores
  *              (pl_store32); the list decoder's levels >= 5 take the same step.  g reads its 32 re-encoded bits from one word of the lane's x row.
+ *              pl_block_beliefs is that descent for one leaf block, which the tally form (qldpc_kernels_polar_tally.h) takes too.
  *   levels <= 5  a leaf block (32 leaves; all N where N < 32, then read from the caller's rows directly) lives in registers: 32 + 16 + .. + 1
  *              beliefs, the recursion unrolled by templates, the frozen flags of the block one wave-uniform word and its frozen values one word of
  *              the frame's frozen row.
@@ -137,6 +138,28 @@ __device__ __forceinline__ void pl_node(const M &m, const typename M::reg *L, ui
     }
 }
 
+/* the 32 beliefs R[] of leaf block j of a frame of n > 5 levels: the levels above the block that change with it, from the lane's quads V (= Vw)
+   and its x row X (stride PL_GROUP), written back level by level; level 5 stays in registers */
+template <class M>
+__device__ __forceinline__ void pl_block_beliefs(const M &m, int n, size_t j, const pl_quad<typename M::mem> *V, pl_quad<typename M::mem> *Vw, const uint32_t *X,
+                                                 typename M::reg *R)
+{
+    const int top = j == 0 ? n - 1 : pl_ctz((long)j) + PL_SUB_LOG;
+    for (int l = top; l > PL_SUB_LOG; l--) {               /* level l from level l + 1 */
+        const size_t qs = pl_level_off(n, l + 1) / 4u, qd = pl_level_off(n, l) / 4u, h = (size_t)1 << l;
+        const bool is_g = j != 0 && l == top;
+        const size_t w0 = j - (h >> 5);                  /* g: the node of h leaves that ends where block j begins */
+        for (size_t k = 0; k < h; k += 32u) {
+            const uint32_t cw = is_g ? X[(w0 + (k >> 5)) * PL_GROUP] : 0u;
+            pl_pair32(m, V, qs + k / 4u, qs + (h + k) / 4u, is_g, cw, R);
+            pl_store32<M>(Vw, qd + k / 4u, R);
+        }
+    }
+    const bool is_g = j != 0 && top == PL_SUB_LOG;
+    const size_t q6 = pl_level_off(n, PL_SUB_LOG + 1) / 4u;
+    pl_pair32(m, V, q6, q6 + 8u, is_g, is_g ? X[(j - 1u) * PL_GROUP] : 0u, R);
+}
+
 /* grid = groups, 64 lanes.  SL = log2 of a leaf block; TOP: the block is the whole frame (n = SL <= 5) and is read from the caller's rows.
    fmask: the code's frozen flags, a row; fval: the frames' frozen values [n_frames][W] or NULL; Us, Xs: [groups][W][64]; leaf: [n_frames][N] or NULL */
 template <class M, int SL, bool TOP>
@@ -161,20 +184,7 @@ __global__ __launch_bounds__(PL_GROUP) void pl_decode(M m, int n, int n_frames, 
 #pragma unroll
             for (int i = 0; i < S; i++) R[i] = m.load(llr[frame * N + i]);
         } else {
-            const int top = j == 0 ? n - 1 : pl_ctz((long)j) + PL_SUB_LOG;
-            for (int l = top; l > PL_SUB_LOG; l--) {               /* level l from level l + 1 */
-                const size_t qs = pl_level_off(n, l + 1) / 4u, qd = pl_level_off(n, l) / 4u, h = (size_t)1 << l;
-                const bool is_g = j != 0 && l == top;
-                const size_t w0 = j - (h >> 5);                  /* g: the node of h leaves that ends where block j begins */
-                for (size_t k = 0; k < h; k += 32u) {
-                    const uint32_t cw = is_g ? X[(w0 + (k >> 5)) * PL_GROUP] : 0u;
-                    pl_pair32(m, V, qs + k / 4u, qs + (h + k) / 4u, is_g, cw, R);
-                    pl_store32<M>(Vw, qd + k / 4u, R);
-                }
-            }
-            const bool is_g = j != 0 && top == PL_SUB_LOG;
-            const size_t q6 = pl_level_off(n, PL_SUB_LOG + 1) / 4u;
-            pl_pair32(m, V, q6, q6 + 8u, is_g, is_g ? X[(j - 1u) * PL_GROUP] : 0u, R);
+            pl_block_beliefs(m, n, j, V, Vw, X, R);
         }
         uint32_t u = 0u, x = 0u;
         pl_node<S, 0>(m, R, fmask[j], fval ? fval[frame * W + j] : 0u, u, x, leaf);

@@ -11,6 +11,9 @@
  * n <= 5 are one leaf block and go the lanes' way in either form.  QLDPC_POLAR_WIDE_CHIP (6 .. 13), QLDPC_POLAR_WIDE_LANES (64, 256, 512, 1024)
  * and QLDPC_POLAR_WIDE_LEAF (1 or 32) in the environment replace the chip level, the workgroup size and the lanes of a leaf block of the
  * contexts created after: what tools/polar_wide_cost.py measures the alternatives with.
+ *
+ * qldpc_polar_tally_dev (the genie-aided construction, qldpc_polar_tally_core.h) is the lanes' decode in its tally form
+ * (qldpc_kernels_polar_tally.h): pl_load, then pl_tally on the same scratch, into an accumulator that is the caller's.
  */
 #include <hip/hip_runtime.h>
 
@@ -19,6 +22,7 @@
 #include <new>
 #include <type_traits>
 
+#include "qldpc_kernels_polar_tally.h"
 #include "qldpc_kernels_polar_wide.h"
 #include "qldpc_polar_ctx.h"
 
@@ -31,6 +35,7 @@ struct qldpc_polar {
 };
 
 const pl_ctx *pl_ctx_of_sc(const qldpc_polar *p) { return &p->c; }
+bool pl_sc_is_wide(const qldpc_polar *p) { return p->wide; }
 
 extern "C" void qldpc_polar_free(qldpc_polar *p)
 {
@@ -184,4 +189,49 @@ extern "C" int qldpc_polar_decode_dev(qldpc_polar *p, int n_frames, const void *
         LAUNCHCHK();
     }
     return QLDPC_OK;
+}
+
+template <class M, int SL, bool TOP>
+static void pl_launch_tally(const qldpc_polar *p, M m, int n_frames, unsigned groups, const void *d_llr, const uint32_t *d_u_true, uint64_t *d_tally)
+{
+    typedef typename M::mem mem;
+    hipLaunchKernelGGL((pl_tally<M, SL, TOP>), dim3(groups), dim3(PL_GROUP), 0, p->c.stream, m, p->c.n, n_frames, (const mem *)d_llr, d_u_true, (mem *)p->d_B, p->d_X,
+                       (unsigned long long *)d_tally);
+}
+
+template <class M>
+static int pl_run_tally(const qldpc_polar *p, M m, int n_frames, const void *d_llr, const uint32_t *d_u_true, uint64_t *d_tally)
+{
+    typedef typename M::mem mem;
+    const int n = p->c.n;
+    const unsigned groups = (unsigned)(((size_t)n_frames + PL_GROUP - 1) / PL_GROUP);
+    if (n > PL_SUB_LOG) {
+        const size_t tiles = ((size_t)1 << n) / 64u;
+        hipLaunchKernelGGL(pl_load<M>, dim3((unsigned)(groups * tiles)), dim3(256), 0, p->c.stream, m, n, n_frames, (const mem *)d_llr, (mem *)p->d_B);
+        LAUNCHCHK();
+    }
+    switch (n) {
+    case 1: pl_launch_tally<M, 1, true>(p, m, n_frames, groups, d_llr, d_u_true, d_tally); break;
+    case 2: pl_launch_tally<M, 2, true>(p, m, n_frames, groups, d_llr, d_u_true, d_tally); break;
+    case 3: pl_launch_tally<M, 3, true>(p, m, n_frames, groups, d_llr, d_u_true, d_tally); break;
+    case 4: pl_launch_tally<M, 4, true>(p, m, n_frames, groups, d_llr, d_u_true, d_tally); break;
+    case 5: pl_launch_tally<M, 5, true>(p, m, n_frames, groups, d_llr, d_u_true, d_tally); break;
+    default: pl_launch_tally<M, 5, false>(p, m, n_frames, groups, d_llr, d_u_true, d_tally); break;
+    }
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_polar_tally_dev(qldpc_polar *p, int n_frames, const void *d_llr, const uint32_t *d_u_true, uint64_t *d_tally)
+{
+    const int rc = pl_ctx_check_frames(PL_CTX(p), n_frames, "polar_tally_dev");
+    if (rc) return rc;
+    if (p->wide) {
+        qldpc_set_error("polar_tally_dev: the tally has no wide form: create a QLDPC_POLAR_LANES context of the same size and messages for it");
+        return QLDPC_EUNSUPPORTED;
+    }
+    if (n_frames == 0) return QLDPC_OK;
+    if (!d_llr || !d_u_true || !d_tally) { qldpc_set_error("polar_tally_dev: NULL device pointer (d_llr, d_u_true and d_tally are required)"); return QLDPC_EINVAL; }
+    HIPCHK(hipSetDevice(p->c.device));
+    return pl_with_messages(&p->c, [&](auto m) { return pl_run_tally(p, m, n_frames, d_llr, d_u_true, d_tally); });
 }

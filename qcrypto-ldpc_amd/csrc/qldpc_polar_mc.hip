@@ -9,6 +9,10 @@
  *
  * The object owns the rows of a batch (info sent and decoded, u, x, LLRs, flips, pick, fail flags), rank[], the table and the counter row with the
  * failed-frame list behind it, all allocated by create: no call allocates anything.  The context is not owned and must outlive the object.
+ *
+ * qldpc_polar_mc_construct is the same loop with the tally of the genie-aided construction (qldpc_polar_tally_dev) in the decoder's place and no
+ * monitor: source -> u -> encode -> table channel -> tally, into a [2][N] row the object owns where its context is an SC context of the lanes'
+ * form, with ONE read-back at the end of the call.
  */
 #include <hip/hip_runtime.h>
 
@@ -23,7 +27,8 @@
 #include "qldpc_polar_ctx.h"
 
 #define PMC_STAGES 5               /* source, encode, channel, decode, monitor */
-#define PMC_ALLOCS 12
+#define PMC_ALLOCS 13
+#define PMC_EVENTS (PMC_STAGES + 1)       /* of a batch; there are two sets: run uses the first, construct takes them in turn */
 
 struct qldpc_polar_mc {
     qldpc_polar *sc;
@@ -42,7 +47,8 @@ struct qldpc_polar_mc {
     int32_t *d_pick;
     void *d_llr;
     pmc_u64 *d_ctr, *h_ctr;        /* PMC_C_ROW counters, then fail_cap entries; the pinned copy of the counters */
-    hipEvent_t ev[PMC_STAGES + 1];
+    uint64_t *d_tally;             /* [2][N], the accumulator of construct; NULL unless the context is an SC context of the lanes' form */
+    hipEvent_t ev[2 * PMC_EVENTS];
     int n_ev;
     void *owned[PMC_ALLOCS];
     int n_owned;
@@ -89,9 +95,10 @@ static int pmc_build(qldpc_polar_mc *mc)
         (rc = pmc_alloc(mc, &mc->d_pick, B)) || (rc = pmc_alloc(mc, (uint8_t **)&mc->d_llr, esz * B * N)) ||
         (rc = pmc_alloc(mc, &mc->d_ctr, (size_t)PMC_C_ROW + (size_t)mc->fail_cap)))
         return rc;
+    if (mc->sc && !pl_sc_is_wide(mc->sc) && (rc = pmc_alloc(mc, &mc->d_tally, 2 * N))) return rc;
     HIPCHK(hipHostMalloc((void **)&mc->h_ctr, sizeof(pmc_u64) * PMC_C_ROW, hipHostMallocDefault));
     memset(mc->h_ctr, 0, sizeof(pmc_u64) * PMC_C_ROW);
-    for (; mc->n_ev <= PMC_STAGES; mc->n_ev++) HIPCHK(hipEventCreate(&mc->ev[mc->n_ev]));
+    for (; mc->n_ev < 2 * PMC_EVENTS; mc->n_ev++) HIPCHK(hipEventCreate(&mc->ev[mc->n_ev]));
     /* rank[] from the context's own info_pos */
     std::vector<int> pos((size_t)std::max(c->n_info, 1)), rank(32 * c->W);
     if (c->n_info) HIPCHK(hipMemcpy(pos.data(), c->d_info_pos, sizeof(int) * (size_t)c->n_info, hipMemcpyDeviceToHost));
@@ -215,6 +222,18 @@ static int pmc_decode(qldpc_polar_mc *mc, int n)
     return qldpc_polar_list_decode_dev(mc->list, n, mc->d_llr, fz, nullptr, nullptr, mc->d_dec, nullptr, mc->d_pick, nullptr, nullptr);
 }
 
+/* the stage times of the batch recorded in the event set `ev`, which has finished or is waited for, added to stage[] */
+static int pmc_add_stage_times(hipEvent_t *ev, int stages, double *stage)
+{
+    HIPCHK(hipEventSynchronize(ev[stages]));
+    for (int k = 0; k < stages; k++) {
+        float t = 0.0f;
+        HIPCHK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+        stage[k] += (double)t;
+    }
+    return QLDPC_OK;
+}
+
 extern "C" int qldpc_polar_mc_run(qldpc_polar_mc *mc, uint64_t first_frame, uint64_t max_frames, uint64_t max_frame_errors, uint64_t *counters, double *ms)
 {
     if (!mc || !counters) return QLDPC_EINVAL;
@@ -253,11 +272,7 @@ extern "C" int qldpc_polar_mc_run(qldpc_polar_mc *mc, uint64_t first_frame, uint
         HIPCHK(hipEventRecord(mc->ev[PMC_STAGES], s));
         HIPCHK(hipMemcpyAsync(mc->h_ctr, mc->d_ctr, sizeof(pmc_u64) * PMC_C_DEVICE, hipMemcpyDeviceToHost, s));      /* the ONE read-back of the batch */
         HIPCHK(hipStreamSynchronize(s));
-        for (int k = 0; k < PMC_STAGES; k++) {
-            float t = 0.0f;
-            HIPCHK(hipEventElapsedTime(&t, mc->ev[k], mc->ev[k + 1]));
-            stage[k] += (double)t;
-        }
+        if ((rc = pmc_add_stage_times(mc->ev, PMC_STAGES, stage))) return rc;
         batches++;
         done += (uint64_t)nb;
         if (max_frame_errors && mc->h_ctr[PMC_C_FRAME_ERRORS] >= max_frame_errors) break;
@@ -273,6 +288,61 @@ extern "C" int qldpc_polar_mc_run(qldpc_polar_mc *mc, uint64_t first_frame, uint
     if (ms) {
         static_assert(QLDPC_POLAR_MC_MS_SOURCE == 0 && QLDPC_POLAR_MC_MS_MONITOR == PMC_STAGES - 1 && QLDPC_POLAR_MC_MS_TOTAL == PMC_STAGES, "the stages in the ABI's order");
         for (int k = 0; k < PMC_STAGES; k++) ms[k] = stage[k];
+        ms[QLDPC_POLAR_MC_MS_TOTAL] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    return QLDPC_OK;
+}
+
+/* The genie-aided construction (qldpc_polar_tally_core.h) over the object's own frames: per batch source -> encode -> channel -> tally of the
+   batch's LLRs against its sent u row, into the object's [2][N] row.  Nothing is read back before the end; the times of a batch are read one
+   batch late, from the other event set, while the next batch runs */
+extern "C" int qldpc_polar_mc_construct(qldpc_polar_mc *mc, uint64_t first_frame, uint64_t n_frames, uint64_t *tally, double *ms)
+{
+    if (!mc || !tally) return QLDPC_EINVAL;
+    if (ms) memset(ms, 0, sizeof(double) * 8);
+    if (!mc->sc) {
+        qldpc_set_error("polar_mc_construct: the tally is the SC decoder's: create the object around a qldpc_polar context of the lanes' form, not a list context");
+        return QLDPC_EUNSUPPORTED;
+    }
+    if (pl_sc_is_wide(mc->sc)) {
+        qldpc_set_error("polar_mc_construct: the tally has no wide form: create the object around a QLDPC_POLAR_LANES context");
+        return QLDPC_EUNSUPPORTED;
+    }
+    if (mc->frozen_mode != QLDPC_POLAR_MC_FROZEN_RANDOM) {
+        qldpc_set_error("polar_mc_construct: u must be uniformly random at every position: create the object with QLDPC_POLAR_MC_FROZEN_RANDOM");
+        return QLDPC_EUNSUPPORTED;
+    }
+    if (mc->source != QLDPC_MC_SOURCE_RANDOM) {
+        qldpc_set_error("polar_mc_construct: u must be uniformly random at every position: qldpc_polar_mc_set_source(QLDPC_MC_SOURCE_RANDOM) comes first");
+        return QLDPC_ESTATE;
+    }
+    if (!mc->have_table) { qldpc_set_error("polar_mc_construct: no channel table (qldpc_polar_mc_set_channel comes first)"); return QLDPC_ESTATE; }
+    const pl_ctx *c = mc->c;
+    const size_t row_bytes = sizeof(uint64_t) * ((size_t)2 << c->n);
+    HIPCHK(hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    HIPCHK(hipMemsetAsync(mc->d_tally, 0, row_bytes, s));
+    double stage[PMC_STAGES] = {0.0};
+    uint64_t batches = 0;
+    int rc;
+    const auto t_start = std::chrono::steady_clock::now();
+    for (uint64_t done = 0; done < n_frames; batches++) {
+        const int nb = (int)std::min<uint64_t>((uint64_t)mc->batch, n_frames - done);
+        hipEvent_t *ev = mc->ev + (batches & 1u) * PMC_EVENTS;
+        if (batches >= 2 && (rc = pmc_add_stage_times(ev, PMC_STAGES - 1, stage))) return rc;      /* the set's last use, two batches ago */
+        HIPCHK(hipEventRecord(ev[0], s));
+        if ((rc = pmc_generate(mc, first_frame + done, nb, 3, mc->d_info, mc->d_u, mc->d_x, mc->d_llr, nullptr, s, ev))) return rc;
+        HIPCHK(hipEventRecord(ev[3], s));
+        if ((rc = qldpc_polar_tally_dev(mc->sc, nb, mc->d_llr, mc->d_u, mc->d_tally))) return rc;
+        HIPCHK(hipEventRecord(ev[4], s));
+        done += (uint64_t)nb;
+    }
+    HIPCHK(hipMemcpyAsync(tally, mc->d_tally, row_bytes, hipMemcpyDeviceToHost, s));      /* the ONE read-back of the call */
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint64_t b = batches > 2 ? batches - 2 : 0; b < batches; b++)
+        if ((rc = pmc_add_stage_times(mc->ev + (b & 1u) * PMC_EVENTS, PMC_STAGES - 1, stage))) return rc;
+    if (ms) {
+        for (int k = 0; k < PMC_STAGES; k++) ms[k] = stage[k];      /* the tally in the decode slot, nothing in the monitor's */
         ms[QLDPC_POLAR_MC_MS_TOTAL] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     }
     return QLDPC_OK;

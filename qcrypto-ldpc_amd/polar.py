@@ -1,10 +1,11 @@
 """Polar codes (qldpc_polar_*): the batched encoder, the successive-cancellation decoder and the CRC-aided list decoder on the device, their
-host mirrors, and a polarization-weight order for callers without a standard's reliability table."""
+host mirrors, a polarization-weight order for callers without a standard's reliability table, and the genie-aided construction that fits an
+information set to a channel (the tally on the device and on the host, the order and the K of a tally)."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import _L, _Handle, _chk, _create, _dev_empty, _dev_rows, _ip, _ptr, _sig, _stream_arg, _torch, _up, _vp, QldpcError
+from ._lib import _L, _Handle, _chk, _create, _dev_empty, _dev_rows, _ip, _ptr, _sig, _stream_arg, _torch, _u64p, _up, _vp, QldpcError
 
 POLAR_I8, POLAR_F32 = 0, 1
 POLAR_FORMS = {"lanes": 0, "wide": 1}
@@ -30,6 +31,10 @@ _sig("qldpc_polar_list_decode_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, 
 _sig("qldpc_polar_list_decode_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, _vp, _up, _up, _up, _up, _up,
                                                _ip, _vp, _up])
 _sig("qldpc_polar_crc_host", C.c_int, [C.c_int, C.c_uint32, C.c_int, C.c_int, _up, _up])
+_sig("qldpc_polar_tally_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp])
+_sig("qldpc_polar_tally_host", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _up, _u64p])
+_sig("qldpc_polar_construct_order_host", C.c_int, [C.c_int, _u64p, _ip, _ip])
+_sig("qldpc_polar_construct_k_host", C.c_int, [C.c_int, _u64p, _ip, C.c_uint64, _ip])
 
 
 def _messages(messages):
@@ -116,6 +121,63 @@ def polar_decode_wide_host(log2_n, info_pos, llr, frozen=None, messages="i8", ma
     return _decode_host(_L.qldpc_polar_decode_wide_host, "polar_decode_wide_host", log2_n, info_pos, llr, frozen, messages, maxq, leaf)
 
 
+# ---- the genie-aided construction --------------------------------------------------------------------------------------------------------
+
+def polar_tally_host(log2_n, llr, u_true, messages="i8", maxq=31, out=None):
+    """the tally's mirror (qldpc_polar_tally_host): llr [F, N] int8 or float32 by `messages`, u_true uint32 [F, W] the frames' true rows
+    -> uint64 [2, N]: the wrong frames and the ties of every position under the SC decoder that is told all earlier bits, ADDED to `out` where
+    one is given"""
+    who = "polar_tally_host"
+    kind, dt, _, llr, tr, n, N, W, F = _host_rows(who, log2_n, POLAR_MAX_LOG2N, [], llr, u_true, messages)
+    if tr is None:
+        raise QldpcError(-1, "polar_tally_host: u_true is required")
+    if out is None:
+        out = np.zeros((2, max(N, 1)), np.uint64)
+    if out.dtype != np.uint64 or out.shape != (2, max(N, 1)) or not out.flags.c_contiguous:
+        raise QldpcError(-6, "polar_tally_host: out must be a contiguous uint64 [2, N]")
+    _chk(_L.qldpc_polar_tally_host(n, kind, int(maxq), F, llr.ctypes.data_as(_vp), tr.ctypes.data_as(_up), out.ctypes.data_as(_u64p)), who)
+    return out
+
+
+def _tally_rows(wrong, ties):
+    """(wrong, ties) of N = 2^n positions each -> n (0: no such size, the library's to refuse) and the [2, N] row the library takes"""
+    t = np.ascontiguousarray(np.stack([np.asarray(wrong).ravel(), np.asarray(ties).ravel()]), dtype=np.uint64)
+    N = t.shape[1]
+    return (N.bit_length() - 1 if N >= 2 and N & (N - 1) == 0 else 0), t
+
+
+def polar_construct_order(wrong, ties, prior=None):
+    """the positions in ascending reliability (qldpc_polar_construct_order_host), so a code of K bits takes the last K: by the score
+    2 wrong + ties descending and, among equal scores, by the rank in `prior` (an order of ascending reliability such as polar_pw_order's; None:
+    by index) -> int32 [N]"""
+    who = "polar_construct_order"
+    n, t = _tally_rows(wrong, ties)
+    pr = None
+    if prior is not None:
+        pr = np.ascontiguousarray(prior, dtype=np.int32).ravel()
+        if pr.size != t.shape[1]:
+            raise QldpcError(-6, "polar_construct_order: prior must hold N = %d positions" % t.shape[1])
+    order = np.zeros(t.shape[1], np.int32)
+    _chk(_L.qldpc_polar_construct_order_host(n, t.ctypes.data_as(_u64p), _ptr(pr, _ip), order.ctypes.data_as(_ip)), who)
+    return order
+
+
+def polar_construct_k(wrong, ties, order, frames, bound):
+    """the largest K whose last K positions of `order` have estimated error probabilities that sum to at most `bound` (a union bound on the frame
+    error rate of SC decoding), from a tally over `frames` frames (qldpc_polar_construct_k_host with floor(2 frames bound))"""
+    who = "polar_construct_k"
+    n, t = _tally_rows(wrong, ties)
+    od = np.ascontiguousarray(order, dtype=np.int32).ravel()
+    if od.size != t.shape[1]:
+        raise QldpcError(-6, "polar_construct_k: order must hold N = %d positions" % t.shape[1])
+    if not (float(bound) >= 0.0 and int(frames) >= 0):
+        raise QldpcError(-1, "polar_construct_k: frames and bound must not be negative")
+    k = C.c_int(0)
+    _chk(_L.qldpc_polar_construct_k_host(n, t.ctypes.data_as(_u64p), od.ctypes.data_as(_ip), min(int(np.floor(2.0 * int(frames) * float(bound))), (1 << 64) - 1),
+                                         C.byref(k)), who)
+    return int(k.value)
+
+
 class _PolarCode(_Handle):
     """what Polar and PolarList share: the code's attributes, the input checks of decode, its output dict and the stream"""
 
@@ -180,6 +242,18 @@ class Polar(_PolarCode):
             out["leaf"] = _dev_empty(llr.device, (F, self.N), llr.dtype)
         self._on_current_stream()
         _chk(_L.qldpc_polar_decode_dev(self._h, F, pl, pf, ptr("u"), ptr("info"), ptr("x"), ptr("leaf")), "Polar.decode")
+        return out
+
+    def tally(self, llr, u_true, out=None):
+        """the genie-aided tally (qldpc_polar_tally_dev): llr [F, N] of the context's messages, u_true int32 / uint32 [F, W] the frames' true rows
+        -> int64 [2, N] on the device, row 0 the wrong frames and row 1 the ties of every position, ADDED to `out` where one is given (a fresh
+        row of zeros otherwise).  The context's own information set plays no part; lanes form only"""
+        torch, F, pl, pu = self._decode_inputs(llr, u_true)
+        if out is None:
+            out = torch.zeros((2, self.N), dtype=torch.int64, device=llr.device)
+        po = _dev_rows(out, 2, self.N, (torch.int64, torch.uint64), "out")
+        self._on_current_stream()
+        _chk(_L.qldpc_polar_tally_dev(self._h, F, pl, pu, po), "Polar.tally")
         return out
 
 

@@ -23,6 +23,7 @@ _sig("qldpc_polar_mc_set_channel", C.c_int, [_vp, C.c_int, _u64p, _u64p, _fp])
 _sig("qldpc_polar_mc_frames_dev", C.c_int, [_vp, C.c_uint64, C.c_int, _vp, _vp, _vp, _vp, _vp])
 _sig("qldpc_polar_mc_run", C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, _u64p, _dp])
 _sig("qldpc_polar_mc_failed_frames", C.c_int, [_vp, _u64p, C.c_int])
+_sig("qldpc_polar_mc_construct", C.c_int, [_vp, C.c_uint64, C.c_uint64, _u64p, _dp])
 _sig("qldpc_polar_mc_awgn_table", C.c_int, [C.c_double, C.c_double, C.c_int, C.c_int, _u64p, _u64p, _fp])
 _sig("qldpc_polar_mc_frames_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_int, _u64p, _u64p, _fp,
                                             C.c_uint64, C.c_int, _up, _up, _up, _vp, _up])
@@ -138,6 +139,19 @@ class PolarMonteCarlo(_Handle):
         _chk(_L.qldpc_polar_mc_run(self._h, int(first_frame) & 0xffffffffffffffff, int(max_frames), int(max_frame_errors), ctr.ctypes.data_as(_u64p),
                                    ms.ctypes.data_as(_dp)), "PolarMonteCarlo.run")
         out = {k: int(ctr[i]) for i, k in enumerate(POLAR_MC_COUNTERS)}
+        out.update({k: float(ms[i]) for i, k in enumerate(POLAR_MC_MS)})
+        return out
+
+    def construct(self, first_frame, n_frames):
+        """the genie-aided tally (qldpc_polar_mc_construct) of the object's own frames first_frame .. first_frame + n_frames - 1, batch by batch on
+        the device with one read-back at the end: for polar_construct_order and polar_construct_k.  It needs a Polar of the lanes' form,
+        frozen="random", the random source and a channel -> dict(wrong, ties uint64 [N], frames, and the times in ms (POLAR_MC_MS): the tally's
+        in decode_ms, monitor_ms 0)"""
+        tally, ms = np.zeros((2, self.decoder.N), np.uint64), np.zeros(8, np.float64)
+        self.decoder._on_current_stream()
+        _chk(_L.qldpc_polar_mc_construct(self._h, int(first_frame) & 0xffffffffffffffff, int(n_frames), tally.ctypes.data_as(_u64p), ms.ctypes.data_as(_dp)),
+             "PolarMonteCarlo.construct")
+        out = dict(wrong=tally[0].copy(), ties=tally[1].copy(), frames=int(n_frames))
         out.update({k: float(ms[i]) for i, k in enumerate(POLAR_MC_MS)})
         return out
 
