@@ -23,6 +23,7 @@
 #include "../../include/qldpc.h"
 #include "qldpc_graph.h"
 #include "qldpc_hip.h"
+#include "qldpc_devmem.h"
 
 struct qldpc_encoder {
     int N, M, K, R;          /* R = number of parity positions (rank of H) */
@@ -34,20 +35,20 @@ struct qldpc_encoder {
     int *d_cn_ptr, *d_cn_var;
     /* IDENTITY */
     uint32_t *d_A; int wpr;  /* [R][wpr] MSB-first rows over the info index */
-    uint8_t *d_par; size_t par_frames;   /* workspace: parity bytes [frames][R] of the call in flight (one encoder is not re-entrant) */
+    uint8_t *d_par; size_t par_cap;      /* workspace: parity bytes [frames][R] of the call in flight (one encoder is not re-entrant), and the bytes it holds */
+    dm_ledger mem;                       /* the tables and the workspace (qldpc_devmem.h) */
 };
 
-/* the workspace holds n_frames frames: grown (never shrunk) with plain hipMalloc -- after a device-wide synchronisation, so nothing in
+/* the workspace holds n_frames frames: grown (never shrunk) with dm_grow -- after a device-wide synchronisation, so nothing in
  * flight still uses the old block -- and kept; qldpc_encoder_reserve sizes it up front so that no call allocates later */
 static int ensure_workspace(qldpc_encoder *e, int n_frames)
 {
-    if ((size_t)n_frames <= e->par_frames) return QLDPC_OK;
+    const size_t need = (size_t)n_frames * (size_t)e->R;
+    if (need <= e->par_cap) return QLDPC_OK;
     HIPCHK(hipDeviceSynchronize());
-    if (e->d_par) (void)hipFree(e->d_par);
-    e->d_par = nullptr; e->par_frames = 0;
-    if (hipMalloc((void **)&e->d_par, (size_t)n_frames * (size_t)e->R) != hipSuccess) { qldpc_set_error("encoder workspace: hipMalloc(%zu bytes) failed", (size_t)n_frames * (size_t)e->R); return QLDPC_ENOMEM; }
-    e->par_frames = (size_t)n_frames;
-    return QLDPC_OK;
+    const int rc = dm_grow(&e->mem, &e->d_par, &e->par_cap, need);
+    if (rc) qldpc_set_error("encoder workspace: device allocation of %zu bytes failed", need);
+    return rc;
 }
 
 __device__ __forceinline__ uint32_t getbit(const uint32_t *w, int i) { return (w[i >> 5] >> (31 - (i & 31))) & 1u; }
@@ -113,9 +114,12 @@ extern "C" void qldpc_encoder_free(qldpc_encoder *e)
 {
     if (!e) return;
     (void)hipSetDevice(e->device);
-    (void)hipFree(e->d_map); (void)hipFree(e->d_cn_ptr); (void)hipFree(e->d_cn_var); (void)hipFree(e->d_A); (void)hipFree(e->d_par);
+    dm_free_all(&e->mem);
     delete e;
 }
+
+/* a table of create that found no room: HIP's status, as ever */
+static int enc_no_room(void) { qldpc_set_error("encoder_create: device allocation failed"); return QLDPC_EHIP; }
 
 static int enc_create(const qldpc_code *code, const char *method, int device, qldpc_encoder *e)
 {
@@ -129,8 +133,7 @@ static int enc_create(const qldpc_code *code, const char *method, int device, ql
         if (code->ira_K <= 0) { qldpc_set_error("encoder IRA: H has no dual-diagonal parity part"); return QLDPC_EUNSUPPORTED; }
         e->ira = 1; e->K = code->ira_K; e->R = code->M;
         for (int n = 0; n < e->N; n++) { if (n < e->K) { e->info_pos.push_back(n); map[(size_t)n] = n; } else { e->parity_pos.push_back(n); map[(size_t)n] = -1 - (n - e->K); } }
-        HIPCHK(hipMalloc((void **)&e->d_cn_ptr, sizeof(int) * ((size_t)e->M + 1)));
-        HIPCHK(hipMalloc((void **)&e->d_cn_var, sizeof(int) * (size_t)code->E));
+        if (dm_alloc(&e->mem, &e->d_cn_ptr, (size_t)e->M + 1) || dm_alloc(&e->mem, &e->d_cn_var, (size_t)code->E)) return enc_no_room();
         HIPCHK(hipMemcpy(e->d_cn_ptr, code->cn_ptr, sizeof(int) * ((size_t)e->M + 1), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->d_cn_var, code->cn_var, sizeof(int) * (size_t)code->E, hipMemcpyHostToDevice));
     } else if (!strcmp(method, "IDENTITY") || !strcmp(method, "LU_DEC") || !strcmp(method, "QC")) {
@@ -145,13 +148,13 @@ static int enc_create(const qldpc_code *code, const char *method, int device, ql
             for (int i = 0; i < e->K; i++)
                 if (A[(size_t)j * wpr64 + i / 64] >> (i % 64) & 1) A32[(size_t)j * e->wpr + i / 32] |= 1u << (31 - i % 32);
         free(piv); free(fr); free(A);
-        HIPCHK(hipMalloc((void **)&e->d_A, sizeof(uint32_t) * A32.size()));
+        if (dm_alloc(&e->mem, &e->d_A, A32.size())) return enc_no_room();
         HIPCHK(hipMemcpy(e->d_A, A32.data(), sizeof(uint32_t) * A32.size(), hipMemcpyHostToDevice));
     } else {
         qldpc_set_error("encoder: unknown method '%s' (IRA | IDENTITY | LU_DEC | QC)", method);
         return QLDPC_EINVAL;
     }
-    HIPCHK(hipMalloc((void **)&e->d_map, sizeof(int) * (size_t)e->N));
+    if (dm_alloc(&e->mem, &e->d_map, (size_t)e->N)) return enc_no_room();
     HIPCHK(hipMemcpy(e->d_map, map.data(), sizeof(int) * (size_t)e->N, hipMemcpyHostToDevice));
     return QLDPC_OK;
 }
@@ -163,7 +166,7 @@ extern "C" int qldpc_encoder_create(const qldpc_code *code, const char *method, 
     if (!code || !method) return QLDPC_EINVAL;
     qldpc_encoder *e = new (std::nothrow) qldpc_encoder();
     if (!e) return QLDPC_ENOMEM;
-    e->d_map = nullptr; e->d_cn_ptr = nullptr; e->d_cn_var = nullptr; e->d_A = nullptr; e->wpr = 0; e->d_par = nullptr; e->par_frames = 0;
+    e->d_map = nullptr; e->d_cn_ptr = nullptr; e->d_cn_var = nullptr; e->d_A = nullptr; e->wpr = 0; e->d_par = nullptr; e->par_cap = 0;
     int rc = enc_create(code, method, device, e);
     if (rc != QLDPC_OK) { qldpc_encoder_free(e); return rc; }
     *out = e;
@@ -218,14 +221,14 @@ extern "C" int qldpc_encode(qldpc_encoder *e, const int *U_K, int *X_N, int n_fr
         for (int i = 0; i < e->K; i++)
             if (U_K[(size_t)f * e->K + i] & 1) info[(size_t)f * Wk + i / 32] |= 1u << (31 - i % 32);
     uint32_t *d_info = nullptr, *d_cw = nullptr;
-    HIPCHK(hipMalloc((void **)&d_info, sizeof(uint32_t) * info.size()));
-    if (hipMalloc((void **)&d_cw, sizeof(uint32_t) * cw.size()) != hipSuccess) { (void)hipFree(d_info); return QLDPC_ENOMEM; }
+    dm_scope tmp;      /* freed on every return */
+    if (dm_alloc(&tmp.m, &d_info, info.size())) { qldpc_set_error("encode: device allocation of %zu bytes failed", sizeof(uint32_t) * info.size()); return QLDPC_EHIP; }
+    if (dm_alloc(&tmp.m, &d_cw, cw.size())) return QLDPC_ENOMEM;
     int rc = QLDPC_OK;
     if (hipMemcpy(d_info, info.data(), sizeof(uint32_t) * info.size(), hipMemcpyHostToDevice) != hipSuccess) rc = QLDPC_EHIP;
     if (!rc) rc = qldpc_encode_packed_dev(e, d_info, d_cw, n_frames, nullptr);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = QLDPC_EHIP;
     if (!rc && hipMemcpy(cw.data(), d_cw, sizeof(uint32_t) * cw.size(), hipMemcpyDeviceToHost) != hipSuccess) rc = QLDPC_EHIP;
-    (void)hipFree(d_info); (void)hipFree(d_cw);
     if (rc) return rc;
     for (int f = 0; f < n_frames; f++)
         for (int n = 0; n < e->N; n++) X_N[(size_t)f * e->N + n] = (int)((cw[(size_t)f * Wn + n / 32] >> (31 - n % 32)) & 1u);

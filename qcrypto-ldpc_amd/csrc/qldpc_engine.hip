@@ -70,10 +70,11 @@ extern "C" int qldpc_copy_probe(int device, size_t bytes, int reps, int wide, do
     const size_t n_rows = bytes / 256 / 64 * 64;      /* whole workgroups of 4 x 16 rows */
     const unsigned blocks = (unsigned)(n_rows / 64);
     float *a = nullptr, *b = nullptr;
+    dm_scope tmp;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = QLDPC_OK;
     float ms = 0.0f;
-    if (hipMalloc((void **)&a, n_rows * 256) != hipSuccess || hipMalloc((void **)&b, n_rows * 256) != hipSuccess) { rc = QLDPC_ENOMEM; goto out; }
+    if (dm_alloc(&tmp.m, &a, n_rows * 64) || dm_alloc(&tmp.m, &b, n_rows * 64)) { rc = QLDPC_ENOMEM; goto out; }
     if (hipMemset(a, 0, n_rows * 256) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { rc = QLDPC_EHIP; goto out; }
     if (wide) hipLaunchKernelGGL((qk_copy_probe<16, true>), dim3(blocks), dim3(256), 0, 0, a, b, n_rows);      /* warm-up */
     else hipLaunchKernelGGL((qk_copy_probe<16, false>), dim3(blocks), dim3(256), 0, 0, a, b, n_rows);
@@ -90,7 +91,6 @@ extern "C" int qldpc_copy_probe(int device, size_t bytes, int reps, int wide, do
 out:
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(a); (void)hipFree(b);
     if (rc == QLDPC_EHIP) qldpc_set_error("copy probe: HIP error");
     return rc;
 }
@@ -121,7 +121,7 @@ static int make_buckets(qldpc_decoder *d, const int *ptr, const int *ids, int n_
         bk.cap = k < n_caps ? caps[k] : 0;
         bk.n = (int)lists[k].size();
         bk.d_rec = nullptr;
-        int rc = dev_alloc(d, &bk.d_list, lists[k].size());
+        int rc = dm_alloc(&d->mem, &bk.d_list, lists[k].size());
         if (rc != QLDPC_OK) return rc;
         out.push_back(bk);
         HIPCHK(hipMemcpy(bk.d_list, lists[k].data(), lists[k].size() * sizeof(int), hipMemcpyHostToDevice));
@@ -134,7 +134,7 @@ static int make_buckets(qldpc_decoder *d, const int *ptr, const int *ids, int n_
                 r[0] = id; r[1] = b; r[2] = deg;
                 for (int e = 0; e < deg; e++) r[QK_REC_HDR + e] = var[b + e];
             }
-            rc = dev_alloc(d, &bk.d_rec, rec.size());
+            rc = dm_alloc(&d->mem, &bk.d_rec, rec.size());
             if (rc != QLDPC_OK) return rc;
             out.back().d_rec = bk.d_rec;
             HIPCHK(hipMemcpy(bk.d_rec, rec.data(), rec.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -161,7 +161,7 @@ static int make_fp_vn_classes(qldpc_decoder *d, const int *vn_ptr, int n_vn, con
         const std::vector<int> &r = recs[(size_t)deg];
         if (r.empty()) continue;
         fp_vn_class c{deg, (int)(r.size() / (size_t)QK_FPV_STRIDE(deg)), nullptr};
-        int rc = dev_alloc(d, &c.d_rec, r.size());
+        int rc = dm_alloc(&d->mem, &c.d_rec, r.size());
         if (rc != QLDPC_OK) return rc;
         out.push_back(c);
         HIPCHK(hipMemcpy(c.d_rec, r.data(), r.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -194,8 +194,7 @@ extern "C" void qldpc_decoder_free(qldpc_decoder *d)
     if (d->stream) (void)hipStreamSynchronize(d->stream); else (void)hipDeviceSynchronize();
     for (auto &r : d->prof_pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     edge_destroy(d);
-    if (d->h_active) (void)hipHostFree(d->h_active);
-    for (auto &b : d->ledger) (void)hipFree(b.p);
+    dm_free_all(&d->mem);
     delete d;
 }
 
@@ -223,13 +222,13 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
     env_int("QLDPC_POLL_EVERY", &d->poll_every);
 
     int rc;
-    if ((rc = dev_alloc(d, &d->d_cn_ptr, (size_t)d->M + 1))) return rc;
-    if ((rc = dev_alloc(d, &d->d_cn_tr, (size_t)d->E + QK_IDX_PAD))) return rc;
-    if ((rc = dev_alloc(d, &d->d_cn_var, (size_t)d->E + QK_IDX_PAD))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_cn_ptr, (size_t)d->M + 1))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_cn_tr, (size_t)d->E + QK_IDX_PAD))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_cn_var, (size_t)d->E + QK_IDX_PAD))) return rc;
     HIPCHK(hipMemset(d->d_cn_tr, 0, sizeof(int) * ((size_t)d->E + QK_IDX_PAD)));
     HIPCHK(hipMemset(d->d_cn_var, 0, sizeof(int) * ((size_t)d->E + QK_IDX_PAD)));
-    if ((rc = dev_alloc(d, &d->d_vn_ptr, (size_t)d->N + 1))) return rc;
-    if ((rc = dev_alloc(d, &d->d_info_pos, (size_t)K))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_vn_ptr, (size_t)d->N + 1))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_info_pos, (size_t)K))) return rc;
     HIPCHK(hipMemcpy(d->d_cn_ptr, code->cn_ptr, sizeof(int) * ((size_t)d->M + 1), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d->d_cn_tr, code->transpose, sizeof(int) * (size_t)d->E, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d->d_cn_var, code->cn_var, sizeof(int) * (size_t)d->E, hipMemcpyHostToDevice));
@@ -237,7 +236,7 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
     {   /* chk_to_var of the frames engine is CN-major: the variable-node passes find the row of slot s at vn_tr[s] */
         std::vector<int> vt((size_t)d->E + QK_IDX_PAD, 0);
         for (int k = 0; k < d->E; k++) vt[(size_t)code->transpose[k]] = k;
-        if ((rc = dev_alloc(d, &d->d_vn_tr, vt.size()))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->d_vn_tr, vt.size()))) return rc;
         HIPCHK(hipMemcpy(d->d_vn_tr, vt.data(), sizeof(int) * vt.size(), hipMemcpyHostToDevice));
     }
     {   /* check -> VN table transposed to [edge position][check] for the syndrome pass (qk_syndrome) */
@@ -245,7 +244,7 @@ static int create_impl(const qldpc_code *code, int K, const int *info_bits_pos, 
         std::vector<int> t((size_t)std::max(1, code->max_dc) * d->M, -1);
         for (int c = 0; c < d->M; c++)
             for (int k = code->cn_ptr[c]; k < code->cn_ptr[c + 1]; k++) t[(size_t)(k - code->cn_ptr[c]) * d->M + c] = code->cn_var[k];
-        if ((rc = dev_alloc(d, &d->d_cn_var_t, t.size()))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->d_cn_var_t, t.size()))) return rc;
         HIPCHK(hipMemcpy(d->d_cn_var_t, t.data(), sizeof(int) * t.size(), hipMemcpyHostToDevice));
     }
     {
@@ -312,7 +311,7 @@ static int frames_create(qldpc_decoder *d, const qldpc_code *code)
         if (n_cls < 0) return n_cls;
         for (int l = 0; l < n_cls; l++)
             if ((rc = make_buckets(d, code->vn_ptr, code->vlayer_order + code->vlayer_ptr[l], code->vlayer_ptr[l + 1] - code->vlayer_ptr[l], nullptr, 0, d->vlayer_classes))) return rc;
-        if ((rc = dev_alloc(d, &d->d_vn_chk, (size_t)d->E))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->d_vn_chk, (size_t)d->E))) return rc;
         HIPCHK(hipMemcpy(d->d_vn_chk, code->vn_chk, sizeof(int) * (size_t)d->E, hipMemcpyHostToDevice));
         double dc2 = 0.0;
         for (int c = 0; c < d->M; c++) { const double dc = code->cn_ptr[c + 1] - code->cn_ptr[c]; dc2 += dc * dc; }
@@ -387,8 +386,8 @@ static int frames_create(qldpc_decoder *d, const qldpc_code *code)
                     }
                 }
                 if (code->max_dv < 32768) {
-                    if ((rc = dev_alloc(d, &d->d_chain_order, (size_t)d->M)) || (rc = dev_alloc(d, &d->d_chain_dep, (size_t)d->E)) ||
-                        (rc = dev_alloc(d, &d->d_chain_ver, (size_t)d->G * d->N)) || (rc = dev_alloc(d, &d->d_chain_ctl, QC_CTL_WORDS))) return rc;
+                    if ((rc = dm_alloc(&d->mem, &d->d_chain_order, (size_t)d->M)) || (rc = dm_alloc(&d->mem, &d->d_chain_dep, (size_t)d->E)) ||
+                        (rc = dm_alloc(&d->mem, &d->d_chain_ver, (size_t)d->G * d->N)) || (rc = dm_alloc(&d->mem, &d->d_chain_ctl, QC_CTL_WORDS))) return rc;
                     HIPCHK(hipMemcpy(d->d_chain_order, chain_order.data(), sizeof(int) * (size_t)d->M, hipMemcpyHostToDevice));
                     HIPCHK(hipMemcpy(d->d_chain_dep, depv.data(), sizeof(int) * (size_t)d->E, hipMemcpyHostToDevice));
                     d->chain = 1;
@@ -400,18 +399,18 @@ static int frames_create(qldpc_decoder *d, const qldpc_code *code)
     /* the fp32 LLR array [G][N][FG] is allocated on first use (ensure_llr): flooding decoders fed through qldpc_load_bits_* never read one */
     if (cfg->schedule == QLDPC_SCHED_FLOODING) {
         const size_t elems = d->msg_i8 ? (G * d->E * FG + 3) / 4 : (d->msg_half ? (G * d->E * FG + 1) / 2 : G * d->E * FG);      /* floats of storage */
-        if (d->msg_i8 && (rc = dev_alloc(d, &d->d_llr8, G * d->N * 64))) return rc;
+        if (d->msg_i8 && (rc = dm_alloc(&d->mem, &d->d_llr8, G * d->N * 64))) return rc;
         const char *coded_env = getenv("QLDPC_CODED_LLR");      /* =0: keep the fp32 LLR array on the load_bits path too (A/B measurements) */
         /* measured: the 8-bit VN pass gets slower with coded LLRs (5.54 vs 6.0 TB/s: four ballot words and selects per VN to save one
          * of nine bytes), so it keeps its quantised LLR array unless QLDPC_CODED_LLR=1 asks otherwise */
         if (!(coded_env && coded_env[0] == '0') && (!d->msg_i8 || (coded_env && coded_env[0] == '1'))) {
-            if ((rc = dev_alloc(d, &d->d_ybits, G * d->N * V))) return rc;
-            if ((rc = dev_alloc(d, &d->d_fmag, G * FG))) return rc;
-            if ((rc = dev_alloc(d, &d->d_fnch, G * FG))) return rc;
-            if ((rc = dev_alloc(d, &d->d_vcls, ((size_t)d->N + 3) / 4 * 4))) return rc;      /* read as dwords by the kernels */
+            if ((rc = dm_alloc(&d->mem, &d->d_ybits, G * d->N * V))) return rc;
+            if ((rc = dm_alloc(&d->mem, &d->d_fmag, G * FG))) return rc;
+            if ((rc = dm_alloc(&d->mem, &d->d_fnch, G * FG))) return rc;
+            if ((rc = dm_alloc(&d->mem, &d->d_vcls, ((size_t)d->N + 3) / 4 * 4))) return rc;      /* read as dwords by the kernels */
         }
-        if ((rc = dev_alloc(d, &d->d_a, elems))) return rc;
-        if ((rc = dev_alloc(d, &d->d_b, elems))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->d_a, elems))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->d_b, elems))) return rc;
         /* The posterior form of a fixed-iteration min-sum run (qldpc_kernels_fpost.h): 0.83 x the rows of an iteration, the same floats.  fp32 messages,
          * 64-frame groups, MS / OMS / NMS, no syndrome test (early exit needs the ballots of every VN after every iteration and stays on the kernels
          * above), every check in a register-resident bucket with degree <= 27, and the IRA chain verified edge by edge.  QLDPC_FLOOD_POST=0 keeps the
@@ -433,39 +432,39 @@ static int frames_create(qldpc_decoder *d, const qldpc_code *code)
                     for (int k = 0; k < d->E; k++) vt[(size_t)code->transpose[k]] = k;
                     if ((rc = make_fp_vn_classes(d, code->vn_ptr, d->ira_K, vt.data(), d->fp_vn_classes))) return rc;
                 }
-                if ((rc = dev_alloc(d, &d->d_fp_chain, (size_t)d->M))) return rc;
+                if ((rc = dm_alloc(&d->mem, &d->d_fp_chain, (size_t)d->M))) return rc;
                 HIPCHK(hipMemcpy(d->d_fp_chain, tab.data(), sizeof(uint32_t) * (size_t)d->M, hipMemcpyHostToDevice));
                 const size_t post_n = G * d->N * 64, st_n = G * d->M * (64 * QK_FP_ROWS);
                 float *base = d->d_a;
-                if (post_n + 2 * st_n > elems) { if ((rc = dev_alloc(d, &d->d_fp_mem, post_n + 2 * st_n))) return rc; base = d->d_fp_mem; }
+                if (post_n + 2 * st_n > elems) { if ((rc = dm_alloc(&d->mem, &d->d_fp_mem, post_n + 2 * st_n))) return rc; base = d->d_fp_mem; }
                 d->fp_post = base; d->fp_st[0] = base + post_n; d->fp_st[1] = base + post_n + st_n;
                 d->fpost = 1;
             }
         }
     } else if (d->msg_i8) {
-        if ((rc = dev_alloc(d, &d->d_llr8, G * d->N * 64))) return rc;
-        if ((rc = dev_alloc(d, &d->d_a, G * d->N * 64))) return rc;      /* post8 */
-        if ((rc = dev_alloc(d, &d->d_b, G * d->E * 64))) return rc;      /* msg8, CN-major */
+        if ((rc = dm_alloc(&d->mem, &d->d_llr8, G * d->N * 64))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->d_a, G * d->N * 64))) return rc;      /* post8 */
+        if ((rc = dm_alloc(&d->mem, &d->d_b, G * d->E * 64))) return rc;      /* msg8, CN-major */
     } else {
-        if ((rc = dev_alloc(d, &d->d_a, G * d->N * FG))) return rc;
-        if ((rc = dev_alloc(d, &d->d_b, G * d->E * FG))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->d_a, G * d->N * FG))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->d_b, G * d->E * FG))) return rc;
     }
-    if ((rc = dev_alloc(d, &d->d_sgn, G * d->N * V))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_sgn, G * d->N * V))) return rc;
     if (d->msg_i8) d->d_hard = d->d_sgn;      /* integer posteriors: signbit(post) and !(post >= 0) are the same ballot */
-    else if ((rc = dev_alloc(d, &d->d_hard, G * d->N * V))) return rc;
-    if ((rc = dev_alloc(d, &d->d_unsat, G * V))) return rc;
-    if ((rc = dev_alloc(d, &d->d_done, G * V))) return rc;
-    if ((rc = dev_alloc(d, &d->d_depth, G * FG))) return rc;
-    if ((rc = dev_alloc(d, &d->d_iters, G * FG))) return rc;
+    else if ((rc = dm_alloc(&d->mem, &d->d_hard, G * d->N * V))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_unsat, G * V))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_done, G * V))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_depth, G * FG))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_iters, G * FG))) return rc;
     d->gu.patience = cfg->giveup_patience;
-    if (d->gu.patience > 0 && ((rc = dev_alloc(d, &d->gu.weight, G * FG)) || (rc = dev_alloc(d, &d->gu.last, G * FG)) || (rc = dev_alloc(d, &d->gu.best, G * FG)) ||
-                               (rc = dev_alloc(d, &d->gu.since, G * FG)) || (rc = dev_alloc(d, &d->gu.gave, G * V)) || (rc = dev_alloc(d, &d->gu.total, 1)))) return rc;
+    if (d->gu.patience > 0 && ((rc = dm_alloc(&d->mem, &d->gu.weight, G * FG)) || (rc = dm_alloc(&d->mem, &d->gu.last, G * FG)) || (rc = dm_alloc(&d->mem, &d->gu.best, G * FG)) ||
+                               (rc = dm_alloc(&d->mem, &d->gu.since, G * FG)) || (rc = dm_alloc(&d->mem, &d->gu.gave, G * V)) || (rc = dm_alloc(&d->mem, &d->gu.total, 1)))) return rc;
     if (d->gu.total) HIPCHK(hipMemset(d->gu.total, 0, sizeof(*d->gu.total)));
-    if ((rc = dev_alloc(d, &d->d_active, 4))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_active, 4))) return rc;
     HIPCHK(hipMemset(d->d_active, 0, 4 * sizeof(int)));
-    if ((rc = dev_alloc(d, &d->d_work, 1))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_work, 1))) return rc;
     /* coherent (fine-grained): the host spins on a word the kernel releases at system scope while the stream is still running */
-    HIPCHK(hipHostMalloc((void **)&d->h_active, 4 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    if (dm_alloc_pinned(&d->mem, &d->h_active, 4, hipHostMallocMapped | hipHostMallocCoherent)) { qldpc_set_error("decoder_create: pinned allocation of the mapped status words failed"); return QLDPC_EHIP; }
     memset(d->h_active, 0, 4 * sizeof(int));
     HIPCHK(hipHostGetDevicePointer((void **)&d->h_active_dev, d->h_active, 0));
     /* active-frame compaction (early exit, messages not frozen): 0 auto (flooding: batches of >= 4 groups; layered: never), 1 always, 2 never.
@@ -478,8 +477,8 @@ static int frames_create(qldpc_decoder *d, const qldpc_code *code)
     const bool layered_compact = cfg->schedule == QLDPC_SCHED_HLAYERED && d->compact_mode == 1 && !d->msg_i8 && !chain_asked && !d->chain;
     if (!cfg->enable_syndrome || (cfg->schedule != QLDPC_SCHED_FLOODING && !layered_compact) || d->freeze || (d->compact_mode == 0 && d->G < 4)) d->compact_mode = 2;
     if (d->compact_mode != 2) {
-        if ((rc = dev_alloc(d, &d->d_gcount, (size_t)d->G))) return rc;
-        if ((rc = dev_alloc(d, &d->d_goff, (size_t)d->G + 1))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->d_gcount, (size_t)d->G))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->d_goff, (size_t)d->G + 1))) return rc;
         if (d->poll_every != 1 && !getenv("QLDPC_POLL_EVERY")) d->poll_every = 1;      /* a compaction is decided on the count the status pass leaves */
     }
     return QLDPC_OK;
@@ -521,6 +520,7 @@ extern "C" int qldpc_decoder_create(const qldpc_code *code, int K, const int *in
     qldpc_decoder *d = new (std::nothrow) qldpc_decoder();
     if (!d) return QLDPC_ENOMEM;
     int rc = create_impl(code, K, info_bits_pos, cfg, d);
+    if (rc == QLDPC_ENOMEM) qldpc_set_error("decoder_create: out of device memory with %zu bytes allocated", d->mem.dev_bytes);
     if (rc != QLDPC_OK) { qldpc_decoder_free(d); return rc; }
     *out = d;
     return QLDPC_OK;
@@ -557,17 +557,17 @@ static void gen0_capture(qldpc_decoder *d)
 static int ensure_llr(qldpc_decoder *d)
 {
     if (d->d_llr) return QLDPC_OK;
-    return dev_alloc(d, &d->d_llr, (size_t)d->G * d->N * d->FG);
+    return dm_alloc(&d->mem, &d->d_llr, (size_t)d->G * d->N * d->FG);
 }
 /* the frame-interleaved posteriors [G][N][FG] fetch_post and fetch_weakest read, on first use */
 static int ensure_post(qldpc_decoder *d)
 {
     if (d->d_post) return QLDPC_OK;
-    return dev_alloc(d, &d->d_post, (size_t)d->G * d->N * d->FG);
+    return dm_alloc(&d->mem, &d->d_post, (size_t)d->G * d->N * d->FG);
 }
 
 extern "C" int qldpc_decoder_set_stream(qldpc_decoder *d, void *s) { if (!d) return QLDPC_EINVAL; d->stream = (hipStream_t)s; return QLDPC_OK; }
-extern "C" size_t qldpc_decoder_device_bytes(const qldpc_decoder *d) { return d ? d->bytes : 0; }
+extern "C" size_t qldpc_decoder_device_bytes(const qldpc_decoder *d) { return d ? d->mem.dev_bytes : 0; }
 extern "C" int qldpc_decoder_flood_post(const qldpc_decoder *d) { return d ? d->fpost : (int)QLDPC_EINVAL; }
 extern "C" int qldpc_last_run_iterations(const qldpc_decoder *d) { return d ? d->last_iters : (int)QLDPC_EINVAL; }
 
@@ -840,7 +840,7 @@ static int poll_active(qldpc_decoder *d, int *active, int *active_frames)
  * Layered schedule: the posteriors are gathered into a side buffer, the next sweep reads the messages of the old generation through d->remap_src and
  * writes them into a side buffer too (the layer kernels update in place: a generation cannot take the place of the one it is read from).
  */
-template <typename T> static int gen_alloc(qldpc_decoder *d, T **p, size_t n) { return *p ? QLDPC_OK : dev_alloc(d, p, n); }
+template <typename T> static int gen_alloc(qldpc_decoder *d, T **p, size_t n) { return *p ? QLDPC_OK : dm_alloc(&d->mem, p, n); }
 
 template <int V>
 static int compact(qldpc_decoder *d, int active_frames)
@@ -854,9 +854,9 @@ static int compact(qldpc_decoder *d, int active_frames)
     if (n.cap < Gn) {      /* first use (or a larger need than any run before): sized for the largest batch this generation can get */
         (void)hipStreamSynchronize(d->stream);
         /* everything a generation past 0 owns (llr / llr8 / post / msg are views into the decoder's side buffers) */
-        dev_release(d, &n.sgn); dev_release(d, &n.hard); dev_release(d, &n.unsat); dev_release(d, &n.done); dev_release(d, &n.ybits); dev_release(d, &n.synd); dev_release(d, &n.ebits);
-        dev_release(d, &n.depth); dev_release(d, &n.iters); dev_release(d, &n.origin); dev_release(d, &n.src); dev_release(d, &n.fmag); dev_release(d, &n.fnch);
-        dev_release(d, &n.gu_last); dev_release(d, &n.gu_best); dev_release(d, &n.gu_since); dev_release(d, &n.gu_gave);
+        dm_release(&d->mem, &n.sgn); dm_release(&d->mem, &n.hard); dm_release(&d->mem, &n.unsat); dm_release(&d->mem, &n.done); dm_release(&d->mem, &n.ybits); dm_release(&d->mem, &n.synd); dm_release(&d->mem, &n.ebits);
+        dm_release(&d->mem, &n.depth); dm_release(&d->mem, &n.iters); dm_release(&d->mem, &n.origin); dm_release(&d->mem, &n.src); dm_release(&d->mem, &n.fmag); dm_release(&d->mem, &n.fnch);
+        dm_release(&d->mem, &n.gu_last); dm_release(&d->mem, &n.gu_best); dm_release(&d->mem, &n.gu_since); dm_release(&d->mem, &n.gu_gave);
         n.cap = std::max(Gn, std::min(o.cap, (int)(d->compact_ratio * (float)o.cap) + 1));
     }
     const size_t C = (size_t)n.cap;
@@ -878,9 +878,9 @@ static int compact(qldpc_decoder *d, int active_frames)
         const int side = k & 1;
         if (d->lay_alt_cap[side] < n.cap) {      /* sized by the first generation that uses it; grows if a later batch needs more */
             (void)hipStreamSynchronize(d->stream);
-            dev_release(d, &d->d_post_alt[side]); dev_release(d, &d->d_msg_alt[side]);
+            dm_release(&d->mem, &d->d_post_alt[side]); dm_release(&d->mem, &d->d_msg_alt[side]);
             d->lay_alt_cap[side] = 0;
-            if ((rc = dev_alloc(d, &d->d_post_alt[side], C * d->N * FG)) || (rc = dev_alloc(d, &d->d_msg_alt[side], C * d->E * FG))) { dev_release(d, &d->d_post_alt[side]); return rc; }
+            if ((rc = dm_alloc(&d->mem, &d->d_post_alt[side], C * d->N * FG)) || (rc = dm_alloc(&d->mem, &d->d_msg_alt[side], C * d->E * FG))) { dm_release(&d->mem, &d->d_post_alt[side]); return rc; }
             d->lay_alt_cap[side] = n.cap;
         }
         n.post = d->d_post_alt[side]; n.msg = d->d_msg_alt[side];
@@ -889,12 +889,12 @@ static int compact(qldpc_decoder *d, int active_frames)
         const int side = k & 1;
         if (d->llr_alt_cap[side] < n.cap) {      /* sized by the first generation that uses it (later ones are smaller); grows if a later batch needs more */
             (void)hipStreamSynchronize(d->stream);
-            dev_release(d, &d->d_llr_alt[side]); dev_release(d, &d->d_llr8_alt[side]);
+            dm_release(&d->mem, &d->d_llr_alt[side]); dm_release(&d->mem, &d->d_llr8_alt[side]);
             d->llr_alt_cap[side] = n.cap;
         }
         const size_t need = (size_t)d->llr_alt_cap[side] * d->N * (rows8 ? 64 : (size_t)FG);
-        if (rows8 && !d->d_llr8_alt[side] && (rc = dev_alloc(d, &d->d_llr8_alt[side], need))) return rc;
-        if (rows32 && !d->d_llr_alt[side] && (rc = dev_alloc(d, &d->d_llr_alt[side], need))) return rc;
+        if (rows8 && !d->d_llr8_alt[side] && (rc = dm_alloc(&d->mem, &d->d_llr8_alt[side], need))) return rc;
+        if (rows32 && !d->d_llr_alt[side] && (rc = dm_alloc(&d->mem, &d->d_llr_alt[side], need))) return rc;
         n.llr8 = rows8 ? d->d_llr8_alt[side] : nullptr; n.llr = rows32 ? d->d_llr_alt[side] : nullptr;
     }
     prof_scope ps(d, KS_STATUS, 0.0);
@@ -1244,7 +1244,7 @@ static int gang_entries(qldpc_decoder *d)
         }
     }
     HIPCHK(hipSetDevice(d->device));
-    int rc = dev_alloc(d, &d->d_gang, h.size());
+    int rc = dm_alloc(&d->mem, &d->d_gang, std::max<size_t>(h.size(), 1));
     if (rc) return rc;
     HIPCHK(hipMemcpy(d->d_gang, h.data(), h.size() * sizeof(qk_gang_entry), hipMemcpyHostToDevice));
     return QLDPC_OK;
@@ -1562,7 +1562,7 @@ extern "C" int qldpc_load_syndrome_dev(qldpc_decoder *d, const uint32_t *d_synd_
     if (rc) return rc;
     if (d->engine == QLDPC_ENGINE_EDGES) return edge_load_syndrome(d, d_synd_bits);
     const int Wm = words32(d->M);
-    if (!d->d_synd && (rc = dev_alloc(d, &d->d_synd, (size_t)d->G * d->M * d->V))) return rc;
+    if (!d->d_synd && (rc = dm_alloc(&d->mem, &d->d_synd, (size_t)d->G * d->M * d->V))) return rc;
     const dim3 grid = grid_4k(d, Wm);
     with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_syndrome<v()>), grid, dim3(QK_THREADS), 0, d->stream, d_synd_bits, d->d_synd, d->M, Wm, n_frames); });
     LAUNCHCHK();
@@ -1585,7 +1585,7 @@ extern "C" int qldpc_load_erasures_dev(qldpc_decoder *d, const uint32_t *d_erase
     const int W = words32(d->N);
     const dim3 grid = grid_4k(d, W);
     if (d->llr_coded) {
-        if (!d->d_ebits && (rc = dev_alloc(d, &d->d_ebits, (size_t)d->G * d->N * d->V))) return rc;
+        if (!d->d_ebits && (rc = dm_alloc(&d->mem, &d->d_ebits, (size_t)d->G * d->N * d->V))) return rc;
         with_v(d, [&](auto v) { hipLaunchKernelGGL((qk_load_syndrome<v()>), grid, dim3(QK_THREADS), 0, d->stream, d_erase_bits, d->d_ebits, d->N, W, n_frames); });
         LAUNCHCHK();
         d->has_erase = 1; d->ran = 0;
@@ -1628,7 +1628,7 @@ extern "C" int qldpc_load_known_dev(qldpc_decoder *d, const uint32_t *d_known_bi
     int rc = need_loaded(d, n_frames, "qldpc_load_known_dev");
     if (rc) return rc;
     const int W = words32(d->N);
-    if (!d->d_known && (rc = dev_alloc(d, &d->d_known, (size_t)d->cfg.max_frames * W * 2))) return rc;
+    if (!d->d_known && (rc = dm_alloc(&d->mem, &d->d_known, (size_t)d->cfg.max_frames * W * 2))) return rc;
     HIPCHK(hipMemcpyAsync(d->d_known, d_known_bits, sizeof(uint32_t) * (size_t)n_frames * W, hipMemcpyDeviceToDevice, d->stream));
     HIPCHK(hipMemcpyAsync(d->d_known + (size_t)d->cfg.max_frames * W, d_value_bits, sizeof(uint32_t) * (size_t)n_frames * W, hipMemcpyDeviceToDevice, d->stream));
     if (d->llr_coded) {      /* the FRAMES engine's coded form (the edge engine has none) */
@@ -1652,7 +1652,7 @@ extern "C" int qldpc_decoder_reserve(qldpc_decoder *d)
     if (!d) return QLDPC_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     view_reset(d);
-    return d->d_ybits && !d->d_ebits ? dev_alloc(d, &d->d_ebits, (size_t)d->G0 * d->N * d->V) : (int)QLDPC_OK;
+    return d->d_ybits && !d->d_ebits ? dm_alloc(&d->mem, &d->d_ebits, (size_t)d->G0 * d->N * d->V) : (int)QLDPC_OK;
 }
 
 /* s = H x on the device for packed words (Alice's side of the syndrome form; also a codeword test) */
@@ -1817,8 +1817,8 @@ extern "C" int qldpc_decode_siho(qldpc_decoder *d, const float *Y_N, int *V_K, i
     HIPCHK(hipSetDevice(d->device));
     /* staging buffers for the host-pointer call live with the decoder (sized for max_frames on first use) */
     if (!d->h_in) {
-        if ((rc = dev_alloc(d, &d->h_in, (size_t)d->cfg.max_frames * d->N))) return rc;
-        if ((rc = dev_alloc(d, &d->h_out, (size_t)d->cfg.max_frames * d->K))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->h_in, (size_t)d->cfg.max_frames * d->N))) return rc;
+        if ((rc = dm_alloc(&d->mem, &d->h_out, (size_t)d->cfg.max_frames * d->K))) return rc;
     }
     float *din = d->h_in; int *dout = d->h_out;
     rc = QLDPC_OK;

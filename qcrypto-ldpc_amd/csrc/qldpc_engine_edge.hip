@@ -32,15 +32,15 @@ int edge_create(qldpc_decoder *d, const qldpc_code *code)
     s.eS = code->max_dc <= 8 ? 8 : (code->max_dc <= 16 ? 16 : (code->max_dc <= 32 ? 32 : 64));
     s.e_lds = (size_t)QE_THREADS * (size_t)code->max_dv * sizeof(float);
     s.e_stride = d->cfg.n_ite + 2;
-    if ((rc = dev_alloc(d, &d->d_llr, F * d->N))) return rc;
-    if ((rc = dev_alloc(d, &d->d_a, F * d->E))) return rc;
-    if ((rc = dev_alloc(d, &d->d_b, F * d->E))) return rc;
-    if ((rc = dev_alloc(d, &s.e_c2v1, F * d->E))) return rc;
-    if ((rc = dev_alloc(d, &s.e_sgn, F * s.eW))) return rc;
-    if ((rc = dev_alloc(d, &s.e_hard, F * s.eW))) return rc;
-    if ((rc = dev_alloc(d, &s.e_unsat, F * s.e_stride))) return rc;
-    if ((rc = dev_alloc(d, &s.e_done_at, F))) return rc;
-    HIPCHK(hipHostMalloc((void **)&s.h_done, sizeof(int) * F * 2));
+    if ((rc = dm_alloc(&d->mem, &d->d_llr, F * d->N))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_a, F * d->E))) return rc;
+    if ((rc = dm_alloc(&d->mem, &d->d_b, F * d->E))) return rc;
+    if ((rc = dm_alloc(&d->mem, &s.e_c2v1, F * d->E))) return rc;
+    if ((rc = dm_alloc(&d->mem, &s.e_sgn, F * s.eW))) return rc;
+    if ((rc = dm_alloc(&d->mem, &s.e_hard, F * s.eW))) return rc;
+    if ((rc = dm_alloc(&d->mem, &s.e_unsat, F * s.e_stride))) return rc;
+    if ((rc = dm_alloc(&d->mem, &s.e_done_at, F))) return rc;
+    if (dm_alloc_pinned(&d->mem, &s.h_done, F * 2)) { qldpc_set_error("edge_create: pinned allocation of %zu bytes failed", sizeof(int) * F * 2); return QLDPC_EHIP; }
     HIPCHK(hipEventCreateWithFlags(&s.e_ev[0], hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&s.e_ev[1], hipEventDisableTiming));
     d->poll_every = 2;
@@ -55,14 +55,13 @@ int edge_create(qldpc_decoder *d, const qldpc_code *code)
      * ~8 us, and one XCD has a fifth of the workgroup slots the chunks of a block would fill) */
     s.persist = 0;
     if (const char *e = getenv("QLDPC_EDGE_PERSIST")) s.persist = (atoi(e) && d->cfg.max_frames <= QE_PERSIST_MAX_FRAMES) ? 1 : 0;
-    return dev_alloc(d, &s.e_ctl, QE_CTL_WORDS);      /* claim / rank / barrier / fault words of qe_xcd */
+    return dm_alloc(&d->mem, &s.e_ctl, QE_CTL_WORDS);      /* claim / rank / barrier / fault words of qe_xcd */
 }
 
-/* what is not device memory (that is the ledger's: qldpc_decoder_free) */
+/* what is not memory (that is the ledger's: qldpc_decoder_free) */
 void edge_destroy(qldpc_decoder *d)
 {
     edge_state &s = d->edge;
-    if (s.h_done) (void)hipHostFree(s.h_done);
     for (auto &g : s.e_graphs) if (g) (void)hipGraphExecDestroy(g);
     if (s.cap_stream) (void)hipStreamDestroy(s.cap_stream);
     if (s.e_ev[0]) (void)hipEventDestroy(s.e_ev[0]);
@@ -290,7 +289,7 @@ int edge_load_syndrome(qldpc_decoder *d, const uint32_t *d_synd_bits)
     edge_state &s = d->edge;
     const int Wm = words32(d->M);
     int rc;
-    if (!s.e_synd && (rc = dev_alloc(d, &s.e_synd, (size_t)d->cfg.max_frames * Wm))) return rc;
+    if (!s.e_synd && (rc = dm_alloc(&d->mem, &s.e_synd, (size_t)d->cfg.max_frames * Wm))) return rc;
     HIPCHK(hipMemcpyAsync(s.e_synd, d_synd_bits, sizeof(uint32_t) * (size_t)d->n_frames * Wm, hipMemcpyDeviceToDevice, d->stream));
     d->has_synd = 1; d->ran = 0;
     return QLDPC_OK;

@@ -1,6 +1,6 @@
 /*
- * qldpc_engine_int.h -- internals shared by the translation units of the decoder (not part of the C ABI): the decoder object with its
- * allocation ledger, the per-generation state of the early-exit run, the state and the entry points of the edge-parallel engine
+ * qldpc_engine_int.h -- internals shared by the translation units of the decoder (not part of the C ABI): the decoder object (its memory
+ * is in one ledger, qldpc_devmem.h), the per-generation state of the early-exit run, the state and the entry points of the edge-parallel engine
  * (qldpc_engine_edge.hip), and the kernel-launch dispatchers.  The dispatchers instantiate every
  * (frames per lane, degree cap, rule family, message type) variant of the hot kernels; they are compiled once per frames-per-lane
  * value (qldpc_launch.hip with -DQL_V=1|2|4) so that the build runs in parallel.
@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "qldpc_hip.h"
+#include "qldpc_devmem.h"
 #include "qldpc_kernels.h"
 #include "qldpc_kernels_i8.h"
 #include "qldpc_kernels_gang.h"
@@ -51,9 +52,6 @@ struct gen_state {
     float *post, *msg;                   /* layered schedule: posteriors and messages / check state of this generation (flooding: NULL past generation 0, its arrays are re-used in place) */
 };
 #define QLDPC_MAX_GENS 6
-
-/* one device allocation of a decoder (dev_alloc below).  Hidden: the std::vector instances over it stay out of the library's dynamic symbols */
-struct __attribute__((visibility("hidden"))) dev_block { void *p; size_t bytes; };
 
 /* What the edge-parallel engine (one block at a time, lanes over edges: qldpc_engine_edge.hip) keeps beside the decoder's shared fields.  It reads the
  * graph arrays and d_llr [F][N], d_a = v2c / d_b = c2v [F][E] (the frames engine lays the same three names out as [G][..][FG]) */
@@ -132,8 +130,7 @@ struct qldpc_decoder {
     int llr_alt_cap[2]; float *d_llr_alt[2]; uint32_t *d_llr8_alt[2];   /* side buffers for compacted LLR rows (generations ping-pong between them; capacity in groups) */
     int lay_alt_cap[2]; float *d_post_alt[2], *d_msg_alt[2];            /* layered: side buffers of the posteriors and messages of generations >= 1 (ping-pong by generation parity: the
                                                                          * layer kernels update in place, so a generation cannot be written over the one it is read from) */
-    std::vector<dev_block> ledger;   /* every live device allocation; bytes = their sum (dev_alloc / dev_release) */
-    size_t bytes;
+    dm_ledger mem;                   /* every live allocation of the decoder and of its edge engine (qldpc_devmem.h); a second name of a block (d_hard with 8-bit messages) is not in it */
     int n_frames;                    /* loaded */
     int loaded, ran;
     int last_iters;
@@ -159,27 +156,6 @@ struct qldpc_decoder {
     std::vector<prof_rec> prof_pending;
     qldpc_kernel_stat stats[KS_COUNT];
 };
-
-/*
- * The decoder's device memory: dev_alloc enters every allocation into the ledger, dev_release takes one out again, qldpc_decoder_free releases
- * what the ledger still holds.  A pointer the ledger does not hold is a second name of one it does (d_hard with 8-bit messages): only cleared.
- */
-template <typename T> static int dev_alloc(qldpc_decoder *d, T **p, size_t n)
-{
-    *p = nullptr;
-    if (n == 0) n = 1;
-    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
-    if (e != hipSuccess) { qldpc_set_error("hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e)); return QLDPC_ENOMEM; }
-    d->ledger.push_back(dev_block{(void *)*p, n * sizeof(T)});
-    d->bytes += n * sizeof(T);
-    return QLDPC_OK;
-}
-template <typename T> static void dev_release(qldpc_decoder *d, T **p)
-{
-    for (auto it = d->ledger.begin(); *p && it != d->ledger.end(); ++it)
-        if (it->p == (void *)*p) { (void)hipFree(it->p); d->bytes -= it->bytes; d->ledger.erase(it); break; }
-    *p = nullptr;
-}
 
 static inline int words32(int n) { return (n + 31) / 32; }
 
@@ -257,7 +233,7 @@ static inline double bytes_vn(const qldpc_decoder *d, int mode)
 /*
  * The edge-parallel engine (qldpc_engine_edge.hip): its half of the entry points of the C ABI.  Each entry point of qldpc_engine.hip checks its
  * arguments and the call sequence, then hands a decoder with engine == QLDPC_ENGINE_EDGES over.  edge_create allocates the engine's arrays,
- * edge_destroy releases what is not device memory (events, capture stream, graph execs, the pinned h_done); the loads take the packed rows of
+ * edge_destroy releases what is not memory (events, capture stream, graph execs); the loads take the packed rows of
  * d->n_frames frames; edge_erase and edge_known rewrite rows of d_llr in place.  Hidden: calls between two units of one library, no dynamic symbols.
  */
 #pragma GCC visibility push(hidden)

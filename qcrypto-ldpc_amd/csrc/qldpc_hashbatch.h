@@ -18,6 +18,7 @@
 
 #include "qldpc_hashbatch_core.h"
 #include "qldpc_hip.h"
+#include "qldpc_devmem.h"
 
 struct hb_stage {
     int device;
@@ -27,7 +28,7 @@ struct hb_stage {
     hb_row *rows;                  /* max_blocks: the layout of the call being made */
     hipStream_t stream;            /* of the host form */
     hipEvent_t done;               /* the reuse rule */
-    size_t dev_bytes;              /* of the staging; the context adds what else it allocates */
+    dm_ledger mem;                 /* the staging and what else the context allocates (qldpc_devmem.h) */
 };
 
 static inline void hb_free(hb_stage *st)
@@ -36,10 +37,7 @@ static inline void hb_free(hb_stage *st)
     (void)hipSetDevice(st->device);
     if (st->done) { (void)hipEventSynchronize(st->done); (void)hipEventDestroy(st->done); }
     if (st->stream) (void)hipStreamDestroy(st->stream);
-    if (st->h_in) (void)hipHostFree(st->h_in);
-    if (st->h_out) (void)hipHostFree(st->h_out);
-    if (st->d_in) (void)hipFree(st->d_in);
-    if (st->d_out) (void)hipFree(st->d_out);
+    dm_free_all(&st->mem);
     free(st->rows);
 }
 
@@ -56,11 +54,8 @@ static inline int hb_create(hb_stage *st, int device, const hb_limits *lim, size
     st->in_words = blocks * (head_words + hb_words(lim->max_key_bits) + extra_words);
     st->rows = (hb_row *)malloc(sizeof(hb_row) * blocks);
     if (!st->rows) return QLDPC_ENOMEM;
-    if (hipHostMalloc((void **)&st->h_in, 4 * st->in_words, hipHostMallocDefault) != hipSuccess) return QLDPC_ENOMEM;
-    if (hipHostMalloc((void **)&st->h_out, 4 * out_words, hipHostMallocDefault) != hipSuccess) return QLDPC_ENOMEM;
-    if (hipMalloc((void **)&st->d_in, 4 * st->in_words) != hipSuccess) return QLDPC_ENOMEM;
-    if (hipMalloc((void **)&st->d_out, 4 * out_words) != hipSuccess) return QLDPC_ENOMEM;
-    st->dev_bytes = 4 * (st->in_words + out_words);
+    if ((rc = dm_alloc_pinned(&st->mem, &st->h_in, st->in_words)) || (rc = dm_alloc_pinned(&st->mem, &st->h_out, out_words)) ||
+        (rc = dm_alloc(&st->mem, &st->d_in, st->in_words)) || (rc = dm_alloc(&st->mem, &st->d_out, out_words))) return rc;
     HIPCHK(hipStreamCreateWithFlags(&st->stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&st->done, hipEventDisableTiming));
     HIPCHK(hipEventRecord(st->done, st->stream));

@@ -54,8 +54,7 @@
  *     kept) onto the row of the rescued (or open) frames and sums the trials' iterations.
  *
  * No kernel waits on another wave.  The decoder and the encoder are driven through their public calls only; qldpc_engine_int.h is read for
- * the decoder's sizes, device and stream.  On the host every buffer is recorded where it is allocated (mc_alloc, mc_alloc_pinned) and freed from that
- * record; the three loops share the event array, the generate + load, fetch and expand helpers and the end of a round (mc_round_end).
+ * the decoder's sizes, device and stream.  On the host every buffer is allocated into the loop's ledger (qldpc_devmem.h); the three loops share the event array, the generate + load, fetch and expand helpers and the end of a round (mc_round_end).
  */
 #include <hip/hip_runtime.h>
 
@@ -581,8 +580,7 @@ struct qldpc_mc {
     int N, K, Wn, Wk, n_ite, batch, fail_cap, device;
     unsigned channel_vns;
     uint64_t seed; double parity_ber;
-    std::vector<void *> dev_owned, pinned_owned;   /* everything mc_alloc and mc_alloc_pinned handed out: what qldpc_mc_free frees */
-    size_t dev_bytes;
+    dm_ledger mem;                                 /* everything the loop allocates (qldpc_devmem.h) */
     uint8_t *d_cls;                    /* [32 Wn] padded class map: qldpc_load_bits_dev reads its first N bytes, mc_channel all of it */
     uint32_t *d_info_mask, *d_chan_mask, *d_info, *d_cw, *d_rx, *d_out;
     float *d_mag; int *d_iters, *d_ok;
@@ -604,7 +602,7 @@ struct qldpc_mc {
     mc_soft_table *d_tab;
     float *d_llr;                      /* [batch][N], what qldpc_load_llr_dev takes; shared with the table sweep, allocated by whichever comes first */
     mc_soft_table *d_tabs;             /* [tabs_cap] the tables of the points of a qldpc_mc_sweep_tables call, grown to the largest P so far */
-    int tabs_cap;
+    size_t tabs_cap;
     /* the QBER sweep; the device side is allocated by the first qldpc_mc_sweep (mc_sweep_reserve) */
     bool sweep_ready;
     std::vector<uint32_t> h_fixed;     /* [Wn] the fixed set of qldpc_mc_set_puncture (empty = none): a point's erase row = this OR its prefix */
@@ -656,47 +654,21 @@ extern "C" void qldpc_mc_free(qldpc_mc *mc)
 {
     if (!mc) return;
     (void)hipSetDevice(mc->device);
-    for (void *p : mc->dev_owned) (void)hipFree(p);
-    for (void *p : mc->pinned_owned) (void)hipHostFree(p);
+    dm_free_all(&mc->mem);
     for (hipEvent_t e : mc->ev) if (e) (void)hipEventDestroy(e);
     delete mc;
 }
 
-/* *p = count elements on the device, owned by mc; a buffer that is already there stays (the reserves are lazy and share d_erase) */
-template <typename T> static int mc_alloc(qldpc_mc *mc, T **p, size_t count)
+/* *p = count elements on the device, in the loop's ledger; a buffer that is already there stays (the reserves are lazy and share d_erase) */
+template <typename T> static int mc_lazy(qldpc_mc *mc, T **p, size_t count)
 {
     if (*p) return QLDPC_OK;
-    if (hipMalloc((void **)p, sizeof(T) * count) != hipSuccess) { *p = nullptr; qldpc_set_error("mc_create: device allocation of %zu bytes failed", sizeof(T) * count); return QLDPC_ENOMEM; }
-    mc->dev_owned.push_back(*p);
-    mc->dev_bytes += sizeof(T) * count;
-    return QLDPC_OK;
+    const int rc = dm_alloc(&mc->mem, p, count);
+    if (rc) qldpc_set_error("mc_create: device allocation of %zu bytes failed", sizeof(T) * count);
+    return rc;
 }
-
-/* *p holds *cap elements (0: none yet) and is to hold `count`: where it is too small it is replaced by a new buffer of `count`, whose contents are
- * undefined; the caller has made sure that nothing queued still reads the old one */
-template <typename T> static int mc_grow(qldpc_mc *mc, T **p, int *cap, size_t count)
-{
-    if (*p && (size_t)*cap >= count) return QLDPC_OK;
-    T *fresh = nullptr;
-    const int rc = mc_alloc(mc, &fresh, count);
-    if (rc) return rc;
-    if (*p) {
-        mc->dev_owned.erase(std::find(mc->dev_owned.begin(), mc->dev_owned.end(), (void *)*p));
-        mc->dev_bytes -= sizeof(T) * (size_t)*cap;
-        (void)hipFree(*p);
-    }
-    *p = fresh; *cap = (int)count;
-    return QLDPC_OK;
-}
-
 /* the pinned counterpart */
-template <typename T> static int mc_alloc_pinned(qldpc_mc *mc, T **p, size_t count)
-{
-    if (*p) return QLDPC_OK;
-    if (hipHostMalloc((void **)p, sizeof(T) * count, hipHostMallocDefault) != hipSuccess) { *p = nullptr; return QLDPC_ENOMEM; }
-    mc->pinned_owned.push_back(*p);
-    return QLDPC_OK;
-}
+template <typename T> static int mc_lazy_pinned(qldpc_mc *mc, T **p, size_t count) { return *p ? (int)QLDPC_OK : dm_alloc_pinned(&mc->mem, p, count); }
 
 /* the candidates a NULL list stands for: every QLDPC_VN_PINNED VN, ascending (the harness's `for a = K .. N-1`) */
 static void mc_default_candidates(qldpc_mc *mc)
@@ -723,10 +695,10 @@ static int mc_build(qldpc_mc *mc, const uint8_t *vn_class)
     mc->h_cls.assign(cls.begin(), cls.begin() + mc->N);
     mc_default_candidates(mc);
     HIPCHK(hipSetDevice(mc->device));
-    if ((rc = mc_alloc(mc, &mc->d_cls, 32 * Wn)) || (rc = mc_alloc(mc, &mc->d_info_mask, Wn)) || (rc = mc_alloc(mc, &mc->d_chan_mask, Wn)) ||
-        (rc = mc_alloc(mc, &mc->d_info, B * (size_t)mc->Wk)) || (rc = mc_alloc(mc, &mc->d_cw, B * Wn)) || (rc = mc_alloc(mc, &mc->d_rx, B * Wn)) ||
-        (rc = mc_alloc(mc, &mc->d_out, B * Wn)) || (rc = mc_alloc(mc, &mc->d_mag, B)) || (rc = mc_alloc(mc, &mc->d_iters, B)) || (rc = mc_alloc(mc, &mc->d_ok, B)) ||
-        (rc = mc_alloc(mc, &mc->d_ctr, (size_t)MC_COUNTERS + (size_t)mc->n_ite + 1 + (size_t)mc->fail_cap)) || (rc = mc_alloc_pinned(mc, &mc->h_ctr, MC_COUNTERS)))
+    if ((rc = mc_lazy(mc, &mc->d_cls, 32 * Wn)) || (rc = mc_lazy(mc, &mc->d_info_mask, Wn)) || (rc = mc_lazy(mc, &mc->d_chan_mask, Wn)) ||
+        (rc = mc_lazy(mc, &mc->d_info, B * (size_t)mc->Wk)) || (rc = mc_lazy(mc, &mc->d_cw, B * Wn)) || (rc = mc_lazy(mc, &mc->d_rx, B * Wn)) ||
+        (rc = mc_lazy(mc, &mc->d_out, B * Wn)) || (rc = mc_lazy(mc, &mc->d_mag, B)) || (rc = mc_lazy(mc, &mc->d_iters, B)) || (rc = mc_lazy(mc, &mc->d_ok, B)) ||
+        (rc = mc_lazy(mc, &mc->d_ctr, (size_t)MC_COUNTERS + (size_t)mc->n_ite + 1 + (size_t)mc->fail_cap)) || (rc = mc_lazy_pinned(mc, &mc->h_ctr, MC_COUNTERS)))
         return rc;
     HIPCHK(hipMemcpy(mc->d_cls, cls.data(), 32 * Wn, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(mc->d_info_mask, info_mask.data(), 4 * Wn, hipMemcpyHostToDevice));
@@ -761,7 +733,7 @@ extern "C" int qldpc_mc_create(qldpc_decoder *dec, qldpc_encoder *enc, const uin
     return QLDPC_OK;
 }
 
-extern "C" size_t qldpc_mc_device_bytes(const qldpc_mc *mc) { return mc ? mc->dev_bytes : 0; }
+extern "C" size_t qldpc_mc_device_bytes(const qldpc_mc *mc) { return mc ? mc->mem.dev_bytes : 0; }
 
 static unsigned mc_blocks(size_t lanes) { return (unsigned)((lanes + MC_LANES - 1) / MC_LANES); }
 
@@ -856,7 +828,7 @@ extern "C" int qldpc_mc_set_channel(qldpc_mc *mc, const qldpc_mc_channel *table)
     if (rc) { qldpc_set_error("mc_set_channel: a missing array, a row that decreases or an entry above 2^32"); return QLDPC_EINVAL; }
     if ((rc = mc_soft_lanes_check(mc, "mc_set_channel", mc->batch))) return rc;
     HIPCHK(hipSetDevice(mc->device));
-    if ((rc = mc_alloc(mc, &mc->d_tab, 1)) || (rc = mc_alloc(mc, &mc->d_llr, (size_t)mc->batch * (size_t)mc->N))) return rc;
+    if ((rc = mc_lazy(mc, &mc->d_tab, 1)) || (rc = mc_lazy(mc, &mc->d_llr, (size_t)mc->batch * (size_t)mc->N))) return rc;
     HIPCHK(hipStreamSynchronize(mc->dec->stream));      /* a queued channel kernel may still read the old table */
     HIPCHK(hipMemcpy(mc->d_tab, &tab, sizeof(tab), hipMemcpyHostToDevice));
     mc->soft = true;
@@ -1016,9 +988,9 @@ static int mc_search_reserve(qldpc_mc *mc)
     if (!mc->search_ready) {
         const size_t Wn = (size_t)mc->Wn, B = (size_t)mc->batch;
         int rc = QLDPC_OK;
-        if ((rc = mc_alloc(mc, &mc->d_cand, (size_t)mc->N)) || (rc = mc_alloc(mc, &mc->d_pat, B * Wn)) || (rc = mc_alloc(mc, &mc->d_erase, B * Wn)) ||
-            (rc = mc_alloc(mc, &mc->d_fixed, Wn)) || (rc = mc_alloc(mc, &mc->d_rows, B * MC_PATTERN_COUNTERS)) ||
-            (rc = mc_alloc_pinned(mc, &mc->h_rows, B * MC_PATTERN_COUNTERS)) || (rc = qldpc_decoder_reserve(mc->dec)))      /* the decoder's erasure ballots */
+        if ((rc = mc_lazy(mc, &mc->d_cand, (size_t)mc->N)) || (rc = mc_lazy(mc, &mc->d_pat, B * Wn)) || (rc = mc_lazy(mc, &mc->d_erase, B * Wn)) ||
+            (rc = mc_lazy(mc, &mc->d_fixed, Wn)) || (rc = mc_lazy(mc, &mc->d_rows, B * MC_PATTERN_COUNTERS)) ||
+            (rc = mc_lazy_pinned(mc, &mc->h_rows, B * MC_PATTERN_COUNTERS)) || (rc = qldpc_decoder_reserve(mc->dec)))      /* the decoder's erasure ballots */
             return rc;
         mc->search_ready = true;
     }
@@ -1169,9 +1141,9 @@ static int mc_sweep_reserve(qldpc_mc *mc)
     if (mc->sweep_ready) return QLDPC_OK;
     const size_t Wn = (size_t)mc->Wn, B = (size_t)mc->batch, P = QLDPC_MC_SWEEP_MAX_POINTS, bins = (size_t)mc->n_ite + 1;
     int rc = QLDPC_OK;
-    if ((rc = mc_alloc(mc, &mc->d_slots, 3 * B)) || (rc = mc_alloc(mc, &mc->d_points, P)) || (rc = mc_alloc(mc, &mc->d_prows, P * Wn)) ||
-        (rc = mc_alloc(mc, &mc->d_erase, B * Wn)) || (rc = mc_alloc(mc, &mc->d_wctr, P * MC_POINT_COUNTERS)) || (rc = mc_alloc(mc, &mc->d_whist, P * bins)) ||
-        (rc = mc_alloc_pinned(mc, &mc->h_slots, 3 * B)) || (rc = mc_alloc_pinned(mc, &mc->h_wctr, P * MC_POINT_COUNTERS)) ||
+    if ((rc = mc_lazy(mc, &mc->d_slots, 3 * B)) || (rc = mc_lazy(mc, &mc->d_points, P)) || (rc = mc_lazy(mc, &mc->d_prows, P * Wn)) ||
+        (rc = mc_lazy(mc, &mc->d_erase, B * Wn)) || (rc = mc_lazy(mc, &mc->d_wctr, P * MC_POINT_COUNTERS)) || (rc = mc_lazy(mc, &mc->d_whist, P * bins)) ||
+        (rc = mc_lazy_pinned(mc, &mc->h_slots, 3 * B)) || (rc = mc_lazy_pinned(mc, &mc->h_wctr, P * MC_POINT_COUNTERS)) ||
         (rc = qldpc_decoder_reserve(mc->dec)))      /* the decoder's erasure ballots */
         return rc;
     mc->sweep_ready = true;
@@ -1349,8 +1321,8 @@ extern "C" int qldpc_mc_sweep_tables(qldpc_mc *mc, const qldpc_mc_sweep_tables_c
         const qldpc_mc_channel &t = cfg->points[q].table;
         if (mc_soft_table_build(t.levels, t.cum[0], t.cum[1], t.value, &tabs[(size_t)q])) return QLDPC_EINVAL;      /* not reached: the check has built it */
     }
-    HIPCHK(hipStreamSynchronize(mc->dec->stream));      /* a queued channel kernel may still read the tables that mc_grow replaces */
-    if ((rc = mc_alloc(mc, &mc->d_llr, (size_t)mc->batch * (size_t)mc->N)) || (rc = mc_grow(mc, &mc->d_tabs, &mc->tabs_cap, (size_t)P))) return rc;
+    HIPCHK(hipStreamSynchronize(mc->dec->stream));      /* a queued channel kernel may still read the tables that dm_grow replaces */
+    if ((rc = mc_lazy(mc, &mc->d_llr, (size_t)mc->batch * (size_t)mc->N)) || (rc = dm_grow(&mc->mem, &mc->d_tabs, &mc->tabs_cap, (size_t)P))) return rc;
     std::vector<uint32_t> erows;
     const bool any_erase = mc_point_erows(mc, cfg->points, P, cfg->punct_order, &erows);
     mc->wstats.assign((size_t)P, qldpc_mc_point_stat());
@@ -1450,17 +1422,6 @@ extern "C" int qldpc_mc_strata_hist(qldpc_mc *mc, int stratum, uint64_t *hist, i
 
 /* ------------------------------------------------------------------ blind reconciliation rounds ---- */
 
-/* the counterpart of mc_alloc for a buffer that has to grow: frees *p (count elements) and takes it off the record */
-template <typename T> static void mc_release(qldpc_mc *mc, T **p, size_t count)
-{
-    if (!*p) return;
-    const auto it = std::find(mc->dev_owned.begin(), mc->dev_owned.end(), (void *)*p);
-    if (it != mc->dev_owned.end()) mc->dev_owned.erase(it);
-    (void)hipFree(*p);
-    mc->dev_bytes -= sizeof(T) * count;
-    *p = nullptr;
-}
-
 /* everything the rounds need on the device: the launch buffers and the open list once, the pools for `levels` levels unless they hold as many already */
 static int mc_blind_reserve(qldpc_mc *mc, int levels)
 {
@@ -1468,19 +1429,19 @@ static int mc_blind_reserve(qldpc_mc *mc, int levels)
     const size_t Wn = (size_t)mc->Wn, B = (size_t)mc->batch, cap = MC_BLIND_POOL_CAP(mc->batch);
     int rc = QLDPC_OK;
     if (!mc->blind_ready) {
-        if ((rc = mc_alloc(mc, &mc->d_bcand, B * Wn)) || (rc = mc_alloc(mc, &mc->d_bweak, B * Wn)) || (rc = mc_alloc(mc, &mc->d_btake, B)) ||
-            (rc = mc_alloc(mc, &mc->d_bopen, B)) || (rc = mc_alloc(mc, &mc->d_oframe, (size_t)mc->fail_cap)) ||
-            (rc = mc_alloc(mc, &mc->d_oknown, (size_t)mc->fail_cap * Wn)) || (rc = mc_alloc(mc, &mc->d_bctr, MC_BLIND_WORDS)) ||
-            (rc = mc_alloc_pinned(mc, &mc->h_bctr, MC_BLIND_WORDS)))
+        if ((rc = mc_lazy(mc, &mc->d_bcand, B * Wn)) || (rc = mc_lazy(mc, &mc->d_bweak, B * Wn)) || (rc = mc_lazy(mc, &mc->d_btake, B)) ||
+            (rc = mc_lazy(mc, &mc->d_bopen, B)) || (rc = mc_lazy(mc, &mc->d_oframe, (size_t)mc->fail_cap)) ||
+            (rc = mc_lazy(mc, &mc->d_oknown, (size_t)mc->fail_cap * Wn)) || (rc = mc_lazy(mc, &mc->d_bctr, MC_BLIND_WORDS)) ||
+            (rc = mc_lazy_pinned(mc, &mc->h_bctr, MC_BLIND_WORDS)))
             return rc;
         mc->blind_ready = true;
     }
     if (levels <= mc->blind_levels) return QLDPC_OK;
     HIPCHK(hipStreamSynchronize(mc->dec->stream));      /* nothing queued reads the pools that go */
-    mc_release(mc, &mc->d_pframe, (size_t)mc->blind_levels * cap);
-    mc_release(mc, &mc->d_pknown, (size_t)mc->blind_levels * cap * Wn);
+    dm_release(&mc->mem, &mc->d_pframe);
+    dm_release(&mc->mem, &mc->d_pknown);
     mc->blind_levels = 0;
-    if ((rc = mc_alloc(mc, &mc->d_pframe, (size_t)levels * cap)) || (rc = mc_alloc(mc, &mc->d_pknown, (size_t)levels * cap * Wn))) return rc;
+    if ((rc = mc_lazy(mc, &mc->d_pframe, (size_t)levels * cap)) || (rc = mc_lazy(mc, &mc->d_pknown, (size_t)levels * cap * Wn))) return rc;
     mc->blind_levels = levels;
     return QLDPC_OK;
 }
@@ -1631,14 +1592,14 @@ static int mc_guess_reserve(qldpc_mc *mc)
     if (mc->guess_ready) return QLDPC_OK;
     const size_t Wn = (size_t)mc->Wn, B = (size_t)mc->batch, cap = MC_GUESS_POOL_CAP(mc->batch), S = B / 2 + 1;
     int rc = QLDPC_OK;
-    if ((rc = mc_alloc(mc, &mc->d_bcand, B * Wn)) || (rc = mc_alloc(mc, &mc->d_bweak, B * Wn)) || (rc = mc_alloc(mc, &mc->d_btake, B)) ||
-        (rc = mc_alloc(mc, &mc->d_bopen, B)) || (rc = mc_alloc(mc, &mc->d_gframe, cap)) || (rc = mc_alloc(mc, &mc->d_gweak, cap * Wn)) ||
-        (rc = mc_alloc(mc, &mc->d_ghard, cap * Wn)) || (rc = mc_alloc(mc, &mc->d_gverd, cap * MC_GUESS_VERDICT)) ||
-        (rc = mc_alloc(mc, &mc->d_gkeep, B * MC_GUESS_VERDICT)) || (rc = mc_alloc(mc, &mc->d_gslot, B)) || (rc = mc_alloc(mc, &mc->d_gknown, B * Wn)) ||
-        (rc = mc_alloc(mc, &mc->d_gvalue, B * Wn)) || (rc = mc_alloc(mc, &mc->d_gwin, S)) || (rc = mc_alloc(mc, &mc->d_gnok, S)) ||
-        (rc = mc_alloc(mc, &mc->d_gamb, S)) || (rc = mc_alloc(mc, &mc->d_gout, S * Wn)) || (rc = mc_alloc(mc, &mc->d_goframe, (size_t)mc->fail_cap)) ||
-        (rc = mc_alloc(mc, &mc->d_goweak, (size_t)mc->fail_cap * Wn)) || (rc = mc_alloc(mc, &mc->d_gctr, (size_t)MC_GUESS_WORDS)) ||
-        (rc = mc_alloc_pinned(mc, &mc->h_gctr, (size_t)MC_GUESS_WORDS)))
+    if ((rc = mc_lazy(mc, &mc->d_bcand, B * Wn)) || (rc = mc_lazy(mc, &mc->d_bweak, B * Wn)) || (rc = mc_lazy(mc, &mc->d_btake, B)) ||
+        (rc = mc_lazy(mc, &mc->d_bopen, B)) || (rc = mc_lazy(mc, &mc->d_gframe, cap)) || (rc = mc_lazy(mc, &mc->d_gweak, cap * Wn)) ||
+        (rc = mc_lazy(mc, &mc->d_ghard, cap * Wn)) || (rc = mc_lazy(mc, &mc->d_gverd, cap * MC_GUESS_VERDICT)) ||
+        (rc = mc_lazy(mc, &mc->d_gkeep, B * MC_GUESS_VERDICT)) || (rc = mc_lazy(mc, &mc->d_gslot, B)) || (rc = mc_lazy(mc, &mc->d_gknown, B * Wn)) ||
+        (rc = mc_lazy(mc, &mc->d_gvalue, B * Wn)) || (rc = mc_lazy(mc, &mc->d_gwin, S)) || (rc = mc_lazy(mc, &mc->d_gnok, S)) ||
+        (rc = mc_lazy(mc, &mc->d_gamb, S)) || (rc = mc_lazy(mc, &mc->d_gout, S * Wn)) || (rc = mc_lazy(mc, &mc->d_goframe, (size_t)mc->fail_cap)) ||
+        (rc = mc_lazy(mc, &mc->d_goweak, (size_t)mc->fail_cap * Wn)) || (rc = mc_lazy(mc, &mc->d_gctr, (size_t)MC_GUESS_WORDS)) ||
+        (rc = mc_lazy_pinned(mc, &mc->h_gctr, (size_t)MC_GUESS_WORDS)))
         return rc;
     mc->guess_ready = true;
     return QLDPC_OK;

@@ -1,6 +1,6 @@
 /*
  * qldpc_polar_ctx.h -- what the device contexts of the polar subsystem (qldpc_polar and qldpc_polar_list embed one pl_ctx) have in common, HIP
- * host code: the code and where it lives on the device, the ledger of what a context allocated, the checks of a call, the encode launch and the
+ * host code: the code and where it lives on the device, the ledger of what a context allocated (qldpc_devmem.h), the checks of a call, the encode launch and the
  * choice of the message type.  A context owns everything a call touches; a call allocates nothing and waits for nothing.
  */
 #ifndef QLDPC_POLAR_CTX_H
@@ -11,10 +11,9 @@
 #include <cstdlib>
 
 #include "qldpc_hip.h"
+#include "qldpc_devmem.h"
 #include "qldpc_kernels_polar.h"
 #include "qldpc_polar_int.h"
-
-#define PL_CTX_ALLOCS 8
 
 struct pl_ctx {
     int n, n_info, messages, maxq, max_frames, device;
@@ -22,9 +21,7 @@ struct pl_ctx {
     hipStream_t stream;
     uint32_t *d_fmask;             /* W words: 1 = frozen */
     int *d_info_pos;
-    size_t dev_bytes;
-    void *owned[PL_CTX_ALLOCS];    /* the ledger: every device allocation of the context, its owner's included */
-    int n_owned;
+    dm_ledger mem;                 /* every device allocation of the context, its owner's included */
     bool alloc_failed;             /* an allocation failed; the ones after it are not tried, and the owner reports it once */
 };
 #define PL_CTX(p) ((p) ? &(p)->c : nullptr)
@@ -35,23 +32,21 @@ const pl_ctx *pl_ctx_of_sc(const qldpc_polar *p);
 bool pl_sc_is_wide(const qldpc_polar *p);
 const pl_ctx *pl_ctx_of_list(const qldpc_polar_list *p, int *crc_len, uint32_t *crc_poly);
 
-/* the only hipMalloc of a context: `bytes` at *q (left NULL for 0 bytes), entered in the ledger and counted in dev_bytes */
+/* the only allocation of a context: `bytes` at *q (left NULL for 0 bytes), in the ledger; alloc_failed around dm_alloc */
 template <class T> static inline void pl_ctx_alloc(pl_ctx *c, T **q, size_t bytes)
 {
-    if (!bytes || c->alloc_failed) return;
-    void *d = nullptr;
-    if (c->n_owned == PL_CTX_ALLOCS || hipMalloc(&d, bytes) != hipSuccess) { (void)hipGetLastError(); c->alloc_failed = true; return; }
-    c->owned[c->n_owned++] = d;
-    c->dev_bytes += bytes;
-    *q = (T *)d;
+    unsigned char *d = nullptr;
+    if (c->alloc_failed) return;
+    if (dm_alloc(&c->mem, &d, bytes)) c->alloc_failed = true;
+    else if (d) *q = (T *)d;
 }
 
 static inline void pl_ctx_free(pl_ctx *c)
 {
-    if (!c->n_owned) return;                                     /* pl_ctx_create refused before it allocated anything */
+    if (c->mem.blocks.empty()) return;                           /* pl_ctx_create refused before it allocated anything */
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);                       /* the last call may still read the scratch */
-    for (int i = 0; i < c->n_owned; i++) (void)hipFree(c->owned[i]);
+    dm_free_all(&c->mem);
 }
 
 /* the device checked, then the frozen mask and info_pos of the code (n, n_info, W set) allocated and sent up */
@@ -95,7 +90,7 @@ static inline int pl_ctx_create(pl_ctx *c, const char *who, int log2_n, int max_
     return rc;
 }
 
-static inline size_t pl_ctx_device_bytes(const pl_ctx *c) { return c ? c->dev_bytes : 0; }
+static inline size_t pl_ctx_device_bytes(const pl_ctx *c) { return c ? c->mem.dev_bytes : 0; }
 
 static inline int pl_ctx_set_stream(pl_ctx *c, void *hip_stream)
 {

@@ -27,7 +27,6 @@
 #include "qldpc_polar_ctx.h"
 
 #define PMC_STAGES 5               /* source, encode, channel, decode, monitor */
-#define PMC_ALLOCS 13
 #define PMC_EVENTS (PMC_STAGES + 1)       /* of a batch; there are two sets: run uses the first, construct takes them in turn */
 
 struct qldpc_polar_mc {
@@ -50,37 +49,27 @@ struct qldpc_polar_mc {
     uint64_t *d_tally;             /* [2][N], the accumulator of construct; NULL unless the context is an SC context of the lanes' form */
     hipEvent_t ev[2 * PMC_EVENTS];
     int n_ev;
-    void *owned[PMC_ALLOCS];
-    int n_owned;
-    size_t dev_bytes;
+    dm_ledger mem;                 /* everything create allocates, the pinned h_ctr included (qldpc_devmem.h) */
 };
 
 extern "C" void qldpc_polar_mc_free(qldpc_polar_mc *mc)
 {
     if (!mc) return;
-    if (mc->n_owned || mc->n_ev || mc->h_ctr) {
+    if (!mc->mem.blocks.empty() || mc->n_ev) {
         (void)hipSetDevice(mc->c->device);
         (void)hipStreamSynchronize(mc->c->stream);
     }
-    for (int i = 0; i < mc->n_owned; i++) (void)hipFree(mc->owned[i]);
     for (int i = 0; i < mc->n_ev; i++) (void)hipEventDestroy(mc->ev[i]);
-    if (mc->h_ctr) (void)hipHostFree(mc->h_ctr);
+    dm_free_all(&mc->mem);
     delete mc;
 }
 
 template <class T> static int pmc_alloc(qldpc_polar_mc *mc, T **q, size_t count)
 {
-    void *d = nullptr;
-    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
-    if (mc->n_owned == PMC_ALLOCS || hipMalloc(&d, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        qldpc_set_error("polar_mc_create: device allocation of %zu bytes failed: lower batch", bytes);
-        return QLDPC_ENOMEM;
-    }
-    mc->owned[mc->n_owned++] = d;
-    mc->dev_bytes += bytes;
-    *q = (T *)d;
-    return QLDPC_OK;
+    count = std::max<size_t>(count, 1);      /* an empty array still gets one element */
+    const int rc = dm_alloc(&mc->mem, q, count);
+    if (rc) qldpc_set_error("polar_mc_create: device allocation of %zu bytes failed: lower batch", sizeof(T) * count);
+    return rc;
 }
 
 static int pmc_build(qldpc_polar_mc *mc)
@@ -96,7 +85,7 @@ static int pmc_build(qldpc_polar_mc *mc)
         (rc = pmc_alloc(mc, &mc->d_ctr, (size_t)PMC_C_ROW + (size_t)mc->fail_cap)))
         return rc;
     if (mc->sc && !pl_sc_is_wide(mc->sc) && (rc = pmc_alloc(mc, &mc->d_tally, 2 * N))) return rc;
-    HIPCHK(hipHostMalloc((void **)&mc->h_ctr, sizeof(pmc_u64) * PMC_C_ROW, hipHostMallocDefault));
+    if (dm_alloc_pinned(&mc->mem, &mc->h_ctr, PMC_C_ROW)) { qldpc_set_error("polar_mc_create: pinned allocation of the counters failed"); return QLDPC_EHIP; }
     memset(mc->h_ctr, 0, sizeof(pmc_u64) * PMC_C_ROW);
     for (; mc->n_ev < 2 * PMC_EVENTS; mc->n_ev++) HIPCHK(hipEventCreate(&mc->ev[mc->n_ev]));
     /* rank[] from the context's own info_pos */
@@ -137,7 +126,7 @@ extern "C" int qldpc_polar_mc_create(qldpc_polar *sc, qldpc_polar_list *list, ui
     return QLDPC_OK;
 }
 
-extern "C" size_t qldpc_polar_mc_device_bytes(const qldpc_polar_mc *mc) { return mc ? mc->dev_bytes : 0; }
+extern "C" size_t qldpc_polar_mc_device_bytes(const qldpc_polar_mc *mc) { return mc ? mc->mem.dev_bytes : 0; }
 
 extern "C" int qldpc_polar_mc_set_source(qldpc_polar_mc *mc, int mode)
 {

@@ -178,7 +178,6 @@ extern "C" void qldpc_polyhash_free(qldpc_polyhash_ctx *ph)
 {
     if (!ph) return;
     hb_free(&ph->st);                                            /* waits for the last call first */
-    if (ph->d_parts) (void)hipFree(ph->d_parts);
     free(ph->tag_bits);
     delete ph;
 }
@@ -207,18 +206,15 @@ extern "C" int qldpc_polyhash_create_cfg(const qldpc_polyhash_cfg *cfg, qldpc_po
         ph->max_tiles = ph_tiles(ph_coefs(lim.max_key_bits), tile);
         const size_t parts = (size_t)lim.max_blocks * ph->max_tiles * (size_t)cfg->n_keys;
         ph->tag_bits = (int *)malloc(sizeof(int) * (size_t)lim.max_blocks);
-        if (!ph->tag_bits || hipMalloc((void **)&ph->d_parts, 8 * parts) != hipSuccess) rc = QLDPC_ENOMEM;
-        else {
-            for (int i = 0; i < lim.max_blocks; i++) ph->tag_bits[i] = lim.max_out_bits;
-            ph->st.dev_bytes += 8 * parts;
-        }
+        if (!ph->tag_bits || dm_alloc(&ph->st.mem, &ph->d_parts, parts)) rc = QLDPC_ENOMEM;
+        else for (int i = 0; i < lim.max_blocks; i++) ph->tag_bits[i] = lim.max_out_bits;
     }
     if (rc) { qldpc_polyhash_free(ph); return rc; }
     *out = ph;
     return QLDPC_OK;
 }
 
-extern "C" size_t qldpc_polyhash_device_bytes(const qldpc_polyhash_ctx *ph) { return ph ? ph->st.dev_bytes : 0; }
+extern "C" size_t qldpc_polyhash_device_bytes(const qldpc_polyhash_ctx *ph) { return ph ? ph->st.mem.dev_bytes : 0; }
 
 /* the layout of the call as descriptor rows into the pinned staging -> the tiles of its longest block.  strides NULL: the host form
    (one_key: every block reads the hash key at 0) */

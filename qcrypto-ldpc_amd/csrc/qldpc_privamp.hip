@@ -20,6 +20,7 @@
 #include "../../include/qldpc.h"
 #include "qldpc_graph.h"
 #include "qldpc_hip.h"
+#include "qldpc_devmem.h"
 
 #define PA_FEEDBACK 0xe0000200u
 #define PA_JUMPS 17                /* output bit index < 2^17 */
@@ -138,13 +139,13 @@ extern "C" int qldpc_privamp(int device, const uint32_t *key_words, int workbits
     std::vector<uint32_t> key(key_words, key_words + numwords);
     if (workbits & 31) key[(size_t)numwords - 1] &= 0xFFFFFFFFu << (32 - (workbits & 31));
     uint32_t *d_key = nullptr, *d_out = nullptr;
-    HIPCHK(hipMalloc((void **)&d_key, sizeof(uint32_t) * (size_t)numwords));
-    if (hipMalloc((void **)&d_out, sizeof(uint32_t) * (size_t)outwords) != hipSuccess) { (void)hipFree(d_key); return QLDPC_ENOMEM; }
+    dm_scope tmp;      /* freed on every return */
+    if (dm_alloc(&tmp.m, &d_key, (size_t)numwords)) { qldpc_set_error("privamp: device allocation of %zu bytes failed", sizeof(uint32_t) * (size_t)numwords); return QLDPC_EHIP; }
+    if (dm_alloc(&tmp.m, &d_out, (size_t)outwords)) return QLDPC_ENOMEM;
     int rc = QLDPC_OK;
     if (hipMemcpy(d_key, key.data(), sizeof(uint32_t) * (size_t)numwords, hipMemcpyHostToDevice) != hipSuccess) rc = QLDPC_EHIP;
     if (!rc) rc = qldpc_privamp_dev(d_key, workbits, seed, final_bits, d_out, nullptr);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = QLDPC_EHIP;
     if (!rc && hipMemcpy(final_words, d_out, sizeof(uint32_t) * (size_t)outwords, hipMemcpyDeviceToHost) != hipSuccess) rc = QLDPC_EHIP;
-    (void)hipFree(d_key); (void)hipFree(d_out);
     return rc;
 }

@@ -262,22 +262,18 @@ extern "C" void qldpc_privamp_free(qldpc_privamp_ctx *pa)
 {
     if (!pa) return;
     hb_free(&pa->st);
-    if (pa->d_at) (void)hipFree(pa->d_at);
-    if (pa->d_rtabs) (void)hipFree(pa->d_rtabs);
     free(pa->sort_buf);
     delete pa;
 }
 
 static int pab_create(qldpc_privamp_ctx *pa, int device, const hb_limits *lim)
 {
-    const int rc = hb_create(&pa->st, device, lim, pab_head_words(1), 0, "privamp_create", &pab_names);
+    int rc = hb_create(&pa->st, device, lim, pab_head_words(1), 0, "privamp_create", &pab_names);
     if (rc) return rc;
     const size_t rtab_words = (size_t)lim->max_blocks * PAB_R_LEVELS * 32, at_words = (size_t)PAB_AT_LEVELS * 32;
     pa->sort_buf = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)lim->max_blocks);
     if (!pa->sort_buf) return QLDPC_ENOMEM;
-    if (hipMalloc((void **)&pa->d_at, 4 * at_words) != hipSuccess) return QLDPC_ENOMEM;
-    if (hipMalloc((void **)&pa->d_rtabs, 4 * rtab_words) != hipSuccess) return QLDPC_ENOMEM;
-    pa->st.dev_bytes += 4 * (at_words + rtab_words);
+    if ((rc = dm_alloc(&pa->st.mem, &pa->d_at, at_words)) || (rc = dm_alloc(&pa->st.mem, &pa->d_rtabs, rtab_words))) return rc;
     uint32_t at_pow[PAB_AT_LEVELS * 32];
     pab_host_at_pow(at_pow);
     HIPCHK(hipMemcpy(pa->d_at, at_pow, sizeof(at_pow), hipMemcpyHostToDevice));
@@ -297,7 +293,7 @@ extern "C" int qldpc_privamp_create(int device, int max_blocks, int max_key_bits
     return QLDPC_OK;
 }
 
-extern "C" size_t qldpc_privamp_device_bytes(const qldpc_privamp_ctx *pa) { return pa ? pa->st.dev_bytes : 0; }
+extern "C" size_t qldpc_privamp_device_bytes(const qldpc_privamp_ctx *pa) { return pa ? pa->st.mem.dev_bytes : 0; }
 
 static int pab_cmp_u32(const void *a, const void *b)
 {

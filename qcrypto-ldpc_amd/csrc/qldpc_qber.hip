@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "qldpc_hip.h"
+#include "qldpc_devmem.h"
 #include "qldpc_kernels_qber.h"
 
 #define QBER_LDS_MAX (144u * 1024u)      /* of the 160 KB of a CU: the rows of one frame plus the histogram, one workgroup resident */
@@ -26,7 +27,8 @@ struct qldpc_qber {
     size_t mlds_bytes;
     uint8_t *d_rep;        /* [D][M] repeat table (qb_earlier_in_run); its presence = the merged tables and buffers are in place */
     int cus;
-    size_t lds_bytes, dev_bytes;
+    size_t lds_bytes;
+    dm_ledger mem;         /* every device array of the estimator (qldpc_devmem.h) */
     hipStream_t stream;
     int *d_tab;            /* [D][M] transposed check table, -1 past a check's degree */
     int32_t *d_L1, *d_L0;  /* [D + 1][n_grid]; after the first qldpc_qber_set_merge(1) [QB_MAX_DEGREE + 1][n_grid], the same rows and more */
@@ -54,8 +56,7 @@ extern "C" void qldpc_qber_free(qldpc_qber *est)
 {
     if (!est) return;
     (void)hipSetDevice(est->cfg.device);
-    (void)hipFree(est->d_tab); (void)hipFree(est->d_L1); (void)hipFree(est->d_L0); (void)hipFree(est->d_q); (void)hipFree(est->d_llr);
-    (void)hipFree(est->d_cls_rows); (void)hipFree(est->d_counts); (void)hipFree(est->d_pool); (void)hipFree(est->d_rep);
+    dm_free_all(&est->mem);
     delete est;
 }
 
@@ -101,17 +102,14 @@ extern "C" int qldpc_qber_create(const qldpc_code *code, const qldpc_qber_cfg *c
     for (int c = 0; c < M; c++)
         for (int k = code->cn_ptr[c]; k < code->cn_ptr[c + 1]; k++) tab[(size_t)(k - code->cn_ptr[c]) * M + c] = code->cn_var[k];
     const size_t tbytes = sizeof(int32_t) * L1.size(), gbytes = sizeof(float) * q.size();
-    const size_t cbytes = sizeof(uint32_t) * (size_t)cfg->max_frames * (size_t)e->bins;
-    auto alloc = [&](void **p, size_t bytes) { if (!rc && hipMalloc(p, bytes) != hipSuccess) rc = QLDPC_ENOMEM; else if (!rc) e->dev_bytes += bytes; };
-    alloc((void **)&e->d_tab, sizeof(int) * tab.size());
-    alloc((void **)&e->d_L1, tbytes);
-    alloc((void **)&e->d_L0, tbytes);
-    alloc((void **)&e->d_q, gbytes);
-    alloc((void **)&e->d_llr, gbytes);
-    alloc((void **)&e->d_cls_rows, sizeof(uint32_t) * 2 * (size_t)e->Wn);
-    alloc((void **)&e->d_counts, cbytes);
-    alloc((void **)&e->d_pool, sizeof(unsigned long long) * (size_t)e->bins);
-    if (rc) { qldpc_set_error("qber_create: device allocation failed"); qldpc_qber_free(e); return rc; }
+    dm_ledger *m = &e->mem;
+    if ((rc = dm_alloc(m, &e->d_tab, tab.size())) || (rc = dm_alloc(m, &e->d_L1, L1.size())) || (rc = dm_alloc(m, &e->d_L0, L0.size())) ||
+        (rc = dm_alloc(m, &e->d_q, q.size())) || (rc = dm_alloc(m, &e->d_llr, llr.size())) || (rc = dm_alloc(m, &e->d_cls_rows, 2 * (size_t)e->Wn)) ||
+        (rc = dm_alloc(m, &e->d_counts, (size_t)cfg->max_frames * (size_t)e->bins)) || (rc = dm_alloc(m, &e->d_pool, (size_t)e->bins))) {
+        qldpc_set_error("qber_create: device allocation failed");
+        qldpc_qber_free(e);
+        return rc;
+    }
     e->h_tab = tab;
     hipError_t he = hipMemcpy(e->d_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(e->d_L1, L1.data(), tbytes, hipMemcpyHostToDevice);
@@ -125,7 +123,7 @@ extern "C" int qldpc_qber_create(const qldpc_code *code, const qldpc_qber_cfg *c
     return QLDPC_OK;
 }
 
-extern "C" size_t qldpc_qber_device_bytes(const qldpc_qber *est) { return est ? est->dev_bytes : 0; }
+extern "C" size_t qldpc_qber_device_bytes(const qldpc_qber *est) { return est ? est->mem.dev_bytes : 0; }
 
 extern "C" int qldpc_qber_set_stream(qldpc_qber *est, void *hip_stream)
 {
@@ -153,16 +151,15 @@ extern "C" int qldpc_qber_set_merge(qldpc_qber *est, int on)
     std::vector<int32_t> L1((size_t)R * (size_t)cfg.n_grid), L0(L1.size());
     if ((rc = qldpc_qber_table_host(QB_MAX_DEGREE, cfg.n_grid, cfg.q_lo, cfg.q_hi, L1.data(), L0.data(), nullptr, nullptr))) return rc;
     HIPCHK(hipSetDevice(cfg.device));
-    const size_t tbytes = sizeof(int32_t) * L1.size(), cbytes = sizeof(uint32_t) * (size_t)cfg.max_frames * 2 * (size_t)R, pbytes = sizeof(unsigned long long) * 2 * (size_t)R;
+    const size_t tbytes = sizeof(int32_t) * L1.size();
+    dm_ledger *m = &est->mem;
     int32_t *d_L1 = nullptr, *d_L0 = nullptr;
     uint32_t *d_counts = nullptr;
     unsigned long long *d_pool = nullptr;
     uint8_t *d_rep = nullptr;
-    hipError_t he = hipMalloc((void **)&d_L1, tbytes);
-    if (he == hipSuccess) he = hipMalloc((void **)&d_L0, tbytes);
-    if (he == hipSuccess) he = hipMalloc((void **)&d_counts, cbytes);
-    if (he == hipSuccess) he = hipMalloc((void **)&d_pool, pbytes);
-    if (he == hipSuccess) he = hipMalloc((void **)&d_rep, rep.size());
+    hipError_t he = hipSuccess;
+    if (dm_alloc(m, &d_L1, L1.size()) || dm_alloc(m, &d_L0, L0.size()) || dm_alloc(m, &d_counts, (size_t)cfg.max_frames * 2 * (size_t)R) ||
+        dm_alloc(m, &d_pool, 2 * (size_t)R) || dm_alloc(m, &d_rep, rep.size())) he = hipErrorOutOfMemory;
     if (he == hipSuccess) he = hipMemcpy(d_L1, L1.data(), tbytes, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(d_L0, L0.data(), tbytes, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(d_rep, rep.data(), rep.size(), hipMemcpyHostToDevice);
@@ -173,13 +170,11 @@ extern "C" int qldpc_qber_set_merge(qldpc_qber *est, int on)
         he = hipFuncSetAttribute((const void *)&qk_qber_count_merged<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds);
     if (he == hipSuccess) he = hipDeviceSynchronize();      /* no call reads the rows that are freed below */
     if (he != hipSuccess) {
-        (void)hipFree(d_L1); (void)hipFree(d_L0); (void)hipFree(d_counts); (void)hipFree(d_pool); (void)hipFree(d_rep);
+        dm_release(m, &d_L1); dm_release(m, &d_L0); dm_release(m, &d_counts); dm_release(m, &d_pool); dm_release(m, &d_rep);
         qldpc_set_error("qber_set_merge: %s", hipGetErrorString(he));
         return QLDPC_EHIP;
     }
-    (void)hipFree(est->d_L1); (void)hipFree(est->d_L0); (void)hipFree(est->d_counts); (void)hipFree(est->d_pool);
-    est->dev_bytes += 2 * (tbytes - sizeof(int32_t) * (size_t)(D + 1) * (size_t)cfg.n_grid) + (cbytes - sizeof(uint32_t) * (size_t)cfg.max_frames * (size_t)est->bins)
-                      + (pbytes - sizeof(unsigned long long) * (size_t)est->bins) + rep.size();
+    dm_release(m, &est->d_L1); dm_release(m, &est->d_L0); dm_release(m, &est->d_counts); dm_release(m, &est->d_pool);
     est->d_L1 = d_L1; est->d_L0 = d_L0; est->d_counts = d_counts; est->d_pool = d_pool; est->d_rep = d_rep;
     est->mstaged = mstaged; est->mlds_bytes = mlds;
     est->merge = 1;

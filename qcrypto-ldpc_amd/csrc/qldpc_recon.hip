@@ -26,6 +26,7 @@
 #include "../../include/qldpc.h"
 #include "qldpc_graph.h"
 #include "qldpc_hip.h"
+#include "qldpc_devmem.h"
 #include "qldpc_recon_core.h"
 
 /*
@@ -57,6 +58,7 @@ struct recon_entry {
     int gpool_cap;
     uint32_t *d_gtrial;   /* ... and the frames of a trial launch: known | value | bits | erase rows [4][max_blocks][Wn], then |LLR| | key_bits | pass | CRC [4][max_blocks] */
     uint32_t *d_est;      /* their outputs: counts [max_blocks][rows][2] | QBER [max_blocks], sized for the merged rows */
+    dm_ledger mem;        /* the entry's own arrays, its staging sets and the lazy blind, guess and estimator buffers (qldpc_devmem.h): touched by the lane that runs the entry */
 };
 
 /* a lane = one host worker with a compute stream and a copy stream: the rate groups of a call run side by side, one lane each */
@@ -75,6 +77,7 @@ struct qldpc_recon {
     int profiling;
     uint32_t *h_tag, *d_tag;        /* qldpc_recon_tag_blocks: the staging block of a launch (recon_tag_layout), pinned and on the device: with the session when it preloads, else at the first such call */
     size_t tag_words;               /* ... and the words each holds */
+    dm_ledger tag_mem;              /* ... and their ledger (qldpc_devmem.h): the calling thread's, never a lane's */
     int gang;                       /* QLDPC_RECON_GANG=1 when the session was made: Bob-side calls with several layered rate groups decode in rounds, one gang run each (run_call_gang) */
 };
 
@@ -260,13 +263,8 @@ static void entry_free(recon_entry &e)
     qldpc_decoder_free(e.dec);
     qldpc_encoder_free(e.enc);
     qldpc_code_free(e.code);
-    (void)hipFree(e.d_est);
-    (void)hipFree(e.d_cls); (void)hipFree(e.d_out); (void)hipFree(e.d_iters); (void)hipFree(e.d_ok); (void)hipFree(e.d_blind);
-    (void)hipFree(e.d_gpool); (void)hipFree(e.d_gtrial);
+    dm_free_all(&e.mem);
     for (auto &st : e.set) {
-        (void)hipFree(st.d_in); (void)hipFree(st.d_res); (void)hipFree(st.d_bits); (void)hipFree(st.d_erase);
-        if (st.h_in) (void)hipHostFree(st.h_in);
-        if (st.h_res) (void)hipHostFree(st.h_res);
         if (st.ev_in) (void)hipEventDestroy(st.ev_in);
         if (st.ev_out) (void)hipEventDestroy(st.ev_out);
         if (st.ev_done) (void)hipEventDestroy(st.ev_done);
@@ -278,8 +276,7 @@ extern "C" void qldpc_recon_free(qldpc_recon *r)
     if (!r) return;
     (void)hipSetDevice(r->cfg.device);
     for (auto &e : r->cache) entry_free(e);
-    (void)hipFree(r->d_tag);
-    if (r->h_tag) (void)hipHostFree(r->h_tag);
+    dm_free_all(&r->tag_mem);
     for (auto &l : r->lane) {
         if (l.stream) (void)hipStreamDestroy(l.stream);
         if (l.copy) (void)hipStreamDestroy(l.copy);
@@ -535,7 +532,7 @@ static int entry_estimator(const qldpc_recon *r, recon_entry &e, bool merge)
     if (!rc && merge && (rc = qldpc_qber_set_merge(est, 1))) { qldpc_qber_free(est); est = nullptr; }
     if (rc) return rc;
     const size_t bins = 2 * (size_t)(QLDPC_QBER_MAX_DEGREE + 1);
-    if (!e.d_est && hipMalloc((void **)&e.d_est, sizeof(uint32_t) * (size_t)r->cfg.max_blocks * (bins + 1)) != hipSuccess) {
+    if (!e.d_est && dm_alloc(&e.mem, &e.d_est, (size_t)r->cfg.max_blocks * (bins + 1))) {
         qldpc_qber_free(est); est = nullptr;
         qldpc_set_error("recon: device allocation for the QBER estimator failed");
         return QLDPC_ENOMEM;
@@ -547,8 +544,7 @@ static int get_entry(qldpc_recon *r, int K, int M, recon_entry **out, qldpc_code
 {
     for (auto it = r->cache.begin(); it != r->cache.end(); ++it)
         if (it->K == K && it->M == M) { r->cache.splice(r->cache.begin(), r->cache, it); *out = &r->cache.front(); return QLDPC_OK; }
-    recon_entry e;
-    memset(&e, 0, sizeof(e));
+    recon_entry e{};
     e.K = K; e.M = M;
     const int N = K + M, Wk = K / 32, Wn = (N + 31) / 32, Wm = (M + 31) / 32, B = r->cfg.max_blocks;
     int rc = QLDPC_OK;
@@ -565,23 +561,22 @@ static int get_entry(qldpc_recon *r, int K, int M, recon_entry **out, qldpc_code
         rc = qldpc_decoder_create(e.code, K, nullptr, &dc, &e.dec);
         if (!rc) rc = qldpc_decoder_reserve(e.dec);      /* nothing is allocated per block later */
     }
-    auto alloc = [&](void **ptr, size_t bytes) { if (!rc && hipMalloc(ptr, bytes) != hipSuccess) rc = QLDPC_ENOMEM; };
-    alloc((void **)&e.d_cls, (size_t)N);
-    alloc((void **)&e.d_out, sizeof(uint32_t) * (size_t)B * Wn);
-    alloc((void **)&e.d_iters, sizeof(int) * (size_t)B);
-    alloc((void **)&e.d_ok, sizeof(int) * (size_t)B);
+    if (!rc) rc = dm_alloc(&e.mem, &e.d_cls, (size_t)N);
+    if (!rc) rc = dm_alloc(&e.mem, &e.d_out, (size_t)B * Wn);
+    if (!rc) rc = dm_alloc(&e.mem, &e.d_iters, (size_t)B);
+    if (!rc) rc = dm_alloc(&e.mem, &e.d_ok, (size_t)B);
     /* a full job's staging blocks; an entry serves both sides, so the result block holds the larger of the two layouts */
     /* a tagged call appends the hash-key rows of its blocks to the input block and receives their tags behind the result block: room for RT_MAX_KEYS keys a block */
     const size_t tag_room = (size_t)B * 2 * RT_MAX_KEYS;
     const size_t in_words = recon_in_layout(nullptr, B, Wk, Wm).words + tag_room;
     const size_t res_words = std::max(recon_bob_layout(nullptr, B, Wk).words, recon_alice_layout(nullptr, B, Wm).words) + tag_room;
     for (auto &st : e.set) {
-        alloc((void **)&st.d_in, sizeof(uint32_t) * in_words);
-        alloc((void **)&st.d_res, sizeof(uint32_t) * res_words);
-        alloc((void **)&st.d_bits, sizeof(uint32_t) * (size_t)B * Wn);
-        alloc((void **)&st.d_erase, sizeof(uint32_t) * (size_t)B * Wn);
-        if (!rc && hipHostMalloc((void **)&st.h_in, sizeof(uint32_t) * in_words) != hipSuccess) rc = QLDPC_ENOMEM;
-        if (!rc && hipHostMalloc((void **)&st.h_res, sizeof(uint32_t) * res_words) != hipSuccess) rc = QLDPC_ENOMEM;
+        if (!rc) rc = dm_alloc(&e.mem, &st.d_in, in_words);
+        if (!rc) rc = dm_alloc(&e.mem, &st.d_res, res_words);
+        if (!rc) rc = dm_alloc(&e.mem, &st.d_bits, (size_t)B * Wn);
+        if (!rc) rc = dm_alloc(&e.mem, &st.d_erase, (size_t)B * Wn);
+        if (!rc) rc = dm_alloc_pinned(&e.mem, &st.h_in, in_words);
+        if (!rc) rc = dm_alloc_pinned(&e.mem, &st.h_res, res_words);
         if (!rc && (hipEventCreateWithFlags(&st.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&st.ev_out, hipEventDisableTiming) != hipSuccess ||
                     hipEventCreateWithFlags(&st.ev_done, hipEventDisableTiming) != hipSuccess)) rc = QLDPC_EHIP;
     }
@@ -594,7 +589,7 @@ static int get_entry(qldpc_recon *r, int K, int M, recon_entry **out, qldpc_code
     if (!rc && r->cfg.preload) rc = entry_estimator(r, e, true);
     if (rc) { entry_free(e); return rc; }
     if (r->profiling) qldpc_profile_enable(e.dec, 1);
-    r->cache.push_front(e);      /* the cache is trimmed to `keep` entries at the end of the call (cache_trim): nothing in use is evicted */
+    r->cache.push_front(std::move(e));      /* the cache is trimmed to `keep` entries at the end of the call (cache_trim): nothing in use is evicted */
     r->created++;
     *out = &r->cache.front();
     return QLDPC_OK;
@@ -768,7 +763,7 @@ static int job_load_blind(lane_run *L, recon_job &j)
     hipStream_t s = L->lane->stream;
     const int n = (int)j.idx.size(), B = L->r->cfg.max_blocks;
     const size_t Wn = (size_t)(e->K + e->M + 31) / 32;
-    if (!e->d_blind && hipMalloc((void **)&e->d_blind, sizeof(uint32_t) * 4 * (size_t)B * Wn) != hipSuccess) { qldpc_set_error("recon_decode_blind: device allocation failed"); return QLDPC_ENOMEM; }
+    if (!e->d_blind && dm_alloc(&e->mem, &e->d_blind, 4 * (size_t)B * Wn)) { qldpc_set_error("recon_decode_blind: device allocation failed"); return QLDPC_ENOMEM; }
     j.h_blind.assign(3 * (size_t)n * Wn, 0u);
     uint32_t *known = j.h_blind.data(), *value = known + (size_t)n * Wn, *cand = value + (size_t)n * Wn;
     bool any = false;
@@ -826,13 +821,13 @@ static int entry_guess_pool(const qldpc_recon *r, recon_entry &e, int sources)
 {
     const size_t B = (size_t)r->cfg.max_blocks, Wk = (size_t)e.K / 32, Wn = (size_t)(e.K + e.M + 31) / 32;
     const int cap = std::max(sources, r->cfg.max_blocks);
-    if (!e.d_gtrial && hipMalloc((void **)&e.d_gtrial, sizeof(uint32_t) * 4 * (B * Wn + B)) != hipSuccess) { qldpc_set_error("recon_decode_guess: device allocation failed"); return QLDPC_ENOMEM; }
+    if (!e.d_gtrial && dm_alloc(&e.mem, &e.d_gtrial, 4 * (B * Wn + B))) { qldpc_set_error("recon_decode_guess: device allocation failed"); return QLDPC_ENOMEM; }
     if (e.gpool_cap >= cap) return QLDPC_OK;
-    (void)hipFree(e.d_gpool);
-    e.d_gpool = nullptr; e.gpool_cap = 0;
+    dm_release(&e.mem, &e.d_gpool);
+    e.gpool_cap = 0;
     /* ... then, for a tagged call, the tags and the hash-key rows of the sources: room for RT_MAX_KEYS keys each */
     const size_t words = recon_guess_pool_layout(nullptr, cap, (int)Wk, (int)Wn).words + recon_bob_layout(nullptr, cap, (int)Wk).words + (size_t)cap * RG_FIELDS + (size_t)cap * 4 * RT_MAX_KEYS;
-    if (hipMalloc((void **)&e.d_gpool, sizeof(uint32_t) * words) != hipSuccess) { qldpc_set_error("recon_decode_guess: device allocation failed"); return QLDPC_ENOMEM; }
+    if (dm_alloc(&e.mem, &e.d_gpool, words)) { qldpc_set_error("recon_decode_guess: device allocation failed"); return QLDPC_ENOMEM; }
     e.gpool_cap = cap;
     return QLDPC_OK;
 }
@@ -1538,12 +1533,11 @@ extern "C" int qldpc_recon_decode_guess_tagged(qldpc_recon *r, int n, uint32_t *
 static int tag_stage_reserve(qldpc_recon *r, size_t words)
 {
     if (r->tag_words >= words) return QLDPC_OK;
-    (void)hipFree(r->d_tag);
-    if (r->h_tag) (void)hipHostFree(r->h_tag);
-    r->h_tag = r->d_tag = nullptr; r->tag_words = 0;
-    if (hipHostMalloc((void **)&r->h_tag, sizeof(uint32_t) * words) != hipSuccess || hipMalloc((void **)&r->d_tag, sizeof(uint32_t) * words) != hipSuccess) {
-        if (r->h_tag) (void)hipHostFree(r->h_tag);
-        r->h_tag = nullptr;
+    dm_release(&r->tag_mem, &r->d_tag);
+    dm_release(&r->tag_mem, &r->h_tag);
+    r->tag_words = 0;
+    if (dm_alloc_pinned(&r->tag_mem, &r->h_tag, words) || dm_alloc(&r->tag_mem, &r->d_tag, words)) {
+        dm_release(&r->tag_mem, &r->h_tag);
         qldpc_set_error("recon_tag_blocks: staging of %zu words could not be allocated", words);
         return QLDPC_ENOMEM;
     }

@@ -121,7 +121,7 @@ static size_t tz_desc_words(int n) { return (size_t)n * (sizeof(tz_desc) / 4); }
 extern "C" void qldpc_toeplitz_free(qldpc_toeplitz_ctx *tz)
 {
     if (!tz) return;
-    hb_free(&tz->st);                                            /* waits for the last call first */
+    hb_free(&tz->st);                                            /* waits for the last call first; the NTT state's device memory goes with the ledger */
     tzn_free(tz);
     delete tz;
 }
@@ -170,7 +170,7 @@ extern "C" int qldpc_toeplitz_stats(const qldpc_toeplitz_ctx *tz, uint64_t out[8
     return QLDPC_OK;
 }
 
-extern "C" size_t qldpc_toeplitz_device_bytes(const qldpc_toeplitz_ctx *tz) { return tz ? tz->st.dev_bytes : 0; }
+extern "C" size_t qldpc_toeplitz_device_bytes(const qldpc_toeplitz_ctx *tz) { return tz ? tz->st.mem.dev_bytes : 0; }
 
 /* the layout of the call as descriptor rows into the pinned staging.  strides NULL: the host form (one_seed: every block reads the seed at 0) */
 static hb_sums tz_fill(qldpc_toeplitz_ctx *tz, int n, const int *key_bits, const int *out_bits, const hb_strides *strides, int one_seed)

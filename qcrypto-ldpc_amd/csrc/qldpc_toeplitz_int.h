@@ -25,9 +25,9 @@ struct qldpc_toeplitz_ctx {
     tzn_state *ntt;
 };
 
-/* allocates everything the method needs and adds it to tz->st.dev_bytes; pass_log2 and work_bytes as in qldpc_toeplitz_cfg */
+/* allocates everything the method needs into the ledger of tz->st; pass_log2 and work_bytes as in qldpc_toeplitz_cfg */
 int tzn_create(qldpc_toeplitz_ctx *tz, int pass_log2, size_t work_bytes);
-void tzn_free(qldpc_toeplitz_ctx *tz);
+void tzn_free(qldpc_toeplitz_ctx *tz);      /* the host side of the state; hb_free(&tz->st) frees what is in the ledger */
 /* the n blocks of a call whose rows `rows` describe (key_off / seed_off / out_off from d_keys / d_seeds / d_out), queued on s;
    shared: every block reads the seed row at rows[0].seed_off, which holds at least the longest seed of the call.  Fills tz->stats */
 int tzn_blocks(qldpc_toeplitz_ctx *tz, int n, const tz_desc *rows, const int *key_bits, int shared,

@@ -257,10 +257,6 @@ void tzn_free(qldpc_toeplitz_ctx *tz)
 {
     tzn_state *st = tz->ntt;
     if (!st) return;
-    if (st->d_work) (void)hipFree(st->d_work);
-    if (st->d_tab) (void)hipFree(st->d_tab);
-    if (st->d_desc) (void)hipFree(st->d_desc);
-    if (st->h_desc) (void)hipHostFree(st->h_desc);
     free(st->order);
     delete st;
     tz->ntt = nullptr;
@@ -292,9 +288,8 @@ int tzn_create(qldpc_toeplitz_ctx *tz, int pass_log2, size_t work_bytes)
     st->order = (int *)malloc(sizeof(int) * (size_t)tz->st.lim.max_blocks);
     if (!h_tab || !st->order) { free(h_tab); return QLDPC_ENOMEM; }
     int rc = QLDPC_OK;
-    if (hipMalloc((void **)&st->d_work, 4 * st->work_res) != hipSuccess || hipMalloc((void **)&st->d_tab, 4 * tw) != hipSuccess ||
-        hipMalloc((void **)&st->d_desc, rows * sizeof(tzn_desc)) != hipSuccess ||
-        hipHostMalloc((void **)&st->h_desc, rows * sizeof(tzn_desc), hipHostMallocDefault) != hipSuccess) {
+    dm_ledger *m = &tz->st.mem;
+    if (dm_alloc(m, &st->d_work, st->work_res) || dm_alloc(m, &st->d_tab, tw) || dm_alloc(m, &st->d_desc, rows) || dm_alloc_pinned(m, &st->h_desc, rows)) {
         qldpc_set_error("toeplitz_create_cfg: no memory for a work area of %zu bytes", 4 * st->work_res);
         rc = QLDPC_ENOMEM;
     }
@@ -303,7 +298,6 @@ int tzn_create(qldpc_toeplitz_ctx *tz, int pass_log2, size_t work_bytes)
         if (hipMemcpy(st->d_tab, h_tab, 4 * tw, hipMemcpyHostToDevice) != hipSuccess) { qldpc_set_error("toeplitz_create_cfg: the tables did not reach the device"); rc = QLDPC_EHIP; }
     }
     free(h_tab);
-    if (!rc) tz->st.dev_bytes += 4 * st->work_res + 4 * tw + rows * sizeof(tzn_desc);
     return rc;
 }
 
