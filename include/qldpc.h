@@ -1585,12 +1585,33 @@ int    qldpc_mc_guess_next_host(int guess_bits, int batch, uint64_t pool, uint64
  *                      Such a context owns less than N beliefs and 8N / 32 bytes of rows per frame of max_frames, and every call above serves it
  *                      with the same contract.
  * qldpc_polar_create_form: a form that is neither is QLDPC_EINVAL; every other refusal is qldpc_polar_create's.
+ *
+ * The decoder has two RULES, and the library does not choose between them either (qldpc_polar_create_rule; csrc/qldpc_polar_ssc_core.h):
+ *   QLDPC_POLAR_SC     the decoder above: every node of the tree is visited whatever the code is.  qldpc_polar_create and _create_form mean this.
+ *   QLDPC_POLAR_SSC    the simplified SC decoder of Alamdar-Yazdi and Kschischang.  A node whose leaves are all frozen (rate 0) returns the
+ *                      encoding of its frozen values and its beliefs are not looked at: exact.  A node with no frozen leaf (rate 1) returns
+ *                      c[k] = (L[k] < 0) and decides u = encode(c).  Every other node takes the SC step.  Where no belief of a rate-1 node of a
+ *                      frame is 0, this is SC bit for bit in u, info and x; where one is, SSC decides 0 for that bit and SC may not: a decoder
+ *                      of its own, with a frame error rate inside SC's statistical band.  Outputs u, info and x; there is no leaf output (a
+ *                      pruned node never forms its leaf beliefs).  Lanes form only.
+ * qldpc_polar_create_rule: with QLDPC_POLAR_SC it is qldpc_polar_create_form; a rule that is neither is QLDPC_EINVAL; QLDPC_POLAR_SSC with
+ * QLDPC_POLAR_WIDE and log2_n > 5 is QLDPC_EUNSUPPORTED (create a QLDPC_POLAR_LANES context).  An SSC context also owns the plan of its code on
+ * the device (at most 12 bytes per 32 positions).  qldpc_polar_decode_dev serves it under the same contract, but a non-NULL d_leaf is
+ * QLDPC_EUNSUPPORTED (create a QLDPC_POLAR_SC context for the leaf beliefs); _encode_dev, _set_stream, _device_bytes and _free are unchanged, and
+ * qldpc_polar_tally_dev runs the tally it always ran: every position is frozen there, so the rule has no say.
+ * qldpc_polar_decode_ssc_host: the mirror, qldpc_polar_decode_host's arguments and refusals without leaf.
+ * qldpc_polar_ssc_plan_host: the plan the kernel and the mirror walk: steps[n_steps][3] = (first 32-leaf block, log2 of the leaves, kind: 0 rate
+ * 0, 1 rate 1, 2 a mixed block decoded by the same rule inside it) in leaf order; the steps with kind < 2 are the maximal rate-0 and rate-1
+ * nodes of 32 leaves or more; for N < 32 one mixed step holds the frame.  steps must hold max(N / 32, 1) x 3 ints.
  */
 typedef struct qldpc_polar qldpc_polar;
 enum { QLDPC_POLAR_I8 = 0, QLDPC_POLAR_F32 = 1 };
 enum { QLDPC_POLAR_LANES = 0, QLDPC_POLAR_WIDE = 1 };
+enum { QLDPC_POLAR_SC = 0, QLDPC_POLAR_SSC = 1 };
 int    qldpc_polar_create(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int max_frames, int device, qldpc_polar **out);
 int    qldpc_polar_create_form(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int max_frames, int form, int device,
+                               qldpc_polar **out);
+int    qldpc_polar_create_rule(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int max_frames, int form, int rule, int device,
                                qldpc_polar **out);
 void   qldpc_polar_free(qldpc_polar *p);
 size_t qldpc_polar_device_bytes(const qldpc_polar *p);
@@ -1604,6 +1625,9 @@ int    qldpc_polar_decode_host(int log2_n, int n_info, const int *info_pos, int 
                                const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf);
 int    qldpc_polar_decode_wide_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
                                     const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf);
+int    qldpc_polar_decode_ssc_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
+                                   const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x);
+int    qldpc_polar_ssc_plan_host(int log2_n, int n_info, const int *info_pos, int *steps /* [N/32 or 1][3] */, int *n_steps);
 
 /* ------------------------------------------------------------------------------------------------------------------------------------------
  * Polar codes: the CRC-aided successive-cancellation LIST decoder (qldpc_polar_list_*), beside the SC decoder above and with its sizes, rows,

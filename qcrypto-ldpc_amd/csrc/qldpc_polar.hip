@@ -12,6 +12,10 @@
  * and QLDPC_POLAR_WIDE_LEAF (1 or 32) in the environment replace the chip level, the workgroup size and the lanes of a leaf block of the
  * contexts created after: what tools/polar_wide_cost.py measures the alternatives with.
  *
+ * A context of the SSC rule (qldpc_polar_create_rule, QLDPC_POLAR_SSC; the rule and the plan are qldpc_polar_ssc_core.h's) is a lanes context that
+ * also owns the plan of its code on the device and decodes with pl_ssc_decode (qldpc_kernels_polar_ssc.h) in pl_decode's place; everything else,
+ * the tally included, is the lanes form's.
+ *
  * qldpc_polar_tally_dev (the genie-aided construction, qldpc_polar_tally_core.h) is the lanes' decode in its tally form
  * (qldpc_kernels_polar_tally.h): pl_load, then pl_tally on the same scratch, into an accumulator that is the caller's.
  */
@@ -22,6 +26,7 @@
 #include <new>
 #include <type_traits>
 
+#include "qldpc_kernels_polar_ssc.h"
 #include "qldpc_kernels_polar_tally.h"
 #include "qldpc_kernels_polar_wide.h"
 #include "qldpc_polar_ctx.h"
@@ -32,6 +37,9 @@ struct qldpc_polar {
     int chip, lanes, leaf_lanes;   /* wide: the chip level asked for, the workgroup, and the lanes of a leaf block (32, or 0: one) */
     void *d_B;                     /* groups x pl_group_elems(n) int8 or float, NULL for n <= 5; wide: max_frames x plw_scratch_elems(n, chip) */
     uint32_t *d_U, *d_X;           /* groups x W x 64 each; wide: max_frames x W each */
+    int rule;                      /* QLDPC_POLAR_SC or QLDPC_POLAR_SSC */
+    int *d_steps;                  /* SSC: the plan of the code, n_steps x PL_SSC_STEP ints; NULL otherwise */
+    int n_steps;
 };
 
 const pl_ctx *pl_ctx_of_sc(const qldpc_polar *p) { return &p->c; }
@@ -55,12 +63,37 @@ template <class Fn> static auto plw_with_lanes(int lanes, Fn fn)
     }
 }
 
-static int pl_create(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int max_frames, int form, int device, qldpc_polar **out)
+/* the plan of an SSC context, built from the code and sent up; the context's ledger owns it */
+static int pl_upload_plan(qldpc_polar *p, const int *info_pos)
+{
+    uint32_t *mask = nullptr;
+    int rc = pl_args_frozen_mask("polar_create", p->c.n, p->c.n_info, info_pos, &mask);
+    if (rc) return rc;
+    int *steps = (int *)malloc(sizeof(int) * PL_SSC_STEP * (size_t)pl_ssc_max_steps(p->c.n));
+    if (!steps) { free(mask); return QLDPC_ENOMEM; }
+    p->n_steps = (int)pl_ssc_plan(p->c.n, mask, steps);
+    free(mask);
+    pl_ctx_alloc(&p->c, &p->d_steps, sizeof(int) * PL_SSC_STEP * (size_t)p->n_steps);
+    hipError_t e = hipSuccess;
+    if (!p->c.alloc_failed) e = hipMemcpy(p->d_steps, steps, sizeof(int) * PL_SSC_STEP * (size_t)p->n_steps, hipMemcpyHostToDevice);
+    free(steps);
+    HIPCHK(e);
+    return QLDPC_OK;
+}
+
+static int pl_create(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int max_frames, int form, int rule, int device, qldpc_polar **out)
 {
     qldpc_polar *p = new (std::nothrow) qldpc_polar();
     if (!p) return QLDPC_ENOMEM;
-    const int rc = pl_ctx_create(&p->c, "polar_create", log2_n, PL_MAX_LOG2N, n_info, info_pos, messages, maxq, max_frames, device, [](int) { return QLDPC_OK; });
+    const int rc = pl_ctx_create(&p->c, "polar_create", log2_n, PL_MAX_LOG2N, n_info, info_pos, messages, maxq, max_frames, device, [&](int stage) {
+        if (stage == 0 && rule == QLDPC_POLAR_SSC && form == QLDPC_POLAR_WIDE && log2_n > PL_SUB_LOG) {
+            qldpc_set_error("polar_create: the SSC rule has no wide form at log2_n=%d (> %d): create a QLDPC_POLAR_LANES context for it", log2_n, PL_SUB_LOG);
+            return (int)QLDPC_EUNSUPPORTED;
+        }
+        return (int)QLDPC_OK;
+    });
     if (rc) { qldpc_polar_free(p); return rc; }
+    p->rule = rule;
     p->wide = form == QLDPC_POLAR_WIDE && log2_n > PL_SUB_LOG;
     p->chip = PLW_CHIP_LOG; p->lanes = PLW_LANES; p->leaf_lanes = PLW_LEAF_LANES;
     if (p->wide) {
@@ -82,6 +115,8 @@ static int pl_create(int log2_n, int n_info, const int *info_pos, int messages, 
     pl_ctx_alloc(&p->c, &p->d_B, esz * beliefs);
     pl_ctx_alloc(&p->c, &p->d_U, sizeof(uint32_t) * row_words);
     pl_ctx_alloc(&p->c, &p->d_X, sizeof(uint32_t) * row_words);
+    if (rule == QLDPC_POLAR_SSC && !p->c.alloc_failed)
+        if (const int prc = pl_upload_plan(p, info_pos)) { qldpc_polar_free(p); return prc; }
     if (p->c.alloc_failed) {
         qldpc_set_error("polar_create: device allocation failed (about %zu MiB for max_frames=%d at N = 2^%d: lower max_frames)",
                         (esz * beliefs + 8 * row_words) >> 20, max_frames, log2_n);
@@ -96,7 +131,7 @@ extern "C" int qldpc_polar_create(int log2_n, int n_info, const int *info_pos, i
 {
     if (!out) return QLDPC_EINVAL;
     *out = nullptr;
-    return pl_create(log2_n, n_info, info_pos, messages, maxq, max_frames, QLDPC_POLAR_LANES, device, out);
+    return pl_create(log2_n, n_info, info_pos, messages, maxq, max_frames, QLDPC_POLAR_LANES, QLDPC_POLAR_SC, device, out);
 }
 
 extern "C" int qldpc_polar_create_form(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int max_frames, int form, int device,
@@ -108,7 +143,23 @@ extern "C" int qldpc_polar_create_form(int log2_n, int n_info, const int *info_p
         qldpc_set_error("polar_create_form: form=%d (QLDPC_POLAR_LANES = %d or QLDPC_POLAR_WIDE = %d)", form, QLDPC_POLAR_LANES, QLDPC_POLAR_WIDE);
         return QLDPC_EINVAL;
     }
-    return pl_create(log2_n, n_info, info_pos, messages, maxq, max_frames, form, device, out);
+    return pl_create(log2_n, n_info, info_pos, messages, maxq, max_frames, form, QLDPC_POLAR_SC, device, out);
+}
+
+extern "C" int qldpc_polar_create_rule(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int max_frames, int form, int rule, int device,
+                                       qldpc_polar **out)
+{
+    if (!out) return QLDPC_EINVAL;
+    *out = nullptr;
+    if (rule != QLDPC_POLAR_SC && rule != QLDPC_POLAR_SSC) {
+        qldpc_set_error("polar_create_rule: rule=%d (QLDPC_POLAR_SC = %d or QLDPC_POLAR_SSC = %d)", rule, QLDPC_POLAR_SC, QLDPC_POLAR_SSC);
+        return QLDPC_EINVAL;
+    }
+    if (form != QLDPC_POLAR_LANES && form != QLDPC_POLAR_WIDE) {
+        qldpc_set_error("polar_create_rule: form=%d (QLDPC_POLAR_LANES = %d or QLDPC_POLAR_WIDE = %d)", form, QLDPC_POLAR_LANES, QLDPC_POLAR_WIDE);
+        return QLDPC_EINVAL;
+    }
+    return pl_create(log2_n, n_info, info_pos, messages, maxq, max_frames, form, rule, device, out);
 }
 
 extern "C" size_t qldpc_polar_device_bytes(const qldpc_polar *p) { return pl_ctx_device_bytes(PL_CTX(p)); }
@@ -132,8 +183,17 @@ static void pl_launch_decode(const qldpc_polar *p, M m, int n_frames, unsigned g
                        d_frozen_u, (mem *)p->d_B, p->d_U, p->d_X, (mem *)d_leaf);
 }
 
+template <class M, int SL, bool TOP>
+static void pl_launch_ssc(const qldpc_polar *p, M m, int n_frames, unsigned groups, const void *d_llr, const uint32_t *d_frozen_u, bool want_u)
+{
+    typedef typename M::mem mem;
+    hipLaunchKernelGGL((pl_ssc_decode<M, SL, TOP>), dim3(groups), dim3(PL_GROUP), 0, p->c.stream, m, p->c.n, n_frames, (const mem *)d_llr, (const uint32_t *)p->c.d_fmask,
+                       d_frozen_u, (const int *)p->d_steps, p->n_steps, want_u, (mem *)p->d_B, p->d_U, p->d_X);
+}
+
+/* d_leaf: SC only (an SSC call with one was refused); want_u: SSC only */
 template <class M>
-static int pl_run_decode(const qldpc_polar *p, M m, int n_frames, const void *d_llr, const uint32_t *d_frozen_u, void *d_leaf)
+static int pl_run_decode(const qldpc_polar *p, M m, int n_frames, const void *d_llr, const uint32_t *d_frozen_u, void *d_leaf, bool want_u)
 {
     typedef typename M::mem mem;
     const int n = p->c.n;
@@ -142,6 +202,18 @@ static int pl_run_decode(const qldpc_polar *p, M m, int n_frames, const void *d_
         const size_t tiles = ((size_t)1 << n) / 64u;
         hipLaunchKernelGGL(pl_load<M>, dim3((unsigned)(groups * tiles)), dim3(256), 0, p->c.stream, m, n, n_frames, (const mem *)d_llr, (mem *)p->d_B);
         LAUNCHCHK();
+    }
+    if (p->rule == QLDPC_POLAR_SSC) {
+        switch (n) {
+        case 1: pl_launch_ssc<M, 1, true>(p, m, n_frames, groups, d_llr, d_frozen_u, want_u); break;
+        case 2: pl_launch_ssc<M, 2, true>(p, m, n_frames, groups, d_llr, d_frozen_u, want_u); break;
+        case 3: pl_launch_ssc<M, 3, true>(p, m, n_frames, groups, d_llr, d_frozen_u, want_u); break;
+        case 4: pl_launch_ssc<M, 4, true>(p, m, n_frames, groups, d_llr, d_frozen_u, want_u); break;
+        case 5: pl_launch_ssc<M, 5, true>(p, m, n_frames, groups, d_llr, d_frozen_u, want_u); break;
+        default: pl_launch_ssc<M, 5, false>(p, m, n_frames, groups, d_llr, d_frozen_u, want_u); break;
+        }
+        LAUNCHCHK();
+        return QLDPC_OK;
     }
     switch (n) {
     case 1: pl_launch_decode<M, 1, true>(p, m, n_frames, groups, d_llr, d_frozen_u, d_leaf); break;
@@ -178,9 +250,13 @@ extern "C" int qldpc_polar_decode_dev(qldpc_polar *p, int n_frames, const void *
     int rc = pl_ctx_check_frames(PL_CTX(p), n_frames, "polar_decode_dev");
     if (rc || n_frames == 0) return rc;
     if (!d_llr) { qldpc_set_error("polar_decode_dev: d_llr is NULL"); return QLDPC_EINVAL; }
+    if (p->rule == QLDPC_POLAR_SSC && d_leaf) {
+        qldpc_set_error("polar_decode_dev: the SSC rule has no leaf output (a pruned node never forms its leaf beliefs): create a QLDPC_POLAR_SC context for it");
+        return QLDPC_EUNSUPPORTED;
+    }
     HIPCHK(hipSetDevice(p->c.device));
     if (p->wide) return pl_with_messages(&p->c, [&](auto m) { return plw_run_decode(p, m, n_frames, d_llr, d_frozen_u, d_u, d_info, d_x, d_leaf); });
-    rc = pl_with_messages(&p->c, [&](auto m) { return pl_run_decode(p, m, n_frames, d_llr, d_frozen_u, d_leaf); });
+    rc = pl_with_messages(&p->c, [&](auto m) { return pl_run_decode(p, m, n_frames, d_llr, d_frozen_u, d_leaf, d_u || d_info); });
     if (rc) return rc;
     if (d_u || d_info || d_x) {
         const size_t groups = ((size_t)n_frames + PL_GROUP - 1) / PL_GROUP, threads = groups * p->c.W * PL_GROUP;

@@ -9,12 +9,15 @@ from ._lib import _L, _Handle, _chk, _create, _dev_empty, _dev_rows, _ip, _ptr, 
 
 POLAR_I8, POLAR_F32 = 0, 1
 POLAR_FORMS = {"lanes": 0, "wide": 1}
+POLAR_RULES = {"sc": 0, "ssc": 1}
+POLAR_SSC_KINDS = ("rate0", "rate1", "mixed")      # the kinds of a plan's steps, by their number
 POLAR_MAX_LOG2N = 20
 POLAR_LIST_MAX_LOG2N = 16
 POLAR_CRC11 = (11, 0x621)          # the CRC of the reference's list decoder: crc_len, crc_poly
 
 _sig("qldpc_polar_create", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)])
 _sig("qldpc_polar_create_form", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)])
+_sig("qldpc_polar_create_rule", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)])
 _sig("qldpc_polar_free", None, [_vp])
 _sig("qldpc_polar_device_bytes", C.c_size_t, [_vp])
 _sig("qldpc_polar_set_stream", C.c_int, [_vp, _vp])
@@ -23,6 +26,8 @@ _sig("qldpc_polar_decode_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, 
 _sig("qldpc_polar_encode_host", C.c_int, [C.c_int, C.c_int, _up, _up])
 _sig("qldpc_polar_decode_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _vp, _up, _up, _up, _up, _vp])
 _sig("qldpc_polar_decode_wide_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _vp, _up, _up, _up, _up, _vp])
+_sig("qldpc_polar_decode_ssc_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _vp, _up, _up, _up, _up])
+_sig("qldpc_polar_ssc_plan_host", C.c_int, [C.c_int, C.c_int, _ip, _ip, _ip])
 _sig("qldpc_polar_list_create", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.POINTER(_vp)])
 _sig("qldpc_polar_list_free", None, [_vp])
 _sig("qldpc_polar_list_device_bytes", C.c_size_t, [_vp])
@@ -52,6 +57,15 @@ def _form(form):
             raise QldpcError(-1, "polar: form=%r ('lanes' or 'wide')" % (form,))
         return POLAR_FORMS[form]
     return int(form)
+
+
+def _rule(rule):
+    """'sc' or 'ssc'; a number goes to the library as it is, which refuses what is neither"""
+    if isinstance(rule, str):
+        if rule not in POLAR_RULES:
+            raise QldpcError(-1, "polar: rule=%r ('sc' or 'ssc')" % (rule,))
+        return POLAR_RULES[rule]
+    return int(rule)
 
 
 def _words(log2_n):
@@ -119,6 +133,27 @@ def polar_decode_host(log2_n, info_pos, llr, frozen=None, messages="i8", maxq=31
 def polar_decode_wide_host(log2_n, info_pos, llr, frozen=None, messages="i8", maxq=31, leaf=False):
     """the host walk of the wide form's memory plan (qldpc_polar_decode_wide_host): the arguments and the results of polar_decode_host, bit for bit"""
     return _decode_host(_L.qldpc_polar_decode_wide_host, "polar_decode_wide_host", log2_n, info_pos, llr, frozen, messages, maxq, leaf)
+
+
+def polar_decode_ssc_host(log2_n, info_pos, llr, frozen=None, messages="i8", maxq=31):
+    """the simplified SC decoder's mirror (qldpc_polar_decode_ssc_host): the arguments of polar_decode_host without leaf -> dict(u, info, x).
+    Rate-0 and rate-1 subtrees are pruned: SC bit for bit on every frame in which no belief of a rate-1 node is 0"""
+    who = "polar_decode_ssc_host"
+    kind, dt, pos, llr, fz, n, N, W, F = _host_rows(who, log2_n, POLAR_MAX_LOG2N, info_pos, llr, frozen, messages)
+    out = dict(u=np.zeros((F, W), np.uint32), info=np.zeros((F, (pos.size + 31) // 32), np.uint32), x=np.zeros((F, W), np.uint32))
+    _chk(_L.qldpc_polar_decode_ssc_host(n, pos.size, pos.ctypes.data_as(_ip), kind, int(maxq), F, llr.ctypes.data_as(_vp), _ptr(fz, _up), _ptr(out["u"], _up),
+                                        _ptr(out["info"], _up), _ptr(out["x"], _up)), who)
+    return out
+
+
+def polar_ssc_plan(log2_n, info_pos):
+    """the plan of a code under the SSC rule (qldpc_polar_ssc_plan_host) -> int32 [steps, 3]: first 32-leaf block, log2 of the leaves, kind (by
+    POLAR_SSC_KINDS) in leaf order; one mixed step of the whole frame for N < 32"""
+    pos = np.ascontiguousarray(info_pos, dtype=np.int32).ravel()
+    steps = np.zeros((_words(log2_n), 3), np.int32)
+    count = C.c_int(0)
+    _chk(_L.qldpc_polar_ssc_plan_host(int(log2_n), pos.size, pos.ctypes.data_as(_ip), steps.ctypes.data_as(_ip), C.byref(count)), "polar_ssc_plan")
+    return steps[:count.value].copy()
 
 
 # ---- the genie-aided construction --------------------------------------------------------------------------------------------------------
@@ -213,13 +248,15 @@ class _PolarCode(_Handle):
 class Polar(_PolarCode):
     """A polar code of N = 2^log2_n bits with information at `info_pos` (every other position frozen) on the device: encode() and the
     successive-cancellation decode() of up to max_frames frames a call.  form="lanes": 64 frames to a wave, for batches; form="wide": a workgroup
-    to a frame, for few long frames.  The same function bit for bit, and the choice is the caller's.  Device tensors in, device tensors out,
-    asynchronous on torch's current stream."""
+    to a frame, for few long frames.  The same function bit for bit, and the choice is the caller's.  rule="sc": every node of the tree is
+    visited; rule="ssc": rate-0 and rate-1 subtrees are pruned (lanes form; no leaf output), which is SC bit for bit on every frame in which no
+    belief of a rate-1 node is 0, and again the choice is the caller's.  Device tensors in, device tensors out, asynchronous on torch's current
+    stream."""
     _free, _device_bytes, _set_stream = _L.qldpc_polar_free, _L.qldpc_polar_device_bytes, _L.qldpc_polar_set_stream
 
-    def __init__(self, log2_n, info_pos, messages="i8", maxq=31, max_frames=4096, device=0, form="lanes"):
-        self.form = _form(form)
-        self._create_code(_L.qldpc_polar_create_form, log2_n, info_pos, messages, maxq, (), max_frames, (self.form,), device)
+    def __init__(self, log2_n, info_pos, messages="i8", maxq=31, max_frames=4096, device=0, form="lanes", rule="sc"):
+        self.form, self.rule = _form(form), _rule(rule)
+        self._create_code(_L.qldpc_polar_create_rule, log2_n, info_pos, messages, maxq, (), max_frames, (self.form, self.rule), device)
 
     def encode(self, u, out=None):
         """u int32 / uint32 [F, W] packed rows on the device -> x of the same shape; out=u encodes in place"""
