@@ -253,7 +253,12 @@ void qldpc_decoder_cfg_default(qldpc_decoder_cfg *cfg);
 int qldpc_decoder_create(const qldpc_code *code, int K, const int *info_bits_pos,
                          const qldpc_decoder_cfg *cfg, qldpc_decoder **out);
 void qldpc_decoder_free(qldpc_decoder *dec);
-/* hipStream_t to launch on (NULL = the null stream).  All *_dev calls are asynchronous on it. */
+/* hipStream_t to launch on (NULL = the null stream).  All *_dev calls are asynchronous on it.
+ * STREAM SWITCH, the rule of every set_stream call of the library (qldpc_decoder_, qldpc_gang_, qldpc_qber_, qldpc_polar_ and qldpc_polar_list_set_stream)
+ * and of a gang that takes a member back: a switch to another stream orders the new stream after everything the context has queued on the old one
+ * (an event recorded on the old stream that the new one waits for; the call itself waits for nothing), so load on A, set_stream(B), run is a run
+ * after the load.  The same stream again does nothing.  The old stream must still exist when the switch is made.  The caller's own buffers are the
+ * caller's to order: what another stream writes into an input is not known to the context. */
 int qldpc_decoder_set_stream(qldpc_decoder *dec, void *hip_stream);
 int qldpc_decoder_reset(qldpc_decoder *dec);
 size_t qldpc_decoder_device_bytes(const qldpc_decoder *dec);   /* HBM held by this decoder        */
@@ -392,7 +397,7 @@ int qldpc_last_run_stats(qldpc_decoder *dec, long long out[4]);
  * Members are loaded and read with their own qldpc_load_* / qldpc_fetch_* calls (syndrome form, erasures and shortened loads included) and stay
  * usable on their own: qldpc_run on a member is legal before and after gang runs, and a decoder may belong to several gangs.  Members are not
  * owned and must outlive the gang.  The gang has ONE stream (member 0's at creation, or qldpc_gang_set_stream); a taken member found on another
- * stream when a run starts is waited for there and moved to the gang's.  Steps are ordered by the stream alone.  The host polls the members'
+ * stream when a run starts is moved to the gang's by the stream switch (qldpc_decoder_set_stream): what it has queued there comes first.  Steps are ordered by the stream alone.  The host polls the members'
  * early-exit counters every p sweeps, p = the smallest non-zero polling period of a member (none: every sweep is issued, converged groups
  * return early inside the kernels); a member with no frame left takes no part in later launches.
  *
@@ -409,7 +414,7 @@ typedef struct qldpc_gang qldpc_gang;
 #define QLDPC_GANG_MAX_MEMBERS 32      /* per gang; launches cover up to 8 members each */
 int  qldpc_gang_create(qldpc_decoder *const *members, int n, qldpc_gang **out);
 void qldpc_gang_free(qldpc_gang *g);                       /* members are not owned and must outlive the gang */
-int  qldpc_gang_set_stream(qldpc_gang *g, void *hip_stream); /* sets every member's stream: loads, the run and fetches are ordered on it */
+int  qldpc_gang_set_stream(qldpc_gang *g, void *hip_stream); /* every member's stream, by the stream switch (qldpc_decoder_set_stream): loads, the run and fetches are ordered on it */
 /* take[n]: which members take part (NULL = every member); the others are left as they are.  Afterwards each taken member is as after qldpc_run. */
 int  qldpc_gang_run(qldpc_gang *g, const unsigned char *take /* n flags, NULL = every member */);
 /* of the last qldpc_gang_run: out[0] = sweeps issued, out[1] = layer launches issued, out[2] = layer launches the members would have issued alone
@@ -753,7 +758,9 @@ void   qldpc_qber_cfg_default(qldpc_qber_cfg *cfg);
 int    qldpc_qber_create(const qldpc_code *code, const qldpc_qber_cfg *cfg, qldpc_qber **out);
 void   qldpc_qber_free(qldpc_qber *est);
 size_t qldpc_qber_device_bytes(const qldpc_qber *est);
-int    qldpc_qber_set_stream(qldpc_qber *est, void *hip_stream);      /* NULL = the null stream */
+/* NULL = the null stream.  A switch to another stream orders it after everything the estimator has queued on the old one, its own count rows included;
+ * the same stream again does nothing (the stream switch, qldpc_decoder_set_stream) */
+int    qldpc_qber_set_stream(qldpc_qber *est, void *hip_stream);
 /* Merging on (non-zero) or off, between calls.  The first call that turns it on verifies the chain (QLDPC_EUNSUPPORTED for any other code), builds and
  * uploads the repeat table (a byte per edge) and replaces the score tables and the estimator's own count rows by ones of QLDPC_QBER_MAX_DEGREE + 1 rows; it
  * synchronises the device.  qldpc_qber_count_rows = the rows of d_counts / d_pool_counts as the estimator stands: D + 1, with merging on
@@ -1615,6 +1622,9 @@ int    qldpc_polar_create_rule(int log2_n, int n_info, const int *info_pos, int 
                                qldpc_polar **out);
 void   qldpc_polar_free(qldpc_polar *p);
 size_t qldpc_polar_device_bytes(const qldpc_polar *p);
+/* NULL = the null stream.  A switch to another stream orders it after everything the context has queued on the old one, so two calls of one context on
+ * two streams still share its scratch one after the other; the same stream again does nothing (the stream switch, qldpc_decoder_set_stream).  The same
+ * holds for qldpc_polar_list_set_stream */
 int    qldpc_polar_set_stream(qldpc_polar *p, void *hip_stream);
 int    qldpc_polar_encode_dev(qldpc_polar *p, int n_frames, const uint32_t *d_u, uint32_t *d_x);
 int    qldpc_polar_decode_dev(qldpc_polar *p, int n_frames, const void *d_llr, const uint32_t *d_frozen_u,

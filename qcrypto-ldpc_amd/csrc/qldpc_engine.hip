@@ -566,7 +566,12 @@ static int ensure_post(qldpc_decoder *d)
     return dm_alloc(&d->mem, &d->d_post, (size_t)d->G * d->N * d->FG);
 }
 
-extern "C" int qldpc_decoder_set_stream(qldpc_decoder *d, void *s) { if (!d) return QLDPC_EINVAL; d->stream = (hipStream_t)s; return QLDPC_OK; }
+extern "C" int qldpc_decoder_set_stream(qldpc_decoder *d, void *s)
+{
+    if (!d) return QLDPC_EINVAL;
+    HIPCHK(hipSetDevice(d->device));
+    return qldpc_stream_switch(&d->stream, s);
+}
 extern "C" size_t qldpc_decoder_device_bytes(const qldpc_decoder *d) { return d ? d->mem.dev_bytes : 0; }
 extern "C" int qldpc_decoder_flood_post(const qldpc_decoder *d) { return d ? d->fpost : (int)QLDPC_EINVAL; }
 extern "C" int qldpc_last_run_iterations(const qldpc_decoder *d) { return d ? d->last_iters : (int)QLDPC_EINVAL; }
@@ -1301,8 +1306,10 @@ extern "C" void qldpc_gang_free(qldpc_gang *g) { delete g; }
 extern "C" int qldpc_gang_set_stream(qldpc_gang *g, void *hip_stream)
 {
     if (!g) return QLDPC_EINVAL;
+    HIPCHK(hipSetDevice(g->device));
+    int rc;
+    for (auto *d : g->m) if ((rc = qldpc_stream_switch(&d->stream, hip_stream))) return rc;
     g->stream = (hipStream_t)hip_stream;
-    for (auto *d : g->m) d->stream = g->stream;
     return QLDPC_OK;
 }
 
@@ -1394,11 +1401,9 @@ extern "C" int qldpc_gang_run(qldpc_gang *g, const unsigned char *take)
     if (!left) return QLDPC_OK;
     HIPCHK(hipSetDevice(g->device));
     int rc;
-    /* one stream for the whole gang: a member that was moved to another stream since is waited for there and brought back */
-    for (int i = 0; i < n; i++) {
-        qldpc_decoder *d = g->m[(size_t)i];
-        if (in[i] && d->stream != g->stream) { HIPCHK(hipStreamSynchronize(d->stream)); d->stream = g->stream; }
-    }
+    /* one stream for the whole gang: a member that was moved to another stream since is brought back by the stream switch (qldpc_hip.h) */
+    for (int i = 0; i < n; i++)
+        if (in[i] && (rc = qldpc_stream_switch(&g->m[(size_t)i]->stream, (void *)g->stream))) return rc;
     const int n_ite = g->m[(size_t)first_in]->cfg.n_ite;
     const bool synd = g->m[(size_t)first_in]->cfg.enable_syndrome != 0;
     /* the host looks at the mailboxes every p sweeps, p = the smallest poll_every a member asks for; none asks: every sweep is issued and the

@@ -25,4 +25,23 @@
         if (e__ != hipSuccess) { qldpc_set_error("%s:%d: kernel launch -> %s", __FILE__, __LINE__, hipGetErrorString(e__)); return QLDPC_EHIP; } \
     } while (0)
 
+/*
+ * The stream switch of every context (decoder, gang member, polar, QBER estimator; qldpc.h "stream switch"): *cur becomes `next`, and what the
+ * context has queued on the old stream comes first -- an event recorded on the old stream that `next` waits for, so the call itself waits for
+ * nothing.  The same stream again does nothing at all.  The old stream must still exist.  The caller has set the device.
+ */
+static inline int qldpc_stream_switch(hipStream_t *cur, void *next)
+{
+    hipStream_t to = (hipStream_t)next;
+    if (to == *cur) return QLDPC_OK;
+    hipEvent_t ev = nullptr;
+    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, *cur);
+    if (e == hipSuccess) e = hipStreamWaitEvent(to, ev, 0);
+    (void)hipEventDestroy(ev);      /* released once it has completed: the wait queued above keeps its place */
+    HIPCHK(e);
+    *cur = to;
+    return QLDPC_OK;
+}
+
 #endif /* QLDPC_HIP_H */

@@ -95,8 +95,8 @@ static inline size_t pl_ctx_device_bytes(const pl_ctx *c) { return c ? c->mem.de
 static inline int pl_ctx_set_stream(pl_ctx *c, void *hip_stream)
 {
     if (!c) return QLDPC_EINVAL;
-    c->stream = (hipStream_t)hip_stream;
-    return QLDPC_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return qldpc_stream_switch(&c->stream, hip_stream);
 }
 
 static inline int pl_ctx_check_frames(const pl_ctx *c, int n_frames, const char *who)

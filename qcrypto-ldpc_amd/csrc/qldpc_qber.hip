@@ -128,8 +128,8 @@ extern "C" size_t qldpc_qber_device_bytes(const qldpc_qber *est) { return est ? 
 extern "C" int qldpc_qber_set_stream(qldpc_qber *est, void *hip_stream)
 {
     if (!est) return QLDPC_EINVAL;
-    est->stream = (hipStream_t)hip_stream;
-    return QLDPC_OK;
+    HIPCHK(hipSetDevice(est->cfg.device));
+    return qldpc_stream_switch(&est->stream, hip_stream);
 }
 
 extern "C" int qldpc_qber_count_rows(const qldpc_qber *est) { return est ? (est->merge ? QB_MAX_DEGREE + 1 : est->D + 1) : QLDPC_EINVAL; }
