@@ -47,6 +47,7 @@
  *   qldpc_polar_list_* / _crc_host        the list decoder with a CRC of the fifth curve (list 4, CRC 11)          ML/nrpolar_sclistdecode_FP.m
  *   qldpc_polar_mc_*                      the frame loop of those two scripts around either decoder, on the device   the while loops of the same scripts
  *   qldpc_polar_tally_* / _construct_*    (not in the reference, which reads the 5G sequence) the information set fitted to a channel by genie-aided Monte Carlo
+ *   qldpc_polar_recon_*                   (not in the reference) reconciliation sessions around either polar decoder: syndrome, crc, prior, verdict, leak
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -1779,6 +1780,80 @@ int    qldpc_polar_mc_construct(qldpc_polar_mc *mc, uint64_t first_frame, uint64
 int    qldpc_polar_tally_host(int log2_n, int messages, int maxq, int n_frames, const void *llr, const uint32_t *u_true, uint64_t *tally);
 int    qldpc_polar_construct_order_host(int log2_n, const uint64_t *tally, const int *prior, int *order);
 int    qldpc_polar_construct_k_host(int log2_n, const uint64_t *tally, const int *order, uint64_t max_score_sum, int *k);
+
+/*
+ * Polar codes: reconciliation sessions (qldpc_polar_recon_*) around an existing qldpc_polar context (any form, any rule) or an existing
+ * qldpc_polar_list context with a CRC: Alice's message (syndrome and crc), Bob's prior, decode and verdict, a status per block, the leak.  The rule
+ * is csrc/qldpc_polar_recon_core.h, shared by the kernels (csrc/qldpc_kernels_polar_recon.h), the host mirrors (csrc/qldpc_polar_recon_host.c) and
+ * the session (csrc/qldpc_polar_recon.hip), which agree bit for bit.
+ *
+ * A session belongs to one code (the context's log2_n and info_pos[K]) and one CRC (crc_len 1 .. 32, crc_poly; the list decoder's register form,
+ * above).  A block is a key of key_bits bits, 1 <= key_bits <= N, packed MSB-first in a row of W = ceil(N / 32) words.
+ *   padding   positions key_bits .. N - 1 are 0 for both parties; Alice's side ignores what the caller left there.  (Last-bits shortening with an
+ *             unchanged information set.)  On Alice's side a key_bits outside 1 .. N leaves no bit: the message of the all-zero key.
+ *   Alice     u = encode(x).  syndrome = the bits of u at the frozen positions in ascending position order, packed MSB-first into
+ *             Wf = ceil((N - K) / 32) words, the tail zero.  crc = the remainder over the K bits u[info_pos[m]], m = 0 .. K - 1, the caller's order:
+ *             qldpc_polar_crc_host on the decoder's info row.  Leak: N - K + crc_len bits a block.
+ *   prior     Bob's LLR of position i < key_bits is +prior where y_i = 0 and -prior where y_i = 1; of i >= key_bits it is +pin.  prior and pin are
+ *             the session's, fixed at create: integers 1 <= prior <= pin <= maxq with QLDPC_POLAR_I8, finite 0 < prior <= pin <= 1e30 with
+ *             QLDPC_POLAR_F32 (QLDPC_EINVAL otherwise).  No QBER enters: on a BSC every unknown position has one magnitude, and min-sum f and the
+ *             additive g do not depend on its scale; magnitude 1 leaves an int8 context the most room before sat.  Nothing is computed.
+ *   frozen    Bob's frozen row: the syndrome scattered back to the frozen positions; bits at other positions are 0.
+ *   decode    the context's own qldpc_polar_decode_dev, or qldpc_polar_list_decode_dev with Alice's crc row.
+ *   verdict   status = QLDPC_OK iff the remainder of the decoded info row equals Alice's crc (SC contexts) or pick >= 0 (list contexts), and every
+ *             bit of x^ at positions >= key_bits is 0; QLDPC_EDECODE otherwise.  corrected = popcount((x^ ^ y) over the first key_bits bits) where
+ *             OK, else -1.  Bob's key row becomes x^ where OK and is untouched otherwise.  The picked path is the only one looked at.
+ *             A block whose key_bits is outside 1 .. N: status QLDPC_ESIZE, corrected -1, the key untouched, its LLR row all +pin.
+ *
+ * qldpc_polar_recon_create: exactly one of sc and list (QLDPC_EINVAL; not owned: it must outlive the session).  With list the CRC is the context's:
+ * crc_len and crc_poly must be 0 and a list context without a CRC is refused (QLDPC_EINVAL).  With sc: crc_len outside 1 .. min(32, K) or
+ * polynomial bits above crc_len are QLDPC_ESIZE.  max_blocks = 0 means the context's max_frames; more than that is QLDPC_ESIZE, negative
+ * QLDPC_EINVAL.  The session allocates everything here (LLR rows [max_blocks][N], frozen, x, info and pick rows, two position tables): no later
+ * call allocates.  _syndrome_words: Wf.  _leaked_bits: N - K + crc_len.
+ * qldpc_polar_recon_encode_dev: d_keys [n_blocks][W], d_key_bits [n_blocks] or NULL (every block is N bits) -> d_syndrome [n_blocks][Wf] (may be
+ * NULL when K = N), d_crc [n_blocks].  qldpc_polar_recon_decode_dev: d_keys corrected in place, d_status [n_blocks], d_corrected optional, d_pick
+ * optional and list only (QLDPC_EINVAL with an SC context).  Both are asynchronous on the wrapped context's stream: nothing crosses the host and
+ * the call waits for nothing.  The session is not re-entrant and shares its context's scratch.
+ * n_blocks above max_blocks: QLDPC_ESIZE; negative: QLDPC_EINVAL; a missing pointer: QLDPC_EINVAL; n_blocks = 0 is a no-op.  Every argument check of
+ * every call runs before the first HIP call.
+ *
+ * The building blocks on their own; the _dev forms take a hip_stream (NULL = the null stream) on the current device and no session, the code
+ * arrives as device tables (qldpc_polar_recon_tables_host: frozen_mask [W] 1 = frozen, frozen_prefix [W] the frozen positions before each word,
+ * frozen_pos [N - K] ascending; each may be NULL):
+ *   _prior_dev / _prior_host      keys, key_bits, syndrome -> llr [n_blocks][N] int8 or float (16-byte aligned on the device), frozen [n_blocks][W]
+ *   _verdict_dev / _verdict_host  info [n_blocks][ceil(K/32)], x [n_blocks][W], pick or NULL (then crc_len, crc_poly and crc decide), keys,
+ *                                 key_bits, crc -> status, corrected (optional), keys
+ * qldpc_polar_recon_encode_host and _decode_host: the mirrors of the two session calls, no device; _decode_host runs the host decoder that
+ * (form, rule, list_size) name between the prior mirror and the verdict mirror: list_size = 0 is qldpc_polar_decode_host, _decode_wide_host or
+ * _decode_ssc_host, 1, 2, 4, 8 qldpc_polar_list_decode_host (form = rule = 0); pick is optional and list only.
+ */
+typedef struct qldpc_polar_recon qldpc_polar_recon;
+int    qldpc_polar_recon_create(qldpc_polar *sc, qldpc_polar_list *list, int crc_len, uint32_t crc_poly, double prior, double pin, int max_blocks,
+                                qldpc_polar_recon **out);
+void   qldpc_polar_recon_free(qldpc_polar_recon *r);
+size_t qldpc_polar_recon_device_bytes(const qldpc_polar_recon *r);
+int    qldpc_polar_recon_syndrome_words(const qldpc_polar_recon *r);
+int    qldpc_polar_recon_leaked_bits(const qldpc_polar_recon *r);
+int    qldpc_polar_recon_encode_dev(qldpc_polar_recon *r, int n_blocks, const uint32_t *d_keys, const int *d_key_bits, uint32_t *d_syndrome, uint32_t *d_crc);
+int    qldpc_polar_recon_decode_dev(qldpc_polar_recon *r, int n_blocks, uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_syndrome,
+                                    const uint32_t *d_crc, int *d_status, int *d_corrected, int32_t *d_pick);
+int    qldpc_polar_recon_prior_dev(void *hip_stream, int log2_n, int n_frozen, const uint32_t *d_frozen_mask, const int *d_frozen_prefix, int messages, int maxq,
+                                   double prior, double pin, int n_blocks, const uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_syndrome, void *d_llr,
+                                   uint32_t *d_frozen);
+int    qldpc_polar_recon_verdict_dev(void *hip_stream, int log2_n, int n_info, int crc_len, uint32_t crc_poly, int n_blocks, const uint32_t *d_info,
+                                     const uint32_t *d_x, const int32_t *d_pick, uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_crc, int *d_status,
+                                     int *d_corrected);
+/* host mirrors, no device needed */
+int    qldpc_polar_recon_tables_host(int log2_n, int n_info, const int *info_pos, uint32_t *frozen_mask, int *frozen_prefix, int *frozen_pos);
+int    qldpc_polar_recon_encode_host(int log2_n, int n_info, const int *info_pos, int crc_len, uint32_t crc_poly, int n_blocks, const uint32_t *keys,
+                                     const int *key_bits, uint32_t *syndrome, uint32_t *crc);
+int    qldpc_polar_recon_decode_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int form, int rule, int list_size, int crc_len,
+                                     uint32_t crc_poly, double prior, double pin, int n_blocks, uint32_t *keys, const int *key_bits, const uint32_t *syndrome,
+                                     const uint32_t *crc, int *status, int *corrected, int32_t *pick);
+int    qldpc_polar_recon_prior_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, double prior, double pin, int n_blocks,
+                                    const uint32_t *keys, const int *key_bits, const uint32_t *syndrome, void *llr, uint32_t *frozen);
+int    qldpc_polar_recon_verdict_host(int log2_n, int n_info, int crc_len, uint32_t crc_poly, int n_blocks, const uint32_t *info, const uint32_t *x,
+                                      const int32_t *pick, uint32_t *keys, const int *key_bits, const uint32_t *crc, int *status, int *corrected);
 
 #ifdef __cplusplus
 }

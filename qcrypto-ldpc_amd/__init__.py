@@ -11,9 +11,9 @@ There is NO CPU fallback: if the shared library is missing the import fails loud
 The directory name has a hyphen, so load it with ``_qldpc_loader.load()`` (repo root) which
 registers it as module ``qcrypto_ldpc_amd``.
 """
-from . import _lib, codes, decoder, qber, hashes, mc, recon, polar, polar_mc
+from . import _lib, codes, decoder, qber, hashes, mc, recon, polar, polar_mc, polar_recon
 
 # One module per subsystem, each importing only from _lib and from the modules before it in this list.  The package's names are its
 # modules' names, the private ones included: tests and tools reach _L, _chk, the pointer types and a few helpers as attributes of the package.
-for _m in (_lib, codes, decoder, qber, hashes, mc, recon, polar, polar_mc):
+for _m in (_lib, codes, decoder, qber, hashes, mc, recon, polar, polar_mc, polar_recon):
     globals().update({_k: _v for _k, _v in vars(_m).items() if not _k.startswith("__")})

@@ -1,0 +1,221 @@
+/*
+ * qldpc_polar_recon.hip -- the session object and the launches of qldpc_polar_recon_*: polar reconciliation around an existing qldpc_polar context
+ * (any form, any rule) or an existing qldpc_polar_list context with a CRC.
+ *
+ *     Alice   mask -> the context's encode launch -> syndrome and crc
+ *     Bob     prior and frozen row -> the context's own decode -> verdict
+ *
+ * The rule is qldpc_polar_recon_core.h's, the kernels qldpc_kernels_polar_recon.h's, the mirrors and the shared argument checks
+ * qldpc_polar_recon_host.c's.  Everything is queued on the context's stream; nothing crosses the host and no call waits for anything.
+ *
+ * The session owns, in a ledger of its own, the rows of a call (LLRs, frozen, x, info, pick) and the two tables the context does not have (the
+ * frozen positions in order and the prefix popcounts of the frozen mask), all allocated by create: no call allocates anything.  The frozen mask
+ * and info_pos are the context's, which is not owned and must outlive the session.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <new>
+#include <vector>
+
+#include "qldpc_kernels_polar_recon.h"
+#include "qldpc_polar_ctx.h"
+#include "qldpc_polar_recon_int.h"
+
+struct qldpc_polar_recon {
+    qldpc_polar *sc;
+    qldpc_polar_list *list;
+    const pl_ctx *c;               /* of the one that is given */
+    int crc_len, n_frozen, max_blocks;
+    uint32_t crc_poly;
+    int prior_i, pin_i;            /* the levels: the integers of an int8 context, the floats of a float one */
+    float prior_f, pin_f;
+    size_t Wf, Wi;                 /* words of a syndrome row and of an info row */
+    int *d_fpos, *d_fprefix;
+    uint32_t *d_frozen, *d_x, *d_info;
+    int32_t *d_pick;
+    void *d_llr;
+    dm_ledger mem;                 /* everything create allocates (qldpc_devmem.h) */
+};
+
+extern "C" void qldpc_polar_recon_free(qldpc_polar_recon *r)
+{
+    if (!r) return;
+    if (!r->mem.blocks.empty()) {
+        (void)hipSetDevice(r->c->device);
+        (void)hipStreamSynchronize(r->c->stream);                /* the last call may still read the rows */
+    }
+    dm_free_all(&r->mem);
+    delete r;
+}
+
+template <class T> static int prc_alloc(qldpc_polar_recon *r, T **q, size_t count)
+{
+    if (count == 0) count = 1;                                   /* an empty array still gets one element */
+    const int rc = dm_alloc(&r->mem, q, count);
+    if (rc) qldpc_set_error("polar_recon_create: device allocation of %zu bytes failed: lower max_blocks", sizeof(T) * count);
+    return rc;
+}
+
+static int prc_build(qldpc_polar_recon *r)
+{
+    const pl_ctx *c = r->c;
+    const size_t B = (size_t)r->max_blocks, N = (size_t)1 << c->n, esz = c->messages == QLDPC_POLAR_I8 ? 1 : sizeof(float);
+    int rc;
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = prc_alloc(r, &r->d_fpos, (size_t)r->n_frozen)) || (rc = prc_alloc(r, &r->d_fprefix, c->W)) || (rc = prc_alloc(r, (uint8_t **)&r->d_llr, esz * B * N)) ||
+        (rc = prc_alloc(r, &r->d_frozen, B * c->W)) || (rc = prc_alloc(r, &r->d_x, B * c->W)) || (rc = prc_alloc(r, &r->d_info, B * r->Wi)) ||
+        (rc = prc_alloc(r, &r->d_pick, B)))
+        return rc;
+    /* the two tables from the context's own frozen mask */
+    std::vector<uint32_t> mask(c->W);
+    std::vector<int> fpos((size_t)r->n_frozen + 1), prefix(c->W);
+    HIPCHK(hipMemcpy(mask.data(), c->d_fmask, sizeof(uint32_t) * c->W, hipMemcpyDeviceToHost));
+    if (prc_tables(c->n, mask.data(), prefix.data(), fpos.data()) != r->n_frozen) { qldpc_set_error("polar_recon_create: the context's frozen mask does not hold N - K positions"); return QLDPC_ESTATE; }
+    HIPCHK(hipMemcpy(r->d_fprefix, prefix.data(), sizeof(int) * c->W, hipMemcpyHostToDevice));
+    if (r->n_frozen) HIPCHK(hipMemcpy(r->d_fpos, fpos.data(), sizeof(int) * (size_t)r->n_frozen, hipMemcpyHostToDevice));
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_polar_recon_create(qldpc_polar *sc, qldpc_polar_list *list, int crc_len, uint32_t crc_poly, double prior, double pin, int max_blocks,
+                                        qldpc_polar_recon **out)
+{
+    const char *who = "polar_recon_create";
+    if (!out) return QLDPC_EINVAL;
+    *out = nullptr;
+    if ((sc != nullptr) == (list != nullptr)) { qldpc_set_error("%s: exactly one of an SC context and a list context is required", who); return QLDPC_EINVAL; }
+    int list_len = 0, rc;
+    uint32_t list_poly = 0u;
+    const pl_ctx *c = sc ? pl_ctx_of_sc(sc) : pl_ctx_of_list(list, &list_len, &list_poly);
+    if (list) {
+        if (crc_len || crc_poly) { qldpc_set_error("%s: with a list context the CRC is the context's: crc_len and crc_poly must be 0", who); return QLDPC_EINVAL; }
+        if (list_len == 0) { qldpc_set_error("%s: the list context has no CRC: a session has no verdict without one", who); return QLDPC_EINVAL; }
+        crc_len = list_len; crc_poly = list_poly;
+    } else if ((rc = prc_args_crc(who, crc_len, crc_poly, c->n_info)))
+        return rc;
+    if (max_blocks < 0 || max_blocks > c->max_frames) {
+        qldpc_set_error("%s: max_blocks=%d (0: the context's max_frames = %d, or 1 .. that)", who, max_blocks, c->max_frames);
+        return max_blocks < 0 ? QLDPC_EINVAL : QLDPC_ESIZE;
+    }
+    if (max_blocks == 0) max_blocks = c->max_frames;
+    qldpc_polar_recon *r = new (std::nothrow) qldpc_polar_recon();
+    if (!r) return QLDPC_ENOMEM;
+    if ((rc = prc_args_levels(who, c->messages, c->maxq, prior, pin, &r->prior_i, &r->pin_i, &r->prior_f, &r->pin_f))) { delete r; return rc; }
+    r->sc = sc; r->list = list; r->c = c;
+    r->crc_len = crc_len; r->crc_poly = crc_poly; r->max_blocks = max_blocks;
+    r->n_frozen = (1 << c->n) - c->n_info; r->Wf = pmc_words(r->n_frozen); r->Wi = pmc_words(c->n_info);
+    if ((rc = prc_build(r))) { qldpc_polar_recon_free(r); return rc; }
+    *out = r;
+    return QLDPC_OK;
+}
+
+extern "C" size_t qldpc_polar_recon_device_bytes(const qldpc_polar_recon *r) { return r ? r->mem.dev_bytes : 0; }
+extern "C" int qldpc_polar_recon_syndrome_words(const qldpc_polar_recon *r) { return r ? (int)r->Wf : QLDPC_EINVAL; }
+extern "C" int qldpc_polar_recon_leaked_bits(const qldpc_polar_recon *r) { return r ? r->n_frozen + r->crc_len : QLDPC_EINVAL; }
+
+static unsigned prc_grid(size_t lanes, unsigned per) { return (unsigned)((lanes + per - 1) / per); }
+
+static int prc_check_blocks(const qldpc_polar_recon *r, int n_blocks, const char *who)
+{
+    if (!r) return QLDPC_EINVAL;
+    const int rc = prc_args_count(who, n_blocks);
+    if (rc) return rc;
+    if (n_blocks > r->max_blocks) { qldpc_set_error("%s: n_blocks=%d exceeds the session's max_blocks=%d: create it larger or split the call", who, n_blocks, r->max_blocks); return QLDPC_ESIZE; }
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_polar_recon_encode_dev(qldpc_polar_recon *r, int n_blocks, const uint32_t *d_keys, const int *d_key_bits, uint32_t *d_syndrome, uint32_t *d_crc)
+{
+    const char *who = "polar_recon_encode_dev";
+    int rc = prc_check_blocks(r, n_blocks, who);
+    if (rc || n_blocks == 0) return rc;
+    if (!d_keys || !d_crc || (r->n_frozen && !d_syndrome)) { qldpc_set_error("%s: NULL device pointer", who); return QLDPC_EINVAL; }
+    const pl_ctx *c = r->c;
+    const hipStream_t s = c->stream;
+    const size_t nb = (size_t)n_blocks, total = nb * c->W;
+    HIPCHK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(prc_mask, dim3(prc_grid(total, PRC_LANES)), dim3(PRC_LANES), 0, s, d_keys, d_key_bits, r->d_x, total, c->n, (unsigned)pl_ctz((long)c->W));
+    LAUNCHCHK();
+    if ((rc = pl_launch_encode(s, c->n, nb, r->d_x, r->d_x))) return rc;      /* the launch of qldpc_polar_encode_dev, in place: u */
+    hipLaunchKernelGGL(prc_syndrome, dim3(prc_grid(nb, PRC_SYN_BLOCKS)), dim3(PRC_SYN_LANES), 0, s, (const uint32_t *)r->d_x, (const int *)r->d_fpos,
+                       (const int *)c->d_info_pos, r->d_info, d_syndrome, d_crc, (unsigned)n_blocks, (unsigned)c->W, (unsigned)r->n_frozen, (unsigned)c->n_info, r->crc_len,
+                       r->crc_poly);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+/* the launch of the prior kernel: the caller has checked everything and set the device */
+static int prc_launch_prior(hipStream_t s, int log2_n, int n_frozen, const uint32_t *d_fmask, const int *d_fprefix, bool i8, int pi, int qi, float pf, float qf,
+                            int n_blocks, const uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_syndrome, void *d_llr, uint32_t *d_frozen)
+{
+    const size_t total = (size_t)n_blocks * pmc_quads(log2_n);
+    const unsigned W = (unsigned)pl_words(log2_n), Wf = pmc_words(n_frozen);
+    if (i8)
+        hipLaunchKernelGGL(prc_prior<int>, dim3(prc_grid(total, PRC_LANES)), dim3(PRC_LANES), 0, s, d_keys, d_key_bits, d_syndrome, d_fmask, d_fprefix, d_llr, d_frozen, total,
+                           log2_n, W, Wf, pi, qi);
+    else
+        hipLaunchKernelGGL(prc_prior<float>, dim3(prc_grid(total, PRC_LANES)), dim3(PRC_LANES), 0, s, d_keys, d_key_bits, d_syndrome, d_fmask, d_fprefix, d_llr, d_frozen, total,
+                           log2_n, W, Wf, pf, qf);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+static int prc_launch_verdict(hipStream_t s, int log2_n, int n_info, int crc_len, uint32_t crc_poly, int n_blocks, const uint32_t *d_info, const uint32_t *d_x,
+                              const int32_t *d_pick, uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_crc, int *d_status, int *d_corrected)
+{
+    hipLaunchKernelGGL(prc_verdict, dim3(prc_grid((size_t)n_blocks, PRC_LANES)), dim3(PRC_LANES), 0, s, d_info, d_x, d_pick, d_keys, d_key_bits, d_crc, d_status, d_corrected,
+                       (unsigned)n_blocks, log2_n, n_info, crc_len, crc_poly);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_polar_recon_decode_dev(qldpc_polar_recon *r, int n_blocks, uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_syndrome,
+                                            const uint32_t *d_crc, int *d_status, int *d_corrected, int32_t *d_pick)
+{
+    const char *who = "polar_recon_decode_dev";
+    int rc = prc_check_blocks(r, n_blocks, who);
+    if (rc) return rc;
+    if (d_pick && !r->list) { qldpc_set_error("%s: d_pick is the list decoder's: this session wraps an SC context", who); return QLDPC_EINVAL; }
+    if (n_blocks == 0) return QLDPC_OK;
+    if (!d_keys || !d_crc || !d_status || (r->n_frozen && !d_syndrome)) { qldpc_set_error("%s: NULL device pointer", who); return QLDPC_EINVAL; }
+    const pl_ctx *c = r->c;
+    const hipStream_t s = c->stream;
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = prc_launch_prior(s, c->n, r->n_frozen, c->d_fmask, r->d_fprefix, c->messages == QLDPC_POLAR_I8, r->prior_i, r->pin_i, r->prior_f, r->pin_f, n_blocks, d_keys,
+                               d_key_bits, d_syndrome, r->d_llr, r->d_frozen)))
+        return rc;
+    int32_t *pick = r->list ? (d_pick ? d_pick : r->d_pick) : nullptr;
+    if (r->sc) rc = qldpc_polar_decode_dev(r->sc, n_blocks, r->d_llr, r->d_frozen, nullptr, r->d_info, r->d_x, nullptr);
+    else rc = qldpc_polar_list_decode_dev(r->list, n_blocks, r->d_llr, r->d_frozen, d_crc, nullptr, r->d_info, r->d_x, pick, nullptr, nullptr);
+    if (rc) return rc;
+    return prc_launch_verdict(s, c->n, c->n_info, r->crc_len, r->crc_poly, n_blocks, r->d_info, r->d_x, pick, d_keys, d_key_bits, d_crc, d_status, d_corrected);
+}
+
+/* ---- the building blocks on their own: a stream and the code as device tables, no session; the current device is the caller's ---- */
+
+extern "C" int qldpc_polar_recon_prior_dev(void *hip_stream, int log2_n, int n_frozen, const uint32_t *d_frozen_mask, const int *d_frozen_prefix, int messages, int maxq,
+                                           double prior, double pin, int n_blocks, const uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_syndrome, void *d_llr,
+                                           uint32_t *d_frozen)
+{
+    const char *who = "polar_recon_prior_dev";
+    int pi, qi;
+    float pf, qf;
+    int rc = pl_args_scalars(who, log2_n, PL_MAX_LOG2N, messages, maxq);
+    if (!rc) rc = prc_args_levels(who, messages, maxq, prior, pin, &pi, &qi, &pf, &qf);
+    if (!rc) rc = prc_args_count(who, n_blocks);
+    if (rc) return rc;
+    if (n_frozen < 0 || n_frozen > (1 << log2_n)) { qldpc_set_error("%s: n_frozen=%d (0 .. N = %d)", who, n_frozen, 1 << log2_n); return QLDPC_ESIZE; }
+    if (n_blocks == 0) return QLDPC_OK;
+    if (!d_frozen_mask || !d_frozen_prefix || !d_keys || !d_llr || !d_frozen || (n_frozen && !d_syndrome)) { qldpc_set_error("%s: NULL device pointer", who); return QLDPC_EINVAL; }
+    return prc_launch_prior((hipStream_t)hip_stream, log2_n, n_frozen, d_frozen_mask, d_frozen_prefix, messages == QLDPC_POLAR_I8, pi, qi, pf, qf, n_blocks, d_keys, d_key_bits,
+                            d_syndrome, d_llr, d_frozen);
+}
+
+extern "C" int qldpc_polar_recon_verdict_dev(void *hip_stream, int log2_n, int n_info, int crc_len, uint32_t crc_poly, int n_blocks, const uint32_t *d_info,
+                                             const uint32_t *d_x, const int32_t *d_pick, uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_crc, int *d_status,
+                                             int *d_corrected)
+{
+    const int rc = prc_args_verdict("polar_recon_verdict_dev", log2_n, n_info, crc_len, crc_poly, n_blocks, d_info, d_x, d_pick, d_keys, d_crc, d_status);
+    if (rc || n_blocks == 0) return rc;
+    return prc_launch_verdict((hipStream_t)hip_stream, log2_n, n_info, crc_len, crc_poly, n_blocks, d_info, d_x, d_pick, d_keys, d_key_bits, d_crc, d_status, d_corrected);
+}

@@ -1,0 +1,29 @@
+/*
+ * qldpc_polar_recon_int.h -- the argument checks that the host mirrors of the polar reconciliation sessions (qldpc_polar_recon_host.c, where they
+ * are defined) and the device side (qldpc_polar_recon.hip) share, worded once.  `who` names the call in every message; each returns QLDPC_OK or
+ * the status of the first refusal, with the message set.  None of them touches a device.
+ */
+#ifndef QLDPC_POLAR_RECON_INT_H
+#define QLDPC_POLAR_RECON_INT_H
+
+#include "qldpc_polar_int.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* the session's CRC on a code of n_info bits: crc_len in 1 .. min(32, n_info), crc_poly within crc_len bits (QLDPC_ESIZE) */
+int prc_args_crc(const char *who, int crc_len, uint32_t crc_poly, int n_info);
+/* prior and pin against the messages (qldpc_polar_recon_core.h: prc_levels) -> the two integers and the two floats (QLDPC_EINVAL) */
+int prc_args_levels(const char *who, int messages, int maxq, double prior, double pin, int *pi, int *qi, float *pf, float *qf);
+/* a block count: negative is QLDPC_EINVAL */
+int prc_args_count(const char *who, int n_blocks);
+/* a verdict call: the size, n_info in 0 .. N, the CRC where no pick decides (then info and crc are required too), x, keys and status */
+int prc_args_verdict(const char *who, int log2_n, int n_info, int crc_len, uint32_t crc_poly, int n_blocks, const void *info, const void *x, const void *pick,
+                     const void *keys, const void *crc, const void *status);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* QLDPC_POLAR_RECON_INT_H */
