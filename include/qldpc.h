@@ -48,6 +48,7 @@
  *   qldpc_polar_mc_*                      the frame loop of those two scripts around either decoder, on the device   the while loops of the same scripts
  *   qldpc_polar_tally_* / _construct_*    (not in the reference, which reads the 5G sequence) the information set fitted to a channel by genie-aided Monte Carlo
  *   qldpc_polar_recon_*                   (not in the reference) reconciliation sessions around either polar decoder: syndrome, crc, prior, verdict, leak
+ *   qldpc_polar_decode_rows_* / _recon_*_ladder, _decode_rounds   (not in the reference) a frozen set per frame, and incremental freezing rounds on it
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -1611,6 +1612,17 @@ int    qldpc_mc_guess_next_host(int guess_bits, int batch, uint64_t pool, uint64
  * qldpc_polar_ssc_plan_host: the plan the kernel and the mirror walk: steps[n_steps][3] = (first 32-leaf block, log2 of the leaves, kind: 0 rate
  * 0, 1 rate 1, 2 a mixed block decoded by the same rule inside it) in leaf order; the steps with kind < 2 are the maximal rate-0 and rate-1
  * nodes of 32 leaves or more; for N < 32 one mixed step holds the frame.  steps must hold max(N / 32, 1) x 3 ints.
+ *
+ * The ROWS form of the decode gives every frame a frozen set of its own (csrc/qldpc_kernels_polar_rows.h): what incremental freezing needs, where
+ * a block that failed is decoded again with more positions frozen, and the blocks of one call sit at different rates.
+ * qldpc_polar_decode_rows_dev: qldpc_polar_decode_dev with one more input, d_frozen_rows[n_frames][ceil(N/32)] packed MSB-first like every row,
+ * required (QLDPC_EINVAL).  Position i of frame f is frozen iff the code's mask has it OR bit i of row f is set: a row only adds frozen
+ * positions.  A frozen position takes its value from d_frozen_u, 0 where that is NULL.  d_info still reads u at the context's info_pos, so an
+ * added position returns its frozen value there.  All-zero rows are qldpc_polar_decode_dev bit for bit.  Lanes form and SC rule only: a wide
+ * context (log2_n > 5) and an SSC context are QLDPC_EUNSUPPORTED (the SSC plan belongs to the code, not to a frame).  Every other rule is
+ * qldpc_polar_decode_dev's: outputs optional, the n_frames checks, asynchronous on the context's stream, all checks before the first HIP call.
+ * The cost is one more word load and one OR per lane and 32 leaves; the flags never steer control flow, so a wave of 64 rates does not diverge.
+ * qldpc_polar_decode_rows_host: the mirror, qldpc_polar_decode_host's arguments and refusals plus frozen_rows.
  */
 typedef struct qldpc_polar qldpc_polar;
 enum { QLDPC_POLAR_I8 = 0, QLDPC_POLAR_F32 = 1 };
@@ -1630,10 +1642,14 @@ int    qldpc_polar_set_stream(qldpc_polar *p, void *hip_stream);
 int    qldpc_polar_encode_dev(qldpc_polar *p, int n_frames, const uint32_t *d_u, uint32_t *d_x);
 int    qldpc_polar_decode_dev(qldpc_polar *p, int n_frames, const void *d_llr, const uint32_t *d_frozen_u,
                               uint32_t *d_u, uint32_t *d_info, uint32_t *d_x, void *d_leaf);
+int    qldpc_polar_decode_rows_dev(qldpc_polar *p, int n_frames, const void *d_llr, const uint32_t *d_frozen_u, const uint32_t *d_frozen_rows,
+                                   uint32_t *d_u, uint32_t *d_info, uint32_t *d_x, void *d_leaf);
 /* host mirrors, no device needed */
 int    qldpc_polar_encode_host(int log2_n, int n_frames, const uint32_t *u, uint32_t *x);
 int    qldpc_polar_decode_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
                                const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf);
+int    qldpc_polar_decode_rows_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
+                                    const uint32_t *frozen_u, const uint32_t *frozen_rows, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf);
 int    qldpc_polar_decode_wide_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
                                     const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf);
 int    qldpc_polar_decode_ssc_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
@@ -1854,6 +1870,66 @@ int    qldpc_polar_recon_prior_host(int log2_n, int n_info, const int *info_pos,
                                     const uint32_t *keys, const int *key_bits, const uint32_t *syndrome, void *llr, uint32_t *frozen);
 int    qldpc_polar_recon_verdict_host(int log2_n, int n_info, int crc_len, uint32_t crc_poly, int n_blocks, const uint32_t *info, const uint32_t *x,
                                       const int32_t *pick, uint32_t *keys, const int *key_bits, const uint32_t *crc, int *status, int *corrected);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Polar reconciliation sessions: INCREMENTAL FREEZING.  A block that failed is decoded again with more positions of the same code frozen, to
+ * bits of u that Alice discloses in a fixed public order; only the blocks that failed need it, and the blocks of one call may sit at different
+ * rates.  The rule is csrc/qldpc_polar_ladder_core.h on top of the session's, shared by the kernels (csrc/qldpc_kernels_polar_ladder.h), the
+ * host mirrors (csrc/qldpc_polar_ladder_host.c) and the session, which agree bit for bit.  The CRC still holds: a frozen information position
+ * decodes to Alice's bit.
+ *
+ *   ladder    extra_pos[E], 0 <= E <= K: distinct information positions of the session's code in the order in which they are given up (the caller
+ *             would pass the least reliable first, e.g. the head of qldpc_polar_construct_order_host's order restricted to info_pos).  Per block an
+ *             integer extra in 0 .. E: its first `extra` entries are frozen for that block.  The sets are nested.
+ *   Alice     besides syndrome and crc: extra_bits [n_blocks][We], We = ceil(E / 32), the bits of u at extra_pos[0 .. E), MSB-first, the tail zero.
+ *             She sends a prefix of that row per round; slicing it is the caller's business.
+ *   Bob       a round decodes the OPEN blocks: their LLR rows, frozen values (the syndrome scattered back plus the first extra[b] bits of the
+ *             block's extra_bits row at their positions) and added frozen flags go to slots 0 .. n_open - 1, qldpc_polar_decode_rows_dev runs on
+ *             n_open frames, and slot i's verdict (the session's, unchanged) goes to block open[i].  After a failed decode at extra = e: if e < E
+ *             and another round is allowed, extra <- min(E, e + step) and the block stays open; otherwise it is closed as QLDPC_EDECODE.  No bit of
+ *             an extra_bits row at or beyond the block's extra is looked at: in a real exchange Bob does not have them yet.
+ *   leak      of a block: qldpc_polar_recon_leaked_bits(r) + d_extra[b] as the call returns it.
+ *
+ * qldpc_polar_recon_create_ladder: qldpc_polar_recon_create around an SC context of the lanes form and the SC rule (a wide or an SSC context:
+ * QLDPC_EUNSUPPORTED; there is no list argument, the list decoder has no rows form), plus the ladder.  n_extra outside 0 .. K: QLDPC_ESIZE; an
+ * entry that comes twice or is no information position: QLDPC_EINVAL.  Everything the new calls need is allocated here, in the session's ledger
+ * (the positions, their rank table [N], the flag rows [max_blocks][W], two open lists and their counters); no later call allocates.  The
+ * existing calls work on such a session exactly as on a plain one.  n_extra = 0 is allowed: every call below then behaves as its plain
+ * counterpart.  _extra_words: We (0 for a session without a ladder).
+ * qldpc_polar_recon_encode_ladder_dev: _encode_dev plus d_extra_bits [n_blocks][We] (may be NULL when E = 0).  Asynchronous as _encode_dev.
+ * qldpc_polar_recon_decode_rounds: up to max_rounds rounds.  d_extra [n_blocks] is read and written: with resume = 0 every block with a valid
+ * key_bits is open in round 0 at the d_extra given; with resume = 1 d_status is read on entry and only the blocks whose status is QLDPC_EDECODE
+ * are open, at the d_extra given, and every other block's status, corrected, key and extra are left alone.  A candidate whose key_bits is outside
+ * 1 .. N or whose d_extra is outside 0 .. E gets QLDPC_ESIZE (corrected -1), is never open and is otherwise untouched.  On return d_extra[b] is the
+ * count the block's last decode ran with, d_decodes[b] (optional) its decodes in this call, open_per_round[t] (host, optional, [max_rounds]) the
+ * blocks decoded in round t, 0 from the round in which nothing was open.  With max_rounds = 1 and resume = 1 the call is the protocol's single
+ * round after Alice's next answer: the caller raises d_extra himself.  R rounds in one call are R such calls.
+ * THIS CALL WAITS, the only one of a session that does: the grid of a round needs the open count on the host, one 4-byte read-back per round,
+ * queued on the context's stream and waited for on that stream only, never the device.  The loop ends at the first round with nothing open.
+ * step < 1, max_rounds < 1, resume outside 0 / 1: QLDPC_EINVAL; a session without a ladder: QLDPC_ESTATE; a missing required pointer
+ * (d_keys, d_crc, d_status, d_extra; d_syndrome where K < N; d_extra_bits where E > 0): QLDPC_EINVAL; all before the first HIP call.
+ *
+ * The mirrors, no device: _encode_ladder_host and _decode_rounds_host take the code and the ladder explicitly and run qldpc_polar_decode_rows_host.
+ * qldpc_polar_recon_ladder_extra_host -> a starting count for a block of key_bits bits at a given QBER, or a negative status: the count at which
+ * the block has leaked f times the Slepian-Wolf bound, clamp(ceil(f h2(qber) key_bits) - (N - K), 0, n_extra).  A pure function; the session
+ * never calls it and nothing gets a default.  QLDPC_ESIZE: the sizes; QLDPC_EINVAL: qber outside 0 .. 0.5, f outside 0 .. 1e6.
+ */
+int    qldpc_polar_recon_create_ladder(qldpc_polar *sc, int crc_len, uint32_t crc_poly, double prior, double pin, int max_blocks, int n_extra,
+                                       const int *extra_pos, qldpc_polar_recon **out);
+int    qldpc_polar_recon_extra_words(const qldpc_polar_recon *r);
+int    qldpc_polar_recon_encode_ladder_dev(qldpc_polar_recon *r, int n_blocks, const uint32_t *d_keys, const int *d_key_bits, uint32_t *d_syndrome,
+                                           uint32_t *d_crc, uint32_t *d_extra_bits);
+int    qldpc_polar_recon_decode_rounds(qldpc_polar_recon *r, int n_blocks, uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_syndrome,
+                                       const uint32_t *d_crc, const uint32_t *d_extra_bits, int *d_extra, int step, int max_rounds, int resume,
+                                       int *d_status, int *d_corrected, int *d_decodes, int *open_per_round);
+/* host mirrors, no device needed */
+int    qldpc_polar_recon_encode_ladder_host(int log2_n, int n_info, const int *info_pos, int crc_len, uint32_t crc_poly, int n_extra, const int *extra_pos,
+                                            int n_blocks, const uint32_t *keys, const int *key_bits, uint32_t *syndrome, uint32_t *crc, uint32_t *extra_bits);
+int    qldpc_polar_recon_decode_rounds_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int crc_len, uint32_t crc_poly, double prior,
+                                            double pin, int n_extra, const int *extra_pos, int n_blocks, uint32_t *keys, const int *key_bits,
+                                            const uint32_t *syndrome, const uint32_t *crc, const uint32_t *extra_bits, int *extra, int step, int max_rounds,
+                                            int resume, int *status, int *corrected, int *decodes, int *open_per_round);
+int    qldpc_polar_recon_ladder_extra_host(int log2_n, int n_info, int n_extra, int key_bits, double qber, double f);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,9 @@
  *
  * qldpc_polar_tally_dev (the genie-aided construction, qldpc_polar_tally_core.h) is the lanes' decode in its tally form
  * (qldpc_kernels_polar_tally.h): pl_load, then pl_tally on the same scratch, into an accumulator that is the caller's.
+ *
+ * qldpc_polar_decode_rows_dev is the lanes' SC decode with a frozen set per frame (qldpc_kernels_polar_rows.h): pl_load, pl_decode_rows in
+ * pl_decode's place on the same scratch, pl_outputs.
  */
 #include <hip/hip_runtime.h>
 
@@ -26,6 +29,7 @@
 #include <new>
 #include <type_traits>
 
+#include "qldpc_kernels_polar_rows.h"
 #include "qldpc_kernels_polar_ssc.h"
 #include "qldpc_kernels_polar_tally.h"
 #include "qldpc_kernels_polar_wide.h"
@@ -44,6 +48,7 @@ struct qldpc_polar {
 
 const pl_ctx *pl_ctx_of_sc(const qldpc_polar *p) { return &p->c; }
 bool pl_sc_is_wide(const qldpc_polar *p) { return p->wide; }
+int pl_sc_rule(const qldpc_polar *p) { return p->rule; }
 
 extern "C" void qldpc_polar_free(qldpc_polar *p)
 {
@@ -244,6 +249,18 @@ static int plw_run_decode(const qldpc_polar *p, M m, int n_frames, const void *d
     return QLDPC_OK;
 }
 
+/* the rows the caller asked for of a lanes decode, from the scratch */
+static int pl_run_outputs(const qldpc_polar *p, int n_frames, uint32_t *d_u, uint32_t *d_info, uint32_t *d_x)
+{
+    if (d_u || d_info || d_x) {
+        const size_t groups = ((size_t)n_frames + PL_GROUP - 1) / PL_GROUP, threads = groups * p->c.W * PL_GROUP;
+        hipLaunchKernelGGL(pl_outputs, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, p->c.stream, p->c.n, n_frames, p->c.n_info, (const int *)p->c.d_info_pos,
+                           (const uint32_t *)p->d_U, (const uint32_t *)p->d_X, d_u, d_info, d_x);
+        LAUNCHCHK();
+    }
+    return QLDPC_OK;
+}
+
 extern "C" int qldpc_polar_decode_dev(qldpc_polar *p, int n_frames, const void *d_llr, const uint32_t *d_frozen_u, uint32_t *d_u, uint32_t *d_info,
                                       uint32_t *d_x, void *d_leaf)
 {
@@ -258,13 +275,60 @@ extern "C" int qldpc_polar_decode_dev(qldpc_polar *p, int n_frames, const void *
     if (p->wide) return pl_with_messages(&p->c, [&](auto m) { return plw_run_decode(p, m, n_frames, d_llr, d_frozen_u, d_u, d_info, d_x, d_leaf); });
     rc = pl_with_messages(&p->c, [&](auto m) { return pl_run_decode(p, m, n_frames, d_llr, d_frozen_u, d_leaf, d_u || d_info); });
     if (rc) return rc;
-    if (d_u || d_info || d_x) {
-        const size_t groups = ((size_t)n_frames + PL_GROUP - 1) / PL_GROUP, threads = groups * p->c.W * PL_GROUP;
-        hipLaunchKernelGGL(pl_outputs, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, p->c.stream, p->c.n, n_frames, p->c.n_info, (const int *)p->c.d_info_pos,
-                           (const uint32_t *)p->d_U, (const uint32_t *)p->d_X, d_u, d_info, d_x);
+    return pl_run_outputs(p, n_frames, d_u, d_info, d_x);
+}
+
+template <class M, int SL, bool TOP>
+static void pl_launch_rows(const qldpc_polar *p, M m, int n_frames, unsigned groups, const void *d_llr, const uint32_t *d_frozen_u, const uint32_t *d_frozen_rows,
+                           void *d_leaf)
+{
+    typedef typename M::mem mem;
+    hipLaunchKernelGGL((pl_decode_rows<M, SL, TOP>), dim3(groups), dim3(PL_GROUP), 0, p->c.stream, m, p->c.n, n_frames, (const mem *)d_llr,
+                       (const uint32_t *)p->c.d_fmask, d_frozen_u, d_frozen_rows, (mem *)p->d_B, p->d_U, p->d_X, (mem *)d_leaf);
+}
+
+template <class M>
+static int pl_run_rows(const qldpc_polar *p, M m, int n_frames, const void *d_llr, const uint32_t *d_frozen_u, const uint32_t *d_frozen_rows, void *d_leaf)
+{
+    typedef typename M::mem mem;
+    const int n = p->c.n;
+    const unsigned groups = (unsigned)(((size_t)n_frames + PL_GROUP - 1) / PL_GROUP);
+    if (n > PL_SUB_LOG) {
+        const size_t tiles = ((size_t)1 << n) / 64u;
+        hipLaunchKernelGGL(pl_load<M>, dim3((unsigned)(groups * tiles)), dim3(256), 0, p->c.stream, m, n, n_frames, (const mem *)d_llr, (mem *)p->d_B);
         LAUNCHCHK();
     }
+    switch (n) {
+    case 1: pl_launch_rows<M, 1, true>(p, m, n_frames, groups, d_llr, d_frozen_u, d_frozen_rows, d_leaf); break;
+    case 2: pl_launch_rows<M, 2, true>(p, m, n_frames, groups, d_llr, d_frozen_u, d_frozen_rows, d_leaf); break;
+    case 3: pl_launch_rows<M, 3, true>(p, m, n_frames, groups, d_llr, d_frozen_u, d_frozen_rows, d_leaf); break;
+    case 4: pl_launch_rows<M, 4, true>(p, m, n_frames, groups, d_llr, d_frozen_u, d_frozen_rows, d_leaf); break;
+    case 5: pl_launch_rows<M, 5, true>(p, m, n_frames, groups, d_llr, d_frozen_u, d_frozen_rows, d_leaf); break;
+    default: pl_launch_rows<M, 5, false>(p, m, n_frames, groups, d_llr, d_frozen_u, d_frozen_rows, d_leaf); break;
+    }
+    LAUNCHCHK();
     return QLDPC_OK;
+}
+
+extern "C" int qldpc_polar_decode_rows_dev(qldpc_polar *p, int n_frames, const void *d_llr, const uint32_t *d_frozen_u, const uint32_t *d_frozen_rows,
+                                           uint32_t *d_u, uint32_t *d_info, uint32_t *d_x, void *d_leaf)
+{
+    int rc = pl_ctx_check_frames(PL_CTX(p), n_frames, "polar_decode_rows_dev");
+    if (rc) return rc;
+    if (p->wide) {
+        qldpc_set_error("polar_decode_rows_dev: the rows decode has no wide form: create a QLDPC_POLAR_LANES context of the same size and messages for it");
+        return QLDPC_EUNSUPPORTED;
+    }
+    if (p->rule == QLDPC_POLAR_SSC) {
+        qldpc_set_error("polar_decode_rows_dev: the rows decode has no SSC rule (the plan of pruned nodes belongs to the code, not to a frame): create a QLDPC_POLAR_SC context for it");
+        return QLDPC_EUNSUPPORTED;
+    }
+    if (n_frames == 0) return QLDPC_OK;
+    if (!d_llr || !d_frozen_rows) { qldpc_set_error("polar_decode_rows_dev: NULL device pointer (d_llr and d_frozen_rows are required)"); return QLDPC_EINVAL; }
+    HIPCHK(hipSetDevice(p->c.device));
+    rc = pl_with_messages(&p->c, [&](auto m) { return pl_run_rows(p, m, n_frames, d_llr, d_frozen_u, d_frozen_rows, d_leaf); });
+    if (rc) return rc;
+    return pl_run_outputs(p, n_frames, d_u, d_info, d_x);
 }
 
 template <class M, int SL, bool TOP>

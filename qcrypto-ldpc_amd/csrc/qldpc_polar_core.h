@@ -56,6 +56,8 @@ PL_FN float pl_f32_f(float a, float b)
 PL_FN float pl_f32_g(float a, float b, unsigned c) { return c ? b - a : b + a; }
 /* a leaf's decision from its belief's sign (neg = L < 0), its frozen flag and its frozen value */
 PL_FN unsigned pl_leaf_bit(unsigned neg, unsigned frozen, unsigned value) { return frozen ? value : neg; }
+/* the frozen flags of a leaf block of one frame in the rows form: the code's word, and what the frame's own row adds to it (a row never thaws) */
+PL_FN uint32_t pl_rows_frozen(uint32_t code_word, uint32_t row_word) { return code_word | row_word; }
 
 /* ---- the encoder ---- */
 /* the stages m = 1 .. 2^(sub_log - 1) of a word whose top 2^sub_log bits are in use (sub_log <= 5) */

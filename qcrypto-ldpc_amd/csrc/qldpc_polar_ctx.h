@@ -26,10 +26,12 @@ struct pl_ctx {
 };
 #define PL_CTX(p) ((p) ? &(p)->c : nullptr)
 
-/* for the Monte-Carlo loop (qldpc_polar_mc.hip), which runs around a context it does not own: the context's pl_ctx, whether an SC context
-   decodes in the wide form, and a list decoder's CRC.  Defined beside the two structs, in qldpc_polar.hip and qldpc_polar_list.hip */
+/* for the Monte-Carlo loop (qldpc_polar_mc.hip) and the sessions (qldpc_polar_recon.hip), which run around a context they do not own: the
+   context's pl_ctx, whether an SC context decodes in the wide form, its rule, and a list decoder's CRC.  Defined beside the two structs, in
+   qldpc_polar.hip and qldpc_polar_list.hip */
 const pl_ctx *pl_ctx_of_sc(const qldpc_polar *p);
 bool pl_sc_is_wide(const qldpc_polar *p);
+int pl_sc_rule(const qldpc_polar *p);
 const pl_ctx *pl_ctx_of_list(const qldpc_polar_list *p, int *crc_len, uint32_t *crc_poly);
 
 /* the only allocation of a context: `bytes` at *q (left NULL for 0 bytes), in the ledger; alloc_failed around dm_alloc */

@@ -1,5 +1,6 @@
 /*
- * qldpc_polar_host.c -- the host mirrors of the polar encoder and SC decoder (qldpc_polar_encode_host, qldpc_polar_decode_host): plain C over the
+ * qldpc_polar_host.c -- the host mirrors of the polar encoder and SC decoder (qldpc_polar_encode_host, qldpc_polar_decode_host, and
+ * qldpc_polar_decode_rows_host with a frozen set per frame): plain C over the
  * functions of qldpc_polar_core.h, one frame at a time, in the order the lanes of qldpc_kernels_polar.h work: leaf block by leaf block, the levels
  * above a block in a scratch of 2N - 1 beliefs, the levels inside it by the core's recursion, the re-encoded word of every finished node in the x
  * row.  And the argument checks of a code (qldpc_polar_int.h), which every unit of the subsystem calls.
@@ -101,21 +102,27 @@ static size_t pl_off(int n, int l) { return ((size_t)2 << n) - ((size_t)2 << l);
     }
 PL_HOST_MESSAGES(PL_HOST_DECODER)
 
-int qldpc_polar_decode_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
-                            const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf)
+/* the two SC mirrors: with_rows = 0 is the code's frozen set for every frame, otherwise frozen_rows is [n_frames][W], each frame's additions to it */
+static int pl_decode_frames(const char *who, int with_rows, int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
+                            const uint32_t *frozen_u, const uint32_t *frozen_rows, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf)
 {
     uint32_t *mask;
-    const int rc = pl_host_decode_args("polar_decode_host", log2_n, n_info, info_pos, messages, maxq, n_frames, llr, &mask);
+    const int rc = pl_host_decode_args(who, log2_n, n_info, info_pos, messages, maxq, n_frames, llr, &mask);
     if (rc) return rc;
+    if (with_rows && n_frames > 0 && !frozen_rows) { qldpc_set_error("%s: frozen_rows is NULL", who); free(mask); return QLDPC_EINVAL; }
     const long N = 1l << log2_n, W = pl_words(log2_n), Wi = (n_info + 31) / 32;
     void *B = malloc((messages == QLDPC_POLAR_I8 ? sizeof(int) : sizeof(float)) * 2 * (size_t)N);
-    uint32_t *rows = (uint32_t *)malloc(sizeof(uint32_t) * 2 * (size_t)W);
+    uint32_t *rows = (uint32_t *)malloc(sizeof(uint32_t) * 3 * (size_t)W);
     if (!B || !rows) { free(B); free(rows); free(mask); return QLDPC_ENOMEM; }
-    uint32_t *uf = rows, *xf = rows + W;
+    uint32_t *uf = rows, *xf = rows + W, *ff = rows + 2 * W;
     for (long f = 0; f < n_frames; f++) {
-        const uint32_t *fval = frozen_u ? frozen_u + f * W : NULL;
-        if (messages == QLDPC_POLAR_I8) pl_decode_i8(log2_n, maxq, (const int8_t *)llr + f * N, mask, fval, (int *)B, uf, xf, leaf ? (int8_t *)leaf + f * N : NULL);
-        else pl_decode_f32(log2_n, maxq, (const float *)llr + f * N, mask, fval, (float *)B, uf, xf, leaf ? (float *)leaf + f * N : NULL);
+        const uint32_t *fval = frozen_u ? frozen_u + f * W : NULL, *fz = mask;
+        if (with_rows) {
+            for (long w = 0; w < W; w++) ff[w] = pl_rows_frozen(mask[w], frozen_rows[f * W + w]);
+            fz = ff;
+        }
+        if (messages == QLDPC_POLAR_I8) pl_decode_i8(log2_n, maxq, (const int8_t *)llr + f * N, fz, fval, (int *)B, uf, xf, leaf ? (int8_t *)leaf + f * N : NULL);
+        else pl_decode_f32(log2_n, maxq, (const float *)llr + f * N, fz, fval, (float *)B, uf, xf, leaf ? (float *)leaf + f * N : NULL);
         if (u) memcpy(u + f * W, uf, sizeof(uint32_t) * (size_t)W);
         if (x) memcpy(x + f * W, xf, sizeof(uint32_t) * (size_t)W);
         if (info)
@@ -123,4 +130,16 @@ int qldpc_polar_decode_host(int log2_n, int n_info, const int *info_pos, int mes
     }
     free(B); free(rows); free(mask);
     return QLDPC_OK;
+}
+
+int qldpc_polar_decode_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
+                            const uint32_t *frozen_u, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf)
+{
+    return pl_decode_frames("polar_decode_host", 0, log2_n, n_info, info_pos, messages, maxq, n_frames, llr, frozen_u, NULL, u, info, x, leaf);
+}
+
+int qldpc_polar_decode_rows_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int n_frames, const void *llr,
+                                 const uint32_t *frozen_u, const uint32_t *frozen_rows, uint32_t *u, uint32_t *info, uint32_t *x, void *leaf)
+{
+    return pl_decode_frames("polar_decode_rows_host", 1, log2_n, n_info, info_pos, messages, maxq, n_frames, llr, frozen_u, frozen_rows, u, info, x, leaf);
 }

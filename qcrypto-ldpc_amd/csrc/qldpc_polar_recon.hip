@@ -11,6 +11,14 @@
  * The session owns, in a ledger of its own, the rows of a call (LLRs, frozen, x, info, pick) and the two tables the context does not have (the
  * frozen positions in order and the prefix popcounts of the frozen mask), all allocated by create: no call allocates anything.  The frozen mask
  * and info_pos are the context's, which is not owned and must outlive the session.
+ *
+ * A session made by qldpc_polar_recon_create_ladder (SC contexts of the lanes form) also owns a ladder (qldpc_polar_ladder_core.h): its positions
+ * and their rank table, the added-flag rows of a round, two open lists and their two counters.  qldpc_polar_recon_decode_rounds runs
+ *
+ *     entry -> per round: read the open count back | slot prior -> the rows form of the SC decode -> slot verdict and the next round's list
+ *
+ * with the kernels of qldpc_kernels_polar_ladder.h.  The grid of a round needs the open count on the host: one 4-byte read-back per round, queued
+ * on the context's stream and waited for on that stream alone.  It is the one call of a session that waits.
  */
 #include <hip/hip_runtime.h>
 
@@ -18,6 +26,7 @@
 #include <new>
 #include <vector>
 
+#include "qldpc_kernels_polar_ladder.h"
 #include "qldpc_kernels_polar_recon.h"
 #include "qldpc_polar_ctx.h"
 #include "qldpc_polar_recon_int.h"
@@ -35,6 +44,13 @@ struct qldpc_polar_recon {
     uint32_t *d_frozen, *d_x, *d_info;
     int32_t *d_pick;
     void *d_llr;
+    bool has_ladder;               /* made by _create_ladder: what follows is set */
+    int n_extra;
+    size_t We;                     /* words of Alice's extra row */
+    int *d_extra_pos, *d_rank;     /* the ladder [n_extra] and its rank table [N] */
+    uint32_t *d_flags;             /* the added frozen flags of a round's slots, max_blocks x W */
+    int *d_open, *d_count;         /* two open lists of max_blocks blocks and their two counters: round t fills those of round t + 1 */
+    int h_open;                    /* where a round's count is read back to */
     dm_ledger mem;                 /* everything create allocates (qldpc_devmem.h) */
 };
 
@@ -218,4 +234,129 @@ extern "C" int qldpc_polar_recon_verdict_dev(void *hip_stream, int log2_n, int n
     const int rc = prc_args_verdict("polar_recon_verdict_dev", log2_n, n_info, crc_len, crc_poly, n_blocks, d_info, d_x, d_pick, d_keys, d_crc, d_status);
     if (rc || n_blocks == 0) return rc;
     return prc_launch_verdict((hipStream_t)hip_stream, log2_n, n_info, crc_len, crc_poly, n_blocks, d_info, d_x, d_pick, d_keys, d_key_bits, d_crc, d_status, d_corrected);
+}
+
+/* ---- incremental freezing: a session with a ladder (qldpc_polar_ladder_core.h) ---- */
+
+extern "C" int qldpc_polar_recon_create_ladder(qldpc_polar *sc, int crc_len, uint32_t crc_poly, double prior, double pin, int max_blocks, int n_extra,
+                                               const int *extra_pos, qldpc_polar_recon **out)
+{
+    const char *who = "polar_recon_create_ladder";
+    if (!out) return QLDPC_EINVAL;
+    *out = nullptr;
+    if (!sc) { qldpc_set_error("%s: an SC context is required (the list decoder has no rows form)", who); return QLDPC_EINVAL; }
+    if (pl_sc_is_wide(sc) || pl_sc_rule(sc) != QLDPC_POLAR_SC) {
+        qldpc_set_error("%s: the rows decode of a ladder session has neither a wide form nor an SSC rule (the SSC plan belongs to the code, not to a block): "
+                        "create a QLDPC_POLAR_LANES context of the QLDPC_POLAR_SC rule for it", who);
+        return QLDPC_EUNSUPPORTED;
+    }
+    const pl_ctx *c = pl_ctx_of_sc(sc);
+    if (n_extra < 0 || n_extra > c->n_info) { qldpc_set_error("%s: n_extra=%d (0 .. n_info = %d)", who, n_extra, c->n_info); return QLDPC_ESIZE; }
+    if (n_extra > 0 && !extra_pos) { qldpc_set_error("%s: extra_pos is NULL", who); return QLDPC_EINVAL; }
+    qldpc_polar_recon *r = nullptr;
+    int rc = qldpc_polar_recon_create(sc, nullptr, crc_len, crc_poly, prior, pin, max_blocks, &r);
+    if (rc) return rc;
+    const size_t N = (size_t)1 << c->n, B = (size_t)r->max_blocks;
+    std::vector<uint32_t> mask(c->W);
+    std::vector<int> rank(N);
+    hipError_t e = hipMemcpy(mask.data(), c->d_fmask, sizeof(uint32_t) * c->W, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { qldpc_set_error("%s: %s", who, hipGetErrorString(e)); rc = QLDPC_EHIP; }
+    if (!rc) rc = pld_args_ladder(who, c->n, mask.data(), c->n_info, n_extra, extra_pos, rank.data());
+    if (!rc && !((rc = prc_alloc(r, &r->d_extra_pos, (size_t)n_extra)) || (rc = prc_alloc(r, &r->d_rank, N)) || (rc = prc_alloc(r, &r->d_flags, B * c->W)) ||
+                 (rc = prc_alloc(r, &r->d_open, 2 * B)) || (rc = prc_alloc(r, &r->d_count, (size_t)2)))) {
+        e = hipMemcpy(r->d_rank, rank.data(), sizeof(int) * N, hipMemcpyHostToDevice);
+        if (e == hipSuccess && n_extra) e = hipMemcpy(r->d_extra_pos, extra_pos, sizeof(int) * (size_t)n_extra, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { qldpc_set_error("%s: %s", who, hipGetErrorString(e)); rc = QLDPC_EHIP; }
+    }
+    if (rc) { qldpc_polar_recon_free(r); return rc; }
+    r->has_ladder = true; r->n_extra = n_extra; r->We = pld_extra_words(n_extra);
+    *out = r;
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_polar_recon_extra_words(const qldpc_polar_recon *r) { return r ? (r->has_ladder ? (int)r->We : 0) : QLDPC_EINVAL; }
+
+static int pld_check_ladder(const qldpc_polar_recon *r, const char *who)
+{
+    if (r->has_ladder) return QLDPC_OK;
+    qldpc_set_error("%s: the session has no ladder: make it with qldpc_polar_recon_create_ladder", who);
+    return QLDPC_ESTATE;
+}
+
+extern "C" int qldpc_polar_recon_encode_ladder_dev(qldpc_polar_recon *r, int n_blocks, const uint32_t *d_keys, const int *d_key_bits, uint32_t *d_syndrome,
+                                                   uint32_t *d_crc, uint32_t *d_extra_bits)
+{
+    const char *who = "polar_recon_encode_ladder_dev";
+    int rc = prc_check_blocks(r, n_blocks, who);
+    if (!rc) rc = pld_check_ladder(r, who);
+    if (rc || n_blocks == 0) return rc;
+    if (r->n_extra && !d_extra_bits) { qldpc_set_error("%s: NULL device pointer (d_extra_bits)", who); return QLDPC_EINVAL; }
+    if ((rc = qldpc_polar_recon_encode_dev(r, n_blocks, d_keys, d_key_bits, d_syndrome, d_crc))) return rc;      /* leaves u in the session's row */
+    if (r->n_extra) {
+        hipLaunchKernelGGL(pld_extra_rows, dim3(prc_grid((size_t)n_blocks, PRC_LANES / 64u)), dim3(PRC_LANES), 0, r->c->stream, (const uint32_t *)r->d_x,
+                           (const int *)r->d_extra_pos, d_extra_bits, (unsigned)n_blocks, (unsigned)r->c->W, (unsigned)r->n_extra);
+        LAUNCHCHK();
+    }
+    return QLDPC_OK;
+}
+
+/* the slot prior of a round: the open list's first n_open blocks into slots 0 .. n_open - 1 */
+static int pld_launch_slot_prior(const qldpc_polar_recon *r, const int *d_open, int n_open, const uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_syndrome,
+                                 const uint32_t *d_extra_bits, const int *d_extra, int *d_decodes)
+{
+    const pl_ctx *c = r->c;
+    const size_t total = (size_t)n_open * pmc_quads(c->n);
+    if (c->messages == QLDPC_POLAR_I8)
+        hipLaunchKernelGGL(pld_slot_prior<int>, dim3(prc_grid(total, PRC_LANES)), dim3(PRC_LANES), 0, c->stream, d_open, d_keys, d_key_bits, d_syndrome, d_extra_bits, d_extra,
+                           (const uint32_t *)c->d_fmask, (const int *)r->d_fprefix, (const int *)r->d_rank, r->d_llr, r->d_frozen, r->d_flags, d_decodes, total, c->n,
+                           (unsigned)c->W, (unsigned)r->Wf, (unsigned)r->We, r->prior_i, r->pin_i);
+    else
+        hipLaunchKernelGGL(pld_slot_prior<float>, dim3(prc_grid(total, PRC_LANES)), dim3(PRC_LANES), 0, c->stream, d_open, d_keys, d_key_bits, d_syndrome, d_extra_bits, d_extra,
+                           (const uint32_t *)c->d_fmask, (const int *)r->d_fprefix, (const int *)r->d_rank, r->d_llr, r->d_frozen, r->d_flags, d_decodes, total, c->n,
+                           (unsigned)c->W, (unsigned)r->Wf, (unsigned)r->We, r->prior_f, r->pin_f);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_polar_recon_decode_rounds(qldpc_polar_recon *r, int n_blocks, uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_syndrome,
+                                               const uint32_t *d_crc, const uint32_t *d_extra_bits, int *d_extra, int step, int max_rounds, int resume,
+                                               int *d_status, int *d_corrected, int *d_decodes, int *open_per_round)
+{
+    const char *who = "polar_recon_decode_rounds";
+    int rc = prc_check_blocks(r, n_blocks, who);
+    if (!rc) rc = pld_args_rounds(who, step, max_rounds, resume);
+    if (!rc) rc = pld_check_ladder(r, who);
+    if (rc) return rc;
+    if (n_blocks > 0 && (!d_keys || !d_crc || !d_status || !d_extra || (r->n_frozen && !d_syndrome) || (r->n_extra && !d_extra_bits))) {
+        qldpc_set_error("%s: NULL device pointer (d_keys, d_crc, d_status and d_extra are required; d_syndrome where N > K, d_extra_bits where n_extra > 0)", who);
+        return QLDPC_EINVAL;
+    }
+    for (int t = 0; open_per_round && t < max_rounds; t++) open_per_round[t] = 0;
+    if (n_blocks == 0) return QLDPC_OK;
+    const pl_ctx *c = r->c;
+    const hipStream_t s = c->stream;
+    const size_t B = (size_t)r->max_blocks;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemsetAsync(r->d_count, 0, 2 * sizeof(int), s));
+    hipLaunchKernelGGL(pld_entry_blocks, dim3(prc_grid((size_t)n_blocks, PRC_LANES)), dim3(PRC_LANES), 0, s, d_key_bits, (const int *)d_extra, d_status, d_corrected, d_decodes,
+                       r->d_open, r->d_count, (unsigned)n_blocks, c->n, r->n_extra, resume);
+    LAUNCHCHK();
+    for (int t = 0; t < max_rounds; t++) {
+        const int cur = t & 1, nxt = cur ^ 1;
+        HIPCHK(hipMemcpyAsync(&r->h_open, r->d_count + cur, sizeof(int), hipMemcpyDeviceToHost, s));      /* the ONE read-back of the round */
+        HIPCHK(hipStreamSynchronize(s));
+        const int n_open = r->h_open;
+        if (n_open < 0 || n_open > n_blocks) { qldpc_set_error("%s: the open count %d of round %d is not in 0 .. n_blocks = %d", who, n_open, t, n_blocks); return QLDPC_ESTATE; }
+        if (n_open == 0) break;
+        if (open_per_round) open_per_round[t] = n_open;
+        const int *open = r->d_open + (size_t)cur * B;
+        HIPCHK(hipMemsetAsync(r->d_count + nxt, 0, sizeof(int), s));
+        if ((rc = pld_launch_slot_prior(r, open, n_open, d_keys, d_key_bits, d_syndrome, d_extra_bits, d_extra, d_decodes))) return rc;
+        if ((rc = qldpc_polar_decode_rows_dev(r->sc, n_open, r->d_llr, r->d_frozen, r->d_flags, nullptr, r->d_info, r->d_x, nullptr))) return rc;
+        hipLaunchKernelGGL(pld_slot_verdict, dim3(prc_grid((size_t)n_open, PRC_LANES)), dim3(PRC_LANES), 0, s, open, (const uint32_t *)r->d_info, (const uint32_t *)r->d_x,
+                           d_keys, d_key_bits, d_crc, d_extra, d_status, d_corrected, r->d_open + (size_t)nxt * B, r->d_count + nxt, (unsigned)n_open, c->n, c->n_info,
+                           r->crc_len, r->crc_poly, r->n_extra, step, t, max_rounds);
+        LAUNCHCHK();
+    }
+    return QLDPC_OK;
 }

@@ -22,6 +22,12 @@ int prc_args_count(const char *who, int n_blocks);
 int prc_args_verdict(const char *who, int log2_n, int n_info, int crc_len, uint32_t crc_poly, int n_blocks, const void *info, const void *x, const void *pick,
                      const void *keys, const void *crc, const void *status);
 
+/* a ladder (qldpc_polar_ladder_core.h: pld_rank_table; defined in qldpc_polar_ladder_host.c) against the code's frozen mask -> rank[N]: n_extra outside
+   0 .. n_info is QLDPC_ESIZE, an entry that is no information position or comes twice QLDPC_EINVAL */
+int pld_args_ladder(const char *who, int log2_n, const uint32_t *fmask, int n_info, int n_extra, const int *extra_pos, int *rank);
+/* the scalars of a rounds call: step >= 1, max_rounds >= 1, resume 0 or 1 (QLDPC_EINVAL) */
+int pld_args_rounds(const char *who, int step, int max_rounds, int resume);
+
 #ifdef __cplusplus
 }
 #endif

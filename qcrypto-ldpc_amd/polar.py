@@ -23,8 +23,10 @@ _sig("qldpc_polar_device_bytes", C.c_size_t, [_vp])
 _sig("qldpc_polar_set_stream", C.c_int, [_vp, _vp])
 _sig("qldpc_polar_encode_dev", C.c_int, [_vp, C.c_int, _vp, _vp])
 _sig("qldpc_polar_decode_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp])
+_sig("qldpc_polar_decode_rows_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 _sig("qldpc_polar_encode_host", C.c_int, [C.c_int, C.c_int, _up, _up])
 _sig("qldpc_polar_decode_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _vp, _up, _up, _up, _up, _vp])
+_sig("qldpc_polar_decode_rows_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _vp, _up, _up, _up, _up, _up, _vp])
 _sig("qldpc_polar_decode_wide_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _vp, _up, _up, _up, _up, _vp])
 _sig("qldpc_polar_decode_ssc_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _vp, _up, _up, _up, _up])
 _sig("qldpc_polar_ssc_plan_host", C.c_int, [C.c_int, C.c_int, _ip, _ip, _ip])
@@ -133,6 +135,25 @@ def polar_decode_host(log2_n, info_pos, llr, frozen=None, messages="i8", maxq=31
 def polar_decode_wide_host(log2_n, info_pos, llr, frozen=None, messages="i8", maxq=31, leaf=False):
     """the host walk of the wide form's memory plan (qldpc_polar_decode_wide_host): the arguments and the results of polar_decode_host, bit for bit"""
     return _decode_host(_L.qldpc_polar_decode_wide_host, "polar_decode_wide_host", log2_n, info_pos, llr, frozen, messages, maxq, leaf)
+
+
+def polar_decode_rows_host(log2_n, info_pos, llr, rows, frozen=None, messages="i8", maxq=31, leaf=False):
+    """the rows decode's mirror (qldpc_polar_decode_rows_host): polar_decode_host with a frozen set per frame, rows uint32 [F, ceil(N/32)]: a set
+    bit freezes that position of that frame on top of the code's frozen set (to its bit of `frozen`, 0 without one) -> the dict of
+    polar_decode_host"""
+    who = "polar_decode_rows_host"
+    kind, dt, pos, llr, fz, n, N, W, F = _host_rows(who, log2_n, POLAR_MAX_LOG2N, info_pos, llr, frozen, messages)
+    rw = None
+    if rows is not None:
+        rw = np.ascontiguousarray(rows, dtype=np.uint32)
+        if rw.shape != (F, W):
+            raise QldpcError(-6, "%s: rows must be [frames, %d] words" % (who, W))
+    out = dict(u=np.zeros((F, W), np.uint32), info=np.zeros((F, (pos.size + 31) // 32), np.uint32), x=np.zeros((F, W), np.uint32))
+    if leaf:
+        out["leaf"] = np.zeros((F, N), dt)
+    _chk(_L.qldpc_polar_decode_rows_host(n, pos.size, pos.ctypes.data_as(_ip), kind, int(maxq), F, llr.ctypes.data_as(_vp), _ptr(fz, _up), _ptr(rw, _up),
+                                         _ptr(out["u"], _up), _ptr(out["info"], _up), _ptr(out["x"], _up), _ptr(out.get("leaf"), _vp)), who)
+    return out
 
 
 def polar_decode_ssc_host(log2_n, info_pos, llr, frozen=None, messages="i8", maxq=31):
@@ -279,6 +300,18 @@ class Polar(_PolarCode):
             out["leaf"] = _dev_empty(llr.device, (F, self.N), llr.dtype)
         self._on_current_stream()
         _chk(_L.qldpc_polar_decode_dev(self._h, F, pl, pf, ptr("u"), ptr("info"), ptr("x"), ptr("leaf")), "Polar.decode")
+        return out
+
+    def decode_rows(self, llr, rows, frozen=None, leaf=False, want=("u", "info", "x")):
+        """decode() with a frozen set per frame (qldpc_polar_decode_rows_dev): rows int32 / uint32 [F, W], a set bit freezes that position of
+        that frame on top of the code's frozen set, to its bit of `frozen` (0 without one) -> the dict of decode().  Lanes form, SC rule"""
+        torch, F, pl, pf = self._decode_inputs(llr, frozen)
+        pr = _dev_rows(rows, F, self.W, (torch.int32, torch.uint32), "rows")
+        out, ptr = self._outputs(llr.device, dict(u=((F, self.W), torch.int32), info=((F, self.Wi), torch.int32), x=((F, self.W), torch.int32)), want)
+        if leaf:
+            out["leaf"] = _dev_empty(llr.device, (F, self.N), llr.dtype)
+        self._on_current_stream()
+        _chk(_L.qldpc_polar_decode_rows_dev(self._h, F, pl, pf, pr, ptr("u"), ptr("info"), ptr("x"), ptr("leaf")), "Polar.decode_rows")
         return out
 
     def tally(self, llr, u_true, out=None):

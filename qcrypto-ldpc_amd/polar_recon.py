@@ -24,6 +24,14 @@ _sig("qldpc_polar_recon_decode_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, 
                                                C.c_int, _up, _ip, _up, _up, _ip, _ip, _ip])
 _sig("qldpc_polar_recon_prior_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _up, _ip, _up, _vp, _up])
 _sig("qldpc_polar_recon_verdict_host", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, _up, _up, _ip, _up, _ip, _up, _ip, _ip])
+_sig("qldpc_polar_recon_create_ladder", C.c_int, [_vp, C.c_int, C.c_uint32, C.c_double, C.c_double, C.c_int, C.c_int, _ip, C.POINTER(_vp)])
+_sig("qldpc_polar_recon_extra_words", C.c_int, [_vp])
+_sig("qldpc_polar_recon_encode_ladder_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp])
+_sig("qldpc_polar_recon_decode_rounds", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _ip])
+_sig("qldpc_polar_recon_encode_ladder_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_uint32, C.c_int, _ip, C.c_int, _up, _ip, _up, _up, _up])
+_sig("qldpc_polar_recon_decode_rounds_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_double, C.c_double, C.c_int, _ip, C.c_int,
+                                                      _up, _ip, _up, _up, _up, _ip, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip])
+_sig("qldpc_polar_recon_ladder_extra_host", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double])
 
 
 def _levels(kind, maxq, prior, pin):
@@ -133,6 +141,56 @@ def polar_recon_verdict_host(log2_n, n_info, info, x, keys, crc=None, pick=None,
     return out
 
 
+# ---- incremental freezing: the mirrors ------------------------------------------------------------------------------------------------------
+
+def polar_recon_encode_ladder_host(log2_n, info_pos, extra_pos, keys, key_bits=None, crc_len=0, crc_poly=0):
+    """Alice's mirror with a ladder (qldpc_polar_recon_encode_ladder_host): extra_pos int32 [E] the disclosure order
+    -> (syndrome, crc, extra_bits uint32 [B, ceil(E / 32)]: the bits of u at extra_pos, MSB-first)"""
+    who = "polar_recon_encode_ladder_host"
+    n, N, W, pos = _code(log2_n, info_pos)
+    xp = np.ascontiguousarray(extra_pos, dtype=np.int32).ravel()
+    keys = _rows(who, keys, W, "keys")
+    B = keys.shape[0]
+    kb = _vec(who, key_bits, B, "key_bits", np.int32)
+    syn, crc, xb = np.zeros((B, (max(N - pos.size, 0) + 31) // 32), np.uint32), np.zeros(B, np.uint32), np.zeros((B, (xp.size + 31) // 32), np.uint32)
+    _chk(_L.qldpc_polar_recon_encode_ladder_host(n, pos.size, pos.ctypes.data_as(_ip), int(crc_len), int(crc_poly) & 0xffffffff, xp.size, xp.ctypes.data_as(_ip), B,
+                                                 keys.ctypes.data_as(_up), _ptr(kb, _ip), syn.ctypes.data_as(_up), crc.ctypes.data_as(_up), xb.ctypes.data_as(_up)), who)
+    return syn, crc, xb
+
+
+def polar_recon_decode_rounds_host(log2_n, info_pos, extra_pos, keys, syndrome, crc, extra_bits, extra, step=16, max_rounds=1, key_bits=None, resume=False,
+                                   status=None, messages="i8", maxq=31, crc_len=0, crc_poly=0, prior=None, pin=None):
+    """Bob's rounds mirror (qldpc_polar_recon_decode_rounds_host): extra int32 [B] the start counts, status int32 [B] read with resume
+    -> dict(keys (a copy, corrected where OK), status, corrected, extra (the count of each block's last decode), decodes, open_per_round int32
+    [max_rounds]); with resume the rows of the blocks that are not open come back as they were given (corrected: -1 where none was given)"""
+    who = "polar_recon_decode_rounds_host"
+    kind, _ = _messages(messages)
+    n, N, W, pos = _code(log2_n, info_pos)
+    xp = np.ascontiguousarray(extra_pos, dtype=np.int32).ravel()
+    keys = _rows(who, keys, W, "keys").copy()
+    B = keys.shape[0]
+    syn, xb = _rows(who, syndrome, (max(N - pos.size, 0) + 31) // 32, "syndrome"), _rows(who, extra_bits, (xp.size + 31) // 32, "extra_bits")
+    cr, kb = _vec(who, crc, B, "crc", np.uint32), _vec(who, key_bits, B, "key_bits", np.int32)
+    ex = _vec(who, extra, B, "extra", np.int32).copy()
+    st = np.zeros(B, np.int32) if status is None else _vec(who, status, B, "status", np.int32).copy()
+    if resume and status is None:
+        raise QldpcError(-1, "%s: resume needs the status of the call before" % who)
+    p, q = _levels(kind, maxq, prior, pin)
+    out = dict(keys=keys, status=st, corrected=np.full(B, -1, np.int32), extra=ex, decodes=np.zeros(B, np.int32),
+               open_per_round=np.zeros(max(int(max_rounds), 1), np.int32))
+    _chk(_L.qldpc_polar_recon_decode_rounds_host(n, pos.size, pos.ctypes.data_as(_ip), kind, int(maxq), int(crc_len), int(crc_poly) & 0xffffffff, p, q, xp.size,
+                                                 xp.ctypes.data_as(_ip), B, keys.ctypes.data_as(_up), _ptr(kb, _ip), _ptr(syn, _up), _ptr(cr, _up), _ptr(xb, _up),
+                                                 ex.ctypes.data_as(_ip), int(step), int(max_rounds), int(resume), st.ctypes.data_as(_ip),
+                                                 out["corrected"].ctypes.data_as(_ip), out["decodes"].ctypes.data_as(_ip), out["open_per_round"].ctypes.data_as(_ip)), who)
+    return out
+
+
+def polar_recon_ladder_extra(log2_n, n_info, n_extra, key_bits, qber, f=1.0):
+    """a starting count for a block of key_bits bits at a given QBER (qldpc_polar_recon_ladder_extra_host): clamp(ceil(f h2(qber) key_bits) -
+    (N - K), 0, n_extra).  A suggestion: no session calls it"""
+    return _chk(_L.qldpc_polar_recon_ladder_extra_host(int(log2_n), int(n_info), int(n_extra), int(key_bits), float(qber), float(f)), "polar_recon_ladder_extra")
+
+
 def _up_dev(a, device=0):
     """a host array on the device (uint32 words as int32); None stays None"""
     if a is None:
@@ -191,12 +249,20 @@ class PolarRecon(_Handle):
     tensors out, asynchronous on torch's current stream."""
     _free = _L.qldpc_polar_recon_free
 
-    def __init__(self, decoder, crc_len=0, crc_poly=0, prior=None, pin=None, max_blocks=0):
+    def __init__(self, decoder, crc_len=0, crc_poly=0, prior=None, pin=None, max_blocks=0, extra_pos=None):
         is_list = isinstance(decoder, PolarList)
         self.decoder = decoder
         self.prior, self.pin = _levels(decoder.messages, decoder.maxq, prior, pin)
-        self._h = _create("PolarRecon", _L.qldpc_polar_recon_create, None if is_list else decoder._h, decoder._h if is_list else None, int(crc_len),
-                          int(crc_poly) & 0xffffffff, self.prior, self.pin, int(max_blocks))
+        self.extra_pos = None if extra_pos is None else np.ascontiguousarray(extra_pos, dtype=np.int32).ravel()
+        if self.extra_pos is not None:      # a ladder session (incremental freezing): an SC Polar of the lanes form only
+            if is_list:
+                raise QldpcError(-7, "PolarRecon: a ladder session needs an SC Polar (the list decoder has no rows form)")
+            self._h = _create("PolarRecon", _L.qldpc_polar_recon_create_ladder, decoder._h, int(crc_len), int(crc_poly) & 0xffffffff, self.prior, self.pin,
+                              int(max_blocks), self.extra_pos.size, self.extra_pos.ctypes.data_as(_ip))
+        else:
+            self._h = _create("PolarRecon", _L.qldpc_polar_recon_create, None if is_list else decoder._h, decoder._h if is_list else None, int(crc_len),
+                              int(crc_poly) & 0xffffffff, self.prior, self.pin, int(max_blocks))
+        self.extra_words = int(_L.qldpc_polar_recon_extra_words(self._h))
         self.max_blocks = int(max_blocks) or decoder.max_frames
         self.crc_len, self.crc_poly = (decoder.crc_len, decoder.crc_poly) if is_list else (int(crc_len), int(crc_poly))
         self.syndrome_words = int(_L.qldpc_polar_recon_syndrome_words(self._h))
@@ -210,12 +276,17 @@ class PolarRecon(_Handle):
         pk = _dev_rows(keys, None, self.decoder.W, (torch.int32, torch.uint32), "keys")
         return torch, keys.shape[0], pk, _dev_vec(key_bits, keys.shape[0], torch.int32, "key_bits")
 
-    def encode(self, keys, key_bits=None):
+    def encode(self, keys, key_bits=None, want_extra=False):
         """Alice: keys int32 / uint32 [B, W] packed rows on the device, key_bits int32 [B] or None (every block is N bits)
-        -> (syndrome int32 [B, syndrome_words], crc int32 [B]) on the device"""
+        -> (syndrome int32 [B, syndrome_words], crc int32 [B]) on the device and, with want_extra (a ladder session), extra_bits int32
+        [B, extra_words]: the bits of u at extra_pos, of which she sends a prefix per round"""
         torch, B, pk, pb = self._inputs(keys, key_bits)
         syn, crc = _dev_empty(keys.device, (B, self.syndrome_words), torch.int32), _dev_empty(keys.device, (B,), torch.int32)
         self.decoder._on_current_stream()
+        if want_extra:
+            xb = _dev_empty(keys.device, (B, self.extra_words), torch.int32)
+            _chk(_L.qldpc_polar_recon_encode_ladder_dev(self._h, B, pk, pb, _p(syn), _p(crc), _p(xb)), "PolarRecon.encode")
+            return syn, crc, xb
         _chk(_L.qldpc_polar_recon_encode_dev(self._h, B, pk, pb, _p(syn), _p(crc)), "PolarRecon.encode")
         return syn, crc
 
@@ -233,4 +304,30 @@ class PolarRecon(_Handle):
         self.decoder._on_current_stream()
         _chk(_L.qldpc_polar_recon_decode_dev(self._h, B, pk, pb, ps, _vp(crc.data_ptr()), _p(out["status"]), _p(out["corrected"]), _p(out.get("pick"))),
              "PolarRecon.decode")
+        return out
+
+    def decode_rounds(self, keys, syndrome, crc, extra_bits, extra, step=16, max_rounds=1, key_bits=None, resume=False, status=None):
+        """Bob, incremental freezing (a ladder session; qldpc_polar_recon_decode_rounds): up to max_rounds rounds over the blocks that are open,
+        each failed block frozen `step` positions further along extra_pos before its next decode.  keys [B, W] corrected IN PLACE where a block
+        is OK; extra int32 [B] the start counts, rewritten IN PLACE to the count of each block's last decode; extra_bits [B, extra_words] Alice's
+        row, of which only the first extra[b] bits of a block are looked at; resume: `status` int32 [B] of the call before is read and rewritten
+        IN PLACE, and only its EDECODE blocks are open.  THIS CALL WAITS for the stream once a round (the open count)
+        -> dict(status, corrected, decodes int32 [B] on the device, open_per_round: a list of max_rounds ints)"""
+        torch, B, pk, pb = self._inputs(keys, key_bits)
+        words = (torch.int32, torch.uint32)
+        ps = _dev_rows(syndrome, B, self.syndrome_words, words, "syndrome") if self.syndrome_words else None
+        px = _dev_rows(extra_bits, B, self.extra_words, words, "extra_bits") if self.extra_words else None
+        assert crc.is_cuda and crc.dtype in words and crc.is_contiguous() and tuple(crc.shape) == (B,), "crc"
+        pe = _dev_vec(extra, B, torch.int32, "extra")
+        if resume and status is None:
+            raise QldpcError(-1, "PolarRecon.decode_rounds: resume needs the status of the call before")
+        st = _dev_empty(keys.device, (B,), torch.int32) if status is None else status
+        _dev_vec(st, B, torch.int32, "status")
+        out = dict(status=st, corrected=torch.full((B,), -1, dtype=torch.int32, device=keys.device) if resume else _dev_empty(keys.device, (B,), torch.int32),
+                   decodes=_dev_empty(keys.device, (B,), torch.int32))
+        rounds = (C.c_int * max(int(max_rounds), 1))()
+        self.decoder._on_current_stream()
+        _chk(_L.qldpc_polar_recon_decode_rounds(self._h, B, pk, pb, ps, _vp(crc.data_ptr()), px, pe, int(step), int(max_rounds), int(resume), _p(st),
+                                                _p(out["corrected"]), _p(out["decodes"]), rounds), "PolarRecon.decode_rounds")
+        out["open_per_round"] = list(rounds)
         return out
