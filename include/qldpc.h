@@ -49,6 +49,7 @@
  *   qldpc_polar_tally_* / _construct_*    (not in the reference, which reads the 5G sequence) the information set fitted to a channel by genie-aided Monte Carlo
  *   qldpc_polar_recon_*                   (not in the reference) reconciliation sessions around either polar decoder: syndrome, crc, prior, verdict, leak
  *   qldpc_polar_decode_rows_* / _recon_*_ladder, _decode_rounds   (not in the reference) a frozen set per frame, and incremental freezing rounds on it
+ *   qldpc_polar_recon_*_flip / qldpc_polar_flip_select_*   (not in the reference) SC-Flip trials for the blocks of a session that failed
  */
 #ifndef QLDPC_H
 #define QLDPC_H
@@ -1904,7 +1905,7 @@ int    qldpc_polar_recon_verdict_host(int log2_n, int n_info, int crc_len, uint3
  * count the block's last decode ran with, d_decodes[b] (optional) its decodes in this call, open_per_round[t] (host, optional, [max_rounds]) the
  * blocks decoded in round t, 0 from the round in which nothing was open.  With max_rounds = 1 and resume = 1 the call is the protocol's single
  * round after Alice's next answer: the caller raises d_extra himself.  R rounds in one call are R such calls.
- * THIS CALL WAITS, the only one of a session that does: the grid of a round needs the open count on the host, one 4-byte read-back per round,
+ * THIS CALL WAITS (of a session's calls only this one and qldpc_polar_recon_decode_flip do): the grid of a round needs the open count on the host, one 4-byte read-back per round,
  * queued on the context's stream and waited for on that stream only, never the device.  The loop ends at the first round with nothing open.
  * step < 1, max_rounds < 1, resume outside 0 / 1: QLDPC_EINVAL; a session without a ladder: QLDPC_ESTATE; a missing required pointer
  * (d_keys, d_crc, d_status, d_extra; d_syndrome where K < N; d_extra_bits where E > 0): QLDPC_EINVAL; all before the first HIP call.
@@ -1930,6 +1931,69 @@ int    qldpc_polar_recon_decode_rounds_host(int log2_n, int n_info, const int *i
                                             const uint32_t *syndrome, const uint32_t *crc, const uint32_t *extra_bits, int *extra, int step, int max_rounds,
                                             int resume, int *status, int *corrected, int *decodes, int *open_per_round);
 int    qldpc_polar_recon_ladder_extra_host(int log2_n, int n_info, int n_extra, int key_bits, double qber, double f);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Polar reconciliation sessions: SC-FLIP TRIALS (Afisiadis, Balatsoukas-Stimming, Burg 2014).  A block whose decode failed the verdict is
+ * decoded again with the decision at one of its T least reliable information leaves inverted; the first trial that passes the verdict is kept.
+ * Local to Bob: no packet, and the leak of a block is what it was.  Successive cancellation is causal, so "decode with the decision at p
+ * inverted" is "decode with p frozen to the inverse of SC's decision": a trial is one more frame of qldpc_polar_decode_rows_dev.  The rule is
+ * csrc/qldpc_polar_flip_core.h on top of the ladder's and the session's, shared by the kernels (csrc/qldpc_kernels_polar_flip.h), the host
+ * mirrors (csrc/qldpc_polar_flip_host.c) and the session, which agree bit for bit.
+ *
+ *   candidate  position i of a block: the code does not freeze it and the block's ladder count does not add it.
+ *   key        (mag << 32) | i.  int8 leaves: mag = |leaf| (0 .. 127).  float leaves: mag = the bit pattern of fabsf(leaf); -0.0 and +0.0 give 0.
+ *   flips      the T smallest keys of the block, ascending: ties in magnitude go to the lower position (with a BSC prior ties are the normal
+ *              case; the order is part of the contract).  With fewer than T candidates the remaining entries are -1: void.
+ *   trial t    the block's inputs plus position p_t frozen to (leaf[p_t] >= 0), the inverse of SC's decision (leaf < 0).  A void trial is never
+ *              accepted.
+ *   settle     the winner is the lowest t whose trial passes the session's verdict test (CRC match and clean pad).  The block then is QLDPC_OK,
+ *              its key row that trial's x^, corrected the flips against Bob's row, flip_pos = p_t.  Without a winner: QLDPC_EDECODE, the key
+ *              untouched, corrected -1, flip_pos -1.  Either way the block's decode count goes up by 1 + T (a probe and T trials).
+ *   THE PRICE  a block now meets up to 1 + T CRC tests, so the chance that a wrong key passes is bounded by (1 + T) 2^-crc_len instead of
+ *              2^-crc_len.  Use a CRC-32, or verify with a keyed tag afterwards (qldpc_polyhash_*).
+ *
+ * qldpc_polar_recon_create_flip: qldpc_polar_recon_create_ladder (its arguments, its refusals; n_extra = 0 is allowed and the common case) plus
+ * the scratch of the trials.  max_flips not a power of two in 1 .. 32: QLDPC_EINVAL; above max_blocks (0: the context's max_frames): QLDPC_ESIZE.
+ * The trials of a call live in the rows its blocks live in (LLR, frozen, flags, info and x rows [max_blocks][..]), so a call with n_flips = T
+ * takes the open blocks in chunks of C = max_blocks / T.  Besides those the session owns, in its ledger, the leaf rows of one chunk's probe and
+ * the flips of its trials.  The leaf buffer is sized for the worst case a call can meet, n_flips = 1 where a chunk is max_blocks blocks:
+ * [max_blocks][N] leaves; the flips are C T <= max_blocks entries.  No later call allocates.  Every existing call works on such a session as on
+ * a ladder session.  _max_flips: the session's max_flips, 0 for any other session.
+ * qldpc_polar_recon_decode_flip: with resume = 0 every block with a valid key_bits and count is decoded once at its d_extra, exactly
+ * qldpc_polar_recon_decode_rounds with max_rounds = 1, and the blocks that fail form the open list; with resume = 1 d_status is read and the open
+ * list is the blocks whose status is QLDPC_EDECODE; every other block is left alone but for its decode count (0) and flip_pos (-1), so the call
+ * composes after _decode_dev or _decode_rounds.  A candidate with a key_bits outside 1 .. N or a count outside 0 .. n_extra gets QLDPC_ESIZE as
+ * there.  The open blocks then go chunk by chunk through: slot prior, a probe (the failed decode again, for its leaf beliefs: the first pass
+ * stays the existing call's and no leaf row is kept for the blocks that pass), select, trial prior on C T slots, rows decode, settle.  d_extra
+ * [n_blocks] is only read, NULL = all 0.  d_flip_pos [n_blocks] is required: -1 for every block not rescued by a flip, the blocks that were OK
+ * at once included.  d_corrected and d_decodes are optional; n_tried (host, optional) = the open count.  THIS CALL WAITS ONCE: one 4-byte
+ * read-back of the open count on the context's stream; after it everything is queued and the call returns.  Chunking shows in no output.
+ * n_flips not a power of two or resume outside 0 / 1: QLDPC_EINVAL; n_flips above the session's max_flips: QLDPC_ESIZE; a session not made by
+ * _create_flip: QLDPC_ESTATE; a missing required pointer (d_keys, d_crc, d_status, d_flip_pos; d_syndrome where K < N; d_extra_bits where
+ * n_extra > 0): QLDPC_EINVAL; all before the first HIP call.
+ *
+ * The select on its own: qldpc_polar_flip_select_dev (hip_stream, NULL = the null stream, on the current device) and _host: d_leaf
+ * [n_frames][N] int8 or float as qldpc_polar_decode_dev's d_leaf gives them (16-byte aligned on the device), d_frozen_mask [W] (1 = frozen),
+ * d_rank [N] a ladder's rank table or NULL (no ladder), d_extra [n_frames] or NULL (all 0; not looked at without d_rank) -> d_pos
+ * [n_frames][n_flips]; n_flips a power of two (QLDPC_EINVAL) up to 32 (QLDPC_ESIZE).  T successive minima of the key, not a radix select: T is small and the output is an ordered list.
+ * qldpc_polar_recon_decode_flip_host: the mirror, _decode_rounds_host's code and ladder arguments plus n_flips, resume and flip_pos; it runs
+ * qldpc_polar_decode_rows_host, a block at a time, with no device and no chunking.
+ */
+int    qldpc_polar_recon_create_flip(qldpc_polar *sc, int crc_len, uint32_t crc_poly, double prior, double pin, int max_blocks, int n_extra,
+                                     const int *extra_pos, int max_flips, qldpc_polar_recon **out);
+int    qldpc_polar_recon_max_flips(const qldpc_polar_recon *r);
+int    qldpc_polar_recon_decode_flip(qldpc_polar_recon *r, int n_blocks, uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_syndrome,
+                                     const uint32_t *d_crc, const uint32_t *d_extra_bits, const int *d_extra, int n_flips, int resume, int *d_status,
+                                     int *d_corrected, int32_t *d_flip_pos, int *d_decodes, int *n_tried);
+int    qldpc_polar_flip_select_dev(void *hip_stream, int log2_n, int messages, int n_frames, const void *d_leaf, const uint32_t *d_frozen_mask,
+                                   const int *d_rank, const int *d_extra, int n_flips, int *d_pos);
+/* host mirrors, no device needed */
+int    qldpc_polar_flip_select_host(int log2_n, int messages, int n_frames, const void *leaf, const uint32_t *frozen_mask, const int *rank,
+                                    const int *extra, int n_flips, int *pos);
+int    qldpc_polar_recon_decode_flip_host(int log2_n, int n_info, const int *info_pos, int messages, int maxq, int crc_len, uint32_t crc_poly, double prior,
+                                          double pin, int n_extra, const int *extra_pos, int n_blocks, uint32_t *keys, const int *key_bits,
+                                          const uint32_t *syndrome, const uint32_t *crc, const uint32_t *extra_bits, const int *extra, int n_flips, int resume,
+                                          int *status, int *corrected, int32_t *flip_pos, int *decodes, int *n_tried);
 
 #ifdef __cplusplus
 }

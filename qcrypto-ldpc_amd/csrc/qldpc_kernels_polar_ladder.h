@@ -8,7 +8,7 @@
  *   pld_slot_prior   Bob, every round: prc_prior for slot s = block open[s], a lane per quad of positions.  Besides the LLR quad and its four bits
  *                    of the frozen row (the syndrome's, or Alice's extra row where the block's count adds the position) the lane forms its four
  *                    added flags; the eight lanes of a word OR both together by shuffles every lane of the wave takes part in.  The first lane of
- *                    a slot counts the decode.
+ *                    a slot counts the decode.  Its body is pld_slot_prior_lane, which the flip trials share (qldpc_kernels_polar_flip.h).
  *   pld_slot_verdict Bob, every round: a lane per slot, prc_verdict_block on the slot's info and x rows and the block's key, crc and key_bits.
  *                    A block that failed and stays open gets its next count and is appended to the NEXT round's open list.
  *
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(PRC_LANES) void pld_extra_rows(const uint32_t *__re
     prc_gather_row(u + f * W, extra_pos, E, extra_bits + f * We, lane);
 }
 
-/* key_bits [n] or NULL, extra [n], status [n] (read with resume) -> status, corrected (or NULL) of the refused, decodes [n] (or NULL) = 0, the
+/* key_bits [n] or NULL, extra [n] or NULL (every count 0), status [n] (read with resume) -> status, corrected (or NULL) of the refused, decodes [n] (or NULL) = 0, the
    open list and *count (zero before) */
 __global__ __launch_bounds__(PRC_LANES) void pld_entry_blocks(const int *__restrict__ key_bits, const int *__restrict__ extra, int *__restrict__ status,
                                                               int *__restrict__ corrected, int *__restrict__ decodes, int *__restrict__ open, int *__restrict__ count,
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(PRC_LANES) void pld_entry_blocks(const int *__restr
     const size_t b = (size_t)blockIdx.x * PRC_LANES + threadIdx.x;
     int what = PLD_KEEP;
     if (b < n) {
-        what = pld_entry(resume, resume ? status[b] : 0, key_bits ? key_bits[b] : 1 << log2_n, log2_n, extra[b], n_extra);
+        what = pld_entry(resume, resume ? status[b] : 0, key_bits ? key_bits[b] : 1 << log2_n, log2_n, extra ? extra[b] : 0, n_extra);
         if (decodes) decodes[b] = 0;
         if (what == PLD_REFUSE) {
             status[b] = PRC_ESIZE;
@@ -64,23 +64,18 @@ __global__ __launch_bounds__(PRC_LANES) void pld_entry_blocks(const int *__restr
     pld_append(what == PLD_OPEN, (int)b, open, count);
 }
 
-/* slot s = block open[s]: keys, key_bits, syn, xbits [.][We], extra of the block -> llr [n_open][N], frozen [n_open][W], flags [n_open][W];
-   total = n_open quads lanes.  rank: the ladder's table [N] */
+/* The slot prior of one lane, a quad of positions: slot s takes the inputs of block b.  Every lane of the wave calls it (the shuffles), active or
+   not.  flip >= 0: position `flip` of the slot is frozen besides, to flip_bit (a flip trial, qldpc_kernels_polar_flip.h); -1: nothing more */
 template <class T>
-__global__ __launch_bounds__(PRC_LANES) void pld_slot_prior(const int *__restrict__ open, const uint32_t *__restrict__ keys, const int *__restrict__ key_bits,
-                                                            const uint32_t *__restrict__ syn, const uint32_t *__restrict__ xbits, const int *__restrict__ extra,
-                                                            const uint32_t *__restrict__ fmask, const int *__restrict__ fprefix, const int *__restrict__ rank,
-                                                            void *__restrict__ llr, uint32_t *__restrict__ frozen, uint32_t *__restrict__ flags, int *__restrict__ decodes,
-                                                            size_t total, int log2_n, unsigned W, unsigned Wf, unsigned We, T prior, T pin)
+__device__ static inline void pld_slot_prior_lane(bool active, size_t s, unsigned q, size_t b, int flip, unsigned flip_bit, const uint32_t *__restrict__ keys,
+                                                  const int *__restrict__ key_bits, const uint32_t *__restrict__ syn, const uint32_t *__restrict__ xbits,
+                                                  const int *__restrict__ extra, const uint32_t *__restrict__ fmask, const int *__restrict__ fprefix,
+                                                  const int *__restrict__ rank, void *__restrict__ llr, uint32_t *__restrict__ frozen, uint32_t *__restrict__ flags,
+                                                  int *__restrict__ decodes, int log2_n, unsigned W, unsigned Wf, unsigned We, T prior, T pin)
 {
-    const size_t i = (size_t)blockIdx.x * PRC_LANES + threadIdx.x;
     const unsigned lq = log2_n >= 2 ? (unsigned)log2_n - 2u : 0u, Qn = 1u << lq, group = Qn < 8u ? Qn : 8u;      /* lanes of a frozen word */
-    const bool active = i < total;
-    const size_t s = active ? i >> lq : 0u;
-    const unsigned q = (unsigned)(i & (Qn - 1u));
     uint32_t fz = 0u, fl = 0u;
     if (active) {
-        const size_t b = (size_t)open[s];
         const int kb = prc_key_bits(key_bits ? key_bits[b] : 1 << log2_n, log2_n);
         const uint32_t bits = pmc_quad_bits(keys + b * W, q);
         T l[4];
@@ -98,8 +93,13 @@ __global__ __launch_bounds__(PRC_LANES) void pld_slot_prior(const int *__restric
         }
         const unsigned w = q >> 3;
         uint32_t va;
-        pld_ladder_bits(rank, log2_n, w, (int)(4u * (q & 7u)), 4, extra[b], xbits + b * We, &fl, &va);
+        pld_ladder_bits(rank, log2_n, w, (int)(4u * (q & 7u)), 4, extra ? extra[b] : 0, xbits + b * We, &fl, &va);
         fz = prc_frozen_bits(syn + b * Wf, fmask[w], (uint32_t)fprefix[w], (int)(4u * (q & 7u)), 4) | va;
+        if (flip >= 0 && (unsigned)flip >> 2 == q) {             /* a candidate: neither the code nor the ladder has set its bits */
+            const uint32_t m = 1u << (31 - (flip & 31));
+            fl |= m;
+            fz = (fz & ~m) | (flip_bit ? m : 0u);
+        }
         if (q == 0u && decodes) decodes[b]++;                    /* the slot's only lane with q = 0, the block's only slot */
     }
     for (unsigned k = 1; k < group; k <<= 1) {                   /* group is the launch's: every lane shuffles */
@@ -110,6 +110,23 @@ __global__ __launch_bounds__(PRC_LANES) void pld_slot_prior(const int *__restric
         frozen[s * W + (q >> 3)] = fz;
         flags[s * W + (q >> 3)] = fl;
     }
+}
+
+/* slot s = block open[s] (open NULL: block s): keys, key_bits, syn, xbits [.][We], extra (NULL: 0) of the block -> llr [n_open][N], frozen
+   [n_open][W], flags [n_open][W]; total = n_open quads lanes.  rank: the ladder's table [N] */
+template <class T>
+__global__ __launch_bounds__(PRC_LANES) void pld_slot_prior(const int *__restrict__ open, const uint32_t *__restrict__ keys, const int *__restrict__ key_bits,
+                                                            const uint32_t *__restrict__ syn, const uint32_t *__restrict__ xbits, const int *__restrict__ extra,
+                                                            const uint32_t *__restrict__ fmask, const int *__restrict__ fprefix, const int *__restrict__ rank,
+                                                            void *__restrict__ llr, uint32_t *__restrict__ frozen, uint32_t *__restrict__ flags, int *__restrict__ decodes,
+                                                            size_t total, int log2_n, unsigned W, unsigned Wf, unsigned We, T prior, T pin)
+{
+    const size_t i = (size_t)blockIdx.x * PRC_LANES + threadIdx.x;
+    const unsigned lq = log2_n >= 2 ? (unsigned)log2_n - 2u : 0u;
+    const bool active = i < total;
+    const size_t s = active ? i >> lq : 0u;
+    pld_slot_prior_lane<T>(active, s, (unsigned)(i & ((1u << lq) - 1u)), active ? (open ? (size_t)open[s] : s) : 0u, -1, 0u, keys, key_bits, syn, xbits, extra, fmask,
+                           fprefix, rank, llr, frozen, flags, decodes, log2_n, W, Wf, We, prior, pin);
 }
 
 /* slot s = block open[s]: info [n_open][Wi], x [n_open][W] -> status, corrected (or NULL), keys, extra of the block, and the next round's list.

@@ -27,6 +27,24 @@ int pld_args_rounds(const char *who, int step, int max_rounds, int resume)
     return QLDPC_OK;
 }
 
+void pld_host_slot(int log2_n, int i8, const uint32_t *mask, const int *prefix, const int *rank, int pi, int qi, float pf, float qf, const uint32_t *key,
+                   int key_bits, const uint32_t *syn, const uint32_t *xbits, int extra, void *llr, uint32_t *frozen, uint32_t *flags)
+{
+    const long N = 1l << log2_n, W = pl_words(log2_n);
+    const int kb = prc_key_bits(key_bits, log2_n);
+    for (long i = 0; i < N; i++) {
+        const unsigned bit = pl_bit(key[i >> 5], (int)(i & 31));
+        if (i8) ((int8_t *)llr)[i] = (int8_t)PRC_LEVEL(i, bit, kb, pi, qi);
+        else ((float *)llr)[i] = PRC_LEVEL(i, bit, kb, pf, qf);
+    }
+    for (long w = 0; w < W; w++) {
+        uint32_t fl, va;
+        pld_ladder_bits(rank, log2_n, (size_t)w, 0, 32, extra, xbits, &fl, &va);
+        frozen[w] = prc_frozen_bits(syn, mask[w], (uint32_t)prefix[w], 0, 32) | va;
+        flags[w] = fl;
+    }
+}
+
 static int pld_null(const char *who, const char *what)
 {
     qldpc_set_error("%s: %s is NULL", who, what);
@@ -113,18 +131,9 @@ int qldpc_polar_recon_decode_rounds_host(int log2_n, int n_info, const int *info
             const int ns = (int)(n_open - s0 < (long)C ? n_open - s0 : (long)C);
             for (int s = 0; s < ns; s++) {                        /* the slot prior: the block's LLR row, frozen values and added flags */
                 const long b = cur[s0 + s];
-                const int kb = prc_key_bits(key_bits ? key_bits[b] : (int)N, log2_n);
-                for (long i = 0; i < N; i++) {
-                    const unsigned bit = pl_bit(keys[b * W + (i >> 5)], (int)(i & 31));
-                    if (messages == QLDPC_POLAR_I8) ((int8_t *)llr)[s * N + i] = (int8_t)PRC_LEVEL(i, bit, kb, pi, qi);
-                    else ((float *)llr)[s * N + i] = PRC_LEVEL(i, bit, kb, pf, qf);
-                }
-                for (long w = 0; w < W; w++) {
-                    uint32_t fl, va;
-                    pld_ladder_bits(rank, log2_n, (size_t)w, 0, 32, extra[b], extra_bits ? extra_bits + b * We : NULL, &fl, &va);
-                    frozen[s * W + w] = prc_frozen_bits(syndrome ? syndrome + b * Wf : NULL, mask[w], (uint32_t)prefix[w], 0, 32) | va;
-                    flags[s * W + w] = fl;
-                }
+                pld_host_slot(log2_n, messages == QLDPC_POLAR_I8, mask, prefix, rank, pi, qi, pf, qf, keys + b * W, key_bits ? key_bits[b] : (int)N,
+                              syndrome ? syndrome + b * Wf : NULL, extra_bits ? extra_bits + b * We : NULL, extra[b], (char *)llr + esz * (size_t)(s * N), frozen + s * W,
+                              flags + s * W);
                 if (decodes) decodes[b]++;
             }
             rc = qldpc_polar_decode_rows_host(log2_n, n_info, info_pos, messages, maxq, ns, llr, frozen, flags, NULL, ih, xh, NULL);

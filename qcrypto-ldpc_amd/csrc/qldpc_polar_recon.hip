@@ -18,7 +18,17 @@
  *     entry -> per round: read the open count back | slot prior -> the rows form of the SC decode -> slot verdict and the next round's list
  *
  * with the kernels of qldpc_kernels_polar_ladder.h.  The grid of a round needs the open count on the host: one 4-byte read-back per round, queued
- * on the context's stream and waited for on that stream alone.  It is the one call of a session that waits.
+ * on the context's stream and waited for on that stream alone.
+ *
+ * A session made by qldpc_polar_recon_create_flip is a ladder session (n_extra = 0 is the common case) that also owns the scratch of SC-Flip trials
+ * (qldpc_polar_flip_core.h): the leaf rows of a chunk's probe and the flip positions of its trials.  qldpc_polar_recon_decode_flip runs
+ *
+ *     first pass (or the entry of a resumed call) -> read the open count back | per chunk of C = max_blocks / T open blocks:
+ *     slot prior -> probe (rows decode with the leaf output) -> select -> trial prior on C T slots -> rows decode -> settle
+ *
+ * with the kernels of qldpc_kernels_polar_flip.h.  The trials live in the rows a call's blocks live in (LLR, frozen, flags, info, x), which is why
+ * a chunk holds max_blocks / T blocks.  One 4-byte read-back, the call's only wait; after it everything is queued.  These two are the calls of a
+ * session that wait.
  */
 #include <hip/hip_runtime.h>
 
@@ -26,6 +36,7 @@
 #include <new>
 #include <vector>
 
+#include "qldpc_kernels_polar_flip.h"
 #include "qldpc_kernels_polar_ladder.h"
 #include "qldpc_kernels_polar_recon.h"
 #include "qldpc_polar_ctx.h"
@@ -51,6 +62,9 @@ struct qldpc_polar_recon {
     uint32_t *d_flags;             /* the added frozen flags of a round's slots, max_blocks x W */
     int *d_open, *d_count;         /* two open lists of max_blocks blocks and their two counters: round t fills those of round t + 1 */
     int h_open;                    /* where a round's count is read back to */
+    int max_flips;                 /* made by _create_flip (0 otherwise): what follows is set */
+    void *d_leaf;                  /* the leaf rows of a chunk's probe, max_blocks x N: a chunk of n_flips = 1 holds max_blocks blocks */
+    int *d_pos;                    /* the flips of a chunk's trials, (max_blocks / T) x T <= max_blocks entries */
     dm_ledger mem;                 /* everything create allocates (qldpc_devmem.h) */
 };
 
@@ -356,6 +370,122 @@ extern "C" int qldpc_polar_recon_decode_rounds(qldpc_polar_recon *r, int n_block
         hipLaunchKernelGGL(pld_slot_verdict, dim3(prc_grid((size_t)n_open, PRC_LANES)), dim3(PRC_LANES), 0, s, open, (const uint32_t *)r->d_info, (const uint32_t *)r->d_x,
                            d_keys, d_key_bits, d_crc, d_extra, d_status, d_corrected, r->d_open + (size_t)nxt * B, r->d_count + nxt, (unsigned)n_open, c->n, c->n_info,
                            r->crc_len, r->crc_poly, r->n_extra, step, t, max_rounds);
+        LAUNCHCHK();
+    }
+    return QLDPC_OK;
+}
+
+/* ---- SC-Flip trials: a ladder session with the scratch of the trials (qldpc_polar_flip_core.h) ---- */
+
+extern "C" int qldpc_polar_recon_create_flip(qldpc_polar *sc, int crc_len, uint32_t crc_poly, double prior, double pin, int max_blocks, int n_extra,
+                                             const int *extra_pos, int max_flips, qldpc_polar_recon **out)
+{
+    const char *who = "polar_recon_create_flip";
+    if (!out) return QLDPC_EINVAL;
+    *out = nullptr;
+    if (!sc) { qldpc_set_error("%s: an SC context is required (the list decoder has no rows form)", who); return QLDPC_EINVAL; }
+    if (max_flips > PFL_MAX_FLIPS || !pfl_flips_pow2(max_flips)) {
+        qldpc_set_error("%s: max_flips=%d (a power of two in 1 .. %d)", who, max_flips, PFL_MAX_FLIPS);
+        return QLDPC_EINVAL;
+    }
+    qldpc_polar_recon *r = nullptr;
+    int rc = qldpc_polar_recon_create_ladder(sc, crc_len, crc_poly, prior, pin, max_blocks, n_extra, extra_pos, &r);
+    if (rc) return rc;
+    const pl_ctx *c = r->c;
+    const size_t B = (size_t)r->max_blocks, N = (size_t)1 << c->n, esz = c->messages == QLDPC_POLAR_I8 ? 1 : sizeof(float);
+    if (max_flips > r->max_blocks) {
+        qldpc_set_error("%s: max_flips=%d exceeds max_blocks=%d: the trials of a block live in the rows of the call's blocks", who, max_flips, r->max_blocks);
+        rc = QLDPC_ESIZE;
+    }
+    if (!rc && !((rc = prc_alloc(r, (uint8_t **)&r->d_leaf, esz * B * N)) || (rc = prc_alloc(r, &r->d_pos, B)))) r->max_flips = max_flips;
+    if (rc) { qldpc_polar_recon_free(r); return rc; }
+    *out = r;
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_polar_recon_max_flips(const qldpc_polar_recon *r) { return r ? r->max_flips : QLDPC_EINVAL; }
+
+/* the launch of the select kernel: the caller has checked everything and set the device */
+static int pfl_launch_select(hipStream_t s, int log2_n, bool i8, int n_slots, const void *d_leaf, const uint32_t *d_fmask, const int *d_rank, const int *d_extra,
+                             const int *d_open, int n_flips, int *d_pos)
+{
+    const dim3 grid(prc_grid((size_t)n_slots, PRC_LANES / 64u)), lanes(PRC_LANES);
+    if (i8) hipLaunchKernelGGL(pfl_select<int8_t>, grid, lanes, 0, s, (const int8_t *)d_leaf, d_fmask, d_rank, d_extra, d_open, d_pos, (unsigned)n_slots, log2_n, n_flips);
+    else hipLaunchKernelGGL(pfl_select<float>, grid, lanes, 0, s, (const float *)d_leaf, d_fmask, d_rank, d_extra, d_open, d_pos, (unsigned)n_slots, log2_n, n_flips);
+    LAUNCHCHK();
+    return QLDPC_OK;
+}
+
+extern "C" int qldpc_polar_flip_select_dev(void *hip_stream, int log2_n, int messages, int n_frames, const void *d_leaf, const uint32_t *d_frozen_mask, const int *d_rank,
+                                           const int *d_extra, int n_flips, int *d_pos)
+{
+    const char *who = "polar_flip_select_dev";
+    int rc = pl_args_scalars(who, log2_n, PL_MAX_LOG2N, messages, 1);
+    if (!rc) rc = prc_args_count(who, n_frames);
+    if (!rc) rc = pfl_args_flips(who, n_flips, PFL_MAX_FLIPS, 0);
+    if (rc || n_frames == 0) return rc;
+    if (!d_leaf || !d_frozen_mask || !d_pos) { qldpc_set_error("%s: NULL device pointer (d_leaf, d_frozen_mask and d_pos are required)", who); return QLDPC_EINVAL; }
+    return pfl_launch_select((hipStream_t)hip_stream, log2_n, messages == QLDPC_POLAR_I8, n_frames, d_leaf, d_frozen_mask, d_rank, d_extra, nullptr, n_flips, d_pos);
+}
+
+extern "C" int qldpc_polar_recon_decode_flip(qldpc_polar_recon *r, int n_blocks, uint32_t *d_keys, const int *d_key_bits, const uint32_t *d_syndrome,
+                                             const uint32_t *d_crc, const uint32_t *d_extra_bits, const int *d_extra, int n_flips, int resume, int *d_status,
+                                             int *d_corrected, int32_t *d_flip_pos, int *d_decodes, int *n_tried)
+{
+    const char *who = "polar_recon_decode_flip";
+    int rc = prc_check_blocks(r, n_blocks, who);
+    if (!rc && !r->max_flips) { qldpc_set_error("%s: the session has no flip scratch: make it with qldpc_polar_recon_create_flip", who); rc = QLDPC_ESTATE; }
+    if (!rc) rc = pfl_args_flips(who, n_flips, r->max_flips, resume);
+    if (rc) return rc;
+    if (n_blocks > 0 && (!d_keys || !d_crc || !d_status || !d_flip_pos || (r->n_frozen && !d_syndrome) || (r->n_extra && !d_extra_bits))) {
+        qldpc_set_error("%s: NULL device pointer (d_keys, d_crc, d_status and d_flip_pos are required; d_syndrome where N > K, d_extra_bits where n_extra > 0)", who);
+        return QLDPC_EINVAL;
+    }
+    if (n_tried) *n_tried = 0;
+    if (n_blocks == 0) return QLDPC_OK;
+    const pl_ctx *c = r->c;
+    const hipStream_t s = c->stream;
+    const bool i8 = c->messages == QLDPC_POLAR_I8;
+    const int T = n_flips, Tlog = pl_ctz((long)T), C = r->max_blocks / T;
+    const dim3 lanes(PRC_LANES);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemsetAsync(r->d_count, 0, sizeof(int), s));
+    HIPCHK(hipMemsetAsync(d_flip_pos, 0xff, sizeof(int32_t) * (size_t)n_blocks, s));      /* -1 */
+    if (resume) {
+        hipLaunchKernelGGL(pld_entry_blocks, dim3(prc_grid((size_t)n_blocks, PRC_LANES)), lanes, 0, s, d_key_bits, d_extra, d_status, d_corrected, d_decodes, r->d_open,
+                           r->d_count, (unsigned)n_blocks, c->n, r->n_extra, 1);
+        LAUNCHCHK();
+    } else {                                                      /* the first pass: decode_rounds' round on slot b = block b, no count needed */
+        if ((rc = pld_launch_slot_prior(r, nullptr, n_blocks, d_keys, d_key_bits, d_syndrome, d_extra_bits, d_extra, nullptr))) return rc;
+        if ((rc = qldpc_polar_decode_rows_dev(r->sc, n_blocks, r->d_llr, r->d_frozen, r->d_flags, nullptr, r->d_info, r->d_x, nullptr))) return rc;
+        hipLaunchKernelGGL(pfl_first_verdict, dim3(prc_grid((size_t)n_blocks, PRC_LANES)), lanes, 0, s, (const uint32_t *)r->d_info, (const uint32_t *)r->d_x, d_keys, d_key_bits,
+                           d_crc, d_extra, d_status, d_corrected, d_decodes, r->d_open, r->d_count, (unsigned)n_blocks, c->n, c->n_info, r->crc_len, r->crc_poly, r->n_extra);
+        LAUNCHCHK();
+    }
+    HIPCHK(hipMemcpyAsync(&r->h_open, r->d_count, sizeof(int), hipMemcpyDeviceToHost, s));      /* the ONE read-back of the call */
+    HIPCHK(hipStreamSynchronize(s));
+    const int n_open = r->h_open;
+    if (n_open < 0 || n_open > n_blocks) { qldpc_set_error("%s: the open count %d is not in 0 .. n_blocks = %d", who, n_open, n_blocks); return QLDPC_ESTATE; }
+    if (n_tried) *n_tried = n_open;
+    for (int o0 = 0; o0 < n_open; o0 += C) {
+        const int nc = n_open - o0 < C ? n_open - o0 : C;
+        const int *open = r->d_open + o0;
+        const size_t n_trials = (size_t)nc * (size_t)T, total = n_trials * pmc_quads(c->n);
+        if ((rc = pld_launch_slot_prior(r, open, nc, d_keys, d_key_bits, d_syndrome, d_extra_bits, d_extra, nullptr))) return rc;
+        if ((rc = qldpc_polar_decode_rows_dev(r->sc, nc, r->d_llr, r->d_frozen, r->d_flags, nullptr, nullptr, nullptr, r->d_leaf))) return rc;      /* the probe */
+        if ((rc = pfl_launch_select(s, c->n, i8, nc, r->d_leaf, c->d_fmask, r->d_rank, d_extra, open, T, r->d_pos))) return rc;
+        if (i8)
+            hipLaunchKernelGGL((pfl_trial_prior<int, int8_t>), dim3(prc_grid(total, PRC_LANES)), lanes, 0, s, open, (const int *)r->d_pos, (const int8_t *)r->d_leaf, d_keys,
+                               d_key_bits, d_syndrome, d_extra_bits, d_extra, (const uint32_t *)c->d_fmask, (const int *)r->d_fprefix, (const int *)r->d_rank, r->d_llr,
+                               r->d_frozen, r->d_flags, total, c->n, (unsigned)c->W, (unsigned)r->Wf, (unsigned)r->We, Tlog, r->prior_i, r->pin_i);
+        else
+            hipLaunchKernelGGL((pfl_trial_prior<float, float>), dim3(prc_grid(total, PRC_LANES)), lanes, 0, s, open, (const int *)r->d_pos, (const float *)r->d_leaf, d_keys,
+                               d_key_bits, d_syndrome, d_extra_bits, d_extra, (const uint32_t *)c->d_fmask, (const int *)r->d_fprefix, (const int *)r->d_rank, r->d_llr,
+                               r->d_frozen, r->d_flags, total, c->n, (unsigned)c->W, (unsigned)r->Wf, (unsigned)r->We, Tlog, r->prior_f, r->pin_f);
+        LAUNCHCHK();
+        if ((rc = qldpc_polar_decode_rows_dev(r->sc, (int)n_trials, r->d_llr, r->d_frozen, r->d_flags, nullptr, r->d_info, r->d_x, nullptr))) return rc;
+        hipLaunchKernelGGL(pfl_settle, dim3(prc_grid(n_trials, PRC_LANES)), lanes, 0, s, open, (const int *)r->d_pos, (const uint32_t *)r->d_info, (const uint32_t *)r->d_x, d_keys,
+                           d_key_bits, d_crc, d_status, d_corrected, d_flip_pos, d_decodes, n_trials, c->n, c->n_info, r->crc_len, r->crc_poly, Tlog);
         LAUNCHCHK();
     }
     return QLDPC_OK;

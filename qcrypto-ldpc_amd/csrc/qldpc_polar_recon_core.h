@@ -86,22 +86,25 @@ PRC_FN uint32_t prc_frozen_bits(const uint32_t *syn, uint32_t fmask_w, uint32_t 
     return out;
 }
 
-/* The verdict of one block.  info = the decoded info row, x = x^, key = Bob's row (rewritten where the block is OK), have_pick: the list
- * decoder's pick decides in the CRC's place.  Every word of x is read once, from the top: the words that hold pad bits first, then, where the pad
- * is clean, the key words together with Bob's, which are rewritten in the same pass; the pad words of the key become 0 as x^'s are */
-PRC_FN void prc_verdict_block(int log2_n, int n_info, int crc_len, uint32_t crc_poly, const uint32_t *info, const uint32_t *x, int have_pick, int32_t pick,
-                              uint32_t *key, int key_bits, uint32_t crc, int *status, int *corrected)
+/* The pure part of the verdict, for a block whose key_bits is in 1 .. N: 1 iff the remainder of the decoded info row equals Alice's crc (or, with
+ * have_pick, the list decoder's pick is >= 0) and every bit of x^ at positions >= key_bits is 0.  Nothing is written: several decodes of one
+ * block may be tested side by side (the flip trials of qldpc_polar_flip_core.h) before one of them takes the key.  The words of x that hold pad
+ * bits are read from the top */
+PRC_FN int prc_accept_block(int log2_n, int n_info, int crc_len, uint32_t crc_poly, const uint32_t *info, const uint32_t *x, int have_pick, int32_t pick,
+                            int key_bits, uint32_t crc)
 {
-    *corrected = -1;
-    if (!prc_key_bits_ok(key_bits, log2_n)) { *status = PRC_ESIZE; return; }
-    *status = PRC_EDECODE;
-    if (have_pick ? pick < 0 : prc_row_crc(info, n_info, crc_len, crc_poly) != crc) return;
+    if (have_pick ? pick < 0 : prc_row_crc(info, n_info, crc_len, crc_poly) != crc) return 0;
     const long W = pl_words(log2_n), wb = key_bits >> 5;      /* the first word with a pad bit, W where there is none */
-    uint32_t xb = 0u;
-    for (long w = W - 1; w >= wb; w--) {
-        xb = x[w];
-        if (xb & ~prc_key_mask(key_bits, (uint32_t)w)) return;
-    }
+    for (long w = W - 1; w >= wb; w--)
+        if (x[w] & ~prc_key_mask(key_bits, (uint32_t)w)) return 0;
+    return 1;
+}
+
+/* The write of the verdict, for a block that prc_accept_block accepted: Bob's row becomes x^, its pad words 0 as x^'s are.  Returns the flips:
+ * popcount((x^ ^ y) over the first key_bits bits) */
+PRC_FN int prc_take_block(int log2_n, const uint32_t *x, uint32_t *key, int key_bits)
+{
+    const long W = pl_words(log2_n), wb = key_bits >> 5;
     int flips = 0;
     for (long w = 0; w < wb; w++) {
         const uint32_t xw = x[w];
@@ -109,12 +112,25 @@ PRC_FN void prc_verdict_block(int log2_n, int n_info, int crc_len, uint32_t crc_
         key[w] = xw;
     }
     if (wb < W) {
+        const uint32_t xb = x[wb];
         flips += __builtin_popcount((xb ^ key[wb]) & prc_key_mask(key_bits, (uint32_t)wb));
         key[wb] = xb;
         for (long w = wb + 1; w < W; w++) key[w] = 0u;
     }
+    return flips;
+}
+
+/* The verdict of one block.  info = the decoded info row, x = x^, key = Bob's row (rewritten where the block is OK), have_pick: the list
+ * decoder's pick decides in the CRC's place: the test of prc_accept_block, then the write of prc_take_block */
+PRC_FN void prc_verdict_block(int log2_n, int n_info, int crc_len, uint32_t crc_poly, const uint32_t *info, const uint32_t *x, int have_pick, int32_t pick,
+                              uint32_t *key, int key_bits, uint32_t crc, int *status, int *corrected)
+{
+    *corrected = -1;
+    if (!prc_key_bits_ok(key_bits, log2_n)) { *status = PRC_ESIZE; return; }
+    *status = PRC_EDECODE;
+    if (!prc_accept_block(log2_n, n_info, crc_len, crc_poly, info, x, have_pick, pick, key_bits, crc)) return;
     *status = PRC_OK;
-    *corrected = flips;
+    *corrected = prc_take_block(log2_n, x, key, key_bits);
 }
 
 /* ---- host side ---- */

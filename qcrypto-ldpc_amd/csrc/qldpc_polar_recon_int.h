@@ -27,6 +27,15 @@ int prc_args_verdict(const char *who, int log2_n, int n_info, int crc_len, uint3
 int pld_args_ladder(const char *who, int log2_n, const uint32_t *fmask, int n_info, int n_extra, const int *extra_pos, int *rank);
 /* the scalars of a rounds call: step >= 1, max_rounds >= 1, resume 0 or 1 (QLDPC_EINVAL) */
 int pld_args_rounds(const char *who, int step, int max_rounds, int resume);
+/* the slot prior of the host mirrors (defined in qldpc_polar_ladder_host.c): one block's LLR row [N] (int8 or float), frozen values [W] and added
+   flags [W] at its count `extra`, from its key row, key_bits as the caller gave it, syndrome row and extra row (either may be NULL where nothing
+   of it is looked at); mask, prefix: the code's tables; rank: the ladder's */
+void pld_host_slot(int log2_n, int i8, const uint32_t *mask, const int *prefix, const int *rank, int pi, int qi, float pf, float qf, const uint32_t *key,
+                   int key_bits, const uint32_t *syn, const uint32_t *xbits, int extra, void *llr, uint32_t *frozen, uint32_t *flags);
+
+/* the scalars of a flip call (qldpc_polar_flip_core.h; defined in qldpc_polar_flip_host.c): n_flips a power of two >= 1 and resume 0 or 1
+   (QLDPC_EINVAL), n_flips at most max_flips (QLDPC_ESIZE) */
+int pfl_args_flips(const char *who, int n_flips, int max_flips, int resume);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 """Polar reconciliation sessions (qldpc_polar_recon_*): Alice's syndrome and CRC, Bob's prior, decode and verdict on the device around an existing
-Polar or PolarList, the host mirrors of both calls, and the two building blocks (prior, verdict) on the device and on the host."""
+Polar or PolarList, the host mirrors of both calls, and the two building blocks (prior, verdict) on the device and on the host; incremental
+freezing rounds on a ladder; SC-Flip trials for the blocks that failed (decode_flip, polar_flip_select) and their mirrors."""
 import ctypes as C
 
 import numpy as np
@@ -32,6 +33,13 @@ _sig("qldpc_polar_recon_encode_ladder_host", C.c_int, [C.c_int, C.c_int, _ip, C.
 _sig("qldpc_polar_recon_decode_rounds_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_double, C.c_double, C.c_int, _ip, C.c_int,
                                                       _up, _ip, _up, _up, _up, _ip, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip])
 _sig("qldpc_polar_recon_ladder_extra_host", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double])
+_sig("qldpc_polar_recon_create_flip", C.c_int, [_vp, C.c_int, C.c_uint32, C.c_double, C.c_double, C.c_int, C.c_int, _ip, C.c_int, C.POINTER(_vp)])
+_sig("qldpc_polar_recon_max_flips", C.c_int, [_vp])
+_sig("qldpc_polar_recon_decode_flip", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _ip])
+_sig("qldpc_polar_flip_select_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp])
+_sig("qldpc_polar_flip_select_host", C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _up, _ip, _ip, C.c_int, _ip])
+_sig("qldpc_polar_recon_decode_flip_host", C.c_int, [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_double, C.c_double, C.c_int, _ip, C.c_int,
+                                                    _up, _ip, _up, _up, _up, _ip, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _ip])
 
 
 def _levels(kind, maxq, prior, pin):
@@ -191,6 +199,57 @@ def polar_recon_ladder_extra(log2_n, n_info, n_extra, key_bits, qber, f=1.0):
     return _chk(_L.qldpc_polar_recon_ladder_extra_host(int(log2_n), int(n_info), int(n_extra), int(key_bits), float(qber), float(f)), "polar_recon_ladder_extra")
 
 
+# ---- SC-Flip trials: the mirrors ------------------------------------------------------------------------------------------------------------
+
+def _select_args(who, log2_n, leaf, frozen_mask, rank, extra, messages):
+    kind, dt = _messages(messages)
+    n = int(log2_n)
+    N, W = (1 << n) if 0 <= n <= POLAR_MAX_LOG2N else 1, _words(n)
+    leaf = np.ascontiguousarray(leaf, dtype=dt)
+    if leaf.ndim != 2 or leaf.shape[1] != N:
+        raise QldpcError(-6, "%s: leaf must be [frames, %d]" % (who, N))
+    F = leaf.shape[0]
+    return kind, n, F, leaf, _vec(who, frozen_mask, W, "frozen_mask", np.uint32), _vec(who, rank, N, "rank", np.int32), _vec(who, extra, F, "extra", np.int32)
+
+
+def polar_flip_select_host(log2_n, leaf, frozen_mask, n_flips, rank=None, extra=None, messages="i8"):
+    """the flips of each frame (qldpc_polar_flip_select_host): leaf [F, N] int8 or float32 the SC decoder's leaf beliefs, frozen_mask uint32 [W]
+    (1 = frozen), rank int32 [N] a ladder's rank table or None, extra int32 [F] the frames' ladder counts or None -> pos int32 [F, n_flips]: the
+    n_flips candidates of the smallest (|leaf|, position), ascending, -1 where there are fewer"""
+    who = "polar_flip_select_host"
+    kind, n, F, leaf, mask, rk, ex = _select_args(who, log2_n, leaf, frozen_mask, rank, extra, messages)
+    pos = np.zeros((F, max(int(n_flips), 0)), np.int32)
+    _chk(_L.qldpc_polar_flip_select_host(n, kind, F, leaf.ctypes.data_as(_vp), _ptr(mask, _up), _ptr(rk, _ip), _ptr(ex, _ip), int(n_flips), pos.ctypes.data_as(_ip)), who)
+    return pos
+
+
+def polar_recon_decode_flip_host(log2_n, info_pos, keys, syndrome, crc, n_flips=8, extra_pos=(), extra_bits=None, extra=None, key_bits=None, resume=False, status=None,
+                                 messages="i8", maxq=31, crc_len=0, crc_poly=0, prior=None, pin=None):
+    """Bob's flip mirror (qldpc_polar_recon_decode_flip_host): the first pass (or, with resume, the EDECODE blocks of `status`), then for each open
+    block a probe and n_flips trials -> dict(keys (a copy, corrected where OK), status, corrected, flip_pos (-1 where no flip rescued the block),
+    decodes, n_tried)"""
+    who = "polar_recon_decode_flip_host"
+    kind, _ = _messages(messages)
+    n, N, W, pos = _code(log2_n, info_pos)
+    xp = np.ascontiguousarray(extra_pos, dtype=np.int32).ravel()
+    keys = _rows(who, keys, W, "keys").copy()
+    B = keys.shape[0]
+    syn, xb = _rows(who, syndrome, (max(N - pos.size, 0) + 31) // 32, "syndrome"), _rows(who, extra_bits, (xp.size + 31) // 32, "extra_bits")
+    cr, kb, ex = _vec(who, crc, B, "crc", np.uint32), _vec(who, key_bits, B, "key_bits", np.int32), _vec(who, extra, B, "extra", np.int32)
+    if resume and status is None:
+        raise QldpcError(-1, "%s: resume needs the status of the call before" % who)
+    st = np.zeros(B, np.int32) if status is None else _vec(who, status, B, "status", np.int32).copy()
+    p, q = _levels(kind, maxq, prior, pin)
+    out = dict(keys=keys, status=st, corrected=np.full(B, -1, np.int32), flip_pos=np.full(B, -1, np.int32), decodes=np.zeros(B, np.int32))
+    tried = C.c_int(0)
+    _chk(_L.qldpc_polar_recon_decode_flip_host(n, pos.size, pos.ctypes.data_as(_ip), kind, int(maxq), int(crc_len), int(crc_poly) & 0xffffffff, p, q, xp.size,
+                                               xp.ctypes.data_as(_ip), B, keys.ctypes.data_as(_up), _ptr(kb, _ip), _ptr(syn, _up), _ptr(cr, _up), _ptr(xb, _up), _ptr(ex, _ip),
+                                               int(n_flips), int(resume), st.ctypes.data_as(_ip), out["corrected"].ctypes.data_as(_ip), out["flip_pos"].ctypes.data_as(_ip),
+                                               out["decodes"].ctypes.data_as(_ip), C.byref(tried)), who)
+    out["n_tried"] = tried.value
+    return out
+
+
 def _up_dev(a, device=0):
     """a host array on the device (uint32 words as int32); None stays None"""
     if a is None:
@@ -242,19 +301,40 @@ def polar_recon_verdict(log2_n, n_info, info, x, keys, crc=None, pick=None, key_
         return dict(keys=d_keys.cpu().numpy().view(np.uint32), status=status.cpu().numpy(), corrected=corrected.cpu().numpy())
 
 
+def polar_flip_select(log2_n, leaf, frozen_mask, n_flips, rank=None, extra=None, messages="i8", device=0):
+    """the select kernel on its own (qldpc_polar_flip_select_dev) on torch's current stream: host arrays in, host array out, as
+    polar_flip_select_host -> pos int32 [F, n_flips]"""
+    who = "polar_flip_select"
+    torch = _torch()
+    kind, n, F, leaf, mask, rk, ex = _select_args(who, log2_n, leaf, frozen_mask, rank, extra, messages)
+    with torch.cuda.device(device):
+        d_leaf, d_mask, d_rk, d_ex = (_up_dev(a, device) for a in (leaf, mask, rk, ex))
+        pos = _dev_empty(device, (F, max(int(n_flips), 0)), torch.int32)
+        _chk(_L.qldpc_polar_flip_select_dev(_stream_arg(None, device), n, kind, F, _p(d_leaf), _p(d_mask), _p(d_rk), _p(d_ex), int(n_flips), _p(pos)), who)
+        return pos.cpu().numpy()
+
+
 class PolarRecon(_Handle):
     """A reconciliation session around `decoder`, a Polar (any form, any rule) or a PolarList with a CRC, which it does not own.  With a Polar the
     CRC is (crc_len, crc_poly); with a PolarList it is the decoder's and both stay 0.  prior and pin: Bob's levels of an unknown and of a padded
     position (None: 1, and maxq with int8 messages, 2^24 with floats).  max_blocks = 0: the decoder's max_frames.  Device tensors in, device
-    tensors out, asynchronous on torch's current stream."""
+    tensors out, asynchronous on torch's current stream.  extra_pos: a ladder session (decode_rounds).  max_flips > 0: a flip session
+    (decode_flip), a ladder session (extra_pos None: an empty ladder) that also owns the scratch of SC-Flip trials."""
     _free = _L.qldpc_polar_recon_free
 
-    def __init__(self, decoder, crc_len=0, crc_poly=0, prior=None, pin=None, max_blocks=0, extra_pos=None):
+    def __init__(self, decoder, crc_len=0, crc_poly=0, prior=None, pin=None, max_blocks=0, extra_pos=None, max_flips=0):
         is_list = isinstance(decoder, PolarList)
         self.decoder = decoder
         self.prior, self.pin = _levels(decoder.messages, decoder.maxq, prior, pin)
+        if max_flips and extra_pos is None:
+            extra_pos = ()
         self.extra_pos = None if extra_pos is None else np.ascontiguousarray(extra_pos, dtype=np.int32).ravel()
-        if self.extra_pos is not None:      # a ladder session (incremental freezing): an SC Polar of the lanes form only
+        if max_flips:                       # a flip session: a ladder session with the scratch of the trials
+            if is_list:
+                raise QldpcError(-7, "PolarRecon: a flip session needs an SC Polar (the list decoder has no rows form)")
+            self._h = _create("PolarRecon", _L.qldpc_polar_recon_create_flip, decoder._h, int(crc_len), int(crc_poly) & 0xffffffff, self.prior, self.pin,
+                              int(max_blocks), self.extra_pos.size, self.extra_pos.ctypes.data_as(_ip), int(max_flips))
+        elif self.extra_pos is not None:      # a ladder session (incremental freezing): an SC Polar of the lanes form only
             if is_list:
                 raise QldpcError(-7, "PolarRecon: a ladder session needs an SC Polar (the list decoder has no rows form)")
             self._h = _create("PolarRecon", _L.qldpc_polar_recon_create_ladder, decoder._h, int(crc_len), int(crc_poly) & 0xffffffff, self.prior, self.pin,
@@ -263,6 +343,7 @@ class PolarRecon(_Handle):
             self._h = _create("PolarRecon", _L.qldpc_polar_recon_create, None if is_list else decoder._h, decoder._h if is_list else None, int(crc_len),
                               int(crc_poly) & 0xffffffff, self.prior, self.pin, int(max_blocks))
         self.extra_words = int(_L.qldpc_polar_recon_extra_words(self._h))
+        self.max_flips = int(_L.qldpc_polar_recon_max_flips(self._h))
         self.max_blocks = int(max_blocks) or decoder.max_frames
         self.crc_len, self.crc_poly = (decoder.crc_len, decoder.crc_poly) if is_list else (int(crc_len), int(crc_poly))
         self.syndrome_words = int(_L.qldpc_polar_recon_syndrome_words(self._h))
@@ -330,4 +411,30 @@ class PolarRecon(_Handle):
         _chk(_L.qldpc_polar_recon_decode_rounds(self._h, B, pk, pb, ps, _vp(crc.data_ptr()), px, pe, int(step), int(max_rounds), int(resume), _p(st),
                                                 _p(out["corrected"]), _p(out["decodes"]), rounds), "PolarRecon.decode_rounds")
         out["open_per_round"] = list(rounds)
+        return out
+
+    def decode_flip(self, keys, syndrome, crc, n_flips=8, extra_bits=None, extra=None, key_bits=None, resume=False, status=None):
+        """Bob, SC-Flip trials (a flip session; qldpc_polar_recon_decode_flip): every block once (or, with resume, nothing: `status` int32 [B] of the
+        call before is read and rewritten IN PLACE and only its EDECODE blocks are open), then each failed block again with the decision at one of
+        its n_flips least reliable information leaves inverted; the first trial that passes the verdict is kept.  Local to Bob: nothing is
+        disclosed.  keys [B, W] corrected IN PLACE where a block is OK; extra int32 [B] the blocks' ladder counts (only read; None: all 0) and
+        extra_bits [B, extra_words] as in decode_rounds.  THIS CALL WAITS for the stream once (the open count)
+        -> dict(keys, status, corrected, flip_pos int32 [B] (-1 where no flip rescued the block), decodes on the device, n_tried: an int)"""
+        torch, B, pk, pb = self._inputs(keys, key_bits)
+        words = (torch.int32, torch.uint32)
+        ps = _dev_rows(syndrome, B, self.syndrome_words, words, "syndrome") if self.syndrome_words else None
+        px = _dev_rows(extra_bits, B, self.extra_words, words, "extra_bits") if self.extra_words and extra_bits is not None else None
+        assert crc.is_cuda and crc.dtype in words and crc.is_contiguous() and tuple(crc.shape) == (B,), "crc"
+        pe = _dev_vec(extra, B, torch.int32, "extra")
+        if resume and status is None:
+            raise QldpcError(-1, "PolarRecon.decode_flip: resume needs the status of the call before")
+        st = _dev_empty(keys.device, (B,), torch.int32) if status is None else status
+        _dev_vec(st, B, torch.int32, "status")
+        out = dict(keys=keys, status=st, corrected=torch.full((B,), -1, dtype=torch.int32, device=keys.device) if resume else _dev_empty(keys.device, (B,), torch.int32),
+                   flip_pos=_dev_empty(keys.device, (B,), torch.int32), decodes=_dev_empty(keys.device, (B,), torch.int32))
+        tried = C.c_int(0)
+        self.decoder._on_current_stream()
+        _chk(_L.qldpc_polar_recon_decode_flip(self._h, B, pk, pb, ps, _vp(crc.data_ptr()), px, pe, int(n_flips), int(resume), _p(st), _p(out["corrected"]),
+                                              _p(out["flip_pos"]), _p(out["decodes"]), C.byref(tried)), "PolarRecon.decode_flip")
+        out["n_tried"] = tried.value
         return out
